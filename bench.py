@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- multiplicative-update iterations/sec of the ResNMTF inner loop on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 A "step" is one full sweep of update_matrices + calculate_error (R/main.r:84-108) over all
 views.  N = 1: BASELINE.json configs[1] (c2: one view 10000 x 2000, k = 16, synthetic planted
@@ -13,6 +13,12 @@ this process touches the GPU, and rank 0's JSON line is relayed.
 
 ``value`` = view-updates per second = steps x n_views / wall (inputs resident in HBM before the
 timed region).  Rank 0 prints ONE JSON line.
+
+``--dump-outputs DIR``: after the timed run, what it returned and the state it left -- ``all_error``
+(one entry per timed step) and the factors ``f_<v>``, ``s_<v>``, ``g_<v>``, ``lam_<v>``, ``mu_<v>`` of
+every view -- as ``DIR/<name>.npy`` (float64), fetched after the clock stopped; at most 64 MB in all
+(larger factors keep a fixed, seeded sample of their rows: dump_outputs).  The inputs are seeded:
+the same arguments give the same inputs, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -28,8 +34,26 @@ if ROOT not in sys.path:
 
 import numpy as np  # noqa: E402
 
-HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0          # MI355X: HBM3E 8.0 TB/s spec
 METRIC = "multiplicative-update iters/sec (all views)"
+DUMP_BYTES_MAX = 64 * 2**20    # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir: str, arrays: dict, budget: int = DUMP_BYTES_MAX) -> None:
+    """Writes every array as ``out_dir/<name>.npy`` in float64.  When they would exceed ``budget`` bytes, each 2-D array
+    above 1 MB keeps a fixed sample of its rows (seed 0, in row order), the same for the same shapes on every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {name: np.asarray(a, dtype=np.float64) for name, a in arrays.items()}
+    big = {name for name, a in arrays.items() if a.ndim == 2 and a.nbytes > 2**20}
+    header = 256 * len(arrays)                     # (.npy headers)
+    whole = sum(a.nbytes for name, a in arrays.items() if name not in big)
+    rows = sum(arrays[name].nbytes for name in big)
+    scale = min(1.0, max(0, budget - header - whole) / rows) if rows else 1.0
+    for name, a in arrays.items():
+        if name in big and scale < 1.0:
+            keep = int(a.shape[0] * scale)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(prob, warm: int = 3, timed: int = 20, budget_s: float = 0.0, note: str = "the same workload") -> dict:
@@ -144,6 +168,9 @@ def run_single(args) -> dict:
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     assert len(errs) == args.steps and np.isfinite(errs).all()
+    if args.dump_outputs:
+        f, s, g, lam, mu = eng.get_factors(0)
+        dump_outputs(args.dump_outputs, {"all_error": errs, "f_0": f, "s_0": s, "g_0": g, "lam_0": lam, "mu_0": mu})
     eng.close()
 
     roofline = pass_roofline(make_engine, args.steps, args.warmup)
@@ -305,6 +332,12 @@ def run_sharded(args) -> dict:
     dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
     errs = drv.mean_errors()
+    if args.dump_outputs:      # every rank writes the views it owns, in its share of the budget; rank 0 also All_Error
+        arrays = {"all_error": errs[-args.steps:]} if rank == 0 else {}
+        for v in (v for v in range(n_views) if drv.owned[v]):
+            f, s, g, lam, mu = drv.engine.get_factors(v)
+            arrays.update({f"f_{v}": f, f"s_{v}": s, f"g_{v}": g, f"lam_{v}": lam, f"mu_{v}": mu})
+        dump_outputs(args.dump_outputs, arrays, DUMP_BYTES_MAX * sum(drv.owned) // n_views)
     # the timed run started from the same factors as the collective reference of the set-up: its first sweeps must be the same bits
     verified = None
     if use_p2p and tab_ref is not None:
@@ -426,6 +459,8 @@ def spawn_ranks(args) -> int:
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     procs = []
     for r in range(args.gpus):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(args.gpus), MASTER_ADDR="127.0.0.1",
@@ -463,7 +498,13 @@ def main():
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed run computed as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.steps * 8 > DUMP_BYTES_MAX // 2:
+        ap.error("--dump-outputs: too many steps for the size limit of the dump")
     # RESNMTF_FORCE_SHARDED=1 exercises the multi-rank code path (nccl init, ordered exchange driver,
     # barrier/max timing) with a single rank -- a rehearsal on the one-GPU box
     sharded_path = args.gpus > 1 or os.environ.get("RESNMTF_FORCE_SHARDED") == "1"
