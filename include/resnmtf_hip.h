@@ -367,6 +367,33 @@ int resnmtf_get_factors(resnmtf_handle* h, int v, double* F, double* S, double* 
 int resnmtf_finalise(resnmtf_handle* h, int v, double* F, double* S, double* G,
                      double* row_clusters, double* col_clusters);
 
+/*
+ * Stability selection (stability_check, R/stability_analysis.r:302-338) scores every sub-sample's factorisation
+ * against the original result.  Two entries replace the scoring step of stability_repeat (:268-276):
+ *
+ *   resnmtf_set_reference_clusters  the original result's binary clusters for view v: n_rows[v] x k and n_cols[v] x k,
+ *                         column-major 0 / 1 fp64 as resnmtf_finalise emits them (results$row_clusters[[v]],
+ *                         results$col_clusters[[v]]); k may differ from the handle's own k[v] (e.g. a data-only
+ *                         handle that the sub-samples are gathered from).  Kept on the device as bytes; a second call
+ *                         replaces them.  Entries other than 0 / 1 are refused (RESNMTF_ERR_INVALID).
+ *   resnmtf_relevance     relevance_results(row_c, col_c, true_r, true_c) (R/stability_analysis.r:45-67, with
+ *                         jaccard_main :16-33 and cart_prod / jaccard_func R/utils.r:117-145) for view v of h:
+ *                         row_c / col_c = the clusters resnmtf_finalise would return for h's current F, S, G
+ *                         (computed on the device, same kernels and comparisons; nothing is copied back and h's state
+ *                         is not modified), true_r = ref_row[rows, ], true_c = ref_col[cols, ] = the clusters set on
+ *                         ref's view v_ref gathered by h's n_rows[v] / n_cols[v] 0-based indices.  relevance receives
+ *                         k doubles: max over h's clusters i of the Jaccard index of the pair sets R_i x C_i and
+ *                         TR_j x TC_j, for every reference cluster j; 0 for every j when exactly one of row_c / true_r
+ *                         has no non-empty column, 1 when neither has.  Counted in integers, one fp64 division per
+ *                         pair: bitwise equal to an fp64 restatement.  Refused before any launch: NULL pointers, a bad
+ *                         view or handle, handles on different devices (RESNMTF_ERR_INVALID), no reference clusters
+ *                         on ref's view or no factors on h's (RESNMTF_ERR_STATE), the reference's k differing from
+ *                         h's k[v], indices out of range (RESNMTF_ERR_INVALID).
+ */
+int resnmtf_set_reference_clusters(resnmtf_handle* h, int v, int k, const double* row_clusters, const double* col_clusters);
+int resnmtf_relevance(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, const int* rows, const int* cols,
+                      double* relevance);
+
 /* ---- phase-level entry points (views sharded one-per-GPU; host does the exchange) ---- */
 
 /* Which image of X the streaming passes of view v use after its upload: *uses_2byte = 0 (f32 images), 1 (fp16) or

@@ -6,14 +6,18 @@ matrices) runs in the HIP library through the C-ABI.  R is not available in the 
 run environment, so this Python module is the tested stand-in for the thin R wrapper shown
 in INTEGRATION.md.
 
+Stability selection (``stability_check``, ``R/stability_analysis.r:302-338``) runs here too: the sub-samples are
+gathered, factorised and scored (relevance) on the device, see ``stability_check``.
+
 Deliberately NOT implemented here (out of scope): spurious-bicluster
-removal, the bisilhouette score, the k sweep and stability selection -- they are statistics
-on top of finished factorisations and stay on the R side.  Requests for them raise
-``NotImplementedError`` instead of silently doing something else.
+removal, the bisilhouette score and the k sweep -- they are statistics on top of finished
+factorisations and stay on the R side.  Requests for them raise ``NotImplementedError``
+instead of silently doing something else.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+import warnings
+from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
@@ -160,26 +164,120 @@ def res_nmtf_inner(data, row_indices, column_indices,
     return res
 
 
+def _number_biclusters(results) -> float:
+    """``number_biclusters`` (``R/stability_analysis.r:92-97``): the sum of every row-cluster matrix; 0 for results
+    without cluster matrices (``no_clusts``)."""
+    return float(sum(np.asarray(rc).sum() for rc in (results.get("row_clusters") or [])))
+
+
+def _check_stability_numbers(sample_rate, stab_thres):
+    """``check_numeric`` (``R/utils.r:286-300``)."""
+    if not isinstance(sample_rate, (int, float, np.integer, np.floating)) or isinstance(sample_rate, bool):
+        raise ValueError("sample_rate must be a numeric.")
+    if not isinstance(stab_thres, (int, float, np.integer, np.floating)) or isinstance(stab_thres, bool):
+        raise ValueError("stab_thres must be a numeric.")
+    if not 0 <= stab_thres <= 1:
+        raise ValueError("stab_thres must be between 0 and 1.")
+    if not 0 < sample_rate <= 1:
+        raise ValueError("sample_rate must be greater than 0 and less than or equal to 1.")
+
+
+def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repeats, no_clusts, distance,
+                    sample_rate=0.9, n_stability=5, stab_thres=0.6, remove_unstable=True, *,
+                    row_names=None, col_names=None, device_id: int = 0, seed: Optional[int] = None, group=None,
+                    max_iters: int = 100000, return_repeats: bool = False, repeat_runner: Optional[Callable] = None):
+    """``stability_check`` (``R/stability_analysis.r:302-338``): ``n_stability`` factorisations of sub-samples
+    (``sample_rate`` of the rows and columns, drawn and trimmed as ``stability_repeat`` does, ``:215-249``), each scored
+    against ``results`` by ``relevance_results`` (``:45-67``) -- the gathers, the factorisations and the scoring run on
+    the device (``batched.stability_relevance_on_device``); the repeats are sharded over the ranks of ``group`` when a
+    process group is initialised, and the mean relevance does not depend on their number.
+
+    ``data``: the pre-processed views the original factorisation used (as ``res_nmtf_inner`` receives them; the
+    sub-samples are not re-normalised, SURVEY B11); ``phi`` / ``xi`` / ``psi``: the symmetrised restriction matrices;
+    ``k``: the number of biclusters (a scalar or the reference's ``k_vec``).  Returns ``results`` itself when it has no
+    biclusters (``no_clusts`` results included; the reference's message becomes a warning) or when a repeat could not
+    be sampled; with ``remove_unstable=False`` ``{"res": results, "relevance": n_views x k array}``; else a copy of
+    ``results`` whose row- and column-cluster columns with a mean relevance below ``stab_thres`` are zero (F, S, G
+    untouched; ``results`` is not modified).  ``spurious=True`` inside the repeats is outside the accelerated path.
+    Keyword-only extras: names, ``device_id``, ``seed`` of the draws and the device SVD inits, ``group``,
+    ``max_iters``; test hooks: ``return_repeats`` (adds ``"repeats"``: per repeat the trimmed draws, relevance and
+    the sub-sample's own clusters -- under ``"stability"`` of a copy of the result), ``repeat_runner(r)`` (replaces
+    one repeat; nothing touches the device).
+    """
+    if _number_biclusters(results) == 0:                                                          # :308-311
+        warnings.warn("No biclusters detected!")
+        return results
+    if spurious:
+        raise NotImplementedError("stability selection with spurious-bicluster removal inside its repeats "
+                                  "(R/stability_analysis.r:254-266) is outside the accelerated path; pass spurious=False")
+    _check_stability_numbers(sample_rate, stab_thres)
+    if int(n_stability) != n_stability or n_stability < 1:
+        raise ValueError("n_stability must be a positive integer.")
+    data = [np.asarray(d, dtype=np.float64) for d in _as_list(data)]
+    n_v = len(data)
+    k = int(np.atleast_1d(k)[0])
+    seed = 0 if seed is None else int(seed)
+    from . import batched
+    dev = None
+    if repeat_runner is None:
+        if row_names is None or col_names is None:
+            rn, cn = naming.give_names(data, None, None, row_names, col_names)
+            row_names = row_names or rn
+            col_names = col_names or cn
+        dev = batched.DeviceData(data, phi, xi, psi, row_names, col_names, device_id=device_id, pre_processed=True)
+    try:
+        stab = batched.stability_relevance_on_device(dev, results, k, int(n_stability), float(sample_rate), n_iters,
+                                                     seed, group, max_iters, keep_clusters=return_repeats,
+                                                     runner=repeat_runner)
+    finally:
+        if dev is not None:
+            dev.close()
+    if not stab["stability_performed"]:                                                          # :323-325
+        warnings.warn("Unable to perform stability analysis due to sparsity of data.")
+        return results
+    relevance = stab["relevance"]
+    if not remove_unstable:                                                                       # :328-329
+        out = {"res": results, "relevance": relevance}
+    else:                                                                                         # :330-337
+        out = dict(results)
+        out["row_clusters"] = [np.array(rc, dtype=np.float64, copy=True) for rc in results["row_clusters"]]
+        out["col_clusters"] = [np.array(cc, dtype=np.float64, copy=True) for cc in results["col_clusters"]]
+        for i in range(n_v):
+            drop = relevance[i] < stab_thres
+            out["row_clusters"][i][:, drop] = 0.0
+            out["col_clusters"][i][:, drop] = 0.0
+    if return_repeats:
+        out = dict(out)
+        out["stability"] = {"relevance": relevance, "repeats": stab["repeats"]}
+    return out
+
+
 def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                   phi=None, xi=None, psi=None, n_iters=None, k_min=3, k_max=8,
                   distance="euclidean", spurious=True, num_repeats=5, no_clusts=False,
                   sample_rate=0.9, n_stability=5, stability=True, stab_thres=0.4,
                   remove_unstable=True, use_parallel=True, *, row_names=None, col_names=None,
                   device_id: int = 0, max_iters: int = 100000, seed: Optional[int] = None):
-    """``apply_resnmtf`` (``R/main.r:214-335``) for a known ``k_val`` without stability
-    selection: naming, shared-name maps, restriction symmetrisation, non-negativity shift and
-    column normalisation on the host, then the device loop."""
+    """``apply_resnmtf`` (``R/main.r:214-335``) for a known ``k_val``: naming, shared-name maps, restriction
+    symmetrisation, non-negativity shift and column normalisation on the host, then the device loop and -- with
+    ``stability=True`` (the default) and ``spurious=False`` -- ``stability_check`` on the pre-processed data, as
+    ``R/main.r:255-262`` does.  As at that call site, ``remove_unstable`` is NOT forwarded: ``stability_check``
+    always runs with its default ``remove_unstable=True`` (unstable biclusters are zeroed whatever is passed here).
+    ``stab_thres`` defaults to 0.4 here, against 0.6 in ``stability_check``.  ``stability=True`` with
+    ``spurious=True`` is refused (spurious-bicluster removal is outside the accelerated path)."""
     data = [np.asarray(d, dtype=np.float64) for d in _as_list(data)]
     n_v = len(data)
     if k_val is None:
         raise NotImplementedError("the k sweep (R/main.r:279-321) needs the bisilhouette score, which is "
                                   "outside the accelerated path; pass k_val")
-    if stability:
-        raise NotImplementedError("stability selection (R/stability_analysis.r) is outside the accelerated "
-                                  "path; pass stability=False or do it on the R side (INTEGRATION.md)")
+    if stability and spurious and not no_clusts:
+        raise NotImplementedError("stability selection with spurious-bicluster removal (R/obtain_bicl.r:31-133) is "
+                                  "outside the accelerated path; pass spurious=False (or stability=False and do the "
+                                  "removal on the R side, INTEGRATION.md)")
     for name, val in (("n_iters", n_iters), ("num_repeats", num_repeats), ("n_stability", n_stability)):
         if val is not None and (int(val) != val or val < 1):
             raise ValueError(f"{name} must be a positive integer.")                               # utils.r:220-253
+    _check_stability_numbers(sample_rate, stab_thres)                                             # utils.r:286-300
     k_vec = [int(np.atleast_1d(k_val)[0])] * n_v                                                  # main.r:226
     ranks = [d.shape[1] for d in data]
     if any(k < 1 for k in k_vec):
@@ -192,6 +290,12 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     psi_m = naming.init_rest_mats(psi, n_v)
     xi_m = naming.init_rest_mats(xi, n_v)
     data = naming.check_data(data)                                                                # main.r:237
-    return res_nmtf_inner(data, row_idx, col_idx, init_f, init_s, init_g, k_vec, phi_m, xi_m, psi_m,
-                          n_iters, num_repeats, spurious, distance, no_clusts,
-                          row_names=rn, col_names=cn, device_id=device_id, max_iters=max_iters, seed=seed)
+    results = res_nmtf_inner(data, row_idx, col_idx, init_f, init_s, init_g, k_vec, phi_m, xi_m, psi_m,
+                             n_iters, num_repeats, spurious, distance, no_clusts,
+                             row_names=rn, col_names=cn, device_id=device_id, max_iters=max_iters, seed=seed)
+    if stability:                                                                                 # main.r:255-262
+        results = stability_check(data, results, k_vec, phi_m, xi_m, psi_m, n_iters, spurious, num_repeats,
+                                  no_clusts, distance, sample_rate, n_stability, stab_thres,
+                                  row_names=rn, col_names=cn, device_id=device_id, seed=seed,
+                                  max_iters=max_iters)
+    return results

@@ -8,9 +8,10 @@ builds the job lists with the reference's own sampling rules and runs them, shar
 over the ranks of a ``torch.distributed`` process group when there is one (one process per GPU, no
 collective in the data path; the results are gathered as Python objects at the end).
 
-What is NOT here, on purpose: the scores computed from the factorisations (bisilhouette, JSD,
-relevance) -- statistics on finished results that stay on the R side (``bisilhouette`` is not even
-available offline).
+Stability selection is scored here too: ``stability_relevance_on_device`` runs the repeats of ``stability_check``
+and reduces each sub-sample's factorisation to its relevance values on the device (``resnmtf_relevance``).  What is
+NOT here, on purpose: the other scores computed from the factorisations (bisilhouette, JSD) -- statistics on finished
+results that stay on the R side (``bisilhouette`` is not even available offline).
 """
 from __future__ import annotations
 
@@ -115,7 +116,7 @@ def stability_jobs(data, k: int, n_stability: int = 5, sample_rate: float = 0.9,
                    n_iters=None, seed: int = 0, row_names=None, col_names=None) -> List[Job]:
     """The factorisations of ``stability_check`` (``R/stability_analysis.r:305-323``): one per
     repeat on a sub-sample drawn by ``subsample_views``; the draws are kept in ``extras`` for the
-    relevance computation on the R side.  Repeats whose sampling fails are skipped, as the reference
+    relevance computation (on the device: ``stability_relevance_on_device``).  Repeats whose sampling fails are skipped, as the reference
     does (``stability_performed = FALSE``)."""
     from . import naming
     rng = np.random.default_rng(seed)
@@ -189,18 +190,33 @@ def run_jobs(jobs: Sequence[Job], device_id: int = 0, group=None, runner: Option
 class DeviceData:
     """The pre-processed views of one data set, uploaded once (``resnmtf_set_view_raw``) and kept for
     any number of factorisations (``resnmtf_copy_view`` / ``resnmtf_shuffle_view``).  At c2 size an
-    upload costs ~45 ms of PCIe + conversion, 500 sweeps ~23 ms: re-uploading per job would dominate."""
+    upload costs ~45 ms of PCIe + conversion, 500 sweeps ~23 ms: re-uploading per job would dominate.
 
-    def __init__(self, data, phi=None, xi=None, psi=None, row_names=None, col_names=None, device_id: int = 0):
+    ``pre_processed=True`` (opt-in) takes the data as ``res_nmtf_inner`` receives them: the views are uploaded exactly
+    as given (``resnmtf_set_view``, no shift, no normalisation) and ``phi`` / ``xi`` / ``psi`` are the symmetrised
+    matrices, used as they are -- the form ``stability_check`` gets both in (``R/main.r:255-262``; its sub-samples are
+    not re-normalised)."""
+
+    def __init__(self, data, phi=None, xi=None, psi=None, row_names=None, col_names=None, device_id: int = 0,
+                 pre_processed: bool = False):
         from . import naming
         from .engine import Engine
         self.data_shapes = [np.asarray(d).shape for d in data]
         n_v = len(data)
         self.rn, self.cn = naming.give_names([np.asarray(d) for d in data], phi, psi, row_names, col_names)
-        self.phi = naming.init_rest_mats(phi, n_v); self.xi = naming.init_rest_mats(xi, n_v); self.psi = naming.init_rest_mats(psi, n_v)
+        if pre_processed:
+            self.phi, self.xi, self.psi = (np.zeros((n_v, n_v)) if m is None else np.asarray(m, dtype=np.float64)
+                                           for m in (phi, xi, psi))
+        else:
+            self.phi = naming.init_rest_mats(phi, n_v); self.xi = naming.init_rest_mats(xi, n_v); self.psi = naming.init_rest_mats(psi, n_v)
         self.device_id = device_id
         self.base = Engine([s[0] for s in self.data_shapes], [s[1] for s in self.data_shapes], [2] * n_v, device_id=device_id)
-        self.was_negative = [self.base.set_view_raw(v, np.asarray(data[v], dtype=np.float64)) for v in range(n_v)]
+        if pre_processed:
+            for v in range(n_v):
+                self.base.set_view(v, np.asarray(data[v], dtype=np.float64))
+            self.was_negative = [False] * n_v
+        else:
+            self.was_negative = [self.base.set_view_raw(v, np.asarray(data[v], dtype=np.float64)) for v in range(n_v)]
 
     def close(self):
         self.base.close()
@@ -240,14 +256,18 @@ class DeviceData:
 
     def factorise(self, k: int, n_iters: Optional[int] = None, seed: int = 0, shuffle_seed: Optional[int] = None,
                   max_iters: int = 100000, tag: str = "", samples=None, return_init: bool = False,
-                  return_data: bool = False) -> dict:
+                  return_data: bool = False, relevance: bool = False, keep_clusters: bool = False) -> dict:
         """One factorisation with k biclusters per view: views copied -- or, with ``shuffle_seed``, shuffled as
         ``obtain_shuffled_f`` does (no restrictions, fresh names; redrawn while a row or a column of the shuffled
         matrix sums to zero, ``R/obtain_bicl.r:14-18``), or, with ``samples = (row_samples, col_samples)``,
         sub-sampled as ``stability_repeat`` does (not re-normalised, names carried over; all-zero rows / columns
         dropped first, ``_trim_samples``) -- on the device, device SVD init, loop, finalise.
         ``return_init`` / ``return_data`` add the initial (F, S, G, lambda, mu) per view and the device's copy of the
-        data actually factorised (fp32 precision) to the result: what a reference run needs to start from the same place."""
+        data actually factorised (fp32 precision) to the result: what a reference run needs to start from the same place.
+        ``relevance`` (with ``samples``): instead of finalise, score the sub-sample's clusters against the reference
+        clusters set on ``self.base`` (``resnmtf_relevance``, ``R/stability_analysis.r:268-276``) -- the result holds
+        the n_views x k ``"relevance"`` matrix and no factors; ``keep_clusters`` adds the sub-sample's own binary
+        clusters (a test hook: they cost a finalise download)."""
         from . import naming
         from .engine import Engine
         n_v = len(self.data_shapes)
@@ -290,10 +310,21 @@ class DeviceData:
             init_state = [eng.get_factors(v) for v in range(n_v)] if return_init else None
             data_used = [eng.get_view(v) for v in range(n_v)] if return_data else None
             errs = eng.run(n_iters=n_iters, tol=1.0e-6, max_iters=max_iters)
-            fin = [eng.finalise(v) for v in range(n_v)]
+            if relevance:
+                rel = np.stack([eng.relevance(v, self.base, v, samples[0][v], samples[1][v]) for v in range(n_v)])
+                fin = [eng.finalise(v) for v in range(n_v)] if keep_clusters else None
+            else:
+                fin = [eng.finalise(v) for v in range(n_v)]
         finally:
             eng.close()
         error = float(np.mean(errs[-10:])) if n_iters is None else float(errs[-1])           # R/main.r:126-130
+        if relevance:
+            res = {"stability_performed": True, "relevance": rel, "Error": error, "All_Error": errs, "tag": tag,
+                   "extras": {"row_samples": samples[0], "col_samples": samples[1]}}
+            if keep_clusters:
+                res["row_clusters"] = [f[3] for f in fin]
+                res["col_clusters"] = [f[4] for f in fin]
+            return res
         res = {"output_f": [f[0] for f in fin], "output_s": [f[1] for f in fin], "output_g": [f[2] for f in fin],
                "row_clusters": [f[3] for f in fin], "col_clusters": [f[4] for f in fin],
                "Error": error, "All_Error": errs, "tag": tag,
@@ -327,15 +358,63 @@ def stability_on_device(dev: DeviceData, k: int, n_stability: int = 5, sample_ra
     columns of a sub-sample -- the pre-processed data are non-negative, not positive: ``make_non_neg`` leaves a zero
     at every shifted column's minimum and sparse inputs stay sparse -- are dropped as the reference does
     (``DeviceData._trim_samples``); a repeat whose sampling fails returns ``stability_performed = False``."""
+    draws = stability_draws(dev.data_shapes, n_stability, sample_rate, seed)
+    return run_jobs(list(range(n_stability)), group=group,
+                    runner=lambda r: dev.factorise(k, n_iters, seed + 2000 + r, samples=draws[r], tag=f"stability={r}"))
+
+
+def stability_draws(shapes, n_stability: int, sample_rate: float, seed: int = 0):
+    """The untrimmed draws of the ``n_stability`` repeats, ``[(row_samples, col_samples)]``: view 1 draws
+    ``floor(dim * sample_rate)`` rows and columns, a later view re-uses view 1's draw along an axis of equal extent
+    (``R/stability_analysis.r:111-132``, ``:230-231``)."""
     rng = np.random.default_rng(seed)
     draws = []
     for _ in range(n_stability):
         rows, cols = [], []
-        for v, (n, m) in enumerate(dev.data_shapes):
-            same_r = v > 0 and n == dev.data_shapes[0][0]
-            same_c = v > 0 and m == dev.data_shapes[0][1]
+        for v, (n, m) in enumerate(shapes):
+            same_r = v > 0 and n == shapes[0][0]
+            same_c = v > 0 and m == shapes[0][1]
             rows.append(rows[0] if same_r else rng.choice(n, int(n * sample_rate), replace=False))      # :114-118, :230
             cols.append(cols[0] if same_c else rng.choice(m, int(m * sample_rate), replace=False))      # :119-123, :231
         draws.append((rows, cols))
-    return run_jobs(list(range(n_stability)), group=group,
-                    runner=lambda r: dev.factorise(k, n_iters, seed + 2000 + r, samples=draws[r], tag=f"stability={r}"))
+    return draws
+
+
+def mean_relevance(repeats: Sequence[dict], n_stability: int) -> Optional[np.ndarray]:
+    """``stability_check``'s reduction (``R/stability_analysis.r:315-327``): the repeats' n_views x k relevance
+    matrices summed on the host in repeat order, then divided by ``n_stability`` -- the same additions in the same
+    order whatever the number of ranks that computed them.  ``None`` when a repeat was not performed (the reference
+    then returns the results unchanged)."""
+    total = None
+    for rep in repeats:
+        if not rep.get("stability_performed", True):
+            return None
+        rel = np.asarray(rep["relevance"], dtype=np.float64)
+        total = (np.zeros_like(rel) if total is None else total) + rel
+    return total / n_stability
+
+
+def stability_relevance_on_device(dev: Optional[DeviceData], results: dict, k: int, n_stability: int = 5,
+                                  sample_rate: float = 0.9, n_iters=None, seed: int = 0, group=None,
+                                  max_iters: int = 100000, keep_clusters: bool = False,
+                                  runner: Optional[Callable] = None) -> dict:
+    """The repeats of ``stability_check`` (``R/stability_analysis.r:302-334``) with their scoring on the device:
+    ``results``' binary clusters are uploaded once onto ``dev.base`` (``resnmtf_set_reference_clusters``), repeat r
+    factorises the sub-sample of ``stability_draws`` (trimmed as ``stability_on_device`` does) up to the end of the loop
+    and returns its n_views x k relevance (``resnmtf_relevance``) -- no factor leaves the device.  The repeats are
+    sharded round-robin over the ranks of an initialised process group (``run_jobs``; every rank holds its own
+    ``DeviceData`` and the same ``results``) and reduced by ``mean_relevance``.  ``runner(r)`` replaces the
+    repeat (the CPU tests inject a stand-in; ``dev`` is then not used).  Returns ``{"stability_performed",
+    "relevance" (None when not performed), "repeats"}``."""
+    if runner is None:
+        n_v = len(dev.data_shapes)
+        for v in range(n_v):
+            dev.base.set_reference_clusters(v, results["row_clusters"][v], results["col_clusters"][v])
+        draws = stability_draws(dev.data_shapes, n_stability, sample_rate, seed)
+
+        def runner(r):
+            return dev.factorise(k, n_iters, seed + 2000 + r, max_iters=max_iters, samples=draws[r], relevance=True,
+                                 keep_clusters=keep_clusters, tag=f"stability={r}")
+    repeats = run_jobs(list(range(n_stability)), group=group, runner=runner)
+    rel = mean_relevance(repeats, n_stability)
+    return {"stability_performed": rel is not None, "relevance": rel, "repeats": repeats}

@@ -54,6 +54,8 @@ struct ViewState {
   bool owned = true, has_x = false, has_factors = false;
   int empty_rows = 0, empty_cols = 0;          // all-zero rows / columns of the latest device-drawn data (shuffle, sub-sample)
   std::vector<unsigned char> empty_mask;     // [n + m], 1 = the row / column sums to zero
+  unsigned char* ref_cl = nullptr;           // resnmtf_set_reference_clusters: [n][ref_k] row, then [m][ref_k] column clusters (0 / 1)
+  int ref_k = 0;
   int n_pad = 0, m_pad = 0;
   size_t ldx = 0, ldxt = 0;      // TILE strides of X32 / Xt32 (floats): tile t (64 columns) is a contiguous [rows_pad][64] block
   size_t x32_floats = 0, xt32_floats = 0;
@@ -220,7 +222,7 @@ void free_view(ViewState& v) {
   if (v.gblk) { v.gblk = nullptr; v.Tsum = nullptr; v.Ma_G = nullptr; v.Md_G = nullptr; v.mu = nullptr; }
   v.sblk = nullptr;
   void* ptrs[] = {v.fuse_cnt, v.Fk, v.Gk, v.X16, v.Xt16, v.X32, v.Xt32, v.xnorm2, v.F, v.G, v.S, v.lambda, v.mu, v.F32, v.G32, v.T32, v.Pxg, v.Pxtf,
-                  v.Paux_xg, v.Paux_xtf, v.cnt_xg, v.cnt_xtf, v.partF, v.partG, v.FtF, v.FtFS, v.cF, v.Ma_F, v.Md_F, v.Ma_G, v.Md_G};
+                  v.Paux_xg, v.Paux_xtf, v.cnt_xg, v.cnt_xtf, v.partF, v.partG, v.FtF, v.FtFS, v.cF, v.Ma_F, v.Md_F, v.Ma_G, v.Md_G, v.ref_cl};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& mp : v.row_map)
@@ -2746,6 +2748,85 @@ int resnmtf_finalise(resnmtf_handle* h, int v, double* F, double* S, double* G, 
   (void)hipFree(buf);
   (void)hipFree(rel);
   if (e != hipSuccess) return h->fail_hip("finalise", e);
+  return RESNMTF_OK;
+}
+
+// ---- stability selection (R/stability_analysis.r:302-338): relevance of a sub-sample's biclusters, on the device
+int resnmtf_set_reference_clusters(resnmtf_handle* h, int v, int k, const double* row_clusters, const double* col_clusters) {
+  if (int rc = check_view(h, v)) return rc;
+  if (!row_clusters || !col_clusters) return h->fail(RESNMTF_ERR_INVALID, "row_clusters / col_clusters are NULL");
+  if (k < 1 || k > RESNMTF_MAX_K) return h->fail(RESNMTF_ERR_INVALID, "k must be in [1, 64]");
+  ViewState& vs = h->views[v];
+  const size_t nk = (size_t)vs.n * k, mk = (size_t)vs.m * k;
+  std::vector<unsigned char> bytes(nk + mk);       // column-major 0 / 1 doubles -> row-major bytes
+  for (int j = 0; j < k; ++j) {
+    for (int r = 0; r < vs.n; ++r) {
+      const double x = row_clusters[(size_t)j * vs.n + r];
+      if (x != 0.0 && x != 1.0) return h->fail(RESNMTF_ERR_INVALID, "row_clusters entries must be 0 or 1");
+      bytes[(size_t)r * k + j] = x != 0.0;
+    }
+    for (int c = 0; c < vs.m; ++c) {
+      const double x = col_clusters[(size_t)j * vs.m + c];
+      if (x != 0.0 && x != 1.0) return h->fail(RESNMTF_ERR_INVALID, "col_clusters entries must be 0 or 1");
+      bytes[nk + (size_t)c * k + j] = x != 0.0;
+    }
+  }
+  HIP_TRY(h, hipSetDevice(h->opt.device_id));
+  if (int rc = sync_both(h)) return rc;
+  if (vs.ref_cl) { (void)hipFree(vs.ref_cl); vs.ref_cl = nullptr; vs.ref_k = 0; }
+  HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&vs.ref_cl), bytes.size()));
+  const hipError_t e = hipMemcpy(vs.ref_cl, bytes.data(), bytes.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { (void)hipFree(vs.ref_cl); vs.ref_cl = nullptr; return h->fail_hip("set_reference_clusters", e); }
+  vs.ref_k = k;
+  return RESNMTF_OK;
+}
+
+int resnmtf_relevance(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, const int* rows, const int* cols,
+                      double* relevance) {
+  if (int rc = check_view(h, v)) return rc;
+  if (!ref || v_ref < 0 || v_ref >= ref->V) return h->fail(RESNMTF_ERR_INVALID, "bad reference handle / view");
+  if (!rows || !cols || !relevance) return h->fail(RESNMTF_ERR_INVALID, "rows / cols / relevance are NULL");
+  if (h->opt.device_id != ref->opt.device_id) return h->fail(RESNMTF_ERR_INVALID, "handles live on different devices");
+  const ViewState& vs = h->views[v];
+  const ViewState& rs = ref->views[v_ref];
+  if (!rs.ref_cl) return h->fail(RESNMTF_ERR_STATE, "no reference clusters set on the reference view");
+  if (!vs.has_factors) return h->fail(RESNMTF_ERR_STATE, "the view has no factors");
+  if (rs.ref_k != vs.k) return h->fail(RESNMTF_ERR_INVALID, "the reference clusters' k differs from the view's k");
+  for (int r = 0; r < vs.n; ++r) if (rows[r] < 0 || rows[r] >= rs.n) return h->fail(RESNMTF_ERR_INVALID, "row index out of range");
+  for (int c = 0; c < vs.m; ++c) if (cols[c] < 0 || cols[c] >= rs.m) return h->fail(RESNMTF_ERR_INVALID, "column index out of range");
+  HIP_TRY(h, hipSetDevice(h->opt.device_id));
+  if (int rc = sync_both(h)) return rc;
+  const int k = vs.k;
+  const size_t kk = (size_t)k * k, side = kk + 2 * (size_t)k;
+  // [cF k][cG k][S_out kk][out k] doubles | [relations k][rows n][cols m] ints | [counts 2 side] unsigned
+  const size_t n_dbl = 3 * (size_t)k + kk, n_int = (size_t)k + vs.n + vs.m;
+  char* buf = nullptr;
+  HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), n_dbl * sizeof(double) + n_int * sizeof(int) + 2 * side * sizeof(unsigned int)));
+  double *cF = reinterpret_cast<double*>(buf), *cG = cF + k, *So = cG + k, *out = So + kk;
+  int *rel = reinterpret_cast<int*>(buf + n_dbl * sizeof(double)), *idx = rel + k;
+  unsigned int* counts = reinterpret_cast<unsigned int*>(idx + vs.n + vs.m);
+  hipError_t e = hipMemcpyAsync(idx, rows, (size_t)vs.n * sizeof(int), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(idx + vs.n, cols, (size_t)vs.m * sizeof(int), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(counts, 0, 2 * side * sizeof(unsigned int), h->stream);
+  if (e == hipSuccess) {
+    // the clusters resnmtf_finalise would emit: same kernels, same reductions, same first-max relations
+    hipLaunchKernelGGL(colsum_kernel, dim3(k), dim3(256), 0, h->stream, vs.F, vs.n, k, cF);
+    hipLaunchKernelGGL(colsum_kernel, dim3(k), dim3(256), 0, h->stream, vs.G, vs.m, k, cG);
+    hipLaunchKernelGGL(finalise_s_kernel, dim3(1), dim3(64), 0, h->stream, vs.S, k, cF, cG, So, rel);
+    const int grid_r = std::max(1, std::min(128, ceil_div(ceil_div(vs.n, 64), 4)));
+    const int grid_c = std::max(1, std::min(128, ceil_div(ceil_div(vs.m, 64), 4)));
+    hipLaunchKernelGGL(relevance_count_kernel, dim3(grid_r), dim3(256), 0, h->stream, vs.F, vs.n, k, cF, (const int*)rel,
+                       (const unsigned char*)rs.ref_cl, (const int*)idx, counts);
+    hipLaunchKernelGGL(relevance_count_kernel, dim3(grid_c), dim3(256), 0, h->stream, vs.G, vs.m, k, cG, (const int*)nullptr,
+                       (const unsigned char*)(rs.ref_cl + (size_t)rs.n * k), (const int*)(idx + vs.n), counts + side);
+    hipLaunchKernelGGL(relevance_epilogue_kernel, dim3(1), dim3(64), 0, h->stream, k, (const unsigned int*)counts,
+                       (const unsigned int*)(counts + side), out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(relevance, out, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  (void)hipFree(buf);
+  if (e != hipSuccess) return h->fail_hip("relevance", e);
   return RESNMTF_OK;
 }
 

@@ -3268,3 +3268,80 @@ static __global__ __launch_bounds__(256) void finalise_factor_kernel(const doubl
   const double v = W[(size_t)r * k + src] / c[src];
   cl_out[idx] = (v > (1.0 / (double)len)) ? 1.0 : 0.0;
 }
+
+// --------------------------------------------------------------------------------------
+// Relevance of a sub-sample biclustering against the original one: relevance_results (R/stability_analysis.r:45-67)
+// with jaccard_main (:16-33), cart_prod and jaccard_func (R/utils.r:117-145).  Bicluster i is the pair set R_i x C_i, so
+// |pairs_i ^ pairs_j| = |R_i ^ TR_j| |C_i ^ TC_j| and |pairs_i| = |R_i| |C_i|: the Jaccard index is a function of integer
+// counts per side.  relevance_count_kernel counts ONE side (rows or columns) per launch: a wave takes 64 lines at a time,
+// forms the membership masks of the sub-sample's clusters (the comparison of finalise_factor_kernel, bit for bit: same
+// W / c[src] > 1/len) and of the reference's clusters gathered through idx with __ballot, and adds popcounts of the
+// ANDed masks into LDS counters, then into `counts` -- integer atomics only, so the counts do not depend on the order
+// in which workgroups or waves run.
+// counts (per side, unsigned): [k * k: |A_i ^ B_j| at i * k + j] [k: |A_i|] [k: |B_j|]   (A = sub-sample, B = reference)
+// ref: the reference's clusters of this side as 0 / 1 bytes, [len_ref][k] row-major; idx: len indices into its rows
+// (validated on the host).
+// --------------------------------------------------------------------------------------
+static __global__ __launch_bounds__(256) void relevance_count_kernel(const double* __restrict__ W, int len, int k,
+                                                                     const double* __restrict__ c,
+                                                                     const int* __restrict__ relations,
+                                                                     const unsigned char* __restrict__ ref,
+                                                                     const int* __restrict__ idx,
+                                                                     unsigned int* __restrict__ counts) {
+  __shared__ unsigned int cnt[RESNMTF_MAX_K * RESNMTF_MAX_K + 2 * RESNMTF_MAX_K];
+  const int total = k * k + 2 * k;
+  for (int t = threadIdx.x; t < total; t += 256) cnt[t] = 0u;
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int chunks = (len + 63) / 64;
+  const double thr = 1.0 / (double)len;
+  for (int ch = blockIdx.x * 4 + wave; ch < chunks; ch += gridDim.x * 4) {
+    const int r = ch * 64 + lane;
+    const bool valid = r < len;
+    const int rr = valid ? r : len - 1;      // lanes past the end address the last line and vote 0
+    const unsigned char* refrow = ref + (size_t)idx[rr] * k;
+    unsigned long long mine = 0ull;          // lane j < k: the reference's cluster j over these 64 lines
+    for (int j = 0; j < k; ++j) {
+      const unsigned long long b = __ballot(valid && refrow[j] != 0);
+      if (lane == j) mine = b;
+    }
+    if (lane < k && mine) atomicAdd(&cnt[k * k + k + lane], (unsigned int)__popcll(mine));
+    for (int i = 0; i < k; ++i) {
+      const int src = relations ? relations[i] : i;
+      const unsigned long long a = __ballot(valid && (W[(size_t)rr * k + src] / c[src] > thr));
+      if (a == 0ull) continue;                                       // (wave-uniform)
+      if (lane == 0) atomicAdd(&cnt[k * k + i], (unsigned int)__popcll(a));
+      if (lane < k) {
+        const unsigned int p = (unsigned int)__popcll(a & mine);
+        if (p) atomicAdd(&cnt[i * k + lane], p);
+      }
+    }
+  }
+  __syncthreads();
+  for (int t = threadIdx.x; t < total; t += 256)
+    if (cnt[t]) atomicAdd(&counts[t], cnt[t]);
+}
+
+// relevance[j] = max_i J(i, j) (apply(jac_mat, 2, max)), J = I / U, I = rI * cI, U = |R_i| |C_i| + |TR_j| |TC_j| - I,
+// 0 when U == 0 -- after the edge cases of relevance_results, decided on the ROW clusters alone (m_0 / n_0 = non-empty
+// columns of row_c / true_r): exactly one of them 0 -> 0, both 0 -> 1, broadcast over j.  Integer products (exact in
+// int64 and, below 2^53, in fp64) and one correctly rounded division per pair: bitwise the fp64 host restatement.
+static __global__ void relevance_epilogue_kernel(int k, const unsigned int* __restrict__ rows_cnt,
+                                                 const unsigned int* __restrict__ cols_cnt, double* __restrict__ out) {
+  const int j = threadIdx.x;
+  if (j >= k) return;
+  const unsigned int *rI = rows_cnt, *rA = rows_cnt + k * k, *rB = rA + k;
+  const unsigned int *cI = cols_cnt, *cA = cols_cnt + k * k, *cB = cA + k;
+  int m0 = 0, n0 = 0;
+  for (int t = 0; t < k; ++t) { m0 += rA[t] != 0u; n0 += rB[t] != 0u; }
+  if ((m0 == 0) != (n0 == 0)) { out[j] = 0.0; return; }     // R/stability_analysis.r:57-59
+  if (m0 == 0) { out[j] = 1.0; return; }                     // :62-64
+  double best = 0.0;
+  for (int i = 0; i < k; ++i) {
+    const long long inter = (long long)rI[i * k + j] * (long long)cI[i * k + j];
+    const long long uni = (long long)rA[i] * (long long)cA[i] + (long long)rB[j] * (long long)cB[j] - inter;
+    const double jac = uni == 0 ? 0.0 : (double)inter / (double)uni;      // jaccard_func, R/utils.r:117-126
+    if (i == 0 || jac > best) best = jac;
+  }
+  out[j] = best;
+}

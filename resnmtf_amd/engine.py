@@ -253,6 +253,27 @@ class Engine:
         self._check(self._lib.resnmtf_finalise(self._h, v, _dp(f), _dp(s), _dp(g), _dp(rc), _dp(cc)))
         return f, s, g, rc, cc
 
+    def set_reference_clusters(self, v: int, rc, cc):
+        """The original result's binary clusters of view ``v`` (n x k and m x k, 0 / 1; k may differ from this engine's
+        k[v]), kept on the device for ``relevance`` calls of the sub-samples' engines (``stability_check``,
+        ``R/stability_analysis.r:268-276``)."""
+        rc = np.asfortranarray(np.asarray(rc, dtype=np.float64))
+        if rc.ndim != 2 or rc.shape[0] != self.n_rows[v]:
+            raise ValueError(f"row clusters must be {self.n_rows[v]} x k")
+        cc = _f64_colmajor(cc, (self.n_cols[v], rc.shape[1]))
+        self._check(self._lib.resnmtf_set_reference_clusters(self._h, v, int(rc.shape[1]), _dp(rc), _dp(cc)))
+
+    def relevance(self, v: int, ref_engine: "Engine", v_ref: int, rows, cols) -> np.ndarray:
+        """``relevance_results`` (``R/stability_analysis.r:45-67``) of this engine's view ``v`` (its current factors,
+        clustered as ``finalise`` would) against the clusters set on ``ref_engine``'s view ``v_ref``, gathered by
+        ``rows`` / ``cols`` (0-based, one per row / column of view ``v``): k relevance values, computed on the device."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32); cols = np.ascontiguousarray(cols, dtype=np.int32)
+        if rows.ndim != 1 or cols.ndim != 1 or len(rows) != self.n_rows[v] or len(cols) != self.n_cols[v]:
+            raise ValueError("index counts must equal the view's shape")
+        out = np.zeros(self.k[v], dtype=np.float64)
+        self._check(self._lib.resnmtf_relevance(self._h, v, ref_engine._h, v_ref, _ip(rows), _ip(cols), _dp(out)))
+        return out
+
     def view_image_info(self, v: int):
         """(kind, rel_error): kind 0 = f32 images, 1 = fp16, 2 = uniform 16-bit integers; the relative quantisation
         error of the 2-byte image of view ``v`` measured at upload (``x_half``)."""
