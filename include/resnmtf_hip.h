@@ -245,6 +245,38 @@ int resnmtf_create(int n_views, const int* n_rows, const int* n_cols, const int*
 int resnmtf_destroy(resnmtf_handle* h);
 
 /*
+ * Sparse data views.  As resnmtf_create, with nnz_capacity[v] per view: < 0 = a dense view (exactly as resnmtf_create
+ * makes it), >= 0 = a SPARSE view that holds at most that many stored entries.  A sparse view allocates no dense image of
+ * X (8 n m bytes), only a CSC copy (int64 column pointers, int32 row indices, fp32 values) for the Xt.F' pass and a CSR
+ * copy (likewise) for the X.G pass: 16 bytes per entry + 8 (n + m).  Its passes are sparse-times-dense kernels that write
+ * the same partial slabs as the dense passes, so the rest of the sweep (updates, k x k chains, error, stop test) is the
+ * dense path's; hand-off mode A at every k; x_half, fuse_updates and the view-sharded layouts (replicate_f / replicate_gs /
+ * slice_chains / slice_p2p: refused) never apply.  resnmtf_get_view, resnmtf_copy_view, resnmtf_shuffle_view and
+ * resnmtf_subsample_view refuse a sparse view (RESNMTF_ERR_INVALID) instead of densifying it.
+ * Replaces: as resnmtf_create (R/main.r:38-48) for views that R holds as Matrix::dgCMatrix (R/utils.r:416-419 densifies
+ * them with as.matrix; the result is defined as the factorisation of that dense matrix).
+ */
+int resnmtf_create_sparse(int n_views, const int* n_rows, const int* n_cols, const int* k, const int* owned,
+                          const long long* nnz_capacity, const resnmtf_options* opts, resnmtf_handle** out);
+/*
+ * Upload the data of a sparse owned view as 0-based CSC: col_ptr [m + 1] (int64), row_idx / values [col_ptr[m]] -- the
+ * @p / @i / @x slots of a dgCMatrix.  Checked on the host before any device work (RESNMTF_ERR_INVALID, text in
+ * resnmtf_last_error): col_ptr[0] = 0 and monotone, col_ptr[m] <= the view's capacity, row indices in range and strictly
+ * increasing within a column, finite non-negative values.  pre_processed = 0: check_inputs on the device --
+ * matrix_normalisation (x / colSums(x), R/utils.r:86-88), fp64, before the f32 copies; an all-zero column is refused (the
+ * reference yields a NaN column) and so is a negative entry (make_non_neg's per-column shift, R/utils.r:20-27, would turn
+ * every implicit zero positive: shift on the host and upload dense).  pre_processed = 1: values taken as given (the
+ * sub-samples of stability selection).  Then data_norms (R/main.r:48) as resnmtf_set_view.  The CSR copy is built here
+ * (entries of a row in ascending column order), and the work split of the two passes is planned from the row / column
+ * lengths.
+ */
+int resnmtf_set_view_csc(resnmtf_handle* h, int v, const long long* col_ptr, const int* row_idx, const double* values,
+                         int pre_processed);
+/* Storage of view v: *is_sparse (0 / 1), *nnz = stored entries of the last upload (0 for dense views), *nnz_capacity (-1 for
+ * dense views).  Any pointer may be NULL. */
+int resnmtf_view_storage(resnmtf_handle* h, int v, int* is_sparse, long long* nnz, long long* nnz_capacity);
+
+/*
  * Upload the data matrix of an owned view: x is n x m fp64 column-major, ALREADY non-negative
  * and column-L1-normalised (what check_inputs produces, R/utils.r:416,422).  Also computes
  * data_norms[v] = ||X||_F^2 (R/main.r:48) on the device.

@@ -21,7 +21,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import naming
+from . import naming, sparse
 from .engine import Engine
 
 _DISTANCES = ("euclidean", "manhattan", "cosine")
@@ -30,7 +30,15 @@ _DISTANCES = ("euclidean", "manhattan", "cosine")
 def _as_list(x):
     if isinstance(x, np.ndarray) and x.ndim == 2:
         return [x]                      # check_lists, R/utils.r:313-316
+    if sparse.is_sparse(x):
+        return [x]
     return list(x)
+
+
+def _views(data) -> list:
+    """The views as fp64 arrays; a ``scipy.sparse`` view becomes a canonical CSC copy (``sparse.canonical_csc``: the
+    caller's matrix is not modified) and stays sparse on the device (``resnmtf_create_sparse``)."""
+    return [sparse.canonical_csc(d) if sparse.is_sparse(d) else np.asarray(d, dtype=np.float64) for d in _as_list(data)]
 
 
 def svd_init(data: Sequence[np.ndarray], k_vec: Sequence[int], seed: Optional[int] = None, sigma: float = 0.05):
@@ -57,7 +65,10 @@ def _load_engine(eng: Engine, data, init_f, init_s, init_g, lam, mu, phi, xi, ps
     n_v = eng.n_views
     for v in range(n_v):
         if eng.owned[v]:
-            eng.set_view(v, data[v])
+            if sparse.is_sparse(data[v]):
+                eng.set_view_sparse(v, data[v], pre_processed=True)                                    # (already pre-processed)
+            else:
+                eng.set_view(v, data[v])
         if init_f is None:
             eng.init_svd(v, seed=(0 if seed is None else int(seed)) + v)                          # update_steps.r:78-125
         else:
@@ -95,7 +106,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
     on the host as the reference's ``svd()``, seconds to minutes -- statistically equivalent),
     ``return_init`` (adds ``"init"``: the (F, S, G, lambda, mu) per view the loop started from).
     """
-    data = [np.asarray(d, dtype=np.float64) for d in _as_list(data)]
+    data = _views(data)
     n_v = len(data)
     if k_vec is None:
         raise ValueError("k_vec is required")
@@ -108,6 +119,13 @@ def res_nmtf_inner(data, row_indices, column_indices,
             "pass spurious=False or do it on the R side (INTEGRATION.md).")
     if distance not in _DISTANCES:
         raise ValueError("distance must be one of 'euclidean', 'manhattan' or 'cosine'.")         # utils.r:425
+    is_sp = [sparse.is_sparse(d) for d in data]
+    for v in range(n_v):
+        if is_sp[v]:
+            sparse.validate(data[v], f"view {v}")
+    if any(is_sp) and host_init and (init_f is None or init_g is None or init_s is None):
+        raise NotImplementedError("host_init=True (NumPy's dense SVD) is not available for sparse views; the device "
+                                  "initialisation (host_init=False) works on them")
     phi = np.zeros((n_v, n_v)) if phi is None else np.asarray(phi, dtype=np.float64)
     xi = np.zeros((n_v, n_v)) if xi is None else np.asarray(xi, dtype=np.float64)
     psi = np.zeros((n_v, n_v)) if psi is None else np.asarray(psi, dtype=np.float64)
@@ -129,7 +147,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
         init_f, init_s, init_g = _as_list(init_f), _as_list(init_s), _as_list(init_g)
 
     eng = Engine([d.shape[0] for d in data], [d.shape[1] for d in data], k_vec, device_id=device_id,
-                 **(engine_opts or {}))
+                 **(engine_opts or {}), **({"nnz": [d.nnz if sp else None for d, sp in zip(data, is_sp)]} if any(is_sp) else {}))
     try:
         _load_engine(eng, data, init_f, init_s, init_g, lam, mu, phi, xi, psi,
                      row_names, col_names, row_indices, column_indices, seed=seed)
@@ -213,7 +231,7 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
     _check_stability_numbers(sample_rate, stab_thres)
     if int(n_stability) != n_stability or n_stability < 1:
         raise ValueError("n_stability must be a positive integer.")
-    data = [np.asarray(d, dtype=np.float64) for d in _as_list(data)]
+    data = _views(data)
     n_v = len(data)
     k = int(np.atleast_1d(k)[0])
     seed = 0 if seed is None else int(seed)
@@ -265,7 +283,7 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     always runs with its default ``remove_unstable=True`` (unstable biclusters are zeroed whatever is passed here).
     ``stab_thres`` defaults to 0.4 here, against 0.6 in ``stability_check``.  ``stability=True`` with
     ``spurious=True`` is refused (spurious-bicluster removal is outside the accelerated path)."""
-    data = [np.asarray(d, dtype=np.float64) for d in _as_list(data)]
+    data = _views(data)
     n_v = len(data)
     if k_val is None:
         raise NotImplementedError("the k sweep (R/main.r:279-321) needs the bisilhouette score, which is "

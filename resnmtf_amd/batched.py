@@ -199,24 +199,43 @@ class DeviceData:
 
     def __init__(self, data, phi=None, xi=None, psi=None, row_names=None, col_names=None, device_id: int = 0,
                  pre_processed: bool = False):
-        from . import naming
+        from . import naming, sparse
         from .engine import Engine
-        self.data_shapes = [np.asarray(d).shape for d in data]
+        # sparse views (scipy.sparse) stay sparse: a canonical, pre-processed CSC copy on the host, from which the
+        # sub-samples are gathered, and a sparse view on the device
+        self.sp = [None if not sparse.is_sparse(d) else (sparse.canonical_csc(d) if pre_processed else sparse.check_data_one(d))
+                   for d in data]
+        if pre_processed:
+            for c in self.sp:
+                if c is not None:
+                    sparse.validate(c)
+        data = [d if c is None else c for d, c in zip(data, self.sp)]
+        self.data_shapes = [tuple(d.shape) if c is not None else np.asarray(d).shape for d, c in zip(data, self.sp)]
         n_v = len(data)
-        self.rn, self.cn = naming.give_names([np.asarray(d) for d in data], phi, psi, row_names, col_names)
+        self.rn, self.cn = naming.give_names([d if c is not None else np.asarray(d) for d, c in zip(data, self.sp)], phi, psi,
+                                             row_names, col_names)
         if pre_processed:
             self.phi, self.xi, self.psi = (np.zeros((n_v, n_v)) if m is None else np.asarray(m, dtype=np.float64)
                                            for m in (phi, xi, psi))
         else:
             self.phi = naming.init_rest_mats(phi, n_v); self.xi = naming.init_rest_mats(xi, n_v); self.psi = naming.init_rest_mats(psi, n_v)
         self.device_id = device_id
-        self.base = Engine([s[0] for s in self.data_shapes], [s[1] for s in self.data_shapes], [2] * n_v, device_id=device_id)
+        nnz = [None if c is None else c.nnz for c in self.sp] if any(c is not None for c in self.sp) else None
+        self.base = Engine([s[0] for s in self.data_shapes], [s[1] for s in self.data_shapes], [2] * n_v, device_id=device_id,
+                           nnz=nnz)
         if pre_processed:
             for v in range(n_v):
-                self.base.set_view(v, np.asarray(data[v], dtype=np.float64))
+                if self.sp[v] is not None:
+                    self.base.set_view_sparse(v, self.sp[v], pre_processed=True)
+                else:
+                    self.base.set_view(v, np.asarray(data[v], dtype=np.float64))
             self.was_negative = [False] * n_v
         else:
-            self.was_negative = [self.base.set_view_raw(v, np.asarray(data[v], dtype=np.float64)) for v in range(n_v)]
+            self.was_negative = [False if self.sp[v] is not None else self.base.set_view_raw(v, np.asarray(data[v], dtype=np.float64))
+                                 for v in range(n_v)]
+            for v in range(n_v):
+                if self.sp[v] is not None:
+                    self.base.set_view_sparse(v, self.sp[v], pre_processed=True)      # (normalised on the host: self.sp)
 
     def close(self):
         self.base.close()
@@ -234,12 +253,18 @@ class DeviceData:
             for i in range(n_v):
                 if len(rows[i]) < 2 or len(cols[i]) < 2:
                     return None
-                probe = Engine([len(rows[i])], [len(cols[i])], [2], device_id=self.device_id)
-                try:
-                    probe.subsample_view_from(0, self.base, i, rows[i], cols[i])
-                    er, ec = probe.empty_lines(0)
-                finally:
-                    probe.close()
+                probe = None
+                if self.sp[i] is not None:          # sparse view: the sub-sample is gathered on the host
+                    from . import sparse
+                    _, er, ec = sparse.subsample(self.sp[i], rows[i], cols[i])
+                else:
+                    probe = Engine([len(rows[i])], [len(cols[i])], [2], device_id=self.device_id)
+                if probe is not None:
+                    try:
+                        probe.subsample_view_from(0, self.base, i, rows[i], cols[i])
+                        er, ec = probe.empty_lines(0)
+                    finally:
+                        probe.close()
                 if er.any() or ec.any():
                     changed = True
                     same_r = self.data_shapes[i][0] == self.data_shapes[0][0]
@@ -280,9 +305,18 @@ class DeviceData:
         if samples is not None:
             rn = [[self.rn[v][t] for t in samples[0][v]] for v in range(n_v)]
             cn = [[self.cn[v][t] for t in samples[1][v]] for v in range(n_v)]
-        eng = Engine([s[0] for s in shapes], [s[1] for s in shapes], [k] * n_v, device_id=self.device_id)
+        shuffled = shuffle_seed is not None
+        host_views = [None] * n_v          # sparse views: what is uploaded (the whole view or its sub-sample), gathered on the host
+        if any(c is not None for c in self.sp):
+            if shuffled:
+                raise NotImplementedError("device shuffles of sparse views are not supported")
+            from . import sparse
+            for v in range(n_v):
+                if self.sp[v] is not None:
+                    host_views[v] = self.sp[v] if samples is None else sparse.subsample(self.sp[v], samples[0][v], samples[1][v])[0]
+        nnz = [None if hv is None else hv.nnz for hv in host_views] if any(hv is not None for hv in host_views) else None
+        eng = Engine([s[0] for s in shapes], [s[1] for s in shapes], [k] * n_v, device_id=self.device_id, nnz=nnz)
         try:
-            shuffled = shuffle_seed is not None
             for v in range(n_v):
                 if shuffled:
                     for attempt in range(64):                              # R/obtain_bicl.r:14-18: redraw on an empty row / column
@@ -292,6 +326,8 @@ class DeviceData:
                             break
                     else:
                         raise RuntimeError("shuffle_view: every draw left an all-zero row or column")
+                elif host_views[v] is not None:
+                    eng.set_view_sparse(v, host_views[v], pre_processed=True)      # (sub-samples are not re-normalised)
                 elif samples is not None:
                     eng.subsample_view_from(v, self.base, v, samples[0][v], samples[1][v])
                 else:
@@ -308,7 +344,9 @@ class DeviceData:
                             eng.set_shared_rows(v, w, *naming.index_pairs(rn[v], rn[w], rs[v].get(w)))
                             eng.set_shared_cols(v, w, *naming.index_pairs(cn[v], cn[w], cs[v].get(w)))
             init_state = [eng.get_factors(v) for v in range(n_v)] if return_init else None
-            data_used = [eng.get_view(v) for v in range(n_v)] if return_data else None
+            # (sparse views: the host copy rounded to f32, as the device holds the values)
+            data_used = ([host_views[v].toarray().astype(np.float32).astype(np.float64) if host_views[v] is not None
+                          else eng.get_view(v) for v in range(n_v)] if return_data else None)
             errs = eng.run(n_iters=n_iters, tol=1.0e-6, max_iters=max_iters)
             if relevance:
                 rel = np.stack([eng.relevance(v, self.base, v, samples[0][v], samples[1][v]) for v in range(n_v)])

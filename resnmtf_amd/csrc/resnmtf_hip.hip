@@ -28,6 +28,7 @@
 
 #include "resnmtf_hip.h"
 #include "resnmtf_kernels.hip.inc"
+#include "resnmtf_sparse.hip.inc"
 #include "resnmtf_split_tu.h"
 #ifdef RESNMTF_SPLIT_TU      // product build: the k <= 16 pass lives in resnmtf_pass_k16.hip (its own scheduling strategy)
 #define RESNMTF_EXTERN(NW, UNR, XG, MA) extern template __global__ void pass_kernel<1, NW, UNR, XG, MA, 0>(PassArgs, KKFArgs, KKSArgs);
@@ -97,6 +98,16 @@ struct ViewState {
   KKFArgs argKF{};
   KKSArgs argKS{};
   PassArgs passXG{}, passXtF{};
+  // sparse view (resnmtf_create_sparse): CSC + CSR copies instead of the X32 / Xt32 images, hand-off mode A, the
+  // passes are spmm_kernel launches (resnmtf_sparse.hip.inc); nsplit_xg / nsplit_xtf are set at upload (<= kSparseMaxSplitXg /
+  // kSparseMaxSplitXtf)
+  bool sparse = false;
+  long long nnz_cap = 0, nnz = 0;
+  long long *cp = nullptr, *rp = nullptr;      // CSC column / CSR row pointers
+  int *ri = nullptr, *ci = nullptr;            // CSC row / CSR column indices
+  float *vcsc = nullptr, *vcsr = nullptr;
+  int *blk_xg = nullptr, *blk_xtf = nullptr;   // work blocks of the two passes: first line of each + end, then a form flag per block
+  int nblk_xg = 0, nblk_xtf = 0;
 };
 
 }  // namespace
@@ -222,7 +233,8 @@ void free_view(ViewState& v) {
   if (v.gblk) { v.gblk = nullptr; v.Tsum = nullptr; v.Ma_G = nullptr; v.Md_G = nullptr; v.mu = nullptr; }
   v.sblk = nullptr;
   void* ptrs[] = {v.fuse_cnt, v.Fk, v.Gk, v.X16, v.Xt16, v.X32, v.Xt32, v.xnorm2, v.F, v.G, v.S, v.lambda, v.mu, v.F32, v.G32, v.T32, v.Pxg, v.Pxtf,
-                  v.Paux_xg, v.Paux_xtf, v.cnt_xg, v.cnt_xtf, v.partF, v.partG, v.FtF, v.FtFS, v.cF, v.Ma_F, v.Md_F, v.Ma_G, v.Md_G, v.ref_cl};
+                  v.Paux_xg, v.Paux_xtf, v.cnt_xg, v.cnt_xtf, v.partF, v.partG, v.FtF, v.FtFS, v.cF, v.Ma_F, v.Md_F, v.Ma_G, v.Md_G, v.ref_cl,
+                  v.cp, v.rp, v.ri, v.ci, v.vcsc, v.vcsr, v.blk_xg, v.blk_xtf};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& mp : v.row_map)
@@ -344,6 +356,10 @@ hipError_t set_all_attrs() {
   SLCHAIN_ATTR(48, false, 4); SLCHAIN_ATTR(48, true, 4); SLCHAIN_ATTR(48, false, 8); SLCHAIN_ATTR(48, true, 8);
   SLCHAIN_ATTR(64, false, 4); SLCHAIN_ATTR(64, true, 4); SLCHAIN_ATTR(64, false, 8); SLCHAIN_ATTR(64, true, 8);
 #undef SLCHAIN_ATTR
+#define SPMM_ATTR(KPV) TRY_ATTR(hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_kernel<KPV, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kk_smem_bytes(KPV, 8))); \
+                       TRY_ATTR(hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_kernel<KPV, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kk_smem_bytes(KPV, 8)))
+  SPMM_ATTR(16); SPMM_ATTR(32); SPMM_ATTR(48); SPMM_ATTR(64);
+#undef SPMM_ATTR
 #define CHAIN_ATTR(NVB, PFV) TRY_ATTR(hipFuncSetAttribute(reinterpret_cast<const void*>(&f_chain_kernel<NVB, PFV>), \
                                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)f_chain_smem_bytes<NVB>()))
   CHAIN_ATTR(2, 1); CHAIN_ATTR(4, 1); CHAIN_ATTR(8, 1); CHAIN_ATTR(2, 4); CHAIN_ATTR(4, 4); CHAIN_ATTR(8, 4);
@@ -367,13 +383,52 @@ int pass_blocks_per_cu(int NT, int nw) { return pass_min_blocks(NT, nw); }
 // k <= 16 with the f32 images and 8-wave workgroups, the unrestricted update form (the coupled forms exceed the pass's
 // register budget), and few enough row blocks that every updater is resident among the launch's first workgroups
 bool can_fuse_update(const resnmtf_handle* h, const ViewState& v, int kind) {
-  if (h->opt.fuse_updates == 0 || v.kk_mode != 0 || v.NT != 1 || v.half || !v.fuse_cnt) return false;
+  if (h->opt.fuse_updates == 0 || v.kk_mode != 0 || v.NT != 1 || v.half || v.sparse || !v.fuse_cnt) return false;
   const UpdateArgs& u = kind == 0 ? v.argF : v.argG;
   const PassArgs& p = kind == 0 ? v.passXtF : v.passXG;
   const int nblk = kind == 0 ? v.nblkF : v.nblkG, nw = kind == 0 ? v.nw_xtf : v.nw_xg;
   return nw == 8 && !u.restricted && nblk <= p.ntiles * p.nsplit && nblk <= h->n_cu;
 }
+// sparse view: X.G from the CSR, Xt.F from the CSC (spmm_kernel), same slabs as the dense passes.  kk: the k x k job in
+// workgroup 0 (hand-off mode A, as pass_kernel); otherwise (SVD initialisation) B / P / width come from the caller
+SpmmArgs spmm_args(const ViewState& v, bool xg) {
+  SpmmArgs a{};
+  if (xg) { a.ptr = v.rp; a.idx = v.ci; a.val = v.vcsr; a.blk = v.blk_xg; a.nblk = v.nblk_xg; a.nsplit = v.nsplit_xg; a.B = v.G32; a.P = v.Pxg; a.cols_pad = v.n_pad; }
+  else { a.ptr = v.cp; a.idx = v.ri; a.val = v.vcsc; a.blk = v.blk_xtf; a.nblk = v.nblk_xtf; a.nsplit = v.nsplit_xtf; a.B = v.F32; a.P = v.Pxtf; a.cols_pad = v.m_pad; }
+  a.ldb = v.KP;
+  return a;
+}
+void launch_spmm(resnmtf_handle* h, const SpmmArgs& a, int KP, bool xg, const KKFArgs& kf, const KKSArgs& ks, bool timed_ok) {
+  const dim3 grid((a.kk_block0 ? 1 : 0) + ceil_div(a.nblk * a.nsplit, 8)), block(512);
+  const size_t smem = a.kk_block0 && !a.no_kk ? kk_smem_bytes(KP, 8) : 0;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  const bool timed = timed_ok && take_events(h, xg ? RESNMTF_TIMED_XG : RESNMTF_TIMED_XTF, &ev0, &ev1);
+#define LAUNCH_SPMM(KPV, XG)                                                                                              \
+  if (timed) hipExtLaunchKernelGGL((spmm_kernel<KPV, XG>), grid, block, smem, h->stream, ev0, ev1, 0, a, kf, ks);        \
+  else hipLaunchKernelGGL((spmm_kernel<KPV, XG>), grid, block, smem, h->stream, a, kf, ks)
+#define LAUNCH_SPMM_K(KPV) if (xg) { LAUNCH_SPMM(KPV, true); } else { LAUNCH_SPMM(KPV, false); }
+  switch (KP) {
+    case 16: LAUNCH_SPMM_K(16); break;
+    case 32: LAUNCH_SPMM_K(32); break;
+    case 48: LAUNCH_SPMM_K(48); break;
+    default: LAUNCH_SPMM_K(64); break;
+  }
+#undef LAUNCH_SPMM_K
+#undef LAUNCH_SPMM
+}
+// (The k x k job's dynamic LDS is requested for every workgroup of the launch: at KP >= 48 one workgroup per CU.  Measured,
+// 200000 x 20000 at 0.5 %, k = 64: the Xt.F pass alone runs 632-650 us without that LDS against 846 us with it, but the job
+// as a launch of its own then takes 354 us behind it (the fp64 partials of 512 update workgroups) -- 1004 us in all -- so it
+// stays in workgroup 0, where it overlaps the pass.  DESIGN.md section 10.)
+void launch_pass_sparse(resnmtf_handle* h, const ViewState& v, bool xg, int mode, double tol, bool check_done) {
+  SpmmArgs a = spmm_args(v, xg);
+  a.kk_block0 = 1; a.no_kk = 0; a.ctl = h->ctl; a.check_done = check_done ? 1 : 0;
+  KKSArgs ks = v.argKS;
+  ks.mode = mode; ks.tol = tol;
+  launch_spmm(h, a, v.KP, xg, v.argKF, ks, true);
+}
 void launch_pass(resnmtf_handle* h, const ViewState& v, bool xg, int mode, double tol, bool check_done, bool fuse_update = false) {
+  if (v.sparse) { launch_pass_sparse(h, v, xg, mode, tol, check_done); return; }
   PassArgs a = xg ? v.passXG : v.passXtF;
   a.check_done = check_done ? 1 : 0;
   KKFArgs kf = v.argKF;
@@ -1126,8 +1181,14 @@ const char* resnmtf_last_error(const resnmtf_handle* h) {
   return h ? h->last_error.c_str() : g_create_error.c_str();
 }
 
-int resnmtf_create(int n_views, const int* n_rows, const int* n_cols, const int* k, const int* owned,
-                   const resnmtf_options* opts, resnmtf_handle** out) {
+}  // extern "C"
+namespace {
+// slabs a sparse view's passes may write (the split count is chosen at upload, resnmtf_set_view_csc): at most 4 for X.G keeps
+// the views eligible for the fused F chain (f_chain_kernel keeps up to four raw split slabs per view); Xt.F: 16, the
+// consumer's prefetch depth, as for the dense passes
+constexpr int kSparseMaxSplitXg = 4, kSparseMaxSplitXtf = 16;
+int create_impl(int n_views, const int* n_rows, const int* n_cols, const int* k, const int* owned, const long long* nnz_capacity,
+                const resnmtf_options* opts, resnmtf_handle** out) {
   if (!out) { g_create_error = "out is NULL"; return RESNMTF_ERR_INVALID; }
   *out = nullptr;
   if (n_views < 1 || !n_rows || !n_cols || !k) { g_create_error = "bad view description"; return RESNMTF_ERR_INVALID; }
@@ -1177,6 +1238,14 @@ int resnmtf_create(int n_views, const int* n_rows, const int* n_cols, const int*
         if ((owned[v] != 0) != (v == o.slice_index)) why = "slice_p2p needs exactly one owned view (view index = slice_index)";
     if (why) { g_create_error = why; return RESNMTF_ERR_INVALID; }
   }
+  if (nnz_capacity) {
+    bool any = false;
+    for (int v = 0; v < n_views; ++v) any = any || nnz_capacity[v] >= 0;
+    if (any && (o.replicate_f || o.replicate_gs || o.slice_chains || o.slice_p2p)) {
+      g_create_error = "sparse views are not supported by the view-sharded layouts (replicate_f / replicate_gs / slice_chains / slice_p2p)";
+      return RESNMTF_ERR_INVALID;
+    }
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
     g_create_error = "no HIP device available (this library has no CPU fallback)";
@@ -1214,6 +1283,8 @@ int resnmtf_create(int n_views, const int* n_rows, const int* n_cols, const int*
     vs.ldx = ((size_t)vs.n_pad + pad_rows) * 64; vs.ldxt = ((size_t)vs.m_pad + pad_rows) * 64;
     vs.x32_floats = (size_t)(vs.m_pad / 64) * vs.ldx; vs.xt32_floats = (size_t)(vs.n_pad / 64) * vs.ldxt;
     vs.owned = owned ? owned[v] != 0 : true;
+    vs.sparse = nnz_capacity && nnz_capacity[v] >= 0;
+    vs.nnz_cap = vs.sparse ? nnz_capacity[v] : 0;
     if (!vs.owned) h->all_owned = false;
     else h->last_owned = v;
     vs.row_map.resize(n_views);
@@ -1331,6 +1402,7 @@ int resnmtf_create(int n_views, const int* n_rows, const int* n_cols, const int*
     vs.kk_mode = (vs.KP == 16) ? 0 : 1;
     if (o.kk_mode == 1) vs.kk_mode = 0;
     if (o.kk_mode == 2 || o.slice_chains) vs.kk_mode = 1;      // (sliced chains: the Gram products come from the received f32 copy)
+    if (vs.sparse) vs.kk_mode = 0;                              // (sparse views: mode A at every k, the job in the spmm launch)
     // workgroup slots of a pass launch: target_workgroups overrides CUs x resident workgroups per CU
     const int nw_guess = (vs.NT <= 1 && (o.pass_waves == 4 || o.pass_waves == 8 || o.pass_waves == 16)) ? o.pass_waves : 8;
     const int aux_cap = (vs.NT >= 2 && o.bf16_split != 2) ? 16 : 64;
@@ -1356,6 +1428,7 @@ int resnmtf_create(int n_views, const int* n_rows, const int* n_cols, const int*
     // 40000 x 2000 view 74 -> 67 us.  With everything resident from t = 0 (c2) the plain form is faster.
     vs.pp_xg = vs.NT == 1 && vs.nw_xg == 8 && (vs.n_pad / 64) * vs.nsplit_xg > slots_xg;
     vs.pp_xtf = vs.NT == 1 && vs.nw_xtf == 8 && (vs.m_pad / 64) * vs.nsplit_xtf > slots_xtf;
+    if (vs.sparse) { vs.nsplit_xg = kSparseMaxSplitXg; vs.nsplit_xtf = kSparseMaxSplitXtf; vs.pp_xg = vs.pp_xtf = false; }   // (slab capacity; set at upload)
     const int RG = update_threads(vs.KP) / vs.KP;
     // update workgroups: mode A ~160 (few partials for the k x k job, two prefetched row groups each
     // at c2 -- tools/tune_c2.py); mode B (k > 16) ONE round of resident workgroups -- one 1024-thread workgroup per CU
@@ -1415,9 +1488,19 @@ int resnmtf_create(int n_views, const int* n_rows, const int* n_cols, const int*
     }
     if (!o.replicate_gs && (e = dev_alloc_zero(&vs.mu, (size_t)vs.k)) != hipSuccess) return bail(e, "hipMalloc mu");
     if ((e = dev_alloc_zero(&vs.xnorm2, 1)) != hipSuccess) return bail(e, "hipMalloc xnorm2");
-    if ((e = dev_alloc_zero(&vs.X32, vs.x32_floats)) != hipSuccess) return bail(e, "hipMalloc X32");
-    if ((e = dev_alloc_zero(&vs.Xt32, vs.xt32_floats)) != hipSuccess) return bail(e, "hipMalloc Xt32");
-    vs.half = (o.x_half >= 1 && o.x_half <= 3) && vs.NT == 1 && vs.kk_mode == 0 && vs.nw_xg == 8 && vs.nw_xtf == 8;
+    if (vs.sparse) {                  // CSC + CSR at the declared capacity, no dense image (x_half never applies)
+      const size_t cap = (size_t)std::max<long long>(vs.nnz_cap, 1);
+      if ((e = dev_alloc_zero(&vs.cp, (size_t)vs.m + 1)) != hipSuccess) return bail(e, "hipMalloc CSC pointers");
+      if ((e = dev_alloc_zero(&vs.rp, (size_t)vs.n + 1)) != hipSuccess) return bail(e, "hipMalloc CSR pointers");
+      if ((e = dev_alloc_zero(&vs.ri, cap)) != hipSuccess) return bail(e, "hipMalloc CSC indices");
+      if ((e = dev_alloc_zero(&vs.ci, cap)) != hipSuccess) return bail(e, "hipMalloc CSR indices");
+      if ((e = dev_alloc_zero(&vs.vcsc, cap)) != hipSuccess) return bail(e, "hipMalloc CSC values");
+      if ((e = dev_alloc_zero(&vs.vcsr, cap)) != hipSuccess) return bail(e, "hipMalloc CSR values");
+    } else {
+      if ((e = dev_alloc_zero(&vs.X32, vs.x32_floats)) != hipSuccess) return bail(e, "hipMalloc X32");
+      if ((e = dev_alloc_zero(&vs.Xt32, vs.xt32_floats)) != hipSuccess) return bail(e, "hipMalloc Xt32");
+    }
+    vs.half = !vs.sparse && (o.x_half >= 1 && o.x_half <= 3) && vs.NT == 1 && vs.kk_mode == 0 && vs.nw_xg == 8 && vs.nw_xtf == 8;
     vs.u16 = vs.half && o.x_half >= 2;
     vs.half_capable = vs.half;
     if (vs.half) {      // one spare row group per tile keeps the tile starts off a common power-of-two stride
@@ -1462,6 +1545,22 @@ int resnmtf_create(int n_views, const int* n_rows, const int* n_cols, const int*
   }
   *out = h;
   return RESNMTF_OK;
+}
+}  // namespace
+extern "C" {
+
+int resnmtf_create(int n_views, const int* n_rows, const int* n_cols, const int* k, const int* owned,
+                   const resnmtf_options* opts, resnmtf_handle** out) {
+  return create_impl(n_views, n_rows, n_cols, k, owned, nullptr, opts, out);
+}
+int resnmtf_create_sparse(int n_views, const int* n_rows, const int* n_cols, const int* k, const int* owned,
+                          const long long* nnz_capacity, const resnmtf_options* opts, resnmtf_handle** out) {
+  if (!nnz_capacity) {
+    if (out) *out = nullptr;
+    g_create_error = "nnz_capacity is NULL (use resnmtf_create for dense views only)";
+    return RESNMTF_ERR_INVALID;
+  }
+  return create_impl(n_views, n_rows, n_cols, k, owned, nnz_capacity, opts, out);
 }
 
 int resnmtf_destroy(resnmtf_handle* h) {
@@ -1559,6 +1658,9 @@ int upload_view(resnmtf_handle* h, int v, const double* x, bool raw, int* was_ne
   if (!x && !shuffle_src) return h->fail(RESNMTF_ERR_INVALID, "x is NULL");
   ViewState& vs = h->views[v];
   if (!vs.owned) return h->fail(RESNMTF_ERR_STATE, "set_view on a view this handle does not own");
+  if (vs.sparse)
+    return h->fail(RESNMTF_ERR_INVALID, shuffle_src ? "the destination view is sparse: device-drawn data (shuffle / sub-sample) needs a dense view"
+                                                    : "the view is sparse: upload it with resnmtf_set_view_csc");
   h->resume_ok = false;
   HIP_TRY(h, hipSetDevice(h->opt.device_id));
   if (int rc = sync_both(h)) return rc;
@@ -1630,6 +1732,167 @@ int resnmtf_set_view_raw(resnmtf_handle* h, int v, const double* x_raw, int* was
   return upload_view(h, v, x_raw, true, was_negative);
 }
 
+// ---- sparse views
+namespace {
+// Work blocks of a sparse pass over `lines` output lines with entry pointers ptr.  Every line's entry range is cut into
+// nsplit equal pieces (one slab each) and the lines into contiguous blocks of about equal cost (entries + a per-line
+// overhead); one wave per (block, piece).  Two forms, chosen per block and fixed here (the bits depend on them):
+//   narrow: each group of the wave sums whole lines of the block, side by side (short lines);
+//   wide:   every group of the wave takes a fixed stride of ONE line, then an xor butterfly sums the groups.
+// Every block is wide when the lines are 2 x groups entries or more on average and too few to give every group of every
+// resident wave its own (c2 at 5 %: Xt.F 58 us narrow, 12 us wide; with lines enough narrow is faster: 200000 x 20000 at
+// 0.5 %, X.G 276 against 337 us at k = 16, 866 against 1320 us at k = 64).  Otherwise a line much longer than a block's
+// share -- a dense row or column among sparse ones -- sits in a block of its own, which runs wide, and nsplit grows until
+// one piece of it costs about what a narrow block does: its entries are spread over nsplit waves x all their groups
+// instead of one sequential chain.  blk = [nblk + 1 first lines][nblk form flags, 1 = wide].
+void plan_sparse(const std::vector<long long>& ptr, int lines, int groups, int n_cu, int max_split, int* nsplit, int* nblk,
+                 std::vector<int>& blk) {
+  constexpr long long kLine = 4;                       // per-line cost in entries (pointer loads, slab store)
+  const long long total = ptr[(size_t)lines] + kLine * lines;
+  const long long waves = (long long)n_cu * 16;        // two 8-wave workgroups per CU
+  const bool all_wide = ptr[(size_t)lines] >= 2LL * groups * lines && (long long)lines < waves * groups;
+  long long maxlen = 0;
+  for (int r = 0; r < lines; ++r) maxlen = std::max(maxlen, ptr[(size_t)r + 1] - ptr[(size_t)r]);
+  const int g_eff = all_wide ? 1 : groups;             // (all wide: a wave's time per line is its length / groups either way)
+  // entries per wave if the launch were spread evenly; a wide piece of L entries costs a wave about what a narrow block
+  // of L entries does (both spread over all groups)
+  const long long unit = std::max<long long>(16 * g_eff, (total + waves - 1) / waves);
+  long long ns = all_wide ? (maxlen + 4 * unit - 1) / (4 * unit) : (maxlen + unit - 1) / unit;
+  ns = std::min<long long>(max_split, std::max<long long>(1, ns));
+  *nsplit = (int)ns;
+  const long long target = std::max<long long>(16 * g_eff, (total * ns + waves - 1) / waves);
+  std::vector<int> first(1, 0);
+  long long acc = 0;
+  for (int r = 0; r < lines; ++r) {
+    const long long c = ptr[(size_t)r + 1] - ptr[(size_t)r] + kLine;
+    if (acc > 0 && acc + c > target) { first.push_back(r); acc = 0; }
+    acc += c;
+  }
+  first.push_back(lines);
+  const int nb = (int)first.size() - 1;
+  blk = first;
+  for (int b = 0; b < nb; ++b) {
+    const bool one_long = first[(size_t)b + 1] - first[(size_t)b] == 1 &&
+                          ptr[(size_t)first[(size_t)b] + 1] - ptr[(size_t)first[(size_t)b]] >= 2LL * groups;
+    blk.push_back(all_wide || one_long ? 1 : 0);
+  }
+  *nblk = nb;
+}
+int spmm_groups_host(int KP) { return KP <= 16 ? 16 : (KP <= 32 ? 8 : 4); }   // = spmm_groups (kernel side)
+}  // namespace
+
+int resnmtf_set_view_csc(resnmtf_handle* h, int v, const long long* col_ptr, const int* row_idx, const double* values,
+                         int pre_processed) {
+  if (int rc = check_view(h, v)) return rc;
+  ViewState& vs = h->views[v];
+  if (!vs.sparse) return h->fail(RESNMTF_ERR_INVALID, "the view is dense: upload it with resnmtf_set_view / resnmtf_set_view_raw");
+  if (!vs.owned) return h->fail(RESNMTF_ERR_STATE, "set_view_csc on a view this handle does not own");
+  if (!col_ptr || !row_idx || !values) return h->fail(RESNMTF_ERR_INVALID, "col_ptr / row_idx / values is NULL");
+  const int n = vs.n, m = vs.m;
+  // ---- host checks, before any device work
+  if (col_ptr[0] != 0) return h->fail(RESNMTF_ERR_INVALID, "col_ptr[0] must be 0 (0-based CSC)");
+  for (int j = 0; j < m; ++j)
+    if (col_ptr[j + 1] < col_ptr[j]) return h->fail(RESNMTF_ERR_INVALID, "col_ptr is not monotone (column " + std::to_string(j) + ")");
+  const long long nnz = col_ptr[m];
+  if (nnz > vs.nnz_cap)
+    return h->fail(RESNMTF_ERR_INVALID, "col_ptr[m] = " + std::to_string(nnz) + " exceeds the view's nnz capacity " + std::to_string(vs.nnz_cap));
+  for (int j = 0; j < m; ++j) {
+    double colsum = 0.0;
+    for (long long e = col_ptr[j]; e < col_ptr[j + 1]; ++e) {
+      const int i = row_idx[e];
+      if (i < 0 || i >= n) return h->fail(RESNMTF_ERR_INVALID, "row index out of range in column " + std::to_string(j));
+      if (e > col_ptr[j] && i <= row_idx[e - 1])
+        return h->fail(RESNMTF_ERR_INVALID, "row indices must be strictly increasing within a column (column " + std::to_string(j) + ")");
+      const double x = values[e];
+      if (!std::isfinite(x)) return h->fail(RESNMTF_ERR_INVALID, "non-finite entry in column " + std::to_string(j));
+      if (x < 0.0)
+        return h->fail(RESNMTF_ERR_INVALID, "negative entry in column " + std::to_string(j) +
+                       ": make_non_neg (R/utils.r:20-27) shifts a whole column by its minimum, which would turn every implicit zero of a "
+                       "sparse view positive -- shift the data on the host and upload it dense");
+      colsum += x;
+    }
+    if (!pre_processed && !(colsum > 0.0))
+      return h->fail(RESNMTF_ERR_INVALID, "column " + std::to_string(j) +
+                     " is all zero: matrix_normalisation (R/utils.r:86-88) would divide it by zero (a NaN column in the reference)");
+  }
+  h->resume_ok = false;
+  HIP_TRY(h, hipSetDevice(h->opt.device_id));
+  if (int rc = sync_both(h)) return rc;
+  // ---- CSR structure on the host: entries of a row in ascending column order (columns are walked in order)
+  std::vector<long long> cp(col_ptr, col_ptr + (size_t)m + 1), rp((size_t)n + 1, 0), perm((size_t)nnz);
+  std::vector<int> ci((size_t)nnz);
+  for (long long e = 0; e < nnz; ++e) ++rp[(size_t)row_idx[e] + 1];
+  for (int i = 0; i < n; ++i) rp[(size_t)i + 1] += rp[(size_t)i];
+  {
+    std::vector<long long> next(rp.begin(), rp.end() - 1);
+    for (int j = 0; j < m; ++j)
+      for (long long e = cp[(size_t)j]; e < cp[(size_t)j + 1]; ++e) {
+        const long long p = next[(size_t)row_idx[e]]++;
+        ci[(size_t)p] = j; perm[(size_t)p] = e;
+      }
+  }
+  std::vector<int> bxg, bxtf;
+  int ns_xg = 1, ns_xtf = 1, nb_xg = 0, nb_xtf = 0;
+  const int groups = spmm_groups_host(vs.KP);
+  plan_sparse(rp, n, groups, h->n_cu, kSparseMaxSplitXg, &ns_xg, &nb_xg, bxg);
+  plan_sparse(cp, m, groups, h->n_cu, kSparseMaxSplitXtf, &ns_xtf, &nb_xtf, bxtf);
+  // ---- device
+  double* v64 = nullptr;
+  long long* dperm = nullptr;
+  double* sq = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&v64), std::max<size_t>((size_t)nnz, 1) * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dperm), std::max<size_t>((size_t)nnz, 1) * sizeof(long long));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sq), (size_t)m * sizeof(double));
+  if (e == hipSuccess && (nb_xg != vs.nblk_xg || !vs.blk_xg)) {
+    if (vs.blk_xg) (void)hipFree(vs.blk_xg);
+    vs.blk_xg = nullptr;
+    e = hipMalloc(reinterpret_cast<void**>(&vs.blk_xg), bxg.size() * sizeof(int));
+  }
+  if (e == hipSuccess && (nb_xtf != vs.nblk_xtf || !vs.blk_xtf)) {
+    if (vs.blk_xtf) (void)hipFree(vs.blk_xtf);
+    vs.blk_xtf = nullptr;
+    e = hipMalloc(reinterpret_cast<void**>(&vs.blk_xtf), bxtf.size() * sizeof(int));
+  }
+  auto up = [&](void* dst, const void* src, size_t bytes) {
+    if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
+  };
+  up(vs.cp, cp.data(), cp.size() * sizeof(long long));
+  up(vs.rp, rp.data(), rp.size() * sizeof(long long));
+  up(vs.ri, row_idx, (size_t)nnz * sizeof(int));
+  up(vs.ci, ci.data(), ci.size() * sizeof(int));
+  up(v64, values, (size_t)nnz * sizeof(double));
+  up(dperm, perm.data(), perm.size() * sizeof(long long));
+  up(vs.blk_xg, bxg.data(), bxg.size() * sizeof(int));
+  up(vs.blk_xtf, bxtf.data(), bxtf.size() * sizeof(int));
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(csc_normalise_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, h->stream, vs.cp, v64, m, pre_processed ? 0 : 1,
+                       vs.vcsc, sq);
+    if (nnz > 0)
+      hipLaunchKernelGGL(csr_gather_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, h->stream, dperm, vs.vcsc, nnz, vs.vcsr);
+    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, h->stream, sq, m, vs.xnorm2);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);      // (host vectors go out of scope)
+  (void)hipFree(v64); (void)hipFree(dperm); (void)hipFree(sq);
+  if (e != hipSuccess) return h->fail_hip("set_view_csc", e);
+  vs.nnz = nnz;
+  vs.nblk_xg = nb_xg; vs.nblk_xtf = nb_xtf;
+  vs.nsplit_xg = ns_xg; vs.nsplit_xtf = ns_xtf;
+  vs.empty_rows = vs.empty_cols = 0; vs.empty_mask.clear();
+  vs.has_x = true;
+  h->prepared = false;          // the slab count of the updates follows the upload
+  return RESNMTF_OK;
+}
+
+int resnmtf_view_storage(resnmtf_handle* h, int v, int* is_sparse, long long* nnz, long long* nnz_capacity) {
+  if (int rc = check_view(h, v)) return rc;
+  const ViewState& vs = h->views[v];
+  if (is_sparse) *is_sparse = vs.sparse ? 1 : 0;
+  if (nnz) *nnz = vs.sparse ? vs.nnz : 0;
+  if (nnz_capacity) *nnz_capacity = vs.sparse ? vs.nnz_cap : -1;
+  return RESNMTF_OK;
+}
+
 // ---- view data without a host round trip (the k sweep re-uses one upload, the shuffles of
 // spurious-bicluster removal are drawn on the device)
 static int check_view_pair(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src) {
@@ -1638,6 +1901,7 @@ static int check_view_pair(resnmtf_handle* dst, int v, resnmtf_handle* src, int 
   const ViewState& a = dst->views[v];
   const ViewState& b = src->views[v_src];
   if (!a.owned || !b.owned || !b.has_x) return dst->fail(RESNMTF_ERR_STATE, "both views must be owned and the source uploaded");
+  if (a.sparse || b.sparse) return dst->fail(RESNMTF_ERR_INVALID, "copy / shuffle of a sparse view is not supported (it would densify it)");
   if (a.n != b.n || a.m != b.m) return dst->fail(RESNMTF_ERR_INVALID, "views differ in shape");
   if (dst->opt.device_id != src->opt.device_id) return dst->fail(RESNMTF_ERR_INVALID, "handles live on different devices");
   return RESNMTF_OK;
@@ -1677,6 +1941,7 @@ int resnmtf_subsample_view(resnmtf_handle* dst, int v, resnmtf_handle* src, int 
   if (!rows || !cols) return dst->fail(RESNMTF_ERR_INVALID, "rows / cols are NULL");
   const ViewState& a = dst->views[v];
   const ViewState& b = src->views[v_src];
+  if (a.sparse || b.sparse) return dst->fail(RESNMTF_ERR_INVALID, "sub-samples of / into a sparse view are gathered on the host (resnmtf_set_view_csc with pre_processed = 1)");
   if (!a.owned || !b.owned || !b.has_x) return dst->fail(RESNMTF_ERR_STATE, "both views must be owned and the source uploaded");
   if (dst->opt.device_id != src->opt.device_id) return dst->fail(RESNMTF_ERR_INVALID, "handles live on different devices");
   for (int r = 0; r < a.n; ++r) if (rows[r] < 0 || rows[r] >= b.n) return dst->fail(RESNMTF_ERR_INVALID, "row index out of range");
@@ -1710,6 +1975,7 @@ int resnmtf_get_view(resnmtf_handle* h, int v, double* x) {
   if (int rc = check_view(h, v)) return rc;
   if (!x) return h->fail(RESNMTF_ERR_INVALID, "x is NULL");
   const ViewState& vs = h->views[v];
+  if (vs.sparse) return h->fail(RESNMTF_ERR_INVALID, "get_view of a sparse view is not supported (it would densify it)");
   if (!vs.owned || !vs.has_x) return h->fail(RESNMTF_ERR_STATE, "no data on this handle for the view");
   HIP_TRY(h, hipSetDevice(h->opt.device_id));
   if (int rc = sync_both(h)) return rc;
@@ -1925,8 +2191,13 @@ int init_svd_thin(resnmtf_handle* h, int v, double sigma, std::mt19937_64& gen, 
       (e = alloc(&sc.gpart, (size_t)(kGramBlocks + 1) * r * r)) != hipSuccess || (e = alloc(&sc.gram, (size_t)r * r)) != hipSuccess ||
       (e = alloc(&sc.M, (size_t)r * r)) != hipSuccess)
     return h->fail_hip("init_svd hipMalloc", e);
-  hipLaunchKernelGGL(widen_rows_kernel, dim3(ceil_div(len * r, 256)), dim3(256), 0, h->stream, tall ? vs.X32 : vs.Xt32,
-                     tall ? vs.ldx : vs.ldxt, len, r, sc.Yn);
+  if (vs.sparse) {      // the short side from the CSR (Y = X) or the CSC (Y = X^T)
+    HIP_TRY(h, hipMemsetAsync(sc.Yn, 0, (size_t)len * r * sizeof(double), h->stream));
+    hipLaunchKernelGGL(sparse_widen_kernel, dim3(ceil_div(len, 256)), dim3(256), 0, h->stream, tall ? vs.rp : vs.cp, tall ? vs.ci : vs.ri,
+                       tall ? vs.vcsr : vs.vcsc, len, r, sc.Yn);
+  } else
+    hipLaunchKernelGGL(widen_rows_kernel, dim3(ceil_div(len * r, 256)), dim3(256), 0, h->stream, tall ? vs.X32 : vs.Xt32,
+                       tall ? vs.ldx : vs.ldxt, len, r, sc.Yn);
   HIP_TRY(h, hipGetLastError());
   std::vector<double> C, W;
   if (int rc = ts_gram_host(h, sc, sc.Yn, len, r, C)) return rc;
@@ -1999,12 +2270,20 @@ int resnmtf_init_svd(resnmtf_handle* h, int v, unsigned long long seed, double s
   HIP_TRY(h, hipMemsetAsync(vs.G32, 0, (size_t)vs.m_pad * 64 * sizeof(float), h->stream));
   hipLaunchKernelGGL(factor_to_f32_kernel, dim3(ceil_div(m * L, 256)), dim3(256), 0, h->stream, sc.Zm, m, L, vs.G32, 64, NTi, 0, (unsigned short*)nullptr);
   HIP_TRY(h, hipStreamSynchronize(h->stream));
+  // sparse view: the same products from the CSR / CSC (spmm_kernel without a k x k job), the same slabs
+  SpmmArgs sxg = spmm_args(vs, true), sxt = spmm_args(vs, false);
+  sxg.B = vs.G32; sxg.ldb = 64; sxg.P = sc.Pn; sxg.ctl = h->ctl;
+  sxt.B = vs.F32; sxt.ldb = 64; sxt.P = sc.Pm; sxt.ctl = h->ctl;
+  auto product = [&](bool is_xg) {
+    if (!vs.sparse) launch_pass_plain(h, is_xg ? xg : xt, NTi, is_xg);
+    else launch_spmm(h, is_xg ? sxg : sxt, L, is_xg, KKFArgs{}, KKSArgs{}, false);
+  };
   for (int it = 0; it < n_power; ++it) {
-    launch_pass_plain(h, xg, NTi, true);                                                   // Y = X Z
+    product(true);                                                                         // Y = X Z
     hipLaunchKernelGGL(slab_sum_kernel, dim3(ceil_div(n * L, 256)), dim3(256), 0, h->stream, sc.Pn, vs.nsplit_xg, vs.n_pad, L, n, sc.Yn);
     HIP_TRY(h, hipGetLastError());
     if (int rc = orthonormalise(h, sc, sc.Yn, sc.Yn2, n, L, vs.F32, NTi)) return rc;          // Q (in Yn) + F32
-    launch_pass_plain(h, xt, NTi, false);                                                  // Z = X^T Q
+    product(false);                                                                        // Z = X^T Q
     hipLaunchKernelGGL(slab_sum_kernel, dim3(ceil_div(m * L, 256)), dim3(256), 0, h->stream, sc.Pm, vs.nsplit_xtf, vs.m_pad, L, m, sc.Zm);
     HIP_TRY(h, hipGetLastError());
     if (it + 1 < n_power)
@@ -3139,6 +3418,12 @@ int resnmtf_pass_timings(resnmtf_handle* h, resnmtf_pass_timing* out, int reset)
     out->xtf_bytes = sx * n * m + 4.0 * (n + m) * k + (can_fuse_update(h, v, 0) && h->all_owned && h->chain_views == 0 ? 24.0 * n * k : 0.0);
     out->xg_flops = 2.0 * n * m * k;
     out->xtf_flops = 2.0 * n * m * k;
+    if (v.sparse) {      // values + indices + pointers + gathered factor rows (f32, KP wide) + slabs written
+      const double z = (double)v.nnz, kp = v.KP;
+      out->xg_bytes = 8.0 * z + 8.0 * (n + 1) + 4.0 * kp * z + 4.0 * kp * n * v.nsplit_xg;
+      out->xtf_bytes = 8.0 * z + 8.0 * (m + 1) + 4.0 * kp * z + 4.0 * kp * m * v.nsplit_xtf;
+      out->xg_flops = out->xtf_flops = 2.0 * z * k;
+    }
     break;
   }
   if (reset) h->timing = resnmtf_pass_timing{};

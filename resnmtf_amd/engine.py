@@ -42,7 +42,10 @@ class Engine:
                  pass_splits_xtf: int = 0, pass_lds_pad_kb: int = 0, update_blocks: int = 0, no_pitch_pad: bool = False,
                  kk_mode: int = 0, bf16_split: int = 0, replicate_f: bool = False, no_f_chain: bool = False,
                  x_half: int = 0, half_unroll: int = 0, replicate_gs: bool = False, wait_mode: int = 0,
-                 slice_chains: bool = False, slice_index: int = 0, slice_count: int = 0, fuse_updates: int = 0, slice_p2p: bool = False, xcd_order: bool = False):
+                 slice_chains: bool = False, slice_index: int = 0, slice_count: int = 0, fuse_updates: int = 0, slice_p2p: bool = False, xcd_order: bool = False,
+                 nnz: Optional[Sequence[Optional[int]]] = None):
+        """``nnz``: per view None (dense) or the number of stored entries a sparse view may hold
+        (``resnmtf_create_sparse``; upload with ``set_view_sparse``)."""
         self._lib = _lib.load()
         self.n_views = len(n_rows)
         self.n_rows = [int(x) for x in n_rows]
@@ -82,8 +85,16 @@ class Engine:
         kk = np.asarray(self.k, dtype=np.int32)
         ow = np.asarray([1 if o else 0 for o in self.owned], dtype=np.int32)
         self._h = C.c_void_p()
-        rc = self._lib.resnmtf_create(self.n_views, _ip(nr), _ip(nc), _ip(kk), _ip(ow), C.byref(opts),
-                                      C.byref(self._h))
+        self.sparse = [False] * self.n_views if nnz is None else [x is not None and int(x) >= 0 for x in nnz]
+        if any(self.sparse):
+            if len(nnz) != self.n_views:
+                raise ValueError("nnz must have one entry per view")
+            cap = np.asarray([int(x) if s else -1 for x, s in zip(nnz, self.sparse)], dtype=np.int64)
+            rc = self._lib.resnmtf_create_sparse(self.n_views, _ip(nr), _ip(nc), _ip(kk), _ip(ow),
+                                                 cap.ctypes.data_as(C.POINTER(C.c_longlong)), C.byref(opts), C.byref(self._h))
+        else:
+            rc = self._lib.resnmtf_create(self.n_views, _ip(nr), _ip(nc), _ip(kk), _ip(ow), C.byref(opts),
+                                          C.byref(self._h))
         if rc != _lib.OK:
             text = self._lib.resnmtf_last_error(None)
             self._h = None
@@ -126,6 +137,29 @@ class Engine:
         neg = C.c_int(0)
         self._check(self._lib.resnmtf_set_view_raw(self._h, v, _dp(x), C.byref(neg)))
         return bool(neg.value)
+
+    def set_view_sparse(self, v: int, m, pre_processed: bool = False):
+        """Upload a sparse view (``scipy.sparse``, any format; a canonical CSC copy is made, ``m`` is not modified) as
+        0-based CSC (``resnmtf_set_view_csc``).  ``pre_processed=False``: the column normalisation of ``check_inputs``
+        (``R/utils.r:86-88``) runs on the device -- negative entries and all-zero columns are refused; ``True``: the
+        values are taken as given (the sub-samples of stability selection)."""
+        from . import sparse
+        c = sparse.canonical_csc(m)
+        if tuple(c.shape) != (self.n_rows[v], self.n_cols[v]):
+            raise ValueError(f"expected shape {(self.n_rows[v], self.n_cols[v])}, got {tuple(c.shape)}")
+        col_ptr = np.ascontiguousarray(c.indptr, dtype=np.int64)
+        row_idx = np.ascontiguousarray(c.indices, dtype=np.int32)
+        vals = np.ascontiguousarray(c.data, dtype=np.float64)
+        if row_idx.size == 0:               # (never a NULL pointer)
+            row_idx = np.zeros(1, dtype=np.int32); vals = np.zeros(1)
+        self._check(self._lib.resnmtf_set_view_csc(self._h, v, col_ptr.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                                   _ip(row_idx), _dp(vals), 1 if pre_processed else 0))
+
+    def view_storage(self, v: int):
+        """(is_sparse, nnz of the last upload, nnz capacity) of view ``v`` (``resnmtf_view_storage``)."""
+        sp, nz, cap = C.c_int(0), C.c_longlong(0), C.c_longlong(0)
+        self._check(self._lib.resnmtf_view_storage(self._h, v, C.byref(sp), C.byref(nz), C.byref(cap)))
+        return bool(sp.value), int(nz.value), int(cap.value)
 
     def copy_view_from(self, v: int, other: "Engine", v_src: int = 0):
         """Device copy of a view another engine (same GPU, same shape) has uploaded."""

@@ -37,6 +37,10 @@ def check_data(data: Sequence[np.ndarray]) -> List[np.ndarray]:
     followed by ``matrix_normalisation`` (``R/utils.r:86-88``)."""
     out = []
     for x in data:
+        if type(x).__module__.startswith("scipy.sparse"):   # sparse view: refused negatives / zero columns, stays sparse
+            from . import sparse
+            out.append(sparse.check_data_one(x))
+            continue
         x = np.asarray(x, dtype=np.float64)
         if x.ndim != 2:
             raise ValueError("Data must be a list of matrices or a matrix.")               # utils.r:317

@@ -945,6 +945,9 @@ def res_nmtf_inner(data, row_indices=None, column_indices=None, init_f=None, ini
     data = list(data)
     if len(data) != n_v:
         raise ValueError("data must have one entry per view (None for views this rank does not own)")
+    if any(d is not None and type(d).__module__.startswith("scipy.sparse") for d in data):
+        raise NotImplementedError("sparse views are not supported by the view-sharded driver; use api.res_nmtf_inner "
+                                  "on one GPU (resnmtf_create_sparse)")
     k_all = [int(np.asarray(f).shape[1]) for f in init_f]
     if k_vec is not None and [int(k) for k in np.atleast_1d(k_vec)] != k_all:
         raise ValueError("k_vec does not match the initial factors")
