@@ -426,6 +426,23 @@ int resnmtf_set_reference_clusters(resnmtf_handle* h, int v, int k, const double
 int resnmtf_relevance(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, const int* rows, const int* cols,
                       double* relevance);
 
+/*
+ * Spurious-bicluster scoring (check_biclusters / get_thresholds, R/obtain_bicl.r:55-133): jsd_calc (R/utils.r:95-106)
+ * for a list of column pairs, replacing the R loops
+ *     scores <- c(scores, jsd_calc(x1, x2))                        (calculate_f_shuffle_jsd, :55-68)
+ *     scores[i, k] <- mean(apply(x_noise, 2, function(y) jsd_calc(x, y)))   (check_biclusters, :125-128)
+ * cols: n_cols columns of length n, fp64 column-major (an R matrix, e.g. cbind(F_i, f_1[[i]], ..., f_R[[i]]));
+ * pairs: n_pairs (x1, x2) 0-based column indices, interleaved; out[p] = jsd_calc(cols[, x1] , cols[, x2]):
+ * philentropy::JSD(unit = "log2", est.prob = "empirical") of stats::density(c, from = 0, to = max(x1, x2)) of both
+ * sides, n = 512, bw.nrd0 bandwidths, R <= 4.3's density coordinates (old.coords = TRUE), zero beyond max(c).  fp64
+ * throughout; bitwise reproducible, and a pair's value depends on its two columns only (not on the other pairs, their
+ * order or n_cols).  A density that sums to zero gives NaN, as in R.  No handle: the call selects device_id, uploads,
+ * computes and returns (blocking); resnmtf_last_error(NULL) describes a failure.  Refused before any launch
+ * (RESNMTF_ERR_INVALID): n < 2, n_cols outside [1, 65535], n_pairs < 0, NULL pointers, a non-finite entry of cols, a
+ * pair index outside [0, n_cols), n * n_cols > 2^31; n_pairs = 0 returns at once.  DESIGN.md section 11.
+ */
+int resnmtf_jsd_pairs(int device_id, int n, int n_cols, const double* cols, int n_pairs, const int* pairs, double* out);
+
 /* ---- phase-level entry points (views sharded one-per-GPU; host does the exchange) ---- */
 
 /* Which image of X the streaming passes of view v use after its upload: *uses_2byte = 0 (f32 images), 1 (fp16) or

@@ -110,3 +110,27 @@ SEXP resnmtf_hip_inner(SEXP data, SEXP init_f, SEXP init_s, SEXP init_g, SEXP ph
   UNPROTECT(9);
   return out;
 }
+
+/*
+ * jsd_calc (R/utils.r:95-106) for a list of column pairs: cols a double matrix (e.g. cbind(F_i, f_1[[i]], ...)),
+ * pairs an integer 2-column matrix of 1-based column indices; returns one score per row of pairs
+ * (resnmtf_jsd_pairs; no handle).
+ */
+SEXP resnmtf_hip_jsd_pairs(SEXP cols, SEXP pairs, SEXP device_id_) {
+  SEXP dims = getAttrib(cols, R_DimSymbol), pdims = getAttrib(pairs, R_DimSymbol);
+  if (!isReal(cols) || length(dims) != 2) error("cols must be a double matrix");
+  if (!isInteger(pairs) || length(pdims) != 2 || INTEGER(pdims)[1] != 2) error("pairs must be an integer 2-column matrix");
+  const int n = INTEGER(dims)[0], n_cols = INTEGER(dims)[1], n_pairs = INTEGER(pdims)[0];
+  int* idx = (int*)R_alloc(2 * (size_t)n_pairs, sizeof(int));
+  for (int p = 0; p < n_pairs; ++p) {                 /* R's column-major 2-column matrix -> interleaved, 0-based */
+    idx[2 * p] = INTEGER(pairs)[p] - 1;
+    idx[2 * p + 1] = INTEGER(pairs)[n_pairs + p] - 1;
+  }
+  SEXP out = PROTECT(allocVector(REALSXP, n_pairs));
+  if (resnmtf_jsd_pairs(asInteger(device_id_), n, n_cols, REAL(cols), n_pairs, idx, REAL(out))) {
+    UNPROTECT(1);
+    fail(NULL, "resnmtf_jsd_pairs");
+  }
+  UNPROTECT(1);
+  return out;
+}

@@ -86,6 +86,7 @@ SIGNATURES = {
     "resnmtf_finalise": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "resnmtf_set_reference_clusters": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp]),
     "resnmtf_relevance": (C.c_int, [_h, C.c_int, _h, C.c_int, _ip, _ip, _dp]),
+    "resnmtf_jsd_pairs": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, _ip, _dp]),
     "resnmtf_reserve_sweeps": (C.c_int, [_h, C.c_int]),
     "resnmtf_prepare": (C.c_int, [_h]),
     "resnmtf_phase": (C.c_int, [_h, C.c_int, C.c_int, C.c_int]),

@@ -9,10 +9,13 @@ in INTEGRATION.md.
 Stability selection (``stability_check``, ``R/stability_analysis.r:302-338``) runs here too: the sub-samples are
 gathered, factorised and scored (relevance) on the device, see ``stability_check``.
 
-Deliberately NOT implemented here (out of scope): spurious-bicluster
-removal, the bisilhouette score and the k sweep -- they are statistics on top of finished
-factorisations and stay on the R side.  Requests for them raise ``NotImplementedError``
-instead of silently doing something else.
+Spurious-bicluster removal is a separate post-step on a finished result (``check_biclusters`` /
+``remove_spurious``, from ``spurious.py``): the shuffled factorisations and the Jensen-Shannon scores run on the
+device.  The ``spurious=True`` flags of the entry points below still raise ``NotImplementedError``.
+
+Deliberately NOT implemented here (out of scope): the bisilhouette score and
+the k sweep -- they are statistics on top of finished factorisations and stay on the R side.
+Requests for them raise ``NotImplementedError`` instead of silently doing something else.
 """
 from __future__ import annotations
 
@@ -23,6 +26,7 @@ import numpy as np
 
 from . import naming, sparse
 from .engine import Engine
+from .spurious import check_biclusters, remove_spurious  # noqa: F401  (post-steps, R/obtain_bicl.r:113-188)
 
 _DISTANCES = ("euclidean", "manhattan", "cosine")
 

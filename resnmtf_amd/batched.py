@@ -382,11 +382,13 @@ def k_sweep_on_device(dev: DeviceData, k_min: int = 3, k_max: int = 8, n_iters=N
     return run_jobs(ks, group=group, runner=lambda k: dev.factorise(k, n_iters, seed + k, tag=f"k={k}"))
 
 
-def shuffles_on_device(dev: DeviceData, n_clusts: int, num_repeats: int = 5, n_iters=None, seed: int = 0, group=None) -> List[dict]:
+def shuffles_on_device(dev: DeviceData, n_clusts: int, num_repeats: int = 5, n_iters=None, seed: int = 0, group=None,
+                       max_iters: int = 100000) -> List[dict]:
     """``obtain_shuffled_f`` (``R/obtain_bicl.r:31-42``) with the shuffles drawn on the device."""
     reps = list(range(num_repeats))
     return run_jobs(reps, group=group,
-                    runner=lambda r: dev.factorise(n_clusts, n_iters, seed + 1000 + r, shuffle_seed=seed * 7919 + r + 1, tag=f"shuffle={r}"))
+                    runner=lambda r: dev.factorise(n_clusts, n_iters, seed + 1000 + r, shuffle_seed=seed * 7919 + r + 1,
+                                                   max_iters=max_iters, tag=f"shuffle={r}"))
 
 
 def stability_on_device(dev: DeviceData, k: int, n_stability: int = 5, sample_rate: float = 0.9, n_iters=None, seed: int = 0,

@@ -29,6 +29,7 @@
 #include "resnmtf_hip.h"
 #include "resnmtf_kernels.hip.inc"
 #include "resnmtf_sparse.hip.inc"
+#include "resnmtf_jsd.hip.inc"
 #include "resnmtf_split_tu.h"
 #ifdef RESNMTF_SPLIT_TU      // product build: the k <= 16 pass lives in resnmtf_pass_k16.hip (its own scheduling strategy)
 #define RESNMTF_EXTERN(NW, UNR, XG, MA) extern template __global__ void pass_kernel<1, NW, UNR, XG, MA, 0>(PassArgs, KKFArgs, KKSArgs);
@@ -3106,6 +3107,62 @@ int resnmtf_relevance(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, 
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   (void)hipFree(buf);
   if (e != hipSuccess) return h->fail_hip("relevance", e);
+  return RESNMTF_OK;
+}
+
+int resnmtf_jsd_pairs(int device_id, int n, int n_cols, const double* cols, int n_pairs, const int* pairs, double* out) {
+  auto bad = [](const char* msg) { g_create_error = msg; return RESNMTF_ERR_INVALID; };
+  if (n < 2) return bad("n must be at least 2 (bw.nrd0 needs two data points)");
+  if (n_cols < 1 || n_cols > 65535 || n_pairs < 0) return bad("n_cols must be in [1, 65535] and n_pairs non-negative");
+  if (!cols || !pairs || !out) return bad("cols / pairs / out are NULL");
+  if ((size_t)n * (size_t)n_cols > ((size_t)1 << 31)) return bad("n * n_cols exceeds 2^31 entries");
+  const size_t total = (size_t)n * n_cols;
+  for (size_t i = 0; i < total; ++i)
+    if (!std::isfinite(cols[i])) return bad("cols has a non-finite entry");
+  for (int p = 0; p < 2 * n_pairs; ++p)
+    if (pairs[p] < 0 || pairs[p] >= n_cols) return bad("pair index out of range");
+  if (n_pairs == 0) return RESNMTF_OK;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_error = "no HIP device"; return RESNMTF_ERR_NO_DEVICE; }
+  if (device_id < 0 || device_id >= ndev) return bad("device_id out of range");
+  hipError_t e = hipSetDevice(device_id);
+  if (e != hipSuccess) { g_create_error = std::string("hipSetDevice: ") + hipGetErrorString(e); return RESNMTF_ERR_HIP; }
+  hipStream_t st = nullptr;
+  e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+  if (e != hipSuccess) { g_create_error = std::string("hipStreamCreate: ") + hipGetErrorString(e); return RESNMTF_ERR_HIP; }
+  // [orig n C][sort A n C][sort B n C][stats 2 C][out P] doubles | [pairs 2 P] ints
+  const size_t n_dbl = 3 * total + 2 * (size_t)n_cols + (size_t)n_pairs;
+  char* buf = nullptr;
+  e = hipMalloc(reinterpret_cast<void**>(&buf), n_dbl * sizeof(double) + 2 * (size_t)n_pairs * sizeof(int));
+  if (e != hipSuccess) {
+    (void)hipStreamDestroy(st);
+    g_create_error = std::string("jsd_pairs: ") + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? RESNMTF_ERR_ALLOC : RESNMTF_ERR_HIP;
+  }
+  double *orig = reinterpret_cast<double*>(buf), *sa = orig + total, *sb = sa + total, *stats = sb + total;
+  double* dout = stats + 2 * (size_t)n_cols;
+  int* dpairs = reinterpret_cast<int*>(buf + n_dbl * sizeof(double));
+  e = hipMemcpyAsync(orig, cols, total * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(dpairs, pairs, 2 * (size_t)n_pairs * sizeof(int), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(jsd_tile_sort_kernel, dim3(ceil_div(n, JSD_TILE), n_cols), dim3(JSD_SORT_THREADS), 0, st,
+                       (const double*)orig, sa, n);
+    double *src = sa, *dst = sb;
+    for (int width = JSD_TILE; width < n; width *= 2) {
+      hipLaunchKernelGGL(jsd_merge_kernel, dim3(ceil_div(n, 256), n_cols), dim3(256), 0, st, (const double*)src, dst, n, width);
+      std::swap(src, dst);
+    }
+    hipLaunchKernelGGL(jsd_stats_kernel, dim3(n_cols), dim3(256), 0, st, (const double*)src, (const double*)orig, n, stats);
+    for (int p0 = 0; p0 < n_pairs; p0 += 1 << 20)              // (grids of at most 2^20 workgroups)
+      hipLaunchKernelGGL(jsd_pair_kernel, dim3(std::min(1 << 20, n_pairs - p0)), dim3(JSD_N), 0, st, (const double*)src,
+                         (const double*)stats, n, (const int*)(dpairs + 2 * (size_t)p0), dout + p0);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t)n_pairs * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(buf);
+  (void)hipStreamDestroy(st);
+  if (e != hipSuccess) { g_create_error = std::string("jsd_pairs: ") + hipGetErrorString(e); return RESNMTF_ERR_HIP; }
   return RESNMTF_OK;
 }
 

@@ -34,6 +34,22 @@ def device_count() -> int:
     return int(_lib.load().resnmtf_device_count())
 
 
+def jsd_pairs(cols, pairs, device_id: int = 0) -> np.ndarray:
+    """``jsd_calc`` (``R/utils.r:95-106``) of every column pair on the device (``resnmtf_jsd_pairs``, no handle):
+    ``cols`` n x C (fp64, taken column-major), ``pairs`` P x 2 0-based column indices; returns P scores."""
+    lib = _lib.load()
+    cols = _f64_colmajor(cols)
+    if cols.ndim != 2:
+        raise ValueError("cols must be an n x C matrix")
+    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    out = np.zeros(len(pairs), dtype=np.float64)
+    rc = lib.resnmtf_jsd_pairs(int(device_id), int(cols.shape[0]), int(cols.shape[1]), _dp(cols), int(len(pairs)),
+                               _ip(pairs), _dp(out))
+    if rc != _lib.OK:
+        raise ResnmtfError(rc, (lib.resnmtf_last_error(None) or b"").decode())
+    return out
+
+
 class Engine:
     def __init__(self, n_rows: Sequence[int], n_cols: Sequence[int], k: Sequence[int],
                  owned: Optional[Sequence[bool]] = None, device_id: int = 0, stream: int = 0,

@@ -1,0 +1,212 @@
+"""Spurious-bicluster removal (``obtain_biclusters(..., remove_spurious = TRUE)``, ``R/obtain_bicl.r:151-204``) as a
+post-step on a finished ``res_nmtf_inner`` / ``apply_resnmtf`` result, in the way ``stability_check`` is one for
+stability selection:
+
+1. ``num_repeats`` factorisations of shuffled views (``obtain_shuffled_f``, ``:31-42``) on the device
+   (``batched.shuffles_on_device``; sharded over the ranks of an initialised process group);
+2. per view, the Jensen-Shannon scores (``jsd_calc``, ``R/utils.r:95-106``) of the shuffled F columns against each
+   other (``get_thresholds``, ``:80-102``) and of the result's F columns against them (``check_biclusters``,
+   ``:113-133``), all on the device in one ``resnmtf_jsd_pairs`` call;
+3. on the host: the mean, the mode of ``stats::density`` of the null scores (``density_mode``), the means of the scores
+   and the removal rule (``:176-188``).
+
+The loops the reference writes in R stay in R's order; DESIGN.md section 11.
+"""
+from __future__ import annotations
+
+import copy
+from typing import Callable, Optional
+
+import numpy as np
+
+from . import sparse
+
+
+# ---------------------------------------------------------------------------------------------
+# stats::density with its defaults, for the mode of the null scores (a few hundred to a few
+# hundred thousand values, once per view: host work)
+# ---------------------------------------------------------------------------------------------
+def _seq(frm: float, to: float, n: int) -> np.ndarray:
+    """``seq.int(from, to, length.out = n)`` (R's symmetric form)."""
+    i = np.arange(n, dtype=np.float64)
+    by = (to - frm) / (n - 1)
+    out = np.where(i < n // 2, frm + i * by, to - (n - 1 - i) * by)
+    out[0], out[-1] = frm, to
+    return out
+
+
+def _dnorm(x: np.ndarray, sigma: float) -> np.ndarray:
+    """``stats::dnorm(x, 0, sigma)``, with nmath's accurate branch for |x| / sigma >= 5."""
+    v = np.abs(x / sigma)
+    out = 0.398942280401432677939946059934 * np.exp(-0.5 * v * v) / sigma
+    far = v >= 5
+    if far.any():
+        x1 = np.ldexp(np.rint(np.ldexp(v[far], 16)), -16)
+        x2 = v[far] - x1
+        out[far] = 0.398942280401432677939946059934 / sigma * (np.exp(-0.5 * x1 * x1) * np.exp((-0.5 * x2 - x1) * x2))
+    out[v > np.sqrt(-2 * np.log(2) * (-1021 + 1 - 53))] = 0.0
+    return out
+
+
+def bw_nrd0(x: np.ndarray) -> float:
+    """``stats::bw.nrd0``: 0.9 min(sd, IQR / 1.34) n^-0.2 with its fallbacks (type-7 quartiles)."""
+    x = np.asarray(x, dtype=np.float64)
+    if len(x) < 2:
+        raise ValueError("need at least 2 data points")
+    m = np.sum(x) / len(x)
+    m = m + np.sum(x - m) / len(x)                      # R's refined mean: a constant vector gets sd = 0 exactly
+    hi = float(np.sqrt(np.sum((x - m) ** 2) / (len(x) - 1)))
+    q25, q75 = np.quantile(x, [0.25, 0.75], method="linear")
+    lo = min(hi, float(q75 - q25) / 1.34)
+    if lo == 0:
+        lo = hi or abs(float(x[0])) or 1.0
+    return 0.9 * lo * len(x) ** (-0.2)
+
+
+def density(x, n: int = 512, cut: float = 3.0):
+    """``stats::density(x)`` with the defaults (gaussian kernel, ``bw.nrd0``, ``from = min - cut bw``, ``to = max + cut
+    bw``), R <= 4.3's coordinates: ``BinDist`` on [lo, up] = [from - 4 bw, to + 4 bw], the circular convolution with
+    the kernel sampled at spacing 2 (up - lo) / (2n - 1) -- here as the equal direct Toeplitz sum (the binned mass has
+    an all-zero upper half) -- clamped at 0 and interpolated onto ``seq(from, to, length.out = n)``.  Returns (x, y)."""
+    x = np.asarray(x, dtype=np.float64)
+    nx = len(x)
+    bw = bw_nrd0(x)
+    frm, to = float(x.min()) - cut * bw, float(x.max()) + cut * bw
+    lo, up = frm - 4 * bw, to + 4 * bw
+    xpos = (x - lo) / ((up - lo) / (n - 1))
+    ix = np.floor(xpos).astype(np.int64)
+    fx = xpos - ix
+    w = 1.0 / nx
+    y = np.zeros(n + 1)
+    inner = (ix >= 0) & (ix <= n - 2)
+    np.add.at(y, ix[inner], w * (1 - fx[inner]))
+    np.add.at(y, ix[inner] + 1, w * fx[inner])
+    np.add.at(y, np.zeros(int(np.sum(ix == -1)), dtype=np.int64), w * fx[ix == -1])
+    np.add.at(y, np.full(int(np.sum(ix == n - 1)), n - 1, dtype=np.int64), w * (1 - fx[ix == n - 1]))
+    y = y[:n]
+    by = 2 * (up - lo) / (2 * n - 1)
+    kern = _dnorm(np.arange(n) * by, bw)
+    conv = np.maximum(0.0, kern[np.abs(np.arange(n)[:, None] - np.arange(n)[None, :])] @ y)
+    xords, xout = _seq(lo, up, n), _seq(frm, to, n)
+    j = np.clip(np.searchsorted(xords, xout, side="right"), 1, n - 1)      # xords[j - 1] <= v < xords[j] (approx's interval)
+    i = j - 1
+    yout = conv[i] + (conv[j] - conv[i]) * ((xout - xords[i]) / (xords[j] - xords[i]))
+    yout = np.where(xout == xords[j], conv[j], np.where(xout == xords[i], conv[i], yout))
+    return xout, yout
+
+
+def density_mode(scores) -> float:
+    """``dens <- stats::density(scores); dens$x[which.max(dens$y)]`` (the first maximum)."""
+    x, y = density(scores)
+    return float(x[int(np.argmax(y))])
+
+
+# ---------------------------------------------------------------------------------------------
+# the pair lists, in R's order
+# ---------------------------------------------------------------------------------------------
+def pool_pairs(K: int, R: int):
+    """The pairs of one view over the column pool ``cbind(F_i, f_1[[i]], ..., f_R[[i]])`` (F column k = k, shuffle r's
+    column m = K + r K + m): ``null`` in ``calculate_f_shuffle_jsd``'s order (j = 1..R-1, k, l = j+1..R, m; K^2 R(R-1)/2
+    pairs) and ``score`` in ``check_biclusters``' (F column k against the R K columns of ``cbind(f_1..f_R)``)."""
+    null = [(K + j * K + k, K + l * K + m) for j in range(R - 1) for k in range(K) for l in range(j + 1, R) for m in range(K)]
+    score = [(k, K + y) for k in range(K) for y in range(R * K)]
+    return np.array(null, dtype=np.int32).reshape(-1, 2), np.array(score, dtype=np.int32).reshape(-1, 2)
+
+
+def _check_factors(mats, what):
+    for i, m in enumerate(mats):
+        if not np.all(np.isfinite(m)):
+            raise ValueError(f"{what} of view {i} has non-finite entries")
+
+
+def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int] = None, device_id: int = 0,
+                     group=None, max_iters: int = 100000, shuffled_f=None, jsd: Optional[Callable] = None) -> dict:
+    """``check_biclusters`` (``R/obtain_bicl.r:113-133``) with ``get_thresholds`` (``:80-102``): returns
+    ``{"score": n_views x K, "avg_threshold": n_views, "max_threshold": n_views}``.
+
+    ``data``: the pre-processed views (as ``res_nmtf_inner`` receives them); ``output_f``: the result's F per view.  The
+    ``num_repeats`` shuffled factorisations run on the device to convergence (``n_iters`` is not forwarded by the
+    reference either; ``max_iters`` guards them), drawn from ``seed``, sharded over ``group``'s ranks; the scores come
+    from ``resnmtf_jsd_pairs``.  Test hooks: ``shuffled_f`` (a list of ``num_repeats`` lists of per-view F matrices:
+    no factorisation) and ``jsd(cols, pairs) -> scores`` (replaces the device scorer)."""
+    if isinstance(num_repeats, bool) or int(num_repeats) != num_repeats or num_repeats < 2:
+        raise ValueError("num_repeats must be an integer >= 2 (the reference indexes a second shuffled repeat)")
+    R = int(num_repeats)
+    views = list(data) if not (isinstance(data, np.ndarray) and data.ndim == 2) and not sparse.is_sparse(data) else [data]
+    if any(sparse.is_sparse(d) for d in views):
+        raise NotImplementedError("spurious-bicluster removal needs shuffled views: device shuffles of sparse views are "
+                                  "not supported")
+    views = [np.asarray(d, dtype=np.float64) for d in views]
+    output_f = [np.asarray(f, dtype=np.float64) for f in output_f]
+    n_v = len(views)
+    if len(output_f) != n_v:
+        raise ValueError("output_f must hold one F per view")
+    K = output_f[0].shape[1]
+    for i, f in enumerate(output_f):
+        if f.ndim != 2 or f.shape != (views[i].shape[0], K):
+            raise ValueError(f"output_f[{i}] must be {views[i].shape[0]} x {K}")
+        if f.shape[0] < 2:
+            raise ValueError("views need at least 2 rows (bw.nrd0 needs two data points)")
+    if K * K * R * (R - 1) // 2 < 2:
+        raise ValueError("a single null score (K = 1, num_repeats = 2): stats::density needs two")
+    _check_factors(output_f, "output_f")
+    if shuffled_f is None:
+        from . import batched
+        dev = batched.DeviceData(views, device_id=device_id, pre_processed=True)
+        try:
+            reps = batched.shuffles_on_device(dev, K, R, n_iters=None, seed=0 if seed is None else int(seed), group=group,
+                                              max_iters=max_iters)
+        finally:
+            dev.close()
+        shuffled_f = [rep["output_f"] for rep in reps]
+    if len(shuffled_f) != R or any(len(fs) != n_v for fs in shuffled_f):
+        raise ValueError("shuffled_f must hold num_repeats lists of one F per view")
+    shuffled_f = [[np.asarray(f, dtype=np.float64) for f in fs] for fs in shuffled_f]
+    for fs in shuffled_f:
+        for i, f in enumerate(fs):
+            if f.shape != output_f[i].shape:
+                raise ValueError(f"shuffled F of view {i} must be {output_f[i].shape[0]} x {K}")
+        _check_factors(fs, "a shuffled F")
+    if jsd is None:
+        from .engine import jsd_pairs
+        jsd = lambda cols, pairs: jsd_pairs(cols, pairs, device_id=device_id)    # noqa: E731
+    null_p, score_p = pool_pairs(K, R)
+    score = np.zeros((n_v, K))
+    avg, mx = np.zeros(n_v), np.zeros(n_v)
+    for i in range(n_v):
+        pool = np.concatenate([output_f[i]] + [fs[i] for fs in shuffled_f], axis=1)
+        vals = np.asarray(jsd(pool, np.concatenate([null_p, score_p])), dtype=np.float64)
+        if not np.all(np.isfinite(vals)):
+            raise ValueError(f"view {i}: a Jensen-Shannon score is not finite (a density summed to zero; R gives NaN "
+                             "here and check_biclusters cannot continue)")
+        null, sc = vals[:len(null_p)], vals[len(null_p):]
+        avg[i] = np.mean(null)                                                    # :97
+        mx[i] = density_mode(null)                                                # :98-99
+        score[i] = sc.reshape(K, R * K).mean(axis=1)                              # :125-128
+    return {"score": score, "avg_threshold": avg, "max_threshold": mx}
+
+
+def remove_spurious(data, results: dict, num_repeats: int = 5, **kwargs) -> dict:
+    """The removal step of ``obtain_biclusters`` (``R/obtain_bicl.r:176-188``) on a ``res_nmtf_inner(spurious=False)``
+    / ``apply_resnmtf(spurious=False, stability=False)`` result: with ``check = check_biclusters(data,
+    results["output_f"], num_repeats, **kwargs)``, view i's cluster columns ``relations`` (``which.max`` of every S
+    column) flagged by ``score < max_threshold | score == 0`` are zeroed in ``row_clusters`` and ``col_clusters``.
+    Returns a copy (F, S, G unchanged; ``results`` is not modified) with ``"spurious"``: ``check`` plus ``"removed"``,
+    the n_views x K mask of the zeroed cluster columns."""
+    if not results.get("row_clusters") or not results.get("col_clusters"):
+        raise ValueError("results has no cluster matrices (a no_clusts result): nothing to remove")
+    _check_factors(results["output_s"], "output_s")
+    check = check_biclusters(data, results["output_f"], num_repeats, **kwargs)
+    out = dict(results)
+    out["row_clusters"] = [np.array(rc, dtype=np.float64, copy=True) for rc in results["row_clusters"]]
+    out["col_clusters"] = [np.array(cc, dtype=np.float64, copy=True) for cc in results["col_clusters"]]
+    removed = []
+    for i in range(len(out["row_clusters"])):
+        relations = np.argmax(np.asarray(results["output_s"][i]), axis=0)        # apply(S, 2, which.max)
+        indices = (check["score"][i] < check["max_threshold"][i]) | (check["score"][i] == 0)
+        new = indices[relations]
+        out["row_clusters"][i][:, new] = 0.0
+        out["col_clusters"][i][:, new] = 0.0
+        removed.append(new)
+    out["spurious"] = dict(copy.deepcopy(check), removed=np.array(removed, dtype=bool))
+    return out
