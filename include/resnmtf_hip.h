@@ -443,6 +443,64 @@ int resnmtf_relevance(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, 
  */
 int resnmtf_jsd_pairs(int device_id, int n, int n_cols, const double* cols, int n_pairs, const int* pairs, double* out);
 
+/*
+ * Many small factorisations in one launch (the k sweep, the shuffled fits of obtain_shuffled_f, the sub-sample fits of
+ * stability_check): res_nmtf_inner (R/main.r:32-140) for every job, one workgroup per job, fp64 throughout.  A job is
+ * what res_nmtf_inner receives: pre-processed views, explicit initial factors, symmetrised restrictions and the
+ * shared-name index pairs of every view pair (as for resnmtf_set_shared_rows / _cols).  Per job the kernel runs the
+ * sweeps of update_matrices (R/update_steps.r:272-319, views in index order), calculate_error as the explicit residual
+ * ||X - F S G^T||_F^2 / ||X||_F^2 (R/utils.r:157-166) averaged over the views, the stop rule and normalisation_check
+ * (R/utils.r:176-195); outputs are F, S, G (normalised), lambda, mu, All_Error and the sweep count.  The caller derives
+ * the binary cluster matrices (R/obtain_bicl.r:162-180) from them.
+ *   n_iters > 0: min(n_iters, max_iters) sweeps; n_iters == 0: while |mean_err_t - mean_err_{t-1}| > tol with
+ *   mean_err_0 = 0 (R/main.r:53-80), at most max_iters sweeps.
+ * Every sum has an order fixed by the job's own shapes and there are no atomics: a job's results are bitwise the same
+ * alone, in any batch, at any position and run to run.  Blocking; no handle: the call selects device_id, uploads
+ * everything in one buffer, makes one launch per k class present (k <= 8, <= 16, <= 32; each job runs in the kernel
+ * instance of its own k) and copies the results back; resnmtf_last_error(NULL) describes a failure.
+ * Refused before any device work (RESNMTF_ERR_INVALID): n_jobs < 0, jobs NULL, a struct_size mismatch, max_iters < 1,
+ * tol not finite, n_views outside [1, 8], k outside [1, 32] or above a view dimension, n_rows * n_cols above 2^22 for a
+ * view, NULL input or output pointers, non-finite inputs, negative restriction entries or a non-zero diagonal, an
+ * index pair outside its views, n_iters < 0, err_capacity below the sweeps allowed.  n_jobs = 0 returns at once.
+ * DESIGN.md section 12.
+ */
+#define RESNMTF_GROUP_MAX_VIEWS 8
+#define RESNMTF_GROUP_MAX_K 32
+#define RESNMTF_GROUP_MAX_VIEW_ENTRIES (1 << 22)
+typedef struct resnmtf_group_job {
+  int struct_size;                       /* sizeof(resnmtf_group_job) */
+  int n_views, k;
+  int n_iters;                           /* 0 = run to convergence */
+  int n_rows[RESNMTF_GROUP_MAX_VIEWS], n_cols[RESNMTF_GROUP_MAX_VIEWS];
+  const double* x[RESNMTF_GROUP_MAX_VIEWS];        /* pre-processed X_v, n x m column-major */
+  const double* f0[RESNMTF_GROUP_MAX_VIEWS];       /* initial F_v n x k, S_v k x k, G_v m x k */
+  const double* s0[RESNMTF_GROUP_MAX_VIEWS];
+  const double* g0[RESNMTF_GROUP_MAX_VIEWS];
+  const double* lambda0[RESNMTF_GROUP_MAX_VIEWS];  /* k entries; NULL = colSums(F0) (R/update_steps.r:55) */
+  const double* mu0[RESNMTF_GROUP_MAX_VIEWS];      /* k entries; NULL = colSums(G0) */
+  const double* phi;                     /* n_views x n_views column-major, symmetrised, zero diagonal; NULL = zeros */
+  const double* xi;
+  const double* psi;
+  /* shared rows / columns of view pair (v, w), v != w: count <= 0 = NA (no shared names), else count positions in
+   * view v and in view w (naming.index_pairs) */
+  int row_count[RESNMTF_GROUP_MAX_VIEWS][RESNMTF_GROUP_MAX_VIEWS];
+  const int* row_idx_v[RESNMTF_GROUP_MAX_VIEWS][RESNMTF_GROUP_MAX_VIEWS];
+  const int* row_idx_w[RESNMTF_GROUP_MAX_VIEWS][RESNMTF_GROUP_MAX_VIEWS];
+  int col_count[RESNMTF_GROUP_MAX_VIEWS][RESNMTF_GROUP_MAX_VIEWS];
+  const int* col_idx_v[RESNMTF_GROUP_MAX_VIEWS][RESNMTF_GROUP_MAX_VIEWS];
+  const int* col_idx_w[RESNMTF_GROUP_MAX_VIEWS][RESNMTF_GROUP_MAX_VIEWS];
+  /* outputs (caller-owned) */
+  double* f_out[RESNMTF_GROUP_MAX_VIEWS];          /* n x k, normalised (output_f) */
+  double* s_out[RESNMTF_GROUP_MAX_VIEWS];          /* k x k (output_s) */
+  double* g_out[RESNMTF_GROUP_MAX_VIEWS];          /* m x k (output_g) */
+  double* lambda_out[RESNMTF_GROUP_MAX_VIEWS];     /* k */
+  double* mu_out[RESNMTF_GROUP_MAX_VIEWS];         /* k */
+  double* all_error;                     /* err_capacity entries; the first *iters_done are written */
+  int err_capacity;                      /* >= n_iters (fixed count, capped by max_iters) or max_iters (convergence) */
+  int* iters_done;
+} resnmtf_group_job;
+int resnmtf_group_run(int device_id, int n_jobs, const resnmtf_group_job* jobs, double tol, int max_iters);
+
 /* ---- phase-level entry points (views sharded one-per-GPU; host does the exchange) ---- */
 
 /* Which image of X the streaming passes of view v use after its upload: *uses_2byte = 0 (f32 images), 1 (fp16) or

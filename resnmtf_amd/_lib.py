@@ -58,6 +58,27 @@ _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 _h = C.c_void_p
 
+GROUP_MAX_VIEWS = 8
+GROUP_MAX_K = 32
+GROUP_MAX_VIEW_ENTRIES = 1 << 22
+_MV = GROUP_MAX_VIEWS
+
+
+class GroupJob(C.Structure):
+    """``resnmtf_group_job`` (include/resnmtf_hip.h)."""
+    _fields_ = [
+        ("struct_size", C.c_int), ("n_views", C.c_int), ("k", C.c_int), ("n_iters", C.c_int),
+        ("n_rows", C.c_int * _MV), ("n_cols", C.c_int * _MV),
+        ("x", _dp * _MV), ("f0", _dp * _MV), ("s0", _dp * _MV), ("g0", _dp * _MV),
+        ("lambda0", _dp * _MV), ("mu0", _dp * _MV),
+        ("phi", _dp), ("xi", _dp), ("psi", _dp),
+        ("row_count", (C.c_int * _MV) * _MV), ("row_idx_v", (_ip * _MV) * _MV), ("row_idx_w", (_ip * _MV) * _MV),
+        ("col_count", (C.c_int * _MV) * _MV), ("col_idx_v", (_ip * _MV) * _MV), ("col_idx_w", (_ip * _MV) * _MV),
+        ("f_out", _dp * _MV), ("s_out", _dp * _MV), ("g_out", _dp * _MV),
+        ("lambda_out", _dp * _MV), ("mu_out", _dp * _MV),
+        ("all_error", _dp), ("err_capacity", C.c_int), ("iters_done", _ip),
+    ]
+
 # name -> (restype, argtypes); must list every symbol include/resnmtf_hip.h declares
 SIGNATURES = {
     "resnmtf_abi_version": (C.c_int, []),
@@ -87,6 +108,7 @@ SIGNATURES = {
     "resnmtf_set_reference_clusters": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp]),
     "resnmtf_relevance": (C.c_int, [_h, C.c_int, _h, C.c_int, _ip, _ip, _dp]),
     "resnmtf_jsd_pairs": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, _ip, _dp]),
+    "resnmtf_group_run": (C.c_int, [C.c_int, C.c_int, C.POINTER(GroupJob), C.c_double, C.c_int]),
     "resnmtf_reserve_sweeps": (C.c_int, [_h, C.c_int]),
     "resnmtf_prepare": (C.c_int, [_h]),
     "resnmtf_phase": (C.c_int, [_h, C.c_int, C.c_int, C.c_int]),

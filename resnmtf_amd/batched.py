@@ -185,6 +185,105 @@ def run_jobs(jobs: Sequence[Job], device_id: int = 0, group=None, runner: Option
 
 
 # ---------------------------------------------------------------------------------------------
+# many small jobs in one launch: one workgroup per job, fp64 (resnmtf_group_run)
+# ---------------------------------------------------------------------------------------------
+def _check_group_limits(i: int, data, k: int):
+    from ._lib import GROUP_MAX_K, GROUP_MAX_VIEW_ENTRIES, GROUP_MAX_VIEWS
+    if len(data) > GROUP_MAX_VIEWS:
+        raise ValueError(f"job {i}: the grouped path takes at most {GROUP_MAX_VIEWS} views, got {len(data)}")
+    if not 1 <= k <= GROUP_MAX_K:
+        raise ValueError(f"job {i}: the grouped path takes 1 <= k <= {GROUP_MAX_K}, got k = {k}")
+    for v, x in enumerate(data):
+        n, m = x.shape
+        if k > n or k > m:
+            raise ValueError(f"job {i}: k = {k} exceeds a dimension of view {v} ({n} x {m})")
+        if n * m > GROUP_MAX_VIEW_ENTRIES:
+            raise ValueError(f"job {i}: view {v} has {n * m} entries, above the grouped path's 2^22; use run_jobs")
+
+
+def prepare_grouped_job(job: Job, i: int = 0, pre_processed: bool = False, init=None) -> dict:
+    """The problem ``engine.group_run`` receives for one job, prepared as ``run_job`` prepares it for the engine:
+    names, shared-name index pairs, symmetrised restrictions, ``check_data`` unless ``pre_processed``, and the initial
+    factors ``init`` = (F, S, G[, lambda, mu]) per view or, when None, ``api.svd_init(data, k_vec, job.seed)`` on the
+    host.  Sparse views and jobs over the kernel's limits are refused here."""
+    from . import api, naming, sparse
+    if any(sparse.is_sparse(d) for d in job.data):
+        raise NotImplementedError(f"job {i}: the grouped path takes dense views only; run sparse views with run_jobs")
+    data = [np.asarray(d, dtype=np.float64) for d in job.data]
+    if any(d.ndim != 2 for d in data):
+        raise ValueError(f"job {i}: every view must be a matrix")
+    n_v, k = len(data), int(job.k_val)
+    _check_group_limits(i, data, k)
+    rn, cn = naming.give_names(data, job.phi, job.psi, job.row_names, job.col_names)
+    row_idx, col_idx = naming.shared_names(rn), naming.shared_names(cn)
+    phi = naming.init_rest_mats(job.phi, n_v); psi = naming.init_rest_mats(job.psi, n_v); xi = naming.init_rest_mats(job.xi, n_v)
+    if not pre_processed:
+        data = naming.check_data(data)
+    if init is None:
+        init = api.svd_init(data, [k] * n_v, job.seed)
+    init = list(init)
+    if len(init) not in (3, 5):
+        raise ValueError(f"job {i}: an initial state is (F, S, G) or (F, S, G, lambda, mu) per view")
+    f0, s0, g0 = init[0], init[1], init[2]
+    lam0 = init[3] if len(init) > 3 else None
+    mu0 = init[4] if len(init) > 4 else None
+    for what, mats, shape in (("F", f0, lambda n, m: (n, k)), ("S", s0, lambda n, m: (k, k)), ("G", g0, lambda n, m: (m, k)),
+                              ("lambda", lam0, lambda n, m: (k,)), ("mu", mu0, lambda n, m: (k,))):
+        if mats is None:
+            continue
+        if len(mats) != n_v:
+            raise ValueError(f"job {i}: the initial {what} must hold one entry per view")
+        for v, (a, x) in enumerate(zip(mats, data)):
+            want = shape(*x.shape)
+            if np.shape(a) != want:
+                raise ValueError(f"job {i}, view {v}: the initial {what} has shape {np.shape(a)}, expected {want}")
+    row_pairs = [[None if v == w else naming.index_pairs(rn[v], rn[w], row_idx[v].get(w)) for w in range(n_v)] for v in range(n_v)]
+    col_pairs = [[None if v == w else naming.index_pairs(cn[v], cn[w], col_idx[v].get(w)) for w in range(n_v)] for v in range(n_v)]
+    return {"data": data, "k": k, "init_f": list(f0), "init_s": list(s0), "init_g": list(g0),
+            "init_lam": None if lam0 is None else list(lam0), "init_mu": None if mu0 is None else list(mu0),
+            "phi": phi, "xi": xi, "psi": psi, "row_pairs": row_pairs, "col_pairs": col_pairs, "n_iters": job.n_iters,
+            "row_names": rn, "col_names": cn}
+
+
+def _binary_clusters(f, g, s):
+    """``R/obtain_bicl.r:162-180`` with ``remove_spurious = FALSE``: thresholds 1/n and 1/m, row clusters re-ordered by
+    the first maximum of every S column."""
+    rc = (f > 1.0 / f.shape[0]).astype(np.float64)
+    cc = (g > 1.0 / g.shape[0]).astype(np.float64)
+    return rc[:, np.argmax(s, axis=0)], cc
+
+
+def run_jobs_grouped(jobs: Sequence[Job], device_id: int = 0, pre_processed: bool = False, inits=None,
+                     max_iters: int = 100000, group_runner: Optional[Callable] = None) -> List[dict]:
+    """Run independent jobs in one ``resnmtf_group_run`` call: every job in its own workgroup, fp64 throughout, from
+    ``inits[i]`` = (F, S, G[, lambda, mu]) per view when given, else from ``api.svd_init`` on the host with the job's
+    seed.  Returns, in job order, the keys ``run_job`` returns (``bisil`` None).  Every job is prepared and checked
+    (dense views only, at most 8 views, 1 <= k <= 32, n * m <= 2^22 per view) before any device work.
+    ``group_runner(problems, tol=, max_iters=, device_id=)`` replaces ``engine.group_run`` (a test hook)."""
+    from . import sparse
+    jobs = list(jobs)
+    if inits is not None and len(inits) != len(jobs):
+        raise ValueError("inits must hold one initial state per job")
+    for i, job in enumerate(jobs):                    # refusals first, before any SVD or device work
+        if any(sparse.is_sparse(d) for d in job.data):
+            raise NotImplementedError(f"job {i}: the grouped path takes dense views only; run sparse views with run_jobs")
+        _check_group_limits(i, [np.asarray(d) for d in job.data], int(job.k_val))
+    problems = [prepare_grouped_job(job, i, pre_processed, None if inits is None else inits[i]) for i, job in enumerate(jobs)]
+    if group_runner is None:
+        from .engine import group_run as group_runner
+    outs = group_runner(problems, tol=1.0e-6, max_iters=max_iters, device_id=device_id)
+    results = []
+    for job, out in zip(jobs, outs):
+        errs = np.asarray(out["all_error"], dtype=np.float64)
+        error = float(np.mean(errs[-10:])) if job.n_iters is None else float(errs[-1])      # R/main.r:126-130
+        rcs, ccs = zip(*[_binary_clusters(f, g, s) for f, g, s in zip(out["f"], out["g"], out["s"])])
+        results.append({"output_f": out["f"], "output_s": out["s"], "output_g": out["g"], "Error": error,
+                        "All_Error": errs, "bisil": None, "row_clusters": list(rcs), "col_clusters": list(ccs),
+                        "lambda": out["lambda"], "mu": out["mu"], "tag": job.tag, "extras": job.extras})
+    return results
+
+
+# ---------------------------------------------------------------------------------------------
 # the same job kinds with the data resident on the device: one upload, copies / shuffles drawn there
 # ---------------------------------------------------------------------------------------------
 class DeviceData:

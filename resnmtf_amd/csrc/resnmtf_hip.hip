@@ -30,6 +30,7 @@
 #include "resnmtf_kernels.hip.inc"
 #include "resnmtf_sparse.hip.inc"
 #include "resnmtf_jsd.hip.inc"
+#include "resnmtf_group.hip.inc"
 #include "resnmtf_split_tu.h"
 #ifdef RESNMTF_SPLIT_TU      // product build: the k <= 16 pass lives in resnmtf_pass_k16.hip (its own scheduling strategy)
 #define RESNMTF_EXTERN(NW, UNR, XG, MA) extern template __global__ void pass_kernel<1, NW, UNR, XG, MA, 0>(PassArgs, KKFArgs, KKSArgs);
@@ -3163,6 +3164,255 @@ int resnmtf_jsd_pairs(int device_id, int n, int n_cols, const double* cols, int 
   (void)hipFree(buf);
   (void)hipStreamDestroy(st);
   if (e != hipSuccess) { g_create_error = std::string("jsd_pairs: ") + hipGetErrorString(e); return RESNMTF_ERR_HIP; }
+  return RESNMTF_OK;
+}
+
+// ---- grouped small factorisations (csrc/resnmtf_group.hip.inc) ----
+namespace {
+bool all_finite(const double* a, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(a[i])) return false;
+  return true;
+}
+
+// a job's host checks; a message on refusal, nullptr when it is fine
+const char* check_group_job(const resnmtf_group_job& j, int max_iters) {
+  if (j.struct_size != (int)sizeof(resnmtf_group_job)) return "resnmtf_group_job struct_size mismatch";
+  const int V = j.n_views, k = j.k;
+  if (V < 1 || V > RESNMTF_GROUP_MAX_VIEWS) return "n_views must be in [1, 8]";
+  if (k < 1 || k > RESNMTF_GROUP_MAX_K) return "k must be in [1, 32]";
+  if (j.n_iters < 0) return "n_iters must be >= 0 (0 = run to convergence)";
+  const int sweeps = j.n_iters > 0 ? std::min(j.n_iters, max_iters) : max_iters;
+  if (!j.all_error || !j.iters_done || j.err_capacity < sweeps) return "all_error / iters_done NULL or err_capacity below the sweeps allowed";
+  for (int v = 0; v < V; ++v) {
+    const int n = j.n_rows[v], m = j.n_cols[v];
+    if (n < 1 || m < 1) return "view dimensions must be positive";
+    if (k > n || k > m) return "k exceeds a view dimension (R/utils.r:444,449)";
+    if ((long long)n * m > RESNMTF_GROUP_MAX_VIEW_ENTRIES) return "a view has more than 2^22 entries";
+    if (!j.x[v] || !j.f0[v] || !j.s0[v] || !j.g0[v]) return "x / f0 / s0 / g0 is NULL";
+    if (!j.f_out[v] || !j.s_out[v] || !j.g_out[v] || !j.lambda_out[v] || !j.mu_out[v]) return "an output pointer is NULL";
+    if (!all_finite(j.x[v], (size_t)n * m)) return "x has a non-finite entry";
+    if (!all_finite(j.f0[v], (size_t)n * k) || !all_finite(j.s0[v], (size_t)k * k) || !all_finite(j.g0[v], (size_t)m * k))
+      return "an initial factor has a non-finite entry";
+    if ((j.lambda0[v] && !all_finite(j.lambda0[v], k)) || (j.mu0[v] && !all_finite(j.mu0[v], k)))
+      return "lambda0 / mu0 has a non-finite entry";
+  }
+  for (const double* r : {j.phi, j.xi, j.psi}) {
+    if (!r) continue;
+    for (int w = 0; w < V; ++w)
+      for (int v = 0; v < V; ++v) {
+        const double x = r[w + v * V];
+        if (!std::isfinite(x) || x < 0) return "restriction entries must be finite and non-negative";
+        if (v == w && x != 0) return "restriction matrices must have a zero diagonal (init_rest_mats)";
+      }
+  }
+  for (int v = 0; v < V; ++v)
+    for (int w = 0; w < V; ++w) {
+      if (v == w) continue;
+      for (int axis = 0; axis < 2; ++axis) {
+        const int c = axis ? j.col_count[v][w] : j.row_count[v][w];
+        if (c <= 0) continue;
+        const int* iv = axis ? j.col_idx_v[v][w] : j.row_idx_v[v][w];
+        const int* iw = axis ? j.col_idx_w[v][w] : j.row_idx_w[v][w];
+        const int lv = axis ? j.n_cols[v] : j.n_rows[v], lw = axis ? j.n_cols[w] : j.n_rows[w];
+        if (!iv || !iw) return "shared index arrays are NULL";
+        for (int p = 0; p < c; ++p)
+          if (iv[p] < 0 || iv[p] >= lv || iw[p] < 0 || iw[p] >= lw) return "shared index out of range";
+      }
+    }
+  return nullptr;
+}
+}  // namespace
+
+int resnmtf_group_run(int device_id, int n_jobs, const resnmtf_group_job* jobs, double tol, int max_iters) {
+  auto bad = [](const std::string& msg) { g_create_error = msg; return RESNMTF_ERR_INVALID; };
+  if (n_jobs < 0) return bad("n_jobs must be >= 0");
+  if (n_jobs > 0 && !jobs) return bad("jobs is NULL");
+  if (max_iters < 1) return bad("max_iters must be >= 1");
+  if (!std::isfinite(tol)) return bad("tol must be finite");
+  for (int q = 0; q < n_jobs; ++q)
+    if (const char* why = check_group_job(jobs[q], max_iters)) return bad("job " + std::to_string(q) + ": " + why);
+  if (n_jobs == 0) return RESNMTF_OK;
+
+  // one buffer: [descriptors | outputs (F, G, S, lambda, mu per job) | sweep counts | X, X^T | row / column maps |
+  // error histories | scratch]; everything before the error histories is uploaded; the outputs and sweep counts come
+  // back, then the first max(sweeps) rows of the error histories (sweep-major: entry it * n_jobs + job)
+  std::vector<GroupDesc> desc(n_jobs);
+  size_t off = ((size_t)n_jobs * sizeof(GroupDesc) + 15) / 16 * 2;      // in doubles
+  int lds[3] = {0, 0, 0};                                                 // per k class (8, 16, 32)
+  int max_cap = 1;
+  for (int q = 0; q < n_jobs; ++q) {
+    const resnmtf_group_job& j = jobs[q];
+    GroupDesc& d = desc[q];
+    std::memset(&d, 0, sizeof(d));
+    d.V = j.n_views; d.k = j.k; d.n_iters = j.n_iters; d.id = q;
+    d.cap = j.n_iters > 0 ? std::min(j.n_iters, max_iters) : max_iters;
+    d.tol = tol;
+    for (int v = 0; v < d.V; ++v) {
+      d.n[v] = j.n_rows[v]; d.m[v] = j.n_cols[v];
+      d.f[v] = off; off += (size_t)d.n[v] * d.k;
+      d.g[v] = off; off += (size_t)d.m[v] * d.k;
+    }
+    d.s = off; off += (size_t)d.V * d.k * d.k;
+    d.lam = off; off += (size_t)d.V * d.k;
+    d.mu = off; off += (size_t)d.V * d.k;
+    max_cap = std::max(max_cap, d.cap);
+    for (int w = 0; w < d.V; ++w)
+      for (int v = 0; v < d.V; ++v) {
+        d.phi[w * GRP_MAX_VIEWS + v] = j.phi ? j.phi[w + v * d.V] : 0.0;
+        d.xi[w * GRP_MAX_VIEWS + v] = j.xi ? j.xi[w + v * d.V] : 0.0;
+        d.psi[w * GRP_MAX_VIEWS + v] = j.psi ? j.psi[w + v * d.V] : 0.0;
+      }
+    const int cls = d.k <= 8 ? 0 : (d.k <= 16 ? 1 : 2);
+    lds[cls] = std::max(lds[cls], group_lds_doubles(d.V, d.k));
+  }
+  const size_t sweeps_off = off;                                          // n_jobs ints, padded to doubles
+  off += ((size_t)n_jobs + 1) / 2;
+  const size_t upload_x = off;
+  for (int q = 0; q < n_jobs; ++q) {
+    GroupDesc& d = desc[q];
+    for (int v = 0; v < d.V; ++v) {
+      d.x[v] = off; off += (size_t)d.n[v] * d.m[v];
+      d.xt[v] = off; off += (size_t)d.n[v] * d.m[v];
+    }
+  }
+  size_t ioff = off * 2;                                                  // maps, in ints from the buffer base
+  for (int q = 0; q < n_jobs; ++q) {
+    const resnmtf_group_job& j = jobs[q];
+    GroupDesc& d = desc[q];
+    for (int v = 0; v < GRP_MAX_VIEWS; ++v)
+      for (int w = 0; w < GRP_MAX_VIEWS; ++w) {
+        const bool pair = v < d.V && w < d.V && v != w;
+        d.rmap[v][w] = pair && j.row_count[v][w] > 0 ? (long long)ioff : -1;
+        if (d.rmap[v][w] >= 0) ioff += d.n[v];
+        d.cmap[v][w] = pair && j.col_count[v][w] > 0 ? (long long)ioff : -1;
+        if (d.cmap[v][w] >= 0) ioff += d.m[v];
+      }
+  }
+  off = (ioff + 1) / 2;
+  const size_t upload_end = off;
+  const size_t err_base = off;
+  off += (size_t)n_jobs * max_cap;
+  for (int q = 0; q < n_jobs; ++q) { desc[q].err = (long long)(err_base + q); desc[q].err_stride = n_jobs; }
+  for (int q = 0; q < n_jobs; ++q) {
+    GroupDesc& d = desc[q];
+    int big = 1;
+    for (int v = 0; v < d.V; ++v) big = std::max(big, std::max(d.n[v], d.m[v]));
+    d.scratch = off; off += (size_t)big * d.k;
+    d.scratch2 = off; off += (size_t)big * d.k;
+  }
+  const size_t total = off;
+
+  // descriptors grouped by k class (stable), one launch per class
+  std::vector<GroupDesc> sorted;
+  int class_first[4] = {0, 0, 0, 0};
+  const int classes[3] = {8, 16, 32};
+  for (int c = 0; c < 3; ++c) {
+    class_first[c] = (int)sorted.size();
+    for (int q = 0; q < n_jobs; ++q)
+      if (group_k_class(desc[q].k) == classes[c]) sorted.push_back(desc[q]);
+  }
+  class_first[3] = n_jobs;
+  std::vector<double> host(upload_end, 0.0);
+  std::memcpy(host.data(), sorted.data(), (size_t)n_jobs * sizeof(GroupDesc));
+  int* ihost = reinterpret_cast<int*>(host.data());
+  for (int q = 0; q < n_jobs; ++q) {
+    const resnmtf_group_job& j = jobs[q];
+    const GroupDesc& d = desc[q];
+    const int k = d.k;
+    for (int v = 0; v < d.V; ++v) {
+      const int n = d.n[v], m = d.m[v];
+      std::memcpy(&host[d.f[v]], j.f0[v], (size_t)n * k * sizeof(double));
+      std::memcpy(&host[d.g[v]], j.g0[v], (size_t)m * k * sizeof(double));
+      std::memcpy(&host[d.s + (size_t)v * k * k], j.s0[v], (size_t)k * k * sizeof(double));
+      for (int c = 0; c < k; ++c) {                                       // explicit init: colSums (R/update_steps.r:55-56)
+        double cf = 0.0, cg = 0.0;
+        if (!j.lambda0[v]) for (int i = 0; i < n; ++i) cf += j.f0[v][i + (size_t)c * n];
+        if (!j.mu0[v]) for (int i = 0; i < m; ++i) cg += j.g0[v][i + (size_t)c * m];
+        host[d.lam + (size_t)v * k + c] = j.lambda0[v] ? j.lambda0[v][c] : cf;
+        host[d.mu + (size_t)v * k + c] = j.mu0[v] ? j.mu0[v][c] : cg;
+      }
+      const double* x = j.x[v];
+      std::memcpy(&host[d.x[v]], x, (size_t)n * m * sizeof(double));
+      double* xt = &host[d.xt[v]];
+      for (int c = 0; c < m; ++c)
+        for (int i = 0; i < n; ++i) xt[c + (size_t)i * m] = x[i + (size_t)c * n];
+      for (int w = 0; w < d.V; ++w) {
+        if (d.rmap[v][w] >= 0) {
+          int* map = ihost + d.rmap[v][w];
+          std::fill(map, map + n, -1);
+          for (int p = 0; p < j.row_count[v][w]; ++p) map[j.row_idx_v[v][w][p]] = j.row_idx_w[v][w][p];
+        }
+        if (d.cmap[v][w] >= 0) {
+          int* map = ihost + d.cmap[v][w];
+          std::fill(map, map + m, -1);
+          for (int p = 0; p < j.col_count[v][w]; ++p) map[j.col_idx_v[v][w][p]] = j.col_idx_w[v][w][p];
+        }
+      }
+    }
+  }
+
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_error = "no HIP device"; return RESNMTF_ERR_NO_DEVICE; }
+  if (device_id < 0 || device_id >= ndev) return bad("device_id out of range");
+  hipError_t e = hipSetDevice(device_id);
+  if (e != hipSuccess) { g_create_error = std::string("hipSetDevice: ") + hipGetErrorString(e); return RESNMTF_ERR_HIP; }
+  const size_t lds_bytes[3] = {(size_t)lds[0] * sizeof(double), (size_t)lds[1] * sizeof(double), (size_t)lds[2] * sizeof(double)};
+  e = hipSuccess;
+  if (lds[0] > 0) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&group_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes[0]);
+  if (e == hipSuccess && lds[1] > 0) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&group_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes[1]);
+  if (e == hipSuccess && lds[2] > 0) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&group_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes[2]);
+  if (e != hipSuccess) { g_create_error = std::string("group_run: ") + hipGetErrorString(e); return RESNMTF_ERR_HIP; }
+  hipStream_t st = nullptr;
+  e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+  if (e != hipSuccess) { g_create_error = std::string("hipStreamCreate: ") + hipGetErrorString(e); return RESNMTF_ERR_HIP; }
+  double* buf = nullptr;
+  e = hipMalloc(reinterpret_cast<void**>(&buf), total * sizeof(double));
+  if (e != hipSuccess) {
+    (void)hipStreamDestroy(st);
+    g_create_error = std::string("group_run: ") + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? RESNMTF_ERR_ALLOC : RESNMTF_ERR_HIP;
+  }
+  const size_t desc_dbl = ((size_t)n_jobs * sizeof(GroupDesc) + 15) / 16 * 2;
+  e = hipMemcpyAsync(buf, host.data(), upload_end * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    const GroupDesc* dd = reinterpret_cast<const GroupDesc*>(buf);
+    int* dsweeps = reinterpret_cast<int*>(buf + sweeps_off);
+    const int cnt[3] = {class_first[1] - class_first[0], class_first[2] - class_first[1], class_first[3] - class_first[2]};
+    if (cnt[0] > 0) hipLaunchKernelGGL(group_kernel<8>, dim3(cnt[0]), dim3(GRP_THREADS), lds_bytes[0], st, dd + class_first[0], buf, (const int*)buf, dsweeps);
+    if (cnt[1] > 0) hipLaunchKernelGGL(group_kernel<16>, dim3(cnt[1]), dim3(GRP_THREADS), lds_bytes[1], st, dd + class_first[1], buf, (const int*)buf, dsweeps);
+    if (cnt[2] > 0) hipLaunchKernelGGL(group_kernel<32>, dim3(cnt[2]), dim3(GRP_THREADS), lds_bytes[2], st, dd + class_first[2], buf, (const int*)buf, dsweeps);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(host.data() + desc_dbl, buf + desc_dbl, (upload_x - desc_dbl) * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  const int* sweeps = reinterpret_cast<const int*>(host.data() + sweeps_off);
+  int max_it = 0;
+  if (e == hipSuccess)
+    for (int q = 0; q < n_jobs; ++q) max_it = std::max(max_it, std::min(std::max(sweeps[q], 0), desc[q].cap));
+  std::vector<double> errs((size_t)max_it * n_jobs);
+  if (e == hipSuccess && max_it > 0)
+    e = hipMemcpyAsync(errs.data(), buf + err_base, errs.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(buf);
+  (void)hipStreamDestroy(st);
+  if (e != hipSuccess) { g_create_error = std::string("group_run: ") + hipGetErrorString(e); return RESNMTF_ERR_HIP; }
+  for (int q = 0; q < n_jobs; ++q) {
+    const resnmtf_group_job& j = jobs[q];
+    const GroupDesc& d = desc[q];
+    const int k = d.k;
+    for (int v = 0; v < d.V; ++v) {
+      std::memcpy(j.f_out[v], &host[d.f[v]], (size_t)d.n[v] * k * sizeof(double));
+      std::memcpy(j.g_out[v], &host[d.g[v]], (size_t)d.m[v] * k * sizeof(double));
+      std::memcpy(j.s_out[v], &host[d.s + (size_t)v * k * k], (size_t)k * k * sizeof(double));
+      std::memcpy(j.lambda_out[v], &host[d.lam + (size_t)v * k], (size_t)k * sizeof(double));
+      std::memcpy(j.mu_out[v], &host[d.mu + (size_t)v * k], (size_t)k * sizeof(double));
+    }
+    const int it = std::min(std::max(sweeps[q], 0), d.cap);
+    for (int t = 0; t < it; ++t) j.all_error[t] = errs[(size_t)t * n_jobs + q];
+    *j.iters_done = it;
+  }
   return RESNMTF_OK;
 }
 

@@ -50,6 +50,92 @@ def jsd_pairs(cols, pairs, device_id: int = 0) -> np.ndarray:
     return out
 
 
+def group_run(problems, tol: float = 1.0e-6, max_iters: int = 100000, device_id: int = 0) -> list:
+    """Many small factorisations in one call (``resnmtf_group_run``: one workgroup per job, fp64 throughout).
+
+    Each problem is a dict as ``res_nmtf_inner`` receives a job: ``data`` (pre-processed views), ``k``, ``init_f`` /
+    ``init_s`` / ``init_g`` per view, optional ``init_lam`` / ``init_mu`` (None: colSums of the initial F / G),
+    ``phi`` / ``xi`` / ``psi`` (symmetrised V x V or None), ``row_pairs`` / ``col_pairs`` (``[v][w]`` = the
+    ``naming.index_pairs`` of views v and w, ``(None, None)`` for NA; None: every pair NA) and ``n_iters`` (None =
+    to convergence).  Returns per problem ``{"f", "s", "g", "lambda", "mu", "all_error", "iters"}`` with F, S, G
+    normalised (``normalisation_check``).  The library refuses bad input before any device work."""
+    lib = _lib.load()
+    problems = list(problems)
+    jobs = (_lib.GroupJob * max(1, len(problems)))()
+    keep, outs = [], []
+    for q, p in enumerate(problems):
+        j = jobs[q]
+        j.struct_size = C.sizeof(_lib.GroupJob)
+        data = [_f64_colmajor(x) for x in p["data"]]
+        V, k = len(data), int(p["k"])
+        if V > _lib.GROUP_MAX_VIEWS:
+            raise ValueError(f"problem {q}: at most {_lib.GROUP_MAX_VIEWS} views")
+        if any(x.ndim != 2 for x in data):
+            raise ValueError(f"problem {q}: every view must be a matrix")
+        for key in ("init_f", "init_s", "init_g", "init_lam", "init_mu"):
+            if p.get(key) is not None and len(p[key]) != V:
+                raise ValueError(f"problem {q}: {key} must hold one entry per view")
+        j.n_views, j.k = V, k
+        n_iters = p.get("n_iters")
+        j.n_iters = 0 if n_iters is None else int(n_iters)
+        cap = max(1, min(int(n_iters), int(max_iters)) if n_iters else int(max_iters))
+        out = {"f": [], "s": [], "g": [], "lambda": [], "mu": [], "all_error": np.empty(cap), "iters": np.zeros(1, np.int32)}
+        for v, x in enumerate(data):
+            n, m = x.shape
+            j.n_rows[v], j.n_cols[v] = n, m
+            try:                                  # (the library reads n k, k k and m k doubles through these pointers)
+                arrs = [x, _f64_colmajor(p["init_f"][v], (n, k)), _f64_colmajor(p["init_s"][v], (k, k)),
+                        _f64_colmajor(p["init_g"][v], (m, k))]
+            except ValueError as exc:
+                raise ValueError(f"problem {q}, view {v}: initial factor: {exc}") from None
+            for name, a in zip(("x", "f0", "s0", "g0"), arrs):
+                getattr(j, name)[v] = _dp(a)
+            keep.extend(arrs)
+            for name, key in (("lambda0", "init_lam"), ("mu0", "init_mu")):
+                vals = p.get(key)
+                if vals is not None and vals[v] is not None:
+                    a = np.ascontiguousarray(vals[v], dtype=np.float64)
+                    if a.shape != (k,):
+                        raise ValueError(f"problem {q}, view {v}: {key} must have k = {k} entries, got shape {a.shape}")
+                    keep.append(a)
+                    getattr(j, name)[v] = _dp(a)
+            for key, shape in (("f", (n, k)), ("s", (k, k)), ("g", (m, k)), ("lambda", (k,)), ("mu", (k,))):
+                out[key].append(np.zeros(shape, dtype=np.float64, order="F"))
+            j.f_out[v], j.s_out[v], j.g_out[v] = _dp(out["f"][v]), _dp(out["s"][v]), _dp(out["g"][v])
+            j.lambda_out[v], j.mu_out[v] = _dp(out["lambda"][v]), _dp(out["mu"][v])
+        for name in ("phi", "xi", "psi"):
+            if p.get(name) is not None:
+                a = _f64_colmajor(p[name], (V, V))
+                keep.append(a)
+                setattr(j, name, _dp(a))
+        for key, cnt, iv_name, iw_name in (("row_pairs", j.row_count, j.row_idx_v, j.row_idx_w),
+                                           ("col_pairs", j.col_count, j.col_idx_v, j.col_idx_w)):
+            pairs = p.get(key)
+            for v in range(V):
+                for w in range(V):
+                    if pairs is None or v == w or pairs[v][w] is None or pairs[v][w][0] is None:
+                        cnt[v][w] = -1
+                        continue
+                    iv = np.ascontiguousarray(pairs[v][w][0], dtype=np.int32)
+                    iw = np.ascontiguousarray(pairs[v][w][1], dtype=np.int32)
+                    if iv.shape != iw.shape or iv.ndim != 1:
+                        raise ValueError(f"problem {q}: index pairs ({v}, {w}) must be two vectors of one length")
+                    keep.extend([iv, iw])
+                    cnt[v][w] = len(iv)
+                    iv_name[v][w], iw_name[v][w] = _ip(iv), _ip(iw)
+        j.all_error, j.err_capacity, j.iters_done = _dp(out["all_error"]), cap, _ip(out["iters"])
+        outs.append(out)
+    rc = lib.resnmtf_group_run(int(device_id), len(problems), jobs, float(tol), int(max_iters))
+    if rc != _lib.OK:
+        raise ResnmtfError(rc, (lib.resnmtf_last_error(None) or b"").decode())
+    res = []
+    for out in outs:
+        it = int(out["iters"][0])
+        res.append({"f": out["f"], "s": out["s"], "g": out["g"], "lambda": out["lambda"], "mu": out["mu"],
+                    "all_error": out["all_error"][:it].copy(), "iters": it})
+    return res
+
+
 class Engine:
     def __init__(self, n_rows: Sequence[int], n_cols: Sequence[int], k: Sequence[int],
                  owned: Optional[Sequence[bool]] = None, device_id: int = 0, stream: int = 0,

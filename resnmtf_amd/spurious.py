@@ -120,7 +120,8 @@ def _check_factors(mats, what):
 
 
 def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int] = None, device_id: int = 0,
-                     group=None, max_iters: int = 100000, shuffled_f=None, jsd: Optional[Callable] = None) -> dict:
+                     group=None, max_iters: int = 100000, shuffled_f=None, jsd: Optional[Callable] = None,
+                     grouped: bool = False) -> dict:
     """``check_biclusters`` (``R/obtain_bicl.r:113-133``) with ``get_thresholds`` (``:80-102``): returns
     ``{"score": n_views x K, "avg_threshold": n_views, "max_threshold": n_views}``.
 
@@ -128,7 +129,12 @@ def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int
     ``num_repeats`` shuffled factorisations run on the device to convergence (``n_iters`` is not forwarded by the
     reference either; ``max_iters`` guards them), drawn from ``seed``, sharded over ``group``'s ranks; the scores come
     from ``resnmtf_jsd_pairs``.  Test hooks: ``shuffled_f`` (a list of ``num_repeats`` lists of per-view F matrices:
-    no factorisation) and ``jsd(cols, pairs) -> scores`` (replaces the device scorer)."""
+    no factorisation) and ``jsd(cols, pairs) -> scores`` (replaces the device scorer).  ``grouped=True``: the shuffled
+    factorisations are ``batched.shuffled_jobs(data, K, num_repeats, seed)`` -- shuffled on the host, re-normalised
+    (``check_data``), to convergence -- run in one ``batched.run_jobs_grouped`` call (fp64, one workgroup per job)
+    instead of ``shuffles_on_device``; ``group`` is then not used.  At the default 5 repeats this is slower than the
+    default path (the grouped kernel is latency-bound per job): it buys fp64 shuffled fits, not
+    speed."""
     if isinstance(num_repeats, bool) or int(num_repeats) != num_repeats or num_repeats < 2:
         raise ValueError("num_repeats must be an integer >= 2 (the reference indexes a second shuffled repeat)")
     R = int(num_repeats)
@@ -150,6 +156,11 @@ def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int
     if K * K * R * (R - 1) // 2 < 2:
         raise ValueError("a single null score (K = 1, num_repeats = 2): stats::density needs two")
     _check_factors(output_f, "output_f")
+    if shuffled_f is None and grouped:
+        from . import batched
+        reps = batched.run_jobs_grouped(batched.shuffled_jobs(views, K, R, seed=0 if seed is None else int(seed)),
+                                        device_id=device_id, pre_processed=False, max_iters=max_iters)
+        shuffled_f = [rep["output_f"] for rep in reps]
     if shuffled_f is None:
         from . import batched
         dev = batched.DeviceData(views, device_id=device_id, pre_processed=True)
@@ -186,17 +197,17 @@ def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int
     return {"score": score, "avg_threshold": avg, "max_threshold": mx}
 
 
-def remove_spurious(data, results: dict, num_repeats: int = 5, **kwargs) -> dict:
+def remove_spurious(data, results: dict, num_repeats: int = 5, *, grouped: bool = False, **kwargs) -> dict:
     """The removal step of ``obtain_biclusters`` (``R/obtain_bicl.r:176-188``) on a ``res_nmtf_inner(spurious=False)``
     / ``apply_resnmtf(spurious=False, stability=False)`` result: with ``check = check_biclusters(data,
     results["output_f"], num_repeats, **kwargs)``, view i's cluster columns ``relations`` (``which.max`` of every S
     column) flagged by ``score < max_threshold | score == 0`` are zeroed in ``row_clusters`` and ``col_clusters``.
     Returns a copy (F, S, G unchanged; ``results`` is not modified) with ``"spurious"``: ``check`` plus ``"removed"``,
-    the n_views x K mask of the zeroed cluster columns."""
+    the n_views x K mask of the zeroed cluster columns.  ``grouped`` is passed on to ``check_biclusters``."""
     if not results.get("row_clusters") or not results.get("col_clusters"):
         raise ValueError("results has no cluster matrices (a no_clusts result): nothing to remove")
     _check_factors(results["output_s"], "output_s")
-    check = check_biclusters(data, results["output_f"], num_repeats, **kwargs)
+    check = check_biclusters(data, results["output_f"], num_repeats, grouped=grouped, **kwargs)
     out = dict(results)
     out["row_clusters"] = [np.array(rc, dtype=np.float64, copy=True) for rc in results["row_clusters"]]
     out["col_clusters"] = [np.array(cc, dtype=np.float64, copy=True) for cc in results["col_clusters"]]
