@@ -444,6 +444,26 @@ int resnmtf_relevance(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, 
 int resnmtf_jsd_pairs(int device_id, int n, int n_cols, const double* cols, int n_pairs, const int* pairs, double* out);
 
 /*
+ * Bisilhouette (res_nmtf_inner's `bisil`, R/obtain_bicl.r:189-199, and the score the k sweep of apply_resnmtf ranks,
+ * R/main.r:291-312 with extract_bisils R/utils.r:203-210): the per-member silhouettes of view v's biclusters that
+ *     bisilhouette::bisilhouette(data[[i]], row_clustering[[i]], col_clustering[[i]], method = distance)
+ * combines (the combination -- bicluster, view and overall means -- stays on the host, resnmtf_amd/bisil.py).
+ * row_clusters / col_clusters: n_rows[v] x k and n_cols[v] x k, column-major 0 / 1 fp64 as resnmtf_finalise emits them;
+ * k may differ from the handle's k[v] (e.g. a data-only handle).  Bicluster l = (rows I_l, columns J_l); it is active
+ * when both are non-empty.  For a member i of an active I_l: a = mean distance to I_l \ {i}, b = min over the other
+ * active l' of the mean distance to I_l' \ {i} (empty sets skipped), both on bicluster l's columns J_l; s = (b - a) /
+ * max(a, b), 0 when |I_l| = 1, no l' is left or max(a, b) = 0.  The columns likewise, on the rows I_l.  metric: 0 =
+ * euclidean, 1 = manhattan, 2 = cosine (1 - x.y / (|x| |y|); 1 when exactly one norm is 0, 0 when both are).
+ * row_sil / col_sil receive n_rows[v] x k and n_cols[v] x k column-major, 0 at non-members and inactive biclusters.
+ * The data are the view's fp32 device image (no upload); distances, sums, a, b and s are fp64, every sum in an order
+ * fixed by the shapes and clusters (no atomics): bitwise reproducible.  Blocking.  Refused before any launch: NULL
+ * pointers, a bad view, k outside [1, 64], entries other than 0 / 1, an unknown metric (RESNMTF_ERR_INVALID); a sparse
+ * view, a view without data on this handle (RESNMTF_ERR_STATE).  DESIGN.md section 13.
+ */
+int resnmtf_bisil(resnmtf_handle* h, int v, int k, const double* row_clusters, const double* col_clusters, int metric,
+                  double* row_sil, double* col_sil);
+
+/*
  * Many small factorisations in one launch (the k sweep, the shuffled fits of obtain_shuffled_f, the sub-sample fits of
  * stability_check): res_nmtf_inner (R/main.r:32-140) for every job, one workgroup per job, fp64 throughout.  A job is
  * what res_nmtf_inner receives: pre-processed views, explicit initial factors, symmetrised restrictions and the

@@ -109,6 +109,7 @@ SIGNATURES = {
     "resnmtf_relevance": (C.c_int, [_h, C.c_int, _h, C.c_int, _ip, _ip, _dp]),
     "resnmtf_jsd_pairs": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, _ip, _dp]),
     "resnmtf_group_run": (C.c_int, [C.c_int, C.c_int, C.POINTER(GroupJob), C.c_double, C.c_int]),
+    "resnmtf_bisil": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_reserve_sweeps": (C.c_int, [_h, C.c_int]),
     "resnmtf_prepare": (C.c_int, [_h]),
     "resnmtf_phase": (C.c_int, [_h, C.c_int, C.c_int, C.c_int]),

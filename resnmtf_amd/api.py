@@ -13,9 +13,11 @@ Spurious-bicluster removal is a separate post-step on a finished result (``check
 ``remove_spurious``, from ``spurious.py``): the shuffled factorisations and the Jensen-Shannon scores run on the
 device.  The ``spurious=True`` flags of the entry points below still raise ``NotImplementedError``.
 
-Deliberately NOT implemented here (out of scope): the bisilhouette score and
-the k sweep -- they are statistics on top of finished factorisations and stay on the R side.
-Requests for them raise ``NotImplementedError`` instead of silently doing something else.
+The bisilhouette score (``bisil``, ``R/obtain_bicl.r:189-199``) is an opt-in here: ``res_nmtf_inner(score_bisil=True)``
+scores the result on the device (per-member silhouettes from ``resnmtf_bisil``, combined by ``bisil.py``), and
+``apply_resnmtf(k_val=None, k_sweep=True)`` runs the reference's k sweep on it (``R/main.r:269-334``).  Its definition
+restates the published score (the R package's source is not available): parity with ``bisilhouette`` is unpinned.
+Without the opt-ins ``bisil`` stays ``None`` and ``k_val=None`` raises ``NotImplementedError``, as before.
 """
 from __future__ import annotations
 
@@ -24,7 +26,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import naming, sparse
+from . import bisil, naming, sparse
 from .engine import Engine
 from .spurious import check_biclusters, remove_spurious  # noqa: F401  (post-steps, R/obtain_bicl.r:113-188)
 
@@ -96,7 +98,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
                    n_iters=None, num_repeats=5, spurious=True, distance="euclidean",
                    no_clusts=False, *, row_names=None, col_names=None, device_id: int = 0,
                    max_iters: int = 100000, seed: Optional[int] = None, engine_opts: Optional[dict] = None,
-                   host_init: bool = False, return_init: bool = False):
+                   host_init: bool = False, return_init: bool = False, score_bisil: bool = False):
     """``res_nmtf_inner`` (``R/main.r:32-140``).
 
     ``data``: list of pre-processed (non-negative, column-normalised) matrices; ``row_indices[v][w]``
@@ -108,7 +110,9 @@ def res_nmtf_inner(data, row_indices, column_indices,
     init noise, ``host_init`` (without explicit initial factors: ``False`` = ``init_mats_inner`` on
     the device, randomized top-k SVD on the pass kernels, milliseconds; ``True`` = NumPy's full SVD
     on the host as the reference's ``svd()``, seconds to minutes -- statistically equivalent),
-    ``return_init`` (adds ``"init"``: the (F, S, G, lambda, mu) per view the loop started from).
+    ``return_init`` (adds ``"init"``: the (F, S, G, lambda, mu) per view the loop started from), ``score_bisil``
+    (``"bisil"`` holds the bisilhouette score of the result under ``distance``, computed on the device before the
+    engine closes, ``bisil.score``; dense views only; default ``None`` as before).
     """
     data = _views(data)
     n_v = len(data)
@@ -127,6 +131,8 @@ def res_nmtf_inner(data, row_indices, column_indices,
     for v in range(n_v):
         if is_sp[v]:
             sparse.validate(data[v], f"view {v}")
+    if score_bisil and any(is_sp):
+        raise NotImplementedError("the bisilhouette score of sparse views is not supported (dense views only)")
     if any(is_sp) and host_init and (init_f is None or init_g is None or init_s is None):
         raise NotImplementedError("host_init=True (NumPy's dense SVD) is not available for sparse views; the device "
                                   "initialisation (host_init=False) works on them")
@@ -163,6 +169,9 @@ def res_nmtf_inner(data, row_indices, column_indices,
             out_f.append(f); out_s.append(s); out_g.append(g); row_cl.append(rc); col_cl.append(cc)
             _, _, _, lv, mv = eng.get_factors(v)
             lams.append(lv); mus.append(mv)
+        score = None
+        if score_bisil and not no_clusts:                                                         # obtain_bicl.r:189-199
+            score = bisil.score(row_cl, col_cl, distance, engine=eng)
     finally:
         eng.close()
     if no_clusts:                                                                                 # main.r:115-120
@@ -177,7 +186,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
     res = {
         "output_f": out_f, "output_s": out_s, "output_g": out_g,
         "Error": error, "All_Error": total_err,
-        "bisil": None,            # bisilhouette::bisilhouette is not available offline
+        "bisil": score,           # None unless score_bisil (bisil.py; parity with bisilhouette::bisilhouette unpinned)
         "row_clusters": row_cl, "col_clusters": col_cl,
         "lambda": lams, "mu": mus,
     }
@@ -279,16 +288,31 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                   distance="euclidean", spurious=True, num_repeats=5, no_clusts=False,
                   sample_rate=0.9, n_stability=5, stability=True, stab_thres=0.4,
                   remove_unstable=True, use_parallel=True, *, row_names=None, col_names=None,
-                  device_id: int = 0, max_iters: int = 100000, seed: Optional[int] = None):
+                  device_id: int = 0, max_iters: int = 100000, seed: Optional[int] = None,
+                  k_sweep: bool = False, return_sweep: bool = False, sweep_runner: Optional[Callable] = None):
     """``apply_resnmtf`` (``R/main.r:214-335``) for a known ``k_val``: naming, shared-name maps, restriction
     symmetrisation, non-negativity shift and column normalisation on the host, then the device loop and -- with
     ``stability=True`` (the default) and ``spurious=False`` -- ``stability_check`` on the pre-processed data, as
     ``R/main.r:255-262`` does.  As at that call site, ``remove_unstable`` is NOT forwarded: ``stability_check``
     always runs with its default ``remove_unstable=True`` (unstable biclusters are zeroed whatever is passed here).
     ``stab_thres`` defaults to 0.4 here, against 0.6 in ``stability_check``.  ``stability=True`` with
-    ``spurious=True`` is refused (spurious-bicluster removal is outside the accelerated path)."""
+    ``spurious=True`` is refused (spurious-bicluster removal is outside the accelerated path).
+
+    ``k_val=None`` with the keyword-only opt-in ``k_sweep=True``: the reference's k sweep (``R/main.r:269-334``, see
+    ``_sweep``): every k in ``k_min:k_max`` factorised from one upload (``batched.k_sweep_on_device``, seeds
+    ``seed + k``), each result scored by ``bisil`` on the device, the first maximum kept, the range extended by one
+    while its largest k scores best; then ``stability_check`` on the pick WITH ``remove_unstable`` forwarded
+    (``R/main.r:324-332``, unlike the ``k_val`` branch).  The result is the picked ``res_nmtf_inner`` result.  Test
+    hooks: ``return_sweep`` adds ``"k_sweep": {"k": [...], "bisil": [...]}``; ``sweep_runner(k)`` replaces one
+    factorisation and its score (a result dict with ``"bisil"``; nothing touches the device).  Without ``k_sweep``,
+    ``k_val=None`` raises ``NotImplementedError`` as before."""
     data = _views(data)
     n_v = len(data)
+    if k_val is None and k_sweep:
+        return _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k_max, distance, spurious,
+                              num_repeats, no_clusts, sample_rate, n_stability, stability, stab_thres, remove_unstable,
+                              row_names=row_names, col_names=col_names, device_id=device_id, max_iters=max_iters,
+                              seed=seed, return_sweep=return_sweep, sweep_runner=sweep_runner)
     if k_val is None:
         raise NotImplementedError("the k sweep (R/main.r:279-321) needs the bisilhouette score, which is "
                                   "outside the accelerated path; pass k_val")
@@ -320,4 +344,106 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                                   no_clusts, distance, sample_rate, n_stability, stab_thres,
                                   row_names=rn, col_names=cn, device_id=device_id, seed=seed,
                                   max_iters=max_iters)
+    return results
+
+
+def _check_whole_number(x, name):
+    """``check_whole_number`` (``R/utils.r:220-227``)."""
+    if not isinstance(x, (int, float, np.integer, np.floating)) or isinstance(x, bool):
+        raise ValueError(f"{name} must be a numeric.")
+    if np.floor(x) != x or x <= 0:
+        raise ValueError(f"{name} must be a positive integer.")
+
+
+def _sweep(run: Callable, k_min: int, k_max: int, cap: int, initial: Optional[list] = None):
+    """The selection of ``R/main.r:269-318``: ``run(k)`` -> a result with ``"bisil"`` for every k in
+    ``k_min:k_max`` (or ``initial``, those results already computed), the first maximum (``which.max``), then one more
+    k while the pick is the largest k scored.
+    The reference would stop with an error once k + 1 exceeds a view's column count; here the range stops at ``cap``
+    (``min(ncol of the views, 64)``) with a warning and the best so far is kept.  Returns (ks, scores, results, pick)."""
+    ks = list(range(k_min, k_max + 1))
+    results = list(initial) if initial is not None else [run(k) for k in ks]
+    scores = [float(r["bisil"]) for r in results]
+    pick = int(np.argmax(scores))                                                                 # main.r:291 (first max)
+    while ks[pick] == ks[-1]:                                                                     # main.r:295-312
+        if ks[-1] + 1 > cap:
+            warnings.warn(f"the k sweep stops at k = {ks[-1]}: k + 1 would exceed min(ncol of the views, 64) = {cap}; "
+                          "the best k so far is kept")
+            break
+        ks.append(ks[-1] + 1)
+        results.append(run(ks[-1]))
+        scores.append(float(results[-1]["bisil"]))
+        pick = int(np.argmax(scores))
+    return ks, scores, results, pick
+
+
+def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k_max, distance, spurious, num_repeats,
+                   no_clusts, sample_rate, n_stability, stability, stab_thres, remove_unstable, *, row_names, col_names,
+                   device_id, max_iters, seed, return_sweep, sweep_runner):
+    """``apply_resnmtf`` with ``k_val = NULL`` (``R/main.r:269-334``); see ``apply_resnmtf``."""
+    n_v = len(data)
+    for name, val in (("n_iters", n_iters), ("num_repeats", num_repeats), ("n_stability", n_stability)):
+        if val is not None and (int(val) != val or val < 1):
+            raise ValueError(f"{name} must be a positive integer.")                               # utils.r:220-253
+    _check_whole_number(k_min, "k_min")
+    _check_whole_number(k_max, "k_max")
+    if k_max <= k_min:
+        raise ValueError("k_max must be greater than k_min.")                                     # utils.r:250-252
+    k_min, k_max = int(k_min), int(k_max)
+    if distance not in _DISTANCES:
+        raise ValueError("distance must be one of 'euclidean', 'manhattan' or 'cosine'.")         # utils.r:425
+    _check_stability_numbers(sample_rate, stab_thres)                                             # utils.r:286-300
+    if spurious and not no_clusts:
+        raise NotImplementedError("spurious-bicluster removal (R/obtain_bicl.r:31-133) is outside the accelerated "
+                                  "path; pass spurious=False")
+    if no_clusts:
+        raise ValueError("the k sweep ranks the biclusters by their bisilhouette score: no_clusts=True has none")
+    if any(sparse.is_sparse(d) for d in data):
+        raise NotImplementedError("the k sweep scores with the bisilhouette, which is not supported for sparse views "
+                                  "(dense views only); pass k_val")
+    if init_f is not None or init_s is not None or init_g is not None:
+        raise NotImplementedError("the k sweep starts every k from the device's SVD initialisation; explicit initial "
+                                  "factors are not supported with k_val=None")
+    cap = min(min(d.shape[1] for d in data), 64)
+    if k_max > cap:
+        raise ValueError("k_vec must be a vector of integers less than or equal to the ranks of the views.")
+    seed = 0 if seed is None else int(seed)
+    rn, cn = naming.give_names(data, phi, psi, row_names, col_names)                              # main.r:228
+    phi_m = naming.init_rest_mats(phi, n_v)                                                       # main.r:233-235
+    psi_m = naming.init_rest_mats(psi, n_v)
+    xi_m = naming.init_rest_mats(xi, n_v)
+    data = naming.check_data(data)                                                                # main.r:237
+    dev = None
+    try:
+        if sweep_runner is None:
+            from . import batched
+            dev = batched.DeviceData(data, phi_m, xi_m, psi_m, rn, cn, device_id=device_id, pre_processed=True)
+
+            def scored(r):                                  # a res_nmtf_inner result with its bisil (main.r:131-139)
+                out = {key: r[key] for key in ("output_f", "output_s", "output_g", "Error", "All_Error")}
+                out["bisil"] = bisil.score(r["row_clusters"], r["col_clusters"], distance, engine=dev.base)
+                out.update({key: r[key] for key in ("row_clusters", "col_clusters", "lambda", "mu")})
+                return out
+
+            # every k, the extra ones included, with the correct shared-column maps (R's extension loop passes NULL
+            # ones, R/main.r:305-309; DESIGN.md section 13)
+            def run(k):
+                return scored(dev.factorise(k, n_iters, seed + k, max_iters=max_iters, tag=f"k={k}", return_lm=True))
+
+            initial = [scored(r) for r in batched.k_sweep_on_device(dev, k_min, k_max, n_iters, seed,       # main.r:279-290
+                                                                    max_iters=max_iters, return_lm=True)]
+        else:
+            run, initial = sweep_runner, None
+        ks, scores, results, pick = _sweep(run, k_min, k_max, cap, initial)
+    finally:
+        if dev is not None:
+            dev.close()
+    results = results[pick]                                                                       # main.r:313-314
+    if stability:                                                                                 # main.r:324-332
+        results = stability_check(data, results, [ks[pick]] * n_v, phi_m, xi_m, psi_m, n_iters, spurious, num_repeats,
+                                  no_clusts, distance, sample_rate, n_stability, stab_thres, remove_unstable,
+                                  row_names=rn, col_names=cn, device_id=device_id, seed=seed, max_iters=max_iters)
+    if return_sweep:
+        results = dict(results)
+        results["k_sweep"] = {"k": ks, "bisil": scores}
     return results

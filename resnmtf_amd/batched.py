@@ -10,8 +10,8 @@ collective in the data path; the results are gathered as Python objects at the e
 
 Stability selection is scored here too: ``stability_relevance_on_device`` runs the repeats of ``stability_check``
 and reduces each sub-sample's factorisation to its relevance values on the device (``resnmtf_relevance``).  What is
-NOT here, on purpose: the other scores computed from the factorisations (bisilhouette, JSD) -- statistics on finished
-results that stay on the R side (``bisilhouette`` is not even available offline).
+NOT here: the other scores computed from the factorisations -- the bisilhouette (``bisil.py``, scored on
+``DeviceData.base`` by the k sweep of ``api.apply_resnmtf``) and the JSD scores (``spurious.py``).
 """
 from __future__ import annotations
 
@@ -380,7 +380,8 @@ class DeviceData:
 
     def factorise(self, k: int, n_iters: Optional[int] = None, seed: int = 0, shuffle_seed: Optional[int] = None,
                   max_iters: int = 100000, tag: str = "", samples=None, return_init: bool = False,
-                  return_data: bool = False, relevance: bool = False, keep_clusters: bool = False) -> dict:
+                  return_data: bool = False, relevance: bool = False, keep_clusters: bool = False,
+                  return_lm: bool = False) -> dict:
         """One factorisation with k biclusters per view: views copied -- or, with ``shuffle_seed``, shuffled as
         ``obtain_shuffled_f`` does (no restrictions, fresh names; redrawn while a row or a column of the shuffled
         matrix sums to zero, ``R/obtain_bicl.r:14-18``), or, with ``samples = (row_samples, col_samples)``,
@@ -391,7 +392,8 @@ class DeviceData:
         ``relevance`` (with ``samples``): instead of finalise, score the sub-sample's clusters against the reference
         clusters set on ``self.base`` (``resnmtf_relevance``, ``R/stability_analysis.r:268-276``) -- the result holds
         the n_views x k ``"relevance"`` matrix and no factors; ``keep_clusters`` adds the sub-sample's own binary
-        clusters (a test hook: they cost a finalise download)."""
+        clusters (a test hook: they cost a finalise download).  ``return_lm`` adds ``"lambda"`` / ``"mu"`` per view (the
+        keys of a ``res_nmtf_inner`` result, for the k sweep of ``apply_resnmtf``)."""
         from . import naming
         from .engine import Engine
         n_v = len(self.data_shapes)
@@ -452,6 +454,7 @@ class DeviceData:
                 fin = [eng.finalise(v) for v in range(n_v)] if keep_clusters else None
             else:
                 fin = [eng.finalise(v) for v in range(n_v)]
+                lms = [eng.get_factors(v)[3:] for v in range(n_v)] if return_lm else None
         finally:
             eng.close()
         error = float(np.mean(errs[-10:])) if n_iters is None else float(errs[-1])           # R/main.r:126-130
@@ -469,16 +472,21 @@ class DeviceData:
                "row_names": rn, "col_names": cn}
         if return_init:
             res["init"] = init_state
+        if return_lm:
+            res["lambda"] = [lm[0] for lm in lms]
+            res["mu"] = [lm[1] for lm in lms]
         if return_data:
             res["data"] = data_used
         return res
 
 
-def k_sweep_on_device(dev: DeviceData, k_min: int = 3, k_max: int = 8, n_iters=None, seed: int = 0, group=None) -> List[dict]:
+def k_sweep_on_device(dev: DeviceData, k_min: int = 3, k_max: int = 8, n_iters=None, seed: int = 0, group=None,
+                      max_iters: int = 100000, return_lm: bool = False) -> List[dict]:
     """The factorisations of the k sweep (``R/main.r:279-290``) from one upload; sharded round-robin over
     the ranks of an initialised process group (every rank holds its own ``DeviceData``)."""
     ks = list(range(k_min, k_max + 1))
-    return run_jobs(ks, group=group, runner=lambda k: dev.factorise(k, n_iters, seed + k, tag=f"k={k}"))
+    return run_jobs(ks, group=group, runner=lambda k: dev.factorise(k, n_iters, seed + k, max_iters=max_iters, tag=f"k={k}",
+                                                                    return_lm=return_lm))
 
 
 def shuffles_on_device(dev: DeviceData, n_clusts: int, num_repeats: int = 5, n_iters=None, seed: int = 0, group=None,

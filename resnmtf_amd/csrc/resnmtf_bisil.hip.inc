@@ -1,0 +1,222 @@
+// resnmtf_bisil.hip.inc -- per-member silhouettes of a view's biclusters (resnmtf_bisil), the device side of the
+// bisilhouette score that res_nmtf_inner reports as `bisil` (R/obtain_bicl.r:189-199) and that the k sweep of
+// apply_resnmtf ranks (R/main.r:291-312).  Included by resnmtf_hip.hip; fp64 arithmetic over the fp32 image values.
+// DESIGN.md section 13 holds the definition; this unit and resnmtf_amd/bisil.py are its only two statements.
+//
+// One side (rows, or columns with the roles swapped) of one active bicluster k is three or four launches:
+//   bisil_gather_kernel   G[f][u] = X(U[u], J_k[f]) as fp32, feature-major [|J_k|][U_pad]: U = the union of the active
+//                         biclusters' members (the only points a silhouette compares with), zero-padded to 64.
+//   bisil_norm_kernel     (cosine) ||G[:, u]||^2 in fp64, features in ascending order.
+//   bisil_dist_kernel     one workgroup per (64 members of I_k) x (one chunk of U's 64-wide tiles): a 64 x 64 distance
+//                         tile on fp64 VALU (4 x 4 per thread over a 32-feature LDS stage), then contracted at once with
+//                         the 0/1 membership bits of the 64 others: every member keeps its K per-bicluster sums in
+//                         registers (K / 4 per thread).  The member itself is skipped by index, so d(i, i) never enters.
+//   bisil_epilogue_kernel one wave per member: the chunk partials summed in chunk order (a lane per bicluster), a,
+//                         b and s.
+// Determinism: every sum has an order fixed by the shapes and the clusters alone (features ascending, tiles ascending
+// inside a chunk, chunks ascending), no atomics -- two calls give bitwise equal silhouettes.
+
+namespace {
+
+constexpr int BISIL_TILE = 64;        // members per workgroup = others per distance tile
+constexpr int BISIL_FT = 32;          // features per LDS stage
+constexpr int BISIL_THREADS = 256;
+enum { BISIL_EUCLIDEAN = 0, BISIL_MANHATTAN = 1, BISIL_COSINE = 2 };
+
+// G[f * upad + u] = img(pts[u], feat[f]) for u < n_u, 0 for n_u <= u < upad; img is tile-major with stride ld
+// (the row side reads Xt32 (column feat, row pts), the column side X32 (row feat, column pts): xidx(feat, pts, ld))
+__global__ void __launch_bounds__(256)
+bisil_gather_kernel(const float* __restrict__ img, size_t ld, const int* __restrict__ feat, int nf,
+                    const int* __restrict__ pts, int n_u, int upad, float* __restrict__ G) {
+  const size_t total = (size_t)nf * upad;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+    const int f = (int)(e / upad), u = (int)(e % upad);
+    G[e] = u < n_u ? img[xidx(feat[f], pts[u], ld)] : 0.f;
+  }
+}
+
+__global__ void __launch_bounds__(256)
+bisil_norm_kernel(const float* __restrict__ G, int nf, int upad, double* __restrict__ norm2) {
+  const int u = blockIdx.x * 256 + threadIdx.x;
+  if (u >= upad) return;
+  double s = 0.0;
+  for (int f = 0; f < nf; ++f) { const double x = (double)G[(size_t)f * upad + u]; s = fma(x, x, s); }
+  norm2[u] = s;
+}
+
+struct BisilShared {
+  union {
+    struct { double a[BISIL_FT][BISIL_TILE]; double b[BISIL_FT][BISIL_TILE]; } f;   // member / other features
+    double d[BISIL_TILE][BISIL_TILE + 1];                                             // distance tile (padded rows)
+  };
+  unsigned long long msk[BISIL_TILE];   // membership bits of the tile's others
+  int mp[BISIL_TILE];                   // the workgroup's members as positions in U
+};
+
+// partial[((chunk * n_mem) + member) * K + l] = sum of d(member, u) over the u of this chunk with bit l set, u != member
+template <int METRIC, int KQ>
+__global__ void __launch_bounds__(BISIL_THREADS)
+bisil_dist_kernel(const float* __restrict__ G, int nf, int upad, int n_u, const int* __restrict__ mpos, int n_mem,
+                  const unsigned long long* __restrict__ umask, const double* __restrict__ norm2, int K,
+                  int chunk_tiles, double* __restrict__ partial) {
+  __shared__ BisilShared sh;
+  const int t = threadIdx.x;
+  const int m0 = blockIdx.x * BISIL_TILE;
+  const int chunk = blockIdx.y;
+  const int tile_beg = chunk * chunk_tiles;
+  const int tile_end = min(upad / BISIL_TILE, tile_beg + chunk_tiles);
+  if (t < BISIL_TILE) sh.mp[t] = m0 + t < n_mem ? mpos[m0 + t] : 0;   // (out-of-range members: position 0, discarded)
+  const int tm = t & 15, to = t >> 4;                                  // distances: members tm + 16 a, others to + 16 b
+  const int ci = t >> 2, cq = t & 3;                                   // contraction: member ci, biclusters cq + 4 s
+  double sums[KQ];
+#pragma unroll
+  for (int s = 0; s < KQ; ++s) sums[s] = 0.0;
+  __syncthreads();
+  for (int tile = tile_beg; tile < tile_end; ++tile) {
+    const int u0 = tile * BISIL_TILE;
+    double acc[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
+    for (int f0 = 0; f0 < nf; f0 += BISIL_FT) {
+#pragma unroll
+      for (int r = 0; r < BISIL_FT * BISIL_TILE / BISIL_THREADS; ++r) {
+        const int e = t + r * BISIL_THREADS, f = e >> 6, c = e & 63;
+        const bool in = f0 + f < nf;
+        const size_t row = (size_t)min(f0 + f, nf - 1) * upad;     // (clamped: every load stays inside G)
+        sh.f.a[f][c] = in ? (double)G[row + sh.mp[c]] : 0.0;
+        sh.f.b[f][c] = in ? (double)G[row + u0 + c] : 0.0;
+      }
+      __syncthreads();
+#pragma unroll 4
+      for (int f = 0; f < BISIL_FT; ++f) {
+        double xa[4], xb[4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) xa[a] = sh.f.a[f][tm + 16 * a];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) xb[b] = sh.f.b[f][to + 16 * b];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            if (METRIC == BISIL_EUCLIDEAN) { const double df = xa[a] - xb[b]; acc[a][b] = fma(df, df, acc[a][b]); }
+            else if (METRIC == BISIL_MANHATTAN) acc[a][b] += fabs(xa[a] - xb[b]);
+            else acc[a][b] = fma(xa[a], xb[b], acc[a][b]);
+          }
+      }
+      __syncthreads();
+    }
+    // the feature stages are done (last barrier above): the distance tile takes their place
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const int ma = tm + 16 * a;
+      const int pa = sh.mp[ma];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int ob = to + 16 * b, u = u0 + ob;
+        double d;
+        if (METRIC == BISIL_EUCLIDEAN) d = sqrt(fmax(acc[a][b], 0.0));
+        else if (METRIC == BISIL_MANHATTAN) d = acc[a][b];
+        else {
+          const double na = norm2[pa], nb = norm2[u];
+          if (na == 0.0 && nb == 0.0) d = 0.0;
+          else if (na == 0.0 || nb == 0.0) d = 1.0;
+          else d = 1.0 - acc[a][b] / (sqrt(na) * sqrt(nb));
+        }
+        sh.d[ma][ob] = (u == pa || u >= n_u) ? 0.0 : d;
+      }
+    }
+    if (t < BISIL_TILE) sh.msk[t] = u0 + t < n_u ? umask[u0 + t] : 0ull;
+    __syncthreads();
+    for (int u = 0; u < BISIL_TILE; ++u) {
+      const double d = sh.d[ci][u];
+      const unsigned long long mk = sh.msk[u] >> cq;
+#pragma unroll
+      for (int s = 0; s < KQ; ++s) sums[s] += ((mk >> (4 * s)) & 1ull) ? d : 0.0;
+    }
+    __syncthreads();
+  }
+  if (m0 + ci < n_mem) {
+    double* out = partial + ((size_t)chunk * n_mem + m0 + ci) * K;
+#pragma unroll
+    for (int s = 0; s < KQ; ++s)
+      if (cq + 4 * s < K) out[cq + 4 * s] = sums[s];
+  }
+}
+
+// per member of bicluster k: a = mean over I_k \ {i}, b = min over the other active l with I_l \ {i} non-empty,
+// s = (b - a) / max(a, b); 0 for a singleton I_k, no l left or max(a, b) = 0.  sil[k * n_pts + point] = s.
+// One wave per member, lane l sums bicluster l's chunk partials in chunk order (coalesced over l); lane 0 then takes
+// a and b from the K means in bicluster order.
+__global__ void __launch_bounds__(256)
+bisil_epilogue_kernel(const double* __restrict__ partial, int n_chunks, int n_mem, int K, int k,
+                      const int* __restrict__ mpos, const unsigned long long* __restrict__ umask,
+                      const int* __restrict__ upts, const int* __restrict__ cnt, unsigned long long active, int n_pts,
+                      double* __restrict__ sil) {
+  __shared__ double mean_s[4][64];
+  __shared__ int ok_s[4][64];
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  const int m = blockIdx.x * 4 + w;
+  double mean = 0.0;
+  int ok = 0;
+  if (m < n_mem && l < K && ((active >> l) & 1ull)) {
+    const int c = cnt[l] - (int)((umask[mpos[m]] >> l) & 1ull);
+    if (c > 0) {
+      double s = 0.0;
+      for (int ch = 0; ch < n_chunks; ++ch) s += partial[((size_t)ch * n_mem + m) * K + l];
+      mean = s / (double)c;
+      ok = 1;
+    }
+  }
+  mean_s[w][l] = mean;
+  ok_s[w][l] = ok;
+  __syncthreads();
+  if (l != 0 || m >= n_mem) return;
+  double a = 0.0, b = 0.0;
+  bool has_a = false, has_b = false;
+  for (int j = 0; j < K; ++j) {
+    if (!ok_s[w][j]) continue;
+    if (j == k) { a = mean_s[w][j]; has_a = true; }
+    else if (!has_b || mean_s[w][j] < b) { b = mean_s[w][j]; has_b = true; }
+  }
+  double s = 0.0;
+  if (has_a && has_b) {
+    const double mx = fmax(a, b);
+    if (mx != 0.0) s = (b - a) / mx;
+  }
+  sil[(size_t)k * n_pts + upts[mpos[m]]] = s;
+}
+
+// one side of resnmtf_bisil on the host: points = rows (features = columns) or the reverse; every list is 0-based
+struct BisilSide {
+  int n_pts = 0;
+  std::vector<int> upts;                      // U: the points in an active bicluster, ascending
+  std::vector<unsigned long long> umask;      // their active-bicluster bits
+  std::vector<std::vector<int>> mpos;         // per bicluster: its members as positions in U
+  std::vector<int> cnt;                       // per bicluster: |I_l|
+};
+
+template <int METRIC>
+void bisil_launch_dist_m(int kq, dim3 grid, hipStream_t st, const float* G, int nf, int upad, int n_u, const int* mpos,
+                         int n_mem, const unsigned long long* umask, const double* norm2, int K, int chunk_tiles,
+                         double* partial) {
+  switch (kq) {
+#define BISIL_CASE(KQ) case KQ: hipLaunchKernelGGL((bisil_dist_kernel<METRIC, KQ>), grid, dim3(BISIL_THREADS), 0, st, G, nf, \
+                                                   upad, n_u, mpos, n_mem, umask, norm2, K, chunk_tiles, partial); break;
+    BISIL_CASE(1) BISIL_CASE(2) BISIL_CASE(4) BISIL_CASE(8) BISIL_CASE(16)
+#undef BISIL_CASE
+    default: break;
+  }
+}
+
+// kq = ceil(K / 4) rounded up to a power of two: the per-thread bicluster sums of bisil_dist_kernel
+void bisil_launch_dist(int metric, int kq, dim3 grid, hipStream_t st, const float* G, int nf, int upad, int n_u,
+                       const int* mpos, int n_mem, const unsigned long long* umask, const double* norm2, int K,
+                       int chunk_tiles, double* partial) {
+  if (metric == BISIL_EUCLIDEAN) bisil_launch_dist_m<BISIL_EUCLIDEAN>(kq, grid, st, G, nf, upad, n_u, mpos, n_mem, umask, norm2, K, chunk_tiles, partial);
+  else if (metric == BISIL_MANHATTAN) bisil_launch_dist_m<BISIL_MANHATTAN>(kq, grid, st, G, nf, upad, n_u, mpos, n_mem, umask, norm2, K, chunk_tiles, partial);
+  else bisil_launch_dist_m<BISIL_COSINE>(kq, grid, st, G, nf, upad, n_u, mpos, n_mem, umask, norm2, K, chunk_tiles, partial);
+}
+
+}  // namespace

@@ -31,6 +31,7 @@
 #include "resnmtf_sparse.hip.inc"
 #include "resnmtf_jsd.hip.inc"
 #include "resnmtf_group.hip.inc"
+#include "resnmtf_bisil.hip.inc"
 #include "resnmtf_split_tu.h"
 #ifdef RESNMTF_SPLIT_TU      // product build: the k <= 16 pass lives in resnmtf_pass_k16.hip (its own scheduling strategy)
 #define RESNMTF_EXTERN(NW, UNR, XG, MA) extern template __global__ void pass_kernel<1, NW, UNR, XG, MA, 0>(PassArgs, KKFArgs, KKSArgs);
@@ -3108,6 +3109,153 @@ int resnmtf_relevance(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, 
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   (void)hipFree(buf);
   if (e != hipSuccess) return h->fail_hip("relevance", e);
+  return RESNMTF_OK;
+}
+
+// ---- bisilhouette (R/obtain_bicl.r:189-199): per-member silhouettes of a view's biclusters (resnmtf_bisil.hip.inc)
+int resnmtf_bisil(resnmtf_handle* h, int v, int k, const double* row_clusters, const double* col_clusters, int metric,
+                  double* row_sil, double* col_sil) {
+  if (int rc = check_view(h, v)) return rc;
+  if (!row_clusters || !col_clusters || !row_sil || !col_sil)
+    return h->fail(RESNMTF_ERR_INVALID, "row_clusters / col_clusters / row_sil / col_sil are NULL");
+  if (k < 1 || k > RESNMTF_MAX_K) return h->fail(RESNMTF_ERR_INVALID, "k must be in [1, 64]");
+  if (metric < BISIL_EUCLIDEAN || metric > BISIL_COSINE)
+    return h->fail(RESNMTF_ERR_INVALID, "metric must be 0 (euclidean), 1 (manhattan) or 2 (cosine)");
+  const ViewState& vs = h->views[v];
+  if (vs.sparse) return h->fail(RESNMTF_ERR_STATE, "bisil of a sparse view is not supported (no dense fp32 image)");
+  if (!vs.owned || !vs.has_x) return h->fail(RESNMTF_ERR_STATE, "no data on this handle for the view");
+  if (!vs.X32 || !vs.Xt32) return h->fail(RESNMTF_ERR_STATE, "bisil needs the view's fp32 images (the view holds only a 2-byte image)");
+  const int n = vs.n, m = vs.m;
+  std::vector<unsigned long long> rbits(n, 0ull), cbits(m, 0ull);
+  std::vector<int> rcount(k, 0), ccount(k, 0);
+  for (int j = 0; j < k; ++j) {
+    for (int r = 0; r < n; ++r) {
+      const double x = row_clusters[(size_t)j * n + r];
+      if (x != 0.0 && x != 1.0) return h->fail(RESNMTF_ERR_INVALID, "row_clusters entries must be 0 or 1");
+      if (x != 0.0) { rbits[r] |= 1ull << j; ++rcount[j]; }
+    }
+    for (int c = 0; c < m; ++c) {
+      const double x = col_clusters[(size_t)j * m + c];
+      if (x != 0.0 && x != 1.0) return h->fail(RESNMTF_ERR_INVALID, "col_clusters entries must be 0 or 1");
+      if (x != 0.0) { cbits[c] |= 1ull << j; ++ccount[j]; }
+    }
+  }
+  unsigned long long active = 0ull;                            // biclusters with rows and columns
+  for (int j = 0; j < k; ++j) if (rcount[j] > 0 && ccount[j] > 0) active |= 1ull << j;
+  auto build = [&](const std::vector<unsigned long long>& bits, const std::vector<int>& count, int n_pts) {
+    BisilSide s;
+    s.n_pts = n_pts; s.cnt = count; s.mpos.resize(k);
+    for (int p = 0; p < n_pts; ++p) {
+      const unsigned long long b = bits[p] & active;
+      if (!b) continue;
+      for (int j = 0; j < k; ++j) if ((b >> j) & 1ull) s.mpos[j].push_back((int)s.upts.size());
+      s.upts.push_back(p); s.umask.push_back(b);
+    }
+    return s;
+  };
+  const BisilSide side[2] = {build(rbits, rcount, n), build(cbits, ccount, m)};
+  // per side: the features of bicluster j are the other side's members of j, as point indices
+  auto features = [&](int sd, int j) {
+    std::vector<int> f;
+    const BisilSide& o = side[1 - sd];
+    for (int p : o.mpos[j]) f.push_back(o.upts[p]);
+    return f;
+  };
+  std::fill(row_sil, row_sil + (size_t)n * k, 0.0);
+  std::fill(col_sil, col_sil + (size_t)m * k, 0.0);
+  if (!active) return RESNMTF_OK;
+  // sizes: G <= max over sides and biclusters of |features| x U_pad floats (<= one X image); partials of one bicluster
+  size_t g_floats = 1, part_dbl = 1, upad_max = 64;
+  int chunks[2][RESNMTF_MAX_K] = {}, chunk_tiles[2][RESNMTF_MAX_K] = {};
+  for (int sd = 0; sd < 2; ++sd) {
+    const BisilSide& s = side[sd];
+    const int upad = round_up((int)s.upts.size(), BISIL_TILE), tiles_u = upad / BISIL_TILE;
+    upad_max = std::max<size_t>(upad_max, upad);
+    for (int j = 0; j < k; ++j) {
+      if (!((active >> j) & 1ull)) continue;
+      const int n_mem = (int)s.mpos[j].size(), tiles_m = ceil_div(n_mem, BISIL_TILE);
+      // enough workgroups to fill the device: the others are split into chunks of whole tiles, summed in order later
+      const int want = std::max(1, std::min(tiles_u, ceil_div(2048, tiles_m)));
+      chunk_tiles[sd][j] = ceil_div(tiles_u, want);
+      chunks[sd][j] = ceil_div(tiles_u, chunk_tiles[sd][j]);
+      g_floats = std::max(g_floats, (size_t)side[1 - sd].mpos[j].size() * upad);
+      part_dbl = std::max(part_dbl, (size_t)chunks[sd][j] * n_mem * k);
+    }
+  }
+  // host image of the metadata: per side [umask (u64) | upts | cnt | per active j: mpos_j | feat_j]
+  std::vector<unsigned long long> meta;
+  size_t off_mask[2], off_pts[2], off_cnt[2], off_mpos[2][RESNMTF_MAX_K], off_feat[2][RESNMTF_MAX_K];
+  {
+    std::vector<int> ints;
+    auto put = [&](const std::vector<int>& a) { const size_t o = ints.size(); ints.insert(ints.end(), a.begin(), a.end()); return o; };
+    for (int sd = 0; sd < 2; ++sd) {
+      const BisilSide& s = side[sd];
+      off_pts[sd] = put(s.upts);
+      off_cnt[sd] = put(s.cnt);
+      for (int j = 0; j < k; ++j) {
+        if (!((active >> j) & 1ull)) continue;
+        off_mpos[sd][j] = put(s.mpos[j]);
+        off_feat[sd][j] = put(features(sd, j));
+      }
+    }
+    ints.resize(round_up((int)ints.size(), 2), 0);
+    const size_t n_mask = side[0].umask.size() + side[1].umask.size();
+    meta.resize(n_mask + ints.size() / 2);
+    off_mask[0] = 0; off_mask[1] = side[0].umask.size();
+    std::copy(side[0].umask.begin(), side[0].umask.end(), meta.begin());
+    std::copy(side[1].umask.begin(), side[1].umask.end(), meta.begin() + off_mask[1]);
+    std::memcpy(meta.data() + n_mask, ints.data(), ints.size() * sizeof(int));
+    for (int sd = 0; sd < 2; ++sd) {      // int offsets -> offsets from the buffer's start, in ints
+      off_pts[sd] += 2 * n_mask; off_cnt[sd] += 2 * n_mask;
+      for (int j = 0; j < k; ++j) { off_mpos[sd][j] += 2 * n_mask; off_feat[sd][j] += 2 * n_mask; }
+    }
+  }
+  HIP_TRY(h, hipSetDevice(h->opt.device_id));
+  if (int rc = sync_both(h)) return rc;
+  // [G g_floats f32 (rounded to doubles)][norm2 upad_max][partial part_dbl][sil n k + m k] doubles | meta
+  const size_t g_dbl = (g_floats + 1) / 2, sil_dbl = (size_t)n * k + (size_t)m * k;
+  const size_t n_dbl = g_dbl + upad_max + part_dbl + sil_dbl;
+  char* buf = nullptr;
+  HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), n_dbl * sizeof(double) + meta.size() * sizeof(unsigned long long)));
+  float* G = reinterpret_cast<float*>(buf);
+  double* norm2 = reinterpret_cast<double*>(buf) + g_dbl;
+  double* partial = norm2 + upad_max;
+  double* sil = partial + part_dbl;
+  unsigned long long* dmeta = reinterpret_cast<unsigned long long*>(sil + sil_dbl);
+  const int* dints = reinterpret_cast<const int*>(dmeta);
+  hipError_t e = hipMemcpyAsync(dmeta, meta.data(), meta.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(sil, 0, sil_dbl * sizeof(double), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(norm2, 0, upad_max * sizeof(double), h->stream);
+  const int kq = k <= 4 ? 1 : k <= 8 ? 2 : k <= 16 ? 4 : k <= 32 ? 8 : 16;
+  for (int sd = 0; sd < 2 && e == hipSuccess; ++sd) {
+    const BisilSide& s = side[sd];
+    const int n_u = (int)s.upts.size(), upad = round_up(n_u, BISIL_TILE);
+    const float* img = sd == 0 ? vs.Xt32 : vs.X32;             // rows: X(row, col) = Xt32(col, row); columns: X32(row, col)
+    const size_t ld = sd == 0 ? vs.ldxt : vs.ldx;
+    double* out = sil + (sd == 0 ? 0 : (size_t)n * k);
+    for (int j = 0; j < k && e == hipSuccess; ++j) {
+      if (!((active >> j) & 1ull)) continue;
+      const int nf = (int)side[1 - sd].mpos[j].size(), n_mem = (int)s.mpos[j].size();
+      const int* feat = dints + off_feat[sd][j];
+      const int* mpos = dints + off_mpos[sd][j];
+      const size_t total = (size_t)nf * upad;
+      hipLaunchKernelGGL(bisil_gather_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0,
+                         h->stream, (const float*)img, ld, feat, nf, dints + off_pts[sd], n_u, upad, G);
+      if (metric == BISIL_COSINE)
+        hipLaunchKernelGGL(bisil_norm_kernel, dim3(ceil_div(upad, 256)), dim3(256), 0, h->stream, (const float*)G, nf, upad, norm2);
+      const dim3 grid(ceil_div(n_mem, BISIL_TILE), chunks[sd][j]);
+      const unsigned long long* umask = dmeta + off_mask[sd];
+      bisil_launch_dist(metric, kq, grid, h->stream, G, nf, upad, n_u, mpos, n_mem, umask, norm2, k, chunk_tiles[sd][j], partial);
+      hipLaunchKernelGGL(bisil_epilogue_kernel, dim3(ceil_div(n_mem, 4)), dim3(256), 0, h->stream, (const double*)partial,
+                         chunks[sd][j], n_mem, k, j, mpos, umask, dints + off_pts[sd], dints + off_cnt[sd], active, s.n_pts, out);
+      e = hipGetLastError();
+    }
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(row_sil, sil, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(col_sil, sil + (size_t)n * k, (size_t)m * k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  (void)hipFree(buf);
+  if (e != hipSuccess) return h->fail_hip("bisil", e);
   return RESNMTF_OK;
 }
 

@@ -410,6 +410,23 @@ class Engine:
         self._check(self._lib.resnmtf_relevance(self._h, v, ref_engine._h, v_ref, _ip(rows), _ip(cols), _dp(out)))
         return out
 
+    def bisil(self, v: int, rc, cc, distance: str = "euclidean"):
+        """The per-member silhouettes of view ``v``'s biclusters (``resnmtf_bisil``, the device side of
+        ``bisilhouette::bisilhouette``, ``R/obtain_bicl.r:189-199``) on the view's device copy of the data: ``rc`` /
+        ``cc`` are n x k and m x k 0 / 1 cluster matrices (k may differ from this engine's k[v]); returns ``(row_sil,
+        col_sil)``, n x k and m x k, 0 at non-members.  ``bisil.score`` turns them into the score."""
+        from .bisil import METRICS
+        if distance not in METRICS:
+            raise ValueError("distance must be one of 'euclidean', 'manhattan' or 'cosine'.")
+        rc = np.asfortranarray(np.asarray(rc, dtype=np.float64))
+        if rc.ndim != 2 or rc.shape[0] != self.n_rows[v]:
+            raise ValueError(f"row clusters must be {self.n_rows[v]} x k")
+        cc = _f64_colmajor(cc, (self.n_cols[v], rc.shape[1]))
+        k = int(rc.shape[1])
+        rs = np.zeros((self.n_rows[v], k), order="F"); cs = np.zeros((self.n_cols[v], k), order="F")
+        self._check(self._lib.resnmtf_bisil(self._h, v, k, _dp(rc), _dp(cc), METRICS[distance], _dp(rs), _dp(cs)))
+        return rs, cs
+
     def view_image_info(self, v: int):
         """(kind, rel_error): kind 0 = f32 images, 1 = fp16, 2 = uniform 16-bit integers; the relative quantisation
         error of the 2-byte image of view ``v`` measured at upload (``x_half``)."""
