@@ -427,6 +427,18 @@ int resnmtf_relevance(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, 
                       double* relevance);
 
 /*
+ * Relevance after a spurious-bicluster removal (a stability repeat of res_nmtf_inner(sub_sample, spurious = TRUE),
+ * R/stability_analysis.r:254-276): resnmtf_relevance with h's clusters cleaned first as obtain_biclusters does
+ * (R/obtain_bicl.r:176-188).  flags: k[v] bytes indexed by F column (nonzero = the removal rule flagged that column's
+ * score); cluster column j of both row_c and col_c is zeroed when flags[relations[j]] is set, relations[j] =
+ * which.max(S[, j]) computed on the device as resnmtf_finalise computes it.  Same counts, same epilogue: bitwise equal to
+ * the fp64 restatement on the cleaned clusters (a mask that empties every cluster included).  Refusals as for
+ * resnmtf_relevance, and flags NULL (RESNMTF_ERR_INVALID).
+ */
+int resnmtf_relevance_masked(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, const int* rows, const int* cols,
+                             const unsigned char* flags, double* relevance);
+
+/*
  * Spurious-bicluster scoring (check_biclusters / get_thresholds, R/obtain_bicl.r:55-133): jsd_calc (R/utils.r:95-106)
  * for a list of column pairs, replacing the R loops
  *     scores <- c(scores, jsd_calc(x1, x2))                        (calculate_f_shuffle_jsd, :55-68)
@@ -442,6 +454,25 @@ int resnmtf_relevance(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, 
  * pair index outside [0, n_cols), n * n_cols > 2^31; n_pairs = 0 returns at once.  DESIGN.md section 11.
  */
 int resnmtf_jsd_pairs(int device_id, int n, int n_cols, const double* cols, int n_pairs, const int* pairs, double* out);
+
+/*
+ * Spurious-bicluster scores of a factorisation against R shuffled ones, all on the device (check_biclusters with
+ * get_thresholds, R/obtain_bicl.r:80-133): view v of h and of each of the R handles in shuffles (same device, same n
+ * and k = K, with factors) is normalised as resnmtf_finalise normalises F (F / colSums(F), the same kernels and bits)
+ * straight into a device pool cbind(F_v, f_1, ..., f_R) (n x K (R + 1)); resnmtf_jsd_pairs' kernels then score the
+ * pairs of calculate_f_shuffle_jsd and check_biclusters over it.  score receives K doubles: score[k] = the mean of
+ * jsd_calc(F_v[, k], cbind(f_1..f_R)[, y]) over y = 1 .. R K (R/obtain_bicl.r:125-128), summed in NumPy's pairwise
+ * order (np.mean's) so that it equals the host's mean of resnmtf_jsd_pairs' values bitwise.  null_scores receives the
+ * K^2 R (R - 1) / 2 null scores in calculate_f_shuffle_jsd's order (j = 1 .. R - 1, k, l = j + 1 .. R, m); their mean
+ * and the mode of stats::density stay with the caller.  No factor leaves the device; blocking, on h's stream, after
+ * every shuffle handle's stream has drained; deterministic (no atomics in any sum).  Refused before any launch: NULL
+ * pointers or handles, a bad view, R < 2, n < 2, a shuffle handle on another device or whose view v differs in n or k,
+ * K (R + 1) > 65535, n K (R + 1) > 2^31, more than 2^31 - 1 pairs (RESNMTF_ERR_INVALID), a view without factors
+ * (RESNMTF_ERR_STATE).  A non-finite entry of a normalised F is refused after the gather, before the scoring
+ * (RESNMTF_ERR_INVALID).  DESIGN.md section 11.
+ */
+int resnmtf_spurious_scores(resnmtf_handle* h, int v, resnmtf_handle* const* shuffles, int R, double* score,
+                            double* null_scores);
 
 /*
  * Bisilhouette (res_nmtf_inner's `bisil`, R/obtain_bicl.r:189-199, and the score the k sweep of apply_resnmtf ranks,

@@ -9,9 +9,12 @@ in INTEGRATION.md.
 Stability selection (``stability_check``, ``R/stability_analysis.r:302-338``) runs here too: the sub-samples are
 gathered, factorised and scored (relevance) on the device, see ``stability_check``.
 
-Spurious-bicluster removal is a separate post-step on a finished result (``check_biclusters`` /
-``remove_spurious``, from ``spurious.py``): the shuffled factorisations and the Jensen-Shannon scores run on the
-device.  The ``spurious=True`` flags of the entry points below still raise ``NotImplementedError``.
+Spurious-bicluster removal exists as a post-step on a finished result (``check_biclusters`` / ``remove_spurious``,
+from ``spurious.py``) and, with the keyword-only opt-in ``spurious_on_device=True``, inside the entry points below as
+the reference runs it (``spurious=True``): in ``res_nmtf_inner`` before the bisilhouette, in every stability repeat
+before its relevance and for every k of the sweep; the shuffled factorisations are drawn from the engine's own device
+copy and scored on the device (``spurious.check_on_device``).  Without the opt-in ``spurious=True`` raises
+``NotImplementedError`` as before.
 
 The bisilhouette score (``bisil``, ``R/obtain_bicl.r:189-199``) is an opt-in here: ``res_nmtf_inner(score_bisil=True)``
 scores the result on the device (per-member silhouettes from ``resnmtf_bisil``, combined by ``bisil.py``), and
@@ -27,6 +30,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 import numpy as np
 
 from . import bisil, naming, sparse
+from . import spurious as _spurious
 from .engine import Engine
 from .spurious import check_biclusters, remove_spurious  # noqa: F401  (post-steps, R/obtain_bicl.r:113-188)
 
@@ -98,7 +102,8 @@ def res_nmtf_inner(data, row_indices, column_indices,
                    n_iters=None, num_repeats=5, spurious=True, distance="euclidean",
                    no_clusts=False, *, row_names=None, col_names=None, device_id: int = 0,
                    max_iters: int = 100000, seed: Optional[int] = None, engine_opts: Optional[dict] = None,
-                   host_init: bool = False, return_init: bool = False, score_bisil: bool = False):
+                   host_init: bool = False, return_init: bool = False, score_bisil: bool = False,
+                   spurious_on_device: bool = False):
     """``res_nmtf_inner`` (``R/main.r:32-140``).
 
     ``data``: list of pre-processed (non-negative, column-normalised) matrices; ``row_indices[v][w]``
@@ -112,7 +117,13 @@ def res_nmtf_inner(data, row_indices, column_indices,
     on the host as the reference's ``svd()``, seconds to minutes -- statistically equivalent),
     ``return_init`` (adds ``"init"``: the (F, S, G, lambda, mu) per view the loop started from), ``score_bisil``
     (``"bisil"`` holds the bisilhouette score of the result under ``distance``, computed on the device before the
-    engine closes, ``bisil.score``; dense views only; default ``None`` as before).
+    engine closes, ``bisil.score``; dense views only; default ``None`` as before), ``spurious_on_device`` (with
+    ``spurious=True``: ``obtain_biclusters(remove_spurious = TRUE)``, ``R/obtain_bicl.r:151-204`` -- ``num_repeats``
+    shuffles of the engine's own views, to convergence, scored on the device, the flagged cluster columns zeroed through
+    ``relations``, then ``bisil`` of the cleaned clusters; the result carries ``"spurious"`` as ``remove_spurious``
+    does and equals ``remove_spurious(data, res_nmtf_inner(..., spurious=False, seed=seed), num_repeats, seed=seed)``:
+    the shuffles use the spurious seed ``0 if seed is None else seed``, repeat r initialising with ``+ 1000 + r`` and
+    shuffling with ``seed * 7919 + r + 1``, as ``check_biclusters`` derives them; dense views only).
     """
     data = _views(data)
     n_v = len(data)
@@ -121,13 +132,19 @@ def res_nmtf_inner(data, row_indices, column_indices,
     k_vec = [int(k) for k in np.atleast_1d(k_vec)]
     if len(k_vec) != n_v:
         raise ValueError("k_vec must be a vector of the same length as the number of views.")   # utils.r:440
-    if not no_clusts and spurious:
+    if not no_clusts and spurious and not spurious_on_device:
         raise NotImplementedError(
             "spurious-bicluster removal (R/obtain_bicl.r:31-133) is outside the accelerated path; "
             "pass spurious=False or do it on the R side (INTEGRATION.md).")
+    remove = bool(spurious) and not no_clusts
     if distance not in _DISTANCES:
         raise ValueError("distance must be one of 'euclidean', 'manhattan' or 'cosine'.")         # utils.r:425
     is_sp = [sparse.is_sparse(d) for d in data]
+    if remove:
+        _spurious.check_num_repeats(num_repeats)
+        if any(is_sp):
+            raise NotImplementedError("spurious-bicluster removal needs shuffled views: device shuffles of sparse views "
+                                      "are not supported")
     for v in range(n_v):
         if is_sp[v]:
             sparse.validate(data[v], f"view {v}")
@@ -169,11 +186,16 @@ def res_nmtf_inner(data, row_indices, column_indices,
             out_f.append(f); out_s.append(s); out_g.append(g); row_cl.append(rc); col_cl.append(cc)
             _, _, _, lv, mv = eng.get_factors(v)
             lams.append(lv); mus.append(mv)
-        score = None
+        check = None
+        if remove:                                                                                # obtain_bicl.r:151-188
+            check = _spurious.check_on_device(eng, num_repeats, seed, max_iters=max_iters, device_id=device_id)
+        score_fn = None
         if score_bisil and not no_clusts:                                                         # obtain_bicl.r:189-199
-            score = bisil.score(row_cl, col_cl, distance, engine=eng)
+            score_fn = lambda rc, cc: bisil.score(rc, cc, distance, engine=eng)             # noqa: E731
+        cleaned = _remove_then_score({"output_s": out_s, "row_clusters": row_cl, "col_clusters": col_cl}, check, score_fn)
     finally:
         eng.close()
+    row_cl, col_cl, score = cleaned["row_clusters"], cleaned["col_clusters"], cleaned.get("bisil")
     if no_clusts:                                                                                 # main.r:115-120
         res = {"output_f": out_f, "output_s": out_s, "output_g": out_g}
         if return_init:
@@ -190,9 +212,20 @@ def res_nmtf_inner(data, row_indices, column_indices,
         "row_clusters": row_cl, "col_clusters": col_cl,
         "lambda": lams, "mu": mus,
     }
+    if "spurious" in cleaned:
+        res["spurious"] = cleaned["spurious"]
     if return_init:               # (test hook: the initial state the device built, for a reference run from the same start)
         res["init"] = init_state
     return res
+
+
+def _remove_then_score(res: dict, check: Optional[dict], score_fn: Optional[Callable]) -> dict:
+    """R's order (``R/obtain_bicl.r:176-199``): with a ``check`` (``check_biclusters``' scores and thresholds) the
+    removal first (``spurious.apply_removal``: copies, ``"spurious"`` added), then ``"bisil"`` = ``score_fn(row_clusters,
+    col_clusters)`` of the cleaned clusters (``None`` without a ``score_fn``).  Returns a new dict."""
+    out = _spurious.apply_removal(res, check) if check is not None else dict(res)
+    out["bisil"] = None if score_fn is None else score_fn(out["row_clusters"], out["col_clusters"])
+    return out
 
 
 def _number_biclusters(results) -> float:
@@ -216,7 +249,8 @@ def _check_stability_numbers(sample_rate, stab_thres):
 def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repeats, no_clusts, distance,
                     sample_rate=0.9, n_stability=5, stab_thres=0.6, remove_unstable=True, *,
                     row_names=None, col_names=None, device_id: int = 0, seed: Optional[int] = None, group=None,
-                    max_iters: int = 100000, return_repeats: bool = False, repeat_runner: Optional[Callable] = None):
+                    max_iters: int = 100000, return_repeats: bool = False, repeat_runner: Optional[Callable] = None,
+                    spurious_on_device: bool = False):
     """``stability_check`` (``R/stability_analysis.r:302-338``): ``n_stability`` factorisations of sub-samples
     (``sample_rate`` of the rows and columns, drawn and trimmed as ``stability_repeat`` does, ``:215-249``), each scored
     against ``results`` by ``relevance_results`` (``:45-67``) -- the gathers, the factorisations and the scoring run on
@@ -229,7 +263,10 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
     biclusters (``no_clusts`` results included; the reference's message becomes a warning) or when a repeat could not
     be sampled; with ``remove_unstable=False`` ``{"res": results, "relevance": n_views x k array}``; else a copy of
     ``results`` whose row- and column-cluster columns with a mean relevance below ``stab_thres`` are zero (F, S, G
-    untouched; ``results`` is not modified).  ``spurious=True`` inside the repeats is outside the accelerated path.
+    untouched; ``results`` is not modified).  ``spurious=True`` inside the repeats needs the opt-in
+    ``spurious_on_device=True``: every repeat then removes the spurious biclusters of its own sub-sample before its
+    relevance is scored (``R/stability_analysis.r:254-266``; ``batched.stability_relevance_on_device``, spurious seed
+    ``seed + 2000 + r`` for repeat r); without it, ``NotImplementedError`` as before.
     Keyword-only extras: names, ``device_id``, ``seed`` of the draws and the device SVD inits, ``group``,
     ``max_iters``; test hooks: ``return_repeats`` (adds ``"repeats"``: per repeat the trimmed draws, relevance and
     the sub-sample's own clusters -- under ``"stability"`` of a copy of the result), ``repeat_runner(r)`` (replaces
@@ -238,9 +275,10 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
     if _number_biclusters(results) == 0:                                                          # :308-311
         warnings.warn("No biclusters detected!")
         return results
-    if spurious:
+    if spurious and not spurious_on_device:
         raise NotImplementedError("stability selection with spurious-bicluster removal inside its repeats "
                                   "(R/stability_analysis.r:254-266) is outside the accelerated path; pass spurious=False")
+    spurious_repeats = _spurious.check_num_repeats(num_repeats) if spurious else 0
     _check_stability_numbers(sample_rate, stab_thres)
     if int(n_stability) != n_stability or n_stability < 1:
         raise ValueError("n_stability must be a positive integer.")
@@ -259,7 +297,7 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
     try:
         stab = batched.stability_relevance_on_device(dev, results, k, int(n_stability), float(sample_rate), n_iters,
                                                      seed, group, max_iters, keep_clusters=return_repeats,
-                                                     runner=repeat_runner)
+                                                     runner=repeat_runner, spurious_repeats=spurious_repeats)
     finally:
         if dev is not None:
             dev.close()
@@ -289,7 +327,8 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                   sample_rate=0.9, n_stability=5, stability=True, stab_thres=0.4,
                   remove_unstable=True, use_parallel=True, *, row_names=None, col_names=None,
                   device_id: int = 0, max_iters: int = 100000, seed: Optional[int] = None,
-                  k_sweep: bool = False, return_sweep: bool = False, sweep_runner: Optional[Callable] = None):
+                  k_sweep: bool = False, return_sweep: bool = False, sweep_runner: Optional[Callable] = None,
+                  spurious_on_device: bool = False):
     """``apply_resnmtf`` (``R/main.r:214-335``) for a known ``k_val``: naming, shared-name maps, restriction
     symmetrisation, non-negativity shift and column normalisation on the host, then the device loop and -- with
     ``stability=True`` (the default) and ``spurious=False`` -- ``stability_check`` on the pre-processed data, as
@@ -305,18 +344,24 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     (``R/main.r:324-332``, unlike the ``k_val`` branch).  The result is the picked ``res_nmtf_inner`` result.  Test
     hooks: ``return_sweep`` adds ``"k_sweep": {"k": [...], "bisil": [...]}``; ``sweep_runner(k)`` replaces one
     factorisation and its score (a result dict with ``"bisil"``; nothing touches the device).  Without ``k_sweep``,
-    ``k_val=None`` raises ``NotImplementedError`` as before."""
+    ``k_val=None`` raises ``NotImplementedError`` as before.
+
+    ``spurious_on_device=True`` (keyword-only opt-in) lets ``spurious=True`` run: ``res_nmtf_inner(spurious=True,
+    spurious_on_device=True)`` for the known k or for every k of the sweep (ranked by the bisilhouette of the cleaned
+    clusters), and ``stability_check`` with the removal inside its repeats.  The reference's default pipeline is
+    ``apply_resnmtf(data, k_sweep=True, spurious_on_device=True)``."""
     data = _views(data)
     n_v = len(data)
     if k_val is None and k_sweep:
         return _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k_max, distance, spurious,
                               num_repeats, no_clusts, sample_rate, n_stability, stability, stab_thres, remove_unstable,
                               row_names=row_names, col_names=col_names, device_id=device_id, max_iters=max_iters,
-                              seed=seed, return_sweep=return_sweep, sweep_runner=sweep_runner)
+                              seed=seed, return_sweep=return_sweep, sweep_runner=sweep_runner,
+                              spurious_on_device=spurious_on_device)
     if k_val is None:
         raise NotImplementedError("the k sweep (R/main.r:279-321) needs the bisilhouette score, which is "
                                   "outside the accelerated path; pass k_val")
-    if stability and spurious and not no_clusts:
+    if stability and spurious and not no_clusts and not spurious_on_device:
         raise NotImplementedError("stability selection with spurious-bicluster removal (R/obtain_bicl.r:31-133) is "
                                   "outside the accelerated path; pass spurious=False (or stability=False and do the "
                                   "removal on the R side, INTEGRATION.md)")
@@ -338,12 +383,13 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     data = naming.check_data(data)                                                                # main.r:237
     results = res_nmtf_inner(data, row_idx, col_idx, init_f, init_s, init_g, k_vec, phi_m, xi_m, psi_m,
                              n_iters, num_repeats, spurious, distance, no_clusts,
-                             row_names=rn, col_names=cn, device_id=device_id, max_iters=max_iters, seed=seed)
+                             row_names=rn, col_names=cn, device_id=device_id, max_iters=max_iters, seed=seed,
+                             spurious_on_device=spurious_on_device)
     if stability:                                                                                 # main.r:255-262
         results = stability_check(data, results, k_vec, phi_m, xi_m, psi_m, n_iters, spurious, num_repeats,
                                   no_clusts, distance, sample_rate, n_stability, stab_thres,
                                   row_names=rn, col_names=cn, device_id=device_id, seed=seed,
-                                  max_iters=max_iters)
+                                  max_iters=max_iters, spurious_on_device=spurious_on_device)
     return results
 
 
@@ -379,7 +425,7 @@ def _sweep(run: Callable, k_min: int, k_max: int, cap: int, initial: Optional[li
 
 def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k_max, distance, spurious, num_repeats,
                    no_clusts, sample_rate, n_stability, stability, stab_thres, remove_unstable, *, row_names, col_names,
-                   device_id, max_iters, seed, return_sweep, sweep_runner):
+                   device_id, max_iters, seed, return_sweep, sweep_runner, spurious_on_device=False):
     """``apply_resnmtf`` with ``k_val = NULL`` (``R/main.r:269-334``); see ``apply_resnmtf``."""
     n_v = len(data)
     for name, val in (("n_iters", n_iters), ("num_repeats", num_repeats), ("n_stability", n_stability)):
@@ -393,9 +439,10 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
     if distance not in _DISTANCES:
         raise ValueError("distance must be one of 'euclidean', 'manhattan' or 'cosine'.")         # utils.r:425
     _check_stability_numbers(sample_rate, stab_thres)                                             # utils.r:286-300
-    if spurious and not no_clusts:
+    if spurious and not no_clusts and not spurious_on_device:
         raise NotImplementedError("spurious-bicluster removal (R/obtain_bicl.r:31-133) is outside the accelerated "
                                   "path; pass spurious=False")
+    spurious_repeats = _spurious.check_num_repeats(num_repeats) if spurious and not no_clusts else 0
     if no_clusts:
         raise ValueError("the k sweep ranks the biclusters by their bisilhouette score: no_clusts=True has none")
     if any(sparse.is_sparse(d) for d in data):
@@ -421,17 +468,25 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
 
             def scored(r):                                  # a res_nmtf_inner result with its bisil (main.r:131-139)
                 out = {key: r[key] for key in ("output_f", "output_s", "output_g", "Error", "All_Error")}
-                out["bisil"] = bisil.score(r["row_clusters"], r["col_clusters"], distance, engine=dev.base)
-                out.update({key: r[key] for key in ("row_clusters", "col_clusters", "lambda", "mu")})
+                cleaned = _remove_then_score({key: r[key] for key in ("output_s", "row_clusters", "col_clusters")},
+                                             r.get("spurious_check"),
+                                             lambda rc, cc: bisil.score(rc, cc, distance, engine=dev.base))
+                out["bisil"] = cleaned["bisil"]
+                out.update({key: cleaned[key] for key in ("row_clusters", "col_clusters")})
+                out.update({key: r[key] for key in ("lambda", "mu")})
+                if "spurious" in cleaned:
+                    out["spurious"] = cleaned["spurious"]
                 return out
 
             # every k, the extra ones included, with the correct shared-column maps (R's extension loop passes NULL
             # ones, R/main.r:305-309)
             def run(k):
-                return scored(dev.factorise(k, n_iters, seed + k, max_iters=max_iters, tag=f"k={k}", return_lm=True))
+                return scored(dev.factorise(k, n_iters, seed + k, max_iters=max_iters, tag=f"k={k}", return_lm=True,
+                                            spurious_repeats=spurious_repeats, spurious_seed=seed + k))
 
             initial = [scored(r) for r in batched.k_sweep_on_device(dev, k_min, k_max, n_iters, seed,       # main.r:279-290
-                                                                    max_iters=max_iters, return_lm=True)]
+                                                                    max_iters=max_iters, return_lm=True,
+                                                                    spurious_repeats=spurious_repeats)]
         else:
             run, initial = sweep_runner, None
         ks, scores, results, pick = _sweep(run, k_min, k_max, cap, initial)
@@ -442,7 +497,8 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
     if stability:                                                                                 # main.r:324-332
         results = stability_check(data, results, [ks[pick]] * n_v, phi_m, xi_m, psi_m, n_iters, spurious, num_repeats,
                                   no_clusts, distance, sample_rate, n_stability, stab_thres, remove_unstable,
-                                  row_names=rn, col_names=cn, device_id=device_id, seed=seed, max_iters=max_iters)
+                                  row_names=rn, col_names=cn, device_id=device_id, seed=seed, max_iters=max_iters,
+                                  spurious_on_device=spurious_on_device)
     if return_sweep:
         results = dict(results)
         results["k_sweep"] = {"k": ks, "bisil": scores}

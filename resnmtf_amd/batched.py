@@ -286,6 +286,43 @@ def run_jobs_grouped(jobs: Sequence[Job], device_id: int = 0, pre_processed: boo
 # ---------------------------------------------------------------------------------------------
 # the same job kinds with the data resident on the device: one upload, copies / shuffles drawn there
 # ---------------------------------------------------------------------------------------------
+def _draw_shuffle(eng, v: int, src, shuffle_seed: int):
+    """``shuffle_view`` (``R/obtain_bicl.r:11-22``) of ``src``'s view v into ``eng``'s view v, drawn and re-normalised
+    on the device; redrawn while a row or a column of the shuffled matrix sums to zero (``:14-18``)."""
+    for attempt in range(64):
+        eng.shuffle_view_from(v, src, v, seed=(shuffle_seed + 7919 * attempt) * 1000003 + v)
+        er, ec = eng.empty_lines(v)
+        if not (er.any() or ec.any()):
+            return
+    raise RuntimeError("shuffle_view: every draw left an all-zero row or column")
+
+
+def shuffled_engines(src, k: int, num_repeats: int, seed: int = 0, max_iters: int = 100000, device_id: int = 0) -> list:
+    """``obtain_shuffled_f`` (``R/obtain_bicl.r:31-42``) drawn from the views an engine already holds on the device
+    (``src``: a ``res_nmtf_inner`` engine or a stability repeat's sub-sample; no second upload): ``num_repeats`` engines,
+    every view shuffled from ``src``'s and re-normalised, no restrictions, uncoupled, device SVD init, run to
+    convergence -- the draws and seeds of ``shuffles_on_device(dev, k, num_repeats, seed=seed)``: repeat r initialises
+    with ``seed + 1000 + r`` and shuffles with ``seed * 7919 + r + 1``.  The engines are returned open, with their
+    factors on the device (``Engine.spurious_scores``); the caller closes them."""
+    from .engine import Engine
+    n_v = src.n_views
+    out = []
+    try:
+        for r in range(num_repeats):
+            eng = Engine(src.n_rows, src.n_cols, [k] * n_v, device_id=device_id)
+            out.append(eng)
+            for v in range(n_v):
+                _draw_shuffle(eng, v, src, seed * 7919 + r + 1)
+                eng.init_svd(v, seed=seed + 1000 + r + v)
+            eng.set_restrictions(None, None, None)          # R/obtain_bicl.r:35-39: apply_resnmtf without phi/xi/psi
+            eng.run(n_iters=None, tol=1.0e-6, max_iters=max_iters)
+    except BaseException:
+        for eng in out:
+            eng.close()
+        raise
+    return out
+
+
 class DeviceData:
     """The pre-processed views of one data set, uploaded once (``resnmtf_set_view_raw``) and kept for
     any number of factorisations (``resnmtf_copy_view`` / ``resnmtf_shuffle_view``).  At c2 size an
@@ -381,7 +418,7 @@ class DeviceData:
     def factorise(self, k: int, n_iters: Optional[int] = None, seed: int = 0, shuffle_seed: Optional[int] = None,
                   max_iters: int = 100000, tag: str = "", samples=None, return_init: bool = False,
                   return_data: bool = False, relevance: bool = False, keep_clusters: bool = False,
-                  return_lm: bool = False) -> dict:
+                  return_lm: bool = False, spurious_repeats: int = 0, spurious_seed: int = 0) -> dict:
         """One factorisation with k biclusters per view: views copied -- or, with ``shuffle_seed``, shuffled as
         ``obtain_shuffled_f`` does (no restrictions, fresh names; redrawn while a row or a column of the shuffled
         matrix sums to zero, ``R/obtain_bicl.r:14-18``), or, with ``samples = (row_samples, col_samples)``,
@@ -393,7 +430,11 @@ class DeviceData:
         clusters set on ``self.base`` (``resnmtf_relevance``, ``R/stability_analysis.r:268-276``) -- the result holds
         the n_views x k ``"relevance"`` matrix and no factors; ``keep_clusters`` adds the sub-sample's own binary
         clusters (a test hook: they cost a finalise download).  ``return_lm`` adds ``"lambda"`` / ``"mu"`` per view (the
-        keys of a ``res_nmtf_inner`` result, for the k sweep of ``apply_resnmtf``)."""
+        keys of a ``res_nmtf_inner`` result, for the k sweep of ``apply_resnmtf``).  ``spurious_repeats`` = R >= 2: the
+        scores of ``check_biclusters`` against R shuffles of this factorisation's own device copy
+        (``spurious.check_on_device`` with ``spurious_seed``) -- with ``relevance``, the flagged cluster columns are
+        removed before the scoring (``resnmtf_relevance_masked``, ``R/stability_analysis.r:254-276``) and the kept
+        clusters are the cleaned ones; else the result holds the check as ``"spurious_check"`` (the caller removes)."""
         from . import naming
         from .engine import Engine
         n_v = len(self.data_shapes)
@@ -420,13 +461,7 @@ class DeviceData:
         try:
             for v in range(n_v):
                 if shuffled:
-                    for attempt in range(64):                              # R/obtain_bicl.r:14-18: redraw on an empty row / column
-                        eng.shuffle_view_from(v, self.base, v, seed=(shuffle_seed + 7919 * attempt) * 1000003 + v)
-                        er, ec = eng.empty_lines(v)
-                        if not (er.any() or ec.any()):
-                            break
-                    else:
-                        raise RuntimeError("shuffle_view: every draw left an all-zero row or column")
+                    _draw_shuffle(eng, v, self.base, shuffle_seed)
                 elif host_views[v] is not None:
                     eng.set_view_sparse(v, host_views[v], pre_processed=True)      # (sub-samples are not re-normalised)
                 elif samples is not None:
@@ -449,7 +484,22 @@ class DeviceData:
             data_used = ([host_views[v].toarray().astype(np.float32).astype(np.float64) if host_views[v] is not None
                           else eng.get_view(v) for v in range(n_v)] if return_data else None)
             errs = eng.run(n_iters=n_iters, tol=1.0e-6, max_iters=max_iters)
-            if relevance:
+            check = None
+            if spurious_repeats:
+                from . import spurious
+                check = spurious.check_on_device(eng, spurious_repeats, spurious_seed, max_iters=max_iters,
+                                                  device_id=self.device_id)
+            if relevance and check is not None:
+                flags = spurious.removal_flags(check)
+                rel = np.stack([eng.relevance_masked(v, self.base, v, samples[0][v], samples[1][v], flags[v])
+                                for v in range(n_v)])
+                fin = None
+                if keep_clusters:
+                    fin = [eng.finalise(v) for v in range(n_v)]
+                    cleaned = spurious.apply_removal({"output_s": [f[1] for f in fin], "row_clusters": [f[3] for f in fin],
+                                                      "col_clusters": [f[4] for f in fin]}, check)
+                    fin = [(None, None, None, rc, cc) for rc, cc in zip(cleaned["row_clusters"], cleaned["col_clusters"])]
+            elif relevance:
                 rel = np.stack([eng.relevance(v, self.base, v, samples[0][v], samples[1][v]) for v in range(n_v)])
                 fin = [eng.finalise(v) for v in range(n_v)] if keep_clusters else None
             else:
@@ -477,16 +527,20 @@ class DeviceData:
             res["mu"] = [lm[1] for lm in lms]
         if return_data:
             res["data"] = data_used
+        if check is not None:
+            res["spurious_check"] = check
         return res
 
 
 def k_sweep_on_device(dev: DeviceData, k_min: int = 3, k_max: int = 8, n_iters=None, seed: int = 0, group=None,
-                      max_iters: int = 100000, return_lm: bool = False) -> List[dict]:
+                      max_iters: int = 100000, return_lm: bool = False, spurious_repeats: int = 0) -> List[dict]:
     """The factorisations of the k sweep (``R/main.r:279-290``) from one upload; sharded round-robin over
-    the ranks of an initialised process group (every rank holds its own ``DeviceData``)."""
+    the ranks of an initialised process group (every rank holds its own ``DeviceData``).  ``spurious_repeats``: each
+    k's result carries its ``"spurious_check"`` (``DeviceData.factorise``, spurious seed ``seed + k``)."""
     ks = list(range(k_min, k_max + 1))
     return run_jobs(ks, group=group, runner=lambda k: dev.factorise(k, n_iters, seed + k, max_iters=max_iters, tag=f"k={k}",
-                                                                    return_lm=return_lm))
+                                                                    return_lm=return_lm, spurious_repeats=spurious_repeats,
+                                                                    spurious_seed=seed + k))
 
 
 def shuffles_on_device(dev: DeviceData, n_clusts: int, num_repeats: int = 5, n_iters=None, seed: int = 0, group=None,
@@ -544,7 +598,7 @@ def mean_relevance(repeats: Sequence[dict], n_stability: int) -> Optional[np.nda
 def stability_relevance_on_device(dev: Optional[DeviceData], results: dict, k: int, n_stability: int = 5,
                                   sample_rate: float = 0.9, n_iters=None, seed: int = 0, group=None,
                                   max_iters: int = 100000, keep_clusters: bool = False,
-                                  runner: Optional[Callable] = None) -> dict:
+                                  runner: Optional[Callable] = None, spurious_repeats: int = 0) -> dict:
     """The repeats of ``stability_check`` (``R/stability_analysis.r:302-334``) with their scoring on the device:
     ``results``' binary clusters are uploaded once onto ``dev.base`` (``resnmtf_set_reference_clusters``), repeat r
     factorises the sub-sample of ``stability_draws`` (trimmed as ``stability_on_device`` does) up to the end of the loop
@@ -552,7 +606,11 @@ def stability_relevance_on_device(dev: Optional[DeviceData], results: dict, k: i
     sharded round-robin over the ranks of an initialised process group (``run_jobs``; every rank holds its own
     ``DeviceData`` and the same ``results``) and reduced by ``mean_relevance``.  ``runner(r)`` replaces the
     repeat (the CPU tests inject a stand-in; ``dev`` is then not used).  Returns ``{"stability_performed",
-    "relevance" (None when not performed), "repeats"}``."""
+    "relevance" (None when not performed), "repeats"}``.  ``spurious_repeats`` = R >= 2: every repeat removes its
+    spurious biclusters before it is scored (``R/stability_analysis.r:254-266``), against R shuffles of its own
+    sub-sample drawn with the spurious seed ``seed + 2000 + r`` -- the repeat's own factorisation seed, so that repeat r
+    equals ``remove_spurious(sub_data, sub_result, R, seed=seed + 2000 + r)``; per repeat only the k-sized flags, scores
+    and the null scores cross to the host."""
     if runner is None:
         n_v = len(dev.data_shapes)
         for v in range(n_v):
@@ -561,7 +619,8 @@ def stability_relevance_on_device(dev: Optional[DeviceData], results: dict, k: i
 
         def runner(r):
             return dev.factorise(k, n_iters, seed + 2000 + r, max_iters=max_iters, samples=draws[r], relevance=True,
-                                 keep_clusters=keep_clusters, tag=f"stability={r}")
+                                 keep_clusters=keep_clusters, tag=f"stability={r}", spurious_repeats=spurious_repeats,
+                                 spurious_seed=seed + 2000 + r)
     repeats = run_jobs(list(range(n_stability)), group=group, runner=runner)
     rel = mean_relevance(repeats, n_stability)
     return {"stability_performed": rel is not None, "relevance": rel, "repeats": repeats}

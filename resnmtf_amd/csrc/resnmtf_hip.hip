@@ -3063,11 +3063,10 @@ int resnmtf_set_reference_clusters(resnmtf_handle* h, int v, int k, const double
   return RESNMTF_OK;
 }
 
-int resnmtf_relevance(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, const int* rows, const int* cols,
-                      double* relevance) {
-  if (int rc = check_view(h, v)) return rc;
-  if (!ref || v_ref < 0 || v_ref >= ref->V) return h->fail(RESNMTF_ERR_INVALID, "bad reference handle / view");
-  if (!rows || !cols || !relevance) return h->fail(RESNMTF_ERR_INVALID, "rows / cols / relevance are NULL");
+namespace {
+// resnmtf_relevance (flags == nullptr) and resnmtf_relevance_masked (k flag bytes, indexed by F column)
+int relevance_impl(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, const int* rows, const int* cols,
+                   const unsigned char* flags, double* relevance) {
   if (h->opt.device_id != ref->opt.device_id) return h->fail(RESNMTF_ERR_INVALID, "handles live on different devices");
   const ViewState& vs = h->views[v];
   const ViewState& rs = ref->views[v_ref];
@@ -3081,14 +3080,18 @@ int resnmtf_relevance(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, 
   const int k = vs.k;
   const size_t kk = (size_t)k * k, side = kk + 2 * (size_t)k;
   // [cF k][cG k][S_out kk][out k] doubles | [relations k][rows n][cols m] ints | [counts 2 side] unsigned
+  // (masked: then [flags k] bytes)
   const size_t n_dbl = 3 * (size_t)k + kk, n_int = (size_t)k + vs.n + vs.m;
+  const size_t n_bytes = n_dbl * sizeof(double) + n_int * sizeof(int) + 2 * side * sizeof(unsigned int);
   char* buf = nullptr;
-  HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), n_dbl * sizeof(double) + n_int * sizeof(int) + 2 * side * sizeof(unsigned int)));
+  HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), n_bytes + (flags ? (size_t)k : 0)));
   double *cF = reinterpret_cast<double*>(buf), *cG = cF + k, *So = cG + k, *out = So + kk;
   int *rel = reinterpret_cast<int*>(buf + n_dbl * sizeof(double)), *idx = rel + k;
   unsigned int* counts = reinterpret_cast<unsigned int*>(idx + vs.n + vs.m);
+  unsigned char* dflags = flags ? reinterpret_cast<unsigned char*>(buf + n_bytes) : nullptr;
   hipError_t e = hipMemcpyAsync(idx, rows, (size_t)vs.n * sizeof(int), hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(idx + vs.n, cols, (size_t)vs.m * sizeof(int), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess && flags) e = hipMemcpyAsync(dflags, flags, (size_t)k, hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) e = hipMemsetAsync(counts, 0, 2 * side * sizeof(unsigned int), h->stream);
   if (e == hipSuccess) {
     // the clusters resnmtf_finalise would emit: same kernels, same reductions, same first-max relations
@@ -3097,10 +3100,19 @@ int resnmtf_relevance(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, 
     hipLaunchKernelGGL(finalise_s_kernel, dim3(1), dim3(64), 0, h->stream, vs.S, k, cF, cG, So, rel);
     const int grid_r = std::max(1, std::min(128, ceil_div(ceil_div(vs.n, 64), 4)));
     const int grid_c = std::max(1, std::min(128, ceil_div(ceil_div(vs.m, 64), 4)));
-    hipLaunchKernelGGL(relevance_count_kernel, dim3(grid_r), dim3(256), 0, h->stream, vs.F, vs.n, k, cF, (const int*)rel,
-                       (const unsigned char*)rs.ref_cl, (const int*)idx, counts);
-    hipLaunchKernelGGL(relevance_count_kernel, dim3(grid_c), dim3(256), 0, h->stream, vs.G, vs.m, k, cG, (const int*)nullptr,
-                       (const unsigned char*)(rs.ref_cl + (size_t)rs.n * k), (const int*)(idx + vs.n), counts + side);
+    if (!flags) {
+      hipLaunchKernelGGL(relevance_count_kernel<false>, dim3(grid_r), dim3(256), 0, h->stream, vs.F, vs.n, k, cF, (const int*)rel,
+                         (const unsigned char*)rs.ref_cl, (const int*)idx, counts, (const int*)nullptr, (const unsigned char*)nullptr);
+      hipLaunchKernelGGL(relevance_count_kernel<false>, dim3(grid_c), dim3(256), 0, h->stream, vs.G, vs.m, k, cG, (const int*)nullptr,
+                         (const unsigned char*)(rs.ref_cl + (size_t)rs.n * k), (const int*)(idx + vs.n), counts + side,
+                         (const int*)nullptr, (const unsigned char*)nullptr);
+    } else {                // the removal's zeroed cluster columns: flags through the relations, on both sides
+      hipLaunchKernelGGL(relevance_count_kernel<true>, dim3(grid_r), dim3(256), 0, h->stream, vs.F, vs.n, k, cF, (const int*)rel,
+                         (const unsigned char*)rs.ref_cl, (const int*)idx, counts, (const int*)rel, (const unsigned char*)dflags);
+      hipLaunchKernelGGL(relevance_count_kernel<true>, dim3(grid_c), dim3(256), 0, h->stream, vs.G, vs.m, k, cG, (const int*)nullptr,
+                         (const unsigned char*)(rs.ref_cl + (size_t)rs.n * k), (const int*)(idx + vs.n), counts + side,
+                         (const int*)rel, (const unsigned char*)dflags);
+    }
     hipLaunchKernelGGL(relevance_epilogue_kernel, dim3(1), dim3(64), 0, h->stream, k, (const unsigned int*)counts,
                        (const unsigned int*)(counts + side), out);
     e = hipGetLastError();
@@ -3110,6 +3122,23 @@ int resnmtf_relevance(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, 
   (void)hipFree(buf);
   if (e != hipSuccess) return h->fail_hip("relevance", e);
   return RESNMTF_OK;
+}
+}  // namespace
+
+int resnmtf_relevance(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, const int* rows, const int* cols,
+                      double* relevance) {
+  if (int rc = check_view(h, v)) return rc;
+  if (!ref || v_ref < 0 || v_ref >= ref->V) return h->fail(RESNMTF_ERR_INVALID, "bad reference handle / view");
+  if (!rows || !cols || !relevance) return h->fail(RESNMTF_ERR_INVALID, "rows / cols / relevance are NULL");
+  return relevance_impl(h, v, ref, v_ref, rows, cols, nullptr, relevance);
+}
+
+int resnmtf_relevance_masked(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, const int* rows, const int* cols,
+                             const unsigned char* flags, double* relevance) {
+  if (int rc = check_view(h, v)) return rc;
+  if (!ref || v_ref < 0 || v_ref >= ref->V) return h->fail(RESNMTF_ERR_INVALID, "bad reference handle / view");
+  if (!rows || !cols || !flags || !relevance) return h->fail(RESNMTF_ERR_INVALID, "rows / cols / flags / relevance are NULL");
+  return relevance_impl(h, v, ref, v_ref, rows, cols, flags, relevance);
 }
 
 // ---- bisilhouette (R/obtain_bicl.r:189-199): per-member silhouettes of a view's biclusters (resnmtf_bisil.hip.inc)
@@ -3312,6 +3341,101 @@ int resnmtf_jsd_pairs(int device_id, int n, int n_cols, const double* cols, int 
   (void)hipFree(buf);
   (void)hipStreamDestroy(st);
   if (e != hipSuccess) { g_create_error = std::string("jsd_pairs: ") + hipGetErrorString(e); return RESNMTF_ERR_HIP; }
+  return RESNMTF_OK;
+}
+
+// ---- spurious-bicluster scoring of handles (check_biclusters with get_thresholds, R/obtain_bicl.r:80-133): the pool
+// cbind(F_v, f_1, ..., f_R) gathered on the device from the handles' own F, then resnmtf_jsd_pairs' kernels over
+// pool_pairs(K, R) (resnmtf_amd/spurious.py), the K means on the device
+int resnmtf_spurious_scores(resnmtf_handle* h, int v, resnmtf_handle* const* shuffles, int R, double* score,
+                            double* null_scores) {
+  if (int rc = check_view(h, v)) return rc;
+  if (!shuffles || !score || !null_scores) return h->fail(RESNMTF_ERR_INVALID, "shuffles / score / null_scores are NULL");
+  if (R < 2) return h->fail(RESNMTF_ERR_INVALID, "R must be at least 2 (the reference indexes a second shuffled repeat)");
+  const ViewState& vs = h->views[v];
+  const int n = vs.n, K = vs.k;
+  if (!vs.has_factors) return h->fail(RESNMTF_ERR_STATE, "the view has no factors");
+  if (n < 2) return h->fail(RESNMTF_ERR_INVALID, "n must be at least 2 (bw.nrd0 needs two data points)");
+  for (int r = 0; r < R; ++r) {
+    const resnmtf_handle* s = shuffles[r];
+    if (!s) return h->fail(RESNMTF_ERR_INVALID, "a shuffle handle is NULL");
+    if (v >= s->V) return h->fail(RESNMTF_ERR_INVALID, "a shuffle handle has no view v");
+    if (s->opt.device_id != h->opt.device_id) return h->fail(RESNMTF_ERR_INVALID, "handles live on different devices");
+    if (s->views[v].n != n || s->views[v].k != K) return h->fail(RESNMTF_ERR_INVALID, "a shuffle handle's view v differs in n or k");
+    if (!s->views[v].has_factors) return h->fail(RESNMTF_ERR_STATE, "a shuffle handle's view v has no factors");
+  }
+  const long long C = (long long)K * (R + 1);
+  const long long RK = (long long)R * K;
+  const long long P_null = (long long)K * K * R * (R - 1) / 2, P = P_null + (long long)K * RK;
+  if (C > 65535) return h->fail(RESNMTF_ERR_INVALID, "K (R + 1) exceeds 65535 pool columns");
+  if ((long long)n * C > ((long long)1 << 31)) return h->fail(RESNMTF_ERR_INVALID, "n K (R + 1) exceeds 2^31 entries");
+  if (P > 2147483647LL) return h->fail(RESNMTF_ERR_INVALID, "K^2 R (R + 1) / 2 pairs exceed 2^31 - 1");
+  // the pairs in pool_pairs' order: null (calculate_f_shuffle_jsd, :55-68), then score (check_biclusters, :125-128)
+  std::vector<int> pairs(2 * (size_t)P);
+  size_t q = 0;
+  for (int j = 0; j < R - 1; ++j)
+    for (int k = 0; k < K; ++k)
+      for (int l = j + 1; l < R; ++l)
+        for (int m = 0; m < K; ++m) { pairs[q++] = K + j * K + k; pairs[q++] = K + l * K + m; }
+  for (int k = 0; k < K; ++k)
+    for (int y = 0; y < R * K; ++y) { pairs[q++] = k; pairs[q++] = K + y; }
+  HIP_TRY(h, hipSetDevice(h->opt.device_id));
+  if (int rc = sync_both(h)) return rc;
+  for (int r = 0; r < R; ++r) HIP_TRY(h, hipStreamSynchronize(shuffles[r]->stream));
+  const size_t total = (size_t)n * C, nk = (size_t)n * K;
+  // [pool n C][sort A n C][sort B n C][stats 2 C][colsum K][clusters n K (unused)][out P][score K] doubles
+  // | [pairs 2 P][flag 1] ints
+  const size_t n_dbl = 3 * total + 2 * (size_t)C + (size_t)K + nk + (size_t)P + (size_t)K;
+  char* buf = nullptr;
+  HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), n_dbl * sizeof(double) + (2 * (size_t)P + 1) * sizeof(int)));
+  double *pool = reinterpret_cast<double*>(buf), *sa = pool + total, *sb = sa + total, *stats = sb + total;
+  double *cF = stats + 2 * (size_t)C, *cl = cF + K, *dout = cl + nk, *dscore = dout + P;
+  int* dpairs = reinterpret_cast<int*>(buf + n_dbl * sizeof(double));
+  int* dflag = dpairs + 2 * (size_t)P;
+  int flag = 0;
+  hipError_t e = hipMemcpyAsync(dpairs, pairs.data(), 2 * (size_t)P * sizeof(int), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(dflag, 0, sizeof(int), h->stream);
+  if (e == hipSuccess) {
+    // F / colSums(F) of every handle, as resnmtf_finalise computes it (same kernels), into its K pool columns
+    for (int t = 0; t <= R; ++t) {
+      const ViewState& src = t == 0 ? vs : shuffles[t - 1]->views[v];
+      hipLaunchKernelGGL(colsum_kernel, dim3(K), dim3(256), 0, h->stream, (const double*)src.F, n, K, cF);
+      hipLaunchKernelGGL(finalise_factor_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, h->stream,
+                         (const double*)src.F, n, K, (const double*)cF, (const int*)nullptr, pool + (size_t)t * nk, cl);
+    }
+    hipLaunchKernelGGL(jsd_finite_kernel, dim3((unsigned)std::min<size_t>(1024, (total + 255) / 256)), dim3(256), 0,
+                       h->stream, (const double*)pool, total, dflag);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e == hipSuccess && flag) {
+    (void)hipFree(buf);
+    return h->fail(RESNMTF_ERR_INVALID, "a factor has a non-finite entry");
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(jsd_tile_sort_kernel, dim3(ceil_div(n, JSD_TILE), (unsigned)C), dim3(JSD_SORT_THREADS), 0, h->stream,
+                       (const double*)pool, sa, n);
+    double *src = sa, *dst = sb;
+    for (int width = JSD_TILE; width < n; width *= 2) {
+      hipLaunchKernelGGL(jsd_merge_kernel, dim3(ceil_div(n, 256), (unsigned)C), dim3(256), 0, h->stream, (const double*)src,
+                         dst, n, width);
+      std::swap(src, dst);
+    }
+    hipLaunchKernelGGL(jsd_stats_kernel, dim3((unsigned)C), dim3(256), 0, h->stream, (const double*)src, (const double*)pool,
+                       n, stats);
+    for (long long p0 = 0; p0 < P; p0 += 1 << 20)              // (grids of at most 2^20 workgroups)
+      hipLaunchKernelGGL(jsd_pair_kernel, dim3((unsigned)std::min<long long>(1 << 20, P - p0)), dim3(JSD_N), 0, h->stream,
+                         (const double*)src, (const double*)stats, n, (const int*)(dpairs + 2 * (size_t)p0), dout + p0);
+    hipLaunchKernelGGL(jsd_score_mean_kernel, dim3((unsigned)ceil_div(K, 64)), dim3(64), 0, h->stream,
+                       (const double*)(dout + P_null), K, (int)RK, dscore);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(score, dscore, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(null_scores, dout, (size_t)P_null * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  (void)hipFree(buf);
+  if (e != hipSuccess) return h->fail_hip("spurious_scores", e);
   return RESNMTF_OK;
 }
 

@@ -278,4 +278,53 @@ jsd_pair_kernel(const double* __restrict__ sorted, const double* __restrict__ st
   if (t == 0) out[p] = 0.5 * (sum1 + sum2);
 }
 
+
+// ---- resnmtf_spurious_scores: the pool is gathered on the device (colsum_kernel + finalise_factor_kernel per handle) --
+// flag[0] = 1 when an entry of the pool is not finite (a plain store of one value: no sum, no atomic)
+__global__ void __launch_bounds__(256)
+jsd_finite_kernel(const double* __restrict__ x, size_t total, int* __restrict__ flag) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256)
+    if (!isfinite(x[i])) flag[0] = 1;
+}
+
+// NumPy's pairwise summation (pairwise_sum of numpy/_core/src/umath/loops_utils.h.src, the order np.mean uses along a
+// contiguous axis): below 8 entries in order from 0; up to 128 eight strided accumulators, combined as
+// ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the tail in order; above, split at n / 2 rounded down to a
+// multiple of 8.  D bounds the depth at compile time (n < 2^31 needs 24 levels).
+__device__ double jsd_np_pairwise_leaf(const double* a, long long n) {
+  if (n < 8) {
+    double r = 0.0;
+    for (long long i = 0; i < n; ++i) r += a[i];
+    return r;
+  }
+  double r[8];
+  for (int j = 0; j < 8; ++j) r[j] = a[j];
+  long long i = 8;
+  for (; i < n - (n % 8); i += 8)
+    for (int j = 0; j < 8; ++j) r[j] += a[i + j];
+  double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  for (; i < n; ++i) res += a[i];
+  return res;
+}
+
+template <int D>
+__device__ double jsd_np_pairwise(const double* a, long long n) {
+  if constexpr (D == 0) {
+    return jsd_np_pairwise_leaf(a, n);
+  } else {
+    if (n <= 128) return jsd_np_pairwise_leaf(a, n);
+    long long n2 = n / 2;
+    n2 -= n2 % 8;
+    return jsd_np_pairwise<D - 1>(a, n2) + jsd_np_pairwise<D - 1>(a + n2, n - n2);
+  }
+}
+
+// score[k] = mean(vals[k * RK .. (k + 1) * RK)) as np.mean(vals.reshape(K, RK), axis=1) computes it: one thread per k
+__global__ void __launch_bounds__(64)
+jsd_score_mean_kernel(const double* __restrict__ vals, int K, int RK, double* __restrict__ score) {
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= K) return;
+  score[k] = jsd_np_pairwise<24>(vals + (size_t)k * RK, RK) / (double)RK;
+}
+
 }  // namespace

@@ -3281,13 +3281,19 @@ static __global__ __launch_bounds__(256) void finalise_factor_kernel(const doubl
 // counts (per side, unsigned): [k * k: |A_i ^ B_j| at i * k + j] [k: |A_i|] [k: |B_j|]   (A = sub-sample, B = reference)
 // ref: the reference's clusters of this side as 0 / 1 bytes, [len_ref][k] row-major; idx: len indices into its rows
 // (validated on the host).
+// MASKED (resnmtf_relevance_masked): the sub-sample's cluster i counts as empty when flags[drop_rel[i]] is set -- flags
+// are indexed by F column and drop_rel is finalise_s_kernel's relations, for the row and the column launch alike (the
+// column zeroing of the spurious-bicluster removal, R/obtain_bicl.r:176-188).
 // --------------------------------------------------------------------------------------
+template <bool MASKED>
 static __global__ __launch_bounds__(256) void relevance_count_kernel(const double* __restrict__ W, int len, int k,
                                                                      const double* __restrict__ c,
                                                                      const int* __restrict__ relations,
                                                                      const unsigned char* __restrict__ ref,
                                                                      const int* __restrict__ idx,
-                                                                     unsigned int* __restrict__ counts) {
+                                                                     unsigned int* __restrict__ counts,
+                                                                     const int* __restrict__ drop_rel,
+                                                                     const unsigned char* __restrict__ flags) {
   __shared__ unsigned int cnt[RESNMTF_MAX_K * RESNMTF_MAX_K + 2 * RESNMTF_MAX_K];
   const int total = k * k + 2 * k;
   for (int t = threadIdx.x; t < total; t += 256) cnt[t] = 0u;
@@ -3307,6 +3313,9 @@ static __global__ __launch_bounds__(256) void relevance_count_kernel(const doubl
     }
     if (lane < k && mine) atomicAdd(&cnt[k * k + k + lane], (unsigned int)__popcll(mine));
     for (int i = 0; i < k; ++i) {
+      if constexpr (MASKED) {
+        if (flags[drop_rel[i]]) continue;                            // a removed cluster: no member (wave-uniform)
+      }
       const int src = relations ? relations[i] : i;
       const unsigned long long a = __ballot(valid && (W[(size_t)rr * k + src] / c[src] > thr));
       if (a == 0ull) continue;                                       // (wave-uniform)

@@ -410,6 +410,34 @@ class Engine:
         self._check(self._lib.resnmtf_relevance(self._h, v, ref_engine._h, v_ref, _ip(rows), _ip(cols), _dp(out)))
         return out
 
+    def relevance_masked(self, v: int, ref_engine: "Engine", v_ref: int, rows, cols, flags) -> np.ndarray:
+        """``relevance`` after a spurious-bicluster removal (``resnmtf_relevance_masked``): ``flags`` holds k[v] booleans
+        indexed by F column (the removal rule of ``R/obtain_bicl.r:176-188``); the cluster columns ``j`` with
+        ``flags[relations[j]]`` are zeroed on the device, through its own ``relations``, before the counting."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32); cols = np.ascontiguousarray(cols, dtype=np.int32)
+        if rows.ndim != 1 or cols.ndim != 1 or len(rows) != self.n_rows[v] or len(cols) != self.n_cols[v]:
+            raise ValueError("index counts must equal the view's shape")
+        fl = np.ascontiguousarray(np.asarray(flags, dtype=bool).astype(np.uint8))
+        if fl.shape != (self.k[v],):
+            raise ValueError(f"flags must hold k = {self.k[v]} entries")
+        out = np.zeros(self.k[v], dtype=np.float64)
+        self._check(self._lib.resnmtf_relevance_masked(self._h, v, ref_engine._h, v_ref, _ip(rows), _ip(cols),
+                                                       fl.ctypes.data_as(C.POINTER(C.c_ubyte)), _dp(out)))
+        return out
+
+    def spurious_scores(self, v: int, shuffles: Sequence["Engine"]):
+        """``check_biclusters`` / ``get_thresholds`` (``R/obtain_bicl.r:80-133``) of view ``v`` against the same view of
+        the ``shuffles`` engines (R shuffled factorisations with this engine's n and k), on the device
+        (``resnmtf_spurious_scores``): returns ``(score, null)`` -- the k[v] scores (means in NumPy's order) and the
+        k^2 R (R - 1) / 2 null scores in ``calculate_f_shuffle_jsd``'s order.  No factor is downloaded."""
+        R = len(shuffles)
+        hs = (C.c_void_p * max(1, R))(*[s._h for s in shuffles])
+        k = self.k[v] if 0 <= v < self.n_views else 0          # (a bad view is refused by the library)
+        score = np.zeros(max(1, k), dtype=np.float64)
+        null = np.zeros(max(1, k * k * R * (R - 1) // 2), dtype=np.float64)
+        self._check(self._lib.resnmtf_spurious_scores(self._h, v, hs, R, _dp(score), _dp(null)))
+        return score[:k], null[:k * k * R * (R - 1) // 2]
+
     def bisil(self, v: int, rc, cc, distance: str = "euclidean"):
         """The per-member silhouettes of view ``v``'s biclusters (``resnmtf_bisil``, the device side of
         ``bisilhouette::bisilhouette``, ``R/obtain_bicl.r:189-199``) on the view's device copy of the data: ``rc`` /

@@ -11,6 +11,11 @@ stability selection:
    and the removal rule (``:176-188``).
 
 The loops the reference writes in R stay in R's order; DESIGN.md section 11.
+
+Inside the pipeline (the opt-in ``spurious_on_device=True`` of ``res_nmtf_inner``, ``stability_check`` and
+``apply_resnmtf``) the same check runs on a live engine instead (``check_on_device``): the shuffles are drawn from the
+engine's own device copy (``batched.shuffled_engines``) and ``resnmtf_spurious_scores`` gathers and scores the pool on
+the device; only the K scores and the null scores come back for ``thresholds``.
 """
 from __future__ import annotations
 
@@ -135,9 +140,7 @@ def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int
     instead of ``shuffles_on_device``; ``group`` is then not used.  At the default 5 repeats this is slower than the
     default path (the grouped kernel is latency-bound per job): it buys fp64 shuffled fits, not
     speed."""
-    if isinstance(num_repeats, bool) or int(num_repeats) != num_repeats or num_repeats < 2:
-        raise ValueError("num_repeats must be an integer >= 2 (the reference indexes a second shuffled repeat)")
-    R = int(num_repeats)
+    R = check_num_repeats(num_repeats)
     views = list(data) if not (isinstance(data, np.ndarray) and data.ndim == 2) and not sparse.is_sparse(data) else [data]
     if any(sparse.is_sparse(d) for d in views):
         raise NotImplementedError("spurious-bicluster removal needs shuffled views: device shuffles of sparse views are "
@@ -191,23 +194,67 @@ def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int
             raise ValueError(f"view {i}: a Jensen-Shannon score is not finite (a density summed to zero; R gives NaN "
                              "here and check_biclusters cannot continue)")
         null, sc = vals[:len(null_p)], vals[len(null_p):]
-        avg[i] = np.mean(null)                                                    # :97
-        mx[i] = density_mode(null)                                                # :98-99
+        avg[i], mx[i] = thresholds(null)
         score[i] = sc.reshape(K, R * K).mean(axis=1)                              # :125-128
     return {"score": score, "avg_threshold": avg, "max_threshold": mx}
 
 
-def remove_spurious(data, results: dict, num_repeats: int = 5, *, grouped: bool = False, **kwargs) -> dict:
-    """The removal step of ``obtain_biclusters`` (``R/obtain_bicl.r:176-188``) on a ``res_nmtf_inner(spurious=False)``
-    / ``apply_resnmtf(spurious=False, stability=False)`` result: with ``check = check_biclusters(data,
-    results["output_f"], num_repeats, **kwargs)``, view i's cluster columns ``relations`` (``which.max`` of every S
-    column) flagged by ``score < max_threshold | score == 0`` are zeroed in ``row_clusters`` and ``col_clusters``.
-    Returns a copy (F, S, G unchanged; ``results`` is not modified) with ``"spurious"``: ``check`` plus ``"removed"``,
-    the n_views x K mask of the zeroed cluster columns.  ``grouped`` is passed on to ``check_biclusters``."""
-    if not results.get("row_clusters") or not results.get("col_clusters"):
-        raise ValueError("results has no cluster matrices (a no_clusts result): nothing to remove")
-    _check_factors(results["output_s"], "output_s")
-    check = check_biclusters(data, results["output_f"], num_repeats, grouped=grouped, **kwargs)
+def check_num_repeats(num_repeats) -> int:
+    if isinstance(num_repeats, bool) or int(num_repeats) != num_repeats or num_repeats < 2:
+        raise ValueError("num_repeats must be an integer >= 2 (the reference indexes a second shuffled repeat)")
+    return int(num_repeats)
+
+
+def thresholds(null):
+    """``get_thresholds`` (``:97-99``) of one view's null scores: (their mean, the mode of ``stats::density``)."""
+    null = np.asarray(null, dtype=np.float64)
+    return float(np.mean(null)), density_mode(null)
+
+
+def check_on_device(eng, num_repeats: int, seed: Optional[int] = None, *, max_iters: int = 100000,
+                    device_id: int = 0) -> dict:
+    """``check_biclusters`` of the factorisation an engine holds (its F on the device, as ``finalise`` normalises it)
+    against ``num_repeats`` shuffles of the engine's own views: ``batched.shuffled_engines(eng, K, num_repeats, seed)``
+    -- the draws of ``check_biclusters(data, F, num_repeats, seed=seed)`` -- scored per view by
+    ``resnmtf_spurious_scores``; the thresholds on the host.  Bitwise ``check_biclusters``' result for the same data,
+    F and seed.  Returns ``{"score", "avg_threshold", "max_threshold"}``."""
+    from . import batched
+    R = check_num_repeats(num_repeats)
+    n_v, K = eng.n_views, eng.k[0]
+    if any(k != K for k in eng.k):
+        raise ValueError("every view needs the same k (the reference's k_vec is one k repeated)")
+    if K * K * R * (R - 1) // 2 < 2:
+        raise ValueError("a single null score (K = 1, num_repeats = 2): stats::density needs two")
+    score = np.zeros((n_v, K))
+    avg, mx = np.zeros(n_v), np.zeros(n_v)
+    shuffles = batched.shuffled_engines(eng, K, R, 0 if seed is None else int(seed), max_iters=max_iters,
+                                        device_id=device_id)
+    try:
+        for i in range(n_v):
+            sc, null = eng.spurious_scores(i, shuffles)
+            if not (np.all(np.isfinite(sc)) and np.all(np.isfinite(null))):
+                raise ValueError(f"view {i}: a Jensen-Shannon score is not finite (a density summed to zero; R gives NaN "
+                                 "here and check_biclusters cannot continue)")
+            avg[i], mx[i] = thresholds(null)
+            score[i] = sc
+    finally:
+        for sh in shuffles:
+            sh.close()
+    return {"score": score, "avg_threshold": avg, "max_threshold": mx}
+
+
+def removal_flags(check: dict) -> np.ndarray:
+    """The removal rule ``score < max_threshold | score == 0`` (``R/obtain_bicl.r:182-183``): n_views x K, by F column."""
+    score = np.asarray(check["score"], dtype=np.float64)
+    mx = np.asarray(check["max_threshold"], dtype=np.float64)
+    return (score < mx[:, None]) | (score == 0)
+
+
+def apply_removal(results: dict, check: dict) -> dict:
+    """The removal of ``obtain_biclusters`` (``R/obtain_bicl.r:176-188``) for a ``check``: view i's cluster columns
+    ``relations`` (``which.max`` of every S column) flagged by ``removal_flags`` are zeroed in copies of
+    ``row_clusters`` and ``col_clusters``.  Returns a copy of ``results`` with ``"spurious"``: ``check`` plus
+    ``"removed"``, the n_views x K mask of the zeroed cluster columns."""
     out = dict(results)
     out["row_clusters"] = [np.array(rc, dtype=np.float64, copy=True) for rc in results["row_clusters"]]
     out["col_clusters"] = [np.array(cc, dtype=np.float64, copy=True) for cc in results["col_clusters"]]
@@ -221,3 +268,17 @@ def remove_spurious(data, results: dict, num_repeats: int = 5, *, grouped: bool 
         removed.append(new)
     out["spurious"] = dict(copy.deepcopy(check), removed=np.array(removed, dtype=bool))
     return out
+
+
+def remove_spurious(data, results: dict, num_repeats: int = 5, *, grouped: bool = False, **kwargs) -> dict:
+    """The removal step of ``obtain_biclusters`` (``R/obtain_bicl.r:176-188``) on a ``res_nmtf_inner(spurious=False)``
+    / ``apply_resnmtf(spurious=False, stability=False)`` result: with ``check = check_biclusters(data,
+    results["output_f"], num_repeats, **kwargs)``, view i's cluster columns ``relations`` (``which.max`` of every S
+    column) flagged by ``score < max_threshold | score == 0`` are zeroed in ``row_clusters`` and ``col_clusters``.
+    Returns a copy (F, S, G unchanged; ``results`` is not modified) with ``"spurious"``: ``check`` plus ``"removed"``,
+    the n_views x K mask of the zeroed cluster columns.  ``grouped`` is passed on to ``check_biclusters``."""
+    if not results.get("row_clusters") or not results.get("col_clusters"):
+        raise ValueError("results has no cluster matrices (a no_clusts result): nothing to remove")
+    _check_factors(results["output_s"], "output_s")
+    check = check_biclusters(data, results["output_f"], num_repeats, grouped=grouped, **kwargs)
+    return apply_removal(results, check)
