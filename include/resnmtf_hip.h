@@ -559,6 +559,39 @@ int resnmtf_group_run(int device_id, int n_jobs, const resnmtf_group_job* jobs, 
  * With x_half = 3 this is the guard's decision (resnmtf_options). */
 int resnmtf_view_image_info(resnmtf_handle* h, int v, int* uses_2byte, double* rel_error);
 
+/* The launch plan of view v's two streaming passes, as resnmtf_create / the upload decided it: index [0] = the X.G pass,
+ * [1] = the Xt.F pass.  Host only, read-only: no device work, no plan is changed.  The f_chain fields describe the sweep
+ * resnmtf_run captured at its latest prepare (prepared = 0: none yet, they read 0).  Refused (RESNMTF_ERR_INVALID): h or
+ * out NULL, a bad view, out->struct_size != sizeof(resnmtf_view_plan_info). */
+typedef struct resnmtf_view_plan_info {
+  int struct_size;         /* = sizeof(resnmtf_view_plan_info), set by the caller */
+  int k, kp, nt;           /* k, padded k (16 NT) and 16-column tiles of k */
+  int image;               /* what the passes stream: 0 = f32 images, 1 = sparse CSC / CSR, 2 = fp16 image, 3 = 16-bit integer image */
+  int kk_mode;             /* k x k hand-off: 0 = mode A (job in workgroup 0), 1 = mode B (aux tiles, last-arriving aux workgroup) */
+  int half_unroll;         /* pass_half_kernel wave-steps per trip in effect (2-byte images), else 0 */
+  int wide[2];             /* k > 16: 1 = the three-bf16-piece wide form, 0 = the plain f32 MFMA form (and k <= 16) */
+  int xcd_order[2];        /* XCD-aware workgroup order in effect (wide form with xcd_order) */
+  int waves[2];            /* waves per workgroup */
+  int unroll[2];           /* pass_kernel UNROLL (dense f32 images), else 0 */
+  int pingpong[2];         /* k <= 16, f32 images: the ping-pong prefetch form */
+  int nsplit[2];           /* row splits (slabs) of the contraction */
+  int rows_per_split[2];
+  int rows[2];             /* contraction rows (X.G: m, Xt.F: n) */
+  int rows_pad[2];         /* contraction rows, padded to 64 (X.G: m_pad, Xt.F: n_pad) */
+  int short_last[2];       /* the last split is shorter than rows_per_split */
+  int ntiles[2];           /* 64-row output tiles (X.G: n_pad / 64, Xt.F: m_pad / 64) */
+  int tiles_per_wg[2];     /* wide form: 64-column tiles per workgroup (8 or 4), else 1 */
+  int aux_splits[2];       /* mode B: row splits of the aux tiles, else 0 */
+  int sparse_blocks[2];    /* sparse view: work blocks of the spmm pass, else 0 */
+  int pitch_pad;           /* dense f32 images: 1 = one spare 256-B row per 64-column tile (resnmtf_options.no_pitch_pad = 0) */
+  int lds_pad_kb;          /* dense passes: extra LDS per workgroup (resnmtf_options.pass_lds_pad_kb) */
+  int prepared;            /* the f_chain fields below are those of the latest prepare */
+  int f_chain_hoisted;     /* resnmtf_run runs every F update of a sweep first, in one f_chain_kernel launch */
+  int f_chain_views;       /* its view-count instantiation (2, 4 or 8), 0 when not hoisted */
+  int f_chain_one_slab;    /* 1: it reads one X.G slab per view (nsplit == 1 everywhere), 0: several */
+} resnmtf_view_plan_info;
+int resnmtf_view_plan(resnmtf_handle* h, int v, resnmtf_view_plan_info* out);
+
 /* Size the per-sweep error buffer for `sweeps` sweeps (phase mode; resnmtf_run sizes it itself).
  * Must precede resnmtf_prepare. */
 int resnmtf_reserve_sweeps(resnmtf_handle* h, int sweeps);

@@ -54,6 +54,20 @@ class PassTiming(C.Structure):
     ]
 
 
+class ViewPlan(C.Structure):
+    """``resnmtf_view_plan_info`` (include/resnmtf_hip.h): [0] = the X.G pass, [1] = the Xt.F pass."""
+    _fields_ = [
+        ("struct_size", C.c_int), ("k", C.c_int), ("kp", C.c_int), ("nt", C.c_int), ("image", C.c_int), ("kk_mode", C.c_int),
+        ("half_unroll", C.c_int),
+        ("wide", C.c_int * 2), ("xcd_order", C.c_int * 2), ("waves", C.c_int * 2), ("unroll", C.c_int * 2),
+        ("pingpong", C.c_int * 2), ("nsplit", C.c_int * 2), ("rows_per_split", C.c_int * 2), ("rows", C.c_int * 2),
+        ("rows_pad", C.c_int * 2),
+        ("short_last", C.c_int * 2), ("ntiles", C.c_int * 2), ("tiles_per_wg", C.c_int * 2), ("aux_splits", C.c_int * 2),
+        ("sparse_blocks", C.c_int * 2), ("pitch_pad", C.c_int), ("lds_pad_kb", C.c_int),
+        ("prepared", C.c_int), ("f_chain_hoisted", C.c_int), ("f_chain_views", C.c_int), ("f_chain_one_slab", C.c_int),
+    ]
+
+
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 _h = C.c_void_p
@@ -120,6 +134,7 @@ SIGNATURES = {
     "resnmtf_synchronize": (C.c_int, [_h]),
     "resnmtf_pass_timings": (C.c_int, [_h, C.POINTER(PassTiming), C.c_int]),
     "resnmtf_view_image_info": (C.c_int, [_h, C.c_int, _ip, _dp]),
+    "resnmtf_view_plan": (C.c_int, [_h, C.c_int, C.POINTER(ViewPlan)]),
     "resnmtf_kernel_timings": (C.c_int, [_h, _dp, C.POINTER(C.c_longlong), C.c_int]),
     "resnmtf_set_stop_tolerance": (C.c_int, [_h, C.c_double]),
     "resnmtf_loop_state": (C.c_int, [_h, _ip, _ip, _ip]),

@@ -3981,6 +3981,63 @@ int resnmtf_view_image_info(resnmtf_handle* h, int v, int* uses_2byte, double* r
   return RESNMTF_OK;
 }
 
+// the decisions launch_pass / launch_pass_sparse / enqueue_sweep take from ViewState and the options, restated for the
+// caller (tests assert which launch form they cover); keep in step with those functions
+int resnmtf_view_plan(resnmtf_handle* h, int v, resnmtf_view_plan_info* out) {
+  if (!h) return RESNMTF_ERR_INVALID;
+  if (!out) return h->fail(RESNMTF_ERR_INVALID, "out is NULL");
+  if (out->struct_size != (int)sizeof(resnmtf_view_plan_info)) return h->fail(RESNMTF_ERR_INVALID, "view plan struct_size mismatch");
+  if (int rc = check_view(h, v)) return rc;
+  const ViewState& vs = h->views[v];
+  resnmtf_view_plan_info p;
+  std::memset(&p, 0, sizeof(p));
+  p.struct_size = (int)sizeof(p);
+  p.k = vs.k; p.kp = vs.KP; p.nt = vs.NT;
+  p.image = vs.sparse ? 1 : (vs.half ? (vs.u16 ? 3 : 2) : 0);
+  p.kk_mode = vs.kk_mode;
+  if (vs.half) {
+    const int un_def = vs.u16 ? 2 : 4, hu = h->opt.half_unroll;
+    p.half_unroll = (hu == 2 || hu == 3 || hu == 4 || hu == 6) ? hu : un_def;
+  }
+  const bool wide = !vs.sparse && vs.NT >= 2 && h->opt.bf16_split != 2;
+  for (int i = 0; i < 2; ++i) {
+    const bool xg = i == 0;
+    const int ns = xg ? vs.nsplit_xg : vs.nsplit_xtf, rps = xg ? vs.rps_xg : vs.rps_xtf;
+    const int rows_pad = xg ? vs.m_pad : vs.n_pad;
+    p.wide[i] = wide ? 1 : 0;
+    p.xcd_order[i] = wide && h->opt.xcd_order ? 1 : 0;
+    p.waves[i] = vs.sparse ? 8 : (xg ? vs.nw_xg : vs.nw_xtf);
+    p.pingpong[i] = !vs.sparse && !vs.half && (xg ? vs.pp_xg : vs.pp_xtf) ? 1 : 0;   // (pass_half_kernel has no such form)
+    if (!vs.sparse && !vs.half)
+      p.unroll[i] = vs.NT >= 2 ? 4 : (p.waves[i] == 8 ? (p.pingpong[i] ? 4 : RESNMTF_K16_UNROLL) : 8);
+    p.nsplit[i] = ns;
+    p.rows[i] = xg ? vs.m : vs.n;
+    p.rows_pad[i] = rows_pad;
+    p.ntiles[i] = (xg ? vs.n_pad : vs.m_pad) / 64;
+    if (!vs.sparse) {
+      p.rows_per_split[i] = rps;
+      p.short_last[i] = ns > 1 && rows_pad - (ns - 1) * rps < rps ? 1 : 0;
+    }
+    p.tiles_per_wg[i] = wide ? (xg ? vs.tw_xg : vs.tw_xtf) : 1;
+    p.aux_splits[i] = vs.kk_mode != 0 ? (xg ? vs.nsaux_xg : vs.nsaux_xtf) : 0;
+    p.sparse_blocks[i] = vs.sparse ? (xg ? vs.nblk_xg : vs.nblk_xtf) : 0;
+  }
+  if (!vs.sparse) {
+    p.pitch_pad = vs.ldx != (size_t)vs.n_pad * 64 ? 1 : 0;
+    p.lds_pad_kb = h->opt.pass_lds_pad_kb;
+  }
+  p.prepared = h->prepared ? 1 : 0;
+  if (h->prepared && h->chain_views > 0 && h->all_owned && !h->wchain_ok[0]) {      // (enqueue_sweep / enqueue_phase_f_all)
+    p.f_chain_hoisted = 1;
+    p.f_chain_views = h->chain_views <= 2 ? 2 : (h->chain_views <= 4 ? 4 : 8);
+    bool one_slab = true;
+    for (int w = 0; w < h->chain_views; ++w) one_slab = one_slab && h->chain.nsplit[w] == 1;
+    p.f_chain_one_slab = one_slab ? 1 : 0;
+  }
+  *out = p;
+  return RESNMTF_OK;
+}
+
 int resnmtf_pass_timings(resnmtf_handle* h, resnmtf_pass_timing* out, int reset) {
   if (!h || !out) return RESNMTF_ERR_INVALID;
   HIP_TRY(h, hipSetDevice(h->opt.device_id));

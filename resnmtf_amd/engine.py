@@ -463,6 +463,24 @@ class Engine:
         self._check(self._lib.resnmtf_view_image_info(self._h, v, C.byref(kind), C.byref(rel)))
         return int(kind.value), float(rel.value)
 
+    def view_plan(self, v: int) -> dict:
+        """The launch plan of view ``v``'s streaming passes (``resnmtf_view_plan``, host only): pass-wise fields are
+        ``(X.G, Xt.F)`` pairs; ``image`` is "f32", "sparse", "fp16" or "u16"; the ``f_chain_*`` fields are those of
+        the latest prepare (``prepared``)."""
+        p = _lib.ViewPlan()
+        p.struct_size = C.sizeof(_lib.ViewPlan)
+        self._check(self._lib.resnmtf_view_plan(self._h, int(v), C.byref(p)))
+        out = {}
+        for name, typ in _lib.ViewPlan._fields_:
+            if name == "struct_size":
+                continue
+            val = getattr(p, name)
+            out[name] = tuple(int(x) for x in val) if hasattr(typ, "_length_") else int(val)
+        out["image"] = ("f32", "sparse", "fp16", "u16")[out["image"]]
+        for key in ("prepared", "f_chain_hoisted", "f_chain_one_slab"):
+            out[key] = bool(out[key])
+        return out
+
     def set_stop_tolerance(self, tol: float):
         """Phase API: ``tol >= 0`` = convergence mode (``R/main.r:50-81``) for the phases enqueued from now on."""
         self._check(self._lib.resnmtf_set_stop_tolerance(self._h, float(tol)))

@@ -1,0 +1,522 @@
+"""One device sweep checked ENTRY BY ENTRY against fp64, for every launch form of the streaming passes.
+
+Each case loads a problem, runs 0 or 10 sweeps, reads the raw state, runs ONE sweep and reads it again; every step of
+that sweep is then compared with its own fp64 reference (tests/sweep_ref.py: the oracle's update rules fed the device's
+outputs of the steps before it, on the image the passes stream).  All factors and the data are non-negative, so no sum
+cancels and each entry of a correct sweep matches fp64 to a small relative error:
+
+* F, G, S, lambda, mu: ``max |got / ref - 1|`` over ``ref > 0`` within the form's bar, ``got == 0`` where ``ref == 0``;
+* the sweep's error against the reference error: absolute bar.
+
+A relative Frobenius norm over a whole factor averages away what breaks a few rows (a ragged last trip, a short last
+split, a wrong pitch, a k column off by one at a tile boundary); this statistic does not.  Each case also shows, on
+the host, that mutants of exactly those bugs exceed its bar at least 4 x, and records ``Engine.view_plan`` of every
+view; ``test_forms_covered`` asserts that the cases together reach every launch form the planner can choose.
+"""
+import json
+import os
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+from helpers import coupled_problem
+from resnmtf_amd import naming, synth
+from resnmtf_amd.engine import Engine
+from sweep_ref import fp16_split, half_image, rel_stat, step_reference, stream_image
+from test_gpu_sparse import sparsify
+
+pytestmark = pytest.mark.gpu
+
+# Elementwise bars per form (max |got / ref - 1|), against each form's own image.  Ceiling 2e-5 for every form (f32
+# accumulation over a split of at most 2048 rows plus at most 16 slabs).  Each bar is the worst value measured on the
+# MI355X over all cases of the form (in brackets), with a margin of 3.5 x or more; the device is run-to-run deterministic.
+CEILING = 2e-5
+BARS = {
+    "f32": 1.0e-6,         # k <= 16, f32 images                    [2.8e-7, k3_plain]
+    "wide": 1.5e-6,        # k > 16, three bf16 pieces per operand  [3.8e-7, k32_wide]
+    "f32_mfma": 1.0e-6,    # k > 16, bf16_split = 2                 [1.5e-7, k64_f32mfma]
+    "sparse": 1.0e-6,      #                                        [1.9e-7, sparse_k8]
+    "fp16": 1.0e-6,        # (half1_u4: see FINDINGS)               [1.4e-7, half1_u2]
+    "u16": 1.0e-6,         #                                        [2.8e-7, half2_u4]
+}
+assert max(BARS.values()) <= CEILING
+ERR_BAR = 5e-7             # absolute, on the sweep's error (ceiling 1e-6; worst measured 9.8e-8, k3_plain)
+MUTANT_MARGIN = 4.0
+RESULTS = {}               # case id -> {"plans": [...], "tags": {...}} of the cases that passed
+ATTEMPTED = set()          # cases run in this session (a failed one does not count as covering its forms)
+DIAG = {}                  # case id -> measured statistics (written to $RESNMTF_ELEMENTWISE_OUT)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# problems
+# ---------------------------------------------------------------------------------------------------------------------
+def dense(n, m, k, seed=0, blocks=None):
+    return synth.make_problem([(n, m)], k, seed_base=seed) if blocks is None else _single(
+        synth.planted_view(n, m, blocks, 1000 + seed), k, seed)
+
+
+def _single(x, k, seed):
+    n, m = x.shape
+    f, s, g = synth.random_init(n, m, k, 2000 + seed)
+    z = np.zeros((1, 1))
+    return synth.Problem([x], [f], [s], [g], z, z, z, k, "single", row_names=[[f"row_{i}" for i in range(n)]],
+                         col_names=[[f"col_{j}" for j in range(m)]])
+
+
+def outliers(n, m, k, seed):
+    """Planted data with a few entries 3000 x the rest: the 16-bit image's error exceeds the x_half = 3 guard."""
+    x = synth.planted_view(n, m, k, 1000 + seed, normalise=False)
+    rng = np.random.default_rng(seed)
+    x[rng.integers(0, n, 5), rng.integers(0, m, 5)] *= 3000.0
+    return _single(x / x.sum(axis=0)[None, :], k, seed)
+
+
+def zero_rows(n, m, k, seed):
+    """A view with all-zero rows (and F rows that start at zero): the zero and NaN -> 1 branches of the updates."""
+    prob = dense(n, m, k, seed)
+    x = prob.data[0].copy()
+    x[[0, 5, n // 2], :] = 0.0
+    prob.data[0] = x / x.sum(axis=0)[None, :]
+    prob.init_f[0][[0, 7], :] = 0.0
+    prob.init_g[0][:, k - 1] = 0.0 if k > 1 else prob.init_g[0][:, k - 1]
+    return prob
+
+
+def sparse_one(n, m, k, density, seed, skew=False, empty=False):
+    rng = np.random.default_rng(seed)
+    x = synth.planted_view(n, m, max(2, min(k, 8)), 1000 + seed)
+    keep = None
+    if skew:                                   # a row and a column far longer than a work block
+        keep = np.zeros((n, m), dtype=bool)
+        keep[3, rng.random(m) < 0.7] = True
+        keep[rng.random(n) < 0.7, m - 2] = True
+    y = sparsify(x, density, seed + 1, keep)
+    if empty:                                  # empty rows and columns (uploaded as pre-processed)
+        y[[1, n // 2], :] = 0.0
+        y[:, [2, m // 3]] = 0.0
+    return _single(y, k, seed)
+
+
+def coupled(n_views, n, m, k, seed, same_rows=True, **w):
+    """n_views views over one row set (identity row maps when same_rows: the fused F chain applies) and partly shared
+    columns, phi / psi / xi couplings."""
+    shapes = [(n, m - 7 * v) for v in range(n_views)]
+    same = tuple(range(n_views)) if same_rows else ()
+    return coupled_problem(shapes, k, seed, same_order_views=same, **w)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the cases: (id, problem factory, engine options, sweeps before, sparse upload)
+# ---------------------------------------------------------------------------------------------------------------------
+def _cases():
+    C = []
+
+    def add(cid, make, opts=None, before=0, sparse=False):
+        C.append((cid, make, dict(opts or {}), before, sparse))
+    # k <= 16, f32 images
+    for k in (2, 3, 8, 15, 16):
+        add(f"k{k}_plain", lambda k=k: dense(1000 + 37 * k, 700 + 11 * k, k, k), before=10)
+    add("k8_w4", lambda: dense(900, 650, 8, 1), {"pass_waves": 4})
+    add("k16_w16", lambda: dense(1100, 900, 16, 2), {"pass_waves": 16}, before=10)
+    add("k8_pingpong", lambda: dense(4100, 4097, 8, 3), {"target_workgroups": 64})
+    add("k16_modeB", lambda: dense(1200, 800, 16, 4), {"kk_mode": 2}, before=10)
+    add("k3_modeB_w4", lambda: dense(600, 500, 3, 5), {"kk_mode": 2, "pass_waves": 4})
+    # geometry edges
+    add("tiny_13x63", lambda: dense(13, 63, 3, 6))
+    add("edge_64x65", lambda: dense(64, 65, 8, 7))
+    add("edge_65x129", lambda: dense(65, 129, 8, 8), before=10)
+    add("edge_129x64", lambda: dense(129, 64, 15, 9))
+    add("edge_63x13", lambda: dense(63, 13, 2, 10))
+    add("forced_splits", lambda: dense(1000, 1000, 8, 11), {"pass_splits_xg": 3, "pass_splits_xtf": 5})
+    add("no_pitch_pad_1024", lambda: dense(1024, 1024, 8, 12), {"no_pitch_pad": True}, before=10)
+    add("lds_pad", lambda: dense(777, 555, 8, 13), {"pass_lds_pad_kb": 8})
+    # k > 16: NT 2, 3, 4, wide form (default) and the plain f32 MFMA form
+    for k in (17, 31, 32, 33, 47, 48, 49, 63, 64):
+        add(f"k{k}_wide", lambda k=k: dense(900 + 13 * k, 600 + 7 * k, k, 20 + k), before=10 if k in (32, 64) else 0)
+    for k in (17, 40, 64):
+        add(f"k{k}_f32mfma", lambda k=k: dense(700 + k, 500 + k, k, 30 + k), {"bf16_split": 2})
+    add("k32_modeA", lambda: dense(1000, 700, 32, 40), {"kk_mode": 1})
+    add("k48_modeA_f32mfma", lambda: dense(800, 600, 48, 41), {"kk_mode": 1, "bf16_split": 2})
+    add("k32_xcd", lambda: dense(3000, 2500, 32, 42), {"xcd_order": True}, before=10)
+    add("k64_xcd_splits", lambda: dense(2000, 3000, 64, 43), {"xcd_order": True, "pass_splits_xg": 3, "pass_splits_xtf": 3})
+    add("k24_tall", lambda: dense(5000, 300, 24, 44))
+    add("k40_wide_grid", lambda: dense(300, 5000, 40, 45))
+    # 2-byte images: x_half 1 (fp16) and 2 (16-bit integers) x half_unroll, partial last trips
+    for xh in (1, 2):
+        for hu in (2, 3, 4, 6):
+            add(f"half{xh}_u{hu}", lambda xh=xh, hu=hu: dense(1000 + 17 * hu, 700 + 9 * hu, 8, 50 + hu), {"x_half": xh, "half_unroll": hu},
+                before=10 if hu == 4 else 0)
+    add("half1_default", lambda: dense(1060, 750, 8, 57), {"x_half": 1})          # (half_unroll 0: the default, 4)
+    add("half3_guard_pass", lambda: dense(900, 700, 8, 60), {"x_half": 3})
+    add("half3_guard_fail", lambda: outliers(900, 700, 8, 61), {"x_half": 3})
+    # sparse views: KP 16 / 32 / 48 / 64, densities, empty lines, long lines
+    for k, dens in ((8, 0.05), (20, 0.1), (40, 0.02), (64, 0.3)):
+        add(f"sparse_k{k}", lambda k=k, dens=dens: sparse_one(1500, 900, k, dens, 70 + k), sparse=True, before=10 if k == 8 else 0)
+    add("sparse_d0.001", lambda: sparse_one(4000, 3000, 6, 0.001, 80), sparse=True)
+    add("sparse_d0.5", lambda: sparse_one(800, 600, 16, 0.5, 81), sparse=True)
+    add("sparse_skew_empty", lambda: sparse_one(2500, 900, 12, 0.002, 82, skew=True, empty=True), sparse=True)
+    # coupled views
+    add("chain2_one_slab", lambda: coupled(2, 900, 300, 8, 90, phi_w=1.0, psi_w=0.5, xi_w=0.3), {"pass_splits_xg": 1})
+    add("chain2_slabs", lambda: coupled(2, 900, 700, 8, 91, phi_w=1.0), {"pass_splits_xg": 3}, before=10)
+    add("chain4_one_slab", lambda: coupled(4, 700, 300, 6, 92, phi_w=1.0, xi_w=0.5), {"pass_splits_xg": 1})
+    add("chain4_slabs", lambda: coupled(4, 700, 500, 6, 93, phi_w=1.0, psi_w=0.4), {"pass_splits_xg": 4})
+    add("chain3_no_f_chain", lambda: coupled(3, 800, 400, 8, 94, phi_w=1.0, psi_w=0.5, xi_w=0.5), {"no_f_chain": True})
+    add("coupled_partial_na", lambda: coupled_problem([(700, 400), (650, 420), (600, 380)], 8, 95, phi_w=1.5, psi_w=0.7,
+                                                      xi_w=0.4, na_pairs=((0, 2),)), before=10)
+    add("coupled_k20_restricted", lambda: coupled_problem([(800, 500), (760, 520)], 20, 96, phi_w=1.0, psi_w=0.6, xi_w=0.3))
+    add("coupled_k40_restricted", lambda: coupled_problem([(600, 450), (640, 430), (620, 470)], 40, 97, phi_w=1.0, psi_w=1.0,
+                                                          na_pairs=((1, 2),)))
+    add("zero_rows", lambda: zero_rows(500, 300, 5, 98))
+    add("zero_rows_coupled", lambda: _zero_rows_coupled())
+    return C
+
+
+def _zero_rows_coupled():
+    prob = coupled(2, 400, 250, 4, 99, phi_w=1.0, xi_w=0.5)
+    x = prob.data[1].copy()
+    x[[2, 9], :] = 0.0
+    prob.data[1] = x / x.sum(axis=0)[None, :]
+    prob.init_f[1][[2, 3], :] = 0.0
+    return prob
+
+
+CASES = _cases()
+CASE_IDS = [c[0] for c in CASES]
+
+# FINDING (fp16 form, pass_half_kernel): the factor operand is split in registers into two fp16 pieces of b * 2^13
+# (RESNMTF_B16_SCALE), hi + lo, "22 bits".  That holds only while the lo piece is a normal fp16 number, i.e. for entries
+# b >= 2^-16; below, lo is subnormal and each entry keeps an ABSOLUTE error of up to 2^-38 (sweep_ref.fp16_split).  The
+# raw factors of the loop are not normalised, and after 10 sweeps of half1_u4 every G entry is below 2^-16 (smallest
+# 8e-12): rows of X.G carried by tiny G entries move, and the device's F step is 1.45e-4 from fp64 on the fp16 image
+# (G and S about 1.2e-6).  A scale chosen from the factor's magnitude (or a third piece) would fix it.  Until then the
+# case is checked twice: every step within the fp16 bar of a reference whose pass products use the emulated split
+# (_split_reference: this pins the deviation to the split and nothing else), and within FINDINGS' bound of plain fp64 --
+# with the F step still above the bar, so that a fix shows.  Measured: every step within 1.5e-7 of the split's
+# reference.  It does not count towards test_forms_covered (half1_default does).
+FINDINGS = {"half1_u4": 3e-4}      # case -> bound on max |got / ref - 1| against plain fp64 (measured 1.45e-4)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the run
+# ---------------------------------------------------------------------------------------------------------------------
+def _engine(prob, sparse_views, opts):
+    shapes = [x.shape for x in prob.data]
+    n_v = len(shapes)
+    nnz = [int(sp.csc_matrix(x).nnz) for x in prob.data] if sparse_views else None
+    e = Engine([s[0] for s in shapes], [s[1] for s in shapes], [prob.k] * n_v, nnz=nnz, **opts)
+    for v in range(n_v):
+        if sparse_views:
+            e.set_view_sparse(v, sp.csc_matrix(prob.data[v]), pre_processed=True)
+        else:
+            e.set_view(v, prob.data[v])
+        e.set_factors(v, prob.init_f[v], prob.init_s[v], prob.init_g[v])
+    e.set_restrictions(prob.phi, prob.xi, prob.psi)
+    rs, cs = naming.shared_names(prob.row_names), naming.shared_names(prob.col_names)
+    for v in range(n_v):
+        for w in range(n_v):
+            if v != w:
+                e.set_shared_rows(v, w, *naming.index_pairs(prob.row_names[v], prob.row_names[w], rs[v].get(w)))
+                e.set_shared_cols(v, w, *naming.index_pairs(prob.col_names[v], prob.col_names[w], cs[v].get(w)))
+    return e
+
+
+def form_of(plan):
+    if plan["image"] != "f32":
+        return plan["image"]
+    if plan["nt"] == 1:
+        return "f32"
+    return "wide" if plan["wide"][0] else "f32_mfma"
+
+
+def _mutants(x, before, ref, prob, v):
+    """The statistic between the true reference and references of the bugs this test exists to catch (view v)."""
+    from oracle import resnmtf_oracle as O
+    f0 = [b[0] for b in before]
+    F, S, G, lam, mu = before[v]
+    rn, cn = prob.row_names, prob.col_names
+    ri, ci = O.reorder_data(rn), O.reorder_data(cn)
+    fs = [r for r in ref["f"][:v]] + f0[v:]
+
+    def f_step(xm, gm=G):
+        return O.update_f(xm, fs, S, gm, lam, prob.phi, v, ri[v], rn[v], rn)
+
+    def g_step(xm):
+        gs = [r for r in ref["g"][:v]] + [b[2] for b in before][v:]
+        return O.update_g(xm, ref["f"][v], S, gs, mu, prob.psi, v, ci[v], cn[v], cn)
+    n, m = x.shape
+    k = F.shape[1]
+    out = {}
+    xm = x.copy(); xm[:, m - 1] = 0.0
+    out["X.G without its last column"] = rel_stat(f_step(xm), ref["f"][v])[0]
+    xm = x.copy(); xm[n - 1, :] = 0.0
+    out["Xt.F without the last row"] = rel_stat(g_step(xm), ref["g"][v])[0]
+    xm = x.copy(); xm[:, 16 * ((m - 1) // 16):] = 0.0
+    out["X.G without its last 16-row step"] = rel_stat(f_step(xm), ref["f"][v])[0]
+    a = 15 if k > 16 else k - 2
+    gm = G.copy(); gm[:, [a, a + 1]] = gm[:, [a + 1, a]]
+    out[f"G columns {a}, {a + 1} swapped"] = rel_stat(f_step(x, gm), ref["f"][v])[0]
+    return out
+
+
+def _split_reference(ref, x, before, after, prob):
+    """The reference of an uncoupled one-view sweep on the fp16 image with the streaming passes' products formed from
+    the emulated two-piece factor operand (sweep_ref.fp16_split) -- X.G in the F step, Xt.F' in the G and S steps --
+    and everything else as in fp64: each step's fp64 reference scaled by the ratio of its numerator
+    product with the split operand to the same product without it (update_f / update_g / update_s of a view without
+    coupling are ``current * numerator / denominator``)."""
+    assert not (np.any(prob.phi) or np.any(prob.psi) or np.any(prob.xi)) and len(prob.data) == 1
+    F0, S0, G0 = before[0], before[1], before[2]
+    F1, G1 = after[0], after[2]
+
+    def ratio(a, b):
+        return np.divide(a, b, out=np.ones_like(b), where=b != 0)
+    out = {key: list(ref[key]) for key in ("f", "g", "s", "lam", "mu")}
+    out["f"][0] = ref["f"][0] * ratio((x @ fp16_split(G0)) @ S0.T, (x @ G0) @ S0.T)
+    out["g"][0] = ref["g"][0] * ratio((x.T @ fp16_split(F1)) @ S0, (x.T @ F1) @ S0)
+    out["s"][0] = ref["s"][0] * ratio((fp16_split(F1).T @ x) @ G1, (F1.T @ x) @ G1)       # ((F^T X) G = T^T G, T = Xt.F')
+    return out
+
+
+def run_case(cid):
+    _, make, opts, n_before, sparse_views = CASES[CASE_IDS.index(cid)]
+    prob = make()
+    e = _engine(prob, sparse_views, opts)
+    try:
+        n_v = len(prob.data)
+        if n_before:
+            e.run(n_before)
+        before = [e.get_factors(v) for v in range(n_v)]
+        err = e.run(1)
+        after = [e.get_factors(v) for v in range(n_v)]
+        plans = [e.view_plan(v) for v in range(n_v)]
+        images = [stream_image(e, v, prob.data[v], plans[v]) for v in range(n_v)]
+        img_info = [e.view_image_info(v) for v in range(n_v)]
+    finally:
+        e.close()
+    return prob, opts, before, after, err, plans, images, img_info
+
+
+@pytest.mark.parametrize("cid", CASE_IDS)
+def test_one_sweep_elementwise(cid):
+    prob, opts, before, after, err, plans, images, img_info = run_case(cid)
+    n_v = len(prob.data)
+    data = [np.asarray(d, dtype=np.float64) for d in prob.data]
+    ref = step_reference(images, before, after, prob.phi, prob.xi, prob.psi, prob.row_names, prob.col_names, data=data)
+    finding = FINDINGS.get(cid)
+    if finding is not None:
+        assert all(p["image"] == "fp16" for p in plans)
+        split = _split_reference(ref, images[0], before[0], after[0], prob)
+    worst, mut_ratio, failures = {}, np.inf, []
+    for v in range(n_v):
+        form = form_of(plans[v])
+        bar = BARS[form]
+        if plans[v]["image"] in ("fp16", "u16") or opts.get("x_half", 0) == 3:       # the quantiser, pinned
+            rel = half_image(data[v], opts.get("x_half", 0) >= 2)[1]
+            assert img_info[v][1] == pytest.approx(rel, rel=1e-12, abs=0), f"view {v}: 2-byte image error"
+        for i, key in enumerate(("f", "s", "g", "lam", "mu")):
+            st, nz = rel_stat(after[v][i], ref[key][v])
+            worst[f"{key}{v}"] = st
+            if finding is not None:                 # (FINDINGS: plain fp64 within the bound, the split's reference within the bar)
+                st_split, nz = rel_stat(after[v][i], split[key][v])
+                worst[f"{key}{v}_split"] = st_split
+                if st > finding or st_split > bar or nz:
+                    failures.append(f"view {v} ({form}) {key}: {st:.3e} from fp64 (bound {finding:.1e}), {st_split:.3e} from "
+                                    f"the fp16-split reference (bar {bar:.1e}), {nz} non-zero where the reference is zero")
+            elif st > bar or nz:
+                failures.append(f"view {v} ({form}) {key}: max |got/ref - 1| = {st:.3e} (bar {bar:.1e}), {nz} entries "
+                                f"non-zero where the reference is zero")
+        if finding is not None and worst[f"f{v}"] <= bar:
+            failures.append(f"view {v}: the fp16 split finding no longer shows (F step {worst[f'f{v}']:.3e} from fp64): "
+                            f"move {cid} out of FINDINGS")
+        muts = _mutants(images[v], before, ref, prob, v)
+        for name, val in muts.items():
+            mut_ratio = min(mut_ratio, val / bar)
+            assert val >= MUTANT_MARGIN * bar, f"view {v}: mutant '{name}' gives only {val:.3e} against the bar {bar:.1e}"
+    d_err = abs(float(err[-1]) - float(np.mean(ref["err"])))
+    worst["err"] = d_err
+    worst["err_values"] = (float(err[-1]), float(np.mean(ref["err"])))
+    ATTEMPTED.add(cid)
+    DIAG[cid] = {"plans": plans, "worst": worst, "form": [form_of(p) for p in plans], "mutant_ratio": float(mut_ratio)}
+    _dump()
+    assert not failures, "\n".join(failures)
+    assert d_err < ERR_BAR, f"error {err[-1]!r} against {np.mean(ref['err'])!r}"
+    RESULTS[cid] = {"plans": plans, "tags": _tags(prob, opts, plans, plans[0]["image"] == "sparse")}
+
+
+def _dump():
+    out = os.environ.get("RESNMTF_ELEMENTWISE_OUT")
+    if out:
+        with open(out, "w") as fh:
+            json.dump(DIAG, fh, indent=1, default=lambda o: list(o) if isinstance(o, tuple) else str(o))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# coverage
+# ---------------------------------------------------------------------------------------------------------------------
+def _tags(prob, opts, plans, sparse_views):
+    """What a case exercises beyond its launch plans: the options, the coupling and the shape of its data."""
+    from resnmtf_amd import naming
+    tags = set()
+    n_v = len(plans)
+    if opts.get("no_f_chain") and n_v > 1 and not any(p["f_chain_hoisted"] for p in plans):
+        tags.add("no_f_chain: several k <= 16 views, F updates not hoisted")
+    for name in ("phi", "psi", "xi"):
+        if np.any(getattr(prob, name) != 0):
+            tags.add(f"coupled: {name}" + (", k > 16" if plans[0]["nt"] >= 2 else ""))
+    for names in (prob.row_names, prob.col_names):
+        shared = naming.shared_names(names)
+        for v in range(n_v):
+            for w, nm in shared[v].items():
+                if nm is None:
+                    tags.add("coupled: NA name map")
+                elif len(nm) < min(len(names[v]), len(names[w])):
+                    tags.add("coupled: partial name map")
+    for x in prob.data:
+        d = sp.csc_matrix(x)
+        rows, cols = np.diff(d.tocsr().indptr), np.diff(d.indptr)
+        if not sparse_views:
+            if (rows == 0).any():
+                tags.add("dense view with all-zero rows")
+            continue
+        density = d.nnz / (x.shape[0] * x.shape[1])
+        if density <= 0.0015:
+            tags.add("sparse: density 0.001")
+        if density >= 0.4:
+            tags.add("sparse: density 0.5")
+        if (rows == 0).any() and (cols == 0).any():
+            tags.add("sparse: empty rows and columns")
+        if rows.max() > 50 * max(rows.mean(), 1) and cols.max() > 50 * max(cols.mean(), 1):
+            tags.add("sparse: a row and a column far longer than the rest")
+    return tags
+
+
+def _plans(cid):
+    """(plans, tags) of a case: as its test recorded them, or -- the case was not run in this session -- read from a
+    fresh engine after one sweep.  A case that ran and failed covers nothing."""
+    if cid not in RESULTS and cid not in ATTEMPTED:
+        _, make, opts, _, sparse_views = CASES[CASE_IDS.index(cid)]
+        prob = make()
+        e = _engine(prob, sparse_views, opts)
+        try:
+            e.run(1)
+            plans = [e.view_plan(v) for v in range(len(prob.data))]
+        finally:
+            e.close()
+        RESULTS[cid] = {"plans": plans, "tags": _tags(prob, opts, plans, sparse_views)}
+    r = RESULTS.get(cid)
+    return (r["plans"], r["tags"]) if r else ([], set())
+
+
+def test_forms_covered():
+    """The cases together reach every form of the issue's table, read from their launch plans (Engine.view_plan) and,
+    where a plan cannot show it, from the case's options and data (_tags).  The FINDINGS cases do not count."""
+    reached = set()
+    for cid in CASE_IDS:
+        if cid in FINDINGS:
+            continue
+        plans, tags = _plans(cid)
+        reached |= {("case", t) for t in tags}
+        for p in plans:
+            img = p["image"]
+            for i, pas in enumerate(("xg", "xtf")):
+                last = p["rows"][i] - (p["nsplit"][i] - 1) * p["rows_per_split"][i]      # rows of the last split
+                if img == "f32" and p["nt"] == 1:
+                    form = "pingpong" if p["pingpong"][i] else "plain"
+                    reached.add(("k16", pas, p["waves"][i], form))
+                    reached.add(("k16_mode", pas, p["kk_mode"]))
+                    reached.add(("k <= 16", p["k"]))
+                    if last % (4 * p["waves"][i] * p["unroll"][i]):
+                        reached.add(("ragged last trip", pas))
+                if img == "f32" and p["nt"] >= 2:
+                    reached.add(("nt", pas, p["nt"]))
+                    reached.add(("k32_mode", pas, p["kk_mode"]))
+                    reached.add(("k > 16", p["k"]))
+                    if p["wide"][i]:
+                        reached.add(("tw", pas, p["tiles_per_wg"][i]))
+                        if p["xcd_order"][i] and p["short_last"][i]:
+                            reached.add(("xcd_short_last", pas))
+                    else:
+                        reached.add(("f32_mfma", pas))
+                if img in ("fp16", "u16"):
+                    reached.add(("half", pas, img, p["half_unroll"]))
+                    if last % (16 * p["waves"][i] * p["half_unroll"]):
+                        reached.add(("half partial last trip", pas, img))
+                if img == "sparse":
+                    reached.add(("spmm", pas, p["kp"]))
+                if img != "sparse":
+                    reached.add(("rows", p["rows"][i]))
+                    if p["short_last"][i]:
+                        reached.add(("short_last", pas))
+                        if p["rows_pad"][i] % p["rows_per_split"][i]:
+                            reached.add(("rows per split not dividing rows_pad", pas))
+            if img == "f32" and not p["pitch_pad"] and p["rows_pad"][1] & (p["rows_pad"][1] - 1) == 0:
+                reached.add(("no_pitch_pad at a power-of-two pitch",))
+            if p["lds_pad_kb"] > 0:
+                reached.add(("pass_lds_pad_kb",))
+            if cid.startswith("half3_"):
+                reached.add(("x_half 3 guard", img))
+            if p["f_chain_hoisted"]:
+                reached.add(("f_chain", p["f_chain_views"], p["f_chain_one_slab"]))
+    want = set()
+    for pas in ("xg", "xtf"):
+        want |= {("k16", pas, 4, "plain"), ("k16", pas, 8, "plain"), ("k16", pas, 8, "pingpong"), ("k16", pas, 16, "plain"),
+                 ("k16_mode", pas, 0), ("k16_mode", pas, 1),
+                 ("nt", pas, 2), ("nt", pas, 3), ("nt", pas, 4), ("k32_mode", pas, 0), ("k32_mode", pas, 1),
+                 ("tw", pas, 8), ("tw", pas, 4), ("xcd_short_last", pas), ("f32_mfma", pas), ("short_last", pas),
+                 ("rows per split not dividing rows_pad", pas), ("ragged last trip", pas)}
+        want |= {("half", pas, img, hu) for img in ("fp16", "u16") for hu in (2, 3, 4, 6)}
+        want |= {("half partial last trip", pas, img) for img in ("fp16", "u16")}
+        want |= {("spmm", pas, kp) for kp in (16, 32, 48, 64)}
+    want |= {("k <= 16", k) for k in (2, 3, 8, 15, 16)}
+    want |= {("k > 16", k) for k in (17, 31, 32, 33, 47, 48, 49, 63, 64)}
+    want |= {("rows", r) for r in (13, 63, 64, 65, 129)}
+    want |= {("no_pitch_pad at a power-of-two pitch",), ("pass_lds_pad_kb",)}
+    want |= {("f_chain", nv, one) for nv in (2, 4, 8) for one in (True, False)}
+    want |= {("x_half 3 guard", "u16"), ("x_half 3 guard", "f32")}      # (both sides of the guard)
+    want |= {("case", t) for t in (
+        "no_f_chain: several k <= 16 views, F updates not hoisted",
+        "coupled: phi", "coupled: psi", "coupled: xi", "coupled: phi, k > 16", "coupled: psi, k > 16",
+        "coupled: partial name map", "coupled: NA name map", "dense view with all-zero rows",
+        "sparse: density 0.001", "sparse: density 0.5", "sparse: empty rows and columns",
+        "sparse: a row and a column far longer than the rest")}
+    # forms the planner cannot reach from resnmtf_run on one handle, with the plan value that rules them out
+    unreachable = {
+        ("f_chain", 8, True): "build_chain refuses more than 4 owned views (n_owned > 4) and enqueue_sweep hoists the chain "
+                              "only when every view is owned (all_owned): f_chain_views 8 runs in the view-sharded layouts only",
+        ("f_chain", 8, False): "as above",
+    }
+    missing = sorted(str(w) for w in want - reached - set(unreachable))
+    assert not missing, "launch forms no case reaches: " + ", ".join(missing)
+
+
+def test_view_plan_refuses_bad_arguments():
+    """resnmtf_view_plan: NULL handle / out, a bad view and a struct_size mismatch are RESNMTF_ERR_INVALID; the query
+    changes nothing (the sweep after it is bitwise the sweep without it)."""
+    import ctypes as C
+    from resnmtf_amd import _lib
+    lib = _lib.load()
+    prob = dense(300, 200, 5, 1)
+    errs = []
+    for query in (False, True):
+        e = _engine(prob, False, {})
+        try:
+            p = _lib.ViewPlan()
+            p.struct_size = C.sizeof(_lib.ViewPlan)
+            if query:
+                assert lib.resnmtf_view_plan(None, 0, C.byref(p)) == 1
+                assert lib.resnmtf_view_plan(e._h, 0, None) == 1
+                assert lib.resnmtf_view_plan(e._h, 1, C.byref(p)) == 1
+                assert lib.resnmtf_view_plan(e._h, -1, C.byref(p)) == 1
+                p.struct_size -= 4
+                assert lib.resnmtf_view_plan(e._h, 0, C.byref(p)) == 1
+                p.struct_size += 4
+                assert lib.resnmtf_view_plan(e._h, 0, C.byref(p)) == 0 and (p.k, p.kp, p.nt) == (5, 16, 1)
+                assert e.view_plan(0)["prepared"] is False
+            errs.append(e.run(3))
+            if query:
+                plan = e.view_plan(0)
+                assert plan["prepared"] and plan["image"] == "f32" and not plan["f_chain_hoisted"]
+        finally:
+            e.close()
+    assert np.array_equal(errs[0], errs[1])
