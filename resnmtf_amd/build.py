@@ -46,8 +46,10 @@ def build(force: bool = False, verbose: bool = True) -> str:
         for cmd in cmds:
             print("[resnmtf_amd.build]", " ".join(cmd), flush=True)
     procs = [subprocess.Popen(cmd) for cmd in cmds]      # (the two units side by side)
-    if any(p.wait() != 0 for p in procs):
-        raise subprocess.CalledProcessError(1, cmds[0])
+    codes = [p.wait() for p in procs]
+    for code, cmd in zip(codes, cmds):
+        if code != 0:
+            raise subprocess.CalledProcessError(code, cmd)
     link = [hipcc_path(), "--offload-arch=gfx950", "-fPIC", "-shared", "-o", OUT] + objs
     if verbose:
         print("[resnmtf_amd.build]", " ".join(link), flush=True)

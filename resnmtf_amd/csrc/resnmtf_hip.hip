@@ -24,6 +24,7 @@
 #include <random>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "resnmtf_hip.h"
@@ -224,12 +225,40 @@ bool take_events(resnmtf_handle* h, int kind, hipEvent_t* e0, hipEvent_t* e1) {
   h->ev_used += 2;
   return true;
 }
-#define LAUNCH_TIMED(h, kind, kern, grid, block, smem, ...)                                                        \
-  do {                                                                                                             \
-    hipEvent_t e0_ = nullptr, e1_ = nullptr;                                                                       \
-    if (take_events(h, kind, &e0_, &e1_)) hipExtLaunchKernelGGL(kern, grid, block, smem, (h)->stream, e0_, e1_, 0, __VA_ARGS__); \
-    else hipLaunchKernelGGL(kern, grid, block, smem, (h)->stream, __VA_ARGS__);                                     \
-  } while (0)
+// ---- the launch layer.  Every kernel of the loop goes out through launch(); WHICH instantiation of a kernel family that is,
+// is answered by the family's select_*() below and by nothing else: the launchers, set_all_attrs() (dynamic LDS limits) and
+// resnmtf_view_plan() all read that one answer.  timed_kind: RESNMTF_TIMED_* or -1 (never timed).  In timed mode the
+// start/stop events are attached to the dispatch itself, so the elapsed time is the kernel's own begin->end, the same
+// quantity rocprofv3 --kernel-trace reports.  A null kernel is a form the planner chose and no selector lists: a bug in
+// this file, not a case to fall back from.
+template <class... KArgs, class... Args>
+void launch(resnmtf_handle* h, int timed_kind, void (*kern)(KArgs...), dim3 grid, dim3 block, size_t smem, Args&&... args) {
+  if (!kern) { std::fprintf(stderr, "resnmtf: no kernel instantiation for the launch form chosen\n"); std::abort(); }
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (timed_kind >= 0 && take_events(h, timed_kind, &e0, &e1))
+    hipExtLaunchKernelGGL(kern, grid, block, smem, h->stream, e0, e1, 0, static_cast<KArgs>(args)...);
+  else
+    hipLaunchKernelGGL(kern, grid, block, smem, h->stream, static_cast<KArgs>(args)...);
+}
+
+// f(std::integral_constant<int, V>{}) for the V of the list that equals x (the last one when none does)
+template <int V0, int... Vs, class F>
+auto pick_int(int x, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+  else return x == V0 ? f(std::integral_constant<int, V0>{}) : pick_int<Vs...>(x, f);
+}
+template <class F>
+auto pick_kp(int KP, F&& f) { return pick_int<16, 32, 48, 64>(KP, f); }
+// f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...)
+template <class F>
+auto pick_bools(F&& f) { return f(); }
+template <class F, class... Bs>
+auto pick_bools(F&& f, bool b, Bs... bs) {
+  return b ? pick_bools([&](auto... cs) { return f(std::true_type{}, cs...); }, bs...)
+           : pick_bools([&](auto... cs) { return f(std::false_type{}, cs...); }, bs...);
+}
+constexpr int kKPs[] = {16, 32, 48, 64};
+constexpr bool kBools[] = {false, true};
 
 void free_view(ViewState& v) {
   if (v.fblk) { v.fblk = nullptr; v.Usum = nullptr; v.Ma_F = nullptr; v.Md_F = nullptr; v.lambda = nullptr; }   // arena slices
@@ -275,123 +304,115 @@ size_t pass_smem_bytes(int KP, int NW) {
 }
 constexpr int kMaxLds = 160 * 1024;
 
-template <int NT, int NW, int UNROLL>
-hipError_t set_pass_attr() {
-  constexpr int S3 = NT >= 2 ? 3 : 0;      // (NT = 1 has no bf16 form: the lists coincide)
-  const void* fns[8] = {reinterpret_cast<const void*>(&pass_kernel<NT, NW, UNROLL, false, false>),
-                         reinterpret_cast<const void*>(&pass_kernel<NT, NW, UNROLL, true, false>),
-                         reinterpret_cast<const void*>(&pass_kernel<NT, NW, UNROLL, false, true>),
-                         reinterpret_cast<const void*>(&pass_kernel<NT, NW, UNROLL, true, true>),
-                         reinterpret_cast<const void*>(&pass_kernel<NT, NW, UNROLL, false, false, S3>),
-                         reinterpret_cast<const void*>(&pass_kernel<NT, NW, UNROLL, true, false, S3>),
-                         reinterpret_cast<const void*>(&pass_kernel<NT, NW, UNROLL, false, true, S3>),
-                         reinterpret_cast<const void*>(&pass_kernel<NT, NW, UNROLL, true, true, S3>)};
-  for (const void* fn : fns) {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-template <int KP>
-hipError_t set_smem_attrs() {
-  hipError_t e;
-#define SET_ATTR(fn, bytes)                                                                                    \
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fn), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                               (int)(bytes))) != hipSuccess)                                                   \
-  return e
-  SET_ATTR((factor_update_kernel<KP, false, 0, false>), update_smem_bytes(KP));
-  SET_ATTR((factor_update_kernel<KP, false, 4, false>), update_smem_bytes(KP));
-  SET_ATTR((factor_update_kernel<KP, false, 8, false>), update_smem_bytes(KP));
-  SET_ATTR((factor_update_kernel<KP, false, RESNMTF_MAX_COUPLE, false>), update_smem_bytes(KP));
-  SET_ATTR((factor_update_kernel<KP, true, 0, false>), update_smem_bytes(KP));
-  SET_ATTR((factor_update_kernel<KP, true, 4, false>), update_smem_bytes(KP));
-  SET_ATTR((factor_update_kernel<KP, true, 8, false>), update_smem_bytes(KP));
-  SET_ATTR((factor_update_kernel<KP, true, RESNMTF_MAX_COUPLE, false>), update_smem_bytes(KP));
-  SET_ATTR((factor_update_kernel<KP, false, 0, true>), update_smem_bytes(KP));
-  SET_ATTR((factor_update_kernel<KP, false, 4, true>), update_smem_bytes(KP));
-  SET_ATTR((factor_update_kernel<KP, false, 8, true>), update_smem_bytes(KP));
-  SET_ATTR((factor_update_kernel<KP, false, RESNMTF_MAX_COUPLE, true>), update_smem_bytes(KP));
-  SET_ATTR((factor_update_kernel<KP, true, 0, true>), update_smem_bytes(KP));
-  SET_ATTR((factor_update_kernel<KP, true, 4, true>), update_smem_bytes(KP));
-  SET_ATTR((factor_update_kernel<KP, true, 8, true>), update_smem_bytes(KP));
-  SET_ATTR((factor_update_kernel<KP, true, RESNMTF_MAX_COUPLE, true>), update_smem_bytes(KP));
-#undef SET_ATTR
-  return hipSuccess;
-}
-
-hipError_t set_all_attrs() {
-  hipError_t e;
-#define TRY_ATTR(x) if ((e = (x)) != hipSuccess) return e
-  TRY_ATTR(set_smem_attrs<16>()); TRY_ATTR(set_smem_attrs<32>());
-  TRY_ATTR(set_smem_attrs<48>()); TRY_ATTR(set_smem_attrs<64>());
-  TRY_ATTR((set_pass_attr<1, 4, 8>())); TRY_ATTR((set_pass_attr<1, 8, 8>())); TRY_ATTR((set_pass_attr<1, 8, 4>())); TRY_ATTR((set_pass_attr<1, 16, 8>()));
-  TRY_ATTR((set_pass_attr<2, 8, 4>())); TRY_ATTR((set_pass_attr<3, 8, 4>())); TRY_ATTR((set_pass_attr<4, 8, 4>()));
-  for (const void* fn : {reinterpret_cast<const void*>(&pass_fused_kernel<8, false, true>), reinterpret_cast<const void*>(&pass_fused_kernel<8, true, true>),
-                         reinterpret_cast<const void*>(&pass_fused_kernel<4, false, true>), reinterpret_cast<const void*>(&pass_fused_kernel<4, true, true>),
-                         reinterpret_cast<const void*>(&pass_fused_kernel<8, false, false>), reinterpret_cast<const void*>(&pass_fused_kernel<8, true, false>),
-                         reinterpret_cast<const void*>(&pass_fused_kernel<4, false, false>), reinterpret_cast<const void*>(&pass_fused_kernel<4, true, false>)})
-    TRY_ATTR(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds));
-  // (s_chain_kernel also holds a static table of NVB x NVB weights: static + dynamic must stay within the CU's LDS)
-#define S_CHAIN_ATTR(KPV, NVBV) TRY_ATTR(hipFuncSetAttribute(reinterpret_cast<const void*>(&s_chain_kernel<KPV, NVBV>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds - 4096))
-  S_CHAIN_ATTR(16, 4); S_CHAIN_ATTR(16, 8); S_CHAIN_ATTR(16, RESNMTF_MAX_COUPLE + 1);
-  S_CHAIN_ATTR(32, 4); S_CHAIN_ATTR(32, 8); S_CHAIN_ATTR(32, RESNMTF_MAX_COUPLE + 1);
-  S_CHAIN_ATTR(48, 4); S_CHAIN_ATTR(48, 8); S_CHAIN_ATTR(48, RESNMTF_MAX_COUPLE + 1);
-  S_CHAIN_ATTR(64, 4); S_CHAIN_ATTR(64, 8); S_CHAIN_ATTR(64, RESNMTF_MAX_COUPLE + 1);
-#undef S_CHAIN_ATTR
-#define WCHAIN_ATTR(KPV, G, NVBV) TRY_ATTR(hipFuncSetAttribute(reinterpret_cast<const void*>(&wide_chain_kernel<KPV, G, NVBV>), \
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)wide_chain_smem_bytes(KPV)))
-  WCHAIN_ATTR(32, false, 4); WCHAIN_ATTR(32, true, 4); WCHAIN_ATTR(32, false, 8); WCHAIN_ATTR(32, true, 8);
-  WCHAIN_ATTR(48, false, 4); WCHAIN_ATTR(48, true, 4); WCHAIN_ATTR(48, false, 8); WCHAIN_ATTR(48, true, 8);
-  WCHAIN_ATTR(64, false, 4); WCHAIN_ATTR(64, true, 4); WCHAIN_ATTR(64, false, 8); WCHAIN_ATTR(64, true, 8);
-#undef WCHAIN_ATTR
-#define SCHAIN_ATTR(KPV, G, NVBV) TRY_ATTR(hipFuncSetAttribute(reinterpret_cast<const void*>(&wide_chain_kernel<KPV, G, NVBV, true>), \
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)wide_chain_smem_bytes(KPV)))
-  SCHAIN_ATTR(16, false, 4); SCHAIN_ATTR(16, true, 4); SCHAIN_ATTR(16, false, 8); SCHAIN_ATTR(16, true, 8);
-  SCHAIN_ATTR(32, false, 4); SCHAIN_ATTR(32, true, 4); SCHAIN_ATTR(32, false, 8); SCHAIN_ATTR(32, true, 8);
-  SCHAIN_ATTR(48, false, 4); SCHAIN_ATTR(48, true, 4); SCHAIN_ATTR(48, false, 8); SCHAIN_ATTR(48, true, 8);
-  SCHAIN_ATTR(64, false, 4); SCHAIN_ATTR(64, true, 4); SCHAIN_ATTR(64, false, 8); SCHAIN_ATTR(64, true, 8);
-#undef SCHAIN_ATTR
-#define SLCHAIN_ATTR(KPV, G, NVBV) TRY_ATTR(hipFuncSetAttribute(reinterpret_cast<const void*>(&slice_chain_kernel<KPV, G, NVBV>), \
-                                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)slice_chain_smem_bytes(KPV, NVBV)))
-  SLCHAIN_ATTR(16, false, 4); SLCHAIN_ATTR(16, true, 4); SLCHAIN_ATTR(16, false, 8); SLCHAIN_ATTR(16, true, 8);
-  SLCHAIN_ATTR(32, false, 4); SLCHAIN_ATTR(32, true, 4); SLCHAIN_ATTR(32, false, 8); SLCHAIN_ATTR(32, true, 8);
-  SLCHAIN_ATTR(48, false, 4); SLCHAIN_ATTR(48, true, 4); SLCHAIN_ATTR(48, false, 8); SLCHAIN_ATTR(48, true, 8);
-  SLCHAIN_ATTR(64, false, 4); SLCHAIN_ATTR(64, true, 4); SLCHAIN_ATTR(64, false, 8); SLCHAIN_ATTR(64, true, 8);
-#undef SLCHAIN_ATTR
-#define SPMM_ATTR(KPV) TRY_ATTR(hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_kernel<KPV, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kk_smem_bytes(KPV, 8))); \
-                       TRY_ATTR(hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_kernel<KPV, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kk_smem_bytes(KPV, 8)))
-  SPMM_ATTR(16); SPMM_ATTR(32); SPMM_ATTR(48); SPMM_ATTR(64);
-#undef SPMM_ATTR
-#define CHAIN_ATTR(NVB, PFV) TRY_ATTR(hipFuncSetAttribute(reinterpret_cast<const void*>(&f_chain_kernel<NVB, PFV>), \
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)f_chain_smem_bytes<NVB>()))
-  CHAIN_ATTR(2, 1); CHAIN_ATTR(4, 1); CHAIN_ATTR(8, 1); CHAIN_ATTR(2, 4); CHAIN_ATTR(4, 4); CHAIN_ATTR(8, 4);
-#undef CHAIN_ATTR
-#define GCHAIN_ATTR(NVB) TRY_ATTR(hipFuncSetAttribute(reinterpret_cast<const void*>(&f_chain_kernel<NVB, 1, true>), \
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)f_chain_smem_bytes<NVB>()))
-  GCHAIN_ATTR(2); GCHAIN_ATTR(4); GCHAIN_ATTR(8);
-#undef GCHAIN_ATTR
-#undef TRY_ATTR
-  return hipSuccess;
-}
-
 // waves per workgroup: 8; k <= 16 also has 4- and 16-wave instantiations (tuning sweeps)
 int max_pass_waves(int NT) { return NT <= 1 ? 16 : 8; }
 // workgroups of a pass launch one CU holds at once: the kernels' __launch_bounds__ (kernels.hip.inc,
 // pass_min_blocks) keeps the k <= 32 instantiations within 128 VGPRs
 int pass_blocks_per_cu(int NT, int nw) { return pass_min_blocks(NT, nw); }
 
-// xg = false: Xt.F pass + kk_f;  xg = true: X.G pass + kk_s (mode 0 = run prologue, 1 = full S update)
-// can the F (kind 0) / G (kind 1) update of view v ride in the pass launch that consumes it (pass_fused_kernel)?  Mode A at
-// k <= 16 with the f32 images and 8-wave workgroups, the unrestricted update form (the coupled forms exceed the pass's
-// register budget), and few enough row blocks that every updater is resident among the launch's first workgroups
-bool can_fuse_update(const resnmtf_handle* h, const ViewState& v, int kind) {
-  if (h->opt.fuse_updates == 0 || v.kk_mode != 0 || v.NT != 1 || v.half || v.sparse || !v.fuse_cnt) return false;
-  const UpdateArgs& u = kind == 0 ? v.argF : v.argG;
-  const PassArgs& p = kind == 0 ? v.passXtF : v.passXG;
-  const int nblk = kind == 0 ? v.nblkF : v.nblkG, nw = kind == 0 ? v.nw_xtf : v.nw_xg;
-  return nw == 8 && !u.restricted && nblk <= p.ntiles * p.nsplit && nblk <= h->n_cu;
+// ---- one selector per kernel family: run-time parameters -> the instantiation, as a typed function pointer
+using PassFn = void (*)(PassArgs, KKFArgs, KKSArgs);
+using FusedFn = void (*)(PassArgs, KKFArgs, KKSArgs, UpdateArgs, FuseArgs);
+using SpmmFn = void (*)(SpmmArgs, KKFArgs, KKSArgs);
+template <int NVB> using WideFn = void (*)(WideChainArgs<NVB>);
+
+// pass_kernel at k <= 16 (NT = 1): exactly the forms of RESNMTF_PASS_K16_LIST, which is also what the second translation
+// unit instantiates -- a form cannot be selectable without being emitted
+struct PassK16Form { int nw, unroll; bool xg, mode_a; PassFn fn; };
+const PassK16Form kPassK16[] = {
+#define RESNMTF_FORM(NW, UNR, XG, MA) {NW, UNR, XG, MA, &pass_kernel<1, NW, UNR, XG, MA, 0>},
+    RESNMTF_PASS_K16_LIST(RESNMTF_FORM)
+#undef RESNMTF_FORM
+};
+// k > 16: 8 waves, UNROLL 4, and the only forms with a `wide` variant (SPLIT = 3: three bf16 pieces per operand)
+PassFn select_pass(int NT, int nw, int unroll, bool xg, bool mode_a, bool wide) {
+  if (NT <= 1) {
+    for (const PassK16Form& f : kPassK16)
+      if (!wide && f.nw == nw && f.unroll == unroll && f.xg == xg && f.mode_a == mode_a) return f.fn;
+    return nullptr;
+  }
+  if (nw != 8 || unroll != 4) return nullptr;
+  return pick_int<2, 3, 4>(NT, [&](auto nt) { return pick_bools([](auto x, auto m, auto w) {
+    return &pass_kernel<decltype(nt)::value, 8, 4, decltype(x)::value, decltype(m)::value, (decltype(w)::value ? 3 : 0)>; }, xg, mode_a, wide); });
 }
+// pass_half_kernel (2-byte images: k <= 16, mode A, 8 waves).  No raised LDS limit: it asks for pass_smem_bytes(16, 8) = 20 KB
+// plus pass_lds_pad_kb, which is within the 64 KB any kernel may have while pass_lds_pad_kb <= 44
+PassFn select_pass_half(int unroll, bool xg, bool u16) {
+  return pick_int<2, 3, 6, 4>(unroll, [&](auto un) { return pick_bools([](auto x, auto u) { return &pass_half_kernel<decltype(un)::value, decltype(x)::value, decltype(u)::value>; }, xg, u16); });
+}
+// pass_fused_kernel: UNROLL 4 = the ping-pong form, 8 the plain one; pre: with the prefetch of the first X trip
+FusedFn select_pass_fused(int unroll, bool xg, bool pre) {
+  return pick_int<4, 8>(unroll, [&](auto un) { return pick_bools([](auto x, auto p) { return &pass_fused_kernel<decltype(un)::value, decltype(x)::value, decltype(p)::value>; }, xg, pre); });
+}
+SpmmFn select_spmm(int KP, bool xg) {
+  return pick_kp(KP, [&](auto kp) { return pick_bools([](auto x) { return &spmm_kernel<decltype(kp)::value, decltype(x)::value>; }, xg); });
+}
+// factor_update_kernel.  Coupling-count bucket of the instantiation: 0 = unrestricted form, else room for 4, 8 or 16 coupled views
+constexpr int kCoupleBuckets[] = {0, 4, 8, RESNMTF_MAX_COUPLE};
+int couple_bucket(const UpdateArgs& a) { return !a.restricted ? 0 : a.n_couple <= 4 ? 4 : a.n_couple <= 8 ? 8 : RESNMTF_MAX_COUPLE; }
+auto select_update(int KP, bool g, int bucket, bool emit) {
+  return pick_kp(KP, [&](auto kp) { return pick_int<0, 4, 8, RESNMTF_MAX_COUPLE>(bucket, [&](auto nc) {
+    return pick_bools([](auto G, auto E) { return &factor_update_kernel<decltype(kp)::value, decltype(G)::value, decltype(nc)::value, decltype(E)::value>; }, g, emit);
+  }); });
+}
+// f_chain_kernel<NVB, PF, IS_G>: the F form reads one folded slab per view (PF = 1) or up to four raw ones, the G form always one
+template <int NVB>
+auto select_f_chain(bool g, bool one_slab) { return g ? &f_chain_kernel<NVB, 1, true> : one_slab ? &f_chain_kernel<NVB, 1> : &f_chain_kernel<NVB, 4>; }
+// wide_chain_kernel<KP, IS_G, NVB, SLICED>: the replicated chains exist for k > 16 only (build_wide_chain), the sliced ones at any k
+template <int NVB>
+WideFn<NVB> select_wide_chain(int KP, bool g, bool sliced) {
+  return pick_kp(KP, [&](auto kp) { return pick_bools([](auto G, auto S) -> WideFn<NVB> {
+    constexpr int K = decltype(kp)::value;
+    if constexpr (decltype(S)::value) return &wide_chain_kernel<K, decltype(G)::value, NVB, true>;
+    else if constexpr (K >= 32) return &wide_chain_kernel<K, decltype(G)::value, NVB>;
+    else return nullptr;
+  }, g, sliced); });
+}
+template <int NVB>
+auto select_slice_chain(int KP, bool g) {
+  return pick_kp(KP, [&](auto kp) { return pick_bools([](auto G) { return &slice_chain_kernel<decltype(kp)::value, decltype(G)::value, NVB>; }, g); });
+}
+// slice_products_kernel, slice_walk_kernel (4-row workgroups), slice_unpack_kernel: no dynamic LDS, so no raised limit
+template <int NVB>
+auto select_slice_products(int KP) { return pick_kp(KP, [](auto kp) { return &slice_products_kernel<decltype(kp)::value, NVB>; }); }
+template <int NVB>
+auto select_slice_walk(int KP) { return pick_kp(KP, [](auto kp) { return &slice_walk_kernel<decltype(kp)::value, NVB, 4>; }); }
+auto select_slice_unpack(int KP) { return pick_kp(KP, [](auto kp) { return &slice_unpack_kernel<decltype(kp)::value>; }); }
+// s_chain_kernel<KP, NVB>: room for 4, 8 or RESNMTF_MAX_COUPLE + 1 views
+constexpr int kSChainViews[] = {4, 8, RESNMTF_MAX_COUPLE + 1};
+auto select_s_chain(int KP, int n_views) {
+  const int nvb = n_views <= 4 ? 4 : n_views <= 8 ? 8 : RESNMTF_MAX_COUPLE + 1;
+  return pick_kp(KP, [&](auto kp) { return pick_int<4, 8, RESNMTF_MAX_COUPLE + 1>(nvb, [](auto nv) { return &s_chain_kernel<decltype(kp)::value, decltype(nv)::value>; }); });
+}
+
+// the dynamic LDS limit of every form the selectors can return, over their whole (finite) domains: what the launchers can
+// select is attributed by construction.  The families without a raised limit say so at their selector.
+hipError_t set_all_attrs() {
+  hipError_t e = hipSuccess;
+  auto lds = [&](auto* fn, size_t bytes) {      // (nullptr: a combination the family does not have)
+    if (e == hipSuccess && fn) e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  };
+  for (const PassK16Form& f : kPassK16) lds(f.fn, kMaxLds);
+  for (bool xg : kBools)
+    for (bool b : kBools) {
+      for (int NT : {2, 3, 4}) { lds(select_pass(NT, 8, 4, xg, b, false), kMaxLds); lds(select_pass(NT, 8, 4, xg, b, true), kMaxLds); }
+      for (int unroll : {4, 8}) lds(select_pass_fused(unroll, xg, b), kMaxLds);
+    }
+  for (int KP : kKPs) {
+    for (bool g : kBools) {      // (g: IS_G of the updates and chains, IS_XG of spmm_kernel)
+      for (int bucket : kCoupleBuckets) { lds(select_update(KP, g, bucket, false), update_smem_bytes(KP)); lds(select_update(KP, g, bucket, true), update_smem_bytes(KP)); }
+      for (bool sliced : kBools) { lds(select_wide_chain<4>(KP, g, sliced), wide_chain_smem_bytes(KP)); lds(select_wide_chain<8>(KP, g, sliced), wide_chain_smem_bytes(KP)); }
+      lds(select_slice_chain<4>(KP, g), slice_chain_smem_bytes(KP, 4)); lds(select_slice_chain<8>(KP, g), slice_chain_smem_bytes(KP, 8));
+      lds(select_spmm(KP, g), kk_smem_bytes(KP, 8));
+    }
+    // (s_chain_kernel also holds a static table of NVB x NVB weights: static + dynamic must stay within the CU's LDS)
+    for (int views : kSChainViews) lds(select_s_chain(KP, views), kMaxLds - 4096);
+  }
+  for (bool g : kBools)
+    for (bool one_slab : kBools) { lds(select_f_chain<2>(g, one_slab), f_chain_smem_bytes<2>()); lds(select_f_chain<4>(g, one_slab), f_chain_smem_bytes<4>()); lds(select_f_chain<8>(g, one_slab), f_chain_smem_bytes<8>()); }
+  return e;
+}
+
 // sparse view: X.G from the CSR, Xt.F from the CSC (spmm_kernel), same slabs as the dense passes.  kk: the k x k job in
 // workgroup 0 (hand-off mode A, as pass_kernel); otherwise (SVD initialisation) B / P / width come from the caller
 SpmmArgs spmm_args(const ViewState& v, bool xg) {
@@ -401,157 +422,150 @@ SpmmArgs spmm_args(const ViewState& v, bool xg) {
   a.ldb = v.KP;
   return a;
 }
-void launch_spmm(resnmtf_handle* h, const SpmmArgs& a, int KP, bool xg, const KKFArgs& kf, const KKSArgs& ks, bool timed_ok) {
-  const dim3 grid((a.kk_block0 ? 1 : 0) + ceil_div(a.nblk * a.nsplit, 8)), block(512);
-  const size_t smem = a.kk_block0 && !a.no_kk ? kk_smem_bytes(KP, 8) : 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  const bool timed = timed_ok && take_events(h, xg ? RESNMTF_TIMED_XG : RESNMTF_TIMED_XTF, &ev0, &ev1);
-#define LAUNCH_SPMM(KPV, XG)                                                                                              \
-  if (timed) hipExtLaunchKernelGGL((spmm_kernel<KPV, XG>), grid, block, smem, h->stream, ev0, ev1, 0, a, kf, ks);        \
-  else hipLaunchKernelGGL((spmm_kernel<KPV, XG>), grid, block, smem, h->stream, a, kf, ks)
-#define LAUNCH_SPMM_K(KPV) if (xg) { LAUNCH_SPMM(KPV, true); } else { LAUNCH_SPMM(KPV, false); }
-  switch (KP) {
-    case 16: LAUNCH_SPMM_K(16); break;
-    case 32: LAUNCH_SPMM_K(32); break;
-    case 48: LAUNCH_SPMM_K(48); break;
-    default: LAUNCH_SPMM_K(64); break;
+dim3 spmm_grid(const SpmmArgs& a) { return dim3((a.kk_block0 ? 1 : 0) + ceil_div(a.nblk * a.nsplit, 8)); }
+size_t spmm_smem(const SpmmArgs& a, int KP) { return a.kk_block0 && !a.no_kk ? kk_smem_bytes(KP, 8) : 0; }
+void launch_spmm(resnmtf_handle* h, const SpmmArgs& a, int KP, bool xg, const KKFArgs& kf, const KKSArgs& ks) {
+  launch(h, -1, select_spmm(KP, xg), spmm_grid(a), dim3(512), spmm_smem(a, KP), a, kf, ks);
+}
+
+// ---- one streaming pass of a view, resolved: everything that is decided before the launch.  launch_pass launches from it,
+// resnmtf_view_plan reports it, can_fuse_update and resnmtf_pass_timings read it
+struct PassLaunch {
+  int image = 0;               // what is streamed: 0 = f32 images, 1 = sparse CSC / CSR, 2 = fp16 image, 3 = 16-bit integer image
+  bool mode_a = true;          // the k x k job is workgroup 0 (B: the last-arriving aux workgroup)
+  bool fused = false;          // the update that feeds the pass rides in its first workgroups (pass_fused_kernel)
+  bool wide = false;           // k > 16: three bf16 pieces per operand on the K = 32 MFMA, in wide workgroups
+  bool xcd_order = false;      // XCD-aware order of the wide form's main workgroups (PassArgs::xcd_n)
+  bool short_last = false;     // the last row split is shorter than the others
+  bool pingpong = false;       // k <= 16, f32 images: the ping-pong prefetch form
+  int waves = 8;
+  int unroll = 0;              // pass_kernel / pass_fused_kernel UNROLL; pass_half_kernel: wave-steps per trip; sparse: 0
+  int tiles_per_wg = 1;        // wide form: 64-column tiles per workgroup
+  int lead_blocks = 1, main_blocks = 0;      // the k x k job / the aux workgroups head the grid
+  dim3 grid, block;
+  size_t smem = 0;
+  PassFn kern = nullptr;       // exactly one of the three is set
+  FusedFn kern_fused = nullptr;
+  SpmmFn kern_spmm = nullptr;
+};
+// xg = false: Xt.F pass + kk_f;  xg = true: X.G pass + kk_s.  Reads the view's geometry (set at create / upload), not the
+// argument blocks of resnmtf_prepare, so it answers before the first prepare as well
+PassLaunch resolve_pass(const resnmtf_handle* h, const ViewState& v, bool xg, bool fuse_update = false) {
+  PassLaunch L;
+  if (v.sparse) {      // X.G from the CSR, Xt.F from the CSC (spmm_kernel), hand-off mode A at every k
+    SpmmArgs a = spmm_args(v, xg);
+    a.kk_block0 = 1;
+    L.image = 1;
+    L.main_blocks = ceil_div(a.nblk * a.nsplit, 8);
+    L.grid = spmm_grid(a); L.block = dim3(512);
+    L.smem = spmm_smem(a, v.KP);
+    L.kern_spmm = select_spmm(v.KP, xg);
+    return L;
   }
-#undef LAUNCH_SPMM_K
-#undef LAUNCH_SPMM
+  const int nw = xg ? v.nw_xg : v.nw_xtf, nsplit = xg ? v.nsplit_xg : v.nsplit_xtf, rps = xg ? v.rps_xg : v.rps_xtf;
+  const int rows_pad = xg ? v.m_pad : v.n_pad, ntiles = (xg ? v.n_pad : v.m_pad) / 64;
+  L.image = v.half ? (v.u16 ? 3 : 2) : 0;
+  L.mode_a = v.kk_mode == 0;
+  L.waves = nw;
+  // MFMA form of the main tiles (resnmtf_options.bf16_split): k <= 16 always the f32 MFMA; k > 16: three bf16 pieces per
+  // operand on the K = 32 MFMA in wide workgroups (f32-grade, default; 1 is accepted as an alias), 2 = plain f32 MFMA
+  L.wide = v.NT >= 2 && h->opt.bf16_split != 2;
+  L.xcd_order = L.wide && h->opt.xcd_order;
+  L.short_last = nsplit > 1 && rows_pad - (nsplit - 1) * rps < rps;
+  L.tiles_per_wg = L.wide ? (xg ? v.tw_xg : v.tw_xtf) : 1;
+  L.main_blocks = ceil_div(ntiles, L.tiles_per_wg) * nsplit;
+  L.lead_blocks = L.mode_a ? 1 : (xg ? 3 * v.nsaux_xg : 2 * v.nsaux_xtf);      // (aux tiles: G^T G, T^T G, colSums(G) / F^T F, colSums(F))
+  L.grid = dim3(L.lead_blocks + L.main_blocks); L.block = dim3(64 * nw);
+  L.smem = std::min<size_t>(pass_smem_bytes(v.KP, nw) + (size_t)h->opt.pass_lds_pad_kb * 1024, kMaxLds);
+  const bool pp = xg ? v.pp_xg : v.pp_xtf;
+  if (fuse_update) {
+    L.fused = true;
+    L.pingpong = pp;
+    L.unroll = pp ? 4 : 8;
+    L.smem = std::min<size_t>(std::max(L.smem, update_smem_bytes(16)), kMaxLds);
+    L.kern_fused = select_pass_fused(L.unroll, xg, h->opt.fuse_updates == 1);   // (2: without the prefetch of the first X trip)
+  } else if (v.half) {
+    // wave-steps per trip: 4 for fp16; 2 for the 16-bit integers (their widening to f32 wants the registers: c2 26.5 k
+    // sweeps/s at 2, 23.5 k at 4).  (pass_half_kernel has no ping-pong form)
+    const int hu = h->opt.half_unroll;
+    L.unroll = (hu == 2 || hu == 3 || hu == 4 || hu == 6) ? hu : (v.u16 ? 2 : 4);
+    L.kern = select_pass_half(L.unroll, xg, v.u16);
+  } else {
+    L.pingpong = v.NT == 1 && nw == 8 && pp;
+    L.unroll = v.NT >= 2 ? 4 : (nw == 8 ? (pp ? 4 : RESNMTF_K16_UNROLL) : 8);
+    L.kern = select_pass(v.NT, nw, L.unroll, xg, L.mode_a, L.wide);
+  }
+  return L;
+}
+// can the F (kind 0) / G (kind 1) update of view v ride in the pass launch that consumes it (pass_fused_kernel)?  Mode A at
+// k <= 16 with the f32 images and 8-wave workgroups, the unrestricted update form (the coupled forms exceed the pass's
+// register budget), and few enough row blocks that every updater is resident among the launch's first workgroups
+bool can_fuse_update(const resnmtf_handle* h, const ViewState& v, int kind) {
+  if (h->opt.fuse_updates == 0 || v.NT != 1 || !v.fuse_cnt) return false;
+  const PassLaunch L = resolve_pass(h, v, kind != 0);
+  if (L.image != 0 || !L.mode_a || L.waves != 8) return false;
+  const UpdateArgs& u = kind == 0 ? v.argF : v.argG;
+  const int nblk = kind == 0 ? v.nblkF : v.nblkG;
+  return !u.restricted && nblk <= L.main_blocks && nblk <= h->n_cu;
 }
 // (The k x k job's dynamic LDS is requested for every workgroup of the launch: at KP >= 48 one workgroup per CU.  Measured,
 // 200000 x 20000 at 0.5 %, k = 64: the Xt.F pass alone runs 632-650 us without that LDS against 846 us with it, but the job
 // as a launch of its own then takes 354 us behind it (the fp64 partials of 512 update workgroups) -- 1004 us in all -- so it
 // stays in workgroup 0, where it overlaps the pass.  DESIGN.md section 10.)
-void launch_pass_sparse(resnmtf_handle* h, const ViewState& v, bool xg, int mode, double tol, bool check_done) {
-  SpmmArgs a = spmm_args(v, xg);
-  a.kk_block0 = 1; a.no_kk = 0; a.ctl = h->ctl; a.check_done = check_done ? 1 : 0;
-  KKSArgs ks = v.argKS;
-  ks.mode = mode; ks.tol = tol;
-  launch_spmm(h, a, v.KP, xg, v.argKF, ks, true);
-}
+// kk_s mode: 0 = run prologue, 1 = full S update
 void launch_pass(resnmtf_handle* h, const ViewState& v, bool xg, int mode, double tol, bool check_done, bool fuse_update = false) {
-  if (v.sparse) { launch_pass_sparse(h, v, xg, mode, tol, check_done); return; }
-  PassArgs a = xg ? v.passXG : v.passXtF;
-  a.check_done = check_done ? 1 : 0;
+  const PassLaunch L = resolve_pass(h, v, xg, fuse_update);
+  const int kind = xg ? RESNMTF_TIMED_XG : RESNMTF_TIMED_XTF;
   KKFArgs kf = v.argKF;
   KKSArgs ks = v.argKS;
   ks.mode = mode; ks.tol = tol;
+  if (L.kern_spmm) {
+    SpmmArgs a = spmm_args(v, xg);
+    a.kk_block0 = 1; a.no_kk = 0; a.ctl = h->ctl; a.check_done = check_done ? 1 : 0;
+    launch(h, kind, L.kern_spmm, L.grid, L.block, L.smem, a, kf, ks);
+    return;
+  }
+  PassArgs a = xg ? v.passXG : v.passXtF;
+  a.check_done = check_done ? 1 : 0;
   // mode A: the k x k job is workgroup 0 and reads the update kernel's fp64 partials
-  a.kk_block0 = (v.kk_mode == 0) ? 1 : 0;
+  a.kk_block0 = L.mode_a ? 1 : 0;
   a.fuse_zero = (a.kk_block0 && v.fuse_cnt && !v.half) ? v.fuse_cnt + (xg ? 0 : 2) : nullptr;   // the sibling launch's arrival counter
   if (!a.kk_block0) { kf.part = nullptr; ks.part = nullptr; }
-  const int nw = xg ? v.nw_xg : v.nw_xtf;
-  // MFMA form of the main tiles (resnmtf_options.bf16_split): k <= 16 always the f32 MFMA; k > 16: three bf16 pieces per
-  // operand on the K = 32 MFMA in wide workgroups (f32-grade, default; 1 is accepted as an alias), 2 = plain f32 MFMA
-  const int split = v.NT < 2 ? 0 : (h->opt.bf16_split == 2 ? 0 : 3);
-  const int main_blocks = split == 3 ? a.ntg * a.nsplit : a.ntiles * a.nsplit;
-  const int lead_blocks = a.kk_block0 ? 1 : a.naux * a.nsplit_aux;       // the k x k job / the aux workgroups head the grid
-  const dim3 grid(lead_blocks + main_blocks), block(64 * nw);
   a.xcd_n = 0;
-  if (split == 3 && h->opt.xcd_order) {
-    // XCD-aware order of the wide form's main workgroups (PassArgs::xcd_n).  A short last split stays at the end of the grid.
-    const bool short_last = a.nsplit > 1 && a.rows_pad - (a.nsplit - 1) * a.rows_per_split < a.rows_per_split;
-    const int n_map = short_last ? (a.nsplit - 1) * a.ntg : main_blocks;
+  if (L.xcd_order) {      // a short last split stays at the end of the grid
+    const int n_map = L.short_last ? (a.nsplit - 1) * a.ntg : L.main_blocks;
     int cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int x = 0; x < 8; ++x) a.xcd_first[x] = -1;
     for (int b = 0; b < n_map; ++b) {
-      const int x = (lead_blocks + b) & 7;
-      if (a.xcd_first[x] < 0) a.xcd_first[x] = lead_blocks + b;
+      const int x = (L.lead_blocks + b) & 7;
+      if (a.xcd_first[x] < 0) a.xcd_first[x] = L.lead_blocks + b;
       ++cnt[x];
     }
     int off = 0;
     for (int x = 0; x < 8; ++x) { a.xcd_off[x] = off; off += cnt[x]; if (a.xcd_first[x] < 0) a.xcd_first[x] = 0; }
     a.xcd_n = n_map;
   }
-  const size_t smem = std::min<size_t>(pass_smem_bytes(v.KP, nw) + (size_t)h->opt.pass_lds_pad_kb * 1024, kMaxLds);
-  // timed mode: the start/stop events are attached to the dispatch itself (hipExtLaunchKernelGGL), so
-  // the elapsed time is the kernel's own begin->end, the same quantity rocprofv3 --kernel-trace reports
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  const bool timed = take_events(h, xg ? RESNMTF_TIMED_XG : RESNMTF_TIMED_XTF, &ev0, &ev1);
-  if (fuse_update) {   // the update that feeds this pass rides in its first workgroups (pass_fused_kernel)
+  if (L.fused) {
     UpdateArgs u = xg ? v.argG : v.argF;
     u.check_done = 0; u.gram_only = 0;
     FuseArgs fz{};
     fz.cnt_own = v.fuse_cnt + (xg ? 2 : 0);      // [0] arrivals, [1] the flag the waiters poll
     { static const int nap = std::getenv("RESNMTF_FUSE_NAP") ? std::atoi(std::getenv("RESNMTF_FUSE_NAP")) : 2; fz.nap = nap; }
     fz.n_upd = xg ? v.nblkG : v.nblkF; fz.err = h->fuse_err_dev;
-    const size_t smem_f = std::min<size_t>(std::max(smem, update_smem_bytes(16)), kMaxLds);
-    const bool pp = xg ? v.pp_xg : v.pp_xtf;
-    const bool pre = h->opt.fuse_updates == 1;   // (2: without the prefetch of the first X trip)
-#define LAUNCH_FUSED_P(UV, XG, PV)                                                                                              \
-    if (timed) hipExtLaunchKernelGGL((pass_fused_kernel<UV, XG, PV>), grid, block, smem_f, h->stream, ev0, ev1, 0, a, kf, ks, u, fz);    \
-    else hipLaunchKernelGGL((pass_fused_kernel<UV, XG, PV>), grid, block, smem_f, h->stream, a, kf, ks, u, fz)
-#define LAUNCH_FUSED(UV, XG) if (pre) { LAUNCH_FUSED_P(UV, XG, true); } else { LAUNCH_FUSED_P(UV, XG, false); }
-    if (xg) { if (pp) { LAUNCH_FUSED(4, true); } else { LAUNCH_FUSED(8, true); } }
-    else { if (pp) { LAUNCH_FUSED(4, false); } else { LAUNCH_FUSED(8, false); } }
-#undef LAUNCH_FUSED
-#undef LAUNCH_FUSED_P
+    launch(h, kind, L.kern_fused, L.grid, L.block, L.smem, a, kf, ks, u, fz);
     return;
   }
-  if (v.half) {       // fp16 image of X: the run-time scale (set at upload) is taken out in the slab store
-    a.out_scale = v.u16 ? 1.f / v.xscale : 1.f / (v.xscale * RESNMTF_B16_SCALE);
-    // wave-steps per trip: 4 for fp16; 2 for the 16-bit integers (their widening to f32 wants the registers: c2 26.5 k
-    // sweeps/s at 2, 23.5 k at 4)
-    const int un_def = v.u16 ? 2 : 4;
-    const int un = h->opt.half_unroll == 2 ? 2 : (h->opt.half_unroll == 6 ? 6 : (h->opt.half_unroll == 3 ? 3 : (h->opt.half_unroll == 4 ? 4 : un_def)));
-#define LAUNCH_HALF(UV, XG, U)                                                                                             \
-    if (timed) hipExtLaunchKernelGGL((pass_half_kernel<UV, XG, U>), grid, block, smem, h->stream, ev0, ev1, 0, a, kf, ks);  \
-    else hipLaunchKernelGGL((pass_half_kernel<UV, XG, U>), grid, block, smem, h->stream, a, kf, ks)
-#define LAUNCH_HALF_U(UV)                                                     \
-    if (v.u16) { if (xg) { LAUNCH_HALF(UV, true, true); } else { LAUNCH_HALF(UV, false, true); } } \
-    else { if (xg) { LAUNCH_HALF(UV, true, false); } else { LAUNCH_HALF(UV, false, false); } }
-    switch (un) {
-      case 2: LAUNCH_HALF_U(2); break;
-      case 3: LAUNCH_HALF_U(3); break;
-      case 6: LAUNCH_HALF_U(6); break;
-      default: LAUNCH_HALF_U(4); break;
-    }
-#undef LAUNCH_HALF_U
-#undef LAUNCH_HALF
-    return;
-  }
-#define LAUNCH_PASS_B(NTV, NWV, UV, XG, MA, SP)                                                                              \
-  if (timed) hipExtLaunchKernelGGL((pass_kernel<NTV, NWV, UV, XG, MA, SP>), grid, block, smem, h->stream, ev0, ev1, 0, a, kf, ks); \
-  else hipLaunchKernelGGL((pass_kernel<NTV, NWV, UV, XG, MA, SP>), grid, block, smem, h->stream, a, kf, ks)
-#define LAUNCH_PASS_M(NTV, NWV, UV, XG, MA)                                              \
-  if (split == 3) { LAUNCH_PASS_B(NTV, NWV, UV, XG, MA, ((NTV) >= 2 ? 3 : 0)); }         \
-  else { LAUNCH_PASS_B(NTV, NWV, UV, XG, MA, 0); }
-#define LAUNCH_PASS(NTV, NWV, UV)                                   \
-  if (xg && a.kk_block0) { LAUNCH_PASS_M(NTV, NWV, UV, true, true); }      \
-  else if (xg) { LAUNCH_PASS_M(NTV, NWV, UV, true, false); }               \
-  else if (a.kk_block0) { LAUNCH_PASS_M(NTV, NWV, UV, false, true); }      \
-  else { LAUNCH_PASS_M(NTV, NWV, UV, false, false); }
-  switch (v.NT * 100 + nw) {
-    case 104: LAUNCH_PASS(1, 4, 8); break;
-    case 108: if (xg ? v.pp_xg : v.pp_xtf) { LAUNCH_PASS(1, 8, 4); } else { LAUNCH_PASS(1, 8, RESNMTF_K16_UNROLL); } break;
-    case 116: LAUNCH_PASS(1, 16, 8); break;
-    case 208: LAUNCH_PASS(2, 8, 4); break;
-    case 308: LAUNCH_PASS(3, 8, 4); break;
-    default: LAUNCH_PASS(4, 8, 4); break;
-  }
-#undef LAUNCH_PASS
-#undef LAUNCH_PASS_M
-#undef LAUNCH_PASS_B
+  // 2-byte image of X: the run-time scale (set at upload) is taken out in the slab store
+  if (L.image >= 2) a.out_scale = v.u16 ? 1.f / v.xscale : 1.f / (v.xscale * RESNMTF_B16_SCALE);
+  launch(h, kind, L.kern, L.grid, L.block, L.smem, a, kf, ks);
 }
 
-// a streaming pass without a k x k job (SVD initialisation): mode A kernel, workgroup 0 idles
+// a streaming pass without a k x k job (SVD initialisation): the default mode A form of the view's k, workgroup 0 idles
 void launch_pass_plain(resnmtf_handle* h, PassArgs a, int NT, bool xg) {
   a.kk_block0 = 1; a.no_kk = 1; a.check_done = 0;
-  const KKFArgs kf{};
-  const KKSArgs ks{};
   const dim3 grid(1 + a.ntiles * a.nsplit), block(64 * 8);
   const size_t smem = std::min<size_t>(pass_smem_bytes(16 * NT, 8), kMaxLds);
-#define LAUNCH_PLAIN(NTV, UV)                                                                                      \
-  if (xg) hipLaunchKernelGGL((pass_kernel<NTV, 8, UV, true, true>), grid, block, smem, h->stream, a, kf, ks);      \
-  else hipLaunchKernelGGL((pass_kernel<NTV, 8, UV, false, true>), grid, block, smem, h->stream, a, kf, ks)
-  switch (NT) {
-    case 1: LAUNCH_PLAIN(1, 8); break;
-    case 2: LAUNCH_PLAIN(2, 4); break;
-    case 3: LAUNCH_PLAIN(3, 4); break;
-    default: LAUNCH_PLAIN(4, 4); break;
-  }
-#undef LAUNCH_PLAIN
+  launch(h, -1, select_pass(NT, 8, NT <= 1 ? RESNMTF_K16_UNROLL : 4, xg, true, false), grid, block, smem, a, KKFArgs{}, KKSArgs{});
 }
 
 template <int NVB>
@@ -577,29 +591,7 @@ void launch_update(resnmtf_handle* h, const ViewState& v, int kind, bool check_d
   a.gram_only = kind == 2 ? 1 : 0;
   if (kind == 2) { a.restricted = 0; a.n_couple = 0; }
   const int nblk = kind == 0 ? v.nblkF : v.nblkG;
-  const size_t smem = update_smem_bytes(v.KP);
-  const bool emit = v.kk_mode == 0;
-  // coupling-count bucket of the kernel instantiation: 0 = unrestricted form, else room for 4, 8 or 16 coupled views
-#define LAUNCH_UPD_K(KPV, G_, C_)                                                                                      \
-  if (emit) hipLaunchKernelGGL((factor_update_kernel<KPV, G_, C_, true>), dim3(nblk), dim3(update_threads(KPV)), smem, h->stream, a); \
-  else hipLaunchKernelGGL((factor_update_kernel<KPV, G_, C_, false>), dim3(nblk), dim3(update_threads(KPV)), smem, h->stream, a)
-#define LAUNCH_UPD_C(KPV, G_)                                               \
-  if (!a.restricted) { LAUNCH_UPD_K(KPV, G_, 0); }                          \
-  else if (a.n_couple <= 4) { LAUNCH_UPD_K(KPV, G_, 4); }                   \
-  else if (a.n_couple <= 8) { LAUNCH_UPD_K(KPV, G_, 8); }                   \
-  else { LAUNCH_UPD_K(KPV, G_, RESNMTF_MAX_COUPLE); }
-#define LAUNCH_UPD(KPV)                                  \
-  if (kind == 0) { LAUNCH_UPD_C(KPV, false); }           \
-  else { LAUNCH_UPD_C(KPV, true); }
-  switch (v.NT) {
-    case 1: LAUNCH_UPD(16); break;
-    case 2: LAUNCH_UPD(32); break;
-    case 3: LAUNCH_UPD(48); break;
-    default: LAUNCH_UPD(64); break;
-  }
-#undef LAUNCH_UPD
-#undef LAUNCH_UPD_C
-#undef LAUNCH_UPD_K
+  launch(h, -1, select_update(v.KP, kind != 0, couple_bucket(a), v.kk_mode == 0), dim3(nblk), dim3(update_threads(v.KP)), update_smem_bytes(v.KP), a);
 }
 
 template <int NVB>
@@ -613,6 +605,18 @@ WideChainArgs<NVB> narrow_wchain(const WideChainArgs<8>& c) {
     for (int w = 0; w < NVB; ++w) a.weight[v][w] = c.weight[v][w];
   }
   return a;
+}
+// the chain kernels are instantiated for 4 or 8 views (f_chain_kernel: 2, 4 or 8): f(width, the arguments narrowed to it)
+template <class F>
+void for_wchain(const WideChainArgs<8>& c, F&& f) {
+  if (c.n_views <= 4) f(std::integral_constant<int, 4>{}, narrow_wchain<4>(c));
+  else f(std::integral_constant<int, 8>{}, c);
+}
+template <class F>
+void for_chain(const ChainArgs<8>& c, int views, F&& f) {
+  if (views <= 2) f(std::integral_constant<int, 2>{}, narrow_chain<2>(c));
+  else if (views <= 4) f(std::integral_constant<int, 4>{}, narrow_chain<4>(c));
+  else f(std::integral_constant<int, 8>{}, c);
 }
 // update_f (g == 0) or update_g (g == 1) of every view in one launch (wide_chain_kernel): the replicated chains (all rows,
 // k > 16) or -- sliced -- this rank's row / column slice of them (any k)
@@ -645,73 +649,50 @@ void launch_wide_chain(resnmtf_handle* h, int g, bool checked, bool sliced = fal
     const int groups16 = ceil_div(c.len, 16);
     const unsigned nd_stride = (unsigned)groups16 * 16u * (unsigned)KP;
     const dim3 gridp(groups16, (c.n_views + 1) / 2), gridw(ceil_div(c.len, 4)), block16(16 * KP), blockw(4 * KP);
-#define SLSPLIT(KPV, NVBV, ARGS) do { \
-    LAUNCH_TIMED(h, kind, (slice_products_kernel<KPV, NVBV>), gridp, block16, 0, ARGS, h->slice_nd, nd_stride); \
-    LAUNCH_TIMED(h, kind, (slice_walk_kernel<KPV, NVBV, 4>), gridw, blockw, 0, ARGS, (const double*)h->slice_nd, nd_stride); } while (0)
-#define SLSPLIT_K(NVBV, ARGS) do { \
-    switch (KP) { case 16: SLSPLIT(16, NVBV, ARGS); break; case 32: SLSPLIT(32, NVBV, ARGS); break; \
-                  case 48: SLSPLIT(48, NVBV, ARGS); break; default: SLSPLIT(64, NVBV, ARGS); break; } } while (0)
-    if (c.n_views <= 4) { WideChainArgs<4> a4 = narrow_wchain<4>(c); SLSPLIT_K(4, a4); }
-    else { SLSPLIT_K(8, c); }
-#undef SLSPLIT_K
-#undef SLSPLIT
+    for_wchain(c, [&](auto nvb, const auto& a) {
+      constexpr int NVB = decltype(nvb)::value;
+      launch(h, kind, select_slice_products<NVB>(KP), gridp, block16, 0, a, h->slice_nd, nd_stride);
+      launch(h, kind, select_slice_walk<NVB>(KP), gridw, blockw, 0, a, h->slice_nd, nd_stride);
+    });
     return;
   }
   if (sliced && !slice_wide) {
-    const int groups16 = ceil_div(c.len, 16);
-    const dim3 grid16(groups16), block16(16 * KP);          // (one row group per workgroup)
-#define SLCHAIN(KPV, NVBV, ARGS) do { const size_t sm = slice_chain_smem_bytes(KPV, NVBV); \
-    if (g == 0) LAUNCH_TIMED(h, kind, (slice_chain_kernel<KPV, false, NVBV>), grid16, block16, sm, ARGS); \
-    else LAUNCH_TIMED(h, kind, (slice_chain_kernel<KPV, true, NVBV>), grid16, block16, sm, ARGS); } while (0)
-#define SLCHAIN_K(NVBV, ARGS) do { \
-    switch (KP) { case 16: SLCHAIN(16, NVBV, ARGS); break; case 32: SLCHAIN(32, NVBV, ARGS); break; \
-                  case 48: SLCHAIN(48, NVBV, ARGS); break; default: SLCHAIN(64, NVBV, ARGS); break; } } while (0)
-    if (c.n_views <= 4) { WideChainArgs<4> a4 = narrow_wchain<4>(c); SLCHAIN_K(4, a4); }
-    else { SLCHAIN_K(8, c); }
-#undef SLCHAIN_K
-#undef SLCHAIN
+    const dim3 grid16(ceil_div(c.len, 16)), block16(16 * KP);          // (one row group per workgroup)
+    for_wchain(c, [&](auto nvb, const auto& a) {
+      constexpr int NVB = decltype(nvb)::value;
+      launch(h, kind, select_slice_chain<NVB>(KP, g != 0), grid16, block16, slice_chain_smem_bytes(KP, NVB), a);
+    });
     return;
   }
   const dim3 grid(ngrid), block(16 * KP);
-#define WCHAIN(KPV, NVBV, ARGS) do { \
-    if (sliced) { if (g == 0) LAUNCH_TIMED(h, kind, (wide_chain_kernel<KPV, false, NVBV, true>), grid, block, smem, ARGS); \
-                  else LAUNCH_TIMED(h, kind, (wide_chain_kernel<KPV, true, NVBV, true>), grid, block, smem, ARGS); } \
-    else if (KPV >= 32) { if (g == 0) LAUNCH_TIMED(h, kind, (wide_chain_kernel<(KPV >= 32 ? KPV : 32), false, NVBV>), grid, block, smem, ARGS); \
-                          else LAUNCH_TIMED(h, kind, (wide_chain_kernel<(KPV >= 32 ? KPV : 32), true, NVBV>), grid, block, smem, ARGS); } } while (0)
-#define WCHAIN_K(NVBV, ARGS) do { \
-    switch (KP) { case 16: WCHAIN(16, NVBV, ARGS); break; case 32: WCHAIN(32, NVBV, ARGS); break; \
-                  case 48: WCHAIN(48, NVBV, ARGS); break; default: WCHAIN(64, NVBV, ARGS); break; } } while (0)
-  if (c.n_views <= 4) {
-    WideChainArgs<4> a = narrow_wchain<4>(c);
-    WCHAIN_K(4, a);
-  } else {
-    WCHAIN_K(8, c);
-  }
-#undef WCHAIN_K
-#undef WCHAIN
+  for_wchain(c, [&](auto nvb, const auto& a) {
+    launch(h, kind, select_wide_chain<decltype(nvb)::value>(KP, g != 0, sliced), grid, block, smem, a);
+  });
 }
 
+// the F updates of every view as ONE f_chain_kernel launch: is the chain there (enqueue_phase_f_all launches it), does
+// resnmtf_run's sweep hoist it ahead of the views (F_w' reads neither G nor S of the same sweep; every view owned), its
+// view-count instantiation, and does it read one X.G slab per view?
+struct FChainPlan { bool chain = false, hoisted = false, one_slab = true; int width = 0; };
+FChainPlan plan_f_chain(const resnmtf_handle* h) {
+  FChainPlan p;
+  p.chain = !h->wchain_ok[0] && h->chain_views > 0;
+  if (!p.chain) return p;
+  p.hoisted = h->all_owned;
+  p.width = h->chain_views <= 2 ? 2 : (h->chain_views <= 4 ? 4 : 8);
+  for (int v = 0; v < h->chain_views; ++v) p.one_slab = p.one_slab && h->chain.nsplit[v] == 1;
+  return p;
+}
 // RESNMTF_PHASE_F_ALL: update_f of every view in view order (one launch when the chain is eligible)
 void enqueue_phase_f_all(resnmtf_handle* h, bool checked = false) {
   if (h->wchain_ok[0]) { launch_wide_chain(h, 0, checked); return; }
-  if (h->chain_views > 0) {
+  const FChainPlan p = plan_f_chain(h);
+  if (p.chain) {
     h->chain.check_done = checked ? 1 : 0;
-    const size_t smem = h->chain_views <= 2 ? f_chain_smem_bytes<2>() : h->chain_views <= 4 ? f_chain_smem_bytes<4>() : f_chain_smem_bytes<8>();
-    bool one_slab = true;
-    for (int v = 0; v < h->chain_views; ++v) one_slab = one_slab && h->chain.nsplit[v] == 1;
-#define LAUNCH_CHAIN(NVB, ARGS)                                                                                         \
-    if (one_slab) LAUNCH_TIMED(h, RESNMTF_TIMED_F_CHAIN, (f_chain_kernel<NVB, 1>), dim3(h->chain_blocks), dim3(512), smem, ARGS);  \
-    else LAUNCH_TIMED(h, RESNMTF_TIMED_F_CHAIN, (f_chain_kernel<NVB, 4>), dim3(h->chain_blocks), dim3(512), smem, ARGS)
-    if (h->chain_views <= 2) {
-      ChainArgs<2> a = narrow_chain<2>(h->chain);
-      LAUNCH_CHAIN(2, a);
-    } else if (h->chain_views <= 4) {
-      ChainArgs<4> a = narrow_chain<4>(h->chain);
-      LAUNCH_CHAIN(4, a);
-    } else {
-      LAUNCH_CHAIN(8, h->chain);
-    }
-#undef LAUNCH_CHAIN
+    for_chain(h->chain, h->chain_views, [&](auto nvb, const auto& a) {
+      constexpr int NVB = decltype(nvb)::value;
+      launch(h, RESNMTF_TIMED_F_CHAIN, select_f_chain<NVB>(false, p.one_slab), dim3(h->chain_blocks), dim3(512), f_chain_smem_bytes<NVB>(), a);
+    });
     return;
   }
   for (const auto& v : h->views)
@@ -722,12 +703,11 @@ void enqueue_phase_f_all(resnmtf_handle* h, bool checked = false) {
 bool enqueue_g_chain(resnmtf_handle* h, bool checked) {
   if (h->gchain_views <= 0) return false;
   h->gchain.check_done = checked ? 1 : 0;
-  const int nvw = h->gchain_views;
-  const size_t smem = nvw <= 2 ? f_chain_smem_bytes<2>() : nvw <= 4 ? f_chain_smem_bytes<4>() : f_chain_smem_bytes<8>();
   const dim3 grid(h->gchain_blocks), block(512);
-  if (nvw <= 2) { ChainArgs<2> a = narrow_chain<2>(h->gchain); LAUNCH_TIMED(h, RESNMTF_TIMED_G_CHAIN, (f_chain_kernel<2, 1, true>), grid, block, smem, a); }
-  else if (nvw <= 4) { ChainArgs<4> a = narrow_chain<4>(h->gchain); LAUNCH_TIMED(h, RESNMTF_TIMED_G_CHAIN, (f_chain_kernel<4, 1, true>), grid, block, smem, a); }
-  else LAUNCH_TIMED(h, RESNMTF_TIMED_G_CHAIN, (f_chain_kernel<8, 1, true>), grid, block, smem, h->gchain);
+  for_chain(h->gchain, h->gchain_views, [&](auto nvb, const auto& a) {
+    constexpr int NVB = decltype(nvb)::value;
+    launch(h, RESNMTF_TIMED_G_CHAIN, select_f_chain<NVB>(true, true), grid, block, f_chain_smem_bytes<NVB>(), a);
+  });
   return true;
 }
 
@@ -738,12 +718,12 @@ void enqueue_phase_f(resnmtf_handle* h, const ViewState& v, bool checked) { laun
 void launch_fold(resnmtf_handle* h, const ViewState& v) {
   if (!v.Usum) return;
   const int quads = v.n_pad * v.KP / 4;
-  LAUNCH_TIMED(h, RESNMTF_TIMED_PACK, slab_fold_kernel, dim3(ceil_div(quads, 256)), dim3(256), 0, v.Pxg, v.nsplit_xg, quads, v.Usum);
+  launch(h, RESNMTF_TIMED_PACK, slab_fold_kernel, dim3(ceil_div(quads, 256)), dim3(256), 0, v.Pxg, v.nsplit_xg, quads, v.Usum);
 }
 void launch_fold_t(resnmtf_handle* h, const ViewState& v) {
   if (!v.Tsum) return;
   const int quads = v.m_pad * v.KP / 4;
-  LAUNCH_TIMED(h, RESNMTF_TIMED_PACK, slab_fold_kernel, dim3(ceil_div(quads, 256)), dim3(256), 0, v.Pxtf, v.nsplit_xtf, quads, v.Tsum);
+  launch(h, RESNMTF_TIMED_PACK, slab_fold_kernel, dim3(ceil_div(quads, 256)), dim3(256), 0, v.Pxtf, v.nsplit_xtf, quads, v.Tsum);
 }
 // slice_chains: the own view's pass result, folded and cut into the V chunks of the next all-to-all (slice_pack_kernel)
 void launch_slice_pack(resnmtf_handle* h, const ViewState& v, bool xg, bool checked) {
@@ -765,7 +745,7 @@ void launch_slice_pack(resnmtf_handle* h, const ViewState& v, bool xg, bool chec
   }
   a.ctl = h->ctl; a.check_done = checked ? 1 : 0;
   const size_t quads = (size_t)a.n_slices * a.rows_per_slice * (a.KP / 4);
-  LAUNCH_TIMED(h, RESNMTF_TIMED_PACK, slice_pack_kernel, dim3((unsigned)std::min<size_t>((quads + 255) / 256, 65535)), dim3(256), 0, a);
+  launch(h, RESNMTF_TIMED_PACK, slice_pack_kernel, dim3((unsigned)std::min<size_t>((quads + 255) / 256, 65535)), dim3(256), 0, a);
 }
 // slice_p2p: one arrival on every rank's counter of exchange e (stream-ordered behind the kernels that stored the data) /
 // the stream waits until `arrivals` of them are in
@@ -798,7 +778,7 @@ void launch_block_push(resnmtf_handle* h, int kind, size_t off0, size_t b0, size
   if (a.n_dst == 0) return;
   a.off[0] = off0; a.bytes[0] = b0; a.off[1] = off1; a.bytes[1] = b1;
   const size_t quads = (b0 + b1) / 16;
-  LAUNCH_TIMED(h, RESNMTF_TIMED_PACK, block_push_kernel, dim3((unsigned)std::max<size_t>(1, std::min<size_t>((quads + 255) / 256, 2048))), dim3(256), 0, a);
+  launch(h, RESNMTF_TIMED_PACK, block_push_kernel, dim3((unsigned)std::max<size_t>(1, std::min<size_t>((quads + 255) / 256, 2048))), dim3(256), 0, a);
 }
 // the F exchange block of an owned view to the peers: everything (replicate_f alone: the owner's coefficients and lambda are
 // the only copy) or, with the replicated S chain, the U rows and the embedded S block only -- every rank computes the
@@ -827,13 +807,7 @@ void launch_slice_unpack(resnmtf_handle* h, const ViewState& v, int g, bool chec
   a.in = g == 0 ? h->f_recv : h->g_recv; a.len = g == 0 ? v.n : v.m; a.k = v.k;
   a.W32 = g == 0 ? v.F32 : v.G32; a.ld32 = 64; a.Wk = g == 0 ? v.Fk : v.Gk;
   a.ctl = h->ctl; a.check_done = checked ? 1 : 0;
-  const dim3 grid(ceil_div(a.len, 32)), block(256);
-  switch (v.KP) {
-    case 16: LAUNCH_TIMED(h, RESNMTF_TIMED_PACK, slice_unpack_kernel<16>, grid, block, 0, a); break;
-    case 32: LAUNCH_TIMED(h, RESNMTF_TIMED_PACK, slice_unpack_kernel<32>, grid, block, 0, a); break;
-    case 48: LAUNCH_TIMED(h, RESNMTF_TIMED_PACK, slice_unpack_kernel<48>, grid, block, 0, a); break;
-    default: LAUNCH_TIMED(h, RESNMTF_TIMED_PACK, slice_unpack_kernel<64>, grid, block, 0, a); break;
-  }
+  launch(h, RESNMTF_TIMED_PACK, select_slice_unpack(v.KP), dim3(ceil_div(a.len, 32)), dim3(256), 0, a);
 }
 // replicate_gs: the second half of the k x k job of EVERY view (update_s chain, update_lm, error, F coefficients)
 int launch_s_chain(resnmtf_handle* h, bool checked) {
@@ -861,17 +835,7 @@ int launch_s_chain(resnmtf_handle* h, bool checked) {
   a.err = h->err; a.err_stride = V; a.err_cap = h->err_cap; a.err_host = h->err_host_dev;
   a.ctl = h->ctl; a.ctl_host = h->ctl_host_dev;
   const size_t smem = kk_smem_bytes(v0.KP, 16);
-#define S_CHAIN(KPV) do { \
-    if (V <= 4) LAUNCH_TIMED(h, RESNMTF_TIMED_S_CHAIN, (s_chain_kernel<KPV, 4>), dim3(V), dim3(s_chain_threads(KPV)), smem, a); \
-    else if (V <= 8) LAUNCH_TIMED(h, RESNMTF_TIMED_S_CHAIN, (s_chain_kernel<KPV, 8>), dim3(V), dim3(s_chain_threads(KPV)), smem, a); \
-    else LAUNCH_TIMED(h, RESNMTF_TIMED_S_CHAIN, (s_chain_kernel<KPV, RESNMTF_MAX_COUPLE + 1>), dim3(V), dim3(s_chain_threads(KPV)), smem, a); } while (0)
-  switch (v0.NT) {
-    case 1: S_CHAIN(16); break;
-    case 2: S_CHAIN(32); break;
-    case 3: S_CHAIN(48); break;
-    default: S_CHAIN(64); break;
-  }
-#undef S_CHAIN
+  launch(h, RESNMTF_TIMED_S_CHAIN, select_s_chain(v0.KP, V), dim3(V), dim3(s_chain_threads(v0.KP)), smem, a);
   return RESNMTF_OK;
 }
 // fuse_f: the view's F update has NOT been enqueued -- it rides in the Xt.F launch (enqueue_sweep decides)
@@ -896,7 +860,7 @@ void enqueue_sweep(resnmtf_handle* h, double tol) {
   const bool checked = tol >= 0.0;
   // F_w' reads neither G nor S of the same sweep: when the fused chain applies (several k <= 16 views sharing
   // their rows in the same order) every F update of the sweep runs first, in one launch
-  const bool hoist = h->chain_views > 0 && h->all_owned;
+  const bool hoist = plan_f_chain(h).hoisted;
   if (hoist) enqueue_phase_f_all(h, checked);
   for (const auto& v : h->views) {
     if (!v.owned) continue;
@@ -2279,7 +2243,7 @@ int resnmtf_init_svd(resnmtf_handle* h, int v, unsigned long long seed, double s
   sxt.B = vs.F32; sxt.ldb = 64; sxt.P = sc.Pm; sxt.ctl = h->ctl;
   auto product = [&](bool is_xg) {
     if (!vs.sparse) launch_pass_plain(h, is_xg ? xg : xt, NTi, is_xg);
-    else launch_spmm(h, is_xg ? sxg : sxt, L, is_xg, KKFArgs{}, KKSArgs{}, false);
+    else launch_spmm(h, is_xg ? sxg : sxt, L, is_xg, KKFArgs{}, KKSArgs{});
   };
   for (int it = 0; it < n_power; ++it) {
     product(true);                                                                         // Y = X Z
@@ -3981,8 +3945,7 @@ int resnmtf_view_image_info(resnmtf_handle* h, int v, int* uses_2byte, double* r
   return RESNMTF_OK;
 }
 
-// the decisions launch_pass / launch_pass_sparse / enqueue_sweep take from ViewState and the options, restated for the
-// caller (tests assert which launch form they cover); keep in step with those functions
+// the launch plan of view v: what resolve_pass / plan_f_chain decide (tests assert which launch forms they cover)
 int resnmtf_view_plan(resnmtf_handle* h, int v, resnmtf_view_plan_info* out) {
   if (!h) return RESNMTF_ERR_INVALID;
   if (!out) return h->fail(RESNMTF_ERR_INVALID, "out is NULL");
@@ -3993,47 +3956,28 @@ int resnmtf_view_plan(resnmtf_handle* h, int v, resnmtf_view_plan_info* out) {
   std::memset(&p, 0, sizeof(p));
   p.struct_size = (int)sizeof(p);
   p.k = vs.k; p.kp = vs.KP; p.nt = vs.NT;
-  p.image = vs.sparse ? 1 : (vs.half ? (vs.u16 ? 3 : 2) : 0);
   p.kk_mode = vs.kk_mode;
-  if (vs.half) {
-    const int un_def = vs.u16 ? 2 : 4, hu = h->opt.half_unroll;
-    p.half_unroll = (hu == 2 || hu == 3 || hu == 4 || hu == 6) ? hu : un_def;
-  }
-  const bool wide = !vs.sparse && vs.NT >= 2 && h->opt.bf16_split != 2;
   for (int i = 0; i < 2; ++i) {
     const bool xg = i == 0;
-    const int ns = xg ? vs.nsplit_xg : vs.nsplit_xtf, rps = xg ? vs.rps_xg : vs.rps_xtf;
-    const int rows_pad = xg ? vs.m_pad : vs.n_pad;
-    p.wide[i] = wide ? 1 : 0;
-    p.xcd_order[i] = wide && h->opt.xcd_order ? 1 : 0;
-    p.waves[i] = vs.sparse ? 8 : (xg ? vs.nw_xg : vs.nw_xtf);
-    p.pingpong[i] = !vs.sparse && !vs.half && (xg ? vs.pp_xg : vs.pp_xtf) ? 1 : 0;   // (pass_half_kernel has no such form)
-    if (!vs.sparse && !vs.half)
-      p.unroll[i] = vs.NT >= 2 ? 4 : (p.waves[i] == 8 ? (p.pingpong[i] ? 4 : RESNMTF_K16_UNROLL) : 8);
-    p.nsplit[i] = ns;
-    p.rows[i] = xg ? vs.m : vs.n;
-    p.rows_pad[i] = rows_pad;
-    p.ntiles[i] = (xg ? vs.n_pad : vs.m_pad) / 64;
-    if (!vs.sparse) {
-      p.rows_per_split[i] = rps;
-      p.short_last[i] = ns > 1 && rows_pad - (ns - 1) * rps < rps ? 1 : 0;
-    }
-    p.tiles_per_wg[i] = wide ? (xg ? vs.tw_xg : vs.tw_xtf) : 1;
-    p.aux_splits[i] = vs.kk_mode != 0 ? (xg ? vs.nsaux_xg : vs.nsaux_xtf) : 0;
-    p.sparse_blocks[i] = vs.sparse ? (xg ? vs.nblk_xg : vs.nblk_xtf) : 0;
+    const PassLaunch L = resolve_pass(h, vs, xg);
+    p.image = L.image;
+    if (L.image >= 2) p.half_unroll = L.unroll;
+    p.wide[i] = L.wide; p.xcd_order[i] = L.xcd_order; p.waves[i] = L.waves; p.pingpong[i] = L.pingpong;
+    p.unroll[i] = L.image == 0 ? L.unroll : 0;
+    p.nsplit[i] = xg ? vs.nsplit_xg : vs.nsplit_xtf;
+    p.rows[i] = xg ? vs.m : vs.n; p.rows_pad[i] = xg ? vs.m_pad : vs.n_pad; p.ntiles[i] = (xg ? vs.n_pad : vs.m_pad) / 64;
+    if (L.image != 1) { p.rows_per_split[i] = xg ? vs.rps_xg : vs.rps_xtf; p.short_last[i] = L.short_last; }
+    p.tiles_per_wg[i] = L.tiles_per_wg;
+    p.aux_splits[i] = L.mode_a ? 0 : (xg ? vs.nsaux_xg : vs.nsaux_xtf);
+    p.sparse_blocks[i] = L.image == 1 ? (xg ? vs.nblk_xg : vs.nblk_xtf) : 0;
   }
   if (!vs.sparse) {
     p.pitch_pad = vs.ldx != (size_t)vs.n_pad * 64 ? 1 : 0;
     p.lds_pad_kb = h->opt.pass_lds_pad_kb;
   }
   p.prepared = h->prepared ? 1 : 0;
-  if (h->prepared && h->chain_views > 0 && h->all_owned && !h->wchain_ok[0]) {      // (enqueue_sweep / enqueue_phase_f_all)
-    p.f_chain_hoisted = 1;
-    p.f_chain_views = h->chain_views <= 2 ? 2 : (h->chain_views <= 4 ? 4 : 8);
-    bool one_slab = true;
-    for (int w = 0; w < h->chain_views; ++w) one_slab = one_slab && h->chain.nsplit[w] == 1;
-    p.f_chain_one_slab = one_slab ? 1 : 0;
-  }
+  const FChainPlan fc = h->prepared ? plan_f_chain(h) : FChainPlan{};
+  if (fc.hoisted) { p.f_chain_hoisted = 1; p.f_chain_views = fc.width; p.f_chain_one_slab = fc.one_slab; }
   *out = p;
   return RESNMTF_OK;
 }
@@ -4047,14 +3991,15 @@ int resnmtf_pass_timings(resnmtf_handle* h, resnmtf_pass_timing* out, int reset)
   for (const auto& v : h->views) {
     if (!v.owned) continue;
     const double n = v.n, m = v.m, k = v.k;
-    const double sx = v.half ? 2.0 : 4.0;          // bytes per element of X as stored
+    const PassLaunch L = resolve_pass(h, v, true);
+    const double sx = L.image >= 2 ? 2.0 : 4.0;    // bytes per element of X as stored
     // (a launch that carries the update of its B operand -- pass_fused_kernel -- also moves that update's algorithmic bytes:
     //  product rows 4 len k once, the fp64 factor 8 len k in and out, its f32 copy 4 len k out)
     out->xg_bytes = sx * n * m + 4.0 * (n + m) * k + (can_fuse_update(h, v, 1) ? 24.0 * m * k : 0.0);
     out->xtf_bytes = sx * n * m + 4.0 * (n + m) * k + (can_fuse_update(h, v, 0) && h->all_owned && h->chain_views == 0 ? 24.0 * n * k : 0.0);
     out->xg_flops = 2.0 * n * m * k;
     out->xtf_flops = 2.0 * n * m * k;
-    if (v.sparse) {      // values + indices + pointers + gathered factor rows (f32, KP wide) + slabs written
+    if (L.image == 1) {      // values + indices + pointers + gathered factor rows (f32, KP wide) + slabs written
       const double z = (double)v.nnz, kp = v.KP;
       out->xg_bytes = 8.0 * z + 8.0 * (n + 1) + 4.0 * kp * z + 4.0 * kp * n * v.nsplit_xg;
       out->xtf_bytes = 8.0 * z + 8.0 * (m + 1) + 4.0 * kp * z + 4.0 * kp * m * v.nsplit_xtf;

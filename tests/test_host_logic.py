@@ -107,3 +107,22 @@ def test_product_does_not_import_oracle():
             if fn.endswith((".py", ".hip", ".inc", ".h")):
                 text = open(os.path.join(dirpath, fn)).read()
                 assert "oracle" not in text.replace("no CPU oracle", ""), f"{fn} mentions the oracle"
+
+
+def test_no_macro_launches_a_kernel_or_sets_an_attribute():
+    """The host decides a launch once: which instantiation goes out is answered by functions (the select_* family, launch(),
+    set_all_attrs() in resnmtf_hip.hip), which the launchers, the dynamic-LDS limits and resnmtf_view_plan share.  A `#define`
+    whose body launches a kernel or raises a function attribute is a second, untied list of instantiations."""
+    csrc = os.path.join(ROOT, "resnmtf_amd", "csrc")
+    banned = ("hipLaunchKernelGGL", "hipExtLaunchKernelGGL", "hipFuncSetAttribute")
+    # every file under csrc/, so that a launch layer carved into an include file stays covered.  One exception, by name: the
+    # bisilhouette kernel file keeps a local five-case switch over its own kernel (no LDS attribute, no plan, one list)
+    known = {("resnmtf_bisil.hip.inc", "BISIL_CASE")}
+    seen = 0
+    for fn in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, fn)).read().replace("\\\n", " ")      # (a macro body runs on over continued lines)
+        for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+)(.*)$", text, re.M):
+            seen += 1
+            for word in banned:
+                assert word not in m.group(2) or (fn, m.group(1)) in known, f"{fn}: #define {m.group(1)} calls {word}"
+    assert seen > 10, "no #define found: the scan is broken"
