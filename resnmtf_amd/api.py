@@ -25,23 +25,22 @@ Without the opt-ins ``bisil`` stays ``None`` and ``k_val=None`` raises ``NotImpl
 from __future__ import annotations
 
 import warnings
-from typing import Callable, Dict, List, Optional, Sequence
+from typing import Callable, Optional
 
 import numpy as np
 
-from . import bisil, naming, sparse
+from . import batched, bisil, naming, sparse
 from . import spurious as _spurious
 from .engine import Engine
+from .problem import couple, inner_result, prepare, svd_init  # noqa: F401  (svd_init: part of this module's surface)
 from .spurious import check_biclusters, remove_spurious  # noqa: F401  (post-steps, R/obtain_bicl.r:113-188)
 
 _DISTANCES = ("euclidean", "manhattan", "cosine")
 
 
 def _as_list(x):
-    if isinstance(x, np.ndarray) and x.ndim == 2:
+    if (isinstance(x, np.ndarray) and x.ndim == 2) or sparse.is_sparse(x):
         return [x]                      # check_lists, R/utils.r:313-316
-    if sparse.is_sparse(x):
-        return [x]
     return list(x)
 
 
@@ -51,49 +50,22 @@ def _views(data) -> list:
     return [sparse.canonical_csc(d) if sparse.is_sparse(d) else np.asarray(d, dtype=np.float64) for d in _as_list(data)]
 
 
-def svd_init(data: Sequence[np.ndarray], k_vec: Sequence[int], seed: Optional[int] = None, sigma: float = 0.05):
-    """``init_mats_inner`` (``R/update_steps.r:78-125``) on the host, as in the reference
-    (the initialisation is outside the accelerated loop).  The noise on S comes from NumPy's
-    generator instead of ``MASS::mvrnorm`` + R's RNG: statistically, not bitwise, equivalent."""
-    rng = np.random.default_rng(seed)
-    init_f, init_s, init_g, init_lam, init_mu = [], [], [], [], []
-    for x, k in zip(data, k_vec):
-        u, d, vt = np.linalg.svd(x, full_matrices=False)
-        f = np.abs(u[:, :k]); g = np.abs(vt.T[:, :k])
-        s = np.abs(np.diag(d)[:k, :k]) + np.abs(rng.normal(0.0, np.sqrt(sigma), size=(k, k)))
-        cf, cg = f.sum(axis=0), g.sum(axis=0)
-        s = s * (cf * cg)[None, :]
-        f = f / cf[None, :]; g = g / cg[None, :]
-        init_f.append(f); init_s.append(s); init_g.append(g)
-        init_lam.append(f.sum(axis=0)); init_mu.append(g.sum(axis=0))
-    return init_f, init_s, init_g, init_lam, init_mu
-
-
 def _load_engine(eng: Engine, data, init_f, init_s, init_g, lam, mu, phi, xi, psi,
                  row_names, col_names, row_indices, column_indices, seed=None):
     """``init_f is None``: the initial factors come from the device (``resnmtf_init_svd``)."""
-    n_v = eng.n_views
-    for v in range(n_v):
+    for v in range(eng.n_views):
         if eng.owned[v]:
             if sparse.is_sparse(data[v]):
                 eng.set_view_sparse(v, data[v], pre_processed=True)                                    # (already pre-processed)
             else:
                 eng.set_view(v, data[v])
         if init_f is None:
-            eng.init_svd(v, seed=(0 if seed is None else int(seed)) + v)                          # update_steps.r:78-125
+            eng.init_svd(v, seed=_seed(seed) + v)                          # update_steps.r:78-125
         else:
             eng.set_factors(v, init_f[v], init_s[v], init_g[v],
                             None if lam is None else lam[v], None if mu is None else mu[v])
     eng.set_restrictions(phi, xi, psi)
-    for v in range(n_v):
-        for w in range(n_v):
-            if w == v:
-                continue
-            if n_v > 1:
-                iv, iw = naming.index_pairs(row_names[v], row_names[w], row_indices[v].get(w))
-                eng.set_shared_rows(v, w, iv, iw)
-                iv, iw = naming.index_pairs(col_names[v], col_names[w], column_indices[v].get(w))
-                eng.set_shared_cols(v, w, iv, iw)
+    couple(eng, row_names, col_names, row_indices, column_indices)
 
 
 def res_nmtf_inner(data, row_indices, column_indices,
@@ -132,13 +104,11 @@ def res_nmtf_inner(data, row_indices, column_indices,
     k_vec = [int(k) for k in np.atleast_1d(k_vec)]
     if len(k_vec) != n_v:
         raise ValueError("k_vec must be a vector of the same length as the number of views.")   # utils.r:440
-    if not no_clusts and spurious and not spurious_on_device:
-        raise NotImplementedError(
-            "spurious-bicluster removal (R/obtain_bicl.r:31-133) is outside the accelerated path; "
-            "pass spurious=False or do it on the R side (INTEGRATION.md).")
     remove = bool(spurious) and not no_clusts
-    if distance not in _DISTANCES:
-        raise ValueError("distance must be one of 'euclidean', 'manhattan' or 'cosine'.")         # utils.r:425
+    _refuse_host_spurious(remove, spurious_on_device,
+                          "spurious-bicluster removal (R/obtain_bicl.r:31-133) is outside the accelerated path; "
+                          "pass spurious=False or do it on the R side (INTEGRATION.md).")
+    _check_distance(distance)
     is_sp = [sparse.is_sparse(d) for d in data]
     if remove:
         _spurious.check_num_repeats(num_repeats)
@@ -153,17 +123,8 @@ def res_nmtf_inner(data, row_indices, column_indices,
     if any(is_sp) and host_init and (init_f is None or init_g is None or init_s is None):
         raise NotImplementedError("host_init=True (NumPy's dense SVD) is not available for sparse views; the device "
                                   "initialisation (host_init=False) works on them")
-    phi = np.zeros((n_v, n_v)) if phi is None else np.asarray(phi, dtype=np.float64)
-    xi = np.zeros((n_v, n_v)) if xi is None else np.asarray(xi, dtype=np.float64)
-    psi = np.zeros((n_v, n_v)) if psi is None else np.asarray(psi, dtype=np.float64)
-    if row_names is None or col_names is None:
-        rn, cn = naming.give_names(data, None, None)
-        row_names = row_names or rn
-        col_names = col_names or cn
-    if row_indices is None:
-        row_indices = naming.shared_names(row_names)
-    if column_indices is None:
-        column_indices = naming.shared_names(col_names)
+    phi, xi, psi = (np.zeros((n_v, n_v)) if m is None else np.asarray(m, dtype=np.float64) for m in (phi, xi, psi))
+    row_names, col_names = naming.give_names(data, None, None, row_names, col_names)
 
     lam = mu = None
     if init_f is None or init_g is None or init_s is None:                                        # update_steps.r:41
@@ -174,49 +135,29 @@ def res_nmtf_inner(data, row_indices, column_indices,
         init_f, init_s, init_g = _as_list(init_f), _as_list(init_s), _as_list(init_g)
 
     eng = Engine([d.shape[0] for d in data], [d.shape[1] for d in data], k_vec, device_id=device_id,
-                 **(engine_opts or {}), **({"nnz": [d.nnz if sp else None for d, sp in zip(data, is_sp)]} if any(is_sp) else {}))
+                 nnz=[d.nnz if sp else None for d, sp in zip(data, is_sp)], **(engine_opts or {}))
     try:
         _load_engine(eng, data, init_f, init_s, init_g, lam, mu, phi, xi, psi,
                      row_names, col_names, row_indices, column_indices, seed=seed)
         init_state = [eng.get_factors(v) for v in range(n_v)] if return_init else None      # (F, S, G, lambda, mu) the loop starts from
         total_err = eng.run(n_iters=n_iters, tol=1.0e-6, max_iters=max_iters)
-        out_f, out_s, out_g, row_cl, col_cl, lams, mus = [], [], [], [], [], [], []
-        for v in range(n_v):
-            f, s, g, rc, cc = eng.finalise(v)                                                     # main.r:110 + obtain_bicl.r:162-180
-            out_f.append(f); out_s.append(s); out_g.append(g); row_cl.append(rc); col_cl.append(cc)
-            _, _, _, lv, mv = eng.get_factors(v)
-            lams.append(lv); mus.append(mv)
-        check = None
-        if remove:                                                                                # obtain_bicl.r:151-188
-            check = _spurious.check_on_device(eng, num_repeats, seed, max_iters=max_iters, device_id=device_id)
-        score_fn = None
-        if score_bisil and not no_clusts:                                                         # obtain_bicl.r:189-199
-            score_fn = lambda rc, cc: bisil.score(rc, cc, distance, engine=eng)             # noqa: E731
+        # per view: F, S, G, the binary clusters (main.r:110 + obtain_bicl.r:162-180), lambda, mu
+        out_f, out_s, out_g, row_cl, col_cl, lams, mus = (
+            list(x) for x in zip(*[(*eng.finalise(v), *eng.get_factors(v)[3:]) for v in range(n_v)]))
+        check = (_spurious.check_on_device(eng, num_repeats, seed, max_iters=max_iters, device_id=device_id)
+                 if remove else None)                                                             # obtain_bicl.r:151-188
+        score_fn = ((lambda rc, cc: bisil.score(rc, cc, distance, engine=eng))
+                    if score_bisil and not no_clusts else None)                                   # obtain_bicl.r:189-199
         cleaned = _remove_then_score({"output_s": out_s, "row_clusters": row_cl, "col_clusters": col_cl}, check, score_fn)
     finally:
         eng.close()
-    row_cl, col_cl, score = cleaned["row_clusters"], cleaned["col_clusters"], cleaned.get("bisil")
+    # ("init": a test hook, the initial state the device built, for a reference run from the same start)
     if no_clusts:                                                                                 # main.r:115-120
-        res = {"output_f": out_f, "output_s": out_s, "output_g": out_g}
-        if return_init:
-            res["init"] = init_state
-        return res
-    if n_iters is None:
-        error = float(np.mean(total_err[-10:]))                                                   # main.r:127
-    else:
-        error = float(total_err[-1])                                                              # main.r:129
-    res = {
-        "output_f": out_f, "output_s": out_s, "output_g": out_g,
-        "Error": error, "All_Error": total_err,
-        "bisil": score,           # None unless score_bisil (bisil.py; parity with bisilhouette::bisilhouette unpinned)
-        "row_clusters": row_cl, "col_clusters": col_cl,
-        "lambda": lams, "mu": mus,
-    }
-    if "spurious" in cleaned:
-        res["spurious"] = cleaned["spurious"]
-    if return_init:               # (test hook: the initial state the device built, for a reference run from the same start)
-        res["init"] = init_state
-    return res
+        return inner_result(out_f, out_s, out_g, init=init_state)
+    # ("bisil": None unless score_bisil; bisil.py, parity with bisilhouette::bisilhouette unpinned)
+    return inner_result(out_f, out_s, out_g, total_err, n_iters, bisil=cleaned.get("bisil"),
+                        row_clusters=cleaned["row_clusters"], col_clusters=cleaned["col_clusters"], lam=lams, mu=mus,
+                        spurious=cleaned.get("spurious"), init=init_state)
 
 
 def _remove_then_score(res: dict, check: Optional[dict], score_fn: Optional[Callable]) -> dict:
@@ -232,6 +173,30 @@ def _number_biclusters(results) -> float:
     """``number_biclusters`` (``R/stability_analysis.r:92-97``): the sum of every row-cluster matrix; 0 for results
     without cluster matrices (``no_clusts``)."""
     return float(sum(np.asarray(rc).sum() for rc in (results.get("row_clusters") or [])))
+
+
+def _refuse_host_spurious(wanted, spurious_on_device: bool, message: str):
+    """``spurious=True`` runs only with the opt-in ``spurious_on_device``; ``message``: the caller's own refusal."""
+    if wanted and not spurious_on_device:
+        raise NotImplementedError(message)
+
+
+def _check_distance(distance):
+    if distance not in _DISTANCES:
+        raise ValueError("distance must be one of 'euclidean', 'manhattan' or 'cosine'.")         # utils.r:425
+
+
+def _check_common(n_iters, num_repeats, n_stability, distance, sample_rate, stab_thres):
+    """What ``apply_resnmtf`` checks for a known k and for the k sweep alike (``R/utils.r:220-253``, ``:425``, ``:286-300``)."""
+    for name, val in (("n_iters", n_iters), ("num_repeats", num_repeats), ("n_stability", n_stability)):
+        if val is not None and (int(val) != val or val < 1):
+            raise ValueError(f"{name} must be a positive integer.")
+    _check_distance(distance)
+    _check_stability_numbers(sample_rate, stab_thres)
+
+
+def _seed(seed) -> int:
+    return 0 if seed is None else int(seed)
 
 
 def _check_stability_numbers(sample_rate, stab_thres):
@@ -275,9 +240,9 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
     if _number_biclusters(results) == 0:                                                          # :308-311
         warnings.warn("No biclusters detected!")
         return results
-    if spurious and not spurious_on_device:
-        raise NotImplementedError("stability selection with spurious-bicluster removal inside its repeats "
-                                  "(R/stability_analysis.r:254-266) is outside the accelerated path; pass spurious=False")
+    _refuse_host_spurious(spurious, spurious_on_device,
+                          "stability selection with spurious-bicluster removal inside its repeats "
+                          "(R/stability_analysis.r:254-266) is outside the accelerated path; pass spurious=False")
     spurious_repeats = _spurious.check_num_repeats(num_repeats) if spurious else 0
     _check_stability_numbers(sample_rate, stab_thres)
     if int(n_stability) != n_stability or n_stability < 1:
@@ -285,14 +250,10 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
     data = _views(data)
     n_v = len(data)
     k = int(np.atleast_1d(k)[0])
-    seed = 0 if seed is None else int(seed)
-    from . import batched
+    seed = _seed(seed)
     dev = None
     if repeat_runner is None:
-        if row_names is None or col_names is None:
-            rn, cn = naming.give_names(data, None, None, row_names, col_names)
-            row_names = row_names or rn
-            col_names = col_names or cn
+        row_names, col_names = naming.give_names(data, None, None, row_names, col_names)
         dev = batched.DeviceData(data, phi, xi, psi, row_names, col_names, device_id=device_id, pre_processed=True)
     try:
         stab = batched.stability_relevance_on_device(dev, results, k, int(n_stability), float(sample_rate), n_iters,
@@ -361,34 +322,26 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     if k_val is None:
         raise NotImplementedError("the k sweep (R/main.r:279-321) needs the bisilhouette score, which is "
                                   "outside the accelerated path; pass k_val")
-    if stability and spurious and not no_clusts and not spurious_on_device:
-        raise NotImplementedError("stability selection with spurious-bicluster removal (R/obtain_bicl.r:31-133) is "
-                                  "outside the accelerated path; pass spurious=False (or stability=False and do the "
-                                  "removal on the R side, INTEGRATION.md)")
-    for name, val in (("n_iters", n_iters), ("num_repeats", num_repeats), ("n_stability", n_stability)):
-        if val is not None and (int(val) != val or val < 1):
-            raise ValueError(f"{name} must be a positive integer.")                               # utils.r:220-253
-    _check_stability_numbers(sample_rate, stab_thres)                                             # utils.r:286-300
+    _refuse_host_spurious(stability and spurious and not no_clusts, spurious_on_device,
+                          "stability selection with spurious-bicluster removal (R/obtain_bicl.r:31-133) is "
+                          "outside the accelerated path; pass spurious=False (or stability=False and do the "
+                          "removal on the R side, INTEGRATION.md)")
+    _check_common(n_iters, num_repeats, n_stability, distance, sample_rate, stab_thres)
     k_vec = [int(np.atleast_1d(k_val)[0])] * n_v                                                  # main.r:226
     ranks = [d.shape[1] for d in data]
     if any(k < 1 for k in k_vec):
         raise ValueError("k_vec must be a vector of integers greater than 1.")                    # utils.r:437
     if any(k > r for k, r in zip(k_vec, ranks)):
         raise ValueError("k_vec must be a vector of integers less than or equal to the ranks of the views.")
-    rn, cn = naming.give_names(data, phi, psi, row_names, col_names)                              # main.r:228
-    row_idx, col_idx = naming.shared_names(rn), naming.shared_names(cn)                           # main.r:230
-    phi_m = naming.init_rest_mats(phi, n_v)                                                       # main.r:233-235
-    psi_m = naming.init_rest_mats(psi, n_v)
-    xi_m = naming.init_rest_mats(xi, n_v)
-    data = naming.check_data(data)                                                                # main.r:237
-    results = res_nmtf_inner(data, row_idx, col_idx, init_f, init_s, init_g, k_vec, phi_m, xi_m, psi_m,
+    p = prepare(data, phi, xi, psi, row_names, col_names, normalise=True, symmetrise=True)        # main.r:228-237
+    results = res_nmtf_inner(p.data, p.row_shared, p.col_shared, init_f, init_s, init_g, k_vec, p.phi, p.xi, p.psi,
                              n_iters, num_repeats, spurious, distance, no_clusts,
-                             row_names=rn, col_names=cn, device_id=device_id, max_iters=max_iters, seed=seed,
-                             spurious_on_device=spurious_on_device)
+                             row_names=p.row_names, col_names=p.col_names, device_id=device_id, max_iters=max_iters,
+                             seed=seed, spurious_on_device=spurious_on_device)
     if stability:                                                                                 # main.r:255-262
-        results = stability_check(data, results, k_vec, phi_m, xi_m, psi_m, n_iters, spurious, num_repeats,
+        results = stability_check(p.data, results, k_vec, p.phi, p.xi, p.psi, n_iters, spurious, num_repeats,
                                   no_clusts, distance, sample_rate, n_stability, stab_thres,
-                                  row_names=rn, col_names=cn, device_id=device_id, seed=seed,
+                                  row_names=p.row_names, col_names=p.col_names, device_id=device_id, seed=seed,
                                   max_iters=max_iters, spurious_on_device=spurious_on_device)
     return results
 
@@ -428,20 +381,15 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
                    device_id, max_iters, seed, return_sweep, sweep_runner, spurious_on_device=False):
     """``apply_resnmtf`` with ``k_val = NULL`` (``R/main.r:269-334``); see ``apply_resnmtf``."""
     n_v = len(data)
-    for name, val in (("n_iters", n_iters), ("num_repeats", num_repeats), ("n_stability", n_stability)):
-        if val is not None and (int(val) != val or val < 1):
-            raise ValueError(f"{name} must be a positive integer.")                               # utils.r:220-253
+    _check_common(n_iters, num_repeats, n_stability, distance, sample_rate, stab_thres)
     _check_whole_number(k_min, "k_min")
     _check_whole_number(k_max, "k_max")
     if k_max <= k_min:
         raise ValueError("k_max must be greater than k_min.")                                     # utils.r:250-252
     k_min, k_max = int(k_min), int(k_max)
-    if distance not in _DISTANCES:
-        raise ValueError("distance must be one of 'euclidean', 'manhattan' or 'cosine'.")         # utils.r:425
-    _check_stability_numbers(sample_rate, stab_thres)                                             # utils.r:286-300
-    if spurious and not no_clusts and not spurious_on_device:
-        raise NotImplementedError("spurious-bicluster removal (R/obtain_bicl.r:31-133) is outside the accelerated "
-                                  "path; pass spurious=False")
+    _refuse_host_spurious(spurious and not no_clusts, spurious_on_device,
+                          "spurious-bicluster removal (R/obtain_bicl.r:31-133) is outside the accelerated "
+                          "path; pass spurious=False")
     spurious_repeats = _spurious.check_num_repeats(num_repeats) if spurious and not no_clusts else 0
     if no_clusts:
         raise ValueError("the k sweep ranks the biclusters by their bisilhouette score: no_clusts=True has none")
@@ -454,29 +402,22 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
     cap = min(min(d.shape[1] for d in data), 64)
     if k_max > cap:
         raise ValueError("k_vec must be a vector of integers less than or equal to the ranks of the views.")
-    seed = 0 if seed is None else int(seed)
-    rn, cn = naming.give_names(data, phi, psi, row_names, col_names)                              # main.r:228
-    phi_m = naming.init_rest_mats(phi, n_v)                                                       # main.r:233-235
-    psi_m = naming.init_rest_mats(psi, n_v)
-    xi_m = naming.init_rest_mats(xi, n_v)
-    data = naming.check_data(data)                                                                # main.r:237
+    seed = _seed(seed)
+    p = prepare(data, phi, xi, psi, row_names, col_names, normalise=True, symmetrise=True)        # main.r:228-237
     dev = None
     try:
         if sweep_runner is None:
-            from . import batched
-            dev = batched.DeviceData(data, phi_m, xi_m, psi_m, rn, cn, device_id=device_id, pre_processed=True)
+            dev = batched.DeviceData(p.data, p.phi, p.xi, p.psi, p.row_names, p.col_names, device_id=device_id,
+                                     pre_processed=True)
 
             def scored(r):                                  # a res_nmtf_inner result with its bisil (main.r:131-139)
-                out = {key: r[key] for key in ("output_f", "output_s", "output_g", "Error", "All_Error")}
                 cleaned = _remove_then_score({key: r[key] for key in ("output_s", "row_clusters", "col_clusters")},
                                              r.get("spurious_check"),
                                              lambda rc, cc: bisil.score(rc, cc, distance, engine=dev.base))
-                out["bisil"] = cleaned["bisil"]
-                out.update({key: cleaned[key] for key in ("row_clusters", "col_clusters")})
-                out.update({key: r[key] for key in ("lambda", "mu")})
-                if "spurious" in cleaned:
-                    out["spurious"] = cleaned["spurious"]
-                return out
+                return inner_result(r["output_f"], r["output_s"], r["output_g"], r["All_Error"], n_iters,
+                                    bisil=cleaned["bisil"], row_clusters=cleaned["row_clusters"],
+                                    col_clusters=cleaned["col_clusters"], lam=r["lambda"], mu=r["mu"],
+                                    spurious=cleaned.get("spurious"))
 
             # every k, the extra ones included, with the correct shared-column maps (R's extension loop passes NULL
             # ones, R/main.r:305-309)
@@ -495,10 +436,10 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
             dev.close()
     results = results[pick]                                                                       # main.r:313-314
     if stability:                                                                                 # main.r:324-332
-        results = stability_check(data, results, [ks[pick]] * n_v, phi_m, xi_m, psi_m, n_iters, spurious, num_repeats,
+        results = stability_check(p.data, results, [ks[pick]] * n_v, p.phi, p.xi, p.psi, n_iters, spurious, num_repeats,
                                   no_clusts, distance, sample_rate, n_stability, stab_thres, remove_unstable,
-                                  row_names=rn, col_names=cn, device_id=device_id, seed=seed, max_iters=max_iters,
-                                  spurious_on_device=spurious_on_device)
+                                  row_names=p.row_names, col_names=p.col_names, device_id=device_id, seed=seed,
+                                  max_iters=max_iters, spurious_on_device=spurious_on_device)
     if return_sweep:
         results = dict(results)
         results["k_sweep"] = {"k": ks, "bisil": scores}

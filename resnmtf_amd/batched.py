@@ -15,10 +15,18 @@ NOT here: the other scores computed from the factorisations -- the bisilhouette 
 """
 from __future__ import annotations
 
+import contextlib
+from collections import namedtuple
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
+
+from . import naming, sparse, spurious
+from ._lib import GROUP_MAX_K, GROUP_MAX_VIEW_ENTRIES, GROUP_MAX_VIEWS
+from .engine import Engine, group_run
+from .problem import (inner_result, load_child, pair_table, prepare, reported_error,  # noqa: F401  (shuffled_engines:
+                      shuffled_engines, svd_init)                                     # part of this module's surface)
 
 
 @dataclass
@@ -118,13 +126,9 @@ def stability_jobs(data, k: int, n_stability: int = 5, sample_rate: float = 0.9,
     repeat on a sub-sample drawn by ``subsample_views``; the draws are kept in ``extras`` for the
     relevance computation (on the device: ``stability_relevance_on_device``).  Repeats whose sampling fails are skipped, as the reference
     does (``stability_performed = FALSE``)."""
-    from . import naming
     rng = np.random.default_rng(seed)
     data = [np.asarray(d, dtype=np.float64) for d in data]
-    if row_names is None or col_names is None:
-        rn, cn = naming.give_names(data, phi, psi, row_names, col_names)
-        row_names = row_names or rn
-        col_names = col_names or cn
+    row_names, col_names = naming.give_names(data, phi, psi, row_names, col_names)
     jobs = []
     for r in range(n_stability):
         s = subsample_views(data, sample_rate, rng, row_names, col_names)
@@ -143,17 +147,12 @@ def run_job(job: Job, device_id: int = 0, pre_processed: bool = False, return_in
     """One factorisation through the accelerated path: naming, symmetrisation and (unless
     ``pre_processed``) non-negativity shift + normalisation as ``apply_resnmtf`` does, device-side SVD
     initialisation, the loop, finalise."""
-    from . import api, naming
-    data = [np.asarray(d, dtype=np.float64) for d in job.data]
-    n_v = len(data)
-    rn, cn = naming.give_names(data, job.phi, job.psi, job.row_names, job.col_names)
-    row_idx, col_idx = naming.shared_names(rn), naming.shared_names(cn)
-    phi = naming.init_rest_mats(job.phi, n_v); psi = naming.init_rest_mats(job.psi, n_v); xi = naming.init_rest_mats(job.xi, n_v)
-    if not pre_processed:
-        data = naming.check_data(data)
-    res = api.res_nmtf_inner(data, row_idx, col_idx, None, None, None, [job.k_val] * n_v, phi, xi, psi,
-                             job.n_iters, spurious=False, row_names=rn, col_names=cn, device_id=device_id,
-                             seed=job.seed, return_init=return_init)
+    from . import api      # (lazy: api imports this module at its top for DeviceData and the repeats)
+    p = prepare([np.asarray(d, dtype=np.float64) for d in job.data], job.phi, job.xi, job.psi, job.row_names, job.col_names,
+                normalise=not pre_processed, symmetrise=True)
+    res = api.res_nmtf_inner(p.data, p.row_shared, p.col_shared, None, None, None, [job.k_val] * len(p.data), p.phi, p.xi,
+                             p.psi, job.n_iters, spurious=False, row_names=p.row_names, col_names=p.col_names,
+                             device_id=device_id, seed=job.seed, return_init=return_init)
     res["tag"] = job.tag
     res["extras"] = job.extras
     return res
@@ -188,7 +187,6 @@ def run_jobs(jobs: Sequence[Job], device_id: int = 0, group=None, runner: Option
 # many small jobs in one launch: one workgroup per job, fp64 (resnmtf_group_run)
 # ---------------------------------------------------------------------------------------------
 def _check_group_limits(i: int, data, k: int):
-    from ._lib import GROUP_MAX_K, GROUP_MAX_VIEW_ENTRIES, GROUP_MAX_VIEWS
     if len(data) > GROUP_MAX_VIEWS:
         raise ValueError(f"job {i}: the grouped path takes at most {GROUP_MAX_VIEWS} views, got {len(data)}")
     if not 1 <= k <= GROUP_MAX_K:
@@ -206,7 +204,6 @@ def prepare_grouped_job(job: Job, i: int = 0, pre_processed: bool = False, init=
     names, shared-name index pairs, symmetrised restrictions, ``check_data`` unless ``pre_processed``, and the initial
     factors ``init`` = (F, S, G[, lambda, mu]) per view or, when None, ``api.svd_init(data, k_vec, job.seed)`` on the
     host.  Sparse views and jobs over the kernel's limits are refused here."""
-    from . import api, naming, sparse
     if any(sparse.is_sparse(d) for d in job.data):
         raise NotImplementedError(f"job {i}: the grouped path takes dense views only; run sparse views with run_jobs")
     data = [np.asarray(d, dtype=np.float64) for d in job.data]
@@ -214,13 +211,10 @@ def prepare_grouped_job(job: Job, i: int = 0, pre_processed: bool = False, init=
         raise ValueError(f"job {i}: every view must be a matrix")
     n_v, k = len(data), int(job.k_val)
     _check_group_limits(i, data, k)
-    rn, cn = naming.give_names(data, job.phi, job.psi, job.row_names, job.col_names)
-    row_idx, col_idx = naming.shared_names(rn), naming.shared_names(cn)
-    phi = naming.init_rest_mats(job.phi, n_v); psi = naming.init_rest_mats(job.psi, n_v); xi = naming.init_rest_mats(job.xi, n_v)
-    if not pre_processed:
-        data = naming.check_data(data)
+    p = prepare(data, job.phi, job.xi, job.psi, job.row_names, job.col_names, normalise=not pre_processed, symmetrise=True)
+    data = p.data
     if init is None:
-        init = api.svd_init(data, [k] * n_v, job.seed)
+        init = svd_init(data, [k] * n_v, job.seed)
     init = list(init)
     if len(init) not in (3, 5):
         raise ValueError(f"job {i}: an initial state is (F, S, G) or (F, S, G, lambda, mu) per view")
@@ -237,12 +231,11 @@ def prepare_grouped_job(job: Job, i: int = 0, pre_processed: bool = False, init=
             want = shape(*x.shape)
             if np.shape(a) != want:
                 raise ValueError(f"job {i}, view {v}: the initial {what} has shape {np.shape(a)}, expected {want}")
-    row_pairs = [[None if v == w else naming.index_pairs(rn[v], rn[w], row_idx[v].get(w)) for w in range(n_v)] for v in range(n_v)]
-    col_pairs = [[None if v == w else naming.index_pairs(cn[v], cn[w], col_idx[v].get(w)) for w in range(n_v)] for v in range(n_v)]
     return {"data": data, "k": k, "init_f": list(f0), "init_s": list(s0), "init_g": list(g0),
             "init_lam": None if lam0 is None else list(lam0), "init_mu": None if mu0 is None else list(mu0),
-            "phi": phi, "xi": xi, "psi": psi, "row_pairs": row_pairs, "col_pairs": col_pairs, "n_iters": job.n_iters,
-            "row_names": rn, "col_names": cn}
+            "phi": p.phi, "xi": p.xi, "psi": p.psi, "row_pairs": pair_table(p.row_names, p.row_shared),
+            "col_pairs": pair_table(p.col_names, p.col_shared), "n_iters": job.n_iters,
+            "row_names": p.row_names, "col_names": p.col_names}
 
 
 def _binary_clusters(f, g, s):
@@ -260,7 +253,6 @@ def run_jobs_grouped(jobs: Sequence[Job], device_id: int = 0, pre_processed: boo
     seed.  Returns, in job order, the keys ``run_job`` returns (``bisil`` None).  Every job is prepared and checked
     (dense views only, at most 8 views, 1 <= k <= 32, n * m <= 2^22 per view) before any device work.
     ``group_runner(problems, tol=, max_iters=, device_id=)`` replaces ``engine.group_run`` (a test hook)."""
-    from . import sparse
     jobs = list(jobs)
     if inits is not None and len(inits) != len(jobs):
         raise ValueError("inits must hold one initial state per job")
@@ -269,58 +261,20 @@ def run_jobs_grouped(jobs: Sequence[Job], device_id: int = 0, pre_processed: boo
             raise NotImplementedError(f"job {i}: the grouped path takes dense views only; run sparse views with run_jobs")
         _check_group_limits(i, [np.asarray(d) for d in job.data], int(job.k_val))
     problems = [prepare_grouped_job(job, i, pre_processed, None if inits is None else inits[i]) for i, job in enumerate(jobs)]
-    if group_runner is None:
-        from .engine import group_run as group_runner
-    outs = group_runner(problems, tol=1.0e-6, max_iters=max_iters, device_id=device_id)
+    outs = (group_runner or group_run)(problems, tol=1.0e-6, max_iters=max_iters, device_id=device_id)
     results = []
     for job, out in zip(jobs, outs):
-        errs = np.asarray(out["all_error"], dtype=np.float64)
-        error = float(np.mean(errs[-10:])) if job.n_iters is None else float(errs[-1])      # R/main.r:126-130
         rcs, ccs = zip(*[_binary_clusters(f, g, s) for f, g, s in zip(out["f"], out["g"], out["s"])])
-        results.append({"output_f": out["f"], "output_s": out["s"], "output_g": out["g"], "Error": error,
-                        "All_Error": errs, "bisil": None, "row_clusters": list(rcs), "col_clusters": list(ccs),
-                        "lambda": out["lambda"], "mu": out["mu"], "tag": job.tag, "extras": job.extras})
+        results.append(inner_result(out["f"], out["s"], out["g"], np.asarray(out["all_error"], dtype=np.float64), job.n_iters,
+                                    row_clusters=list(rcs), col_clusters=list(ccs), lam=out["lambda"], mu=out["mu"], tag=job.tag,
+                                    extras=job.extras))
     return results
 
 
 # ---------------------------------------------------------------------------------------------
 # the same job kinds with the data resident on the device: one upload, copies / shuffles drawn there
 # ---------------------------------------------------------------------------------------------
-def _draw_shuffle(eng, v: int, src, shuffle_seed: int):
-    """``shuffle_view`` (``R/obtain_bicl.r:11-22``) of ``src``'s view v into ``eng``'s view v, drawn and re-normalised
-    on the device; redrawn while a row or a column of the shuffled matrix sums to zero (``:14-18``)."""
-    for attempt in range(64):
-        eng.shuffle_view_from(v, src, v, seed=(shuffle_seed + 7919 * attempt) * 1000003 + v)
-        er, ec = eng.empty_lines(v)
-        if not (er.any() or ec.any()):
-            return
-    raise RuntimeError("shuffle_view: every draw left an all-zero row or column")
-
-
-def shuffled_engines(src, k: int, num_repeats: int, seed: int = 0, max_iters: int = 100000, device_id: int = 0) -> list:
-    """``obtain_shuffled_f`` (``R/obtain_bicl.r:31-42``) drawn from the views an engine already holds on the device
-    (``src``: a ``res_nmtf_inner`` engine or a stability repeat's sub-sample; no second upload): ``num_repeats`` engines,
-    every view shuffled from ``src``'s and re-normalised, no restrictions, uncoupled, device SVD init, run to
-    convergence -- the draws and seeds of ``shuffles_on_device(dev, k, num_repeats, seed=seed)``: repeat r initialises
-    with ``seed + 1000 + r`` and shuffles with ``seed * 7919 + r + 1``.  The engines are returned open, with their
-    factors on the device (``Engine.spurious_scores``); the caller closes them."""
-    from .engine import Engine
-    n_v = src.n_views
-    out = []
-    try:
-        for r in range(num_repeats):
-            eng = Engine(src.n_rows, src.n_cols, [k] * n_v, device_id=device_id)
-            out.append(eng)
-            for v in range(n_v):
-                _draw_shuffle(eng, v, src, seed * 7919 + r + 1)
-                eng.init_svd(v, seed=seed + 1000 + r + v)
-            eng.set_restrictions(None, None, None)          # R/obtain_bicl.r:35-39: apply_resnmtf without phi/xi/psi
-            eng.run(n_iters=None, tol=1.0e-6, max_iters=max_iters)
-    except BaseException:
-        for eng in out:
-            eng.close()
-        raise
-    return out
+Child = namedtuple("Child", "eng row_names col_names samples host_views")
 
 
 class DeviceData:
@@ -335,43 +289,30 @@ class DeviceData:
 
     def __init__(self, data, phi=None, xi=None, psi=None, row_names=None, col_names=None, device_id: int = 0,
                  pre_processed: bool = False):
-        from . import naming, sparse
-        from .engine import Engine
         # sparse views (scipy.sparse) stay sparse: a canonical, pre-processed CSC copy on the host, from which the
         # sub-samples are gathered, and a sparse view on the device
         self.sp = [None if not sparse.is_sparse(d) else (sparse.canonical_csc(d) if pre_processed else sparse.check_data_one(d))
                    for d in data]
-        if pre_processed:
-            for c in self.sp:
-                if c is not None:
-                    sparse.validate(c)
-        data = [d if c is None else c for d, c in zip(data, self.sp)]
-        self.data_shapes = [tuple(d.shape) if c is not None else np.asarray(d).shape for d, c in zip(data, self.sp)]
+        for c in self.sp:
+            if pre_processed and c is not None:
+                sparse.validate(c)
+        data = [np.asarray(d) if c is None else c for d, c in zip(data, self.sp)]
+        self.data_shapes = [tuple(d.shape) for d in data]
         n_v = len(data)
-        self.rn, self.cn = naming.give_names([d if c is not None else np.asarray(d) for d, c in zip(data, self.sp)], phi, psi,
-                                             row_names, col_names)
-        if pre_processed:
-            self.phi, self.xi, self.psi = (np.zeros((n_v, n_v)) if m is None else np.asarray(m, dtype=np.float64)
-                                           for m in (phi, xi, psi))
-        else:
-            self.phi = naming.init_rest_mats(phi, n_v); self.xi = naming.init_rest_mats(xi, n_v); self.psi = naming.init_rest_mats(psi, n_v)
+        # (not pre_processed: the device shifts and normalises the dense views, set_view_raw below)
+        p = prepare(data, phi, xi, psi, row_names, col_names, normalise=False, symmetrise=not pre_processed)
+        self.rn, self.cn, self.phi, self.xi, self.psi = p.row_names, p.col_names, p.phi, p.xi, p.psi
         self.device_id = device_id
-        nnz = [None if c is None else c.nnz for c in self.sp] if any(c is not None for c in self.sp) else None
         self.base = Engine([s[0] for s in self.data_shapes], [s[1] for s in self.data_shapes], [2] * n_v, device_id=device_id,
-                           nnz=nnz)
-        if pre_processed:
-            for v in range(n_v):
-                if self.sp[v] is not None:
-                    self.base.set_view_sparse(v, self.sp[v], pre_processed=True)
-                else:
-                    self.base.set_view(v, np.asarray(data[v], dtype=np.float64))
-            self.was_negative = [False] * n_v
-        else:
-            self.was_negative = [False if self.sp[v] is not None else self.base.set_view_raw(v, np.asarray(data[v], dtype=np.float64))
-                                 for v in range(n_v)]
-            for v in range(n_v):
-                if self.sp[v] is not None:
-                    self.base.set_view_sparse(v, self.sp[v], pre_processed=True)      # (normalised on the host: self.sp)
+                           nnz=[None if c is None else c.nnz for c in self.sp])
+        self.was_negative = [False] * n_v
+        for v in range(n_v):
+            if self.sp[v] is not None:
+                self.base.set_view_sparse(v, self.sp[v], pre_processed=True)      # (normalised on the host: self.sp)
+            elif pre_processed:
+                self.base.set_view(v, np.asarray(data[v], dtype=np.float64))
+            else:
+                self.was_negative[v] = self.base.set_view_raw(v, np.asarray(data[v], dtype=np.float64))
 
     def close(self):
         self.base.close()
@@ -381,7 +322,6 @@ class DeviceData:
         columns of a sub-sample are dropped -- from every earlier view that shares the draw (equal extent along that
         axis) -- and the sub-samples gathered again, until none is left.  The emptiness test runs on the device
         (``resnmtf_view_empty_lines``), on probes that hold only the data.  Returns the trimmed draws or ``None``."""
-        from .engine import Engine
         n_v = len(self.data_shapes)
         rows = [np.asarray(r).copy() for r in samples[0]]; cols = [np.asarray(c).copy() for c in samples[1]]
         for _ in range(max_rounds):
@@ -389,18 +329,12 @@ class DeviceData:
             for i in range(n_v):
                 if len(rows[i]) < 2 or len(cols[i]) < 2:
                     return None
-                probe = None
                 if self.sp[i] is not None:          # sparse view: the sub-sample is gathered on the host
-                    from . import sparse
                     _, er, ec = sparse.subsample(self.sp[i], rows[i], cols[i])
                 else:
-                    probe = Engine([len(rows[i])], [len(cols[i])], [2], device_id=self.device_id)
-                if probe is not None:
-                    try:
+                    with Engine([len(rows[i])], [len(cols[i])], [2], device_id=self.device_id) as probe:
                         probe.subsample_view_from(0, self.base, i, rows[i], cols[i])
                         er, ec = probe.empty_lines(0)
-                    finally:
-                        probe.close()
                 if er.any() or ec.any():
                     changed = True
                     same_r = self.data_shapes[i][0] == self.data_shapes[0][0]
@@ -415,120 +349,100 @@ class DeviceData:
                 return rows, cols
         return None
 
-    def factorise(self, k: int, n_iters: Optional[int] = None, seed: int = 0, shuffle_seed: Optional[int] = None,
-                  max_iters: int = 100000, tag: str = "", samples=None, return_init: bool = False,
-                  return_data: bool = False, relevance: bool = False, keep_clusters: bool = False,
-                  return_lm: bool = False, spurious_repeats: int = 0, spurious_seed: int = 0) -> dict:
-        """One factorisation with k biclusters per view: views copied -- or, with ``shuffle_seed``, shuffled as
-        ``obtain_shuffled_f`` does (no restrictions, fresh names; redrawn while a row or a column of the shuffled
-        matrix sums to zero, ``R/obtain_bicl.r:14-18``), or, with ``samples = (row_samples, col_samples)``,
-        sub-sampled as ``stability_repeat`` does (not re-normalised, names carried over; all-zero rows / columns
-        dropped first, ``_trim_samples``) -- on the device, device SVD init, loop, finalise.
-        ``return_init`` / ``return_data`` add the initial (F, S, G, lambda, mu) per view and the device's copy of the
-        data actually factorised (fp32 precision) to the result: what a reference run needs to start from the same place.
-        ``relevance`` (with ``samples``): instead of finalise, score the sub-sample's clusters against the reference
-        clusters set on ``self.base`` (``resnmtf_relevance``, ``R/stability_analysis.r:268-276``) -- the result holds
-        the n_views x k ``"relevance"`` matrix and no factors; ``keep_clusters`` adds the sub-sample's own binary
-        clusters (a test hook: they cost a finalise download).  ``return_lm`` adds ``"lambda"`` / ``"mu"`` per view (the
-        keys of a ``res_nmtf_inner`` result, for the k sweep of ``apply_resnmtf``).  ``spurious_repeats`` = R >= 2: the
-        scores of ``check_biclusters`` against R shuffles of this factorisation's own device copy
-        (``spurious.check_on_device`` with ``spurious_seed``) -- with ``relevance``, the flagged cluster columns are
-        removed before the scoring (``resnmtf_relevance_masked``, ``R/stability_analysis.r:254-276``) and the kept
-        clusters are the cleaned ones; else the result holds the check as ``"spurious_check"`` (the caller removes)."""
-        from . import naming
-        from .engine import Engine
+    @contextlib.contextmanager
+    def child(self, k: int, seed: int = 0, shuffle_seed: Optional[int] = None, samples=None):
+        """An engine with k biclusters per view, loaded from ``self.base`` and closed on exit: the views copied -- or
+        shuffled as ``obtain_shuffled_f`` does (``shuffle_seed``: no restrictions, uncoupled), or sub-sampled as
+        ``stability_repeat`` does (``samples = (row_samples, col_samples)``: trimmed first, ``_trim_samples``; not
+        re-normalised, names carried over) -- and SVD-initialised on the device (``problem.load_child``).  Yields
+        ``Child(eng, row_names, col_names, samples, host_views)``: the names in use, the trimmed samples, what was uploaded
+        of a sparse view -- or ``None`` when the trimming fails (``R/stability_analysis.r:223-226``)."""
         n_v = len(self.data_shapes)
+        shapes, rn, cn = self.data_shapes, self.rn, self.cn
         if samples is not None:
             samples = self._trim_samples(samples)
             if samples is None:
-                return {"stability_performed": False, "tag": tag}          # R/stability_analysis.r:223-226
-        shapes = self.data_shapes if samples is None else [(len(samples[0][v]), len(samples[1][v])) for v in range(n_v)]
-        rn, cn = self.rn, self.cn
-        if samples is not None:
+                yield None
+                return
+            shapes = [(len(samples[0][v]), len(samples[1][v])) for v in range(n_v)]
             rn = [[self.rn[v][t] for t in samples[0][v]] for v in range(n_v)]
             cn = [[self.cn[v][t] for t in samples[1][v]] for v in range(n_v)]
-        shuffled = shuffle_seed is not None
-        host_views = [None] * n_v          # sparse views: what is uploaded (the whole view or its sub-sample), gathered on the host
-        if any(c is not None for c in self.sp):
-            if shuffled:
-                raise NotImplementedError("device shuffles of sparse views are not supported")
-            from . import sparse
-            for v in range(n_v):
-                if self.sp[v] is not None:
-                    host_views[v] = self.sp[v] if samples is None else sparse.subsample(self.sp[v], samples[0][v], samples[1][v])[0]
-        nnz = [None if hv is None else hv.nnz for hv in host_views] if any(hv is not None for hv in host_views) else None
-        eng = Engine([s[0] for s in shapes], [s[1] for s in shapes], [k] * n_v, device_id=self.device_id, nnz=nnz)
-        try:
-            for v in range(n_v):
-                if shuffled:
-                    _draw_shuffle(eng, v, self.base, shuffle_seed)
-                elif host_views[v] is not None:
-                    eng.set_view_sparse(v, host_views[v], pre_processed=True)      # (sub-samples are not re-normalised)
-                elif samples is not None:
-                    eng.subsample_view_from(v, self.base, v, samples[0][v], samples[1][v])
-                else:
-                    eng.copy_view_from(v, self.base, v)
-                eng.init_svd(v, seed=seed + v)
-            if shuffled:
-                eng.set_restrictions(None, None, None)          # R/obtain_bicl.r:35-39: apply_resnmtf without phi/xi/psi
-            else:
-                eng.set_restrictions(self.phi, self.xi, self.psi)
-                rs, cs = naming.shared_names(rn), naming.shared_names(cn)
-                for v in range(n_v):
-                    for w in range(n_v):
-                        if v != w:
-                            eng.set_shared_rows(v, w, *naming.index_pairs(rn[v], rn[w], rs[v].get(w)))
-                            eng.set_shared_cols(v, w, *naming.index_pairs(cn[v], cn[w], cs[v].get(w)))
+        if shuffle_seed is not None and any(c is not None for c in self.sp):
+            raise NotImplementedError("device shuffles of sparse views are not supported")
+        # sparse views: the whole view or its sub-sample, gathered on the host
+        host_views = [c if c is None or samples is None else sparse.subsample(c, samples[0][v], samples[1][v])[0]
+                      for v, c in enumerate(self.sp)]
+        with Engine([s[0] for s in shapes], [s[1] for s in shapes], [k] * n_v, device_id=self.device_id,
+                    nnz=[None if hv is None else hv.nnz for hv in host_views]) as eng:
+            load_child(eng, self.base, seed, shuffle_seed=shuffle_seed, samples=samples, host_views=host_views,
+                       coupling=(self.phi, self.xi, self.psi, rn, cn))
+            yield Child(eng, rn, cn, samples, host_views)
+
+    def factorise(self, k: int, n_iters: Optional[int] = None, seed: int = 0, shuffle_seed: Optional[int] = None,
+                  max_iters: int = 100000, tag: str = "", samples=None, return_init: bool = False,
+                  return_data: bool = False, return_lm: bool = False, spurious_repeats: int = 0,
+                  spurious_seed: int = 0) -> dict:
+        """One factorisation with k biclusters per view of the views copied, shuffled (``shuffle_seed``) or sub-sampled
+        (``samples``) on the device (``child``): device SVD init, loop, finalise.  With ``samples`` whose trimming
+        fails: ``{"stability_performed": False, "tag"}``.
+        ``return_init`` / ``return_data`` add the initial (F, S, G, lambda, mu) per view and the device's copy of the
+        data actually factorised (fp32 precision) to the result: what a reference run needs to start from the same place.
+        ``return_lm`` adds ``"lambda"`` / ``"mu"`` per view (the keys of a ``res_nmtf_inner`` result, for the k sweep of
+        ``apply_resnmtf``).  ``spurious_repeats`` = R >= 2: the scores of ``check_biclusters`` against R shuffles of
+        this factorisation's own device copy (``spurious.check_on_device`` with ``spurious_seed``) as
+        ``"spurious_check"`` (the caller removes)."""
+        n_v = len(self.data_shapes)
+        with self.child(k, seed, shuffle_seed, samples) as ch:
+            if ch is None:
+                return {"stability_performed": False, "tag": tag}
+            eng = ch.eng
             init_state = [eng.get_factors(v) for v in range(n_v)] if return_init else None
             # (sparse views: the host copy rounded to f32, as the device holds the values)
-            data_used = ([host_views[v].toarray().astype(np.float32).astype(np.float64) if host_views[v] is not None
+            data_used = ([ch.host_views[v].toarray().astype(np.float32).astype(np.float64) if ch.host_views[v] is not None
                           else eng.get_view(v) for v in range(n_v)] if return_data else None)
             errs = eng.run(n_iters=n_iters, tol=1.0e-6, max_iters=max_iters)
-            check = None
-            if spurious_repeats:
-                from . import spurious
-                check = spurious.check_on_device(eng, spurious_repeats, spurious_seed, max_iters=max_iters,
-                                                  device_id=self.device_id)
-            if relevance and check is not None:
-                flags = spurious.removal_flags(check)
-                rel = np.stack([eng.relevance_masked(v, self.base, v, samples[0][v], samples[1][v], flags[v])
-                                for v in range(n_v)])
-                fin = None
-                if keep_clusters:
-                    fin = [eng.finalise(v) for v in range(n_v)]
-                    cleaned = spurious.apply_removal({"output_s": [f[1] for f in fin], "row_clusters": [f[3] for f in fin],
-                                                      "col_clusters": [f[4] for f in fin]}, check)
-                    fin = [(None, None, None, rc, cc) for rc, cc in zip(cleaned["row_clusters"], cleaned["col_clusters"])]
-            elif relevance:
-                rel = np.stack([eng.relevance(v, self.base, v, samples[0][v], samples[1][v]) for v in range(n_v)])
-                fin = [eng.finalise(v) for v in range(n_v)] if keep_clusters else None
+            check = (spurious.check_on_device(eng, spurious_repeats, spurious_seed, max_iters=max_iters,
+                                              device_id=self.device_id) if spurious_repeats else None)
+            fin = [eng.finalise(v) for v in range(n_v)]
+            lms = [eng.get_factors(v)[3:] for v in range(n_v)] if return_lm else None
+        f, s, g, rc, cc = (list(x) for x in zip(*fin))
+        return inner_result(f, s, g, errs, n_iters, device_data=True, row_clusters=rc, col_clusters=cc, tag=tag,
+                            extras={} if ch.samples is None else {"row_samples": ch.samples[0], "col_samples": ch.samples[1]},
+                            row_names=ch.row_names, col_names=ch.col_names, init=init_state,
+                            lam=lms and [lm[0] for lm in lms], mu=lms and [lm[1] for lm in lms], data=data_used,
+                            spurious_check=check)
+
+    def stability_repeat(self, k: int, n_iters: Optional[int], seed: int, samples, max_iters: int = 100000, tag: str = "",
+                         keep_clusters: bool = False, spurious_repeats: int = 0, spurious_seed: int = 0) -> dict:
+        """One repeat of ``stability_check`` (``R/stability_analysis.r:215-278``): the sub-sample ``samples`` factorised
+        (``child``) and, instead of finalise, its clusters scored against the reference clusters set on ``self.base``
+        (``resnmtf_relevance``, ``:268-276``) -- the result holds the n_views x k ``"relevance"`` matrix and no factors,
+        or ``{"stability_performed": False, "tag"}`` when the trimming fails.  ``keep_clusters`` adds the sub-sample's
+        own binary clusters (a test hook: they cost a finalise download).  ``spurious_repeats`` = R >= 2: the cluster
+        columns flagged against R shuffles of the sub-sample (``spurious.check_on_device`` with ``spurious_seed``) are
+        removed before the scoring (``resnmtf_relevance_masked``, ``:254-276``) and the kept clusters are the cleaned
+        ones."""
+        n_v = len(self.data_shapes)
+        with self.child(k, seed, samples=samples) as ch:
+            if ch is None:
+                return {"stability_performed": False, "tag": tag}
+            eng, (rows, cols) = ch.eng, ch.samples
+            errs = eng.run(n_iters=n_iters, tol=1.0e-6, max_iters=max_iters)
+            check = (spurious.check_on_device(eng, spurious_repeats, spurious_seed, max_iters=max_iters,
+                                              device_id=self.device_id) if spurious_repeats else None)
+            if check is None:
+                rel = [eng.relevance(v, self.base, v, rows[v], cols[v]) for v in range(n_v)]
             else:
-                fin = [eng.finalise(v) for v in range(n_v)]
-                lms = [eng.get_factors(v)[3:] for v in range(n_v)] if return_lm else None
-        finally:
-            eng.close()
-        error = float(np.mean(errs[-10:])) if n_iters is None else float(errs[-1])           # R/main.r:126-130
-        if relevance:
-            res = {"stability_performed": True, "relevance": rel, "Error": error, "All_Error": errs, "tag": tag,
-                   "extras": {"row_samples": samples[0], "col_samples": samples[1]}}
+                flags = spurious.removal_flags(check)
+                rel = [eng.relevance_masked(v, self.base, v, rows[v], cols[v], flags[v]) for v in range(n_v)]
+            res = {"stability_performed": True, "relevance": np.stack(rel), "Error": reported_error(errs, n_iters),
+                   "All_Error": errs, "tag": tag, "extras": {"row_samples": rows, "col_samples": cols}}
             if keep_clusters:
-                res["row_clusters"] = [f[3] for f in fin]
-                res["col_clusters"] = [f[4] for f in fin]
-            return res
-        res = {"output_f": [f[0] for f in fin], "output_s": [f[1] for f in fin], "output_g": [f[2] for f in fin],
-               "row_clusters": [f[3] for f in fin], "col_clusters": [f[4] for f in fin],
-               "Error": error, "All_Error": errs, "tag": tag,
-               "extras": {} if samples is None else {"row_samples": samples[0], "col_samples": samples[1]},
-               "row_names": rn, "col_names": cn}
-        if return_init:
-            res["init"] = init_state
-        if return_lm:
-            res["lambda"] = [lm[0] for lm in lms]
-            res["mu"] = [lm[1] for lm in lms]
-        if return_data:
-            res["data"] = data_used
-        if check is not None:
-            res["spurious_check"] = check
+                fin = [eng.finalise(v) for v in range(n_v)]
+                kept = {"output_s": [f[1] for f in fin], "row_clusters": [f[3] for f in fin], "col_clusters": [f[4] for f in fin]}
+                if check is not None:
+                    kept = spurious.apply_removal(kept, check)
+                res["row_clusters"], res["col_clusters"] = kept["row_clusters"], kept["col_clusters"]
         return res
 
 
@@ -618,9 +532,9 @@ def stability_relevance_on_device(dev: Optional[DeviceData], results: dict, k: i
         draws = stability_draws(dev.data_shapes, n_stability, sample_rate, seed)
 
         def runner(r):
-            return dev.factorise(k, n_iters, seed + 2000 + r, max_iters=max_iters, samples=draws[r], relevance=True,
-                                 keep_clusters=keep_clusters, tag=f"stability={r}", spurious_repeats=spurious_repeats,
-                                 spurious_seed=seed + 2000 + r)
+            return dev.stability_repeat(k, n_iters, seed + 2000 + r, draws[r], max_iters=max_iters, tag=f"stability={r}",
+                                        keep_clusters=keep_clusters, spurious_repeats=spurious_repeats,
+                                        spurious_seed=seed + 2000 + r)
     repeats = run_jobs(list(range(n_stability)), group=group, runner=runner)
     rel = mean_relevance(repeats, n_stability)
     return {"stability_performed": rel is not None, "relevance": rel, "repeats": repeats}

@@ -1,0 +1,152 @@
+"""The steps every entry point shares, written once: preparing a problem (names, shared-name maps, symmetrised
+restrictions, pre-processing: ``prepare``), wiring an engine's view coupling (``couple`` over ``pair_table``), loading a
+child engine from one that already holds the data (``load_child``), and assembling a ``res_nmtf_inner`` result
+(``inner_result`` with ``reported_error``).  Imported at module top by ``api``, ``batched``, ``spurious`` and ``sharded``;
+imports only ``naming`` and ``engine`` itself."""
+from __future__ import annotations
+
+from collections import namedtuple
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import naming
+from .engine import Engine
+
+
+def svd_init(data: Sequence[np.ndarray], k_vec: Sequence[int], seed: Optional[int] = None, sigma: float = 0.05):
+    """``init_mats_inner`` (``R/update_steps.r:78-125``) on the host, as in the reference
+    (the initialisation is outside the accelerated loop).  The noise on S comes from NumPy's
+    generator instead of ``MASS::mvrnorm`` + R's RNG: statistically, not bitwise, equivalent."""
+    rng = np.random.default_rng(seed)
+    init_f, init_s, init_g, init_lam, init_mu = [], [], [], [], []
+    for x, k in zip(data, k_vec):
+        u, d, vt = np.linalg.svd(x, full_matrices=False)
+        f = np.abs(u[:, :k]); g = np.abs(vt.T[:, :k])
+        s = np.abs(np.diag(d)[:k, :k]) + np.abs(rng.normal(0.0, np.sqrt(sigma), size=(k, k)))
+        cf, cg = f.sum(axis=0), g.sum(axis=0)
+        s = s * (cf * cg)[None, :]
+        f = f / cf[None, :]; g = g / cg[None, :]
+        init_f.append(f); init_s.append(s); init_g.append(g)
+        init_lam.append(f.sum(axis=0)); init_mu.append(g.sum(axis=0))
+    return init_f, init_s, init_g, init_lam, init_mu
+
+
+# a problem as res_nmtf_inner receives it (R/main.r:225-249)
+Prepared = namedtuple("Prepared", "data row_names col_names phi xi psi row_shared col_shared")
+
+
+def prepare(data, phi, xi, psi, row_names, col_names, *, normalise: bool, symmetrise: bool) -> Prepared:
+    """``apply_resnmtf``'s steps before the loop: ``give_names`` (``R/main.r:228``; only the shapes of ``data`` are
+    read), the shared-name maps (``:230``), the restriction matrices -- symmetrised (``init_rest_mats``, ``:233-235``)
+    or, with ``symmetrise=False``, taken as the symmetrised matrices they already are (None = zeros) -- and, with
+    ``normalise``, the non-negativity shift and column normalisation on the host (``check_data``, ``:237``)."""
+    n_v = len(data)
+    rn, cn = naming.give_names(data, phi, psi, row_names, col_names)
+    shared = naming.shared_names(rn), naming.shared_names(cn)
+    if symmetrise:
+        phi, psi, xi = (naming.init_rest_mats(m, n_v) for m in (phi, psi, xi))
+    else:
+        phi, psi, xi = (np.zeros((n_v, n_v)) if m is None else np.asarray(m, dtype=np.float64) for m in (phi, psi, xi))
+    return Prepared(naming.check_data(data) if normalise else list(data), rn, cn, phi, xi, psi, *shared)
+
+
+def pair_table(names, shared=None) -> list:
+    """``table[v][w]`` = the index pairs (``naming.index_pairs``) of the names views v and w share along one axis --
+    ``(None, None)`` for NA -- and ``None`` on the diagonal.  ``shared``: the axis' shared-name map, built from the
+    names when not given."""
+    shared = naming.shared_names(names) if shared is None else shared
+    return [[None if v == w else naming.index_pairs(names[v], names[w], shared[v].get(w)) for w in range(len(names))]
+            for v in range(len(names))]
+
+
+def couple(eng, row_names, col_names, row_shared=None, col_shared=None):
+    """Hand ``eng`` the shared rows and columns of every ordered pair of views (nothing to do for one view)."""
+    rows, cols = pair_table(row_names, row_shared), pair_table(col_names, col_shared)
+    for v in range(len(row_names)):
+        for w in range(len(row_names)):
+            if v != w:
+                eng.set_shared_rows(v, w, *rows[v][w])
+                eng.set_shared_cols(v, w, *cols[v][w])
+
+
+def _draw_shuffle(eng, v: int, src, shuffle_seed: int):
+    """``shuffle_view`` (``R/obtain_bicl.r:11-22``) of ``src``'s view v into ``eng``'s view v, drawn and re-normalised
+    on the device; redrawn while a row or a column of the shuffled matrix sums to zero (``:14-18``)."""
+    for attempt in range(64):
+        eng.shuffle_view_from(v, src, v, seed=(shuffle_seed + 7919 * attempt) * 1000003 + v)
+        er, ec = eng.empty_lines(v)
+        if not (er.any() or ec.any()):
+            return
+    raise RuntimeError("shuffle_view: every draw left an all-zero row or column")
+
+
+def load_child(eng, src, seed: int, *, shuffle_seed: Optional[int] = None, samples=None, host_views=None, coupling=None):
+    """Fill ``eng`` from ``src``, an engine on the same device that holds the data: every view shuffled (with
+    ``shuffle_seed``), sub-sampled (``samples = (row_samples, col_samples)``) or copied -- a sparse view is uploaded from
+    ``host_views[v]`` instead -- then the device SVD init with ``seed + v``; at last ``coupling`` = (phi, xi, psi,
+    row_names, col_names), or for shuffles none: no restrictions, uncoupled (``R/obtain_bicl.r:35-39``)."""
+    for v in range(eng.n_views):
+        if shuffle_seed is not None:
+            _draw_shuffle(eng, v, src, shuffle_seed)
+        elif host_views is not None and host_views[v] is not None:
+            eng.set_view_sparse(v, host_views[v], pre_processed=True)      # (sub-samples are not re-normalised)
+        elif samples is not None:
+            eng.subsample_view_from(v, src, v, samples[0][v], samples[1][v])
+        else:
+            eng.copy_view_from(v, src, v)
+        eng.init_svd(v, seed=seed + v)
+    if shuffle_seed is not None:
+        eng.set_restrictions(None, None, None)
+    else:
+        eng.set_restrictions(*coupling[:3])
+        couple(eng, *coupling[3:])
+
+
+def shuffled_engines(src, k: int, num_repeats: int, seed: int = 0, max_iters: int = 100000, device_id: int = 0) -> list:
+    """``obtain_shuffled_f`` (``R/obtain_bicl.r:31-42``) drawn from the views an engine already holds on the device
+    (``src``: a ``res_nmtf_inner`` engine or a stability repeat's sub-sample; no second upload): ``num_repeats`` engines,
+    every view shuffled from ``src``'s and re-normalised, no restrictions, uncoupled, device SVD init, run to
+    convergence -- the draws and seeds of ``shuffles_on_device(dev, k, num_repeats, seed=seed)``: repeat r initialises
+    with ``seed + 1000 + r`` and shuffles with ``seed * 7919 + r + 1``.  The engines are returned open, with their
+    factors on the device (``Engine.spurious_scores``); the caller closes them."""
+    out = []
+    try:
+        for r in range(num_repeats):
+            eng = Engine(src.n_rows, src.n_cols, [k] * src.n_views, device_id=device_id)
+            out.append(eng)
+            load_child(eng, src, seed + 1000 + r, shuffle_seed=seed * 7919 + r + 1)
+            eng.run(n_iters=None, tol=1.0e-6, max_iters=max_iters)
+    except BaseException:
+        for eng in out:
+            eng.close()
+        raise
+    return out
+
+
+def reported_error(errs, n_iters) -> float:
+    """``R/main.r:126-130``: the mean of the last ten errors of a run to convergence, else the last error."""
+    return float(np.mean(errs[-10:])) if n_iters is None else float(errs[-1])
+
+
+_INNER_KEYS = ("output_f", "output_s", "output_g", "Error", "All_Error", "bisil", "row_clusters", "col_clusters",
+               "lambda", "mu", "spurious", "init", "tag", "extras")
+_DEVICE_DATA_KEYS = ("output_f", "output_s", "output_g", "row_clusters", "col_clusters", "Error", "All_Error", "tag",
+                     "extras", "row_names", "col_names", "init", "lambda", "mu", "data", "spurious_check")
+
+
+def inner_result(output_f, output_s, output_g, errs=None, n_iters=None, *, lam=None, mu=None, device_data: bool = False,
+                 **more) -> dict:
+    """The result of ``res_nmtf_inner`` (``R/main.r:115-139``) with its keys in their fixed order -- ``device_data``:
+    the order of ``DeviceData.factorise`` (clusters before the errors, no ``"bisil"``).  ``errs``: the error trace, which
+    gives ``"Error"``; without it the ``no_clusts`` result.  ``lam``: ``"lambda"``; ``more``: the clusters, ``bisil`` and
+    the optional keys.  A value that is None is left out (``"bisil"`` stays: None = not scored)."""
+    vals = dict(more, output_f=output_f, output_s=output_s, output_g=output_g, mu=mu, **{"lambda": lam})
+    if errs is not None:
+        vals.update(Error=reported_error(errs, n_iters), All_Error=errs)
+        if not device_data:
+            vals.setdefault("bisil", None)
+    keys = _DEVICE_DATA_KEYS if device_data else _INNER_KEYS
+    if not set(vals) <= set(keys):
+        raise TypeError(f"not keys of this result: {sorted(set(vals) - set(keys))}")
+    return {key: vals[key] for key in keys if key in vals and (vals[key] is not None or key == "bisil")}

@@ -55,6 +55,8 @@ from typing import Callable, Dict, List, Optional, Sequence
 import numpy as np
 
 from . import naming
+from .engine import Engine
+from .problem import couple, inner_result, prepare
 from ._lib import (FACTOR_F, FACTOR_FBLOCK, FACTOR_FBLOCK_ALL, FACTOR_FNEW_RECV, FACTOR_FNEW_SEND, FACTOR_G, FACTOR_GBLOCK,
                    FACTOR_GBLOCK_ALL, FACTOR_GNEW_RECV, FACTOR_GNEW_SEND, FACTOR_S, FACTOR_SBLOCK, FACTOR_SBLOCK_ALL,
                    FACTOR_T_RECV, FACTOR_T_SEND, FACTOR_U_RECV, FACTOR_U_SEND, PHASE_F, PHASE_F_ALL, PHASE_G, PHASE_G_ALL,
@@ -223,8 +225,6 @@ def make_hip_engine(prob: Problem, owned: Sequence[bool], device_index: int, str
     on the given HIP stream -- the torch stream the driver makes current around its broadcasts, so
     that torch.distributed orders them against the kernels.  (The legacy NULL stream must not be
     used: the library would fall back to a private non-blocking stream the broadcasts never see.)"""
-    from .engine import Engine
-
     if not stream:
         raise ValueError("a non-default HIP stream is required")
     n_v = len(prob.init_f)
@@ -236,15 +236,7 @@ def make_hip_engine(prob: Problem, owned: Sequence[bool], device_index: int, str
             eng.set_view(v, prob.data[v])
         eng.set_factors(v, prob.init_f[v], prob.init_s[v], prob.init_g[v])
     eng.set_restrictions(prob.phi, prob.xi, prob.psi)
-    row_sh, col_sh = naming.shared_names(prob.row_names), naming.shared_names(prob.col_names)
-    for v in range(n_v):
-        for w in range(n_v):
-            if w == v:
-                continue
-            iv, iw = naming.index_pairs(prob.row_names[v], prob.row_names[w], row_sh[v].get(w))
-            eng.set_shared_rows(v, w, iv, iw)
-            iv, iw = naming.index_pairs(prob.col_names[v], prob.col_names[w], col_sh[v].get(w))
-            eng.set_shared_cols(v, w, iv, iw)
+    couple(eng, prob.row_names, prob.col_names)
     return HipEngineAdapter(eng)
 
 
@@ -958,17 +950,15 @@ def res_nmtf_inner(data, row_indices=None, column_indices=None, init_f=None, ini
         if owner_of[v] == rank and data[v] is None:
             raise ValueError(f"rank {rank} owns view {v} but was not given its data")
     shapes = [(np.asarray(f).shape[0], np.asarray(g).shape[0]) for f, g in zip(init_f, init_g)]
-    zeros = np.zeros((n_v, n_v))
+    # names: as given, else the reference's auto-naming (R/utils.r:482-491) from the shapes alone -- a stand-in with no
+    # memory behind it, since a rank holds only its own views; phi / xi / psi arrive symmetrised
+    p = prepare([np.broadcast_to(0.0, sh) for sh in shapes], phi, xi, psi, row_names, col_names,
+                normalise=False, symmetrise=False)
     prob = Problem([None if d is None else np.asarray(d, dtype=np.float64) for d in data],
                    [np.asarray(x, dtype=np.float64) for x in init_f], [np.asarray(x, dtype=np.float64) for x in init_s],
-                   [np.asarray(x, dtype=np.float64) for x in init_g],
-                   zeros if phi is None else np.asarray(phi, dtype=np.float64), zeros if xi is None else np.asarray(xi, dtype=np.float64),
-                   zeros if psi is None else np.asarray(psi, dtype=np.float64), k_all[0], "res_nmtf_inner (view-sharded)")
-    if row_names is None or col_names is None:      # the reference's auto-naming (R/utils.r:482-491) from the shapes alone
-        stand_in = [np.broadcast_to(0.0, sh) for sh in shapes]      # (shape only: no memory behind it)
-        rn, cn = naming.give_names(stand_in, prob.phi if prob.phi.any() else None, prob.psi if prob.psi.any() else None)
-        row_names, col_names = row_names or rn, col_names or cn
-    prob.row_names, prob.col_names = [list(x) for x in row_names], [list(x) for x in col_names]
+                   [np.asarray(x, dtype=np.float64) for x in init_g], p.phi, p.xi, p.psi, k_all[0],
+                   "res_nmtf_inner (view-sharded)")
+    prob.row_names, prob.col_names = p.row_names, p.col_names
     prob.extras["shapes"] = shapes
     if "engine_factory" in driver_opts or "engine" in driver_opts:
         drv = ShardedSweep(prob, owner_of, rank, world, group=group, **driver_opts)
@@ -1001,12 +991,11 @@ def res_nmtf_inner(data, row_indices=None, column_indices=None, init_f=None, ini
     if rank != dst:
         return None
     if no_clusts:                                                                                 # main.r:115-120
-        return {k: res[k] for k in ("output_f", "output_s", "output_g")}
+        return inner_result(res["output_f"], res["output_s"], res["output_g"])
     lam_mu = {}
     for part in everyone:
         lam_mu.update(part or {})
-    error = float(np.mean(errs[-10:])) if n_iters is None else float(errs[-1])                    # main.r:127 / :129
-    return {"output_f": res["output_f"], "output_s": res["output_s"], "output_g": res["output_g"],
-            "Error": error, "All_Error": np.asarray(errs), "bisil": None,
-            "row_clusters": res["row_clusters"], "col_clusters": res["col_clusters"],
-            "lambda": [lam_mu.get(v, (None, None))[0] for v in range(n_v)], "mu": [lam_mu.get(v, (None, None))[1] for v in range(n_v)]}
+    return inner_result(res["output_f"], res["output_s"], res["output_g"], np.asarray(errs), n_iters,
+                        row_clusters=res["row_clusters"], col_clusters=res["col_clusters"],
+                        lam=[lam_mu.get(v, (None, None))[0] for v in range(n_v)],
+                        mu=[lam_mu.get(v, (None, None))[1] for v in range(n_v)])

@@ -14,7 +14,7 @@ The loops the reference writes in R stay in R's order; DESIGN.md section 11.
 
 Inside the pipeline (the opt-in ``spurious_on_device=True`` of ``res_nmtf_inner``, ``stability_check`` and
 ``apply_resnmtf``) the same check runs on a live engine instead (``check_on_device``): the shuffles are drawn from the
-engine's own device copy (``batched.shuffled_engines``) and ``resnmtf_spurious_scores`` gathers and scores the pool on
+engine's own device copy (``problem.shuffled_engines``) and ``resnmtf_spurious_scores`` gathers and scores the pool on
 the device; only the K scores and the null scores come back for ``thresholds``.
 """
 from __future__ import annotations
@@ -25,6 +25,8 @@ from typing import Callable, Optional
 import numpy as np
 
 from . import sparse
+from .engine import jsd_pairs
+from .problem import shuffled_engines
 
 
 # ---------------------------------------------------------------------------------------------
@@ -156,22 +158,20 @@ def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int
             raise ValueError(f"output_f[{i}] must be {views[i].shape[0]} x {K}")
         if f.shape[0] < 2:
             raise ValueError("views need at least 2 rows (bw.nrd0 needs two data points)")
-    if K * K * R * (R - 1) // 2 < 2:
-        raise ValueError("a single null score (K = 1, num_repeats = 2): stats::density needs two")
+    _check_null_count(K, R)
     _check_factors(output_f, "output_f")
-    if shuffled_f is None and grouped:
-        from . import batched
-        reps = batched.run_jobs_grouped(batched.shuffled_jobs(views, K, R, seed=0 if seed is None else int(seed)),
-                                        device_id=device_id, pre_processed=False, max_iters=max_iters)
-        shuffled_f = [rep["output_f"] for rep in reps]
     if shuffled_f is None:
-        from . import batched
-        dev = batched.DeviceData(views, device_id=device_id, pre_processed=True)
-        try:
-            reps = batched.shuffles_on_device(dev, K, R, n_iters=None, seed=0 if seed is None else int(seed), group=group,
-                                              max_iters=max_iters)
-        finally:
-            dev.close()
+        from . import batched      # (lazy: batched imports this module at its top for check_on_device and the removal)
+        seed = 0 if seed is None else int(seed)
+        if grouped:
+            reps = batched.run_jobs_grouped(batched.shuffled_jobs(views, K, R, seed=seed), device_id=device_id,
+                                            pre_processed=False, max_iters=max_iters)
+        else:
+            dev = batched.DeviceData(views, device_id=device_id, pre_processed=True)
+            try:
+                reps = batched.shuffles_on_device(dev, K, R, n_iters=None, seed=seed, group=group, max_iters=max_iters)
+            finally:
+                dev.close()
         shuffled_f = [rep["output_f"] for rep in reps]
     if len(shuffled_f) != R or any(len(fs) != n_v for fs in shuffled_f):
         raise ValueError("shuffled_f must hold num_repeats lists of one F per view")
@@ -182,27 +182,40 @@ def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int
                 raise ValueError(f"shuffled F of view {i} must be {output_f[i].shape[0]} x {K}")
         _check_factors(fs, "a shuffled F")
     if jsd is None:
-        from .engine import jsd_pairs
         jsd = lambda cols, pairs: jsd_pairs(cols, pairs, device_id=device_id)    # noqa: E731
     null_p, score_p = pool_pairs(K, R)
-    score = np.zeros((n_v, K))
-    avg, mx = np.zeros(n_v), np.zeros(n_v)
+    rows = []
     for i in range(n_v):
         pool = np.concatenate([output_f[i]] + [fs[i] for fs in shuffled_f], axis=1)
         vals = np.asarray(jsd(pool, np.concatenate([null_p, score_p])), dtype=np.float64)
-        if not np.all(np.isfinite(vals)):
-            raise ValueError(f"view {i}: a Jensen-Shannon score is not finite (a density summed to zero; R gives NaN "
-                             "here and check_biclusters cannot continue)")
-        null, sc = vals[:len(null_p)], vals[len(null_p):]
-        avg[i], mx[i] = thresholds(null)
-        score[i] = sc.reshape(K, R * K).mean(axis=1)                              # :125-128
-    return {"score": score, "avg_threshold": avg, "max_threshold": mx}
+        rows.append(_view_check(i, vals[len(null_p):].reshape(K, R * K), vals[:len(null_p)]))
+    return _check_result(rows)
 
 
 def check_num_repeats(num_repeats) -> int:
     if isinstance(num_repeats, bool) or int(num_repeats) != num_repeats or num_repeats < 2:
         raise ValueError("num_repeats must be an integer >= 2 (the reference indexes a second shuffled repeat)")
     return int(num_repeats)
+
+
+def _check_null_count(K: int, R: int):
+    if K * K * R * (R - 1) // 2 < 2:
+        raise ValueError("a single null score (K = 1, num_repeats = 2): stats::density needs two")
+
+
+def _view_check(i: int, scores, null):
+    """View i's (score row, avg threshold, max threshold) from its null scores and its K scores -- or the K x (R K)
+    single scores they are the row means of (``:125-128``) -- all of which must be finite."""
+    scores = np.asarray(scores, dtype=np.float64)
+    if not (np.all(np.isfinite(scores)) and np.all(np.isfinite(null))):
+        raise ValueError(f"view {i}: a Jensen-Shannon score is not finite (a density summed to zero; R gives NaN "
+                         "here and check_biclusters cannot continue)")
+    return (scores if scores.ndim == 1 else scores.mean(axis=1), *thresholds(null))
+
+
+def _check_result(rows) -> dict:
+    score, avg, mx = zip(*rows)
+    return {"score": np.array(score, dtype=np.float64), "avg_threshold": np.array(avg), "max_threshold": np.array(mx)}
 
 
 def thresholds(null):
@@ -214,33 +227,21 @@ def thresholds(null):
 def check_on_device(eng, num_repeats: int, seed: Optional[int] = None, *, max_iters: int = 100000,
                     device_id: int = 0) -> dict:
     """``check_biclusters`` of the factorisation an engine holds (its F on the device, as ``finalise`` normalises it)
-    against ``num_repeats`` shuffles of the engine's own views: ``batched.shuffled_engines(eng, K, num_repeats, seed)``
+    against ``num_repeats`` shuffles of the engine's own views: ``problem.shuffled_engines(eng, K, num_repeats, seed)``
     -- the draws of ``check_biclusters(data, F, num_repeats, seed=seed)`` -- scored per view by
     ``resnmtf_spurious_scores``; the thresholds on the host.  Bitwise ``check_biclusters``' result for the same data,
     F and seed.  Returns ``{"score", "avg_threshold", "max_threshold"}``."""
-    from . import batched
-    R = check_num_repeats(num_repeats)
     n_v, K = eng.n_views, eng.k[0]
+    R = check_num_repeats(num_repeats)
     if any(k != K for k in eng.k):
         raise ValueError("every view needs the same k (the reference's k_vec is one k repeated)")
-    if K * K * R * (R - 1) // 2 < 2:
-        raise ValueError("a single null score (K = 1, num_repeats = 2): stats::density needs two")
-    score = np.zeros((n_v, K))
-    avg, mx = np.zeros(n_v), np.zeros(n_v)
-    shuffles = batched.shuffled_engines(eng, K, R, 0 if seed is None else int(seed), max_iters=max_iters,
-                                        device_id=device_id)
+    _check_null_count(K, R)
+    shuffles = shuffled_engines(eng, K, R, 0 if seed is None else int(seed), max_iters=max_iters, device_id=device_id)
     try:
-        for i in range(n_v):
-            sc, null = eng.spurious_scores(i, shuffles)
-            if not (np.all(np.isfinite(sc)) and np.all(np.isfinite(null))):
-                raise ValueError(f"view {i}: a Jensen-Shannon score is not finite (a density summed to zero; R gives NaN "
-                                 "here and check_biclusters cannot continue)")
-            avg[i], mx[i] = thresholds(null)
-            score[i] = sc
+        return _check_result([_view_check(i, *eng.spurious_scores(i, shuffles)) for i in range(n_v)])
     finally:
         for sh in shuffles:
             sh.close()
-    return {"score": score, "avg_threshold": avg, "max_threshold": mx}
 
 
 def removal_flags(check: dict) -> np.ndarray:

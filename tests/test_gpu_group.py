@@ -10,6 +10,7 @@ import helpers
 from oracle import resnmtf_oracle as O
 from resnmtf_amd import _lib, api, batched, naming, spurious
 from resnmtf_amd.engine import group_run
+from resnmtf_amd.problem import pair_table
 
 pytestmark = pytest.mark.gpu
 
@@ -17,12 +18,7 @@ FIX_F, FIX_ERR, CONV_F = 1e-11, 1e-13, 1e-8
 
 
 def _problem(prob, n_iters):
-    n_v = len(prob.data)
-    rs, cs = naming.shared_names(prob.row_names), naming.shared_names(prob.col_names)
-    rp = [[None if v == w else naming.index_pairs(prob.row_names[v], prob.row_names[w], rs[v].get(w)) for w in range(n_v)]
-          for v in range(n_v)]
-    cp = [[None if v == w else naming.index_pairs(prob.col_names[v], prob.col_names[w], cs[v].get(w)) for w in range(n_v)]
-          for v in range(n_v)]
+    rp, cp = pair_table(prob.row_names), pair_table(prob.col_names)
     return {"data": prob.data, "k": prob.init_f[0].shape[1], "init_f": prob.init_f, "init_s": prob.init_s,
             "init_g": prob.init_g, "phi": prob.phi, "xi": prob.xi, "psi": prob.psi, "row_pairs": rp, "col_pairs": cp,
             "n_iters": n_iters}

@@ -251,8 +251,8 @@ def test_full_size_c2_properties():
 
 def _engine_for(prob, **opts):
     """Engine loaded with a (possibly multi-view, coupled) problem -- the C-ABI call sequence of api.py."""
-    from resnmtf_amd import naming
     from resnmtf_amd.engine import Engine
+    from resnmtf_amd.problem import couple
     shapes = [x.shape for x in prob.data]
     n_v = len(shapes)
     e = Engine([s[0] for s in shapes], [s[1] for s in shapes], [prob.k] * n_v, **opts)
@@ -260,12 +260,7 @@ def _engine_for(prob, **opts):
         e.set_view(v, prob.data[v])
         e.set_factors(v, prob.init_f[v], prob.init_s[v], prob.init_g[v])
     e.set_restrictions(prob.phi, prob.xi, prob.psi)
-    rs, cs = naming.shared_names(prob.row_names), naming.shared_names(prob.col_names)
-    for v in range(n_v):
-        for w in range(n_v):
-            if v != w:
-                e.set_shared_rows(v, w, *naming.index_pairs(prob.row_names[v], prob.row_names[w], rs[v].get(w)))
-                e.set_shared_cols(v, w, *naming.index_pairs(prob.col_names[v], prob.col_names[w], cs[v].get(w)))
+    couple(e, prob.row_names, prob.col_names)
     return e
 
 

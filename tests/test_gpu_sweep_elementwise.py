@@ -21,8 +21,9 @@ import pytest
 import scipy.sparse as sp
 
 from helpers import coupled_problem
-from resnmtf_amd import naming, synth
+from resnmtf_amd import synth
 from resnmtf_amd.engine import Engine
+from resnmtf_amd.problem import couple
 from sweep_ref import fp16_split, half_image, rel_stat, step_reference, stream_image
 from test_gpu_sparse import sparsify
 
@@ -212,12 +213,7 @@ def _engine(prob, sparse_views, opts):
             e.set_view(v, prob.data[v])
         e.set_factors(v, prob.init_f[v], prob.init_s[v], prob.init_g[v])
     e.set_restrictions(prob.phi, prob.xi, prob.psi)
-    rs, cs = naming.shared_names(prob.row_names), naming.shared_names(prob.col_names)
-    for v in range(n_v):
-        for w in range(n_v):
-            if v != w:
-                e.set_shared_rows(v, w, *naming.index_pairs(prob.row_names[v], prob.row_names[w], rs[v].get(w)))
-                e.set_shared_cols(v, w, *naming.index_pairs(prob.col_names[v], prob.col_names[w], cs[v].get(w)))
+    couple(e, prob.row_names, prob.col_names)
     return e
 
 

@@ -5,10 +5,11 @@ import argparse, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
-from resnmtf_amd import naming, synth, _lib
+from resnmtf_amd import synth, _lib
 if os.environ.get("LIB"):
     _lib.LIB_PATH = os.environ["LIB"]
 from resnmtf_amd.engine import Engine
+from resnmtf_amd.problem import couple
 
 ap = argparse.ArgumentParser()
 ap.add_argument("configs", nargs="*", default=["c2", "c3", "c4v1", "c5v1"])
@@ -37,12 +38,7 @@ for name in a.configs:
         for v in range(V):
             e.set_view(v, prob.data[v]); e.set_factors(v, prob.init_f[v], prob.init_s[v], prob.init_g[v])
         e.set_restrictions(prob.phi, prob.xi, prob.psi)
-        rs, cs = naming.shared_names(prob.row_names), naming.shared_names(prob.col_names)
-        for v in range(V):
-            for w in range(V):
-                if v != w:
-                    e.set_shared_rows(v, w, *naming.index_pairs(prob.row_names[v], prob.row_names[w], rs[v].get(w)))
-                    e.set_shared_cols(v, w, *naming.index_pairs(prob.col_names[v], prob.col_names[w], cs[v].get(w)))
+        couple(e, prob.row_names, prob.col_names)
         return e
     e = mk(); e.run(5)
     dt = 1e9

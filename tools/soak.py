@@ -10,8 +10,9 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import psutil  # noqa: E402
 import torch  # noqa: E402
-from resnmtf_amd import naming, synth  # noqa: E402
+from resnmtf_amd import synth  # noqa: E402
 from resnmtf_amd.engine import Engine  # noqa: E402
+from resnmtf_amd.problem import couple  # noqa: E402
 
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 probs = [synth.make_problem([(3000, 700)], 16), synth.make_problem([(1200, 500)] * 3, 40, phi=2.0, psi=1.0, xi=0.5)]
@@ -29,12 +30,7 @@ for it in range(rounds + 2):
         e.set_view(v, prob.data[v]); e.set_factors(v, prob.init_f[v], prob.init_s[v], prob.init_g[v])
     e.set_restrictions(prob.phi, prob.xi, prob.psi)
     if V > 1:
-        rs, cs = naming.shared_names(prob.row_names), naming.shared_names(prob.col_names)
-        for v in range(V):
-            for w in range(V):
-                if v != w:
-                    e.set_shared_rows(v, w, *naming.index_pairs(prob.row_names[v], prob.row_names[w], rs[v].get(w)))
-                    e.set_shared_cols(v, w, *naming.index_pairs(prob.col_names[v], prob.col_names[w], cs[v].get(w)))
+        couple(e, prob.row_names, prob.col_names)
     errs = e.run(37 + it)                                   # a different run length every time (graph cache)
     assert np.isfinite(errs).all()
     errs = e.run(n_iters=None, tol=1e-7, max_iters=300)     # convergence mode

@@ -24,6 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from resnmtf_amd import api, batched, naming, synth  # noqa: E402
 from resnmtf_amd.engine import group_run  # noqa: E402
+from resnmtf_amd.problem import pair_table  # noqa: E402
 
 
 def planted():
@@ -76,12 +77,9 @@ def planted_problem(n_iters):
     data = naming.check_data(planted())
     init = api.svd_init(data, [3, 3], 3)
     rn, cn = naming.give_names(data)
-    rs, cs = naming.shared_names(rn), naming.shared_names(cn)
-    pairs = lambda names, sh: [[None if v == w else naming.index_pairs(names[v], names[w], sh[v].get(w)) for w in range(2)]  # noqa: E731
-                               for v in range(2)]
     return {"data": data, "k": 3, "init_f": init[0], "init_s": init[1], "init_g": init[2], "init_lam": init[3],
             "init_mu": init[4], "phi": np.zeros((2, 2)), "xi": np.zeros((2, 2)), "psi": np.zeros((2, 2)),
-            "row_pairs": pairs(rn, rs), "col_pairs": pairs(cn, cs), "n_iters": n_iters}
+            "row_pairs": pair_table(rn), "col_pairs": pair_table(cn), "n_iters": n_iters}
 
 
 def throughput(quick):

@@ -6,7 +6,7 @@ toy: the reference test's problem (test-resnmtf.R:38-52, two 180 x 180 views wit
 ``apply_resnmtf(data, k_sweep=True, spurious_on_device=True)`` -- k sweep 3..8, 5 shuffled repeats per k, 5 stability
 draws, each with its own 5 shuffles.  c2: one 10000 x 2000 view (synth.config("c2")), ``apply_resnmtf(data, k_val=16,
 spurious_on_device=True)``.  Each is run once to warm up, then timed end to end (host pre-processing included).  The
-share of the shuffled factorisations is the time spent in ``batched.shuffled_engines`` (draws, SVD inits and the loops
+share of the shuffled factorisations is the time spent in ``problem.shuffled_engines`` (draws, SVD inits and the loops
 to convergence; blocking), the scoring share the time in ``Engine.spurious_scores``.  Prints one JSON line per run."""
 from __future__ import annotations
 
@@ -21,14 +21,14 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import resnmtf_amd  # noqa: E402
-from resnmtf_amd import batched, synth  # noqa: E402
+from resnmtf_amd import problem, spurious, synth  # noqa: E402
 from resnmtf_amd.engine import Engine  # noqa: E402
 
 _T = {"shuffles": 0.0, "shuffle_fits": 0, "scores": 0.0, "score_calls": 0}
 
 
 def _wrap():
-    inner_sh, inner_sc = batched.shuffled_engines, Engine.spurious_scores
+    inner_sh, inner_sc = problem.shuffled_engines, Engine.spurious_scores
 
     def shuffled_engines(src, k, num_repeats, *a, **kw):
         t = time.perf_counter()
@@ -44,7 +44,7 @@ def _wrap():
         _T["score_calls"] += 1
         return out
 
-    batched.shuffled_engines = shuffled_engines
+    spurious.shuffled_engines = shuffled_engines          # (the name check_on_device calls)
     Engine.spurious_scores = spurious_scores
 
 
