@@ -253,6 +253,8 @@ int resnmtf_destroy(resnmtf_handle* h);
  * dense path's; hand-off mode A at every k; x_half, fuse_updates and the view-sharded layouts (replicate_f / replicate_gs /
  * slice_chains / slice_p2p: refused) never apply.  resnmtf_get_view, resnmtf_copy_view, resnmtf_shuffle_view and
  * resnmtf_subsample_view refuse a sparse view (RESNMTF_ERR_INVALID) instead of densifying it.
+ * resnmtf_bisil refuses one too (RESNMTF_ERR_STATE: it reads the fp32 images); resnmtf_bisil_sparse scores it from the
+ * CSC / CSR copies.
  * Replaces: as resnmtf_create (R/main.r:38-48) for views that R holds as Matrix::dgCMatrix (R/utils.r:416-419 densifies
  * them with as.matrix; the result is defined as the factorisation of that dense matrix).
  */
@@ -489,10 +491,26 @@ int resnmtf_spurious_scores(resnmtf_handle* h, int v, resnmtf_handle* const* shu
  * The data are the view's fp32 device image (no upload); distances, sums, a, b and s are fp64, every sum in an order
  * fixed by the shapes and clusters (no atomics): bitwise reproducible.  Blocking.  Refused before any launch: NULL
  * pointers, a bad view, k outside [1, 64], entries other than 0 / 1, an unknown metric (RESNMTF_ERR_INVALID); a sparse
- * view, a view without data on this handle (RESNMTF_ERR_STATE).  DESIGN.md section 13.
+ * view (resnmtf_bisil_sparse takes those), a view without data on this handle (RESNMTF_ERR_STATE).  DESIGN.md section 13.
  */
 int resnmtf_bisil(resnmtf_handle* h, int v, int k, const double* row_clusters, const double* col_clusters, int metric,
                   double* row_sil, double* col_sil);
+/*
+ * resnmtf_bisil for a SPARSE view (resnmtf_create_sparse + resnmtf_set_view_csc): the same arguments, outputs,
+ * definition and determinism promise, hence the same R lines (bisilhouette::bisilhouette on as.matrix of the view,
+ * R/obtain_bicl.r:189-199, R/utils.r:416-419).  No dense image is built: for one side of one bicluster the restricted
+ * block G[f][u] = X(U[u], J_l[f]) (features x members of the active biclusters, fp32) is zero-filled and the stored
+ * entries of its feature lines are written into it -- columns from the CSC copy for the row side, rows from the CSR copy
+ * for the column side -- and the norm, distance and epilogue kernels of resnmtf_bisil run on it.  row_sil / col_sil are
+ * bitwise equal to resnmtf_bisil on a dense view that holds the same fp32 values (both uploaded pre-processed); no
+ * atomics, two calls give equal bits.  The workspace is sized before it is allocated: the largest block is
+ * max_l |J_l| x |U| floats per side, at most one padded dense image; one that exceeds the device's free memory is
+ * refused with RESNMTF_ERR_ALLOC and the bytes asked for in resnmtf_last_error.  Refused as resnmtf_bisil refuses, with
+ * the same codes; a DENSE view (RESNMTF_ERR_STATE: use resnmtf_bisil), a view without data (RESNMTF_ERR_STATE).
+ * DESIGN.md section 13.
+ */
+int resnmtf_bisil_sparse(resnmtf_handle* h, int v, int k, const double* row_clusters, const double* col_clusters,
+                         int metric, double* row_sil, double* col_sil);
 
 /*
  * Many small factorisations in one launch (the k sweep, the shuffled fits of obtain_shuffled_f, the sub-sample fits of

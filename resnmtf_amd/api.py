@@ -18,8 +18,10 @@ copy and scored on the device (``spurious.check_on_device``).  Without the opt-i
 
 The bisilhouette score (``bisil``, ``R/obtain_bicl.r:189-199``) is an opt-in here: ``res_nmtf_inner(score_bisil=True)``
 scores the result on the device (per-member silhouettes from ``resnmtf_bisil``, combined by ``bisil.py``), and
-``apply_resnmtf(k_val=None, k_sweep=True)`` runs the reference's k sweep on it (``R/main.r:269-334``).  Its definition
-restates the published score (the R package's source is not available): parity with ``bisilhouette`` is unpinned.
+``apply_resnmtf(k_val=None, k_sweep=True)`` runs the reference's k sweep on it (``R/main.r:269-334``).  Sparse views
+are scored only with the further opt-in ``bisil_sparse=True`` (``resnmtf_bisil_sparse``, from the CSC / CSR copies).
+Its definition restates the published score (the R package's source is not available): parity with ``bisilhouette`` is
+unpinned.
 Without the opt-ins ``bisil`` stays ``None`` and ``k_val=None`` raises ``NotImplementedError``, as before.
 """
 from __future__ import annotations
@@ -75,7 +77,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
                    no_clusts=False, *, row_names=None, col_names=None, device_id: int = 0,
                    max_iters: int = 100000, seed: Optional[int] = None, engine_opts: Optional[dict] = None,
                    host_init: bool = False, return_init: bool = False, score_bisil: bool = False,
-                   spurious_on_device: bool = False):
+                   spurious_on_device: bool = False, bisil_sparse: bool = False):
     """``res_nmtf_inner`` (``R/main.r:32-140``).
 
     ``data``: list of pre-processed (non-negative, column-normalised) matrices; ``row_indices[v][w]``
@@ -89,7 +91,10 @@ def res_nmtf_inner(data, row_indices, column_indices,
     on the host as the reference's ``svd()``, seconds to minutes -- statistically equivalent),
     ``return_init`` (adds ``"init"``: the (F, S, G, lambda, mu) per view the loop started from), ``score_bisil``
     (``"bisil"`` holds the bisilhouette score of the result under ``distance``, computed on the device before the
-    engine closes, ``bisil.score``; dense views only; default ``None`` as before), ``spurious_on_device`` (with
+    engine closes, ``bisil.score``; dense views only unless ``bisil_sparse``; default ``None`` as before),
+    ``bisil_sparse`` (opt-in: ``score_bisil`` then scores sparse views too, from their CSC / CSR copies on the device,
+    ``Engine.bisil_sparse`` -- bitwise the score of the densified view; no effect on dense views),
+    ``spurious_on_device`` (with
     ``spurious=True``: ``obtain_biclusters(remove_spurious = TRUE)``, ``R/obtain_bicl.r:151-204`` -- ``num_repeats``
     shuffles of the engine's own views, to convergence, scored on the device, the flagged cluster columns zeroed through
     ``relations``, then ``bisil`` of the cleaned clusters; the result carries ``"spurious"`` as ``remove_spurious``
@@ -118,7 +123,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
     for v in range(n_v):
         if is_sp[v]:
             sparse.validate(data[v], f"view {v}")
-    if score_bisil and any(is_sp):
+    if score_bisil and any(is_sp) and not bisil_sparse:
         raise NotImplementedError("the bisilhouette score of sparse views is not supported (dense views only)")
     if any(is_sp) and host_init and (init_f is None or init_g is None or init_s is None):
         raise NotImplementedError("host_init=True (NumPy's dense SVD) is not available for sparse views; the device "
@@ -146,7 +151,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
             list(x) for x in zip(*[(*eng.finalise(v), *eng.get_factors(v)[3:]) for v in range(n_v)]))
         check = (_spurious.check_on_device(eng, num_repeats, seed, max_iters=max_iters, device_id=device_id)
                  if remove else None)                                                             # obtain_bicl.r:151-188
-        score_fn = ((lambda rc, cc: bisil.score(rc, cc, distance, engine=eng))
+        score_fn = ((lambda rc, cc: bisil.score(rc, cc, distance, engine=eng, sparse_views=bisil_sparse))
                     if score_bisil and not no_clusts else None)                                   # obtain_bicl.r:189-199
         cleaned = _remove_then_score({"output_s": out_s, "row_clusters": row_cl, "col_clusters": col_cl}, check, score_fn)
     finally:
@@ -289,7 +294,7 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                   remove_unstable=True, use_parallel=True, *, row_names=None, col_names=None,
                   device_id: int = 0, max_iters: int = 100000, seed: Optional[int] = None,
                   k_sweep: bool = False, return_sweep: bool = False, sweep_runner: Optional[Callable] = None,
-                  spurious_on_device: bool = False):
+                  spurious_on_device: bool = False, bisil_sparse: bool = False):
     """``apply_resnmtf`` (``R/main.r:214-335``) for a known ``k_val``: naming, shared-name maps, restriction
     symmetrisation, non-negativity shift and column normalisation on the host, then the device loop and -- with
     ``stability=True`` (the default) and ``spurious=False`` -- ``stability_check`` on the pre-processed data, as
@@ -310,7 +315,12 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     ``spurious_on_device=True`` (keyword-only opt-in) lets ``spurious=True`` run: ``res_nmtf_inner(spurious=True,
     spurious_on_device=True)`` for the known k or for every k of the sweep (ranked by the bisilhouette of the cleaned
     clusters), and ``stability_check`` with the removal inside its repeats.  The reference's default pipeline is
-    ``apply_resnmtf(data, k_sweep=True, spurious_on_device=True)``."""
+    ``apply_resnmtf(data, k_sweep=True, spurious_on_device=True)``.
+
+    ``bisil_sparse=True`` (keyword-only opt-in) lets the k sweep run on ``scipy.sparse`` views: they stay sparse on the
+    device and every k is scored from their CSC / CSR copies (``Engine.bisil_sparse``), bitwise the score of the
+    densified views; ``stability=True`` then works as it does for sparse views with a known ``k_val``.  No effect on
+    dense data; ``spurious=True`` on sparse views stays refused (device shuffles of sparse views are not supported)."""
     data = _views(data)
     n_v = len(data)
     if k_val is None and k_sweep:
@@ -318,7 +328,7 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                               num_repeats, no_clusts, sample_rate, n_stability, stability, stab_thres, remove_unstable,
                               row_names=row_names, col_names=col_names, device_id=device_id, max_iters=max_iters,
                               seed=seed, return_sweep=return_sweep, sweep_runner=sweep_runner,
-                              spurious_on_device=spurious_on_device)
+                              spurious_on_device=spurious_on_device, bisil_sparse=bisil_sparse)
     if k_val is None:
         raise NotImplementedError("the k sweep (R/main.r:279-321) needs the bisilhouette score, which is "
                                   "outside the accelerated path; pass k_val")
@@ -378,7 +388,7 @@ def _sweep(run: Callable, k_min: int, k_max: int, cap: int, initial: Optional[li
 
 def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k_max, distance, spurious, num_repeats,
                    no_clusts, sample_rate, n_stability, stability, stab_thres, remove_unstable, *, row_names, col_names,
-                   device_id, max_iters, seed, return_sweep, sweep_runner, spurious_on_device=False):
+                   device_id, max_iters, seed, return_sweep, sweep_runner, spurious_on_device=False, bisil_sparse=False):
     """``apply_resnmtf`` with ``k_val = NULL`` (``R/main.r:269-334``); see ``apply_resnmtf``."""
     n_v = len(data)
     _check_common(n_iters, num_repeats, n_stability, distance, sample_rate, stab_thres)
@@ -394,8 +404,12 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
     if no_clusts:
         raise ValueError("the k sweep ranks the biclusters by their bisilhouette score: no_clusts=True has none")
     if any(sparse.is_sparse(d) for d in data):
-        raise NotImplementedError("the k sweep scores with the bisilhouette, which is not supported for sparse views "
-                                  "(dense views only); pass k_val")
+        if not bisil_sparse:
+            raise NotImplementedError("the k sweep scores with the bisilhouette, which is not supported for sparse views "
+                                      "(dense views only); pass k_val")
+        if spurious_repeats:
+            raise NotImplementedError("spurious-bicluster removal needs shuffled views: device shuffles of sparse views "
+                                      "are not supported")
     if init_f is not None or init_s is not None or init_g is not None:
         raise NotImplementedError("the k sweep starts every k from the device's SVD initialisation; explicit initial "
                                   "factors are not supported with k_val=None")
@@ -413,7 +427,8 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
             def scored(r):                                  # a res_nmtf_inner result with its bisil (main.r:131-139)
                 cleaned = _remove_then_score({key: r[key] for key in ("output_s", "row_clusters", "col_clusters")},
                                              r.get("spurious_check"),
-                                             lambda rc, cc: bisil.score(rc, cc, distance, engine=dev.base))
+                                             lambda rc, cc: bisil.score(rc, cc, distance, engine=dev.base,
+                                                                        sparse_views=bisil_sparse))
                 return inner_result(r["output_f"], r["output_s"], r["output_g"], r["All_Error"], n_iters,
                                     bisil=cleaned["bisil"], row_clusters=cleaned["row_clusters"],
                                     col_clusters=cleaned["col_clusters"], lam=r["lambda"], mu=r["mu"],

@@ -1,10 +1,11 @@
 """The bisilhouette score of a biclustering (``bisil`` in a ``res_nmtf_inner`` result, ``R/obtain_bicl.r:189-199``;
 the score the k sweep of ``apply_resnmtf`` ranks, ``R/main.r:291-312``): the host half of the definition.
 
-The per-member silhouettes come from the device (``Engine.bisil`` -> ``resnmtf_bisil``, ``csrc/resnmtf_bisil.hip.inc``);
-this module combines them.  The definition restates the published score, since the source of
-``bisilhouette::bisilhouette`` is not available: parity with the R package is unpinned.  With bicluster l = (rows I_l,
-columns J_l), active when both are non-empty:
+The per-member silhouettes come from the device (``Engine.bisil`` -> ``resnmtf_bisil``, for sparse views
+``Engine.bisil_sparse`` -> ``resnmtf_bisil_sparse``; ``csrc/resnmtf_bisil.hip.inc``); this module combines them.  The
+definition restates the published score, since the source of ``bisilhouette::bisilhouette`` is
+not available: parity with the R package is unpinned.  With bicluster l = (rows I_l, columns J_l), active when both
+are non-empty:
 
 - sigma_l = (mean of the row silhouettes over I_l + mean of the column silhouettes over J_l) / 2;
 - a view's score = the mean of sigma_l over the active biclusters, 0 with fewer than two;
@@ -46,10 +47,12 @@ def overall(view_scores: Sequence[float]) -> float:
 
 
 def score(row_clusters, col_clusters, distance: str = "euclidean", *,
-          sil: Optional[Callable] = None, engine=None) -> float:
+          sil: Optional[Callable] = None, engine=None, sparse_views: bool = False) -> float:
     """``bisil`` of a result's cluster matrices (one per view).  The silhouettes of view v come from
     ``sil(v, rc, cc, distance)`` -> ``(row_sil, col_sil)``; by default ``engine.bisil`` (an ``Engine`` that holds the
-    views' data).  ``sil`` is also the stand-in hook for tests without a device."""
+    views' data).  ``sil`` is also the stand-in hook for tests without a device.  ``sparse_views=True`` (with
+    ``engine``): a view with ``engine.sparse[v]`` goes through ``engine.bisil_sparse`` (``resnmtf_bisil_sparse``), the
+    others through ``engine.bisil``; by default every view goes through ``engine.bisil``, which refuses a sparse one."""
     if distance not in METRICS:
         raise ValueError("distance must be one of 'euclidean', 'manhattan' or 'cosine'.")
     if len(row_clusters) != len(col_clusters):
@@ -58,6 +61,9 @@ def score(row_clusters, col_clusters, distance: str = "euclidean", *,
         if engine is None:
             raise ValueError("pass engine (an Engine holding the views' data) or sil")
         sil = engine.bisil
+        if sparse_views:
+            def sil(v, rc, cc, distance):
+                return (engine.bisil_sparse if engine.sparse[v] else engine.bisil)(v, rc, cc, distance)
     scores = []
     for v, (rc, cc) in enumerate(zip(row_clusters, col_clusters)):
         rs, cs = sil(v, rc, cc, distance)

@@ -6,6 +6,9 @@
 // One side (rows, or columns with the roles swapped) of one active bicluster k is three or four launches:
 //   bisil_gather_kernel   G[f][u] = X(U[u], J_k[f]) as fp32, feature-major [|J_k|][U_pad]: U = the union of the active
 //                         biclusters' members (the only points a silhouette compares with), zero-padded to 64.
+//                         A sparse view (resnmtf_bisil_sparse) has no image: G is zero-filled and bisil_scatter_kernel
+//                         writes the stored entries of the feature lines (CSC columns / CSR rows) that fall in U --
+//                         the same fp32 values at the same places, so everything below gives the same bits.
 //   bisil_norm_kernel     (cosine) ||G[:, u]||^2 in fp64, features in ascending order.
 //   bisil_dist_kernel     one workgroup per (64 members of I_k) x (one chunk of U's 64-wide tiles): a 64 x 64 distance
 //                         tile on fp64 VALU (4 x 4 per thread over a 32-feature LDS stage), then contracted at once with
@@ -32,6 +35,27 @@ bisil_gather_kernel(const float* __restrict__ img, size_t ld, const int* __restr
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
     const int f = (int)(e / upad), u = (int)(e % upad);
     G[e] = u < n_u ? img[xidx(feat[f], pts[u], ld)] : 0.f;
+  }
+}
+
+// sparse views: G (zero-filled by the caller) [f * upad + rank[idx[e]]] = val[e] over the stored entries e of line
+// feat[f] whose point is in U (rank >= 0, the position in U; < upad).  ptr / idx / val: the CSC (row side: lines are
+// columns, idx rows) or the CSR (column side).  One wave per feature line, lanes striding its entries -- a dense line
+// among sparse ones costs its own wave len / 64 steps, not one thread len steps; indices are strictly increasing within
+// a line (checked at upload), so no two lanes write one element.
+__global__ void __launch_bounds__(BISIL_THREADS)
+bisil_scatter_kernel(const long long* __restrict__ ptr, const int* __restrict__ idx, const float* __restrict__ val,
+                     const int* __restrict__ feat, int nf, const int* __restrict__ rank, int upad, float* __restrict__ G) {
+  const int lane = threadIdx.x & 63;
+  const int waves = BISIL_THREADS / 64;
+  for (int f = blockIdx.x * waves + (threadIdx.x >> 6); f < nf; f += (int)gridDim.x * waves) {
+    const int line = feat[f];
+    const long long p1 = ptr[line + 1];
+    float* __restrict__ g = G + (size_t)f * upad;
+    for (long long e = ptr[line] + lane; e < p1; e += 64) {
+      const int r = rank[idx[e]];
+      if (r >= 0) g[r] = val[e];
+    }
   }
 }
 

@@ -3106,8 +3106,11 @@ int resnmtf_relevance_masked(resnmtf_handle* h, int v, resnmtf_handle* ref, int 
 }
 
 // ---- bisilhouette (R/obtain_bicl.r:189-199): per-member silhouettes of a view's biclusters (resnmtf_bisil.hip.inc)
-int resnmtf_bisil(resnmtf_handle* h, int v, int k, const double* row_clusters, const double* col_clusters, int metric,
-                  double* row_sil, double* col_sil) {
+namespace {
+// resnmtf_bisil (from_sparse = false: G gathered from the fp32 images) and resnmtf_bisil_sparse (true: G scattered from
+// the CSC / CSR copies); everything but the view's storage check and the build of G is common
+int bisil_impl(resnmtf_handle* h, int v, int k, const double* row_clusters, const double* col_clusters, int metric,
+               double* row_sil, double* col_sil, bool from_sparse) {
   if (int rc = check_view(h, v)) return rc;
   if (!row_clusters || !col_clusters || !row_sil || !col_sil)
     return h->fail(RESNMTF_ERR_INVALID, "row_clusters / col_clusters / row_sil / col_sil are NULL");
@@ -3115,9 +3118,11 @@ int resnmtf_bisil(resnmtf_handle* h, int v, int k, const double* row_clusters, c
   if (metric < BISIL_EUCLIDEAN || metric > BISIL_COSINE)
     return h->fail(RESNMTF_ERR_INVALID, "metric must be 0 (euclidean), 1 (manhattan) or 2 (cosine)");
   const ViewState& vs = h->views[v];
-  if (vs.sparse) return h->fail(RESNMTF_ERR_STATE, "bisil of a sparse view is not supported (no dense fp32 image)");
+  if (from_sparse && !vs.sparse) return h->fail(RESNMTF_ERR_STATE, "bisil_sparse of a dense view: use resnmtf_bisil");
+  if (!from_sparse && vs.sparse) return h->fail(RESNMTF_ERR_STATE, "bisil of a sparse view is not supported (no dense fp32 image)");
   if (!vs.owned || !vs.has_x) return h->fail(RESNMTF_ERR_STATE, "no data on this handle for the view");
-  if (!vs.X32 || !vs.Xt32) return h->fail(RESNMTF_ERR_STATE, "bisil needs the view's fp32 images (the view holds only a 2-byte image)");
+  if (!from_sparse && (!vs.X32 || !vs.Xt32))
+    return h->fail(RESNMTF_ERR_STATE, "bisil needs the view's fp32 images (the view holds only a 2-byte image)");
   const int n = vs.n, m = vs.m;
   std::vector<unsigned long long> rbits(n, 0ull), cbits(m, 0ull);
   std::vector<int> rcount(k, 0), ccount(k, 0);
@@ -3157,7 +3162,8 @@ int resnmtf_bisil(resnmtf_handle* h, int v, int k, const double* row_clusters, c
   std::fill(row_sil, row_sil + (size_t)n * k, 0.0);
   std::fill(col_sil, col_sil + (size_t)m * k, 0.0);
   if (!active) return RESNMTF_OK;
-  // sizes: G <= max over sides and biclusters of |features| x U_pad floats (<= one X image); partials of one bicluster
+  // sizes: G <= max over sides and biclusters of |features| x U_pad floats (<= one padded X image, which a sparse view
+  // never held: checked against the device's free memory below); partials of one bicluster
   size_t g_floats = 1, part_dbl = 1, upad_max = 64;
   int chunks[2][RESNMTF_MAX_K] = {}, chunk_tiles[2][RESNMTF_MAX_K] = {};
   for (int sd = 0; sd < 2; ++sd) {
@@ -3175,9 +3181,10 @@ int resnmtf_bisil(resnmtf_handle* h, int v, int k, const double* row_clusters, c
       part_dbl = std::max(part_dbl, (size_t)chunks[sd][j] * n_mem * k);
     }
   }
-  // host image of the metadata: per side [umask (u64) | upts | cnt | per active j: mpos_j | feat_j]
+  // host image of the metadata: per side [umask (u64) | upts | cnt | (sparse: rank) | per active j: mpos_j | feat_j];
+  // rank[p] = the position of point p in U or -1 (bisil_scatter_kernel)
   std::vector<unsigned long long> meta;
-  size_t off_mask[2], off_pts[2], off_cnt[2], off_mpos[2][RESNMTF_MAX_K], off_feat[2][RESNMTF_MAX_K];
+  size_t off_mask[2], off_pts[2], off_cnt[2], off_rank[2] = {0, 0}, off_mpos[2][RESNMTF_MAX_K], off_feat[2][RESNMTF_MAX_K];
   {
     std::vector<int> ints;
     auto put = [&](const std::vector<int>& a) { const size_t o = ints.size(); ints.insert(ints.end(), a.begin(), a.end()); return o; };
@@ -3185,6 +3192,11 @@ int resnmtf_bisil(resnmtf_handle* h, int v, int k, const double* row_clusters, c
       const BisilSide& s = side[sd];
       off_pts[sd] = put(s.upts);
       off_cnt[sd] = put(s.cnt);
+      if (from_sparse) {
+        std::vector<int> rank(s.n_pts, -1);
+        for (size_t u = 0; u < s.upts.size(); ++u) rank[s.upts[u]] = (int)u;
+        off_rank[sd] = put(rank);
+      }
       for (int j = 0; j < k; ++j) {
         if (!((active >> j) & 1ull)) continue;
         off_mpos[sd][j] = put(s.mpos[j]);
@@ -3199,7 +3211,7 @@ int resnmtf_bisil(resnmtf_handle* h, int v, int k, const double* row_clusters, c
     std::copy(side[1].umask.begin(), side[1].umask.end(), meta.begin() + off_mask[1]);
     std::memcpy(meta.data() + n_mask, ints.data(), ints.size() * sizeof(int));
     for (int sd = 0; sd < 2; ++sd) {      // int offsets -> offsets from the buffer's start, in ints
-      off_pts[sd] += 2 * n_mask; off_cnt[sd] += 2 * n_mask;
+      off_pts[sd] += 2 * n_mask; off_cnt[sd] += 2 * n_mask; off_rank[sd] += 2 * n_mask;
       for (int j = 0; j < k; ++j) { off_mpos[sd][j] += 2 * n_mask; off_feat[sd][j] += 2 * n_mask; }
     }
   }
@@ -3208,8 +3220,18 @@ int resnmtf_bisil(resnmtf_handle* h, int v, int k, const double* row_clusters, c
   // [G g_floats f32 (rounded to doubles)][norm2 upad_max][partial part_dbl][sil n k + m k] doubles | meta
   const size_t g_dbl = (g_floats + 1) / 2, sil_dbl = (size_t)n * k + (size_t)m * k;
   const size_t n_dbl = g_dbl + upad_max + part_dbl + sil_dbl;
+  const size_t bytes = n_dbl * sizeof(double) + meta.size() * sizeof(unsigned long long);
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
+  if (bytes > free_b)
+    return h->fail(RESNMTF_ERR_ALLOC, "bisil workspace: " + std::to_string(bytes) + " bytes asked for (" + std::to_string(g_floats * sizeof(float)) +
+                   " of them the restricted block, features x padded members), " + std::to_string(free_b) + " free on the device");
   char* buf = nullptr;
-  HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), n_dbl * sizeof(double) + meta.size() * sizeof(unsigned long long)));
+  if (hipError_t ea = hipMalloc(reinterpret_cast<void**>(&buf), bytes); ea != hipSuccess) {
+    (void)hipGetLastError();
+    return h->fail(ea == hipErrorOutOfMemory ? RESNMTF_ERR_ALLOC : RESNMTF_ERR_HIP,
+                   "bisil workspace: hipMalloc of " + std::to_string(bytes) + " bytes asked for: " + hipGetErrorString(ea));
+  }
   float* G = reinterpret_cast<float*>(buf);
   double* norm2 = reinterpret_cast<double*>(buf) + g_dbl;
   double* partial = norm2 + upad_max;
@@ -3232,8 +3254,15 @@ int resnmtf_bisil(resnmtf_handle* h, int v, int k, const double* row_clusters, c
       const int* feat = dints + off_feat[sd][j];
       const int* mpos = dints + off_mpos[sd][j];
       const size_t total = (size_t)nf * upad;
-      hipLaunchKernelGGL(bisil_gather_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0,
-                         h->stream, (const float*)img, ld, feat, nf, dints + off_pts[sd], n_u, upad, G);
+      if (!from_sparse) {
+        hipLaunchKernelGGL(bisil_gather_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0,
+                           h->stream, (const float*)img, ld, feat, nf, dints + off_pts[sd], n_u, upad, G);
+      } else {      // rows: the features are columns, their entries in the CSC; columns: rows, in the CSR
+        if ((e = hipMemsetAsync(G, 0, total * sizeof(float), h->stream)) != hipSuccess) break;
+        hipLaunchKernelGGL(bisil_scatter_kernel, dim3((unsigned)std::min(ceil_div(nf, BISIL_THREADS / 64), 65536)), dim3(BISIL_THREADS), 0,
+                           h->stream, (const long long*)(sd == 0 ? vs.cp : vs.rp), (const int*)(sd == 0 ? vs.ri : vs.ci),
+                           (const float*)(sd == 0 ? vs.vcsc : vs.vcsr), feat, nf, dints + off_rank[sd], upad, G);
+      }
       if (metric == BISIL_COSINE)
         hipLaunchKernelGGL(bisil_norm_kernel, dim3(ceil_div(upad, 256)), dim3(256), 0, h->stream, (const float*)G, nf, upad, norm2);
       const dim3 grid(ceil_div(n_mem, BISIL_TILE), chunks[sd][j]);
@@ -3250,6 +3279,17 @@ int resnmtf_bisil(resnmtf_handle* h, int v, int k, const double* row_clusters, c
   (void)hipFree(buf);
   if (e != hipSuccess) return h->fail_hip("bisil", e);
   return RESNMTF_OK;
+}
+}  // namespace
+
+int resnmtf_bisil(resnmtf_handle* h, int v, int k, const double* row_clusters, const double* col_clusters, int metric,
+                  double* row_sil, double* col_sil) {
+  return bisil_impl(h, v, k, row_clusters, col_clusters, metric, row_sil, col_sil, false);
+}
+
+int resnmtf_bisil_sparse(resnmtf_handle* h, int v, int k, const double* row_clusters, const double* col_clusters, int metric,
+                         double* row_sil, double* col_sil) {
+  return bisil_impl(h, v, k, row_clusters, col_clusters, metric, row_sil, col_sil, true);
 }
 
 int resnmtf_jsd_pairs(int device_id, int n, int n_cols, const double* cols, int n_pairs, const int* pairs, double* out) {

@@ -443,6 +443,15 @@ class Engine:
         ``bisilhouette::bisilhouette``, ``R/obtain_bicl.r:189-199``) on the view's device copy of the data: ``rc`` /
         ``cc`` are n x k and m x k 0 / 1 cluster matrices (k may differ from this engine's k[v]); returns ``(row_sil,
         col_sil)``, n x k and m x k, 0 at non-members.  ``bisil.score`` turns them into the score."""
+        return self._bisil(self._lib.resnmtf_bisil, v, rc, cc, distance)
+
+    def bisil_sparse(self, v: int, rc, cc, distance: str = "euclidean"):
+        """``bisil`` for a sparse view (``resnmtf_bisil_sparse``): the same arguments and result, computed from the
+        view's CSC / CSR copies -- bitwise what ``bisil`` returns on a dense view holding the same fp32 values.  A
+        dense view is refused (use ``bisil``)."""
+        return self._bisil(self._lib.resnmtf_bisil_sparse, v, rc, cc, distance)
+
+    def _bisil(self, entry, v: int, rc, cc, distance: str):
         from .bisil import METRICS
         if distance not in METRICS:
             raise ValueError("distance must be one of 'euclidean', 'manhattan' or 'cosine'.")
@@ -452,7 +461,7 @@ class Engine:
         cc = _f64_colmajor(cc, (self.n_cols[v], rc.shape[1]))
         k = int(rc.shape[1])
         rs = np.zeros((self.n_rows[v], k), order="F"); cs = np.zeros((self.n_cols[v], k), order="F")
-        self._check(self._lib.resnmtf_bisil(self._h, v, k, _dp(rc), _dp(cc), METRICS[distance], _dp(rs), _dp(cs)))
+        self._check(entry(self._h, v, k, _dp(rc), _dp(cc), METRICS[distance], _dp(rs), _dp(cs)))
         return rs, cs
 
     def view_image_info(self, v: int):
