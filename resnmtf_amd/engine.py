@@ -279,14 +279,17 @@ class Engine:
             raise ValueError("index counts must equal the view's shape")
         self._check(self._lib.resnmtf_subsample_view(self._h, v, other._h, v_src, _ip(rows), _ip(cols)))
 
-    def empty_lines(self, v: int):
+    def empty_lines(self, v: int, counts: bool = False):
         """(row_mask, col_mask) of view ``v``'s latest device-drawn data (shuffle / sub-sample): True where a row / column
         sums to exactly zero -- the condition of the reference's redraw (``R/obtain_bicl.r:14-18``) and of its trimming
-        of sub-samples (``R/stability_analysis.r:165-190``)."""
+        of sub-samples (``R/stability_analysis.r:165-190``).  ``counts=True``: ``(row_mask, col_mask, n_empty_rows,
+        n_empty_cols)``, the counts as the device took them."""
         nr, nc = C.c_int(0), C.c_int(0)
         rm = np.zeros(self.n_rows[v], dtype=np.uint8); cm = np.zeros(self.n_cols[v], dtype=np.uint8)
         self._check(self._lib.resnmtf_view_empty_lines(self._h, v, C.byref(nr), C.byref(nc),
                                                        rm.ctypes.data_as(C.POINTER(C.c_ubyte)), cm.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        if counts:
+            return rm.astype(bool), cm.astype(bool), int(nr.value), int(nc.value)
         return rm.astype(bool), cm.astype(bool)
 
     def get_view(self, v: int) -> np.ndarray:

@@ -37,7 +37,8 @@ BARS = {
     "f32": 1.0e-6,         # k <= 16, f32 images                    [2.8e-7, k3_plain]
     "wide": 1.5e-6,        # k > 16, three bf16 pieces per operand  [3.8e-7, k32_wide]
     "f32_mfma": 1.0e-6,    # k > 16, bf16_split = 2                 [1.5e-7, k64_f32mfma]
-    "sparse": 1.0e-6,      #                                        [1.9e-7, sparse_k8]
+    "sparse": 1.0e-6,      # [3.1e-7, sparse_scaled_counts, normalised on the device from rounded column sums: margin 3.2 x;
+                           #  integer counts 2.2e-7, sparse_counts_129x64; uploaded pre-processed 1.9e-7, sparse_k8]
     "fp16": 1.0e-6,        # (half1_u4: see FINDINGS)               [1.4e-7, half1_u2]
     "u16": 1.0e-6,         #                                        [2.8e-7, half2_u4]
 }
@@ -99,6 +100,26 @@ def sparse_one(n, m, k, density, seed, skew=False, empty=False):
     return _single(y, k, seed)
 
 
+def sparse_counts(n, m, k, density, seed, scale=None):
+    """Integer counts (every column sum above 10, asserted: dozens at 129 x 64, hundreds at 1500 x 900), uploaded raw:
+    matrix_normalisation runs on the device (csc_normalise_kernel).  ``data`` is the fp64 normalisation.  The column
+    sums of integers are exact in any order, so the device's fp64 quotient is the host's and the streamed image is its
+    f32 rounding: these cases pin the division and the gather, not the 1-ulp freedom of a rounded column sum.
+    ``scale``: every count times a factor from U(scale): the sums round, the device's (in entry order) may differ from
+    NumPy's in the last place and an entry of the image by one f32 ulp (1.2e-7, inside the "sparse" bar)."""
+    rng = np.random.default_rng(seed)
+    x = synth.planted_view(n, m, max(2, min(k, 8)), 1000 + seed, normalise=False)
+    mask = rng.random((n, m)) < density
+    mask[rng.integers(0, n, m), np.arange(m)] = True
+    counts = np.where(mask, np.floor(3.0 * x) + 1.0, 0.0)
+    assert counts.sum(axis=0).min() > 10.0
+    if scale is not None:
+        counts = counts * rng.uniform(*scale, size=(n, m))
+    prob = _single(counts / counts.sum(axis=0)[None, :], k, seed)
+    prob.raw_counts = [counts]
+    return prob
+
+
 def coupled(n_views, n, m, k, seed, same_rows=True, **w):
     """n_views views over one row set (identity row maps when same_rows: the fused F chain applies) and partly shared
     columns, phi / psi / xi couplings."""
@@ -110,6 +131,9 @@ def coupled(n_views, n, m, k, seed, same_rows=True, **w):
 # ---------------------------------------------------------------------------------------------------------------------
 # the cases: (id, problem factory, engine options, sweeps before, sparse upload)
 # ---------------------------------------------------------------------------------------------------------------------
+NORMALISE = "normalise"     # sparse upload mode: raw counts, pre_processed = 0 (any other true value: pre_processed = 1)
+
+
 def _cases():
     C = []
 
@@ -157,6 +181,11 @@ def _cases():
     add("sparse_d0.001", lambda: sparse_one(4000, 3000, 6, 0.001, 80), sparse=True)
     add("sparse_d0.5", lambda: sparse_one(800, 600, 16, 0.5, 81), sparse=True)
     add("sparse_skew_empty", lambda: sparse_one(2500, 900, 12, 0.002, 82, skew=True, empty=True), sparse=True)
+    # ... normalised on the device (pre_processed = 0) from integer counts
+    add("sparse_counts_k8", lambda: sparse_counts(1500, 900, 8, 0.05, 83), sparse=NORMALISE, before=10)
+    add("sparse_counts_k40", lambda: sparse_counts(1500, 900, 40, 0.05, 84), sparse=NORMALISE)
+    add("sparse_counts_129x64", lambda: sparse_counts(129, 64, 3, 0.3, 85), sparse=NORMALISE)
+    add("sparse_scaled_counts", lambda: sparse_counts(700, 300, 5, 0.1, 86, scale=(0.5, 3.0)), sparse=NORMALISE)
     # coupled views
     add("chain2_one_slab", lambda: coupled(2, 900, 300, 8, 90, phi_w=1.0, psi_w=0.5, xi_w=0.3), {"pass_splits_xg": 1})
     add("chain2_slabs", lambda: coupled(2, 900, 700, 8, 91, phi_w=1.0), {"pass_splits_xg": 3}, before=10)
@@ -207,7 +236,9 @@ def _engine(prob, sparse_views, opts):
     nnz = [int(sp.csc_matrix(x).nnz) for x in prob.data] if sparse_views else None
     e = Engine([s[0] for s in shapes], [s[1] for s in shapes], [prob.k] * n_v, nnz=nnz, **opts)
     for v in range(n_v):
-        if sparse_views:
+        if sparse_views == NORMALISE:
+            e.set_view_sparse(v, sp.csc_matrix(prob.raw_counts[v]), pre_processed=False)
+        elif sparse_views:
             e.set_view_sparse(v, sp.csc_matrix(prob.data[v]), pre_processed=True)
         else:
             e.set_view(v, prob.data[v])
@@ -337,7 +368,8 @@ def test_one_sweep_elementwise(cid):
     _dump()
     assert not failures, "\n".join(failures)
     assert d_err < ERR_BAR, f"error {err[-1]!r} against {np.mean(ref['err'])!r}"
-    RESULTS[cid] = {"plans": plans, "tags": _tags(prob, opts, plans, plans[0]["image"] == "sparse")}
+    assert (plans[0]["image"] == "sparse") == bool(CASES[CASE_IDS.index(cid)][4])
+    RESULTS[cid] = {"plans": plans, "tags": _tags(prob, opts, plans, CASES[CASE_IDS.index(cid)][4])}
 
 
 def _dump():
@@ -355,6 +387,8 @@ def _tags(prob, opts, plans, sparse_views):
     from resnmtf_amd import naming
     tags = set()
     n_v = len(plans)
+    if sparse_views == NORMALISE:
+        tags.add("sparse: normalised on the device")
     if opts.get("no_f_chain") and n_v > 1 and not any(p["f_chain_hoisted"] for p in plans):
         tags.add("no_f_chain: several k <= 16 views, F updates not hoisted")
     for name in ("phi", "psi", "xi"):
@@ -475,7 +509,7 @@ def test_forms_covered():
         "coupled: phi", "coupled: psi", "coupled: xi", "coupled: phi, k > 16", "coupled: psi, k > 16",
         "coupled: partial name map", "coupled: NA name map", "dense view with all-zero rows",
         "sparse: density 0.001", "sparse: density 0.5", "sparse: empty rows and columns",
-        "sparse: a row and a column far longer than the rest")}
+        "sparse: a row and a column far longer than the rest", "sparse: normalised on the device")}
     # forms the planner cannot reach from resnmtf_run on one handle, with the plan value that rules them out
     unreachable = {
         ("f_chain", 8, True): "build_chain refuses more than 4 owned views (n_owned > 4) and enqueue_sweep hoists the chain "
