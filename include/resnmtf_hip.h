@@ -350,6 +350,19 @@ int resnmtf_init_svd(resnmtf_handle* h, int v, unsigned long long seed, double s
                      double* singular_values);
 
 /*
+ * resnmtf_init_svd with a read-back of the signed basis it takes |.| of (resnmtf_init_svd is this call without the
+ * read-back: the same arithmetic, the same factors).  Column-major fp64: U receives the k leading left vectors (n x k),
+ * V the right ones (m x k), d ALL singular values the route computed, in descending order (room for 64), and *n_d their
+ * count: min(L, min(n, m)), L the sketch width.  U = Q Ut and V = X^T Q Ut / d are formed in fp64 from the sketch's
+ * last orthonormal basis Q; X^T Q is the last streaming pass (f32).  A triplet past the numerical rank of X (the rank
+ * cut of the sketch's CholeskyQR2, or an exactly zero eigenvalue) has d = 0 and zero vectors here; the factors then
+ * hold the constant unit vector in its place (svd() returns some unit vector there).
+ * U, V, d, n_d must not be NULL (RESNMTF_ERR_INVALID); singular_values may be.
+ */
+int resnmtf_init_svd_basis(resnmtf_handle* h, int v, unsigned long long seed, double sigma, int n_power,
+                           double* singular_values, double* U, double* V, double* d, int* n_d);
+
+/*
  * Restriction matrices, n_views x n_views column-major, ALREADY symmetrised with zero diagonal
  * (the output of init_rest_mats, R/update_steps.r:12-24).  NULL = all zero.
  */

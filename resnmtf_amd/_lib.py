@@ -113,6 +113,7 @@ SIGNATURES = {
     "resnmtf_get_view": (C.c_int, [_h, C.c_int, _dp]),
     "resnmtf_set_factors": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "resnmtf_init_svd": (C.c_int, [_h, C.c_int, C.c_ulonglong, C.c_double, C.c_int, _dp]),
+    "resnmtf_init_svd_basis": (C.c_int, [_h, C.c_int, C.c_ulonglong, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _ip]),
     "resnmtf_set_restrictions": (C.c_int, [_h, _dp, _dp, _dp]),
     "resnmtf_set_shared_rows": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip, _ip]),
     "resnmtf_set_shared_cols": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip, _ip]),

@@ -2002,13 +2002,18 @@ int resnmtf_set_factors(resnmtf_handle* h, int v, const double* F, const double*
 // symmetric eigenproblem are fp64, their L x L factorisations on the host.
 // ---------------------------------------------------------------------------------------------
 namespace {
-// C (L x L, row-major, symmetric positive definite) = R^T R, R upper triangular; returns false if not PD
-bool cholesky_upper(const std::vector<double>& C, int L, std::vector<double>& R) {
+// C (L x L, row-major, symmetric positive semi-definite) = R^T R, R upper triangular.  A pivot that is not above `cut`
+// marks a column that depends on the ones before it: its row of R stays zero (R[j][j] = 0) and the factorisation goes on
+// without it.  Returns the number of columns kept, -1 for a pivot that is not a number.
+int cholesky_upper(const std::vector<double>& C, int L, double cut, std::vector<double>& R) {
   R.assign((size_t)L * L, 0.0);
+  int kept = 0;
   for (int j = 0; j < L; ++j) {
     double d = C[(size_t)j * L + j];
     for (int t = 0; t < j; ++t) d -= R[(size_t)t * L + j] * R[(size_t)t * L + j];
-    if (!(d > 0.0)) return false;
+    if (d != d) return -1;
+    if (!(d > cut)) continue;
+    ++kept;
     const double rjj = std::sqrt(d);
     R[(size_t)j * L + j] = rjj;
     for (int c = j + 1; c < L; ++c) {
@@ -2017,13 +2022,16 @@ bool cholesky_upper(const std::vector<double>& C, int L, std::vector<double>& R)
       R[(size_t)j * L + c] = v / rjj;
     }
   }
-  return true;
+  return kept;
 }
+// Ri = R^-1 on the columns cholesky_upper kept; row and column j of Ri are zero for a column j it cut (Y Ri is then zero there)
 void invert_upper(const std::vector<double>& R, int L, std::vector<double>& Ri) {
   Ri.assign((size_t)L * L, 0.0);
   for (int j = 0; j < L; ++j) {
+    if (R[(size_t)j * L + j] == 0.0) continue;
     Ri[(size_t)j * L + j] = 1.0 / R[(size_t)j * L + j];
     for (int i = j - 1; i >= 0; --i) {
+      if (R[(size_t)i * L + i] == 0.0) continue;
       double v = 0.0;
       for (int t = i + 1; t <= j; ++t) v += R[(size_t)i * L + t] * Ri[(size_t)t * L + j];
       Ri[(size_t)i * L + j] = -v / R[(size_t)i * L + i];
@@ -2095,19 +2103,27 @@ int ts_apply(resnmtf_handle* h, InitScratch& sc, const double* Y, int len, int L
   HIP_TRY(h, hipStreamSynchronize(h->stream));       // M (host vector) may go out of scope
   return RESNMTF_OK;
 }
-// CholeskyQR2: Y (in `a`) -> orthonormal columns (back in `a`, `b` is scratch) + f32 operand copy
+// CholeskyQR2: Y (in `a`) -> orthonormal columns (back in `a`, `b` is scratch) + f32 operand copy.
+// Rank cut (kRankCut): a sketch of a view whose rank is below L has columns that depend on the others -- exactly so when
+// rows of X repeat or are zero, since equal rows of X give bitwise equal rows of every product.  Their pivots are the
+// ridge alone in round 0 and rounding noise in round 1, where dividing by them gave a basis that was neither orthonormal
+// nor in the range of X (or no factorisation at all).  Such a column is zeroed instead, in both rounds: it stays zero
+// through the products that follow and ends as a zero singular value with zero vectors.  A pivot above the cut takes
+// the same arithmetic as before, so a sketch of full rank keeps its bits.
+constexpr double kRankCut = 2e-14;      // times trace(C): twice the ridge of round 0, 1e4 x the rounding of a pivot
 int orthonormalise(resnmtf_handle* h, InitScratch& sc, double* a, double* b, int len, int L, float* W32, int nt) {
   std::vector<double> C, R, Ri;
   for (int round = 0; round < 2; ++round) {
     double* src = round == 0 ? a : b;
     double* dst = round == 0 ? b : a;
     if (int rc = ts_gram_host(h, sc, src, len, L, C)) return rc;
-    if (round == 0) {            // tiny ridge: random sketches of rank-deficient data stay factorable
-      double tr = 0.0;
-      for (int i = 0; i < L; ++i) tr += C[(size_t)i * L + i];
+    double tr = 0.0;
+    for (int i = 0; i < L; ++i) tr += C[(size_t)i * L + i];
+    if (round == 0)              // tiny ridge: sketches of nearly rank-deficient data stay factorable
       for (int i = 0; i < L; ++i) C[(size_t)i * L + i] += 1e-14 * tr;
-    }
-    if (!cholesky_upper(C, L, R)) return h->fail(RESNMTF_ERR_INVALID, "init_svd: sketch is rank deficient");
+    const int kept = cholesky_upper(C, L, kRankCut * tr, R);
+    if (kept < 0) return h->fail(RESNMTF_ERR_INVALID, "init_svd: the view holds entries that are not finite");
+    if (kept == 0) return h->fail(RESNMTF_ERR_INVALID, "init_svd: the view is all zero");
     invert_upper(R, L, Ri);
     if (int rc = ts_apply(h, sc, src, len, L, Ri, dst, round == 1 ? W32 : nullptr, nt)) return rc;
   }
@@ -2116,16 +2132,30 @@ int orthonormalise(resnmtf_handle* h, InitScratch& sc, double* a, double* b, int
 }  // namespace
 
 namespace {
+// the signed basis resnmtf_init_svd_basis hands back (all four pointers set, or no BasisOut at all)
+struct BasisOut { double *U, *V, *d; int* n_d; };
+
 // R/update_steps.r:93-115 on the k leading triplets: U (n x ldu), V (m x ldv) row-major, d descending.
 // Column-major outputs go through resnmtf_set_factors.
 int finish_init(resnmtf_handle* h, int v, const std::vector<double>& U, int ldu, const std::vector<double>& V, int ldv,
-                const std::vector<double>& d, double sigma, std::mt19937_64& gen, double* singular_values) {
+                const std::vector<double>& d, double sigma, std::mt19937_64& gen, double* singular_values, const BasisOut* basis) {
   const ViewState& vs = h->views[v];
   const int n = vs.n, m = vs.m, k = vs.k;
+  if (basis) {
+    for (int j = 0; j < k; ++j) {
+      for (int i = 0; i < n; ++i) basis->U[(size_t)j * n + i] = U[(size_t)i * ldu + j];
+      for (int i = 0; i < m; ++i) basis->V[(size_t)j * m + i] = V[(size_t)i * ldv + j];
+    }
+    for (size_t j = 0; j < d.size(); ++j) basis->d[j] = d[j];
+    *basis->n_d = (int)d.size();
+  }
   std::vector<double> F0((size_t)n * k), G0((size_t)m * k), S0((size_t)k * k, 0.0), cf(k, 0.0), cg(k, 0.0), lam(k, 0.0), muv(k, 0.0);
   for (int j = 0; j < k; ++j) {
     for (int i = 0; i < n; ++i) { const double a = std::fabs(U[(size_t)i * ldu + j]); F0[(size_t)j * n + i] = a; cf[j] += a; }   // :93,:100
     for (int i = 0; i < m; ++i) { const double a = std::fabs(V[(size_t)i * ldv + j]); G0[(size_t)j * m + i] = a; cg[j] += a; }   // :94,:101
+    // a zero vector (a triplet past the rank of X): svd() returns some unit vector there; the constant one stands in
+    if (cf[j] == 0.0) { for (int i = 0; i < n; ++i) F0[(size_t)j * n + i] = 1.0 / std::sqrt((double)n); cf[j] = std::sqrt((double)n); }
+    if (cg[j] == 0.0) { for (int i = 0; i < m; ++i) G0[(size_t)j * m + i] = 1.0 / std::sqrt((double)m); cg[j] = std::sqrt((double)m); }
   }
   std::normal_distribution<double> noise(0.0, std::sqrt(sigma));                    // mvrnorm(k, 0, sigma I), :96-99
   for (int j = 0; j < k; ++j)
@@ -2146,7 +2176,7 @@ int finish_init(resnmtf_handle* h, int v, const std::vector<double>& U, int ldu,
 // Thin views (min(n, m) smaller than the sketch): the exact SVD through the Gram matrix of the short
 // side -- Y = X (m <= n) or X^T, C = Y^T Y (r x r, fp64, device), Jacobi on the host, the long-side
 // vectors Y W Sigma^-1 on the device.  No random sketch, no iteration.
-int init_svd_thin(resnmtf_handle* h, int v, double sigma, std::mt19937_64& gen, double* singular_values) {
+int init_svd_thin(resnmtf_handle* h, int v, double sigma, std::mt19937_64& gen, double* singular_values, const BasisOut* basis) {
   ViewState& vs = h->views[v];
   const int n = vs.n, m = vs.m;
   const bool tall = m <= n;                       // Y = X [n][m]  or  X^T [m][n]
@@ -2185,14 +2215,12 @@ int init_svd_thin(resnmtf_handle* h, int v, double sigma, std::mt19937_64& gen, 
   std::vector<double> Lg((size_t)len * r);
   HIP_TRY(h, hipMemcpyAsync(Lg.data(), sc.Yn2, Lg.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return tall ? finish_init(h, v, Lg, r, Ws, r, d, sigma, gen, singular_values)
-              : finish_init(h, v, Ws, r, Lg, r, d, sigma, gen, singular_values);
+  return tall ? finish_init(h, v, Lg, r, Ws, r, d, sigma, gen, singular_values, basis)
+              : finish_init(h, v, Ws, r, Lg, r, d, sigma, gen, singular_values, basis);
 }
-}  // namespace
 
-int resnmtf_init_svd(resnmtf_handle* h, int v, unsigned long long seed, double sigma, int n_power,
-                     double* singular_values) {
-  if (int rc = check_view(h, v)) return rc;
+int init_svd_impl(resnmtf_handle* h, int v, unsigned long long seed, double sigma, int n_power, double* singular_values,
+                  const BasisOut* basis) {
   ViewState& vs = h->views[v];
   if (!vs.owned || !vs.has_x) return h->fail(RESNMTF_ERR_STATE, "init_svd needs an owned view with data (set_view first)");
   if (n_power < 1) n_power = 3;
@@ -2203,7 +2231,7 @@ int resnmtf_init_svd(resnmtf_handle* h, int v, unsigned long long seed, double s
   const int n = vs.n, m = vs.m, k = vs.k;
   const int L = std::min(64, 16 * ceil_div(k + 8, 16)), NTi = L / 16;
   std::mt19937_64 gen(seed);
-  if (std::min(n, m) < L) return init_svd_thin(h, v, sigma, gen, singular_values);
+  if (std::min(n, m) < L) return init_svd_thin(h, v, sigma, gen, singular_values, basis);
   InitScratch sc;
   hipError_t e;
   auto alloc = [&](double** p, size_t cnt) { return hipMalloc(reinterpret_cast<void**>(p), cnt * sizeof(double)); };
@@ -2278,7 +2306,22 @@ int resnmtf_init_svd(resnmtf_handle* h, int v, unsigned long long seed, double s
   HIP_TRY(h, hipMemcpyAsync(U.data(), sc.Yn2, U.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipMemcpyAsync(V.data(), sc.Zm2, V.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return finish_init(h, v, U, L, V, L, d, sigma, gen, singular_values);
+  return finish_init(h, v, U, L, V, L, d, sigma, gen, singular_values, basis);
+}
+}  // namespace
+
+int resnmtf_init_svd(resnmtf_handle* h, int v, unsigned long long seed, double sigma, int n_power,
+                     double* singular_values) {
+  if (int rc = check_view(h, v)) return rc;
+  return init_svd_impl(h, v, seed, sigma, n_power, singular_values, nullptr);
+}
+
+int resnmtf_init_svd_basis(resnmtf_handle* h, int v, unsigned long long seed, double sigma, int n_power,
+                           double* singular_values, double* U, double* V, double* d, int* n_d) {
+  if (int rc = check_view(h, v)) return rc;
+  if (!U || !V || !d || !n_d) return h->fail(RESNMTF_ERR_INVALID, "init_svd_basis: U, V, d and n_d must not be NULL");
+  const BasisOut basis{U, V, d, n_d};
+  return init_svd_impl(h, v, seed, sigma, n_power, singular_values, &basis);
 }
 
 int resnmtf_set_restrictions(resnmtf_handle* h, const double* phi, const double* xi, const double* psi) {

@@ -298,12 +298,20 @@ class Engine:
         self._check(self._lib.resnmtf_get_view(self._h, v, _dp(x)))
         return x
 
-    def init_svd(self, v: int, seed: int = 0, sigma: float = 0.05, n_power: int = 0) -> np.ndarray:
+    def init_svd(self, v: int, seed: int = 0, sigma: float = 0.05, n_power: int = 0, return_basis: bool = False):
         """``init_mats_inner`` (``R/update_steps.r:78-125``) on the device for view ``v`` (randomized
-        top-k SVD on the streaming-pass kernels); returns the k leading singular values."""
+        top-k SVD on the streaming-pass kernels); returns the k leading singular values.
+        ``return_basis=True`` (``resnmtf_init_svd_basis``): ``(d, U, V, d_all)`` -- the signed vectors the factors are
+        built from, n x k and m x k, and every singular value the route computed, descending; same factors."""
         d = np.zeros(self.k[v])
-        self._check(self._lib.resnmtf_init_svd(self._h, v, int(seed), float(sigma), int(n_power), _dp(d)))
-        return d
+        if not return_basis:
+            self._check(self._lib.resnmtf_init_svd(self._h, v, int(seed), float(sigma), int(n_power), _dp(d)))
+            return d
+        u = np.zeros((self.n_rows[v], self.k[v]), order="F"); w = np.zeros((self.n_cols[v], self.k[v]), order="F")
+        d_all = np.zeros(64); n_d = C.c_int(0)
+        self._check(self._lib.resnmtf_init_svd_basis(self._h, v, int(seed), float(sigma), int(n_power), _dp(d), _dp(u), _dp(w),
+                                                     _dp(d_all), C.byref(n_d)))
+        return d, u, w, d_all[:n_d.value].copy()
 
     def set_factors(self, v: int, f, s, g, lam=None, mu=None):
         k = self.k[v]
