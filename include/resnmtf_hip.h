@@ -252,7 +252,8 @@ int resnmtf_destroy(resnmtf_handle* h);
  * the same partial slabs as the dense passes, so the rest of the sweep (updates, k x k chains, error, stop test) is the
  * dense path's; hand-off mode A at every k; x_half, fuse_updates and the view-sharded layouts (replicate_f / replicate_gs /
  * slice_chains / slice_p2p: refused) never apply.  resnmtf_get_view, resnmtf_copy_view, resnmtf_shuffle_view and
- * resnmtf_subsample_view refuse a sparse view (RESNMTF_ERR_INVALID) instead of densifying it.
+ * resnmtf_subsample_view refuse a sparse view (RESNMTF_ERR_INVALID) instead of densifying it; a sparse view is shuffled
+ * by resnmtf_shuffle_view_sparse (it stays sparse) and read back by resnmtf_get_view_csc.
  * resnmtf_bisil refuses one too (RESNMTF_ERR_STATE: it reads the fp32 images); resnmtf_bisil_sparse scores it from the
  * CSC / CSR copies.
  * Replaces: as resnmtf_create (R/main.r:38-48) for views that R holds as Matrix::dgCMatrix (R/utils.r:416-419 densifies
@@ -277,6 +278,29 @@ int resnmtf_set_view_csc(resnmtf_handle* h, int v, const long long* col_ptr, con
 /* Storage of view v: *is_sparse (0 / 1), *nnz = stored entries of the last upload (0 for dense views), *nnz_capacity (-1 for
  * dense views).  Any pointer may be NULL. */
 int resnmtf_view_storage(resnmtf_handle* h, int v, int* is_sparse, long long* nnz, long long* nnz_capacity);
+/*
+ * shuffle_view (R/obtain_bicl.r:11-22) of a SPARSE view into a sparse view of another (or the same) handle, on the device:
+ * exactly resnmtf_shuffle_view's draw of the densified source -- the same Feistel permutation of the n m positions for the
+ * same `seed` -- built from the stored entries alone.  The shuffle holds the source's nnz stored entries (explicit zeros
+ * included) and no dense image is allocated at any point.  normalise != 0: matrix_normalisation (R/utils.r:86-88) of the
+ * shuffle, fp64, as apply_resnmtf applies it to shuffled data (R/obtain_bicl.r:35 -> R/utils.r:416,422; the values are
+ * non-negative, so make_non_neg shifts nothing); normalise == 0: the values as they are.  Then data_norms, the CSR copy and
+ * the work split of the passes as resnmtf_set_view_csc: the view is bit for bit the one resnmtf_set_view_csc makes of the
+ * same shuffle built on the host from the source's stored fp32 values, with pre_processed = !normalise.  The redraw
+ * condition of the reference (:14-18; a line is empty when it holds no stored entry > 0) is reported by
+ * resnmtf_view_empty_lines, as after resnmtf_shuffle_view; the caller redraws with another seed.
+ * Refused: a dense dst or src view, a shape mismatch, another device, src's nnz above dst's capacity (RESNMTF_ERR_INVALID);
+ * a view that is not owned, a source that has not been uploaded (RESNMTF_ERR_STATE).
+ */
+int resnmtf_shuffle_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src, unsigned long long seed,
+                                int normalise);
+/*
+ * The device CSC copy of a sparse view back on the host: col_ptr [m + 1], row_idx / values [nnz] (nnz from
+ * resnmtf_view_storage; values at fp32 precision) -- the @p / @i / @x slots of the dgCMatrix that R/utils.r:416-419 would
+ * densify.  Any pointer may be NULL.  A dense view is refused (RESNMTF_ERR_INVALID: resnmtf_get_view reads it); nothing is
+ * densified.
+ */
+int resnmtf_get_view_csc(resnmtf_handle* h, int v, long long* col_ptr, int* row_idx, double* values);
 
 /*
  * Upload the data matrix of an owned view: x is n x m fp64 column-major, ALREADY non-negative

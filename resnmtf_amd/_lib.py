@@ -104,6 +104,8 @@ SIGNATURES = {
     "resnmtf_create_sparse": (C.c_int, [C.c_int, _ip, _ip, _ip, _ip, C.POINTER(C.c_longlong), C.POINTER(Options), C.POINTER(_h)]),
     "resnmtf_set_view_csc": (C.c_int, [_h, C.c_int, C.POINTER(C.c_longlong), _ip, _dp, C.c_int]),
     "resnmtf_view_storage": (C.c_int, [_h, C.c_int, _ip, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "resnmtf_shuffle_view_sparse": (C.c_int, [_h, C.c_int, _h, C.c_int, C.c_ulonglong, C.c_int]),
+    "resnmtf_get_view_csc": (C.c_int, [_h, C.c_int, C.POINTER(C.c_longlong), _ip, _dp]),
     "resnmtf_set_view": (C.c_int, [_h, C.c_int, _dp]),
     "resnmtf_set_view_raw": (C.c_int, [_h, C.c_int, _dp, _ip]),
     "resnmtf_copy_view": (C.c_int, [_h, C.c_int, _h, C.c_int]),

@@ -14,7 +14,8 @@ from ``spurious.py``) and, with the keyword-only opt-in ``spurious_on_device=Tru
 the reference runs it (``spurious=True``): in ``res_nmtf_inner`` before the bisilhouette, in every stability repeat
 before its relevance and for every k of the sweep; the shuffled factorisations are drawn from the engine's own device
 copy and scored on the device (``spurious.check_on_device``).  Without the opt-in ``spurious=True`` raises
-``NotImplementedError`` as before.
+``NotImplementedError`` as before.  On ``scipy.sparse`` views the removal needs the further opt-in
+``shuffle_sparse=True``: their shuffles are drawn on the device as sparse views (``resnmtf_shuffle_view_sparse``).
 
 The bisilhouette score (``bisil``, ``R/obtain_bicl.r:189-199``) is an opt-in here: ``res_nmtf_inner(score_bisil=True)``
 scores the result on the device (per-member silhouettes from ``resnmtf_bisil``, combined by ``bisil.py``), and
@@ -77,7 +78,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
                    no_clusts=False, *, row_names=None, col_names=None, device_id: int = 0,
                    max_iters: int = 100000, seed: Optional[int] = None, engine_opts: Optional[dict] = None,
                    host_init: bool = False, return_init: bool = False, score_bisil: bool = False,
-                   spurious_on_device: bool = False, bisil_sparse: bool = False):
+                   spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False):
     """``res_nmtf_inner`` (``R/main.r:32-140``).
 
     ``data``: list of pre-processed (non-negative, column-normalised) matrices; ``row_indices[v][w]``
@@ -100,7 +101,11 @@ def res_nmtf_inner(data, row_indices, column_indices,
     ``relations``, then ``bisil`` of the cleaned clusters; the result carries ``"spurious"`` as ``remove_spurious``
     does and equals ``remove_spurious(data, res_nmtf_inner(..., spurious=False, seed=seed), num_repeats, seed=seed)``:
     the shuffles use the spurious seed ``0 if seed is None else seed``, repeat r initialising with ``+ 1000 + r`` and
-    shuffling with ``seed * 7919 + r + 1``, as ``check_biclusters`` derives them; dense views only).
+    shuffling with ``seed * 7919 + r + 1``, as ``check_biclusters`` derives them; dense views only unless
+    ``shuffle_sparse``), ``shuffle_sparse`` (opt-in: the removal then runs on sparse views too -- each is shuffled on the
+    device as a sparse view, ``Engine.shuffle_view_sparse_from``: the dense path's draw of the densified view, same seeds,
+    same redraw rule; a view with fewer stored entries than ``max(n, m)`` raises ``ValueError``, no shuffle of it can pass
+    the rule; pass the same flag to ``remove_spurious`` for the identity above; no effect on dense views).
     """
     data = _views(data)
     n_v = len(data)
@@ -117,7 +122,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
     is_sp = [sparse.is_sparse(d) for d in data]
     if remove:
         _spurious.check_num_repeats(num_repeats)
-        if any(is_sp):
+        if any(is_sp) and not shuffle_sparse:
             raise NotImplementedError("spurious-bicluster removal needs shuffled views: device shuffles of sparse views "
                                       "are not supported")
     for v in range(n_v):
@@ -149,7 +154,8 @@ def res_nmtf_inner(data, row_indices, column_indices,
         # per view: F, S, G, the binary clusters (main.r:110 + obtain_bicl.r:162-180), lambda, mu
         out_f, out_s, out_g, row_cl, col_cl, lams, mus = (
             list(x) for x in zip(*[(*eng.finalise(v), *eng.get_factors(v)[3:]) for v in range(n_v)]))
-        check = (_spurious.check_on_device(eng, num_repeats, seed, max_iters=max_iters, device_id=device_id)
+        check = (_spurious.check_on_device(eng, num_repeats, seed, max_iters=max_iters, device_id=device_id,
+                                           shuffle_sparse=shuffle_sparse)
                  if remove else None)                                                             # obtain_bicl.r:151-188
         score_fn = ((lambda rc, cc: bisil.score(rc, cc, distance, engine=eng, sparse_views=bisil_sparse))
                     if score_bisil and not no_clusts else None)                                   # obtain_bicl.r:189-199
@@ -220,7 +226,7 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
                     sample_rate=0.9, n_stability=5, stab_thres=0.6, remove_unstable=True, *,
                     row_names=None, col_names=None, device_id: int = 0, seed: Optional[int] = None, group=None,
                     max_iters: int = 100000, return_repeats: bool = False, repeat_runner: Optional[Callable] = None,
-                    spurious_on_device: bool = False):
+                    spurious_on_device: bool = False, shuffle_sparse: bool = False):
     """``stability_check`` (``R/stability_analysis.r:302-338``): ``n_stability`` factorisations of sub-samples
     (``sample_rate`` of the rows and columns, drawn and trimmed as ``stability_repeat`` does, ``:215-249``), each scored
     against ``results`` by ``relevance_results`` (``:45-67``) -- the gathers, the factorisations and the scoring run on
@@ -236,7 +242,9 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
     untouched; ``results`` is not modified).  ``spurious=True`` inside the repeats needs the opt-in
     ``spurious_on_device=True``: every repeat then removes the spurious biclusters of its own sub-sample before its
     relevance is scored (``R/stability_analysis.r:254-266``; ``batched.stability_relevance_on_device``, spurious seed
-    ``seed + 2000 + r`` for repeat r); without it, ``NotImplementedError`` as before.
+    ``seed + 2000 + r`` for repeat r); without it, ``NotImplementedError`` as before.  On sparse views the removal needs
+    the further opt-in ``shuffle_sparse=True``: the shuffles are drawn from each repeat's own sparse sub-sample handle
+    and re-normalised (``Engine.shuffle_view_sparse_from``).
     Keyword-only extras: names, ``device_id``, ``seed`` of the draws and the device SVD inits, ``group``,
     ``max_iters``; test hooks: ``return_repeats`` (adds ``"repeats"``: per repeat the trimmed draws, relevance and
     the sub-sample's own clusters -- under ``"stability"`` of a copy of the result), ``repeat_runner(r)`` (replaces
@@ -254,6 +262,9 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
         raise ValueError("n_stability must be a positive integer.")
     data = _views(data)
     n_v = len(data)
+    if spurious_repeats and repeat_runner is None and not shuffle_sparse and any(sparse.is_sparse(d) for d in data):
+        raise NotImplementedError("spurious-bicluster removal needs shuffled views: device shuffles of sparse views "
+                                  "are not supported")
     k = int(np.atleast_1d(k)[0])
     seed = _seed(seed)
     dev = None
@@ -263,7 +274,8 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
     try:
         stab = batched.stability_relevance_on_device(dev, results, k, int(n_stability), float(sample_rate), n_iters,
                                                      seed, group, max_iters, keep_clusters=return_repeats,
-                                                     runner=repeat_runner, spurious_repeats=spurious_repeats)
+                                                     runner=repeat_runner, spurious_repeats=spurious_repeats,
+                                                     shuffle_sparse=shuffle_sparse)
     finally:
         if dev is not None:
             dev.close()
@@ -294,7 +306,7 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                   remove_unstable=True, use_parallel=True, *, row_names=None, col_names=None,
                   device_id: int = 0, max_iters: int = 100000, seed: Optional[int] = None,
                   k_sweep: bool = False, return_sweep: bool = False, sweep_runner: Optional[Callable] = None,
-                  spurious_on_device: bool = False, bisil_sparse: bool = False):
+                  spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False):
     """``apply_resnmtf`` (``R/main.r:214-335``) for a known ``k_val``: naming, shared-name maps, restriction
     symmetrisation, non-negativity shift and column normalisation on the host, then the device loop and -- with
     ``stability=True`` (the default) and ``spurious=False`` -- ``stability_check`` on the pre-processed data, as
@@ -320,7 +332,14 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     ``bisil_sparse=True`` (keyword-only opt-in) lets the k sweep run on ``scipy.sparse`` views: they stay sparse on the
     device and every k is scored from their CSC / CSR copies (``Engine.bisil_sparse``), bitwise the score of the
     densified views; ``stability=True`` then works as it does for sparse views with a known ``k_val``.  No effect on
-    dense data; ``spurious=True`` on sparse views stays refused (device shuffles of sparse views are not supported)."""
+    dense data; ``spurious=True`` on sparse views stays refused (device shuffles of sparse views are not supported)
+    unless ``shuffle_sparse`` is set too.
+
+    ``shuffle_sparse=True`` (keyword-only opt-in) lets ``spurious=True`` run on ``scipy.sparse`` views: every shuffle of
+    a sparse view is drawn on the device as a sparse view (``resnmtf_shuffle_view_sparse``: the dense path's draw of
+    the densified view, DESIGN.md section 10 "Sparse shuffles"), in ``res_nmtf_inner``, for every k of the sweep and
+    inside the stability repeats.  The reference's default pipeline on sparse data is ``apply_resnmtf(data,
+    k_sweep=True, spurious_on_device=True, bisil_sparse=True, shuffle_sparse=True)``.  No effect on dense data."""
     data = _views(data)
     n_v = len(data)
     if k_val is None and k_sweep:
@@ -328,7 +347,8 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                               num_repeats, no_clusts, sample_rate, n_stability, stability, stab_thres, remove_unstable,
                               row_names=row_names, col_names=col_names, device_id=device_id, max_iters=max_iters,
                               seed=seed, return_sweep=return_sweep, sweep_runner=sweep_runner,
-                              spurious_on_device=spurious_on_device, bisil_sparse=bisil_sparse)
+                              spurious_on_device=spurious_on_device, bisil_sparse=bisil_sparse,
+                              shuffle_sparse=shuffle_sparse)
     if k_val is None:
         raise NotImplementedError("the k sweep (R/main.r:279-321) needs the bisilhouette score, which is "
                                   "outside the accelerated path; pass k_val")
@@ -347,12 +367,13 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     results = res_nmtf_inner(p.data, p.row_shared, p.col_shared, init_f, init_s, init_g, k_vec, p.phi, p.xi, p.psi,
                              n_iters, num_repeats, spurious, distance, no_clusts,
                              row_names=p.row_names, col_names=p.col_names, device_id=device_id, max_iters=max_iters,
-                             seed=seed, spurious_on_device=spurious_on_device)
+                             seed=seed, spurious_on_device=spurious_on_device, shuffle_sparse=shuffle_sparse)
     if stability:                                                                                 # main.r:255-262
         results = stability_check(p.data, results, k_vec, p.phi, p.xi, p.psi, n_iters, spurious, num_repeats,
                                   no_clusts, distance, sample_rate, n_stability, stab_thres,
                                   row_names=p.row_names, col_names=p.col_names, device_id=device_id, seed=seed,
-                                  max_iters=max_iters, spurious_on_device=spurious_on_device)
+                                  max_iters=max_iters, spurious_on_device=spurious_on_device,
+                                  shuffle_sparse=shuffle_sparse)
     return results
 
 
@@ -388,7 +409,8 @@ def _sweep(run: Callable, k_min: int, k_max: int, cap: int, initial: Optional[li
 
 def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k_max, distance, spurious, num_repeats,
                    no_clusts, sample_rate, n_stability, stability, stab_thres, remove_unstable, *, row_names, col_names,
-                   device_id, max_iters, seed, return_sweep, sweep_runner, spurious_on_device=False, bisil_sparse=False):
+                   device_id, max_iters, seed, return_sweep, sweep_runner, spurious_on_device=False, bisil_sparse=False,
+                   shuffle_sparse=False):
     """``apply_resnmtf`` with ``k_val = NULL`` (``R/main.r:269-334``); see ``apply_resnmtf``."""
     n_v = len(data)
     _check_common(n_iters, num_repeats, n_stability, distance, sample_rate, stab_thres)
@@ -407,7 +429,7 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
         if not bisil_sparse:
             raise NotImplementedError("the k sweep scores with the bisilhouette, which is not supported for sparse views "
                                       "(dense views only); pass k_val")
-        if spurious_repeats:
+        if spurious_repeats and not shuffle_sparse:
             raise NotImplementedError("spurious-bicluster removal needs shuffled views: device shuffles of sparse views "
                                       "are not supported")
     if init_f is not None or init_s is not None or init_g is not None:
@@ -438,11 +460,13 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
             # ones, R/main.r:305-309)
             def run(k):
                 return scored(dev.factorise(k, n_iters, seed + k, max_iters=max_iters, tag=f"k={k}", return_lm=True,
-                                            spurious_repeats=spurious_repeats, spurious_seed=seed + k))
+                                            spurious_repeats=spurious_repeats, spurious_seed=seed + k,
+                                            shuffle_sparse=shuffle_sparse))
 
             initial = [scored(r) for r in batched.k_sweep_on_device(dev, k_min, k_max, n_iters, seed,       # main.r:279-290
                                                                     max_iters=max_iters, return_lm=True,
-                                                                    spurious_repeats=spurious_repeats)]
+                                                                    spurious_repeats=spurious_repeats,
+                                                                    shuffle_sparse=shuffle_sparse)]
         else:
             run, initial = sweep_runner, None
         ks, scores, results, pick = _sweep(run, k_min, k_max, cap, initial)
@@ -454,7 +478,8 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
         results = stability_check(p.data, results, [ks[pick]] * n_v, p.phi, p.xi, p.psi, n_iters, spurious, num_repeats,
                                   no_clusts, distance, sample_rate, n_stability, stab_thres, remove_unstable,
                                   row_names=p.row_names, col_names=p.col_names, device_id=device_id, seed=seed,
-                                  max_iters=max_iters, spurious_on_device=spurious_on_device)
+                                  max_iters=max_iters, spurious_on_device=spurious_on_device,
+                                  shuffle_sparse=shuffle_sparse)
     if return_sweep:
         results = dict(results)
         results["k_sweep"] = {"k": ks, "bisil": scores}

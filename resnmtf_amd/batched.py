@@ -350,13 +350,15 @@ class DeviceData:
         return None
 
     @contextlib.contextmanager
-    def child(self, k: int, seed: int = 0, shuffle_seed: Optional[int] = None, samples=None):
+    def child(self, k: int, seed: int = 0, shuffle_seed: Optional[int] = None, samples=None, *, shuffle_sparse: bool = False):
         """An engine with k biclusters per view, loaded from ``self.base`` and closed on exit: the views copied -- or
         shuffled as ``obtain_shuffled_f`` does (``shuffle_seed``: no restrictions, uncoupled), or sub-sampled as
         ``stability_repeat`` does (``samples = (row_samples, col_samples)``: trimmed first, ``_trim_samples``; not
         re-normalised, names carried over) -- and SVD-initialised on the device (``problem.load_child``).  Yields
         ``Child(eng, row_names, col_names, samples, host_views)``: the names in use, the trimmed samples, what was uploaded
-        of a sparse view -- or ``None`` when the trimming fails (``R/stability_analysis.r:223-226``)."""
+        of a sparse view -- or ``None`` when the trimming fails (``R/stability_analysis.r:223-226``).  ``shuffle_sparse``
+        (opt-in): with ``shuffle_seed`` the sparse views are shuffled on the device as sparse views
+        (``resnmtf_shuffle_view_sparse``); without it they are refused."""
         n_v = len(self.data_shapes)
         shapes, rn, cn = self.data_shapes, self.rn, self.cn
         if samples is not None:
@@ -367,7 +369,7 @@ class DeviceData:
             shapes = [(len(samples[0][v]), len(samples[1][v])) for v in range(n_v)]
             rn = [[self.rn[v][t] for t in samples[0][v]] for v in range(n_v)]
             cn = [[self.cn[v][t] for t in samples[1][v]] for v in range(n_v)]
-        if shuffle_seed is not None and any(c is not None for c in self.sp):
+        if shuffle_seed is not None and any(c is not None for c in self.sp) and not shuffle_sparse:
             raise NotImplementedError("device shuffles of sparse views are not supported")
         # sparse views: the whole view or its sub-sample, gathered on the host
         host_views = [c if c is None or samples is None else sparse.subsample(c, samples[0][v], samples[1][v])[0]
@@ -375,13 +377,13 @@ class DeviceData:
         with Engine([s[0] for s in shapes], [s[1] for s in shapes], [k] * n_v, device_id=self.device_id,
                     nnz=[None if hv is None else hv.nnz for hv in host_views]) as eng:
             load_child(eng, self.base, seed, shuffle_seed=shuffle_seed, samples=samples, host_views=host_views,
-                       coupling=(self.phi, self.xi, self.psi, rn, cn))
+                       coupling=(self.phi, self.xi, self.psi, rn, cn), shuffle_sparse=shuffle_sparse)
             yield Child(eng, rn, cn, samples, host_views)
 
     def factorise(self, k: int, n_iters: Optional[int] = None, seed: int = 0, shuffle_seed: Optional[int] = None,
                   max_iters: int = 100000, tag: str = "", samples=None, return_init: bool = False,
                   return_data: bool = False, return_lm: bool = False, spurious_repeats: int = 0,
-                  spurious_seed: int = 0) -> dict:
+                  spurious_seed: int = 0, *, shuffle_sparse: bool = False) -> dict:
         """One factorisation with k biclusters per view of the views copied, shuffled (``shuffle_seed``) or sub-sampled
         (``samples``) on the device (``child``): device SVD init, loop, finalise.  With ``samples`` whose trimming
         fails: ``{"stability_performed": False, "tag"}``.
@@ -390,9 +392,13 @@ class DeviceData:
         ``return_lm`` adds ``"lambda"`` / ``"mu"`` per view (the keys of a ``res_nmtf_inner`` result, for the k sweep of
         ``apply_resnmtf``).  ``spurious_repeats`` = R >= 2: the scores of ``check_biclusters`` against R shuffles of
         this factorisation's own device copy (``spurious.check_on_device`` with ``spurious_seed``) as
-        ``"spurious_check"`` (the caller removes)."""
+        ``"spurious_check"`` (the caller removes).  ``shuffle_sparse`` (opt-in): sparse views are shuffled as sparse
+        views, by ``shuffle_seed`` and by the spurious check alike; ``return_data`` of a shuffled sparse view stays
+        refused (the host holds no copy of the shuffle: ``Engine.get_view_sparse`` reads it without densifying)."""
         n_v = len(self.data_shapes)
-        with self.child(k, seed, shuffle_seed, samples) as ch:
+        if return_data and shuffle_seed is not None and any(c is not None for c in self.sp):
+            raise NotImplementedError("return_data of a shuffled sparse view is not supported (it would densify the shuffle)")
+        with self.child(k, seed, shuffle_seed, samples, shuffle_sparse=shuffle_sparse) as ch:
             if ch is None:
                 return {"stability_performed": False, "tag": tag}
             eng = ch.eng
@@ -402,7 +408,8 @@ class DeviceData:
                           else eng.get_view(v) for v in range(n_v)] if return_data else None)
             errs = eng.run(n_iters=n_iters, tol=1.0e-6, max_iters=max_iters)
             check = (spurious.check_on_device(eng, spurious_repeats, spurious_seed, max_iters=max_iters,
-                                              device_id=self.device_id) if spurious_repeats else None)
+                                              device_id=self.device_id, shuffle_sparse=shuffle_sparse)
+                     if spurious_repeats else None)
             fin = [eng.finalise(v) for v in range(n_v)]
             lms = [eng.get_factors(v)[3:] for v in range(n_v)] if return_lm else None
         f, s, g, rc, cc = (list(x) for x in zip(*fin))
@@ -413,7 +420,8 @@ class DeviceData:
                             spurious_check=check)
 
     def stability_repeat(self, k: int, n_iters: Optional[int], seed: int, samples, max_iters: int = 100000, tag: str = "",
-                         keep_clusters: bool = False, spurious_repeats: int = 0, spurious_seed: int = 0) -> dict:
+                         keep_clusters: bool = False, spurious_repeats: int = 0, spurious_seed: int = 0, *,
+                         shuffle_sparse: bool = False) -> dict:
         """One repeat of ``stability_check`` (``R/stability_analysis.r:215-278``): the sub-sample ``samples`` factorised
         (``child``) and, instead of finalise, its clusters scored against the reference clusters set on ``self.base``
         (``resnmtf_relevance``, ``:268-276``) -- the result holds the n_views x k ``"relevance"`` matrix and no factors,
@@ -421,7 +429,8 @@ class DeviceData:
         own binary clusters (a test hook: they cost a finalise download).  ``spurious_repeats`` = R >= 2: the cluster
         columns flagged against R shuffles of the sub-sample (``spurious.check_on_device`` with ``spurious_seed``) are
         removed before the scoring (``resnmtf_relevance_masked``, ``:254-276``) and the kept clusters are the cleaned
-        ones."""
+        ones.  ``shuffle_sparse`` (opt-in): the shuffles of a sparse view are drawn from the repeat's own sparse
+        sub-sample handle (gathered on the host as before) and re-normalised, as for dense views."""
         n_v = len(self.data_shapes)
         with self.child(k, seed, samples=samples) as ch:
             if ch is None:
@@ -429,7 +438,8 @@ class DeviceData:
             eng, (rows, cols) = ch.eng, ch.samples
             errs = eng.run(n_iters=n_iters, tol=1.0e-6, max_iters=max_iters)
             check = (spurious.check_on_device(eng, spurious_repeats, spurious_seed, max_iters=max_iters,
-                                              device_id=self.device_id) if spurious_repeats else None)
+                                              device_id=self.device_id, shuffle_sparse=shuffle_sparse)
+                     if spurious_repeats else None)
             if check is None:
                 rel = [eng.relevance(v, self.base, v, rows[v], cols[v]) for v in range(n_v)]
             else:
@@ -447,23 +457,25 @@ class DeviceData:
 
 
 def k_sweep_on_device(dev: DeviceData, k_min: int = 3, k_max: int = 8, n_iters=None, seed: int = 0, group=None,
-                      max_iters: int = 100000, return_lm: bool = False, spurious_repeats: int = 0) -> List[dict]:
+                      max_iters: int = 100000, return_lm: bool = False, spurious_repeats: int = 0, *,
+                      shuffle_sparse: bool = False) -> List[dict]:
     """The factorisations of the k sweep (``R/main.r:279-290``) from one upload; sharded round-robin over
     the ranks of an initialised process group (every rank holds its own ``DeviceData``).  ``spurious_repeats``: each
     k's result carries its ``"spurious_check"`` (``DeviceData.factorise``, spurious seed ``seed + k``)."""
     ks = list(range(k_min, k_max + 1))
     return run_jobs(ks, group=group, runner=lambda k: dev.factorise(k, n_iters, seed + k, max_iters=max_iters, tag=f"k={k}",
                                                                     return_lm=return_lm, spurious_repeats=spurious_repeats,
-                                                                    spurious_seed=seed + k))
+                                                                    spurious_seed=seed + k, shuffle_sparse=shuffle_sparse))
 
 
 def shuffles_on_device(dev: DeviceData, n_clusts: int, num_repeats: int = 5, n_iters=None, seed: int = 0, group=None,
-                       max_iters: int = 100000) -> List[dict]:
-    """``obtain_shuffled_f`` (``R/obtain_bicl.r:31-42``) with the shuffles drawn on the device."""
+                       max_iters: int = 100000, *, shuffle_sparse: bool = False) -> List[dict]:
+    """``obtain_shuffled_f`` (``R/obtain_bicl.r:31-42``) with the shuffles drawn on the device (``shuffle_sparse``:
+    sparse views shuffled as sparse views, ``DeviceData.child``)."""
     reps = list(range(num_repeats))
     return run_jobs(reps, group=group,
                     runner=lambda r: dev.factorise(n_clusts, n_iters, seed + 1000 + r, shuffle_seed=seed * 7919 + r + 1,
-                                                   max_iters=max_iters, tag=f"shuffle={r}"))
+                                                   max_iters=max_iters, tag=f"shuffle={r}", shuffle_sparse=shuffle_sparse))
 
 
 def stability_on_device(dev: DeviceData, k: int, n_stability: int = 5, sample_rate: float = 0.9, n_iters=None, seed: int = 0,
@@ -512,7 +524,8 @@ def mean_relevance(repeats: Sequence[dict], n_stability: int) -> Optional[np.nda
 def stability_relevance_on_device(dev: Optional[DeviceData], results: dict, k: int, n_stability: int = 5,
                                   sample_rate: float = 0.9, n_iters=None, seed: int = 0, group=None,
                                   max_iters: int = 100000, keep_clusters: bool = False,
-                                  runner: Optional[Callable] = None, spurious_repeats: int = 0) -> dict:
+                                  runner: Optional[Callable] = None, spurious_repeats: int = 0, *,
+                                  shuffle_sparse: bool = False) -> dict:
     """The repeats of ``stability_check`` (``R/stability_analysis.r:302-334``) with their scoring on the device:
     ``results``' binary clusters are uploaded once onto ``dev.base`` (``resnmtf_set_reference_clusters``), repeat r
     factorises the sub-sample of ``stability_draws`` (trimmed as ``stability_on_device`` does) up to the end of the loop
@@ -534,7 +547,7 @@ def stability_relevance_on_device(dev: Optional[DeviceData], results: dict, k: i
         def runner(r):
             return dev.stability_repeat(k, n_iters, seed + 2000 + r, draws[r], max_iters=max_iters, tag=f"stability={r}",
                                         keep_clusters=keep_clusters, spurious_repeats=spurious_repeats,
-                                        spurious_seed=seed + 2000 + r)
+                                        spurious_seed=seed + 2000 + r, shuffle_sparse=shuffle_sparse)
     repeats = run_jobs(list(range(n_stability)), group=group, runner=runner)
     rel = mean_relevance(repeats, n_stability)
     return {"stability_performed": rel is not None, "relevance": rel, "repeats": repeats}

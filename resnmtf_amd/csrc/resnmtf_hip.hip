@@ -30,6 +30,8 @@
 #include "resnmtf_hip.h"
 #include "resnmtf_kernels.hip.inc"
 #include "resnmtf_sparse.hip.inc"
+#include <rocprim/rocprim.hpp>
+#include "resnmtf_sparse_shuffle.hip.inc"
 #include "resnmtf_jsd.hip.inc"
 #include "resnmtf_group.hip.inc"
 #include "resnmtf_bisil.hip.inc"
@@ -1746,6 +1748,41 @@ void plan_sparse(const std::vector<long long>& ptr, int lines, int groups, int n
   *nblk = nb;
 }
 int spmm_groups_host(int KP) { return KP <= 16 ? 16 : (KP <= 32 ? 8 : 4); }   // = spmm_groups (kernel side)
+
+// The tail every sparse upload shares (resnmtf_set_view_csc, resnmtf_shuffle_view_sparse): the work split of the two
+// passes planned from the host copies of the line pointers, the block lists (re)allocated and their upload enqueued on
+// the handle's stream (the caller synchronises while `pl` is alive), then -- commit_sparse_upload -- the view's state.
+struct SparsePlan {
+  std::vector<int> bxg, bxtf;
+  int ns_xg = 1, ns_xtf = 1, nb_xg = 0, nb_xtf = 0;
+};
+hipError_t upload_sparse_plan(resnmtf_handle* h, ViewState& vs, const std::vector<long long>& rp, const std::vector<long long>& cp,
+                              SparsePlan& pl) {
+  const int groups = spmm_groups_host(vs.KP);
+  plan_sparse(rp, vs.n, groups, h->n_cu, kSparseMaxSplitXg, &pl.ns_xg, &pl.nb_xg, pl.bxg);
+  plan_sparse(cp, vs.m, groups, h->n_cu, kSparseMaxSplitXtf, &pl.ns_xtf, &pl.nb_xtf, pl.bxtf);
+  hipError_t e = hipSuccess;
+  if (pl.nb_xg != vs.nblk_xg || !vs.blk_xg) {
+    if (vs.blk_xg) (void)hipFree(vs.blk_xg);
+    vs.blk_xg = nullptr;
+    e = hipMalloc(reinterpret_cast<void**>(&vs.blk_xg), pl.bxg.size() * sizeof(int));
+  }
+  if (e == hipSuccess && (pl.nb_xtf != vs.nblk_xtf || !vs.blk_xtf)) {
+    if (vs.blk_xtf) (void)hipFree(vs.blk_xtf);
+    vs.blk_xtf = nullptr;
+    e = hipMalloc(reinterpret_cast<void**>(&vs.blk_xtf), pl.bxtf.size() * sizeof(int));
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(vs.blk_xg, pl.bxg.data(), pl.bxg.size() * sizeof(int), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(vs.blk_xtf, pl.bxtf.data(), pl.bxtf.size() * sizeof(int), hipMemcpyHostToDevice, h->stream);
+  return e;
+}
+void commit_sparse_upload(resnmtf_handle* h, ViewState& vs, const SparsePlan& pl, long long nnz) {
+  vs.nnz = nnz;
+  vs.nblk_xg = pl.nb_xg; vs.nblk_xtf = pl.nb_xtf;
+  vs.nsplit_xg = pl.ns_xg; vs.nsplit_xtf = pl.ns_xtf;
+  vs.has_x = true;
+  h->prepared = false;          // the slab count of the updates follows the upload
+}
 }  // namespace
 
 int resnmtf_set_view_csc(resnmtf_handle* h, int v, const long long* col_ptr, const int* row_idx, const double* values,
@@ -1798,28 +1835,14 @@ int resnmtf_set_view_csc(resnmtf_handle* h, int v, const long long* col_ptr, con
         ci[(size_t)p] = j; perm[(size_t)p] = e;
       }
   }
-  std::vector<int> bxg, bxtf;
-  int ns_xg = 1, ns_xtf = 1, nb_xg = 0, nb_xtf = 0;
-  const int groups = spmm_groups_host(vs.KP);
-  plan_sparse(rp, n, groups, h->n_cu, kSparseMaxSplitXg, &ns_xg, &nb_xg, bxg);
-  plan_sparse(cp, m, groups, h->n_cu, kSparseMaxSplitXtf, &ns_xtf, &nb_xtf, bxtf);
   // ---- device
   double* v64 = nullptr;
   long long* dperm = nullptr;
   double* sq = nullptr;
+  SparsePlan pl;
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&v64), std::max<size_t>((size_t)nnz, 1) * sizeof(double));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dperm), std::max<size_t>((size_t)nnz, 1) * sizeof(long long));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sq), (size_t)m * sizeof(double));
-  if (e == hipSuccess && (nb_xg != vs.nblk_xg || !vs.blk_xg)) {
-    if (vs.blk_xg) (void)hipFree(vs.blk_xg);
-    vs.blk_xg = nullptr;
-    e = hipMalloc(reinterpret_cast<void**>(&vs.blk_xg), bxg.size() * sizeof(int));
-  }
-  if (e == hipSuccess && (nb_xtf != vs.nblk_xtf || !vs.blk_xtf)) {
-    if (vs.blk_xtf) (void)hipFree(vs.blk_xtf);
-    vs.blk_xtf = nullptr;
-    e = hipMalloc(reinterpret_cast<void**>(&vs.blk_xtf), bxtf.size() * sizeof(int));
-  }
   auto up = [&](void* dst, const void* src, size_t bytes) {
     if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
   };
@@ -1829,8 +1852,7 @@ int resnmtf_set_view_csc(resnmtf_handle* h, int v, const long long* col_ptr, con
   up(vs.ci, ci.data(), ci.size() * sizeof(int));
   up(v64, values, (size_t)nnz * sizeof(double));
   up(dperm, perm.data(), perm.size() * sizeof(long long));
-  up(vs.blk_xg, bxg.data(), bxg.size() * sizeof(int));
-  up(vs.blk_xtf, bxtf.data(), bxtf.size() * sizeof(int));
+  if (e == hipSuccess) e = upload_sparse_plan(h, vs, rp, cp, pl);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(csc_normalise_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, h->stream, vs.cp, v64, m, pre_processed ? 0 : 1,
                        vs.vcsc, sq);
@@ -1842,12 +1864,8 @@ int resnmtf_set_view_csc(resnmtf_handle* h, int v, const long long* col_ptr, con
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);      // (host vectors go out of scope)
   (void)hipFree(v64); (void)hipFree(dperm); (void)hipFree(sq);
   if (e != hipSuccess) return h->fail_hip("set_view_csc", e);
-  vs.nnz = nnz;
-  vs.nblk_xg = nb_xg; vs.nblk_xtf = nb_xtf;
-  vs.nsplit_xg = ns_xg; vs.nsplit_xtf = ns_xtf;
   vs.empty_rows = vs.empty_cols = 0; vs.empty_mask.clear();
-  vs.has_x = true;
-  h->prepared = false;          // the slab count of the updates follows the upload
+  commit_sparse_upload(h, vs, pl, nnz);
   return RESNMTF_OK;
 }
 
@@ -1902,6 +1920,119 @@ int resnmtf_shuffle_view(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_
   return upload_view(dst, v, nullptr, normalise != 0, nullptr, &sh);
 }
 
+// shuffle_view (R/obtain_bicl.r:11-22) of a sparse view into a sparse view: the dense path's draw (feistel_perm, same seed)
+// of the densified source, built from the stored entries alone (resnmtf_sparse_shuffle.hip.inc).  Transient device memory:
+// five 8-byte arrays of nnz (two key buffers, the fp64 values, two payload buffers) + rocPRIM's histograms.
+int resnmtf_shuffle_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src, unsigned long long seed, int normalise) {
+  if (int rc = check_view(dst, v)) return rc;
+  if (!src || v_src < 0 || v_src >= src->V) return dst->fail(RESNMTF_ERR_INVALID, "bad source handle / view");
+  ViewState& a = dst->views[v];
+  const ViewState& b = src->views[v_src];
+  if (!a.sparse) return dst->fail(RESNMTF_ERR_INVALID, "shuffle_view_sparse: the destination view is dense (resnmtf_shuffle_view shuffles dense views)");
+  if (!b.sparse) return dst->fail(RESNMTF_ERR_INVALID, "shuffle_view_sparse: the source view is dense (resnmtf_shuffle_view shuffles dense views)");
+  if (!a.owned || !b.owned) return dst->fail(RESNMTF_ERR_STATE, "shuffle_view_sparse: both views must be owned");
+  if (!b.has_x) return dst->fail(RESNMTF_ERR_STATE, "shuffle_view_sparse: the source view has not been uploaded");
+  if (a.n != b.n || a.m != b.m) return dst->fail(RESNMTF_ERR_INVALID, "shuffle_view_sparse: views differ in shape");
+  if (dst->opt.device_id != src->opt.device_id) return dst->fail(RESNMTF_ERR_INVALID, "shuffle_view_sparse: handles live on different devices");
+  if (b.nnz > a.nnz_cap)
+    return dst->fail(RESNMTF_ERR_INVALID, "shuffle_view_sparse: the source holds " + std::to_string(b.nnz) +
+                     " stored entries, above the destination's nnz capacity " + std::to_string(a.nnz_cap));
+  const int n = a.n, m = a.m;
+  const long long nnz = b.nnz;
+  dst->resume_ok = false;
+  HIP_TRY(dst, hipSetDevice(dst->opt.device_id));
+  HIP_TRY(dst, hipStreamSynchronize(src->stream));
+  if (int rc = sync_both(dst)) return rc;
+  hipStream_t st = dst->stream;
+  const size_t cnt = std::max<size_t>((size_t)nnz, 1);
+  unsigned long long* key[2] = {nullptr, nullptr};
+  long long* pay[3] = {nullptr, nullptr, nullptr};       // 8-byte payloads: the fp64 values (first sort), CSC positions (second)
+  double* sq = nullptr;
+  unsigned char* line_mask = nullptr;
+  void* tmp = nullptr;
+  std::vector<long long> cp((size_t)m + 1, 0), rp((size_t)n + 1, 0);
+  std::vector<int> line_counts(2, 0);
+  SparsePlan pl;
+  a.empty_rows = a.empty_cols = 0; a.empty_mask.assign((size_t)n + m, 1);
+  hipError_t e = hipSuccess;
+  auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
+  for (auto& p : key) alloc(reinterpret_cast<void**>(&p), cnt * sizeof(unsigned long long));
+  for (auto& p : pay) alloc(reinterpret_cast<void**>(&p), cnt * sizeof(long long));
+  alloc(reinterpret_cast<void**>(&sq), (size_t)m * sizeof(double));
+  alloc(reinterpret_cast<void**>(&line_mask), (size_t)n + m + 2 * sizeof(int) + 8);
+  const double* v64 = reinterpret_cast<const double*>(pay[0]);
+  if (e == hipSuccess && nnz == 0) {          // every line empty: zero pointers, nothing of size zero launched
+    e = hipMemsetAsync(a.cp, 0, ((size_t)m + 1) * sizeof(long long), st);
+    if (e == hipSuccess) e = hipMemsetAsync(a.rp, 0, ((size_t)n + 1) * sizeof(long long), st);
+    line_counts[0] = n; line_counts[1] = m;
+  }
+  if (e == hipSuccess && nnz > 0) {
+    const unsigned grid = (unsigned)((nnz + 255) / 256);
+    const unsigned long long count = (unsigned long long)n * m;
+    unsigned int end_bit = 1;                           // the bits of n m: every key is < count
+    while (end_bit < 64 && ((count - 1) >> end_bit) != 0) ++end_bit;
+    hipLaunchKernelGGL(sparse_shuffle_keys_kernel, dim3(grid), dim3(256), 0, st, b.cp, b.ri, b.vcsc, nnz, n, m, seed, key[0],
+                       reinterpret_cast<double*>(pay[0]));
+    e = hipGetLastError();
+    // ---- the CSC of the shuffle: the entries sorted by destination position
+    rocprim::double_buffer<unsigned long long> kb(key[0], key[1]);
+    rocprim::double_buffer<double> vb(reinterpret_cast<double*>(pay[0]), reinterpret_cast<double*>(pay[1]));
+    size_t tmp_bytes = 0, tmp_bytes2 = 0;
+    if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, kb, vb, (size_t)nnz, 0u, end_bit, st);
+    rocprim::double_buffer<unsigned long long> kb2(key[0], key[1]);
+    rocprim::double_buffer<long long> pb(pay[1], pay[2]);
+    if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, tmp_bytes2, kb2, pb, (size_t)nnz, 0u, end_bit, st);
+    tmp_bytes = std::max<size_t>(std::max(tmp_bytes, tmp_bytes2), 8);
+    alloc(&tmp, tmp_bytes);
+    if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kb, vb, (size_t)nnz, 0u, end_bit, st);
+    if (e == hipSuccess) {
+      v64 = vb.current();
+      hipLaunchKernelGGL(sorted_lines_kernel, dim3(grid), dim3(256), 0, st, kb.current(), nnz, (unsigned long long)n, m, a.cp, a.ri);
+      // ---- the CSR: the CSC positions sorted by r' m + c' (the values stay where the first sort left them)
+      kb2 = rocprim::double_buffer<unsigned long long>(kb.alternate(), kb.current());
+      pb = rocprim::double_buffer<long long>(reinterpret_cast<long long*>(vb.alternate()), pay[2]);
+      hipLaunchKernelGGL(sparse_shuffle_csr_keys_kernel, dim3(grid), dim3(256), 0, st, kb.current(), nnz, n, m, kb2.current(), pb.current());
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kb2, pb, (size_t)nnz, 0u, end_bit, st);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(sorted_lines_kernel, dim3(grid), dim3(256), 0, st, kb2.current(), nnz, (unsigned long long)m, n, a.rp, a.ci);
+      int* counts = reinterpret_cast<int*>(line_mask + (((size_t)n + m + 7) / 8) * 8);
+      e = hipMemsetAsync(counts, 0, 2 * sizeof(int), st);
+      hipLaunchKernelGGL(sparse_empty_lines_kernel, dim3(ceil_div(n + m, 256)), dim3(256), 0, st, a.cp, a.rp, pb.current(), v64, n, m,
+                         line_mask, counts);
+      if (e == hipSuccess) e = hipGetLastError();
+      if (e == hipSuccess) e = hipMemcpyAsync(a.empty_mask.data(), line_mask, (size_t)n + m, hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipMemcpyAsync(line_counts.data(), counts, 2 * sizeof(int), hipMemcpyDeviceToHost, st);
+    }
+    // ---- values: matrix_normalisation of the shuffle (fp64, ascending entry order) or the copy, data_norms, the CSR values
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(csc_normalise_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, a.cp, v64, m, normalise ? 1 : 0, a.vcsc, sq);
+      hipLaunchKernelGGL(csr_gather_kernel, dim3(grid), dim3(256), 0, st, pb.current(), a.vcsc, nnz, a.vcsr);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(cp.data(), a.cp, cp.size() * sizeof(long long), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(rp.data(), a.rp, rp.size() * sizeof(long long), hipMemcpyDeviceToHost, st);
+  } else if (e == hipSuccess) {
+    hipLaunchKernelGGL(csc_normalise_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, a.cp, v64, m, 0, a.vcsc, sq);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, st, sq, m, a.xnorm2);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);             // the line pointers are on the host: plan the passes
+  if (e == hipSuccess) e = upload_sparse_plan(dst, a, rp, cp, pl);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  for (auto p : key) (void)hipFree(p);
+  for (auto p : pay) (void)hipFree(p);
+  (void)hipFree(sq); (void)hipFree(line_mask); (void)hipFree(tmp);
+  if (e != hipSuccess) { a.empty_mask.clear(); return dst->fail_hip("shuffle_view_sparse", e); }
+  a.empty_rows = line_counts[0]; a.empty_cols = line_counts[1];
+  commit_sparse_upload(dst, a, pl, nnz);
+  return RESNMTF_OK;
+}
+
 int resnmtf_subsample_view(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src, const int* rows, const int* cols) {
   if (int rc = check_view(dst, v)) return rc;
   if (!src || v_src < 0 || v_src >= src->V) return dst->fail(RESNMTF_ERR_INVALID, "bad source handle / view");
@@ -1950,6 +2081,24 @@ int resnmtf_get_view(resnmtf_handle* h, int v, double* x) {
   HIP_TRY(h, hipMemcpy(t.data(), vs.Xt32, t.size() * sizeof(float), hipMemcpyDeviceToHost));
   for (int c = 0; c < vs.m; ++c)
     for (int r = 0; r < vs.n; ++r) x[(size_t)c * vs.n + r] = (double)t[xidx(c, r, vs.ldxt)];
+  return RESNMTF_OK;
+}
+
+// the device CSC copy of a sparse view back on the host (sizes from resnmtf_view_storage); never densifies
+int resnmtf_get_view_csc(resnmtf_handle* h, int v, long long* col_ptr, int* row_idx, double* values) {
+  if (int rc = check_view(h, v)) return rc;
+  const ViewState& vs = h->views[v];
+  if (!vs.sparse) return h->fail(RESNMTF_ERR_INVALID, "get_view_csc of a dense view: read it with resnmtf_get_view");
+  if (!vs.owned || !vs.has_x) return h->fail(RESNMTF_ERR_STATE, "no data on this handle for the view");
+  HIP_TRY(h, hipSetDevice(h->opt.device_id));
+  if (int rc = sync_both(h)) return rc;
+  if (col_ptr) HIP_TRY(h, hipMemcpy(col_ptr, vs.cp, ((size_t)vs.m + 1) * sizeof(long long), hipMemcpyDeviceToHost));
+  if (row_idx && vs.nnz > 0) HIP_TRY(h, hipMemcpy(row_idx, vs.ri, (size_t)vs.nnz * sizeof(int), hipMemcpyDeviceToHost));
+  if (values && vs.nnz > 0) {
+    std::vector<float> t((size_t)vs.nnz);
+    HIP_TRY(h, hipMemcpy(t.data(), vs.vcsc, t.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < t.size(); ++e) values[e] = (double)t[e];
+  }
   return RESNMTF_OK;
 }
 

@@ -271,6 +271,23 @@ class Engine:
         """``shuffle_view`` (``R/obtain_bicl.r:11-22``) of another engine's view, drawn on the device."""
         self._check(self._lib.resnmtf_shuffle_view(self._h, v, other._h, v_src, int(seed), 1 if normalise else 0))
 
+    def shuffle_view_sparse_from(self, v: int, other: "Engine", v_src: int = 0, seed: int = 0, normalise: bool = True):
+        """``shuffle_view`` (``R/obtain_bicl.r:11-22``) of another engine's SPARSE view into this engine's sparse view
+        ``v`` (``resnmtf_shuffle_view_sparse``): the draw ``shuffle_view_from`` makes of the densified view for the same
+        seed, from the stored entries alone; the shuffle stays sparse."""
+        self._check(self._lib.resnmtf_shuffle_view_sparse(self._h, v, other._h, v_src, int(seed), 1 if normalise else 0))
+
+    def get_view_sparse(self, v: int):
+        """The device CSC copy of sparse view ``v`` (``resnmtf_get_view_csc``; fp32 precision, explicit zeros kept) as a
+        ``scipy.sparse.csc_matrix``.  A dense view is refused (``get_view``)."""
+        import scipy.sparse as sp
+        nnz = self.view_storage(v)[1]
+        col_ptr = np.zeros(self.n_cols[v] + 1, dtype=np.int64)
+        row_idx = np.zeros(max(nnz, 1), dtype=np.int32); vals = np.zeros(max(nnz, 1))
+        self._check(self._lib.resnmtf_get_view_csc(self._h, v, col_ptr.ctypes.data_as(C.POINTER(C.c_longlong)), _ip(row_idx),
+                                                   _dp(vals)))
+        return sp.csc_matrix((vals[:nnz], row_idx[:nnz], col_ptr), shape=(self.n_rows[v], self.n_cols[v]))
+
     def subsample_view_from(self, v: int, other: "Engine", v_src: int, rows, cols):
         """The sub-sample ``X[rows, cols]`` of another engine's view (``R/stability_analysis.r:230-249``), gathered
         on the device; this engine's view v must have the shape ``(len(rows), len(cols))``."""

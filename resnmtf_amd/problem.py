@@ -70,25 +70,38 @@ def couple(eng, row_names, col_names, row_shared=None, col_shared=None):
                 eng.set_shared_cols(v, w, *cols[v][w])
 
 
-def _draw_shuffle(eng, v: int, src, shuffle_seed: int):
+def _draw_shuffle(eng, v: int, src, shuffle_seed: int, shuffle_sparse: bool = False):
     """``shuffle_view`` (``R/obtain_bicl.r:11-22``) of ``src``'s view v into ``eng``'s view v, drawn and re-normalised
-    on the device; redrawn while a row or a column of the shuffled matrix sums to zero (``:14-18``)."""
+    on the device; redrawn while a row or a column of the shuffled matrix sums to zero (``:14-18``).  ``shuffle_sparse``
+    (opt-in): a sparse view is shuffled as a sparse view (``Engine.shuffle_view_sparse_from``: the same draws, the same
+    seeds, the same bound of 64); without it the library refuses it as before.  A sparse view with fewer stored entries
+    than ``max(n, m)`` is refused before the first draw: every shuffle of it has an all-zero row or column."""
+    draw = eng.shuffle_view_from
+    if shuffle_sparse and src.sparse[v]:
+        lines = max(src.n_rows[v], src.n_cols[v])
+        stored = src.view_storage(v)[1]                 # (>= the number of positive entries)
+        if stored < lines:
+            raise ValueError(f"shuffle_view: view {v} stores {stored} entries, fewer than max(n, m) = {lines}: every shuffle "
+                             "of it has an all-zero row or column, and the reference's shuffle_view (R/obtain_bicl.r:14-18) "
+                             "would not terminate on this view")
+        draw = eng.shuffle_view_sparse_from
     for attempt in range(64):
-        eng.shuffle_view_from(v, src, v, seed=(shuffle_seed + 7919 * attempt) * 1000003 + v)
+        draw(v, src, v, seed=(shuffle_seed + 7919 * attempt) * 1000003 + v)
         er, ec = eng.empty_lines(v)
         if not (er.any() or ec.any()):
             return
     raise RuntimeError("shuffle_view: every draw left an all-zero row or column")
 
 
-def load_child(eng, src, seed: int, *, shuffle_seed: Optional[int] = None, samples=None, host_views=None, coupling=None):
+def load_child(eng, src, seed: int, *, shuffle_seed: Optional[int] = None, samples=None, host_views=None, coupling=None,
+               shuffle_sparse: bool = False):
     """Fill ``eng`` from ``src``, an engine on the same device that holds the data: every view shuffled (with
-    ``shuffle_seed``), sub-sampled (``samples = (row_samples, col_samples)``) or copied -- a sparse view is uploaded from
+    ``shuffle_seed``; sparse views only with ``shuffle_sparse``, ``_draw_shuffle``), sub-sampled (``samples = (row_samples, col_samples)``) or copied -- a sparse view is uploaded from
     ``host_views[v]`` instead -- then the device SVD init with ``seed + v``; at last ``coupling`` = (phi, xi, psi,
     row_names, col_names), or for shuffles none: no restrictions, uncoupled (``R/obtain_bicl.r:35-39``)."""
     for v in range(eng.n_views):
         if shuffle_seed is not None:
-            _draw_shuffle(eng, v, src, shuffle_seed)
+            _draw_shuffle(eng, v, src, shuffle_seed, shuffle_sparse)
         elif host_views is not None and host_views[v] is not None:
             eng.set_view_sparse(v, host_views[v], pre_processed=True)      # (sub-samples are not re-normalised)
         elif samples is not None:
@@ -103,19 +116,23 @@ def load_child(eng, src, seed: int, *, shuffle_seed: Optional[int] = None, sampl
         couple(eng, *coupling[3:])
 
 
-def shuffled_engines(src, k: int, num_repeats: int, seed: int = 0, max_iters: int = 100000, device_id: int = 0) -> list:
+def shuffled_engines(src, k: int, num_repeats: int, seed: int = 0, max_iters: int = 100000, device_id: int = 0, *,
+                     shuffle_sparse: bool = False) -> list:
     """``obtain_shuffled_f`` (``R/obtain_bicl.r:31-42``) drawn from the views an engine already holds on the device
     (``src``: a ``res_nmtf_inner`` engine or a stability repeat's sub-sample; no second upload): ``num_repeats`` engines,
     every view shuffled from ``src``'s and re-normalised, no restrictions, uncoupled, device SVD init, run to
     convergence -- the draws and seeds of ``shuffles_on_device(dev, k, num_repeats, seed=seed)``: repeat r initialises
     with ``seed + 1000 + r`` and shuffles with ``seed * 7919 + r + 1``.  The engines are returned open, with their
-    factors on the device (``Engine.spurious_scores``); the caller closes them."""
+    factors on the device (``Engine.spurious_scores``); the caller closes them.  ``shuffle_sparse`` (opt-in): a sparse
+    view of ``src`` is shuffled into a sparse view of the same capacity (mixed problems work view by view); without it
+    the engines are dense and the library refuses a sparse source as before."""
     out = []
+    nnz = [src.view_storage(v)[1] if shuffle_sparse and src.sparse[v] else None for v in range(src.n_views)]
     try:
         for r in range(num_repeats):
-            eng = Engine(src.n_rows, src.n_cols, [k] * src.n_views, device_id=device_id)
+            eng = Engine(src.n_rows, src.n_cols, [k] * src.n_views, device_id=device_id, nnz=nnz)
             out.append(eng)
-            load_child(eng, src, seed + 1000 + r, shuffle_seed=seed * 7919 + r + 1)
+            load_child(eng, src, seed + 1000 + r, shuffle_seed=seed * 7919 + r + 1, shuffle_sparse=shuffle_sparse)
             eng.run(n_iters=None, tol=1.0e-6, max_iters=max_iters)
     except BaseException:
         for eng in out:

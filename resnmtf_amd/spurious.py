@@ -128,7 +128,7 @@ def _check_factors(mats, what):
 
 def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int] = None, device_id: int = 0,
                      group=None, max_iters: int = 100000, shuffled_f=None, jsd: Optional[Callable] = None,
-                     grouped: bool = False) -> dict:
+                     grouped: bool = False, shuffle_sparse: bool = False) -> dict:
     """``check_biclusters`` (``R/obtain_bicl.r:113-133``) with ``get_thresholds`` (``:80-102``): returns
     ``{"score": n_views x K, "avg_threshold": n_views, "max_threshold": n_views}``.
 
@@ -141,13 +141,19 @@ def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int
     (``check_data``), to convergence -- run in one ``batched.run_jobs_grouped`` call (fp64, one workgroup per job)
     instead of ``shuffles_on_device``; ``group`` is then not used.  At the default 5 repeats this is slower than the
     default path (the grouped kernel is latency-bound per job): it buys fp64 shuffled fits, not
-    speed."""
+    speed.  ``shuffle_sparse=True`` (opt-in): ``scipy.sparse`` views are shuffled as sparse views on the device
+    (``resnmtf_shuffle_view_sparse``: the dense path's draws of the densified views, DESIGN.md section 10 "Sparse
+    shuffles"); without it they are refused as before, and with ``grouped`` they stay refused."""
     R = check_num_repeats(num_repeats)
     views = list(data) if not (isinstance(data, np.ndarray) and data.ndim == 2) and not sparse.is_sparse(data) else [data]
     if any(sparse.is_sparse(d) for d in views):
-        raise NotImplementedError("spurious-bicluster removal needs shuffled views: device shuffles of sparse views are "
-                                  "not supported")
-    views = [np.asarray(d, dtype=np.float64) for d in views]
+        if not shuffle_sparse:
+            raise NotImplementedError("spurious-bicluster removal needs shuffled views: device shuffles of sparse views are "
+                                      "not supported")
+        if grouped and shuffled_f is None:
+            raise NotImplementedError("the grouped path takes dense views only; sparse views are shuffled on the device "
+                                      "(grouped=False)")
+    views = [sparse.canonical_csc(d) if sparse.is_sparse(d) else np.asarray(d, dtype=np.float64) for d in views]
     output_f = [np.asarray(f, dtype=np.float64) for f in output_f]
     n_v = len(views)
     if len(output_f) != n_v:
@@ -169,7 +175,8 @@ def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int
         else:
             dev = batched.DeviceData(views, device_id=device_id, pre_processed=True)
             try:
-                reps = batched.shuffles_on_device(dev, K, R, n_iters=None, seed=seed, group=group, max_iters=max_iters)
+                reps = batched.shuffles_on_device(dev, K, R, n_iters=None, seed=seed, group=group, max_iters=max_iters,
+                                                  shuffle_sparse=shuffle_sparse)
             finally:
                 dev.close()
         shuffled_f = [rep["output_f"] for rep in reps]
@@ -225,18 +232,20 @@ def thresholds(null):
 
 
 def check_on_device(eng, num_repeats: int, seed: Optional[int] = None, *, max_iters: int = 100000,
-                    device_id: int = 0) -> dict:
+                    device_id: int = 0, shuffle_sparse: bool = False) -> dict:
     """``check_biclusters`` of the factorisation an engine holds (its F on the device, as ``finalise`` normalises it)
     against ``num_repeats`` shuffles of the engine's own views: ``problem.shuffled_engines(eng, K, num_repeats, seed)``
     -- the draws of ``check_biclusters(data, F, num_repeats, seed=seed)`` -- scored per view by
     ``resnmtf_spurious_scores``; the thresholds on the host.  Bitwise ``check_biclusters``' result for the same data,
-    F and seed.  Returns ``{"score", "avg_threshold", "max_threshold"}``."""
+    F and seed.  Returns ``{"score", "avg_threshold", "max_threshold"}``.  ``shuffle_sparse``: passed on to
+    ``shuffled_engines`` (sparse views of ``eng`` shuffled as sparse views)."""
     n_v, K = eng.n_views, eng.k[0]
     R = check_num_repeats(num_repeats)
     if any(k != K for k in eng.k):
         raise ValueError("every view needs the same k (the reference's k_vec is one k repeated)")
     _check_null_count(K, R)
-    shuffles = shuffled_engines(eng, K, R, 0 if seed is None else int(seed), max_iters=max_iters, device_id=device_id)
+    shuffles = shuffled_engines(eng, K, R, 0 if seed is None else int(seed), max_iters=max_iters, device_id=device_id,
+                                shuffle_sparse=shuffle_sparse)
     try:
         return _check_result([_view_check(i, *eng.spurious_scores(i, shuffles)) for i in range(n_v)])
     finally:
