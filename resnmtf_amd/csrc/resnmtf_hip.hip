@@ -56,64 +56,87 @@ struct SharedMap {
   bool identity = false;   // every row of v maps to the same row of w (auto-named views): no lookup needed
 };
 
+// One half of a view.  X (n x m) ~ F S G^T has two symmetric halves, and everything that exists once per half lives here
+// under one name:
+//   side[SIDE_F]: length n, factor F, multiplier lambda, coupling matrix phi, row maps;    fed by the X.G pass
+//   side[SIDE_G]: length m, factor G, multiplier mu,     coupling matrix psi, column maps; fed by the Xt.F pass
+// THE CROSSOVER (the one place the mapping is easy to get backwards): the pass that feeds side s writes its product slab
+// P ([nsplit][pad][KP]) for the update of side s, but its B operand is the factor of the OTHER side, other(s), and the image
+// it streams has the lines of side s as its 64-wide tiles and the lines of other(s) as its rows: X.G feeds F, multiplies by
+// G and streams X^T (tile-major over the rows of X; sparse: the CSR); Xt.F feeds G, multiplies by F and streams X (the CSC).
+// feeds(xg) names the side a pass feeds; index 0 = F matches wchain[g], schain[g] and the [0] = X.G columns of
+// resnmtf_view_plan_info.
+enum { SIDE_F = 0, SIDE_G = 1 };
+inline int other(int s) { return 1 - s; }
+inline int feeds(bool xg) { return xg ? SIDE_F : SIDE_G; }
+
+struct Side {
+  int len = 0, pad = 0;              // n / m and their multiples of 64
+  double* W = nullptr;               // the fp64 factor F / G [len][k]
+  float* W32 = nullptr;              // its f32 operand copy
+  unsigned short* Wk = nullptr;      // k > 16: its K-packed bf16 pieces (B operand of pass_body_k32)
+  double* lm = nullptr;              // lambda / mu
+  double *Ma = nullptr, *Md = nullptr;   // the k x k coefficient matrices of the update
+  double* part = nullptr;            // mode A: fp64 Gram partials of the update workgroups
+  int rpb = 16, nblk = 1;            // rows per update workgroup, update workgroups
+  // exchange block (replicate_f / replicate_gs): [xsum | Ma | Md | lm] contiguous -- the update's inputs -- a slice of the
+  // handle's arena[s]; xsum = the split slabs of the pass folded into one f32 slab
+  void* xblk = nullptr;
+  size_t xblk_bytes = 0;
+  float* xsum = nullptr;
+  bool replica = false;              // non-owned view whose update of this side runs here too
+  std::vector<SharedMap> map;        // shared rows / columns, indexed by the other view
+  UpdateArgs arg{};
+  // ---- the pass that feeds this side
+  PassArgs pass{};
+  int nsplit = 1, rps = 64, nw = 4, nsaux = 1, rpsaux = 64;
+  int tw = 8;                        // k > 16 (wide form): 64-column tiles per workgroup
+  bool pp = false;                   // k <= 16, streamed geometry: ping-pong prefetch form of the pass (UNROLL 4)
+  float *P = nullptr, *Paux = nullptr;
+  int* cnt = nullptr;
+  // the dense image it streams, tile-major: tile t (64 lines of this side) is a contiguous [other's pad][64] block; ldx = the
+  // TILE stride (floats).  SIDE_F: X^T, SIDE_G: X
+  float* X = nullptr;
+  size_t ldx = 0, x_floats = 0;
+  _Float16* X16 = nullptr;           // fp16 passes (resnmtf_options.x_half, k <= 16): K-packed 2-byte image, tile stride (halves)
+  size_t ld16 = 0, x16_halves = 0;
+  // sparse view: the compressed copy it walks (SIDE_F: CSR, SIDE_G: CSC) and its work blocks: first line of each + end,
+  // then a form flag per block
+  long long* sp_ptr = nullptr;
+  int* sp_idx = nullptr;
+  float* sp_val = nullptr;
+  int* sp_blk = nullptr;
+  int sp_nblk = 0;
+};
+
 struct ViewState {
   int n = 0, m = 0, k = 0, KP = 16, NT = 1;
+  int n_pad = 0, m_pad = 0;          // (= side[SIDE_F].pad, side[SIDE_G].pad)
   bool owned = true, has_x = false, has_factors = false;
   int empty_rows = 0, empty_cols = 0;          // all-zero rows / columns of the latest device-drawn data (shuffle, sub-sample)
   std::vector<unsigned char> empty_mask;     // [n + m], 1 = the row / column sums to zero
   unsigned char* ref_cl = nullptr;           // resnmtf_set_reference_clusters: [n][ref_k] row, then [m][ref_k] column clusters (0 / 1)
   int ref_k = 0;
-  int n_pad = 0, m_pad = 0;
-  size_t ldx = 0, ldxt = 0;      // TILE strides of X32 / Xt32 (floats): tile t (64 columns) is a contiguous [rows_pad][64] block
-  size_t x32_floats = 0, xt32_floats = 0;
-  // fp16 passes (resnmtf_options.x_half, k <= 16): K-packed fp16 images of X / X^T, their tile strides (halves), scale
+  Side side[2];
+  // fp16 passes (resnmtf_options.x_half, k <= 16): scale of the 2-byte images
   bool half = false, u16 = false;   // u16: uniform 16-bit integers instead of fp16 (x_half = 2, 3)
   bool half_capable = false;        // the 2-byte images are allocated; `half` says whether the passes use them (x_half = 3: guard)
   double x_relerr = 0.0;            // || X~ - X ||_F / || X ||_F of the 2-byte image (set at upload)
-  _Float16 *X16 = nullptr, *Xt16 = nullptr;
-  size_t ld16x = 0, ld16xt = 0, x16_halves = 0, xt16_halves = 0;
   float xscale = 1.f;
-  float *X32 = nullptr, *Xt32 = nullptr;
   double* xnorm2 = nullptr;
-  double *F = nullptr, *G = nullptr, *S = nullptr, *lambda = nullptr, *mu = nullptr;
-  float *F32 = nullptr, *G32 = nullptr, *T32 = nullptr;
-  unsigned short *Fk = nullptr, *Gk = nullptr;   // k > 16: K-packed bf16 pieces of F / G (B operands of pass_body_k32)
-  int nsplit_xg = 1, rps_xg = 64, nw_xg = 4, nsaux_xg = 1, rpsaux_xg = 64;
-  int nsplit_xtf = 1, rps_xtf = 64, nw_xtf = 4, nsaux_xtf = 1, rpsaux_xtf = 64;
-  int tw_xg = 8, tw_xtf = 8;         // k > 16 (wide form): 64-column tiles per workgroup
-  float *Pxg = nullptr, *Pxtf = nullptr, *Paux_xg = nullptr, *Paux_xtf = nullptr;
-  int *cnt_xg = nullptr, *cnt_xtf = nullptr;
+  double* S = nullptr;
+  float* T32 = nullptr;              // (G side only: the f32 copy of T = X^T F the X.G launch's aux tiles read)
   int* fuse_cnt = nullptr;           // [2] arrivals of the update blocks fused into the Xt.F ([0]) / X.G ([1]) launch (pass_fused_kernel)
-  int rpbF = 16, nblkF = 1, rpbG = 16, nblkG = 1;
-  void* fblk = nullptr;              // replicate_f: [Usum | Ma_F | Md_F | lambda] contiguous (the F-update's inputs), a
-  size_t fblk_bytes = 0;             // slice of the handle's arena; Usum = the X.G split slabs folded into one f32 slab
-  float* Usum = nullptr;
-  bool f_replica = false;            // non-owned view whose F update runs here too (replicate_f)
-  void* gblk = nullptr; size_t gblk_bytes = 0;   // replicate_gs: [Tsum | Ma_G | Md_G | mu] (the G update's inputs), arena slice
-  float* Tsum = nullptr;             //   Tsum = the Xt.F split slabs folded into one f32 slab
-  bool g_replica = false;            // non-owned view whose G update runs here too (replicate_gs)
   double* sblk = nullptr;            // replicate_gs: the S update's inputs (sblock_layout), arena slice
-  bool pp_xg = false, pp_xtf = false; // k <= 16, streamed geometry: ping-pong prefetch form of the pass (UNROLL 4)
   int kk_mode = 0;                   // 0 = A: Gram partials from the update kernels, k x k job = workgroup 0
                                      // 1 = B: Gram/cross/colsum on MFMA aux tiles, k x k job = last-arriving aux workgroup
-  double *partF = nullptr, *partG = nullptr;
   double *FtF = nullptr, *FtFS = nullptr, *cF = nullptr;
-  double *Ma_F = nullptr, *Md_F = nullptr, *Ma_G = nullptr, *Md_G = nullptr;
-  std::vector<SharedMap> row_map, col_map;   // indexed by the other view
-  UpdateArgs argF{}, argG{};
   KKFArgs argKF{};
   KKSArgs argKS{};
-  PassArgs passXG{}, passXtF{};
-  // sparse view (resnmtf_create_sparse): CSC + CSR copies instead of the X32 / Xt32 images, hand-off mode A, the
-  // passes are spmm_kernel launches (resnmtf_sparse.hip.inc); nsplit_xg / nsplit_xtf are set at upload (<= kSparseMaxSplitXg /
-  // kSparseMaxSplitXtf)
+  // sparse view (resnmtf_create_sparse): CSC + CSR copies instead of the dense images, hand-off mode A, the passes are
+  // spmm_kernel launches (resnmtf_sparse.hip.inc); the sides' nsplit are set at upload (<= kSparseMaxSplit[s])
   bool sparse = false;
   long long nnz_cap = 0, nnz = 0;
-  long long *cp = nullptr, *rp = nullptr;      // CSC column / CSR row pointers
-  int *ri = nullptr, *ci = nullptr;            // CSC row / CSR column indices
-  float *vcsc = nullptr, *vcsr = nullptr;
-  int *blk_xg = nullptr, *blk_xtf = nullptr;   // work blocks of the two passes: first line of each + end, then a form flag per block
-  int nblk_xg = 0, nblk_xtf = 0;
 };
 
 }  // namespace
@@ -146,17 +169,14 @@ struct resnmtf_handle {
   SweepCtl* ctl_host_dev = nullptr;
   double* err_host_dev = nullptr;
   int n_cu = 256;                     // compute units of the device (multiProcessorCount)
-  ChainArgs<8> chain{};               // RESNMTF_PHASE_F_ALL: the F updates of every view in one launch (when eligible)
-  int chain_views = 0;                // 0 = not eligible: one launch per view
-  ChainArgs<8> gchain{};              // RESNMTF_PHASE_G_ALL at k <= 16 (replicated G chain): the G updates of every view in one launch
-  int gchain_views = 0, gchain_blocks = 0;
+  ChainArgs<8> chain[2]{};            // k <= 16: the F ([0], RESNMTF_PHASE_F_ALL) / G ([1], PHASE_G_ALL, replicated G chain) updates of
+  int chain_views[2] = {0, 0};        //   every view in one launch (when eligible); 0 views = not eligible: one launch per view
+  int chain_blocks[2] = {0, 0};
   WideChainArgs<8> wchain[2]{};       // k = 32 / 64: the F ([0]) and G ([1]) updates of every view in one launch (wide_chain_kernel)
   bool wchain_ok[2] = {false, false};
   int wchain_grid[2] = {0, 0};
-  int chain_blocks = 0;
-  void* fblk_arena = nullptr;         // replicate_f: the F exchange blocks of all views, in view order
-  size_t fblk_arena_bytes = 0;
-  void* gblk_arena = nullptr; size_t gblk_arena_bytes = 0;     // replicate_gs: the G / S exchange blocks of all views
+  void* arena[2] = {nullptr, nullptr};          // replicate_f ([0]) / replicate_gs ([1]): the exchange blocks of all views, in view order
+  size_t arena_bytes[2] = {0, 0};
   double* sblk_arena = nullptr; size_t sblk_stride = 0;        //   (S blocks: sblk_stride doubles each)
   bool sblk_embedded = false;         // the S block of a view sits at the end of its F block (equal-shaped views): they travel together
   double* sblk_base = nullptr; size_t sblk_step = 0;           // S block of view v = sblk_base + v * sblk_step (doubles)
@@ -167,15 +187,15 @@ struct resnmtf_handle {
   // slice_chains: rank r walks the F (G) chain of every view on the row (column) slice r; exchange buffers of the four
   // all-to-alls of a sweep (V chunks each) and the two chain launches
   bool sliced = false;
-  int sl_rows = 0, sl_cols = 0;       // rows / columns per slice (multiples of 32)
-  char *u_send = nullptr, *u_recv = nullptr, *t_send = nullptr, *t_recv = nullptr;
-  size_t u_chunk = 0, t_chunk = 0;    // bytes per chunk: [per_slice][KP] f32 (+ the fp64 tail Ma_G | Md_G for T)
-  float *f_send = nullptr, *f_recv = nullptr, *g_send = nullptr, *g_recv = nullptr;      // [V][per_slice][KP] f32 each
+  int sl_len[2] = {0, 0};             // rows / columns per slice (multiples of 32)
+  char *p_send[2] = {nullptr, nullptr}, *p_recv[2] = {nullptr, nullptr};      // the products U ([0]) / T ([1]) of the passes
+  size_t p_chunk[2] = {0, 0};         // bytes per chunk: [per_slice][KP] f32 (+ the fp64 tail Ma_G | Md_G for T)
+  float *w_send[2] = {nullptr, nullptr}, *w_recv[2] = {nullptr, nullptr};      // the new F / G rows: [V][per_slice][KP] f32 each
   // slice_p2p: the exchange as peer stores + stream-ordered flags (no collective): every rank's receive buffers and flag words,
   // mapped through hipIpc (own rank: the local pointers); flags[e] counts the arrivals of exchange e (0 U + S blocks, 1 new F
   // rows, 2 T slices, 3 new G rows): V per sweep
-  struct Peer { char *u_recv = nullptr, *t_recv = nullptr; float *f_recv = nullptr, *g_recv = nullptr; double* sblk = nullptr;
-                char *fblk_arena = nullptr, *gblk_arena = nullptr;      // block_p2p: the replicated layouts' exchange arenas
+  struct Peer { char* p_recv[2] = {nullptr, nullptr}; float* w_recv[2] = {nullptr, nullptr}; double* sblk = nullptr;
+                char* arena[2] = {nullptr, nullptr};      // block_p2p: the replicated layouts' exchange arenas
                 unsigned int* flags = nullptr; bool imported = false; void* opened[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; };
   std::vector<Peer> peers;
   unsigned int* p2p_flags = nullptr;
@@ -263,18 +283,18 @@ constexpr int kKPs[] = {16, 32, 48, 64};
 constexpr bool kBools[] = {false, true};
 
 void free_view(ViewState& v) {
-  if (v.fblk) { v.fblk = nullptr; v.Usum = nullptr; v.Ma_F = nullptr; v.Md_F = nullptr; v.lambda = nullptr; }   // arena slices
-  if (v.gblk) { v.gblk = nullptr; v.Tsum = nullptr; v.Ma_G = nullptr; v.Md_G = nullptr; v.mu = nullptr; }
+  for (Side& sd : v.side) {
+    if (sd.xblk) { sd.xblk = nullptr; sd.xsum = nullptr; sd.Ma = nullptr; sd.Md = nullptr; sd.lm = nullptr; }   // arena slices
+    void* ptrs[] = {sd.W, sd.W32, sd.Wk, sd.lm, sd.Ma, sd.Md, sd.part, sd.P, sd.Paux, sd.cnt, sd.X, sd.X16, sd.sp_ptr, sd.sp_idx, sd.sp_val, sd.sp_blk};
+    for (void* p : ptrs)
+      if (p) (void)hipFree(p);
+    for (auto& mp : sd.map)
+      if (mp.dev) (void)hipFree(mp.dev);
+  }
   v.sblk = nullptr;
-  void* ptrs[] = {v.fuse_cnt, v.Fk, v.Gk, v.X16, v.Xt16, v.X32, v.Xt32, v.xnorm2, v.F, v.G, v.S, v.lambda, v.mu, v.F32, v.G32, v.T32, v.Pxg, v.Pxtf,
-                  v.Paux_xg, v.Paux_xtf, v.cnt_xg, v.cnt_xtf, v.partF, v.partG, v.FtF, v.FtFS, v.cF, v.Ma_F, v.Md_F, v.Ma_G, v.Md_G, v.ref_cl,
-                  v.cp, v.rp, v.ri, v.ci, v.vcsc, v.vcsr, v.blk_xg, v.blk_xtf};
+  void* ptrs[] = {v.fuse_cnt, v.xnorm2, v.S, v.T32, v.FtF, v.FtFS, v.cF, v.ref_cl};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
-  for (auto& mp : v.row_map)
-    if (mp.dev) (void)hipFree(mp.dev);
-  for (auto& mp : v.col_map)
-    if (mp.dev) (void)hipFree(mp.dev);
 }
 
 int check_view(resnmtf_handle* h, int v) {
@@ -418,9 +438,10 @@ hipError_t set_all_attrs() {
 // sparse view: X.G from the CSR, Xt.F from the CSC (spmm_kernel), same slabs as the dense passes.  kk: the k x k job in
 // workgroup 0 (hand-off mode A, as pass_kernel); otherwise (SVD initialisation) B / P / width come from the caller
 SpmmArgs spmm_args(const ViewState& v, bool xg) {
+  const Side& sd = v.side[feeds(xg)];
   SpmmArgs a{};
-  if (xg) { a.ptr = v.rp; a.idx = v.ci; a.val = v.vcsr; a.blk = v.blk_xg; a.nblk = v.nblk_xg; a.nsplit = v.nsplit_xg; a.B = v.G32; a.P = v.Pxg; a.cols_pad = v.n_pad; }
-  else { a.ptr = v.cp; a.idx = v.ri; a.val = v.vcsc; a.blk = v.blk_xtf; a.nblk = v.nblk_xtf; a.nsplit = v.nsplit_xtf; a.B = v.F32; a.P = v.Pxtf; a.cols_pad = v.m_pad; }
+  a.ptr = sd.sp_ptr; a.idx = sd.sp_idx; a.val = sd.sp_val; a.blk = sd.sp_blk; a.nblk = sd.sp_nblk; a.nsplit = sd.nsplit;
+  a.B = v.side[other(feeds(xg))].W32; a.P = sd.P; a.cols_pad = sd.pad;
   a.ldb = v.KP;
   return a;
 }
@@ -432,6 +453,8 @@ void launch_spmm(resnmtf_handle* h, const SpmmArgs& a, int KP, bool xg, const KK
 
 // ---- one streaming pass of a view, resolved: everything that is decided before the launch.  launch_pass launches from it,
 // resnmtf_view_plan reports it, can_fuse_update and resnmtf_pass_timings read it
+// aux products of a pass launch in hand-off mode B, by the side it feeds: X.G carries G^T G, T^T G, colSums(G); Xt.F F^T F, colSums(F)
+constexpr int kAuxKinds[2] = {3, 2};
 struct PassLaunch {
   int image = 0;               // what is streamed: 0 = f32 images, 1 = sparse CSC / CSR, 2 = fp16 image, 3 = 16-bit integer image
   bool mode_a = true;          // the k x k job is workgroup 0 (B: the last-arriving aux workgroup)
@@ -464,8 +487,9 @@ PassLaunch resolve_pass(const resnmtf_handle* h, const ViewState& v, bool xg, bo
     L.kern_spmm = select_spmm(v.KP, xg);
     return L;
   }
-  const int nw = xg ? v.nw_xg : v.nw_xtf, nsplit = xg ? v.nsplit_xg : v.nsplit_xtf, rps = xg ? v.rps_xg : v.rps_xtf;
-  const int rows_pad = xg ? v.m_pad : v.n_pad, ntiles = (xg ? v.n_pad : v.m_pad) / 64;
+  const Side& sd = v.side[feeds(xg)];
+  const int nw = sd.nw, nsplit = sd.nsplit, rps = sd.rps;
+  const int rows_pad = v.side[other(feeds(xg))].pad, ntiles = sd.pad / 64;      // (the reduction runs over the OTHER side's lines)
   L.image = v.half ? (v.u16 ? 3 : 2) : 0;
   L.mode_a = v.kk_mode == 0;
   L.waves = nw;
@@ -474,12 +498,12 @@ PassLaunch resolve_pass(const resnmtf_handle* h, const ViewState& v, bool xg, bo
   L.wide = v.NT >= 2 && h->opt.bf16_split != 2;
   L.xcd_order = L.wide && h->opt.xcd_order;
   L.short_last = nsplit > 1 && rows_pad - (nsplit - 1) * rps < rps;
-  L.tiles_per_wg = L.wide ? (xg ? v.tw_xg : v.tw_xtf) : 1;
+  L.tiles_per_wg = L.wide ? sd.tw : 1;
   L.main_blocks = ceil_div(ntiles, L.tiles_per_wg) * nsplit;
-  L.lead_blocks = L.mode_a ? 1 : (xg ? 3 * v.nsaux_xg : 2 * v.nsaux_xtf);      // (aux tiles: G^T G, T^T G, colSums(G) / F^T F, colSums(F))
+  L.lead_blocks = L.mode_a ? 1 : kAuxKinds[feeds(xg)] * sd.nsaux;
   L.grid = dim3(L.lead_blocks + L.main_blocks); L.block = dim3(64 * nw);
   L.smem = std::min<size_t>(pass_smem_bytes(v.KP, nw) + (size_t)h->opt.pass_lds_pad_kb * 1024, kMaxLds);
-  const bool pp = xg ? v.pp_xg : v.pp_xtf;
+  const bool pp = sd.pp;
   if (fuse_update) {
     L.fused = true;
     L.pingpong = pp;
@@ -506,9 +530,8 @@ bool can_fuse_update(const resnmtf_handle* h, const ViewState& v, int kind) {
   if (h->opt.fuse_updates == 0 || v.NT != 1 || !v.fuse_cnt) return false;
   const PassLaunch L = resolve_pass(h, v, kind != 0);
   if (L.image != 0 || !L.mode_a || L.waves != 8) return false;
-  const UpdateArgs& u = kind == 0 ? v.argF : v.argG;
-  const int nblk = kind == 0 ? v.nblkF : v.nblkG;
-  return !u.restricted && nblk <= L.main_blocks && nblk <= h->n_cu;
+  const Side& sd = v.side[kind];
+  return !sd.arg.restricted && sd.nblk <= L.main_blocks && sd.nblk <= h->n_cu;
 }
 // (The k x k job's dynamic LDS is requested for every workgroup of the launch: at KP >= 48 one workgroup per CU.  Measured,
 // 200000 x 20000 at 0.5 %, k = 64: the Xt.F pass alone runs 632-650 us without that LDS against 846 us with it, but the job
@@ -527,7 +550,7 @@ void launch_pass(resnmtf_handle* h, const ViewState& v, bool xg, int mode, doubl
     launch(h, kind, L.kern_spmm, L.grid, L.block, L.smem, a, kf, ks);
     return;
   }
-  PassArgs a = xg ? v.passXG : v.passXtF;
+  PassArgs a = v.side[feeds(xg)].pass;
   a.check_done = check_done ? 1 : 0;
   // mode A: the k x k job is workgroup 0 and reads the update kernel's fp64 partials
   a.kk_block0 = L.mode_a ? 1 : 0;
@@ -548,12 +571,13 @@ void launch_pass(resnmtf_handle* h, const ViewState& v, bool xg, int mode, doubl
     a.xcd_n = n_map;
   }
   if (L.fused) {
-    UpdateArgs u = xg ? v.argG : v.argF;
+    const Side& upd = v.side[other(feeds(xg))];      // the update of the pass's B operand
+    UpdateArgs u = upd.arg;
     u.check_done = 0; u.gram_only = 0;
     FuseArgs fz{};
     fz.cnt_own = v.fuse_cnt + (xg ? 2 : 0);      // [0] arrivals, [1] the flag the waiters poll
     { static const int nap = std::getenv("RESNMTF_FUSE_NAP") ? std::atoi(std::getenv("RESNMTF_FUSE_NAP")) : 2; fz.nap = nap; }
-    fz.n_upd = xg ? v.nblkG : v.nblkF; fz.err = h->fuse_err_dev;
+    fz.n_upd = upd.nblk; fz.err = h->fuse_err_dev;
     launch(h, kind, L.kern_fused, L.grid, L.block, L.smem, a, kf, ks, u, fz);
     return;
   }
@@ -588,12 +612,12 @@ ChainArgs<NVB> narrow_chain(const ChainArgs<8>& c) {
 
 // kind: 0 = F update, 1 = G update, 2 = mode A run prologue: partials of the current G, nothing updated
 void launch_update(resnmtf_handle* h, const ViewState& v, int kind, bool check_done) {
-  UpdateArgs a = kind == 0 ? v.argF : v.argG;
+  const Side& sd = v.side[kind == 0 ? SIDE_F : SIDE_G];
+  UpdateArgs a = sd.arg;
   a.check_done = check_done ? 1 : 0;
   a.gram_only = kind == 2 ? 1 : 0;
   if (kind == 2) { a.restricted = 0; a.n_couple = 0; }
-  const int nblk = kind == 0 ? v.nblkF : v.nblkG;
-  launch(h, -1, select_update(v.KP, kind != 0, couple_bucket(a), v.kk_mode == 0), dim3(nblk), dim3(update_threads(v.KP)), update_smem_bytes(v.KP), a);
+  launch(h, -1, select_update(v.KP, kind != 0, couple_bucket(a), v.kk_mode == 0), dim3(sd.nblk), dim3(update_threads(v.KP)), update_smem_bytes(v.KP), a);
 }
 
 template <int NVB>
@@ -678,69 +702,59 @@ void launch_wide_chain(resnmtf_handle* h, int g, bool checked, bool sliced = fal
 struct FChainPlan { bool chain = false, hoisted = false, one_slab = true; int width = 0; };
 FChainPlan plan_f_chain(const resnmtf_handle* h) {
   FChainPlan p;
-  p.chain = !h->wchain_ok[0] && h->chain_views > 0;
+  p.chain = !h->wchain_ok[0] && h->chain_views[SIDE_F] > 0;
   if (!p.chain) return p;
   p.hoisted = h->all_owned;
-  p.width = h->chain_views <= 2 ? 2 : (h->chain_views <= 4 ? 4 : 8);
-  for (int v = 0; v < h->chain_views; ++v) p.one_slab = p.one_slab && h->chain.nsplit[v] == 1;
+  p.width = h->chain_views[SIDE_F] <= 2 ? 2 : (h->chain_views[SIDE_F] <= 4 ? 4 : 8);
+  for (int v = 0; v < h->chain_views[SIDE_F]; ++v) p.one_slab = p.one_slab && h->chain[SIDE_F].nsplit[v] == 1;
   return p;
+}
+// the k <= 16 chain of side s (every view's update of that side) as ONE f_chain_kernel launch; false: not eligible
+bool enqueue_chain(resnmtf_handle* h, int s, bool one_slab, bool checked) {
+  if (h->chain_views[s] <= 0) return false;
+  h->chain[s].check_done = checked ? 1 : 0;
+  const int kind = s == SIDE_F ? RESNMTF_TIMED_F_CHAIN : RESNMTF_TIMED_G_CHAIN;
+  for_chain(h->chain[s], h->chain_views[s], [&](auto nvb, const auto& a) {
+    constexpr int NVB = decltype(nvb)::value;
+    launch(h, kind, select_f_chain<NVB>(s == SIDE_G, one_slab), dim3(h->chain_blocks[s]), dim3(512), f_chain_smem_bytes<NVB>(), a);
+  });
+  return true;
 }
 // RESNMTF_PHASE_F_ALL: update_f of every view in view order (one launch when the chain is eligible)
 void enqueue_phase_f_all(resnmtf_handle* h, bool checked = false) {
   if (h->wchain_ok[0]) { launch_wide_chain(h, 0, checked); return; }
   const FChainPlan p = plan_f_chain(h);
-  if (p.chain) {
-    h->chain.check_done = checked ? 1 : 0;
-    for_chain(h->chain, h->chain_views, [&](auto nvb, const auto& a) {
-      constexpr int NVB = decltype(nvb)::value;
-      launch(h, RESNMTF_TIMED_F_CHAIN, select_f_chain<NVB>(false, p.one_slab), dim3(h->chain_blocks), dim3(512), f_chain_smem_bytes<NVB>(), a);
-    });
-    return;
-  }
+  if (p.chain && enqueue_chain(h, SIDE_F, p.one_slab, checked)) return;
   for (const auto& v : h->views)
-    if (v.owned || v.f_replica) launch_update(h, v, 0, checked);
-}
-
-// RESNMTF_PHASE_G_ALL at k <= 16: update_g of every view in one launch (f_chain_kernel, G form) when eligible
-bool enqueue_g_chain(resnmtf_handle* h, bool checked) {
-  if (h->gchain_views <= 0) return false;
-  h->gchain.check_done = checked ? 1 : 0;
-  const dim3 grid(h->gchain_blocks), block(512);
-  for_chain(h->gchain, h->gchain_views, [&](auto nvb, const auto& a) {
-    constexpr int NVB = decltype(nvb)::value;
-    launch(h, RESNMTF_TIMED_G_CHAIN, select_f_chain<NVB>(true, true), grid, block, f_chain_smem_bytes<NVB>(), a);
-  });
-  return true;
+    if (v.owned || v.side[SIDE_F].replica) launch_update(h, v, 0, checked);
 }
 
 // ---- the phases of one view (see the header comment)
 void enqueue_phase_f(resnmtf_handle* h, const ViewState& v, bool checked) { launch_update(h, v, 0, checked); }
-// replicate_f: the X.G split slabs of an owned view -> the one f32 slab of its exchange block (what every
-// rank's F update of this view reads, the owner's included: a third of the bytes on the wire at c2)
-void launch_fold(resnmtf_handle* h, const ViewState& v) {
-  if (!v.Usum) return;
-  const int quads = v.n_pad * v.KP / 4;
-  launch(h, RESNMTF_TIMED_PACK, slab_fold_kernel, dim3(ceil_div(quads, 256)), dim3(256), 0, v.Pxg, v.nsplit_xg, quads, v.Usum);
-}
-void launch_fold_t(resnmtf_handle* h, const ViewState& v) {
-  if (!v.Tsum) return;
-  const int quads = v.m_pad * v.KP / 4;
-  launch(h, RESNMTF_TIMED_PACK, slab_fold_kernel, dim3(ceil_div(quads, 256)), dim3(256), 0, v.Pxtf, v.nsplit_xtf, quads, v.Tsum);
+// replicate_f / replicate_gs: the split slabs of the pass that feeds side s of an owned view -> the one f32 slab of its
+// exchange block (what every rank's update of this view reads, the owner's included: a third of the bytes on the wire at c2)
+void launch_fold(resnmtf_handle* h, const ViewState& v, int s) {
+  const Side& sd = v.side[s];
+  if (!sd.xsum) return;
+  const int quads = sd.pad * v.KP / 4;
+  launch(h, RESNMTF_TIMED_PACK, slab_fold_kernel, dim3(ceil_div(quads, 256)), dim3(256), 0, sd.P, sd.nsplit, quads, sd.xsum);
 }
 // slice_chains: the own view's pass result, folded and cut into the V chunks of the next all-to-all (slice_pack_kernel)
 void launch_slice_pack(resnmtf_handle* h, const ViewState& v, bool xg, bool checked) {
   SlicePackArgs a{};
-  a.P = xg ? v.Pxg : v.Pxtf; a.nsplit = xg ? v.nsplit_xg : v.nsplit_xtf; a.rows_pad = xg ? v.n_pad : v.m_pad;
+  const int s = feeds(xg);
+  const Side& sd = v.side[s];
+  a.P = sd.P; a.nsplit = sd.nsplit; a.rows_pad = sd.pad;
   a.KP = v.KP; a.NT = v.NT;
-  a.rows_per_slice = xg ? h->sl_rows : h->sl_cols; a.n_slices = h->opt.slice_count;
-  a.out = xg ? h->u_send : h->t_send; a.chunk_bytes = xg ? h->u_chunk : h->t_chunk;
-  if (!xg) { a.tail[0] = v.Ma_G; a.tail[1] = v.Md_G; a.tail_count = v.k * v.k; a.T32 = v.T32; a.ld32 = 64; }
+  a.rows_per_slice = h->sl_len[s]; a.n_slices = h->opt.slice_count;
+  a.out = h->p_send[s]; a.chunk_bytes = h->p_chunk[s];
+  if (!xg) { a.tail[0] = sd.Ma; a.tail[1] = sd.Md; a.tail_count = v.k * v.k; a.T32 = v.T32; a.ld32 = 64; }
   if (h->opt.slice_p2p) {      // chunk c straight into rank c's receive slot for this rank; U: the own S block into every rank's arena
     const int r = h->opt.slice_index, vi = (int)(&v - h->views.data());
     a.out = nullptr;
     for (int c = 0; c < a.n_slices; ++c) {
       const resnmtf_handle::Peer& pc = h->peers[(size_t)c];
-      a.outv[c] = (xg ? pc.u_recv : pc.t_recv) + (size_t)r * a.chunk_bytes;
+      a.outv[c] = pc.p_recv[s] + (size_t)r * a.chunk_bytes;
       if (xg) a.tailv[c] = pc.sblk + (size_t)vi * h->sblk_stride;
     }
     if (xg) { a.tail[0] = v.sblk; a.tail[1] = v.sblk + h->sblk_stride / 2; a.tail_count = (int)(h->sblk_stride / 2); }
@@ -768,46 +782,43 @@ hipError_t p2p_wait(resnmtf_handle* h, int e, int site, int sweep, int add) {
   return hipGetLastError();
 }
 // block_p2p: byte ranges [off0, off0 + b0) and [off1, off1 + b1) of this rank's part of an arena -> the same place on every peer
-// kind 0: F exchange arena, 1: G exchange arena, 2: S block arena
+// kind SIDE_F / SIDE_G: that exchange arena, 2: S block arena
 void launch_block_push(resnmtf_handle* h, int kind, size_t off0, size_t b0, size_t off1, size_t b1) {
   BlockPushArgs a{};
-  a.src = static_cast<const char*>(kind == 0 ? h->fblk_arena : kind == 1 ? h->gblk_arena : (void*)h->sblk_arena);
+  a.src = static_cast<const char*>(kind < 2 ? h->arena[kind] : (void*)h->sblk_arena);
   for (int c = 0; c < h->V; ++c) {
     if (c == h->opt.slice_index) continue;
     const resnmtf_handle::Peer& pc = h->peers[(size_t)c];
-    a.dst[a.n_dst++] = kind == 0 ? pc.fblk_arena : kind == 1 ? pc.gblk_arena : reinterpret_cast<char*>(pc.sblk);
+    a.dst[a.n_dst++] = kind < 2 ? pc.arena[kind] : reinterpret_cast<char*>(pc.sblk);
   }
   if (a.n_dst == 0) return;
   a.off[0] = off0; a.bytes[0] = b0; a.off[1] = off1; a.bytes[1] = b1;
   const size_t quads = (b0 + b1) / 16;
   launch(h, RESNMTF_TIMED_PACK, block_push_kernel, dim3((unsigned)std::max<size_t>(1, std::min<size_t>((quads + 255) / 256, 2048))), dim3(256), 0, a);
 }
-// the F exchange block of an owned view to the peers: everything (replicate_f alone: the owner's coefficients and lambda are
-// the only copy) or, with the replicated S chain, the U rows and the embedded S block only -- every rank computes the
-// coefficients, lambda and mu of every view itself and a late store must not land on them
-void push_f_block(resnmtf_handle* h, const ViewState& v) {
-  const size_t base = (size_t)(static_cast<const char*>(v.fblk) - static_cast<const char*>(h->fblk_arena));
-  if (!h->opt.replicate_gs) { launch_block_push(h, 0, base, v.fblk_bytes, 0, 0); return; }
-  const size_t usum = ((size_t)v.n_pad * v.KP * sizeof(float) + 255) / 256 * 256;
-  if (h->sblk_embedded) {
-    const size_t s_off = (size_t)(reinterpret_cast<const char*>(v.sblk) - static_cast<const char*>(h->fblk_arena));
-    launch_block_push(h, 0, base, usum, s_off, h->sblk_stride * sizeof(double));
+// the exchange block of side s of an owned view to the peers.  F: everything (replicate_f alone: the owner's coefficients and
+// lambda are the only copy) or, with the replicated S chain, the U rows and the S block only -- every rank computes the
+// coefficients, lambda and mu of every view itself and a late store must not land on them.  G: [Tsum | Ma_G | Md_G], not mu
+void push_block(resnmtf_handle* h, const ViewState& v, int s) {
+  const Side& sd = v.side[s];
+  const size_t base = (size_t)(static_cast<const char*>(sd.xblk) - static_cast<const char*>(h->arena[s]));
+  const size_t sum = ((size_t)sd.pad * v.KP * sizeof(float) + 255) / 256 * 256;
+  if (s == SIDE_G) { launch_block_push(h, s, base, (sum + 2 * (size_t)v.k * v.k * sizeof(double)) / 16 * 16, 0, 0); return; }
+  if (!h->opt.replicate_gs) { launch_block_push(h, s, base, sd.xblk_bytes, 0, 0); return; }
+  if (h->sblk_embedded) {      // the S block travels with the U rows: the F-side special case
+    const size_t s_off = (size_t)(reinterpret_cast<const char*>(v.sblk) - static_cast<const char*>(h->arena[s]));
+    launch_block_push(h, s, base, sum, s_off, h->sblk_stride * sizeof(double));
   } else {
-    launch_block_push(h, 0, base, usum, 0, 0);
+    launch_block_push(h, s, base, sum, 0, 0);
     const size_t sb = (h->sblk_stride * sizeof(double));
     launch_block_push(h, 2, (size_t)(&v - h->views.data()) * sb, sb / 16 * 16, 0, 0);
   }
 }
-void push_g_block(resnmtf_handle* h, const ViewState& v) {      // [Tsum | Ma_G | Md_G], not mu
-  const size_t base = (size_t)(static_cast<const char*>(v.gblk) - static_cast<const char*>(h->gblk_arena));
-  const size_t tsum = ((size_t)v.m_pad * v.KP * sizeof(float) + 255) / 256 * 256;
-  launch_block_push(h, 1, base, (tsum + 2 * (size_t)v.k * v.k * sizeof(double)) / 16 * 16, 0, 0);
-}
 // slice_chains: the own view's new F (g == 0) / G (g == 1) rows, as received, -> the operand copies of the next pass
 void launch_slice_unpack(resnmtf_handle* h, const ViewState& v, int g, bool checked) {
   SliceUnpackArgs a{};
-  a.in = g == 0 ? h->f_recv : h->g_recv; a.len = g == 0 ? v.n : v.m; a.k = v.k;
-  a.W32 = g == 0 ? v.F32 : v.G32; a.ld32 = 64; a.Wk = g == 0 ? v.Fk : v.Gk;
+  a.in = h->w_recv[g]; a.len = v.side[g].len; a.k = v.k;
+  a.W32 = v.side[g].W32; a.ld32 = 64; a.Wk = v.side[g].Wk;
   a.ctl = h->ctl; a.check_done = checked ? 1 : 0;
   launch(h, RESNMTF_TIMED_PACK, select_slice_unpack(v.KP), dim3(ceil_div(a.len, 32)), dim3(256), 0, a);
 }
@@ -825,7 +836,7 @@ int launch_s_chain(resnmtf_handle* h, bool checked) {
   a.restricted = sum_xi != 0.0 ? 1 : 0;
   for (int w = 0; w < V; ++w) {
     const ViewState& vs = h->views[w];
-    a.S[w] = vs.S; a.lambda[w] = vs.lambda; a.mu[w] = vs.mu; a.Ma_F[w] = vs.Ma_F; a.Md_F[w] = vs.Md_F;
+    a.S[w] = vs.S; a.lambda[w] = vs.side[SIDE_F].lm; a.mu[w] = vs.side[SIDE_G].lm; a.Ma_F[w] = vs.side[SIDE_F].Ma; a.Md_F[w] = vs.side[SIDE_F].Md;
     double sg = 0.0;
     for (int c = 0; c < V; ++c) {
       const double wgt = h->xi[(size_t)c + (size_t)w * V];                          // xi[c, w]
@@ -846,14 +857,14 @@ void enqueue_phase_g(resnmtf_handle* h, const ViewState& v, double tol, bool che
   const bool fuse_g = can_fuse_update(h, v, 1);
   if (!fuse_g) launch_update(h, v, 1, checked);
   launch_pass(h, v, true, 1, tol, checked, fuse_g);
-  launch_fold(h, v);
+  launch_fold(h, v, SIDE_F);
 }
 // run prologue of one view: X.G launch whose kk_s runs in mode 0 (F coefficients from the current S, G);
 // mode A first emits the fp64 partials of the current G so that a resumed run is bitwise identical
 void enqueue_prologue(resnmtf_handle* h, const ViewState& v) {
   if (v.kk_mode == 0) launch_update(h, v, 2, false);
   launch_pass(h, v, true, 0, -1.0, false);
-  launch_fold(h, v);
+  launch_fold(h, v, SIDE_F);
   if (h->sliced) launch_slice_pack(h, v, true, false);
   if (h->sliced && h->opt.slice_p2p) p2p_signal(h, 0);
 }
@@ -1155,7 +1166,10 @@ namespace {
 // slabs a sparse view's passes may write (the split count is chosen at upload, resnmtf_set_view_csc): at most 4 for X.G keeps
 // the views eligible for the fused F chain (f_chain_kernel keeps up to four raw split slabs per view); Xt.F: 16, the
 // consumer's prefetch depth, as for the dense passes
-constexpr int kSparseMaxSplitXg = 4, kSparseMaxSplitXtf = 16;
+constexpr int kSparseMaxSplit[2] = {4, 16};
+// what the allocations of a side are called in create's error messages
+struct SideNames { const char *factor, *mult, *slab, *image, *sparse; };
+constexpr SideNames kNames[2] = {{"F", "lambda", "Pxg", "Xt", "CSR"}, {"G", "mu", "Pxtf", "X", "CSC"}};
 int create_impl(int n_views, const int* n_rows, const int* n_cols, const int* k, const int* owned, const long long* nnz_capacity,
                 const resnmtf_options* opts, resnmtf_handle** out) {
   if (!out) { g_create_error = "out is NULL"; return RESNMTF_ERR_INVALID; }
@@ -1246,21 +1260,23 @@ int create_impl(int n_views, const int* n_rows, const int* n_cols, const int* k,
     vs.n = n_rows[v]; vs.m = n_cols[v]; vs.k = k[v];
     vs.NT = ceil_div(k[v], 16); vs.KP = 16 * vs.NT;
     vs.n_pad = round_up(vs.n, 64); vs.m_pad = round_up(vs.m, 64);
-    // tile-major images: tile t of X32 = columns 64 t .. 64 t + 63 of X as [n_pad][64], contiguous; one extra
-    // 256-B row per tile keeps the tile starts off a common power-of-two stride (memory channels)
+    // tile-major images: tile t of side s's image = its lines 64 t .. 64 t + 63 as [other side's pad][64], contiguous; one
+    // extra 256-B row per tile keeps the tile starts off a common power-of-two stride (memory channels)
     const size_t pad_rows = o.no_pitch_pad ? 0 : 1;
-    vs.ldx = ((size_t)vs.n_pad + pad_rows) * 64; vs.ldxt = ((size_t)vs.m_pad + pad_rows) * 64;
-    vs.x32_floats = (size_t)(vs.m_pad / 64) * vs.ldx; vs.xt32_floats = (size_t)(vs.n_pad / 64) * vs.ldxt;
+    for (int s = 0; s < 2; ++s) {
+      Side& sd = vs.side[s];
+      sd.len = s == SIDE_F ? vs.n : vs.m; sd.pad = round_up(sd.len, 64);
+      sd.ldx = ((size_t)(s == SIDE_F ? vs.m_pad : vs.n_pad) + pad_rows) * 64; sd.x_floats = (size_t)(sd.pad / 64) * sd.ldx;
+      sd.map.resize(n_views);
+    }
     vs.owned = owned ? owned[v] != 0 : true;
     vs.sparse = nnz_capacity && nnz_capacity[v] >= 0;
     vs.nnz_cap = vs.sparse ? nnz_capacity[v] : 0;
     if (!vs.owned) h->all_owned = false;
     else h->last_owned = v;
-    vs.row_map.resize(n_views);
-    vs.col_map.resize(n_views);
   }
-  auto bail = [&](hipError_t err, const char* what) {
-    g_create_error = std::string(what) + ": " + hipGetErrorString(err);
+  auto bail = [&](hipError_t err, const std::string& what) {
+    g_create_error = what + ": " + hipGetErrorString(err);
     resnmtf_destroy(h);
     return err == hipErrorOutOfMemory ? RESNMTF_ERR_ALLOC : RESNMTF_ERR_HIP;
   };
@@ -1274,45 +1290,40 @@ int create_impl(int n_views, const int* n_rows, const int* n_cols, const int* k,
   h->err_cap = 1024;
   if ((e = dev_alloc_zero(&h->err, (size_t)h->err_cap * n_views)) != hipSuccess) return bail(e, "hipMalloc err");
   if ((e = alloc_host_mirrors(h, h->err_cap)) != hipSuccess) return bail(e, "hipHostMalloc error mirror");
-  // replicate_f: one arena holds the F exchange block of every view, in view order (equal-shaped views
-  // give equal strides, so that one in-place all-gather moves every rank's block -- sharded.py)
-  auto fblk_usum_bytes = [](const ViewState& vs) { return ((size_t)vs.n_pad * vs.KP * sizeof(float) + 255) / 256 * 256; };
-  auto fblk_size = [&](const ViewState& vs) {
-    return (fblk_usum_bytes(vs) + (2 * (size_t)vs.k * vs.k + (size_t)vs.k) * sizeof(double) + 255) / 256 * 256;
-  };
-  // replicate_gs, equal-shaped F blocks: the S block of a view (k x k inputs of the S rule, written by the same pass launch
-  // that produces U) is appended to its F block, so that ONE all-gather after the X.G pass moves both -- two collectives per
-  // sweep between dependent steps instead of three
-  size_t sblk_tail_bytes = 0;
-  if (o.replicate_f && o.replicate_gs && !o.slice_chains) {      // (sliced chains: the S blocks travel on their own, beside the U slices)
-    bool equal = true;
-    for (const auto& vs : h->views) equal = equal && fblk_size(vs) == fblk_size(h->views[0]) && vs.k == h->views[0].k;
-    if (equal) {
-      const size_t kk0 = (size_t)h->views[0].k * h->views[0].k;
-      h->sblk_stride = (5 * kk0 + 2 * (size_t)h->views[0].k + 1 + 31) / 32 * 32;
-      sblk_tail_bytes = (h->sblk_stride * sizeof(double) + 255) / 256 * 256;
-      h->sblk_embedded = true;
-    }
-  }
-  if (o.replicate_f) {
-    for (const auto& vs : h->views) h->fblk_arena_bytes += fblk_size(vs) + sblk_tail_bytes;
-    if ((e = hipMalloc(&h->fblk_arena, h->fblk_arena_bytes)) != hipSuccess) return bail(e, "hipMalloc F exchange blocks");
-    if ((e = hipMemset(h->fblk_arena, 0, h->fblk_arena_bytes)) != hipSuccess) return bail(e, "hipMemset F exchange blocks");
-  }
-  auto gblk_tsum_bytes = [](const ViewState& vs) { return ((size_t)vs.m_pad * vs.KP * sizeof(float) + 255) / 256 * 256; };
-  auto gblk_size = [&](const ViewState& vs) {
-    return (gblk_tsum_bytes(vs) + (2 * (size_t)vs.k * vs.k + (size_t)vs.k) * sizeof(double) + 255) / 256 * 256;
+  // replicate_f / replicate_gs: one arena per side holds that side's exchange block of every view, in view order
+  // (equal-shaped views give equal strides, so that one in-place all-gather moves every rank's block -- sharded.py)
+  const bool replicated[2] = {o.replicate_f != 0, o.replicate_gs != 0};
+  auto sum_bytes = [](const ViewState& vs, int s) { return ((size_t)vs.side[s].pad * vs.KP * sizeof(float) + 255) / 256 * 256; };
+  auto blk_size = [&](const ViewState& vs, int s) {
+    return (sum_bytes(vs, s) + (2 * (size_t)vs.k * vs.k + (size_t)vs.k) * sizeof(double) + 255) / 256 * 256;
   };
   if (o.replicate_gs) {
     if (!o.replicate_f) { g_create_error = "replicate_gs needs replicate_f"; resnmtf_destroy(h); return RESNMTF_ERR_INVALID; }
     for (const auto& vs : h->views)
       if (vs.k != h->views[0].k) { g_create_error = "replicate_gs needs the same k in every view"; resnmtf_destroy(h); return RESNMTF_ERR_INVALID; }
-    for (const auto& vs : h->views) h->gblk_arena_bytes += gblk_size(vs);
-    if ((e = hipMalloc(&h->gblk_arena, h->gblk_arena_bytes)) != hipSuccess) return bail(e, "hipMalloc G exchange blocks");
-    if ((e = hipMemset(h->gblk_arena, 0, h->gblk_arena_bytes)) != hipSuccess) return bail(e, "hipMemset G exchange blocks");
+  }
+  // replicate_gs, equal-shaped F blocks: the S block of a view (k x k inputs of the S rule, written by the same pass launch
+  // that produces U) is appended to its F block, so that ONE all-gather after the X.G pass moves both -- two collectives per
+  // sweep between dependent steps instead of three
+  const size_t kk0 = (size_t)h->views[0].k * h->views[0].k;
+  if (o.replicate_gs) h->sblk_stride = (5 * kk0 + 2 * (size_t)h->views[0].k + 1 + 31) / 32 * 32;
+  size_t sblk_tail_bytes = 0;
+  if (o.replicate_f && o.replicate_gs && !o.slice_chains) {      // (sliced chains: the S blocks travel on their own, beside the U slices)
+    bool equal = true;
+    for (const auto& vs : h->views) equal = equal && blk_size(vs, SIDE_F) == blk_size(h->views[0], SIDE_F) && vs.k == h->views[0].k;
+    if (equal) {
+      sblk_tail_bytes = (h->sblk_stride * sizeof(double) + 255) / 256 * 256;
+      h->sblk_embedded = true;
+    }
+  }
+  for (int s = 0; s < 2; ++s) {
+    if (!replicated[s]) continue;
+    for (const auto& vs : h->views) h->arena_bytes[s] += blk_size(vs, s) + (s == SIDE_F ? sblk_tail_bytes : 0);
+    if ((e = hipMalloc(&h->arena[s], h->arena_bytes[s])) != hipSuccess) return bail(e, std::string("hipMalloc ") + kNames[s].factor + " exchange blocks");
+    if ((e = hipMemset(h->arena[s], 0, h->arena_bytes[s])) != hipSuccess) return bail(e, std::string("hipMemset ") + kNames[s].factor + " exchange blocks");
+  }
+  if (o.replicate_gs) {
     if (!h->sblk_embedded) {
-      const size_t kk0 = (size_t)h->views[0].k * h->views[0].k;
-      h->sblk_stride = (5 * kk0 + 2 * (size_t)h->views[0].k + 1 + 31) / 32 * 32;
       if ((e = dev_alloc_zero(&h->sblk_arena, h->sblk_stride * n_views)) != hipSuccess) return bail(e, "hipMalloc S exchange blocks");
       h->sblk_base = h->sblk_arena; h->sblk_step = h->sblk_stride;
     }
@@ -1322,21 +1333,19 @@ int create_impl(int n_views, const int* n_rows, const int* n_cols, const int* k,
     const ViewState& v0 = h->views[0];
     const int V = n_views;
     h->sliced = true;
-    h->sl_rows = round_up(ceil_div(v0.n, V), 32); h->sl_cols = round_up(ceil_div(v0.m, V), 32);
-    h->u_chunk = (size_t)h->sl_rows * v0.KP * sizeof(float);
-    h->t_chunk = ((size_t)h->sl_cols * v0.KP * sizeof(float) + 2 * (size_t)v0.k * v0.k * sizeof(double) + 255) / 256 * 256;
-    char** bufs[4] = {&h->u_send, &h->u_recv, &h->t_send, &h->t_recv};
-    for (int b = 0; b < 4; ++b) {
-      const size_t bytes = (b < 2 ? h->u_chunk : h->t_chunk) * V;
-      if ((e = hipMalloc(reinterpret_cast<void**>(bufs[b]), bytes)) != hipSuccess) return bail(e, "hipMalloc slice exchange buffers");
-      if ((e = hipMemset(*bufs[b], 0, bytes)) != hipSuccess) return bail(e, "hipMemset slice exchange buffers");
+    for (int s = 0; s < 2; ++s) {
+      h->sl_len[s] = round_up(ceil_div(v0.side[s].len, V), 32);
+      h->p_chunk[s] = (size_t)h->sl_len[s] * v0.KP * sizeof(float);
+      if (s == SIDE_G) h->p_chunk[s] = (h->p_chunk[s] + 2 * (size_t)v0.k * v0.k * sizeof(double) + 255) / 256 * 256;      // (+ the tail Ma_G | Md_G)
+      for (char** buf : {&h->p_send[s], &h->p_recv[s]}) {
+        if ((e = hipMalloc(reinterpret_cast<void**>(buf), h->p_chunk[s] * V)) != hipSuccess) return bail(e, "hipMalloc slice exchange buffers");
+        if ((e = hipMemset(*buf, 0, h->p_chunk[s] * V)) != hipSuccess) return bail(e, "hipMemset slice exchange buffers");
+      }
+      for (float** buf : {&h->w_send[s], &h->w_recv[s]})
+        if ((e = dev_alloc_zero(buf, (size_t)V * h->sl_len[s] * v0.KP)) != hipSuccess) return bail(e, "hipMalloc slice exchange buffers");
     }
-    if ((e = dev_alloc_zero(&h->f_send, (size_t)V * h->sl_rows * v0.KP)) != hipSuccess) return bail(e, "hipMalloc slice exchange buffers");
-    if ((e = dev_alloc_zero(&h->f_recv, (size_t)V * h->sl_rows * v0.KP)) != hipSuccess) return bail(e, "hipMalloc slice exchange buffers");
-    if ((e = dev_alloc_zero(&h->slice_nd, (size_t)V * 2 * (size_t)round_up(std::max(h->sl_rows, h->sl_cols), 16) * v0.KP)) != hipSuccess)
+    if ((e = dev_alloc_zero(&h->slice_nd, (size_t)V * 2 * (size_t)round_up(std::max(h->sl_len[SIDE_F], h->sl_len[SIDE_G]), 16) * v0.KP)) != hipSuccess)
       return bail(e, "hipMalloc slice product scratch");
-    if ((e = dev_alloc_zero(&h->g_send, (size_t)V * h->sl_cols * v0.KP)) != hipSuccess) return bail(e, "hipMalloc slice exchange buffers");
-    if ((e = dev_alloc_zero(&h->g_recv, (size_t)V * h->sl_cols * v0.KP)) != hipSuccess) return bail(e, "hipMalloc slice exchange buffers");
   }
   if (o.slice_p2p) {
     int can = 0;
@@ -1353,12 +1362,13 @@ int create_impl(int n_views, const int* n_rows, const int* n_cols, const int* k,
     h->peers.resize((size_t)n_views);
     h->block_p2p = !o.slice_chains;
   }
-  size_t fblk_off = 0, gblk_off = 0;
+  const int force_ns[2] = {o.pass_splits_xg, o.pass_splits_xtf};
+  size_t blk_off[2] = {0, 0};
   for (int v = 0; v < n_views; ++v) {
     ViewState& vs = h->views[v];
-    const size_t kk = (size_t)vs.k * vs.k;
-    if ((e = dev_alloc_zero(&vs.F, (size_t)vs.n * vs.k)) != hipSuccess) return bail(e, "hipMalloc F");
-    if ((e = dev_alloc_zero(&vs.G, (size_t)vs.m * vs.k)) != hipSuccess) return bail(e, "hipMalloc G");
+    const size_t kk = (size_t)vs.k * vs.k, kkp = (size_t)vs.KP * vs.KP;
+    for (int s = 0; s < 2; ++s)
+      if ((e = dev_alloc_zero(&vs.side[s].W, (size_t)vs.side[s].len * vs.k)) != hipSuccess) return bail(e, std::string("hipMalloc ") + kNames[s].factor);
     if ((e = dev_alloc_zero(&vs.S, kk)) != hipSuccess) return bail(e, "hipMalloc S");
     // ---- geometry (identical on every rank for a given view: n, m, k and the options decide it)
     // k x k mode (kernels.hip.inc, pass_kernel).  A (k <= 16): the update kernels emit fp64 partial
@@ -1374,30 +1384,10 @@ int create_impl(int n_views, const int* n_rows, const int* n_cols, const int* k,
     if (vs.sparse) vs.kk_mode = 0;                              // (sparse views: mode A at every k, the job in the spmm launch)
     // workgroup slots of a pass launch: target_workgroups overrides CUs x resident workgroups per CU
     const int nw_guess = (vs.NT <= 1 && (o.pass_waves == 4 || o.pass_waves == 8 || o.pass_waves == 16)) ? o.pass_waves : 8;
-    const int aux_cap = (vs.NT >= 2 && o.bf16_split != 2) ? 16 : 64;
-    size_aux(vs.m_pad, nw_guess, aux_cap, &vs.nsaux_xg, &vs.rpsaux_xg);
-    size_aux(vs.n_pad, nw_guess, aux_cap, &vs.nsaux_xtf, &vs.rpsaux_xtf);
+    const bool wide = vs.NT >= 2 && o.bf16_split != 2;          // k > 16: the wide bf16-piece form
+    const int aux_cap = wide ? 16 : 64;
     const int slots_all = o.target_workgroups > 0 ? o.target_workgroups : h->n_cu * pass_blocks_per_cu(vs.NT, nw_guess);
-    const int slots_xg = slots_all - (vs.kk_mode == 0 ? 1 : 3 * vs.nsaux_xg);
-    const int slots_xtf = slots_all - (vs.kk_mode == 0 ? 1 : 2 * vs.nsaux_xtf);
     const bool fine = o.x_half == 0;
-    size_pass(vs.NT, vs.n_pad / 64, vs.m_pad, slots_xg, max_pass_waves(vs.NT), o.pass_waves, o.pass_splits_xg, fine,
-              &vs.nsplit_xg, &vs.rps_xg, &vs.nw_xg);
-    size_pass(vs.NT, vs.m_pad / 64, vs.n_pad, slots_xtf, max_pass_waves(vs.NT), o.pass_waves, o.pass_splits_xtf, fine,
-              &vs.nsplit_xtf, &vs.rps_xtf, &vs.nw_xtf);
-    if (vs.NT >= 2 && o.bf16_split != 2) {      // k > 16: the wide bf16-piece form
-      const WidePlan pg = plan_wide(vs.n_pad / 64, vs.m_pad, vs.KP, vs.kk_mode == 0 ? 0 : 3, slots_all, o.pass_splits_xg, nw_guess);
-      const WidePlan pf = plan_wide(vs.m_pad / 64, vs.n_pad, vs.KP, vs.kk_mode == 0 ? 0 : 2, slots_all, o.pass_splits_xtf, nw_guess);
-      vs.tw_xg = pg.tw; vs.nsplit_xg = pg.nsplit; vs.rps_xg = pg.rps;
-      vs.tw_xtf = pf.tw; vs.nsplit_xtf = pf.nsplit; vs.rps_xtf = pf.rps;
-      if (vs.kk_mode != 0) { vs.nsaux_xg = pg.nsaux; vs.rpsaux_xg = pg.rpsaux; vs.nsaux_xtf = pf.nsaux; vs.rpsaux_xtf = pf.rpsaux; }
-    }
-    // k <= 16: when the workgroups of a pass outnumber the slots (streamed geometry) each wave keeps the next
-    // trip's loads in flight while it multiplies (two buffers of 4 steps instead of one of 8): X.G pass of a
-    // 40000 x 2000 view 74 -> 67 us.  With everything resident from t = 0 (c2) the plain form is faster.
-    vs.pp_xg = vs.NT == 1 && vs.nw_xg == 8 && (vs.n_pad / 64) * vs.nsplit_xg > slots_xg;
-    vs.pp_xtf = vs.NT == 1 && vs.nw_xtf == 8 && (vs.m_pad / 64) * vs.nsplit_xtf > slots_xtf;
-    if (vs.sparse) { vs.nsplit_xg = kSparseMaxSplitXg; vs.nsplit_xtf = kSparseMaxSplitXtf; vs.pp_xg = vs.pp_xtf = false; }   // (slab capacity; set at upload)
     const int RG = update_threads(vs.KP) / vs.KP;
     // update workgroups: mode A ~160 (few partials for the k x k job, two prefetched row groups each
     // at c2 -- tools/tune_c2.py); mode B (k > 16) ONE round of resident workgroups -- one 1024-thread workgroup per CU
@@ -1406,101 +1396,86 @@ int create_impl(int n_views, const int* n_rows, const int* n_cols, const int* k,
     // did it: tools/ab_update_blocks.sh, F update 61 -> 43 us at c5, 13.5 -> 11.8 at c4; G 19 -> 14.5 at c5)
     const int nblk_round = h->n_cu * (update_threads(vs.KP) >= 1024 ? 1 : 2);
     const int nblk_target = o.update_blocks > 0 ? o.update_blocks : (vs.kk_mode == 0 ? (xbytes <= ((size_t)256 << 20) ? 160 : 512) : nblk_round);
-    vs.rpbF = round_up(std::max(RG, ceil_div(vs.n, nblk_target)), RG); vs.nblkF = ceil_div(vs.n, vs.rpbF);
-    vs.rpbG = round_up(std::max(RG, ceil_div(vs.m, nblk_target)), RG); vs.nblkG = ceil_div(vs.m, vs.rpbG);
-    const size_t kkp = (size_t)vs.KP * vs.KP;
-    // ---- the F update's inputs.  replicate_f: one contiguous exchange block per view, on every rank
-    // (the sharded driver broadcasts it from the owner and runs the F update of coupled views everywhere)
-    const size_t pxg_floats = (size_t)vs.nsplit_xg * vs.n_pad * vs.KP;
-    if (o.replicate_f) {
-      vs.fblk_bytes = fblk_size(vs) + sblk_tail_bytes;
-      char* base = static_cast<char*>(h->fblk_arena) + fblk_off;
-      if (h->sblk_embedded) {
-        vs.sblk = reinterpret_cast<double*>(base + fblk_size(vs));
-        if (v == 0) { h->sblk_base = vs.sblk; h->sblk_step = vs.fblk_bytes / sizeof(double); }
+    for (int s = 0; s < 2; ++s) {      // the pass that feeds side s: pad / 64 tiles, reduction over the other side's lines
+      Side& sd = vs.side[s];
+      const int ntiles = sd.pad / 64, rows_pad = vs.side[other(s)].pad;
+      const int kinds = vs.kk_mode == 0 ? 0 : kAuxKinds[s];
+      size_aux(rows_pad, nw_guess, aux_cap, &sd.nsaux, &sd.rpsaux);
+      const int slots = slots_all - (kinds == 0 ? 1 : kinds * sd.nsaux);
+      size_pass(vs.NT, ntiles, rows_pad, slots, max_pass_waves(vs.NT), o.pass_waves, force_ns[s], fine, &sd.nsplit, &sd.rps, &sd.nw);
+      if (wide) {
+        const WidePlan pw = plan_wide(ntiles, rows_pad, vs.KP, kinds, slots_all, force_ns[s], nw_guess);
+        sd.tw = pw.tw; sd.nsplit = pw.nsplit; sd.rps = pw.rps;
+        if (kinds != 0) { sd.nsaux = pw.nsaux; sd.rpsaux = pw.rpsaux; }
       }
-      fblk_off += vs.fblk_bytes;
-      vs.fblk = base;
-      vs.Usum = reinterpret_cast<float*>(base);
-      vs.Ma_F = reinterpret_cast<double*>(base + fblk_usum_bytes(vs));
-      vs.Md_F = vs.Ma_F + kk;
-      vs.lambda = vs.Md_F + kk;
-      if (!vs.owned) {
-        vs.f_replica = true;
-        if ((e = dev_alloc_zero(&vs.F32, (size_t)vs.n_pad * 64)) != hipSuccess) return bail(e, "hipMalloc F32");
-        if (vs.kk_mode == 0 && (e = dev_alloc_zero(&vs.partF, (size_t)vs.nblkF * (kkp + vs.KP))) != hipSuccess) return bail(e, "hipMalloc partF");
-      }
+      // k <= 16: when the workgroups of a pass outnumber the slots (streamed geometry) each wave keeps the next
+      // trip's loads in flight while it multiplies (two buffers of 4 steps instead of one of 8): X.G pass of a
+      // 40000 x 2000 view 74 -> 67 us.  With everything resident from t = 0 (c2) the plain form is faster.
+      sd.pp = vs.NT == 1 && sd.nw == 8 && ntiles * sd.nsplit > slots;
+      if (vs.sparse) { sd.nsplit = kSparseMaxSplit[s]; sd.pp = false; }   // (slab capacity; set at upload)
+      sd.rpb = round_up(std::max(RG, ceil_div(sd.len, nblk_target)), RG); sd.nblk = ceil_div(sd.len, sd.rpb);
     }
-    if (o.replicate_gs) {
-      vs.gblk_bytes = gblk_size(vs);
-      char* base = static_cast<char*>(h->gblk_arena) + gblk_off;
-      gblk_off += vs.gblk_bytes;
-      vs.gblk = base;
-      vs.Tsum = reinterpret_cast<float*>(base);
-      vs.Ma_G = reinterpret_cast<double*>(base + gblk_tsum_bytes(vs));
-      vs.Md_G = vs.Ma_G + kk;
-      vs.mu = vs.Md_G + kk;
-      if (!h->sblk_embedded) vs.sblk = h->sblk_arena + (size_t)v * h->sblk_stride;
-      if (!vs.owned) {                // (a G replica writes the same copies as the owner: nobody reads them here)
-        vs.g_replica = true;
-        if ((e = dev_alloc_zero(&vs.G32, (size_t)vs.m_pad * 64)) != hipSuccess) return bail(e, "hipMalloc G32");
-        if ((e = dev_alloc_zero(&vs.T32, (size_t)vs.m_pad * 64)) != hipSuccess) return bail(e, "hipMalloc T32");
-        if (vs.kk_mode == 0 && (e = dev_alloc_zero(&vs.partG, (size_t)vs.nblkG * (2 * kkp + vs.KP))) != hipSuccess) return bail(e, "hipMalloc partG");
+    // mode A: fp64 partials of the update workgroups (G: the cross product T^T G beside the Gram)
+    auto part_count = [&](int s) { return (size_t)vs.side[s].nblk * ((s == SIDE_F ? 1 : 2) * kkp + vs.KP); };
+    // ---- the updates' inputs.  replicate_f / replicate_gs: one contiguous exchange block per view and side, on every rank
+    // (the sharded driver broadcasts it from the owner and runs the update of coupled views everywhere)
+    for (int s = 0; s < 2; ++s) {
+      if (!replicated[s]) continue;
+      Side& sd = vs.side[s];
+      sd.xblk_bytes = blk_size(vs, s) + (s == SIDE_F ? sblk_tail_bytes : 0);
+      char* base = static_cast<char*>(h->arena[s]) + blk_off[s];
+      blk_off[s] += sd.xblk_bytes;
+      sd.xblk = base;
+      sd.xsum = reinterpret_cast<float*>(base);
+      sd.Ma = reinterpret_cast<double*>(base + sum_bytes(vs, s));
+      sd.Md = sd.Ma + kk;
+      sd.lm = sd.Md + kk;
+      if (s == SIDE_F && h->sblk_embedded) {
+        vs.sblk = reinterpret_cast<double*>(base + blk_size(vs, s));
+        if (v == 0) { h->sblk_base = vs.sblk; h->sblk_step = sd.xblk_bytes / sizeof(double); }
+      }
+      if (s == SIDE_G && !h->sblk_embedded) vs.sblk = h->sblk_arena + (size_t)v * h->sblk_stride;
+      if (!vs.owned) {                // (a replica writes the same copies as the owner: nobody reads them here)
+        sd.replica = true;
+        if ((e = dev_alloc_zero(&sd.W32, (size_t)sd.pad * 64)) != hipSuccess) return bail(e, std::string("hipMalloc ") + kNames[s].factor + "32");
+        if (s == SIDE_G && (e = dev_alloc_zero(&vs.T32, (size_t)sd.pad * 64)) != hipSuccess) return bail(e, "hipMalloc T32");
+        if (vs.kk_mode == 0 && (e = dev_alloc_zero(&sd.part, part_count(s))) != hipSuccess) return bail(e, std::string("hipMalloc part") + kNames[s].factor);
       }
     }
     if (!vs.owned) continue;
-    if ((e = dev_alloc_zero(&vs.Pxg, pxg_floats)) != hipSuccess) return bail(e, "hipMalloc Pxg");
-    if (!o.replicate_f) {
-      if ((e = dev_alloc_zero(&vs.lambda, (size_t)vs.k)) != hipSuccess) return bail(e, "hipMalloc lambda");
-      for (double** pp : {&vs.Ma_F, &vs.Md_F})
-        if ((e = dev_alloc_zero(pp, kk)) != hipSuccess) return bail(e, "hipMalloc kxk");
-    }
-    if (!o.replicate_gs && (e = dev_alloc_zero(&vs.mu, (size_t)vs.k)) != hipSuccess) return bail(e, "hipMalloc mu");
-    if ((e = dev_alloc_zero(&vs.xnorm2, 1)) != hipSuccess) return bail(e, "hipMalloc xnorm2");
-    if (vs.sparse) {                  // CSC + CSR at the declared capacity, no dense image (x_half never applies)
-      const size_t cap = (size_t)std::max<long long>(vs.nnz_cap, 1);
-      if ((e = dev_alloc_zero(&vs.cp, (size_t)vs.m + 1)) != hipSuccess) return bail(e, "hipMalloc CSC pointers");
-      if ((e = dev_alloc_zero(&vs.rp, (size_t)vs.n + 1)) != hipSuccess) return bail(e, "hipMalloc CSR pointers");
-      if ((e = dev_alloc_zero(&vs.ri, cap)) != hipSuccess) return bail(e, "hipMalloc CSC indices");
-      if ((e = dev_alloc_zero(&vs.ci, cap)) != hipSuccess) return bail(e, "hipMalloc CSR indices");
-      if ((e = dev_alloc_zero(&vs.vcsc, cap)) != hipSuccess) return bail(e, "hipMalloc CSC values");
-      if ((e = dev_alloc_zero(&vs.vcsr, cap)) != hipSuccess) return bail(e, "hipMalloc CSR values");
-    } else {
-      if ((e = dev_alloc_zero(&vs.X32, vs.x32_floats)) != hipSuccess) return bail(e, "hipMalloc X32");
-      if ((e = dev_alloc_zero(&vs.Xt32, vs.xt32_floats)) != hipSuccess) return bail(e, "hipMalloc Xt32");
-    }
-    vs.half = !vs.sparse && (o.x_half >= 1 && o.x_half <= 3) && vs.NT == 1 && vs.kk_mode == 0 && vs.nw_xg == 8 && vs.nw_xtf == 8;
+    vs.half = !vs.sparse && (o.x_half >= 1 && o.x_half <= 3) && vs.NT == 1 && vs.kk_mode == 0 && vs.side[SIDE_F].nw == 8 && vs.side[SIDE_G].nw == 8;
     vs.u16 = vs.half && o.x_half >= 2;
     vs.half_capable = vs.half;
-    if (vs.half) {      // one spare row group per tile keeps the tile starts off a common power-of-two stride
-      vs.ld16x = ((size_t)vs.n_pad + 4) * 64; vs.ld16xt = ((size_t)vs.m_pad + 4) * 64;
-      vs.x16_halves = (size_t)(vs.m_pad / 64) * vs.ld16x; vs.xt16_halves = (size_t)(vs.n_pad / 64) * vs.ld16xt;
-      if ((e = dev_alloc_zero(&vs.X16, vs.x16_halves)) != hipSuccess) return bail(e, "hipMalloc X16");
-      if ((e = dev_alloc_zero(&vs.Xt16, vs.xt16_halves)) != hipSuccess) return bail(e, "hipMalloc Xt16");
+    for (int s = 0; s < 2; ++s) {
+      Side& sd = vs.side[s];
+      if ((e = dev_alloc_zero(&sd.P, (size_t)sd.nsplit * sd.pad * vs.KP)) != hipSuccess) return bail(e, std::string("hipMalloc ") + kNames[s].slab);
+      if (!replicated[s]) {
+        if ((e = dev_alloc_zero(&sd.lm, (size_t)vs.k)) != hipSuccess) return bail(e, std::string("hipMalloc ") + kNames[s].mult);
+        for (double** pp : {&sd.Ma, &sd.Md})
+          if ((e = dev_alloc_zero(pp, kk)) != hipSuccess) return bail(e, "hipMalloc kxk");
+      }
+      if (vs.sparse) {                // CSC + CSR at the declared capacity, no dense image (x_half never applies)
+        const size_t cap = (size_t)std::max<long long>(vs.nnz_cap, 1);
+        if ((e = dev_alloc_zero(&sd.sp_ptr, (size_t)sd.len + 1)) != hipSuccess) return bail(e, std::string("hipMalloc ") + kNames[s].sparse + " pointers");
+        if ((e = dev_alloc_zero(&sd.sp_idx, cap)) != hipSuccess) return bail(e, std::string("hipMalloc ") + kNames[s].sparse + " indices");
+        if ((e = dev_alloc_zero(&sd.sp_val, cap)) != hipSuccess) return bail(e, std::string("hipMalloc ") + kNames[s].sparse + " values");
+      } else if ((e = dev_alloc_zero(&sd.X, sd.x_floats)) != hipSuccess) return bail(e, std::string("hipMalloc ") + kNames[s].image + "32");
+      if (vs.half) {      // one spare row group per tile keeps the tile starts off a common power-of-two stride
+        sd.ld16 = ((size_t)vs.side[other(s)].pad + 4) * 64; sd.x16_halves = (size_t)(sd.pad / 64) * sd.ld16;
+        if ((e = dev_alloc_zero(&sd.X16, sd.x16_halves)) != hipSuccess) return bail(e, std::string("hipMalloc ") + kNames[s].image + "16");
+      }
+      if ((e = dev_alloc_zero(&sd.W32, (size_t)sd.pad * 64)) != hipSuccess) return bail(e, std::string("hipMalloc ") + kNames[s].factor + "32");
+      if (vs.NT >= 2 && (e = dev_alloc_zero(&sd.Wk, (size_t)sd.pad * vs.KP * 3)) != hipSuccess) return bail(e, std::string("hipMalloc ") + kNames[s].factor + "k");
+      if ((e = dev_alloc_zero(&sd.cnt, 4)) != hipSuccess) return bail(e, "hipMalloc cnt");
+      if ((e = dev_alloc_zero(&sd.Paux, (size_t)kAuxKinds[s] * sd.nsaux * 64 * vs.KP)) != hipSuccess) return bail(e, "hipMalloc Paux");
+      if (vs.kk_mode == 0 && (e = dev_alloc_zero(&sd.part, part_count(s))) != hipSuccess) return bail(e, std::string("hipMalloc part") + kNames[s].factor);
     }
-    if ((e = dev_alloc_zero(&vs.F32, (size_t)vs.n_pad * 64)) != hipSuccess) return bail(e, "hipMalloc F32");
-    if ((e = dev_alloc_zero(&vs.G32, (size_t)vs.m_pad * 64)) != hipSuccess) return bail(e, "hipMalloc G32");
+    if ((e = dev_alloc_zero(&vs.xnorm2, 1)) != hipSuccess) return bail(e, "hipMalloc xnorm2");
     if ((e = dev_alloc_zero(&vs.T32, (size_t)vs.m_pad * 64)) != hipSuccess) return bail(e, "hipMalloc T32");
-    if (vs.NT >= 2) {
-      if ((e = dev_alloc_zero(&vs.Fk, (size_t)vs.n_pad * vs.KP * 3)) != hipSuccess) return bail(e, "hipMalloc Fk");
-      if ((e = dev_alloc_zero(&vs.Gk, (size_t)vs.m_pad * vs.KP * 3)) != hipSuccess) return bail(e, "hipMalloc Gk");
-    }
     if ((e = dev_alloc_zero(&vs.fuse_cnt, 4)) != hipSuccess) return bail(e, "hipMalloc cnt");
-    if ((e = dev_alloc_zero(&vs.cnt_xg, 4)) != hipSuccess) return bail(e, "hipMalloc cnt");
-    if ((e = dev_alloc_zero(&vs.cnt_xtf, 4)) != hipSuccess) return bail(e, "hipMalloc cnt");
     for (double** pp : {&vs.FtF, &vs.FtFS})
       if ((e = dev_alloc_zero(pp, kk)) != hipSuccess) return bail(e, "hipMalloc kxk");
-    if (!o.replicate_gs)
-      for (double** pp : {&vs.Ma_G, &vs.Md_G})
-        if ((e = dev_alloc_zero(pp, kk)) != hipSuccess) return bail(e, "hipMalloc kxk");
     if ((e = dev_alloc_zero(&vs.cF, (size_t)vs.k)) != hipSuccess) return bail(e, "hipMalloc cF");
-    if ((e = dev_alloc_zero(&vs.Pxtf, (size_t)vs.nsplit_xtf * vs.m_pad * vs.KP)) != hipSuccess) return bail(e, "hipMalloc Pxtf");
-    if ((e = dev_alloc_zero(&vs.Paux_xg, (size_t)3 * vs.nsaux_xg * 64 * vs.KP)) != hipSuccess) return bail(e, "hipMalloc Paux");
-    if ((e = dev_alloc_zero(&vs.Paux_xtf, (size_t)2 * vs.nsaux_xtf * 64 * vs.KP)) != hipSuccess) return bail(e, "hipMalloc Paux");
-    if (vs.kk_mode == 0) {
-      if ((e = dev_alloc_zero(&vs.partF, (size_t)vs.nblkF * (kkp + vs.KP))) != hipSuccess) return bail(e, "hipMalloc partF");
-      if ((e = dev_alloc_zero(&vs.partG, (size_t)vs.nblkG * (2 * kkp + vs.KP))) != hipSuccess) return bail(e, "hipMalloc partG");
-    }
   }
   if ((e = set_all_attrs()) != hipSuccess) return bail(e, "hipFuncSetAttribute");
   // the zero fills above ran on the NULL stream, which the handle's (non-blocking) stream does not wait
@@ -1538,14 +1513,14 @@ int resnmtf_destroy(resnmtf_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   destroy_graphs(h);
   for (auto& v : h->views) free_view(v);
-  if (h->fblk_arena) (void)hipFree(h->fblk_arena);
-  if (h->gblk_arena) (void)hipFree(h->gblk_arena);
+  if (h->arena[SIDE_F]) (void)hipFree(h->arena[SIDE_F]);
+  if (h->arena[SIDE_G]) (void)hipFree(h->arena[SIDE_G]);
   if (h->sblk_arena) (void)hipFree(h->sblk_arena);
   for (auto& pc : h->peers)
     for (void* q : pc.opened)
       if (q) (void)hipIpcCloseMemHandle(q);
-  for (void* p : {(void*)h->slice_nd, (void*)h->p2p_flags, (void*)h->view_sweep, (void*)h->u_send, (void*)h->u_recv, (void*)h->t_send, (void*)h->t_recv, (void*)h->f_send,
-                  (void*)h->f_recv, (void*)h->g_send, (void*)h->g_recv})
+  for (void* p : {(void*)h->slice_nd, (void*)h->p2p_flags, (void*)h->view_sweep, (void*)h->p_send[SIDE_F], (void*)h->p_recv[SIDE_F], (void*)h->p_send[SIDE_G], (void*)h->p_recv[SIDE_G], (void*)h->w_send[SIDE_F],
+                  (void*)h->w_recv[SIDE_F], (void*)h->w_send[SIDE_G], (void*)h->w_recv[SIDE_G]})
     if (p) (void)hipFree(p);
   if (h->ctl) (void)hipFree(h->ctl);
   if (h->err) (void)hipFree(h->err);
@@ -1574,7 +1549,7 @@ int build_half_images(resnmtf_handle* h, ViewState& vs) {
   hipError_t e = hipMemsetAsync(scratch, 0, 3 * sizeof(double), h->stream);
   unsigned int bits = 0;
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(max_entry_kernel, dim3(1024), dim3(256), 0, h->stream, vs.X32, vs.x32_floats,
+    hipLaunchKernelGGL(max_entry_kernel, dim3(1024), dim3(256), 0, h->stream, vs.side[SIDE_G].X, vs.side[SIDE_G].x_floats,
                        reinterpret_cast<unsigned int*>(scratch));
     e = hipMemcpyAsync(&bits, scratch, sizeof(bits), hipMemcpyDeviceToHost, h->stream);
   }
@@ -1591,9 +1566,9 @@ int build_half_images(resnmtf_handle* h, ViewState& vs) {
     vs.xscale = vs.u16 ? 65535.f / mx : std::ldexp(1.f, 14 - ex);
   }
   hipLaunchKernelGGL(pack_half_kernel, dim3((unsigned)(((size_t)(vs.n_pad / 4) * 64 * (vs.m_pad / 64) + 255) / 256)), dim3(256), 0,
-                     h->stream, vs.X32, vs.ldx, vs.n_pad, vs.m_pad / 64, vs.xscale, vs.X16, vs.ld16x, vs.u16 ? 1 : 0, scratch + 1);
+                     h->stream, vs.side[SIDE_G].X, vs.side[SIDE_G].ldx, vs.n_pad, vs.m_pad / 64, vs.xscale, vs.side[SIDE_G].X16, vs.side[SIDE_G].ld16, vs.u16 ? 1 : 0, scratch + 1);
   hipLaunchKernelGGL(pack_half_kernel, dim3((unsigned)(((size_t)(vs.m_pad / 4) * 64 * (vs.n_pad / 64) + 255) / 256)), dim3(256), 0,
-                     h->stream, vs.Xt32, vs.ldxt, vs.m_pad, vs.n_pad / 64, vs.xscale, vs.Xt16, vs.ld16xt, vs.u16 ? 1 : 0,
+                     h->stream, vs.side[SIDE_F].X, vs.side[SIDE_F].ldx, vs.m_pad, vs.n_pad / 64, vs.xscale, vs.side[SIDE_F].X16, vs.side[SIDE_F].ld16, vs.u16 ? 1 : 0,
                      (double*)nullptr);
   double host[2] = {0.0, 0.0};
   e = hipGetLastError();
@@ -1607,12 +1582,12 @@ int build_half_images(resnmtf_handle* h, ViewState& vs) {
   if (use != vs.half) {               // the factor operand copies follow the image's layout: rewrite them
     vs.half = use;
     if (vs.has_factors) {
-      HIP_TRY(h, hipMemsetAsync(vs.F32, 0, (size_t)vs.n_pad * 64 * sizeof(float), h->stream));
-      HIP_TRY(h, hipMemsetAsync(vs.G32, 0, (size_t)vs.m_pad * 64 * sizeof(float), h->stream));
-      hipLaunchKernelGGL(factor_to_f32_kernel, dim3(ceil_div(vs.n * vs.k, 256)), dim3(256), 0, h->stream, vs.F, vs.n,
-                         vs.k, vs.F32, vs.kk_mode == 0 ? vs.KP : 64, vs.NT, vs.half ? 1 : 0, vs.Fk);
-      hipLaunchKernelGGL(factor_to_f32_kernel, dim3(ceil_div(vs.m * vs.k, 256)), dim3(256), 0, h->stream, vs.G, vs.m,
-                         vs.k, vs.G32, vs.kk_mode == 0 ? vs.KP : 64, vs.NT, vs.half ? 1 : 0, vs.Gk);
+      HIP_TRY(h, hipMemsetAsync(vs.side[SIDE_F].W32, 0, (size_t)vs.n_pad * 64 * sizeof(float), h->stream));
+      HIP_TRY(h, hipMemsetAsync(vs.side[SIDE_G].W32, 0, (size_t)vs.m_pad * 64 * sizeof(float), h->stream));
+      hipLaunchKernelGGL(factor_to_f32_kernel, dim3(ceil_div(vs.n * vs.k, 256)), dim3(256), 0, h->stream, vs.side[SIDE_F].W, vs.n,
+                         vs.k, vs.side[SIDE_F].W32, vs.kk_mode == 0 ? vs.KP : 64, vs.NT, vs.half ? 1 : 0, vs.side[SIDE_F].Wk);
+      hipLaunchKernelGGL(factor_to_f32_kernel, dim3(ceil_div(vs.m * vs.k, 256)), dim3(256), 0, h->stream, vs.side[SIDE_G].W, vs.m,
+                         vs.k, vs.side[SIDE_G].W32, vs.kk_mode == 0 ? vs.KP : 64, vs.NT, vs.half ? 1 : 0, vs.side[SIDE_G].Wk);
       HIP_TRY(h, hipGetLastError());
       HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
@@ -1671,13 +1646,13 @@ int upload_view(resnmtf_handle* h, int v, const double* x, bool raw, int* was_ne
       if (e == hipSuccess) e = hipMemcpyAsync(line_counts.data(), counts, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream);
     }
   }
-  if (e == hipSuccess) e = hipMemsetAsync(vs.X32, 0, vs.x32_floats * sizeof(float), h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(vs.Xt32, 0, vs.xt32_floats * sizeof(float), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(vs.side[SIDE_G].X, 0, vs.side[SIDE_G].x_floats * sizeof(float), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(vs.side[SIDE_F].X, 0, vs.side[SIDE_F].x_floats * sizeof(float), h->stream);
   if (e == hipSuccess && raw) e = hipMemsetAsync(neg, 0, sizeof(double), h->stream);
   if (e == hipSuccess) {
     if (raw) hipLaunchKernelGGL(column_stats_kernel, dim3(vs.m), dim3(256), 0, h->stream, staging, vs.n, vs.m, shift, colsum, neg);
-    hipLaunchKernelGGL(convert_x_kernel, grid, dim3(256), 0, h->stream, staging, vs.n, vs.m, vs.X32, vs.ldx,
-                       vs.Xt32, vs.ldxt, partial, shift, colsum);
+    hipLaunchKernelGGL(convert_x_kernel, grid, dim3(256), 0, h->stream, staging, vs.n, vs.m, vs.side[SIDE_G].X, vs.side[SIDE_G].ldx,
+                       vs.side[SIDE_F].X, vs.side[SIDE_F].ldx, partial, shift, colsum);
     hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, h->stream, partial, nparts, vs.xnorm2);
     e = hipGetLastError();
   }
@@ -1759,27 +1734,27 @@ struct SparsePlan {
 hipError_t upload_sparse_plan(resnmtf_handle* h, ViewState& vs, const std::vector<long long>& rp, const std::vector<long long>& cp,
                               SparsePlan& pl) {
   const int groups = spmm_groups_host(vs.KP);
-  plan_sparse(rp, vs.n, groups, h->n_cu, kSparseMaxSplitXg, &pl.ns_xg, &pl.nb_xg, pl.bxg);
-  plan_sparse(cp, vs.m, groups, h->n_cu, kSparseMaxSplitXtf, &pl.ns_xtf, &pl.nb_xtf, pl.bxtf);
+  plan_sparse(rp, vs.n, groups, h->n_cu, kSparseMaxSplit[SIDE_F], &pl.ns_xg, &pl.nb_xg, pl.bxg);
+  plan_sparse(cp, vs.m, groups, h->n_cu, kSparseMaxSplit[SIDE_G], &pl.ns_xtf, &pl.nb_xtf, pl.bxtf);
   hipError_t e = hipSuccess;
-  if (pl.nb_xg != vs.nblk_xg || !vs.blk_xg) {
-    if (vs.blk_xg) (void)hipFree(vs.blk_xg);
-    vs.blk_xg = nullptr;
-    e = hipMalloc(reinterpret_cast<void**>(&vs.blk_xg), pl.bxg.size() * sizeof(int));
+  if (pl.nb_xg != vs.side[SIDE_F].sp_nblk || !vs.side[SIDE_F].sp_blk) {
+    if (vs.side[SIDE_F].sp_blk) (void)hipFree(vs.side[SIDE_F].sp_blk);
+    vs.side[SIDE_F].sp_blk = nullptr;
+    e = hipMalloc(reinterpret_cast<void**>(&vs.side[SIDE_F].sp_blk), pl.bxg.size() * sizeof(int));
   }
-  if (e == hipSuccess && (pl.nb_xtf != vs.nblk_xtf || !vs.blk_xtf)) {
-    if (vs.blk_xtf) (void)hipFree(vs.blk_xtf);
-    vs.blk_xtf = nullptr;
-    e = hipMalloc(reinterpret_cast<void**>(&vs.blk_xtf), pl.bxtf.size() * sizeof(int));
+  if (e == hipSuccess && (pl.nb_xtf != vs.side[SIDE_G].sp_nblk || !vs.side[SIDE_G].sp_blk)) {
+    if (vs.side[SIDE_G].sp_blk) (void)hipFree(vs.side[SIDE_G].sp_blk);
+    vs.side[SIDE_G].sp_blk = nullptr;
+    e = hipMalloc(reinterpret_cast<void**>(&vs.side[SIDE_G].sp_blk), pl.bxtf.size() * sizeof(int));
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(vs.blk_xg, pl.bxg.data(), pl.bxg.size() * sizeof(int), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(vs.blk_xtf, pl.bxtf.data(), pl.bxtf.size() * sizeof(int), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(vs.side[SIDE_F].sp_blk, pl.bxg.data(), pl.bxg.size() * sizeof(int), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(vs.side[SIDE_G].sp_blk, pl.bxtf.data(), pl.bxtf.size() * sizeof(int), hipMemcpyHostToDevice, h->stream);
   return e;
 }
 void commit_sparse_upload(resnmtf_handle* h, ViewState& vs, const SparsePlan& pl, long long nnz) {
   vs.nnz = nnz;
-  vs.nblk_xg = pl.nb_xg; vs.nblk_xtf = pl.nb_xtf;
-  vs.nsplit_xg = pl.ns_xg; vs.nsplit_xtf = pl.ns_xtf;
+  vs.side[SIDE_F].sp_nblk = pl.nb_xg; vs.side[SIDE_G].sp_nblk = pl.nb_xtf;
+  vs.side[SIDE_F].nsplit = pl.ns_xg; vs.side[SIDE_G].nsplit = pl.ns_xtf;
   vs.has_x = true;
   h->prepared = false;          // the slab count of the updates follows the upload
 }
@@ -1846,18 +1821,18 @@ int resnmtf_set_view_csc(resnmtf_handle* h, int v, const long long* col_ptr, con
   auto up = [&](void* dst, const void* src, size_t bytes) {
     if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
   };
-  up(vs.cp, cp.data(), cp.size() * sizeof(long long));
-  up(vs.rp, rp.data(), rp.size() * sizeof(long long));
-  up(vs.ri, row_idx, (size_t)nnz * sizeof(int));
-  up(vs.ci, ci.data(), ci.size() * sizeof(int));
+  up(vs.side[SIDE_G].sp_ptr, cp.data(), cp.size() * sizeof(long long));
+  up(vs.side[SIDE_F].sp_ptr, rp.data(), rp.size() * sizeof(long long));
+  up(vs.side[SIDE_G].sp_idx, row_idx, (size_t)nnz * sizeof(int));
+  up(vs.side[SIDE_F].sp_idx, ci.data(), ci.size() * sizeof(int));
   up(v64, values, (size_t)nnz * sizeof(double));
   up(dperm, perm.data(), perm.size() * sizeof(long long));
   if (e == hipSuccess) e = upload_sparse_plan(h, vs, rp, cp, pl);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(csc_normalise_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, h->stream, vs.cp, v64, m, pre_processed ? 0 : 1,
-                       vs.vcsc, sq);
+    hipLaunchKernelGGL(csc_normalise_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, h->stream, vs.side[SIDE_G].sp_ptr, v64, m, pre_processed ? 0 : 1,
+                       vs.side[SIDE_G].sp_val, sq);
     if (nnz > 0)
-      hipLaunchKernelGGL(csr_gather_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, h->stream, dperm, vs.vcsc, nnz, vs.vcsr);
+      hipLaunchKernelGGL(csr_gather_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, h->stream, dperm, vs.side[SIDE_G].sp_val, nnz, vs.side[SIDE_F].sp_val);
     hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, h->stream, sq, m, vs.xnorm2);
     e = hipGetLastError();
   }
@@ -1901,9 +1876,9 @@ int resnmtf_copy_view(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src
   HIP_TRY(dst, hipStreamSynchronize(src->stream));
   if (int rc = sync_both(dst)) return rc;
   // same shape and options decide the same pitches; guard anyway
-  if (a.ldx != b.ldx || a.ldxt != b.ldxt) return dst->fail(RESNMTF_ERR_INVALID, "views differ in device layout (no_pitch_pad)");
-  HIP_TRY(dst, hipMemcpyAsync(a.X32, b.X32, a.x32_floats * sizeof(float), hipMemcpyDeviceToDevice, dst->stream));
-  HIP_TRY(dst, hipMemcpyAsync(a.Xt32, b.Xt32, a.xt32_floats * sizeof(float), hipMemcpyDeviceToDevice, dst->stream));
+  if (a.side[SIDE_G].ldx != b.side[SIDE_G].ldx || a.side[SIDE_F].ldx != b.side[SIDE_F].ldx) return dst->fail(RESNMTF_ERR_INVALID, "views differ in device layout (no_pitch_pad)");
+  HIP_TRY(dst, hipMemcpyAsync(a.side[SIDE_G].X, b.side[SIDE_G].X, a.side[SIDE_G].x_floats * sizeof(float), hipMemcpyDeviceToDevice, dst->stream));
+  HIP_TRY(dst, hipMemcpyAsync(a.side[SIDE_F].X, b.side[SIDE_F].X, a.side[SIDE_F].x_floats * sizeof(float), hipMemcpyDeviceToDevice, dst->stream));
   HIP_TRY(dst, hipMemcpyAsync(a.xnorm2, b.xnorm2, sizeof(double), hipMemcpyDeviceToDevice, dst->stream));
   HIP_TRY(dst, hipStreamSynchronize(dst->stream));
   a.has_x = true;
@@ -1916,7 +1891,7 @@ int resnmtf_shuffle_view(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_
   const ViewState& b = src->views[v_src];
   HIP_TRY(dst, hipSetDevice(dst->opt.device_id));
   HIP_TRY(dst, hipStreamSynchronize(src->stream));
-  const ShuffleSrc sh{b.X32, b.ldx, seed, nullptr, nullptr};
+  const ShuffleSrc sh{b.side[SIDE_G].X, b.side[SIDE_G].ldx, seed, nullptr, nullptr};
   return upload_view(dst, v, nullptr, normalise != 0, nullptr, &sh);
 }
 
@@ -1962,8 +1937,8 @@ int resnmtf_shuffle_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src,
   alloc(reinterpret_cast<void**>(&line_mask), (size_t)n + m + 2 * sizeof(int) + 8);
   const double* v64 = reinterpret_cast<const double*>(pay[0]);
   if (e == hipSuccess && nnz == 0) {          // every line empty: zero pointers, nothing of size zero launched
-    e = hipMemsetAsync(a.cp, 0, ((size_t)m + 1) * sizeof(long long), st);
-    if (e == hipSuccess) e = hipMemsetAsync(a.rp, 0, ((size_t)n + 1) * sizeof(long long), st);
+    e = hipMemsetAsync(a.side[SIDE_G].sp_ptr, 0, ((size_t)m + 1) * sizeof(long long), st);
+    if (e == hipSuccess) e = hipMemsetAsync(a.side[SIDE_F].sp_ptr, 0, ((size_t)n + 1) * sizeof(long long), st);
     line_counts[0] = n; line_counts[1] = m;
   }
   if (e == hipSuccess && nnz > 0) {
@@ -1971,7 +1946,7 @@ int resnmtf_shuffle_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src,
     const unsigned long long count = (unsigned long long)n * m;
     unsigned int end_bit = 1;                           // the bits of n m: every key is < count
     while (end_bit < 64 && ((count - 1) >> end_bit) != 0) ++end_bit;
-    hipLaunchKernelGGL(sparse_shuffle_keys_kernel, dim3(grid), dim3(256), 0, st, b.cp, b.ri, b.vcsc, nnz, n, m, seed, key[0],
+    hipLaunchKernelGGL(sparse_shuffle_keys_kernel, dim3(grid), dim3(256), 0, st, b.side[SIDE_G].sp_ptr, b.side[SIDE_G].sp_idx, b.side[SIDE_G].sp_val, nnz, n, m, seed, key[0],
                        reinterpret_cast<double*>(pay[0]));
     e = hipGetLastError();
     // ---- the CSC of the shuffle: the entries sorted by destination position
@@ -1987,7 +1962,7 @@ int resnmtf_shuffle_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src,
     if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kb, vb, (size_t)nnz, 0u, end_bit, st);
     if (e == hipSuccess) {
       v64 = vb.current();
-      hipLaunchKernelGGL(sorted_lines_kernel, dim3(grid), dim3(256), 0, st, kb.current(), nnz, (unsigned long long)n, m, a.cp, a.ri);
+      hipLaunchKernelGGL(sorted_lines_kernel, dim3(grid), dim3(256), 0, st, kb.current(), nnz, (unsigned long long)n, m, a.side[SIDE_G].sp_ptr, a.side[SIDE_G].sp_idx);
       // ---- the CSR: the CSC positions sorted by r' m + c' (the values stay where the first sort left them)
       kb2 = rocprim::double_buffer<unsigned long long>(kb.alternate(), kb.current());
       pb = rocprim::double_buffer<long long>(reinterpret_cast<long long*>(vb.alternate()), pay[2]);
@@ -1996,10 +1971,10 @@ int resnmtf_shuffle_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src,
     }
     if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kb2, pb, (size_t)nnz, 0u, end_bit, st);
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(sorted_lines_kernel, dim3(grid), dim3(256), 0, st, kb2.current(), nnz, (unsigned long long)m, n, a.rp, a.ci);
+      hipLaunchKernelGGL(sorted_lines_kernel, dim3(grid), dim3(256), 0, st, kb2.current(), nnz, (unsigned long long)m, n, a.side[SIDE_F].sp_ptr, a.side[SIDE_F].sp_idx);
       int* counts = reinterpret_cast<int*>(line_mask + (((size_t)n + m + 7) / 8) * 8);
       e = hipMemsetAsync(counts, 0, 2 * sizeof(int), st);
-      hipLaunchKernelGGL(sparse_empty_lines_kernel, dim3(ceil_div(n + m, 256)), dim3(256), 0, st, a.cp, a.rp, pb.current(), v64, n, m,
+      hipLaunchKernelGGL(sparse_empty_lines_kernel, dim3(ceil_div(n + m, 256)), dim3(256), 0, st, a.side[SIDE_G].sp_ptr, a.side[SIDE_F].sp_ptr, pb.current(), v64, n, m,
                          line_mask, counts);
       if (e == hipSuccess) e = hipGetLastError();
       if (e == hipSuccess) e = hipMemcpyAsync(a.empty_mask.data(), line_mask, (size_t)n + m, hipMemcpyDeviceToHost, st);
@@ -2007,14 +1982,14 @@ int resnmtf_shuffle_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src,
     }
     // ---- values: matrix_normalisation of the shuffle (fp64, ascending entry order) or the copy, data_norms, the CSR values
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(csc_normalise_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, a.cp, v64, m, normalise ? 1 : 0, a.vcsc, sq);
-      hipLaunchKernelGGL(csr_gather_kernel, dim3(grid), dim3(256), 0, st, pb.current(), a.vcsc, nnz, a.vcsr);
+      hipLaunchKernelGGL(csc_normalise_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, a.side[SIDE_G].sp_ptr, v64, m, normalise ? 1 : 0, a.side[SIDE_G].sp_val, sq);
+      hipLaunchKernelGGL(csr_gather_kernel, dim3(grid), dim3(256), 0, st, pb.current(), a.side[SIDE_G].sp_val, nnz, a.side[SIDE_F].sp_val);
       e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(cp.data(), a.cp, cp.size() * sizeof(long long), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(rp.data(), a.rp, rp.size() * sizeof(long long), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(cp.data(), a.side[SIDE_G].sp_ptr, cp.size() * sizeof(long long), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(rp.data(), a.side[SIDE_F].sp_ptr, rp.size() * sizeof(long long), hipMemcpyDeviceToHost, st);
   } else if (e == hipSuccess) {
-    hipLaunchKernelGGL(csc_normalise_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, a.cp, v64, m, 0, a.vcsc, sq);
+    hipLaunchKernelGGL(csc_normalise_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, a.side[SIDE_G].sp_ptr, v64, m, 0, a.side[SIDE_G].sp_val, sq);
     e = hipGetLastError();
   }
   if (e == hipSuccess) {
@@ -2051,7 +2026,7 @@ int resnmtf_subsample_view(resnmtf_handle* dst, int v, resnmtf_handle* src, int 
   hipError_t e = hipMemcpy(idx, rows, (size_t)a.n * sizeof(int), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(idx + a.n, cols, (size_t)a.m * sizeof(int), hipMemcpyHostToDevice);
   if (e != hipSuccess) { (void)hipFree(idx); return dst->fail_hip("subsample_view", e); }
-  const ShuffleSrc sh{b.X32, b.ldx, 0ull, idx, idx + a.n};
+  const ShuffleSrc sh{b.side[SIDE_G].X, b.side[SIDE_G].ldx, 0ull, idx, idx + a.n};
   const int rc = upload_view(dst, v, nullptr, false, nullptr, &sh);      // sub-samples are NOT re-normalised (Appendix B11)
   (void)hipFree(idx);
   return rc;
@@ -2077,10 +2052,10 @@ int resnmtf_get_view(resnmtf_handle* h, int v, double* x) {
   if (!vs.owned || !vs.has_x) return h->fail(RESNMTF_ERR_STATE, "no data on this handle for the view");
   HIP_TRY(h, hipSetDevice(h->opt.device_id));
   if (int rc = sync_both(h)) return rc;
-  std::vector<float> t(vs.xt32_floats);                  // Xt32(c, r) = X[r][c], tile-major over r
-  HIP_TRY(h, hipMemcpy(t.data(), vs.Xt32, t.size() * sizeof(float), hipMemcpyDeviceToHost));
+  std::vector<float> t(vs.side[SIDE_F].x_floats);                  // Xt32(c, r) = X[r][c], tile-major over r
+  HIP_TRY(h, hipMemcpy(t.data(), vs.side[SIDE_F].X, t.size() * sizeof(float), hipMemcpyDeviceToHost));
   for (int c = 0; c < vs.m; ++c)
-    for (int r = 0; r < vs.n; ++r) x[(size_t)c * vs.n + r] = (double)t[xidx(c, r, vs.ldxt)];
+    for (int r = 0; r < vs.n; ++r) x[(size_t)c * vs.n + r] = (double)t[xidx(c, r, vs.side[SIDE_F].ldx)];
   return RESNMTF_OK;
 }
 
@@ -2092,11 +2067,11 @@ int resnmtf_get_view_csc(resnmtf_handle* h, int v, long long* col_ptr, int* row_
   if (!vs.owned || !vs.has_x) return h->fail(RESNMTF_ERR_STATE, "no data on this handle for the view");
   HIP_TRY(h, hipSetDevice(h->opt.device_id));
   if (int rc = sync_both(h)) return rc;
-  if (col_ptr) HIP_TRY(h, hipMemcpy(col_ptr, vs.cp, ((size_t)vs.m + 1) * sizeof(long long), hipMemcpyDeviceToHost));
-  if (row_idx && vs.nnz > 0) HIP_TRY(h, hipMemcpy(row_idx, vs.ri, (size_t)vs.nnz * sizeof(int), hipMemcpyDeviceToHost));
+  if (col_ptr) HIP_TRY(h, hipMemcpy(col_ptr, vs.side[SIDE_G].sp_ptr, ((size_t)vs.m + 1) * sizeof(long long), hipMemcpyDeviceToHost));
+  if (row_idx && vs.nnz > 0) HIP_TRY(h, hipMemcpy(row_idx, vs.side[SIDE_G].sp_idx, (size_t)vs.nnz * sizeof(int), hipMemcpyDeviceToHost));
   if (values && vs.nnz > 0) {
     std::vector<float> t((size_t)vs.nnz);
-    HIP_TRY(h, hipMemcpy(t.data(), vs.vcsc, t.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(t.data(), vs.side[SIDE_G].sp_val, t.size() * sizeof(float), hipMemcpyDeviceToHost));
     for (size_t e = 0; e < t.size(); ++e) values[e] = (double)t[e];
   }
   return RESNMTF_OK;
@@ -2114,9 +2089,9 @@ int resnmtf_set_factors(resnmtf_handle* h, int v, const double* F, const double*
   to_row_major(F, vs.n, vs.k, f);
   to_row_major(S, vs.k, vs.k, s);
   to_row_major(G, vs.m, vs.k, g);
-  HIP_TRY(h, hipMemcpyAsync(vs.F, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(vs.side[SIDE_F].W, f.data(), f.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipMemcpyAsync(vs.S, s.data(), s.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(vs.G, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(vs.side[SIDE_G].W, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   std::vector<double> lam(vs.k, 0.0), muv(vs.k, 0.0);
   if (vs.owned) {
     // explicit-init branch: lambda = colSums(F), mu = colSums(G) (R/update_steps.r:55-56)
@@ -2126,17 +2101,17 @@ int resnmtf_set_factors(resnmtf_handle* h, int v, const double* F, const double*
       if (mu) muv[j] = mu[j];
       else { double t = 0.0; for (int i = 0; i < vs.m; ++i) t += G[(size_t)j * vs.m + i]; muv[j] = t; }
     }
-    HIP_TRY(h, hipMemcpyAsync(vs.lambda, lam.data(), lam.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(vs.mu, muv.data(), muv.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemsetAsync(vs.F32, 0, (size_t)vs.n_pad * 64 * sizeof(float), h->stream));
-    HIP_TRY(h, hipMemsetAsync(vs.G32, 0, (size_t)vs.m_pad * 64 * sizeof(float), h->stream));
+    HIP_TRY(h, hipMemcpyAsync(vs.side[SIDE_F].lm, lam.data(), lam.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(vs.side[SIDE_G].lm, muv.data(), muv.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(vs.side[SIDE_F].W32, 0, (size_t)vs.n_pad * 64 * sizeof(float), h->stream));
+    HIP_TRY(h, hipMemsetAsync(vs.side[SIDE_G].W32, 0, (size_t)vs.m_pad * 64 * sizeof(float), h->stream));
     HIP_TRY(h, hipMemsetAsync(vs.T32, 0, (size_t)vs.m_pad * 64 * sizeof(float), h->stream));
-    HIP_TRY(h, hipMemsetAsync(vs.cnt_xg, 0, 4 * sizeof(int), h->stream));
-    HIP_TRY(h, hipMemsetAsync(vs.cnt_xtf, 0, 4 * sizeof(int), h->stream));
-    hipLaunchKernelGGL(factor_to_f32_kernel, dim3(ceil_div(vs.n * vs.k, 256)), dim3(256), 0, h->stream, vs.F, vs.n,
-                       vs.k, vs.F32, vs.kk_mode == 0 ? vs.KP : 64, vs.NT, vs.half ? 1 : 0, vs.Fk);
-    hipLaunchKernelGGL(factor_to_f32_kernel, dim3(ceil_div(vs.m * vs.k, 256)), dim3(256), 0, h->stream, vs.G, vs.m,
-                       vs.k, vs.G32, vs.kk_mode == 0 ? vs.KP : 64, vs.NT, vs.half ? 1 : 0, vs.Gk);
+    HIP_TRY(h, hipMemsetAsync(vs.side[SIDE_F].cnt, 0, 4 * sizeof(int), h->stream));
+    HIP_TRY(h, hipMemsetAsync(vs.side[SIDE_G].cnt, 0, 4 * sizeof(int), h->stream));
+    hipLaunchKernelGGL(factor_to_f32_kernel, dim3(ceil_div(vs.n * vs.k, 256)), dim3(256), 0, h->stream, vs.side[SIDE_F].W, vs.n,
+                       vs.k, vs.side[SIDE_F].W32, vs.kk_mode == 0 ? vs.KP : 64, vs.NT, vs.half ? 1 : 0, vs.side[SIDE_F].Wk);
+    hipLaunchKernelGGL(factor_to_f32_kernel, dim3(ceil_div(vs.m * vs.k, 256)), dim3(256), 0, h->stream, vs.side[SIDE_G].W, vs.m,
+                       vs.k, vs.side[SIDE_G].W32, vs.kk_mode == 0 ? vs.KP : 64, vs.NT, vs.half ? 1 : 0, vs.side[SIDE_G].Wk);
     HIP_TRY(h, hipGetLastError());
   }
   HIP_TRY(h, hipStreamSynchronize(h->stream));   // host vectors go out of scope
@@ -2337,13 +2312,13 @@ int init_svd_thin(resnmtf_handle* h, int v, double sigma, std::mt19937_64& gen, 
       (e = alloc(&sc.gpart, (size_t)(kGramBlocks + 1) * r * r)) != hipSuccess || (e = alloc(&sc.gram, (size_t)r * r)) != hipSuccess ||
       (e = alloc(&sc.M, (size_t)r * r)) != hipSuccess)
     return h->fail_hip("init_svd hipMalloc", e);
+  const int long_side = tall ? SIDE_F : SIDE_G;      // Y has one row per line of the long side
+  const Side& lines = vs.side[long_side];
   if (vs.sparse) {      // the short side from the CSR (Y = X) or the CSC (Y = X^T)
     HIP_TRY(h, hipMemsetAsync(sc.Yn, 0, (size_t)len * r * sizeof(double), h->stream));
-    hipLaunchKernelGGL(sparse_widen_kernel, dim3(ceil_div(len, 256)), dim3(256), 0, h->stream, tall ? vs.rp : vs.cp, tall ? vs.ci : vs.ri,
-                       tall ? vs.vcsr : vs.vcsc, len, r, sc.Yn);
+    hipLaunchKernelGGL(sparse_widen_kernel, dim3(ceil_div(len, 256)), dim3(256), 0, h->stream, lines.sp_ptr, lines.sp_idx, lines.sp_val, len, r, sc.Yn);
   } else
-    hipLaunchKernelGGL(widen_rows_kernel, dim3(ceil_div(len * r, 256)), dim3(256), 0, h->stream, tall ? vs.X32 : vs.Xt32,
-                       tall ? vs.ldx : vs.ldxt, len, r, sc.Yn);
+    hipLaunchKernelGGL(widen_rows_kernel, dim3(ceil_div(len * r, 256)), dim3(256), 0, h->stream, vs.side[other(long_side)].X, vs.side[other(long_side)].ldx, len, r, sc.Yn);
   HIP_TRY(h, hipGetLastError());
   std::vector<double> C, W;
   if (int rc = ts_gram_host(h, sc, sc.Yn, len, r, C)) return rc;
@@ -2390,48 +2365,48 @@ int init_svd_impl(resnmtf_handle* h, int v, unsigned long long seed, double sigm
       (e = alloc(&sc.M, (size_t)L * L)) != hipSuccess)
     return h->fail_hip("init_svd hipMalloc", e);
   // slabs: the view's own when the sketch is as wide as its KP, else temporaries
-  if (L == vs.KP) { sc.Pn = vs.Pxg; sc.Pm = vs.Pxtf; }
+  if (L == vs.KP) { sc.Pn = vs.side[SIDE_F].P; sc.Pm = vs.side[SIDE_G].P; }
   else {
-    if ((e = hipMalloc(reinterpret_cast<void**>(&sc.Pn), (size_t)vs.nsplit_xg * vs.n_pad * L * sizeof(float))) != hipSuccess)
+    if ((e = hipMalloc(reinterpret_cast<void**>(&sc.Pn), (size_t)vs.side[SIDE_F].nsplit * vs.n_pad * L * sizeof(float))) != hipSuccess)
       return h->fail_hip("init_svd hipMalloc slabs", e);
     sc.own_pn = true;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&sc.Pm), (size_t)vs.nsplit_xtf * vs.m_pad * L * sizeof(float))) != hipSuccess)
+    if ((e = hipMalloc(reinterpret_cast<void**>(&sc.Pm), (size_t)vs.side[SIDE_G].nsplit * vs.m_pad * L * sizeof(float))) != hipSuccess)
       return h->fail_hip("init_svd hipMalloc slabs", e);
     sc.own_pm = true;
   }
   PassArgs xg{}, xt{};
-  xg.A = vs.Xt32; xg.lda = 64; xg.tile_stride = vs.ldxt; xg.ntiles = vs.n_pad / 64; xg.B = vs.G32; xg.ldb = 64; xg.P = sc.Pn;
-  xg.cols_pad = vs.n_pad; xg.rows_pad = vs.m_pad; xg.rows_per_split = vs.rps_xg; xg.nsplit = vs.nsplit_xg; xg.ctl = h->ctl;
-  xt.A = vs.X32; xt.lda = 64; xt.tile_stride = vs.ldx; xt.ntiles = vs.m_pad / 64; xt.B = vs.F32; xt.ldb = 64; xt.P = sc.Pm;
-  xt.cols_pad = vs.m_pad; xt.rows_pad = vs.n_pad; xt.rows_per_split = vs.rps_xtf; xt.nsplit = vs.nsplit_xtf; xt.ctl = h->ctl;
+  xg.A = vs.side[SIDE_F].X; xg.lda = 64; xg.tile_stride = vs.side[SIDE_F].ldx; xg.ntiles = vs.n_pad / 64; xg.B = vs.side[SIDE_G].W32; xg.ldb = 64; xg.P = sc.Pn;
+  xg.cols_pad = vs.n_pad; xg.rows_pad = vs.m_pad; xg.rows_per_split = vs.side[SIDE_F].rps; xg.nsplit = vs.side[SIDE_F].nsplit; xg.ctl = h->ctl;
+  xt.A = vs.side[SIDE_G].X; xt.lda = 64; xt.tile_stride = vs.side[SIDE_G].ldx; xt.ntiles = vs.m_pad / 64; xt.B = vs.side[SIDE_F].W32; xt.ldb = 64; xt.P = sc.Pm;
+  xt.cols_pad = vs.m_pad; xt.rows_pad = vs.n_pad; xt.rows_per_split = vs.side[SIDE_G].rps; xt.nsplit = vs.side[SIDE_G].nsplit; xt.ctl = h->ctl;
 
   // Omega: m x L standard normal (host generator: the reference's RNG is not reproducible anyway)
   std::normal_distribution<double> normal(0.0, 1.0);
   std::vector<double> omega((size_t)m * L);
   for (double& x : omega) x = normal(gen);
   HIP_TRY(h, hipMemcpyAsync(sc.Zm, omega.data(), omega.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemsetAsync(vs.F32, 0, (size_t)vs.n_pad * 64 * sizeof(float), h->stream));
-  HIP_TRY(h, hipMemsetAsync(vs.G32, 0, (size_t)vs.m_pad * 64 * sizeof(float), h->stream));
-  hipLaunchKernelGGL(factor_to_f32_kernel, dim3(ceil_div(m * L, 256)), dim3(256), 0, h->stream, sc.Zm, m, L, vs.G32, 64, NTi, 0, (unsigned short*)nullptr);
+  HIP_TRY(h, hipMemsetAsync(vs.side[SIDE_F].W32, 0, (size_t)vs.n_pad * 64 * sizeof(float), h->stream));
+  HIP_TRY(h, hipMemsetAsync(vs.side[SIDE_G].W32, 0, (size_t)vs.m_pad * 64 * sizeof(float), h->stream));
+  hipLaunchKernelGGL(factor_to_f32_kernel, dim3(ceil_div(m * L, 256)), dim3(256), 0, h->stream, sc.Zm, m, L, vs.side[SIDE_G].W32, 64, NTi, 0, (unsigned short*)nullptr);
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   // sparse view: the same products from the CSR / CSC (spmm_kernel without a k x k job), the same slabs
   SpmmArgs sxg = spmm_args(vs, true), sxt = spmm_args(vs, false);
-  sxg.B = vs.G32; sxg.ldb = 64; sxg.P = sc.Pn; sxg.ctl = h->ctl;
-  sxt.B = vs.F32; sxt.ldb = 64; sxt.P = sc.Pm; sxt.ctl = h->ctl;
+  sxg.B = vs.side[SIDE_G].W32; sxg.ldb = 64; sxg.P = sc.Pn; sxg.ctl = h->ctl;
+  sxt.B = vs.side[SIDE_F].W32; sxt.ldb = 64; sxt.P = sc.Pm; sxt.ctl = h->ctl;
   auto product = [&](bool is_xg) {
     if (!vs.sparse) launch_pass_plain(h, is_xg ? xg : xt, NTi, is_xg);
     else launch_spmm(h, is_xg ? sxg : sxt, L, is_xg, KKFArgs{}, KKSArgs{});
   };
   for (int it = 0; it < n_power; ++it) {
     product(true);                                                                         // Y = X Z
-    hipLaunchKernelGGL(slab_sum_kernel, dim3(ceil_div(n * L, 256)), dim3(256), 0, h->stream, sc.Pn, vs.nsplit_xg, vs.n_pad, L, n, sc.Yn);
+    hipLaunchKernelGGL(slab_sum_kernel, dim3(ceil_div(n * L, 256)), dim3(256), 0, h->stream, sc.Pn, vs.side[SIDE_F].nsplit, vs.n_pad, L, n, sc.Yn);
     HIP_TRY(h, hipGetLastError());
-    if (int rc = orthonormalise(h, sc, sc.Yn, sc.Yn2, n, L, vs.F32, NTi)) return rc;          // Q (in Yn) + F32
+    if (int rc = orthonormalise(h, sc, sc.Yn, sc.Yn2, n, L, vs.side[SIDE_F].W32, NTi)) return rc;          // Q (in Yn) + F32
     product(false);                                                                        // Z = X^T Q
-    hipLaunchKernelGGL(slab_sum_kernel, dim3(ceil_div(m * L, 256)), dim3(256), 0, h->stream, sc.Pm, vs.nsplit_xtf, vs.m_pad, L, m, sc.Zm);
+    hipLaunchKernelGGL(slab_sum_kernel, dim3(ceil_div(m * L, 256)), dim3(256), 0, h->stream, sc.Pm, vs.side[SIDE_G].nsplit, vs.m_pad, L, m, sc.Zm);
     HIP_TRY(h, hipGetLastError());
     if (it + 1 < n_power)
-      if (int rc = orthonormalise(h, sc, sc.Zm, sc.Zm2, m, L, vs.G32, NTi)) return rc;
+      if (int rc = orthonormalise(h, sc, sc.Zm, sc.Zm2, m, L, vs.side[SIDE_G].W32, NTi)) return rc;
   }
   // Z = X^T Q = V Sigma Ut^T  ->  Z^T Z = Ut Sigma^2 Ut^T;  U = Q Ut,  V = Z Ut Sigma^-1
   std::vector<double> C, Ut;
@@ -2498,8 +2473,9 @@ static int set_shared(resnmtf_handle* h, int v, int w, int count, const int* idx
   if (v == w) return h->fail(RESNMTF_ERR_INVALID, "shared map needs two different views");
   ViewState& vs = h->views[v];
   const ViewState& ws = h->views[w];
-  SharedMap& mp = rows ? vs.row_map[w] : vs.col_map[w];
-  const int len_v = rows ? vs.n : vs.m, len_w = rows ? ws.n : ws.m;
+  const int s = rows ? SIDE_F : SIDE_G;
+  SharedMap& mp = vs.side[s].map[w];
+  const int len_v = vs.side[s].len, len_w = ws.side[s].len;
   HIP_TRY(h, hipSetDevice(h->opt.device_id));
   h->prepared = false;
   h->resume_ok = false;
@@ -2530,98 +2506,86 @@ int resnmtf_set_shared_cols(resnmtf_handle* h, int v, int w, int count, const in
   return set_shared(h, v, w, count, idx_v, idx_w, false);
 }
 
-// RESNMTF_PHASE_F_ALL in one launch (f_chain_kernel): every view holds the inputs of its F update here
-// (owned, or an F replica), k <= 16 in hand-off mode A, equal row counts and row blocking, every coupling
-// through identity row maps, at most four owned views, at most 8 views.  Otherwise one launch per view.
-static void build_chain(resnmtf_handle* h) {
-  h->chain_views = 0;
+// ---- the chain builders.  What is the same for every chain of side s: the per-view fields (fill_chain_view) and the
+// coupling table (fill_coupling); what differs is listed at each builder.
+extern "C++" {      // (templates: ChainArgs<8> and WideChainArgs<8> share the field names)
+// cmask / weight of view v from the couple list of its update: which views' running factors it reads, and how strongly
+template <class Chain>
+static void fill_coupling(const resnmtf_handle* h, int s, int v, const UpdateArgs& u, Chain& a) {
+  for (int c = 0; c < u.n_couple; ++c)
+    for (int w = 0; w < h->V; ++w)
+      if (u.couple[c].W == h->views[w].side[s].W) { a.cmask[v] |= 1u << w; a.weight[v][w] = u.couple[c].weight; }
+}
+// W, U, Ma, Md, lm, sigma, n_other, the restricted bit and the couplings of view v, from the update arguments of its side s
+template <class Chain>
+static void fill_chain_view(const resnmtf_handle* h, int s, int v, Chain& a) {
+  const UpdateArgs& u = h->views[v].side[s].arg;
+  a.W[v] = u.W; a.U[v] = u.P; a.Ma[v] = u.Ma; a.Md[v] = u.Md; a.lm[v] = u.lm;
+  a.sigma[v] = u.sigma;
+  a.n_other[v] = (double)u.len;
+  if (u.restricted) a.restricted |= 1u << v;
+  fill_coupling(h, s, v, u, a);
+}
+}  // extern "C++"
+static bool identity_coupled(const UpdateArgs& u) {      // a permuted shared map: rows of other workgroups
+  for (int c = 0; c < u.n_couple; ++c)
+    if (u.couple[c].map) return false;
+  return true;
+}
+
+// RESNMTF_PHASE_F_ALL (s = SIDE_F) / RESNMTF_PHASE_G_ALL (SIDE_G; replicated G chain, R/update_steps.r:195-204) at k <= 16 in
+// one f_chain_kernel launch: every view holds the inputs of that update here (owned, or a replica), hand-off mode A, equal
+// lengths, k and blocking, every coupling through identity maps, at most 8 views.  Otherwise one launch per view.
+// Where the two sides differ:          F                                   G
+//   layout gate                        --                                  replicate_gs and not slice_chains
+//   slabs per view (u.nsplit)          up to 4 raw split slabs             1 (the folded slab of the exchange block)
+//   2-byte images (half)               allowed, but the same in all        not allowed
+//                                      owned views (one kpack32)
+//   owned views                        at most 4                           at most 2
+static void build_chain(resnmtf_handle* h, int s) {
+  h->chain_views[s] = 0;
   const int V = h->V;
   if (V < 2 || V > 8 || h->opt.no_f_chain) return;
+  if (s == SIDE_G && (!h->opt.replicate_gs || h->sliced)) return;
+  const int max_nsplit = s == SIDE_F ? 4 : 1, max_owned = s == SIDE_F ? 4 : 2;
   const ViewState& v0 = h->views[0];
+  const Side& s0 = v0.side[s];
   int n_owned = 0, kpack = -1;
   for (int v = 0; v < V; ++v) {
     const ViewState& vs = h->views[v];
-    if (!vs.owned && !vs.f_replica) return;
+    const Side& sd = vs.side[s];
+    if (!vs.owned && !sd.replica) return;
+    if (s == SIDE_G && vs.half) return;
     if (vs.owned) {                                         // one operand-copy layout for all owned views
       if (kpack < 0) kpack = vs.half ? 1 : 0;
       else if (kpack != (vs.half ? 1 : 0)) return;
     }
-    if (vs.KP != 16 || vs.kk_mode != 0 || vs.n != v0.n || vs.k != v0.k || vs.rpbF != v0.rpbF || vs.nblkF != v0.nblkF) return;
-    if (vs.argF.nsplit > 4 || vs.argF.cols_pad != v0.argF.cols_pad) return;     // raw split slabs the kernel keeps per view
-    if (vs.owned) ++n_owned;
-    for (int c = 0; c < vs.argF.n_couple; ++c)
-      if (vs.argF.couple[c].map) return;                    // permuted shared rows: rows of different workgroups
+    if (vs.KP != 16 || vs.kk_mode != 0 || sd.len != s0.len || vs.k != v0.k || sd.rpb != s0.rpb || sd.nblk != s0.nblk) return;
+    if (sd.arg.nsplit > max_nsplit || sd.arg.cols_pad != s0.arg.cols_pad) return;     // raw split slabs the kernel keeps per view
+    if (vs.owned && ++n_owned > max_owned) return;
+    if (!identity_coupled(sd.arg)) return;
   }
-  if (n_owned > 4) return;
-  ChainArgs<8>& a = h->chain;
+  ChainArgs<8>& a = h->chain[s];
   a = ChainArgs<8>{};
-  a.len = v0.n; a.k = v0.k; a.n_views = V; a.rows_per_block = v0.rpbF;
+  a.len = s0.len; a.k = v0.k; a.n_views = V; a.rows_per_block = s0.rpb;
   a.ctl = h->ctl;
-  a.pstride = (size_t)v0.argF.cols_pad * 16;
+  a.pstride = (size_t)s0.arg.cols_pad * 16;
   a.kpack32 = kpack > 0 ? 1 : 0;
   for (int v = 0; v < 8; ++v) a.emit_slot[v] = -1;
   for (int v = 0; v < V; ++v) {
     const ViewState& vs = h->views[v];
-    const UpdateArgs& f = vs.argF;
+    const Side& sd = vs.side[s];
     if (vs.owned) {
       a.emit_slot[v] = a.n_emit;
-      a.W32e[a.n_emit] = vs.F32; a.parte[a.n_emit] = vs.partF;
+      a.W32e[a.n_emit] = sd.W32; a.parte[a.n_emit] = sd.part;
+      if (s == SIDE_G) a.T32e[a.n_emit] = vs.T32;
       ++a.n_emit;
     }
-    a.W[v] = vs.F; a.U[v] = f.P; a.nsplit[v] = f.nsplit; a.Ma[v] = vs.Ma_F; a.Md[v] = vs.Md_F; a.lm[v] = vs.lambda;
-    a.sigma[v] = f.sigma;
-    a.n_other[v] = (double)vs.n;
-    if (f.restricted) a.restricted |= 1u << v;
-    for (int c = 0; c < f.n_couple; ++c)
-      for (int w = 0; w < V; ++w)
-        if (f.couple[c].W == h->views[w].F) { a.cmask[v] |= 1u << w; a.weight[v][w] = f.couple[c].weight; }
+    fill_chain_view(h, s, v, a);
+    a.nsplit[v] = sd.arg.nsplit;
   }
-  h->chain_views = V;
-  h->chain_blocks = v0.nblkF;
-}
-
-// RESNMTF_PHASE_G_ALL in one launch at k <= 16 (f_chain_kernel, G form; replicated G chain, R/update_steps.r:195-204): every view
-// holds the inputs of its G update here (owned, or a G replica) as ONE folded slab, hand-off mode A, equal column counts and
-// blocking, every coupling through identity column maps, at most two owned views, at most 8 views.  Else one launch per view.
-static void build_g_chain(resnmtf_handle* h) {
-  h->gchain_views = 0;
-  const int V = h->V;
-  if (V < 2 || V > 8 || h->opt.no_f_chain || !h->opt.replicate_gs || h->sliced) return;
-  const ViewState& v0 = h->views[0];
-  int n_owned = 0;
-  for (int v = 0; v < V; ++v) {
-    const ViewState& vs = h->views[v];
-    if (!vs.owned && !vs.g_replica) return;
-    if (vs.KP != 16 || vs.kk_mode != 0 || vs.half || vs.m != v0.m || vs.k != v0.k || vs.rpbG != v0.rpbG || vs.nblkG != v0.nblkG) return;
-    if (vs.argG.nsplit != 1 || vs.argG.cols_pad != v0.argG.cols_pad) return;
-    if (vs.owned && ++n_owned > 2) return;
-    for (int c = 0; c < vs.argG.n_couple; ++c)
-      if (vs.argG.couple[c].map) return;
-  }
-  ChainArgs<8>& a = h->gchain;
-  a = ChainArgs<8>{};
-  a.len = v0.m; a.k = v0.k; a.n_views = V; a.rows_per_block = v0.rpbG;
-  a.ctl = h->ctl;
-  a.pstride = (size_t)v0.argG.cols_pad * 16;
-  for (int v = 0; v < 8; ++v) a.emit_slot[v] = -1;
-  for (int v = 0; v < V; ++v) {
-    const ViewState& vs = h->views[v];
-    const UpdateArgs& g = vs.argG;
-    if (vs.owned) {
-      a.emit_slot[v] = a.n_emit;
-      a.W32e[a.n_emit] = vs.G32; a.parte[a.n_emit] = vs.partG; a.T32e[a.n_emit] = vs.T32;
-      ++a.n_emit;
-    }
-    a.W[v] = vs.G; a.U[v] = g.P; a.nsplit[v] = 1; a.Ma[v] = vs.Ma_G; a.Md[v] = vs.Md_G; a.lm[v] = vs.mu;
-    a.sigma[v] = g.sigma;
-    a.n_other[v] = (double)vs.m;
-    if (g.restricted) a.restricted |= 1u << v;
-    for (int c = 0; c < g.n_couple; ++c)
-      for (int w = 0; w < V; ++w)
-        if (g.couple[c].W == h->views[w].G) { a.cmask[v] |= 1u << w; a.weight[v][w] = g.couple[c].weight; }
-  }
-  h->gchain_views = V;
-  h->gchain_blocks = v0.nblkG;
+  h->chain_views[s] = V;
+  h->chain_blocks[s] = s0.nblk;
 }
 
 // RESNMTF_PHASE_F_ALL / G_ALL in one launch at k = 32 / 64 (wide_chain_kernel): every view holds the inputs of the update
@@ -2641,27 +2605,21 @@ static void build_wide_chain(resnmtf_handle* h) {
     int n_owned = 0;
     for (int v = 0; v < V && ok; ++v) {
       const ViewState& vs = h->views[v];
-      const UpdateArgs& u = g == 0 ? vs.argF : vs.argG;
-      if (!vs.owned && !(g == 0 ? vs.f_replica : vs.g_replica)) { ok = false; break; }
-      if (vs.KP != v0.KP || vs.k != v0.k || (g == 0 ? vs.n != v0.n : vs.m != v0.m)) { ok = false; break; }
+      const Side& sd = vs.side[g];
+      const UpdateArgs& u = sd.arg;
+      if (!vs.owned && !sd.replica) { ok = false; break; }
+      if (vs.KP != v0.KP || vs.k != v0.k || sd.len != v0.side[g].len) { ok = false; break; }
       if (u.nsplit != 1 || u.P == nullptr) { ok = false; break; }            // the folded slab of an exchange block
-      for (int c = 0; c < u.n_couple; ++c)
-        if (u.couple[c].map) ok = false;                                     // permuted shared rows: rows of other workgroups
+      if (!identity_coupled(u)) ok = false;
       if (vs.owned) {
         if (++n_owned > 1) { ok = false; break; }
-        a.own = v; a.W32 = g == 0 ? vs.F32 : vs.G32; a.Wk = g == 0 ? vs.Fk : vs.Gk; a.T32 = g == 0 ? nullptr : vs.T32; a.ld32 = u.ld32;
-        if (!a.W32 || !a.Wk || (g == 1 && !a.T32)) { ok = false; break; }
+        a.own = v; a.W32 = sd.W32; a.Wk = sd.Wk; a.T32 = g == SIDE_F ? nullptr : vs.T32; a.ld32 = u.ld32;
+        if (!a.W32 || !a.Wk || (g == SIDE_G && !a.T32)) { ok = false; break; }
       }
-      a.W[v] = u.W; a.U[v] = u.P; a.Ma[v] = u.Ma; a.Md[v] = u.Md; a.lm[v] = u.lm;
-      a.sigma[v] = u.sigma;
-      a.n_other[v] = (double)(g == 0 ? vs.n : vs.m);
-      if (u.restricted) a.restricted |= 1u << v;
-      for (int c = 0; c < u.n_couple; ++c)
-        for (int w = 0; w < V; ++w)
-          if (u.couple[c].W == (g == 0 ? h->views[w].F : h->views[w].G)) { a.cmask[v] |= 1u << w; a.weight[v][w] = u.couple[c].weight; }
+      fill_chain_view(h, g, v, a);
     }
     if (!ok) continue;
-    a.len = g == 0 ? v0.n : v0.m; a.n_self = a.len; a.k = v0.k; a.n_views = V; a.ngroups = ceil_div(a.len, 32);
+    a.len = v0.side[g].len; a.n_self = a.len; a.k = v0.k; a.n_views = V; a.ngroups = ceil_div(a.len, 32);
     a.ctl = h->ctl;
     // persistent workgroups: one per CU at k > 32 (157 KB of LDS at k = 64, 131 KB at 48), two at k = 32
     h->wchain_grid[g] = std::min(a.ngroups, h->n_cu * (v0.KP == 32 ? 2 : 1));
@@ -2679,36 +2637,25 @@ static int build_slice_chain(resnmtf_handle* h) {
     WideChainArgs<8>& a = h->schain[g];
     a = WideChainArgs<8>{};
     a.own = -1;
-    const int per = g == 0 ? h->sl_rows : h->sl_cols, full = g == 0 ? v0.n : v0.m;
+    const int per = h->sl_len[g], full = v0.side[g].len;
     const int begin = std::min(r * per, full), len = std::min(per, full - begin);
     for (int v = 0; v < V; ++v) {
       const ViewState& vs = h->views[v];
-      const UpdateArgs& u = g == 0 ? vs.argF : vs.argG;
-      for (int c = 0; c < u.n_couple; ++c)
-        if (u.couple[c].map)
-          return h->fail(RESNMTF_ERR_INVALID, "slice_chains: coupled views must share all their rows / columns in the same order (identity maps)");
-      a.W[v] = (g == 0 ? vs.F : vs.G) + (size_t)begin * vs.k;
-      if (g == 0) {
-        a.U[v] = reinterpret_cast<const float*>(h->u_recv + (size_t)v * h->u_chunk);
-        a.Ma[v] = vs.Ma_F; a.Md[v] = vs.Md_F; a.lm[v] = vs.lambda;
-      } else {
-        const char* chunk = h->t_recv + (size_t)v * h->t_chunk;
-        a.U[v] = reinterpret_cast<const float*>(chunk);
-        a.Ma[v] = reinterpret_cast<const double*>(chunk + (size_t)per * vs.KP * sizeof(float)); a.Md[v] = a.Ma[v] + (size_t)vs.k * vs.k;
-        a.lm[v] = vs.mu;
-      }
-      a.sigma[v] = u.sigma;
+      if (!identity_coupled(vs.side[g].arg))
+        return h->fail(RESNMTF_ERR_INVALID, "slice_chains: coupled views must share all their rows / columns in the same order (identity maps)");
+      fill_chain_view(h, g, v, a);
+      // this rank's slice: its rows of the factor, and the received chunk of view v's product (G: its Ma | Md ride behind it)
+      a.W[v] = vs.side[g].W + (size_t)begin * vs.k;
+      const char* chunk = h->p_recv[g] + (size_t)v * h->p_chunk[g];
+      a.U[v] = reinterpret_cast<const float*>(chunk);
+      if (g == SIDE_G) { a.Ma[v] = reinterpret_cast<const double*>(chunk + (size_t)per * vs.KP * sizeof(float)); a.Md[v] = a.Ma[v] + (size_t)vs.k * vs.k; }
       a.n_other[v] = (double)full;
-      if (u.restricted) a.restricted |= 1u << v;
-      for (int c = 0; c < u.n_couple; ++c)
-        for (int w = 0; w < V; ++w)
-          if (u.couple[c].W == (g == 0 ? h->views[w].F : h->views[w].G)) { a.cmask[v] |= 1u << w; a.weight[v][w] = u.couple[c].weight; }
     }
-    a.O32 = g == 0 ? h->f_send : h->g_send; a.o32_stride = (unsigned)((size_t)per * v0.KP);
+    a.O32 = h->w_send[g]; a.o32_stride = (unsigned)((size_t)per * v0.KP);
     if (h->opt.slice_p2p) {      // straight into the owner's receive slot for this rank's slice
       if (!h->p2p_ready) return h->fail(RESNMTF_ERR_STATE, "slice_p2p: import every rank's buffers first (resnmtf_p2p_import)");
       a.O32 = nullptr;
-      for (int v = 0; v < V; ++v) a.O32v[v] = (g == 0 ? h->peers[(size_t)v].f_recv : h->peers[(size_t)v].g_recv) + (size_t)r * per * v0.KP;
+      for (int v = 0; v < V; ++v) a.O32v[v] = h->peers[(size_t)v].w_recv[g] + (size_t)r * per * v0.KP;
     }
     a.len = len; a.n_self = full; a.k = v0.k; a.n_views = V; a.ngroups = ceil_div(std::max(len, 0), 32);
     a.ctl = h->ctl;
@@ -2717,99 +2664,83 @@ static int build_slice_chain(resnmtf_handle* h) {
   return RESNMTF_OK;
 }
 
+// the update arguments of side s of view v: R/update_steps.r:141-165 (F) / :180-207 (G), coupling table included
+static int fill_update(resnmtf_handle* h, int v, int s) {
+  const int V = h->V;
+  ViewState& vs = h->views[v];
+  Side& sd = vs.side[s];
+  const std::vector<double>& coupling = s == SIDE_F ? h->phi : h->psi;
+  UpdateArgs& u = sd.arg;
+  u = UpdateArgs{};
+  u.len = sd.len; u.k = vs.k; u.W = sd.W; u.W32 = sd.W32; u.Wk = sd.Wk; u.ld32 = vs.kk_mode == 0 ? vs.KP : 64; u.kpack32 = vs.half ? 1 : 0;
+  u.P = sd.P; u.nsplit = sd.nsplit; u.cols_pad = sd.pad;
+  if (sd.xsum) { u.P = sd.xsum; u.nsplit = 1; }      // replicate_f / replicate_gs: the folded slab of the exchange block
+  u.Ma = sd.Ma; u.Md = sd.Md; u.lm = sd.lm; u.T32 = s == SIDE_G ? vs.T32 : nullptr; u.part = sd.part;
+  if (!vs.owned && vs.NT >= 2) { u.W32 = nullptr; u.Wk = nullptr; u.T32 = nullptr; }   // only this view's passes (on its owner) read them
+  u.rows_per_block = sd.rpb; u.ctl = h->ctl;
+  double sigma = 0.0, whole = 0.0;
+  for (int i = 0; i < V; ++i) sigma += coupling[(size_t)i + (size_t)v * V];       // sum(phi[, v]) (:150,:152) / sum(psi[, v]) (:195,:200)
+  for (double x : coupling) whole += x;
+  // the documented asymmetry: F restricts on its own column sum(phi[, v]); G branches on the WHOLE matrix sum(psi) (:190)
+  u.restricted = ((s == SIDE_F ? sigma : whole) != 0.0) ? 1 : 0;
+  u.sigma = sigma;
+  u.n_couple = 0;
+  for (int i = 0; i < V && u.restricted; ++i) {
+    const double wgt = coupling[(size_t)i + (size_t)v * V];
+    if (wgt == 0.0 || i == v) continue;                                            // utils.r:66
+    const SharedMap& mp = sd.map[i];
+    if (!mp.set || mp.count < 0) continue;                                         // NA: utils.r:70
+    if (h->views[i].k != vs.k) return h->fail(RESNMTF_ERR_INVALID, s == SIDE_F ? "phi-coupled views need equal k" : "psi-coupled views need equal k");
+    CoupleDesc& c = u.couple[u.n_couple++];
+    c.W = h->views[i].side[s].W; c.map = mp.identity ? nullptr : mp.dev; c.weight = wgt; c.n_other = (double)h->views[i].side[s].len;
+  }
+  return RESNMTF_OK;
+}
+// the arguments of the pass that feeds side s of view v: it streams side s's image and multiplies by the OTHER side's factor
+static void fill_pass(resnmtf_handle* h, int v, int s) {
+  ViewState& vs = h->views[v];
+  Side& sd = vs.side[s];
+  const Side& b = vs.side[other(s)];
+  PassArgs& a = sd.pass;
+  a = PassArgs{};
+  a.A = sd.X; a.lda = 64; a.tile_stride = sd.ldx; a.ntiles = sd.pad / 64; a.B = b.W32; a.Bk = b.Wk; a.ldb = vs.kk_mode == 0 ? vs.KP : 64; a.P = sd.P;
+  a.cols_pad = sd.pad; a.rows_pad = b.pad; a.rows_per_split = sd.rps; a.nsplit = sd.nsplit;
+  a.tw = sd.tw; a.ntg = ceil_div(a.ntiles, a.tw);
+  a.A16 = sd.X16; a.tile_stride16 = sd.ld16;
+  a.aux[0] = b.W32; a.naux = kAuxKinds[s];
+  if (s == SIDE_F) { a.aux[1] = vs.T32; a.aux[2] = nullptr; }     // X.G:  G^T G, T^T G, colSums(G)
+  else a.aux[1] = nullptr;                                        // Xt.F: F^T F, colSums(F)
+  a.Paux = sd.Paux; a.rows_per_split_aux = sd.rpsaux; a.nsplit_aux = sd.nsaux; a.aux_cnt = sd.cnt;
+  a.ctl = h->ctl;
+}
+
 // builds the kernel argument blocks (coupling tables included) from the host-side description
 static int build_args(resnmtf_handle* h) {
   const int V = h->V;
-  double sum_psi = 0.0, sum_xi = 0.0;
-  for (double x : h->psi) sum_psi += x;
+  double sum_xi = 0.0;
   for (double x : h->xi) sum_xi += x;
   for (int v = 0; v < V; ++v) {
     ViewState& vs = h->views[v];
     if (!vs.has_factors) return h->fail(RESNMTF_ERR_STATE, "set_factors missing for a view");
-    if (!vs.owned && !vs.f_replica && !vs.g_replica) continue;
-    // --- F update (R/update_steps.r:141-165)
-    UpdateArgs& f = vs.argF;
-    f = UpdateArgs{};
-    f.len = vs.n; f.k = vs.k; f.W = vs.F; f.W32 = vs.F32; f.Wk = vs.Fk; f.ld32 = vs.kk_mode == 0 ? vs.KP : 64; f.kpack32 = vs.half ? 1 : 0;
-    f.P = vs.Pxg; f.nsplit = vs.nsplit_xg; f.cols_pad = vs.n_pad;
-    if (vs.Usum) { f.P = vs.Usum; f.nsplit = 1; }      // replicate_f: the folded slab of the exchange block
-    if (!vs.owned && vs.NT >= 2) { f.W32 = nullptr; f.Wk = nullptr; }   // only this view's passes (on its owner) read them
-    f.Ma = vs.Ma_F; f.Md = vs.Md_F; f.lm = vs.lambda; f.T32 = nullptr; f.part = vs.partF;
-    f.rows_per_block = vs.rpbF; f.ctl = h->ctl;
-    {
-      double sigma = 0.0;
-      for (int i = 0; i < V; ++i) sigma += h->phi[(size_t)i + (size_t)v * V];     // sum(phi[, v])  (:150,:152)
-      f.restricted = (sigma != 0.0) ? 1 : 0;
-      f.sigma = sigma;
-      f.n_couple = 0;
-      for (int i = 0; i < V && f.restricted; ++i) {
-        const double wgt = h->phi[(size_t)i + (size_t)v * V];
-        if (wgt == 0.0 || i == v) continue;                                        // utils.r:66
-        const SharedMap& mp = vs.row_map[i];
-        if (!mp.set || mp.count < 0) continue;                                     // NA: utils.r:70
-        if (h->views[i].k != vs.k) return h->fail(RESNMTF_ERR_INVALID, "phi-coupled views need equal k");
-        CoupleDesc& c = f.couple[f.n_couple++];
-        c.W = h->views[i].F; c.map = mp.identity ? nullptr : mp.dev; c.weight = wgt; c.n_other = (double)h->views[i].n;
-      }
-    }
-    // --- G update (R/update_steps.r:180-207); branch on the WHOLE psi matrix (:190)
-    if (vs.owned || vs.g_replica) {
-    UpdateArgs& g = vs.argG;
-    g = UpdateArgs{};
-    g.len = vs.m; g.k = vs.k; g.W = vs.G; g.W32 = vs.G32; g.Wk = vs.Gk; g.ld32 = vs.kk_mode == 0 ? vs.KP : 64; g.kpack32 = vs.half ? 1 : 0;
-    g.P = vs.Pxtf; g.nsplit = vs.nsplit_xtf; g.cols_pad = vs.m_pad;
-    if (vs.Tsum) { g.P = vs.Tsum; g.nsplit = 1; }      // replicate_gs: the folded slab of the exchange block
-    g.Ma = vs.Ma_G; g.Md = vs.Md_G; g.lm = vs.mu; g.T32 = vs.T32; g.part = vs.partG;
-    if (!vs.owned && vs.NT >= 2) { g.W32 = nullptr; g.Wk = nullptr; g.T32 = nullptr; }
-    g.rows_per_block = vs.rpbG; g.ctl = h->ctl;
-    {
-      double sigma = 0.0;
-      for (int i = 0; i < V; ++i) sigma += h->psi[(size_t)i + (size_t)v * V];     // sum(psi[, v])  (:195,:200)
-      g.restricted = (sum_psi != 0.0) ? 1 : 0;
-      g.sigma = sigma;
-      g.n_couple = 0;
-      for (int i = 0; i < V && g.restricted; ++i) {
-        const double wgt = h->psi[(size_t)i + (size_t)v * V];
-        if (wgt == 0.0 || i == v) continue;
-        const SharedMap& mp = vs.col_map[i];
-        if (!mp.set || mp.count < 0) continue;
-        if (h->views[i].k != vs.k) return h->fail(RESNMTF_ERR_INVALID, "psi-coupled views need equal k");
-        CoupleDesc& c = g.couple[g.n_couple++];
-        c.W = h->views[i].G; c.map = mp.identity ? nullptr : mp.dev; c.weight = wgt; c.n_other = (double)h->views[i].m;
-      }
-    }
-    }
+    if (!vs.owned && !vs.side[SIDE_F].replica && !vs.side[SIDE_G].replica) continue;
+    if (int rc = fill_update(h, v, SIDE_F)) return rc;
+    if (vs.owned || vs.side[SIDE_G].replica)
+      if (int rc = fill_update(h, v, SIDE_G)) return rc;
     if (!vs.owned) continue;       // (replicas only ever run the update kernels)
     if (!vs.has_x) return h->fail(RESNMTF_ERR_STATE, "set_view missing for an owned view");
     // --- streaming passes
-    PassArgs& xg = vs.passXG;
-    xg = PassArgs{};
-    xg.A = vs.Xt32; xg.lda = 64; xg.tile_stride = vs.ldxt; xg.ntiles = vs.n_pad / 64; xg.B = vs.G32; xg.Bk = vs.Gk; xg.ldb = vs.kk_mode == 0 ? vs.KP : 64; xg.P = vs.Pxg;
-    xg.cols_pad = vs.n_pad; xg.rows_pad = vs.m_pad; xg.rows_per_split = vs.rps_xg; xg.nsplit = vs.nsplit_xg;
-    xg.tw = vs.tw_xg; xg.ntg = ceil_div(xg.ntiles, xg.tw);
-    xg.A16 = vs.Xt16; xg.tile_stride16 = vs.ld16xt;
-    xg.aux[0] = vs.G32; xg.aux[1] = vs.T32; xg.aux[2] = nullptr; xg.naux = 3;     // G^T G, T^T G, colSums(G)
-    xg.Paux = vs.Paux_xg; xg.rows_per_split_aux = vs.rpsaux_xg; xg.nsplit_aux = vs.nsaux_xg; xg.aux_cnt = vs.cnt_xg;
-    xg.ctl = h->ctl;
-    PassArgs& xt = vs.passXtF;
-    xt = PassArgs{};
-    xt.A = vs.X32; xt.lda = 64; xt.tile_stride = vs.ldx; xt.ntiles = vs.m_pad / 64; xt.B = vs.F32; xt.Bk = vs.Fk; xt.ldb = vs.kk_mode == 0 ? vs.KP : 64; xt.P = vs.Pxtf;
-    xt.cols_pad = vs.m_pad; xt.rows_pad = vs.n_pad; xt.rows_per_split = vs.rps_xtf; xt.nsplit = vs.nsplit_xtf;
-    xt.tw = vs.tw_xtf; xt.ntg = ceil_div(xt.ntiles, xt.tw);
-    xt.A16 = vs.X16; xt.tile_stride16 = vs.ld16x;
-    xt.aux[0] = vs.F32; xt.aux[1] = nullptr; xt.naux = 2;                          // F^T F, colSums(F)
-    xt.Paux = vs.Paux_xtf; xt.rows_per_split_aux = vs.rpsaux_xtf; xt.nsplit_aux = vs.nsaux_xtf; xt.aux_cnt = vs.cnt_xtf;
-    xt.ctl = h->ctl;
+    fill_pass(h, v, SIDE_F);
+    fill_pass(h, v, SIDE_G);
     // --- k x k side kernels
     KKFArgs& kf = vs.argKF;
     kf = KKFArgs{};
-    kf.k = vs.k; kf.S = vs.S; kf.part = vs.partF; kf.nblk = vs.nblkF;
-    kf.FtF = vs.FtF; kf.FtFS = vs.FtFS; kf.Ma_G = vs.Ma_G; kf.Md_G = vs.Md_G; kf.cF = vs.cF;
+    kf.k = vs.k; kf.S = vs.S; kf.part = vs.side[SIDE_F].part; kf.nblk = vs.side[SIDE_F].nblk;
+    kf.FtF = vs.FtF; kf.FtFS = vs.FtFS; kf.Ma_G = vs.side[SIDE_G].Ma; kf.Md_G = vs.side[SIDE_G].Md; kf.cF = vs.cF;
     KKSArgs& ks = vs.argKS;
     ks = KKSArgs{};
-    ks.k = vs.k; ks.mode = 1; ks.part = vs.partG; ks.nblk = vs.nblkG;
+    ks.k = vs.k; ks.mode = 1; ks.part = vs.side[SIDE_G].part; ks.nblk = vs.side[SIDE_G].nblk;
     ks.FtF = vs.FtF; ks.FtFS = vs.FtFS; ks.cF = vs.cF;
-    ks.S = vs.S; ks.lambda = vs.lambda; ks.mu = vs.mu; ks.Ma_F = vs.Ma_F; ks.Md_F = vs.Md_F;
+    ks.S = vs.S; ks.lambda = vs.side[SIDE_F].lm; ks.mu = vs.side[SIDE_G].lm; ks.Ma_F = vs.side[SIDE_F].Ma; ks.Md_F = vs.side[SIDE_F].Md;
     ks.xnorm2 = vs.xnorm2;
     ks.err = h->err; ks.err_stride = V; ks.err_col = v; ks.err_cap = h->err_cap;
     ks.err_host = h->err_host_dev; ks.ctl_host = h->ctl_host_dev;
@@ -2831,8 +2762,8 @@ static int build_args(resnmtf_handle* h) {
       }
     }
   }
-  build_chain(h);
-  build_g_chain(h);
+  build_chain(h, SIDE_F);
+  build_chain(h, SIDE_G);
   build_wide_chain(h);
   if (h->sliced)
     if (int rc = build_slice_chain(h)) return rc;
@@ -2892,7 +2823,7 @@ int resnmtf_phase(resnmtf_handle* h, int v, int phase, int sweep) {
   if (int rc = check_view(h, v)) return rc;
   if (!h->prepared) return h->fail(RESNMTF_ERR_STATE, "resnmtf_prepare has not been called");
   const ViewState& vs = h->views[v];
-  if (!vs.owned && !(vs.f_replica && phase == RESNMTF_PHASE_F) && phase != RESNMTF_PHASE_F_ALL && phase != RESNMTF_PHASE_LOCAL_SWEEP &&
+  if (!vs.owned && !(vs.side[SIDE_F].replica && phase == RESNMTF_PHASE_F) && phase != RESNMTF_PHASE_F_ALL && phase != RESNMTF_PHASE_LOCAL_SWEEP &&
       phase != RESNMTF_PHASE_G_ALL && phase != RESNMTF_PHASE_S_ALL)
     return h->fail(RESNMTF_ERR_STATE, "phase on a view this handle does not own");
   if (phase >= RESNMTF_PHASE_XTF && phase <= RESNMTF_PHASE_S_ALL && !h->opt.replicate_gs)
@@ -2934,7 +2865,7 @@ int resnmtf_phase(resnmtf_handle* h, int v, int phase, int sweep) {
           if (w.owned) enqueue_phase_g(h, w, -1.0, false);
         HIP_TRY(h, p2p_wait(h, 1, 1, sweep, 1));
         for (const auto& w : h->views)
-          if (w.owned) push_f_block(h, w);
+          if (w.owned) push_block(h, w, SIDE_F);
         p2p_signal(h, 0);
         break;
       }
@@ -2945,19 +2876,19 @@ int resnmtf_phase(resnmtf_handle* h, int v, int phase, int sweep) {
     // order keeps a writer behind its readers, and what every rank computes itself (coefficients,
     // lambda, mu) is never stored to a peer
     case RESNMTF_PHASE_XTF:
-      launch_pass(h, vs, false, 1, tol, checked); launch_fold_t(h, vs);
-      if (h->block_p2p) { push_g_block(h, vs); p2p_signal(h, 1); }
+      launch_pass(h, vs, false, 1, tol, checked); launch_fold(h, vs, SIDE_G);
+      if (h->block_p2p) { push_block(h, vs, SIDE_G); p2p_signal(h, 1); }
       break;
     case RESNMTF_PHASE_G_ALL:
       if (h->block_p2p) HIP_TRY(h, p2p_wait(h, 1, 2, sweep, 1));
       if (h->wchain_ok[1]) { launch_wide_chain(h, 1, checked); break; }
-      if (enqueue_g_chain(h, checked)) break;
+      if (enqueue_chain(h, SIDE_G, true, checked)) break;      // (the G form always reads one folded slab per view)
       for (const auto& w : h->views)
-        if (w.owned || w.g_replica) launch_update(h, w, 1, checked);
+        if (w.owned || w.side[SIDE_G].replica) launch_update(h, w, 1, checked);
       break;
     case RESNMTF_PHASE_XG:
-      launch_pass(h, vs, true, 1, tol, checked); launch_fold(h, vs);
-      if (h->block_p2p) { push_f_block(h, vs); p2p_signal(h, 0); }
+      launch_pass(h, vs, true, 1, tol, checked); launch_fold(h, vs, SIDE_F);
+      if (h->block_p2p) { push_block(h, vs, SIDE_F); p2p_signal(h, 0); }
       break;
     // slice_p2p: every phase first waits (in stream order, hipStreamWaitValue32) until the V arrivals of the exchange that
     // feeds it are in, and ends with one arrival on every rank's counter of the exchange it fed with peer stores.
@@ -3144,13 +3075,13 @@ int resnmtf_get_factors(resnmtf_handle* h, int v, double* F, double* S, double* 
   HIP_TRY(h, hipSetDevice(h->opt.device_id));
   if (int rc = sync_both(h)) return rc;
   std::vector<double> tmp;
-  if (F) { tmp.resize((size_t)vs.n * vs.k); HIP_TRY(h, hipMemcpy(tmp.data(), vs.F, tmp.size() * sizeof(double), hipMemcpyDeviceToHost)); to_col_major(tmp, vs.n, vs.k, F); }
+  if (F) { tmp.resize((size_t)vs.n * vs.k); HIP_TRY(h, hipMemcpy(tmp.data(), vs.side[SIDE_F].W, tmp.size() * sizeof(double), hipMemcpyDeviceToHost)); to_col_major(tmp, vs.n, vs.k, F); }
   if (S) { tmp.resize((size_t)vs.k * vs.k); HIP_TRY(h, hipMemcpy(tmp.data(), vs.S, tmp.size() * sizeof(double), hipMemcpyDeviceToHost)); to_col_major(tmp, vs.k, vs.k, S); }
-  if (G) { tmp.resize((size_t)vs.m * vs.k); HIP_TRY(h, hipMemcpy(tmp.data(), vs.G, tmp.size() * sizeof(double), hipMemcpyDeviceToHost)); to_col_major(tmp, vs.m, vs.k, G); }
+  if (G) { tmp.resize((size_t)vs.m * vs.k); HIP_TRY(h, hipMemcpy(tmp.data(), vs.side[SIDE_G].W, tmp.size() * sizeof(double), hipMemcpyDeviceToHost)); to_col_major(tmp, vs.m, vs.k, G); }
   if (lambda || mu) {
     if (!vs.owned) return h->fail(RESNMTF_ERR_STATE, "lambda/mu only exist on the owning handle");
-    if (lambda) HIP_TRY(h, hipMemcpy(lambda, vs.lambda, (size_t)vs.k * sizeof(double), hipMemcpyDeviceToHost));
-    if (mu) HIP_TRY(h, hipMemcpy(mu, vs.mu, (size_t)vs.k * sizeof(double), hipMemcpyDeviceToHost));
+    if (lambda) HIP_TRY(h, hipMemcpy(lambda, vs.side[SIDE_F].lm, (size_t)vs.k * sizeof(double), hipMemcpyDeviceToHost));
+    if (mu) HIP_TRY(h, hipMemcpy(mu, vs.side[SIDE_G].lm, (size_t)vs.k * sizeof(double), hipMemcpyDeviceToHost));
   }
   return RESNMTF_OK;
 }
@@ -3169,12 +3100,12 @@ int resnmtf_finalise(resnmtf_handle* h, int v, double* F, double* S, double* G, 
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&rel), (size_t)vs.k * sizeof(int));
   if (e != hipSuccess) { (void)hipFree(buf); return h->fail_hip("hipMalloc", e); }
   double *cF = buf, *cG = cF + vs.k, *So = cG + vs.k, *Fo = So + kk, *rc_ = Fo + nk, *Go = rc_ + nk, *cc = Go + mk;
-  hipLaunchKernelGGL(colsum_kernel, dim3(vs.k), dim3(256), 0, h->stream, vs.F, vs.n, vs.k, cF);
-  hipLaunchKernelGGL(colsum_kernel, dim3(vs.k), dim3(256), 0, h->stream, vs.G, vs.m, vs.k, cG);
+  hipLaunchKernelGGL(colsum_kernel, dim3(vs.k), dim3(256), 0, h->stream, vs.side[SIDE_F].W, vs.n, vs.k, cF);
+  hipLaunchKernelGGL(colsum_kernel, dim3(vs.k), dim3(256), 0, h->stream, vs.side[SIDE_G].W, vs.m, vs.k, cG);
   hipLaunchKernelGGL(finalise_s_kernel, dim3(1), dim3(64), 0, h->stream, vs.S, vs.k, cF, cG, So, rel);
-  hipLaunchKernelGGL(finalise_factor_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, h->stream, vs.F, vs.n,
+  hipLaunchKernelGGL(finalise_factor_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, h->stream, vs.side[SIDE_F].W, vs.n,
                      vs.k, cF, rel, Fo, rc_);
-  hipLaunchKernelGGL(finalise_factor_kernel, dim3((unsigned)((mk + 255) / 256)), dim3(256), 0, h->stream, vs.G, vs.m,
+  hipLaunchKernelGGL(finalise_factor_kernel, dim3((unsigned)((mk + 255) / 256)), dim3(256), 0, h->stream, vs.side[SIDE_G].W, vs.m,
                      vs.k, cG, (const int*)nullptr, Go, cc);
   e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -3251,21 +3182,21 @@ int relevance_impl(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, con
   if (e == hipSuccess) e = hipMemsetAsync(counts, 0, 2 * side * sizeof(unsigned int), h->stream);
   if (e == hipSuccess) {
     // the clusters resnmtf_finalise would emit: same kernels, same reductions, same first-max relations
-    hipLaunchKernelGGL(colsum_kernel, dim3(k), dim3(256), 0, h->stream, vs.F, vs.n, k, cF);
-    hipLaunchKernelGGL(colsum_kernel, dim3(k), dim3(256), 0, h->stream, vs.G, vs.m, k, cG);
+    hipLaunchKernelGGL(colsum_kernel, dim3(k), dim3(256), 0, h->stream, vs.side[SIDE_F].W, vs.n, k, cF);
+    hipLaunchKernelGGL(colsum_kernel, dim3(k), dim3(256), 0, h->stream, vs.side[SIDE_G].W, vs.m, k, cG);
     hipLaunchKernelGGL(finalise_s_kernel, dim3(1), dim3(64), 0, h->stream, vs.S, k, cF, cG, So, rel);
     const int grid_r = std::max(1, std::min(128, ceil_div(ceil_div(vs.n, 64), 4)));
     const int grid_c = std::max(1, std::min(128, ceil_div(ceil_div(vs.m, 64), 4)));
     if (!flags) {
-      hipLaunchKernelGGL(relevance_count_kernel<false>, dim3(grid_r), dim3(256), 0, h->stream, vs.F, vs.n, k, cF, (const int*)rel,
+      hipLaunchKernelGGL(relevance_count_kernel<false>, dim3(grid_r), dim3(256), 0, h->stream, vs.side[SIDE_F].W, vs.n, k, cF, (const int*)rel,
                          (const unsigned char*)rs.ref_cl, (const int*)idx, counts, (const int*)nullptr, (const unsigned char*)nullptr);
-      hipLaunchKernelGGL(relevance_count_kernel<false>, dim3(grid_c), dim3(256), 0, h->stream, vs.G, vs.m, k, cG, (const int*)nullptr,
+      hipLaunchKernelGGL(relevance_count_kernel<false>, dim3(grid_c), dim3(256), 0, h->stream, vs.side[SIDE_G].W, vs.m, k, cG, (const int*)nullptr,
                          (const unsigned char*)(rs.ref_cl + (size_t)rs.n * k), (const int*)(idx + vs.n), counts + side,
                          (const int*)nullptr, (const unsigned char*)nullptr);
     } else {                // the removal's zeroed cluster columns: flags through the relations, on both sides
-      hipLaunchKernelGGL(relevance_count_kernel<true>, dim3(grid_r), dim3(256), 0, h->stream, vs.F, vs.n, k, cF, (const int*)rel,
+      hipLaunchKernelGGL(relevance_count_kernel<true>, dim3(grid_r), dim3(256), 0, h->stream, vs.side[SIDE_F].W, vs.n, k, cF, (const int*)rel,
                          (const unsigned char*)rs.ref_cl, (const int*)idx, counts, (const int*)rel, (const unsigned char*)dflags);
-      hipLaunchKernelGGL(relevance_count_kernel<true>, dim3(grid_c), dim3(256), 0, h->stream, vs.G, vs.m, k, cG, (const int*)nullptr,
+      hipLaunchKernelGGL(relevance_count_kernel<true>, dim3(grid_c), dim3(256), 0, h->stream, vs.side[SIDE_G].W, vs.m, k, cG, (const int*)nullptr,
                          (const unsigned char*)(rs.ref_cl + (size_t)rs.n * k), (const int*)(idx + vs.n), counts + side,
                          (const int*)rel, (const unsigned char*)dflags);
     }
@@ -3313,7 +3244,7 @@ int bisil_impl(resnmtf_handle* h, int v, int k, const double* row_clusters, cons
   if (from_sparse && !vs.sparse) return h->fail(RESNMTF_ERR_STATE, "bisil_sparse of a dense view: use resnmtf_bisil");
   if (!from_sparse && vs.sparse) return h->fail(RESNMTF_ERR_STATE, "bisil of a sparse view is not supported (no dense fp32 image)");
   if (!vs.owned || !vs.has_x) return h->fail(RESNMTF_ERR_STATE, "no data on this handle for the view");
-  if (!from_sparse && (!vs.X32 || !vs.Xt32))
+  if (!from_sparse && (!vs.side[SIDE_G].X || !vs.side[SIDE_F].X))
     return h->fail(RESNMTF_ERR_STATE, "bisil needs the view's fp32 images (the view holds only a 2-byte image)");
   const int n = vs.n, m = vs.m;
   std::vector<unsigned long long> rbits(n, 0ull), cbits(m, 0ull);
@@ -3437,8 +3368,8 @@ int bisil_impl(resnmtf_handle* h, int v, int k, const double* row_clusters, cons
   for (int sd = 0; sd < 2 && e == hipSuccess; ++sd) {
     const BisilSide& s = side[sd];
     const int n_u = (int)s.upts.size(), upad = round_up(n_u, BISIL_TILE);
-    const float* img = sd == 0 ? vs.Xt32 : vs.X32;             // rows: X(row, col) = Xt32(col, row); columns: X32(row, col)
-    const size_t ld = sd == 0 ? vs.ldxt : vs.ldx;
+    const float* img = vs.side[sd].X;             // rows: X(row, col) = X^T image (col, row); columns: X image (row, col)
+    const size_t ld = vs.side[sd].ldx;
     double* out = sil + (sd == 0 ? 0 : (size_t)n * k);
     for (int j = 0; j < k && e == hipSuccess; ++j) {
       if (!((active >> j) & 1ull)) continue;
@@ -3452,8 +3383,8 @@ int bisil_impl(resnmtf_handle* h, int v, int k, const double* row_clusters, cons
       } else {      // rows: the features are columns, their entries in the CSC; columns: rows, in the CSR
         if ((e = hipMemsetAsync(G, 0, total * sizeof(float), h->stream)) != hipSuccess) break;
         hipLaunchKernelGGL(bisil_scatter_kernel, dim3((unsigned)std::min(ceil_div(nf, BISIL_THREADS / 64), 65536)), dim3(BISIL_THREADS), 0,
-                           h->stream, (const long long*)(sd == 0 ? vs.cp : vs.rp), (const int*)(sd == 0 ? vs.ri : vs.ci),
-                           (const float*)(sd == 0 ? vs.vcsc : vs.vcsr), feat, nf, dints + off_rank[sd], upad, G);
+                           h->stream, (const long long*)vs.side[1 - sd].sp_ptr, (const int*)vs.side[1 - sd].sp_idx,
+                           (const float*)vs.side[1 - sd].sp_val, feat, nf, dints + off_rank[sd], upad, G);
       }
       if (metric == BISIL_COSINE)
         hipLaunchKernelGGL(bisil_norm_kernel, dim3(ceil_div(upad, 256)), dim3(256), 0, h->stream, (const float*)G, nf, upad, norm2);
@@ -3595,9 +3526,9 @@ int resnmtf_spurious_scores(resnmtf_handle* h, int v, resnmtf_handle* const* shu
     // F / colSums(F) of every handle, as resnmtf_finalise computes it (same kernels), into its K pool columns
     for (int t = 0; t <= R; ++t) {
       const ViewState& src = t == 0 ? vs : shuffles[t - 1]->views[v];
-      hipLaunchKernelGGL(colsum_kernel, dim3(K), dim3(256), 0, h->stream, (const double*)src.F, n, K, cF);
+      hipLaunchKernelGGL(colsum_kernel, dim3(K), dim3(256), 0, h->stream, (const double*)src.side[SIDE_F].W, n, K, cF);
       hipLaunchKernelGGL(finalise_factor_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, h->stream,
-                         (const double*)src.F, n, K, (const double*)cF, (const int*)nullptr, pool + (size_t)t * nk, cl);
+                         (const double*)src.side[SIDE_F].W, n, K, (const double*)cF, (const int*)nullptr, pool + (size_t)t * nk, cl);
     }
     hipLaunchKernelGGL(jsd_finite_kernel, dim3((unsigned)std::min<size_t>(1024, (total + 255) / 256)), dim3(256), 0,
                        h->stream, (const double*)pool, total, dflag);
@@ -3889,21 +3820,21 @@ int resnmtf_factor_device_ptr(resnmtf_handle* h, int v, int which, void** ptr, s
   if (!ptr || !bytes) return h->fail(RESNMTF_ERR_INVALID, "ptr/bytes are NULL");
   ViewState& vs = h->views[v];
   switch (which) {
-    case RESNMTF_FACTOR_F: *ptr = vs.F; *bytes = (size_t)vs.n * vs.k * sizeof(double); break;
-    case RESNMTF_FACTOR_G: *ptr = vs.G; *bytes = (size_t)vs.m * vs.k * sizeof(double); break;
+    case RESNMTF_FACTOR_F: *ptr = vs.side[SIDE_F].W; *bytes = (size_t)vs.n * vs.k * sizeof(double); break;
+    case RESNMTF_FACTOR_G: *ptr = vs.side[SIDE_G].W; *bytes = (size_t)vs.m * vs.k * sizeof(double); break;
     case RESNMTF_FACTOR_S: *ptr = vs.S; *bytes = (size_t)vs.k * vs.k * sizeof(double); break;
     case RESNMTF_FACTOR_FBLOCK:
-      if (!vs.fblk) return h->fail(RESNMTF_ERR_STATE, "no F exchange block: create the handle with replicate_f = 1");
-      *ptr = vs.fblk; *bytes = vs.fblk_bytes; break;
+      if (!vs.side[SIDE_F].xblk) return h->fail(RESNMTF_ERR_STATE, "no F exchange block: create the handle with replicate_f = 1");
+      *ptr = vs.side[SIDE_F].xblk; *bytes = vs.side[SIDE_F].xblk_bytes; break;
     case RESNMTF_FACTOR_FBLOCK_ALL:
-      if (!h->fblk_arena) return h->fail(RESNMTF_ERR_STATE, "no F exchange blocks: create the handle with replicate_f = 1");
-      *ptr = h->fblk_arena; *bytes = h->fblk_arena_bytes; break;
+      if (!h->arena[SIDE_F]) return h->fail(RESNMTF_ERR_STATE, "no F exchange blocks: create the handle with replicate_f = 1");
+      *ptr = h->arena[SIDE_F]; *bytes = h->arena_bytes[SIDE_F]; break;
     case RESNMTF_FACTOR_GBLOCK:
-      if (!vs.gblk) return h->fail(RESNMTF_ERR_STATE, "no G exchange block: create the handle with replicate_gs = 1");
-      *ptr = vs.gblk; *bytes = vs.gblk_bytes; break;
+      if (!vs.side[SIDE_G].xblk) return h->fail(RESNMTF_ERR_STATE, "no G exchange block: create the handle with replicate_gs = 1");
+      *ptr = vs.side[SIDE_G].xblk; *bytes = vs.side[SIDE_G].xblk_bytes; break;
     case RESNMTF_FACTOR_GBLOCK_ALL:
-      if (!h->gblk_arena) return h->fail(RESNMTF_ERR_STATE, "no G exchange blocks: create the handle with replicate_gs = 1");
-      *ptr = h->gblk_arena; *bytes = h->gblk_arena_bytes; break;
+      if (!h->arena[SIDE_G]) return h->fail(RESNMTF_ERR_STATE, "no G exchange blocks: create the handle with replicate_gs = 1");
+      *ptr = h->arena[SIDE_G]; *bytes = h->arena_bytes[SIDE_G]; break;
     case RESNMTF_FACTOR_SBLOCK:
       if (!vs.sblk) return h->fail(RESNMTF_ERR_STATE, "no S exchange block: create the handle with replicate_gs = 1");
       *ptr = vs.sblk; *bytes = h->sblk_stride * sizeof(double); break;
@@ -3916,21 +3847,21 @@ int resnmtf_factor_device_ptr(resnmtf_handle* h, int v, int which, void** ptr, s
     case RESNMTF_FACTOR_F_SLICE: case RESNMTF_FACTOR_G_SLICE: {
       if (!h->sliced) return h->fail(RESNMTF_ERR_STATE, "no slice buffers: create the handle with slice_chains = 1");
       const size_t V = (size_t)h->V;
-      const size_t fbytes = V * h->sl_rows * vs.KP * sizeof(float), gbytes = V * h->sl_cols * vs.KP * sizeof(float);
+      const size_t fbytes = V * h->sl_len[SIDE_F] * vs.KP * sizeof(float), gbytes = V * h->sl_len[SIDE_G] * vs.KP * sizeof(float);
       switch (which) {
-        case RESNMTF_FACTOR_U_SEND: *ptr = h->u_send; *bytes = V * h->u_chunk; break;
-        case RESNMTF_FACTOR_U_RECV: *ptr = h->u_recv; *bytes = V * h->u_chunk; break;
-        case RESNMTF_FACTOR_T_SEND: *ptr = h->t_send; *bytes = V * h->t_chunk; break;
-        case RESNMTF_FACTOR_T_RECV: *ptr = h->t_recv; *bytes = V * h->t_chunk; break;
-        case RESNMTF_FACTOR_FNEW_SEND: *ptr = h->f_send; *bytes = fbytes; break;
-        case RESNMTF_FACTOR_FNEW_RECV: *ptr = h->f_recv; *bytes = fbytes; break;
-        case RESNMTF_FACTOR_GNEW_SEND: *ptr = h->g_send; *bytes = gbytes; break;
-        case RESNMTF_FACTOR_GNEW_RECV: *ptr = h->g_recv; *bytes = gbytes; break;
+        case RESNMTF_FACTOR_U_SEND: *ptr = h->p_send[SIDE_F]; *bytes = V * h->p_chunk[SIDE_F]; break;
+        case RESNMTF_FACTOR_U_RECV: *ptr = h->p_recv[SIDE_F]; *bytes = V * h->p_chunk[SIDE_F]; break;
+        case RESNMTF_FACTOR_T_SEND: *ptr = h->p_send[SIDE_G]; *bytes = V * h->p_chunk[SIDE_G]; break;
+        case RESNMTF_FACTOR_T_RECV: *ptr = h->p_recv[SIDE_G]; *bytes = V * h->p_chunk[SIDE_G]; break;
+        case RESNMTF_FACTOR_FNEW_SEND: *ptr = h->w_send[SIDE_F]; *bytes = fbytes; break;
+        case RESNMTF_FACTOR_FNEW_RECV: *ptr = h->w_recv[SIDE_F]; *bytes = fbytes; break;
+        case RESNMTF_FACTOR_GNEW_SEND: *ptr = h->w_send[SIDE_G]; *bytes = gbytes; break;
+        case RESNMTF_FACTOR_GNEW_RECV: *ptr = h->w_recv[SIDE_G]; *bytes = gbytes; break;
         default: {
-          const bool f = which == RESNMTF_FACTOR_F_SLICE;
-          const int per = f ? h->sl_rows : h->sl_cols, full = f ? vs.n : vs.m;
+          const int s = which == RESNMTF_FACTOR_F_SLICE ? SIDE_F : SIDE_G;
+          const int per = h->sl_len[s], full = vs.side[s].len;
           const int begin = std::min(h->opt.slice_index * per, full), len = std::min(per, full - begin);
-          *ptr = (f ? vs.F : vs.G) + (size_t)begin * vs.k; *bytes = (size_t)len * vs.k * sizeof(double);
+          *ptr = vs.side[s].W + (size_t)begin * vs.k; *bytes = (size_t)len * vs.k * sizeof(double);
         }
       }
       break;
@@ -3963,8 +3894,8 @@ int resnmtf_loop_state(resnmtf_handle* h, int* sweeps_done, int* done, int* stop
 int resnmtf_slice_info(resnmtf_handle* h, int* rows_per_slice, int* cols_per_slice) {
   if (!h) return RESNMTF_ERR_INVALID;
   if (!h->sliced) return h->fail(RESNMTF_ERR_STATE, "not a slice_chains handle");
-  if (rows_per_slice) *rows_per_slice = h->sl_rows;
-  if (cols_per_slice) *cols_per_slice = h->sl_cols;
+  if (rows_per_slice) *rows_per_slice = h->sl_len[SIDE_F];
+  if (cols_per_slice) *cols_per_slice = h->sl_len[SIDE_G];
   return RESNMTF_OK;
 }
 
@@ -3972,9 +3903,9 @@ int resnmtf_slice_info(resnmtf_handle* h, int* rows_per_slice, int* cols_per_sli
 // exchange arenas of the replicated layouts (those the layout has); the arrival counters in both
 static void p2p_buffers(resnmtf_handle* h, void* bufs[6]) {
   if (h->block_p2p) {
-    bufs[0] = h->fblk_arena; bufs[1] = nullptr; bufs[2] = h->gblk_arena; bufs[3] = nullptr; bufs[4] = h->sblk_arena;
+    bufs[0] = h->arena[SIDE_F]; bufs[1] = nullptr; bufs[2] = h->arena[SIDE_G]; bufs[3] = nullptr; bufs[4] = h->sblk_arena;
   } else {
-    bufs[0] = h->u_recv; bufs[1] = h->f_recv; bufs[2] = h->t_recv; bufs[3] = h->g_recv; bufs[4] = h->sblk_arena;
+    bufs[0] = h->p_recv[SIDE_F]; bufs[1] = h->w_recv[SIDE_F]; bufs[2] = h->p_recv[SIDE_G]; bufs[3] = h->w_recv[SIDE_G]; bufs[4] = h->sblk_arena;
   }
   bufs[5] = h->p2p_flags;
 }
@@ -4017,10 +3948,10 @@ int resnmtf_p2p_import(resnmtf_handle* h, int rank, const void* handles, size_t 
     }
   }
   if (h->block_p2p) {
-    pc.fblk_arena = static_cast<char*>(ptr[0]); pc.gblk_arena = static_cast<char*>(ptr[2]);
+    pc.arena[SIDE_F] = static_cast<char*>(ptr[0]); pc.arena[SIDE_G] = static_cast<char*>(ptr[2]);
   } else {
-    pc.u_recv = static_cast<char*>(ptr[0]); pc.f_recv = static_cast<float*>(ptr[1]); pc.t_recv = static_cast<char*>(ptr[2]);
-    pc.g_recv = static_cast<float*>(ptr[3]);
+    pc.p_recv[SIDE_F] = static_cast<char*>(ptr[0]); pc.w_recv[SIDE_F] = static_cast<float*>(ptr[1]); pc.p_recv[SIDE_G] = static_cast<char*>(ptr[2]);
+    pc.w_recv[SIDE_G] = static_cast<float*>(ptr[3]);
   }
   pc.sblk = static_cast<double*>(ptr[4]); pc.flags = static_cast<unsigned int*>(ptr[5]);
   pc.imported = true;
@@ -4043,8 +3974,8 @@ int resnmtf_p2p_selftest(resnmtf_handle* h, int timeout_ms) {
   // where rank `from` writes on rank `on` (a place the run prologue overwrites): block form -- the head of view `from`'s U
   // rows in the F arena; sliced form -- the head of chunk `from` of the U receive buffer
   auto region = [&](char* f_arena, char* u_recv, int from) -> unsigned int* {
-    if (h->block_p2p) return reinterpret_cast<unsigned int*>(f_arena + (static_cast<const char*>(h->views[(size_t)from].fblk) - static_cast<const char*>(h->fblk_arena)));
-    return reinterpret_cast<unsigned int*>(u_recv + (size_t)from * h->u_chunk);
+    if (h->block_p2p) return reinterpret_cast<unsigned int*>(f_arena + (static_cast<const char*>(h->views[(size_t)from].side[SIDE_F].xblk) - static_cast<const char*>(h->arena[SIDE_F])));
+    return reinterpret_cast<unsigned int*>(u_recv + (size_t)from * h->p_chunk[SIDE_F]);
   };
   // host-side waits, all under the one deadline
   auto poll_flag = [&](int flag, unsigned int want, const char* what) -> int {
@@ -4089,7 +4020,7 @@ int resnmtf_p2p_selftest(resnmtf_handle* h, int timeout_ms) {
     P2pProbeArgs a{};
     a.tag = tag_of(r);
     for (int c = 0; c < V; ++c)
-      if (c != r) a.dst[a.n_dst++] = region(h->peers[(size_t)c].fblk_arena, h->peers[(size_t)c].u_recv, r);
+      if (c != r) a.dst[a.n_dst++] = region(h->peers[(size_t)c].arena[SIDE_F], h->peers[(size_t)c].p_recv[SIDE_F], r);
     if (a.n_dst) hipLaunchKernelGGL(p2p_probe_kernel, dim3(1), dim3(kWords), 0, h->stream, a);
     p2p_signal(h, kProbeFlag);
     HIP_TRY(h, hipGetLastError());
@@ -4098,7 +4029,7 @@ int resnmtf_p2p_selftest(resnmtf_handle* h, int timeout_ms) {
     HIP_TRY(h, hipStreamWaitValue32(h->stream, h->p2p_flags + kProbeFlag, want, hipStreamWaitValueGte, 0xFFFFFFFFu));
     P2pCheckArgs ck{};
     for (int c = 0; c < V; ++c)
-      if (c != r) { ck.src[ck.n_src] = region(static_cast<char*>(h->fblk_arena), h->u_recv, c); ck.tag[ck.n_src++] = tag_of(c); }
+      if (c != r) { ck.src[ck.n_src] = region(static_cast<char*>(h->arena[SIDE_F]), h->p_recv[SIDE_F], c); ck.tag[ck.n_src++] = tag_of(c); }
     ck.bad = bad_dev;
     if (ck.n_src) hipLaunchKernelGGL(p2p_check_kernel, dim3(1), dim3(kWords), 0, h->stream, ck);
     HIP_TRY(h, hipGetLastError());
@@ -4115,7 +4046,7 @@ int resnmtf_p2p_selftest(resnmtf_handle* h, int timeout_ms) {
   }
   h->probe_epoch += 1;
   for (int c = 0; c < V; ++c)
-    if (c != r) HIP_TRY(h, hipMemset(region(static_cast<char*>(h->fblk_arena), h->u_recv, c), 0, kWords * sizeof(unsigned int)));
+    if (c != r) HIP_TRY(h, hipMemset(region(static_cast<char*>(h->arena[SIDE_F]), h->p_recv[SIDE_F], c), 0, kWords * sizeof(unsigned int)));
   return RESNMTF_OK;
 }
 
@@ -4196,15 +4127,16 @@ int resnmtf_view_plan(resnmtf_handle* h, int v, resnmtf_view_plan_info* out) {
     if (L.image >= 2) p.half_unroll = L.unroll;
     p.wide[i] = L.wide; p.xcd_order[i] = L.xcd_order; p.waves[i] = L.waves; p.pingpong[i] = L.pingpong;
     p.unroll[i] = L.image == 0 ? L.unroll : 0;
-    p.nsplit[i] = xg ? vs.nsplit_xg : vs.nsplit_xtf;
-    p.rows[i] = xg ? vs.m : vs.n; p.rows_pad[i] = xg ? vs.m_pad : vs.n_pad; p.ntiles[i] = (xg ? vs.n_pad : vs.m_pad) / 64;
-    if (L.image != 1) { p.rows_per_split[i] = xg ? vs.rps_xg : vs.rps_xtf; p.short_last[i] = L.short_last; }
+    const Side &sd = vs.side[i], &red = vs.side[other(i)];      // (i = the side the pass feeds; it reduces over the other)
+    p.nsplit[i] = sd.nsplit;
+    p.rows[i] = red.len; p.rows_pad[i] = red.pad; p.ntiles[i] = sd.pad / 64;
+    if (L.image != 1) { p.rows_per_split[i] = sd.rps; p.short_last[i] = L.short_last; }
     p.tiles_per_wg[i] = L.tiles_per_wg;
-    p.aux_splits[i] = L.mode_a ? 0 : (xg ? vs.nsaux_xg : vs.nsaux_xtf);
-    p.sparse_blocks[i] = L.image == 1 ? (xg ? vs.nblk_xg : vs.nblk_xtf) : 0;
+    p.aux_splits[i] = L.mode_a ? 0 : sd.nsaux;
+    p.sparse_blocks[i] = L.image == 1 ? sd.sp_nblk : 0;
   }
   if (!vs.sparse) {
-    p.pitch_pad = vs.ldx != (size_t)vs.n_pad * 64 ? 1 : 0;
+    p.pitch_pad = vs.side[SIDE_G].ldx != (size_t)vs.n_pad * 64 ? 1 : 0;
     p.lds_pad_kb = h->opt.pass_lds_pad_kb;
   }
   p.prepared = h->prepared ? 1 : 0;
@@ -4228,13 +4160,13 @@ int resnmtf_pass_timings(resnmtf_handle* h, resnmtf_pass_timing* out, int reset)
     // (a launch that carries the update of its B operand -- pass_fused_kernel -- also moves that update's algorithmic bytes:
     //  product rows 4 len k once, the fp64 factor 8 len k in and out, its f32 copy 4 len k out)
     out->xg_bytes = sx * n * m + 4.0 * (n + m) * k + (can_fuse_update(h, v, 1) ? 24.0 * m * k : 0.0);
-    out->xtf_bytes = sx * n * m + 4.0 * (n + m) * k + (can_fuse_update(h, v, 0) && h->all_owned && h->chain_views == 0 ? 24.0 * n * k : 0.0);
+    out->xtf_bytes = sx * n * m + 4.0 * (n + m) * k + (can_fuse_update(h, v, 0) && h->all_owned && h->chain_views[SIDE_F] == 0 ? 24.0 * n * k : 0.0);
     out->xg_flops = 2.0 * n * m * k;
     out->xtf_flops = 2.0 * n * m * k;
     if (L.image == 1) {      // values + indices + pointers + gathered factor rows (f32, KP wide) + slabs written
       const double z = (double)v.nnz, kp = v.KP;
-      out->xg_bytes = 8.0 * z + 8.0 * (n + 1) + 4.0 * kp * z + 4.0 * kp * n * v.nsplit_xg;
-      out->xtf_bytes = 8.0 * z + 8.0 * (m + 1) + 4.0 * kp * z + 4.0 * kp * m * v.nsplit_xtf;
+      out->xg_bytes = 8.0 * z + 8.0 * (n + 1) + 4.0 * kp * z + 4.0 * kp * n * v.side[SIDE_F].nsplit;
+      out->xtf_bytes = 8.0 * z + 8.0 * (m + 1) + 4.0 * kp * z + 4.0 * kp * m * v.side[SIDE_G].nsplit;
       out->xg_flops = out->xtf_flops = 2.0 * z * k;
     }
     break;
