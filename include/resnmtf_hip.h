@@ -253,7 +253,8 @@ int resnmtf_destroy(resnmtf_handle* h);
  * dense path's; hand-off mode A at every k; x_half, fuse_updates and the view-sharded layouts (replicate_f / replicate_gs /
  * slice_chains / slice_p2p: refused) never apply.  resnmtf_get_view, resnmtf_copy_view, resnmtf_shuffle_view and
  * resnmtf_subsample_view refuse a sparse view (RESNMTF_ERR_INVALID) instead of densifying it; a sparse view is shuffled
- * by resnmtf_shuffle_view_sparse (it stays sparse) and read back by resnmtf_get_view_csc.
+ * by resnmtf_shuffle_view_sparse, copied by resnmtf_copy_view_sparse and sub-sampled by resnmtf_subsample_view_sparse (it
+ * stays sparse), and read back by resnmtf_get_view_csc.
  * resnmtf_bisil refuses one too (RESNMTF_ERR_STATE: it reads the fp32 images); resnmtf_bisil_sparse scores it from the
  * CSC / CSR copies.
  * Replaces: as resnmtf_create (R/main.r:38-48) for views that R holds as Matrix::dgCMatrix (R/utils.r:416-419 densifies
@@ -294,6 +295,41 @@ int resnmtf_view_storage(resnmtf_handle* h, int v, int* is_sparse, long long* nn
  */
 int resnmtf_shuffle_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src, unsigned long long seed,
                                 int normalise);
+/*
+ * Sub-samples and copies of sparse views on the device (DESIGN.md section 10 "Device copies and sub-samples").
+ *
+ * resnmtf_subsample_count_sparse: the number of stored entries (stored zeros included) of X[rows, cols] of sparse view
+ * v_src -- what the nnz_capacity of a destination for resnmtf_subsample_view_sparse must be at least.  rows holds n_rows
+ * and cols n_cols 0-based indices, in any order; nothing is built and the view is not changed.
+ * Replaces: the size of data[[i]][row_samples[[i]], col_samples[[i]]] (R/stability_analysis.r:124, :184, :232, :238),
+ * which R's Matrix package finds while it builds the sub-matrix.
+ *
+ * resnmtf_subsample_view_sparse: dst's sparse view v = X[rows, cols] of src's sparse view v_src, as a sparse view.  rows
+ * holds dst view v's n entries, cols its m entries, as in resnmtf_subsample_view, in any order (R's sample is unsorted:
+ * destination row i is source row rows[i]).  The values are carried over as stored, fp32, NOT re-normalised;
+ * stored zeros stay stored.  The view is bit for bit -- pointers, indices, both value arrays, data_norms, the work split of
+ * the passes -- the one resnmtf_set_view_csc(pre_processed = 1) makes of the same sub-sample built on the host from
+ * resnmtf_get_view_csc of the source.  The rows and columns without a stored entry > 0 (the trimming condition,
+ * R/stability_analysis.r:165-190, :233-240) are reported by resnmtf_view_empty_lines, as after resnmtf_subsample_view.
+ * Replaces: data[[i]][row_samples[[i]], col_samples[[i]]] (R/stability_analysis.r:124, :184, :232, :238).
+ *
+ * resnmtf_copy_view_sparse: dst's sparse view v = src's sparse view v_src, device to device, as resnmtf_copy_view does for
+ * dense views (the k sweep, R/main.r:279-290, factorises the same data for every k); k may differ between the handles --
+ * the work split of the passes is planned again for dst's k.  Bit for bit resnmtf_set_view_csc(pre_processed = 1) of the
+ * source's read-back on dst, with the source's data_norms.
+ *
+ * Refused on the host before any launch, the destination left as it was (RESNMTF_ERR_INVALID): NULL arguments, a dense
+ * source or destination (resnmtf_subsample_view / resnmtf_copy_view take those), handles on different devices, for the
+ * copy views that differ in shape, an index out of range, an index that occurs twice in rows or in cols (the reference
+ * samples without replacement); a view that is not owned or a source that has not been uploaded (RESNMTF_ERR_STATE).
+ * A destination whose nnz_capacity is below the stored entries of the sub-sample (known after the counting pass, which
+ * writes nothing of dst) or of the source is refused too (RESNMTF_ERR_INVALID; the text names both numbers).
+ */
+int resnmtf_subsample_count_sparse(resnmtf_handle* src, int v_src, int n_rows, const int* rows, int n_cols, const int* cols,
+                                   long long* nnz);
+int resnmtf_subsample_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src, const int* rows,
+                                  const int* cols);
+int resnmtf_copy_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src);
 /*
  * The device CSC copy of a sparse view back on the host: col_ptr [m + 1], row_idx / values [nnz] (nnz from
  * resnmtf_view_storage; values at fp32 precision) -- the @p / @i / @x slots of the dgCMatrix that R/utils.r:416-419 would

@@ -105,6 +105,9 @@ SIGNATURES = {
     "resnmtf_set_view_csc": (C.c_int, [_h, C.c_int, C.POINTER(C.c_longlong), _ip, _dp, C.c_int]),
     "resnmtf_view_storage": (C.c_int, [_h, C.c_int, _ip, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "resnmtf_shuffle_view_sparse": (C.c_int, [_h, C.c_int, _h, C.c_int, C.c_ulonglong, C.c_int]),
+    "resnmtf_subsample_count_sparse": (C.c_int, [_h, C.c_int, C.c_int, _ip, C.c_int, _ip, C.POINTER(C.c_longlong)]),
+    "resnmtf_subsample_view_sparse": (C.c_int, [_h, C.c_int, _h, C.c_int, _ip, _ip]),
+    "resnmtf_copy_view_sparse": (C.c_int, [_h, C.c_int, _h, C.c_int]),
     "resnmtf_get_view_csc": (C.c_int, [_h, C.c_int, C.POINTER(C.c_longlong), _ip, _dp]),
     "resnmtf_set_view": (C.c_int, [_h, C.c_int, _dp]),
     "resnmtf_set_view_raw": (C.c_int, [_h, C.c_int, _dp, _ip]),

@@ -17,6 +17,13 @@ copy and scored on the device (``spurious.check_on_device``).  Without the opt-i
 ``NotImplementedError`` as before.  On ``scipy.sparse`` views the removal needs the further opt-in
 ``shuffle_sparse=True``: their shuffles are drawn on the device as sparse views (``resnmtf_shuffle_view_sparse``).
 
+Copies (the k sweep) and sub-samples (stability selection, its trimming probes included) of ``scipy.sparse`` views are
+gathered on the host and uploaded, unless the keyword-only opt-in ``sparse_on_device=True`` is given: then they are made
+on the device from the one upload (``resnmtf_copy_view_sparse``, ``resnmtf_subsample_count_sparse`` +
+``resnmtf_subsample_view_sparse``).  Same clusters and factors; a sub-sample's ``data_norms`` is then summed from the f32
+values the device holds, so ``All_Error`` of the stability repeats may move (tested bar: 1e-6 absolute; not at all when the data are
+f32-representable); copies are bitwise.  No effect on dense data.
+
 The bisilhouette score (``bisil``, ``R/obtain_bicl.r:189-199``) is an opt-in here: ``res_nmtf_inner(score_bisil=True)``
 scores the result on the device (per-member silhouettes from ``resnmtf_bisil``, combined by ``bisil.py``), and
 ``apply_resnmtf(k_val=None, k_sweep=True)`` runs the reference's k sweep on it (``R/main.r:269-334``).  Sparse views
@@ -78,7 +85,8 @@ def res_nmtf_inner(data, row_indices, column_indices,
                    no_clusts=False, *, row_names=None, col_names=None, device_id: int = 0,
                    max_iters: int = 100000, seed: Optional[int] = None, engine_opts: Optional[dict] = None,
                    host_init: bool = False, return_init: bool = False, score_bisil: bool = False,
-                   spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False):
+                   spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False,
+                   sparse_on_device: bool = False):
     """``res_nmtf_inner`` (``R/main.r:32-140``).
 
     ``data``: list of pre-processed (non-negative, column-normalised) matrices; ``row_indices[v][w]``
@@ -105,7 +113,10 @@ def res_nmtf_inner(data, row_indices, column_indices,
     ``shuffle_sparse``), ``shuffle_sparse`` (opt-in: the removal then runs on sparse views too -- each is shuffled on the
     device as a sparse view, ``Engine.shuffle_view_sparse_from``: the dense path's draw of the densified view, same seeds,
     same redraw rule; a view with fewer stored entries than ``max(n, m)`` raises ``ValueError``, no shuffle of it can pass
-    the rule; pass the same flag to ``remove_spurious`` for the identity above; no effect on dense views).
+    the rule; pass the same flag to ``remove_spurious`` for the identity above; no effect on dense views),
+    ``sparse_on_device`` (a no-op here by design, DESIGN.md section 10: accepted so that callers pass one set of flags to
+    every entry point; this function uploads ``data`` itself and its spurious children are shuffles, which always draw
+    from the engine's own handle, so it has no copy or sub-sample to route).
     """
     data = _views(data)
     n_v = len(data)
@@ -226,7 +237,7 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
                     sample_rate=0.9, n_stability=5, stab_thres=0.6, remove_unstable=True, *,
                     row_names=None, col_names=None, device_id: int = 0, seed: Optional[int] = None, group=None,
                     max_iters: int = 100000, return_repeats: bool = False, repeat_runner: Optional[Callable] = None,
-                    spurious_on_device: bool = False, shuffle_sparse: bool = False):
+                    spurious_on_device: bool = False, shuffle_sparse: bool = False, sparse_on_device: bool = False):
     """``stability_check`` (``R/stability_analysis.r:302-338``): ``n_stability`` factorisations of sub-samples
     (``sample_rate`` of the rows and columns, drawn and trimmed as ``stability_repeat`` does, ``:215-249``), each scored
     against ``results`` by ``relevance_results`` (``:45-67``) -- the gathers, the factorisations and the scoring run on
@@ -244,7 +255,9 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
     relevance is scored (``R/stability_analysis.r:254-266``; ``batched.stability_relevance_on_device``, spurious seed
     ``seed + 2000 + r`` for repeat r); without it, ``NotImplementedError`` as before.  On sparse views the removal needs
     the further opt-in ``shuffle_sparse=True``: the shuffles are drawn from each repeat's own sparse sub-sample handle
-    and re-normalised (``Engine.shuffle_view_sparse_from``).
+    and re-normalised (``Engine.shuffle_view_sparse_from``).  ``sparse_on_device=True`` (opt-in): the sub-samples of
+    sparse views are probed, trimmed and gathered on the device (``resnmtf_subsample_view_sparse``) instead of on the
+    host; same draws, clusters and factors, ``All_Error`` within 1e-6 absolute (module docstring).
     Keyword-only extras: names, ``device_id``, ``seed`` of the draws and the device SVD inits, ``group``,
     ``max_iters``; test hooks: ``return_repeats`` (adds ``"repeats"``: per repeat the trimmed draws, relevance and
     the sub-sample's own clusters -- under ``"stability"`` of a copy of the result), ``repeat_runner(r)`` (replaces
@@ -275,7 +288,8 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
         stab = batched.stability_relevance_on_device(dev, results, k, int(n_stability), float(sample_rate), n_iters,
                                                      seed, group, max_iters, keep_clusters=return_repeats,
                                                      runner=repeat_runner, spurious_repeats=spurious_repeats,
-                                                     shuffle_sparse=shuffle_sparse)
+                                                     shuffle_sparse=shuffle_sparse,
+                                                     **({"sparse_on_device": True} if sparse_on_device else {}))
     finally:
         if dev is not None:
             dev.close()
@@ -306,7 +320,8 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                   remove_unstable=True, use_parallel=True, *, row_names=None, col_names=None,
                   device_id: int = 0, max_iters: int = 100000, seed: Optional[int] = None,
                   k_sweep: bool = False, return_sweep: bool = False, sweep_runner: Optional[Callable] = None,
-                  spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False):
+                  spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False,
+                  sparse_on_device: bool = False):
     """``apply_resnmtf`` (``R/main.r:214-335``) for a known ``k_val``: naming, shared-name maps, restriction
     symmetrisation, non-negativity shift and column normalisation on the host, then the device loop and -- with
     ``stability=True`` (the default) and ``spurious=False`` -- ``stability_check`` on the pre-processed data, as
@@ -339,7 +354,14 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     a sparse view is drawn on the device as a sparse view (``resnmtf_shuffle_view_sparse``: the dense path's draw of
     the densified view, DESIGN.md section 10 "Sparse shuffles"), in ``res_nmtf_inner``, for every k of the sweep and
     inside the stability repeats.  The reference's default pipeline on sparse data is ``apply_resnmtf(data,
-    k_sweep=True, spurious_on_device=True, bisil_sparse=True, shuffle_sparse=True)``.  No effect on dense data."""
+    k_sweep=True, spurious_on_device=True, bisil_sparse=True, shuffle_sparse=True)``.  No effect on dense data.
+
+    ``sparse_on_device=True`` (keyword-only opt-in): the copies of sparse views the k sweep makes for every k and the
+    sub-samples of the stability repeats are made on the device from the one upload (``resnmtf_copy_view_sparse``,
+    ``resnmtf_subsample_view_sparse``; DESIGN.md section 10 "Device copies and sub-samples") instead of gathered on the
+    host and uploaded.  Same clusters, factors and stability outcome; ``All_Error`` of the repeats within 1e-6 absolute.  No
+    effect on dense data."""
+    on_dev = {"sparse_on_device": True} if sparse_on_device else {}      # (off: every call below is the earlier one)
     data = _views(data)
     n_v = len(data)
     if k_val is None and k_sweep:
@@ -348,7 +370,7 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                               row_names=row_names, col_names=col_names, device_id=device_id, max_iters=max_iters,
                               seed=seed, return_sweep=return_sweep, sweep_runner=sweep_runner,
                               spurious_on_device=spurious_on_device, bisil_sparse=bisil_sparse,
-                              shuffle_sparse=shuffle_sparse)
+                              shuffle_sparse=shuffle_sparse, **on_dev)
     if k_val is None:
         raise NotImplementedError("the k sweep (R/main.r:279-321) needs the bisilhouette score, which is "
                                   "outside the accelerated path; pass k_val")
@@ -367,13 +389,13 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     results = res_nmtf_inner(p.data, p.row_shared, p.col_shared, init_f, init_s, init_g, k_vec, p.phi, p.xi, p.psi,
                              n_iters, num_repeats, spurious, distance, no_clusts,
                              row_names=p.row_names, col_names=p.col_names, device_id=device_id, max_iters=max_iters,
-                             seed=seed, spurious_on_device=spurious_on_device, shuffle_sparse=shuffle_sparse)
+                             seed=seed, spurious_on_device=spurious_on_device, shuffle_sparse=shuffle_sparse, **on_dev)
     if stability:                                                                                 # main.r:255-262
         results = stability_check(p.data, results, k_vec, p.phi, p.xi, p.psi, n_iters, spurious, num_repeats,
                                   no_clusts, distance, sample_rate, n_stability, stab_thres,
                                   row_names=p.row_names, col_names=p.col_names, device_id=device_id, seed=seed,
                                   max_iters=max_iters, spurious_on_device=spurious_on_device,
-                                  shuffle_sparse=shuffle_sparse)
+                                  shuffle_sparse=shuffle_sparse, **on_dev)
     return results
 
 
@@ -410,9 +432,10 @@ def _sweep(run: Callable, k_min: int, k_max: int, cap: int, initial: Optional[li
 def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k_max, distance, spurious, num_repeats,
                    no_clusts, sample_rate, n_stability, stability, stab_thres, remove_unstable, *, row_names, col_names,
                    device_id, max_iters, seed, return_sweep, sweep_runner, spurious_on_device=False, bisil_sparse=False,
-                   shuffle_sparse=False):
+                   shuffle_sparse=False, sparse_on_device=False):
     """``apply_resnmtf`` with ``k_val = NULL`` (``R/main.r:269-334``); see ``apply_resnmtf``."""
     n_v = len(data)
+    on_dev = {"sparse_on_device": True} if sparse_on_device else {}
     _check_common(n_iters, num_repeats, n_stability, distance, sample_rate, stab_thres)
     _check_whole_number(k_min, "k_min")
     _check_whole_number(k_max, "k_max")
@@ -461,12 +484,12 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
             def run(k):
                 return scored(dev.factorise(k, n_iters, seed + k, max_iters=max_iters, tag=f"k={k}", return_lm=True,
                                             spurious_repeats=spurious_repeats, spurious_seed=seed + k,
-                                            shuffle_sparse=shuffle_sparse))
+                                            shuffle_sparse=shuffle_sparse, **on_dev))
 
             initial = [scored(r) for r in batched.k_sweep_on_device(dev, k_min, k_max, n_iters, seed,       # main.r:279-290
                                                                     max_iters=max_iters, return_lm=True,
                                                                     spurious_repeats=spurious_repeats,
-                                                                    shuffle_sparse=shuffle_sparse)]
+                                                                    shuffle_sparse=shuffle_sparse, **on_dev)]
         else:
             run, initial = sweep_runner, None
         ks, scores, results, pick = _sweep(run, k_min, k_max, cap, initial)
@@ -479,7 +502,7 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
                                   no_clusts, distance, sample_rate, n_stability, stab_thres, remove_unstable,
                                   row_names=p.row_names, col_names=p.col_names, device_id=device_id, seed=seed,
                                   max_iters=max_iters, spurious_on_device=spurious_on_device,
-                                  shuffle_sparse=shuffle_sparse)
+                                  shuffle_sparse=shuffle_sparse, **on_dev)
     if return_sweep:
         results = dict(results)
         results["k_sweep"] = {"k": ks, "bisil": scores}

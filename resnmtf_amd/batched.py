@@ -12,6 +12,14 @@ Stability selection is scored here too: ``stability_relevance_on_device`` runs t
 and reduces each sub-sample's factorisation to its relevance values on the device (``resnmtf_relevance``).  What is
 NOT here: the other scores computed from the factorisations -- the bisilhouette (``bisil.py``, scored on
 ``DeviceData.base`` by the k sweep of ``api.apply_resnmtf``) and the JSD scores (``spurious.py``).
+
+Sparse views (``scipy.sparse``) stay sparse on the device.  Their copies (k sweep) and sub-samples (stability repeats,
+the trimming probes included) are gathered on the host and uploaded, unless the keyword-only opt-in
+``sparse_on_device=True`` is passed down (``DeviceData.child`` / ``factorise`` / ``stability_repeat``,
+``k_sweep_on_device``, ``stability_relevance_on_device``): then they are made on the device from ``DeviceData.base``
+(``resnmtf_copy_view_sparse``, ``resnmtf_subsample_count_sparse`` + ``resnmtf_subsample_view_sparse``) and the results
+are those of the host route, except that a sub-sample's ``data_norms`` is summed from the f32 values the device holds
+(DESIGN.md section 10 "Device copies and sub-samples").
 """
 from __future__ import annotations
 
@@ -317,11 +325,15 @@ class DeviceData:
     def close(self):
         self.base.close()
 
-    def _trim_samples(self, samples, max_rounds: int = 20):
+    def _trim_samples(self, samples, max_rounds: int = 20, *, sparse_on_device: bool = False, counts: Optional[dict] = None):
         """``sample_view`` / ``stability_repeat`` (``R/stability_analysis.r:165-190``, ``:233-240``): all-zero rows and
         columns of a sub-sample are dropped -- from every earlier view that shares the draw (equal extent along that
         axis) -- and the sub-samples gathered again, until none is left.  The emptiness test runs on the device
-        (``resnmtf_view_empty_lines``), on probes that hold only the data.  Returns the trimmed draws or ``None``."""
+        (``resnmtf_view_empty_lines``), on probes that hold only the data; a sparse view's sub-sample is gathered on the
+        host instead, or with ``sparse_on_device`` (opt-in) probed like a dense one: the count of its stored entries
+        (``Engine.subsample_count_sparse``), a sparse probe of that capacity, ``subsample_view_sparse_from``.  Returns the
+        trimmed draws or ``None``.  ``counts``: a dict of the caller's that receives, per sparse view probed on the
+        device, ``(rows, cols, stored entries)`` of its last probe (``child`` sizes its engine from them)."""
         n_v = len(self.data_shapes)
         rows = [np.asarray(r).copy() for r in samples[0]]; cols = [np.asarray(c).copy() for c in samples[1]]
         for _ in range(max_rounds):
@@ -329,7 +341,14 @@ class DeviceData:
             for i in range(n_v):
                 if len(rows[i]) < 2 or len(cols[i]) < 2:
                     return None
-                if self.sp[i] is not None:          # sparse view: the sub-sample is gathered on the host
+                if self.sp[i] is not None and sparse_on_device:
+                    count = self.base.subsample_count_sparse(i, rows[i], cols[i])
+                    if counts is not None:
+                        counts[i] = (rows[i], cols[i], count)
+                    with Engine([len(rows[i])], [len(cols[i])], [2], device_id=self.device_id, nnz=[count]) as probe:
+                        probe.subsample_view_sparse_from(0, self.base, i, rows[i], cols[i])
+                        er, ec = probe.empty_lines(0)
+                elif self.sp[i] is not None:        # sparse view: the sub-sample is gathered on the host
                     _, er, ec = sparse.subsample(self.sp[i], rows[i], cols[i])
                 else:
                     with Engine([len(rows[i])], [len(cols[i])], [2], device_id=self.device_id) as probe:
@@ -349,8 +368,18 @@ class DeviceData:
                 return rows, cols
         return None
 
+    def _subsample_count(self, v: int, rows, cols, counts: dict) -> int:
+        """The stored entries of the sub-sample of sparse view ``v``: the count ``_trim_samples`` left in ``counts`` for
+        its last probe when that probe had these lists (a view trimmed through a later one is counted again), else a
+        count."""
+        seen = counts.get(v)
+        if seen is not None and np.array_equal(seen[0], rows) and np.array_equal(seen[1], cols):
+            return seen[2]
+        return self.base.subsample_count_sparse(v, rows, cols)
+
     @contextlib.contextmanager
-    def child(self, k: int, seed: int = 0, shuffle_seed: Optional[int] = None, samples=None, *, shuffle_sparse: bool = False):
+    def child(self, k: int, seed: int = 0, shuffle_seed: Optional[int] = None, samples=None, *, shuffle_sparse: bool = False,
+              sparse_on_device: bool = False):
         """An engine with k biclusters per view, loaded from ``self.base`` and closed on exit: the views copied -- or
         shuffled as ``obtain_shuffled_f`` does (``shuffle_seed``: no restrictions, uncoupled), or sub-sampled as
         ``stability_repeat`` does (``samples = (row_samples, col_samples)``: trimmed first, ``_trim_samples``; not
@@ -358,11 +387,16 @@ class DeviceData:
         ``Child(eng, row_names, col_names, samples, host_views)``: the names in use, the trimmed samples, what was uploaded
         of a sparse view -- or ``None`` when the trimming fails (``R/stability_analysis.r:223-226``).  ``shuffle_sparse``
         (opt-in): with ``shuffle_seed`` the sparse views are shuffled on the device as sparse views
-        (``resnmtf_shuffle_view_sparse``); without it they are refused."""
+        (``resnmtf_shuffle_view_sparse``); without it they are refused.  ``sparse_on_device`` (opt-in): the sparse views
+        are copied (``resnmtf_copy_view_sparse``) or sub-sampled (``resnmtf_subsample_view_sparse``, the trimming
+        included) from ``self.base`` on the device instead of gathered on the host and uploaded; the new engine's view
+        is sized from ``base.view_storage`` or from the sub-sample's count, and ``host_views[v]`` is ``None`` for it
+        (``Engine.get_view_sparse`` reads the same f32-rounded matrix).  Shuffles are not affected."""
         n_v = len(self.data_shapes)
         shapes, rn, cn = self.data_shapes, self.rn, self.cn
+        counts = {}
         if samples is not None:
-            samples = self._trim_samples(samples)
+            samples = self._trim_samples(samples, sparse_on_device=sparse_on_device, counts=counts)
             if samples is None:
                 yield None
                 return
@@ -372,18 +406,24 @@ class DeviceData:
         if shuffle_seed is not None and any(c is not None for c in self.sp) and not shuffle_sparse:
             raise NotImplementedError("device shuffles of sparse views are not supported")
         # sparse views: the whole view or its sub-sample, gathered on the host
-        host_views = [c if c is None or samples is None else sparse.subsample(c, samples[0][v], samples[1][v])[0]
+        on_device = [sparse_on_device and shuffle_seed is None and c is not None for c in self.sp]
+        host_views = [None if c is None or on_device[v] else
+                      (c if samples is None else sparse.subsample(c, samples[0][v], samples[1][v])[0])
                       for v, c in enumerate(self.sp)]
-        with Engine([s[0] for s in shapes], [s[1] for s in shapes], [k] * n_v, device_id=self.device_id,
-                    nnz=[None if hv is None else hv.nnz for hv in host_views]) as eng:
+        nnz = [None if hv is None else hv.nnz for hv in host_views]
+        for v in range(n_v):
+            if on_device[v]:
+                nnz[v] = self.base.view_storage(v)[1] if samples is None else self._subsample_count(v, samples[0][v], samples[1][v], counts)
+        more = {"sparse_on_device": True} if any(on_device) else {}      # (off: the calls are exactly the earlier ones)
+        with Engine([s[0] for s in shapes], [s[1] for s in shapes], [k] * n_v, device_id=self.device_id, nnz=nnz) as eng:
             load_child(eng, self.base, seed, shuffle_seed=shuffle_seed, samples=samples, host_views=host_views,
-                       coupling=(self.phi, self.xi, self.psi, rn, cn), shuffle_sparse=shuffle_sparse)
+                       coupling=(self.phi, self.xi, self.psi, rn, cn), shuffle_sparse=shuffle_sparse, **more)
             yield Child(eng, rn, cn, samples, host_views)
 
     def factorise(self, k: int, n_iters: Optional[int] = None, seed: int = 0, shuffle_seed: Optional[int] = None,
                   max_iters: int = 100000, tag: str = "", samples=None, return_init: bool = False,
                   return_data: bool = False, return_lm: bool = False, spurious_repeats: int = 0,
-                  spurious_seed: int = 0, *, shuffle_sparse: bool = False) -> dict:
+                  spurious_seed: int = 0, *, shuffle_sparse: bool = False, sparse_on_device: bool = False) -> dict:
         """One factorisation with k biclusters per view of the views copied, shuffled (``shuffle_seed``) or sub-sampled
         (``samples``) on the device (``child``): device SVD init, loop, finalise.  With ``samples`` whose trimming
         fails: ``{"stability_performed": False, "tag"}``.
@@ -394,18 +434,21 @@ class DeviceData:
         this factorisation's own device copy (``spurious.check_on_device`` with ``spurious_seed``) as
         ``"spurious_check"`` (the caller removes).  ``shuffle_sparse`` (opt-in): sparse views are shuffled as sparse
         views, by ``shuffle_seed`` and by the spurious check alike; ``return_data`` of a shuffled sparse view stays
-        refused (the host holds no copy of the shuffle: ``Engine.get_view_sparse`` reads it without densifying)."""
+        refused (the host holds no copy of the shuffle: ``Engine.get_view_sparse`` reads it without densifying).
+        ``sparse_on_device`` (opt-in): sparse views are copied / sub-sampled on the device (``child``); ``return_data``
+        then reads them back (``Engine.get_view_sparse``: the same f32-rounded matrix)."""
         n_v = len(self.data_shapes)
         if return_data and shuffle_seed is not None and any(c is not None for c in self.sp):
             raise NotImplementedError("return_data of a shuffled sparse view is not supported (it would densify the shuffle)")
-        with self.child(k, seed, shuffle_seed, samples, shuffle_sparse=shuffle_sparse) as ch:
+        with self.child(k, seed, shuffle_seed, samples, shuffle_sparse=shuffle_sparse, sparse_on_device=sparse_on_device) as ch:
             if ch is None:
                 return {"stability_performed": False, "tag": tag}
             eng = ch.eng
             init_state = [eng.get_factors(v) for v in range(n_v)] if return_init else None
             # (sparse views: the host copy rounded to f32, as the device holds the values)
             data_used = ([ch.host_views[v].toarray().astype(np.float32).astype(np.float64) if ch.host_views[v] is not None
-                          else eng.get_view(v) for v in range(n_v)] if return_data else None)
+                          else (eng.get_view_sparse(v).toarray() if self.sp[v] is not None else eng.get_view(v))
+                          for v in range(n_v)] if return_data else None)
             errs = eng.run(n_iters=n_iters, tol=1.0e-6, max_iters=max_iters)
             check = (spurious.check_on_device(eng, spurious_repeats, spurious_seed, max_iters=max_iters,
                                               device_id=self.device_id, shuffle_sparse=shuffle_sparse)
@@ -421,7 +464,7 @@ class DeviceData:
 
     def stability_repeat(self, k: int, n_iters: Optional[int], seed: int, samples, max_iters: int = 100000, tag: str = "",
                          keep_clusters: bool = False, spurious_repeats: int = 0, spurious_seed: int = 0, *,
-                         shuffle_sparse: bool = False) -> dict:
+                         shuffle_sparse: bool = False, sparse_on_device: bool = False) -> dict:
         """One repeat of ``stability_check`` (``R/stability_analysis.r:215-278``): the sub-sample ``samples`` factorised
         (``child``) and, instead of finalise, its clusters scored against the reference clusters set on ``self.base``
         (``resnmtf_relevance``, ``:268-276``) -- the result holds the n_views x k ``"relevance"`` matrix and no factors,
@@ -430,9 +473,11 @@ class DeviceData:
         columns flagged against R shuffles of the sub-sample (``spurious.check_on_device`` with ``spurious_seed``) are
         removed before the scoring (``resnmtf_relevance_masked``, ``:254-276``) and the kept clusters are the cleaned
         ones.  ``shuffle_sparse`` (opt-in): the shuffles of a sparse view are drawn from the repeat's own sparse
-        sub-sample handle (gathered on the host as before) and re-normalised, as for dense views."""
+        sub-sample handle (gathered on the host as before) and re-normalised, as for dense views.  ``sparse_on_device``
+        (opt-in): the sparse sub-sample is probed, trimmed and gathered on the device (``child``); the shuffles keep
+        drawing from the repeat's own handle."""
         n_v = len(self.data_shapes)
-        with self.child(k, seed, samples=samples) as ch:
+        with self.child(k, seed, samples=samples, sparse_on_device=sparse_on_device) as ch:
             if ch is None:
                 return {"stability_performed": False, "tag": tag}
             eng, (rows, cols) = ch.eng, ch.samples
@@ -458,14 +503,17 @@ class DeviceData:
 
 def k_sweep_on_device(dev: DeviceData, k_min: int = 3, k_max: int = 8, n_iters=None, seed: int = 0, group=None,
                       max_iters: int = 100000, return_lm: bool = False, spurious_repeats: int = 0, *,
-                      shuffle_sparse: bool = False) -> List[dict]:
+                      shuffle_sparse: bool = False, sparse_on_device: bool = False) -> List[dict]:
     """The factorisations of the k sweep (``R/main.r:279-290``) from one upload; sharded round-robin over
     the ranks of an initialised process group (every rank holds its own ``DeviceData``).  ``spurious_repeats``: each
-    k's result carries its ``"spurious_check"`` (``DeviceData.factorise``, spurious seed ``seed + k``)."""
+    k's result carries its ``"spurious_check"`` (``DeviceData.factorise``, spurious seed ``seed + k``).
+    ``sparse_on_device`` (opt-in): every k copies the sparse views from ``dev.base`` on the device
+    (``resnmtf_copy_view_sparse``) instead of uploading the host CSC again."""
+    more = {"sparse_on_device": True} if sparse_on_device else {}
     ks = list(range(k_min, k_max + 1))
     return run_jobs(ks, group=group, runner=lambda k: dev.factorise(k, n_iters, seed + k, max_iters=max_iters, tag=f"k={k}",
                                                                     return_lm=return_lm, spurious_repeats=spurious_repeats,
-                                                                    spurious_seed=seed + k, shuffle_sparse=shuffle_sparse))
+                                                                    spurious_seed=seed + k, shuffle_sparse=shuffle_sparse, **more))
 
 
 def shuffles_on_device(dev: DeviceData, n_clusts: int, num_repeats: int = 5, n_iters=None, seed: int = 0, group=None,
@@ -479,15 +527,17 @@ def shuffles_on_device(dev: DeviceData, n_clusts: int, num_repeats: int = 5, n_i
 
 
 def stability_on_device(dev: DeviceData, k: int, n_stability: int = 5, sample_rate: float = 0.9, n_iters=None, seed: int = 0,
-                        group=None) -> List[dict]:
+                        group=None, *, sparse_on_device: bool = False) -> List[dict]:
     """The factorisations of ``stability_check`` (``R/stability_analysis.r:305-323``): the draws follow
     ``subsample_views`` (shared draws for equal extents), the sub-samples are gathered on the device; all-zero rows /
     columns of a sub-sample -- the pre-processed data are non-negative, not positive: ``make_non_neg`` leaves a zero
     at every shifted column's minimum and sparse inputs stay sparse -- are dropped as the reference does
-    (``DeviceData._trim_samples``); a repeat whose sampling fails returns ``stability_performed = False``."""
+    (``DeviceData._trim_samples``); a repeat whose sampling fails returns ``stability_performed = False``.
+    ``sparse_on_device`` (opt-in): sparse views are probed, trimmed and sub-sampled on the device (``DeviceData.child``)."""
+    more = {"sparse_on_device": True} if sparse_on_device else {}
     draws = stability_draws(dev.data_shapes, n_stability, sample_rate, seed)
     return run_jobs(list(range(n_stability)), group=group,
-                    runner=lambda r: dev.factorise(k, n_iters, seed + 2000 + r, samples=draws[r], tag=f"stability={r}"))
+                    runner=lambda r: dev.factorise(k, n_iters, seed + 2000 + r, samples=draws[r], tag=f"stability={r}", **more))
 
 
 def stability_draws(shapes, n_stability: int, sample_rate: float, seed: int = 0):
@@ -525,7 +575,7 @@ def stability_relevance_on_device(dev: Optional[DeviceData], results: dict, k: i
                                   sample_rate: float = 0.9, n_iters=None, seed: int = 0, group=None,
                                   max_iters: int = 100000, keep_clusters: bool = False,
                                   runner: Optional[Callable] = None, spurious_repeats: int = 0, *,
-                                  shuffle_sparse: bool = False) -> dict:
+                                  shuffle_sparse: bool = False, sparse_on_device: bool = False) -> dict:
     """The repeats of ``stability_check`` (``R/stability_analysis.r:302-334``) with their scoring on the device:
     ``results``' binary clusters are uploaded once onto ``dev.base`` (``resnmtf_set_reference_clusters``), repeat r
     factorises the sub-sample of ``stability_draws`` (trimmed as ``stability_on_device`` does) up to the end of the loop
@@ -537,8 +587,10 @@ def stability_relevance_on_device(dev: Optional[DeviceData], results: dict, k: i
     spurious biclusters before it is scored (``R/stability_analysis.r:254-266``), against R shuffles of its own
     sub-sample drawn with the spurious seed ``seed + 2000 + r`` -- the repeat's own factorisation seed, so that repeat r
     equals ``remove_spurious(sub_data, sub_result, R, seed=seed + 2000 + r)``; per repeat only the k-sized flags, scores
-    and the null scores cross to the host."""
+    and the null scores cross to the host.  ``sparse_on_device`` (opt-in): the repeats probe, trim and gather the sparse
+    views' sub-samples on the device (``DeviceData.stability_repeat``)."""
     if runner is None:
+        more = {"sparse_on_device": True} if sparse_on_device else {}
         n_v = len(dev.data_shapes)
         for v in range(n_v):
             dev.base.set_reference_clusters(v, results["row_clusters"][v], results["col_clusters"][v])
@@ -547,7 +599,7 @@ def stability_relevance_on_device(dev: Optional[DeviceData], results: dict, k: i
         def runner(r):
             return dev.stability_repeat(k, n_iters, seed + 2000 + r, draws[r], max_iters=max_iters, tag=f"stability={r}",
                                         keep_clusters=keep_clusters, spurious_repeats=spurious_repeats,
-                                        spurious_seed=seed + 2000 + r, shuffle_sparse=shuffle_sparse)
+                                        spurious_seed=seed + 2000 + r, shuffle_sparse=shuffle_sparse, **more)
     repeats = run_jobs(list(range(n_stability)), group=group, runner=runner)
     rel = mean_relevance(repeats, n_stability)
     return {"stability_performed": rel is not None, "relevance": rel, "repeats": repeats}

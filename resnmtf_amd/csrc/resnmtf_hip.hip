@@ -32,6 +32,7 @@
 #include "resnmtf_sparse.hip.inc"
 #include <rocprim/rocprim.hpp>
 #include "resnmtf_sparse_shuffle.hip.inc"
+#include "resnmtf_sparse_subsample.hip.inc"
 #include "resnmtf_jsd.hip.inc"
 #include "resnmtf_group.hip.inc"
 #include "resnmtf_bisil.hip.inc"
@@ -1724,7 +1725,7 @@ void plan_sparse(const std::vector<long long>& ptr, int lines, int groups, int n
 }
 int spmm_groups_host(int KP) { return KP <= 16 ? 16 : (KP <= 32 ? 8 : 4); }   // = spmm_groups (kernel side)
 
-// The tail every sparse upload shares (resnmtf_set_view_csc, resnmtf_shuffle_view_sparse): the work split of the two
+// The tail every sparse upload shares (resnmtf_set_view_csc, finish_sparse_build, resnmtf_copy_view_sparse): the work split of the two
 // passes planned from the host copies of the line pointers, the block lists (re)allocated and their upload enqueued on
 // the handle's stream (the caller synchronises while `pl` is alive), then -- commit_sparse_upload -- the view's state.
 struct SparsePlan {
@@ -1895,9 +1896,179 @@ int resnmtf_shuffle_view(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_
   return upload_view(dst, v, nullptr, normalise != 0, nullptr, &sh);
 }
 
+// ---- sparse views built on the device from (destination position, value) pairs: the shuffle and the sub-sample
+namespace {
+// The transient device memory of one such build: five 8-byte arrays of nnz (two key buffers, the fp64 values, two payload
+// buffers) + rocPRIM's histograms, the per-column squares and the line masks.  Freed with the object.
+struct SparseBuild {
+  unsigned long long* key[2] = {nullptr, nullptr};
+  long long* pay[3] = {nullptr, nullptr, nullptr};       // 8-byte payloads: the fp64 values (first sort), CSC positions (second)
+  double* sq = nullptr;
+  unsigned char* line_mask = nullptr;
+  void* tmp = nullptr;
+  hipError_t alloc(long long nnz, int n, int m) {
+    const size_t cnt = std::max<size_t>((size_t)nnz, 1);
+    hipError_t e = hipSuccess;
+    for (auto& p : key) if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p), cnt * sizeof(unsigned long long));
+    for (auto& p : pay) if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p), cnt * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sq), (size_t)m * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&line_mask), (size_t)n + m + 2 * sizeof(int) + 8);
+    return e;
+  }
+  ~SparseBuild() {
+    for (auto p : key) (void)hipFree(p);
+    for (auto p : pay) (void)hipFree(p);
+    (void)hipFree(sq); (void)hipFree(line_mask); (void)hipFree(tmp);
+  }
+  SparseBuild() = default;
+  SparseBuild(const SparseBuild&) = delete;
+  SparseBuild& operator=(const SparseBuild&) = delete;
+};
+
+// The tail resnmtf_shuffle_view_sparse and resnmtf_subsample_view_sparse share.  On entry sb.key[0][0 .. nnz) holds the
+// column-major destination position c' n + r' of every entry (distinct, any order) and sb.pay[0] its value as fp64, both
+// enqueued on dst's stream; `e` is the status so far.  The entries sorted by position ARE the CSC (the keys are distinct,
+// so the sorted order is unique and every correct sort gives the same bits); sorted by r' m + c' they are the CSR; then
+// the masks of the lines without an entry > 0, the values (normalised or as they are), data_norms, the plan of the
+// passes and the view's state.  nnz = 0: zero pointers, every line empty, nothing of size zero launched.
+int finish_sparse_build(resnmtf_handle* dst, ViewState& a, SparseBuild& sb, long long nnz, int normalise, hipError_t e, const char* what) {
+  const int n = a.n, m = a.m;
+  hipStream_t st = dst->stream;
+  std::vector<long long> cp((size_t)m + 1, 0), rp((size_t)n + 1, 0);
+  std::vector<int> line_counts(2, 0);
+  SparsePlan pl;
+  a.empty_rows = a.empty_cols = 0; a.empty_mask.assign((size_t)n + m, 1);
+  const double* v64 = reinterpret_cast<const double*>(sb.pay[0]);
+  if (e == hipSuccess && nnz == 0) {          // every line empty: zero pointers, nothing of size zero launched
+    e = hipMemsetAsync(a.side[SIDE_G].sp_ptr, 0, ((size_t)m + 1) * sizeof(long long), st);
+    if (e == hipSuccess) e = hipMemsetAsync(a.side[SIDE_F].sp_ptr, 0, ((size_t)n + 1) * sizeof(long long), st);
+    line_counts[0] = n; line_counts[1] = m;
+  }
+  if (e == hipSuccess && nnz > 0) {
+    const unsigned grid = (unsigned)((nnz + 255) / 256);
+    const unsigned long long count = (unsigned long long)n * m;
+    unsigned int end_bit = 1;                           // the bits of n m: every key is < count
+    while (end_bit < 64 && ((count - 1) >> end_bit) != 0) ++end_bit;
+    // ---- the CSC: the entries sorted by destination position
+    rocprim::double_buffer<unsigned long long> kb(sb.key[0], sb.key[1]);
+    rocprim::double_buffer<double> vb(reinterpret_cast<double*>(sb.pay[0]), reinterpret_cast<double*>(sb.pay[1]));
+    size_t tmp_bytes = 0, tmp_bytes2 = 0;
+    e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, kb, vb, (size_t)nnz, 0u, end_bit, st);
+    rocprim::double_buffer<unsigned long long> kb2(sb.key[0], sb.key[1]);
+    rocprim::double_buffer<long long> pb(sb.pay[1], sb.pay[2]);
+    if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, tmp_bytes2, kb2, pb, (size_t)nnz, 0u, end_bit, st);
+    tmp_bytes = std::max<size_t>(std::max(tmp_bytes, tmp_bytes2), 8);
+    if (e == hipSuccess) e = hipMalloc(&sb.tmp, tmp_bytes);
+    if (e == hipSuccess) e = rocprim::radix_sort_pairs(sb.tmp, tmp_bytes, kb, vb, (size_t)nnz, 0u, end_bit, st);
+    if (e == hipSuccess) {
+      v64 = vb.current();
+      hipLaunchKernelGGL(sorted_lines_kernel, dim3(grid), dim3(256), 0, st, kb.current(), nnz, (unsigned long long)n, m, a.side[SIDE_G].sp_ptr, a.side[SIDE_G].sp_idx);
+      // ---- the CSR: the CSC positions sorted by r' m + c' (the values stay where the first sort left them)
+      kb2 = rocprim::double_buffer<unsigned long long>(kb.alternate(), kb.current());
+      pb = rocprim::double_buffer<long long>(reinterpret_cast<long long*>(vb.alternate()), sb.pay[2]);
+      hipLaunchKernelGGL(sparse_shuffle_csr_keys_kernel, dim3(grid), dim3(256), 0, st, kb.current(), nnz, n, m, kb2.current(), pb.current());
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = rocprim::radix_sort_pairs(sb.tmp, tmp_bytes, kb2, pb, (size_t)nnz, 0u, end_bit, st);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(sorted_lines_kernel, dim3(grid), dim3(256), 0, st, kb2.current(), nnz, (unsigned long long)m, n, a.side[SIDE_F].sp_ptr, a.side[SIDE_F].sp_idx);
+      int* counts = reinterpret_cast<int*>(sb.line_mask + (((size_t)n + m + 7) / 8) * 8);
+      e = hipMemsetAsync(counts, 0, 2 * sizeof(int), st);
+      hipLaunchKernelGGL(sparse_empty_lines_kernel, dim3(ceil_div(n + m, 256)), dim3(256), 0, st, a.side[SIDE_G].sp_ptr, a.side[SIDE_F].sp_ptr, pb.current(), v64, n, m,
+                         sb.line_mask, counts);
+      if (e == hipSuccess) e = hipGetLastError();
+      if (e == hipSuccess) e = hipMemcpyAsync(a.empty_mask.data(), sb.line_mask, (size_t)n + m, hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipMemcpyAsync(line_counts.data(), counts, 2 * sizeof(int), hipMemcpyDeviceToHost, st);
+    }
+    // ---- values: matrix_normalisation (fp64, ascending entry order) or the copy, data_norms, the CSR values
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(csc_normalise_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, a.side[SIDE_G].sp_ptr, v64, m, normalise ? 1 : 0, a.side[SIDE_G].sp_val, sb.sq);
+      hipLaunchKernelGGL(csr_gather_kernel, dim3(grid), dim3(256), 0, st, pb.current(), a.side[SIDE_G].sp_val, nnz, a.side[SIDE_F].sp_val);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(cp.data(), a.side[SIDE_G].sp_ptr, cp.size() * sizeof(long long), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(rp.data(), a.side[SIDE_F].sp_ptr, rp.size() * sizeof(long long), hipMemcpyDeviceToHost, st);
+  } else if (e == hipSuccess) {
+    hipLaunchKernelGGL(csc_normalise_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, a.side[SIDE_G].sp_ptr, v64, m, 0, a.side[SIDE_G].sp_val, sb.sq);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, st, sb.sq, m, a.xnorm2);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);             // the line pointers are on the host: plan the passes
+  if (e == hipSuccess) e = upload_sparse_plan(dst, a, rp, cp, pl);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) { a.empty_mask.clear(); return dst->fail_hip(what, e); }
+  a.empty_rows = line_counts[0]; a.empty_cols = line_counts[1];
+  commit_sparse_upload(dst, a, pl, nnz);
+  return RESNMTF_OK;
+}
+
+// The index lists of a sub-sample, checked on the host: in range and free of repeats (the reference samples without
+// replacement, and a repeated row has no inverse map).  `h` takes the refusal's text.
+int check_sample_lists(resnmtf_handle* h, const char* what, const ViewState& b, int n_dst, const int* rows, int m_dst, const int* cols) {
+  const std::string w = std::string(what) + ": ";
+  std::vector<unsigned char> seen((size_t)std::max(b.n, b.m), 0);
+  for (int i = 0; i < n_dst; ++i) {
+    if (rows[i] < 0 || rows[i] >= b.n) return h->fail(RESNMTF_ERR_INVALID, w + "row index out of range");
+    if (seen[(size_t)rows[i]])
+      return h->fail(RESNMTF_ERR_INVALID, w + "row index " + std::to_string(rows[i]) + " occurs twice (sub-samples are drawn without replacement)");
+    seen[(size_t)rows[i]] = 1;
+  }
+  std::fill(seen.begin(), seen.end(), 0);
+  for (int j = 0; j < m_dst; ++j) {
+    if (cols[j] < 0 || cols[j] >= b.m) return h->fail(RESNMTF_ERR_INVALID, w + "column index out of range");
+    if (seen[(size_t)cols[j]])
+      return h->fail(RESNMTF_ERR_INVALID, w + "column index " + std::to_string(cols[j]) + " occurs twice (sub-samples are drawn without replacement)");
+    seen[(size_t)cols[j]] = 1;
+  }
+  return RESNMTF_OK;
+}
+
+// The counting half of a sub-sample of source view b (resnmtf_sparse_subsample.hip.inc steps 1 and 2) on stream st: the
+// lists and the inverse row map on the device, the kept entries per destination column and their exclusive scan cp, the
+// total back on the host.  Transient: 4 (n' + m' + n_src) + 16 (m' + 1) bytes + rocPRIM's scan storage.
+struct SubsampleMap {
+  int* idx = nullptr;            // rows [n_dst], then cols [m_dst]
+  int* inv_row = nullptr;        // [n_src]
+  long long* counts = nullptr;   // [m_dst + 1]
+  long long* cp = nullptr;       // [m_dst + 1]
+  void* tmp = nullptr;
+  ~SubsampleMap() { (void)hipFree(idx); (void)hipFree(inv_row); (void)hipFree(counts); (void)hipFree(cp); (void)hipFree(tmp); }
+  SubsampleMap() = default;
+  SubsampleMap(const SubsampleMap&) = delete;
+  SubsampleMap& operator=(const SubsampleMap&) = delete;
+};
+hipError_t subsample_count(hipStream_t st, const ViewState& b, int n_dst, const int* rows, int m_dst, const int* cols, SubsampleMap& sm,
+                           long long* total) {
+  *total = 0;
+  if (b.nnz == 0) return hipSuccess;                      // nothing stored, nothing kept: no launch
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&sm.idx), ((size_t)n_dst + m_dst) * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sm.inv_row), (size_t)b.n * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sm.counts), ((size_t)m_dst + 1) * sizeof(long long));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sm.cp), ((size_t)m_dst + 1) * sizeof(long long));
+  if (e == hipSuccess) e = hipMemcpyAsync(sm.idx, rows, (size_t)n_dst * sizeof(int), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(sm.idx + n_dst, cols, (size_t)m_dst * sizeof(int), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(sm.inv_row, 0xFF, (size_t)b.n * sizeof(int), st);       // every row -1: not kept
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(sparse_subsample_inverse_kernel, dim3(ceil_div(n_dst, 256)), dim3(256), 0, st, sm.idx, n_dst, sm.inv_row);
+  hipLaunchKernelGGL(sparse_subsample_count_kernel, dim3(ceil_div(m_dst + 1, 4)), dim3(256), 0, st, b.side[SIDE_G].sp_ptr, b.side[SIDE_G].sp_idx,
+                     sm.idx + n_dst, m_dst, sm.inv_row, sm.counts);
+  e = hipGetLastError();
+  size_t tmp_bytes = 0;
+  if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, tmp_bytes, sm.counts, sm.cp, 0LL, (size_t)m_dst + 1, rocprim::plus<long long>(), st);
+  if (e == hipSuccess) e = hipMalloc(&sm.tmp, std::max<size_t>(tmp_bytes, 8));
+  if (e == hipSuccess) e = rocprim::exclusive_scan(sm.tmp, tmp_bytes, sm.counts, sm.cp, 0LL, (size_t)m_dst + 1, rocprim::plus<long long>(), st);
+  if (e == hipSuccess) e = hipMemcpyAsync(total, sm.cp + m_dst, sizeof(long long), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  return e;
+}
+}  // namespace
+
 // shuffle_view (R/obtain_bicl.r:11-22) of a sparse view into a sparse view: the dense path's draw (feistel_perm, same seed)
 // of the densified source, built from the stored entries alone (resnmtf_sparse_shuffle.hip.inc).  Transient device memory:
-// five 8-byte arrays of nnz (two key buffers, the fp64 values, two payload buffers) + rocPRIM's histograms.
+// SparseBuild's 40 bytes per stored entry.
 int resnmtf_shuffle_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src, unsigned long long seed, int normalise) {
   if (int rc = check_view(dst, v)) return rc;
   if (!src || v_src < 0 || v_src >= src->V) return dst->fail(RESNMTF_ERR_INVALID, "bad source handle / view");
@@ -1918,92 +2089,126 @@ int resnmtf_shuffle_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src,
   HIP_TRY(dst, hipSetDevice(dst->opt.device_id));
   HIP_TRY(dst, hipStreamSynchronize(src->stream));
   if (int rc = sync_both(dst)) return rc;
-  hipStream_t st = dst->stream;
-  const size_t cnt = std::max<size_t>((size_t)nnz, 1);
-  unsigned long long* key[2] = {nullptr, nullptr};
-  long long* pay[3] = {nullptr, nullptr, nullptr};       // 8-byte payloads: the fp64 values (first sort), CSC positions (second)
-  double* sq = nullptr;
-  unsigned char* line_mask = nullptr;
-  void* tmp = nullptr;
-  std::vector<long long> cp((size_t)m + 1, 0), rp((size_t)n + 1, 0);
-  std::vector<int> line_counts(2, 0);
-  SparsePlan pl;
-  a.empty_rows = a.empty_cols = 0; a.empty_mask.assign((size_t)n + m, 1);
-  hipError_t e = hipSuccess;
-  auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
-  for (auto& p : key) alloc(reinterpret_cast<void**>(&p), cnt * sizeof(unsigned long long));
-  for (auto& p : pay) alloc(reinterpret_cast<void**>(&p), cnt * sizeof(long long));
-  alloc(reinterpret_cast<void**>(&sq), (size_t)m * sizeof(double));
-  alloc(reinterpret_cast<void**>(&line_mask), (size_t)n + m + 2 * sizeof(int) + 8);
-  const double* v64 = reinterpret_cast<const double*>(pay[0]);
-  if (e == hipSuccess && nnz == 0) {          // every line empty: zero pointers, nothing of size zero launched
-    e = hipMemsetAsync(a.side[SIDE_G].sp_ptr, 0, ((size_t)m + 1) * sizeof(long long), st);
-    if (e == hipSuccess) e = hipMemsetAsync(a.side[SIDE_F].sp_ptr, 0, ((size_t)n + 1) * sizeof(long long), st);
-    line_counts[0] = n; line_counts[1] = m;
-  }
+  SparseBuild sb;
+  hipError_t e = sb.alloc(nnz, n, m);
   if (e == hipSuccess && nnz > 0) {
-    const unsigned grid = (unsigned)((nnz + 255) / 256);
-    const unsigned long long count = (unsigned long long)n * m;
-    unsigned int end_bit = 1;                           // the bits of n m: every key is < count
-    while (end_bit < 64 && ((count - 1) >> end_bit) != 0) ++end_bit;
-    hipLaunchKernelGGL(sparse_shuffle_keys_kernel, dim3(grid), dim3(256), 0, st, b.side[SIDE_G].sp_ptr, b.side[SIDE_G].sp_idx, b.side[SIDE_G].sp_val, nnz, n, m, seed, key[0],
-                       reinterpret_cast<double*>(pay[0]));
-    e = hipGetLastError();
-    // ---- the CSC of the shuffle: the entries sorted by destination position
-    rocprim::double_buffer<unsigned long long> kb(key[0], key[1]);
-    rocprim::double_buffer<double> vb(reinterpret_cast<double*>(pay[0]), reinterpret_cast<double*>(pay[1]));
-    size_t tmp_bytes = 0, tmp_bytes2 = 0;
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, kb, vb, (size_t)nnz, 0u, end_bit, st);
-    rocprim::double_buffer<unsigned long long> kb2(key[0], key[1]);
-    rocprim::double_buffer<long long> pb(pay[1], pay[2]);
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, tmp_bytes2, kb2, pb, (size_t)nnz, 0u, end_bit, st);
-    tmp_bytes = std::max<size_t>(std::max(tmp_bytes, tmp_bytes2), 8);
-    alloc(&tmp, tmp_bytes);
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kb, vb, (size_t)nnz, 0u, end_bit, st);
-    if (e == hipSuccess) {
-      v64 = vb.current();
-      hipLaunchKernelGGL(sorted_lines_kernel, dim3(grid), dim3(256), 0, st, kb.current(), nnz, (unsigned long long)n, m, a.side[SIDE_G].sp_ptr, a.side[SIDE_G].sp_idx);
-      // ---- the CSR: the CSC positions sorted by r' m + c' (the values stay where the first sort left them)
-      kb2 = rocprim::double_buffer<unsigned long long>(kb.alternate(), kb.current());
-      pb = rocprim::double_buffer<long long>(reinterpret_cast<long long*>(vb.alternate()), pay[2]);
-      hipLaunchKernelGGL(sparse_shuffle_csr_keys_kernel, dim3(grid), dim3(256), 0, st, kb.current(), nnz, n, m, kb2.current(), pb.current());
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kb2, pb, (size_t)nnz, 0u, end_bit, st);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(sorted_lines_kernel, dim3(grid), dim3(256), 0, st, kb2.current(), nnz, (unsigned long long)m, n, a.side[SIDE_F].sp_ptr, a.side[SIDE_F].sp_idx);
-      int* counts = reinterpret_cast<int*>(line_mask + (((size_t)n + m + 7) / 8) * 8);
-      e = hipMemsetAsync(counts, 0, 2 * sizeof(int), st);
-      hipLaunchKernelGGL(sparse_empty_lines_kernel, dim3(ceil_div(n + m, 256)), dim3(256), 0, st, a.side[SIDE_G].sp_ptr, a.side[SIDE_F].sp_ptr, pb.current(), v64, n, m,
-                         line_mask, counts);
-      if (e == hipSuccess) e = hipGetLastError();
-      if (e == hipSuccess) e = hipMemcpyAsync(a.empty_mask.data(), line_mask, (size_t)n + m, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(line_counts.data(), counts, 2 * sizeof(int), hipMemcpyDeviceToHost, st);
-    }
-    // ---- values: matrix_normalisation of the shuffle (fp64, ascending entry order) or the copy, data_norms, the CSR values
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(csc_normalise_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, a.side[SIDE_G].sp_ptr, v64, m, normalise ? 1 : 0, a.side[SIDE_G].sp_val, sq);
-      hipLaunchKernelGGL(csr_gather_kernel, dim3(grid), dim3(256), 0, st, pb.current(), a.side[SIDE_G].sp_val, nnz, a.side[SIDE_F].sp_val);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(cp.data(), a.side[SIDE_G].sp_ptr, cp.size() * sizeof(long long), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(rp.data(), a.side[SIDE_F].sp_ptr, rp.size() * sizeof(long long), hipMemcpyDeviceToHost, st);
-  } else if (e == hipSuccess) {
-    hipLaunchKernelGGL(csc_normalise_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, a.side[SIDE_G].sp_ptr, v64, m, 0, a.side[SIDE_G].sp_val, sq);
+    hipLaunchKernelGGL(sparse_shuffle_keys_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, dst->stream, b.side[SIDE_G].sp_ptr, b.side[SIDE_G].sp_idx,
+                       b.side[SIDE_G].sp_val, nnz, n, m, seed, sb.key[0], reinterpret_cast<double*>(sb.pay[0]));
     e = hipGetLastError();
   }
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, st, sq, m, a.xnorm2);
+  return finish_sparse_build(dst, a, sb, nnz, normalise, e, "shuffle_view_sparse");
+}
+
+// The refusals resnmtf_subsample_count_sparse and resnmtf_subsample_view_sparse share for their source: NULL, a dense
+// view, not owned, not uploaded.  `h` takes the message.
+static int check_sparse_source(resnmtf_handle* h, const resnmtf_handle* src, int v_src, const char* what, const char* dense_entry) {
+  const std::string w(what);
+  if (v_src < 0 || v_src >= src->V) return h->fail(RESNMTF_ERR_INVALID, w + ": bad source view");
+  const ViewState& b = src->views[v_src];
+  if (!b.sparse) return h->fail(RESNMTF_ERR_INVALID, w + ": the source view is dense (" + dense_entry + ")");
+  if (!b.owned) return h->fail(RESNMTF_ERR_STATE, w + ": the source view is not owned");
+  if (!b.has_x) return h->fail(RESNMTF_ERR_STATE, w + ": the source view has not been uploaded");
+  return RESNMTF_OK;
+}
+
+// The number of stored entries of X[rows, cols] of a sparse view (stored zeros count); nothing is built.
+int resnmtf_subsample_count_sparse(resnmtf_handle* src, int v_src, int n_rows, const int* rows, int n_cols, const int* cols, long long* nnz) {
+  if (!src) return RESNMTF_ERR_INVALID;
+  if (!rows || !cols || !nnz) return src->fail(RESNMTF_ERR_INVALID, "subsample_count_sparse: rows / cols / nnz is NULL");
+  if (n_rows < 0 || n_cols < 0) return src->fail(RESNMTF_ERR_INVALID, "subsample_count_sparse: negative index count");
+  if (int rc = check_sparse_source(src, src, v_src, "subsample_count_sparse", "resnmtf_subsample_view sub-samples dense views")) return rc;
+  const ViewState& b = src->views[v_src];
+  if (int rc = check_sample_lists(src, "subsample_count_sparse", b, n_rows, rows, n_cols, cols)) return rc;
+  *nnz = 0;
+  if (n_rows == 0 || n_cols == 0) return RESNMTF_OK;
+  HIP_TRY(src, hipSetDevice(src->opt.device_id));
+  if (int rc = sync_both(src)) return rc;
+  SubsampleMap sm;
+  const hipError_t e = subsample_count(src->stream, b, n_rows, rows, n_cols, cols, sm, nnz);
+  if (e != hipSuccess) return src->fail_hip("subsample_count_sparse", e);
+  return RESNMTF_OK;
+}
+
+// data[[i]][row_samples[[i]], col_samples[[i]]] (R/stability_analysis.r:124, :184, :232, :238) of a sparse view into a
+// sparse view: the values as stored (f32, not re-normalised: SURVEY B11), stored zeros kept.  The view is bit for bit
+// resnmtf_set_view_csc(pre_processed = 1) of the same sub-sample of the source's read-back.  Transient device memory:
+// SparseBuild's 40 bytes per kept entry + SubsampleMap.
+int resnmtf_subsample_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src, const int* rows, const int* cols) {
+  if (int rc = check_view(dst, v)) return rc;
+  if (!src) return dst->fail(RESNMTF_ERR_INVALID, "subsample_view_sparse: the source handle is NULL");
+  if (!rows || !cols) return dst->fail(RESNMTF_ERR_INVALID, "subsample_view_sparse: rows / cols are NULL");
+  ViewState& a = dst->views[v];
+  if (!a.sparse) return dst->fail(RESNMTF_ERR_INVALID, "subsample_view_sparse: the destination view is dense (resnmtf_subsample_view sub-samples dense views)");
+  if (int rc = check_sparse_source(dst, src, v_src, "subsample_view_sparse", "resnmtf_subsample_view sub-samples dense views")) return rc;
+  const ViewState& b = src->views[v_src];
+  if (!a.owned) return dst->fail(RESNMTF_ERR_STATE, "subsample_view_sparse: the destination view is not owned");
+  if (dst->opt.device_id != src->opt.device_id) return dst->fail(RESNMTF_ERR_INVALID, "subsample_view_sparse: handles live on different devices");
+  if (int rc = check_sample_lists(dst, "subsample_view_sparse", b, a.n, rows, a.m, cols)) return rc;
+  HIP_TRY(dst, hipSetDevice(dst->opt.device_id));
+  HIP_TRY(dst, hipStreamSynchronize(src->stream));
+  if (int rc = sync_both(dst)) return rc;
+  SubsampleMap sm;
+  long long nnz = 0;
+  hipError_t e = subsample_count(dst->stream, b, a.n, rows, a.m, cols, sm, &nnz);
+  if (e != hipSuccess) return dst->fail_hip("subsample_view_sparse", e);
+  if (nnz > a.nnz_cap)               // (the destination is still what it was)
+    return dst->fail(RESNMTF_ERR_INVALID, "subsample_view_sparse: the sub-sample holds " + std::to_string(nnz) +
+                     " stored entries, above the destination's nnz capacity " + std::to_string(a.nnz_cap));
+  dst->resume_ok = false;
+  SparseBuild sb;
+  e = sb.alloc(nnz, a.n, a.m);
+  if (e == hipSuccess && nnz > 0) {
+    hipLaunchKernelGGL(sparse_subsample_emit_kernel, dim3(ceil_div(a.m, 4)), dim3(256), 0, dst->stream, b.side[SIDE_G].sp_ptr, b.side[SIDE_G].sp_idx,
+                       b.side[SIDE_G].sp_val, sm.idx + a.n, a.n, a.m, sm.inv_row, sm.cp, sb.key[0], reinterpret_cast<double*>(sb.pay[0]));
     e = hipGetLastError();
   }
+  return finish_sparse_build(dst, a, sb, nnz, 0, e, "subsample_view_sparse");
+}
+
+// resnmtf_copy_view for sparse views: both pointer arrays, both index arrays, both value arrays and data_norms device to
+// device.  The block lists and nsplit depend on KP (spmm_groups_host), and k may differ between the handles (the k sweep
+// copies from a k = 2 base), so the 8 (n + m + 2) bytes of line pointers are read back and the passes planned again.
+int resnmtf_copy_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src) {
+  if (int rc = check_view(dst, v)) return rc;
+  if (!src) return dst->fail(RESNMTF_ERR_INVALID, "copy_view_sparse: the source handle is NULL");
+  ViewState& a = dst->views[v];
+  if (!a.sparse) return dst->fail(RESNMTF_ERR_INVALID, "copy_view_sparse: the destination view is dense (resnmtf_copy_view copies dense views)");
+  if (int rc = check_sparse_source(dst, src, v_src, "copy_view_sparse", "resnmtf_copy_view copies dense views")) return rc;
+  const ViewState& b = src->views[v_src];
+  if (!a.owned) return dst->fail(RESNMTF_ERR_STATE, "copy_view_sparse: the destination view is not owned");
+  if (a.n != b.n || a.m != b.m) return dst->fail(RESNMTF_ERR_INVALID, "copy_view_sparse: views differ in shape");
+  if (dst->opt.device_id != src->opt.device_id) return dst->fail(RESNMTF_ERR_INVALID, "copy_view_sparse: handles live on different devices");
+  if (b.nnz > a.nnz_cap)
+    return dst->fail(RESNMTF_ERR_INVALID, "copy_view_sparse: the source holds " + std::to_string(b.nnz) +
+                     " stored entries, above the destination's nnz capacity " + std::to_string(a.nnz_cap));
+  if (&a == &b) return RESNMTF_OK;
+  const int n = a.n, m = a.m;
+  const long long nnz = b.nnz;
+  dst->resume_ok = false;
+  HIP_TRY(dst, hipSetDevice(dst->opt.device_id));
+  HIP_TRY(dst, hipStreamSynchronize(src->stream));
+  if (int rc = sync_both(dst)) return rc;
+  hipStream_t st = dst->stream;
+  std::vector<long long> cp((size_t)m + 1, 0), rp((size_t)n + 1, 0);
+  SparsePlan pl;
+  hipError_t e = hipSuccess;
+  auto copy = [&](void* to, const void* from, size_t bytes) {
+    if (e == hipSuccess && bytes) e = hipMemcpyAsync(to, from, bytes, hipMemcpyDeviceToDevice, st);
+  };
+  copy(a.side[SIDE_G].sp_ptr, b.side[SIDE_G].sp_ptr, cp.size() * sizeof(long long));
+  copy(a.side[SIDE_F].sp_ptr, b.side[SIDE_F].sp_ptr, rp.size() * sizeof(long long));
+  copy(a.side[SIDE_G].sp_idx, b.side[SIDE_G].sp_idx, (size_t)nnz * sizeof(int));
+  copy(a.side[SIDE_F].sp_idx, b.side[SIDE_F].sp_idx, (size_t)nnz * sizeof(int));
+  copy(a.side[SIDE_G].sp_val, b.side[SIDE_G].sp_val, (size_t)nnz * sizeof(float));
+  copy(a.side[SIDE_F].sp_val, b.side[SIDE_F].sp_val, (size_t)nnz * sizeof(float));
+  copy(a.xnorm2, b.xnorm2, sizeof(double));
+  if (e == hipSuccess) e = hipMemcpyAsync(cp.data(), b.side[SIDE_G].sp_ptr, cp.size() * sizeof(long long), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(rp.data(), b.side[SIDE_F].sp_ptr, rp.size() * sizeof(long long), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);             // the line pointers are on the host: plan the passes
   if (e == hipSuccess) e = upload_sparse_plan(dst, a, rp, cp, pl);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  for (auto p : key) (void)hipFree(p);
-  for (auto p : pay) (void)hipFree(p);
-  (void)hipFree(sq); (void)hipFree(line_mask); (void)hipFree(tmp);
-  if (e != hipSuccess) { a.empty_mask.clear(); return dst->fail_hip("shuffle_view_sparse", e); }
-  a.empty_rows = line_counts[0]; a.empty_cols = line_counts[1];
+  if (e != hipSuccess) { a.has_x = false; return dst->fail_hip("copy_view_sparse", e); }   // (the arrays may be partly overwritten)
+  a.empty_rows = a.empty_cols = 0; a.empty_mask.clear();      // (as after resnmtf_set_view_csc: not device-drawn data)
   commit_sparse_upload(dst, a, pl, nnz);
   return RESNMTF_OK;
 }

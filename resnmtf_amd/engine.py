@@ -277,6 +277,35 @@ class Engine:
         seed, from the stored entries alone; the shuffle stays sparse."""
         self._check(self._lib.resnmtf_shuffle_view_sparse(self._h, v, other._h, v_src, int(seed), 1 if normalise else 0))
 
+    def subsample_count_sparse(self, v: int, rows, cols) -> int:
+        """The number of stored entries of ``X[rows, cols]`` of this engine's sparse view ``v``
+        (``resnmtf_subsample_count_sparse``): the ``nnz`` an engine needs to receive that sub-sample
+        (``subsample_view_sparse_from``).  Nothing is built."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32); cols = np.ascontiguousarray(cols, dtype=np.int32)
+        if rows.ndim != 1 or cols.ndim != 1:
+            raise ValueError("rows and cols must be vectors")
+        nnz = C.c_longlong(0)
+        # (never a NULL pointer for an empty list)
+        r = rows if rows.size else np.zeros(1, dtype=np.int32); c = cols if cols.size else np.zeros(1, dtype=np.int32)
+        self._check(self._lib.resnmtf_subsample_count_sparse(self._h, v, int(rows.size), _ip(r), int(cols.size), _ip(c),
+                                                             C.byref(nnz)))
+        return int(nnz.value)
+
+    def subsample_view_sparse_from(self, v: int, other: "Engine", v_src: int, rows, cols):
+        """The sub-sample ``X[rows, cols]`` of another engine's SPARSE view (``R/stability_analysis.r:230-249``) into
+        this engine's sparse view ``v`` (``resnmtf_subsample_view_sparse``), gathered on the device from the stored
+        entries; the view must have the shape ``(len(rows), len(cols))`` and room for ``other.subsample_count_sparse``
+        entries.  The lists come in any order, without repeats; the values are not re-normalised."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32); cols = np.ascontiguousarray(cols, dtype=np.int32)
+        if len(rows) != self.n_rows[v] or len(cols) != self.n_cols[v]:
+            raise ValueError("index counts must equal the view's shape")
+        self._check(self._lib.resnmtf_subsample_view_sparse(self._h, v, other._h, v_src, _ip(rows), _ip(cols)))
+
+    def copy_view_sparse_from(self, v: int, other: "Engine", v_src: int = 0):
+        """Device copy of a SPARSE view another engine (same GPU, same shape, any k) has uploaded
+        (``resnmtf_copy_view_sparse``); the passes are planned for this engine's k."""
+        self._check(self._lib.resnmtf_copy_view_sparse(self._h, v, other._h, v_src))
+
     def get_view_sparse(self, v: int):
         """The device CSC copy of sparse view ``v`` (``resnmtf_get_view_csc``; fp32 precision, explicit zeros kept) as a
         ``scipy.sparse.csc_matrix``.  A dense view is refused (``get_view``)."""

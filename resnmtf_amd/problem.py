@@ -94,14 +94,21 @@ def _draw_shuffle(eng, v: int, src, shuffle_seed: int, shuffle_sparse: bool = Fa
 
 
 def load_child(eng, src, seed: int, *, shuffle_seed: Optional[int] = None, samples=None, host_views=None, coupling=None,
-               shuffle_sparse: bool = False):
+               shuffle_sparse: bool = False, sparse_on_device: bool = False):
     """Fill ``eng`` from ``src``, an engine on the same device that holds the data: every view shuffled (with
     ``shuffle_seed``; sparse views only with ``shuffle_sparse``, ``_draw_shuffle``), sub-sampled (``samples = (row_samples, col_samples)``) or copied -- a sparse view is uploaded from
-    ``host_views[v]`` instead -- then the device SVD init with ``seed + v``; at last ``coupling`` = (phi, xi, psi,
+    ``host_views[v]`` instead, or with ``sparse_on_device`` (opt-in) sub-sampled / copied on the device as a sparse view
+    (``Engine.subsample_view_sparse_from`` / ``copy_view_sparse_from``; ``host_views`` is then not read for it) -- then the
+    device SVD init with ``seed + v``; at last ``coupling`` = (phi, xi, psi,
     row_names, col_names), or for shuffles none: no restrictions, uncoupled (``R/obtain_bicl.r:35-39``)."""
     for v in range(eng.n_views):
         if shuffle_seed is not None:
             _draw_shuffle(eng, v, src, shuffle_seed, shuffle_sparse)
+        elif sparse_on_device and src.sparse[v]:
+            if samples is not None:
+                eng.subsample_view_sparse_from(v, src, v, samples[0][v], samples[1][v])
+            else:
+                eng.copy_view_sparse_from(v, src, v)
         elif host_views is not None and host_views[v] is not None:
             eng.set_view_sparse(v, host_views[v], pre_processed=True)      # (sub-samples are not re-normalised)
         elif samples is not None:
