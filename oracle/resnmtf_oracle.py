@@ -357,7 +357,9 @@ def res_nmtf_inner(data, init_f, init_s, init_g, phi, xi, psi,
         return float(np.mean(calculate_error(data, cur_f, cur_s, cur_g, data_norms)))
 
     if n_iters is None:                                                            # main.r:50
-        err_diff, err_temp = 1.0, 0.0                                              # :53-54
+        # :53-54.  The reference's `err_diff <- 1` only enters the loop of its fixed 1e-6 (:55); with `tol` an argument the
+        # same start is "greater than any tol": the first sweep always runs and is the first one tested (against 0)
+        err_diff, err_temp = np.inf, 0.0
         while err_diff > tol:                                                      # :55
             mean_err = sweep()
             total_err.append(mean_err)                                             # :78

@@ -934,6 +934,8 @@ def res_nmtf_inner(data, row_indices=None, column_indices=None, init_f=None, ini
     n_v = len(init_f) if init_f is not None else 0
     if not n_v or init_s is None or init_g is None or len(init_s) != n_v or len(init_g) != n_v:
         raise ValueError("the view-sharded entry needs explicit initial factors of every view on every rank")
+    if n_iters is None and int(max_iters) < 1:
+        raise ValueError("max_iters must be at least 1 (the convergence loop runs one sweep before its first test)")
     data = list(data)
     if len(data) != n_v:
         raise ValueError("data must have one entry per view (None for views this rank does not own)")
@@ -975,11 +977,11 @@ def res_nmtf_inner(data, row_indices=None, column_indices=None, init_f=None, ini
             errs = drv.mean_errors()
         else:      # no replicated S chain to hold the stop test: one sweep, one look (R/main.r:55,77-80)
             drv.reserve(max_iters + 8)
-            prev = None
+            prev = 0.0                                                              # err_temp, main.r:54
             while drv.sweeps_done < max_iters:
                 drv.run(1)
                 errs = drv.mean_errors()
-                if prev is not None and not (abs(errs[-1] - prev) > tol):
+                if not (abs(errs[-1] - prev) > tol):                               # the first sweep is tested too (against 0)
                     break
                 prev = errs[-1]
         res = drv.gather_results(dst)

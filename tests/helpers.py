@@ -38,11 +38,11 @@ def rel_fro(a: np.ndarray, b: np.ndarray) -> float:
     return float(np.linalg.norm(a - b) / den) if den > 0 else float(np.linalg.norm(a - b))
 
 
-def run_oracle(prob, n_iters=None, max_iters=None):
+def run_oracle(prob, n_iters=None, max_iters=None, tol=1.0e-6):
     from oracle import resnmtf_oracle as O
     return O.res_nmtf_inner(prob.data, prob.init_f, prob.init_s, prob.init_g, prob.phi, prob.xi, prob.psi,
                             row_names=prob.row_names, col_names=prob.col_names, n_iters=n_iters,
-                            max_iters=max_iters)
+                            max_iters=max_iters, tol=tol)
 
 
 def run_hip(prob, n_iters=None, max_iters=100000, **engine_opts):

@@ -9,6 +9,7 @@ everything else in fp64."""
 import numpy as np
 import pytest
 
+import loop_ref
 from helpers import GOLDEN_NAMES, golden_problem, load_golden, rel_fro, run_hip, run_oracle
 from resnmtf_amd import synth
 
@@ -164,6 +165,7 @@ def test_convergence_mode_matches_oracle():
     res = run_hip(prob, n_iters=None, max_iters=3000)
     n_ref, n_hip = len(ref["All_Error"]), len(res["All_Error"])
     assert abs(n_ref - n_hip) <= 2, (n_ref, n_hip)      # the stop test sits on rounding
+    assert n_hip == loop_ref.stop_sweep(res["All_Error"], 1e-6)      # ... and is exact on the device's own trace
     m = min(n_ref, n_hip)
     np.testing.assert_allclose(res["All_Error"][:m], ref["All_Error"][:m], atol=TOL_ERR)
     assert abs(res["Error"] - ref["Error"]) < TOL_ERR

@@ -6,6 +6,7 @@ import pytest
 import scipy.sparse as sp
 
 import resnmtf_amd
+import loop_ref
 from helpers import load_golden, golden_problem, rel_fro, run_hip, run_oracle
 from resnmtf_amd import synth
 from resnmtf_amd.engine import Engine
@@ -106,6 +107,7 @@ def test_convergence_mode_matches_oracle():
     res = run_hip(sparse_problem(prob), n_iters=None, max_iters=3000)
     n_ref, n_hip = len(ref["All_Error"]), len(res["All_Error"])
     assert abs(n_ref - n_hip) <= 2, (n_ref, n_hip)
+    assert n_hip == loop_ref.stop_sweep(res["All_Error"], 1e-6)      # exact on the device's own trace
     m = min(n_ref, n_hip)
     np.testing.assert_allclose(res["All_Error"][:m], ref["All_Error"][:m], atol=2e-5)
 

@@ -645,6 +645,26 @@ def test_sharded_res_nmtf_inner_gloo_cpu(tmp_path, mode):
         assert np.array_equal(got[f"col_clusters{v}"], ref["col_clusters"][v])
 
 
+def test_sharded_fallback_tests_the_first_sweep_gloo_cpu(tmp_path):
+    """The sweep-by-sweep convergence loop starts from err_temp = 0 (R/main.r:54) and tests the first sweep like every other:
+    errors lie in [0, 1], so tol = 2 stops after one sweep, as the oracle and the device loop do."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import dist_worker
+    import loop_ref
+    got = launch("cpu_api_conv", tmp_path, world=2, sweeps=400, extra=("--tol", 2.0))
+    ref = _oracle_inner(dist_worker.build_problem(), tol=2.0, max_iters=400)
+    assert len(got["all_error"]) == len(ref["All_Error"]) == loop_ref.stop_sweep(ref["All_Error"], 2.0) == 1
+    np.testing.assert_allclose(got["all_error"], ref["All_Error"], rtol=1e-10, atol=1e-12)
+
+
+def test_sharded_res_nmtf_inner_refuses_max_iters_below_one():
+    from resnmtf_amd import sharded
+    f, s, g = np.ones((4, 2)), np.eye(2), np.ones((3, 2))
+    for bad in (0, -3):
+        with pytest.raises(ValueError, match="max_iters"):
+            sharded.res_nmtf_inner([np.ones((4, 3))], init_f=[f], init_s=[s], init_g=[g], rank=0, world=1, max_iters=bad)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode,world,k", [("gpu_api", 3, 7), ("gpu_api_conv", 2, 24)])
 def test_sharded_res_nmtf_inner_hip(tmp_path, mode, world, k):
