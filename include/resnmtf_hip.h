@@ -356,6 +356,28 @@ int resnmtf_set_view(resnmtf_handle* h, int v, const double* x);
 int resnmtf_set_view_raw(resnmtf_handle* h, int v, const double* x_raw, int* was_negative);
 
 /*
+ * The same two uploads for a dense matrix that is ALREADY in device memory, in any of four floating types and with
+ * any (non-negative) strides, without a host copy and without an fp64 staging buffer: element (r, c) of the n x m view
+ * is x[r * row_stride + c * col_stride], strides in ELEMENTS (column-major: 1, n; row-major: m, 1; transposed views and
+ * slices likewise; x points at element (0, 0)).  raw == 0 takes the values as resnmtf_set_view does (already non-negative
+ * and column-normalised, R/utils.r:416,422); raw != 0 runs make_non_neg_inner and matrix_normalisation on the device as
+ * resnmtf_set_view_raw does (R/utils.r:20-27,86-88) and reports *was_negative (may be NULL); data_norms (R/main.r:48)
+ * either way.  Widening to fp64 is exact for all four types and every sum keeps the order of the host route, so the
+ * images, data_norms and *was_negative are BIT FOR BIT those of resnmtf_set_view / resnmtf_set_view_raw of the same
+ * values widened on the host.  A zero column yields NaN as there; resnmtf_view_empty_lines reports zero, as after a
+ * host upload.
+ *   stream  the hipStream_t on which the producer of x was enqueued (NULL: the null stream).  The library records an
+ *           event there and makes its own stream wait for it.  The call returns when the images are built
+ *           (as resnmtf_set_view does), so x may be freed on return.
+ * Refused before any device work (RESNMTF_ERR_INVALID / _STATE, text in resnmtf_last_error): x == NULL, an unknown
+ * dtype, a negative stride, a pointer that is not device memory of the handle's device, a view the handle does not
+ * own, a sparse view (resnmtf_set_view_csc).
+ */
+enum { RESNMTF_DTYPE_F64 = 0, RESNMTF_DTYPE_F32 = 1, RESNMTF_DTYPE_F16 = 2, RESNMTF_DTYPE_BF16 = 3 };
+int resnmtf_set_view_device(resnmtf_handle* h, int v, const void* x, int dtype, long long row_stride, long long col_stride,
+                            int raw, int* was_negative, void* stream);
+
+/*
  * View data without a host round trip (the callers of the loop repeat it 36-66 times per apply_resnmtf):
  *   resnmtf_copy_view     device copy of an uploaded view of another handle on the same GPU (same n x m) --
  *                         the k sweep (R/main.r:279-290) factorises ONE data set for every k;
@@ -473,6 +495,15 @@ int resnmtf_get_factors(resnmtf_handle* h, int v, double* F, double* S, double* 
  */
 int resnmtf_finalise(resnmtf_handle* h, int v, double* F, double* S, double* G,
                      double* row_clusters, double* col_clusters);
+/*
+ * The same (same kernels, same bits: R/utils.r:176-195, R/obtain_bicl.r:162-180), written to caller-owned DEVICE
+ * buffers on the handle's device: fp64 column-major, n x k, k x k, m x k, n x k, m x k; any may be NULL.  `stream` is
+ * the hipStream_t the caller works on (NULL: the null stream): the library's writes are ordered after the work already
+ * enqueued there and before any work enqueued there after the call returns.  A pointer that is not device memory of the
+ * handle's device is refused before any device work.
+ */
+int resnmtf_finalise_device(resnmtf_handle* h, int v, double* F, double* S, double* G,
+                            double* row_clusters, double* col_clusters, void* stream);
 
 /*
  * Stability selection (stability_check, R/stability_analysis.r:302-338) scores every sub-sample's factorisation

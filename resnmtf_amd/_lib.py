@@ -22,6 +22,7 @@ PHASE_SLICE_F, PHASE_SLICE_XTF, PHASE_SLICE_G, PHASE_SLICE_XG = 9, 10, 11, 12
 FACTOR_U_SEND, FACTOR_U_RECV, FACTOR_FNEW_SEND, FACTOR_FNEW_RECV = 9, 10, 11, 12
 FACTOR_T_SEND, FACTOR_T_RECV, FACTOR_GNEW_SEND, FACTOR_GNEW_RECV, FACTOR_F_SLICE, FACTOR_G_SLICE = 13, 14, 15, 16, 17, 18
 TIMED_KINDS = ("xg", "xtf", "f_chain", "g_chain", "s_chain", "pack")
+DTYPE_F64, DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2, 3      # RESNMTF_DTYPE_* (resnmtf_set_view_device)
 ABI_VERSION = 2
 MAX_K = 64
 
@@ -111,6 +112,7 @@ SIGNATURES = {
     "resnmtf_get_view_csc": (C.c_int, [_h, C.c_int, C.POINTER(C.c_longlong), _ip, _dp]),
     "resnmtf_set_view": (C.c_int, [_h, C.c_int, _dp]),
     "resnmtf_set_view_raw": (C.c_int, [_h, C.c_int, _dp, _ip]),
+    "resnmtf_set_view_device": (C.c_int, [_h, C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_int, _ip, C.c_void_p]),
     "resnmtf_copy_view": (C.c_int, [_h, C.c_int, _h, C.c_int]),
     "resnmtf_shuffle_view": (C.c_int, [_h, C.c_int, _h, C.c_int, C.c_ulonglong, C.c_int]),
     "resnmtf_subsample_view": (C.c_int, [_h, C.c_int, _h, C.c_int, _ip, _ip]),
@@ -125,6 +127,7 @@ SIGNATURES = {
     "resnmtf_run": (C.c_int, [_h, C.c_int, C.c_double, C.c_int, _dp, C.c_int, _ip]),
     "resnmtf_get_factors": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "resnmtf_finalise": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "resnmtf_finalise_device": (C.c_int, [_h, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "resnmtf_set_reference_clusters": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp]),
     "resnmtf_relevance": (C.c_int, [_h, C.c_int, _h, C.c_int, _ip, _ip, _dp]),
     "resnmtf_relevance_masked": (C.c_int, [_h, C.c_int, _h, C.c_int, _ip, _ip, C.POINTER(C.c_ubyte), _dp]),

@@ -39,7 +39,7 @@ from typing import Callable, Optional
 
 import numpy as np
 
-from . import batched, bisil, naming, sparse
+from . import batched, bisil, device_views, naming, sparse
 from . import spurious as _spurious
 from .engine import Engine
 from .problem import couple, inner_result, prepare, svd_init  # noqa: F401  (svd_init: part of this module's surface)
@@ -49,15 +49,21 @@ _DISTANCES = ("euclidean", "manhattan", "cosine")
 
 
 def _as_list(x):
-    if (isinstance(x, np.ndarray) and x.ndim == 2) or sparse.is_sparse(x):
+    if (isinstance(x, np.ndarray) and x.ndim == 2) or sparse.is_sparse(x) or isinstance(x, device_views.RawDeviceView):
         return [x]                      # check_lists, R/utils.r:313-316
+    if device_views.is_tensor(x):       # one tensor is one view (never a list of its rows)
+        device_views.check_tensor(x)
+        return [x]
     return list(x)
 
 
-def _views(data) -> list:
+def _views(data, device_id: int = 0) -> list:
     """The views as fp64 arrays; a ``scipy.sparse`` view becomes a canonical CSC copy (``sparse.canonical_csc``: the
-    caller's matrix is not modified) and stays sparse on the device (``resnmtf_create_sparse``)."""
-    return [sparse.canonical_csc(d) if sparse.is_sparse(d) else np.asarray(d, dtype=np.float64) for d in _as_list(data)]
+    caller's matrix is not modified) and stays sparse on the device (``resnmtf_create_sparse``); a ``torch`` tensor on
+    ``cuda:device_id`` stays the tensor it is (``device_views.as_view``: 2-D, floating, on that device, else
+    ``ValueError``; a CPU tensor becomes its fp64 array)."""
+    return [sparse.canonical_csc(d) if sparse.is_sparse(d) else device_views.as_view(d, device_id, f"view {v}")
+            for v, d in enumerate(_as_list(data))]
 
 
 def _load_engine(eng: Engine, data, init_f, init_s, init_g, lam, mu, phi, xi, psi,
@@ -68,7 +74,7 @@ def _load_engine(eng: Engine, data, init_f, init_s, init_g, lam, mu, phi, xi, ps
             if sparse.is_sparse(data[v]):
                 eng.set_view_sparse(v, data[v], pre_processed=True)                                    # (already pre-processed)
             else:
-                eng.set_view(v, data[v])
+                device_views.upload(eng, v, data[v])                                                   # (a tensor: in place)
         if init_f is None:
             eng.init_svd(v, seed=_seed(seed) + v)                          # update_steps.r:78-125
         else:
@@ -86,7 +92,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
                    max_iters: int = 100000, seed: Optional[int] = None, engine_opts: Optional[dict] = None,
                    host_init: bool = False, return_init: bool = False, score_bisil: bool = False,
                    spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False,
-                   sparse_on_device: bool = False):
+                   sparse_on_device: bool = False, output: str = "numpy"):
     """``res_nmtf_inner`` (``R/main.r:32-140``).
 
     ``data``: list of pre-processed (non-negative, column-normalised) matrices; ``row_indices[v][w]``
@@ -116,9 +122,19 @@ def res_nmtf_inner(data, row_indices, column_indices,
     the rule; pass the same flag to ``remove_spurious`` for the identity above; no effect on dense views),
     ``sparse_on_device`` (a no-op here by design, DESIGN.md section 10: accepted so that callers pass one set of flags to
     every entry point; this function uploads ``data`` itself and its spurious children are shuffles, which always draw
-    from the engine's own handle, so it has no copy or sub-sample to route).
+    from the engine's own handle, so it has no copy or sub-sample to route), ``output`` (``"numpy"``, or ``"torch"``:
+    ``output_f`` / ``output_s`` / ``output_g`` / ``row_clusters`` / ``col_clusters`` are then fp64 ``torch`` tensors on
+    ``cuda:device_id``, written there by ``Engine.finalise_device`` -- bitwise the NumPy result; the small values stay
+    NumPy).
+
+    A view may also be a 2-D floating ``torch`` tensor on ``cuda:device_id`` (fp64 / fp32 / fp16 / bf16, any strides;
+    mixed freely with NumPy and ``scipy.sparse`` views): it is uploaded in place (``Engine.set_view_device``), bitwise
+    as ``t.double().cpu().numpy()`` would be, and never converted to NumPy.  A CPU tensor is taken as its NumPy array.
+    ``ValueError`` for a non-floating dtype, another device, or a tensor that is not 2-D; ``host_init=True`` without
+    explicit initial factors raises ``NotImplementedError`` for such a view, as for a sparse one.
     """
-    data = _views(data)
+    device_views.check_output(output)
+    data = _views(data, device_id)
     n_v = len(data)
     if k_vec is None:
         raise ValueError("k_vec is required")
@@ -144,6 +160,9 @@ def res_nmtf_inner(data, row_indices, column_indices,
     if any(is_sp) and host_init and (init_f is None or init_g is None or init_s is None):
         raise NotImplementedError("host_init=True (NumPy's dense SVD) is not available for sparse views; the device "
                                   "initialisation (host_init=False) works on them")
+    if any(device_views.is_device_view(d) for d in data) and host_init and (init_f is None or init_g is None or init_s is None):
+        raise NotImplementedError("host_init=True (NumPy's dense SVD) is not available for views in device memory; the "
+                                  "device initialisation (host_init=False) works on them")
     phi, xi, psi = (np.zeros((n_v, n_v)) if m is None else np.asarray(m, dtype=np.float64) for m in (phi, xi, psi))
     row_names, col_names = naming.give_names(data, None, None, row_names, col_names)
 
@@ -165,6 +184,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
         # per view: F, S, G, the binary clusters (main.r:110 + obtain_bicl.r:162-180), lambda, mu
         out_f, out_s, out_g, row_cl, col_cl, lams, mus = (
             list(x) for x in zip(*[(*eng.finalise(v), *eng.get_factors(v)[3:]) for v in range(n_v)]))
+        on_device = [eng.finalise_device(v) for v in range(n_v)] if output == "torch" else None
         check = (_spurious.check_on_device(eng, num_repeats, seed, max_iters=max_iters, device_id=device_id,
                                            shuffle_sparse=shuffle_sparse)
                  if remove else None)                                                             # obtain_bicl.r:151-188
@@ -174,12 +194,23 @@ def res_nmtf_inner(data, row_indices, column_indices,
     finally:
         eng.close()
     # ("init": a test hook, the initial state the device built, for a reference run from the same start)
+    if on_device is not None:        # the host steps above read the NumPy copies; what is returned lives on the device
+        out_f, out_s, out_g = _device_outputs(on_device, row_cl, col_cl, cleaned)
     if no_clusts:                                                                                 # main.r:115-120
         return inner_result(out_f, out_s, out_g, init=init_state)
     # ("bisil": None unless score_bisil; bisil.py, parity with bisilhouette::bisilhouette unpinned)
     return inner_result(out_f, out_s, out_g, total_err, n_iters, bisil=cleaned.get("bisil"),
                         row_clusters=cleaned["row_clusters"], col_clusters=cleaned["col_clusters"], lam=lams, mu=mus,
                         spurious=cleaned.get("spurious"), init=init_state)
+
+
+def _device_outputs(on_device, row_cl, col_cl, cleaned: dict):
+    """``output="torch"``: ``on_device`` holds ``Engine.finalise_device``'s five tensors per view, ``row_cl`` / ``col_cl``
+    the NumPy clusters ``finalise`` gave and ``cleaned`` what the host steps made of them (spurious columns zeroed).
+    Returns the F, S, G lists on the device and replaces ``cleaned``'s clusters by the tensors, the same columns zeroed."""
+    for key, i, before in (("row_clusters", 3, row_cl), ("col_clusters", 4, col_cl)):
+        cleaned[key] = [device_views.zero_columns_like(t[i], b, a) for t, b, a in zip(on_device, before, cleaned[key])]
+    return tuple([t[i] for t in on_device] for i in range(3))
 
 
 def _remove_then_score(res: dict, check: Optional[dict], score_fn: Optional[Callable]) -> dict:
@@ -194,7 +225,7 @@ def _remove_then_score(res: dict, check: Optional[dict], score_fn: Optional[Call
 def _number_biclusters(results) -> float:
     """``number_biclusters`` (``R/stability_analysis.r:92-97``): the sum of every row-cluster matrix; 0 for results
     without cluster matrices (``no_clusts``)."""
-    return float(sum(np.asarray(rc).sum() for rc in (results.get("row_clusters") or [])))
+    return float(sum(np.asarray(device_views.to_numpy(rc)).sum() for rc in (results.get("row_clusters") or [])))
 
 
 def _refuse_host_spurious(wanted, spurious_on_device: bool, message: str):
@@ -237,7 +268,8 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
                     sample_rate=0.9, n_stability=5, stab_thres=0.6, remove_unstable=True, *,
                     row_names=None, col_names=None, device_id: int = 0, seed: Optional[int] = None, group=None,
                     max_iters: int = 100000, return_repeats: bool = False, repeat_runner: Optional[Callable] = None,
-                    spurious_on_device: bool = False, shuffle_sparse: bool = False, sparse_on_device: bool = False):
+                    spurious_on_device: bool = False, shuffle_sparse: bool = False, sparse_on_device: bool = False,
+                    output: str = "numpy"):
     """``stability_check`` (``R/stability_analysis.r:302-338``): ``n_stability`` factorisations of sub-samples
     (``sample_rate`` of the rows and columns, drawn and trimmed as ``stability_repeat`` does, ``:215-249``), each scored
     against ``results`` by ``relevance_results`` (``:45-67``) -- the gathers, the factorisations and the scoring run on
@@ -261,8 +293,12 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
     Keyword-only extras: names, ``device_id``, ``seed`` of the draws and the device SVD inits, ``group``,
     ``max_iters``; test hooks: ``return_repeats`` (adds ``"repeats"``: per repeat the trimmed draws, relevance and
     the sub-sample's own clusters -- under ``"stability"`` of a copy of the result), ``repeat_runner(r)`` (replaces
-    one repeat; nothing touches the device).
+    one repeat; nothing touches the device); ``output``: ``"torch"`` returns the two cluster lists as fp64 ``torch``
+    tensors on ``cuda:device_id`` (those of ``results`` when it holds tensors, with the unstable columns zeroed there;
+    the scoring reads NumPy copies of them either way), ``"numpy"`` as NumPy arrays.  The views may be ``torch`` tensors
+    on that device, as for ``res_nmtf_inner``.
     """
+    device_views.check_output(output)
     if _number_biclusters(results) == 0:                                                          # :308-311
         warnings.warn("No biclusters detected!")
         return results
@@ -273,8 +309,11 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
     _check_stability_numbers(sample_rate, stab_thres)
     if int(n_stability) != n_stability or n_stability < 1:
         raise ValueError("n_stability must be a positive integer.")
-    data = _views(data)
+    data = _views(data, device_id)
     n_v = len(data)
+    given = results                 # host copies of the small cluster matrices for the scoring; `given` keeps the caller's
+    results = dict(results, row_clusters=[device_views.to_numpy(rc) for rc in results["row_clusters"]],
+                   col_clusters=[device_views.to_numpy(cc) for cc in results["col_clusters"]])
     if spurious_repeats and repeat_runner is None and not shuffle_sparse and any(sparse.is_sparse(d) for d in data):
         raise NotImplementedError("spurious-bicluster removal needs shuffled views: device shuffles of sparse views "
                                   "are not supported")
@@ -295,22 +334,35 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
             dev.close()
     if not stab["stability_performed"]:                                                          # :323-325
         warnings.warn("Unable to perform stability analysis due to sparsity of data.")
-        return results
+        return given
     relevance = stab["relevance"]
     if not remove_unstable:                                                                       # :328-329
-        out = {"res": results, "relevance": relevance}
+        out = {"res": given, "relevance": relevance}
     else:                                                                                         # :330-337
-        out = dict(results)
+        out = dict(given)
         out["row_clusters"] = [np.array(rc, dtype=np.float64, copy=True) for rc in results["row_clusters"]]
         out["col_clusters"] = [np.array(cc, dtype=np.float64, copy=True) for cc in results["col_clusters"]]
         for i in range(n_v):
             drop = relevance[i] < stab_thres
             out["row_clusters"][i][:, drop] = 0.0
             out["col_clusters"][i][:, drop] = 0.0
+        for key in ("row_clusters", "col_clusters"):
+            out[key] = [_cluster_output(g, b, a, output, device_id) for g, b, a in zip(given[key], results[key], out[key])]
     if return_repeats:
         out = dict(out)
         out["stability"] = {"relevance": relevance, "repeats": stab["repeats"]}
     return out
+
+
+def _cluster_output(given, before: np.ndarray, after: np.ndarray, output: str, device_id: int):
+    """A cluster matrix of ``stability_check``'s result in the form ``output`` asks for: ``after`` is the host copy
+    ``before`` of ``given`` with its unstable columns zeroed.  A tensor is cloned and the same columns zeroed on the device."""
+    if output == "numpy":
+        return after
+    import torch        # (output="torch": the caller works with it)
+    if device_views.is_tensor(given):
+        return device_views.zero_columns_like(given.clone(), before, after)
+    return torch.as_tensor(after, device=torch.device("cuda", int(device_id)))
 
 
 def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
@@ -321,7 +373,7 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                   device_id: int = 0, max_iters: int = 100000, seed: Optional[int] = None,
                   k_sweep: bool = False, return_sweep: bool = False, sweep_runner: Optional[Callable] = None,
                   spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False,
-                  sparse_on_device: bool = False):
+                  sparse_on_device: bool = False, output: str = "numpy"):
     """``apply_resnmtf`` (``R/main.r:214-335``) for a known ``k_val``: naming, shared-name maps, restriction
     symmetrisation, non-negativity shift and column normalisation on the host, then the device loop and -- with
     ``stability=True`` (the default) and ``spurious=False`` -- ``stability_check`` on the pre-processed data, as
@@ -360,9 +412,17 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     sub-samples of the stability repeats are made on the device from the one upload (``resnmtf_copy_view_sparse``,
     ``resnmtf_subsample_view_sparse``; DESIGN.md section 10 "Device copies and sub-samples") instead of gathered on the
     host and uploaded.  Same clusters, factors and stability outcome; ``All_Error`` of the repeats within 1e-6 absolute.  No
-    effect on dense data."""
+    effect on dense data.
+
+    A view may be a 2-D floating ``torch`` tensor on ``cuda:device_id`` (``res_nmtf_inner``): it is never brought to the
+    host -- its shift and column normalisation run on the device at every upload (``Engine.set_view_device(raw=True)``,
+    the sums in the device's order, where ``check_data`` sums a host view in NumPy's).  ``output="torch"`` (keyword-only)
+    returns ``output_f`` / ``output_s`` / ``output_g`` / ``row_clusters`` / ``col_clusters`` as fp64 ``torch`` tensors on
+    that device (``Engine.finalise_device``); the small values stay NumPy."""
+    device_views.check_output(output)
     on_dev = {"sparse_on_device": True} if sparse_on_device else {}      # (off: every call below is the earlier one)
-    data = _views(data)
+    out_kw = {"output": output} if output != "numpy" else {}
+    data = _views(data, device_id)
     n_v = len(data)
     if k_val is None and k_sweep:
         return _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k_max, distance, spurious,
@@ -370,7 +430,7 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                               row_names=row_names, col_names=col_names, device_id=device_id, max_iters=max_iters,
                               seed=seed, return_sweep=return_sweep, sweep_runner=sweep_runner,
                               spurious_on_device=spurious_on_device, bisil_sparse=bisil_sparse,
-                              shuffle_sparse=shuffle_sparse, **on_dev)
+                              shuffle_sparse=shuffle_sparse, **on_dev, **out_kw)
     if k_val is None:
         raise NotImplementedError("the k sweep (R/main.r:279-321) needs the bisilhouette score, which is "
                                   "outside the accelerated path; pass k_val")
@@ -389,13 +449,14 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     results = res_nmtf_inner(p.data, p.row_shared, p.col_shared, init_f, init_s, init_g, k_vec, p.phi, p.xi, p.psi,
                              n_iters, num_repeats, spurious, distance, no_clusts,
                              row_names=p.row_names, col_names=p.col_names, device_id=device_id, max_iters=max_iters,
-                             seed=seed, spurious_on_device=spurious_on_device, shuffle_sparse=shuffle_sparse, **on_dev)
+                             seed=seed, spurious_on_device=spurious_on_device, shuffle_sparse=shuffle_sparse, **on_dev,
+                             **out_kw)
     if stability:                                                                                 # main.r:255-262
         results = stability_check(p.data, results, k_vec, p.phi, p.xi, p.psi, n_iters, spurious, num_repeats,
                                   no_clusts, distance, sample_rate, n_stability, stab_thres,
                                   row_names=p.row_names, col_names=p.col_names, device_id=device_id, seed=seed,
                                   max_iters=max_iters, spurious_on_device=spurious_on_device,
-                                  shuffle_sparse=shuffle_sparse, **on_dev)
+                                  shuffle_sparse=shuffle_sparse, **on_dev, **out_kw)
     return results
 
 
@@ -432,10 +493,11 @@ def _sweep(run: Callable, k_min: int, k_max: int, cap: int, initial: Optional[li
 def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k_max, distance, spurious, num_repeats,
                    no_clusts, sample_rate, n_stability, stability, stab_thres, remove_unstable, *, row_names, col_names,
                    device_id, max_iters, seed, return_sweep, sweep_runner, spurious_on_device=False, bisil_sparse=False,
-                   shuffle_sparse=False, sparse_on_device=False):
+                   shuffle_sparse=False, sparse_on_device=False, output="numpy"):
     """``apply_resnmtf`` with ``k_val = NULL`` (``R/main.r:269-334``); see ``apply_resnmtf``."""
     n_v = len(data)
     on_dev = {"sparse_on_device": True} if sparse_on_device else {}
+    out_kw = {"output": output} if output != "numpy" else {}
     _check_common(n_iters, num_repeats, n_stability, distance, sample_rate, stab_thres)
     _check_whole_number(k_min, "k_min")
     _check_whole_number(k_max, "k_max")
@@ -474,7 +536,10 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
                                              r.get("spurious_check"),
                                              lambda rc, cc: bisil.score(rc, cc, distance, engine=dev.base,
                                                                         sparse_views=bisil_sparse))
-                return inner_result(r["output_f"], r["output_s"], r["output_g"], r["All_Error"], n_iters,
+                out = (r["output_f"], r["output_s"], r["output_g"])
+                if r.get("device_out") is not None:         # output="torch": what is returned lives on the device
+                    out = _device_outputs(r["device_out"], r["row_clusters"], r["col_clusters"], cleaned)
+                return inner_result(*out, r["All_Error"], n_iters,
                                     bisil=cleaned["bisil"], row_clusters=cleaned["row_clusters"],
                                     col_clusters=cleaned["col_clusters"], lam=r["lambda"], mu=r["mu"],
                                     spurious=cleaned.get("spurious"))
@@ -484,12 +549,12 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
             def run(k):
                 return scored(dev.factorise(k, n_iters, seed + k, max_iters=max_iters, tag=f"k={k}", return_lm=True,
                                             spurious_repeats=spurious_repeats, spurious_seed=seed + k,
-                                            shuffle_sparse=shuffle_sparse, **on_dev))
+                                            shuffle_sparse=shuffle_sparse, **on_dev, **out_kw))
 
             initial = [scored(r) for r in batched.k_sweep_on_device(dev, k_min, k_max, n_iters, seed,       # main.r:279-290
                                                                     max_iters=max_iters, return_lm=True,
                                                                     spurious_repeats=spurious_repeats,
-                                                                    shuffle_sparse=shuffle_sparse, **on_dev)]
+                                                                    shuffle_sparse=shuffle_sparse, **on_dev, **out_kw)]
         else:
             run, initial = sweep_runner, None
         ks, scores, results, pick = _sweep(run, k_min, k_max, cap, initial)
@@ -502,7 +567,7 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
                                   no_clusts, distance, sample_rate, n_stability, stab_thres, remove_unstable,
                                   row_names=p.row_names, col_names=p.col_names, device_id=device_id, seed=seed,
                                   max_iters=max_iters, spurious_on_device=spurious_on_device,
-                                  shuffle_sparse=shuffle_sparse, **on_dev)
+                                  shuffle_sparse=shuffle_sparse, **on_dev, **out_kw)
     if return_sweep:
         results = dict(results)
         results["k_sweep"] = {"k": ks, "bisil": scores}

@@ -30,7 +30,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import naming, sparse, spurious
+from . import device_views, naming, sparse, spurious
 from ._lib import GROUP_MAX_K, GROUP_MAX_VIEW_ENTRIES, GROUP_MAX_VIEWS
 from .engine import Engine, group_run
 from .problem import (inner_result, load_child, pair_table, prepare, reported_error,  # noqa: F401  (shuffled_engines:
@@ -293,7 +293,12 @@ class DeviceData:
     ``pre_processed=True`` (opt-in) takes the data as ``res_nmtf_inner`` receives them: the views are uploaded exactly
     as given (``resnmtf_set_view``, no shift, no normalisation) and ``phi`` / ``xi`` / ``psi`` are the symmetrised
     matrices, used as they are -- the form ``stability_check`` gets both in (``R/main.r:255-262``; its sub-samples are
-    not re-normalised)."""
+    not re-normalised).
+
+    A dense view may be a 2-D floating ``torch`` tensor on ``cuda:device_id``: it is uploaded in place
+    (``resnmtf_set_view_device``, with the shift and the normalisation unless ``pre_processed``), bitwise as its values
+    widened on the host would be, and never converted to NumPy; a ``device_views.RawDeviceView`` is pre-processed at
+    its upload either way (what ``prepare(normalise=True)`` makes of a device tensor)."""
 
     def __init__(self, data, phi=None, xi=None, psi=None, row_names=None, col_names=None, device_id: int = 0,
                  pre_processed: bool = False):
@@ -304,7 +309,7 @@ class DeviceData:
         for c in self.sp:
             if pre_processed and c is not None:
                 sparse.validate(c)
-        data = [np.asarray(d) if c is None else c for d, c in zip(data, self.sp)]
+        data = [device_views.as_view(d, device_id, f"view {v}") if c is None else c for v, (d, c) in enumerate(zip(data, self.sp))]
         self.data_shapes = [tuple(d.shape) for d in data]
         n_v = len(data)
         # (not pre_processed: the device shifts and normalises the dense views, set_view_raw below)
@@ -317,10 +322,8 @@ class DeviceData:
         for v in range(n_v):
             if self.sp[v] is not None:
                 self.base.set_view_sparse(v, self.sp[v], pre_processed=True)      # (normalised on the host: self.sp)
-            elif pre_processed:
-                self.base.set_view(v, np.asarray(data[v], dtype=np.float64))
-            else:
-                self.was_negative[v] = self.base.set_view_raw(v, np.asarray(data[v], dtype=np.float64))
+            else:           # (a host array: set_view / set_view_raw; a tensor: set_view_device, in place)
+                self.was_negative[v] = device_views.upload(self.base, v, data[v], raw=not pre_processed)
 
     def close(self):
         self.base.close()
@@ -423,7 +426,8 @@ class DeviceData:
     def factorise(self, k: int, n_iters: Optional[int] = None, seed: int = 0, shuffle_seed: Optional[int] = None,
                   max_iters: int = 100000, tag: str = "", samples=None, return_init: bool = False,
                   return_data: bool = False, return_lm: bool = False, spurious_repeats: int = 0,
-                  spurious_seed: int = 0, *, shuffle_sparse: bool = False, sparse_on_device: bool = False) -> dict:
+                  spurious_seed: int = 0, *, shuffle_sparse: bool = False, sparse_on_device: bool = False,
+                  output: str = "numpy") -> dict:
         """One factorisation with k biclusters per view of the views copied, shuffled (``shuffle_seed``) or sub-sampled
         (``samples``) on the device (``child``): device SVD init, loop, finalise.  With ``samples`` whose trimming
         fails: ``{"stability_performed": False, "tag"}``.
@@ -436,8 +440,10 @@ class DeviceData:
         views, by ``shuffle_seed`` and by the spurious check alike; ``return_data`` of a shuffled sparse view stays
         refused (the host holds no copy of the shuffle: ``Engine.get_view_sparse`` reads it without densifying).
         ``sparse_on_device`` (opt-in): sparse views are copied / sub-sampled on the device (``child``); ``return_data``
-        then reads them back (``Engine.get_view_sparse``: the same f32-rounded matrix)."""
+        then reads them back (``Engine.get_view_sparse``: the same f32-rounded matrix).  ``output="torch"`` adds
+        ``"device_out"``: per view ``Engine.finalise_device``'s five tensors (the other keys stay NumPy)."""
         n_v = len(self.data_shapes)
+        device_views.check_output(output)
         if return_data and shuffle_seed is not None and any(c is not None for c in self.sp):
             raise NotImplementedError("return_data of a shuffled sparse view is not supported (it would densify the shuffle)")
         with self.child(k, seed, shuffle_seed, samples, shuffle_sparse=shuffle_sparse, sparse_on_device=sparse_on_device) as ch:
@@ -454,13 +460,14 @@ class DeviceData:
                                               device_id=self.device_id, shuffle_sparse=shuffle_sparse)
                      if spurious_repeats else None)
             fin = [eng.finalise(v) for v in range(n_v)]
+            fin_dev = [eng.finalise_device(v) for v in range(n_v)] if output == "torch" else None
             lms = [eng.get_factors(v)[3:] for v in range(n_v)] if return_lm else None
         f, s, g, rc, cc = (list(x) for x in zip(*fin))
         return inner_result(f, s, g, errs, n_iters, device_data=True, row_clusters=rc, col_clusters=cc, tag=tag,
                             extras={} if ch.samples is None else {"row_samples": ch.samples[0], "col_samples": ch.samples[1]},
                             row_names=ch.row_names, col_names=ch.col_names, init=init_state,
                             lam=lms and [lm[0] for lm in lms], mu=lms and [lm[1] for lm in lms], data=data_used,
-                            spurious_check=check)
+                            spurious_check=check, device_out=fin_dev)
 
     def stability_repeat(self, k: int, n_iters: Optional[int], seed: int, samples, max_iters: int = 100000, tag: str = "",
                          keep_clusters: bool = False, spurious_repeats: int = 0, spurious_seed: int = 0, *,
@@ -503,13 +510,15 @@ class DeviceData:
 
 def k_sweep_on_device(dev: DeviceData, k_min: int = 3, k_max: int = 8, n_iters=None, seed: int = 0, group=None,
                       max_iters: int = 100000, return_lm: bool = False, spurious_repeats: int = 0, *,
-                      shuffle_sparse: bool = False, sparse_on_device: bool = False) -> List[dict]:
+                      shuffle_sparse: bool = False, sparse_on_device: bool = False, output: str = "numpy") -> List[dict]:
     """The factorisations of the k sweep (``R/main.r:279-290``) from one upload; sharded round-robin over
     the ranks of an initialised process group (every rank holds its own ``DeviceData``).  ``spurious_repeats``: each
     k's result carries its ``"spurious_check"`` (``DeviceData.factorise``, spurious seed ``seed + k``).
     ``sparse_on_device`` (opt-in): every k copies the sparse views from ``dev.base`` on the device
-    (``resnmtf_copy_view_sparse``) instead of uploading the host CSC again."""
+    (``resnmtf_copy_view_sparse``) instead of uploading the host CSC again.  ``output``: ``DeviceData.factorise``."""
     more = {"sparse_on_device": True} if sparse_on_device else {}
+    if output != "numpy":
+        more["output"] = output
     ks = list(range(k_min, k_max + 1))
     return run_jobs(ks, group=group, runner=lambda k: dev.factorise(k, n_iters, seed + k, max_iters=max_iters, tag=f"k={k}",
                                                                     return_lm=return_lm, spurious_repeats=spurious_repeats,

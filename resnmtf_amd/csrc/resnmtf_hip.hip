@@ -29,6 +29,7 @@
 
 #include "resnmtf_hip.h"
 #include "resnmtf_kernels.hip.inc"
+#include "resnmtf_device_view.hip.inc"
 #include "resnmtf_sparse.hip.inc"
 #include <rocprim/rocprim.hpp>
 #include "resnmtf_sparse_shuffle.hip.inc"
@@ -1670,11 +1671,93 @@ int upload_view(resnmtf_handle* h, int v, const double* x, bool raw, int* was_ne
   if (vs.half_capable) return build_half_images(h, vs);
   return RESNMTF_OK;
 }
+
+// ---- device-resident callers (resnmtf_set_view_device, resnmtf_finalise_device)
+// true when p is device memory of the handle's device; a host pointer makes hipPointerGetAttributes fail (or report host
+// memory, by version): both are "no", and the sticky error is cleared
+bool on_handle_device(resnmtf_handle* h, const void* p) {
+  hipPointerAttribute_t attr;
+  std::memset(&attr, 0, sizeof(attr));
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return attr.type == hipMemoryTypeDevice && attr.device == h->opt.device_id;
+}
+// the handle's stream waits for everything enqueued on the caller's stream so far
+hipError_t wait_for_caller(resnmtf_handle* h, void* stream) {
+  hipEvent_t ev = nullptr;
+  hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+  if (e != hipSuccess) return e;
+  e = hipEventRecord(ev, static_cast<hipStream_t>(stream));
+  if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, ev, 0);
+  (void)hipEventDestroy(ev);          // (released once the recorded work completes)
+  return e;
+}
+// upload_view without the staging image: the kernels of resnmtf_device_view.hip.inc read the caller's matrix in place.
+// Transient device memory: the ceil(n/32) ceil(m/32) block partials and, raw, the 2 m + 1 column statistics.
+int upload_view_device(resnmtf_handle* h, int v, const void* x, int dtype, long long rs, long long cs, bool raw, int* was_negative,
+                       void* stream) {
+  if (int rc = check_view(h, v)) return rc;
+  if (!x) return h->fail(RESNMTF_ERR_INVALID, "x is NULL");
+  if (dtype != RESNMTF_DTYPE_F64 && dtype != RESNMTF_DTYPE_F32 && dtype != RESNMTF_DTYPE_F16 && dtype != RESNMTF_DTYPE_BF16)
+    return h->fail(RESNMTF_ERR_INVALID, "unknown dtype: one of RESNMTF_DTYPE_F64 / _F32 / _F16 / _BF16");
+  if (rs < 0 || cs < 0) return h->fail(RESNMTF_ERR_INVALID, "negative strides are not supported");
+  ViewState& vs = h->views[v];
+  if (!vs.owned) return h->fail(RESNMTF_ERR_STATE, "set_view on a view this handle does not own");
+  if (vs.sparse) return h->fail(RESNMTF_ERR_INVALID, "the view is sparse: upload it with resnmtf_set_view_csc");
+  if (!on_handle_device(h, x)) return h->fail(RESNMTF_ERR_INVALID, "x is not device memory of the handle's device (host data: resnmtf_set_view / resnmtf_set_view_raw)");
+  h->resume_ok = false;
+  HIP_TRY(h, hipSetDevice(h->opt.device_id));
+  if (int rc = sync_both(h)) return rc;
+  double* partial = nullptr;
+  double* colstat = nullptr;      // [2][m]: shift, colsum; then one int flag
+  const dim3 grid(ceil_div(vs.n, 32), ceil_div(vs.m, 32));
+  const int nparts = grid.x * grid.y;
+  HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&partial), (size_t)nparts * sizeof(double)));
+  hipError_t e = raw ? hipMalloc(reinterpret_cast<void**>(&colstat), ((size_t)2 * vs.m + 1) * sizeof(double)) : hipSuccess;
+  if (e != hipSuccess) { (void)hipFree(partial); return h->fail_hip("hipMalloc upload buffers", e); }
+  double* shift = raw ? colstat : nullptr;
+  double* colsum = raw ? colstat + vs.m : nullptr;
+  int* neg = raw ? reinterpret_cast<int*>(colstat + 2 * (size_t)vs.m) : nullptr;
+  int neg_host = 0;
+  vs.empty_rows = vs.empty_cols = 0; vs.empty_mask.clear();
+  e = wait_for_caller(h, stream);
+  if (e == hipSuccess) e = hipMemsetAsync(vs.side[SIDE_G].X, 0, vs.side[SIDE_G].x_floats * sizeof(float), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(vs.side[SIDE_F].X, 0, vs.side[SIDE_F].x_floats * sizeof(float), h->stream);
+  if (e == hipSuccess && raw) e = hipMemsetAsync(neg, 0, sizeof(double), h->stream);
+  if (e == hipSuccess) {
+    const bool rows = cs == 1 && rs != 1;             // a row-major source: read along c
+    pick_int<RESNMTF_DTYPE_F64, RESNMTF_DTYPE_F32, RESNMTF_DTYPE_F16, RESNMTF_DTYPE_BF16>(dtype, [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      if (raw) {
+        if (rows) hipLaunchKernelGGL(device_column_stats_rows_kernel<DT>, dim3(ceil_div(vs.m, 32)), dim3(256), 0, h->stream, x, rs, vs.n, vs.m, shift, colsum, neg);
+        else hipLaunchKernelGGL(device_column_stats_kernel<DT>, dim3(vs.m), dim3(256), 0, h->stream, x, rs, cs, vs.n, vs.m, shift, colsum, neg);
+      }
+      if (rows) hipLaunchKernelGGL((device_convert_x_kernel<DT, true>), grid, dim3(256), 0, h->stream, x, rs, cs, vs.n, vs.m, vs.side[SIDE_G].X,
+                                   vs.side[SIDE_G].ldx, vs.side[SIDE_F].X, vs.side[SIDE_F].ldx, partial, shift, colsum);
+      else hipLaunchKernelGGL((device_convert_x_kernel<DT, false>), grid, dim3(256), 0, h->stream, x, rs, cs, vs.n, vs.m, vs.side[SIDE_G].X,
+                              vs.side[SIDE_G].ldx, vs.side[SIDE_F].X, vs.side[SIDE_F].ldx, partial, shift, colsum);
+    });
+    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, h->stream, partial, nparts, vs.xnorm2);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && raw) e = hipMemcpyAsync(&neg_host, neg, sizeof(int), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  (void)hipFree(partial);
+  (void)hipFree(colstat);
+  if (e != hipSuccess) return h->fail_hip("set_view_device", e);
+  if (was_negative) *was_negative = neg_host;
+  vs.has_x = true;
+  if (vs.half_capable) return build_half_images(h, vs);
+  return RESNMTF_OK;
+}
 }  // namespace
 
 int resnmtf_set_view(resnmtf_handle* h, int v, const double* x) { return upload_view(h, v, x, false, nullptr); }
 int resnmtf_set_view_raw(resnmtf_handle* h, int v, const double* x_raw, int* was_negative) {
   return upload_view(h, v, x_raw, true, was_negative);
+}
+int resnmtf_set_view_device(resnmtf_handle* h, int v, const void* x, int dtype, long long row_stride, long long col_stride, int raw,
+                            int* was_negative, void* stream) {
+  return upload_view_device(h, v, x, dtype, row_stride, col_stride, raw != 0, was_negative, stream);
 }
 
 // ---- sparse views
@@ -3291,12 +3374,19 @@ int resnmtf_get_factors(resnmtf_handle* h, int v, double* F, double* S, double* 
   return RESNMTF_OK;
 }
 
-int resnmtf_finalise(resnmtf_handle* h, int v, double* F, double* S, double* G, double* row_clusters,
-                     double* col_clusters) {
+namespace {
+// resnmtf_finalise (outputs on the host) and resnmtf_finalise_device (outputs in device memory, ordered with `stream`)
+int finalise_impl(resnmtf_handle* h, int v, double* F, double* S, double* G, double* row_clusters, double* col_clusters,
+                  bool to_device, void* stream) {
   if (int rc = check_view(h, v)) return rc;
   ViewState& vs = h->views[v];
+  if (to_device)
+    for (const double* p : {F, S, G, row_clusters, col_clusters})
+      if (p && !on_handle_device(h, p)) return h->fail(RESNMTF_ERR_INVALID, "an output is not device memory of the handle's device (host buffers: resnmtf_finalise)");
   HIP_TRY(h, hipSetDevice(h->opt.device_id));
   if (int rc = sync_both(h)) return rc;
+  if (to_device) HIP_TRY(h, wait_for_caller(h, stream));
+  const hipMemcpyKind kind = to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   const size_t nk = (size_t)vs.n * vs.k, mk = (size_t)vs.m * vs.k, kk = (size_t)vs.k * vs.k;
   double* buf = nullptr;   // [cF k][cG k][S kk][Fout nk][rc nk][Gout mk][cc mk]
   int* rel = nullptr;
@@ -3313,16 +3403,32 @@ int resnmtf_finalise(resnmtf_handle* h, int v, double* F, double* S, double* G, 
   hipLaunchKernelGGL(finalise_factor_kernel, dim3((unsigned)((mk + 255) / 256)), dim3(256), 0, h->stream, vs.side[SIDE_G].W, vs.m,
                      vs.k, cG, (const int*)nullptr, Go, cc);
   e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e == hipSuccess && S) e = hipMemcpy(S, So, kk * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && F) e = hipMemcpy(F, Fo, nk * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && G) e = hipMemcpy(G, Go, mk * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && row_clusters) e = hipMemcpy(row_clusters, rc_, nk * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && col_clusters) e = hipMemcpy(col_clusters, cc, mk * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && !to_device) e = hipStreamSynchronize(h->stream);
+  // (to the device: the copies follow the kernels on the handle's stream, which is drained before the call returns --
+  // whatever the caller enqueues afterwards, on any stream, comes after them)
+  auto copy = [&](double* dst, const double* src, size_t count) {
+    return to_device ? hipMemcpyAsync(dst, src, count * sizeof(double), kind, h->stream) : hipMemcpy(dst, src, count * sizeof(double), kind);
+  };
+  if (e == hipSuccess && S) e = copy(S, So, kk);
+  if (e == hipSuccess && F) e = copy(F, Fo, nk);
+  if (e == hipSuccess && G) e = copy(G, Go, mk);
+  if (e == hipSuccess && row_clusters) e = copy(row_clusters, rc_, nk);
+  if (e == hipSuccess && col_clusters) e = copy(col_clusters, cc, mk);
+  if (to_device) { const hipError_t es = hipStreamSynchronize(h->stream); if (e == hipSuccess) e = es; }
   (void)hipFree(buf);
   (void)hipFree(rel);
   if (e != hipSuccess) return h->fail_hip("finalise", e);
   return RESNMTF_OK;
+}
+}  // namespace
+
+int resnmtf_finalise(resnmtf_handle* h, int v, double* F, double* S, double* G, double* row_clusters,
+                     double* col_clusters) {
+  return finalise_impl(h, v, F, S, G, row_clusters, col_clusters, false, nullptr);
+}
+int resnmtf_finalise_device(resnmtf_handle* h, int v, double* F, double* S, double* G, double* row_clusters,
+                            double* col_clusters, void* stream) {
+  return finalise_impl(h, v, F, S, G, row_clusters, col_clusters, true, stream);
 }
 
 // ---- stability selection (R/stability_analysis.r:302-338): relevance of a sub-sample's biclusters, on the device

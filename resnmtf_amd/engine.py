@@ -154,6 +154,7 @@ class Engine:
         self.n_cols = [int(x) for x in n_cols]
         self.k = [int(x) for x in k]
         self.owned = [True] * self.n_views if owned is None else [bool(x) for x in owned]
+        self.device_id = int(device_id)
         opts = _lib.Options()
         self._lib.resnmtf_default_options(C.byref(opts))
         opts.device_id = int(device_id)
@@ -238,6 +239,35 @@ class Engine:
         x = _f64_colmajor(x_raw, (self.n_rows[v], self.n_cols[v]))
         neg = C.c_int(0)
         self._check(self._lib.resnmtf_set_view_raw(self._h, v, _dp(x), C.byref(neg)))
+        return bool(neg.value)
+
+    def set_view_device(self, v: int, tensor, raw: bool = False) -> bool:
+        """Upload a dense view from device memory (``resnmtf_set_view_device``): ``tensor`` is a 2-D floating
+        ``torch.Tensor`` (fp64 / fp32 / fp16 / bf16, any strides) on this engine's GPU; it is read in place, ordered after
+        the work enqueued on torch's current stream of that device, and may be freed on return.  ``raw=False`` takes the
+        values as ``set_view`` does, ``raw=True`` shifts and normalises them on the device as ``set_view_raw`` does
+        (``R/utils.r:416,422``) and returns True when an entry was negative (``R/utils.r:23-25``).  The images,
+        ``data_norms`` and the flag are bit for bit those of ``set_view`` / ``set_view_raw`` of
+        ``tensor.double().cpu().numpy()``."""
+        import torch            # (lazily: nothing else in this module needs it)
+        if not isinstance(tensor, torch.Tensor):
+            raise TypeError("set_view_device takes a torch.Tensor (host data: set_view / set_view_raw)")
+        if tensor.ndim != 2:
+            raise ValueError(f"a tensor view must be 2-D, got {tensor.ndim} dimensions")
+        codes = {torch.float64: _lib.DTYPE_F64, torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16,
+                 torch.bfloat16: _lib.DTYPE_BF16}
+        if tensor.dtype not in codes:
+            raise ValueError(f"a tensor view must be fp64, fp32, fp16 or bf16, got {tensor.dtype}")
+        if tensor.device.type != "cuda" or tensor.device.index != self.device_id:
+            raise ValueError(f"the tensor lives on {tensor.device}, the engine on cuda:{self.device_id}")
+        if tuple(tensor.shape) != (self.n_rows[v], self.n_cols[v]):
+            raise ValueError(f"expected shape {(self.n_rows[v], self.n_cols[v])}, got {tuple(tensor.shape)}")
+        tensor = tensor.detach()
+        neg = C.c_int(0)
+        stream = torch.cuda.current_stream(tensor.device).cuda_stream
+        self._check(self._lib.resnmtf_set_view_device(self._h, v, C.c_void_p(tensor.data_ptr()), codes[tensor.dtype],
+                                                      int(tensor.stride(0)), int(tensor.stride(1)), 1 if raw else 0,
+                                                      C.byref(neg), C.c_void_p(stream)))
         return bool(neg.value)
 
     def set_view_sparse(self, v: int, m, pre_processed: bool = False):
@@ -444,6 +474,20 @@ class Engine:
         f = np.zeros((n, k), order="F"); s = np.zeros((k, k), order="F"); g = np.zeros((m, k), order="F")
         rc = np.zeros((n, k), order="F"); cc = np.zeros((m, k), order="F")
         self._check(self._lib.resnmtf_finalise(self._h, v, _dp(f), _dp(s), _dp(g), _dp(rc), _dp(cc)))
+        return f, s, g, rc, cc
+
+    def finalise_device(self, v: int):
+        """``finalise`` with the five results left on the device (``resnmtf_finalise_device``): fp64 ``torch`` tensors
+        on this engine's GPU, column-major (``torch.empty((k, n)).T``), bitwise what ``finalise`` returns; ordered with
+        torch's current stream of that device."""
+        import torch            # (lazily: nothing else in this module needs it)
+        n, m, k = self.n_rows[v], self.n_cols[v], self.k[v]
+        dev = torch.device("cuda", self.device_id)
+        f, s, g, rc, cc = (torch.empty((cols, rows), dtype=torch.float64, device=dev).T
+                           for rows, cols in ((n, k), (k, k), (m, k), (n, k), (m, k)))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self._check(self._lib.resnmtf_finalise_device(self._h, v, *(C.c_void_p(t.data_ptr()) for t in (f, s, g, rc, cc)),
+                                                      C.c_void_p(stream)))
         return f, s, g, rc, cc
 
     def set_reference_clusters(self, v: int, rc, cc):

@@ -10,7 +10,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import naming
+from . import device_views, naming
 from .engine import Engine
 
 
@@ -40,15 +40,21 @@ def prepare(data, phi, xi, psi, row_names, col_names, *, normalise: bool, symmet
     """``apply_resnmtf``'s steps before the loop: ``give_names`` (``R/main.r:228``; only the shapes of ``data`` are
     read), the shared-name maps (``:230``), the restriction matrices -- symmetrised (``init_rest_mats``, ``:233-235``)
     or, with ``symmetrise=False``, taken as the symmetrised matrices they already are (None = zeros) -- and, with
-    ``normalise``, the non-negativity shift and column normalisation on the host (``check_data``, ``:237``)."""
+    ``normalise``, the non-negativity shift and column normalisation on the host (``check_data``, ``:237``).  A CPU
+    ``torch`` tensor is taken as its NumPy array; a tensor on a GPU is never brought to the host: with ``normalise`` it
+    is wrapped in ``device_views.RawDeviceView`` and pre-processed on the device at its upload."""
     n_v = len(data)
+    data = [device_views.host_or_device(d, f"view {v}") for v, d in enumerate(data)]
     rn, cn = naming.give_names(data, phi, psi, row_names, col_names)
     shared = naming.shared_names(rn), naming.shared_names(cn)
     if symmetrise:
         phi, psi, xi = (naming.init_rest_mats(m, n_v) for m in (phi, psi, xi))
     else:
         phi, psi, xi = (np.zeros((n_v, n_v)) if m is None else np.asarray(m, dtype=np.float64) for m in (phi, psi, xi))
-    return Prepared(naming.check_data(data) if normalise else list(data), rn, cn, phi, xi, psi, *shared)
+    if normalise:
+        data = [device_views.RawDeviceView(d) if device_views.is_tensor(d) else
+                (d if isinstance(d, device_views.RawDeviceView) else naming.check_data([d])[0]) for d in data]
+    return Prepared(list(data), rn, cn, phi, xi, psi, *shared)
 
 
 def pair_table(names, shared=None) -> list:
@@ -156,7 +162,7 @@ def reported_error(errs, n_iters) -> float:
 _INNER_KEYS = ("output_f", "output_s", "output_g", "Error", "All_Error", "bisil", "row_clusters", "col_clusters",
                "lambda", "mu", "spurious", "init", "tag", "extras")
 _DEVICE_DATA_KEYS = ("output_f", "output_s", "output_g", "row_clusters", "col_clusters", "Error", "All_Error", "tag",
-                     "extras", "row_names", "col_names", "init", "lambda", "mu", "data", "spurious_check")
+                     "extras", "row_names", "col_names", "init", "lambda", "mu", "data", "spurious_check", "device_out")
 
 
 def inner_result(output_f, output_s, output_g, errs=None, n_iters=None, *, lam=None, mu=None, device_data: bool = False,
