@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <random>
 #include <string>
 #include <thread>
@@ -240,6 +241,30 @@ hipError_t dev_alloc_zero(T** p, size_t count) {
   if (e != hipSuccess) return e;
   return hipMemset(*p, 0, std::max<size_t>(count, 1) * sizeof(T));
 }
+
+// The owner of a call's transient device memory: what take() hands out is freed when the object goes out of scope, on
+// every path out of the function.  One hipMalloc per take() and nothing kept between calls.  After a failed take() it
+// holds that error (error()), returns nullptr and allocates nothing further, so a run of take() calls is checked once.
+// hipFree synchronises the device: declare a Scratch where it dies after the last stream synchronisation of its function.
+class Scratch {
+ public:
+  Scratch() = default;
+  Scratch(const Scratch&) = delete;
+  Scratch& operator=(const Scratch&) = delete;
+  ~Scratch() { for (void* p : taken_) (void)hipFree(p); }
+  template <class T>
+  T* take(size_t count) {
+    void* p = nullptr;
+    if (err_ == hipSuccess) err_ = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
+    if (err_ != hipSuccess) return nullptr;
+    taken_.push_back(p);
+    return static_cast<T*>(p);
+  }
+  hipError_t error() const { return err_; }
+ private:
+  std::vector<void*> taken_;
+  hipError_t err_ = hipSuccess;
+};
 
 // time_kernels: a pair of events for one launch of the given kind (RESNMTF_TIMED_*), attached to the dispatch itself
 bool take_events(resnmtf_handle* h, int kind, hipEvent_t* e0, hipEvent_t* e1) {
@@ -1537,17 +1562,14 @@ int resnmtf_destroy(resnmtf_handle* h) {
 }
 
 namespace {
-// raw = false: x is already non-negative and column-normalised.  raw = true: make_non_neg_inner +
-// matrix_normalisation (R/utils.r:20-27, 86-88) run on the device, fused into the conversion.
-// Source of the staging image: the host matrix x, or (x == NULL) a pseudo-random permutation of the
-// entries of another view's device copy (shuffle_src, see resnmtf_shuffle_view).
 // fp16 images of an uploaded view: per-view power-of-two scale that puts the largest entry near 2^14
 // relative quantisation error of X below which the guarded mode (x_half = 3) lets the passes use the 16-bit image:
 // F / G move by 0.2 ... 2 x that error (tools/quant_study.py), the bar is 1e-4
 constexpr double kHalfGuard = 3.0e-5;
 int build_half_images(resnmtf_handle* h, ViewState& vs) {
-  double* scratch = nullptr;          // [0] = max entry bits (as unsigned), [1] = sum (x~ - x)^2, [2] = copy of ||X||^2
-  HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&scratch), 3 * sizeof(double)));
+  Scratch sc;
+  double* scratch = sc.take<double>(3);          // [0] = max entry bits (as unsigned), [1] = sum (x~ - x)^2, [2] = copy of ||X||^2
+  if (!scratch) return h->fail_hip("2-byte images (hipMalloc)", sc.error());
   hipError_t e = hipMemsetAsync(scratch, 0, 3 * sizeof(double), h->stream);
   unsigned int bits = 0;
   if (e == hipSuccess) {
@@ -1556,7 +1578,7 @@ int build_half_images(resnmtf_handle* h, ViewState& vs) {
     e = hipMemcpyAsync(&bits, scratch, sizeof(bits), hipMemcpyDeviceToHost, h->stream);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) { (void)hipFree(scratch); return h->fail_hip("2-byte images (max)", e); }
+  if (e != hipSuccess) return h->fail_hip("2-byte images (max)", e);
   float mx;
   std::memcpy(&mx, &bits, sizeof(mx));
   int ex = 0;
@@ -1577,7 +1599,6 @@ int build_half_images(resnmtf_handle* h, ViewState& vs) {
   if (e == hipSuccess) e = hipMemcpyAsync(&host[0], scratch + 1, sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(&host[1], vs.xnorm2, sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  (void)hipFree(scratch);
   if (e != hipSuccess) return h->fail_hip("2-byte images (pack)", e);
   vs.x_relerr = host[1] > 0.0 ? std::sqrt(host[0] / host[1]) : 0.0;
   const bool use = h->opt.x_half == 3 ? vs.x_relerr <= kHalfGuard : true;
@@ -1598,81 +1619,22 @@ int build_half_images(resnmtf_handle* h, ViewState& vs) {
   h->resume_ok = false;
   return RESNMTF_OK;
 }
-struct ShuffleSrc { const float* X32; size_t ldx; unsigned long long seed; const int* rows; const int* cols; };   // rows != NULL: sub-sample
-int upload_view(resnmtf_handle* h, int v, const double* x, bool raw, int* was_negative, const ShuffleSrc* shuffle_src = nullptr) {
-  if (int rc = check_view(h, v)) return rc;
-  if (!x && !shuffle_src) return h->fail(RESNMTF_ERR_INVALID, "x is NULL");
-  ViewState& vs = h->views[v];
-  if (!vs.owned) return h->fail(RESNMTF_ERR_STATE, "set_view on a view this handle does not own");
-  if (vs.sparse)
-    return h->fail(RESNMTF_ERR_INVALID, shuffle_src ? "the destination view is sparse: device-drawn data (shuffle / sub-sample) needs a dense view"
-                                                    : "the view is sparse: upload it with resnmtf_set_view_csc");
-  h->resume_ok = false;
-  HIP_TRY(h, hipSetDevice(h->opt.device_id));
-  if (int rc = sync_both(h)) return rc;
-  const size_t count = (size_t)vs.n * vs.m;
-  double* staging = nullptr;
-  double* partial = nullptr;
-  double* colstat = nullptr;      // [2][m]: shift, colsum; then one int flag
-  const dim3 grid(ceil_div(vs.n, 32), ceil_div(vs.m, 32));
-  const int nparts = grid.x * grid.y;
-  HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&staging), count * sizeof(double)));
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&partial), (size_t)nparts * sizeof(double));
-  if (e == hipSuccess && raw) e = hipMalloc(reinterpret_cast<void**>(&colstat), ((size_t)2 * vs.m + 1) * sizeof(double));
-  if (e != hipSuccess) { (void)hipFree(staging); (void)hipFree(partial); return h->fail_hip("hipMalloc upload buffers", e); }
-  double* shift = raw ? colstat : nullptr;
-  double* colsum = raw ? colstat + vs.m : nullptr;
-  int* neg = raw ? reinterpret_cast<int*>(colstat + 2 * (size_t)vs.m) : nullptr;
-  int neg_host = 0;
-  if (x) e = hipMemcpyAsync(staging, x, count * sizeof(double), hipMemcpyHostToDevice, h->stream);
-  else {
-    if (shuffle_src->rows)
-      hipLaunchKernelGGL(subsample_gather_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream, shuffle_src->X32,
-                         shuffle_src->ldx, shuffle_src->rows, vs.n, shuffle_src->cols, vs.m, staging);
-    else
-      hipLaunchKernelGGL(shuffle_gather_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream, shuffle_src->X32,
-                         shuffle_src->ldx, vs.n, vs.m, shuffle_src->seed, staging);
-    e = hipGetLastError();
-  }
-  unsigned char* line_mask = nullptr;      // device-drawn data: which rows / columns came out all zero
-  std::vector<int> line_counts(2, 0);
-  vs.empty_rows = vs.empty_cols = 0; vs.empty_mask.clear();
-  if (e == hipSuccess && !x) {
-    e = hipMalloc(reinterpret_cast<void**>(&line_mask), (size_t)vs.n + vs.m + 2 * sizeof(int) + 8);
-    if (e == hipSuccess) {
-      int* counts = reinterpret_cast<int*>(line_mask + (((size_t)vs.n + vs.m + 7) / 8) * 8);
-      e = hipMemsetAsync(counts, 0, 2 * sizeof(int), h->stream);
-      hipLaunchKernelGGL(empty_lines_kernel, dim3(ceil_div(vs.n + vs.m, 256)), dim3(256), 0, h->stream, staging, vs.n, vs.m, line_mask, counts);
-      vs.empty_mask.resize((size_t)vs.n + vs.m);
-      if (e == hipSuccess) e = hipMemcpyAsync(vs.empty_mask.data(), line_mask, (size_t)vs.n + vs.m, hipMemcpyDeviceToHost, h->stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(line_counts.data(), counts, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream);
-    }
-  }
-  if (e == hipSuccess) e = hipMemsetAsync(vs.side[SIDE_G].X, 0, vs.side[SIDE_G].x_floats * sizeof(float), h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(vs.side[SIDE_F].X, 0, vs.side[SIDE_F].x_floats * sizeof(float), h->stream);
-  if (e == hipSuccess && raw) e = hipMemsetAsync(neg, 0, sizeof(double), h->stream);
-  if (e == hipSuccess) {
-    if (raw) hipLaunchKernelGGL(column_stats_kernel, dim3(vs.m), dim3(256), 0, h->stream, staging, vs.n, vs.m, shift, colsum, neg);
-    hipLaunchKernelGGL(convert_x_kernel, grid, dim3(256), 0, h->stream, staging, vs.n, vs.m, vs.side[SIDE_G].X, vs.side[SIDE_G].ldx,
-                       vs.side[SIDE_F].X, vs.side[SIDE_F].ldx, partial, shift, colsum);
-    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, h->stream, partial, nparts, vs.xnorm2);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess && raw) e = hipMemcpyAsync(&neg_host, neg, sizeof(int), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  (void)hipFree(staging);
-  (void)hipFree(partial);
-  (void)hipFree(colstat);
-  (void)hipFree(line_mask);
-  if (e != hipSuccess) return h->fail_hip("set_view", e);
-  vs.empty_rows = line_counts[0]; vs.empty_cols = line_counts[1];
-  if (was_negative) *was_negative = neg_host;
-  vs.has_x = true;
-  if (vs.half_capable) return build_half_images(h, vs);
-  return RESNMTF_OK;
-}
-
-// ---- device-resident callers (resnmtf_set_view_device, resnmtf_finalise_device)
+// ---- the dense upload.  A dense view gets its data from a host matrix, from a shuffle or a sub-sample of another view's
+// image (resnmtf_shuffle_view, resnmtf_subsample_view), or from a matrix in the caller's device memory
+// (resnmtf_set_view_device): all of them are upload_dense.  It refuses, zeroes the two f32 images,
+// lets `enqueue` put the kernels of the route on the handle's stream -- they fill the images and one partial of ||X||^2 per
+// 32 x 32 block -- and then sums the partials, reads the flag back and sets the view's state.
+// raw = false: x is already non-negative and column-normalised.  raw = true: make_non_neg_inner +
+// matrix_normalisation (R/utils.r:20-27, 86-88) run on the device, fused into the conversion.
+// Transient device memory: the ceil(n/32) ceil(m/32) block partials and, raw, the 2 m + 1 column statistics, + the route's.
+struct DenseUpload {                  // what upload_dense hands to `enqueue`
+  Scratch& scratch;                   // the route's own transient buffers come from here too
+  dim3 grid;                          // of the convert kernel
+  double* partial;
+  double *shift, *colsum;             // raw: the column statistics and the was_negative flag (else NULL)
+  int* neg;
+  int* line_counts;                   // host [2]: device-drawn data reports its all-zero rows / columns here (and in empty_mask)
+};
 // true when p is device memory of the handle's device; a host pointer makes hipPointerGetAttributes fail (or report host
 // memory, by version): both are "no", and the sticky error is cleared
 bool on_handle_device(resnmtf_handle* h, const void* p) {
@@ -1691,8 +1653,88 @@ hipError_t wait_for_caller(resnmtf_handle* h, void* stream) {
   (void)hipEventDestroy(ev);          // (released once the recorded work completes)
   return e;
 }
-// upload_view without the staging image: the kernels of resnmtf_device_view.hip.inc read the caller's matrix in place.
-// Transient device memory: the ceil(n/32) ceil(m/32) block partials and, raw, the 2 m + 1 column statistics.
+// device_x: the caller's matrix when the route reads device memory (refused unless it is on the handle's device), else NULL
+int upload_dense(resnmtf_handle* h, int v, bool raw, int* was_negative, const void* device_x, const char* what,
+                 const std::function<hipError_t(const DenseUpload&)>& enqueue) {
+  if (int rc = check_view(h, v)) return rc;
+  ViewState& vs = h->views[v];
+  if (!vs.owned) return h->fail(RESNMTF_ERR_STATE, "set_view on a view this handle does not own");
+  if (vs.sparse) return h->fail(RESNMTF_ERR_INVALID, "the view is sparse: upload it with resnmtf_set_view_csc");
+  if (device_x && !on_handle_device(h, device_x))
+    return h->fail(RESNMTF_ERR_INVALID, "x is not device memory of the handle's device (host data: resnmtf_set_view / resnmtf_set_view_raw)");
+  h->resume_ok = false;
+  HIP_TRY(h, hipSetDevice(h->opt.device_id));
+  if (int rc = sync_both(h)) return rc;
+  const dim3 grid(ceil_div(vs.n, 32), ceil_div(vs.m, 32));
+  const int nparts = grid.x * grid.y;
+  int neg_host = 0, line_counts[2] = {0, 0};
+  vs.empty_rows = vs.empty_cols = 0; vs.empty_mask.clear();
+  {      // (the transients, the staging image among them, are gone before build_half_images takes its own)
+    Scratch sc;
+    double* partial = sc.take<double>((size_t)nparts);
+    double* colstat = raw ? sc.take<double>((size_t)2 * vs.m + 1) : nullptr;      // [2][m]: shift, colsum; then one int flag
+    if (sc.error() != hipSuccess) return h->fail_hip("hipMalloc upload buffers", sc.error());
+    int* neg = raw ? reinterpret_cast<int*>(colstat + 2 * (size_t)vs.m) : nullptr;
+    hipError_t e = hipMemsetAsync(vs.side[SIDE_G].X, 0, vs.side[SIDE_G].x_floats * sizeof(float), h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(vs.side[SIDE_F].X, 0, vs.side[SIDE_F].x_floats * sizeof(float), h->stream);
+    if (e == hipSuccess && raw) e = hipMemsetAsync(neg, 0, sizeof(double), h->stream);
+    if (e == hipSuccess) e = enqueue(DenseUpload{sc, grid, partial, colstat, raw ? colstat + vs.m : nullptr, neg, line_counts});
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, h->stream, partial, nparts, vs.xnorm2);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess && raw) e = hipMemcpyAsync(&neg_host, neg, sizeof(int), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return h->fail_hip(what, e);
+  }
+  vs.empty_rows = line_counts[0]; vs.empty_cols = line_counts[1];
+  if (was_negative) *was_negative = neg_host;
+  vs.has_x = true;
+  if (vs.half_capable) return build_half_images(h, vs);
+  return RESNMTF_OK;
+}
+
+// The staged routes: an fp64 image of the view in transient memory (n m doubles), copied from the host matrix x or
+// (x == NULL) drawn from another view's device copy -- a pseudo-random permutation of its entries (resnmtf_shuffle_view)
+// or a sub-sample (rows != NULL) -- and then which rows / columns of the draw came out all zero.
+struct ShuffleSrc { const float* X32; size_t ldx; unsigned long long seed; const int* rows; const int* cols; };   // rows != NULL: sub-sample
+int upload_view(resnmtf_handle* h, int v, const double* x, bool raw, int* was_negative, const ShuffleSrc* shuffle_src = nullptr) {
+  if (int rc = check_view(h, v)) return rc;
+  if (!x && !shuffle_src) return h->fail(RESNMTF_ERR_INVALID, "x is NULL");
+  ViewState& vs = h->views[v];
+  return upload_dense(h, v, raw, was_negative, nullptr, "set_view", [&](const DenseUpload& u) {
+    const size_t count = (size_t)vs.n * vs.m;
+    double* staging = u.scratch.take<double>(count);
+    unsigned char* line_mask = x ? nullptr : u.scratch.take<unsigned char>((size_t)vs.n + vs.m + 2 * sizeof(int) + 8);
+    if (u.scratch.error() != hipSuccess) return u.scratch.error();
+    hipError_t e = hipSuccess;
+    if (x) e = hipMemcpyAsync(staging, x, count * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    else {
+      if (shuffle_src->rows)
+        hipLaunchKernelGGL(subsample_gather_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream, shuffle_src->X32,
+                           shuffle_src->ldx, shuffle_src->rows, vs.n, shuffle_src->cols, vs.m, staging);
+      else
+        hipLaunchKernelGGL(shuffle_gather_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream, shuffle_src->X32,
+                           shuffle_src->ldx, vs.n, vs.m, shuffle_src->seed, staging);
+      e = hipGetLastError();
+      int* counts = reinterpret_cast<int*>(line_mask + (((size_t)vs.n + vs.m + 7) / 8) * 8);
+      if (e == hipSuccess) e = hipMemsetAsync(counts, 0, 2 * sizeof(int), h->stream);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(empty_lines_kernel, dim3(ceil_div(vs.n + vs.m, 256)), dim3(256), 0, h->stream, staging, vs.n, vs.m, line_mask, counts);
+      vs.empty_mask.resize((size_t)vs.n + vs.m);
+      e = hipMemcpyAsync(vs.empty_mask.data(), line_mask, (size_t)vs.n + vs.m, hipMemcpyDeviceToHost, h->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(u.line_counts, counts, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream);
+    }
+    if (e != hipSuccess) return e;
+    if (raw) hipLaunchKernelGGL(column_stats_kernel, dim3(vs.m), dim3(256), 0, h->stream, staging, vs.n, vs.m, u.shift, u.colsum, u.neg);
+    hipLaunchKernelGGL(convert_x_kernel, u.grid, dim3(256), 0, h->stream, staging, vs.n, vs.m, vs.side[SIDE_G].X, vs.side[SIDE_G].ldx,
+                       vs.side[SIDE_F].X, vs.side[SIDE_F].ldx, u.partial, u.shift, u.colsum);
+    return hipGetLastError();
+  });
+}
+
+// The device route (resnmtf_set_view_device): no staging image, the kernels of resnmtf_device_view.hip.inc read the
+// caller's matrix in place once the handle's stream has waited for the caller's.
 int upload_view_device(resnmtf_handle* h, int v, const void* x, int dtype, long long rs, long long cs, bool raw, int* was_negative,
                        void* stream) {
   if (int rc = check_view(h, v)) return rc;
@@ -1701,53 +1743,23 @@ int upload_view_device(resnmtf_handle* h, int v, const void* x, int dtype, long 
     return h->fail(RESNMTF_ERR_INVALID, "unknown dtype: one of RESNMTF_DTYPE_F64 / _F32 / _F16 / _BF16");
   if (rs < 0 || cs < 0) return h->fail(RESNMTF_ERR_INVALID, "negative strides are not supported");
   ViewState& vs = h->views[v];
-  if (!vs.owned) return h->fail(RESNMTF_ERR_STATE, "set_view on a view this handle does not own");
-  if (vs.sparse) return h->fail(RESNMTF_ERR_INVALID, "the view is sparse: upload it with resnmtf_set_view_csc");
-  if (!on_handle_device(h, x)) return h->fail(RESNMTF_ERR_INVALID, "x is not device memory of the handle's device (host data: resnmtf_set_view / resnmtf_set_view_raw)");
-  h->resume_ok = false;
-  HIP_TRY(h, hipSetDevice(h->opt.device_id));
-  if (int rc = sync_both(h)) return rc;
-  double* partial = nullptr;
-  double* colstat = nullptr;      // [2][m]: shift, colsum; then one int flag
-  const dim3 grid(ceil_div(vs.n, 32), ceil_div(vs.m, 32));
-  const int nparts = grid.x * grid.y;
-  HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&partial), (size_t)nparts * sizeof(double)));
-  hipError_t e = raw ? hipMalloc(reinterpret_cast<void**>(&colstat), ((size_t)2 * vs.m + 1) * sizeof(double)) : hipSuccess;
-  if (e != hipSuccess) { (void)hipFree(partial); return h->fail_hip("hipMalloc upload buffers", e); }
-  double* shift = raw ? colstat : nullptr;
-  double* colsum = raw ? colstat + vs.m : nullptr;
-  int* neg = raw ? reinterpret_cast<int*>(colstat + 2 * (size_t)vs.m) : nullptr;
-  int neg_host = 0;
-  vs.empty_rows = vs.empty_cols = 0; vs.empty_mask.clear();
-  e = wait_for_caller(h, stream);
-  if (e == hipSuccess) e = hipMemsetAsync(vs.side[SIDE_G].X, 0, vs.side[SIDE_G].x_floats * sizeof(float), h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(vs.side[SIDE_F].X, 0, vs.side[SIDE_F].x_floats * sizeof(float), h->stream);
-  if (e == hipSuccess && raw) e = hipMemsetAsync(neg, 0, sizeof(double), h->stream);
-  if (e == hipSuccess) {
+  return upload_dense(h, v, raw, was_negative, x, "set_view_device", [&](const DenseUpload& u) {
+    const hipError_t e = wait_for_caller(h, stream);
+    if (e != hipSuccess) return e;
     const bool rows = cs == 1 && rs != 1;             // a row-major source: read along c
     pick_int<RESNMTF_DTYPE_F64, RESNMTF_DTYPE_F32, RESNMTF_DTYPE_F16, RESNMTF_DTYPE_BF16>(dtype, [&](auto dt) {
       constexpr int DT = decltype(dt)::value;
       if (raw) {
-        if (rows) hipLaunchKernelGGL(device_column_stats_rows_kernel<DT>, dim3(ceil_div(vs.m, 32)), dim3(256), 0, h->stream, x, rs, vs.n, vs.m, shift, colsum, neg);
-        else hipLaunchKernelGGL(device_column_stats_kernel<DT>, dim3(vs.m), dim3(256), 0, h->stream, x, rs, cs, vs.n, vs.m, shift, colsum, neg);
+        if (rows) hipLaunchKernelGGL(device_column_stats_rows_kernel<DT>, dim3(ceil_div(vs.m, 32)), dim3(256), 0, h->stream, x, rs, vs.n, vs.m, u.shift, u.colsum, u.neg);
+        else hipLaunchKernelGGL(device_column_stats_kernel<DT>, dim3(vs.m), dim3(256), 0, h->stream, x, rs, cs, vs.n, vs.m, u.shift, u.colsum, u.neg);
       }
-      if (rows) hipLaunchKernelGGL((device_convert_x_kernel<DT, true>), grid, dim3(256), 0, h->stream, x, rs, cs, vs.n, vs.m, vs.side[SIDE_G].X,
-                                   vs.side[SIDE_G].ldx, vs.side[SIDE_F].X, vs.side[SIDE_F].ldx, partial, shift, colsum);
-      else hipLaunchKernelGGL((device_convert_x_kernel<DT, false>), grid, dim3(256), 0, h->stream, x, rs, cs, vs.n, vs.m, vs.side[SIDE_G].X,
-                              vs.side[SIDE_G].ldx, vs.side[SIDE_F].X, vs.side[SIDE_F].ldx, partial, shift, colsum);
+      if (rows) hipLaunchKernelGGL((device_convert_x_kernel<DT, true>), u.grid, dim3(256), 0, h->stream, x, rs, cs, vs.n, vs.m, vs.side[SIDE_G].X,
+                                   vs.side[SIDE_G].ldx, vs.side[SIDE_F].X, vs.side[SIDE_F].ldx, u.partial, u.shift, u.colsum);
+      else hipLaunchKernelGGL((device_convert_x_kernel<DT, false>), u.grid, dim3(256), 0, h->stream, x, rs, cs, vs.n, vs.m, vs.side[SIDE_G].X,
+                              vs.side[SIDE_G].ldx, vs.side[SIDE_F].X, vs.side[SIDE_F].ldx, u.partial, u.shift, u.colsum);
     });
-    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, h->stream, partial, nparts, vs.xnorm2);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess && raw) e = hipMemcpyAsync(&neg_host, neg, sizeof(int), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  (void)hipFree(partial);
-  (void)hipFree(colstat);
-  if (e != hipSuccess) return h->fail_hip("set_view_device", e);
-  if (was_negative) *was_negative = neg_host;
-  vs.has_x = true;
-  if (vs.half_capable) return build_half_images(h, vs);
-  return RESNMTF_OK;
+    return hipGetLastError();
+  });
 }
 }  // namespace
 
@@ -1808,9 +1820,10 @@ void plan_sparse(const std::vector<long long>& ptr, int lines, int groups, int n
 }
 int spmm_groups_host(int KP) { return KP <= 16 ? 16 : (KP <= 32 ? 8 : 4); }   // = spmm_groups (kernel side)
 
-// The tail every sparse upload shares (resnmtf_set_view_csc, finish_sparse_build, resnmtf_copy_view_sparse): the work split of the two
-// passes planned from the host copies of the line pointers, the block lists (re)allocated and their upload enqueued on
-// the handle's stream (the caller synchronises while `pl` is alive), then -- commit_sparse_upload -- the view's state.
+// The tail every sparse upload shares (resnmtf_set_view_csc, finish_sparse_build, resnmtf_copy_view_sparse) is
+// plan_and_commit below.  Its pieces: the work split of the two passes planned from the host copies of the line pointers,
+// the block lists (re)allocated and their upload enqueued on the handle's stream (synchronised while `pl` is alive), then
+// -- commit_sparse_upload -- the view's state.
 struct SparsePlan {
   std::vector<int> bxg, bxtf;
   int ns_xg = 1, ns_xtf = 1, nb_xg = 0, nb_xtf = 0;
@@ -1841,6 +1854,17 @@ void commit_sparse_upload(resnmtf_handle* h, ViewState& vs, const SparsePlan& pl
   vs.side[SIDE_F].nsplit = pl.ns_xg; vs.side[SIDE_G].nsplit = pl.ns_xtf;
   vs.has_x = true;
   h->prepared = false;          // the slab count of the updates follows the upload
+}
+// `e`: the status of what the caller enqueued to fill the view's arrays.  The first synchronisation completes that work
+// (and puts rp / cp on the host where the caller read them back), the second one the upload of the block lists.
+hipError_t plan_and_commit(resnmtf_handle* h, ViewState& vs, const std::vector<long long>& rp, const std::vector<long long>& cp, long long nnz,
+                           hipError_t e) {
+  SparsePlan pl;
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e == hipSuccess) e = upload_sparse_plan(h, vs, rp, cp, pl);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e == hipSuccess) commit_sparse_upload(h, vs, pl, nnz);
+  return e;
 }
 }  // namespace
 
@@ -1895,13 +1919,11 @@ int resnmtf_set_view_csc(resnmtf_handle* h, int v, const long long* col_ptr, con
       }
   }
   // ---- device
-  double* v64 = nullptr;
-  long long* dperm = nullptr;
-  double* sq = nullptr;
-  SparsePlan pl;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&v64), std::max<size_t>((size_t)nnz, 1) * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dperm), std::max<size_t>((size_t)nnz, 1) * sizeof(long long));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sq), (size_t)m * sizeof(double));
+  Scratch sc;
+  double* v64 = sc.take<double>((size_t)nnz);
+  long long* dperm = sc.take<long long>((size_t)nnz);
+  double* sq = sc.take<double>((size_t)m);
+  hipError_t e = sc.error();
   auto up = [&](void* dst, const void* src, size_t bytes) {
     if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream);
   };
@@ -1911,7 +1933,6 @@ int resnmtf_set_view_csc(resnmtf_handle* h, int v, const long long* col_ptr, con
   up(vs.side[SIDE_F].sp_idx, ci.data(), ci.size() * sizeof(int));
   up(v64, values, (size_t)nnz * sizeof(double));
   up(dperm, perm.data(), perm.size() * sizeof(long long));
-  if (e == hipSuccess) e = upload_sparse_plan(h, vs, rp, cp, pl);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(csc_normalise_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, h->stream, vs.side[SIDE_G].sp_ptr, v64, m, pre_processed ? 0 : 1,
                        vs.side[SIDE_G].sp_val, sq);
@@ -1920,11 +1941,9 @@ int resnmtf_set_view_csc(resnmtf_handle* h, int v, const long long* col_ptr, con
     hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, h->stream, sq, m, vs.xnorm2);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);      // (host vectors go out of scope)
-  (void)hipFree(v64); (void)hipFree(dperm); (void)hipFree(sq);
+  e = plan_and_commit(h, vs, rp, cp, nnz, e);      // (synchronises: the host vectors go out of scope)
   if (e != hipSuccess) return h->fail_hip("set_view_csc", e);
   vs.empty_rows = vs.empty_cols = 0; vs.empty_mask.clear();
-  commit_sparse_upload(h, vs, pl, nnz);
   return RESNMTF_OK;
 }
 
@@ -1938,27 +1957,86 @@ int resnmtf_view_storage(resnmtf_handle* h, int v, int* is_sparse, long long* nn
 }
 
 // ---- view data without a host round trip (the k sweep re-uses one upload, the shuffles of
-// spurious-bicluster removal are drawn on the device)
-static int check_view_pair(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src) {
-  if (int rc = check_view(dst, v)) return rc;
-  if (!src || v_src < 0 || v_src >= src->V) return dst->fail(RESNMTF_ERR_INVALID, "bad source handle / view");
-  const ViewState& a = dst->views[v];
+// spurious-bicluster removal are drawn on the device).  Every entry that fills a view of `dst` from a view of `src` --
+// copy, shuffle and sub-sample, dense and sparse, and the count of a sparse sub-sample -- is refused by check_view_pair
+// and starts its device work with begin_view_route.
+namespace {
+struct PairNeeds {
+  const char* what;          // the entry's name: it heads every message
+  bool sparse;               // the entry works on sparse views (else on dense ones) ...
+  const char* other_entry;   // ... and this is what the message for a view of the other kind says in brackets
+  bool same_shape;           // copy and shuffle; a sub-sample's shape is that of its index lists
+  bool holds_source;         // the destination's nnz capacity must hold the source's stored entries
+  bool has_dst = true;       // false: resnmtf_subsample_count_sparse, the source half alone (messages go to `dst`)
+};
+// The checks, in one order for every entry: destination view index, source handle NULL, source view index, destination
+// kind, source kind, destination owned, source owned, source uploaded, shape, device, capacity.
+int check_view_pair(resnmtf_handle* dst, int v, const resnmtf_handle* src, int v_src, const PairNeeds& need) {
+  if (!dst) return RESNMTF_ERR_INVALID;
+  if (need.has_dst)
+    if (int rc = check_view(dst, v)) return rc;
+  const std::string w = std::string(need.what) + ": ";
+  const std::string other = std::string(need.sparse ? "dense (" : "sparse (") + need.other_entry + ")";
+  if (!src) return dst->fail(RESNMTF_ERR_INVALID, w + "the source handle is NULL");
+  if (v_src < 0 || v_src >= src->V) return dst->fail(RESNMTF_ERR_INVALID, w + "bad source view");
+  const ViewState* a = need.has_dst ? &dst->views[v] : nullptr;
   const ViewState& b = src->views[v_src];
-  if (!a.owned || !b.owned || !b.has_x) return dst->fail(RESNMTF_ERR_STATE, "both views must be owned and the source uploaded");
-  if (a.sparse || b.sparse) return dst->fail(RESNMTF_ERR_INVALID, "copy / shuffle of a sparse view is not supported (it would densify it)");
-  if (a.n != b.n || a.m != b.m) return dst->fail(RESNMTF_ERR_INVALID, "views differ in shape");
-  if (dst->opt.device_id != src->opt.device_id) return dst->fail(RESNMTF_ERR_INVALID, "handles live on different devices");
+  if (a && a->sparse != need.sparse) return dst->fail(RESNMTF_ERR_INVALID, w + "the destination view is " + other);
+  if (b.sparse != need.sparse) return dst->fail(RESNMTF_ERR_INVALID, w + "the source view is " + other);
+  if (a && !a->owned) return dst->fail(RESNMTF_ERR_STATE, w + "the destination view is not owned");
+  if (!b.owned) return dst->fail(RESNMTF_ERR_STATE, w + "the source view is not owned");
+  if (!b.has_x) return dst->fail(RESNMTF_ERR_STATE, w + "the source view has not been uploaded");
+  if (a && need.same_shape && (a->n != b.n || a->m != b.m)) return dst->fail(RESNMTF_ERR_INVALID, w + "views differ in shape");
+  if (dst->opt.device_id != src->opt.device_id) return dst->fail(RESNMTF_ERR_INVALID, w + "handles live on different devices");
+  if (a && need.holds_source && b.nnz > a->nnz_cap)
+    return dst->fail(RESNMTF_ERR_INVALID, w + "the source holds " + std::to_string(b.nnz) + " stored entries, above the destination's nnz capacity " +
+                     std::to_string(a->nnz_cap));
   return RESNMTF_OK;
 }
+// What follows every successful check: the device, the source's stream drained (its view is complete), then dst's own.
+int begin_view_route(resnmtf_handle* dst, const resnmtf_handle* src) {
+  HIP_TRY(dst, hipSetDevice(dst->opt.device_id));
+  HIP_TRY(dst, hipStreamSynchronize(src->stream));
+  return sync_both(dst);
+}
+constexpr PairNeeds kCopyView{"copy_view", false, "resnmtf_copy_view_sparse copies sparse views", true, false};
+constexpr PairNeeds kShuffleView{"shuffle_view", false, "resnmtf_shuffle_view_sparse shuffles sparse views", true, false};
+constexpr PairNeeds kSubsampleView{"subsample_view", false, "resnmtf_subsample_view_sparse sub-samples sparse views", false, false};
+constexpr PairNeeds kCopySparse{"copy_view_sparse", true, "resnmtf_copy_view copies dense views", true, true};
+constexpr PairNeeds kShuffleSparse{"shuffle_view_sparse", true, "resnmtf_shuffle_view shuffles dense views", true, true};
+constexpr PairNeeds kSubsampleSparse{"subsample_view_sparse", true, "resnmtf_subsample_view sub-samples dense views", false, false};
+constexpr PairNeeds kSubsampleCount{"subsample_count_sparse", true, "resnmtf_subsample_view sub-samples dense views", false, false, false};
+
+// The index lists of a sub-sample, checked on the host: in range and, `distinct`, free of repeats (the reference samples
+// without replacement, and a repeated row has no inverse map: the sparse route; the dense gather takes repeats).  `h`
+// takes the refusal's text.
+int check_sample_lists(resnmtf_handle* h, const char* what, const ViewState& b, int n_dst, const int* rows, int m_dst, const int* cols,
+                       bool distinct) {
+  const std::string w = std::string(what) + ": ";
+  std::vector<unsigned char> seen((size_t)std::max(b.n, b.m), 0);
+  for (int i = 0; i < n_dst; ++i) {
+    if (rows[i] < 0 || rows[i] >= b.n) return h->fail(RESNMTF_ERR_INVALID, w + "row index out of range");
+    if (distinct && seen[(size_t)rows[i]])
+      return h->fail(RESNMTF_ERR_INVALID, w + "row index " + std::to_string(rows[i]) + " occurs twice (sub-samples are drawn without replacement)");
+    seen[(size_t)rows[i]] = 1;
+  }
+  std::fill(seen.begin(), seen.end(), 0);
+  for (int j = 0; j < m_dst; ++j) {
+    if (cols[j] < 0 || cols[j] >= b.m) return h->fail(RESNMTF_ERR_INVALID, w + "column index out of range");
+    if (distinct && seen[(size_t)cols[j]])
+      return h->fail(RESNMTF_ERR_INVALID, w + "column index " + std::to_string(cols[j]) + " occurs twice (sub-samples are drawn without replacement)");
+    seen[(size_t)cols[j]] = 1;
+  }
+  return RESNMTF_OK;
+}
+}  // namespace
 
 int resnmtf_copy_view(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src) {
-  if (int rc = check_view_pair(dst, v, src, v_src)) return rc;
+  if (int rc = check_view_pair(dst, v, src, v_src, kCopyView)) return rc;
   ViewState& a = dst->views[v];
   const ViewState& b = src->views[v_src];
   dst->resume_ok = false;
-  HIP_TRY(dst, hipSetDevice(dst->opt.device_id));
-  HIP_TRY(dst, hipStreamSynchronize(src->stream));
-  if (int rc = sync_both(dst)) return rc;
+  if (int rc = begin_view_route(dst, src)) return rc;
   // same shape and options decide the same pitches; guard anyway
   if (a.side[SIDE_G].ldx != b.side[SIDE_G].ldx || a.side[SIDE_F].ldx != b.side[SIDE_F].ldx) return dst->fail(RESNMTF_ERR_INVALID, "views differ in device layout (no_pitch_pad)");
   HIP_TRY(dst, hipMemcpyAsync(a.side[SIDE_G].X, b.side[SIDE_G].X, a.side[SIDE_G].x_floats * sizeof(float), hipMemcpyDeviceToDevice, dst->stream));
@@ -1971,42 +2049,48 @@ int resnmtf_copy_view(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src
 }
 
 int resnmtf_shuffle_view(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src, unsigned long long seed, int normalise) {
-  if (int rc = check_view_pair(dst, v, src, v_src)) return rc;
+  if (int rc = check_view_pair(dst, v, src, v_src, kShuffleView)) return rc;
   const ViewState& b = src->views[v_src];
-  HIP_TRY(dst, hipSetDevice(dst->opt.device_id));
-  HIP_TRY(dst, hipStreamSynchronize(src->stream));
+  if (int rc = begin_view_route(dst, src)) return rc;
   const ShuffleSrc sh{b.side[SIDE_G].X, b.side[SIDE_G].ldx, seed, nullptr, nullptr};
   return upload_view(dst, v, nullptr, normalise != 0, nullptr, &sh);
+}
+
+int resnmtf_subsample_view(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src, const int* rows, const int* cols) {
+  if (int rc = check_view_pair(dst, v, src, v_src, kSubsampleView)) return rc;
+  if (!rows || !cols) return dst->fail(RESNMTF_ERR_INVALID, "subsample_view: rows / cols are NULL");
+  const ViewState& a = dst->views[v];
+  const ViewState& b = src->views[v_src];
+  if (int rc = check_sample_lists(dst, "subsample_view", b, a.n, rows, a.m, cols, false)) return rc;
+  if (int rc = begin_view_route(dst, src)) return rc;
+  Scratch sc;
+  int* idx = sc.take<int>((size_t)a.n + a.m);
+  hipError_t e = sc.error();
+  if (e == hipSuccess) e = hipMemcpy(idx, rows, (size_t)a.n * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(idx + a.n, cols, (size_t)a.m * sizeof(int), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return dst->fail_hip("subsample_view", e);
+  const ShuffleSrc sh{b.side[SIDE_G].X, b.side[SIDE_G].ldx, 0ull, idx, idx + a.n};
+  return upload_view(dst, v, nullptr, false, nullptr, &sh);      // sub-samples are NOT re-normalised (Appendix B11)
 }
 
 // ---- sparse views built on the device from (destination position, value) pairs: the shuffle and the sub-sample
 namespace {
 // The transient device memory of one such build: five 8-byte arrays of nnz (two key buffers, the fp64 values, two payload
-// buffers) + rocPRIM's histograms, the per-column squares and the line masks.  Freed with the object.
+// buffers) + rocPRIM's histograms, the per-column squares and the line masks, all taken from the caller's Scratch.
 struct SparseBuild {
-  unsigned long long* key[2] = {nullptr, nullptr};
-  long long* pay[3] = {nullptr, nullptr, nullptr};       // 8-byte payloads: the fp64 values (first sort), CSC positions (second)
-  double* sq = nullptr;
-  unsigned char* line_mask = nullptr;
-  void* tmp = nullptr;
-  hipError_t alloc(long long nnz, int n, int m) {
-    const size_t cnt = std::max<size_t>((size_t)nnz, 1);
-    hipError_t e = hipSuccess;
-    for (auto& p : key) if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p), cnt * sizeof(unsigned long long));
-    for (auto& p : pay) if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p), cnt * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sq), (size_t)m * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&line_mask), (size_t)n + m + 2 * sizeof(int) + 8);
-    return e;
-  }
-  ~SparseBuild() {
-    for (auto p : key) (void)hipFree(p);
-    for (auto p : pay) (void)hipFree(p);
-    (void)hipFree(sq); (void)hipFree(line_mask); (void)hipFree(tmp);
-  }
-  SparseBuild() = default;
-  SparseBuild(const SparseBuild&) = delete;
-  SparseBuild& operator=(const SparseBuild&) = delete;
+  unsigned long long* key[2];
+  long long* pay[3];             // 8-byte payloads: the fp64 values (first sort), CSC positions (second)
+  double* sq;
+  unsigned char* line_mask;
 };
+SparseBuild take_sparse_build(Scratch& sc, long long nnz, int n, int m) {
+  SparseBuild sb{};
+  for (auto& p : sb.key) p = sc.take<unsigned long long>((size_t)nnz);
+  for (auto& p : sb.pay) p = sc.take<long long>((size_t)nnz);
+  sb.sq = sc.take<double>((size_t)m);
+  sb.line_mask = sc.take<unsigned char>((size_t)n + m + 2 * sizeof(int) + 8);
+  return sb;
+}
 
 // The tail resnmtf_shuffle_view_sparse and resnmtf_subsample_view_sparse share.  On entry sb.key[0][0 .. nnz) holds the
 // column-major destination position c' n + r' of every entry (distinct, any order) and sb.pay[0] its value as fp64, both
@@ -2014,12 +2098,12 @@ struct SparseBuild {
 // so the sorted order is unique and every correct sort gives the same bits); sorted by r' m + c' they are the CSR; then
 // the masks of the lines without an entry > 0, the values (normalised or as they are), data_norms, the plan of the
 // passes and the view's state.  nnz = 0: zero pointers, every line empty, nothing of size zero launched.
-int finish_sparse_build(resnmtf_handle* dst, ViewState& a, SparseBuild& sb, long long nnz, int normalise, hipError_t e, const char* what) {
+int finish_sparse_build(resnmtf_handle* dst, ViewState& a, Scratch& sc, const SparseBuild& sb, long long nnz, int normalise, hipError_t e,
+                        const char* what) {
   const int n = a.n, m = a.m;
   hipStream_t st = dst->stream;
   std::vector<long long> cp((size_t)m + 1, 0), rp((size_t)n + 1, 0);
   std::vector<int> line_counts(2, 0);
-  SparsePlan pl;
   a.empty_rows = a.empty_cols = 0; a.empty_mask.assign((size_t)n + m, 1);
   const double* v64 = reinterpret_cast<const double*>(sb.pay[0]);
   if (e == hipSuccess && nnz == 0) {          // every line empty: zero pointers, nothing of size zero launched
@@ -2041,8 +2125,9 @@ int finish_sparse_build(resnmtf_handle* dst, ViewState& a, SparseBuild& sb, long
     rocprim::double_buffer<long long> pb(sb.pay[1], sb.pay[2]);
     if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, tmp_bytes2, kb2, pb, (size_t)nnz, 0u, end_bit, st);
     tmp_bytes = std::max<size_t>(std::max(tmp_bytes, tmp_bytes2), 8);
-    if (e == hipSuccess) e = hipMalloc(&sb.tmp, tmp_bytes);
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(sb.tmp, tmp_bytes, kb, vb, (size_t)nnz, 0u, end_bit, st);
+    void* tmp = e == hipSuccess ? sc.take<char>(tmp_bytes) : nullptr;
+    if (e == hipSuccess) e = sc.error();
+    if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kb, vb, (size_t)nnz, 0u, end_bit, st);
     if (e == hipSuccess) {
       v64 = vb.current();
       hipLaunchKernelGGL(sorted_lines_kernel, dim3(grid), dim3(256), 0, st, kb.current(), nnz, (unsigned long long)n, m, a.side[SIDE_G].sp_ptr, a.side[SIDE_G].sp_idx);
@@ -2052,7 +2137,7 @@ int finish_sparse_build(resnmtf_handle* dst, ViewState& a, SparseBuild& sb, long
       hipLaunchKernelGGL(sparse_shuffle_csr_keys_kernel, dim3(grid), dim3(256), 0, st, kb.current(), nnz, n, m, kb2.current(), pb.current());
       e = hipGetLastError();
     }
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(sb.tmp, tmp_bytes, kb2, pb, (size_t)nnz, 0u, end_bit, st);
+    if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kb2, pb, (size_t)nnz, 0u, end_bit, st);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(sorted_lines_kernel, dim3(grid), dim3(256), 0, st, kb2.current(), nnz, (unsigned long long)m, n, a.side[SIDE_F].sp_ptr, a.side[SIDE_F].sp_idx);
       int* counts = reinterpret_cast<int*>(sb.line_mask + (((size_t)n + m + 7) / 8) * 8);
@@ -2079,70 +2164,42 @@ int finish_sparse_build(resnmtf_handle* dst, ViewState& a, SparseBuild& sb, long
     hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, st, sb.sq, m, a.xnorm2);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipStreamSynchronize(st);             // the line pointers are on the host: plan the passes
-  if (e == hipSuccess) e = upload_sparse_plan(dst, a, rp, cp, pl);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  e = plan_and_commit(dst, a, rp, cp, nnz, e);                   // the line pointers are on the host: plan the passes
   if (e != hipSuccess) { a.empty_mask.clear(); return dst->fail_hip(what, e); }
   a.empty_rows = line_counts[0]; a.empty_cols = line_counts[1];
-  commit_sparse_upload(dst, a, pl, nnz);
-  return RESNMTF_OK;
-}
-
-// The index lists of a sub-sample, checked on the host: in range and free of repeats (the reference samples without
-// replacement, and a repeated row has no inverse map).  `h` takes the refusal's text.
-int check_sample_lists(resnmtf_handle* h, const char* what, const ViewState& b, int n_dst, const int* rows, int m_dst, const int* cols) {
-  const std::string w = std::string(what) + ": ";
-  std::vector<unsigned char> seen((size_t)std::max(b.n, b.m), 0);
-  for (int i = 0; i < n_dst; ++i) {
-    if (rows[i] < 0 || rows[i] >= b.n) return h->fail(RESNMTF_ERR_INVALID, w + "row index out of range");
-    if (seen[(size_t)rows[i]])
-      return h->fail(RESNMTF_ERR_INVALID, w + "row index " + std::to_string(rows[i]) + " occurs twice (sub-samples are drawn without replacement)");
-    seen[(size_t)rows[i]] = 1;
-  }
-  std::fill(seen.begin(), seen.end(), 0);
-  for (int j = 0; j < m_dst; ++j) {
-    if (cols[j] < 0 || cols[j] >= b.m) return h->fail(RESNMTF_ERR_INVALID, w + "column index out of range");
-    if (seen[(size_t)cols[j]])
-      return h->fail(RESNMTF_ERR_INVALID, w + "column index " + std::to_string(cols[j]) + " occurs twice (sub-samples are drawn without replacement)");
-    seen[(size_t)cols[j]] = 1;
-  }
   return RESNMTF_OK;
 }
 
 // The counting half of a sub-sample of source view b (resnmtf_sparse_subsample.hip.inc steps 1 and 2) on stream st: the
 // lists and the inverse row map on the device, the kept entries per destination column and their exclusive scan cp, the
-// total back on the host.  Transient: 4 (n' + m' + n_src) + 16 (m' + 1) bytes + rocPRIM's scan storage.
+// total back on the host.  Transient: 4 (n' + m' + n_src) + 16 (m' + 1) bytes + rocPRIM's scan storage, from `sc`.
 struct SubsampleMap {
   int* idx = nullptr;            // rows [n_dst], then cols [m_dst]
   int* inv_row = nullptr;        // [n_src]
-  long long* counts = nullptr;   // [m_dst + 1]
   long long* cp = nullptr;       // [m_dst + 1]
-  void* tmp = nullptr;
-  ~SubsampleMap() { (void)hipFree(idx); (void)hipFree(inv_row); (void)hipFree(counts); (void)hipFree(cp); (void)hipFree(tmp); }
-  SubsampleMap() = default;
-  SubsampleMap(const SubsampleMap&) = delete;
-  SubsampleMap& operator=(const SubsampleMap&) = delete;
 };
-hipError_t subsample_count(hipStream_t st, const ViewState& b, int n_dst, const int* rows, int m_dst, const int* cols, SubsampleMap& sm,
-                           long long* total) {
+hipError_t subsample_count(hipStream_t st, Scratch& sc, const ViewState& b, int n_dst, const int* rows, int m_dst, const int* cols,
+                           SubsampleMap& sm, long long* total) {
   *total = 0;
   if (b.nnz == 0) return hipSuccess;                      // nothing stored, nothing kept: no launch
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&sm.idx), ((size_t)n_dst + m_dst) * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sm.inv_row), (size_t)b.n * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sm.counts), ((size_t)m_dst + 1) * sizeof(long long));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sm.cp), ((size_t)m_dst + 1) * sizeof(long long));
+  sm.idx = sc.take<int>((size_t)n_dst + m_dst);
+  sm.inv_row = sc.take<int>((size_t)b.n);
+  long long* counts = sc.take<long long>((size_t)m_dst + 1);
+  sm.cp = sc.take<long long>((size_t)m_dst + 1);
+  hipError_t e = sc.error();
   if (e == hipSuccess) e = hipMemcpyAsync(sm.idx, rows, (size_t)n_dst * sizeof(int), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(sm.idx + n_dst, cols, (size_t)m_dst * sizeof(int), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemsetAsync(sm.inv_row, 0xFF, (size_t)b.n * sizeof(int), st);       // every row -1: not kept
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(sparse_subsample_inverse_kernel, dim3(ceil_div(n_dst, 256)), dim3(256), 0, st, sm.idx, n_dst, sm.inv_row);
   hipLaunchKernelGGL(sparse_subsample_count_kernel, dim3(ceil_div(m_dst + 1, 4)), dim3(256), 0, st, b.side[SIDE_G].sp_ptr, b.side[SIDE_G].sp_idx,
-                     sm.idx + n_dst, m_dst, sm.inv_row, sm.counts);
+                     sm.idx + n_dst, m_dst, sm.inv_row, counts);
   e = hipGetLastError();
   size_t tmp_bytes = 0;
-  if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, tmp_bytes, sm.counts, sm.cp, 0LL, (size_t)m_dst + 1, rocprim::plus<long long>(), st);
-  if (e == hipSuccess) e = hipMalloc(&sm.tmp, std::max<size_t>(tmp_bytes, 8));
-  if (e == hipSuccess) e = rocprim::exclusive_scan(sm.tmp, tmp_bytes, sm.counts, sm.cp, 0LL, (size_t)m_dst + 1, rocprim::plus<long long>(), st);
+  if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, tmp_bytes, counts, sm.cp, 0LL, (size_t)m_dst + 1, rocprim::plus<long long>(), st);
+  void* tmp = e == hipSuccess ? sc.take<char>(std::max<size_t>(tmp_bytes, 8)) : nullptr;
+  if (e == hipSuccess) e = sc.error();
+  if (e == hipSuccess) e = rocprim::exclusive_scan(tmp, tmp_bytes, counts, sm.cp, 0LL, (size_t)m_dst + 1, rocprim::plus<long long>(), st);
   if (e == hipSuccess) e = hipMemcpyAsync(total, sm.cp + m_dst, sizeof(long long), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   return e;
@@ -2153,61 +2210,37 @@ hipError_t subsample_count(hipStream_t st, const ViewState& b, int n_dst, const 
 // of the densified source, built from the stored entries alone (resnmtf_sparse_shuffle.hip.inc).  Transient device memory:
 // SparseBuild's 40 bytes per stored entry.
 int resnmtf_shuffle_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src, unsigned long long seed, int normalise) {
-  if (int rc = check_view(dst, v)) return rc;
-  if (!src || v_src < 0 || v_src >= src->V) return dst->fail(RESNMTF_ERR_INVALID, "bad source handle / view");
+  if (int rc = check_view_pair(dst, v, src, v_src, kShuffleSparse)) return rc;
   ViewState& a = dst->views[v];
   const ViewState& b = src->views[v_src];
-  if (!a.sparse) return dst->fail(RESNMTF_ERR_INVALID, "shuffle_view_sparse: the destination view is dense (resnmtf_shuffle_view shuffles dense views)");
-  if (!b.sparse) return dst->fail(RESNMTF_ERR_INVALID, "shuffle_view_sparse: the source view is dense (resnmtf_shuffle_view shuffles dense views)");
-  if (!a.owned || !b.owned) return dst->fail(RESNMTF_ERR_STATE, "shuffle_view_sparse: both views must be owned");
-  if (!b.has_x) return dst->fail(RESNMTF_ERR_STATE, "shuffle_view_sparse: the source view has not been uploaded");
-  if (a.n != b.n || a.m != b.m) return dst->fail(RESNMTF_ERR_INVALID, "shuffle_view_sparse: views differ in shape");
-  if (dst->opt.device_id != src->opt.device_id) return dst->fail(RESNMTF_ERR_INVALID, "shuffle_view_sparse: handles live on different devices");
-  if (b.nnz > a.nnz_cap)
-    return dst->fail(RESNMTF_ERR_INVALID, "shuffle_view_sparse: the source holds " + std::to_string(b.nnz) +
-                     " stored entries, above the destination's nnz capacity " + std::to_string(a.nnz_cap));
   const int n = a.n, m = a.m;
   const long long nnz = b.nnz;
   dst->resume_ok = false;
-  HIP_TRY(dst, hipSetDevice(dst->opt.device_id));
-  HIP_TRY(dst, hipStreamSynchronize(src->stream));
-  if (int rc = sync_both(dst)) return rc;
-  SparseBuild sb;
-  hipError_t e = sb.alloc(nnz, n, m);
+  if (int rc = begin_view_route(dst, src)) return rc;
+  Scratch sc;
+  const SparseBuild sb = take_sparse_build(sc, nnz, n, m);
+  hipError_t e = sc.error();
   if (e == hipSuccess && nnz > 0) {
     hipLaunchKernelGGL(sparse_shuffle_keys_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, dst->stream, b.side[SIDE_G].sp_ptr, b.side[SIDE_G].sp_idx,
                        b.side[SIDE_G].sp_val, nnz, n, m, seed, sb.key[0], reinterpret_cast<double*>(sb.pay[0]));
     e = hipGetLastError();
   }
-  return finish_sparse_build(dst, a, sb, nnz, normalise, e, "shuffle_view_sparse");
-}
-
-// The refusals resnmtf_subsample_count_sparse and resnmtf_subsample_view_sparse share for their source: NULL, a dense
-// view, not owned, not uploaded.  `h` takes the message.
-static int check_sparse_source(resnmtf_handle* h, const resnmtf_handle* src, int v_src, const char* what, const char* dense_entry) {
-  const std::string w(what);
-  if (v_src < 0 || v_src >= src->V) return h->fail(RESNMTF_ERR_INVALID, w + ": bad source view");
-  const ViewState& b = src->views[v_src];
-  if (!b.sparse) return h->fail(RESNMTF_ERR_INVALID, w + ": the source view is dense (" + dense_entry + ")");
-  if (!b.owned) return h->fail(RESNMTF_ERR_STATE, w + ": the source view is not owned");
-  if (!b.has_x) return h->fail(RESNMTF_ERR_STATE, w + ": the source view has not been uploaded");
-  return RESNMTF_OK;
+  return finish_sparse_build(dst, a, sc, sb, nnz, normalise, e, "shuffle_view_sparse");
 }
 
 // The number of stored entries of X[rows, cols] of a sparse view (stored zeros count); nothing is built.
 int resnmtf_subsample_count_sparse(resnmtf_handle* src, int v_src, int n_rows, const int* rows, int n_cols, const int* cols, long long* nnz) {
-  if (!src) return RESNMTF_ERR_INVALID;
+  if (int rc = check_view_pair(src, -1, src, v_src, kSubsampleCount)) return rc;
   if (!rows || !cols || !nnz) return src->fail(RESNMTF_ERR_INVALID, "subsample_count_sparse: rows / cols / nnz is NULL");
   if (n_rows < 0 || n_cols < 0) return src->fail(RESNMTF_ERR_INVALID, "subsample_count_sparse: negative index count");
-  if (int rc = check_sparse_source(src, src, v_src, "subsample_count_sparse", "resnmtf_subsample_view sub-samples dense views")) return rc;
   const ViewState& b = src->views[v_src];
-  if (int rc = check_sample_lists(src, "subsample_count_sparse", b, n_rows, rows, n_cols, cols)) return rc;
+  if (int rc = check_sample_lists(src, "subsample_count_sparse", b, n_rows, rows, n_cols, cols, true)) return rc;
   *nnz = 0;
   if (n_rows == 0 || n_cols == 0) return RESNMTF_OK;
-  HIP_TRY(src, hipSetDevice(src->opt.device_id));
-  if (int rc = sync_both(src)) return rc;
+  if (int rc = begin_view_route(src, src)) return rc;
+  Scratch sc;
   SubsampleMap sm;
-  const hipError_t e = subsample_count(src->stream, b, n_rows, rows, n_cols, cols, sm, nnz);
+  const hipError_t e = subsample_count(src->stream, sc, b, n_rows, rows, n_cols, cols, sm, nnz);
   if (e != hipSuccess) return src->fail_hip("subsample_count_sparse", e);
   return RESNMTF_OK;
 }
@@ -2217,63 +2250,45 @@ int resnmtf_subsample_count_sparse(resnmtf_handle* src, int v_src, int n_rows, c
 // resnmtf_set_view_csc(pre_processed = 1) of the same sub-sample of the source's read-back.  Transient device memory:
 // SparseBuild's 40 bytes per kept entry + SubsampleMap.
 int resnmtf_subsample_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src, const int* rows, const int* cols) {
-  if (int rc = check_view(dst, v)) return rc;
-  if (!src) return dst->fail(RESNMTF_ERR_INVALID, "subsample_view_sparse: the source handle is NULL");
+  if (int rc = check_view_pair(dst, v, src, v_src, kSubsampleSparse)) return rc;
   if (!rows || !cols) return dst->fail(RESNMTF_ERR_INVALID, "subsample_view_sparse: rows / cols are NULL");
   ViewState& a = dst->views[v];
-  if (!a.sparse) return dst->fail(RESNMTF_ERR_INVALID, "subsample_view_sparse: the destination view is dense (resnmtf_subsample_view sub-samples dense views)");
-  if (int rc = check_sparse_source(dst, src, v_src, "subsample_view_sparse", "resnmtf_subsample_view sub-samples dense views")) return rc;
   const ViewState& b = src->views[v_src];
-  if (!a.owned) return dst->fail(RESNMTF_ERR_STATE, "subsample_view_sparse: the destination view is not owned");
-  if (dst->opt.device_id != src->opt.device_id) return dst->fail(RESNMTF_ERR_INVALID, "subsample_view_sparse: handles live on different devices");
-  if (int rc = check_sample_lists(dst, "subsample_view_sparse", b, a.n, rows, a.m, cols)) return rc;
-  HIP_TRY(dst, hipSetDevice(dst->opt.device_id));
-  HIP_TRY(dst, hipStreamSynchronize(src->stream));
-  if (int rc = sync_both(dst)) return rc;
+  if (int rc = check_sample_lists(dst, "subsample_view_sparse", b, a.n, rows, a.m, cols, true)) return rc;
+  if (int rc = begin_view_route(dst, src)) return rc;
+  Scratch sc;
   SubsampleMap sm;
   long long nnz = 0;
-  hipError_t e = subsample_count(dst->stream, b, a.n, rows, a.m, cols, sm, &nnz);
+  hipError_t e = subsample_count(dst->stream, sc, b, a.n, rows, a.m, cols, sm, &nnz);
   if (e != hipSuccess) return dst->fail_hip("subsample_view_sparse", e);
   if (nnz > a.nnz_cap)               // (the destination is still what it was)
     return dst->fail(RESNMTF_ERR_INVALID, "subsample_view_sparse: the sub-sample holds " + std::to_string(nnz) +
                      " stored entries, above the destination's nnz capacity " + std::to_string(a.nnz_cap));
   dst->resume_ok = false;
-  SparseBuild sb;
-  e = sb.alloc(nnz, a.n, a.m);
+  const SparseBuild sb = take_sparse_build(sc, nnz, a.n, a.m);
+  e = sc.error();
   if (e == hipSuccess && nnz > 0) {
     hipLaunchKernelGGL(sparse_subsample_emit_kernel, dim3(ceil_div(a.m, 4)), dim3(256), 0, dst->stream, b.side[SIDE_G].sp_ptr, b.side[SIDE_G].sp_idx,
                        b.side[SIDE_G].sp_val, sm.idx + a.n, a.n, a.m, sm.inv_row, sm.cp, sb.key[0], reinterpret_cast<double*>(sb.pay[0]));
     e = hipGetLastError();
   }
-  return finish_sparse_build(dst, a, sb, nnz, 0, e, "subsample_view_sparse");
+  return finish_sparse_build(dst, a, sc, sb, nnz, 0, e, "subsample_view_sparse");
 }
 
 // resnmtf_copy_view for sparse views: both pointer arrays, both index arrays, both value arrays and data_norms device to
 // device.  The block lists and nsplit depend on KP (spmm_groups_host), and k may differ between the handles (the k sweep
 // copies from a k = 2 base), so the 8 (n + m + 2) bytes of line pointers are read back and the passes planned again.
 int resnmtf_copy_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src) {
-  if (int rc = check_view(dst, v)) return rc;
-  if (!src) return dst->fail(RESNMTF_ERR_INVALID, "copy_view_sparse: the source handle is NULL");
+  if (int rc = check_view_pair(dst, v, src, v_src, kCopySparse)) return rc;
   ViewState& a = dst->views[v];
-  if (!a.sparse) return dst->fail(RESNMTF_ERR_INVALID, "copy_view_sparse: the destination view is dense (resnmtf_copy_view copies dense views)");
-  if (int rc = check_sparse_source(dst, src, v_src, "copy_view_sparse", "resnmtf_copy_view copies dense views")) return rc;
   const ViewState& b = src->views[v_src];
-  if (!a.owned) return dst->fail(RESNMTF_ERR_STATE, "copy_view_sparse: the destination view is not owned");
-  if (a.n != b.n || a.m != b.m) return dst->fail(RESNMTF_ERR_INVALID, "copy_view_sparse: views differ in shape");
-  if (dst->opt.device_id != src->opt.device_id) return dst->fail(RESNMTF_ERR_INVALID, "copy_view_sparse: handles live on different devices");
-  if (b.nnz > a.nnz_cap)
-    return dst->fail(RESNMTF_ERR_INVALID, "copy_view_sparse: the source holds " + std::to_string(b.nnz) +
-                     " stored entries, above the destination's nnz capacity " + std::to_string(a.nnz_cap));
   if (&a == &b) return RESNMTF_OK;
   const int n = a.n, m = a.m;
   const long long nnz = b.nnz;
   dst->resume_ok = false;
-  HIP_TRY(dst, hipSetDevice(dst->opt.device_id));
-  HIP_TRY(dst, hipStreamSynchronize(src->stream));
-  if (int rc = sync_both(dst)) return rc;
+  if (int rc = begin_view_route(dst, src)) return rc;
   hipStream_t st = dst->stream;
   std::vector<long long> cp((size_t)m + 1, 0), rp((size_t)n + 1, 0);
-  SparsePlan pl;
   hipError_t e = hipSuccess;
   auto copy = [&](void* to, const void* from, size_t bytes) {
     if (e == hipSuccess && bytes) e = hipMemcpyAsync(to, from, bytes, hipMemcpyDeviceToDevice, st);
@@ -2287,37 +2302,10 @@ int resnmtf_copy_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* src, in
   copy(a.xnorm2, b.xnorm2, sizeof(double));
   if (e == hipSuccess) e = hipMemcpyAsync(cp.data(), b.side[SIDE_G].sp_ptr, cp.size() * sizeof(long long), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipMemcpyAsync(rp.data(), b.side[SIDE_F].sp_ptr, rp.size() * sizeof(long long), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);             // the line pointers are on the host: plan the passes
-  if (e == hipSuccess) e = upload_sparse_plan(dst, a, rp, cp, pl);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  e = plan_and_commit(dst, a, rp, cp, nnz, e);                  // the line pointers are on the host: plan the passes
   if (e != hipSuccess) { a.has_x = false; return dst->fail_hip("copy_view_sparse", e); }   // (the arrays may be partly overwritten)
   a.empty_rows = a.empty_cols = 0; a.empty_mask.clear();      // (as after resnmtf_set_view_csc: not device-drawn data)
-  commit_sparse_upload(dst, a, pl, nnz);
   return RESNMTF_OK;
-}
-
-int resnmtf_subsample_view(resnmtf_handle* dst, int v, resnmtf_handle* src, int v_src, const int* rows, const int* cols) {
-  if (int rc = check_view(dst, v)) return rc;
-  if (!src || v_src < 0 || v_src >= src->V) return dst->fail(RESNMTF_ERR_INVALID, "bad source handle / view");
-  if (!rows || !cols) return dst->fail(RESNMTF_ERR_INVALID, "rows / cols are NULL");
-  const ViewState& a = dst->views[v];
-  const ViewState& b = src->views[v_src];
-  if (a.sparse || b.sparse) return dst->fail(RESNMTF_ERR_INVALID, "sub-samples of / into a sparse view are gathered on the host (resnmtf_set_view_csc with pre_processed = 1)");
-  if (!a.owned || !b.owned || !b.has_x) return dst->fail(RESNMTF_ERR_STATE, "both views must be owned and the source uploaded");
-  if (dst->opt.device_id != src->opt.device_id) return dst->fail(RESNMTF_ERR_INVALID, "handles live on different devices");
-  for (int r = 0; r < a.n; ++r) if (rows[r] < 0 || rows[r] >= b.n) return dst->fail(RESNMTF_ERR_INVALID, "row index out of range");
-  for (int c = 0; c < a.m; ++c) if (cols[c] < 0 || cols[c] >= b.m) return dst->fail(RESNMTF_ERR_INVALID, "column index out of range");
-  HIP_TRY(dst, hipSetDevice(dst->opt.device_id));
-  HIP_TRY(dst, hipStreamSynchronize(src->stream));
-  int* idx = nullptr;
-  HIP_TRY(dst, hipMalloc(reinterpret_cast<void**>(&idx), ((size_t)a.n + a.m) * sizeof(int)));
-  hipError_t e = hipMemcpy(idx, rows, (size_t)a.n * sizeof(int), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(idx + a.n, cols, (size_t)a.m * sizeof(int), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(idx); return dst->fail_hip("subsample_view", e); }
-  const ShuffleSrc sh{b.side[SIDE_G].X, b.side[SIDE_G].ldx, 0ull, idx, idx + a.n};
-  const int rc = upload_view(dst, v, nullptr, false, nullptr, &sh);      // sub-samples are NOT re-normalised (Appendix B11)
-  (void)hipFree(idx);
-  return rc;
 }
 
 int resnmtf_view_empty_lines(resnmtf_handle* h, int v, int* n_empty_rows, int* n_empty_cols, unsigned char* row_mask,
@@ -2485,15 +2473,10 @@ void jacobi_eigen(std::vector<double>& A, int L, std::vector<double>& V) {
   }
 }
 
+// the work arrays of the SVD initialisation, taken from the Scratch of the route (Pn / Pm: the view's own slabs or temporaries)
 struct InitScratch {
   double *Yn = nullptr, *Yn2 = nullptr, *Zm = nullptr, *Zm2 = nullptr, *gpart = nullptr, *gram = nullptr, *M = nullptr;
   float *Pn = nullptr, *Pm = nullptr;
-  bool own_pn = false, own_pm = false;
-  ~InitScratch() {
-    for (double* p : {Yn, Yn2, Zm, Zm2, gpart, gram, M}) if (p) (void)hipFree(p);
-    if (own_pn && Pn) (void)hipFree(Pn);
-    if (own_pm && Pm) (void)hipFree(Pm);
-  }
 };
 constexpr int kGramBlocks = 256;
 
@@ -2593,13 +2576,12 @@ int init_svd_thin(resnmtf_handle* h, int v, double sigma, std::mt19937_64& gen, 
   const int n = vs.n, m = vs.m;
   const bool tall = m <= n;                       // Y = X [n][m]  or  X^T [m][n]
   const int len = tall ? n : m, r = tall ? m : n;
+  Scratch mem;
   InitScratch sc;
-  hipError_t e;
-  auto alloc = [&](double** p, size_t cnt) { return hipMalloc(reinterpret_cast<void**>(p), cnt * sizeof(double)); };
-  if ((e = alloc(&sc.Yn, (size_t)len * r)) != hipSuccess || (e = alloc(&sc.Yn2, (size_t)len * r)) != hipSuccess ||
-      (e = alloc(&sc.gpart, (size_t)(kGramBlocks + 1) * r * r)) != hipSuccess || (e = alloc(&sc.gram, (size_t)r * r)) != hipSuccess ||
-      (e = alloc(&sc.M, (size_t)r * r)) != hipSuccess)
-    return h->fail_hip("init_svd hipMalloc", e);
+  sc.Yn = mem.take<double>((size_t)len * r); sc.Yn2 = mem.take<double>((size_t)len * r);
+  sc.gpart = mem.take<double>((size_t)(kGramBlocks + 1) * r * r); sc.gram = mem.take<double>((size_t)r * r);
+  sc.M = mem.take<double>((size_t)r * r);
+  if (mem.error() != hipSuccess) return h->fail_hip("init_svd hipMalloc", mem.error());
   const int long_side = tall ? SIDE_F : SIDE_G;      // Y has one row per line of the long side
   const Side& lines = vs.side[long_side];
   if (vs.sparse) {      // the short side from the CSR (Y = X) or the CSC (Y = X^T)
@@ -2644,23 +2626,19 @@ int init_svd_impl(resnmtf_handle* h, int v, unsigned long long seed, double sigm
   const int L = std::min(64, 16 * ceil_div(k + 8, 16)), NTi = L / 16;
   std::mt19937_64 gen(seed);
   if (std::min(n, m) < L) return init_svd_thin(h, v, sigma, gen, singular_values, basis);
+  Scratch mem;
   InitScratch sc;
-  hipError_t e;
-  auto alloc = [&](double** p, size_t cnt) { return hipMalloc(reinterpret_cast<void**>(p), cnt * sizeof(double)); };
-  if ((e = alloc(&sc.Yn, (size_t)n * L)) != hipSuccess || (e = alloc(&sc.Yn2, (size_t)n * L)) != hipSuccess ||
-      (e = alloc(&sc.Zm, (size_t)m * L)) != hipSuccess || (e = alloc(&sc.Zm2, (size_t)m * L)) != hipSuccess ||
-      (e = alloc(&sc.gpart, (size_t)(kGramBlocks + 1) * L * L)) != hipSuccess || (e = alloc(&sc.gram, (size_t)L * L)) != hipSuccess ||
-      (e = alloc(&sc.M, (size_t)L * L)) != hipSuccess)
-    return h->fail_hip("init_svd hipMalloc", e);
+  sc.Yn = mem.take<double>((size_t)n * L); sc.Yn2 = mem.take<double>((size_t)n * L);
+  sc.Zm = mem.take<double>((size_t)m * L); sc.Zm2 = mem.take<double>((size_t)m * L);
+  sc.gpart = mem.take<double>((size_t)(kGramBlocks + 1) * L * L); sc.gram = mem.take<double>((size_t)L * L);
+  sc.M = mem.take<double>((size_t)L * L);
+  if (mem.error() != hipSuccess) return h->fail_hip("init_svd hipMalloc", mem.error());
   // slabs: the view's own when the sketch is as wide as its KP, else temporaries
   if (L == vs.KP) { sc.Pn = vs.side[SIDE_F].P; sc.Pm = vs.side[SIDE_G].P; }
   else {
-    if ((e = hipMalloc(reinterpret_cast<void**>(&sc.Pn), (size_t)vs.side[SIDE_F].nsplit * vs.n_pad * L * sizeof(float))) != hipSuccess)
-      return h->fail_hip("init_svd hipMalloc slabs", e);
-    sc.own_pn = true;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&sc.Pm), (size_t)vs.side[SIDE_G].nsplit * vs.m_pad * L * sizeof(float))) != hipSuccess)
-      return h->fail_hip("init_svd hipMalloc slabs", e);
-    sc.own_pm = true;
+    sc.Pn = mem.take<float>((size_t)vs.side[SIDE_F].nsplit * vs.n_pad * L);
+    sc.Pm = mem.take<float>((size_t)vs.side[SIDE_G].nsplit * vs.m_pad * L);
+    if (mem.error() != hipSuccess) return h->fail_hip("init_svd hipMalloc slabs", mem.error());
   }
   PassArgs xg{}, xt{};
   xg.A = vs.side[SIDE_F].X; xg.lda = 64; xg.tile_stride = vs.side[SIDE_F].ldx; xg.ntiles = vs.n_pad / 64; xg.B = vs.side[SIDE_G].W32; xg.ldb = 64; xg.P = sc.Pn;
@@ -3388,12 +3366,12 @@ int finalise_impl(resnmtf_handle* h, int v, double* F, double* S, double* G, dou
   if (to_device) HIP_TRY(h, wait_for_caller(h, stream));
   const hipMemcpyKind kind = to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   const size_t nk = (size_t)vs.n * vs.k, mk = (size_t)vs.m * vs.k, kk = (size_t)vs.k * vs.k;
-  double* buf = nullptr;   // [cF k][cG k][S kk][Fout nk][rc nk][Gout mk][cc mk]
-  int* rel = nullptr;
   const size_t total = 2 * (size_t)vs.k + kk + 2 * nk + 2 * mk;
-  HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), total * sizeof(double)));
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&rel), (size_t)vs.k * sizeof(int));
-  if (e != hipSuccess) { (void)hipFree(buf); return h->fail_hip("hipMalloc", e); }
+  Scratch sc;
+  double* buf = sc.take<double>(total);   // [cF k][cG k][S kk][Fout nk][rc nk][Gout mk][cc mk]
+  int* rel = sc.take<int>((size_t)vs.k);
+  hipError_t e = sc.error();
+  if (e != hipSuccess) return h->fail_hip("hipMalloc", e);
   double *cF = buf, *cG = cF + vs.k, *So = cG + vs.k, *Fo = So + kk, *rc_ = Fo + nk, *Go = rc_ + nk, *cc = Go + mk;
   hipLaunchKernelGGL(colsum_kernel, dim3(vs.k), dim3(256), 0, h->stream, vs.side[SIDE_F].W, vs.n, vs.k, cF);
   hipLaunchKernelGGL(colsum_kernel, dim3(vs.k), dim3(256), 0, h->stream, vs.side[SIDE_G].W, vs.m, vs.k, cG);
@@ -3415,8 +3393,6 @@ int finalise_impl(resnmtf_handle* h, int v, double* F, double* S, double* G, dou
   if (e == hipSuccess && row_clusters) e = copy(row_clusters, rc_, nk);
   if (e == hipSuccess && col_clusters) e = copy(col_clusters, cc, mk);
   if (to_device) { const hipError_t es = hipStreamSynchronize(h->stream); if (e == hipSuccess) e = es; }
-  (void)hipFree(buf);
-  (void)hipFree(rel);
   if (e != hipSuccess) return h->fail_hip("finalise", e);
   return RESNMTF_OK;
 }
@@ -3481,8 +3457,9 @@ int relevance_impl(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, con
   // (masked: then [flags k] bytes)
   const size_t n_dbl = 3 * (size_t)k + kk, n_int = (size_t)k + vs.n + vs.m;
   const size_t n_bytes = n_dbl * sizeof(double) + n_int * sizeof(int) + 2 * side * sizeof(unsigned int);
-  char* buf = nullptr;
-  HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), n_bytes + (flags ? (size_t)k : 0)));
+  Scratch sc;
+  char* buf = sc.take<char>(n_bytes + (flags ? (size_t)k : 0));
+  if (!buf) return h->fail_hip("relevance hipMalloc", sc.error());
   double *cF = reinterpret_cast<double*>(buf), *cG = cF + k, *So = cG + k, *out = So + kk;
   int *rel = reinterpret_cast<int*>(buf + n_dbl * sizeof(double)), *idx = rel + k;
   unsigned int* counts = reinterpret_cast<unsigned int*>(idx + vs.n + vs.m);
@@ -3517,7 +3494,6 @@ int relevance_impl(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, con
   }
   if (e == hipSuccess) e = hipMemcpyAsync(relevance, out, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  (void)hipFree(buf);
   if (e != hipSuccess) return h->fail_hip("relevance", e);
   return RESNMTF_OK;
 }
@@ -3660,8 +3636,9 @@ int bisil_impl(resnmtf_handle* h, int v, int k, const double* row_clusters, cons
   if (bytes > free_b)
     return h->fail(RESNMTF_ERR_ALLOC, "bisil workspace: " + std::to_string(bytes) + " bytes asked for (" + std::to_string(g_floats * sizeof(float)) +
                    " of them the restricted block, features x padded members), " + std::to_string(free_b) + " free on the device");
-  char* buf = nullptr;
-  if (hipError_t ea = hipMalloc(reinterpret_cast<void**>(&buf), bytes); ea != hipSuccess) {
+  Scratch sc;
+  char* buf = sc.take<char>(bytes);
+  if (const hipError_t ea = sc.error(); ea != hipSuccess) {
     (void)hipGetLastError();
     return h->fail(ea == hipErrorOutOfMemory ? RESNMTF_ERR_ALLOC : RESNMTF_ERR_HIP,
                    "bisil workspace: hipMalloc of " + std::to_string(bytes) + " bytes asked for: " + hipGetErrorString(ea));
@@ -3710,7 +3687,6 @@ int bisil_impl(resnmtf_handle* h, int v, int k, const double* row_clusters, cons
   if (e == hipSuccess) e = hipMemcpyAsync(row_sil, sil, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(col_sil, sil + (size_t)n * k, (size_t)m * k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  (void)hipFree(buf);
   if (e != hipSuccess) return h->fail_hip("bisil", e);
   return RESNMTF_OK;
 }
@@ -3725,6 +3701,25 @@ int resnmtf_bisil_sparse(resnmtf_handle* h, int v, int k, const double* row_clus
                          double* row_sil, double* col_sil) {
   return bisil_impl(h, v, k, row_clusters, col_clusters, metric, row_sil, col_sil, true);
 }
+
+namespace {
+// The JSD pipeline, enqueued on `st`: the n_cols columns of `cols` ([n_cols][n]) sorted (tiles in sort_a, then merge passes
+// between sort_a and sort_b), the statistics of every column, then out[p] for the n_pairs column pairs of `pairs`, in grids
+// of at most 2^20 workgroups.  All pointers are device memory; the caller checks hipGetLastError.
+void enqueue_jsd(hipStream_t st, const double* cols, int n, int n_cols, double* sort_a, double* sort_b, double* stats, const int* pairs,
+                 long long n_pairs, double* out) {
+  hipLaunchKernelGGL(jsd_tile_sort_kernel, dim3(ceil_div(n, JSD_TILE), (unsigned)n_cols), dim3(JSD_SORT_THREADS), 0, st, cols, sort_a, n);
+  double *src = sort_a, *dst = sort_b;
+  for (int width = JSD_TILE; width < n; width *= 2) {
+    hipLaunchKernelGGL(jsd_merge_kernel, dim3(ceil_div(n, 256), (unsigned)n_cols), dim3(256), 0, st, (const double*)src, dst, n, width);
+    std::swap(src, dst);
+  }
+  hipLaunchKernelGGL(jsd_stats_kernel, dim3((unsigned)n_cols), dim3(256), 0, st, (const double*)src, cols, n, stats);
+  for (long long p0 = 0; p0 < n_pairs; p0 += 1 << 20)
+    hipLaunchKernelGGL(jsd_pair_kernel, dim3((unsigned)std::min<long long>(1 << 20, n_pairs - p0)), dim3(JSD_N), 0, st, (const double*)src,
+                       (const double*)stats, n, pairs + 2 * (size_t)p0, out + p0);
+}
+}  // namespace
 
 int resnmtf_jsd_pairs(int device_id, int n, int n_cols, const double* cols, int n_pairs, const int* pairs, double* out) {
   auto bad = [](const char* msg) { g_create_error = msg; return RESNMTF_ERR_INVALID; };
@@ -3748,8 +3743,9 @@ int resnmtf_jsd_pairs(int device_id, int n, int n_cols, const double* cols, int 
   if (e != hipSuccess) { g_create_error = std::string("hipStreamCreate: ") + hipGetErrorString(e); return RESNMTF_ERR_HIP; }
   // [orig n C][sort A n C][sort B n C][stats 2 C][out P] doubles | [pairs 2 P] ints
   const size_t n_dbl = 3 * total + 2 * (size_t)n_cols + (size_t)n_pairs;
-  char* buf = nullptr;
-  e = hipMalloc(reinterpret_cast<void**>(&buf), n_dbl * sizeof(double) + 2 * (size_t)n_pairs * sizeof(int));
+  Scratch sc;
+  char* buf = sc.take<char>(n_dbl * sizeof(double) + 2 * (size_t)n_pairs * sizeof(int));
+  e = sc.error();
   if (e != hipSuccess) {
     (void)hipStreamDestroy(st);
     g_create_error = std::string("jsd_pairs: ") + hipGetErrorString(e);
@@ -3761,22 +3757,11 @@ int resnmtf_jsd_pairs(int device_id, int n, int n_cols, const double* cols, int 
   e = hipMemcpyAsync(orig, cols, total * sizeof(double), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(dpairs, pairs, 2 * (size_t)n_pairs * sizeof(int), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(jsd_tile_sort_kernel, dim3(ceil_div(n, JSD_TILE), n_cols), dim3(JSD_SORT_THREADS), 0, st,
-                       (const double*)orig, sa, n);
-    double *src = sa, *dst = sb;
-    for (int width = JSD_TILE; width < n; width *= 2) {
-      hipLaunchKernelGGL(jsd_merge_kernel, dim3(ceil_div(n, 256), n_cols), dim3(256), 0, st, (const double*)src, dst, n, width);
-      std::swap(src, dst);
-    }
-    hipLaunchKernelGGL(jsd_stats_kernel, dim3(n_cols), dim3(256), 0, st, (const double*)src, (const double*)orig, n, stats);
-    for (int p0 = 0; p0 < n_pairs; p0 += 1 << 20)              // (grids of at most 2^20 workgroups)
-      hipLaunchKernelGGL(jsd_pair_kernel, dim3(std::min(1 << 20, n_pairs - p0)), dim3(JSD_N), 0, st, (const double*)src,
-                         (const double*)stats, n, (const int*)(dpairs + 2 * (size_t)p0), dout + p0);
+    enqueue_jsd(st, orig, n, n_cols, sa, sb, stats, dpairs, n_pairs, dout);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t)n_pairs * sizeof(double), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(buf);
   (void)hipStreamDestroy(st);
   if (e != hipSuccess) { g_create_error = std::string("jsd_pairs: ") + hipGetErrorString(e); return RESNMTF_ERR_HIP; }
   return RESNMTF_OK;
@@ -3824,8 +3809,9 @@ int resnmtf_spurious_scores(resnmtf_handle* h, int v, resnmtf_handle* const* shu
   // [pool n C][sort A n C][sort B n C][stats 2 C][colsum K][clusters n K (unused)][out P][score K] doubles
   // | [pairs 2 P][flag 1] ints
   const size_t n_dbl = 3 * total + 2 * (size_t)C + (size_t)K + nk + (size_t)P + (size_t)K;
-  char* buf = nullptr;
-  HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&buf), n_dbl * sizeof(double) + (2 * (size_t)P + 1) * sizeof(int)));
+  Scratch sc;
+  char* buf = sc.take<char>(n_dbl * sizeof(double) + (2 * (size_t)P + 1) * sizeof(int));
+  if (!buf) return h->fail_hip("spurious_scores hipMalloc", sc.error());
   double *pool = reinterpret_cast<double*>(buf), *sa = pool + total, *sb = sa + total, *stats = sb + total;
   double *cF = stats + 2 * (size_t)C, *cl = cF + K, *dout = cl + nk, *dscore = dout + P;
   int* dpairs = reinterpret_cast<int*>(buf + n_dbl * sizeof(double));
@@ -3847,24 +3833,9 @@ int resnmtf_spurious_scores(resnmtf_handle* h, int v, resnmtf_handle* const* shu
   }
   if (e == hipSuccess) e = hipMemcpyAsync(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e == hipSuccess && flag) {
-    (void)hipFree(buf);
-    return h->fail(RESNMTF_ERR_INVALID, "a factor has a non-finite entry");
-  }
+  if (e == hipSuccess && flag) return h->fail(RESNMTF_ERR_INVALID, "a factor has a non-finite entry");
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(jsd_tile_sort_kernel, dim3(ceil_div(n, JSD_TILE), (unsigned)C), dim3(JSD_SORT_THREADS), 0, h->stream,
-                       (const double*)pool, sa, n);
-    double *src = sa, *dst = sb;
-    for (int width = JSD_TILE; width < n; width *= 2) {
-      hipLaunchKernelGGL(jsd_merge_kernel, dim3(ceil_div(n, 256), (unsigned)C), dim3(256), 0, h->stream, (const double*)src,
-                         dst, n, width);
-      std::swap(src, dst);
-    }
-    hipLaunchKernelGGL(jsd_stats_kernel, dim3((unsigned)C), dim3(256), 0, h->stream, (const double*)src, (const double*)pool,
-                       n, stats);
-    for (long long p0 = 0; p0 < P; p0 += 1 << 20)              // (grids of at most 2^20 workgroups)
-      hipLaunchKernelGGL(jsd_pair_kernel, dim3((unsigned)std::min<long long>(1 << 20, P - p0)), dim3(JSD_N), 0, h->stream,
-                         (const double*)src, (const double*)stats, n, (const int*)(dpairs + 2 * (size_t)p0), dout + p0);
+    enqueue_jsd(h->stream, pool, n, (int)C, sa, sb, stats, dpairs, P, dout);
     hipLaunchKernelGGL(jsd_score_mean_kernel, dim3((unsigned)ceil_div(K, 64)), dim3(64), 0, h->stream,
                        (const double*)(dout + P_null), K, (int)RK, dscore);
     e = hipGetLastError();
@@ -3872,7 +3843,6 @@ int resnmtf_spurious_scores(resnmtf_handle* h, int v, resnmtf_handle* const* shu
   if (e == hipSuccess) e = hipMemcpyAsync(score, dscore, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(null_scores, dout, (size_t)P_null * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  (void)hipFree(buf);
   if (e != hipSuccess) return h->fail_hip("spurious_scores", e);
   return RESNMTF_OK;
 }
@@ -4076,8 +4046,9 @@ int resnmtf_group_run(int device_id, int n_jobs, const resnmtf_group_job* jobs, 
   hipStream_t st = nullptr;
   e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
   if (e != hipSuccess) { g_create_error = std::string("hipStreamCreate: ") + hipGetErrorString(e); return RESNMTF_ERR_HIP; }
-  double* buf = nullptr;
-  e = hipMalloc(reinterpret_cast<void**>(&buf), total * sizeof(double));
+  Scratch sc;
+  double* buf = sc.take<double>(total);
+  e = sc.error();
   if (e != hipSuccess) {
     (void)hipStreamDestroy(st);
     g_create_error = std::string("group_run: ") + hipGetErrorString(e);
@@ -4105,7 +4076,6 @@ int resnmtf_group_run(int device_id, int n_jobs, const resnmtf_group_job* jobs, 
   if (e == hipSuccess && max_it > 0)
     e = hipMemcpyAsync(errs.data(), buf + err_base, errs.size() * sizeof(double), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(buf);
   (void)hipStreamDestroy(st);
   if (e != hipSuccess) { g_create_error = std::string("group_run: ") + hipGetErrorString(e); return RESNMTF_ERR_HIP; }
   for (int q = 0; q < n_jobs; ++q) {

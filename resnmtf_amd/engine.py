@@ -307,13 +307,23 @@ class Engine:
         seed, from the stored entries alone; the shuffle stays sparse."""
         self._check(self._lib.resnmtf_shuffle_view_sparse(self._h, v, other._h, v_src, int(seed), 1 if normalise else 0))
 
+    def _index_lists(self, rows, cols, v=None, vectors=True):
+        """``rows`` / ``cols`` as contiguous int32 arrays.  ``v``: their counts must equal the shape of this engine's view
+        ``v`` (``vectors``: and they must be 1-D); ``None``: they only have to be vectors."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32); cols = np.ascontiguousarray(cols, dtype=np.int32)
+        flat = rows.ndim == 1 and cols.ndim == 1
+        if v is None:
+            if not flat:
+                raise ValueError("rows and cols must be vectors")
+        elif (vectors and not flat) or len(rows) != self.n_rows[v] or len(cols) != self.n_cols[v]:
+            raise ValueError("index counts must equal the view's shape")
+        return rows, cols
+
     def subsample_count_sparse(self, v: int, rows, cols) -> int:
         """The number of stored entries of ``X[rows, cols]`` of this engine's sparse view ``v``
         (``resnmtf_subsample_count_sparse``): the ``nnz`` an engine needs to receive that sub-sample
         (``subsample_view_sparse_from``).  Nothing is built."""
-        rows = np.ascontiguousarray(rows, dtype=np.int32); cols = np.ascontiguousarray(cols, dtype=np.int32)
-        if rows.ndim != 1 or cols.ndim != 1:
-            raise ValueError("rows and cols must be vectors")
+        rows, cols = self._index_lists(rows, cols)
         nnz = C.c_longlong(0)
         # (never a NULL pointer for an empty list)
         r = rows if rows.size else np.zeros(1, dtype=np.int32); c = cols if cols.size else np.zeros(1, dtype=np.int32)
@@ -326,9 +336,7 @@ class Engine:
         this engine's sparse view ``v`` (``resnmtf_subsample_view_sparse``), gathered on the device from the stored
         entries; the view must have the shape ``(len(rows), len(cols))`` and room for ``other.subsample_count_sparse``
         entries.  The lists come in any order, without repeats; the values are not re-normalised."""
-        rows = np.ascontiguousarray(rows, dtype=np.int32); cols = np.ascontiguousarray(cols, dtype=np.int32)
-        if len(rows) != self.n_rows[v] or len(cols) != self.n_cols[v]:
-            raise ValueError("index counts must equal the view's shape")
+        rows, cols = self._index_lists(rows, cols, v, vectors=False)
         self._check(self._lib.resnmtf_subsample_view_sparse(self._h, v, other._h, v_src, _ip(rows), _ip(cols)))
 
     def copy_view_sparse_from(self, v: int, other: "Engine", v_src: int = 0):
@@ -350,9 +358,7 @@ class Engine:
     def subsample_view_from(self, v: int, other: "Engine", v_src: int, rows, cols):
         """The sub-sample ``X[rows, cols]`` of another engine's view (``R/stability_analysis.r:230-249``), gathered
         on the device; this engine's view v must have the shape ``(len(rows), len(cols))``."""
-        rows = np.ascontiguousarray(rows, dtype=np.int32); cols = np.ascontiguousarray(cols, dtype=np.int32)
-        if len(rows) != self.n_rows[v] or len(cols) != self.n_cols[v]:
-            raise ValueError("index counts must equal the view's shape")
+        rows, cols = self._index_lists(rows, cols, v, vectors=False)
         self._check(self._lib.resnmtf_subsample_view(self._h, v, other._h, v_src, _ip(rows), _ip(cols)))
 
     def empty_lines(self, v: int, counts: bool = False):
@@ -504,9 +510,7 @@ class Engine:
         """``relevance_results`` (``R/stability_analysis.r:45-67``) of this engine's view ``v`` (its current factors,
         clustered as ``finalise`` would) against the clusters set on ``ref_engine``'s view ``v_ref``, gathered by
         ``rows`` / ``cols`` (0-based, one per row / column of view ``v``): k relevance values, computed on the device."""
-        rows = np.ascontiguousarray(rows, dtype=np.int32); cols = np.ascontiguousarray(cols, dtype=np.int32)
-        if rows.ndim != 1 or cols.ndim != 1 or len(rows) != self.n_rows[v] or len(cols) != self.n_cols[v]:
-            raise ValueError("index counts must equal the view's shape")
+        rows, cols = self._index_lists(rows, cols, v)
         out = np.zeros(self.k[v], dtype=np.float64)
         self._check(self._lib.resnmtf_relevance(self._h, v, ref_engine._h, v_ref, _ip(rows), _ip(cols), _dp(out)))
         return out
@@ -515,9 +519,7 @@ class Engine:
         """``relevance`` after a spurious-bicluster removal (``resnmtf_relevance_masked``): ``flags`` holds k[v] booleans
         indexed by F column (the removal rule of ``R/obtain_bicl.r:176-188``); the cluster columns ``j`` with
         ``flags[relations[j]]`` are zeroed on the device, through its own ``relations``, before the counting."""
-        rows = np.ascontiguousarray(rows, dtype=np.int32); cols = np.ascontiguousarray(cols, dtype=np.int32)
-        if rows.ndim != 1 or cols.ndim != 1 or len(rows) != self.n_rows[v] or len(cols) != self.n_cols[v]:
-            raise ValueError("index counts must equal the view's shape")
+        rows, cols = self._index_lists(rows, cols, v)
         fl = np.ascontiguousarray(np.asarray(flags, dtype=bool).astype(np.uint8))
         if fl.shape != (self.k[v],):
             raise ValueError(f"flags must hold k = {self.k[v]} entries")
