@@ -3584,6 +3584,7 @@ int bisil_impl(resnmtf_handle* h, int v, int k, const double* row_clusters, cons
       if (!((active >> j) & 1ull)) continue;
       const int n_mem = (int)s.mpos[j].size(), tiles_m = ceil_div(n_mem, BISIL_TILE);
       // enough workgroups to fill the device: the others are split into chunks of whole tiles, summed in order later
+      // (tests/test_gpu_bisil_forms.py restates this rule and the kq table below: change them together)
       const int want = std::max(1, std::min(tiles_u, ceil_div(2048, tiles_m)));
       chunk_tiles[sd][j] = ceil_div(tiles_u, want);
       chunks[sd][j] = ceil_div(tiles_u, chunk_tiles[sd][j]);

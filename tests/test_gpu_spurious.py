@@ -57,6 +57,25 @@ def test_jsd_pairs_is_bitwise_reproducible():
     assert sub.tobytes() == a[[3 * 12 + 7, 7 * 12 + 3]].tobytes()
 
 
+def test_jsd_pairs_second_grid():
+    """enqueue_jsd launches the pairs in grids of at most 2^20 workgroups and offsets ``pairs`` and ``out`` for the next:
+    2^20 + 37 pairs (the 25 distinct ones of five columns, shuffled) reach the second grid, and every output is bitwise
+    the value a 25-pair call gives for its pair."""
+    n = 513
+    cols = _pool(n, n)
+    C_ = cols.shape[1]
+    pairs = np.array([(a, b) for a in range(C_) for b in range(C_)], dtype=np.int32)
+    base = jsd_pairs(cols, pairs)
+    want = np.array([J.jsd_calc(cols[:, a], cols[:, b]) for a, b in pairs])
+    assert float(np.max(np.abs(base - want))) <= 1e-10
+    total = (1 << 20) + 37
+    pick = np.random.default_rng(513).permutation(np.arange(total) % len(pairs))
+    assert len(set(pick[1 << 20:])) > 1 and len(set(pick[:1 << 20])) == len(pairs)
+    got = jsd_pairs(cols, pairs[pick])
+    assert got.shape == (total,)
+    assert got.tobytes() == base[pick].tobytes()
+
+
 def test_jsd_pairs_host_refusals():
     lib = _lib.load()
     dp = C.POINTER(C.c_double); ip = C.POINTER(C.c_int)
