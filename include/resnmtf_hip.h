@@ -378,6 +378,42 @@ int resnmtf_set_view_device(resnmtf_handle* h, int v, const void* x, int dtype, 
                             int raw, int* was_negative, void* stream);
 
 /*
+ * Upload the data of a sparse owned view from arrays that are ALREADY in device memory -- what torch's sparse_csc,
+ * sparse_csr and (coalesced) sparse_coo tensors hold -- without a host copy: nothing runs per entry on the host.
+ *   layout      RESNMTF_SPARSE_CSC: ptr_or_rows = the m + 1 column pointers, idx_or_cols = the row index of every entry;
+ *               RESNMTF_SPARSE_CSR: the n + 1 row pointers and the column indices;
+ *               RESNMTF_SPARSE_COO: nnz row indices and nnz column indices.
+ *   index_type  RESNMTF_INDEX_I32 / _I64, one type for both index arrays; dtype: RESNMTF_DTYPE_* of values [nnz].
+ *               Every array is contiguous and 0-based.
+ *   stream      as for resnmtf_set_view_device: an event recorded there, the handle's stream waits for it, and the call
+ *               returns when the view is built, so the arrays may be freed on return.
+ * The entries may come in ANY order (within a column, within a row, arbitrary for COO).  Stored positions must be
+ * distinct: a position stored twice is refused (the caller coalesces; nothing is summed).  Explicit zeros stay stored.
+ * pre_processed as for resnmtf_set_view_csc: 0 = matrix_normalisation (R/utils.r:86-88) on the device, a column without
+ * an entry > 0 refused; 1 = the values as they are.
+ * The view is BIT FOR BIT the one resnmtf_set_view_csc makes of the canonical CSC (columns ascending, rows ascending
+ * within a column, explicit zeros kept) of the same (row, column, value widened to fp64) set: both pointer and index
+ * arrays, both value arrays, data_norms, the work split of the passes, resnmtf_view_empty_lines reporting zero.
+ * Widening is exact, the positions are distinct (so their sorted order is unique), and normalisation, the CSR values,
+ * data_norms and the plan are the host route's own code.  A CSC input whose rows already ascend strictly within every
+ * column skips the first of the two sorts.  nnz = 0 is accepted with pre_processed = 1.
+ * Transient device memory: 40 bytes per entry (the sparse shuffle's build) + m bytes + 16.
+ * Refused before any device work (RESNMTF_ERR_INVALID / _STATE, text in resnmtf_last_error): a NULL array (values /
+ * idx_or_cols, and COO's rows, may be NULL only when nnz = 0), an unknown layout, index type or dtype, nnz < 0 or above
+ * the view's capacity, a dense view, a view the handle does not own, an array that is not device memory of the handle's
+ * device.  Refused by the device checks (RESNMTF_ERR_INVALID; the text names the condition and the lowest offending
+ * line, entry or position): pointers that do not start at 0, are not monotone or do not end at nnz; an index out of
+ * range; a non-finite or negative value; a position stored twice; with pre_processed = 0 an all-zero column (nnz = 0:
+ * every column).  Every refusal leaves the view exactly as it was.
+ * Replaces: as resnmtf_set_view_csc (R/utils.r:416-419 for a Matrix::dgCMatrix), for data produced on the device.
+ */
+enum { RESNMTF_SPARSE_CSC = 0, RESNMTF_SPARSE_CSR = 1, RESNMTF_SPARSE_COO = 2 };
+enum { RESNMTF_INDEX_I32 = 0, RESNMTF_INDEX_I64 = 1 };
+int resnmtf_set_view_sparse_device(resnmtf_handle* h, int v, int layout, const void* ptr_or_rows, const void* idx_or_cols,
+                                   int index_type, const void* values, int dtype, long long nnz, int pre_processed,
+                                   void* stream);
+
+/*
  * View data without a host round trip (the callers of the loop repeat it 36-66 times per apply_resnmtf):
  *   resnmtf_copy_view     device copy of an uploaded view of another handle on the same GPU (same n x m) --
  *                         the k sweep (R/main.r:279-290) factorises ONE data set for every k;

@@ -23,6 +23,8 @@ FACTOR_U_SEND, FACTOR_U_RECV, FACTOR_FNEW_SEND, FACTOR_FNEW_RECV = 9, 10, 11, 12
 FACTOR_T_SEND, FACTOR_T_RECV, FACTOR_GNEW_SEND, FACTOR_GNEW_RECV, FACTOR_F_SLICE, FACTOR_G_SLICE = 13, 14, 15, 16, 17, 18
 TIMED_KINDS = ("xg", "xtf", "f_chain", "g_chain", "s_chain", "pack")
 DTYPE_F64, DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2, 3      # RESNMTF_DTYPE_* (resnmtf_set_view_device)
+SPARSE_CSC, SPARSE_CSR, SPARSE_COO = 0, 1, 2                   # RESNMTF_SPARSE_* (resnmtf_set_view_sparse_device)
+INDEX_I32, INDEX_I64 = 0, 1                                   # RESNMTF_INDEX_*
 ABI_VERSION = 2
 MAX_K = 64
 
@@ -113,6 +115,8 @@ SIGNATURES = {
     "resnmtf_set_view": (C.c_int, [_h, C.c_int, _dp]),
     "resnmtf_set_view_raw": (C.c_int, [_h, C.c_int, _dp, _ip]),
     "resnmtf_set_view_device": (C.c_int, [_h, C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_int, _ip, C.c_void_p]),
+    "resnmtf_set_view_sparse_device": (C.c_int, [_h, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_int,
+                                                 C.c_void_p]),
     "resnmtf_copy_view": (C.c_int, [_h, C.c_int, _h, C.c_int]),
     "resnmtf_shuffle_view": (C.c_int, [_h, C.c_int, _h, C.c_int, C.c_ulonglong, C.c_int]),
     "resnmtf_subsample_view": (C.c_int, [_h, C.c_int, _h, C.c_int, _ip, _ip]),

@@ -49,10 +49,11 @@ _DISTANCES = ("euclidean", "manhattan", "cosine")
 
 
 def _as_list(x):
-    if (isinstance(x, np.ndarray) and x.ndim == 2) or sparse.is_sparse(x) or isinstance(x, device_views.RawDeviceView):
+    if ((isinstance(x, np.ndarray) and x.ndim == 2) or sparse.is_sparse(x)
+            or isinstance(x, (device_views.RawDeviceView, device_views.SparseDeviceView))):
         return [x]                      # check_lists, R/utils.r:313-316
     if device_views.is_tensor(x):       # one tensor is one view (never a list of its rows)
-        device_views.check_tensor(x)
+        (device_views.check_sparse_tensor if device_views.is_sparse_tensor(x) else device_views.check_tensor)(x)
         return [x]
     return list(x)
 
@@ -61,9 +62,11 @@ def _views(data, device_id: int = 0) -> list:
     """The views as fp64 arrays; a ``scipy.sparse`` view becomes a canonical CSC copy (``sparse.canonical_csc``: the
     caller's matrix is not modified) and stays sparse on the device (``resnmtf_create_sparse``); a ``torch`` tensor on
     ``cuda:device_id`` stays the tensor it is (``device_views.as_view``: 2-D, floating, on that device, else
-    ``ValueError``; a CPU tensor becomes its fp64 array)."""
+    ``ValueError``; a CPU tensor becomes its fp64 array); a sparse tensor on that device becomes its
+    ``device_views.SparseDeviceView`` and is a sparse view too (a CPU one: its ``scipy.sparse`` matrix)."""
+    data = [device_views.host_or_device(d, f"view {v}") for v, d in enumerate(_as_list(data))]      # (a CPU sparse tensor: scipy)
     return [sparse.canonical_csc(d) if sparse.is_sparse(d) else device_views.as_view(d, device_id, f"view {v}")
-            for v, d in enumerate(_as_list(data))]
+            for v, d in enumerate(data)]
 
 
 def _load_engine(eng: Engine, data, init_f, init_s, init_g, lam, mu, phi, xi, psi,
@@ -71,7 +74,9 @@ def _load_engine(eng: Engine, data, init_f, init_s, init_g, lam, mu, phi, xi, ps
     """``init_f is None``: the initial factors come from the device (``resnmtf_init_svd``)."""
     for v in range(eng.n_views):
         if eng.owned[v]:
-            if sparse.is_sparse(data[v]):
+            if isinstance(data[v], device_views.SparseDeviceView):
+                device_views.upload_sparse(eng, v, data[v], pre_processed=True)                        # (in place, taken as given)
+            elif sparse.is_sparse(data[v]):
                 eng.set_view_sparse(v, data[v], pre_processed=True)                                    # (already pre-processed)
             else:
                 device_views.upload(eng, v, data[v])                                                   # (a tensor: in place)
@@ -132,6 +137,12 @@ def res_nmtf_inner(data, row_indices, column_indices,
     as ``t.double().cpu().numpy()`` would be, and never converted to NumPy.  A CPU tensor is taken as its NumPy array.
     ``ValueError`` for a non-floating dtype, another device, or a tensor that is not 2-D; ``host_init=True`` without
     explicit initial factors raises ``NotImplementedError`` for such a view, as for a sparse one.
+
+    A 2-D ``sparse_csc`` / ``sparse_csr`` / coalesced ``sparse_coo`` tensor on ``cuda:device_id`` is a SPARSE view
+    (DESIGN.md section 16): uploaded from its own arrays (``Engine.set_view_sparse_device``, values taken as given), checked
+    on the device -- its refusals surface as ``ResnmtfError`` --, bitwise the ``scipy.sparse`` view of the same values and
+    never brought to the host.  Everything said of sparse views above holds for it; a CPU sparse tensor is taken as its
+    ``scipy.sparse`` matrix.
     """
     device_views.check_output(output)
     data = _views(data, device_id)
@@ -146,14 +157,14 @@ def res_nmtf_inner(data, row_indices, column_indices,
                           "spurious-bicluster removal (R/obtain_bicl.r:31-133) is outside the accelerated path; "
                           "pass spurious=False or do it on the R side (INTEGRATION.md).")
     _check_distance(distance)
-    is_sp = [sparse.is_sparse(d) for d in data]
+    is_sp = [sparse.is_sparse_view(d) for d in data]
     if remove:
         _spurious.check_num_repeats(num_repeats)
         if any(is_sp) and not shuffle_sparse:
             raise NotImplementedError("spurious-bicluster removal needs shuffled views: device shuffles of sparse views "
                                       "are not supported")
     for v in range(n_v):
-        if is_sp[v]:
+        if is_sp[v] and sparse.is_sparse(data[v]):      # (a sparse tensor in device memory: the device checks stand in)
             sparse.validate(data[v], f"view {v}")
     if score_bisil and any(is_sp) and not bisil_sparse:
         raise NotImplementedError("the bisilhouette score of sparse views is not supported (dense views only)")
@@ -314,7 +325,7 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
     given = results                 # host copies of the small cluster matrices for the scoring; `given` keeps the caller's
     results = dict(results, row_clusters=[device_views.to_numpy(rc) for rc in results["row_clusters"]],
                    col_clusters=[device_views.to_numpy(cc) for cc in results["col_clusters"]])
-    if spurious_repeats and repeat_runner is None and not shuffle_sparse and any(sparse.is_sparse(d) for d in data):
+    if spurious_repeats and repeat_runner is None and not shuffle_sparse and any(sparse.is_sparse_view(d) for d in data):
         raise NotImplementedError("spurious-bicluster removal needs shuffled views: device shuffles of sparse views "
                                   "are not supported")
     k = int(np.atleast_1d(k)[0])
@@ -510,7 +521,7 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
     spurious_repeats = _spurious.check_num_repeats(num_repeats) if spurious and not no_clusts else 0
     if no_clusts:
         raise ValueError("the k sweep ranks the biclusters by their bisilhouette score: no_clusts=True has none")
-    if any(sparse.is_sparse(d) for d in data):
+    if any(sparse.is_sparse_view(d) for d in data):
         if not bisil_sparse:
             raise NotImplementedError("the k sweep scores with the bisilhouette, which is not supported for sparse views "
                                       "(dense views only); pass k_val")

@@ -212,7 +212,7 @@ def prepare_grouped_job(job: Job, i: int = 0, pre_processed: bool = False, init=
     names, shared-name index pairs, symmetrised restrictions, ``check_data`` unless ``pre_processed``, and the initial
     factors ``init`` = (F, S, G[, lambda, mu]) per view or, when None, ``api.svd_init(data, k_vec, job.seed)`` on the
     host.  Sparse views and jobs over the kernel's limits are refused here."""
-    if any(sparse.is_sparse(d) for d in job.data):
+    if any(sparse.is_sparse_view(d) for d in job.data):
         raise NotImplementedError(f"job {i}: the grouped path takes dense views only; run sparse views with run_jobs")
     data = [np.asarray(d, dtype=np.float64) for d in job.data]
     if any(d.ndim != 2 for d in data):
@@ -265,7 +265,7 @@ def run_jobs_grouped(jobs: Sequence[Job], device_id: int = 0, pre_processed: boo
     if inits is not None and len(inits) != len(jobs):
         raise ValueError("inits must hold one initial state per job")
     for i, job in enumerate(jobs):                    # refusals first, before any SVD or device work
-        if any(sparse.is_sparse(d) for d in job.data):
+        if any(sparse.is_sparse_view(d) for d in job.data):
             raise NotImplementedError(f"job {i}: the grouped path takes dense views only; run sparse views with run_jobs")
         _check_group_limits(i, [np.asarray(d) for d in job.data], int(job.k_val))
     problems = [prepare_grouped_job(job, i, pre_processed, None if inits is None else inits[i]) for i, job in enumerate(jobs)]
@@ -304,10 +304,15 @@ class DeviceData:
                  pre_processed: bool = False):
         # sparse views (scipy.sparse) stay sparse: a canonical, pre-processed CSC copy on the host, from which the
         # sub-samples are gathered, and a sparse view on the device
-        self.sp = [None if not sparse.is_sparse(d) else (sparse.canonical_csc(d) if pre_processed else sparse.check_data_one(d))
-                   for d in data]
-        for c in self.sp:
-            if pre_processed and c is not None:
+        # A sparse tensor in device memory has no host copy: self.sp holds its marker (device_views.SparseDeviceView:
+        # shape and nnz), the device checks stand in for sparse.validate, the device normalises at the base upload, and
+        # its copies and sub-samples are made on the device whatever sparse_on_device says.
+        data = [device_views.host_or_device(d, f"view {v}") for v, d in enumerate(data)]
+        self.sp = [device_views.as_sparse_view(d, device_id, f"view {v}") if device_views.is_sparse_device_view(d) else
+                   (None if not sparse.is_sparse(d) else (sparse.canonical_csc(d) if pre_processed else sparse.check_data_one(d)))
+                   for v, d in enumerate(data)]
+        for v, c in enumerate(self.sp):
+            if pre_processed and c is not None and not self._sp_device(v):
                 sparse.validate(c)
         data = [device_views.as_view(d, device_id, f"view {v}") if c is None else c for v, (d, c) in enumerate(zip(data, self.sp))]
         self.data_shapes = [tuple(d.shape) for d in data]
@@ -320,13 +325,19 @@ class DeviceData:
                            nnz=[None if c is None else c.nnz for c in self.sp])
         self.was_negative = [False] * n_v
         for v in range(n_v):
-            if self.sp[v] is not None:
+            if self._sp_device(v):
+                device_views.upload_sparse(self.base, v, self.sp[v], pre_processed=pre_processed)      # (the device normalises)
+            elif self.sp[v] is not None:
                 self.base.set_view_sparse(v, self.sp[v], pre_processed=True)      # (normalised on the host: self.sp)
             else:           # (a host array: set_view / set_view_raw; a tensor: set_view_device, in place)
                 self.was_negative[v] = device_views.upload(self.base, v, data[v], raw=not pre_processed)
 
     def close(self):
         self.base.close()
+
+    def _sp_device(self, v: int) -> bool:
+        """View ``v`` is a sparse view that came from device memory: ``self.sp[v]`` is its marker, not a host copy."""
+        return isinstance(self.sp[v], device_views.SparseDeviceView)
 
     def _trim_samples(self, samples, max_rounds: int = 20, *, sparse_on_device: bool = False, counts: Optional[dict] = None):
         """``sample_view`` / ``stability_repeat`` (``R/stability_analysis.r:165-190``, ``:233-240``): all-zero rows and
@@ -344,7 +355,7 @@ class DeviceData:
             for i in range(n_v):
                 if len(rows[i]) < 2 or len(cols[i]) < 2:
                     return None
-                if self.sp[i] is not None and sparse_on_device:
+                if self.sp[i] is not None and (sparse_on_device or self._sp_device(i)):
                     count = self.base.subsample_count_sparse(i, rows[i], cols[i])
                     if counts is not None:
                         counts[i] = (rows[i], cols[i], count)
@@ -409,7 +420,7 @@ class DeviceData:
         if shuffle_seed is not None and any(c is not None for c in self.sp) and not shuffle_sparse:
             raise NotImplementedError("device shuffles of sparse views are not supported")
         # sparse views: the whole view or its sub-sample, gathered on the host
-        on_device = [sparse_on_device and shuffle_seed is None and c is not None for c in self.sp]
+        on_device = [(sparse_on_device or self._sp_device(v)) and shuffle_seed is None and c is not None for v, c in enumerate(self.sp)]
         host_views = [None if c is None or on_device[v] else
                       (c if samples is None else sparse.subsample(c, samples[0][v], samples[1][v])[0])
                       for v, c in enumerate(self.sp)]
@@ -418,6 +429,8 @@ class DeviceData:
             if on_device[v]:
                 nnz[v] = self.base.view_storage(v)[1] if samples is None else self._subsample_count(v, samples[0][v], samples[1][v], counts)
         more = {"sparse_on_device": True} if any(on_device) else {}      # (off: the calls are exactly the earlier ones)
+        if any(on_device) and not sparse_on_device:
+            more = {"sparse_on_device": on_device}                        # (view by view: scipy.sparse views keep the host route)
         with Engine([s[0] for s in shapes], [s[1] for s in shapes], [k] * n_v, device_id=self.device_id, nnz=nnz) as eng:
             load_child(eng, self.base, seed, shuffle_seed=shuffle_seed, samples=samples, host_views=host_views,
                        coupling=(self.phi, self.xi, self.psi, rn, cn), shuffle_sparse=shuffle_sparse, **more)

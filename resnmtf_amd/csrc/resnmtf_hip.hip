@@ -35,6 +35,7 @@
 #include <rocprim/rocprim.hpp>
 #include "resnmtf_sparse_shuffle.hip.inc"
 #include "resnmtf_sparse_subsample.hip.inc"
+#include "resnmtf_sparse_device_view.hip.inc"
 #include "resnmtf_jsd.hip.inc"
 #include "resnmtf_group.hip.inc"
 #include "resnmtf_bisil.hip.inc"
@@ -1589,8 +1590,14 @@ int build_half_images(resnmtf_handle* h, ViewState& vs) {
     // widening is exact whatever the step, the step is taken out once per output in f32)
     vs.xscale = vs.u16 ? 65535.f / mx : std::ldexp(1.f, 14 - ex);
   }
-  hipLaunchKernelGGL(pack_half_kernel, dim3((unsigned)(((size_t)(vs.n_pad / 4) * 64 * (vs.m_pad / 64) + 255) / 256)), dim3(256), 0,
-                     h->stream, vs.side[SIDE_G].X, vs.side[SIDE_G].ldx, vs.n_pad, vs.m_pad / 64, vs.xscale, vs.side[SIDE_G].X16, vs.side[SIDE_G].ld16, vs.u16 ? 1 : 0, scratch + 1);
+  // the squared quantisation error: one partial per block of the first pack, then a fixed-order sum (no float atomics: the
+  // figure resnmtf_view_image_info reports is the same on every run and for every route that left the same image)
+  const unsigned pack_blocks = (unsigned)(((size_t)(vs.n_pad / 4) * 64 * (vs.m_pad / 64) + 255) / 256);
+  double* sq_part = sc.take<double>(pack_blocks);
+  if (!sq_part) return h->fail_hip("2-byte images (hipMalloc)", sc.error());
+  hipLaunchKernelGGL(pack_half_kernel, dim3(pack_blocks), dim3(256), 0,
+                     h->stream, vs.side[SIDE_G].X, vs.side[SIDE_G].ldx, vs.n_pad, vs.m_pad / 64, vs.xscale, vs.side[SIDE_G].X16, vs.side[SIDE_G].ld16, vs.u16 ? 1 : 0, sq_part);
+  hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, h->stream, sq_part, (int)pack_blocks, scratch + 1);
   hipLaunchKernelGGL(pack_half_kernel, dim3((unsigned)(((size_t)(vs.m_pad / 4) * 64 * (vs.n_pad / 64) + 255) / 256)), dim3(256), 0,
                      h->stream, vs.side[SIDE_F].X, vs.side[SIDE_F].ldx, vs.m_pad, vs.n_pad / 64, vs.xscale, vs.side[SIDE_F].X16, vs.side[SIDE_F].ld16, vs.u16 ? 1 : 0,
                      (double*)nullptr);
@@ -2098,8 +2105,13 @@ SparseBuild take_sparse_build(Scratch& sc, long long nnz, int n, int m) {
 // so the sorted order is unique and every correct sort gives the same bits); sorted by r' m + c' they are the CSR; then
 // the masks of the lines without an entry > 0, the values (normalised or as they are), data_norms, the plan of the
 // passes and the view's state.  nnz = 0: zero pointers, every line empty, nothing of size zero launched.
+// The seam of resnmtf_set_view_sparse_device (the shuffle and the sub-sample leave both at their defaults): `presorted`
+// -- the keys already ascend strictly, the first sort is skipped and key[0] / pay[0] go straight to the CSC stage;
+// `check_sorted` -- called with the sorted keys between the first sort and the first store into the view's own arrays,
+// a non-zero return (the refusal, already recorded on dst) ends the build there.
 int finish_sparse_build(resnmtf_handle* dst, ViewState& a, Scratch& sc, const SparseBuild& sb, long long nnz, int normalise, hipError_t e,
-                        const char* what) {
+                        const char* what, bool presorted = false,
+                        const std::function<int(const unsigned long long*)>& check_sorted = nullptr) {
   const int n = a.n, m = a.m;
   hipStream_t st = dst->stream;
   std::vector<long long> cp((size_t)m + 1, 0), rp((size_t)n + 1, 0);
@@ -2127,7 +2139,9 @@ int finish_sparse_build(resnmtf_handle* dst, ViewState& a, Scratch& sc, const Sp
     tmp_bytes = std::max<size_t>(std::max(tmp_bytes, tmp_bytes2), 8);
     void* tmp = e == hipSuccess ? sc.take<char>(tmp_bytes) : nullptr;
     if (e == hipSuccess) e = sc.error();
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kb, vb, (size_t)nnz, 0u, end_bit, st);
+    if (e == hipSuccess && !presorted) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kb, vb, (size_t)nnz, 0u, end_bit, st);
+    if (e == hipSuccess && check_sorted)
+      if (int rc = check_sorted(kb.current())) return rc;
     if (e == hipSuccess) {
       v64 = vb.current();
       hipLaunchKernelGGL(sorted_lines_kernel, dim3(grid), dim3(256), 0, st, kb.current(), nnz, (unsigned long long)n, m, a.side[SIDE_G].sp_ptr, a.side[SIDE_G].sp_idx);
@@ -2273,6 +2287,125 @@ int resnmtf_subsample_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* sr
     e = hipGetLastError();
   }
   return finish_sparse_build(dst, a, sc, sb, nnz, 0, e, "subsample_view_sparse");
+}
+
+// A sparse view from CSC / CSR / COO arrays in the caller's device memory (resnmtf_sparse_device_view.hip.inc, DESIGN.md
+// section 16): checked on the device, turned into (position, value) pairs and built by finish_sparse_build.  Transient
+// device memory: SparseBuild's 40 bytes per entry + m flag bytes + the two flag words.
+int resnmtf_set_view_sparse_device(resnmtf_handle* h, int v, int layout, const void* ptr_or_rows, const void* idx_or_cols, int index_type,
+                                   const void* values, int dtype, long long nnz, int pre_processed, void* stream) {
+  const char* what = "set_view_sparse_device";
+  const std::string w = std::string(what) + ": ";
+  if (int rc = check_view(h, v)) return rc;
+  ViewState& vs = h->views[v];
+  if (!vs.sparse) return h->fail(RESNMTF_ERR_INVALID, "the view is dense: upload it with resnmtf_set_view / resnmtf_set_view_raw / resnmtf_set_view_device");
+  if (!vs.owned) return h->fail(RESNMTF_ERR_STATE, w + "a view this handle does not own");
+  if (layout != RESNMTF_SPARSE_CSC && layout != RESNMTF_SPARSE_CSR && layout != RESNMTF_SPARSE_COO)
+    return h->fail(RESNMTF_ERR_INVALID, w + "unknown layout: one of RESNMTF_SPARSE_CSC / _CSR / _COO");
+  if (index_type != RESNMTF_INDEX_I32 && index_type != RESNMTF_INDEX_I64)
+    return h->fail(RESNMTF_ERR_INVALID, w + "unknown index type: RESNMTF_INDEX_I32 or _I64");
+  if (dtype != RESNMTF_DTYPE_F64 && dtype != RESNMTF_DTYPE_F32 && dtype != RESNMTF_DTYPE_F16 && dtype != RESNMTF_DTYPE_BF16)
+    return h->fail(RESNMTF_ERR_INVALID, w + "unknown dtype: one of RESNMTF_DTYPE_F64 / _F32 / _F16 / _BF16");
+  if (nnz < 0) return h->fail(RESNMTF_ERR_INVALID, w + "nnz is negative");
+  if (nnz > vs.nnz_cap)
+    return h->fail(RESNMTF_ERR_INVALID, w + "nnz = " + std::to_string(nnz) + " exceeds the view's nnz capacity " + std::to_string(vs.nnz_cap));
+  const bool coo = layout == RESNMTF_SPARSE_COO, csc = layout == RESNMTF_SPARSE_CSC;
+  if ((!ptr_or_rows && !(coo && nnz == 0)) || ((!idx_or_cols || !values) && nnz > 0))
+    return h->fail(RESNMTF_ERR_INVALID, w + "ptr_or_rows / idx_or_cols / values is NULL");
+  for (const void* p : {ptr_or_rows, idx_or_cols, values})
+    if (p && !on_handle_device(h, p))
+      return h->fail(RESNMTF_ERR_INVALID, w + "an array is not device memory of the handle's device (host data: resnmtf_set_view_csc)");
+  const int n = vs.n, m = vs.m, lines = csc ? m : n;
+  const char* pname = csc ? "col_ptr" : "row_ptr";
+  const char* lname = csc ? "column" : "row";
+  const bool i64 = index_type == RESNMTF_INDEX_I64;
+  HIP_TRY(h, hipSetDevice(h->opt.device_id));
+  if (int rc = sync_both(h)) return rc;
+  hipStream_t st = h->stream;
+  Scratch sc;
+  unsigned long long* flags = sc.take<unsigned long long>(2);      // the failure word, "CSC rows not ascending"
+  unsigned char* col_pos = pre_processed ? nullptr : sc.take<unsigned char>((size_t)m);
+  if (sc.error() != hipSuccess) return h->fail_hip("hipMalloc set_view_sparse_device flags", sc.error());
+  unsigned long long host_flags[2] = {kSpdvNone, 0ull};
+  // the flags as they are on the device after everything enqueued so far; the refusal, if the word holds one
+  auto verdict = [&](const unsigned long long* sorted_keys) -> int {
+    hipError_t e = hipMemcpyAsync(host_flags, flags, sizeof(host_flags), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return h->fail_hip(what, e);
+    if (host_flags[0] == kSpdvNone) return RESNMTF_OK;
+    const unsigned long long kind = host_flags[0] >> 56;
+    const long long at = (long long)(host_flags[0] & ((1ull << 56) - 1ull));
+    const std::string num = std::to_string(at);
+    switch (kind) {
+      case SPDV_PTR_FIRST: return h->fail(RESNMTF_ERR_INVALID, std::string(pname) + "[0] must be 0 (0-based " + (csc ? "CSC)" : "CSR)"));
+      case SPDV_PTR_MONOTONE: return h->fail(RESNMTF_ERR_INVALID, std::string(pname) + " is not monotone (" + lname + " " + num + ")");
+      case SPDV_PTR_LAST: return h->fail(RESNMTF_ERR_INVALID, std::string(pname) + "[" + num + "] must equal nnz = " + std::to_string(nnz));
+      case SPDV_ROW_RANGE: return h->fail(RESNMTF_ERR_INVALID, "row index out of range (entry " + num + ")");
+      case SPDV_COL_RANGE: return h->fail(RESNMTF_ERR_INVALID, "column index out of range (entry " + num + ")");
+      case SPDV_NON_FINITE: return h->fail(RESNMTF_ERR_INVALID, "non-finite entry (entry " + num + ")");
+      case SPDV_NEGATIVE:
+        return h->fail(RESNMTF_ERR_INVALID, "negative entry (entry " + num +
+                       "): make_non_neg (R/utils.r:20-27) shifts a whole column by its minimum, which would turn every implicit zero of a "
+                       "sparse view positive -- shift the data on the host and upload it dense");
+      case SPDV_DUPLICATE: {
+        unsigned long long k = 0;
+        e = hipMemcpy(&k, sorted_keys + at, sizeof(k), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return h->fail_hip(what, e);
+        return h->fail(RESNMTF_ERR_INVALID, "position (row " + std::to_string(k % (unsigned long long)n) + ", column " + std::to_string(k / (unsigned long long)n) +
+                       ") is stored twice: coalesce the entries first (nothing is summed)");
+      }
+      default:
+        return h->fail(RESNMTF_ERR_INVALID, "column " + num +
+                       " is all zero: matrix_normalisation (R/utils.r:86-88) would divide it by zero (a NaN column in the reference)");
+    }
+  };
+  hipError_t e = wait_for_caller(h, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(flags, host_flags, sizeof(host_flags), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && col_pos) e = hipMemsetAsync(col_pos, 0, (size_t)m, st);
+  if (e != hipSuccess) return h->fail_hip(what, e);
+  // ---- the line pointers, judged before any kernel bounds a search by them
+  if (!coo) {
+    if (i64) hipLaunchKernelGGL(sparse_device_ptr_check_kernel<true>, dim3(ceil_div(lines + 1, 256)), dim3(256), 0, st, ptr_or_rows, lines, nnz, flags);
+    else hipLaunchKernelGGL(sparse_device_ptr_check_kernel<false>, dim3(ceil_div(lines + 1, 256)), dim3(256), 0, st, ptr_or_rows, lines, nnz, flags);
+    HIP_TRY(h, hipGetLastError());
+    if (int rc = verdict(nullptr)) return rc;
+  }
+  if (nnz == 0 && !pre_processed)
+    return h->fail(RESNMTF_ERR_INVALID, "column 0 is all zero: matrix_normalisation (R/utils.r:86-88) would divide it by zero (a NaN column in the reference)");
+  // ---- the entries: checks, keys, values
+  const SparseBuild sb = take_sparse_build(sc, nnz, n, m);
+  if (sc.error() != hipSuccess) return h->fail_hip("hipMalloc set_view_sparse_device build", sc.error());
+  if (nnz > 0) {
+    const dim3 grid((unsigned)((nnz + 255) / 256));
+    pick_int<RESNMTF_SPARSE_CSC, RESNMTF_SPARSE_CSR, RESNMTF_SPARSE_COO>(layout, [&](auto lay) {
+      pick_bools([&](auto wide) {
+        pick_int<RESNMTF_DTYPE_F64, RESNMTF_DTYPE_F32, RESNMTF_DTYPE_F16, RESNMTF_DTYPE_BF16>(dtype, [&](auto dt) {
+          hipLaunchKernelGGL((sparse_device_entries_kernel<decltype(lay)::value, decltype(wide)::value, decltype(dt)::value>), grid, dim3(256), 0, st,
+                             ptr_or_rows, idx_or_cols, values, nnz, n, m, sb.key[0], reinterpret_cast<double*>(sb.pay[0]), col_pos, flags);
+        });
+      }, i64);
+    });
+    if (col_pos) hipLaunchKernelGGL(sparse_device_columns_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, col_pos, m, flags);
+    HIP_TRY(h, hipGetLastError());
+    if (int rc = verdict(nullptr)) return rc;
+  }
+  // ---- the build.  A refusal at the duplicates stage comes before anything is stored into the view's arrays: what
+  // finish_sparse_build has done to the empty-line state by then is put back.
+  const bool presorted = csc && host_flags[1] == 0ull;
+  const int empty_rows = vs.empty_rows, empty_cols = vs.empty_cols;
+  std::vector<unsigned char> empty_mask = vs.empty_mask;
+  h->resume_ok = false;
+  std::function<int(const unsigned long long*)> duplicates;
+  if (!presorted && nnz > 1)
+    duplicates = [&](const unsigned long long* sorted_keys) -> int {
+      hipLaunchKernelGGL(sparse_device_duplicates_kernel, dim3((unsigned)((nnz + 254) / 256)), dim3(256), 0, st, sorted_keys, nnz, flags);
+      HIP_TRY(h, hipGetLastError());
+      return verdict(sorted_keys);
+    };
+  const int rc = finish_sparse_build(h, vs, sc, sb, nnz, pre_processed ? 0 : 1, hipSuccess, what, presorted, duplicates);
+  if (rc != RESNMTF_OK) { vs.empty_rows = empty_rows; vs.empty_cols = empty_cols; vs.empty_mask = std::move(empty_mask); return rc; }
+  vs.empty_rows = vs.empty_cols = 0; vs.empty_mask.clear();      // (as after resnmtf_set_view_csc: not device-drawn data)
+  return RESNMTF_OK;
 }
 
 // resnmtf_copy_view for sparse views: both pointer arrays, both index arrays, both value arrays and data_norms device to

@@ -257,7 +257,7 @@ static __global__ __launch_bounds__(256) void max_entry_kernel(const float* __re
 // entry -- on block-structured data an order of magnitude less in Frobenius norm (tools/quant_study.py)
 static __global__ __launch_bounds__(256) void pack_half_kernel(const float* __restrict__ X32, size_t ts32, int rows_pad, int ntiles,
                                                         float scale, _Float16* __restrict__ X16, size_t ts16, int u16,
-                                                        double* __restrict__ sq_err /* += sum (x~ - x)^2, or nullptr */) {
+                                                        double* __restrict__ sq_err /* [gridDim.x]: the block's sum (x~ - x)^2, or nullptr */) {
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;       // (tile, row group, column)
   const size_t per_tile = (size_t)(rows_pad / 4) * 64;
   __shared__ double red[4];
@@ -293,12 +293,12 @@ static __global__ __launch_bounds__(256) void pack_half_kernel(const float* __re
     *reinterpret_cast<h4*>(dst) = v;
   }
   }
-  if (sq_err) {                                         // block sum -> one atomic per block (order-independent use: a threshold test)
+  if (sq_err) {                                         // one partial per block, summed in a fixed order by reduce_sum_kernel: the same bits on every run
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) e2 += __shfl_xor(e2, off);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = e2;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(sq_err, red[0] + red[1] + red[2] + red[3]);
+    if (threadIdx.x == 0) sq_err[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
   }
 }
 

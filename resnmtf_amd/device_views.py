@@ -6,9 +6,15 @@ only be a tensor when the caller has imported it.
 ``RawDeviceView`` marks a device tensor whose non-negativity shift and column normalisation (``check_data``,
 ``R/utils.r:416,422``) are still to be done: ``problem.prepare(normalise=True)`` wraps a device tensor in it instead of
 pre-processing it on the host, and the upload then runs them on the device (``raw=True``), as ``resnmtf_set_view_raw``
-does for host data."""
+does for host data.
+
+Sparse ``torch`` tensors: a 2-D ``sparse_csc`` / ``sparse_csr`` / (coalesced) ``sparse_coo`` tensor
+on the engine's GPU is a SPARSE view, uploaded from its own index and value arrays (``Engine.set_view_sparse_device``) and
+never brought to the host; the host layer keeps it as a ``SparseDeviceView`` -- the tensor, its shape and its nnz, no host
+copy.  A CPU sparse tensor becomes the ``scipy.sparse.csc_matrix`` of its values and takes the host route."""
 from __future__ import annotations
 
+import copy
 import sys
 import warnings
 
@@ -24,6 +30,97 @@ def _torch():
 def is_tensor(x) -> bool:
     t = _torch()
     return t is not None and isinstance(x, t.Tensor)
+
+
+def is_sparse_tensor(x) -> bool:
+    """A ``torch`` tensor of any sparse layout (COO, CSR, CSC, BSR, BSC)."""
+    return is_tensor(x) and x.layout != _torch().strided
+
+
+class SparseDeviceView:
+    """A sparse CUDA tensor as the host layer keeps a sparse view that lives in device memory: ``tensor``, ``shape``,
+    ``nnz`` (stored entries) and ``raw`` -- True when the column normalisation of ``check_data`` (``R/utils.r:86-88``)
+    is still to be done, at every upload of it (``pre_processed=False``), as for a ``RawDeviceView``."""
+
+    def __init__(self, tensor, raw: bool = False):
+        self.tensor = tensor
+        self.shape = tuple(tensor.shape)
+        self.nnz = int(tensor._nnz())
+        self.raw = bool(raw)
+        self.ndim = 2
+
+    def as_raw(self):
+        out = copy.copy(self)            # (the same tensor: nothing is read from it again)
+        out.raw = True
+        return out
+
+
+def check_sparse_tensor(t, what: str = "view"):
+    """The refusals of a sparse tensor view that need no device: a ``sparse_csc`` / ``sparse_csr`` / ``sparse_coo``
+    layout, 2-D without dense or batch dimensions, floating values, int32 / int64 indices, a coalesced COO."""
+    torch = _torch()
+    if t.layout not in (torch.sparse_csc, torch.sparse_csr, torch.sparse_coo):
+        raise ValueError(f"{what}: a sparse tensor view must be sparse_csc, sparse_csr or sparse_coo, got {t.layout} "
+                         "(convert it with .to_sparse_csc())")
+    if t.dense_dim() != 0:
+        raise ValueError(f"{what}: a hybrid sparse tensor (dense dimensions) is not a view")
+    if t.ndim != 2:
+        raise ValueError(f"{what}: a sparse tensor view must be 2-D, got {t.ndim} dimensions (batched tensors are not supported)")
+    if not t.dtype.is_floating_point:
+        raise ValueError(f"{what}: a tensor view must have a floating dtype, got {t.dtype}")
+    if t.layout == torch.sparse_coo and not t.is_coalesced():
+        raise ValueError(f"{what}: the COO tensor is not coalesced: call .coalesce() first (a position stored twice is "
+                         "refused, nothing is summed)")
+    index = sparse_tensor_parts(t)[0]
+    if index.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{what}: the indices of a sparse tensor view must be int32 or int64, got {index.dtype}")
+
+
+def sparse_tensor_parts(t):
+    """(pointers or row indices, indices or column indices, values) of a checked 2-D sparse tensor, as torch holds them."""
+    torch = _torch()
+    if t.layout == torch.sparse_csc:
+        return t.ccol_indices(), t.row_indices(), t.values()
+    if t.layout == torch.sparse_csr:
+        return t.crow_indices(), t.col_indices(), t.values()
+    idx = t._indices()
+    return idx[0], idx[1], t._values()
+
+
+def sparse_tensor_to_scipy(t):
+    """A CPU sparse tensor (checked) as the ``scipy.sparse.csc_matrix`` of its values widened to fp64."""
+    import scipy.sparse as sp
+    torch = _torch()
+    a, b, vals = (x.detach() for x in sparse_tensor_parts(t))
+    vals = vals.to(torch.float64).numpy()
+    a, b = a.numpy(), b.numpy()
+    shape = tuple(t.shape)
+    if t.layout == torch.sparse_csc:
+        return sp.csc_matrix((vals, b, a), shape=shape)
+    if t.layout == torch.sparse_csr:
+        return sp.csc_matrix(sp.csr_matrix((vals, b, a), shape=shape))
+    return sp.csc_matrix(sp.coo_matrix((vals, (a, b)), shape=shape))
+
+
+def is_sparse_device_view(x) -> bool:
+    """A sparse view that lives in device memory: a ``SparseDeviceView`` or a sparse tensor that is not on the CPU."""
+    return isinstance(x, SparseDeviceView) or (is_sparse_tensor(x) and x.device.type != "cpu")
+
+
+def as_sparse_view(x, device_id: int = 0, what: str = "view") -> SparseDeviceView:
+    """A sparse CUDA tensor (or ``SparseDeviceView``) as a ``SparseDeviceView``, after the checks: ``check_sparse_tensor``
+    and the device (``ValueError`` otherwise)."""
+    t = x.tensor if isinstance(x, SparseDeviceView) else x
+    check_sparse_tensor(t, what)
+    if t.device.type != "cuda" or t.device.index != int(device_id):
+        raise ValueError(f"{what}: the tensor lives on {t.device}, the engine on cuda:{int(device_id)}")
+    return x if isinstance(x, SparseDeviceView) else SparseDeviceView(t)
+
+
+def upload_sparse(eng, v: int, x: SparseDeviceView, pre_processed: bool = True):
+    """``x`` into ``eng``'s sparse view ``v`` (``Engine.set_view_sparse_device``); a ``raw`` view is normalised on the
+    device whatever ``pre_processed`` says."""
+    eng.set_view_sparse_device(v, x.tensor, pre_processed=pre_processed and not x.raw)
 
 
 class RawDeviceView:
@@ -42,8 +139,9 @@ class RawDeviceView:
 
 
 def is_device_view(x) -> bool:
-    """A view that is uploaded from device memory: a CUDA tensor or a ``RawDeviceView``."""
-    return isinstance(x, RawDeviceView) or (is_tensor(x) and x.device.type != "cpu")
+    """A view that is uploaded from device memory: a CUDA tensor (dense or sparse), a ``RawDeviceView`` or a
+    ``SparseDeviceView``."""
+    return isinstance(x, (RawDeviceView, SparseDeviceView)) or (is_tensor(x) and x.device.type != "cpu")
 
 
 def check_tensor(t, what: str = "view"):
@@ -55,7 +153,11 @@ def check_tensor(t, what: str = "view"):
 
 
 def host_or_device(x, what: str = "view"):
-    """A CPU tensor as the fp64 array of its values (after the checks); everything else as it is."""
+    """A CPU tensor as the fp64 array of its values (after the checks) -- a sparse one as the ``scipy.sparse.csc_matrix``
+    of them; everything else as it is."""
+    if is_sparse_tensor(x):
+        check_sparse_tensor(x, what)
+        return sparse_tensor_to_scipy(x) if x.device.type == "cpu" else x
     if is_tensor(x):
         check_tensor(x, what)
         if x.device.type == "cpu":
@@ -66,11 +168,16 @@ def host_or_device(x, what: str = "view"):
 def as_view(x, device_id: int = 0, what: str = "view"):
     """A dense view as the host layer keeps it: a CUDA tensor (or ``RawDeviceView``) as it is, after the checks -- 2-D,
     floating, on ``cuda:device_id`` (``ValueError`` otherwise) --, a CPU tensor as the fp64 array of its values, anything
-    else as ``np.asarray(x, dtype=np.float64)``."""
+    else as ``np.asarray(x, dtype=np.float64)``.  A sparse tensor is never taken for a dense view: on the GPU it becomes a
+    ``SparseDeviceView`` (``as_sparse_view``), on the CPU a ``scipy.sparse.csc_matrix``; both are sparse views."""
     if isinstance(x, RawDeviceView):
         as_view(x.tensor, device_id, what)
         return x
     x = host_or_device(x, what)
+    if is_sparse_device_view(x):
+        return as_sparse_view(x, device_id, what)
+    if type(x).__module__.startswith("scipy.sparse"):
+        return x
     if not is_tensor(x):
         return np.asarray(x, dtype=np.float64)
     if x.device.type != "cuda" or x.device.index != int(device_id):

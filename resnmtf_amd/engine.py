@@ -287,6 +287,37 @@ class Engine:
         self._check(self._lib.resnmtf_set_view_csc(self._h, v, col_ptr.ctypes.data_as(C.POINTER(C.c_longlong)),
                                                    _ip(row_idx), _dp(vals), 1 if pre_processed else 0))
 
+    def set_view_sparse_device(self, v: int, tensor, pre_processed: bool = False):
+        """Upload a sparse view from device memory (``resnmtf_set_view_sparse_device``): ``tensor`` is a 2-D ``torch``
+        tensor of layout ``sparse_csc``, ``sparse_csr`` or (coalesced) ``sparse_coo`` on this engine's GPU, floating values
+        (fp64 / fp32 / fp16 / bf16), int32 or int64 indices, its entries in any order.  Its arrays are read in place,
+        ordered after the work enqueued on torch's current stream of that device, checked on the device (a refusal raises
+        ``ResnmtfError`` and leaves the view as it was) and may be freed on return.  ``pre_processed`` as for
+        ``set_view_sparse``.  The view is bit for bit the one ``resnmtf_set_view_csc`` makes of the canonical CSC of the
+        same values widened to fp64 (explicit zeros stay stored)."""
+        import torch            # (lazily: nothing else in this module needs it)
+        from . import device_views
+        if not isinstance(tensor, torch.Tensor):
+            raise TypeError("set_view_sparse_device takes a sparse torch.Tensor (host data: set_view_sparse)")
+        device_views.check_sparse_tensor(tensor, "set_view_sparse_device")
+        layouts = {torch.sparse_csc: _lib.SPARSE_CSC, torch.sparse_csr: _lib.SPARSE_CSR, torch.sparse_coo: _lib.SPARSE_COO}
+        codes = {torch.float64: _lib.DTYPE_F64, torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16,
+                 torch.bfloat16: _lib.DTYPE_BF16}
+        if tensor.dtype not in codes:
+            raise ValueError(f"a tensor view must be fp64, fp32, fp16 or bf16, got {tensor.dtype}")
+        if tuple(tensor.shape) != (self.n_rows[v], self.n_cols[v]):
+            raise ValueError(f"expected shape {(self.n_rows[v], self.n_cols[v])}, got {tuple(tensor.shape)}")
+        if tensor.device.type != "cuda" or tensor.device.index != self.device_id:
+            raise ValueError(f"the tensor lives on {tensor.device}, the engine on cuda:{self.device_id}")
+        tensor = tensor.detach()
+        # (.contiguous() only where a piece is not: the rows of a COO index matrix are, a sliced tensor's pieces may not be)
+        a, b, vals = (x if x.is_contiguous() else x.contiguous() for x in device_views.sparse_tensor_parts(tensor))
+        index_type = _lib.INDEX_I64 if a.dtype == torch.int64 else _lib.INDEX_I32
+        stream = torch.cuda.current_stream(tensor.device).cuda_stream
+        self._check(self._lib.resnmtf_set_view_sparse_device(
+            self._h, v, layouts[tensor.layout], C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), index_type,
+            C.c_void_p(vals.data_ptr()), codes[tensor.dtype], int(tensor._nnz()), 1 if pre_processed else 0, C.c_void_p(stream)))
+
     def view_storage(self, v: int):
         """(is_sparse, nnz of the last upload, nnz capacity) of view ``v`` (``resnmtf_view_storage``)."""
         sp, nz, cap = C.c_int(0), C.c_longlong(0), C.c_longlong(0)

@@ -32,6 +32,18 @@ def svd_init(data: Sequence[np.ndarray], k_vec: Sequence[int], seed: Optional[in
     return init_f, init_s, init_g, init_lam, init_mu
 
 
+def _raw_on_device(d):
+    """A view in device memory whose pre-processing is left to its upload: a dense tensor as a ``RawDeviceView``, a
+    sparse one as a raw ``SparseDeviceView`` (the tensor itself is left as it is)."""
+    if isinstance(d, device_views.RawDeviceView):
+        return d
+    if isinstance(d, device_views.SparseDeviceView):
+        return d.as_raw()
+    if device_views.is_sparse_tensor(d):
+        return device_views.SparseDeviceView(d, raw=True)
+    return device_views.RawDeviceView(d)
+
+
 # a problem as res_nmtf_inner receives it (R/main.r:225-249)
 Prepared = namedtuple("Prepared", "data row_names col_names phi xi psi row_shared col_shared")
 
@@ -42,7 +54,8 @@ def prepare(data, phi, xi, psi, row_names, col_names, *, normalise: bool, symmet
     or, with ``symmetrise=False``, taken as the symmetrised matrices they already are (None = zeros) -- and, with
     ``normalise``, the non-negativity shift and column normalisation on the host (``check_data``, ``:237``).  A CPU
     ``torch`` tensor is taken as its NumPy array; a tensor on a GPU is never brought to the host: with ``normalise`` it
-    is wrapped in ``device_views.RawDeviceView`` and pre-processed on the device at its upload."""
+    is wrapped in ``device_views.RawDeviceView`` (a sparse one in a raw ``device_views.SparseDeviceView``) and pre-processed
+    on the device at its upload."""
     n_v = len(data)
     data = [device_views.host_or_device(d, f"view {v}") for v, d in enumerate(data)]
     rn, cn = naming.give_names(data, phi, psi, row_names, col_names)
@@ -52,8 +65,7 @@ def prepare(data, phi, xi, psi, row_names, col_names, *, normalise: bool, symmet
     else:
         phi, psi, xi = (np.zeros((n_v, n_v)) if m is None else np.asarray(m, dtype=np.float64) for m in (phi, psi, xi))
     if normalise:
-        data = [device_views.RawDeviceView(d) if device_views.is_tensor(d) else
-                (d if isinstance(d, device_views.RawDeviceView) else naming.check_data([d])[0]) for d in data]
+        data = [_raw_on_device(d) if device_views.is_device_view(d) else naming.check_data([d])[0] for d in data]
     return Prepared(list(data), rn, cn, phi, xi, psi, *shared)
 
 
@@ -105,12 +117,13 @@ def load_child(eng, src, seed: int, *, shuffle_seed: Optional[int] = None, sampl
     ``shuffle_seed``; sparse views only with ``shuffle_sparse``, ``_draw_shuffle``), sub-sampled (``samples = (row_samples, col_samples)``) or copied -- a sparse view is uploaded from
     ``host_views[v]`` instead, or with ``sparse_on_device`` (opt-in) sub-sampled / copied on the device as a sparse view
     (``Engine.subsample_view_sparse_from`` / ``copy_view_sparse_from``; ``host_views`` is then not read for it) -- then the
-    device SVD init with ``seed + v``; at last ``coupling`` = (phi, xi, psi,
+    device SVD init with ``seed + v``; ``sparse_on_device`` may also be one flag per view (a sparse view that came from
+    device memory has no host copy and always takes the device route); at last ``coupling`` = (phi, xi, psi,
     row_names, col_names), or for shuffles none: no restrictions, uncoupled (``R/obtain_bicl.r:35-39``)."""
     for v in range(eng.n_views):
         if shuffle_seed is not None:
             _draw_shuffle(eng, v, src, shuffle_seed, shuffle_sparse)
-        elif sparse_on_device and src.sparse[v]:
+        elif (sparse_on_device[v] if isinstance(sparse_on_device, (list, tuple)) else sparse_on_device) and src.sparse[v]:
             if samples is not None:
                 eng.subsample_view_sparse_from(v, src, v, samples[0][v], samples[1][v])
             else:

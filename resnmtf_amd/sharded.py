@@ -54,7 +54,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import naming
+from . import naming, sparse
 from .engine import Engine
 from .problem import couple, inner_result, prepare
 from ._lib import (FACTOR_F, FACTOR_FBLOCK, FACTOR_FBLOCK_ALL, FACTOR_FNEW_RECV, FACTOR_FNEW_SEND, FACTOR_G, FACTOR_GBLOCK,
@@ -939,7 +939,7 @@ def res_nmtf_inner(data, row_indices=None, column_indices=None, init_f=None, ini
     data = list(data)
     if len(data) != n_v:
         raise ValueError("data must have one entry per view (None for views this rank does not own)")
-    if any(d is not None and type(d).__module__.startswith("scipy.sparse") for d in data):
+    if any(d is not None and sparse.is_sparse_view(d) for d in data):
         raise NotImplementedError("sparse views are not supported by the view-sharded driver; use api.res_nmtf_inner "
                                   "on one GPU (resnmtf_create_sparse)")
     k_all = [int(np.asarray(f).shape[1]) for f in init_f]

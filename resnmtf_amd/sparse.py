@@ -15,6 +15,14 @@ def is_sparse(x) -> bool:
     return type(x).__module__.startswith("scipy.sparse")
 
 
+def is_sparse_view(x) -> bool:
+    """True for every view that is stored sparse on the device: a ``scipy.sparse`` matrix, or a sparse ``torch`` tensor in
+    device memory / its ``device_views.SparseDeviceView`` (no host copy exists of those: ``validate`` and the host
+    sub-samples do not apply, the device checks and the device routes stand in)."""
+    from . import device_views
+    return is_sparse(x) or device_views.is_sparse_device_view(x)
+
+
 def canonical_csc(x):
     """A canonical fp64 CSC copy of ``x``: sorted row indices, duplicates summed, explicit zeros dropped."""
     import scipy.sparse as sp
