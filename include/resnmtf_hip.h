@@ -598,6 +598,19 @@ int resnmtf_relevance_masked(resnmtf_handle* h, int v, resnmtf_handle* ref, int 
 int resnmtf_jsd_pairs(int device_id, int n, int n_cols, const double* cols, int n_pairs, const int* pairs, double* out);
 
 /*
+ * resnmtf_jsd_pairs (the same body, kernels, refusals and out, bit for bit) that also hands back what its stages made,
+ * for tests of each stage against a reference; every one of the three may be NULL (all NULL = resnmtf_jsd_pairs):
+ *   sorted  [n_cols][n]          every column ascending, -0 stored as +0: the buffer the statistics and pair kernels
+ *                                read (the last merge destination);
+ *   stats   [n_cols][2]          per column bw.nrd0 and the maximum;
+ *   dens    [n_pairs][2][512]    per pair, side 0 (x1) then side 1 (x2): stats::density on seq(0, M, length = 512) after
+ *                                the values beyond max(c) are zeroed and before the division by the sum.
+ * With n_pairs = 0, sorted and stats are still produced when asked for.
+ */
+int resnmtf_jsd_stages(int device_id, int n, int n_cols, const double* cols, int n_pairs, const int* pairs, double* out,
+                       double* sorted, double* stats, double* dens);
+
+/*
  * Spurious-bicluster scores of a factorisation against R shuffled ones, all on the device (check_biclusters with
  * get_thresholds, R/obtain_bicl.r:80-133): view v of h and of each of the R handles in shuffles (same device, same n
  * and k = K, with factors) is normalised as resnmtf_finalise normalises F (F / colSums(F), the same kernels and bits)

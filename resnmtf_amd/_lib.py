@@ -136,6 +136,7 @@ SIGNATURES = {
     "resnmtf_relevance": (C.c_int, [_h, C.c_int, _h, C.c_int, _ip, _ip, _dp]),
     "resnmtf_relevance_masked": (C.c_int, [_h, C.c_int, _h, C.c_int, _ip, _ip, C.POINTER(C.c_ubyte), _dp]),
     "resnmtf_jsd_pairs": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, _ip, _dp]),
+    "resnmtf_jsd_stages": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, _ip, _dp, _dp, _dp, _dp]),
     "resnmtf_spurious_scores": (C.c_int, [_h, C.c_int, C.POINTER(_h), C.c_int, _dp, _dp]),
     "resnmtf_group_run": (C.c_int, [C.c_int, C.c_int, C.POINTER(GroupJob), C.c_double, C.c_int]),
     "resnmtf_bisil": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),

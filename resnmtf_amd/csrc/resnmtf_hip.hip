@@ -3839,23 +3839,28 @@ int resnmtf_bisil_sparse(resnmtf_handle* h, int v, int k, const double* row_clus
 namespace {
 // The JSD pipeline, enqueued on `st`: the n_cols columns of `cols` ([n_cols][n]) sorted (tiles in sort_a, then merge passes
 // between sort_a and sort_b), the statistics of every column, then out[p] for the n_pairs column pairs of `pairs`, in grids
-// of at most 2^20 workgroups.  All pointers are device memory; the caller checks hipGetLastError.
-void enqueue_jsd(hipStream_t st, const double* cols, int n, int n_cols, double* sort_a, double* sort_b, double* stats, const int* pairs,
-                 long long n_pairs, double* out) {
+// of at most 2^20 workgroups.  `dens` (nullable): [n_pairs][2][512], the pair kernel's densities.  Returns the buffer the
+// statistics and pair kernels read (the last merge destination: sort_a or sort_b).  All pointers are device memory; the
+// caller checks hipGetLastError.
+const double* enqueue_jsd(hipStream_t st, const double* cols, int n, int n_cols, double* sort_a, double* sort_b, double* stats,
+                          const int* pairs, long long n_pairs, double* out, double* dens) {
   hipLaunchKernelGGL(jsd_tile_sort_kernel, dim3(ceil_div(n, JSD_TILE), (unsigned)n_cols), dim3(JSD_SORT_THREADS), 0, st, cols, sort_a, n);
   double *src = sort_a, *dst = sort_b;
   for (int width = JSD_TILE; width < n; width *= 2) {
     hipLaunchKernelGGL(jsd_merge_kernel, dim3(ceil_div(n, 256), (unsigned)n_cols), dim3(256), 0, st, (const double*)src, dst, n, width);
     std::swap(src, dst);
   }
-  hipLaunchKernelGGL(jsd_stats_kernel, dim3((unsigned)n_cols), dim3(256), 0, st, (const double*)src, cols, n, stats);
+  hipLaunchKernelGGL(jsd_stats_kernel, dim3((unsigned)n_cols), dim3(256), 0, st, (const double*)src, cols, n, std::pow((double)n, -0.2),
+                     stats);
   for (long long p0 = 0; p0 < n_pairs; p0 += 1 << 20)
     hipLaunchKernelGGL(jsd_pair_kernel, dim3((unsigned)std::min<long long>(1 << 20, n_pairs - p0)), dim3(JSD_N), 0, st, (const double*)src,
-                       (const double*)stats, n, pairs + 2 * (size_t)p0, out + p0);
+                       (const double*)stats, n, pairs + 2 * (size_t)p0, out + p0, dens ? dens + 2 * (size_t)JSD_N * (size_t)p0 : nullptr);
+  return src;
 }
 }  // namespace
 
-int resnmtf_jsd_pairs(int device_id, int n, int n_cols, const double* cols, int n_pairs, const int* pairs, double* out) {
+int resnmtf_jsd_stages(int device_id, int n, int n_cols, const double* cols, int n_pairs, const int* pairs, double* out,
+                       double* sorted, double* stats_out, double* dens) {
   auto bad = [](const char* msg) { g_create_error = msg; return RESNMTF_ERR_INVALID; };
   if (n < 2) return bad("n must be at least 2 (bw.nrd0 needs two data points)");
   if (n_cols < 1 || n_cols > 65535 || n_pairs < 0) return bad("n_cols must be in [1, 65535] and n_pairs non-negative");
@@ -3866,7 +3871,7 @@ int resnmtf_jsd_pairs(int device_id, int n, int n_cols, const double* cols, int 
     if (!std::isfinite(cols[i])) return bad("cols has a non-finite entry");
   for (int p = 0; p < 2 * n_pairs; ++p)
     if (pairs[p] < 0 || pairs[p] >= n_cols) return bad("pair index out of range");
-  if (n_pairs == 0) return RESNMTF_OK;
+  if (n_pairs == 0 && !sorted && !stats_out) return RESNMTF_OK;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_error = "no HIP device"; return RESNMTF_ERR_NO_DEVICE; }
   if (device_id < 0 || device_id >= ndev) return bad("device_id out of range");
@@ -3875,8 +3880,9 @@ int resnmtf_jsd_pairs(int device_id, int n, int n_cols, const double* cols, int 
   hipStream_t st = nullptr;
   e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
   if (e != hipSuccess) { g_create_error = std::string("hipStreamCreate: ") + hipGetErrorString(e); return RESNMTF_ERR_HIP; }
-  // [orig n C][sort A n C][sort B n C][stats 2 C][out P] doubles | [pairs 2 P] ints
-  const size_t n_dbl = 3 * total + 2 * (size_t)n_cols + (size_t)n_pairs;
+  // [orig n C][sort A n C][sort B n C][stats 2 C][out P][dens 1024 P, when asked for] doubles | [pairs 2 P] ints
+  const size_t n_dens = dens ? 2 * (size_t)JSD_N * (size_t)n_pairs : 0;
+  const size_t n_dbl = 3 * total + 2 * (size_t)n_cols + (size_t)n_pairs + n_dens;
   Scratch sc;
   char* buf = sc.take<char>(n_dbl * sizeof(double) + 2 * (size_t)n_pairs * sizeof(int));
   e = sc.error();
@@ -3887,18 +3893,27 @@ int resnmtf_jsd_pairs(int device_id, int n, int n_cols, const double* cols, int 
   }
   double *orig = reinterpret_cast<double*>(buf), *sa = orig + total, *sb = sa + total, *stats = sb + total;
   double* dout = stats + 2 * (size_t)n_cols;
+  double* ddens = dens ? dout + n_pairs : nullptr;
   int* dpairs = reinterpret_cast<int*>(buf + n_dbl * sizeof(double));
+  const double* dsorted = nullptr;
   e = hipMemcpyAsync(orig, cols, total * sizeof(double), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(dpairs, pairs, 2 * (size_t)n_pairs * sizeof(int), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && n_pairs > 0) e = hipMemcpyAsync(dpairs, pairs, 2 * (size_t)n_pairs * sizeof(int), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
-    enqueue_jsd(st, orig, n, n_cols, sa, sb, stats, dpairs, n_pairs, dout);
+    dsorted = enqueue_jsd(st, orig, n, n_cols, sa, sb, stats, dpairs, n_pairs, dout, ddens);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t)n_pairs * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && n_pairs > 0) e = hipMemcpyAsync(out, dout, (size_t)n_pairs * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && sorted) e = hipMemcpyAsync(sorted, dsorted, total * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && stats_out) e = hipMemcpyAsync(stats_out, stats, 2 * (size_t)n_cols * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && n_dens) e = hipMemcpyAsync(dens, ddens, n_dens * sizeof(double), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   (void)hipStreamDestroy(st);
   if (e != hipSuccess) { g_create_error = std::string("jsd_pairs: ") + hipGetErrorString(e); return RESNMTF_ERR_HIP; }
   return RESNMTF_OK;
+}
+
+int resnmtf_jsd_pairs(int device_id, int n, int n_cols, const double* cols, int n_pairs, const int* pairs, double* out) {
+  return resnmtf_jsd_stages(device_id, n, n_cols, cols, n_pairs, pairs, out, nullptr, nullptr, nullptr);
 }
 
 // ---- spurious-bicluster scoring of handles (check_biclusters with get_thresholds, R/obtain_bicl.r:80-133): the pool
@@ -3969,7 +3984,7 @@ int resnmtf_spurious_scores(resnmtf_handle* h, int v, resnmtf_handle* const* shu
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e == hipSuccess && flag) return h->fail(RESNMTF_ERR_INVALID, "a factor has a non-finite entry");
   if (e == hipSuccess) {
-    enqueue_jsd(h->stream, pool, n, (int)C, sa, sb, stats, dpairs, P, dout);
+    enqueue_jsd(h->stream, pool, n, (int)C, sa, sb, stats, dpairs, P, dout, nullptr);
     hipLaunchKernelGGL(jsd_score_mean_kernel, dim3((unsigned)ceil_div(K, 64)), dim3(64), 0, h->stream,
                        (const double*)(dout + P_null), K, (int)RK, dscore);
     e = hipGetLastError();

@@ -25,7 +25,8 @@ constexpr int JSD_N = 512;            // density()'s n
 constexpr int JSD_TILE = 2048;        // entries of one LDS-sorted tile
 constexpr int JSD_SORT_THREADS = 1024;
 constexpr int JSD_KEY_LOW = -2;       // bin keys outside [-1, 511] (no contribution) are clamped to -2 / 512
-constexpr int JSD_KEY_HIGH = 512;
+constexpr int JSD_KEY_HIGH = 512;     // (jsd_pair_kernel bins x <= M < up = M + 4 bw with bw > 0, so xpos < 511: key 510 is the
+                                      // highest any input reaches; 511 and JSD_KEY_HIGH are kept for BinDist's form only)
 constexpr int JSD_KEY_EMPTY = 1 << 30;
 
 __device__ __forceinline__ double jsd_canon(double v) { return v == 0.0 ? 0.0 : v; }
@@ -84,9 +85,12 @@ __device__ double jsd_block_sum256(double v, double* red) {   // fixed tree over
 }
 
 // per column: bw.nrd0 (stats::bw.nrd0) and the maximum; sorted = the sorted columns, orig = the columns as given
-// (bw.nrd0's abs(x[1]) fallback reads the first entry in the caller's order)
+// (bw.nrd0's abs(x[1]) fallback reads the first entry in the caller's order).  n_pow = n^-0.2 from the host's pow, the
+// one R's length(x)^(-0.2) calls: the device's pow is a last bit off it at some n (511, 2048, 2049, 6145 among the
+// tested sizes), which a constant column's bandwidth 0.9 |x[1]| n^-0.2 shows bit for bit
 __global__ void __launch_bounds__(256)
-jsd_stats_kernel(const double* __restrict__ sorted, const double* __restrict__ orig, int n, double* __restrict__ stats) {
+jsd_stats_kernel(const double* __restrict__ sorted, const double* __restrict__ orig, int n, double n_pow,
+                 double* __restrict__ stats) {
   __shared__ double red[4];
   const size_t col = (size_t)blockIdx.x * n;
   const double* x = sorted + col;
@@ -116,7 +120,7 @@ jsd_stats_kernel(const double* __restrict__ sorted, const double* __restrict__ o
     lo = hi;
     if (lo == 0.0) { lo = fabs(orig[col]); if (lo == 0.0) lo = 1.0; }
   }
-  stats[2 * blockIdx.x] = 0.9 * lo * pow((double)n, -0.2);
+  stats[2 * blockIdx.x] = 0.9 * lo * n_pow;
   stats[2 * blockIdx.x + 1] = x[n - 1];
 }
 
@@ -218,10 +222,11 @@ __device__ void jsd_bin(const double* __restrict__ x, int n, double lo, double x
   __syncthreads();
 }
 
-// out[p] = jsd_calc(cols[:, pairs[2p]], cols[:, pairs[2p + 1]])
+// out[p] = jsd_calc(cols[:, pairs[2p]], cols[:, pairs[2p + 1]]); dens (nullable, [n_pairs][2][512], resnmtf_jsd_stages)
+// receives both sides' densities on xout after the zeroing, before the normalisation
 __global__ void __launch_bounds__(JSD_N)
 jsd_pair_kernel(const double* __restrict__ sorted, const double* __restrict__ stats, int n,
-                const int* __restrict__ pairs, double* __restrict__ out) {
+                const int* __restrict__ pairs, double* __restrict__ out, double* __restrict__ dens) {
   __shared__ JsdPairShared sh;
   const int t = threadIdx.x;
   const int p = blockIdx.x;
@@ -266,6 +271,7 @@ jsd_pair_kernel(const double* __restrict__ sorted, const double* __restrict__ st
       else r = ys[i] + (ys[j] - ys[i]) * ((v - xi) / (xj - xi));
     }
     yv[s] = v > mx[s] ? 0.0 : r;
+    if (dens) dens[((size_t)p * 2 + s) * JSD_N + t] = yv[s];
   }
   const double s0 = jsd_block_sum512(yv[0], sh.red);
   const double s1 = jsd_block_sum512(yv[1], sh.red);

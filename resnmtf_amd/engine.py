@@ -50,6 +50,28 @@ def jsd_pairs(cols, pairs, device_id: int = 0) -> np.ndarray:
     return out
 
 
+def jsd_stages(cols, pairs, sorted: bool = True, stats: bool = True, dens: bool = True, device_id: int = 0) -> dict:
+    """``jsd_pairs`` with its stages handed back (``resnmtf_jsd_stages``; for tests of each stage): ``{"out": P scores,
+    "sorted": n x C (every column ascending, as the later kernels read it), "stats": C x 2 (``bw.nrd0``, maximum),
+    "dens": P x 2 x 512 (both sides' zeroed, un-normalised densities)}``; a stage not asked for is ``None``."""
+    lib = _lib.load()
+    cols = _f64_colmajor(cols)
+    if cols.ndim != 2:
+        raise ValueError("cols must be an n x C matrix")
+    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    n, n_cols, n_pairs = int(cols.shape[0]), int(cols.shape[1]), int(len(pairs))
+    out = np.zeros(n_pairs, dtype=np.float64)
+    got = {"out": out,
+           "sorted": np.zeros((n, n_cols), dtype=np.float64, order="F") if sorted else None,
+           "stats": np.zeros((n_cols, 2), dtype=np.float64) if stats else None,
+           "dens": np.zeros((n_pairs, 2, 512), dtype=np.float64) if dens else None}
+    rc = lib.resnmtf_jsd_stages(int(device_id), n, n_cols, _dp(cols), n_pairs, _ip(pairs), _dp(out), _dp(got["sorted"]),
+                                _dp(got["stats"]), _dp(got["dens"]))
+    if rc != _lib.OK:
+        raise ResnmtfError(rc, (lib.resnmtf_last_error(None) or b"").decode())
+    return got
+
+
 def group_run(problems, tol: float = 1.0e-6, max_iters: int = 100000, device_id: int = 0) -> list:
     """Many small factorisations in one call (``resnmtf_group_run``: one workgroup per job, fp64 throughout).
 

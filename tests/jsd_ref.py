@@ -164,13 +164,36 @@ def jsd(p, q):
     return 0.5 * (float(np.sum(t1)) + float(np.sum(t2)))
 
 
-def jsd_calc(x1, x2):
+def column_stats(x):
+    """What the scoring keeps of one column: the column sorted ascending with -0 as +0, ``bw.nrd0(x)`` and ``max(x)``."""
+    x = np.asarray(x, dtype=np.float64)
+    return np.sort(x) + 0.0, bw_nrd0(x), float(np.max(x))
+
+
+def pair_stages(x1, x2):
+    """``jsd_calc`` with its stages: both sides' densities on ``seq(0, max_val, 512)`` after the zeroing beyond the side's
+    own maximum (un-normalised), and the value."""
     max_val = max(float(np.max(x1)), float(np.max(x2)))
     d1x, d1y = density(x1, 0.0, max_val)
     d2x, d2y = density(x2, 0.0, max_val)
     d1y[d1x > np.max(x1)] = 0.0
     d2y[d2x > np.max(x2)] = 0.0
-    return jsd(d1y, d2y)
+    with np.errstate(divide="ignore", invalid="ignore"):     # a density that sums to 0: NaN, as in R
+        return d1y, d2y, jsd(d1y, d2y)
+
+
+def jsd_calc(x1, x2):
+    return pair_stages(x1, x2)[2]
+
+
+def bin_keys(x, M):
+    """``floor(xpos)`` of every entry of ``x`` in ``BinDist`` as ``density(x, 0, M)`` calls it (512 bins from
+    ``-4 bw`` to ``M + 4 bw``): keys 0 .. 510 feed bins ix and ix + 1, key -1 feeds bin 0 only, anything lower nothing."""
+    x = np.asarray(x, dtype=np.float64)
+    bw = bw_nrd0(x)
+    lo, up = 0.0 - 4 * bw, M + 4 * bw
+    xdelta = (up - lo) / 511
+    return np.array([math.floor((xi - lo) / xdelta) for xi in x], dtype=np.int64)
 
 
 def density_mode(scores):
