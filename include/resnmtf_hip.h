@@ -452,6 +452,35 @@ int resnmtf_set_factors(resnmtf_handle* h, int v, const double* F, const double*
                         const double* G, const double* lambda, const double* mu);
 
 /*
+ * The same for initial factors that are ALREADY in device memory (R/update_steps.r:41-56), in any of the four floating
+ * types and with any (non-negative) strides, without a host copy: nothing runs per element on the host.  A matrix is
+ * (ptr, dtype, row_stride, col_stride): ptr points at element (0, 0), element (r, c) is ptr[r * row_stride +
+ * c * col_stride], strides in ELEMENTS (column-major n x k: 1, n; row-major: k, 1; transposed views and slices likewise);
+ * one dtype per matrix.  F n x k, S k x k, G m x k; lambda / mu k x 1 (col_stride is not read), or NULL: they are then
+ * colSums(F) / colSums(G) (R/update_steps.r:55-56), summed on the device per column in ascending row order from 0.0, as
+ * resnmtf_set_factors sums them.  Widening to fp64 is exact for all four types, so the view's whole factor state is BIT
+ * FOR BIT what resnmtf_set_factors leaves when given the same values widened on the host (the operand images are built
+ * by the same code).  Values are not validated (NaN, Inf and negative entries pass, as there).  Works for an owned or
+ * a mirror view, dense or sparse.  The sources must not overlap the handle's own buffers.
+ *   stream  the hipStream_t on which the producer of the matrices was enqueued (NULL: the null stream).  The library
+ *           records an event there and makes its own stream wait for it.  The call returns when the state is built, so
+ *           the sources may be freed on return.
+ * Refused before any device work (RESNMTF_ERR_INVALID / _STATE, text in resnmtf_last_error), the view's factors and
+ * whether it has any left as they were: a NULL handle, a bad view, F / S / G NULL or with a NULL ptr, lambda / mu with
+ * a NULL ptr, an unknown dtype, a negative stride, a pointer that is not device memory of the handle's device, lambda
+ * or mu for a view the handle does not own (RESNMTF_ERR_STATE).
+ * No transient device memory.
+ */
+typedef struct {
+  const void* ptr;                     /* element (0, 0) */
+  int dtype;                           /* RESNMTF_DTYPE_* */
+  long long row_stride, col_stride;    /* in ELEMENTS, >= 0 */
+} resnmtf_device_matrix;
+int resnmtf_set_factors_device(resnmtf_handle* h, int v, const resnmtf_device_matrix* F, const resnmtf_device_matrix* S,
+                               const resnmtf_device_matrix* G, const resnmtf_device_matrix* lambda,
+                               const resnmtf_device_matrix* mu, void* stream);
+
+/*
  * Initial factors of an owned view from its data: init_mats_inner (R/update_steps.r:78-125) --
  * F0 = |U[, 1:k]|, G0 = |V[, 1:k]| of the SVD of X, S0 = |diag(d)[1:k, 1:k]| + |N(0, sigma I)| noise,
  * S0 columns scaled by colSums(F0) * colSums(G0), F0 and G0 column-L1-normalised, lambda / mu their
@@ -522,6 +551,16 @@ int resnmtf_run(resnmtf_handle* h, int n_iters, double tol, int max_iters, doubl
 /* Raw (un-normalised) state, so that a caller can resume exactly.  Any pointer may be NULL. */
 int resnmtf_get_factors(resnmtf_handle* h, int v, double* F, double* S, double* G,
                         double* lambda, double* mu);
+/*
+ * The same raw state (R/update_steps.r:41-56: what the explicit-init branch takes), bitwise, written to caller-owned
+ * DEVICE buffers on the handle's device: fp64 column-major F n x k, S k x k, G m x k, lambda and mu of length k; any may
+ * be NULL.  `stream` as for resnmtf_finalise_device: the library's writes are ordered after the work already enqueued
+ * there and before any work enqueued there after the call returns.  Refused before any device work: a pointer that is
+ * not device memory of the handle's device (RESNMTF_ERR_INVALID), lambda / mu of a view the handle does not own
+ * (RESNMTF_ERR_STATE).  No transient device memory.
+ */
+int resnmtf_get_factors_device(resnmtf_handle* h, int v, double* F, double* S, double* G,
+                               double* lambda, double* mu, void* stream);
 
 /*
  * normalisation_check (R/utils.r:176-195) followed by the binary cluster matrices of

@@ -96,6 +96,14 @@ class GroupJob(C.Structure):
         ("all_error", _dp), ("err_capacity", C.c_int), ("iters_done", _ip),
     ]
 
+
+class DeviceMatrix(C.Structure):
+    """``resnmtf_device_matrix`` (include/resnmtf_hip.h): a strided matrix in device memory, strides in elements."""
+    _fields_ = [("ptr", C.c_void_p), ("dtype", C.c_int), ("row_stride", C.c_longlong), ("col_stride", C.c_longlong)]
+
+
+_dm = C.POINTER(DeviceMatrix)
+
 # name -> (restype, argtypes); must list every symbol include/resnmtf_hip.h declares
 SIGNATURES = {
     "resnmtf_abi_version": (C.c_int, []),
@@ -123,6 +131,7 @@ SIGNATURES = {
     "resnmtf_view_empty_lines": (C.c_int, [_h, C.c_int, _ip, _ip, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
     "resnmtf_get_view": (C.c_int, [_h, C.c_int, _dp]),
     "resnmtf_set_factors": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "resnmtf_set_factors_device": (C.c_int, [_h, C.c_int, _dm, _dm, _dm, _dm, _dm, C.c_void_p]),
     "resnmtf_init_svd": (C.c_int, [_h, C.c_int, C.c_ulonglong, C.c_double, C.c_int, _dp]),
     "resnmtf_init_svd_basis": (C.c_int, [_h, C.c_int, C.c_ulonglong, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _ip]),
     "resnmtf_set_restrictions": (C.c_int, [_h, _dp, _dp, _dp]),
@@ -130,6 +139,7 @@ SIGNATURES = {
     "resnmtf_set_shared_cols": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, _ip, _ip]),
     "resnmtf_run": (C.c_int, [_h, C.c_int, C.c_double, C.c_int, _dp, C.c_int, _ip]),
     "resnmtf_get_factors": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "resnmtf_get_factors_device": (C.c_int, [_h, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "resnmtf_finalise": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "resnmtf_finalise_device": (C.c_int, [_h, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "resnmtf_set_reference_clusters": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp]),

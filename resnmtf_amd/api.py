@@ -70,8 +70,10 @@ def _views(data, device_id: int = 0) -> list:
 
 
 def _load_engine(eng: Engine, data, init_f, init_s, init_g, lam, mu, phi, xi, psi,
-                 row_names, col_names, row_indices, column_indices, seed=None):
-    """``init_f is None``: the initial factors come from the device (``resnmtf_init_svd``)."""
+                 row_names, col_names, row_indices, column_indices, seed=None, device_factors=None):
+    """``init_f is None``: the initial factors come from the device (``resnmtf_init_svd``).  ``device_factors[v]``
+    (``device_views.factor_routes``): view v's initial factors are device tensors and go in through
+    ``Engine.set_factors_device``."""
     for v in range(eng.n_views):
         if eng.owned[v]:
             if isinstance(data[v], device_views.SparseDeviceView):
@@ -82,9 +84,13 @@ def _load_engine(eng: Engine, data, init_f, init_s, init_g, lam, mu, phi, xi, ps
                 device_views.upload(eng, v, data[v])                                                   # (a tensor: in place)
         if init_f is None:
             eng.init_svd(v, seed=_seed(seed) + v)                          # update_steps.r:78-125
+        elif device_factors is not None and device_factors[v]:
+            eng.set_factors_device(v, init_f[v], init_s[v], init_g[v],
+                                   None if lam is None else lam[v], None if mu is None else mu[v])
         else:
             eng.set_factors(v, init_f[v], init_s[v], init_g[v],
-                            None if lam is None else lam[v], None if mu is None else mu[v])
+                            None if lam is None else device_views.to_numpy(lam[v]),
+                            None if mu is None else device_views.to_numpy(mu[v]))
     eng.set_restrictions(phi, xi, psi)
     couple(eng, row_names, col_names, row_indices, column_indices)
 
@@ -97,7 +103,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
                    max_iters: int = 100000, seed: Optional[int] = None, engine_opts: Optional[dict] = None,
                    host_init: bool = False, return_init: bool = False, score_bisil: bool = False,
                    spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False,
-                   sparse_on_device: bool = False, output: str = "numpy"):
+                   sparse_on_device: bool = False, output: str = "numpy", init_lm=None, return_state: bool = False):
     """``res_nmtf_inner`` (``R/main.r:32-140``).
 
     ``data``: list of pre-processed (non-negative, column-normalised) matrices; ``row_indices[v][w]``
@@ -143,6 +149,22 @@ def res_nmtf_inner(data, row_indices, column_indices,
     on the device -- its refusals surface as ``ResnmtfError`` --, bitwise the ``scipy.sparse`` view of the same values and
     never brought to the host.  Everything said of sparse views above holds for it; a CPU sparse tensor is taken as its
     ``scipy.sparse`` matrix.
+
+    Initial factors may be ``torch`` tensors too.  Per view, ``init_f[v]``, ``init_s[v]`` and
+    ``init_g[v]`` that are all tensors on ``cuda:device_id`` (2-D, fp64 / fp32 / fp16 / bf16, any strides) are read in
+    place (``Engine.set_factors_device``), bitwise as ``t.double().cpu().numpy()`` would be; all three on the host (NumPy,
+    or a CPU tensor, taken as its fp64 array) take the host route; a mix within one view, or a tensor on another
+    device, is a ``ValueError`` before any engine exists.  ``init_lm`` (keyword-only): ``(lambdas, mus)``, one entry of
+    k values per view, taken in place of ``colSums(init_f[v])`` / ``colSums(init_g[v])`` (``R/update_steps.r:55-56``);
+    needs explicit initial factors.  ``return_state`` (keyword-only) adds ``"state"``: per view the raw ``(F, S, G, lambda,
+    mu)`` after the last sweep -- ``Engine.get_factors`` with ``output="numpy"``, ``Engine.get_factors_device`` (fp64
+    tensors on the device) with ``output="torch"``; with ``output="torch"``, ``"init"`` comes from the device as well.
+
+    Resuming: a call given another call's ``"state"`` as ``init_f`` / ``init_s`` / ``init_g`` and ``init_lm`` continues it.
+    With a fixed ``n_iters`` the two calls together are bit for bit the one uninterrupted call (``All_Error``
+    concatenated, the state and the outputs).  In convergence mode (``n_iters=None``) the first stop test after a resume
+    compares with 0, as that of any fresh run does (``R/main.r:53-54``): the previous mean error is not carried over, so
+    the stop sweep can differ, and only when the uninterrupted run would have stopped on the first resumed sweep.
     """
     device_views.check_output(output)
     data = _views(data, device_id)
@@ -182,16 +204,25 @@ def res_nmtf_inner(data, row_indices, column_indices,
         init_f = init_s = init_g = None
         if host_init:
             init_f, init_s, init_g, lam, mu = svd_init(data, k_vec, seed)
+    device_factors = None
     if init_f is not None:
         init_f, init_s, init_g = _as_list(init_f), _as_list(init_s), _as_list(init_g)
+        if lam is None:                           # (svd_init's own factors are host arrays)
+            device_factors, init_f, init_s, init_g = device_views.factor_routes(init_f, init_s, init_g, device_id)
+    if init_lm is not None:
+        if init_f is None or lam is not None:
+            raise ValueError("init_lm needs explicit initial factors (init_f, init_s and init_g)")
+        lam, mu = device_views.check_init_lm(init_lm, n_v)
 
     eng = Engine([d.shape[0] for d in data], [d.shape[1] for d in data], k_vec, device_id=device_id,
                  nnz=[d.nnz if sp else None for d, sp in zip(data, is_sp)], **(engine_opts or {}))
     try:
         _load_engine(eng, data, init_f, init_s, init_g, lam, mu, phi, xi, psi,
-                     row_names, col_names, row_indices, column_indices, seed=seed)
-        init_state = [eng.get_factors(v) for v in range(n_v)] if return_init else None      # (F, S, G, lambda, mu) the loop starts from
+                     row_names, col_names, row_indices, column_indices, seed=seed, device_factors=device_factors)
+        raw_state = eng.get_factors_device if output == "torch" else eng.get_factors
+        init_state = [raw_state(v) for v in range(n_v)] if return_init else None      # (F, S, G, lambda, mu) the loop starts from
         total_err = eng.run(n_iters=n_iters, tol=1.0e-6, max_iters=max_iters)
+        state = [raw_state(v) for v in range(n_v)] if return_state else None          # ... and the one it ended in
         # per view: F, S, G, the binary clusters (main.r:110 + obtain_bicl.r:162-180), lambda, mu
         out_f, out_s, out_g, row_cl, col_cl, lams, mus = (
             list(x) for x in zip(*[(*eng.finalise(v), *eng.get_factors(v)[3:]) for v in range(n_v)]))
@@ -208,11 +239,11 @@ def res_nmtf_inner(data, row_indices, column_indices,
     if on_device is not None:        # the host steps above read the NumPy copies; what is returned lives on the device
         out_f, out_s, out_g = _device_outputs(on_device, row_cl, col_cl, cleaned)
     if no_clusts:                                                                                 # main.r:115-120
-        return inner_result(out_f, out_s, out_g, init=init_state)
+        return inner_result(out_f, out_s, out_g, init=init_state, state=state)
     # ("bisil": None unless score_bisil; bisil.py, parity with bisilhouette::bisilhouette unpinned)
     return inner_result(out_f, out_s, out_g, total_err, n_iters, bisil=cleaned.get("bisil"),
                         row_clusters=cleaned["row_clusters"], col_clusters=cleaned["col_clusters"], lam=lams, mu=mus,
-                        spurious=cleaned.get("spurious"), init=init_state)
+                        spurious=cleaned.get("spurious"), init=init_state, state=state)
 
 
 def _device_outputs(on_device, row_cl, col_cl, cleaned: dict):
@@ -429,7 +460,9 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     host -- its shift and column normalisation run on the device at every upload (``Engine.set_view_device(raw=True)``,
     the sums in the device's order, where ``check_data`` sums a host view in NumPy's).  ``output="torch"`` (keyword-only)
     returns ``output_f`` / ``output_s`` / ``output_g`` / ``row_clusters`` / ``col_clusters`` as fp64 ``torch`` tensors on
-    that device (``Engine.finalise_device``); the small values stay NumPy."""
+    that device (``Engine.finalise_device``); the small values stay NumPy.  With a ``k_val``, ``init_f`` / ``init_s`` /
+    ``init_g`` may be ``torch`` tensors on that device too (``res_nmtf_inner``); the k sweep refuses
+    explicit factors as before."""
     device_views.check_output(output)
     on_dev = {"sparse_on_device": True} if sparse_on_device else {}      # (off: every call below is the earlier one)
     out_kw = {"output": output} if output != "numpy" else {}

@@ -17,7 +17,7 @@ SOURCES = [os.path.join(CSRC, "resnmtf_hip.hip")]
 # the k <= 16 streaming pass: a translation unit of its own, compiled with the max-ILP machine scheduler (csrc/resnmtf_split_tu.h)
 PASS_K16 = os.path.join(CSRC, "resnmtf_pass_k16.hip")
 PASS_K16_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
-DEPS = SOURCES + [PASS_K16, os.path.join(CSRC, "resnmtf_kernels.hip.inc"), os.path.join(CSRC, "resnmtf_device_view.hip.inc"), os.path.join(CSRC, "resnmtf_sparse.hip.inc"), os.path.join(CSRC, "resnmtf_sparse_shuffle.hip.inc"), os.path.join(CSRC, "resnmtf_sparse_subsample.hip.inc"), os.path.join(CSRC, "resnmtf_sparse_device_view.hip.inc"), os.path.join(CSRC, "resnmtf_jsd.hip.inc"), os.path.join(CSRC, "resnmtf_group.hip.inc"), os.path.join(CSRC, "resnmtf_bisil.hip.inc"), os.path.join(CSRC, "resnmtf_split_tu.h"),
+DEPS = SOURCES + [PASS_K16, os.path.join(CSRC, "resnmtf_kernels.hip.inc"), os.path.join(CSRC, "resnmtf_device_view.hip.inc"), os.path.join(CSRC, "resnmtf_device_factors.hip.inc"), os.path.join(CSRC, "resnmtf_sparse.hip.inc"), os.path.join(CSRC, "resnmtf_sparse_shuffle.hip.inc"), os.path.join(CSRC, "resnmtf_sparse_subsample.hip.inc"), os.path.join(CSRC, "resnmtf_sparse_device_view.hip.inc"), os.path.join(CSRC, "resnmtf_jsd.hip.inc"), os.path.join(CSRC, "resnmtf_group.hip.inc"), os.path.join(CSRC, "resnmtf_bisil.hip.inc"), os.path.join(CSRC, "resnmtf_split_tu.h"),
                   os.path.join(ROOT, "include", "resnmtf_hip.h")]
 
 

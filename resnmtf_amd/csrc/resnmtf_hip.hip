@@ -31,6 +31,7 @@
 #include "resnmtf_hip.h"
 #include "resnmtf_kernels.hip.inc"
 #include "resnmtf_device_view.hip.inc"
+#include "resnmtf_device_factors.hip.inc"
 #include "resnmtf_sparse.hip.inc"
 #include <rocprim/rocprim.hpp>
 #include "resnmtf_sparse_shuffle.hip.inc"
@@ -2486,6 +2487,25 @@ int resnmtf_get_view_csc(resnmtf_handle* h, int v, long long* col_ptr, int* row_
   return RESNMTF_OK;
 }
 
+namespace {
+// The tail of both factor routes (resnmtf_set_factors, resnmtf_set_factors_device) for an owned view, once W of both sides
+// and both lm vectors are on their way on the handle's stream: the zeroed operand images, T32 and counters, then the f32 /
+// bf16 operand copies of the new factors.
+hipError_t enqueue_factor_images(resnmtf_handle* h, ViewState& vs) {
+  hipError_t e = hipMemsetAsync(vs.side[SIDE_F].W32, 0, (size_t)vs.n_pad * 64 * sizeof(float), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(vs.side[SIDE_G].W32, 0, (size_t)vs.m_pad * 64 * sizeof(float), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(vs.T32, 0, (size_t)vs.m_pad * 64 * sizeof(float), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(vs.side[SIDE_F].cnt, 0, 4 * sizeof(int), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(vs.side[SIDE_G].cnt, 0, 4 * sizeof(int), h->stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(factor_to_f32_kernel, dim3(ceil_div(vs.n * vs.k, 256)), dim3(256), 0, h->stream, vs.side[SIDE_F].W, vs.n,
+                     vs.k, vs.side[SIDE_F].W32, vs.kk_mode == 0 ? vs.KP : 64, vs.NT, vs.half ? 1 : 0, vs.side[SIDE_F].Wk);
+  hipLaunchKernelGGL(factor_to_f32_kernel, dim3(ceil_div(vs.m * vs.k, 256)), dim3(256), 0, h->stream, vs.side[SIDE_G].W, vs.m,
+                     vs.k, vs.side[SIDE_G].W32, vs.kk_mode == 0 ? vs.KP : 64, vs.NT, vs.half ? 1 : 0, vs.side[SIDE_G].Wk);
+  return hipGetLastError();
+}
+}  // namespace
+
 int resnmtf_set_factors(resnmtf_handle* h, int v, const double* F, const double* S, const double* G,
                         const double* lambda, const double* mu) {
   if (int rc = check_view(h, v)) return rc;
@@ -2512,18 +2532,65 @@ int resnmtf_set_factors(resnmtf_handle* h, int v, const double* F, const double*
     }
     HIP_TRY(h, hipMemcpyAsync(vs.side[SIDE_F].lm, lam.data(), lam.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(vs.side[SIDE_G].lm, muv.data(), muv.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemsetAsync(vs.side[SIDE_F].W32, 0, (size_t)vs.n_pad * 64 * sizeof(float), h->stream));
-    HIP_TRY(h, hipMemsetAsync(vs.side[SIDE_G].W32, 0, (size_t)vs.m_pad * 64 * sizeof(float), h->stream));
-    HIP_TRY(h, hipMemsetAsync(vs.T32, 0, (size_t)vs.m_pad * 64 * sizeof(float), h->stream));
-    HIP_TRY(h, hipMemsetAsync(vs.side[SIDE_F].cnt, 0, 4 * sizeof(int), h->stream));
-    HIP_TRY(h, hipMemsetAsync(vs.side[SIDE_G].cnt, 0, 4 * sizeof(int), h->stream));
-    hipLaunchKernelGGL(factor_to_f32_kernel, dim3(ceil_div(vs.n * vs.k, 256)), dim3(256), 0, h->stream, vs.side[SIDE_F].W, vs.n,
-                       vs.k, vs.side[SIDE_F].W32, vs.kk_mode == 0 ? vs.KP : 64, vs.NT, vs.half ? 1 : 0, vs.side[SIDE_F].Wk);
-    hipLaunchKernelGGL(factor_to_f32_kernel, dim3(ceil_div(vs.m * vs.k, 256)), dim3(256), 0, h->stream, vs.side[SIDE_G].W, vs.m,
-                       vs.k, vs.side[SIDE_G].W32, vs.kk_mode == 0 ? vs.KP : 64, vs.NT, vs.half ? 1 : 0, vs.side[SIDE_G].Wk);
-    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, enqueue_factor_images(h, vs));
   }
   HIP_TRY(h, hipStreamSynchronize(h->stream));   // host vectors go out of scope
+  vs.has_factors = true;
+  return RESNMTF_OK;
+}
+
+// The device route: the kernels of resnmtf_device_factors.hip.inc widen the caller's matrices
+// straight into W / S / lm once the handle's stream has waited for the caller's; no host copy, no transient memory.
+int resnmtf_set_factors_device(resnmtf_handle* h, int v, const resnmtf_device_matrix* F, const resnmtf_device_matrix* S,
+                               const resnmtf_device_matrix* G, const resnmtf_device_matrix* lambda,
+                               const resnmtf_device_matrix* mu, void* stream) {
+  if (int rc = check_view(h, v)) return rc;
+  if (!F || !S || !G || !F->ptr || !S->ptr || !G->ptr) return h->fail(RESNMTF_ERR_INVALID, "F, S and G are required");
+  if ((lambda && !lambda->ptr) || (mu && !mu->ptr)) return h->fail(RESNMTF_ERR_INVALID, "lambda / mu: the matrix has a NULL ptr (pass NULL for colSums)");
+  ViewState& vs = h->views[v];
+  for (const resnmtf_device_matrix* a : {F, S, G, lambda, mu}) {
+    if (!a) continue;
+    if (a->dtype != RESNMTF_DTYPE_F64 && a->dtype != RESNMTF_DTYPE_F32 && a->dtype != RESNMTF_DTYPE_F16 && a->dtype != RESNMTF_DTYPE_BF16)
+      return h->fail(RESNMTF_ERR_INVALID, "unknown dtype: one of RESNMTF_DTYPE_F64 / _F32 / _F16 / _BF16");
+    if (a->row_stride < 0 || a->col_stride < 0) return h->fail(RESNMTF_ERR_INVALID, "negative strides are not supported");
+  }
+  for (const resnmtf_device_matrix* a : {F, S, G, lambda, mu})
+    if (a && !on_handle_device(h, a->ptr))
+      return h->fail(RESNMTF_ERR_INVALID, "a factor is not device memory of the handle's device (host factors: resnmtf_set_factors)");
+  if ((lambda || mu) && !vs.owned) return h->fail(RESNMTF_ERR_STATE, "lambda/mu only exist on the owning handle");
+  h->resume_ok = false;
+  HIP_TRY(h, hipSetDevice(h->opt.device_id));
+  if (int rc = sync_both(h)) return rc;
+  HIP_TRY(h, wait_for_caller(h, stream));
+  // rows x cols of `a` into the row-major fp64 dst; a column-major source (row stride 1) goes through the LDS transpose
+  auto widen = [&](const resnmtf_device_matrix* a, int rows, int cols, double* dst) {
+    pick_int<RESNMTF_DTYPE_F64, RESNMTF_DTYPE_F32, RESNMTF_DTYPE_F16, RESNMTF_DTYPE_BF16>(a->dtype, [&](auto dt) {
+      constexpr int DT = decltype(dt)::value;
+      if (a->row_stride == 1 && a->col_stride != 1)
+        hipLaunchKernelGGL(device_factor_transpose_kernel<DT>, dim3(ceil_div(rows, 32) * ceil_div(cols, 32)), dim3(256), 0, h->stream, a->ptr,
+                           a->row_stride, a->col_stride, rows, cols, dst, (long long)cols, 1LL);
+      else
+        hipLaunchKernelGGL(device_factor_copy_kernel<DT>, dim3((unsigned)(((size_t)rows * cols + 255) / 256)), dim3(256), 0, h->stream, a->ptr,
+                           a->row_stride, a->col_stride, rows, cols, dst);
+    });
+  };
+  widen(F, vs.n, vs.k, vs.side[SIDE_F].W);
+  widen(S, vs.k, vs.k, vs.S);
+  widen(G, vs.m, vs.k, vs.side[SIDE_G].W);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && vs.owned) {
+    // explicit-init branch: lambda = colSums(F), mu = colSums(G) (R/update_steps.r:55-56), in the host route's order
+    if (lambda) widen(lambda, vs.k, 1, vs.side[SIDE_F].lm);
+    if (mu) widen(mu, vs.k, 1, vs.side[SIDE_G].lm);
+    if (!lambda || !mu)
+      hipLaunchKernelGGL(device_factor_colsum_kernel, dim3(2), dim3(256), 0, h->stream, vs.side[SIDE_F].W, vs.n,
+                         lambda ? (double*)nullptr : vs.side[SIDE_F].lm, vs.side[SIDE_G].W, vs.m, mu ? (double*)nullptr : vs.side[SIDE_G].lm, vs.k);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = enqueue_factor_images(h, vs);
+  }
+  const hipError_t es = hipStreamSynchronize(h->stream);   // the sources may be freed on return
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return h->fail_hip("set_factors_device", e);
   vs.has_factors = true;
   return RESNMTF_OK;
 }
@@ -3482,6 +3549,35 @@ int resnmtf_get_factors(resnmtf_handle* h, int v, double* F, double* S, double* 
     if (lambda) HIP_TRY(h, hipMemcpy(lambda, vs.side[SIDE_F].lm, (size_t)vs.k * sizeof(double), hipMemcpyDeviceToHost));
     if (mu) HIP_TRY(h, hipMemcpy(mu, vs.side[SIDE_G].lm, (size_t)vs.k * sizeof(double), hipMemcpyDeviceToHost));
   }
+  return RESNMTF_OK;
+}
+
+// The raw state into caller-owned device buffers: the transposes write them in place, ordered with
+// `stream` as resnmtf_finalise_device orders its copies; no transient memory.
+int resnmtf_get_factors_device(resnmtf_handle* h, int v, double* F, double* S, double* G, double* lambda, double* mu, void* stream) {
+  if (int rc = check_view(h, v)) return rc;
+  ViewState& vs = h->views[v];
+  for (const double* p : {F, S, G, lambda, mu})
+    if (p && !on_handle_device(h, p)) return h->fail(RESNMTF_ERR_INVALID, "an output is not device memory of the handle's device (host buffers: resnmtf_get_factors)");
+  if ((lambda || mu) && !vs.owned) return h->fail(RESNMTF_ERR_STATE, "lambda/mu only exist on the owning handle");
+  HIP_TRY(h, hipSetDevice(h->opt.device_id));
+  if (int rc = sync_both(h)) return rc;
+  HIP_TRY(h, wait_for_caller(h, stream));
+  // row-major W [len][k] -> column-major out: W read as the k x len matrix of row stride 1 it also is
+  auto emit = [&](const double* W, int len, int k, double* out) {
+    hipLaunchKernelGGL(device_factor_transpose_kernel<RESNMTF_DTYPE_F64>, dim3(ceil_div(k, 32) * ceil_div(len, 32)), dim3(256), 0, h->stream,
+                       W, 1LL, (long long)k, k, len, out, (long long)len, 1LL);
+  };
+  if (F) emit(vs.side[SIDE_F].W, vs.n, vs.k, F);
+  if (S) emit(vs.S, vs.k, vs.k, S);
+  if (G) emit(vs.side[SIDE_G].W, vs.m, vs.k, G);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && lambda) e = hipMemcpyAsync(lambda, vs.side[SIDE_F].lm, (size_t)vs.k * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+  if (e == hipSuccess && mu) e = hipMemcpyAsync(mu, vs.side[SIDE_G].lm, (size_t)vs.k * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+  // (the handle's stream is drained before the call returns: whatever the caller enqueues afterwards comes after the writes)
+  const hipError_t es = hipStreamSynchronize(h->stream);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return h->fail_hip("get_factors_device", e);
   return RESNMTF_OK;
 }
 

@@ -185,6 +185,52 @@ def as_view(x, device_id: int = 0, what: str = "view"):
     return x
 
 
+def is_device_tensor(x) -> bool:
+    """A ``torch`` tensor that does not live on the CPU."""
+    return is_tensor(x) and x.device.type != "cpu"
+
+
+def factor_route(f, s, g, what: str = "view", on_device=is_device_tensor) -> bool:
+    """Which route the three initial factors of one view take: True = the device route
+    (``Engine.set_factors_device``: all three are device tensors), False = the host route (none is).  A mix is a
+    ``ValueError`` naming ``what``.  Pure: ``on_device`` decides what a device tensor is."""
+    flags = [bool(on_device(x)) for x in (f, s, g)]
+    if all(flags):
+        return True
+    if any(flags):
+        where = ", ".join(f"init_{name} on the {'device' if flag else 'host'}" for name, flag in zip("fsg", flags))
+        raise ValueError(f"{what}: the initial factors mix device tensors and host arrays ({where}); give all three of a "
+                         "view in one place")
+    return False
+
+
+def factor_routes(init_f, init_s, init_g, device_id: int = 0):
+    """The initial factors of every view, ready for ``Engine.set_factors`` / ``set_factors_device``: returns ``(routes,
+    init_f, init_s, init_g)`` -- ``routes[v]`` as ``factor_route`` decides it, a CPU tensor replaced by the fp64 array of
+    its values, a device tensor checked (2-D, floating, on ``cuda:device_id``; ``ValueError`` otherwise) and left where
+    it is.  No device is touched."""
+    routes, lists = [], ([], [], [])
+    for v, parts in enumerate(zip(init_f, init_s, init_g)):
+        parts = [host_or_device(x, f"view {v}: init_{name}") for x, name in zip(parts, "fsg")]
+        routes.append(factor_route(*parts, what=f"view {v}"))
+        for x, name, out in zip(parts, "fsg", lists):
+            if routes[v] and (x.device.type != "cuda" or x.device.index != int(device_id)):
+                raise ValueError(f"view {v}: init_{name} lives on {x.device}, the engine on cuda:{int(device_id)}")
+            out.append(x)
+    return (routes, *lists)
+
+
+def check_init_lm(init_lm, n_views: int):
+    """``init_lm`` of ``res_nmtf_inner``: ``(lambdas, mus)``, one entry per view each (``ValueError`` otherwise)."""
+    try:
+        ok = len(init_lm) == 2 and all(len(x) == n_views for x in init_lm)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError(f"init_lm must be (lambdas, mus) with one entry per view each ({n_views} views)")
+    return list(init_lm[0]), list(init_lm[1])
+
+
 def upload(eng, v: int, x, raw: bool = False) -> bool:
     """``x`` (as ``as_view`` returns a dense view) into ``eng``'s view ``v``: a device view through ``set_view_device``
     (a ``RawDeviceView`` always with the pre-processing, with the reference's warning, ``R/utils.r:23-25``), a host array

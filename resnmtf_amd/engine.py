@@ -457,6 +457,46 @@ class Engine:
         mu = None if mu is None else np.ascontiguousarray(mu, dtype=np.float64)
         self._check(self._lib.resnmtf_set_factors(self._h, v, _dp(f), _dp(s), _dp(g), _dp(lam), _dp(mu)))
 
+    def set_factors_device(self, v: int, f, s, g, lam=None, mu=None):
+        """``set_factors`` from device memory (``resnmtf_set_factors_device``, ``R/update_steps.r:41-56``): ``f`` (n x k),
+        ``s`` (k x k) and ``g`` (m x k) are 2-D floating ``torch`` tensors (fp64 / fp32 / fp16 / bf16, one dtype each, any
+        strides) on this engine's GPU, read in place, ordered after the work enqueued on torch's current stream of that
+        device; they may be freed on return.  ``lam`` / ``mu``: ``None`` (the column sums of ``f`` / ``g``, summed on the
+        device in ``set_factors``' order) or k values -- a 1-D tensor on that GPU, made contiguous, or anything NumPy takes,
+        moved there.  The view's factor state is bit for bit what ``set_factors`` of
+        ``t.double().cpu().numpy()`` leaves."""
+        import torch            # (lazily: nothing else in this module needs it)
+        n, m, k = self.n_rows[v], self.n_cols[v], self.k[v]
+        dev = torch.device("cuda", self.device_id)
+        codes = {torch.float64: _lib.DTYPE_F64, torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16,
+                 torch.bfloat16: _lib.DTYPE_BF16}
+
+        def check(t, name, shape):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"set_factors_device takes torch.Tensors, {name} is a {type(t).__name__} (host factors: set_factors)")
+            if t.dtype not in codes:
+                raise ValueError(f"{name} must be fp64, fp32, fp16 or bf16, got {t.dtype}")
+            if t.device.type != "cuda" or t.device.index != self.device_id:
+                raise ValueError(f"{name} lives on {t.device}, the engine on cuda:{self.device_id}")
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+            return t.detach()
+
+        mats = [check(t, name, shape) for t, name, shape in ((f, "f", (n, k)), (s, "s", (k, k)), (g, "g", (m, k)))]
+        descs = [_lib.DeviceMatrix(t.data_ptr(), codes[t.dtype], int(t.stride(0)), int(t.stride(1))) for t in mats]
+        for vec, name in ((lam, "lam"), (mu, "mu")):
+            if vec is None:
+                descs.append(None)
+                continue
+            if not isinstance(vec, torch.Tensor):
+                vec = torch.as_tensor(np.ascontiguousarray(vec, dtype=np.float64), device=dev)
+            vec = check(vec, name, (k,)).contiguous()
+            mats.append(vec)            # (kept alive until the call returns)
+            descs.append(_lib.DeviceMatrix(vec.data_ptr(), codes[vec.dtype], 1, 1))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self._check(self._lib.resnmtf_set_factors_device(self._h, v, *(None if d is None else C.byref(d) for d in descs),
+                                                         C.c_void_p(stream)))
+
     def set_restrictions(self, phi=None, xi=None, psi=None):
         mats = []
         for m in (phi, xi, psi):
@@ -526,6 +566,21 @@ class Engine:
         lam = np.zeros(k) if with_lm else None
         mu = np.zeros(k) if with_lm else None
         self._check(self._lib.resnmtf_get_factors(self._h, v, _dp(f), _dp(s), _dp(g), _dp(lam), _dp(mu)))
+        return f, s, g, lam, mu
+
+    def get_factors_device(self, v: int, with_lm: bool = True):
+        """``get_factors`` with the raw state left on the device (``resnmtf_get_factors_device``): fp64 ``torch`` tensors
+        on this engine's GPU, F, S and G column-major (``torch.empty((k, n)).T``), bitwise what ``get_factors`` returns;
+        ordered with torch's current stream of that device.  ``with_lm=False``: lambda and mu are ``None``."""
+        import torch            # (lazily: nothing else in this module needs it)
+        n, m, k = self.n_rows[v], self.n_cols[v], self.k[v]
+        dev = torch.device("cuda", self.device_id)
+        f, s, g = (torch.empty((cols, rows), dtype=torch.float64, device=dev).T for rows, cols in ((n, k), (k, k), (m, k)))
+        lam = torch.empty(k, dtype=torch.float64, device=dev) if with_lm else None
+        mu = torch.empty(k, dtype=torch.float64, device=dev) if with_lm else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self._check(self._lib.resnmtf_get_factors_device(
+            self._h, v, *(None if t is None else C.c_void_p(t.data_ptr()) for t in (f, s, g, lam, mu)), C.c_void_p(stream)))
         return f, s, g, lam, mu
 
     def finalise(self, v: int):

@@ -173,7 +173,7 @@ def reported_error(errs, n_iters) -> float:
 
 
 _INNER_KEYS = ("output_f", "output_s", "output_g", "Error", "All_Error", "bisil", "row_clusters", "col_clusters",
-               "lambda", "mu", "spurious", "init", "tag", "extras")
+               "lambda", "mu", "spurious", "init", "state", "tag", "extras")
 _DEVICE_DATA_KEYS = ("output_f", "output_s", "output_g", "row_clusters", "col_clusters", "Error", "All_Error", "tag",
                      "extras", "row_names", "col_names", "init", "lambda", "mu", "data", "spurious_check", "device_out")
 
