@@ -50,6 +50,10 @@ struct SweepCtl {            // device-resident loop control (one per handle)
   double prev_mean;          // err_temp of R/main.r:54,80
 };
 
+// The kernels that are not templates are `static __global__`: every translation unit that includes them emits its own copy.
+// resnmtf_pass_k16.hip needs the templates alone and defines RESNMTF_TEMPLATES_ONLY: the three stretches of such kernels
+// (upload and pre-processing here, the operand copy below, everything after the passes at the end) are left out there.
+#ifndef RESNMTF_TEMPLATES_ONLY
 // --------------------------------------------------------------------------------------
 // Pre-processing of a raw view on upload (SURVEY 8(f2)): per column c of the column-major source
 //   shift[c]  = |min(0, min(x[, c]))|                 make_non_neg_inner, R/utils.r:22
@@ -203,6 +207,7 @@ static __global__ __launch_bounds__(256) void reduce_sum_kernel(const double* __
   }
   if (threadIdx.x == 0) *out = red[0];
 }
+#endif      // RESNMTF_TEMPLATES_ONLY
 
 // f32 factor operand copies keep their KP columns INTERLEAVED: column i = 16 nt + p lives at position
 // p NT + nt (NT = KP / 16), so that a lane's NT B-operand values B[row][16 nt + p], nt = 0..NT-1, are
@@ -234,6 +239,7 @@ __device__ __forceinline__ size_t kpack16(int r, int i) { return ((size_t)(r >> 
 // fp64 factor [len][k] -> f32 operand copy [len_pad][ld] (columns >= k and rows >= len stay zero)
 __host__ __device__ __forceinline__ size_t bk_index(int r, int i, int NT, int piece);
 __device__ __forceinline__ void bk_store(unsigned short* __restrict__ Bk, int r, int i, int NT, float x);
+#ifndef RESNMTF_TEMPLATES_ONLY
 static __global__ __launch_bounds__(256) void factor_to_f32_kernel(const double* __restrict__ W, int len, int k,
                                                             float* __restrict__ W32, int ld, int nt, int kpack,
                                                             unsigned short* __restrict__ Wk /* bf16 pieces (k > 16) or nullptr */) {
@@ -301,6 +307,7 @@ static __global__ __launch_bounds__(256) void pack_half_kernel(const float* __re
     if (threadIdx.x == 0) sq_err[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
   }
 }
+#endif      // RESNMTF_TEMPLATES_ONLY
 
 // --------------------------------------------------------------------------------------
 // Streaming pass  P[s] = A[rows of split s]^T * B[rows of split s]   (the two big contractions)
@@ -2955,6 +2962,7 @@ __global__ __launch_bounds__(512, 4) void pass_fused_kernel(PassArgs a, KKFArgs 
   STAMP(SB + 1);
 }
 
+#ifndef RESNMTF_TEMPLATES_ONLY
 // --------------------------------------------------------------------------------------
 // Row-sliced chains (view-sharded runs, resnmtf_options.slice_chains): star_prod_relevant is row-local by NAME
 // (R/utils.r:67-73: row r of view v reads only the same-named row of view i) and ordered over the views
@@ -3354,3 +3362,4 @@ static __global__ void relevance_epilogue_kernel(int k, const unsigned int* __re
   }
   out[j] = best;
 }
+#endif      // RESNMTF_TEMPLATES_ONLY

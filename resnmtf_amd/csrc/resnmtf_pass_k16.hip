@@ -1,8 +1,7 @@
 // resnmtf_pass_k16.hip -- the pass_kernel<NT = 1, ...> instantiations (k <= 16: f32 MFMA, one tile per workgroup), compiled with
 // -mllvm -amdgpu-sched-strategy=max-ilp (resnmtf_amd/build.py); resnmtf_hip.hip declares them `extern template`
-// (-DRESNMTF_SPLIT_TU).  The kernels of resnmtf_kernels.hip.inc that are not templates are `static __global__`: this unit's
-// code object carries its own copy of each of them (25 kernels: profiles/kernel_fingerprint.txt, unit1), which nothing
-// launches -- the host side launches the first unit's.  See resnmtf_split_tu.h for the measurement behind the split.
+// (-DRESNMTF_SPLIT_TU).  RESNMTF_TEMPLATES_ONLY leaves the `static __global__` kernels of resnmtf_kernels.hip.inc out, so this
+// unit's code object carries these sixteen kernels and nothing else.  See resnmtf_split_tu.h for the measurement behind the split.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -14,6 +13,7 @@
 #include <type_traits>
 
 #include "resnmtf_hip.h"
+#define RESNMTF_TEMPLATES_ONLY
 #include "resnmtf_kernels.hip.inc"
 #include "resnmtf_split_tu.h"
 

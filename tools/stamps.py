@@ -6,7 +6,6 @@ wall-clock ticks (10 ns); columns 0-4 belong to the X.G launch, 8-12 to the Xt.F
     python tools/stamps.py [config] [kk_mode]"""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,9 +16,8 @@ cfg = sys.argv[1] if len(sys.argv) > 1 else "c2"
 kk_mode = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 so = os.path.join(ROOT, "resnmtf_amd", "libresnmtf_hip_stamps.so")
 if not os.path.exists(so) or os.environ.get("STAMPS_REBUILD") == "1":
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DRESNMTF_STAMPS",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "resnmtf_amd", "csrc"), "-o", so,
-                    os.path.join(ROOT, "resnmtf_amd", "csrc", "resnmtf_hip.hip")], check=True)
+    from resnmtf_amd import build as B  # noqa: E402
+    B.compile_units(so, defines=["-DRESNMTF_STAMPS"], one_code_object=True)
 from resnmtf_amd import _lib, synth  # noqa: E402
 _lib.LIB_PATH = so
 from resnmtf_amd.engine import Engine  # noqa: E402

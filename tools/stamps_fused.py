@@ -5,7 +5,6 @@ the arrival flag).  -DRESNMTF_STAMPS build; stamps are 100 MHz ticks.  Columns (
     python tools/stamps_fused.py [fuse_updates: 1 | 2]"""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,9 +14,8 @@ import numpy as np  # noqa: E402
 mode = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 so = os.path.join(ROOT, "resnmtf_amd", "libresnmtf_hip_stamps.so")
 if not os.path.exists(so) or os.environ.get("STAMPS_REBUILD") == "1":
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DRESNMTF_STAMPS",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "resnmtf_amd", "csrc"), "-o", so,
-                    os.path.join(ROOT, "resnmtf_amd", "csrc", "resnmtf_hip.hip")], check=True)
+    from resnmtf_amd import build as B  # noqa: E402
+    B.compile_units(so, defines=["-DRESNMTF_STAMPS"], one_code_object=True)
 from resnmtf_amd import _lib, synth  # noqa: E402
 _lib.LIB_PATH = so
 from resnmtf_amd.engine import Engine  # noqa: E402

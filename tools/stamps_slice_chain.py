@@ -5,7 +5,6 @@ Columns (F chain 0.., G chain 8..): +0 entry, +1 rows in LDS, +2 first pair's pr
     python tools/stamps_slice_chain.py 8 50000 8000 64"""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,9 +14,8 @@ import numpy as np  # noqa: E402
 V, n, m, k = (int(x) for x in sys.argv[1:5])
 so = os.path.join(ROOT, "resnmtf_amd", "libresnmtf_hip_stamps.so")
 if not os.path.exists(so) or os.environ.get("STAMPS_REBUILD") == "1":
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DRESNMTF_STAMPS",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "resnmtf_amd", "csrc"), "-o", so,
-                    os.path.join(ROOT, "resnmtf_amd", "csrc", "resnmtf_hip.hip")], check=True)
+    from resnmtf_amd import build as B  # noqa: E402
+    B.compile_units(so, defines=["-DRESNMTF_STAMPS"], one_code_object=True)
 from resnmtf_amd import _lib  # noqa: E402
 _lib.LIB_PATH = so
 import torch  # noqa: E402

@@ -3,16 +3,15 @@
 Runs a few sweeps of a config eagerly, then ONE PHASE_F and ONE PHASE_G with the stamp buffer
 attached (the pass launches stamp other columns of other rows; only update-kernel rows are read:
 the update kernels run first in each phase and their block ids are the lowest)."""
-import ctypes as C, os, subprocess, sys
+import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 cfg = sys.argv[1] if len(sys.argv) > 1 else "c2"
 so = os.path.join(ROOT, "resnmtf_amd", "libresnmtf_hip_stamps.so")
 if not os.path.exists(so) or os.environ.get("STAMPS_REBUILD") == "1":
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DRESNMTF_STAMPS",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "resnmtf_amd", "csrc"), "-o", so,
-                    os.path.join(ROOT, "resnmtf_amd", "csrc", "resnmtf_hip.hip")], check=True)
+    from resnmtf_amd import build as B  # noqa: E402
+    B.compile_units(so, defines=["-DRESNMTF_STAMPS"], one_code_object=True)
 from resnmtf_amd import _lib, synth
 _lib.LIB_PATH = so
 from resnmtf_amd.engine import Engine
