@@ -444,6 +444,47 @@ int resnmtf_view_empty_lines(resnmtf_handle* h, int v, int* n_empty_rows, int* n
 int resnmtf_get_view(resnmtf_handle* h, int v, double* x);
 
 /*
+ * The data a handle holds, written to caller-owned DEVICE memory without a host round trip: the pre-processed matrix the
+ * library factorises (R/utils.r:416,422), a shuffle drawn on the device (R/obtain_bicl.r:11-22) or a stability
+ * sub-sample gathered there (R/stability_analysis.r:230-249).
+ *
+ * resnmtf_get_view_device: element (r, c) of dense view v is written to out[r * row_stride + c * col_stride], strides in
+ * ELEMENTS (column-major: 1, n; row-major: m, 1; slices and transposes of a contiguous buffer likewise).  dtype is
+ * RESNMTF_DTYPE_F64 or _F32.  The values are BIT FOR BIT those of resnmtf_get_view: the stored f32 image, widened exactly
+ * or kept.  One kernel reads the tile-major image through an LDS tile and writes with neighbouring lanes along the
+ * smaller of the two strides; no atomics, no transient device memory.
+ *   stream  as for resnmtf_finalise_device: the library's writes are ordered after the work already enqueued there and
+ *           before any work enqueued there after the call returns.
+ * Refused before any device work, out untouched (RESNMTF_ERR_INVALID unless noted): out == NULL or not device memory of
+ * the handle's device; RESNMTF_DTYPE_F16 / _BF16 (narrowing is not a copy) or an unknown dtype; a stride <= 0 along an
+ * extent > 1; strides under which two elements would share an address (with a <= b the two strides and e the extent
+ * along a: a (e - 1) < b is required); a sparse view (resnmtf_get_view_sparse_device); a view that is not owned or has
+ * no data (RESNMTF_ERR_STATE).
+ *
+ * resnmtf_get_view_sparse_device: the mirror of resnmtf_set_view_sparse_device.
+ *   layout      RESNMTF_SPARSE_CSC: ptr_or_rows receives the m + 1 column pointers, idx_or_cols the row index and values
+ *               the value of every stored entry -- the CSC copy: columns ascending, rows ascending within a column,
+ *               explicit zeros kept; BIT FOR BIT resnmtf_get_view_csc;
+ *               RESNMTF_SPARSE_CSR: the n + 1 row pointers, column indices and values of the CSR copy, columns ascending
+ *               within a row: what the canonical CSR of that CSC holds;
+ *               RESNMTF_SPARSE_COO: nnz row and nnz column indices in the CSR copy's order (row-major sorted, what
+ *               torch calls coalesced); the row pointers are expanded to a row index per entry on the device.
+ *   index_type  RESNMTF_INDEX_I32 / _I64 for both index arrays (the stored pointers are int64 and the stored indices
+ *               int32: one of them is converted on the device); I32 is refused when nnz exceeds 2^31 - 1.
+ *   dtype       RESNMTF_DTYPE_F64 or _F32 of values.
+ * Sizes from resnmtf_view_storage.  Any of the three arrays may be NULL and is then skipped; nnz = 0 writes the pointers
+ * only.  stream as above.  No transient device memory.
+ * Refused before any device work (RESNMTF_ERR_INVALID unless noted): a dense view; an unknown layout, index type or
+ * dtype; a 16-bit dtype; a non-NULL array that is not device memory of the handle's device; a view that is not owned or
+ * has no data (RESNMTF_ERR_STATE).
+ * Replaces: the dgCMatrix slots R/utils.r:416-419 would densify, as resnmtf_get_view_csc, for a caller on the device.
+ */
+int resnmtf_get_view_device(resnmtf_handle* h, int v, void* out, int dtype, long long row_stride, long long col_stride,
+                            void* stream);
+int resnmtf_get_view_sparse_device(resnmtf_handle* h, int v, int layout, void* ptr_or_rows, void* idx_or_cols,
+                                   int index_type, void* values, int dtype, void* stream);
+
+/*
  * Initial factors of view v (owned or mirror): F n x k, S k x k, G m x k, column-major.
  * lambda / mu may be NULL: they are then colSums(F) / colSums(G), the reference's
  * explicit-init branch (R/update_steps.r:49-56).
@@ -606,6 +647,22 @@ int resnmtf_finalise_device(resnmtf_handle* h, int v, double* F, double* S, doub
 int resnmtf_set_reference_clusters(resnmtf_handle* h, int v, int k, const double* row_clusters, const double* col_clusters);
 int resnmtf_relevance(resnmtf_handle* h, int v, resnmtf_handle* ref, int v_ref, const int* rows, const int* cols,
                       double* relevance);
+
+/*
+ * resnmtf_set_reference_clusters for cluster matrices that are ALREADY in device memory (results$row_clusters[[v]] /
+ * results$col_clusters[[v]] of R/stability_analysis.r:268-276, as resnmtf_finalise_device leaves them): n x k and m x k,
+ * 0 / 1, each a resnmtf_device_matrix as resnmtf_set_factors_device takes one -- any of the four floating types, any
+ * non-negative strides.  They are read in place after an event recorded on `stream` and may be freed on return.  Every
+ * entry is checked on the device: anything other than 0 or 1 is refused (RESNMTF_ERR_INVALID; NaN included; -0.0 counts
+ * as 0, as on the host route), with the message of row_clusters if that matrix has a bad entry, otherwise that of
+ * col_clusters.  The entries are packed into the same row-major byte block resnmtf_set_reference_clusters uploads, so
+ * resnmtf_relevance and resnmtf_relevance_masked return the same bits as after the host route.  Also refused, before any
+ * device work: NULL pointers, k outside [1, 64], an unknown dtype, a negative stride, a pointer that is not device
+ * memory of the handle's device.  EVERY refusal leaves the view's previous reference clusters exactly as they were (the
+ * block is built in a fresh allocation and swapped in only on success).  Transient device memory: 8 bytes.
+ */
+int resnmtf_set_reference_clusters_device(resnmtf_handle* h, int v, int k, const resnmtf_device_matrix* row_clusters,
+                                          const resnmtf_device_matrix* col_clusters, void* stream);
 
 /*
  * Relevance after a spurious-bicluster removal (a stability repeat of res_nmtf_inner(sub_sample, spurious = TRUE),

@@ -130,6 +130,8 @@ SIGNATURES = {
     "resnmtf_subsample_view": (C.c_int, [_h, C.c_int, _h, C.c_int, _ip, _ip]),
     "resnmtf_view_empty_lines": (C.c_int, [_h, C.c_int, _ip, _ip, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
     "resnmtf_get_view": (C.c_int, [_h, C.c_int, _dp]),
+    "resnmtf_get_view_device": (C.c_int, [_h, C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p]),
+    "resnmtf_get_view_sparse_device": (C.c_int, [_h, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "resnmtf_set_factors": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "resnmtf_set_factors_device": (C.c_int, [_h, C.c_int, _dm, _dm, _dm, _dm, _dm, C.c_void_p]),
     "resnmtf_init_svd": (C.c_int, [_h, C.c_int, C.c_ulonglong, C.c_double, C.c_int, _dp]),
@@ -143,6 +145,7 @@ SIGNATURES = {
     "resnmtf_finalise": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "resnmtf_finalise_device": (C.c_int, [_h, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "resnmtf_set_reference_clusters": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp]),
+    "resnmtf_set_reference_clusters_device": (C.c_int, [_h, C.c_int, C.c_int, _dm, _dm, C.c_void_p]),
     "resnmtf_relevance": (C.c_int, [_h, C.c_int, _h, C.c_int, _ip, _ip, _dp]),
     "resnmtf_relevance_masked": (C.c_int, [_h, C.c_int, _h, C.c_int, _ip, _ip, C.POINTER(C.c_ubyte), _dp]),
     "resnmtf_jsd_pairs": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, _ip, _dp]),

@@ -267,7 +267,15 @@ def _remove_then_score(res: dict, check: Optional[dict], score_fn: Optional[Call
 def _number_biclusters(results) -> float:
     """``number_biclusters`` (``R/stability_analysis.r:92-97``): the sum of every row-cluster matrix; 0 for results
     without cluster matrices (``no_clusts``)."""
-    return float(sum(np.asarray(device_views.to_numpy(rc)).sum() for rc in (results.get("row_clusters") or [])))
+    return float(sum(_cluster_sum(rc) for rc in (results.get("row_clusters") or [])))
+
+
+def _cluster_sum(rc) -> float:
+    """The sum of a cluster matrix: a tensor in device memory is summed there in fp64 (0 / 1 entries: exact in any order),
+    anything else on the host."""
+    if device_views.is_device_tensor(rc):
+        return float(rc.detach().double().sum().item())
+    return float(np.asarray(device_views.to_numpy(rc)).sum())
 
 
 def _refuse_host_spurious(wanted, spurious_on_device: bool, message: str):
@@ -336,8 +344,10 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
     ``max_iters``; test hooks: ``return_repeats`` (adds ``"repeats"``: per repeat the trimmed draws, relevance and
     the sub-sample's own clusters -- under ``"stability"`` of a copy of the result), ``repeat_runner(r)`` (replaces
     one repeat; nothing touches the device); ``output``: ``"torch"`` returns the two cluster lists as fp64 ``torch``
-    tensors on ``cuda:device_id`` (those of ``results`` when it holds tensors, with the unstable columns zeroed there;
-    the scoring reads NumPy copies of them either way), ``"numpy"`` as NumPy arrays.  The views may be ``torch`` tensors
+    tensors on ``cuda:device_id`` (those of ``results`` when it holds tensors, with the unstable columns zeroed there),
+    ``"numpy"`` as NumPy arrays.  The cluster matrices of a view that are both tensors on ``cuda:device_id`` are scored
+    from there (``Engine.set_reference_clusters_device``) and are not turned into NumPy unless ``"numpy"`` asks for them;
+    anything else is scored from NumPy copies.  The views may be ``torch`` tensors
     on that device, as for ``res_nmtf_inner``.
     """
     device_views.check_output(output)
@@ -353,9 +363,13 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
         raise ValueError("n_stability must be a positive integer.")
     data = _views(data, device_id)
     n_v = len(data)
-    given = results                 # host copies of the small cluster matrices for the scoring; `given` keeps the caller's
-    results = dict(results, row_clusters=[device_views.to_numpy(rc) for rc in results["row_clusters"]],
-                   col_clusters=[device_views.to_numpy(cc) for cc in results["col_clusters"]])
+    # host copies of the small cluster matrices for the scoring, unless both of a view's are on the engine's device (they
+    # are then read in place); `given` keeps the caller's
+    given = results
+    kept = [all(device_views.on_engine_device(x, device_id) and x.dtype.is_floating_point for x in (rc, cc))
+            for rc, cc in zip(results["row_clusters"], results["col_clusters"])]
+    results = dict(results, row_clusters=[rc if on else device_views.to_numpy(rc) for rc, on in zip(results["row_clusters"], kept)],
+                   col_clusters=[cc if on else device_views.to_numpy(cc) for cc, on in zip(results["col_clusters"], kept)])
     if spurious_repeats and repeat_runner is None and not shuffle_sparse and any(sparse.is_sparse_view(d) for d in data):
         raise NotImplementedError("spurious-bicluster removal needs shuffled views: device shuffles of sparse views "
                                   "are not supported")
@@ -382,17 +396,31 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
         out = {"res": given, "relevance": relevance}
     else:                                                                                         # :330-337
         out = dict(given)
-        out["row_clusters"] = [np.array(rc, dtype=np.float64, copy=True) for rc in results["row_clusters"]]
-        out["col_clusters"] = [np.array(cc, dtype=np.float64, copy=True) for cc in results["col_clusters"]]
-        for i in range(n_v):
-            drop = relevance[i] < stab_thres
-            out["row_clusters"][i][:, drop] = 0.0
-            out["col_clusters"][i][:, drop] = 0.0
         for key in ("row_clusters", "col_clusters"):
-            out[key] = [_cluster_output(g, b, a, output, device_id) for g, b, a in zip(given[key], results[key], out[key])]
+            out[key] = []
+            for i in range(n_v):
+                drop = relevance[i] < stab_thres
+                if kept[i] and output == "torch":       # stays on the device: a clone with the unstable columns zeroed there
+                    out[key].append(_zero_columns_on_device(given[key][i], drop))
+                    continue
+                before = device_views.to_numpy(results[key][i])
+                after = np.array(before, dtype=np.float64, copy=True)
+                after[:, drop] = 0.0
+                out[key].append(_cluster_output(given[key][i], before, after, output, device_id))
     if return_repeats:
         out = dict(out)
         out["stability"] = {"relevance": relevance, "repeats": stab["repeats"]}
+    return out
+
+
+def _zero_columns_on_device(t, drop: np.ndarray):
+    """A clone of the device cluster matrix ``t`` whose columns ``drop`` are zero: what ``_cluster_output`` makes of its
+    host copy (``zero_columns_like`` writes only the columns that change: those of ``drop`` that hold a non-zero entry)."""
+    out = t.clone()
+    cols = np.flatnonzero(np.asarray(drop) & (out != 0).any(dim=0).cpu().numpy())      # (k flags, not the matrix)
+    if cols.size:
+        import torch        # (the caller works with it)
+        out[:, torch.as_tensor(cols, device=out.device)] = 0.0
     return out
 
 

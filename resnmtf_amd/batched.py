@@ -451,13 +451,19 @@ class DeviceData:
         this factorisation's own device copy (``spurious.check_on_device`` with ``spurious_seed``) as
         ``"spurious_check"`` (the caller removes).  ``shuffle_sparse`` (opt-in): sparse views are shuffled as sparse
         views, by ``shuffle_seed`` and by the spurious check alike; ``return_data`` of a shuffled sparse view stays
-        refused (the host holds no copy of the shuffle: ``Engine.get_view_sparse`` reads it without densifying).
+        refused with ``output="numpy"`` (the host holds no copy of the shuffle: ``Engine.get_view_sparse`` reads it without
+        densifying).
         ``sparse_on_device`` (opt-in): sparse views are copied / sub-sampled on the device (``child``); ``return_data``
         then reads them back (``Engine.get_view_sparse``: the same f32-rounded matrix).  ``output="torch"`` adds
-        ``"device_out"``: per view ``Engine.finalise_device``'s five tensors (the other keys stay NumPy)."""
+        ``"device_out"``: per view ``Engine.finalise_device``'s five tensors (the other keys stay NumPy), and with
+        ``return_data`` ``"device_data"``: per view the device's copy of the data factorised, left on the device -- a
+        dense fp32 tensor (``Engine.get_view_device``) or a ``sparse_csc`` tensor (``Engine.get_view_sparse_device``).  A
+        shuffled sparse view is then not refused: its entry of ``"data"`` is ``None`` and ``"device_data"`` holds the
+        shuffle."""
         n_v = len(self.data_shapes)
         device_views.check_output(output)
-        if return_data and shuffle_seed is not None and any(c is not None for c in self.sp):
+        shuffled_sparse = shuffle_seed is not None and any(c is not None for c in self.sp)
+        if return_data and shuffled_sparse and output != "torch":
             raise NotImplementedError("return_data of a shuffled sparse view is not supported (it would densify the shuffle)")
         with self.child(k, seed, shuffle_seed, samples, shuffle_sparse=shuffle_sparse, sparse_on_device=sparse_on_device) as ch:
             if ch is None:
@@ -465,9 +471,12 @@ class DeviceData:
             eng = ch.eng
             init_state = [eng.get_factors(v) for v in range(n_v)] if return_init else None
             # (sparse views: the host copy rounded to f32, as the device holds the values)
-            data_used = ([ch.host_views[v].toarray().astype(np.float32).astype(np.float64) if ch.host_views[v] is not None
+            data_used = ([None if shuffled_sparse and self.sp[v] is not None else
+                          ch.host_views[v].toarray().astype(np.float32).astype(np.float64) if ch.host_views[v] is not None
                           else (eng.get_view_sparse(v).toarray() if self.sp[v] is not None else eng.get_view(v))
                           for v in range(n_v)] if return_data else None)
+            data_dev = ([eng.get_view_sparse_device(v) if self.sp[v] is not None else eng.get_view_device(v) for v in range(n_v)]
+                        if return_data and output == "torch" else None)
             errs = eng.run(n_iters=n_iters, tol=1.0e-6, max_iters=max_iters)
             check = (spurious.check_on_device(eng, spurious_repeats, spurious_seed, max_iters=max_iters,
                                               device_id=self.device_id, shuffle_sparse=shuffle_sparse)
@@ -480,6 +489,7 @@ class DeviceData:
                             extras={} if ch.samples is None else {"row_samples": ch.samples[0], "col_samples": ch.samples[1]},
                             row_names=ch.row_names, col_names=ch.col_names, init=init_state,
                             lam=lms and [lm[0] for lm in lms], mu=lms and [lm[1] for lm in lms], data=data_used,
+                            data_on_device=data_dev,
                             spurious_check=check, device_out=fin_dev)
 
     def stability_repeat(self, k: int, n_iters: Optional[int], seed: int, samples, max_iters: int = 100000, tag: str = "",
@@ -599,7 +609,8 @@ def stability_relevance_on_device(dev: Optional[DeviceData], results: dict, k: i
                                   runner: Optional[Callable] = None, spurious_repeats: int = 0, *,
                                   shuffle_sparse: bool = False, sparse_on_device: bool = False) -> dict:
     """The repeats of ``stability_check`` (``R/stability_analysis.r:302-334``) with their scoring on the device:
-    ``results``' binary clusters are uploaded once onto ``dev.base`` (``resnmtf_set_reference_clusters``), repeat r
+    ``results``' binary clusters are set once on ``dev.base`` (``resnmtf_set_reference_clusters``; a view whose two cluster
+    matrices are ``torch`` tensors on the engine's GPU: ``resnmtf_set_reference_clusters_device``, read in place), repeat r
     factorises the sub-sample of ``stability_draws`` (trimmed as ``stability_on_device`` does) up to the end of the loop
     and returns its n_views x k relevance (``resnmtf_relevance``) -- no factor leaves the device.  The repeats are
     sharded round-robin over the ranks of an initialised process group (``run_jobs``; every rank holds its own
@@ -615,7 +626,11 @@ def stability_relevance_on_device(dev: Optional[DeviceData], results: dict, k: i
         more = {"sparse_on_device": True} if sparse_on_device else {}
         n_v = len(dev.data_shapes)
         for v in range(n_v):
-            dev.base.set_reference_clusters(v, results["row_clusters"][v], results["col_clusters"][v])
+            rc, cc = results["row_clusters"][v], results["col_clusters"][v]
+            if all(device_views.is_tensor(x) and device_views.on_engine_device(x, dev.device_id) for x in (rc, cc)):
+                dev.base.set_reference_clusters_device(v, rc, cc)
+            else:
+                dev.base.set_reference_clusters(v, rc, cc)
         draws = stability_draws(dev.data_shapes, n_stability, sample_rate, seed)
 
         def runner(r):

@@ -32,6 +32,7 @@
 #include "resnmtf_kernels.hip.inc"
 #include "resnmtf_device_view.hip.inc"
 #include "resnmtf_device_factors.hip.inc"
+#include "resnmtf_view_readback.hip.inc"
 #include "resnmtf_sparse.hip.inc"
 #include <rocprim/rocprim.hpp>
 #include "resnmtf_sparse_shuffle.hip.inc"
@@ -2487,6 +2488,103 @@ int resnmtf_get_view_csc(resnmtf_handle* h, int v, long long* col_ptr, int* row_
   return RESNMTF_OK;
 }
 
+// The dense view into caller-owned device memory (resnmtf_view_readback.hip.inc): the image
+// resnmtf_get_view downloads, copied by one kernel, ordered with `stream` as resnmtf_finalise_device orders its copies; no
+// transient memory.
+int resnmtf_get_view_device(resnmtf_handle* h, int v, void* out, int dtype, long long row_stride, long long col_stride, void* stream) {
+  const std::string w = "get_view_device: ";
+  if (int rc = check_view(h, v)) return rc;
+  if (!out) return h->fail(RESNMTF_ERR_INVALID, w + "out is NULL");
+  if (dtype == RESNMTF_DTYPE_F16 || dtype == RESNMTF_DTYPE_BF16)
+    return h->fail(RESNMTF_ERR_INVALID, w + "a 16-bit output would narrow the stored f32 values, which is not a copy: RESNMTF_DTYPE_F64 or _F32");
+  if (dtype != RESNMTF_DTYPE_F64 && dtype != RESNMTF_DTYPE_F32) return h->fail(RESNMTF_ERR_INVALID, w + "unknown dtype: RESNMTF_DTYPE_F64 or _F32");
+  const ViewState& vs = h->views[v];
+  if (vs.sparse) return h->fail(RESNMTF_ERR_INVALID, w + "the view is sparse (it would densify it): read it with resnmtf_get_view_sparse_device");
+  if (!vs.owned || !vs.has_x) return h->fail(RESNMTF_ERR_STATE, "no data on this handle for the view");
+  const int n = vs.n, m = vs.m;
+  if ((n > 1 && row_stride <= 0) || (m > 1 && col_stride <= 0))
+    return h->fail(RESNMTF_ERR_INVALID, w + "a stride along an extent above 1 must be positive");
+  if (n > 1 && m > 1) {      // no two elements on one address: the smaller stride's whole extent fits below the larger stride
+    const bool rows_inner = row_stride <= col_stride;
+    const long long a = rows_inner ? row_stride : col_stride, b = rows_inner ? col_stride : row_stride;
+    const long long e = rows_inner ? n : m;
+    if (a * (e - 1) >= b) return h->fail(RESNMTF_ERR_INVALID, w + "the strides make two elements share an address");
+  }
+  if (!on_handle_device(h, out))
+    return h->fail(RESNMTF_ERR_INVALID, w + "out is not device memory of the handle's device (host buffers: resnmtf_get_view)");
+  HIP_TRY(h, hipSetDevice(h->opt.device_id));
+  if (int rc = sync_both(h)) return rc;
+  HIP_TRY(h, wait_for_caller(h, stream));
+  const dim3 grid((unsigned)ceil_div(n, 32) * (unsigned)ceil_div(m, 32));
+  const bool along_c = col_stride < row_stride;      // neighbouring lanes write along the smaller stride
+  pick_bools([&](auto f64, auto ac) {
+    using OUT = std::conditional_t<decltype(f64)::value, double, float>;
+    hipLaunchKernelGGL((view_readback_kernel<OUT, decltype(ac)::value>), grid, dim3(256), 0, h->stream, (const float*)vs.side[SIDE_F].X,
+                       vs.side[SIDE_F].ldx, n, m, static_cast<OUT*>(out), row_stride, col_stride);
+  }, dtype == RESNMTF_DTYPE_F64, along_c);
+  hipError_t e = hipGetLastError();
+  // (the handle's stream is drained before the call returns: whatever the caller enqueues afterwards comes after the writes)
+  const hipError_t es = hipStreamSynchronize(h->stream);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return h->fail_hip("get_view_device", e);
+  return RESNMTF_OK;
+}
+
+// The sparse view into caller-owned device memory, the mirror of resnmtf_set_view_sparse_device:
+// the CSC copy, the CSR copy, or the CSR copy with its row pointers expanded to a row index per entry (COO).  A kept type
+// is a device-to-device copy, a widened or narrowed one a conversion kernel; no transient memory.
+int resnmtf_get_view_sparse_device(resnmtf_handle* h, int v, int layout, void* ptr_or_rows, void* idx_or_cols, int index_type, void* values,
+                                   int dtype, void* stream) {
+  const std::string w = "get_view_sparse_device: ";
+  if (int rc = check_view(h, v)) return rc;
+  const ViewState& vs = h->views[v];
+  if (!vs.sparse) return h->fail(RESNMTF_ERR_INVALID, w + "the view is dense: read it with resnmtf_get_view_device");
+  if (layout != RESNMTF_SPARSE_CSC && layout != RESNMTF_SPARSE_CSR && layout != RESNMTF_SPARSE_COO)
+    return h->fail(RESNMTF_ERR_INVALID, w + "unknown layout: one of RESNMTF_SPARSE_CSC / _CSR / _COO");
+  if (index_type != RESNMTF_INDEX_I32 && index_type != RESNMTF_INDEX_I64)
+    return h->fail(RESNMTF_ERR_INVALID, w + "unknown index type: RESNMTF_INDEX_I32 or _I64");
+  if (dtype == RESNMTF_DTYPE_F16 || dtype == RESNMTF_DTYPE_BF16)
+    return h->fail(RESNMTF_ERR_INVALID, w + "a 16-bit output would narrow the stored f32 values, which is not a copy: RESNMTF_DTYPE_F64 or _F32");
+  if (dtype != RESNMTF_DTYPE_F64 && dtype != RESNMTF_DTYPE_F32) return h->fail(RESNMTF_ERR_INVALID, w + "unknown dtype: RESNMTF_DTYPE_F64 or _F32");
+  if (!vs.owned || !vs.has_x) return h->fail(RESNMTF_ERR_STATE, "no data on this handle for the view");
+  const long long nnz = vs.nnz;
+  const bool i64 = index_type == RESNMTF_INDEX_I64;
+  if (!i64 && nnz > 2147483647LL)
+    return h->fail(RESNMTF_ERR_INVALID, w + "nnz = " + std::to_string(nnz) + " does not fit RESNMTF_INDEX_I32: ask for RESNMTF_INDEX_I64");
+  for (const void* p : {(const void*)ptr_or_rows, (const void*)idx_or_cols, (const void*)values})
+    if (p && !on_handle_device(h, p))
+      return h->fail(RESNMTF_ERR_INVALID, w + "an array is not device memory of the handle's device (host buffers: resnmtf_get_view_csc)");
+  HIP_TRY(h, hipSetDevice(h->opt.device_id));
+  if (int rc = sync_both(h)) return rc;
+  HIP_TRY(h, wait_for_caller(h, stream));
+  hipStream_t st = h->stream;
+  const bool csc = layout == RESNMTF_SPARSE_CSC, coo = layout == RESNMTF_SPARSE_COO;
+  const Side& sd = vs.side[csc ? SIDE_G : SIDE_F];      // the CSC copy walks the columns (SIDE_G), the CSR copy the rows
+  const long long lines = sd.len;
+  auto blocks = [](long long count) { return dim3((unsigned)((count + 255) / 256)); };
+  hipError_t e = hipSuccess;
+  if (ptr_or_rows && coo && nnz > 0) {
+    if (i64) hipLaunchKernelGGL(readback_expand_rows_kernel<long long>, blocks(nnz), dim3(256), 0, st, (const long long*)sd.sp_ptr, vs.n, nnz, static_cast<long long*>(ptr_or_rows));
+    else hipLaunchKernelGGL(readback_expand_rows_kernel<int>, blocks(nnz), dim3(256), 0, st, (const long long*)sd.sp_ptr, vs.n, nnz, static_cast<int*>(ptr_or_rows));
+  } else if (ptr_or_rows && !coo) {
+    if (i64) e = hipMemcpyAsync(ptr_or_rows, sd.sp_ptr, (size_t)(lines + 1) * sizeof(long long), hipMemcpyDeviceToDevice, st);
+    else hipLaunchKernelGGL((readback_convert_kernel<long long, int>), blocks(lines + 1), dim3(256), 0, st, (const long long*)sd.sp_ptr, lines + 1, static_cast<int*>(ptr_or_rows));
+  }
+  if (e == hipSuccess && idx_or_cols && nnz > 0) {
+    if (!i64) e = hipMemcpyAsync(idx_or_cols, sd.sp_idx, (size_t)nnz * sizeof(int), hipMemcpyDeviceToDevice, st);
+    else hipLaunchKernelGGL((readback_convert_kernel<int, long long>), blocks(nnz), dim3(256), 0, st, (const int*)sd.sp_idx, nnz, static_cast<long long*>(idx_or_cols));
+  }
+  if (e == hipSuccess && values && nnz > 0) {
+    if (dtype == RESNMTF_DTYPE_F32) e = hipMemcpyAsync(values, sd.sp_val, (size_t)nnz * sizeof(float), hipMemcpyDeviceToDevice, st);
+    else hipLaunchKernelGGL((readback_convert_kernel<float, double>), blocks(nnz), dim3(256), 0, st, (const float*)sd.sp_val, nnz, static_cast<double*>(values));
+  }
+  if (e == hipSuccess) e = hipGetLastError();
+  const hipError_t es = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return h->fail_hip("get_view_sparse_device", e);
+  return RESNMTF_OK;
+}
+
 namespace {
 // The tail of both factor routes (resnmtf_set_factors, resnmtf_set_factors_device) for an owned view, once W of both sides
 // and both lm vectors are on their way on the handle's stream: the zeroed operand images, T32 and counters, then the f32 /
@@ -3662,6 +3760,66 @@ int resnmtf_set_reference_clusters(resnmtf_handle* h, int v, int k, const double
   HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&vs.ref_cl), bytes.size()));
   const hipError_t e = hipMemcpy(vs.ref_cl, bytes.data(), bytes.size(), hipMemcpyHostToDevice);
   if (e != hipSuccess) { (void)hipFree(vs.ref_cl); vs.ref_cl = nullptr; return h->fail_hip("set_reference_clusters", e); }
+  vs.ref_k = k;
+  return RESNMTF_OK;
+}
+
+// The same from 0 / 1 matrices that are ALREADY in device memory (resnmtf_view_readback.hip.inc):
+// checked and packed on the device into a fresh block, which replaces the view's block only when every entry passed.
+// Transient device memory: the two flag words.
+int resnmtf_set_reference_clusters_device(resnmtf_handle* h, int v, int k, const resnmtf_device_matrix* row_clusters,
+                                          const resnmtf_device_matrix* col_clusters, void* stream) {
+  if (int rc = check_view(h, v)) return rc;
+  if (!row_clusters || !col_clusters || !row_clusters->ptr || !col_clusters->ptr) return h->fail(RESNMTF_ERR_INVALID, "row_clusters / col_clusters are NULL");
+  if (k < 1 || k > RESNMTF_MAX_K) return h->fail(RESNMTF_ERR_INVALID, "k must be in [1, 64]");
+  for (const resnmtf_device_matrix* a : {row_clusters, col_clusters}) {
+    if (a->dtype != RESNMTF_DTYPE_F64 && a->dtype != RESNMTF_DTYPE_F32 && a->dtype != RESNMTF_DTYPE_F16 && a->dtype != RESNMTF_DTYPE_BF16)
+      return h->fail(RESNMTF_ERR_INVALID, "unknown dtype: one of RESNMTF_DTYPE_F64 / _F32 / _F16 / _BF16");
+    if (a->row_stride < 0 || a->col_stride < 0) return h->fail(RESNMTF_ERR_INVALID, "negative strides are not supported");
+  }
+  for (const resnmtf_device_matrix* a : {row_clusters, col_clusters})
+    if (!on_handle_device(h, a->ptr))
+      return h->fail(RESNMTF_ERR_INVALID, "a cluster matrix is not device memory of the handle's device (host matrices: resnmtf_set_reference_clusters)");
+  ViewState& vs = h->views[v];
+  const size_t nk = (size_t)vs.n * k, mk = (size_t)vs.m * k;
+  HIP_TRY(h, hipSetDevice(h->opt.device_id));
+  if (int rc = sync_both(h)) return rc;
+  unsigned char* fresh = nullptr;
+  int bad_host[2] = {0, 0};
+  hipError_t e = hipSuccess;
+  {
+    Scratch sc;
+    int* bad = sc.take<int>(2);                        // [0]: a bad entry in row_clusters, [1]: in col_clusters
+    if (sc.error() != hipSuccess) return h->fail_hip("hipMalloc set_reference_clusters_device flags", sc.error());
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&fresh), nk + mk));
+    e = wait_for_caller(h, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(bad, 0, 2 * sizeof(int), h->stream);
+    if (e == hipSuccess) {
+      // a column-major source (row stride the smaller) is read with threads along the rows, through the LDS tile
+      auto pack = [&](const resnmtf_device_matrix* a, int len, unsigned char* dst, int* flag) {
+        const dim3 grid((unsigned)ceil_div(len, 32) * (unsigned)ceil_div(k, 32));
+        pick_int<RESNMTF_DTYPE_F64, RESNMTF_DTYPE_F32, RESNMTF_DTYPE_F16, RESNMTF_DTYPE_BF16>(a->dtype, [&](auto dt) {
+          pick_bools([&](auto along_r) {
+            hipLaunchKernelGGL((reference_clusters_pack_kernel<decltype(dt)::value, decltype(along_r)::value>), grid, dim3(256), 0, h->stream,
+                               a->ptr, a->row_stride, a->col_stride, len, k, dst, flag);
+          }, a->row_stride < a->col_stride);
+        });
+      };
+      pack(row_clusters, vs.n, fresh, bad);
+      pack(col_clusters, vs.m, fresh + nk, bad + 1);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(bad_host, bad, sizeof(bad_host), hipMemcpyDeviceToHost, h->stream);
+    const hipError_t es = hipStreamSynchronize(h->stream);   // the sources may be freed on return
+    if (e == hipSuccess) e = es;
+  }
+  if (e != hipSuccess) { (void)hipFree(fresh); return h->fail_hip("set_reference_clusters_device", e); }
+  if (bad_host[0] || bad_host[1]) {
+    (void)hipFree(fresh);
+    return h->fail(RESNMTF_ERR_INVALID, bad_host[0] ? "row_clusters entries must be 0 or 1" : "col_clusters entries must be 0 or 1");
+  }
+  if (vs.ref_cl) (void)hipFree(vs.ref_cl);
+  vs.ref_cl = fresh;
   vs.ref_k = k;
   return RESNMTF_OK;
 }

@@ -248,6 +248,27 @@ def upload(eng, v: int, x, raw: bool = False) -> bool:
     return False
 
 
+def on_engine_device(x, device_id: int = 0) -> bool:
+    """A ``torch`` tensor that lives on ``cuda:device_id``: what the device routes read in place."""
+    return is_tensor(x) and x.device.type == "cuda" and x.device.index == int(device_id)
+
+
+def check_readback_strides(shape, strides, what: str = "out"):
+    """The layout ``Engine.get_view_device`` may write to (``resnmtf_get_view_device``): ``shape`` =
+    (n, m), ``strides`` = (row stride, column stride) in ELEMENTS.  A stride along an extent above 1 must be positive,
+    and no two elements may share an address: with a <= b the two strides and e the extent along a, a (e - 1) < b --
+    every slice or transpose of a contiguous tensor passes.  The stride of an extent-1 axis is never used and may be
+    anything.  Pure; ``ValueError`` otherwise."""
+    (n, m), (rs, cs) = (int(x) for x in shape), (int(x) for x in strides)
+    if (n > 1 and rs <= 0) or (m > 1 and cs <= 0):
+        raise ValueError(f"{what}: a stride along an extent above 1 must be positive, got strides ({rs}, {cs}) for shape "
+                         f"({n}, {m}) (an expand()ed tensor has stride 0)")
+    if n > 1 and m > 1:
+        a, b, e = (rs, cs, n) if rs <= cs else (cs, rs, m)
+        if a * (e - 1) >= b:
+            raise ValueError(f"{what}: strides ({rs}, {cs}) make two elements of a ({n}, {m}) matrix share an address")
+
+
 def to_numpy(x):
     """A NumPy copy of a small result matrix for the host steps (a tensor is downloaded; an array is returned as it is)."""
     return x.detach().cpu().numpy() if is_tensor(x) else x

@@ -433,6 +433,79 @@ class Engine:
         self._check(self._lib.resnmtf_get_view(self._h, v, _dp(x)))
         return x
 
+    def get_view_device(self, v: int, dtype=None, order: str = "C", out=None):
+        """``get_view`` with the data left on the device (``resnmtf_get_view_device``): a ``torch`` tensor on this engine's
+        GPU, ``dtype`` fp32 (default: the stored image, kept) or fp64 (widened exactly), row-major (``order="C"``) or
+        column-major (``"F"``); bitwise the values ``get_view`` returns.  ``out=``: any 2-D fp32 / fp64 tensor of the
+        view's shape on this GPU whose strides put no two elements on one address (a slice or transpose of a larger
+        tensor included; ``device_views.check_readback_strides``) is written in place and returned; ``dtype`` and
+        ``order`` are then not read.  Ordered with torch's current stream of that device.  A sparse view is refused
+        (``get_view_sparse_device``)."""
+        import torch            # (lazily: nothing else in this module needs it)
+        from . import device_views
+        n, m = self.n_rows[v], self.n_cols[v]
+        dev = torch.device("cuda", self.device_id)
+        codes = {torch.float64: _lib.DTYPE_F64, torch.float32: _lib.DTYPE_F32}
+        if out is None:
+            dtype = torch.float32 if dtype is None else dtype
+            if dtype not in codes:
+                raise ValueError(f"get_view_device returns fp32 or fp64 (narrowing is not a copy), got {dtype}")
+            if order not in ("C", "F"):
+                raise ValueError("order must be 'C' or 'F'.")
+            out = torch.empty((n, m), dtype=dtype, device=dev) if order == "C" else torch.empty((m, n), dtype=dtype, device=dev).T
+        else:
+            if not isinstance(out, torch.Tensor):
+                raise TypeError("out must be a torch.Tensor (host data: get_view)")
+            if out.dtype not in codes:
+                raise ValueError(f"out must be fp32 or fp64 (narrowing is not a copy), got {out.dtype}")
+            if out.ndim != 2 or tuple(out.shape) != (n, m):
+                raise ValueError(f"expected shape {(n, m)}, got {tuple(out.shape)}")
+            if out.device.type != "cuda" or out.device.index != self.device_id:
+                raise ValueError(f"out lives on {out.device}, the engine on cuda:{self.device_id}")
+            device_views.check_readback_strides(out.shape, out.stride())
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self._check(self._lib.resnmtf_get_view_device(self._h, v, C.c_void_p(out.data_ptr()), codes[out.dtype],
+                                                      int(out.stride(0)), int(out.stride(1)), C.c_void_p(stream)))
+        return out
+
+    def get_view_sparse_device(self, v: int, layout: str = "csc", index_dtype=None, dtype=None):
+        """``get_view_sparse`` with the data left on the device (``resnmtf_get_view_sparse_device``): sparse view ``v`` as
+        a ``torch.sparse_csc_tensor`` (``layout="csc"``: bitwise the arrays ``get_view_sparse`` returns, explicit zeros
+        kept), ``sparse_csr_tensor`` (``"csr"``: columns ascending within a row) or ``sparse_coo_tensor`` (``"coo"``:
+        row-major sorted, built with ``is_coalesced=True``) on this engine's GPU, indices int64 (default) or int32 (a COO
+        tensor holds int64 indices whatever it is given: torch widens them), values fp32 (default) or fp64.  Ordered with torch's current stream of that device.  A dense view is refused
+        (``get_view_device``)."""
+        import torch            # (lazily: nothing else in this module needs it)
+        layouts = {"csc": _lib.SPARSE_CSC, "csr": _lib.SPARSE_CSR, "coo": _lib.SPARSE_COO}
+        if layout not in layouts:
+            raise ValueError("layout must be 'csc', 'csr' or 'coo'.")
+        index_dtype = torch.int64 if index_dtype is None else index_dtype
+        dtype = torch.float32 if dtype is None else dtype
+        if index_dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"index_dtype must be int32 or int64, got {index_dtype}")
+        codes = {torch.float64: _lib.DTYPE_F64, torch.float32: _lib.DTYPE_F32}
+        if dtype not in codes:
+            raise ValueError(f"get_view_sparse_device returns fp32 or fp64 values (narrowing is not a copy), got {dtype}")
+        n, m = self.n_rows[v], self.n_cols[v]
+        sparse_view, nnz, _ = self.view_storage(v)
+        if not sparse_view:
+            nnz = 0                 # (the library refuses the dense view below, before it writes anything)
+        dev = torch.device("cuda", self.device_id)
+        a = torch.empty(nnz if layout == "coo" else (m if layout == "csc" else n) + 1, dtype=index_dtype, device=dev)
+        b = torch.empty(nnz, dtype=index_dtype, device=dev)
+        vals = torch.empty(nnz, dtype=dtype, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        # (an empty tensor has no allocation: NULL = skipped)
+        ptrs = [C.c_void_p(t.data_ptr()) if t.numel() else None for t in (a, b, vals)]
+        self._check(self._lib.resnmtf_get_view_sparse_device(
+            self._h, v, layouts[layout], ptrs[0], ptrs[1], _lib.INDEX_I64 if index_dtype == torch.int64 else _lib.INDEX_I32,
+            ptrs[2], codes[dtype], C.c_void_p(stream)))
+        if layout == "csc":
+            return torch.sparse_csc_tensor(a, b, vals, size=(n, m))
+        if layout == "csr":
+            return torch.sparse_csr_tensor(a, b, vals, size=(n, m))
+        return torch.sparse_coo_tensor(torch.stack((a, b)), vals, size=(n, m), is_coalesced=True)
+
     def init_svd(self, v: int, seed: int = 0, sigma: float = 0.05, n_power: int = 0, return_basis: bool = False):
         """``init_mats_inner`` (``R/update_steps.r:78-125``) on the device for view ``v`` (randomized
         top-k SVD on the streaming-pass kernels); returns the k leading singular values.
@@ -613,6 +686,34 @@ class Engine:
             raise ValueError(f"row clusters must be {self.n_rows[v]} x k")
         cc = _f64_colmajor(cc, (self.n_cols[v], rc.shape[1]))
         self._check(self._lib.resnmtf_set_reference_clusters(self._h, v, int(rc.shape[1]), _dp(rc), _dp(cc)))
+
+    def set_reference_clusters_device(self, v: int, rc, cc):
+        """``set_reference_clusters`` from device memory (``resnmtf_set_reference_clusters_device``): ``rc`` (n x k) and
+        ``cc`` (m x k) are 2-D floating ``torch`` tensors (fp64 / fp32 / fp16 / bf16, any strides) of 0 / 1 on this
+        engine's GPU -- ``finalise_device``'s cluster matrices as they come --, read in place, ordered after the work
+        enqueued on torch's current stream of that device, checked on the device (an entry other than 0 or 1 raises
+        ``ResnmtfError`` and leaves the earlier reference clusters in place).  ``relevance`` / ``relevance_masked`` then
+        return the bits they return after ``set_reference_clusters`` of the same values."""
+        import torch            # (lazily: nothing else in this module needs it)
+        codes = {torch.float64: _lib.DTYPE_F64, torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16,
+                 torch.bfloat16: _lib.DTYPE_BF16}
+        for t, name in ((rc, "rc"), (cc, "cc")):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"set_reference_clusters_device takes torch.Tensors, {name} is a {type(t).__name__} "
+                                "(host matrices: set_reference_clusters)")
+            if t.dtype not in codes:
+                raise ValueError(f"{name} must be fp64, fp32, fp16 or bf16, got {t.dtype}")
+            if t.device.type != "cuda" or t.device.index != self.device_id:
+                raise ValueError(f"{name} lives on {t.device}, the engine on cuda:{self.device_id}")
+        if rc.ndim != 2 or rc.shape[0] != self.n_rows[v]:
+            raise ValueError(f"row clusters must be {self.n_rows[v]} x k")
+        if tuple(cc.shape) != (self.n_cols[v], rc.shape[1]):
+            raise ValueError(f"expected shape {(self.n_cols[v], rc.shape[1])}, got {tuple(cc.shape)}")
+        rc, cc = rc.detach(), cc.detach()
+        descs = [_lib.DeviceMatrix(t.data_ptr(), codes[t.dtype], int(t.stride(0)), int(t.stride(1))) for t in (rc, cc)]
+        stream = torch.cuda.current_stream(torch.device("cuda", self.device_id)).cuda_stream
+        self._check(self._lib.resnmtf_set_reference_clusters_device(self._h, v, int(rc.shape[1]), C.byref(descs[0]),
+                                                                    C.byref(descs[1]), C.c_void_p(stream)))
 
     def relevance(self, v: int, ref_engine: "Engine", v_ref: int, rows, cols) -> np.ndarray:
         """``relevance_results`` (``R/stability_analysis.r:45-67``) of this engine's view ``v`` (its current factors,

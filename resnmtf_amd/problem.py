@@ -175,16 +175,18 @@ def reported_error(errs, n_iters) -> float:
 _INNER_KEYS = ("output_f", "output_s", "output_g", "Error", "All_Error", "bisil", "row_clusters", "col_clusters",
                "lambda", "mu", "spurious", "init", "state", "tag", "extras")
 _DEVICE_DATA_KEYS = ("output_f", "output_s", "output_g", "row_clusters", "col_clusters", "Error", "All_Error", "tag",
-                     "extras", "row_names", "col_names", "init", "lambda", "mu", "data", "spurious_check", "device_out")
+                     "extras", "row_names", "col_names", "init", "lambda", "mu", "data", "device_data", "spurious_check", "device_out")
 
 
 def inner_result(output_f, output_s, output_g, errs=None, n_iters=None, *, lam=None, mu=None, device_data: bool = False,
-                 **more) -> dict:
+                 data_on_device=None, **more) -> dict:
     """The result of ``res_nmtf_inner`` (``R/main.r:115-139``) with its keys in their fixed order -- ``device_data``:
     the order of ``DeviceData.factorise`` (clusters before the errors, no ``"bisil"``).  ``errs``: the error trace, which
-    gives ``"Error"``; without it the ``no_clusts`` result.  ``lam``: ``"lambda"``; ``more``: the clusters, ``bisil`` and
-    the optional keys.  A value that is None is left out (``"bisil"`` stays: None = not scored)."""
+    gives ``"Error"``; without it the ``no_clusts`` result.  ``lam``: ``"lambda"``; ``data_on_device``: the key
+    ``"device_data"`` (the flag has the name); ``more``: the clusters, ``bisil`` and the optional keys.  A value that is None is left out (``"bisil"`` stays: None = not scored)."""
     vals = dict(more, output_f=output_f, output_s=output_s, output_g=output_g, mu=mu, **{"lambda": lam})
+    if data_on_device is not None:
+        vals["device_data"] = data_on_device
     if errs is not None:
         vals.update(Error=reported_error(errs, n_iters), All_Error=errs)
         if not device_data:
