@@ -760,6 +760,32 @@ int resnmtf_bisil(resnmtf_handle* h, int v, int k, const double* row_clusters, c
  */
 int resnmtf_bisil_sparse(resnmtf_handle* h, int v, int k, const double* row_clusters, const double* col_clusters,
                          int metric, double* row_sil, double* col_sil);
+/*
+ * resnmtf_bisil / resnmtf_bisil_sparse from cluster matrices that are ALREADY in device memory, with the view's score
+ * (bisilhouette::bisilhouette's value for the view, R/obtain_bicl.r:189-199) combined on the device too; dense and
+ * sparse views alike (the entry dispatches on the view's storage).  row_clusters / col_clusters: n_rows[v] x k and
+ * n_cols[v] x k matrices of 0 / 1, each a resnmtf_device_matrix as resnmtf_set_reference_clusters_device takes one -- any
+ * of the four floating types, any non-negative strides --, read in place after an event recorded on `stream`; checked on
+ * the device (an entry other than 0 or 1, NaN included, is refused with resnmtf_bisil's message, that of row_clusters
+ * first; -0.0 is 0).  row_sil / col_sil: DEVICE pointers to n_rows[v] x k and n_cols[v] x k fp64 column-major arrays, or
+ * both NULL when only the score is wanted; bit for bit what resnmtf_bisil / resnmtf_bisil_sparse write for the same
+ * clusters (the membership words, counts, the union U, rank and every bicluster's member and feature lists are built by
+ * kernels in the order the host builds them; the gather / scatter, norm, distance and epilogue kernels are the same).
+ * view_score: a HOST pointer to one double, required: per active bicluster l the mean of the row silhouettes over I_l
+ * and of the column silhouettes over J_l (members in ascending index order, summed in NumPy's order), sigma_l = half
+ * their sum, then the mean of the sigma_l; 0 with fewer than two active biclusters -- resnmtf_amd/bisil.py's view_score,
+ * bit for bit.  No active bicluster: zero silhouettes, score 0, RESNMTF_OK.  Blocking.  The host reads back 2 k + 3 ints
+ * (the refusal bits, |U| of both sides, the member counts) and the score; nothing of size n or m crosses the bus.
+ * Transient device memory beyond resnmtf_bisil's workspace (sized and refused in the same way, RESNMTF_ERR_ALLOC): two
+ * u64 arrays and one int array (sparse: two) over n + m points, the int lists and the gathered silhouettes over
+ * sum |I_l| + sum |J_l| entries: O(n + m + sum |I_l| + sum |J_l|).  Refused before any device work: NULL descriptors or
+ * view_score, k outside [1, 64], an unknown dtype, a negative stride, a matrix or output that is not device memory of
+ * the handle's device, an unknown metric (RESNMTF_ERR_INVALID); a view without data, a dense view that holds only a
+ * 2-byte image (RESNMTF_ERR_STATE).  A refusal writes neither output.  DESIGN.md section 19.
+ */
+int resnmtf_bisil_device(resnmtf_handle* h, int v, int k, const resnmtf_device_matrix* row_clusters,
+                         const resnmtf_device_matrix* col_clusters, int metric, double* row_sil, double* col_sil,
+                         double* view_score, void* stream);
 
 /*
  * Many small factorisations in one launch (the k sweep, the shuffled fits of obtain_shuffled_f, the sub-sample fits of

@@ -154,7 +154,8 @@ SIGNATURES = {
     "resnmtf_group_run": (C.c_int, [C.c_int, C.c_int, C.POINTER(GroupJob), C.c_double, C.c_int]),
     "resnmtf_bisil": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_bisil_sparse": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
-    "resnmtf_reserve_sweeps": (C.c_int, [_h, C.c_int]),
+    "resnmtf_bisil_device": (C.c_int, [_h, C.c_int, C.c_int, _dm, _dm, C.c_int, C.c_void_p, C.c_void_p, _dp, C.c_void_p]),
+    "resnmtf_reserve_sweeps":(C.c_int, [_h, C.c_int]),
     "resnmtf_prepare": (C.c_int, [_h]),
     "resnmtf_phase": (C.c_int, [_h, C.c_int, C.c_int, C.c_int]),
     "resnmtf_factor_device_ptr": (C.c_int, [_h, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),

@@ -103,7 +103,8 @@ def res_nmtf_inner(data, row_indices, column_indices,
                    max_iters: int = 100000, seed: Optional[int] = None, engine_opts: Optional[dict] = None,
                    host_init: bool = False, return_init: bool = False, score_bisil: bool = False,
                    spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False,
-                   sparse_on_device: bool = False, output: str = "numpy", init_lm=None, return_state: bool = False):
+                   sparse_on_device: bool = False, output: str = "numpy", init_lm=None, return_state: bool = False,
+                   post_on_device: bool = False):
     """``res_nmtf_inner`` (``R/main.r:32-140``).
 
     ``data``: list of pre-processed (non-negative, column-normalised) matrices; ``row_indices[v][w]``
@@ -165,8 +166,17 @@ def res_nmtf_inner(data, row_indices, column_indices,
     concatenated, the state and the outputs).  In convergence mode (``n_iters=None``) the first stop test after a resume
     compares with 0, as that of any fresh run does (``R/main.r:53-54``): the previous mean error is not carried over, so
     the stop sweep can differ, and only when the uninterrupted run would have stopped on the first resumed sweep.
+
+    ``post_on_device`` (keyword-only opt-in; needs ``output="torch"``, else ``ValueError``): the
+    steps after the loop stay on the device.  ``Engine.finalise`` and ``Engine.get_factors`` are not called: F, S, G and
+    the clusters come from ``Engine.finalise_device``, lambda and mu from ``Engine.get_factors_device`` (those two
+    k-vectors are copied to the host: the result keeps its types); the removal is ``spurious.apply_removal_device`` (the
+    k x k S copied to the host, the flagged columns zeroed in clones of the cluster tensors) and ``bisil`` is scored from
+    the cleaned tensors (``Engine.bisil_device``: silhouettes and their combination on the device).  The result equals
+    the same call without the flag key for key, bit for bit.
     """
     device_views.check_output(output)
+    _check_post_on_device(post_on_device, output)
     data = _views(data, device_id)
     n_v = len(data)
     if k_vec is None:
@@ -224,15 +234,22 @@ def res_nmtf_inner(data, row_indices, column_indices,
         total_err = eng.run(n_iters=n_iters, tol=1.0e-6, max_iters=max_iters)
         state = [raw_state(v) for v in range(n_v)] if return_state else None          # ... and the one it ended in
         # per view: F, S, G, the binary clusters (main.r:110 + obtain_bicl.r:162-180), lambda, mu
-        out_f, out_s, out_g, row_cl, col_cl, lams, mus = (
-            list(x) for x in zip(*[(*eng.finalise(v), *eng.get_factors(v)[3:]) for v in range(n_v)]))
-        on_device = [eng.finalise_device(v) for v in range(n_v)] if output == "torch" else None
+        if post_on_device:               # everything of size n or m stays where it is; the two k-vectors come to the host
+            out_f, out_s, out_g, row_cl, col_cl, lams, mus = (
+                list(x) for x in zip(*[(*eng.finalise_device(v), *(device_views.to_numpy(t) for t in eng.get_factors_device(v)[3:]))
+                                       for v in range(n_v)]))
+            on_device = None
+        else:
+            out_f, out_s, out_g, row_cl, col_cl, lams, mus = (
+                list(x) for x in zip(*[(*eng.finalise(v), *eng.get_factors(v)[3:]) for v in range(n_v)]))
+            on_device = [eng.finalise_device(v) for v in range(n_v)] if output == "torch" else None
         check = (_spurious.check_on_device(eng, num_repeats, seed, max_iters=max_iters, device_id=device_id,
                                            shuffle_sparse=shuffle_sparse)
                  if remove else None)                                                             # obtain_bicl.r:151-188
         score_fn = ((lambda rc, cc: bisil.score(rc, cc, distance, engine=eng, sparse_views=bisil_sparse))
                     if score_bisil and not no_clusts else None)                                   # obtain_bicl.r:189-199
-        cleaned = _remove_then_score({"output_s": out_s, "row_clusters": row_cl, "col_clusters": col_cl}, check, score_fn)
+        cleaned = _remove_then_score({"output_s": out_s, "row_clusters": row_cl, "col_clusters": col_cl}, check, score_fn,
+                                     on_device=post_on_device)
     finally:
         eng.close()
     # ("init": a test hook, the initial state the device built, for a reference run from the same start)
@@ -255,11 +272,18 @@ def _device_outputs(on_device, row_cl, col_cl, cleaned: dict):
     return tuple([t[i] for t in on_device] for i in range(3))
 
 
-def _remove_then_score(res: dict, check: Optional[dict], score_fn: Optional[Callable]) -> dict:
+def _check_post_on_device(post_on_device: bool, output: str):
+    if post_on_device and output != "torch":
+        raise ValueError("post_on_device=True needs output='torch' (the steps after the loop then work on the device tensors).")
+
+
+def _remove_then_score(res: dict, check: Optional[dict], score_fn: Optional[Callable], on_device: bool = False) -> dict:
     """R's order (``R/obtain_bicl.r:176-199``): with a ``check`` (``check_biclusters``' scores and thresholds) the
-    removal first (``spurious.apply_removal``: copies, ``"spurious"`` added), then ``"bisil"`` = ``score_fn(row_clusters,
-    col_clusters)`` of the cleaned clusters (``None`` without a ``score_fn``).  Returns a new dict."""
-    out = _spurious.apply_removal(res, check) if check is not None else dict(res)
+    removal first (``spurious.apply_removal``: copies, ``"spurious"`` added; ``on_device``: the clusters are tensors,
+    ``spurious.apply_removal_device``), then ``"bisil"`` = ``score_fn(row_clusters, col_clusters)`` of the cleaned
+    clusters (``None`` without a ``score_fn``).  Returns a new dict."""
+    removal = _spurious.apply_removal_device if on_device else _spurious.apply_removal
+    out = removal(res, check) if check is not None else dict(res)
     out["bisil"] = None if score_fn is None else score_fn(out["row_clusters"], out["col_clusters"])
     return out
 
@@ -443,7 +467,7 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                   device_id: int = 0, max_iters: int = 100000, seed: Optional[int] = None,
                   k_sweep: bool = False, return_sweep: bool = False, sweep_runner: Optional[Callable] = None,
                   spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False,
-                  sparse_on_device: bool = False, output: str = "numpy"):
+                  sparse_on_device: bool = False, output: str = "numpy", post_on_device: bool = False):
     """``apply_resnmtf`` (``R/main.r:214-335``) for a known ``k_val``: naming, shared-name maps, restriction
     symmetrisation, non-negativity shift and column normalisation on the host, then the device loop and -- with
     ``stability=True`` (the default) and ``spurious=False`` -- ``stability_check`` on the pre-processed data, as
@@ -490,10 +514,18 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     returns ``output_f`` / ``output_s`` / ``output_g`` / ``row_clusters`` / ``col_clusters`` as fp64 ``torch`` tensors on
     that device (``Engine.finalise_device``); the small values stay NumPy.  With a ``k_val``, ``init_f`` / ``init_s`` /
     ``init_g`` may be ``torch`` tensors on that device too (``res_nmtf_inner``); the k sweep refuses
-    explicit factors as before."""
+    explicit factors as before.
+
+    ``post_on_device=True`` (keyword-only opt-in, needs ``output="torch"``): the steps after the
+    loop stay on the device, in ``res_nmtf_inner`` and for every k of the sweep, the extension k's included
+    (``DeviceData.factorise(post_on_device=True)``; removal and ``bisil`` from the tensors it returns).  Same result,
+    bit for bit."""
     device_views.check_output(output)
+    _check_post_on_device(post_on_device, output)
     on_dev = {"sparse_on_device": True} if sparse_on_device else {}      # (off: every call below is the earlier one)
     out_kw = {"output": output} if output != "numpy" else {}
+    if post_on_device:
+        out_kw["post_on_device"] = True
     data = _views(data, device_id)
     n_v = len(data)
     if k_val is None and k_sweep:
@@ -523,6 +555,7 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                              row_names=p.row_names, col_names=p.col_names, device_id=device_id, max_iters=max_iters,
                              seed=seed, spurious_on_device=spurious_on_device, shuffle_sparse=shuffle_sparse, **on_dev,
                              **out_kw)
+    out_kw.pop("post_on_device", None)                                                            # (stability_check has no such step)
     if stability:                                                                                 # main.r:255-262
         results = stability_check(p.data, results, k_vec, p.phi, p.xi, p.psi, n_iters, spurious, num_repeats,
                                   no_clusts, distance, sample_rate, n_stability, stab_thres,
@@ -565,11 +598,12 @@ def _sweep(run: Callable, k_min: int, k_max: int, cap: int, initial: Optional[li
 def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k_max, distance, spurious, num_repeats,
                    no_clusts, sample_rate, n_stability, stability, stab_thres, remove_unstable, *, row_names, col_names,
                    device_id, max_iters, seed, return_sweep, sweep_runner, spurious_on_device=False, bisil_sparse=False,
-                   shuffle_sparse=False, sparse_on_device=False, output="numpy"):
+                   shuffle_sparse=False, sparse_on_device=False, output="numpy", post_on_device=False):
     """``apply_resnmtf`` with ``k_val = NULL`` (``R/main.r:269-334``); see ``apply_resnmtf``."""
     n_v = len(data)
     on_dev = {"sparse_on_device": True} if sparse_on_device else {}
     out_kw = {"output": output} if output != "numpy" else {}
+    post_kw = {"post_on_device": True} if post_on_device else {}
     _check_common(n_iters, num_repeats, n_stability, distance, sample_rate, stab_thres)
     _check_whole_number(k_min, "k_min")
     _check_whole_number(k_max, "k_max")
@@ -607,9 +641,10 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
                 cleaned = _remove_then_score({key: r[key] for key in ("output_s", "row_clusters", "col_clusters")},
                                              r.get("spurious_check"),
                                              lambda rc, cc: bisil.score(rc, cc, distance, engine=dev.base,
-                                                                        sparse_views=bisil_sparse))
+                                                                        sparse_views=bisil_sparse),
+                                             on_device=post_on_device)
                 out = (r["output_f"], r["output_s"], r["output_g"])
-                if r.get("device_out") is not None:         # output="torch": what is returned lives on the device
+                if r.get("device_out") is not None and not post_on_device:      # output="torch": what is returned lives on the device
                     out = _device_outputs(r["device_out"], r["row_clusters"], r["col_clusters"], cleaned)
                 return inner_result(*out, r["All_Error"], n_iters,
                                     bisil=cleaned["bisil"], row_clusters=cleaned["row_clusters"],
@@ -621,12 +656,13 @@ def _apply_k_sweep(data, init_f, init_s, init_g, phi, xi, psi, n_iters, k_min, k
             def run(k):
                 return scored(dev.factorise(k, n_iters, seed + k, max_iters=max_iters, tag=f"k={k}", return_lm=True,
                                             spurious_repeats=spurious_repeats, spurious_seed=seed + k,
-                                            shuffle_sparse=shuffle_sparse, **on_dev, **out_kw))
+                                            shuffle_sparse=shuffle_sparse, **on_dev, **out_kw, **post_kw))
 
             initial = [scored(r) for r in batched.k_sweep_on_device(dev, k_min, k_max, n_iters, seed,       # main.r:279-290
                                                                     max_iters=max_iters, return_lm=True,
                                                                     spurious_repeats=spurious_repeats,
-                                                                    shuffle_sparse=shuffle_sparse, **on_dev, **out_kw)]
+                                                                    shuffle_sparse=shuffle_sparse, **on_dev, **out_kw,
+                                                                    **post_kw)]
         else:
             run, initial = sweep_runner, None
         ks, scores, results, pick = _sweep(run, k_min, k_max, cap, initial)

@@ -440,7 +440,7 @@ class DeviceData:
                   max_iters: int = 100000, tag: str = "", samples=None, return_init: bool = False,
                   return_data: bool = False, return_lm: bool = False, spurious_repeats: int = 0,
                   spurious_seed: int = 0, *, shuffle_sparse: bool = False, sparse_on_device: bool = False,
-                  output: str = "numpy") -> dict:
+                  output: str = "numpy", post_on_device: bool = False) -> dict:
         """One factorisation with k biclusters per view of the views copied, shuffled (``shuffle_seed``) or sub-sampled
         (``samples``) on the device (``child``): device SVD init, loop, finalise.  With ``samples`` whose trimming
         fails: ``{"stability_performed": False, "tag"}``.
@@ -459,9 +459,14 @@ class DeviceData:
         ``return_data`` ``"device_data"``: per view the device's copy of the data factorised, left on the device -- a
         dense fp32 tensor (``Engine.get_view_device``) or a ``sparse_csc`` tensor (``Engine.get_view_sparse_device``).  A
         shuffled sparse view is then not refused: its entry of ``"data"`` is ``None`` and ``"device_data"`` holds the
-        shuffle."""
+        shuffle.  ``post_on_device`` (opt-in, needs ``output="torch"``, else ``ValueError``):
+        ``Engine.finalise`` and ``Engine.get_factors`` are not called -- ``output_f`` / ``output_s`` / ``output_g`` /
+        ``row_clusters`` / ``col_clusters`` ARE ``finalise_device``'s tensors and ``"lambda"`` / ``"mu"`` come from
+        ``get_factors_device`` (the two k-vectors copied to the host); same values, bit for bit."""
         n_v = len(self.data_shapes)
         device_views.check_output(output)
+        if post_on_device and output != "torch":
+            raise ValueError("post_on_device=True needs output='torch' (the steps after the loop then work on the device tensors).")
         shuffled_sparse = shuffle_seed is not None and any(c is not None for c in self.sp)
         if return_data and shuffled_sparse and output != "torch":
             raise NotImplementedError("return_data of a shuffled sparse view is not supported (it would densify the shuffle)")
@@ -481,9 +486,14 @@ class DeviceData:
             check = (spurious.check_on_device(eng, spurious_repeats, spurious_seed, max_iters=max_iters,
                                               device_id=self.device_id, shuffle_sparse=shuffle_sparse)
                      if spurious_repeats else None)
-            fin = [eng.finalise(v) for v in range(n_v)]
-            fin_dev = [eng.finalise_device(v) for v in range(n_v)] if output == "torch" else None
-            lms = [eng.get_factors(v)[3:] for v in range(n_v)] if return_lm else None
+            if post_on_device:           # nothing of size n or m is downloaded
+                fin = fin_dev = [eng.finalise_device(v) for v in range(n_v)]
+                lms = ([[device_views.to_numpy(t) for t in eng.get_factors_device(v)[3:]] for v in range(n_v)]
+                       if return_lm else None)
+            else:
+                fin = [eng.finalise(v) for v in range(n_v)]
+                fin_dev = [eng.finalise_device(v) for v in range(n_v)] if output == "torch" else None
+                lms = [eng.get_factors(v)[3:] for v in range(n_v)] if return_lm else None
         f, s, g, rc, cc = (list(x) for x in zip(*fin))
         return inner_result(f, s, g, errs, n_iters, device_data=True, row_clusters=rc, col_clusters=cc, tag=tag,
                             extras={} if ch.samples is None else {"row_samples": ch.samples[0], "col_samples": ch.samples[1]},
@@ -533,15 +543,19 @@ class DeviceData:
 
 def k_sweep_on_device(dev: DeviceData, k_min: int = 3, k_max: int = 8, n_iters=None, seed: int = 0, group=None,
                       max_iters: int = 100000, return_lm: bool = False, spurious_repeats: int = 0, *,
-                      shuffle_sparse: bool = False, sparse_on_device: bool = False, output: str = "numpy") -> List[dict]:
+                      shuffle_sparse: bool = False, sparse_on_device: bool = False, output: str = "numpy",
+                      post_on_device: bool = False) -> List[dict]:
     """The factorisations of the k sweep (``R/main.r:279-290``) from one upload; sharded round-robin over
     the ranks of an initialised process group (every rank holds its own ``DeviceData``).  ``spurious_repeats``: each
     k's result carries its ``"spurious_check"`` (``DeviceData.factorise``, spurious seed ``seed + k``).
     ``sparse_on_device`` (opt-in): every k copies the sparse views from ``dev.base`` on the device
-    (``resnmtf_copy_view_sparse``) instead of uploading the host CSC again.  ``output``: ``DeviceData.factorise``."""
+    (``resnmtf_copy_view_sparse``) instead of uploading the host CSC again.  ``output`` / ``post_on_device``:
+    ``DeviceData.factorise``."""
     more = {"sparse_on_device": True} if sparse_on_device else {}
     if output != "numpy":
         more["output"] = output
+    if post_on_device:
+        more["post_on_device"] = True
     ks = list(range(k_min, k_max + 1))
     return run_jobs(ks, group=group, runner=lambda k: dev.factorise(k, n_iters, seed + k, max_iters=max_iters, tag=f"k={k}",
                                                                     return_lm=return_lm, spurious_repeats=spurious_repeats,

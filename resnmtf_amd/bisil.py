@@ -17,6 +17,8 @@ from typing import Callable, Optional, Sequence
 
 import numpy as np
 
+from . import device_views
+
 METRICS = {"euclidean": 0, "manhattan": 1, "cosine": 2}     # resnmtf_bisil's metric codes (R/utils.r:424-427)
 
 
@@ -52,7 +54,11 @@ def score(row_clusters, col_clusters, distance: str = "euclidean", *,
     ``sil(v, rc, cc, distance)`` -> ``(row_sil, col_sil)``; by default ``engine.bisil`` (an ``Engine`` that holds the
     views' data).  ``sil`` is also the stand-in hook for tests without a device.  ``sparse_views=True`` (with
     ``engine``): a view with ``engine.sparse[v]`` goes through ``engine.bisil_sparse`` (``resnmtf_bisil_sparse``), the
-    others through ``engine.bisil``; by default every view goes through ``engine.bisil``, which refuses a sparse one."""
+    others through ``engine.bisil``; by default every view goes through ``engine.bisil``, which refuses a sparse one.
+    A view whose two cluster matrices are ``torch`` tensors on the engine's GPU is scored there instead
+    (``engine.bisil_device(..., silhouettes=False)``: the silhouettes and their combination stay on the device, dense
+    and sparse views alike, and the returned score is ``view_score`` of them bit for bit); one tensor on the device
+    paired with a host matrix is a ``ValueError``.  ``sparse_views`` keeps its meaning for host matrices only."""
     if distance not in METRICS:
         raise ValueError("distance must be one of 'euclidean', 'manhattan' or 'cosine'.")
     if len(row_clusters) != len(col_clusters):
@@ -66,6 +72,10 @@ def score(row_clusters, col_clusters, distance: str = "euclidean", *,
                 return (engine.bisil_sparse if engine.sparse[v] else engine.bisil)(v, rc, cc, distance)
     scores = []
     for v, (rc, cc) in enumerate(zip(row_clusters, col_clusters)):
+        # both matrices tensors on the engine's GPU: scored and combined there, nothing is downloaded but the score
+        if engine is not None and device_views.cluster_route(rc, cc, getattr(engine, "device_id", 0), f"view {v}"):
+            scores.append(engine.bisil_device(v, rc, cc, distance, silhouettes=False)[2])
+            continue
         rs, cs = sil(v, rc, cc, distance)
         scores.append(view_score(rc, cc, rs, cs))
     return overall(scores)

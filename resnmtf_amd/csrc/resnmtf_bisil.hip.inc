@@ -243,4 +243,186 @@ void bisil_launch_dist(int metric, int kq, dim3 grid, hipStream_t st, const floa
   else bisil_launch_dist_m<BISIL_COSINE>(kq, grid, st, G, nf, upad, n_u, mpos, n_mem, umask, norm2, K, chunk_tiles, partial);
 }
 
+// ---- resnmtf_bisil_device (DESIGN.md section 19): the cluster matrices are in device memory, so the lists above are
+// built there, each in the order bisil_impl builds it on the host, and the score is combined there too.
+//   bisil_words_kernel        one wave per 64 points: the u64 membership word of every point (bit j = entry (p, j) != 0),
+//                             the refusal bit of an entry other than 0 / 1 (x != 0.0 && x != 1.0: NaN is refused, -0.0 is
+//                             0) and the member counts of the k biclusters (integer atomics: exact in any order).  A
+//                             source whose row stride is the smaller is read with lanes along the points, any other with
+//                             lanes along the biclusters and a ballot per point.
+//   bisil_union_kernel        one workgroup per side: the active mask from the counts, then U as an ordered compaction
+//                             of the points with an active bit -- upts ascending, umask, (sparse) rank -- and |U|.
+//   bisil_members_kernel      one workgroup per (active bicluster j, side): the ordered compaction of U's positions with
+//                             bit j (mpos_j, ascending) and, through upts, of those points (the other side's feat_j).
+//   bisil_member_mean_kernel  one workgroup per (active bicluster, side): the members' silhouettes gathered in ascending
+//                             point order, then their mean in NumPy's order (bisil_np_sum) by one thread.
+//   bisil_score_kernel        sigma_l = 0.5 (row mean + column mean) per active l, their mean in NumPy's order; 0 with
+//                             fewer than two active biclusters: bisil.view_score, bit for bit.
+// The compactions are chunked scans inside one workgroup (bisil_scan_step: a ballot per wave, the wave totals through
+// LDS): positions depend on the flags alone.  No spins, no waits between workgroups, no floating-point atomics.
+// Every kernel here is a template (<int UNUSED> where it has no parameter of its own): instantiations are emitted after
+// the existing code, so no existing kernel is displaced in the code object (profiles/kernel_fingerprint.txt).
+
+constexpr int BISIL_SCAN_THREADS = 1024;
+constexpr int BISIL_NP_BLOCK = 8192;      // NumPy reduces a long 1-D array in buffers of 8192 entries, summed in order
+
+// hdr, the ints the host reads back: [0] the refusal bits (1: the row matrix, 2: the column matrix), [1] |U| of the rows,
+// [2] of the columns, [3 .. 3 + k) the row counts, [3 + k .. 3 + 2 k) the column counts
+constexpr int BISIL_HDR_COUNTS = 3;
+
+struct BisilSideMeta {                    // one side's arrays in device memory
+  const unsigned long long* words;        // [n_pts]
+  int n_pts;
+  unsigned long long* umask;              // [n_pts] (|U| used)
+  int* upts;                              // [n_pts] (|U| used)
+  int* rank;                              // [n_pts] or NULL (dense views)
+};
+
+struct BisilOffsets {                     // per side and bicluster: where its lists start (ints of `lists`, doubles of `vals`)
+  int mpos[2][RESNMTF_MAX_K];
+  int feat[2][RESNMTF_MAX_K];
+  int val[2][RESNMTF_MAX_K];
+};
+
+template <int DT, bool ALONG_R>
+__global__ void __launch_bounds__(256)
+bisil_words_kernel(const void* __restrict__ src, long long rs, long long cs, int len, int k, int bad_bit,
+                   unsigned long long* __restrict__ words, int* __restrict__ count, int* __restrict__ refusal) {
+  const int lane = threadIdx.x & 63;
+  const long long p0 = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64;
+  if (p0 >= len) return;                                   // (the whole wave)
+  unsigned long long word = 0ull;
+  bool bad = false;
+  if constexpr (ALONG_R) {
+    const long long p = p0 + lane;
+    if (p < len)
+      for (int j = 0; j < k; ++j) {
+        const double x = load_wide<DT>(src, p * rs + (long long)j * cs);
+        bad |= x != 0.0 && x != 1.0;
+        word |= (unsigned long long)(x != 0.0) << j;
+      }
+  } else {
+    for (int i = 0; i < 64; ++i) {
+      const long long p = p0 + i;
+      double x = 0.0;
+      if (p < len && lane < k) x = load_wide<DT>(src, p * rs + (long long)lane * cs);
+      bad |= x != 0.0 && x != 1.0;
+      const unsigned long long b = __ballot(x != 0.0);
+      if (lane == i) word = b;
+    }
+  }
+  if (__ballot(bad) != 0ull && lane == 0) atomicOr(refusal, bad_bit);
+  if (p0 + lane < len) words[p0 + lane] = word;
+  int mine = 0;
+  for (int j = 0; j < k; ++j) {
+    const int c = __popcll(__ballot((word >> j) & 1ull));
+    if (lane == j) mine = c;
+  }
+  if (mine > 0) atomicAdd(count + lane, mine);
+}
+
+// one step of a workgroup's ordered compaction (every thread calls it): the position of this thread's element among
+// the flagged ones, `running` advanced by the step's count
+__device__ __forceinline__ int bisil_scan_step(bool flag, int& running, int* __restrict__ wsum) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned long long b = __ballot(flag);
+  if (lane == 0) wsum[w] = __popcll(b);
+  __syncthreads();
+  int before = 0, total = 0;
+  for (int i = 0; i < BISIL_SCAN_THREADS / 64; ++i) {
+    const int c = wsum[i];
+    if (i < w) before += c;
+    total += c;
+  }
+  __syncthreads();                                         // (wsum is written again by the next step)
+  const int pos = running + before + __popcll(b & ((1ull << lane) - 1ull));
+  running += total;
+  return pos;
+}
+
+template <int UNUSED>
+__global__ void __launch_bounds__(BISIL_SCAN_THREADS)
+bisil_union_kernel(BisilSideMeta rows, BisilSideMeta cols, int k, int* __restrict__ hdr) {
+  __shared__ int wsum[BISIL_SCAN_THREADS / 64];
+  __shared__ unsigned long long active_s;
+  if (hdr[0] != 0) return;                                 // refused: nothing is built
+  const BisilSideMeta s = blockIdx.x == 0 ? rows : cols;
+  const int t = threadIdx.x;
+  if (t < 64) {
+    const bool on = t < k && hdr[BISIL_HDR_COUNTS + t] > 0 && hdr[BISIL_HDR_COUNTS + k + t] > 0;
+    const unsigned long long a = __ballot(on);
+    if (t == 0) active_s = a;
+  }
+  __syncthreads();
+  const unsigned long long active = active_s;
+  int running = 0;
+  for (int base = 0; base < s.n_pts; base += BISIL_SCAN_THREADS) {
+    const int p = base + t;
+    const unsigned long long b = p < s.n_pts ? s.words[p] & active : 0ull;
+    const int pos = bisil_scan_step(b != 0ull, running, wsum);
+    if (b != 0ull) { s.upts[pos] = p; s.umask[pos] = b; }
+    if (s.rank && p < s.n_pts) s.rank[p] = b != 0ull ? pos : -1;
+  }
+  if (t == 0) hdr[1 + blockIdx.x] = running;
+}
+
+template <int UNUSED>
+__global__ void __launch_bounds__(BISIL_SCAN_THREADS)
+bisil_members_kernel(const unsigned long long* __restrict__ umask_r, const int* __restrict__ upts_r, int n_u_r,
+                     const unsigned long long* __restrict__ umask_c, const int* __restrict__ upts_c, int n_u_c,
+                     unsigned long long active, BisilOffsets off, int* __restrict__ lists) {
+  __shared__ int wsum[BISIL_SCAN_THREADS / 64];
+  const int j = blockIdx.x, sd = blockIdx.y, t = threadIdx.x;
+  if (!((active >> j) & 1ull)) return;
+  const unsigned long long* __restrict__ umask = sd == 0 ? umask_r : umask_c;
+  const int* __restrict__ upts = sd == 0 ? upts_r : upts_c;
+  const int n_u = sd == 0 ? n_u_r : n_u_c;
+  int* __restrict__ mpos = lists + off.mpos[sd][j];
+  int* __restrict__ feat = lists + off.feat[1 - sd][j];    // this side's members are the other side's features
+  int running = 0;
+  for (int base = 0; base < n_u; base += BISIL_SCAN_THREADS) {
+    const int u = base + t;
+    const bool in = u < n_u && ((umask[u] >> j) & 1ull);
+    const int pos = bisil_scan_step(in, running, wsum);
+    if (in) { mpos[pos] = u; feat[pos] = upts[u]; }
+  }
+}
+
+// ndarray.mean()'s sum of a contiguous 1-D fp64 array: buffers of 8192 entries, each summed pairwise
+// (jsd_np_pairwise, resnmtf_jsd.hip.inc), the buffer sums added in order; tests/test_post_on_device_host.py restates it
+__device__ double bisil_np_sum(const double* a, long long n) {
+  double s = jsd_np_pairwise<8>(a, n < BISIL_NP_BLOCK ? n : (long long)BISIL_NP_BLOCK);
+  for (long long i = BISIL_NP_BLOCK; i < n; i += BISIL_NP_BLOCK)
+    s += jsd_np_pairwise<8>(a + i, n - i < BISIL_NP_BLOCK ? n - i : (long long)BISIL_NP_BLOCK);
+  return s;
+}
+
+// sil: [n k] row silhouettes then [m k] column silhouettes, column-major; cnt: [k] row counts then [k] column counts
+template <int UNUSED>
+__global__ void __launch_bounds__(256)
+bisil_member_mean_kernel(const double* __restrict__ sil, int n, int m, int k, const int* __restrict__ cnt,
+                         unsigned long long active, BisilOffsets off, const int* __restrict__ lists,
+                         double* __restrict__ vals, double* __restrict__ means) {
+  const int j = blockIdx.x, sd = blockIdx.y;
+  if (!((active >> j) & 1ull)) return;
+  const int c = cnt[sd * k + j], n_pts = sd == 0 ? n : m;
+  const double* __restrict__ s = sil + (sd == 0 ? (size_t)0 : (size_t)n * k) + (size_t)j * n_pts;
+  const int* __restrict__ pts = lists + off.feat[1 - sd][j];
+  double* v = vals + off.val[sd][j];
+  for (int i = threadIdx.x; i < c; i += 256) v[i] = s[pts[i]];
+  __syncthreads();
+  if (threadIdx.x == 0) means[sd * RESNMTF_MAX_K + j] = bisil_np_sum(v, c) / (double)c;
+}
+
+template <int UNUSED>
+__global__ void __launch_bounds__(64)
+bisil_score_kernel(const double* __restrict__ means, int k, unsigned long long active, double* __restrict__ score) {
+  __shared__ double sigma[RESNMTF_MAX_K];
+  if (threadIdx.x != 0) return;
+  int n_act = 0;
+  for (int l = 0; l < k; ++l)
+    if ((active >> l) & 1ull) sigma[n_act++] = 0.5 * (means[l] + means[RESNMTF_MAX_K + l]);
+  score[0] = n_act < 2 ? 0.0 : bisil_np_sum(sigma, n_act) / (double)n_act;
+}
+
 }  // namespace

@@ -3904,6 +3904,117 @@ int resnmtf_relevance_masked(resnmtf_handle* h, int v, resnmtf_handle* ref, int 
 
 // ---- bisilhouette (R/obtain_bicl.r:189-199): per-member silhouettes of a view's biclusters (resnmtf_bisil.hip.inc)
 namespace {
+// What resnmtf_bisil / _sparse and resnmtf_bisil_device share: the sizing of a call from its counts (bisil_plan), the
+// checked workspace (bisil_take_workspace) and the launches of every side and bicluster (bisil_enqueue_sides).
+struct BisilPlan {
+  size_t g_floats = 1, part_dbl = 1, upad_max = 64;
+  int chunks[2][RESNMTF_MAX_K] = {}, chunk_tiles[2][RESNMTF_MAX_K] = {};
+  int kq = 1;                             // the per-thread bicluster sums of bisil_dist_kernel
+  size_t g_dbl() const { return (g_floats + 1) / 2; }
+  size_t work_dbl() const { return g_dbl() + upad_max + part_dbl; }      // [G g_floats f32 (rounded to doubles)][norm2][partial]
+};
+// n_u: |U| per side; cnt[sd][j] = the members of bicluster j on side sd (= |mpos_j| for an active j).
+// sizes: G <= max over sides and biclusters of |features| x U_pad floats (<= one padded X image, which a sparse view
+// never held: checked against the device's free memory, bisil_take_workspace); partials of one bicluster
+void bisil_plan(int k, unsigned long long active, const int n_u[2], const int* const cnt[2], BisilPlan& p) {
+  p = BisilPlan();
+  for (int sd = 0; sd < 2; ++sd) {
+    const int upad = round_up(n_u[sd], BISIL_TILE), tiles_u = upad / BISIL_TILE;
+    p.upad_max = std::max<size_t>(p.upad_max, upad);
+    for (int j = 0; j < k; ++j) {
+      if (!((active >> j) & 1ull)) continue;
+      const int n_mem = cnt[sd][j], tiles_m = ceil_div(n_mem, BISIL_TILE);
+      // enough workgroups to fill the device: the others are split into chunks of whole tiles, summed in order later
+      // (tests/test_gpu_bisil_forms.py restates this rule and the kq table below: change them together)
+      const int want = std::max(1, std::min(tiles_u, ceil_div(2048, tiles_m)));
+      p.chunk_tiles[sd][j] = ceil_div(tiles_u, want);
+      p.chunks[sd][j] = ceil_div(tiles_u, p.chunk_tiles[sd][j]);
+      p.g_floats = std::max(p.g_floats, (size_t)cnt[1 - sd][j] * upad);
+      p.part_dbl = std::max(p.part_dbl, (size_t)p.chunks[sd][j] * n_mem * k);
+    }
+  }
+  p.kq = k <= 4 ? 1 : k <= 8 ? 2 : k <= 16 ? 4 : k <= 32 ? 8 : 16;
+}
+
+// `bytes` of transient device memory from `sc`, refused with the sizes when the device has not that much free
+int bisil_take_workspace(resnmtf_handle* h, Scratch& sc, size_t bytes, size_t g_floats, char** buf) {
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
+  if (bytes > free_b)
+    return h->fail(RESNMTF_ERR_ALLOC, "bisil workspace: " + std::to_string(bytes) + " bytes asked for (" + std::to_string(g_floats * sizeof(float)) +
+                   " of them the restricted block, features x padded members), " + std::to_string(free_b) + " free on the device");
+  *buf = sc.take<char>(bytes);
+  if (const hipError_t ea = sc.error(); ea != hipSuccess) {
+    (void)hipGetLastError();
+    return h->fail(ea == hipErrorOutOfMemory ? RESNMTF_ERR_ALLOC : RESNMTF_ERR_HIP,
+                   "bisil workspace: hipMalloc of " + std::to_string(bytes) + " bytes asked for: " + hipGetErrorString(ea));
+  }
+  return RESNMTF_OK;
+}
+
+struct BisilLists {                       // one call's metadata in device memory, per side (and active bicluster)
+  const unsigned long long* umask[2] = {};
+  const int* upts[2] = {};
+  const int* cnt[2] = {};
+  const int* rank[2] = {};                // sparse views only
+  const int* mpos[2][RESNMTF_MAX_K] = {};
+  const int* feat[2][RESNMTF_MAX_K] = {};
+};
+
+// the launches of every side and active bicluster on the handle's stream; work: BisilPlan::work_dbl() doubles; sil:
+// [n k][m k], zeroed by the caller
+hipError_t bisil_enqueue_sides(resnmtf_handle* h, const ViewState& vs, int k, int metric, bool from_sparse, unsigned long long active,
+                               const int n_u_side[2], const int* const cnt[2], const BisilPlan& plan, const BisilLists& d,
+                               char* work, double* sil) {
+  float* G = reinterpret_cast<float*>(work);
+  double* norm2 = reinterpret_cast<double*>(work) + plan.g_dbl();
+  double* partial = norm2 + plan.upad_max;
+  hipError_t e = hipMemsetAsync(norm2, 0, plan.upad_max * sizeof(double), h->stream);
+  for (int sd = 0; sd < 2 && e == hipSuccess; ++sd) {
+    const int n_u = n_u_side[sd], upad = round_up(n_u, BISIL_TILE);
+    const int n_pts = sd == 0 ? vs.n : vs.m;
+    const float* img = vs.side[sd].X;             // rows: X(row, col) = X^T image (col, row); columns: X image (row, col)
+    const size_t ld = vs.side[sd].ldx;
+    double* out = sil + (sd == 0 ? 0 : (size_t)vs.n * k);
+    for (int j = 0; j < k && e == hipSuccess; ++j) {
+      if (!((active >> j) & 1ull)) continue;
+      const int nf = cnt[1 - sd][j], n_mem = cnt[sd][j];
+      const int* feat = d.feat[sd][j];
+      const int* mpos = d.mpos[sd][j];
+      const size_t total = (size_t)nf * upad;
+      if (!from_sparse) {
+        hipLaunchKernelGGL(bisil_gather_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0,
+                           h->stream, (const float*)img, ld, feat, nf, d.upts[sd], n_u, upad, G);
+      } else {      // rows: the features are columns, their entries in the CSC; columns: rows, in the CSR
+        if ((e = hipMemsetAsync(G, 0, total * sizeof(float), h->stream)) != hipSuccess) break;
+        hipLaunchKernelGGL(bisil_scatter_kernel, dim3((unsigned)std::min(ceil_div(nf, BISIL_THREADS / 64), 65536)), dim3(BISIL_THREADS), 0,
+                           h->stream, (const long long*)vs.side[1 - sd].sp_ptr, (const int*)vs.side[1 - sd].sp_idx,
+                           (const float*)vs.side[1 - sd].sp_val, feat, nf, d.rank[sd], upad, G);
+      }
+      if (metric == BISIL_COSINE)
+        hipLaunchKernelGGL(bisil_norm_kernel, dim3(ceil_div(upad, 256)), dim3(256), 0, h->stream, (const float*)G, nf, upad, norm2);
+      const dim3 grid(ceil_div(n_mem, BISIL_TILE), plan.chunks[sd][j]);
+      bisil_launch_dist(metric, plan.kq, grid, h->stream, G, nf, upad, n_u, mpos, n_mem, d.umask[sd], norm2, k, plan.chunk_tiles[sd][j], partial);
+      hipLaunchKernelGGL(bisil_epilogue_kernel, dim3(ceil_div(n_mem, 4)), dim3(256), 0, h->stream, (const double*)partial,
+                         plan.chunks[sd][j], n_mem, k, j, mpos, d.umask[sd], d.upts[sd], d.cnt[sd], active, n_pts, out);
+      e = hipGetLastError();
+    }
+  }
+  return e;
+}
+
+// the refusals of a view's state, shared by the three entries; *from_sparse: asked for (resnmtf_bisil / _sparse) or, with
+// `dispatch`, taken from the view's storage (resnmtf_bisil_device)
+int bisil_check_state(resnmtf_handle* h, const ViewState& vs, bool dispatch, bool* from_sparse) {
+  if (dispatch) *from_sparse = vs.sparse;
+  if (*from_sparse && !vs.sparse) return h->fail(RESNMTF_ERR_STATE, "bisil_sparse of a dense view: use resnmtf_bisil");
+  if (!*from_sparse && vs.sparse) return h->fail(RESNMTF_ERR_STATE, "bisil of a sparse view is not supported (no dense fp32 image)");
+  if (!vs.owned || !vs.has_x) return h->fail(RESNMTF_ERR_STATE, "no data on this handle for the view");
+  if (!*from_sparse && (!vs.side[SIDE_G].X || !vs.side[SIDE_F].X))
+    return h->fail(RESNMTF_ERR_STATE, "bisil needs the view's fp32 images (the view holds only a 2-byte image)");
+  return RESNMTF_OK;
+}
+
 // resnmtf_bisil (from_sparse = false: G gathered from the fp32 images) and resnmtf_bisil_sparse (true: G scattered from
 // the CSC / CSR copies); everything but the view's storage check and the build of G is common
 int bisil_impl(resnmtf_handle* h, int v, int k, const double* row_clusters, const double* col_clusters, int metric,
@@ -3915,11 +4026,7 @@ int bisil_impl(resnmtf_handle* h, int v, int k, const double* row_clusters, cons
   if (metric < BISIL_EUCLIDEAN || metric > BISIL_COSINE)
     return h->fail(RESNMTF_ERR_INVALID, "metric must be 0 (euclidean), 1 (manhattan) or 2 (cosine)");
   const ViewState& vs = h->views[v];
-  if (from_sparse && !vs.sparse) return h->fail(RESNMTF_ERR_STATE, "bisil_sparse of a dense view: use resnmtf_bisil");
-  if (!from_sparse && vs.sparse) return h->fail(RESNMTF_ERR_STATE, "bisil of a sparse view is not supported (no dense fp32 image)");
-  if (!vs.owned || !vs.has_x) return h->fail(RESNMTF_ERR_STATE, "no data on this handle for the view");
-  if (!from_sparse && (!vs.side[SIDE_G].X || !vs.side[SIDE_F].X))
-    return h->fail(RESNMTF_ERR_STATE, "bisil needs the view's fp32 images (the view holds only a 2-byte image)");
+  if (int rc = bisil_check_state(h, vs, false, &from_sparse)) return rc;
   const int n = vs.n, m = vs.m;
   std::vector<unsigned long long> rbits(n, 0ull), cbits(m, 0ull);
   std::vector<int> rcount(k, 0), ccount(k, 0);
@@ -3959,26 +4066,10 @@ int bisil_impl(resnmtf_handle* h, int v, int k, const double* row_clusters, cons
   std::fill(row_sil, row_sil + (size_t)n * k, 0.0);
   std::fill(col_sil, col_sil + (size_t)m * k, 0.0);
   if (!active) return RESNMTF_OK;
-  // sizes: G <= max over sides and biclusters of |features| x U_pad floats (<= one padded X image, which a sparse view
-  // never held: checked against the device's free memory below); partials of one bicluster
-  size_t g_floats = 1, part_dbl = 1, upad_max = 64;
-  int chunks[2][RESNMTF_MAX_K] = {}, chunk_tiles[2][RESNMTF_MAX_K] = {};
-  for (int sd = 0; sd < 2; ++sd) {
-    const BisilSide& s = side[sd];
-    const int upad = round_up((int)s.upts.size(), BISIL_TILE), tiles_u = upad / BISIL_TILE;
-    upad_max = std::max<size_t>(upad_max, upad);
-    for (int j = 0; j < k; ++j) {
-      if (!((active >> j) & 1ull)) continue;
-      const int n_mem = (int)s.mpos[j].size(), tiles_m = ceil_div(n_mem, BISIL_TILE);
-      // enough workgroups to fill the device: the others are split into chunks of whole tiles, summed in order later
-      // (tests/test_gpu_bisil_forms.py restates this rule and the kq table below: change them together)
-      const int want = std::max(1, std::min(tiles_u, ceil_div(2048, tiles_m)));
-      chunk_tiles[sd][j] = ceil_div(tiles_u, want);
-      chunks[sd][j] = ceil_div(tiles_u, chunk_tiles[sd][j]);
-      g_floats = std::max(g_floats, (size_t)side[1 - sd].mpos[j].size() * upad);
-      part_dbl = std::max(part_dbl, (size_t)chunks[sd][j] * n_mem * k);
-    }
-  }
+  const int n_u[2] = {(int)side[0].upts.size(), (int)side[1].upts.size()};
+  const int* const cnt[2] = {rcount.data(), ccount.data()};
+  BisilPlan plan;
+  bisil_plan(k, active, n_u, cnt, plan);
   // host image of the metadata: per side [umask (u64) | upts | cnt | (sparse: rank) | per active j: mpos_j | feat_j];
   // rank[p] = the position of point p in U or -1 (bisil_scatter_kernel)
   std::vector<unsigned long long> meta;
@@ -4015,63 +4106,25 @@ int bisil_impl(resnmtf_handle* h, int v, int k, const double* row_clusters, cons
   }
   HIP_TRY(h, hipSetDevice(h->opt.device_id));
   if (int rc = sync_both(h)) return rc;
-  // [G g_floats f32 (rounded to doubles)][norm2 upad_max][partial part_dbl][sil n k + m k] doubles | meta
-  const size_t g_dbl = (g_floats + 1) / 2, sil_dbl = (size_t)n * k + (size_t)m * k;
-  const size_t n_dbl = g_dbl + upad_max + part_dbl + sil_dbl;
-  const size_t bytes = n_dbl * sizeof(double) + meta.size() * sizeof(unsigned long long);
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
-  if (bytes > free_b)
-    return h->fail(RESNMTF_ERR_ALLOC, "bisil workspace: " + std::to_string(bytes) + " bytes asked for (" + std::to_string(g_floats * sizeof(float)) +
-                   " of them the restricted block, features x padded members), " + std::to_string(free_b) + " free on the device");
+  // [G | norm2 | partial (BisilPlan::work_dbl)][sil n k + m k] doubles | meta
+  const size_t sil_dbl = (size_t)n * k + (size_t)m * k;
+  const size_t bytes = (plan.work_dbl() + sil_dbl) * sizeof(double) + meta.size() * sizeof(unsigned long long);
   Scratch sc;
-  char* buf = sc.take<char>(bytes);
-  if (const hipError_t ea = sc.error(); ea != hipSuccess) {
-    (void)hipGetLastError();
-    return h->fail(ea == hipErrorOutOfMemory ? RESNMTF_ERR_ALLOC : RESNMTF_ERR_HIP,
-                   "bisil workspace: hipMalloc of " + std::to_string(bytes) + " bytes asked for: " + hipGetErrorString(ea));
-  }
-  float* G = reinterpret_cast<float*>(buf);
-  double* norm2 = reinterpret_cast<double*>(buf) + g_dbl;
-  double* partial = norm2 + upad_max;
-  double* sil = partial + part_dbl;
+  char* buf = nullptr;
+  if (int rc = bisil_take_workspace(h, sc, bytes, plan.g_floats, &buf)) return rc;
+  double* sil = reinterpret_cast<double*>(buf) + plan.work_dbl();
   unsigned long long* dmeta = reinterpret_cast<unsigned long long*>(sil + sil_dbl);
   const int* dints = reinterpret_cast<const int*>(dmeta);
+  BisilLists d;
+  for (int sd = 0; sd < 2; ++sd) {
+    d.umask[sd] = dmeta + off_mask[sd]; d.upts[sd] = dints + off_pts[sd]; d.cnt[sd] = dints + off_cnt[sd];
+    d.rank[sd] = from_sparse ? dints + off_rank[sd] : nullptr;
+    for (int j = 0; j < k; ++j)
+      if ((active >> j) & 1ull) { d.mpos[sd][j] = dints + off_mpos[sd][j]; d.feat[sd][j] = dints + off_feat[sd][j]; }
+  }
   hipError_t e = hipMemcpyAsync(dmeta, meta.data(), meta.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) e = hipMemsetAsync(sil, 0, sil_dbl * sizeof(double), h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(norm2, 0, upad_max * sizeof(double), h->stream);
-  const int kq = k <= 4 ? 1 : k <= 8 ? 2 : k <= 16 ? 4 : k <= 32 ? 8 : 16;
-  for (int sd = 0; sd < 2 && e == hipSuccess; ++sd) {
-    const BisilSide& s = side[sd];
-    const int n_u = (int)s.upts.size(), upad = round_up(n_u, BISIL_TILE);
-    const float* img = vs.side[sd].X;             // rows: X(row, col) = X^T image (col, row); columns: X image (row, col)
-    const size_t ld = vs.side[sd].ldx;
-    double* out = sil + (sd == 0 ? 0 : (size_t)n * k);
-    for (int j = 0; j < k && e == hipSuccess; ++j) {
-      if (!((active >> j) & 1ull)) continue;
-      const int nf = (int)side[1 - sd].mpos[j].size(), n_mem = (int)s.mpos[j].size();
-      const int* feat = dints + off_feat[sd][j];
-      const int* mpos = dints + off_mpos[sd][j];
-      const size_t total = (size_t)nf * upad;
-      if (!from_sparse) {
-        hipLaunchKernelGGL(bisil_gather_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0,
-                           h->stream, (const float*)img, ld, feat, nf, dints + off_pts[sd], n_u, upad, G);
-      } else {      // rows: the features are columns, their entries in the CSC; columns: rows, in the CSR
-        if ((e = hipMemsetAsync(G, 0, total * sizeof(float), h->stream)) != hipSuccess) break;
-        hipLaunchKernelGGL(bisil_scatter_kernel, dim3((unsigned)std::min(ceil_div(nf, BISIL_THREADS / 64), 65536)), dim3(BISIL_THREADS), 0,
-                           h->stream, (const long long*)vs.side[1 - sd].sp_ptr, (const int*)vs.side[1 - sd].sp_idx,
-                           (const float*)vs.side[1 - sd].sp_val, feat, nf, dints + off_rank[sd], upad, G);
-      }
-      if (metric == BISIL_COSINE)
-        hipLaunchKernelGGL(bisil_norm_kernel, dim3(ceil_div(upad, 256)), dim3(256), 0, h->stream, (const float*)G, nf, upad, norm2);
-      const dim3 grid(ceil_div(n_mem, BISIL_TILE), chunks[sd][j]);
-      const unsigned long long* umask = dmeta + off_mask[sd];
-      bisil_launch_dist(metric, kq, grid, h->stream, G, nf, upad, n_u, mpos, n_mem, umask, norm2, k, chunk_tiles[sd][j], partial);
-      hipLaunchKernelGGL(bisil_epilogue_kernel, dim3(ceil_div(n_mem, 4)), dim3(256), 0, h->stream, (const double*)partial,
-                         chunks[sd][j], n_mem, k, j, mpos, umask, dints + off_pts[sd], dints + off_cnt[sd], active, s.n_pts, out);
-      e = hipGetLastError();
-    }
-  }
+  if (e == hipSuccess) e = bisil_enqueue_sides(h, vs, k, metric, from_sparse, active, n_u, cnt, plan, d, buf, sil);
   if (e == hipSuccess) e = hipMemcpyAsync(row_sil, sil, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(col_sil, sil + (size_t)n * k, (size_t)m * k * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -4088,6 +4141,143 @@ int resnmtf_bisil(resnmtf_handle* h, int v, int k, const double* row_clusters, c
 int resnmtf_bisil_sparse(resnmtf_handle* h, int v, int k, const double* row_clusters, const double* col_clusters, int metric,
                          double* row_sil, double* col_sil) {
   return bisil_impl(h, v, k, row_clusters, col_clusters, metric, row_sil, col_sil, true);
+}
+
+// The same from 0 / 1 matrices that are ALREADY in device memory, with the silhouettes left there and the view's score
+// combined there (resnmtf_bisil.hip.inc).  Dense and sparse views alike: G is gathered or scattered
+// as the view is stored.  The lists bisil_impl builds on the host are built by kernels, in its order, so the silhouettes
+// are its bits; the host reads back 2 k + 3 ints -- the refusal bits, |U| of both sides and the 2 k member counts -- to
+// size the grids and the workspace (bisil_plan), and at the end the score.
+// Transient device memory, beyond the workspace of resnmtf_bisil: the two u64 arrays (membership words, umask) and the
+// int arrays upts and (sparse) rank over n + m points, the lists mpos_j and feat_j and the gathered member silhouettes
+// over sum |I_j| + sum |J_j| entries: O(n + m + sum |I_j| + sum |J_j|).
+int resnmtf_bisil_device(resnmtf_handle* h, int v, int k, const resnmtf_device_matrix* row_clusters,
+                         const resnmtf_device_matrix* col_clusters, int metric, double* row_sil, double* col_sil,
+                         double* view_score, void* stream) {
+  if (int rc = check_view(h, v)) return rc;
+  if (!row_clusters || !col_clusters || !row_clusters->ptr || !col_clusters->ptr || !view_score)
+    return h->fail(RESNMTF_ERR_INVALID, "row_clusters / col_clusters / view_score are NULL");
+  if (k < 1 || k > RESNMTF_MAX_K) return h->fail(RESNMTF_ERR_INVALID, "k must be in [1, 64]");
+  if (metric < BISIL_EUCLIDEAN || metric > BISIL_COSINE)
+    return h->fail(RESNMTF_ERR_INVALID, "metric must be 0 (euclidean), 1 (manhattan) or 2 (cosine)");
+  for (const resnmtf_device_matrix* a : {row_clusters, col_clusters}) {
+    if (a->dtype != RESNMTF_DTYPE_F64 && a->dtype != RESNMTF_DTYPE_F32 && a->dtype != RESNMTF_DTYPE_F16 && a->dtype != RESNMTF_DTYPE_BF16)
+      return h->fail(RESNMTF_ERR_INVALID, "unknown dtype: one of RESNMTF_DTYPE_F64 / _F32 / _F16 / _BF16");
+    if (a->row_stride < 0 || a->col_stride < 0) return h->fail(RESNMTF_ERR_INVALID, "negative strides are not supported");
+  }
+  for (const resnmtf_device_matrix* a : {row_clusters, col_clusters})
+    if (!on_handle_device(h, a->ptr))
+      return h->fail(RESNMTF_ERR_INVALID, "a cluster matrix is not device memory of the handle's device (host matrices: resnmtf_bisil)");
+  for (const double* p : {row_sil, col_sil})
+    if (p && !on_handle_device(h, p))
+      return h->fail(RESNMTF_ERR_INVALID, "row_sil / col_sil are not device memory of the handle's device (host buffers: resnmtf_bisil)");
+  const ViewState& vs = h->views[v];
+  bool from_sparse = false;
+  if (int rc = bisil_check_state(h, vs, true, &from_sparse)) return rc;
+  const int n = vs.n, m = vs.m;
+  const size_t pts = (size_t)n + m, sil_dbl = (size_t)n * k + (size_t)m * k;
+  const int n_hdr = BISIL_HDR_COUNTS + 2 * k;
+  HIP_TRY(h, hipSetDevice(h->opt.device_id));
+  if (int rc = sync_both(h)) return rc;
+  Scratch sc;                             // (dies after the last synchronisation below)
+  // [words n + m][umask n + m] u64 | [upts n + m][(sparse) rank n + m][hdr] ints
+  const size_t pre_ints = pts * (from_sparse ? 2 : 1) + n_hdr;
+  char* pre = sc.take<char>(2 * pts * sizeof(unsigned long long) + pre_ints * sizeof(int));
+  if (!pre) return h->fail_hip("hipMalloc bisil_device metadata", sc.error());
+  unsigned long long *words = reinterpret_cast<unsigned long long*>(pre), *umask = words + pts;
+  int* upts = reinterpret_cast<int*>(umask + pts);
+  int* rank = from_sparse ? upts + pts : nullptr;
+  int* hdr = upts + pts * (from_sparse ? 2 : 1);
+  std::vector<int> hdr_host(n_hdr, 0);
+  hipError_t e = wait_for_caller(h, stream);
+  if (e == hipSuccess) e = hipMemsetAsync(hdr, 0, (size_t)n_hdr * sizeof(int), h->stream);
+  if (e == hipSuccess) {
+    auto pack = [&](const resnmtf_device_matrix* a, int len, int bad_bit, unsigned long long* w, int* count) {
+      pick_int<RESNMTF_DTYPE_F64, RESNMTF_DTYPE_F32, RESNMTF_DTYPE_F16, RESNMTF_DTYPE_BF16>(a->dtype, [&](auto dt) {
+        pick_bools([&](auto along_r) {
+          hipLaunchKernelGGL((bisil_words_kernel<decltype(dt)::value, decltype(along_r)::value>), dim3((unsigned)ceil_div(len, 256)), dim3(256), 0,
+                             h->stream, a->ptr, a->row_stride, a->col_stride, len, k, bad_bit, w, count, hdr);
+        }, a->row_stride < a->col_stride);
+      });
+    };
+    pack(row_clusters, n, 1, words, hdr + BISIL_HDR_COUNTS);
+    pack(col_clusters, m, 2, words + n, hdr + BISIL_HDR_COUNTS + k);
+    const BisilSideMeta sr = {words, n, umask, upts, rank}, scl = {words + n, m, umask + n, upts + n, rank ? rank + n : nullptr};
+    hipLaunchKernelGGL(bisil_union_kernel<0>, dim3(2), dim3(BISIL_SCAN_THREADS), 0, h->stream, sr, scl, k, hdr);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(hdr_host.data(), hdr, (size_t)n_hdr * sizeof(int), hipMemcpyDeviceToHost, h->stream);
+  {
+    const hipError_t es = hipStreamSynchronize(h->stream);   // the one read-back
+    if (e == hipSuccess) e = es;
+  }
+  if (e != hipSuccess) return h->fail_hip("bisil_device (metadata)", e);
+  if (hdr_host[0])
+    return h->fail(RESNMTF_ERR_INVALID, (hdr_host[0] & 1) ? "row_clusters entries must be 0 or 1" : "col_clusters entries must be 0 or 1");
+  const int n_u[2] = {hdr_host[1], hdr_host[2]};
+  const int* const cnt[2] = {hdr_host.data() + BISIL_HDR_COUNTS, hdr_host.data() + BISIL_HDR_COUNTS + k};
+  unsigned long long active = 0ull;                            // biclusters with rows and columns
+  for (int j = 0; j < k; ++j) if (cnt[0][j] > 0 && cnt[1][j] > 0) active |= 1ull << j;
+  if (!active) {
+    if (row_sil) e = hipMemsetAsync(row_sil, 0, (size_t)n * k * sizeof(double), h->stream);
+    if (e == hipSuccess && col_sil) e = hipMemsetAsync(col_sil, 0, (size_t)m * k * sizeof(double), h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return h->fail_hip("bisil_device", e);
+    *view_score = 0.0;
+    return RESNMTF_OK;
+  }
+  BisilPlan plan;
+  bisil_plan(k, active, n_u, cnt, plan);
+  // the lists of every active bicluster: per side mpos_j then feat_j (ints), and the members' silhouettes (doubles)
+  BisilOffsets off = {};
+  size_t n_ints = 0, n_vals = 0;
+  for (int sd = 0; sd < 2; ++sd)
+    for (int j = 0; j < k; ++j) {
+      if (!((active >> j) & 1ull)) continue;
+      off.mpos[sd][j] = (int)n_ints; n_ints += cnt[sd][j];
+      off.feat[sd][j] = (int)n_ints; n_ints += cnt[1 - sd][j];
+      off.val[sd][j] = (int)n_vals; n_vals += cnt[sd][j];
+    }
+  if (n_ints > 2147483647u) return h->fail(RESNMTF_ERR_INVALID, "the member lists exceed 2^31 - 1 entries");
+  // [G | norm2 | partial (BisilPlan::work_dbl)][sil n k + m k][vals][means 2 x 64][score] doubles | [lists] ints
+  const size_t n_dbl = plan.work_dbl() + sil_dbl + n_vals + 2 * RESNMTF_MAX_K + 1;
+  const size_t bytes = n_dbl * sizeof(double) + n_ints * sizeof(int);
+  char* buf = nullptr;
+  if (int rc = bisil_take_workspace(h, sc, bytes, plan.g_floats, &buf)) return rc;
+  double* sil = reinterpret_cast<double*>(buf) + plan.work_dbl();
+  double *vals = sil + sil_dbl, *means = vals + n_vals, *score = means + 2 * RESNMTF_MAX_K;
+  int* lists = reinterpret_cast<int*>(score + 1);
+  BisilLists d;
+  for (int sd = 0; sd < 2; ++sd) {
+    d.umask[sd] = umask + (sd ? n : 0); d.upts[sd] = upts + (sd ? n : 0); d.cnt[sd] = hdr + BISIL_HDR_COUNTS + sd * k;
+    d.rank[sd] = rank ? rank + (sd ? n : 0) : nullptr;
+    for (int j = 0; j < k; ++j)
+      if ((active >> j) & 1ull) { d.mpos[sd][j] = lists + off.mpos[sd][j]; d.feat[sd][j] = lists + off.feat[sd][j]; }
+  }
+  e = hipMemsetAsync(sil, 0, sil_dbl * sizeof(double), h->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(bisil_members_kernel<0>, dim3(k, 2), dim3(BISIL_SCAN_THREADS), 0, h->stream, d.umask[0], d.upts[0], n_u[0],
+                       d.umask[1], d.upts[1], n_u[1], active, off, lists);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = bisil_enqueue_sides(h, vs, k, metric, from_sparse, active, n_u, cnt, plan, d, buf, sil);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(bisil_member_mean_kernel<0>, dim3(k, 2), dim3(256), 0, h->stream, (const double*)sil, n, m, k,
+                       (const int*)(hdr + BISIL_HDR_COUNTS), active, off, (const int*)lists, vals, means);
+    hipLaunchKernelGGL(bisil_score_kernel<0>, dim3(1), dim3(64), 0, h->stream, (const double*)means, k, active, score);
+    e = hipGetLastError();
+  }
+  double score_host = 0.0;
+  if (e == hipSuccess && row_sil) e = hipMemcpyAsync(row_sil, sil, (size_t)n * k * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+  if (e == hipSuccess && col_sil) e = hipMemcpyAsync(col_sil, sil + (size_t)n * k, (size_t)m * k * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(&score_host, score, sizeof(double), hipMemcpyDeviceToHost, h->stream);
+  {
+    const hipError_t es = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = es;
+  }
+  if (e != hipSuccess) return h->fail_hip("bisil_device", e);
+  *view_score = score_host;
+  return RESNMTF_OK;
 }
 
 namespace {

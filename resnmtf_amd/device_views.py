@@ -253,6 +253,41 @@ def on_engine_device(x, device_id: int = 0) -> bool:
     return is_tensor(x) and x.device.type == "cuda" and x.device.index == int(device_id)
 
 
+CLUSTER_DTYPES = ("torch.float64", "torch.float32", "torch.float16", "torch.bfloat16")
+
+
+def check_cluster_tensors(rc, cc, n: int, m: int, device_id: int = 0, what: str = "bisil_device"):
+    """The refusals of a view's two cluster matrices in device memory that need no device (``Engine.bisil_device``):
+    both ``torch`` tensors (``TypeError`` otherwise), fp64 / fp32 / fp16 / bf16, on ``cuda:device_id``, ``rc`` n x k and
+    ``cc`` m x k with one k (``ValueError``).  Returns ``(rc, cc, k)``, the tensors detached."""
+    for t, name in ((rc, "rc"), (cc, "cc")):
+        if not is_tensor(t):
+            raise TypeError(f"{what} takes torch.Tensors, {name} is a {type(t).__name__} (host matrices: bisil)")
+        if str(t.dtype) not in CLUSTER_DTYPES:
+            raise ValueError(f"{what}: {name} must be fp64, fp32, fp16 or bf16, got {t.dtype}")
+        if not on_engine_device(t, device_id):
+            raise ValueError(f"{what}: {name} lives on {t.device}, the engine on cuda:{int(device_id)}")
+    if rc.ndim != 2 or rc.shape[0] != int(n):
+        raise ValueError(f"{what}: row clusters must be {int(n)} x k, got {tuple(rc.shape)}")
+    if cc.ndim != 2 or tuple(cc.shape) != (int(m), rc.shape[1]):
+        raise ValueError(f"{what}: expected column clusters of shape {(int(m), rc.shape[1])}, got {tuple(cc.shape)}")
+    return rc.detach(), cc.detach(), int(rc.shape[1])
+
+
+def cluster_route(rc, cc, device_id: int = 0, what: str = "view", on_device=None) -> bool:
+    """Which route one view's cluster matrices take to the bisilhouette: True = the device route
+    (``Engine.bisil_device``: both are tensors on ``cuda:device_id``), False = the host route (neither is).  One of each
+    is a ``ValueError`` naming ``what``.  Pure: ``on_device`` decides what a tensor on the engine's device is."""
+    on_device = on_device or (lambda x: on_engine_device(x, device_id))
+    flags = [bool(on_device(x)) for x in (rc, cc)]
+    if all(flags):
+        return True
+    if any(flags):
+        where = ", ".join(f"{name} on the {'device' if flag else 'host'}" for name, flag in zip(("row_clusters", "col_clusters"), flags))
+        raise ValueError(f"{what}: the cluster matrices mix a device tensor and a host matrix ({where}); give both in one place")
+    return False
+
+
 def check_readback_strides(shape, strides, what: str = "out"):
     """The layout ``Engine.get_view_device`` may write to (``resnmtf_get_view_device``): ``shape`` =
     (n, m), ``strides`` = (row stride, column stride) in ELEMENTS.  A stride along an extent above 1 must be positive,

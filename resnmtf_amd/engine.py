@@ -763,6 +763,47 @@ class Engine:
         dense view is refused (use ``bisil``)."""
         return self._bisil(self._lib.resnmtf_bisil_sparse, v, rc, cc, distance)
 
+    def bisil_device(self, v: int, rc, cc, distance: str = "euclidean", *, silhouettes: bool = True, out=None):
+        """``bisil`` / ``bisil_sparse`` from device memory, and the view's score with them (``resnmtf_bisil_device``):
+        ``rc`` (n x k) and ``cc`` (m x k) are 2-D floating ``torch`` tensors (fp64 / fp32 / fp16 / bf16, any strides) of
+        0 / 1 on this engine's GPU -- ``finalise_device``'s cluster matrices as they come --, read in place, ordered after
+        the work enqueued on torch's current stream of that device and checked on the device (an entry other than 0 or 1
+        raises ``ResnmtfError``).  A dense view and a sparse one alike.  Returns ``(row_sil, col_sil, score)``: the
+        silhouettes as fp64 column-major tensors on that GPU, bitwise what ``bisil`` / ``bisil_sparse`` return, and
+        ``score == bisil.view_score(rc, cc, row_sil, col_sil)``, combined on the device.  ``silhouettes=False``: only
+        the score; ``row_sil`` and ``col_sil`` are ``None``.  ``out=(row_sil, col_sil)``: two fp64 column-major tensors
+        of the cluster matrices' shapes on this GPU to write into (a refusal leaves them untouched)."""
+        import torch            # (lazily: nothing else in this module needs it)
+        from . import device_views
+        from .bisil import METRICS
+        if distance not in METRICS:
+            raise ValueError("distance must be one of 'euclidean', 'manhattan' or 'cosine'.")
+        n, m = self.n_rows[v], self.n_cols[v]
+        rc, cc, k = device_views.check_cluster_tensors(rc, cc, n, m, self.device_id, "bisil_device")
+        codes = {torch.float64: _lib.DTYPE_F64, torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16,
+                 torch.bfloat16: _lib.DTYPE_BF16}
+        dev = torch.device("cuda", self.device_id)
+        rs = cs = None
+        if out is not None:
+            if not silhouettes:
+                raise ValueError("out= needs silhouettes=True")
+            rs, cs = out
+            for t, shape, name in ((rs, (n, k), "out[0]"), (cs, (m, k), "out[1]")):
+                if not device_views.on_engine_device(t, self.device_id) or t.dtype != torch.float64:
+                    raise ValueError(f"bisil_device: {name} must be an fp64 tensor on cuda:{self.device_id}")
+                if tuple(t.shape) != shape or (k > 0 and (t.stride(0) != 1 or (k > 1 and t.stride(1) != shape[0]))):
+                    raise ValueError(f"bisil_device: {name} must be a column-major {shape} tensor")
+        elif silhouettes:
+            rs, cs = (torch.empty((k, rows), dtype=torch.float64, device=dev).T for rows in (n, m))
+        descs = [_lib.DeviceMatrix(t.data_ptr(), codes[t.dtype], int(t.stride(0)), int(t.stride(1))) for t in (rc, cc)]
+        score = C.c_double(0.0)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        self._check(self._lib.resnmtf_bisil_device(
+            self._h, v, k, C.byref(descs[0]), C.byref(descs[1]), METRICS[distance],
+            *(None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr()) for t in (rs, cs)),
+            C.byref(score), C.c_void_p(stream)))
+        return rs, cs, float(score.value)
+
     def _bisil(self, entry, v: int, rc, cc, distance: str):
         from .bisil import METRICS
         if distance not in METRICS:

@@ -24,7 +24,7 @@ from typing import Callable, Optional
 
 import numpy as np
 
-from . import sparse
+from . import device_views, sparse
 from .engine import jsd_pairs
 from .problem import shuffled_engines
 
@@ -275,6 +275,29 @@ def apply_removal(results: dict, check: dict) -> dict:
         new = indices[relations]
         out["row_clusters"][i][:, new] = 0.0
         out["col_clusters"][i][:, new] = 0.0
+        removed.append(new)
+    out["spurious"] = dict(copy.deepcopy(check), removed=np.array(removed, dtype=bool))
+    return out
+
+
+def apply_removal_device(results: dict, check: dict) -> dict:
+    """``apply_removal`` for cluster matrices that are ``torch`` tensors (``post_on_device``): the
+    same ``removed`` mask -- ``relations`` from the k x k S, copied to the host when it is a tensor --, the flagged
+    columns zeroed in clones of the cluster tensors where they live; nothing of size n or m is copied to the host and
+    the inputs are not written.  ``"spurious"`` is the entry ``apply_removal`` returns."""
+    out = dict(results)
+    out["row_clusters"], out["col_clusters"], removed = [], [], []
+    for i, (rc, cc) in enumerate(zip(results["row_clusters"], results["col_clusters"])):
+        relations = np.argmax(np.asarray(device_views.to_numpy(results["output_s"][i])), axis=0)   # apply(S, 2, which.max)
+        indices = (check["score"][i] < check["max_threshold"][i]) | (check["score"][i] == 0)
+        new = indices[relations]
+        rc, cc = rc.clone(), cc.clone()
+        cols = np.flatnonzero(new)
+        if cols.size:
+            for t in (rc, cc):
+                t[:, t.new_tensor(cols, dtype=device_views._torch().long)] = 0.0
+        out["row_clusters"].append(rc)
+        out["col_clusters"].append(cc)
         removed.append(new)
     out["spurious"] = dict(copy.deepcopy(check), removed=np.array(removed, dtype=bool))
     return out
