@@ -885,6 +885,39 @@ typedef struct resnmtf_view_plan_info {
 } resnmtf_view_plan_info;
 int resnmtf_view_plan(resnmtf_handle* h, int v, resnmtf_view_plan_info* out);
 
+/* The update side of view v's sweep: which factor_update_kernel<KP, IS_G, NCB, EMIT> instantiation its F and G updates
+ * launch and which slab-prefetch depth that instantiation takes at run time, read from the argument blocks of the latest
+ * resnmtf_prepare (the ones the launches copy).  Index [0] = the F update, [1] = the G update.  Host only, read-only: no
+ * device work, nothing is changed.  Before the first prepare (prepared = 0) the coupling fields (restricted, n_couple,
+ * couple_bucket, the map counts, sigma_is_zero, route and the S fields) read 0; the geometry is valid from resnmtf_create on.
+ * Refused (RESNMTF_ERR_INVALID): h or out NULL, a bad view, out->struct_size != sizeof(resnmtf_update_plan_info). */
+typedef struct resnmtf_update_plan_info {
+  int struct_size;         /* = sizeof(resnmtf_update_plan_info), set by the caller */
+  int prepared;            /* the coupling fields below are those of the latest prepare */
+  int k, kp;               /* k and padded k: the KP of the instantiation */
+  int threads;             /* threads per update workgroup */
+  int rows_per_group;      /* factor rows a workgroup processes per trip (threads / kp) */
+  int emit;                /* 1: the update emits its own fp64 Gram partials (hand-off mode A), 0: mode B */
+  int mm64;                /* num and den of a row group on the fp64 MFMA (kp 16, 32, 64), 0: the scalar loop (kp 48) */
+  int packk;               /* the bf16 pieces of a row group staged through LDS (kp 32 / 64 without emit) */
+  int restricted[2];       /* 1: the coupled formula (no NaN -> 1 guard), 0: the unrestricted form */
+  int n_couple[2];         /* coupled views in the numerator: weight != 0, not the view itself, pair not NA */
+  int couple_bucket[2];    /* NCB of the instantiation: 0 (unrestricted), 4, 8 or 16 */
+  int n_identity_maps[2];  /* of the n_couple views: reached without a map (same names in the same order) ... */
+  int n_index_maps[2];     /* ... and through an integer row map */
+  int sigma_is_zero[2];    /* the view's own column of phi / psi sums to zero */
+  int nsplit[2];           /* slabs of the producing pass the update sums */
+  int split_bucket[2];     /* the prefetch depth PF it takes for them: 4, 8 or 16 */
+  int rows_per_block[2];   /* factor rows per workgroup (a multiple of rows_per_group) */
+  int nblk[2];             /* workgroups of the launch */
+  int last_block_rows[2];  /* rows of the last workgroup */
+  int route[2];            /* how resnmtf_run's sweep runs this update: 0 = a factor_update_kernel launch, 1 = in the first
+                            * workgroups of the pass that consumes it (fuse_updates), 2 = the hoisted f_chain_kernel launch */
+  int s_restricted;        /* update_s takes the coupled formula (sum(xi) != 0) */
+  int s_n_couple;          /* xi-coupled views in its numerator */
+} resnmtf_update_plan_info;
+int resnmtf_update_plan(resnmtf_handle* h, int v, resnmtf_update_plan_info* out);
+
 /* Size the per-sweep error buffer for `sweeps` sweeps (phase mode; resnmtf_run sizes it itself).
  * Must precede resnmtf_prepare. */
 int resnmtf_reserve_sweeps(resnmtf_handle* h, int sweeps);

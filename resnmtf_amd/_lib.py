@@ -71,6 +71,18 @@ class ViewPlan(C.Structure):
     ]
 
 
+class UpdatePlan(C.Structure):
+    """``resnmtf_update_plan_info`` (include/resnmtf_hip.h): [0] = the F update, [1] = the G update."""
+    _fields_ = [
+        ("struct_size", C.c_int), ("prepared", C.c_int), ("k", C.c_int), ("kp", C.c_int), ("threads", C.c_int),
+        ("rows_per_group", C.c_int), ("emit", C.c_int), ("mm64", C.c_int), ("packk", C.c_int),
+        ("restricted", C.c_int * 2), ("n_couple", C.c_int * 2), ("couple_bucket", C.c_int * 2),
+        ("n_identity_maps", C.c_int * 2), ("n_index_maps", C.c_int * 2), ("sigma_is_zero", C.c_int * 2),
+        ("nsplit", C.c_int * 2), ("split_bucket", C.c_int * 2), ("rows_per_block", C.c_int * 2), ("nblk", C.c_int * 2),
+        ("last_block_rows", C.c_int * 2), ("route", C.c_int * 2), ("s_restricted", C.c_int), ("s_n_couple", C.c_int),
+    ]
+
+
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 _h = C.c_void_p
@@ -164,6 +176,7 @@ SIGNATURES = {
     "resnmtf_pass_timings": (C.c_int, [_h, C.POINTER(PassTiming), C.c_int]),
     "resnmtf_view_image_info": (C.c_int, [_h, C.c_int, _ip, _dp]),
     "resnmtf_view_plan": (C.c_int, [_h, C.c_int, C.POINTER(ViewPlan)]),
+    "resnmtf_update_plan": (C.c_int, [_h, C.c_int, C.POINTER(UpdatePlan)]),
     "resnmtf_kernel_timings": (C.c_int, [_h, _dp, C.POINTER(C.c_longlong), C.c_int]),
     "resnmtf_set_stop_tolerance": (C.c_int, [_h, C.c_double]),
     "resnmtf_loop_state": (C.c_int, [_h, _ip, _ip, _ip]),

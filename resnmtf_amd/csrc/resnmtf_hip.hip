@@ -5020,6 +5020,46 @@ int resnmtf_view_plan(resnmtf_handle* h, int v, resnmtf_view_plan_info* out) {
   return RESNMTF_OK;
 }
 
+// the update side of view v: the template arguments launch_update hands select_update and the run-time buckets of
+// factor_update_body, each read where the launch reads it (couple_bucket, update_threads, the UpdateArgs / KKSArgs that
+// build_args filled, Side::rpb / nblk)
+int resnmtf_update_plan(resnmtf_handle* h, int v, resnmtf_update_plan_info* out) {
+  if (!h) return RESNMTF_ERR_INVALID;
+  if (!out) return h->fail(RESNMTF_ERR_INVALID, "out is NULL");
+  if (out->struct_size != (int)sizeof(resnmtf_update_plan_info)) return h->fail(RESNMTF_ERR_INVALID, "update plan struct_size mismatch");
+  if (int rc = check_view(h, v)) return rc;
+  const ViewState& vs = h->views[v];
+  resnmtf_update_plan_info p;
+  std::memset(&p, 0, sizeof(p));
+  p.struct_size = (int)sizeof(p);
+  p.prepared = h->prepared ? 1 : 0;
+  p.k = vs.k; p.kp = vs.KP;
+  p.threads = update_threads(vs.KP);
+  p.rows_per_group = p.threads / vs.KP;
+  p.emit = vs.kk_mode == 0 ? 1 : 0;
+  p.mm64 = update_mm64(vs.KP) ? 1 : 0;
+  p.packk = update_packk(vs.KP, p.emit != 0) ? 1 : 0;
+  const bool hoist = h->prepared && plan_f_chain(h).hoisted;
+  for (int s = 0; s < 2; ++s) {
+    const Side& sd = vs.side[s];
+    const UpdateArgs& u = sd.arg;
+    // (before the first prepare the argument block is empty: the slabs are then those fill_update will copy from the side)
+    p.nsplit[s] = h->prepared ? u.nsplit : (sd.xsum ? 1 : sd.nsplit);
+    p.split_bucket[s] = update_split_bucket(p.nsplit[s]);
+    p.rows_per_block[s] = sd.rpb; p.nblk[s] = sd.nblk;
+    p.last_block_rows[s] = sd.len - (sd.nblk - 1) * sd.rpb;
+    if (!h->prepared) continue;
+    p.restricted[s] = u.restricted; p.n_couple[s] = u.n_couple;
+    p.couple_bucket[s] = couple_bucket(u);
+    for (int c = 0; c < u.n_couple; ++c) ++(u.couple[c].map ? p.n_index_maps : p.n_identity_maps)[s];
+    p.sigma_is_zero[s] = u.sigma == 0.0 ? 1 : 0;
+    p.route[s] = (s == SIDE_F && hoist) ? 2 : (can_fuse_update(h, vs, s) ? 1 : 0);
+  }
+  if (h->prepared) { p.s_restricted = vs.argKS.restricted; p.s_n_couple = vs.argKS.n_couple; }
+  *out = p;
+  return RESNMTF_OK;
+}
+
 int resnmtf_pass_timings(resnmtf_handle* h, resnmtf_pass_timing* out, int reset) {
   if (!h || !out) return RESNMTF_ERR_INVALID;
   HIP_TRY(h, hipSetDevice(h->opt.device_id));

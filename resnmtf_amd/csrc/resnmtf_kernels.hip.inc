@@ -1143,6 +1143,14 @@ struct UpdateArgs {
 #define RESNMTF_UPD16_THREADS UPDATE_THREADS
 #endif
 constexpr int update_threads(int KP) { return KP >= 48 ? 1024 : (KP == 16 ? RESNMTF_UPD16_THREADS : UPDATE_THREADS); }
+// the two body forms that follow from KP (and EMIT) alone, for resnmtf_update_plan; factor_update_body asserts that they are its own
+constexpr bool update_mm64(int KP) {       // num and den of a row group on the fp64 MFMA: whole 16-row tiles, one wave per output tile
+  return (KP == 16 || KP == 32 || KP == 64) && (update_threads(KP) / KP) % 16 == 0 &&
+         (update_threads(KP) / KP / 16) * 2 * (KP / 16) <= update_threads(KP) / 64;
+}
+constexpr bool update_packk(int KP, bool emit) { return (KP == 32 || KP == 64) && !emit && update_threads(KP) / KP == 16; }
+// the slab-prefetch depth PF of a launch: the bucket of its number of splits, as the end of factor_update_body dispatches it
+constexpr int update_split_bucket(int nsplit) { return nsplit <= 4 ? 4 : nsplit <= 8 ? 8 : 16; }
 // NCB: coupling-count bucket -- 0 = the unrestricted form (NaN -> 1 branch), else the restricted form with
 // room for NCB coupled views in registers (4 keeps the gathered rows within the register budget)
 // (the body is a device function: factor_update_kernel runs it per workgroup, pass_fused_kernel runs it in the first
@@ -1164,6 +1172,7 @@ __device__ __forceinline__ void factor_update_body(const UpdateArgs& a, const in
   // LDS pitches are padded so that the operand reads of a half-wave hit 32 distinct 8-byte slots.
   constexpr int NRT = RG / 16;                       // 16-row tiles of a group
   constexpr bool MM64 = (KP == 16 || KP == 32 || KP == 64) && RG % 16 == 0 && NRT * 2 * (KP / 16) <= UT / 64;
+  static_assert(MM64 == update_mm64(KP), "update_mm64 (what resnmtf_update_plan reports) has drifted from the body");
   constexpr int P16 = (KP % 32 == 0) ? KP + 16 : KP + 32;   // a pitch == 16 (mod 32) doubles
   constexpr int PMa = MM64 ? P16 : KP;               // pitch of Ma / Md       (B operand: lanes (j, k) -> slot j + 16 k)
   constexpr int PSU = MM64 ? KP + 2 : KP;            // pitch of sU / sW       (A operand: lanes (i, k) -> slot 2 i + k)
@@ -1256,6 +1265,7 @@ __device__ __forceinline__ void factor_update_body(const UpdateArgs& a, const in
   // new[4 s + q][p].  Accumulated over the groups in registers, no LDS reduction.
   constexpr bool MFMA64 = EMIT && KP == 16;
   constexpr bool PACKK = (KP == 32 || KP == 64) && !EMIT && RG == 16;   // bf16 pieces of a row group staged through LDS
+  static_assert(PACKK == update_packk(KP, EMIT), "update_packk (what resnmtf_update_plan reports) has drifted from the body");
   f64x4 mg = {0.0, 0.0, 0.0, 0.0}, mc = {0.0, 0.0, 0.0, 0.0}, ms = {0.0, 0.0, 0.0, 0.0};
 
   for (int g0 = r_begin; g0 < r_end; g0 += RG) {
@@ -1439,7 +1449,7 @@ __device__ __forceinline__ void factor_update_body(const UpdateArgs& a, const in
     if (threadIdx.x < KP) out[(IS_G ? 2 : 1) * KK + threadIdx.x] = colsum;
   }
   };   // run
-  if (a.nsplit <= 4) run(std::integral_constant<int, 4>{});
+  if (a.nsplit <= 4) run(std::integral_constant<int, 4>{});             // (update_split_bucket restates these three lines)
   else if (a.nsplit <= 8) run(std::integral_constant<int, 8>{});
   else run(std::integral_constant<int, 16>{});
   STAMP_U(SU + 4);

@@ -843,6 +843,24 @@ class Engine:
             out[key] = bool(out[key])
         return out
 
+    def update_plan(self, v: int) -> dict:
+        """The update side of view ``v``'s sweep (``resnmtf_update_plan``, host only): which ``factor_update_kernel``
+        instantiation ``(kp, side, couple_bucket, emit)`` and which slab bucket its F and G updates take; side-wise
+        fields are ``(F, G)`` pairs.  The coupling fields are those of the latest prepare (``prepared``), 0 before it;
+        ``route`` is "kernel" (a launch of its own), "fused" (rides in the consuming pass) or "chain" (the hoisted F chain)."""
+        p = _lib.UpdatePlan()
+        p.struct_size = C.sizeof(_lib.UpdatePlan)
+        self._check(self._lib.resnmtf_update_plan(self._h, int(v), C.byref(p)))
+        out = {}
+        for name, typ in _lib.UpdatePlan._fields_:
+            if name == "struct_size":
+                continue
+            val = getattr(p, name)
+            out[name] = tuple(int(x) for x in val) if hasattr(typ, "_length_") else int(val)
+        out["prepared"] = bool(out["prepared"])
+        out["route"] = tuple(("kernel", "fused", "chain")[r] for r in out["route"])
+        return out
+
     def set_stop_tolerance(self, tol: float):
         """Phase API: ``tol >= 0`` = convergence mode (``R/main.r:50-81``) for the phases enqueued from now on."""
         self._check(self._lib.resnmtf_set_stop_tolerance(self._h, float(tol)))

@@ -223,3 +223,33 @@ def test_tuning_options_on_coupled_views_never_change_the_answer(k):
             wrong.append(opts)
     assert not wrong, wrong
     assert accepted >= 12, accepted      # (the test is about the sets that run)
+
+
+@pytest.mark.parametrize("which", ["phi", "psi", "xi"])
+def test_coupled_views_of_unequal_k_are_refused(which):
+    """A handle may mix k, but views coupled through phi, psi or xi need equal k (their factors are added entry by entry):
+    resnmtf_prepare and resnmtf_run refuse with RESNMTF_ERR_INVALID and say which restriction; the same handle with
+    those weights zero runs."""
+    from helpers import coupled_problem
+    from resnmtf_amd.problem import couple
+    shapes = [(70, 50), (64, 56)]
+    prob = coupled_problem(shapes, 5, seed=3, **{which + "_w": 1.0})
+    prob.init_f[1], prob.init_s[1], prob.init_g[1] = synth.random_init(64, 56, 8, 9)
+    e = Engine([70, 64], [50, 56], [5, 8])
+    try:
+        for v in range(2):
+            e.set_view(v, prob.data[v])
+            e.set_factors(v, prob.init_f[v], prob.init_s[v], prob.init_g[v])
+        e.set_restrictions(prob.phi, prob.xi, prob.psi)
+        couple(e, prob.row_names, prob.col_names)
+        for call in (lambda: e.run(2), lambda: (e.reserve_sweeps(4), e.prepare())):
+            with pytest.raises(ResnmtfError, match=f"{which}-coupled views need equal k") as ei:
+                call()
+            assert ei.value.code == 1                          # RESNMTF_ERR_INVALID
+        assert not e.update_plan(0)["prepared"]
+        e.set_restrictions()                                   # the same handle, uncoupled
+        errs = e.run(3)
+        assert len(errs) == 3 and np.isfinite(errs).all()
+        assert [e.update_plan(v)["kp"] for v in range(2)] == [16, 16] and e.update_plan(1)["k"] == 8
+    finally:
+        e.close()

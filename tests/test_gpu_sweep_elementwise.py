@@ -48,6 +48,7 @@ MUTANT_MARGIN = 4.0
 RESULTS = {}               # case id -> {"plans": [...], "tags": {...}} of the cases that passed
 ATTEMPTED = set()          # cases run in this session (a failed one does not count as covering its forms)
 DIAG = {}                  # case id -> measured statistics (written to $RESNMTF_ELEMENTWISE_OUT)
+UPDATE_PLANS = {}          # case id -> Engine.update_plan of every view (tests/test_gpu_update_forms.py counts them)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -231,18 +232,24 @@ FINDINGS = {"half1_u4": 3e-4}      # case -> bound on max |got / ref - 1| agains
 # the run
 # ---------------------------------------------------------------------------------------------------------------------
 def _engine(prob, sparse_views, opts):
+    """``sparse_views``: false, NORMALISE, true (every view sparse) or one flag per view.  k is read per view from the
+    initial factors (a handle may mix them); ``prob.init_lam`` / ``prob.init_mu`` ({view: values}), where a problem has
+    them, replace the column sums."""
     shapes = [x.shape for x in prob.data]
     n_v = len(shapes)
-    nnz = [int(sp.csc_matrix(x).nnz) for x in prob.data] if sparse_views else None
-    e = Engine([s[0] for s in shapes], [s[1] for s in shapes], [prob.k] * n_v, nnz=nnz, **opts)
+    per_view = isinstance(sparse_views, (list, tuple))
+    is_sparse = [bool(f) for f in sparse_views] if per_view else [bool(sparse_views)] * n_v
+    nnz = [int(sp.csc_matrix(x).nnz) if s else None for x, s in zip(prob.data, is_sparse)] if any(is_sparse) else None
+    e = Engine([s[0] for s in shapes], [s[1] for s in shapes], [f.shape[1] for f in prob.init_f], nnz=nnz, **opts)
     for v in range(n_v):
         if sparse_views == NORMALISE:
             e.set_view_sparse(v, sp.csc_matrix(prob.raw_counts[v]), pre_processed=False)
-        elif sparse_views:
+        elif is_sparse[v]:
             e.set_view_sparse(v, sp.csc_matrix(prob.data[v]), pre_processed=True)
         else:
             e.set_view(v, prob.data[v])
-        e.set_factors(v, prob.init_f[v], prob.init_s[v], prob.init_g[v])
+        e.set_factors(v, prob.init_f[v], prob.init_s[v], prob.init_g[v], lam=getattr(prob, "init_lam", {}).get(v),
+                      mu=getattr(prob, "init_mu", {}).get(v))
     e.set_restrictions(prob.phi, prob.xi, prob.psi)
     couple(e, prob.row_names, prob.col_names)
     return e
@@ -319,6 +326,7 @@ def run_case(cid):
         plans = [e.view_plan(v) for v in range(n_v)]
         images = [stream_image(e, v, prob.data[v], plans[v]) for v in range(n_v)]
         img_info = [e.view_image_info(v) for v in range(n_v)]
+        UPDATE_PLANS[cid] = [e.update_plan(v) for v in range(n_v)]
     finally:
         e.close()
     return prob, opts, before, after, err, plans, images, img_info
