@@ -845,6 +845,41 @@ typedef struct resnmtf_group_job {
 } resnmtf_group_job;
 int resnmtf_group_run(int device_id, int n_jobs, const resnmtf_group_job* jobs, double tol, int max_iters);
 
+/*
+ * One factorisation in fp64 at any size: res_nmtf_inner (R/main.r:32-140) for one job, spread over the whole device.
+ * The job, its outputs, n_iters, tol and max_iters mean what they mean for resnmtf_group_run, and the arithmetic is that
+ * entry's own -- update_matrices (R/update_steps.r:272-319) view by view in index order with the association orders
+ * (X G) S^T, (F S) ((G^T G) S^T), (F^T X) G, the branch tests, NaN -> 1 in the unrestricted branches only,
+ * star_prod_relevant through the row / column maps, update_lm, abs; calculate_error as the explicit residual
+ * ||X - (F S) G^T||_F^2 / ||X||_F^2 (R/utils.r:157-166) averaged over the views; the loop of R/main.r:53-80 and
+ * normalisation_check (R/utils.r:176-195) -- only its distribution differs: a sweep of a view is a short sequence of
+ * ordinary launches on one stream (tall-skinny products on the fp64 MFMA, row-local updates, k x k jobs), so there is no
+ * cap on n_rows * n_cols and k goes to RESNMTF_MAX_K.  No atomics and no waiting between workgroups; every sum has an order
+ * fixed by the job's shapes and k, so two calls give the same bits (not the bits of resnmtf_group_run: the orders differ).
+ * In convergence mode (n_iters == 0) the sweep's mean error is read back after every sweep and the stop rule is applied
+ * on the host; the state returned is the stop sweep's.
+ * Blocking; no handle: the call selects device_id, sizes one device buffer (two padded fp64 images of every view, the
+ * factors, two scratch matrices, product slabs, partials, the error history, the maps) before any launch and refuses
+ * with RESNMTF_ERR_ALLOC, the byte count in resnmtf_last_error(NULL), when it exceeds the free device memory.
+ * Refused before any device work (RESNMTF_ERR_INVALID), with resnmtf_group_run's texts: job NULL, a struct_size
+ * mismatch, max_iters < 1, tol not finite, n_views outside [1, 8], k outside [1, 64] or above a view dimension, NULL
+ * input or output pointers, non-finite inputs, negative restriction entries or a non-zero diagonal, an index pair
+ * outside its views, n_iters < 0, err_capacity below the sweeps allowed.  A refusal writes no output.
+ * DESIGN.md section 21.
+ */
+int resnmtf_fp64_run(int device_id, const resnmtf_group_job* job, double tol, int max_iters);
+
+/*
+ * The launch geometry resnmtf_fp64_run takes for an n_rows x n_cols view at k -- a function of these three numbers alone.
+ * out[RESNMTF_FP64_PLAN_INTS]: the padded k (16 / 32 / 48 / 64); then row tiles, contraction splits and contraction
+ * indices per split of the X G product, of the X^T F product, and (64-row tiles, column splits, columns per split) of
+ * the residual; last the leading dimensions of the fp64 images of X and of X^T (rows padded to 32, kept off the multiples
+ * of 1024).  A split count above 1 means partial products in a slab, summed in split order by the consumer.
+ * Refused (RESNMTF_ERR_INVALID): out NULL, a dimension below 1, k outside [1, 64] or above a dimension.  No device work.
+ */
+#define RESNMTF_FP64_PLAN_INTS 12
+int resnmtf_fp64_plan(int n_rows, int n_cols, int k, int* out);
+
 /* ---- phase-level entry points (views sharded one-per-GPU; host does the exchange) ---- */
 
 /* Which image of X the streaming passes of view v use after its upload: *uses_2byte = 0 (f32 images), 1 (fp16) or

@@ -90,6 +90,7 @@ _h = C.c_void_p
 GROUP_MAX_VIEWS = 8
 GROUP_MAX_K = 32
 GROUP_MAX_VIEW_ENTRIES = 1 << 22
+FP64_PLAN_INTS = 12        # RESNMTF_FP64_PLAN_INTS
 _MV = GROUP_MAX_VIEWS
 
 
@@ -164,6 +165,8 @@ SIGNATURES = {
     "resnmtf_jsd_stages": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, _ip, _dp, _dp, _dp, _dp]),
     "resnmtf_spurious_scores": (C.c_int, [_h, C.c_int, C.POINTER(_h), C.c_int, _dp, _dp]),
     "resnmtf_group_run": (C.c_int, [C.c_int, C.c_int, C.POINTER(GroupJob), C.c_double, C.c_int]),
+    "resnmtf_fp64_run": (C.c_int, [C.c_int, C.POINTER(GroupJob), C.c_double, C.c_int]),
+    "resnmtf_fp64_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip]),
     "resnmtf_bisil": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_bisil_sparse": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_bisil_device": (C.c_int, [_h, C.c_int, C.c_int, _dm, _dm, C.c_int, C.c_void_p, C.c_void_p, _dp, C.c_void_p]),

@@ -40,6 +40,7 @@ from typing import Callable, Optional
 import numpy as np
 
 from . import batched, bisil, device_views, naming, sparse
+from . import engine as _engine
 from . import spurious as _spurious
 from .engine import Engine
 from .problem import couple, inner_result, prepare, svd_init  # noqa: F401  (svd_init: part of this module's surface)
@@ -104,7 +105,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
                    host_init: bool = False, return_init: bool = False, score_bisil: bool = False,
                    spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False,
                    sparse_on_device: bool = False, output: str = "numpy", init_lm=None, return_state: bool = False,
-                   post_on_device: bool = False):
+                   post_on_device: bool = False, precision: str = "f32"):
     """``res_nmtf_inner`` (``R/main.r:32-140``).
 
     ``data``: list of pre-processed (non-negative, column-normalised) matrices; ``row_indices[v][w]``
@@ -174,7 +175,27 @@ def res_nmtf_inner(data, row_indices, column_indices,
     k x k S copied to the host, the flagged columns zeroed in clones of the cluster tensors) and ``bisil`` is scored from
     the cleaned tensors (``Engine.bisil_device``: silhouettes and their combination on the device).  The result equals
     the same call without the flag key for key, bit for bit.
+
+    ``precision`` (keyword-only; ``"f32"``, the default, is everything above, untouched; anything but ``"f32"`` or
+    ``"fp64"`` is a ``ValueError``): ``"fp64"`` runs the loop through ``engine.fp64_run`` -- the
+    reference's arithmetic in double on the whole device, at any size, k up to 64 and one k for all views, at most 8
+    views.  Views are dense NumPy arrays or CPU tensors; restrictions and names as above; the initial state is the explicit factors
+    (with ``init_lm`` if given), ``svd_init`` with ``host_init=True``, else the device's own SVD initialisation (an engine
+    is built, loaded, initialised, read with ``get_factors`` and closed: the start ``return_init`` reports).  The result
+    has the keys and types of the f32 call; ``return_init`` is honoured.  What needs a live handle is refused before any
+    device work with a ``NotImplementedError`` naming the flag: ``spurious=True`` with ``spurious_on_device``,
+    ``score_bisil``, ``output="torch"``, ``post_on_device``, ``return_state``, sparse views, views or factors in device
+    memory.
     """
+    if precision not in ("f32", "fp64"):
+        raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
+    if precision == "fp64":
+        return _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init_g, k_vec, phi, xi, psi, n_iters,
+                                    spurious, distance, no_clusts, row_names=row_names, col_names=col_names,
+                                    device_id=device_id, max_iters=max_iters, seed=seed, engine_opts=engine_opts,
+                                    host_init=host_init, return_init=return_init, score_bisil=score_bisil,
+                                    spurious_on_device=spurious_on_device, output=output, init_lm=init_lm,
+                                    return_state=return_state, post_on_device=post_on_device)
     device_views.check_output(output)
     _check_post_on_device(post_on_device, output)
     data = _views(data, device_id)
@@ -261,6 +282,89 @@ def res_nmtf_inner(data, row_indices, column_indices,
     return inner_result(out_f, out_s, out_g, total_err, n_iters, bisil=cleaned.get("bisil"),
                         row_clusters=cleaned["row_clusters"], col_clusters=cleaned["col_clusters"], lam=lams, mu=mus,
                         spurious=cleaned.get("spurious"), init=init_state, state=state)
+
+
+def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init_g, k_vec, phi, xi, psi, n_iters, spurious,
+                         distance, no_clusts, *, row_names, col_names, device_id, max_iters, seed, engine_opts, host_init,
+                         return_init, score_bisil, spurious_on_device, output, init_lm, return_state, post_on_device,
+                         runner: Optional[Callable] = None):
+    """``res_nmtf_inner(precision="fp64")``: the checks of the f32 call, the refusals of what needs a live handle, the
+    initial state, then one ``engine.fp64_run`` (``runner`` replaces it: a test hook)."""
+    def refuse(flag):
+        raise NotImplementedError(f'precision="fp64": {flag} needs a live engine handle, which the fp64 path does not '
+                                  'keep (it runs through resnmtf_fp64_run); use precision="f32" for it')
+    device_views.check_output(output)
+    remove = bool(spurious) and not no_clusts
+    for flag, on in (("spurious_on_device", remove and spurious_on_device), ("score_bisil", score_bisil),
+                     ("post_on_device", post_on_device), ('output="torch"', output == "torch"),
+                     ("return_state", return_state)):
+        if on:
+            refuse(flag)
+    _refuse_host_spurious(remove, spurious_on_device,
+                          "spurious-bicluster removal (R/obtain_bicl.r:31-133) is outside the accelerated path; "
+                          "pass spurious=False or do it on the R side (INTEGRATION.md).")
+    _check_distance(distance)
+    views = []
+    for v, d in enumerate(_as_list(data)):
+        d = device_views.host_or_device(d, f"view {v}")
+        if sparse.is_sparse_view(d) or device_views.is_sparse_tensor(d):
+            refuse(f"sparse views (view {v})")
+        if device_views.is_device_view(d):
+            refuse(f"views in device memory (view {v})")
+        views.append(np.asarray(d, dtype=np.float64))
+    data, n_v = views, len(views)
+    if k_vec is None:
+        raise ValueError("k_vec is required")
+    k_vec = [int(k) for k in np.atleast_1d(k_vec)]
+    if len(k_vec) != n_v:
+        raise ValueError("k_vec must be a vector of the same length as the number of views.")   # utils.r:440
+    if len(set(k_vec)) != 1:
+        raise ValueError('precision="fp64" takes one k for all views (resnmtf_fp64_run)')
+    lam = mu = None
+    if init_f is None or init_g is None or init_s is None:
+        init_f = init_s = init_g = None
+    else:
+        init_f, init_s, init_g = _as_list(init_f), _as_list(init_s), _as_list(init_g)
+        if any(device_views.is_device_tensor(x) for x in (*init_f, *init_s, *init_g)):
+            refuse("factors in device memory")
+        _, init_f, init_s, init_g = device_views.factor_routes(init_f, init_s, init_g, device_id)
+    if init_lm is not None:
+        if init_f is None:
+            raise ValueError("init_lm needs explicit initial factors (init_f, init_s and init_g)")
+        lam, mu = device_views.check_init_lm(init_lm, n_v)
+        if any(device_views.is_device_tensor(x) for x in (*lam, *mu)):
+            refuse("factors in device memory")
+        lam, mu = [device_views.to_numpy(x) for x in lam], [device_views.to_numpy(x) for x in mu]
+    phi, xi, psi = (np.zeros((n_v, n_v)) if m is None else np.asarray(m, dtype=np.float64) for m in (phi, xi, psi))
+    row_names, col_names = naming.give_names(data, None, None, row_names, col_names)
+    batched._check_group_limits(0, data, k_vec[0], batched.FP64_LIMITS)
+
+    if init_f is None and host_init:
+        init_f, init_s, init_g, lam, mu = svd_init(data, k_vec, seed)
+    elif init_f is None:                          # the device's own SVD initialisation: the start the f32 call reports
+        eng = Engine([d.shape[0] for d in data], [d.shape[1] for d in data], k_vec, device_id=device_id, **(engine_opts or {}))
+        try:
+            _load_engine(eng, data, None, None, None, None, None, phi, xi, psi, row_names, col_names, row_indices,
+                         column_indices, seed=seed)
+            init_f, init_s, init_g, lam, mu = (list(x) for x in zip(*[eng.get_factors(v) for v in range(n_v)]))
+        finally:
+            eng.close()
+    problem = {"data": data, "k": k_vec[0], "init_f": list(init_f), "init_s": list(init_s), "init_g": list(init_g),
+               "init_lam": None if lam is None else list(lam), "init_mu": None if mu is None else list(mu),
+               "phi": phi, "xi": xi, "psi": psi, "row_pairs": batched.pair_table(row_names, row_indices),
+               "col_pairs": batched.pair_table(col_names, column_indices), "n_iters": n_iters}
+    init_state = None
+    if return_init:                               # (F, S, G, lambda, mu) the loop starts from; None lambda / mu: the colSums
+        init_state = [tuple(np.array(a, dtype=np.float64) for a in
+                            (init_f[v], init_s[v], init_g[v],
+                             np.sum(init_f[v], axis=0) if lam is None or lam[v] is None else lam[v],
+                             np.sum(init_g[v], axis=0) if mu is None or mu[v] is None else mu[v])) for v in range(n_v)]
+    out = (runner or _engine.fp64_run)(problem, tol=1.0e-6, max_iters=max_iters, device_id=device_id)
+    if no_clusts:                                                                                 # main.r:115-120
+        return inner_result(out["f"], out["s"], out["g"], init=init_state)
+    rcs, ccs = zip(*[batched._binary_clusters(f, g, s) for f, g, s in zip(out["f"], out["g"], out["s"])])
+    return inner_result(out["f"], out["s"], out["g"], np.asarray(out["all_error"], dtype=np.float64), n_iters, bisil=None,
+                        row_clusters=list(rcs), col_clusters=list(ccs), lam=out["lambda"], mu=out["mu"], init=init_state)
 
 
 def _device_outputs(on_device, row_cl, col_cl, cleaned: dict):

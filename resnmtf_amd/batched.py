@@ -31,7 +31,8 @@ from typing import Callable, Dict, List, Optional, Sequence
 import numpy as np
 
 from . import device_views, naming, sparse, spurious
-from ._lib import GROUP_MAX_K, GROUP_MAX_VIEW_ENTRIES, GROUP_MAX_VIEWS
+from . import engine as _engine
+from ._lib import GROUP_MAX_K, GROUP_MAX_VIEW_ENTRIES, GROUP_MAX_VIEWS, MAX_K
 from .engine import Engine, group_run
 from .problem import (inner_result, load_child, pair_table, prepare, reported_error,  # noqa: F401  (shuffled_engines:
                       shuffled_engines, svd_init)                                     # part of this module's surface)
@@ -194,31 +195,38 @@ def run_jobs(jobs: Sequence[Job], device_id: int = 0, group=None, runner: Option
 # ---------------------------------------------------------------------------------------------
 # many small jobs in one launch: one workgroup per job, fp64 (resnmtf_group_run)
 # ---------------------------------------------------------------------------------------------
-def _check_group_limits(i: int, data, k: int):
-    if len(data) > GROUP_MAX_VIEWS:
-        raise ValueError(f"job {i}: the grouped path takes at most {GROUP_MAX_VIEWS} views, got {len(data)}")
-    if not 1 <= k <= GROUP_MAX_K:
-        raise ValueError(f"job {i}: the grouped path takes 1 <= k <= {GROUP_MAX_K}, got k = {k}")
+GroupLimits = namedtuple("GroupLimits", "path max_views max_k max_view_entries")
+GROUPED_LIMITS = GroupLimits("grouped", GROUP_MAX_VIEWS, GROUP_MAX_K, GROUP_MAX_VIEW_ENTRIES)      # resnmtf_group_run
+FP64_LIMITS = GroupLimits("fp64", GROUP_MAX_VIEWS, MAX_K, None)                                    # resnmtf_fp64_run: no cap on n * m
+
+
+def _check_group_limits(i: int, data, k: int, limits: GroupLimits = GROUPED_LIMITS):
+    if len(data) > limits.max_views:
+        raise ValueError(f"job {i}: the {limits.path} path takes at most {limits.max_views} views, got {len(data)}")
+    if not 1 <= k <= limits.max_k:
+        raise ValueError(f"job {i}: the {limits.path} path takes 1 <= k <= {limits.max_k}, got k = {k}")
     for v, x in enumerate(data):
         n, m = x.shape
         if k > n or k > m:
             raise ValueError(f"job {i}: k = {k} exceeds a dimension of view {v} ({n} x {m})")
-        if n * m > GROUP_MAX_VIEW_ENTRIES:
-            raise ValueError(f"job {i}: view {v} has {n * m} entries, above the grouped path's 2^22; use run_jobs")
+        if limits.max_view_entries is not None and n * m > limits.max_view_entries:
+            raise ValueError(f"job {i}: view {v} has {n * m} entries, above the {limits.path} path's 2^22; use run_jobs")
 
 
-def prepare_grouped_job(job: Job, i: int = 0, pre_processed: bool = False, init=None) -> dict:
+def prepare_grouped_job(job: Job, i: int = 0, pre_processed: bool = False, init=None,
+                        limits: GroupLimits = GROUPED_LIMITS) -> dict:
     """The problem ``engine.group_run`` receives for one job, prepared as ``run_job`` prepares it for the engine:
     names, shared-name index pairs, symmetrised restrictions, ``check_data`` unless ``pre_processed``, and the initial
     factors ``init`` = (F, S, G[, lambda, mu]) per view or, when None, ``api.svd_init(data, k_vec, job.seed)`` on the
-    host.  Sparse views and jobs over the kernel's limits are refused here."""
+    host.  Sparse views and jobs over the kernel's limits are refused here; ``limits`` names the path and its caps
+    (``GROUPED_LIMITS``, the default, or ``FP64_LIMITS`` for ``engine.fp64_run``)."""
     if any(sparse.is_sparse_view(d) for d in job.data):
-        raise NotImplementedError(f"job {i}: the grouped path takes dense views only; run sparse views with run_jobs")
+        raise NotImplementedError(f"job {i}: the {limits.path} path takes dense views only; run sparse views with run_jobs")
     data = [np.asarray(d, dtype=np.float64) for d in job.data]
     if any(d.ndim != 2 for d in data):
         raise ValueError(f"job {i}: every view must be a matrix")
     n_v, k = len(data), int(job.k_val)
-    _check_group_limits(i, data, k)
+    _check_group_limits(i, data, k, limits)
     p = prepare(data, job.phi, job.xi, job.psi, job.row_names, job.col_names, normalise=not pre_processed, symmetrise=True)
     data = p.data
     if init is None:
@@ -277,6 +285,21 @@ def run_jobs_grouped(jobs: Sequence[Job], device_id: int = 0, pre_processed: boo
                                     row_clusters=list(rcs), col_clusters=list(ccs), lam=out["lambda"], mu=out["mu"], tag=job.tag,
                                     extras=job.extras))
     return results
+
+
+def run_job_fp64(job: Job, device_id: int = 0, pre_processed: bool = False, init=None, max_iters: int = 100000,
+                 runner: Optional[Callable] = None) -> dict:
+    """One job through the device-wide fp64 path (``engine.fp64_run``): prepared as
+    ``prepare_grouped_job`` prepares it -- dense views only, at most 8 views, 1 <= k <= 64, no cap on n * m -- from
+    ``init`` = (F, S, G[, lambda, mu]) per view or, when None, ``api.svd_init`` on the host with the job's seed.
+    Returns the keys ``run_job`` returns (``bisil`` None).  ``runner(problem, tol=, max_iters=, device_id=)`` replaces
+    ``engine.fp64_run`` (a test hook); every refusal comes before it is called."""
+    problem = prepare_grouped_job(job, 0, pre_processed, init, limits=FP64_LIMITS)
+    out = (runner or _engine.fp64_run)(problem, tol=1.0e-6, max_iters=max_iters, device_id=device_id)
+    rcs, ccs = zip(*[_binary_clusters(f, g, s) for f, g, s in zip(out["f"], out["g"], out["s"])])
+    return inner_result(out["f"], out["s"], out["g"], np.asarray(out["all_error"], dtype=np.float64), job.n_iters,
+                        row_clusters=list(rcs), col_clusters=list(ccs), lam=out["lambda"], mu=out["mu"], tag=job.tag,
+                        extras=job.extras)
 
 
 # ---------------------------------------------------------------------------------------------

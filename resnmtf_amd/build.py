@@ -22,7 +22,9 @@ SWEEP = "resnmtf_hip.hip"
 # the k <= 16 streaming pass: a translation unit of its own, compiled with the max-ILP machine scheduler (csrc/resnmtf_split_tu.h)
 PASS_K16 = "resnmtf_pass_k16.hip"
 PASS_K16_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
-UNITS = [SWEEP, PASS_K16]
+# the device-wide fp64 path (resnmtf_fp64_run): host side and kernels in a unit, and so a code object, of their own
+FP64 = "resnmtf_fp64.hip"
+UNITS = [SWEEP, PASS_K16, FP64]
 ARCH = "--offload-arch=gfx950"
 
 

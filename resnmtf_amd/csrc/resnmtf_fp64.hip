@@ -1,0 +1,405 @@
+// Device-wide fp64 factorisation: the host side of resnmtf_fp64_run and resnmtf_fp64_plan, and --
+// through resnmtf_fp64.hip.inc -- their kernels.  A translation unit of its own: the kernels get a code object of their
+// own and leave the main unit's device code as it was.  The job checks and the error text are the main unit's
+// (resnmtf_internal.h): this entry and resnmtf_group_run refuse the same things with the same texts.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "resnmtf_hip.h"
+#include "resnmtf_internal.h"
+#include "resnmtf_fp64.hip.inc"
+
+namespace {
+struct DeviceBuffer {
+  void* p = nullptr;
+  ~DeviceBuffer() { if (p) (void)hipFree(p); }
+};
+
+inline size_t rup(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+struct F64View {
+  int n = 0, m = 0;
+  size_t ldn = 0, mpad = 0;                // X: ldn x mpad, column-major (ldn = f64_ld(n), mpad = m to 64), zero-filled
+  size_t ldm = 0, npad = 0;                // X^T: ldm x npad
+  size_t x = 0, xt = 0, f = 0, g = 0;      // offsets in doubles
+  F64ProductPlan xg, xtf, res;
+};
+
+// the job's one device buffer, in doubles: [X, X^T per view | F, G per view | S | lambda | mu] (uploaded) | the k x k work
+// area | column sums, norms, errors | two scratch matrices | product slab | partials | error history | maps (ints)
+struct F64Layout {
+  int V = 0, k = 0, KP = 0, cap = 0;
+  F64View vw[RESNMTF_GROUP_MAX_VIEWS];
+  size_t out_begin = 0, out_end = 0;       // F, G, S, lambda, mu: one contiguous region, read back at the end
+  size_t s = 0, lam = 0, mu = 0, kk = 0, cf = 0, cg = 0, norms = 0, errs = 0, scratch = 0, scratch2 = 0, slab = 0;
+  size_t part0 = 0, part1 = 0, colf = 0, colg = 0, spart = 0, err = 0, maps = 0, total = 0;
+  long long rmap[RESNMTF_GROUP_MAX_VIEWS][RESNMTF_GROUP_MAX_VIEWS];     // int offsets from the buffer base, -1 = NA
+  long long cmap[RESNMTF_GROUP_MAX_VIEWS][RESNMTF_GROUP_MAX_VIEWS];
+};
+
+// the shapes alone pass (what fp64_layout may be called on); everything else is check_group_job's to say
+bool fp64_shapes_ok(const resnmtf_group_job& j) {
+  if (j.struct_size != (int)sizeof(resnmtf_group_job)) return false;
+  if (j.n_views < 1 || j.n_views > RESNMTF_GROUP_MAX_VIEWS || j.k < 1 || j.k > RESNMTF_MAX_K || j.n_iters < 0) return false;
+  for (int v = 0; v < j.n_views; ++v)
+    if (j.n_rows[v] < 1 || j.n_cols[v] < 1 || j.k > j.n_rows[v] || j.k > j.n_cols[v]) return false;
+  return true;
+}
+
+// bytes of the two images of every view, the bulk of the buffer, without overflow
+long double fp64_image_bytes(const resnmtf_group_job& j) {
+  long double b = 0;
+  for (int v = 0; v < j.n_views; ++v) {
+    const long double n = j.n_rows[v], m = j.n_cols[v];
+    b += ((n + 63) * (m + 63) + (m + 63) * (n + 63)) * sizeof(double);
+  }
+  return b;
+}
+
+void fp64_layout(const resnmtf_group_job& j, int cap, F64Layout& L) {
+  L.V = j.n_views; L.k = j.k; L.KP = f64_kp(j.k); L.cap = cap;
+  const size_t k = (size_t)L.k, V = (size_t)L.V;
+  size_t off = 0, big = 1, slab = 1, gram_blk = 1, col_blk = 1, spart = 1;
+  for (int v = 0; v < L.V; ++v) {
+    F64View& w = L.vw[v];
+    w.n = j.n_rows[v]; w.m = j.n_cols[v];
+    w.ldn = f64_ld(w.n); w.mpad = rup(w.m, F64_JC); w.ldm = f64_ld(w.m); w.npad = rup(w.n, F64_JC);
+    w.x = off; off += w.ldn * w.mpad;
+    w.xt = off; off += w.ldm * w.npad;
+    w.xg = f64_plan_product(w.n, w.m);
+    w.xtf = f64_plan_product(w.m, w.n);
+    w.res = f64_plan_resid(w.n, w.m);
+    big = std::max(big, (size_t)std::max(w.n, w.m));
+    slab = std::max(slab, std::max((size_t)w.xg.splits * w.ldn, (size_t)w.xtf.splits * w.ldm) * (size_t)L.KP);
+    spart = std::max(spart, (size_t)w.res.tiles * w.res.splits);
+    spart = std::max(spart, (std::max(w.ldn * w.mpad, w.ldm * w.npad) + F64_NORM_CHUNK - 1) / F64_NORM_CHUNK);
+  }
+  gram_blk = (big + F64_GRAM_ROWS - 1) / F64_GRAM_ROWS;
+  col_blk = (big + F64_UPD_ROWS - 1) / F64_UPD_ROWS;
+  L.out_begin = off;
+  for (int v = 0; v < L.V; ++v) {
+    L.vw[v].f = off; off += (size_t)L.vw[v].n * k;
+    L.vw[v].g = off; off += (size_t)L.vw[v].m * k;
+  }
+  L.s = off; off += V * k * k;
+  L.lam = off; off += V * k;
+  L.mu = off; off += V * k;
+  L.out_end = off;
+  L.kk = off; off += 4 * k * k;
+  L.cf = off; off += V * k;
+  L.cg = off; off += V * k;
+  L.norms = off; off += RESNMTF_GROUP_MAX_VIEWS;
+  L.errs = off; off += RESNMTF_GROUP_MAX_VIEWS;
+  L.scratch = off; off += big * k;
+  L.scratch2 = off; off += big * k;
+  L.slab = off; off += slab;
+  L.part0 = off; off += gram_blk * k * k;
+  L.part1 = off; off += gram_blk * k * k;
+  L.colf = off; off += col_blk * k;
+  L.colg = off; off += col_blk * k;
+  L.spart = off; off += spart;
+  L.err = off; off += (size_t)cap;
+  L.maps = off;
+  size_t ioff = off * 2;
+  for (int v = 0; v < RESNMTF_GROUP_MAX_VIEWS; ++v)
+    for (int w = 0; w < RESNMTF_GROUP_MAX_VIEWS; ++w) {
+      const bool pair = v < L.V && w < L.V && v != w;
+      L.rmap[v][w] = pair && j.row_count[v][w] > 0 ? (long long)ioff : -1;
+      if (L.rmap[v][w] >= 0) ioff += (size_t)L.vw[v].n;
+      L.cmap[v][w] = pair && j.col_count[v][w] > 0 ? (long long)ioff : -1;
+      if (L.cmap[v][w] >= 0) ioff += (size_t)L.vw[v].m;
+    }
+  L.total = (ioff + 1) / 2;
+}
+
+// numpy's pairwise sum of a column of a V x V restriction (as grp_vec_sum)
+double fp64_col_sum(const double* r, int V, int v) {
+  if (!r) return 0.0;
+  const double* a = r + (size_t)v * V;       // column v of the column-major matrix: entries [w + v V] = r[w, v]
+  if (V < 8) {
+    double s = 0.0;
+    for (int w = 0; w < V; ++w) s += a[w];
+    return s;
+  }
+  return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+}
+bool fp64_all_zero(const double* r, int V) {
+  if (!r) return true;
+  for (int e = 0; e < V * V; ++e)
+    if (r[e] != 0.0) return false;
+  return true;
+}
+
+// one sweep of update_matrices (R/update_steps.r:272-319, views in index order) and the error of every view; the mean
+// error of the sweep lands in the error history at `it`
+void fp64_enqueue_sweep(hipStream_t st, const resnmtf_group_job& j, const F64Layout& L, double* buf, int it) {
+  const int V = L.V, k = L.k, KP = L.KP;
+  const int* ibuf = reinterpret_cast<const int*>(buf);
+  double* kkA = buf + L.kk;
+  double* kkB = kkA + (size_t)k * k;
+  double* kkC = kkB + (size_t)k * k;
+  double* kkD = kkC + (size_t)k * k;
+  const bool psi_zero = fp64_all_zero(j.psi, V), xi_zero = fp64_all_zero(j.xi, V);
+  for (int v = 0; v < V; ++v) {
+    const F64View& w = L.vw[v];
+    double* F = buf + w.f;
+    double* G = buf + w.g;
+    F64KKArgs kk{};
+    kk.k = k; kk.V = V; kk.v = v;
+    kk.kkA = kkA; kk.kkB = kkB; kk.kkC = kkC; kk.kkD = kkD;
+    kk.S = buf + L.s; kk.lam = buf + L.lam + (size_t)v * k; kk.mu = buf + L.mu + (size_t)v * k;
+    kk.cf = buf + L.cf + (size_t)v * k; kk.cg = buf + L.cg + (size_t)v * k;
+    kk.norms = buf + L.norms; kk.errs = buf + L.errs; kk.err_out = buf + L.err + it;
+    for (int side = 0; side < 2; ++side) {
+      const bool g_form = side == 1;
+      const int n = g_form ? w.m : w.n, m = g_form ? w.n : w.m;           // rows of the factor updated / of the other
+      double* P = g_form ? G : F;
+      const double* O = g_form ? F : G;
+      const int gram_blk = (m + F64_GRAM_ROWS - 1) / F64_GRAM_ROWS;
+      F64GramArgs ga{};
+      ga.A[0] = O; ga.B[0] = O; ga.part[0] = buf + L.part0; ga.len = m; ga.k = k;
+      hipLaunchKernelGGL(fp64_gram_kernel, dim3(gram_blk, 1), dim3(F64_THREADS), 0, st, ga);            // O^T O
+      kk.mode = g_form ? F64_KK_SIDE_G : F64_KK_SIDE_F;
+      kk.part_a = buf + L.part0; kk.nblk_a = gram_blk;
+      hipLaunchKernelGGL(fp64_kk_kernel, dim3(1), dim3(F64_THREADS), 0, st, kk);
+      fp64_product(st, KP, g_form ? w.xtf : w.xg, buf + (g_form ? w.xt : w.x), g_form ? w.ldm : w.ldn, O, m, k,
+                   g_form ? w.npad : w.mpad, buf + L.slab);
+      F64UpdArgs u{};
+      u.n = n; u.k = k; u.KP = KP; u.V = V; u.nsplit = g_form ? w.xtf.splits : w.xg.splits;
+      u.ldx = g_form ? w.ldm : w.ldn;
+      u.slab = buf + L.slab; u.P = P; u.xo = buf + L.scratch; u.ps = buf + L.scratch2;
+      u.S = buf + L.s + (size_t)v * k * k; u.W = kkB; u.lm = g_form ? kk.mu : kk.lam;
+      const double* R = g_form ? j.psi : j.phi;
+      u.rsum = fp64_col_sum(R, V, v);
+      u.unrestricted = g_form ? (psi_zero ? 1 : 0) : (u.rsum == 0.0 ? 1 : 0);     // :190 / :152
+      for (int x = 0; x < V; ++x) {
+        u.r[x] = R ? R[x + (size_t)v * V] : 0.0;
+        const long long mo = g_form ? L.cmap[v][x] : L.rmap[v][x];
+        u.map[x] = mo >= 0 ? ibuf + mo : nullptr;
+        u.Pw[x] = buf + (g_form ? L.vw[x].g : L.vw[x].f);
+        u.nw[x] = g_form ? L.vw[x].m : L.vw[x].n;
+      }
+      u.colpart = buf + (g_form ? L.colg : L.colf);
+      const int upd_blk = (n + F64_UPD_ROWS - 1) / F64_UPD_ROWS;
+      if (g_form) hipLaunchKernelGGL(fp64_update_kernel<true>, dim3(upd_blk), dim3(F64_UPD_ROWS), 0, st, u);
+      else hipLaunchKernelGGL(fp64_update_kernel<false>, dim3(upd_blk), dim3(F64_UPD_ROWS), 0, st, u);
+    }
+    // update_s (:220-240): (F^T X) G from the X^T F the G update kept, and G^T G of the new G; then update_lm
+    const int gblk = (w.m + F64_GRAM_ROWS - 1) / F64_GRAM_ROWS;
+    F64GramArgs gs{};
+    gs.A[0] = buf + L.scratch; gs.B[0] = G; gs.part[0] = buf + L.part0;
+    gs.A[1] = G; gs.B[1] = G; gs.part[1] = buf + L.part1;
+    gs.len = w.m; gs.k = k;
+    hipLaunchKernelGGL(fp64_gram_kernel, dim3(gblk, 2), dim3(F64_THREADS), 0, st, gs);
+    kk.mode = F64_KK_S;
+    kk.part_a = buf + L.part0; kk.nblk_a = gblk; kk.part_b = buf + L.part1; kk.nblk_b = gblk;
+    kk.col_f = buf + L.colf; kk.nblk_f = (w.n + F64_UPD_ROWS - 1) / F64_UPD_ROWS;
+    kk.col_g = buf + L.colg; kk.nblk_g = (w.m + F64_UPD_ROWS - 1) / F64_UPD_ROWS;
+    kk.xi_zero = xi_zero ? 1 : 0;
+    kk.xsum = fp64_col_sum(j.xi, V, v);
+    for (int x = 0; x < V; ++x) kk.xi[x] = j.xi ? j.xi[x + (size_t)v * V] : 0.0;
+    hipLaunchKernelGGL(fp64_kk_kernel, dim3(1), dim3(F64_THREADS), 0, st, kk);
+  }
+  for (int v = 0; v < V; ++v) {            // calculate_error (R/utils.r:157-166) of every view, after all updates (:316-319)
+    const F64View& w = L.vw[v];
+    hipLaunchKernelGGL(fp64_fs_kernel, dim3((w.n + F64_UPD_ROWS - 1) / F64_UPD_ROWS), dim3(F64_UPD_ROWS), 0, st,
+                       (const double*)(buf + w.f), (const double*)(buf + L.s + (size_t)v * k * k), w.n, k, buf + L.scratch2);
+    fp64_resid(st, KP, w.res, buf + w.x, w.ldn, buf + L.scratch2, w.n, buf + w.g, w.m, k, buf + L.spart);
+    F64KKArgs kk{};
+    kk.mode = F64_KK_ERR; kk.k = k; kk.V = V; kk.v = v;
+    kk.part_a = buf + L.spart; kk.nblk_a = w.res.tiles * w.res.splits;
+    kk.S = buf + L.s; kk.norms = buf + L.norms; kk.errs = buf + L.errs; kk.err_out = buf + L.err + it;
+    hipLaunchKernelGGL(fp64_kk_kernel, dim3(1), dim3(F64_THREADS), 0, st, kk);
+  }
+}
+}  // namespace
+
+extern "C" {
+
+int resnmtf_fp64_plan(int n_rows, int n_cols, int k, int* out) {
+  auto bad = [](const std::string& msg) { resnmtf_set_create_error(msg); return RESNMTF_ERR_INVALID; };
+  if (!out) return bad("out is NULL");
+  if (n_rows < 1 || n_cols < 1) return bad("view dimensions must be positive");
+  if (k < 1 || k > RESNMTF_MAX_K) return bad("k must be in [1, 64]");
+  if (k > n_rows || k > n_cols) return bad("k exceeds a view dimension (R/utils.r:444,449)");
+  const F64ProductPlan xg = f64_plan_product(n_rows, n_cols), xtf = f64_plan_product(n_cols, n_rows);
+  const F64ProductPlan res = f64_plan_resid(n_rows, n_cols);
+  const int vals[RESNMTF_FP64_PLAN_INTS] = {f64_kp(k), xg.tiles, xg.splits, xg.chunk, xtf.tiles, xtf.splits, xtf.chunk,
+                                            res.tiles, res.splits, res.chunk, (int)f64_ld(n_rows), (int)f64_ld(n_cols)};
+  std::memcpy(out, vals, sizeof(vals));
+  return RESNMTF_OK;
+}
+
+int resnmtf_fp64_run(int device_id, const resnmtf_group_job* job, double tol, int max_iters) {
+  auto bad = [](const std::string& msg) { resnmtf_set_create_error(msg); return RESNMTF_ERR_INVALID; };
+  if (!job) return bad("job is NULL");
+  if (max_iters < 1) return bad("max_iters must be >= 1");
+  if (!std::isfinite(tol)) return bad("tol must be finite");
+  const resnmtf_group_job& j = *job;
+  // a shape no device holds is refused on its byte count before the data behind it is read
+  if (fp64_shapes_ok(j)) {
+    const long double img = fp64_image_bytes(j);
+    if (img >= 0x1p58L) {
+      char text[160];
+      std::snprintf(text, sizeof(text), "fp64_run: more than %.0Lf bytes asked for (the fp64 images of the views alone)", img);
+      resnmtf_set_create_error(text);
+      return RESNMTF_ERR_ALLOC;
+    }
+  }
+  if (const char* why = resnmtf_check_fp64_job(j, max_iters)) return bad(why);
+
+  const int cap = j.n_iters > 0 ? std::min(j.n_iters, max_iters) : max_iters;
+  F64Layout L;
+  fp64_layout(j, cap, L);
+  const size_t bytes = L.total * sizeof(double);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { resnmtf_set_create_error("no HIP device"); return RESNMTF_ERR_NO_DEVICE; }
+  if (device_id < 0 || device_id >= ndev) return bad("device_id out of range");
+  hipError_t e = hipSetDevice(device_id);
+  if (e != hipSuccess) { resnmtf_set_create_error(std::string("hipSetDevice: ") + hipGetErrorString(e)); return RESNMTF_ERR_HIP; }
+  size_t free_b = 0, total_b = 0;
+  e = hipMemGetInfo(&free_b, &total_b);
+  if (e != hipSuccess) { resnmtf_set_create_error(std::string("fp64_run: ") + hipGetErrorString(e)); return RESNMTF_ERR_HIP; }
+  if (bytes > free_b) {
+    resnmtf_set_create_error("fp64_run: " + std::to_string(bytes) + " bytes asked for (two fp64 images of every view, factors, slabs), " +
+                     std::to_string(free_b) + " free on the device");
+    return RESNMTF_ERR_ALLOC;
+  }
+  hipStream_t st = nullptr;
+  e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+  if (e != hipSuccess) { resnmtf_set_create_error(std::string("hipStreamCreate: ") + hipGetErrorString(e)); return RESNMTF_ERR_HIP; }
+  DeviceBuffer owner;                      // (freed on every path out; hipFree waits for the stream's work)
+  e = hipMalloc(&owner.p, std::max<size_t>(bytes, 8));
+  double* buf = static_cast<double*>(owner.p);
+  if (e != hipSuccess) {
+    (void)hipStreamDestroy(st);
+    resnmtf_set_create_error(std::string("fp64_run: ") + hipGetErrorString(e) + " (" + std::to_string(bytes) + " bytes asked for)");
+    return e == hipErrorOutOfMemory ? RESNMTF_ERR_ALLOC : RESNMTF_ERR_HIP;
+  }
+  auto fail = [&](hipError_t err) {
+    (void)hipStreamSynchronize(st);
+    (void)hipStreamDestroy(st);
+    resnmtf_set_create_error(std::string("fp64_run: ") + hipGetErrorString(err));
+    return RESNMTF_ERR_HIP;
+  };
+  const int V = L.V, k = L.k;
+  e = hipMemsetAsync(buf, 0, bytes, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return fail(e);
+
+  // upload: the padded images view by view (one staging vector), then the initial state and the maps
+  {
+    std::vector<double> img;
+    for (int v = 0; v < V && e == hipSuccess; ++v) {
+      const F64View& w = L.vw[v];
+      const double* x = j.x[v];
+      const size_t n = (size_t)w.n, m = (size_t)w.m;
+      img.assign(w.ldn * w.mpad, 0.0);
+      for (size_t c = 0; c < m; ++c) std::memcpy(&img[c * w.ldn], x + c * n, n * sizeof(double));
+      e = hipMemcpy(buf + w.x, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice);
+      if (e != hipSuccess) break;
+      img.assign(w.ldm * w.npad, 0.0);
+      for (size_t c = 0; c < m; ++c)
+        for (size_t i = 0; i < n; ++i) img[c + i * w.ldm] = x[i + c * n];
+      e = hipMemcpy(buf + w.xt, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice);
+    }
+  }
+  if (e != hipSuccess) return fail(e);
+  std::vector<double> host(L.out_end - L.out_begin, 0.0);
+  auto at = [&](size_t off) { return host.data() + (off - L.out_begin); };
+  for (int v = 0; v < V; ++v) {
+    const size_t n = (size_t)L.vw[v].n, m = (size_t)L.vw[v].m;
+    std::memcpy(at(L.vw[v].f), j.f0[v], n * k * sizeof(double));
+    std::memcpy(at(L.vw[v].g), j.g0[v], m * k * sizeof(double));
+    std::memcpy(at(L.s + (size_t)v * k * k), j.s0[v], (size_t)k * k * sizeof(double));
+    for (int c = 0; c < k; ++c) {                                         // explicit init: colSums (R/update_steps.r:55-56)
+      double cf = 0.0, cg = 0.0;
+      if (!j.lambda0[v]) for (size_t i = 0; i < n; ++i) cf += j.f0[v][i + (size_t)c * n];
+      if (!j.mu0[v]) for (size_t i = 0; i < m; ++i) cg += j.g0[v][i + (size_t)c * m];
+      *at(L.lam + (size_t)v * k + c) = j.lambda0[v] ? j.lambda0[v][c] : cf;
+      *at(L.mu + (size_t)v * k + c) = j.mu0[v] ? j.mu0[v][c] : cg;
+    }
+  }
+  e = hipMemcpy(buf + L.out_begin, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return fail(e);
+  if (L.total > L.maps) {
+    std::vector<int> maps((L.total - L.maps) * 2, -1);
+    const size_t ibase = L.maps * 2;
+    for (int v = 0; v < V; ++v)
+      for (int w = 0; w < V; ++w) {
+        if (L.rmap[v][w] >= 0)
+          for (int p = 0; p < j.row_count[v][w]; ++p) maps[(size_t)L.rmap[v][w] - ibase + j.row_idx_v[v][w][p]] = j.row_idx_w[v][w][p];
+        if (L.cmap[v][w] >= 0)
+          for (int p = 0; p < j.col_count[v][w]; ++p) maps[(size_t)L.cmap[v][w] - ibase + j.col_idx_v[v][w][p]] = j.col_idx_w[v][w][p];
+      }
+    e = hipMemcpy(buf + L.maps, maps.data(), maps.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(e);
+  }
+
+  // ||X_v||_F^2 as norm()^2 (R/main.r:48)
+  for (int v = 0; v < V; ++v) {
+    const F64View& w = L.vw[v];
+    const size_t total = w.ldn * w.mpad;
+    const int nb = (int)((total + F64_NORM_CHUNK - 1) / F64_NORM_CHUNK);
+    hipLaunchKernelGGL(fp64_norm_kernel, dim3(nb), dim3(F64_THREADS), 0, st, (const double*)(buf + w.x), total, buf + L.spart);
+    F64KKArgs kk{};
+    kk.mode = F64_KK_NORM; kk.k = k; kk.V = V; kk.v = v; kk.part_a = buf + L.spart; kk.nblk_a = nb;
+    kk.S = buf + L.s; kk.norms = buf + L.norms; kk.errs = buf + L.errs; kk.err_out = buf + L.err;
+    hipLaunchKernelGGL(fp64_kk_kernel, dim3(1), dim3(F64_THREADS), 0, st, kk);
+  }
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail(e);
+
+  // the loop of R/main.r:53-80.  A fixed count is enqueued whole; in convergence mode the 8-byte mean error comes back
+  // after every sweep and the host applies the stop rule, so the state on the device is the stop sweep's own
+  int it = 0;
+  double err_temp = 0.0;
+  while (it < cap) {
+    fp64_enqueue_sweep(st, j, L, buf, it);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(e);
+    ++it;
+    if (j.n_iters == 0) {
+      double mean = 0.0;
+      e = hipMemcpyAsync(&mean, buf + L.err + (it - 1), sizeof(double), hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess) e = hipStreamSynchronize(st);
+      if (e != hipSuccess) return fail(e);
+      const double diff = std::fabs(mean - err_temp);
+      err_temp = mean;
+      if (!(diff > tol)) break;
+    }
+  }
+  for (int v = 0; v < V; ++v) {            // normalisation_check (R/utils.r:176-195)
+    const F64View& w = L.vw[v];
+    const size_t total = ((size_t)w.n + w.m + k) * k;
+    const int nb = (int)std::min<size_t>((total + F64_THREADS - 1) / F64_THREADS, 4096);
+    hipLaunchKernelGGL(fp64_normalise_kernel, dim3(nb), dim3(F64_THREADS), 0, st, buf + w.f, buf + w.g,
+                       buf + L.s + (size_t)v * k * k, (const double*)(buf + L.cf + (size_t)v * k),
+                       (const double*)(buf + L.cg + (size_t)v * k), w.n, w.m, k);
+  }
+  e = hipGetLastError();
+  std::vector<double> errs((size_t)it);
+  if (e == hipSuccess) e = hipMemcpyAsync(host.data(), buf + L.out_begin, host.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && it > 0) e = hipMemcpyAsync(errs.data(), buf + L.err, errs.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return fail(e);
+  (void)hipStreamDestroy(st);
+  for (int v = 0; v < V; ++v) {
+    std::memcpy(j.f_out[v], at(L.vw[v].f), (size_t)L.vw[v].n * k * sizeof(double));
+    std::memcpy(j.g_out[v], at(L.vw[v].g), (size_t)L.vw[v].m * k * sizeof(double));
+    std::memcpy(j.s_out[v], at(L.s + (size_t)v * k * k), (size_t)k * k * sizeof(double));
+    std::memcpy(j.lambda_out[v], at(L.lam + (size_t)v * k), (size_t)k * sizeof(double));
+    std::memcpy(j.mu_out[v], at(L.mu + (size_t)v * k), (size_t)k * sizeof(double));
+  }
+  for (int t = 0; t < it; ++t) j.all_error[t] = errs[(size_t)t];
+  *j.iters_done = it;
+  return RESNMTF_OK;
+}
+
+}  // extern "C"

@@ -42,6 +42,7 @@
 #include "resnmtf_group.hip.inc"
 #include "resnmtf_bisil.hip.inc"
 #include "resnmtf_split_tu.h"
+#include "resnmtf_internal.h"
 #ifdef RESNMTF_SPLIT_TU      // product build: the k <= 16 pass lives in resnmtf_pass_k16.hip (its own scheduling strategy)
 #define RESNMTF_EXTERN(NW, UNR, XG, MA) extern template __global__ void pass_kernel<1, NW, UNR, XG, MA, 0>(PassArgs, KKFArgs, KKSArgs);
 RESNMTF_PASS_K16_LIST(RESNMTF_EXTERN)
@@ -4448,12 +4449,22 @@ bool all_finite(const double* a, size_t n) {
   return true;
 }
 
+// what an entry point that takes a resnmtf_group_job allows: resnmtf_group_run (one workgroup per job) and
+// resnmtf_fp64_run (device-wide) share every check below and differ in these
+struct GroupJobLimits {
+  int max_k;
+  const char* k_text;
+  long long max_view_entries;            // 0 = no cap on n * m
+};
+const GroupJobLimits kGroupLimits = {RESNMTF_GROUP_MAX_K, "k must be in [1, 32]", RESNMTF_GROUP_MAX_VIEW_ENTRIES};
+const GroupJobLimits kFp64Limits = {RESNMTF_MAX_K, "k must be in [1, 64]", 0};
+
 // a job's host checks; a message on refusal, nullptr when it is fine
-const char* check_group_job(const resnmtf_group_job& j, int max_iters) {
+const char* check_group_job(const resnmtf_group_job& j, int max_iters, const GroupJobLimits& lim) {
   if (j.struct_size != (int)sizeof(resnmtf_group_job)) return "resnmtf_group_job struct_size mismatch";
   const int V = j.n_views, k = j.k;
   if (V < 1 || V > RESNMTF_GROUP_MAX_VIEWS) return "n_views must be in [1, 8]";
-  if (k < 1 || k > RESNMTF_GROUP_MAX_K) return "k must be in [1, 32]";
+  if (k < 1 || k > lim.max_k) return lim.k_text;
   if (j.n_iters < 0) return "n_iters must be >= 0 (0 = run to convergence)";
   const int sweeps = j.n_iters > 0 ? std::min(j.n_iters, max_iters) : max_iters;
   if (!j.all_error || !j.iters_done || j.err_capacity < sweeps) return "all_error / iters_done NULL or err_capacity below the sweeps allowed";
@@ -4461,7 +4472,7 @@ const char* check_group_job(const resnmtf_group_job& j, int max_iters) {
     const int n = j.n_rows[v], m = j.n_cols[v];
     if (n < 1 || m < 1) return "view dimensions must be positive";
     if (k > n || k > m) return "k exceeds a view dimension (R/utils.r:444,449)";
-    if ((long long)n * m > RESNMTF_GROUP_MAX_VIEW_ENTRIES) return "a view has more than 2^22 entries";
+    if (lim.max_view_entries > 0 && (long long)n * m > lim.max_view_entries) return "a view has more than 2^22 entries";
     if (!j.x[v] || !j.f0[v] || !j.s0[v] || !j.g0[v]) return "x / f0 / s0 / g0 is NULL";
     if (!j.f_out[v] || !j.s_out[v] || !j.g_out[v] || !j.lambda_out[v] || !j.mu_out[v]) return "an output pointer is NULL";
     if (!all_finite(j.x[v], (size_t)n * m)) return "x has a non-finite entry";
@@ -4504,7 +4515,7 @@ int resnmtf_group_run(int device_id, int n_jobs, const resnmtf_group_job* jobs, 
   if (max_iters < 1) return bad("max_iters must be >= 1");
   if (!std::isfinite(tol)) return bad("tol must be finite");
   for (int q = 0; q < n_jobs; ++q)
-    if (const char* why = check_group_job(jobs[q], max_iters)) return bad("job " + std::to_string(q) + ": " + why);
+    if (const char* why = check_group_job(jobs[q], max_iters, kGroupLimits)) return bad("job " + std::to_string(q) + ": " + why);
   if (n_jobs == 0) return RESNMTF_OK;
 
   // one buffer: [descriptors | outputs (F, G, S, lambda, mu per job) | sweep counts | X, X^T | row / column maps |
@@ -4688,6 +4699,14 @@ int resnmtf_group_run(int device_id, int n_jobs, const resnmtf_group_job* jobs, 
   }
   return RESNMTF_OK;
 }
+
+// ---- device-wide fp64 factorisation: the entry points live in csrc/resnmtf_fp64.hip (a translation unit of its own,
+// so that its kernels sit in a code object of their own); these two hand it the checks and the error text it shares
+// with resnmtf_group_run (csrc/resnmtf_internal.h) ----
+}  // extern "C"
+const char* resnmtf_check_fp64_job(const resnmtf_group_job& j, int max_iters) { return check_group_job(j, max_iters, kFp64Limits); }
+void resnmtf_set_create_error(const std::string& text) { g_create_error = text; }
+extern "C" {
 
 int resnmtf_factor_device_ptr(resnmtf_handle* h, int v, int which, void** ptr, size_t* bytes) {
   if (int rc = check_view(h, v)) return rc;

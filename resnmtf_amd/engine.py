@@ -72,6 +72,78 @@ def jsd_stages(cols, pairs, sorted: bool = True, stats: bool = True, dens: bool 
     return got
 
 
+def _fill_group_job(j, p, q: int, max_iters: int, keep: list) -> dict:
+    """Fill one ``resnmtf_group_job`` (``j``) from the problem dict ``p`` (problem ``q`` of its call; the layout
+    ``group_run`` documents) and return the output arrays it points to.  ``keep`` collects every array the struct
+    points into: the caller holds it until the library call has returned."""
+    j.struct_size = C.sizeof(_lib.GroupJob)
+    data = [_f64_colmajor(x) for x in p["data"]]
+    V, k = len(data), int(p["k"])
+    if V > _lib.GROUP_MAX_VIEWS:
+        raise ValueError(f"problem {q}: at most {_lib.GROUP_MAX_VIEWS} views")
+    if any(x.ndim != 2 for x in data):
+        raise ValueError(f"problem {q}: every view must be a matrix")
+    for key in ("init_f", "init_s", "init_g", "init_lam", "init_mu"):
+        if p.get(key) is not None and len(p[key]) != V:
+            raise ValueError(f"problem {q}: {key} must hold one entry per view")
+    j.n_views, j.k = V, k
+    n_iters = p.get("n_iters")
+    j.n_iters = 0 if n_iters is None else int(n_iters)
+    cap = max(1, min(int(n_iters), int(max_iters)) if n_iters else int(max_iters))
+    out = {"f": [], "s": [], "g": [], "lambda": [], "mu": [], "all_error": np.empty(cap), "iters": np.zeros(1, np.int32)}
+    for v, x in enumerate(data):
+        n, m = x.shape
+        j.n_rows[v], j.n_cols[v] = n, m
+        try:                                  # (the library reads n k, k k and m k doubles through these pointers)
+            arrs = [x, _f64_colmajor(p["init_f"][v], (n, k)), _f64_colmajor(p["init_s"][v], (k, k)),
+                    _f64_colmajor(p["init_g"][v], (m, k))]
+        except ValueError as exc:
+            raise ValueError(f"problem {q}, view {v}: initial factor: {exc}") from None
+        for name, a in zip(("x", "f0", "s0", "g0"), arrs):
+            getattr(j, name)[v] = _dp(a)
+        keep.extend(arrs)
+        for name, key in (("lambda0", "init_lam"), ("mu0", "init_mu")):
+            vals = p.get(key)
+            if vals is not None and vals[v] is not None:
+                a = np.ascontiguousarray(vals[v], dtype=np.float64)
+                if a.shape != (k,):
+                    raise ValueError(f"problem {q}, view {v}: {key} must have k = {k} entries, got shape {a.shape}")
+                keep.append(a)
+                getattr(j, name)[v] = _dp(a)
+        for key, shape in (("f", (n, k)), ("s", (k, k)), ("g", (m, k)), ("lambda", (k,)), ("mu", (k,))):
+            out[key].append(np.zeros(shape, dtype=np.float64, order="F"))
+        j.f_out[v], j.s_out[v], j.g_out[v] = _dp(out["f"][v]), _dp(out["s"][v]), _dp(out["g"][v])
+        j.lambda_out[v], j.mu_out[v] = _dp(out["lambda"][v]), _dp(out["mu"][v])
+    for name in ("phi", "xi", "psi"):
+        if p.get(name) is not None:
+            a = _f64_colmajor(p[name], (V, V))
+            keep.append(a)
+            setattr(j, name, _dp(a))
+    for key, cnt, iv_name, iw_name in (("row_pairs", j.row_count, j.row_idx_v, j.row_idx_w),
+                                       ("col_pairs", j.col_count, j.col_idx_v, j.col_idx_w)):
+        pairs = p.get(key)
+        for v in range(V):
+            for w in range(V):
+                if pairs is None or v == w or pairs[v][w] is None or pairs[v][w][0] is None:
+                    cnt[v][w] = -1
+                    continue
+                iv = np.ascontiguousarray(pairs[v][w][0], dtype=np.int32)
+                iw = np.ascontiguousarray(pairs[v][w][1], dtype=np.int32)
+                if iv.shape != iw.shape or iv.ndim != 1:
+                    raise ValueError(f"problem {q}: index pairs ({v}, {w}) must be two vectors of one length")
+                keep.extend([iv, iw])
+                cnt[v][w] = len(iv)
+                iv_name[v][w], iw_name[v][w] = _ip(iv), _ip(iw)
+    j.all_error, j.err_capacity, j.iters_done = _dp(out["all_error"]), cap, _ip(out["iters"])
+    return out
+
+
+def _group_result(out: dict) -> dict:
+    it = int(out["iters"][0])
+    return {"f": out["f"], "s": out["s"], "g": out["g"], "lambda": out["lambda"], "mu": out["mu"],
+            "all_error": out["all_error"][:it].copy(), "iters": it}
+
+
 def group_run(problems, tol: float = 1.0e-6, max_iters: int = 100000, device_id: int = 0) -> list:
     """Many small factorisations in one call (``resnmtf_group_run``: one workgroup per job, fp64 throughout).
 
@@ -84,78 +156,41 @@ def group_run(problems, tol: float = 1.0e-6, max_iters: int = 100000, device_id:
     lib = _lib.load()
     problems = list(problems)
     jobs = (_lib.GroupJob * max(1, len(problems)))()
-    keep, outs = [], []
-    for q, p in enumerate(problems):
-        j = jobs[q]
-        j.struct_size = C.sizeof(_lib.GroupJob)
-        data = [_f64_colmajor(x) for x in p["data"]]
-        V, k = len(data), int(p["k"])
-        if V > _lib.GROUP_MAX_VIEWS:
-            raise ValueError(f"problem {q}: at most {_lib.GROUP_MAX_VIEWS} views")
-        if any(x.ndim != 2 for x in data):
-            raise ValueError(f"problem {q}: every view must be a matrix")
-        for key in ("init_f", "init_s", "init_g", "init_lam", "init_mu"):
-            if p.get(key) is not None and len(p[key]) != V:
-                raise ValueError(f"problem {q}: {key} must hold one entry per view")
-        j.n_views, j.k = V, k
-        n_iters = p.get("n_iters")
-        j.n_iters = 0 if n_iters is None else int(n_iters)
-        cap = max(1, min(int(n_iters), int(max_iters)) if n_iters else int(max_iters))
-        out = {"f": [], "s": [], "g": [], "lambda": [], "mu": [], "all_error": np.empty(cap), "iters": np.zeros(1, np.int32)}
-        for v, x in enumerate(data):
-            n, m = x.shape
-            j.n_rows[v], j.n_cols[v] = n, m
-            try:                                  # (the library reads n k, k k and m k doubles through these pointers)
-                arrs = [x, _f64_colmajor(p["init_f"][v], (n, k)), _f64_colmajor(p["init_s"][v], (k, k)),
-                        _f64_colmajor(p["init_g"][v], (m, k))]
-            except ValueError as exc:
-                raise ValueError(f"problem {q}, view {v}: initial factor: {exc}") from None
-            for name, a in zip(("x", "f0", "s0", "g0"), arrs):
-                getattr(j, name)[v] = _dp(a)
-            keep.extend(arrs)
-            for name, key in (("lambda0", "init_lam"), ("mu0", "init_mu")):
-                vals = p.get(key)
-                if vals is not None and vals[v] is not None:
-                    a = np.ascontiguousarray(vals[v], dtype=np.float64)
-                    if a.shape != (k,):
-                        raise ValueError(f"problem {q}, view {v}: {key} must have k = {k} entries, got shape {a.shape}")
-                    keep.append(a)
-                    getattr(j, name)[v] = _dp(a)
-            for key, shape in (("f", (n, k)), ("s", (k, k)), ("g", (m, k)), ("lambda", (k,)), ("mu", (k,))):
-                out[key].append(np.zeros(shape, dtype=np.float64, order="F"))
-            j.f_out[v], j.s_out[v], j.g_out[v] = _dp(out["f"][v]), _dp(out["s"][v]), _dp(out["g"][v])
-            j.lambda_out[v], j.mu_out[v] = _dp(out["lambda"][v]), _dp(out["mu"][v])
-        for name in ("phi", "xi", "psi"):
-            if p.get(name) is not None:
-                a = _f64_colmajor(p[name], (V, V))
-                keep.append(a)
-                setattr(j, name, _dp(a))
-        for key, cnt, iv_name, iw_name in (("row_pairs", j.row_count, j.row_idx_v, j.row_idx_w),
-                                           ("col_pairs", j.col_count, j.col_idx_v, j.col_idx_w)):
-            pairs = p.get(key)
-            for v in range(V):
-                for w in range(V):
-                    if pairs is None or v == w or pairs[v][w] is None or pairs[v][w][0] is None:
-                        cnt[v][w] = -1
-                        continue
-                    iv = np.ascontiguousarray(pairs[v][w][0], dtype=np.int32)
-                    iw = np.ascontiguousarray(pairs[v][w][1], dtype=np.int32)
-                    if iv.shape != iw.shape or iv.ndim != 1:
-                        raise ValueError(f"problem {q}: index pairs ({v}, {w}) must be two vectors of one length")
-                    keep.extend([iv, iw])
-                    cnt[v][w] = len(iv)
-                    iv_name[v][w], iw_name[v][w] = _ip(iv), _ip(iw)
-        j.all_error, j.err_capacity, j.iters_done = _dp(out["all_error"]), cap, _ip(out["iters"])
-        outs.append(out)
+    keep = []
+    outs = [_fill_group_job(jobs[q], p, q, max_iters, keep) for q, p in enumerate(problems)]
     rc = lib.resnmtf_group_run(int(device_id), len(problems), jobs, float(tol), int(max_iters))
     if rc != _lib.OK:
         raise ResnmtfError(rc, (lib.resnmtf_last_error(None) or b"").decode())
-    res = []
-    for out in outs:
-        it = int(out["iters"][0])
-        res.append({"f": out["f"], "s": out["s"], "g": out["g"], "lambda": out["lambda"], "mu": out["mu"],
-                    "all_error": out["all_error"][:it].copy(), "iters": it})
-    return res
+    return [_group_result(out) for out in outs]
+
+
+def fp64_run(problem, tol: float = 1.0e-6, max_iters: int = 100000, device_id: int = 0) -> dict:
+    """One factorisation in fp64 at any size (``resnmtf_fp64_run``: the arithmetic of ``group_run``, spread over the
+    whole device).  ``problem`` is one problem dict of ``group_run`` -- without its caps: k up to
+    64, no limit on n * m -- and the result is one element of its list.  Bad input is refused before any device work
+    (``ResnmtfError``), a job the device cannot hold with ``RESNMTF_ERR_ALLOC`` and its byte count."""
+    lib = _lib.load()
+    job = _lib.GroupJob()
+    keep = []
+    out = _fill_group_job(job, problem, 0, max_iters, keep)
+    rc = lib.resnmtf_fp64_run(int(device_id), C.byref(job), float(tol), int(max_iters))
+    if rc != _lib.OK:
+        raise ResnmtfError(rc, (lib.resnmtf_last_error(None) or b"").decode())
+    return _group_result(out)
+
+
+def fp64_plan(n_rows: int, n_cols: int, k: int) -> dict:
+    """The launch geometry ``fp64_run`` takes for an ``n_rows`` x ``n_cols`` view at ``k`` (``resnmtf_fp64_plan``; no
+    device work): ``{"kp", "xg": (row tiles, splits, indices per split), "xtf": ..., "resid": (64-row tiles, column
+    splits, columns per split), "ld": (leading dimension of the fp64 image of X, of X^T)}``.  A split count above 1: partial
+    products in a slab, summed in split order."""
+    lib = _lib.load()
+    out = (C.c_int * _lib.FP64_PLAN_INTS)()
+    rc = lib.resnmtf_fp64_plan(int(n_rows), int(n_cols), int(k), out)
+    if rc != _lib.OK:
+        raise ResnmtfError(rc, (lib.resnmtf_last_error(None) or b"").decode())
+    v = list(out)
+    return {"kp": v[0], "xg": tuple(v[1:4]), "xtf": tuple(v[4:7]), "resid": tuple(v[7:10]), "ld": tuple(v[10:12])}
 
 
 class Engine:
