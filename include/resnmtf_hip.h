@@ -880,6 +880,53 @@ int resnmtf_fp64_run(int device_id, const resnmtf_group_job* job, double tol, in
 #define RESNMTF_FP64_PLAN_INTS 12
 int resnmtf_fp64_plan(int n_rows, int n_cols, int k, int* out);
 
+/*
+ * resnmtf_fp64_run with sparse views, stored sparse and streamed sparse.  View v is sparse when
+ * sp->view[v].col_ptr is not NULL: the 0-based canonical CSC of the PRE-PROCESSED view (what R/utils.r:416-422 leaves of
+ * it: non-negative, column-normalised; the reference densifies a sparse Matrix with as.matrix, R/utils.r:416-419, and so
+ * factorises the matrix these arrays stand for).  job->x[v] must then be NULL; a view with both, or with neither, is
+ * refused.  Dense and sparse views mix freely; with sp NULL or no sparse view the call is resnmtf_fp64_run, bit for bit.
+ * Everything else about the job -- limits, outputs, n_iters, tol, max_iters, restrictions, maps, refusal texts -- is
+ * resnmtf_fp64_run's.
+ * A sparse view keeps no fp64 image on the device: a CSC copy for X^T F and a CSR copy for X G (built on the host by a
+ * counting sort, a row's entries in ascending column order), int64 pointers, int32 indices, fp64 values -- 24 bytes per
+ * stored entry plus the pointers.  update_f / update_g (R/update_steps.r:141-207) get their products from an fp64 SpMM
+ * over a row-major copy of the other factor: one lane group per line, fma in ascending entry order; a line longer than
+ * 256 entries is cut into at most 16 pieces of equal length, summed in piece order.  update_s (R/update_steps.r:220-240)
+ * is unchanged.  calculate_error (R/utils.r:157-166) of a sparse view is the trace form
+ *   (||X||^2 - 2 <S, (F^T X) G> + <((F^T F) S) (G^T G), S>) / ||X||^2
+ * from the k x k matrices of the view's own sweep step (no pass over X; within 1e-15 of the explicit residual); a dense
+ * view of the same job keeps the explicit residual.  ||X||^2 is summed over the stored values (R/main.r:48).  Same
+ * determinism as resnmtf_fp64_run: no atomics, orders fixed by the structure and k, two calls give the same bits.
+ * Refused before any device work (RESNMTF_ERR_INVALID): an sp->struct_size mismatch, and per sparse view what
+ * resnmtf_set_view_csc refuses on the host -- col_ptr[0] != 0, col_ptr not monotone, a row index out of range or not
+ * strictly increasing within a column, a non-finite or negative value, NULL row_idx / values.  The one device buffer is
+ * sized before any launch and refused with RESNMTF_ERR_ALLOC and its byte count.  A refusal writes no output.
+ */
+typedef struct resnmtf_fp64_sparse_view {   /* 0-based canonical CSC of the pre-processed view; all NULL = dense view */
+  const long long* col_ptr;                 /* n_cols + 1 */
+  const int* row_idx;                       /* strictly ascending within a column */
+  const double* values;                     /* finite, >= 0 */
+} resnmtf_fp64_sparse_view;
+typedef struct resnmtf_fp64_sparse {
+  int struct_size;                          /* sizeof the struct */
+  resnmtf_fp64_sparse_view view[RESNMTF_GROUP_MAX_VIEWS];
+} resnmtf_fp64_sparse;
+int resnmtf_fp64_run_sparse(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp,
+                            double tol, int max_iters);
+
+/*
+ * How resnmtf_fp64_run_sparse streams an n_rows x n_cols sparse view of this structure at k -- a function of the
+ * structure and k alone, never of the device.  out[RESNMTF_FP64_SPARSE_PLAN_INTS]: the padded k (16 / 32 / 48 / 64);
+ * for the X G product (lines = rows) the split count, the entries per piece and the longest line; the same three for
+ * X^T F (lines = columns); last the lines one 64-lane wave owns (64 / padded k, one above 32).  There is one form: every
+ * line piece is owned by one lane group.  A split count above 1: pieces in a slab, summed in piece order by the update.
+ * Refused (RESNMTF_ERR_INVALID): out NULL, a dimension below 1, k outside [1, 64] or above a dimension, and the
+ * structural refusals of resnmtf_fp64_run_sparse.  No device work.
+ */
+#define RESNMTF_FP64_SPARSE_PLAN_INTS 8
+int resnmtf_fp64_sparse_plan(int n_rows, int n_cols, int k, const long long* col_ptr, const int* row_idx, int* out);
+
 /* ---- phase-level entry points (views sharded one-per-GPU; host does the exchange) ---- */
 
 /* Which image of X the streaming passes of view v use after its upload: *uses_2byte = 0 (f32 images), 1 (fp16) or

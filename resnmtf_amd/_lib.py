@@ -110,6 +110,19 @@ class GroupJob(C.Structure):
     ]
 
 
+FP64_SPARSE_PLAN_INTS = 8  # RESNMTF_FP64_SPARSE_PLAN_INTS
+
+
+class Fp64SparseView(C.Structure):
+    """``resnmtf_fp64_sparse_view`` (include/resnmtf_hip.h): the canonical CSC of one view; all NULL = a dense view."""
+    _fields_ = [("col_ptr", C.POINTER(C.c_longlong)), ("row_idx", _ip), ("values", _dp)]
+
+
+class Fp64Sparse(C.Structure):
+    """``resnmtf_fp64_sparse`` (include/resnmtf_hip.h)."""
+    _fields_ = [("struct_size", C.c_int), ("view", Fp64SparseView * _MV)]
+
+
 class DeviceMatrix(C.Structure):
     """``resnmtf_device_matrix`` (include/resnmtf_hip.h): a strided matrix in device memory, strides in elements."""
     _fields_ = [("ptr", C.c_void_p), ("dtype", C.c_int), ("row_stride", C.c_longlong), ("col_stride", C.c_longlong)]
@@ -167,6 +180,8 @@ SIGNATURES = {
     "resnmtf_group_run": (C.c_int, [C.c_int, C.c_int, C.POINTER(GroupJob), C.c_double, C.c_int]),
     "resnmtf_fp64_run": (C.c_int, [C.c_int, C.POINTER(GroupJob), C.c_double, C.c_int]),
     "resnmtf_fp64_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip]),
+    "resnmtf_fp64_run_sparse": (C.c_int, [C.c_int, C.POINTER(GroupJob), C.POINTER(Fp64Sparse), C.c_double, C.c_int]),
+    "resnmtf_fp64_sparse_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong), _ip, _ip]),
     "resnmtf_bisil": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_bisil_sparse": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_bisil_device": (C.c_int, [_h, C.c_int, C.c_int, _dm, _dm, C.c_int, C.c_void_p, C.c_void_p, _dp, C.c_void_p]),

@@ -105,7 +105,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
                    host_init: bool = False, return_init: bool = False, score_bisil: bool = False,
                    spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False,
                    sparse_on_device: bool = False, output: str = "numpy", init_lm=None, return_state: bool = False,
-                   post_on_device: bool = False, precision: str = "f32"):
+                   post_on_device: bool = False, precision: str = "f32", fp64_sparse: bool = False):
     """``res_nmtf_inner`` (``R/main.r:32-140``).
 
     ``data``: list of pre-processed (non-negative, column-normalised) matrices; ``row_indices[v][w]``
@@ -186,6 +186,13 @@ def res_nmtf_inner(data, row_indices, column_indices,
     device work with a ``NotImplementedError`` naming the flag: ``spurious=True`` with ``spurious_on_device``,
     ``score_bisil``, ``output="torch"``, ``post_on_device``, ``return_state``, sparse views, views or factors in device
     memory.
+
+    ``fp64_sparse`` (keyword-only opt-in; a no-op with ``precision="f32"``): with
+    ``precision="fp64"``, ``scipy.sparse`` views (a CPU sparse tensor is taken as its SciPy matrix) are accepted,
+    validated as on the f32 route, and stored and streamed sparse (``resnmtf_fp64_run_sparse``); dense and sparse views
+    mix.  The initial state is the explicit factors (with ``init_lm``) or the device's SVD initialisation through a
+    short-lived sparse engine; ``host_init=True`` without explicit factors raises ``NotImplementedError``, as on the f32
+    route.  Sparse tensors in device memory stay refused, and without the flag sparse views are refused as before.
     """
     if precision not in ("f32", "fp64"):
         raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
@@ -195,7 +202,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
                                     device_id=device_id, max_iters=max_iters, seed=seed, engine_opts=engine_opts,
                                     host_init=host_init, return_init=return_init, score_bisil=score_bisil,
                                     spurious_on_device=spurious_on_device, output=output, init_lm=init_lm,
-                                    return_state=return_state, post_on_device=post_on_device)
+                                    return_state=return_state, post_on_device=post_on_device, fp64_sparse=fp64_sparse)
     device_views.check_output(output)
     _check_post_on_device(post_on_device, output)
     data = _views(data, device_id)
@@ -287,7 +294,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
 def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init_g, k_vec, phi, xi, psi, n_iters, spurious,
                          distance, no_clusts, *, row_names, col_names, device_id, max_iters, seed, engine_opts, host_init,
                          return_init, score_bisil, spurious_on_device, output, init_lm, return_state, post_on_device,
-                         runner: Optional[Callable] = None):
+                         fp64_sparse: bool = False, runner: Optional[Callable] = None):
     """``res_nmtf_inner(precision="fp64")``: the checks of the f32 call, the refusals of what needs a live handle, the
     initial state, then one ``engine.fp64_run`` (``runner`` replaces it: a test hook)."""
     def refuse(flag):
@@ -306,13 +313,22 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
     _check_distance(distance)
     views = []
     for v, d in enumerate(_as_list(data)):
-        d = device_views.host_or_device(d, f"view {v}")
+        d = device_views.host_or_device(d, f"view {v}")      # (a CPU sparse tensor: its scipy.sparse matrix)
+        if fp64_sparse and sparse.is_sparse(d):              # opt-in: stored and streamed sparse (resnmtf_fp64_run_sparse)
+            d = sparse.canonical_csc(d)
+            sparse.validate(d, f"view {v}")
+            views.append(d)
+            continue
         if sparse.is_sparse_view(d) or device_views.is_sparse_tensor(d):
             refuse(f"sparse views (view {v})")
         if device_views.is_device_view(d):
             refuse(f"views in device memory (view {v})")
         views.append(np.asarray(d, dtype=np.float64))
     data, n_v = views, len(views)
+    is_sp = [sparse.is_sparse(d) for d in data]
+    if any(is_sp) and host_init and (init_f is None or init_g is None or init_s is None):
+        raise NotImplementedError("host_init=True (NumPy's dense SVD) is not available for sparse views; the device "
+                                  "initialisation (host_init=False) works on them")
     if k_vec is None:
         raise ValueError("k_vec is required")
     k_vec = [int(k) for k in np.atleast_1d(k_vec)]
@@ -342,7 +358,9 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
     if init_f is None and host_init:
         init_f, init_s, init_g, lam, mu = svd_init(data, k_vec, seed)
     elif init_f is None:                          # the device's own SVD initialisation: the start the f32 call reports
-        eng = Engine([d.shape[0] for d in data], [d.shape[1] for d in data], k_vec, device_id=device_id, **(engine_opts or {}))
+        more = {"nnz": [d.nnz if sp else None for d, sp in zip(data, is_sp)]} if any(is_sp) else {}      # (a short-lived sparse engine)
+        eng = Engine([d.shape[0] for d in data], [d.shape[1] for d in data], k_vec, device_id=device_id, **more,
+                     **(engine_opts or {}))
         try:
             _load_engine(eng, data, None, None, None, None, None, phi, xi, psi, row_names, col_names, row_indices,
                          column_indices, seed=seed)

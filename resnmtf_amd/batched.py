@@ -214,19 +214,30 @@ def _check_group_limits(i: int, data, k: int, limits: GroupLimits = GROUPED_LIMI
 
 
 def prepare_grouped_job(job: Job, i: int = 0, pre_processed: bool = False, init=None,
-                        limits: GroupLimits = GROUPED_LIMITS) -> dict:
+                        limits: GroupLimits = GROUPED_LIMITS, allow_sparse: bool = False) -> dict:
     """The problem ``engine.group_run`` receives for one job, prepared as ``run_job`` prepares it for the engine:
     names, shared-name index pairs, symmetrised restrictions, ``check_data`` unless ``pre_processed``, and the initial
     factors ``init`` = (F, S, G[, lambda, mu]) per view or, when None, ``api.svd_init(data, k_vec, job.seed)`` on the
     host.  Sparse views and jobs over the kernel's limits are refused here; ``limits`` names the path and its caps
-    (``GROUPED_LIMITS``, the default, or ``FP64_LIMITS`` for ``engine.fp64_run``)."""
-    if any(sparse.is_sparse_view(d) for d in job.data):
-        raise NotImplementedError(f"job {i}: the {limits.path} path takes dense views only; run sparse views with run_jobs")
-    data = [np.asarray(d, dtype=np.float64) for d in job.data]
+    (``GROUPED_LIMITS``, the default, or ``FP64_LIMITS`` for ``engine.fp64_run``).  ``allow_sparse`` (opt-in, the fp64
+    path alone: DESIGN.md section 22): ``scipy.sparse`` views pass -- canonical CSC copies, validated
+    (``sparse.validate``) and pre-processed as on the f32 route -- and need an explicit ``init`` (NumPy's dense SVD is
+    not available for them); sparse tensors in device memory stay refused."""
+    sparse_views = [d for d in job.data if sparse.is_sparse_view(d)]
+    if sparse_views:
+        if not (allow_sparse and all(sparse.is_sparse(d) for d in sparse_views)):
+            raise NotImplementedError(f"job {i}: the {limits.path} path takes dense views only; run sparse views with run_jobs")
+        if init is None:
+            raise NotImplementedError(f"job {i}: the host SVD initialisation (NumPy's dense SVD) is not available for sparse "
+                                      "views; pass init = (F, S, G[, lambda, mu])")
+    data = [sparse.canonical_csc(d) if sparse.is_sparse(d) else np.asarray(d, dtype=np.float64) for d in job.data]
     if any(d.ndim != 2 for d in data):
         raise ValueError(f"job {i}: every view must be a matrix")
     n_v, k = len(data), int(job.k_val)
     _check_group_limits(i, data, k, limits)
+    for v, d in enumerate(data):
+        if sparse.is_sparse(d):
+            sparse.validate(d, f"view {v}")
     p = prepare(data, job.phi, job.xi, job.psi, job.row_names, job.col_names, normalise=not pre_processed, symmetrise=True)
     data = p.data
     if init is None:
@@ -288,13 +299,15 @@ def run_jobs_grouped(jobs: Sequence[Job], device_id: int = 0, pre_processed: boo
 
 
 def run_job_fp64(job: Job, device_id: int = 0, pre_processed: bool = False, init=None, max_iters: int = 100000,
-                 runner: Optional[Callable] = None) -> dict:
+                 runner: Optional[Callable] = None, sparse: bool = False) -> dict:
     """One job through the device-wide fp64 path (``engine.fp64_run``): prepared as
     ``prepare_grouped_job`` prepares it -- dense views only, at most 8 views, 1 <= k <= 64, no cap on n * m -- from
     ``init`` = (F, S, G[, lambda, mu]) per view or, when None, ``api.svd_init`` on the host with the job's seed.
     Returns the keys ``run_job`` returns (``bisil`` None).  ``runner(problem, tol=, max_iters=, device_id=)`` replaces
-    ``engine.fp64_run`` (a test hook); every refusal comes before it is called."""
-    problem = prepare_grouped_job(job, 0, pre_processed, init, limits=FP64_LIMITS)
+    ``engine.fp64_run`` (a test hook); every refusal comes before it is called.  ``sparse`` (opt-in, DESIGN.md section
+    22): ``scipy.sparse`` views are accepted and reach the runner as canonical CSC matrices, pre-processed as on the f32
+    route; they need an explicit ``init``."""
+    problem = prepare_grouped_job(job, 0, pre_processed, init, limits=FP64_LIMITS, allow_sparse=bool(sparse))
     out = (runner or _engine.fp64_run)(problem, tol=1.0e-6, max_iters=max_iters, device_id=device_id)
     rcs, ccs = zip(*[_binary_clusters(f, g, s) for f, g, s in zip(out["f"], out["g"], out["s"])])
     return inner_result(out["f"], out["s"], out["g"], np.asarray(out["all_error"], dtype=np.float64), job.n_iters,

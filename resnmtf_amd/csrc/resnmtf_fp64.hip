@@ -1,5 +1,6 @@
-// Device-wide fp64 factorisation: the host side of resnmtf_fp64_run and resnmtf_fp64_plan, and --
-// through resnmtf_fp64.hip.inc -- their kernels.  A translation unit of its own: the kernels get a code object of their
+// Device-wide fp64 factorisation (DESIGN.md sections 21 and 22): the host side of resnmtf_fp64_run, resnmtf_fp64_run_sparse
+// and their two plan queries, and -- through resnmtf_fp64.hip.inc and resnmtf_fp64_sparse.hip.inc (sparse views) -- their
+// kernels.  A translation unit of its own: the kernels get a code object of their
 // own and leave the main unit's device code as it was.  The job checks and the error text are the main unit's
 // (resnmtf_internal.h): this entry and resnmtf_group_run refuse the same things with the same texts.
 #include <hip/hip_runtime.h>
@@ -14,6 +15,7 @@
 #include "resnmtf_hip.h"
 #include "resnmtf_internal.h"
 #include "resnmtf_fp64.hip.inc"
+#include "resnmtf_fp64_sparse.hip.inc"
 
 namespace {
 struct DeviceBuffer {
@@ -29,16 +31,29 @@ struct F64View {
   size_t ldm = 0, npad = 0;                // X^T: ldm x npad
   size_t x = 0, xt = 0, f = 0, g = 0;      // offsets in doubles
   F64ProductPlan xg, xtf, res;
+  // a sparse view (section 22) keeps no images: CSC (columns of X, for X^T F) and CSR (rows, for X G), offsets in doubles
+  bool sparse = false;
+  size_t nnz = 0;
+  size_t cptr = 0, cval = 0, cidx = 0, rptr = 0, rval = 0, ridx = 0;
+  F64SparsePlan sxg, sxtf;                 // how X G cuts its rows, X^T F its columns
 };
 
-// the job's one device buffer, in doubles: [X, X^T per view | F, G per view | S | lambda | mu] (uploaded) | the k x k work
-// area | column sums, norms, errors | two scratch matrices | product slab | partials | error history | maps (ints)
+// what the layout needs to know of a sparse view: its stored entries and its longest row and column
+struct F64SparseShape {
+  bool sparse = false;
+  size_t nnz = 0;
+  long long longest_row = 0, longest_col = 0;
+};
+
+// the job's one device buffer, in doubles: [X, X^T per dense view, CSC and CSR per sparse view | F, G per view | S |
+// lambda | mu] (uploaded) | the k x k work area | column sums, norms, errors | two scratch matrices | product slab |
+// partials | error history | with a sparse view: the k x k slots of every view, the row-major operand | maps (ints)
 struct F64Layout {
   int V = 0, k = 0, KP = 0, cap = 0;
   F64View vw[RESNMTF_GROUP_MAX_VIEWS];
   size_t out_begin = 0, out_end = 0;       // F, G, S, lambda, mu: one contiguous region, read back at the end
   size_t s = 0, lam = 0, mu = 0, kk = 0, cf = 0, cg = 0, norms = 0, errs = 0, scratch = 0, scratch2 = 0, slab = 0;
-  size_t part0 = 0, part1 = 0, colf = 0, colg = 0, spart = 0, err = 0, maps = 0, total = 0;
+  size_t part0 = 0, part1 = 0, colf = 0, colg = 0, spart = 0, err = 0, slots = 0, ot = 0, maps = 0, total = 0;
   long long rmap[RESNMTF_GROUP_MAX_VIEWS][RESNMTF_GROUP_MAX_VIEWS];     // int offsets from the buffer base, -1 = NA
   long long cmap[RESNMTF_GROUP_MAX_VIEWS][RESNMTF_GROUP_MAX_VIEWS];
 };
@@ -52,24 +67,43 @@ bool fp64_shapes_ok(const resnmtf_group_job& j) {
   return true;
 }
 
-// bytes of the two images of every view, the bulk of the buffer, without overflow
-long double fp64_image_bytes(const resnmtf_group_job& j) {
+// bytes of the two images of every dense view, the bulk of the buffer, without overflow
+long double fp64_image_bytes(const resnmtf_group_job& j, unsigned sparse_views) {
   long double b = 0;
   for (int v = 0; v < j.n_views; ++v) {
+    if ((sparse_views >> v) & 1u) continue;
     const long double n = j.n_rows[v], m = j.n_cols[v];
     b += ((n + 63) * (m + 63) + (m + 63) * (n + 63)) * sizeof(double);
   }
   return b;
 }
 
-void fp64_layout(const resnmtf_group_job& j, int cap, F64Layout& L) {
+void fp64_layout(const resnmtf_group_job& j, int cap, F64Layout& L, const F64SparseShape* shapes = nullptr) {
   L.V = j.n_views; L.k = j.k; L.KP = f64_kp(j.k); L.cap = cap;
   const size_t k = (size_t)L.k, V = (size_t)L.V;
   size_t off = 0, big = 1, slab = 1, gram_blk = 1, col_blk = 1, spart = 1;
+  bool any_sparse = false;
   for (int v = 0; v < L.V; ++v) {
     F64View& w = L.vw[v];
     w.n = j.n_rows[v]; w.m = j.n_cols[v];
     w.ldn = f64_ld(w.n); w.mpad = rup(w.m, F64_JC); w.ldm = f64_ld(w.m); w.npad = rup(w.n, F64_JC);
+    if (shapes && shapes[v].sparse) {          // 24 bytes per stored entry plus the pointers; no image, no residual
+      any_sparse = true;
+      w.sparse = true; w.nnz = shapes[v].nnz;
+      const size_t idx_doubles = (w.nnz + 1) / 2;
+      w.cptr = off; off += (size_t)w.m + 1;
+      w.cval = off; off += w.nnz;
+      w.cidx = off; off += idx_doubles;
+      w.rptr = off; off += (size_t)w.n + 1;
+      w.rval = off; off += w.nnz;
+      w.ridx = off; off += idx_doubles;
+      w.sxg = f64_plan_sparse(shapes[v].longest_row);
+      w.sxtf = f64_plan_sparse(shapes[v].longest_col);
+      big = std::max(big, (size_t)std::max(w.n, w.m));
+      slab = std::max(slab, std::max((size_t)w.sxg.splits * w.ldn, (size_t)w.sxtf.splits * w.ldm) * (size_t)L.KP);
+      spart = std::max(spart, (w.nnz + F64_NORM_CHUNK - 1) / F64_NORM_CHUNK);
+      continue;
+    }
     w.x = off; off += w.ldn * w.mpad;
     w.xt = off; off += w.ldm * w.npad;
     w.xg = f64_plan_product(w.n, w.m);
@@ -105,6 +139,10 @@ void fp64_layout(const resnmtf_group_job& j, int cap, F64Layout& L) {
   L.colg = off; off += col_blk * k;
   L.spart = off; off += spart;
   L.err = off; off += (size_t)cap;
+  if (any_sparse) {
+    L.slots = off; off += V * 3 * k * k;
+    L.ot = off; off += big * (size_t)L.KP;
+  }
   L.maps = off;
   size_t ioff = off * 2;
   for (int v = 0; v < RESNMTF_GROUP_MAX_VIEWS; ++v)
@@ -168,10 +206,17 @@ void fp64_enqueue_sweep(hipStream_t st, const resnmtf_group_job& j, const F64Lay
       kk.mode = g_form ? F64_KK_SIDE_G : F64_KK_SIDE_F;
       kk.part_a = buf + L.part0; kk.nblk_a = gram_blk;
       hipLaunchKernelGGL(fp64_kk_kernel, dim3(1), dim3(F64_THREADS), 0, st, kk);
-      fp64_product(st, KP, g_form ? w.xtf : w.xg, buf + (g_form ? w.xt : w.x), g_form ? w.ldm : w.ldn, O, m, k,
-                   g_form ? w.npad : w.mpad, buf + L.slab);
+      if (w.sparse) {                        // the operand row-major, then the SpMM over the lines of this side
+        fp64_spmm(st, KP, g_form ? w.sxtf : w.sxg, reinterpret_cast<const long long*>(buf + (g_form ? w.cptr : w.rptr)),
+                  reinterpret_cast<const int*>(buf + (g_form ? w.cidx : w.ridx)), buf + (g_form ? w.cval : w.rval), O, m, k,
+                  buf + L.ot, n, g_form ? w.ldm : w.ldn, buf + L.slab);
+      } else {
+        fp64_product(st, KP, g_form ? w.xtf : w.xg, buf + (g_form ? w.xt : w.x), g_form ? w.ldm : w.ldn, O, m, k,
+                     g_form ? w.npad : w.mpad, buf + L.slab);
+      }
       F64UpdArgs u{};
-      u.n = n; u.k = k; u.KP = KP; u.V = V; u.nsplit = g_form ? w.xtf.splits : w.xg.splits;
+      u.n = n; u.k = k; u.KP = KP; u.V = V;
+      u.nsplit = w.sparse ? (g_form ? w.sxtf.splits : w.sxg.splits) : (g_form ? w.xtf.splits : w.xg.splits);
       u.ldx = g_form ? w.ldm : w.ldn;
       u.slab = buf + L.slab; u.P = P; u.xo = buf + L.scratch; u.ps = buf + L.scratch2;
       u.S = buf + L.s + (size_t)v * k * k; u.W = kkB; u.lm = g_form ? kk.mu : kk.lam;
@@ -197,6 +242,13 @@ void fp64_enqueue_sweep(hipStream_t st, const resnmtf_group_job& j, const F64Lay
     gs.A[1] = G; gs.B[1] = G; gs.part[1] = buf + L.part1;
     gs.len = w.m; gs.k = k;
     hipLaunchKernelGGL(fp64_gram_kernel, dim3(gblk, 2), dim3(F64_THREADS), 0, st, gs);
+    if (w.sparse) {                          // the three k x k matrices of the trace-form error, before update_s reuses kkA
+      F64KKSparseArgs ks{};
+      ks.k = k; ks.V = V; ks.v = v;
+      ks.part_a = buf + L.part0; ks.nblk_a = gblk; ks.part_b = buf + L.part1; ks.nblk_b = gblk;
+      ks.kkA = kkA; ks.slot = buf + L.slots + (size_t)v * 3 * k * k;
+      fp64_kk_sparse(st, false, ks);
+    }
     kk.mode = F64_KK_S;
     kk.part_a = buf + L.part0; kk.nblk_a = gblk; kk.part_b = buf + L.part1; kk.nblk_b = gblk;
     kk.col_f = buf + L.colf; kk.nblk_f = (w.n + F64_UPD_ROWS - 1) / F64_UPD_ROWS;
@@ -208,6 +260,15 @@ void fp64_enqueue_sweep(hipStream_t st, const resnmtf_group_job& j, const F64Lay
   }
   for (int v = 0; v < V; ++v) {            // calculate_error (R/utils.r:157-166) of every view, after all updates (:316-319)
     const F64View& w = L.vw[v];
+    if (w.sparse) {                          // the trace form, all k x k (section 22): no pass over X
+      F64KKSparseArgs ks{};
+      ks.k = k; ks.V = V; ks.v = v;
+      ks.slot = buf + L.slots + (size_t)v * 3 * k * k; ks.t0 = kkB; ks.t1 = kkC;
+      ks.S = buf + L.s + (size_t)v * k * k;
+      ks.norms = buf + L.norms; ks.errs = buf + L.errs; ks.err_out = buf + L.err + it;
+      fp64_kk_sparse(st, true, ks);
+      continue;
+    }
     hipLaunchKernelGGL(fp64_fs_kernel, dim3((w.n + F64_UPD_ROWS - 1) / F64_UPD_ROWS), dim3(F64_UPD_ROWS), 0, st,
                        (const double*)(buf + w.f), (const double*)(buf + L.s + (size_t)v * k * k), w.n, k, buf + L.scratch2);
     fp64_resid(st, KP, w.res, buf + w.x, w.ldn, buf + L.scratch2, w.n, buf + w.g, w.m, k, buf + L.spart);
@@ -218,9 +279,86 @@ void fp64_enqueue_sweep(hipStream_t st, const resnmtf_group_job& j, const F64Lay
     hipLaunchKernelGGL(fp64_kk_kernel, dim3(1), dim3(F64_THREADS), 0, st, kk);
   }
 }
+// what resnmtf_set_view_csc refuses on the host, for one n x m CSC structure (values NULL: the structure alone); the
+// text of the refusal or "" when it is fine, and then the view's stored entries, longest row and longest column
+std::string fp64_check_csc(int n, int m, const long long* col_ptr, const int* row_idx, const double* values,
+                           F64SparseShape& sh) {
+  if (!col_ptr || !row_idx) return "col_ptr / row_idx is NULL";
+  if (col_ptr[0] != 0) return "col_ptr[0] must be 0 (0-based CSC)";
+  for (int c = 0; c < m; ++c)
+    if (col_ptr[c + 1] < col_ptr[c]) return "col_ptr is not monotone (column " + std::to_string(c) + ")";
+  std::vector<long long> per_row((size_t)n, 0);
+  long long longest_col = 0;
+  for (int c = 0; c < m; ++c) {
+    longest_col = std::max(longest_col, col_ptr[c + 1] - col_ptr[c]);
+    for (long long e = col_ptr[c]; e < col_ptr[c + 1]; ++e) {
+      const int i = row_idx[e];
+      if (i < 0 || i >= n) return "row index out of range in column " + std::to_string(c);
+      if (e > col_ptr[c] && i <= row_idx[e - 1])
+        return "row indices must be strictly increasing within a column (column " + std::to_string(c) + ")";
+      if (values) {
+        if (!std::isfinite(values[e])) return "non-finite entry in column " + std::to_string(c);
+        if (values[e] < 0.0) return "negative entry in column " + std::to_string(c);
+      }
+      ++per_row[(size_t)i];
+    }
+  }
+  sh.sparse = true;
+  sh.nnz = (size_t)col_ptr[m];
+  sh.longest_col = longest_col;
+  sh.longest_row = n > 0 ? *std::max_element(per_row.begin(), per_row.end()) : 0;
+  return "";
+}
+
+// the CSR copy of a checked CSC structure by a counting sort: a row's entries in ascending column order
+void fp64_csr_from_csc(int n, int m, const long long* col_ptr, const int* row_idx, const double* values,
+                       std::vector<long long>& rp, std::vector<int>& ci, std::vector<double>& rv) {
+  const size_t nnz = (size_t)col_ptr[m];
+  rp.assign((size_t)n + 1, 0); ci.resize(nnz); rv.resize(nnz);
+  for (size_t e = 0; e < nnz; ++e) ++rp[(size_t)row_idx[e] + 1];
+  for (int i = 0; i < n; ++i) rp[(size_t)i + 1] += rp[(size_t)i];
+  std::vector<long long> next(rp.begin(), rp.end() - 1);
+  for (int c = 0; c < m; ++c)
+    for (long long e = col_ptr[c]; e < col_ptr[c + 1]; ++e) {
+      const size_t p = (size_t)next[(size_t)row_idx[e]]++;
+      ci[p] = c; rv[p] = values[e];
+    }
+}
+
+int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp, double tol, int max_iters);
 }  // namespace
 
 extern "C" {
+
+int resnmtf_fp64_sparse_plan(int n_rows, int n_cols, int k, const long long* col_ptr, const int* row_idx, int* out) {
+  auto bad = [](const std::string& msg) { resnmtf_set_create_error(msg); return RESNMTF_ERR_INVALID; };
+  if (!out) return bad("out is NULL");
+  if (n_rows < 1 || n_cols < 1) return bad("view dimensions must be positive");
+  if (k < 1 || k > RESNMTF_MAX_K) return bad("k must be in [1, 64]");
+  if (k > n_rows || k > n_cols) return bad("k exceeds a view dimension (R/utils.r:444,449)");
+  F64SparseShape sh;
+  const std::string why = fp64_check_csc(n_rows, n_cols, col_ptr, row_idx, nullptr, sh);
+  if (!why.empty()) return bad(why);
+  const int KP = f64_kp(k);
+  const F64SparsePlan xg = f64_plan_sparse(sh.longest_row), xtf = f64_plan_sparse(sh.longest_col);
+  const int vals[RESNMTF_FP64_SPARSE_PLAN_INTS] = {KP, xg.splits, (int)xg.piece, (int)xg.longest, xtf.splits, (int)xtf.piece,
+                                                   (int)xtf.longest, 64 / f64_sp_group(KP)};
+  std::memcpy(out, vals, sizeof(vals));
+  return RESNMTF_OK;
+}
+
+int resnmtf_fp64_run(int device_id, const resnmtf_group_job* job, double tol, int max_iters) {
+  return fp64_run_impl(device_id, job, nullptr, tol, max_iters);
+}
+
+int resnmtf_fp64_run_sparse(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp, double tol,
+                            int max_iters) {
+  if (sp && sp->struct_size != (int)sizeof(resnmtf_fp64_sparse)) {
+    resnmtf_set_create_error("resnmtf_fp64_sparse struct_size mismatch");
+    return RESNMTF_ERR_INVALID;
+  }
+  return fp64_run_impl(device_id, job, sp, tol, max_iters);
+}
 
 int resnmtf_fp64_plan(int n_rows, int n_cols, int k, int* out) {
   auto bad = [](const std::string& msg) { resnmtf_set_create_error(msg); return RESNMTF_ERR_INVALID; };
@@ -236,15 +374,24 @@ int resnmtf_fp64_plan(int n_rows, int n_cols, int k, int* out) {
   return RESNMTF_OK;
 }
 
-int resnmtf_fp64_run(int device_id, const resnmtf_group_job* job, double tol, int max_iters) {
+}  // extern "C"
+
+namespace {
+// resnmtf_fp64_run (sp == nullptr) and resnmtf_fp64_run_sparse: one body.  Without a sparse view every step below is
+// resnmtf_fp64_run's own -- the same layout, the same launches, the same bits.
+int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp, double tol, int max_iters) {
   auto bad = [](const std::string& msg) { resnmtf_set_create_error(msg); return RESNMTF_ERR_INVALID; };
   if (!job) return bad("job is NULL");
   if (max_iters < 1) return bad("max_iters must be >= 1");
   if (!std::isfinite(tol)) return bad("tol must be finite");
   const resnmtf_group_job& j = *job;
+  unsigned sparse_views = 0;                // bit v: view v comes as CSC arrays
+  if (sp)
+    for (int v = 0; v < RESNMTF_GROUP_MAX_VIEWS; ++v)
+      if (sp->view[v].col_ptr) sparse_views |= 1u << v;
   // a shape no device holds is refused on its byte count before the data behind it is read
   if (fp64_shapes_ok(j)) {
-    const long double img = fp64_image_bytes(j);
+    const long double img = fp64_image_bytes(j, sparse_views);
     if (img >= 0x1p58L) {
       char text[160];
       std::snprintf(text, sizeof(text), "fp64_run: more than %.0Lf bytes asked for (the fp64 images of the views alone)", img);
@@ -252,11 +399,20 @@ int resnmtf_fp64_run(int device_id, const resnmtf_group_job* job, double tol, in
       return RESNMTF_ERR_ALLOC;
     }
   }
-  if (const char* why = resnmtf_check_fp64_job(j, max_iters)) return bad(why);
+  if (const char* why = resnmtf_check_fp64_job(j, max_iters, sparse_views)) return bad(why);
+  if (sparse_views >> j.n_views) return bad("a sparse view is given beyond n_views");
+  F64SparseShape shapes[RESNMTF_GROUP_MAX_VIEWS];
+  for (int v = 0; v < j.n_views; ++v) {
+    if (!((sparse_views >> v) & 1u)) continue;
+    const resnmtf_fp64_sparse_view& c = sp->view[v];
+    if (!c.values) return bad("view " + std::to_string(v) + ": values is NULL");
+    const std::string why = fp64_check_csc(j.n_rows[v], j.n_cols[v], c.col_ptr, c.row_idx, c.values, shapes[v]);
+    if (!why.empty()) return bad("view " + std::to_string(v) + ": " + why);
+  }
 
   const int cap = j.n_iters > 0 ? std::min(j.n_iters, max_iters) : max_iters;
   F64Layout L;
-  fp64_layout(j, cap, L);
+  fp64_layout(j, cap, L, sparse_views ? shapes : nullptr);
   const size_t bytes = L.total * sizeof(double);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { resnmtf_set_create_error("no HIP device"); return RESNMTF_ERR_NO_DEVICE; }
@@ -298,6 +454,22 @@ int resnmtf_fp64_run(int device_id, const resnmtf_group_job* job, double tol, in
     std::vector<double> img;
     for (int v = 0; v < V && e == hipSuccess; ++v) {
       const F64View& w = L.vw[v];
+      if (w.sparse) {                        // the CSC arrays as given, and the CSR copy built here
+        const resnmtf_fp64_sparse_view& c = sp->view[v];
+        std::vector<long long> rp;
+        std::vector<int> ci;
+        std::vector<double> rv;
+        fp64_csr_from_csc(w.n, w.m, c.col_ptr, c.row_idx, c.values, rp, ci, rv);
+        e = hipMemcpy(buf + w.cptr, c.col_ptr, ((size_t)w.m + 1) * sizeof(long long), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(buf + w.rptr, rp.data(), rp.size() * sizeof(long long), hipMemcpyHostToDevice);
+        if (w.nnz > 0) {
+          if (e == hipSuccess) e = hipMemcpy(buf + w.cval, c.values, w.nnz * sizeof(double), hipMemcpyHostToDevice);
+          if (e == hipSuccess) e = hipMemcpy(buf + w.cidx, c.row_idx, w.nnz * sizeof(int), hipMemcpyHostToDevice);
+          if (e == hipSuccess) e = hipMemcpy(buf + w.rval, rv.data(), w.nnz * sizeof(double), hipMemcpyHostToDevice);
+          if (e == hipSuccess) e = hipMemcpy(buf + w.ridx, ci.data(), w.nnz * sizeof(int), hipMemcpyHostToDevice);
+        }
+        continue;
+      }
       const double* x = j.x[v];
       const size_t n = (size_t)w.n, m = (size_t)w.m;
       img.assign(w.ldn * w.mpad, 0.0);
@@ -345,9 +517,12 @@ int resnmtf_fp64_run(int device_id, const resnmtf_group_job* job, double tol, in
   // ||X_v||_F^2 as norm()^2 (R/main.r:48)
   for (int v = 0; v < V; ++v) {
     const F64View& w = L.vw[v];
-    const size_t total = w.ldn * w.mpad;
+    // (a sparse view: over the CSC values, the image's non-zeros in entry order)
+    const size_t total = w.sparse ? w.nnz : w.ldn * w.mpad;
     const int nb = (int)((total + F64_NORM_CHUNK - 1) / F64_NORM_CHUNK);
-    hipLaunchKernelGGL(fp64_norm_kernel, dim3(nb), dim3(F64_THREADS), 0, st, (const double*)(buf + w.x), total, buf + L.spart);
+    if (nb > 0)
+      hipLaunchKernelGGL(fp64_norm_kernel, dim3(nb), dim3(F64_THREADS), 0, st, (const double*)(buf + (w.sparse ? w.cval : w.x)),
+                         total, buf + L.spart);
     F64KKArgs kk{};
     kk.mode = F64_KK_NORM; kk.k = k; kk.V = V; kk.v = v; kk.part_a = buf + L.spart; kk.nblk_a = nb;
     kk.S = buf + L.s; kk.norms = buf + L.norms; kk.errs = buf + L.errs; kk.err_out = buf + L.err;
@@ -401,5 +576,4 @@ int resnmtf_fp64_run(int device_id, const resnmtf_group_job* job, double tol, in
   *j.iters_done = it;
   return RESNMTF_OK;
 }
-
-}  // extern "C"
+}  // namespace

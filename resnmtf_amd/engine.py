@@ -12,6 +12,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
+from . import sparse as _sparse
 from ._lib import ResnmtfError
 
 
@@ -72,12 +73,16 @@ def jsd_stages(cols, pairs, sorted: bool = True, stats: bool = True, dens: bool 
     return got
 
 
-def _fill_group_job(j, p, q: int, max_iters: int, keep: list) -> dict:
+def _fill_group_job(j, p, q: int, max_iters: int, keep: list, sp=None) -> dict:
     """Fill one ``resnmtf_group_job`` (``j``) from the problem dict ``p`` (problem ``q`` of its call; the layout
     ``group_run`` documents) and return the output arrays it points to.  ``keep`` collects every array the struct
-    points into: the caller holds it until the library call has returned."""
+    points into: the caller holds it until the library call has returned.  ``sp`` (``fp64_run`` alone): the
+    ``resnmtf_fp64_sparse`` that receives the canonical CSC arrays of every ``scipy.sparse`` view, whose ``x`` stays
+    NULL; without it such a view is a ``ValueError``."""
     j.struct_size = C.sizeof(_lib.GroupJob)
-    data = [_f64_colmajor(x) for x in p["data"]]
+    data = [_sparse.canonical_csc(x) if _sparse.is_sparse(x) else _f64_colmajor(x) for x in p["data"]]
+    if sp is None and any(_sparse.is_sparse(x) for x in data):
+        raise ValueError(f"problem {q}: a sparse view (scipy.sparse) is taken by fp64_run alone")
     V, k = len(data), int(p["k"])
     if V > _lib.GROUP_MAX_VIEWS:
         raise ValueError(f"problem {q}: at most {_lib.GROUP_MAX_VIEWS} views")
@@ -99,7 +104,14 @@ def _fill_group_job(j, p, q: int, max_iters: int, keep: list) -> dict:
                     _f64_colmajor(p["init_g"][v], (m, k))]
         except ValueError as exc:
             raise ValueError(f"problem {q}, view {v}: initial factor: {exc}") from None
-        for name, a in zip(("x", "f0", "s0", "g0"), arrs):
+        if _sparse.is_sparse(x):              # the CSC arrays go into sp; j.x[v] stays NULL
+            csc = [np.ascontiguousarray(x.indptr, dtype=np.int64), np.ascontiguousarray(x.indices, dtype=np.int32),
+                   np.ascontiguousarray(x.data, dtype=np.float64)]
+            sp.view[v].col_ptr = csc[0].ctypes.data_as(C.POINTER(C.c_longlong))
+            sp.view[v].row_idx, sp.view[v].values = _ip(csc[1]), _dp(csc[2])
+            keep.extend(csc)
+            arrs = arrs[1:]
+        for name, a in zip(("f0", "s0", "g0") if _sparse.is_sparse(x) else ("x", "f0", "s0", "g0"), arrs):
             getattr(j, name)[v] = _dp(a)
         keep.extend(arrs)
         for name, key in (("lambda0", "init_lam"), ("mu0", "init_mu")):
@@ -168,15 +180,47 @@ def fp64_run(problem, tol: float = 1.0e-6, max_iters: int = 100000, device_id: i
     """One factorisation in fp64 at any size (``resnmtf_fp64_run``: the arithmetic of ``group_run``, spread over the
     whole device).  ``problem`` is one problem dict of ``group_run`` -- without its caps: k up to
     64, no limit on n * m -- and the result is one element of its list.  Bad input is refused before any device work
-    (``ResnmtfError``), a job the device cannot hold with ``RESNMTF_ERR_ALLOC`` and its byte count."""
+    (``ResnmtfError``), a job the device cannot hold with ``RESNMTF_ERR_ALLOC`` and its byte count.
+
+    A ``scipy.sparse`` matrix in ``problem["data"][v]`` is a SPARSE view: taken as its canonical
+    CSC (``sparse.canonical_csc``, a copy), already pre-processed, stored and streamed sparse on the device
+    (``resnmtf_fp64_run_sparse``); dense and sparse views mix freely.  A problem without one calls ``resnmtf_fp64_run``
+    exactly as before."""
     lib = _lib.load()
     job = _lib.GroupJob()
     keep = []
-    out = _fill_group_job(job, problem, 0, max_iters, keep)
-    rc = lib.resnmtf_fp64_run(int(device_id), C.byref(job), float(tol), int(max_iters))
+    if any(_sparse.is_sparse(x) for x in problem["data"]):
+        sp = _lib.Fp64Sparse()
+        sp.struct_size = C.sizeof(_lib.Fp64Sparse)
+        out = _fill_group_job(job, problem, 0, max_iters, keep, sp=sp)
+        rc = lib.resnmtf_fp64_run_sparse(int(device_id), C.byref(job), C.byref(sp), float(tol), int(max_iters))
+    else:
+        out = _fill_group_job(job, problem, 0, max_iters, keep)
+        rc = lib.resnmtf_fp64_run(int(device_id), C.byref(job), float(tol), int(max_iters))
     if rc != _lib.OK:
         raise ResnmtfError(rc, (lib.resnmtf_last_error(None) or b"").decode())
     return _group_result(out)
+
+
+def fp64_sparse_plan(x, k: int) -> dict:
+    """How ``fp64_run`` streams the sparse view ``x`` (a ``scipy.sparse`` matrix, taken as its canonical CSC) at ``k``
+    (``resnmtf_fp64_sparse_plan``; no device work): ``{"kp", "xg": (splits, entries per piece, longest row), "xtf":
+    (splits, entries per piece, longest column), "lines_per_wave"}`` -- a function of the structure and k alone.  A
+    split count above 1: the lines are cut into that many pieces, summed in piece order."""
+    lib = _lib.load()
+    c = _sparse.canonical_csc(x)
+    ptr = np.ascontiguousarray(c.indptr, dtype=np.int64)
+    idx = np.ascontiguousarray(c.indices, dtype=np.int32)
+    return _sparse_plan_raw(lib, c.shape[0], c.shape[1], k, ptr, idx)
+
+
+def _sparse_plan_raw(lib, n_rows: int, n_cols: int, k: int, ptr: np.ndarray, idx: np.ndarray) -> dict:
+    out = (C.c_int * _lib.FP64_SPARSE_PLAN_INTS)()
+    rc = lib.resnmtf_fp64_sparse_plan(int(n_rows), int(n_cols), int(k), ptr.ctypes.data_as(C.POINTER(C.c_longlong)), _ip(idx), out)
+    if rc != _lib.OK:
+        raise ResnmtfError(rc, (lib.resnmtf_last_error(None) or b"").decode())
+    v = list(out)
+    return {"kp": v[0], "xg": tuple(v[1:4]), "xtf": tuple(v[4:7]), "lines_per_wave": v[7]}
 
 
 def fp64_plan(n_rows: int, n_cols: int, k: int) -> dict:
