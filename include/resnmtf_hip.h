@@ -927,6 +927,44 @@ int resnmtf_fp64_run_sparse(int device_id, const resnmtf_group_job* job, const r
 #define RESNMTF_FP64_SPARSE_PLAN_INTS 8
 int resnmtf_fp64_sparse_plan(int n_rows, int n_cols, int k, const long long* col_ptr, const int* row_idx, int* out);
 
+/*
+ * resnmtf_fp64_run_sparse with views, initial factors and results in DEVICE memory.  With dev NULL
+ * the call is resnmtf_fp64_run_sparse: the same launches, the same bits.  Every result is BIT FOR BIT that of the host
+ * route on the same values: widening fp32 / fp16 / bf16 to fp64 is exact, the two padded images of a device view are byte
+ * for byte those the host loops build, and the column sums keep the host loop's order.
+ *   x[v]        a dense view in device memory: a resnmtf_device_matrix, its ptr NULL when not given, of any of the four dtypes and
+ *               any strides >= 0 (0: an expanded tensor); job->x[v] must then be NULL.  One kernel reads it once and writes
+ *               both images.  Host dense views, device dense views and host sparse views mix in one job; a view given in
+ *               two places, or in none, is refused.  The values of a device view are not validated.
+ *   f0 / s0 / g0 [v]   initial factors in device memory, n x k, k x k, m x k: all three of a view, or none of them (then the
+ *               job's host pointers are read); with them job->f0[v], s0[v], g0[v], lambda0[v] and mu0[v] must be NULL.
+ *   lambda0 / mu0 [v]  k x 1 (col_stride is not read); only beside device factors.  ptr NULL: the column sums of F0 / G0,
+ *               one accumulator per column from 0.0 over ascending rows, as the host route sums them.
+ *   f_out ... mu_out   device double*, column-major contiguous (as resnmtf_get_factors_device writes): all five of every
+ *               view of the job, or none.  With them the job's five host output pointers may be NULL (one that is set is
+ *               still written) and nothing of size n or m is downloaded.  all_error and iters_done stay host pointers.
+ *   state_f ... state_mu   optional, all five of every view or none: the RAW state after the last sweep, before
+ *               normalisation_check, copied device to device on the run's stream -- what a later call resumes from.
+ *   stream      as for resnmtf_set_view_device: an event is recorded there and the run's stream waits for it.  The call
+ *               blocks until every output is written, so the sources may be freed on return.
+ * Refused before any allocation or launch (RESNMTF_ERR_INVALID), the text naming the view and the field: a struct_size
+ * mismatch, a device view or factor given beyond n_views, the both / neither / partial cases above, an unknown dtype, a
+ * negative stride, a pointer that is not device memory of device_id, a matrix that reaches beyond its allocation.
+ */
+typedef struct resnmtf_fp64_device {
+  int struct_size;                                         /* sizeof the struct */
+  void* stream;
+  resnmtf_device_matrix x[RESNMTF_GROUP_MAX_VIEWS];
+  resnmtf_device_matrix f0[RESNMTF_GROUP_MAX_VIEWS], s0[RESNMTF_GROUP_MAX_VIEWS], g0[RESNMTF_GROUP_MAX_VIEWS];
+  resnmtf_device_matrix lambda0[RESNMTF_GROUP_MAX_VIEWS], mu0[RESNMTF_GROUP_MAX_VIEWS];
+  double *f_out[RESNMTF_GROUP_MAX_VIEWS], *s_out[RESNMTF_GROUP_MAX_VIEWS], *g_out[RESNMTF_GROUP_MAX_VIEWS];
+  double *lambda_out[RESNMTF_GROUP_MAX_VIEWS], *mu_out[RESNMTF_GROUP_MAX_VIEWS];
+  double *state_f[RESNMTF_GROUP_MAX_VIEWS], *state_s[RESNMTF_GROUP_MAX_VIEWS], *state_g[RESNMTF_GROUP_MAX_VIEWS];
+  double *state_lambda[RESNMTF_GROUP_MAX_VIEWS], *state_mu[RESNMTF_GROUP_MAX_VIEWS];
+} resnmtf_fp64_device;
+int resnmtf_fp64_run_device(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp,
+                            const resnmtf_fp64_device* dev, double tol, int max_iters);
+
 /* ---- phase-level entry points (views sharded one-per-GPU; host does the exchange) ---- */
 
 /* Which image of X the streaming passes of view v use after its upload: *uses_2byte = 0 (f32 images), 1 (fp16) or

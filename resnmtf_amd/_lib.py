@@ -130,6 +130,16 @@ class DeviceMatrix(C.Structure):
 
 _dm = C.POINTER(DeviceMatrix)
 
+
+class Fp64Device(C.Structure):
+    """``resnmtf_fp64_device`` (include/resnmtf_hip.h): what ``resnmtf_fp64_run_device`` reads from, and writes to, device
+    memory -- views and initial factors as ``DeviceMatrix``, results and raw state as device ``double*``."""
+    _fields_ = ([("struct_size", C.c_int), ("stream", C.c_void_p)] +
+                [(name, DeviceMatrix * _MV) for name in ("x", "f0", "s0", "g0", "lambda0", "mu0")] +
+                [(name, C.c_void_p * _MV) for name in ("f_out", "s_out", "g_out", "lambda_out", "mu_out",
+                                                      "state_f", "state_s", "state_g", "state_lambda", "state_mu")])
+
+
 # name -> (restype, argtypes); must list every symbol include/resnmtf_hip.h declares
 SIGNATURES = {
     "resnmtf_abi_version": (C.c_int, []),
@@ -182,6 +192,8 @@ SIGNATURES = {
     "resnmtf_fp64_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip]),
     "resnmtf_fp64_run_sparse": (C.c_int, [C.c_int, C.POINTER(GroupJob), C.POINTER(Fp64Sparse), C.c_double, C.c_int]),
     "resnmtf_fp64_sparse_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong), _ip, _ip]),
+    "resnmtf_fp64_run_device": (C.c_int, [C.c_int, C.POINTER(GroupJob), C.POINTER(Fp64Sparse), C.POINTER(Fp64Device), C.c_double,
+                                          C.c_int]),
     "resnmtf_bisil": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_bisil_sparse": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_bisil_device": (C.c_int, [_h, C.c_int, C.c_int, _dm, _dm, C.c_int, C.c_void_p, C.c_void_p, _dp, C.c_void_p]),

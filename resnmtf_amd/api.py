@@ -105,7 +105,8 @@ def res_nmtf_inner(data, row_indices, column_indices,
                    host_init: bool = False, return_init: bool = False, score_bisil: bool = False,
                    spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False,
                    sparse_on_device: bool = False, output: str = "numpy", init_lm=None, return_state: bool = False,
-                   post_on_device: bool = False, precision: str = "f32", fp64_sparse: bool = False):
+                   post_on_device: bool = False, precision: str = "f32", fp64_sparse: bool = False,
+                   fp64_device: bool = False):
     """``res_nmtf_inner`` (``R/main.r:32-140``).
 
     ``data``: list of pre-processed (non-negative, column-normalised) matrices; ``row_indices[v][w]``
@@ -193,6 +194,16 @@ def res_nmtf_inner(data, row_indices, column_indices,
     mix.  The initial state is the explicit factors (with ``init_lm``) or the device's SVD initialisation through a
     short-lived sparse engine; ``host_init=True`` without explicit factors raises ``NotImplementedError``, as on the f32
     route.  Sparse tensors in device memory stay refused, and without the flag sparse views are refused as before.
+
+    ``fp64_device`` (keyword-only opt-in; a no-op with ``precision="f32"``): with
+    ``precision="fp64"``, dense views, initial factors and ``init_lm`` may be ``torch`` tensors on ``cuda:device_id`` (read
+    where they lie, ``resnmtf_fp64_run_device``: bitwise ``t.double().cpu().numpy()`` through the host route), and
+    ``output="torch"`` and ``return_state`` (which needs ``output="torch"``, else ``ValueError``) are honoured: F, S, G,
+    lambda, mu and the raw state stay on the device, and the cluster matrices are built there from F, G and S (bitwise the
+    host's).  The device's SVD initialisation then stays on the device too: the short-lived engine is loaded with
+    ``set_view_device`` and read with ``get_factors_device``.  Combines with ``fp64_sparse`` (host ``scipy.sparse`` views
+    beside device dense views).  Still refused: ``score_bisil``, ``spurious_on_device``, ``post_on_device`` and sparse
+    tensors in device memory.  Without the flag every refusal above stands word for word.
     """
     if precision not in ("f32", "fp64"):
         raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
@@ -202,7 +213,8 @@ def res_nmtf_inner(data, row_indices, column_indices,
                                     device_id=device_id, max_iters=max_iters, seed=seed, engine_opts=engine_opts,
                                     host_init=host_init, return_init=return_init, score_bisil=score_bisil,
                                     spurious_on_device=spurious_on_device, output=output, init_lm=init_lm,
-                                    return_state=return_state, post_on_device=post_on_device, fp64_sparse=fp64_sparse)
+                                    return_state=return_state, post_on_device=post_on_device, fp64_sparse=fp64_sparse,
+                                    fp64_device=fp64_device)
     device_views.check_output(output)
     _check_post_on_device(post_on_device, output)
     data = _views(data, device_id)
@@ -294,19 +306,23 @@ def res_nmtf_inner(data, row_indices, column_indices,
 def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init_g, k_vec, phi, xi, psi, n_iters, spurious,
                          distance, no_clusts, *, row_names, col_names, device_id, max_iters, seed, engine_opts, host_init,
                          return_init, score_bisil, spurious_on_device, output, init_lm, return_state, post_on_device,
-                         fp64_sparse: bool = False, runner: Optional[Callable] = None):
+                         fp64_sparse: bool = False, fp64_device: bool = False, runner: Optional[Callable] = None):
     """``res_nmtf_inner(precision="fp64")``: the checks of the f32 call, the refusals of what needs a live handle, the
-    initial state, then one ``engine.fp64_run`` (``runner`` replaces it: a test hook)."""
+    initial state, then one ``engine.fp64_run`` (``runner`` replaces it: a test hook).  ``fp64_device``: views, factors
+    and results may live in device memory (``res_nmtf_inner``'s docstring); the runner then also gets ``output`` and
+    ``return_state``."""
     def refuse(flag):
         raise NotImplementedError(f'precision="fp64": {flag} needs a live engine handle, which the fp64 path does not '
                                   'keep (it runs through resnmtf_fp64_run); use precision="f32" for it')
     device_views.check_output(output)
     remove = bool(spurious) and not no_clusts
     for flag, on in (("spurious_on_device", remove and spurious_on_device), ("score_bisil", score_bisil),
-                     ("post_on_device", post_on_device), ('output="torch"', output == "torch"),
-                     ("return_state", return_state)):
+                     ("post_on_device", post_on_device), ('output="torch"', output == "torch" and not fp64_device),
+                     ("return_state", return_state and not fp64_device)):
         if on:
             refuse(flag)
+    if return_state and output != "torch":
+        raise ValueError("precision=\"fp64\": return_state=True needs output='torch' (the raw state is left on the device)")
     _refuse_host_spurious(remove, spurious_on_device,
                           "spurious-bicluster removal (R/obtain_bicl.r:31-133) is outside the accelerated path; "
                           "pass spurious=False or do it on the R side (INTEGRATION.md).")
@@ -322,10 +338,16 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
         if sparse.is_sparse_view(d) or device_views.is_sparse_tensor(d):
             refuse(f"sparse views (view {v})")
         if device_views.is_device_view(d):
-            refuse(f"views in device memory (view {v})")
+            if not (fp64_device and device_views.is_tensor(d)):
+                refuse(f"views in device memory (view {v})")
+            views.append(device_views.as_view(d, device_id, f"view {v}"))      # (checked; read where it lies)
+            continue
         views.append(np.asarray(d, dtype=np.float64))
     data, n_v = views, len(views)
     is_sp = [sparse.is_sparse(d) for d in data]
+    if any(device_views.is_device_view(d) for d in data) and host_init and (init_f is None or init_g is None or init_s is None):
+        raise NotImplementedError("host_init=True (NumPy's dense SVD) is not available for views in device memory; the "
+                                  "device initialisation (host_init=False) works on them")
     if any(is_sp) and host_init and (init_f is None or init_g is None or init_s is None):
         raise NotImplementedError("host_init=True (NumPy's dense SVD) is not available for sparse views; the device "
                                   "initialisation (host_init=False) works on them")
@@ -341,16 +363,17 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
         init_f = init_s = init_g = None
     else:
         init_f, init_s, init_g = _as_list(init_f), _as_list(init_s), _as_list(init_g)
-        if any(device_views.is_device_tensor(x) for x in (*init_f, *init_s, *init_g)):
+        if not fp64_device and any(device_views.is_device_tensor(x) for x in (*init_f, *init_s, *init_g)):
             refuse("factors in device memory")
         _, init_f, init_s, init_g = device_views.factor_routes(init_f, init_s, init_g, device_id)
     if init_lm is not None:
         if init_f is None:
             raise ValueError("init_lm needs explicit initial factors (init_f, init_s and init_g)")
         lam, mu = device_views.check_init_lm(init_lm, n_v)
-        if any(device_views.is_device_tensor(x) for x in (*lam, *mu)):
+        if not fp64_device and any(device_views.is_device_tensor(x) for x in (*lam, *mu)):
             refuse("factors in device memory")
-        lam, mu = [device_views.to_numpy(x) for x in lam], [device_views.to_numpy(x) for x in mu]
+        if not fp64_device:
+            lam, mu = [device_views.to_numpy(x) for x in lam], [device_views.to_numpy(x) for x in mu]
     phi, xi, psi = (np.zeros((n_v, n_v)) if m is None else np.asarray(m, dtype=np.float64) for m in (phi, xi, psi))
     row_names, col_names = naming.give_names(data, None, None, row_names, col_names)
     batched._check_group_limits(0, data, k_vec[0], batched.FP64_LIMITS)
@@ -364,7 +387,9 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
         try:
             _load_engine(eng, data, None, None, None, None, None, phi, xi, psi, row_names, col_names, row_indices,
                          column_indices, seed=seed)
-            init_f, init_s, init_g, lam, mu = (list(x) for x in zip(*[eng.get_factors(v) for v in range(n_v)]))
+            # (fp64_device: the start stays on the device and is handed straight to the run)
+            start = eng.get_factors_device if fp64_device else eng.get_factors
+            init_f, init_s, init_g, lam, mu = (list(x) for x in zip(*[start(v) for v in range(n_v)]))
         finally:
             eng.close()
     problem = {"data": data, "k": k_vec[0], "init_f": list(init_f), "init_s": list(init_s), "init_g": list(init_g),
@@ -373,16 +398,37 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
                "col_pairs": batched.pair_table(col_names, column_indices), "n_iters": n_iters}
     init_state = None
     if return_init:                               # (F, S, G, lambda, mu) the loop starts from; None lambda / mu: the colSums
-        init_state = [tuple(np.array(a, dtype=np.float64) for a in
-                            (init_f[v], init_s[v], init_g[v],
-                             np.sum(init_f[v], axis=0) if lam is None or lam[v] is None else lam[v],
-                             np.sum(init_g[v], axis=0) if mu is None or mu[v] is None else mu[v])) for v in range(n_v)]
-    out = (runner or _engine.fp64_run)(problem, tol=1.0e-6, max_iters=max_iters, device_id=device_id)
+        def held(a):                              # as the result holds it: an fp64 tensor on the device, or an fp64 array
+            if output == "torch":
+                import torch
+                return (a.detach() if device_views.is_tensor(a) else torch.as_tensor(np.asarray(a, dtype=np.float64))).to(
+                    device=torch.device("cuda", int(device_id)), dtype=torch.float64)
+            return np.array(device_views.to_numpy(a.detach().double()) if device_views.is_tensor(a) else a, dtype=np.float64)
+        init_state = []
+        for v in range(n_v):
+            f0, s0, g0 = held(init_f[v]), held(init_s[v]), held(init_g[v])
+            init_state.append((f0, s0, g0, f0.sum(0) if lam is None or lam[v] is None else held(lam[v]),
+                               g0.sum(0) if mu is None or mu[v] is None else held(mu[v])))
+    more = {"output": output, "return_state": return_state} if fp64_device else {}
+    out = (runner or _engine.fp64_run)(problem, tol=1.0e-6, max_iters=max_iters, device_id=device_id, **more)
+    state = out.get("state") if return_state else None
     if no_clusts:                                                                                 # main.r:115-120
-        return inner_result(out["f"], out["s"], out["g"], init=init_state)
-    rcs, ccs = zip(*[batched._binary_clusters(f, g, s) for f, g, s in zip(out["f"], out["g"], out["s"])])
+        return inner_result(out["f"], out["s"], out["g"], init=init_state, state=state)
+    clusters = _binary_clusters_device if output == "torch" else batched._binary_clusters
+    rcs, ccs = zip(*[clusters(f, g, s) for f, g, s in zip(out["f"], out["g"], out["s"])])
     return inner_result(out["f"], out["s"], out["g"], np.asarray(out["all_error"], dtype=np.float64), n_iters, bisil=None,
-                        row_clusters=list(rcs), col_clusters=list(ccs), lam=out["lambda"], mu=out["mu"], init=init_state)
+                        row_clusters=list(rcs), col_clusters=list(ccs), lam=out["lambda"], mu=out["mu"], init=init_state,
+                        state=state)
+
+
+def _binary_clusters_device(f, g, s):
+    """``batched._binary_clusters`` of F, G and S in device memory, built there: the comparisons with 1/n and 1/m are
+    exact, and ``argmax`` takes the first maximum of every S column as NumPy's does, so the matrices are bitwise the
+    host's."""
+    import torch
+    rc = (f > 1.0 / f.shape[0]).to(torch.float64)
+    cc = (g > 1.0 / g.shape[0]).to(torch.float64)
+    return rc[:, torch.argmax(s, dim=0)], cc
 
 
 def _device_outputs(on_device, row_cl, col_cl, cleaned: dict):

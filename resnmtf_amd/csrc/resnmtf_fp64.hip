@@ -1,6 +1,6 @@
-// Device-wide fp64 factorisation (DESIGN.md sections 21 and 22): the host side of resnmtf_fp64_run, resnmtf_fp64_run_sparse
-// and their two plan queries, and -- through resnmtf_fp64.hip.inc and resnmtf_fp64_sparse.hip.inc (sparse views) -- their
-// kernels.  A translation unit of its own: the kernels get a code object of their
+// Device-wide fp64 factorisation (DESIGN.md sections 21 to 23): the host side of resnmtf_fp64_run, resnmtf_fp64_run_sparse,
+// resnmtf_fp64_run_device and the two plan queries, and -- through resnmtf_fp64.hip.inc, resnmtf_fp64_sparse.hip.inc (sparse
+// views) and resnmtf_fp64_device.hip.inc (views and factors from device memory) -- their kernels.  A translation unit of its own: the kernels get a code object of their
 // own and leave the main unit's device code as it was.  The job checks and the error text are the main unit's
 // (resnmtf_internal.h): this entry and resnmtf_group_run refuse the same things with the same texts.
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 #include "resnmtf_internal.h"
 #include "resnmtf_fp64.hip.inc"
 #include "resnmtf_fp64_sparse.hip.inc"
+#include "resnmtf_fp64_device.hip.inc"
 
 namespace {
 struct DeviceBuffer {
@@ -325,7 +326,126 @@ void fp64_csr_from_csc(int n, int m, const long long* col_ptr, const int* row_id
     }
 }
 
-int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp, double tol, int max_iters);
+// ---- resnmtf_fp64_run_device: what it refuses before any allocation or launch ----
+// what of a job comes from, and goes to, device memory
+struct F64DeviceUse {
+  unsigned views = 0, factors = 0;          // bit v: view v's data / its initial factors are device matrices
+  bool out = false, state = false;          // the results / the raw state are written to device memory
+};
+
+inline size_t fp64_dtype_bytes(int dtype) { return dtype == RESNMTF_DTYPE_F64 ? 8 : dtype == RESNMTF_DTYPE_F32 ? 4 : 2; }
+
+// the refusals that need no device: the text, or "" when the struct is fine (and then `use`)
+std::string fp64_check_device_struct(const resnmtf_group_job& j, const resnmtf_fp64_device& d, unsigned sparse_views, F64DeviceUse& use) {
+  if (d.struct_size != (int)sizeof(resnmtf_fp64_device)) return "resnmtf_fp64_device struct_size mismatch";
+  if (j.struct_size != (int)sizeof(resnmtf_group_job) || j.n_views < 1 || j.n_views > RESNMTF_GROUP_MAX_VIEWS) return "";   // (the job check says it)
+  const int V = j.n_views;
+  auto view = [](int v) { return "view " + std::to_string(v) + ": "; };
+  struct Field { const char* name; const resnmtf_device_matrix* m; };
+  for (int v = 0; v < RESNMTF_GROUP_MAX_VIEWS; ++v) {
+    const Field in[6] = {{"x", &d.x[v]}, {"f0", &d.f0[v]}, {"s0", &d.s0[v]}, {"g0", &d.g0[v]}, {"lambda0", &d.lambda0[v]}, {"mu0", &d.mu0[v]}};
+    double* const out[10] = {d.f_out[v], d.s_out[v], d.g_out[v], d.lambda_out[v], d.mu_out[v],
+                             d.state_f[v], d.state_s[v], d.state_g[v], d.state_lambda[v], d.state_mu[v]};
+    if (v >= V) {
+      for (const Field& f : in)
+        if (f.m->ptr) return view(v) + "dev->" + f.name + " is given beyond n_views";
+      for (double* p : out)
+        if (p) return view(v) + "a device output is given beyond n_views";
+      continue;
+    }
+    for (const Field& f : in) {
+      if (!f.m->ptr) continue;
+      if (f.m->dtype < RESNMTF_DTYPE_F64 || f.m->dtype > RESNMTF_DTYPE_BF16)
+        return view(v) + "dev->" + f.name + " has an unknown dtype (" + std::to_string(f.m->dtype) + ")";
+      if (f.m->row_stride < 0 || f.m->col_stride < 0) return view(v) + "dev->" + f.name + " has a negative stride";
+    }
+    const bool sparse = (sparse_views >> v) & 1u;
+    if (d.x[v].ptr && j.x[v]) return view(v) + "x is given both in the job (job->x) and in device memory (dev->x): one of them must be NULL";
+    if (d.x[v].ptr && sparse) return view(v) + "x is given both sparse (col_ptr) and in device memory (dev->x): one of them must be NULL";
+    if (!d.x[v].ptr && !j.x[v] && !sparse) return view(v) + "x is given neither in the job (job->x) nor in device memory (dev->x)";
+    if (d.x[v].ptr) use.views |= 1u << v;
+    const int n_there = (d.f0[v].ptr ? 1 : 0) + (d.s0[v].ptr ? 1 : 0) + (d.g0[v].ptr ? 1 : 0);
+    if (n_there != 0 && n_there != 3)
+      return view(v) + "f0 / s0 / g0 are given partly in device memory (" + (d.f0[v].ptr ? "" : "dev->f0 ") + (d.s0[v].ptr ? "" : "dev->s0 ") +
+             (d.g0[v].ptr ? "" : "dev->g0 ") + "NULL): all three of a view in one place";
+    if (n_there == 3 && (j.f0[v] || j.s0[v] || j.g0[v] || j.lambda0[v] || j.mu0[v]))
+      return view(v) + "f0 / s0 / g0 are given in device memory: job->f0 / s0 / g0 / lambda0 / mu0 must be NULL";
+    if (n_there == 0 && (d.lambda0[v].ptr || d.mu0[v].ptr))
+      return view(v) + "dev->lambda0 / dev->mu0 need f0 / s0 / g0 in device memory (dev->f0, dev->s0, dev->g0)";
+    if (n_there == 3) use.factors |= 1u << v;
+  }
+  static const char* const names[10] = {"f_out", "s_out", "g_out", "lambda_out", "mu_out",
+                                        "state_f", "state_s", "state_g", "state_lambda", "state_mu"};
+  for (int set = 0; set < 2; ++set) {                  // each set of five: for every view of the job, or for none
+    int given = 0, missing_v = -1, missing_f = -1;
+    for (int v = 0; v < V; ++v) {
+      double* const out[10] = {d.f_out[v], d.s_out[v], d.g_out[v], d.lambda_out[v], d.mu_out[v],
+                               d.state_f[v], d.state_s[v], d.state_g[v], d.state_lambda[v], d.state_mu[v]};
+      for (int f = 0; f < 5; ++f) {
+        if (out[set * 5 + f]) ++given;
+        else if (missing_v < 0) { missing_v = v; missing_f = set * 5 + f; }
+      }
+    }
+    if (given != 0 && given != 5 * V)
+      return view(missing_v) + "dev->" + names[missing_f] + " is NULL while other device " + (set ? "state outputs" : "outputs") +
+             " are given: all five of every view, or none";
+    (set ? use.state : use.out) = given != 0;
+  }
+  return "";
+}
+
+// true when [p, p + bytes) is device memory of device_id and inside its allocation; a host pointer makes
+// hipPointerGetAttributes fail (or report host memory, by version): both are "no", and the sticky error is cleared
+bool fp64_on_device(int device_id, const void* p, size_t bytes, bool& beyond) {
+  beyond = false;
+  hipPointerAttribute_t attr;
+  std::memset(&attr, 0, sizeof(attr));
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  if (attr.type != hipMemoryTypeDevice || attr.device != device_id) return false;
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) { (void)hipGetLastError(); return true; }
+  const char* lo = static_cast<const char*>(static_cast<const void*>(base));
+  beyond = static_cast<const char*>(p) + bytes > lo + size;
+  return !beyond;
+}
+
+// the refusals that ask the runtime: every pointer of the struct is device memory of device_id and every matrix stays
+// inside its allocation
+std::string fp64_check_device_pointers(int device_id, const resnmtf_group_job& j, const resnmtf_fp64_device& d, const F64DeviceUse& use) {
+  const int V = j.n_views, k = j.k;
+  auto refusal = [&](int v, const char* name, bool beyond) {
+    return "view " + std::to_string(v) + ": dev->" + name +
+           (beyond ? " reaches beyond its allocation (too short for the shape and strides given)"
+                   : " is not device memory of device " + std::to_string(device_id));
+  };
+  for (int v = 0; v < V; ++v) {
+    const size_t n = (size_t)j.n_rows[v], m = (size_t)j.n_cols[v], kk = (size_t)k;
+    struct In { const char* name; const resnmtf_device_matrix* a; size_t rows, cols; };
+    const In in[6] = {{"x", &d.x[v], n, m}, {"f0", &d.f0[v], n, kk}, {"s0", &d.s0[v], kk, kk}, {"g0", &d.g0[v], m, kk},
+                      {"lambda0", &d.lambda0[v], kk, 1}, {"mu0", &d.mu0[v], kk, 1}};
+    for (const In& f : in) {
+      if (!f.a->ptr) continue;
+      const size_t last = (f.rows - 1) * (size_t)f.a->row_stride + (f.cols - 1) * (size_t)f.a->col_stride;
+      bool beyond = false;
+      if (!fp64_on_device(device_id, f.a->ptr, (last + 1) * fp64_dtype_bytes(f.a->dtype), beyond)) return refusal(v, f.name, beyond);
+    }
+    struct Out { const char* name; const double* p; size_t count; };
+    const Out out[10] = {{"f_out", d.f_out[v], n * kk}, {"s_out", d.s_out[v], kk * kk}, {"g_out", d.g_out[v], m * kk},
+                         {"lambda_out", d.lambda_out[v], kk}, {"mu_out", d.mu_out[v], kk},
+                         {"state_f", d.state_f[v], n * kk}, {"state_s", d.state_s[v], kk * kk}, {"state_g", d.state_g[v], m * kk},
+                         {"state_lambda", d.state_lambda[v], kk}, {"state_mu", d.state_mu[v], kk}};
+    for (int f = 0; f < 10; ++f) {
+      if (!(f < 5 ? use.out : use.state)) continue;
+      bool beyond = false;
+      if (!fp64_on_device(device_id, out[f].p, out[f].count * sizeof(double), beyond)) return refusal(v, out[f].name, beyond);
+    }
+  }
+  return "";
+}
+
+int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp, const resnmtf_fp64_device* dev,
+                  double tol, int max_iters);
 }  // namespace
 
 extern "C" {
@@ -348,7 +468,7 @@ int resnmtf_fp64_sparse_plan(int n_rows, int n_cols, int k, const long long* col
 }
 
 int resnmtf_fp64_run(int device_id, const resnmtf_group_job* job, double tol, int max_iters) {
-  return fp64_run_impl(device_id, job, nullptr, tol, max_iters);
+  return fp64_run_impl(device_id, job, nullptr, nullptr, tol, max_iters);
 }
 
 int resnmtf_fp64_run_sparse(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp, double tol,
@@ -357,7 +477,16 @@ int resnmtf_fp64_run_sparse(int device_id, const resnmtf_group_job* job, const r
     resnmtf_set_create_error("resnmtf_fp64_sparse struct_size mismatch");
     return RESNMTF_ERR_INVALID;
   }
-  return fp64_run_impl(device_id, job, sp, tol, max_iters);
+  return fp64_run_impl(device_id, job, sp, nullptr, tol, max_iters);
+}
+
+int resnmtf_fp64_run_device(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp,
+                            const resnmtf_fp64_device* dev, double tol, int max_iters) {
+  if (sp && sp->struct_size != (int)sizeof(resnmtf_fp64_sparse)) {
+    resnmtf_set_create_error("resnmtf_fp64_sparse struct_size mismatch");
+    return RESNMTF_ERR_INVALID;
+  }
+  return fp64_run_impl(device_id, job, sp, dev, tol, max_iters);
 }
 
 int resnmtf_fp64_plan(int n_rows, int n_cols, int k, int* out) {
@@ -377,9 +506,11 @@ int resnmtf_fp64_plan(int n_rows, int n_cols, int k, int* out) {
 }  // extern "C"
 
 namespace {
-// resnmtf_fp64_run (sp == nullptr) and resnmtf_fp64_run_sparse: one body.  Without a sparse view every step below is
-// resnmtf_fp64_run's own -- the same layout, the same launches, the same bits.
-int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp, double tol, int max_iters) {
+// resnmtf_fp64_run (sp == nullptr), resnmtf_fp64_run_sparse (dev == nullptr) and resnmtf_fp64_run_device: one body.  Without
+// a sparse view every step below is resnmtf_fp64_run's own -- the same layout, the same launches, the same bits --, and
+// without dev every step is resnmtf_fp64_run_sparse's.
+int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp, const resnmtf_fp64_device* dev,
+                  double tol, int max_iters) {
   auto bad = [](const std::string& msg) { resnmtf_set_create_error(msg); return RESNMTF_ERR_INVALID; };
   if (!job) return bad("job is NULL");
   if (max_iters < 1) return bad("max_iters must be >= 1");
@@ -399,8 +530,17 @@ int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp6
       return RESNMTF_ERR_ALLOC;
     }
   }
-  if (const char* why = resnmtf_check_fp64_job(j, max_iters, sparse_views)) return bad(why);
+  F64DeviceUse use;                         // what comes from, and goes to, device memory (resnmtf_fp64_run_device)
+  if (dev) {
+    const std::string why = fp64_check_device_struct(j, *dev, sparse_views, use);
+    if (!why.empty()) return bad(why);
+  }
+  if (const char* why = resnmtf_check_fp64_job(j, max_iters, sparse_views | use.views, use.factors, use.out)) return bad(why);
   if (sparse_views >> j.n_views) return bad("a sparse view is given beyond n_views");
+  if (dev) {
+    const std::string why = fp64_check_device_pointers(device_id, j, *dev, use);
+    if (!why.empty()) return bad(why);
+  }
   F64SparseShape shapes[RESNMTF_GROUP_MAX_VIEWS];
   for (int v = 0; v < j.n_views; ++v) {
     if (!((sparse_views >> v) & 1u)) continue;
@@ -445,6 +585,16 @@ int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp6
     return RESNMTF_ERR_HIP;
   };
   const int V = L.V, k = L.k;
+  if (dev) {                                // the run's stream waits for what the caller's stream holds so far
+    hipEvent_t ev = nullptr;
+    e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e == hipSuccess) {
+      e = hipEventRecord(ev, static_cast<hipStream_t>(dev->stream));
+      if (e == hipSuccess) e = hipStreamWaitEvent(st, ev, 0);
+      (void)hipEventDestroy(ev);            // (released once the recorded work completes)
+    }
+    if (e != hipSuccess) return fail(e);
+  }
   e = hipMemsetAsync(buf, 0, bytes, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return fail(e);
@@ -470,6 +620,11 @@ int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp6
         }
         continue;
       }
+      if ((use.views >> v) & 1u) {           // from device memory: one read, both images, no staging (section 23)
+        fp64_images(st, dev->x[v], w.n, w.m, buf + w.x, w.ldn, buf + w.xt, w.ldm);
+        e = hipGetLastError();
+        continue;
+      }
       const double* x = j.x[v];
       const size_t n = (size_t)w.n, m = (size_t)w.m;
       img.assign(w.ldn * w.mpad, 0.0);
@@ -486,6 +641,7 @@ int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp6
   std::vector<double> host(L.out_end - L.out_begin, 0.0);
   auto at = [&](size_t off) { return host.data() + (off - L.out_begin); };
   for (int v = 0; v < V; ++v) {
+    if ((use.factors >> v) & 1u) continue;  // (from device memory, below)
     const size_t n = (size_t)L.vw[v].n, m = (size_t)L.vw[v].m;
     std::memcpy(at(L.vw[v].f), j.f0[v], n * k * sizeof(double));
     std::memcpy(at(L.vw[v].g), j.g0[v], m * k * sizeof(double));
@@ -498,7 +654,36 @@ int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp6
       *at(L.mu + (size_t)v * k + c) = j.mu0[v] ? j.mu0[v][c] : cg;
     }
   }
-  e = hipMemcpy(buf + L.out_begin, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (!use.factors) {
+    e = hipMemcpy(buf + L.out_begin, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice);
+  } else {                                  // the host views' pieces alone; the others are written by kernels on the stream
+    for (int v = 0; v < V && e == hipSuccess; ++v) {
+      if ((use.factors >> v) & 1u) continue;
+      const size_t fg = ((size_t)L.vw[v].n + L.vw[v].m) * k;               // F and G of a view are neighbours
+      const size_t pieces[4][2] = {{L.vw[v].f, fg}, {L.s + (size_t)v * k * k, (size_t)k * k}, {L.lam + (size_t)v * k, (size_t)k},
+                                   {L.mu + (size_t)v * k, (size_t)k}};
+      for (int p = 0; p < 4 && e == hipSuccess; ++p)
+        e = hipMemcpy(buf + pieces[p][0], at(pieces[p][0]), pieces[p][1] * sizeof(double), hipMemcpyHostToDevice);
+    }
+    for (int v = 0; v < V && e == hipSuccess; ++v) {
+      if (!((use.factors >> v) & 1u)) continue;
+      const F64View& w = L.vw[v];
+      double* lam = buf + L.lam + (size_t)v * k;
+      double* mu = buf + L.mu + (size_t)v * k;
+      fp64_factors_in(st, dev->f0[v], w.n, k, buf + w.f);
+      fp64_factors_in(st, dev->s0[v], k, k, buf + L.s + (size_t)v * k * k);
+      fp64_factors_in(st, dev->g0[v], w.m, k, buf + w.g);
+      for (int side = 0; side < 2; ++side) {                               // given: a k x 1 matrix (col_stride is not read)
+        resnmtf_device_matrix vec = side ? dev->mu0[v] : dev->lambda0[v];
+        vec.col_stride = vec.row_stride;
+        if (vec.ptr) fp64_factors_in(st, vec, k, 1, side ? mu : lam);
+      }
+      if (!dev->lambda0[v].ptr || !dev->mu0[v].ptr)                        // not given: colSums (R/update_steps.r:55-56)
+        hipLaunchKernelGGL(fp64_colsum_seq_kernel, dim3(2), dim3(64), 0, st, (const double*)(buf + w.f), w.n,
+                           dev->lambda0[v].ptr ? nullptr : lam, (const double*)(buf + w.g), w.m, dev->mu0[v].ptr ? nullptr : mu, k);
+      e = hipGetLastError();
+    }
+  }
   if (e != hipSuccess) return fail(e);
   if (L.total > L.maps) {
     std::vector<int> maps((L.total - L.maps) * 2, -1);
@@ -550,6 +735,22 @@ int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp6
       if (!(diff > tol)) break;
     }
   }
+  // the raw state, as a later call resumes from it, and the normalised results: device to device, on the run's stream
+  auto copy_out = [&](int v, double* f, double* s, double* g, double* lam, double* mu) {
+    const F64View& w = L.vw[v];
+    const size_t kk = (size_t)k;
+    hipError_t c = hipMemcpyAsync(f, buf + w.f, (size_t)w.n * kk * sizeof(double), hipMemcpyDeviceToDevice, st);
+    if (c == hipSuccess) c = hipMemcpyAsync(s, buf + L.s + (size_t)v * kk * kk, kk * kk * sizeof(double), hipMemcpyDeviceToDevice, st);
+    if (c == hipSuccess) c = hipMemcpyAsync(g, buf + w.g, (size_t)w.m * kk * sizeof(double), hipMemcpyDeviceToDevice, st);
+    if (c == hipSuccess) c = hipMemcpyAsync(lam, buf + L.lam + (size_t)v * kk, kk * sizeof(double), hipMemcpyDeviceToDevice, st);
+    if (c == hipSuccess) c = hipMemcpyAsync(mu, buf + L.mu + (size_t)v * kk, kk * sizeof(double), hipMemcpyDeviceToDevice, st);
+    return c;
+  };
+  if (use.state)
+    for (int v = 0; v < V; ++v) {
+      e = copy_out(v, dev->state_f[v], dev->state_s[v], dev->state_g[v], dev->state_lambda[v], dev->state_mu[v]);
+      if (e != hipSuccess) return fail(e);
+    }
   for (int v = 0; v < V; ++v) {            // normalisation_check (R/utils.r:176-195)
     const F64View& w = L.vw[v];
     const size_t total = ((size_t)w.n + w.m + k) * k;
@@ -560,17 +761,23 @@ int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp6
   }
   e = hipGetLastError();
   std::vector<double> errs((size_t)it);
-  if (e == hipSuccess) e = hipMemcpyAsync(host.data(), buf + L.out_begin, host.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+  bool to_host = !use.out;                  // with device outputs the host copy is made only for a host pointer that is set
+  for (int v = 0; v < V; ++v) {
+    if (use.out && e == hipSuccess) e = copy_out(v, dev->f_out[v], dev->s_out[v], dev->g_out[v], dev->lambda_out[v], dev->mu_out[v]);
+    to_host = to_host || j.f_out[v] || j.s_out[v] || j.g_out[v] || j.lambda_out[v] || j.mu_out[v];
+  }
+  if (e == hipSuccess && to_host)
+    e = hipMemcpyAsync(host.data(), buf + L.out_begin, host.size() * sizeof(double), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && it > 0) e = hipMemcpyAsync(errs.data(), buf + L.err, errs.size() * sizeof(double), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return fail(e);
   (void)hipStreamDestroy(st);
-  for (int v = 0; v < V; ++v) {
-    std::memcpy(j.f_out[v], at(L.vw[v].f), (size_t)L.vw[v].n * k * sizeof(double));
-    std::memcpy(j.g_out[v], at(L.vw[v].g), (size_t)L.vw[v].m * k * sizeof(double));
-    std::memcpy(j.s_out[v], at(L.s + (size_t)v * k * k), (size_t)k * k * sizeof(double));
-    std::memcpy(j.lambda_out[v], at(L.lam + (size_t)v * k), (size_t)k * sizeof(double));
-    std::memcpy(j.mu_out[v], at(L.mu + (size_t)v * k), (size_t)k * sizeof(double));
+  for (int v = 0; v < V; ++v) {            // (a host pointer may be NULL only beside device outputs)
+    if (j.f_out[v]) std::memcpy(j.f_out[v], at(L.vw[v].f), (size_t)L.vw[v].n * k * sizeof(double));
+    if (j.g_out[v]) std::memcpy(j.g_out[v], at(L.vw[v].g), (size_t)L.vw[v].m * k * sizeof(double));
+    if (j.s_out[v]) std::memcpy(j.s_out[v], at(L.s + (size_t)v * k * k), (size_t)k * k * sizeof(double));
+    if (j.lambda_out[v]) std::memcpy(j.lambda_out[v], at(L.lam + (size_t)v * k), (size_t)k * sizeof(double));
+    if (j.mu_out[v]) std::memcpy(j.mu_out[v], at(L.mu + (size_t)v * k), (size_t)k * sizeof(double));
   }
   for (int t = 0; t < it; ++t) j.all_error[t] = errs[(size_t)t];
   *j.iters_done = it;

@@ -4460,8 +4460,12 @@ const GroupJobLimits kGroupLimits = {RESNMTF_GROUP_MAX_K, "k must be in [1, 32]"
 const GroupJobLimits kFp64Limits = {RESNMTF_MAX_K, "k must be in [1, 64]", 0};
 
 // a job's host checks; a message on refusal, nullptr when it is fine
-// (x_elsewhere: bit v set = view v's data come from outside the job, resnmtf_fp64_run_sparse's CSC arrays, and x[v] must be NULL)
-const char* check_group_job(const resnmtf_group_job& j, int max_iters, const GroupJobLimits& lim, unsigned x_elsewhere = 0) {
+// (x_elsewhere: bit v set = view v's data come from outside the job, resnmtf_fp64_run_sparse's CSC arrays or
+// resnmtf_fp64_run_device's device matrix, and x[v] must be NULL; factors_elsewhere: bit v set = so do its initial factors,
+// and f0 / s0 / g0 / lambda0 / mu0 [v] must be NULL; outputs_elsewhere: the results go to device memory and the job's five
+// output pointers per view may be NULL)
+const char* check_group_job(const resnmtf_group_job& j, int max_iters, const GroupJobLimits& lim, unsigned x_elsewhere = 0,
+                            unsigned factors_elsewhere = 0, bool outputs_elsewhere = false) {
   if (j.struct_size != (int)sizeof(resnmtf_group_job)) return "resnmtf_group_job struct_size mismatch";
   const int V = j.n_views, k = j.k;
   if (V < 1 || V > RESNMTF_GROUP_MAX_VIEWS) return "n_views must be in [1, 8]";
@@ -4476,9 +4480,14 @@ const char* check_group_job(const resnmtf_group_job& j, int max_iters, const Gro
     if (lim.max_view_entries > 0 && (long long)n * m > lim.max_view_entries) return "a view has more than 2^22 entries";
     const bool elsewhere = (x_elsewhere >> v) & 1u;
     if (elsewhere && j.x[v]) return "a view is given both dense (x) and sparse (col_ptr): x must be NULL for a sparse view";
-    if ((!elsewhere && !j.x[v]) || !j.f0[v] || !j.s0[v] || !j.g0[v]) return "x / f0 / s0 / g0 is NULL";
-    if (!j.f_out[v] || !j.s_out[v] || !j.g_out[v] || !j.lambda_out[v] || !j.mu_out[v]) return "an output pointer is NULL";
+    const bool factors_there = (factors_elsewhere >> v) & 1u;
+    if (factors_there && (j.f0[v] || j.s0[v] || j.g0[v] || j.lambda0[v] || j.mu0[v]))
+      return "a view's initial factors are given in device memory: f0 / s0 / g0 / lambda0 / mu0 must be NULL for it";
+    if ((!elsewhere && !j.x[v]) || (!factors_there && (!j.f0[v] || !j.s0[v] || !j.g0[v]))) return "x / f0 / s0 / g0 is NULL";
+    if (!outputs_elsewhere && (!j.f_out[v] || !j.s_out[v] || !j.g_out[v] || !j.lambda_out[v] || !j.mu_out[v]))
+      return "an output pointer is NULL";
     if (!elsewhere && !all_finite(j.x[v], (size_t)n * m)) return "x has a non-finite entry";
+    if (factors_there) continue;
     if (!all_finite(j.f0[v], (size_t)n * k) || !all_finite(j.s0[v], (size_t)k * k) || !all_finite(j.g0[v], (size_t)m * k))
       return "an initial factor has a non-finite entry";
     if ((j.lambda0[v] && !all_finite(j.lambda0[v], k)) || (j.mu0[v] && !all_finite(j.mu0[v], k)))
@@ -4707,8 +4716,9 @@ int resnmtf_group_run(int device_id, int n_jobs, const resnmtf_group_job* jobs, 
 // so that its kernels sit in a code object of their own); these two hand it the checks and the error text it shares
 // with resnmtf_group_run (csrc/resnmtf_internal.h) ----
 }  // extern "C"
-const char* resnmtf_check_fp64_job(const resnmtf_group_job& j, int max_iters, unsigned sparse_views) {
-  return check_group_job(j, max_iters, kFp64Limits, sparse_views);
+const char* resnmtf_check_fp64_job(const resnmtf_group_job& j, int max_iters, unsigned x_elsewhere, unsigned factors_elsewhere,
+                                   bool outputs_elsewhere) {
+  return check_group_job(j, max_iters, kFp64Limits, x_elsewhere, factors_elsewhere, outputs_elsewhere);
 }
 void resnmtf_set_create_error(const std::string& text) { g_create_error = text; }
 extern "C" {

@@ -12,6 +12,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
+from . import device_views as _device_views
 from . import sparse as _sparse
 from ._lib import ResnmtfError
 
@@ -73,14 +74,87 @@ def jsd_stages(cols, pairs, sorted: bool = True, stats: bool = True, dens: bool 
     return got
 
 
-def _fill_group_job(j, p, q: int, max_iters: int, keep: list, sp=None) -> dict:
+_DTYPE_CODES = {"torch.float64": _lib.DTYPE_F64, "torch.float32": _lib.DTYPE_F32, "torch.float16": _lib.DTYPE_F16,
+                "torch.bfloat16": _lib.DTYPE_BF16}
+
+
+def _device_matrix(t, shape, device_id: int, what: str) -> _lib.DeviceMatrix:
+    """The ``resnmtf_device_matrix`` of a ``torch`` tensor as it lies (``data_ptr``, dtype, strides in elements), after the
+    checks that need no device: fp64 / fp32 / fp16 / bf16, on ``cuda:device_id``, of ``shape`` (``ValueError``)."""
+    if str(t.dtype) not in _DTYPE_CODES:
+        raise ValueError(f"{what} must be fp64, fp32, fp16 or bf16, got {t.dtype}")
+    if not _device_views.on_engine_device(t, device_id):
+        raise ValueError(f"{what} lives on {t.device}, the run on cuda:{int(device_id)}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    strides = [int(x) for x in t.stride()] + [1]                      # (a vector: the column stride is not read)
+    return _lib.DeviceMatrix(t.data_ptr(), _DTYPE_CODES[str(t.dtype)], strides[0], strides[1])
+
+
+def _fill_fp64_device(dev, v: int, x, p, k: int, q: int, device_id: int, keep: list) -> tuple:
+    """View ``v`` of ``fp64_run``'s problem ``p`` into the ``resnmtf_fp64_device`` ``dev``: its data when ``x`` is a device
+    tensor, its initial factors when they are.  Returns (data on the device, factors on the device); what is not stays
+    ``_fill_group_job``'s.  ``init_f[v]`` / ``init_s[v]`` / ``init_g[v]`` are all three device tensors or none is
+    (``ValueError``); beside device factors ``init_lam[v]`` / ``init_mu[v]`` are moved to the device when they are not there."""
+    n, m = (int(d) for d in x.shape)
+    x_there = _device_views.is_device_tensor(x)
+    if x_there:
+        t = x.detach()
+        keep.append(t)
+        dev.x[v] = _device_matrix(t, (n, m), device_id, f"problem {q}, view {v}: data")
+    parts = [p["init_f"][v], p["init_s"][v], p["init_g"][v]]
+    if not _device_views.factor_route(*parts, what=f"problem {q}, view {v}"):
+        return x_there, False
+    for t, name, shape in zip(parts, ("f0", "s0", "g0"), ((n, k), (k, k), (m, k))):
+        t = t.detach()
+        keep.append(t)
+        getattr(dev, name)[v] = _device_matrix(t, shape, device_id, f"problem {q}, view {v}: init_{name[0]}")
+    for name, key in (("lambda0", "init_lam"), ("mu0", "init_mu")):
+        vals = p.get(key)
+        if vals is None or vals[v] is None:
+            continue
+        t = vals[v]
+        if not _device_views.is_tensor(t):
+            import torch            # (lazily: the factors are tensors, so it is loaded)
+            t = torch.as_tensor(np.ascontiguousarray(t, dtype=np.float64), device=torch.device("cuda", int(device_id)))
+        elif t.device.type == "cpu":
+            t = t.to(parts[0].device)
+        t = t.detach()
+        keep.append(t)
+        getattr(dev, name)[v] = _device_matrix(t, (k,), device_id, f"problem {q}, view {v}: {key}")
+    return x_there, True
+
+
+def _fp64_device_outputs(dev, j, out: dict, device_id: int, return_state: bool):
+    """``output="torch"``: the five results per view (and the raw state) as fp64 tensors on ``cuda:device_id``, F, S and G
+    column-major (``torch.empty((k, n)).T``, as ``Engine.get_factors_device`` wraps its own), their addresses in ``dev``."""
+    import torch                    # (lazily: nothing else in this module needs it)
+    where = torch.device("cuda", int(device_id))
+    k = int(j.k)
+    sets = [("", out)] + ([("state_", out.setdefault("state", {"f": [], "s": [], "g": [], "lambda": [], "mu": []}))] if return_state else [])
+    for v in range(int(j.n_views)):
+        n, m = int(j.n_rows[v]), int(j.n_cols[v])
+        for prefix, store in sets:
+            for key, shape in (("f", (n, k)), ("s", (k, k)), ("g", (m, k)), ("lambda", (k,)), ("mu", (k,))):
+                t = (torch.empty(shape[::-1], dtype=torch.float64, device=where).T if len(shape) == 2
+                     else torch.empty(shape, dtype=torch.float64, device=where))
+                store[key].append(t)
+                getattr(dev, (prefix + key) if prefix else key + "_out")[v] = t.data_ptr()
+
+
+def _fill_group_job(j, p, q: int, max_iters: int, keep: list, sp=None, dev=None, device_id: int = 0,
+                    device_out: bool = False) -> dict:
     """Fill one ``resnmtf_group_job`` (``j``) from the problem dict ``p`` (problem ``q`` of its call; the layout
     ``group_run`` documents) and return the output arrays it points to.  ``keep`` collects every array the struct
     points into: the caller holds it until the library call has returned.  ``sp`` (``fp64_run`` alone): the
     ``resnmtf_fp64_sparse`` that receives the canonical CSC arrays of every ``scipy.sparse`` view, whose ``x`` stays
-    NULL; without it such a view is a ``ValueError``."""
+    NULL; without it such a view is a ``ValueError``.  ``dev`` (``fp64_run`` alone): the ``resnmtf_fp64_device`` that
+    receives every view and every set of initial factors that are ``torch`` tensors on ``cuda:device_id``
+    (``_fill_fp64_device``); the job's own pointers to them stay NULL.  ``device_out``: the job's per-view output pointers
+    stay NULL and the returned lists empty (``_fp64_device_outputs`` fills them)."""
     j.struct_size = C.sizeof(_lib.GroupJob)
-    data = [_sparse.canonical_csc(x) if _sparse.is_sparse(x) else _f64_colmajor(x) for x in p["data"]]
+    data = [_sparse.canonical_csc(x) if _sparse.is_sparse(x)
+            else x if dev is not None and _device_views.is_device_tensor(x) else _f64_colmajor(x) for x in p["data"]]
     if sp is None and any(_sparse.is_sparse(x) for x in data):
         raise ValueError(f"problem {q}: a sparse view (scipy.sparse) is taken by fp64_run alone")
     V, k = len(data), int(p["k"])
@@ -97,11 +171,12 @@ def _fill_group_job(j, p, q: int, max_iters: int, keep: list, sp=None) -> dict:
     cap = max(1, min(int(n_iters), int(max_iters)) if n_iters else int(max_iters))
     out = {"f": [], "s": [], "g": [], "lambda": [], "mu": [], "all_error": np.empty(cap), "iters": np.zeros(1, np.int32)}
     for v, x in enumerate(data):
-        n, m = x.shape
+        n, m = (int(d) for d in x.shape)
         j.n_rows[v], j.n_cols[v] = n, m
+        x_there, factors_there = (False, False) if dev is None else _fill_fp64_device(dev, v, x, p, k, q, device_id, keep)
         try:                                  # (the library reads n k, k k and m k doubles through these pointers)
-            arrs = [x, _f64_colmajor(p["init_f"][v], (n, k)), _f64_colmajor(p["init_s"][v], (k, k)),
-                    _f64_colmajor(p["init_g"][v], (m, k))]
+            arrs = [x] + ([] if factors_there else [_f64_colmajor(p["init_f"][v], (n, k)), _f64_colmajor(p["init_s"][v], (k, k)),
+                                                    _f64_colmajor(p["init_g"][v], (m, k))])
         except ValueError as exc:
             raise ValueError(f"problem {q}, view {v}: initial factor: {exc}") from None
         if _sparse.is_sparse(x):              # the CSC arrays go into sp; j.x[v] stays NULL
@@ -111,17 +186,21 @@ def _fill_group_job(j, p, q: int, max_iters: int, keep: list, sp=None) -> dict:
             sp.view[v].row_idx, sp.view[v].values = _ip(csc[1]), _dp(csc[2])
             keep.extend(csc)
             arrs = arrs[1:]
-        for name, a in zip(("f0", "s0", "g0") if _sparse.is_sparse(x) else ("x", "f0", "s0", "g0"), arrs):
+        elif x_there:                         # dev.x[v] describes it; j.x[v] stays NULL
+            arrs = arrs[1:]
+        for name, a in zip(("f0", "s0", "g0") if _sparse.is_sparse(x) or x_there else ("x", "f0", "s0", "g0"), arrs):
             getattr(j, name)[v] = _dp(a)
         keep.extend(arrs)
         for name, key in (("lambda0", "init_lam"), ("mu0", "init_mu")):
             vals = p.get(key)
-            if vals is not None and vals[v] is not None:
-                a = np.ascontiguousarray(vals[v], dtype=np.float64)
+            if vals is not None and vals[v] is not None and not factors_there:
+                a = np.ascontiguousarray(_device_views.to_numpy(vals[v]), dtype=np.float64)
                 if a.shape != (k,):
                     raise ValueError(f"problem {q}, view {v}: {key} must have k = {k} entries, got shape {a.shape}")
                 keep.append(a)
                 getattr(j, name)[v] = _dp(a)
+        if device_out:
+            continue
         for key, shape in (("f", (n, k)), ("s", (k, k)), ("g", (m, k)), ("lambda", (k,)), ("mu", (k,))):
             out[key].append(np.zeros(shape, dtype=np.float64, order="F"))
         j.f_out[v], j.s_out[v], j.g_out[v] = _dp(out["f"][v]), _dp(out["s"][v]), _dp(out["g"][v])
@@ -152,8 +231,12 @@ def _fill_group_job(j, p, q: int, max_iters: int, keep: list, sp=None) -> dict:
 
 def _group_result(out: dict) -> dict:
     it = int(out["iters"][0])
-    return {"f": out["f"], "s": out["s"], "g": out["g"], "lambda": out["lambda"], "mu": out["mu"],
-            "all_error": out["all_error"][:it].copy(), "iters": it}
+    res = {"f": out["f"], "s": out["s"], "g": out["g"], "lambda": out["lambda"], "mu": out["mu"],
+           "all_error": out["all_error"][:it].copy(), "iters": it}
+    if "state" in out:              # (fp64_run(return_state=True)): per view (F, S, G, lambda, mu)
+        st = out["state"]
+        res["state"] = [tuple(st[key][v] for key in ("f", "s", "g", "lambda", "mu")) for v in range(len(st["f"]))]
+    return res
 
 
 def group_run(problems, tol: float = 1.0e-6, max_iters: int = 100000, device_id: int = 0) -> list:
@@ -176,7 +259,8 @@ def group_run(problems, tol: float = 1.0e-6, max_iters: int = 100000, device_id:
     return [_group_result(out) for out in outs]
 
 
-def fp64_run(problem, tol: float = 1.0e-6, max_iters: int = 100000, device_id: int = 0) -> dict:
+def fp64_run(problem, tol: float = 1.0e-6, max_iters: int = 100000, device_id: int = 0, output: str = "numpy",
+             return_state: bool = False) -> dict:
     """One factorisation in fp64 at any size (``resnmtf_fp64_run``: the arithmetic of ``group_run``, spread over the
     whole device).  ``problem`` is one problem dict of ``group_run`` -- without its caps: k up to
     64, no limit on n * m -- and the result is one element of its list.  Bad input is refused before any device work
@@ -185,11 +269,41 @@ def fp64_run(problem, tol: float = 1.0e-6, max_iters: int = 100000, device_id: i
     A ``scipy.sparse`` matrix in ``problem["data"][v]`` is a SPARSE view: taken as its canonical
     CSC (``sparse.canonical_csc``, a copy), already pre-processed, stored and streamed sparse on the device
     (``resnmtf_fp64_run_sparse``); dense and sparse views mix freely.  A problem without one calls ``resnmtf_fp64_run``
-    exactly as before."""
+    exactly as before.
+
+    Device memory (``resnmtf_fp64_run_device``).  An entry of ``problem["data"]`` that is a ``torch``
+    tensor on ``cuda:device_id`` (2-D, fp64 / fp32 / fp16 / bf16, any strides, an expanded one included) is read where it
+    lies: one kernel builds both fp64 images of it, no host copy, no staging.  So are ``init_f[v]`` / ``init_s[v]`` /
+    ``init_g[v]`` when all three of a view are such tensors (a mix is a ``ValueError``), and ``init_lam[v]`` / ``init_mu[v]``
+    beside them (``None``: the column sums, summed on the device in the host loop's order).  The call is ordered after the
+    work enqueued on torch's current stream of that device.  ``output="torch"``: F, S, G, lambda and mu come back as fp64
+    tensors on the device (F, S, G column-major, as ``Engine.get_factors_device`` wraps its own) under the same keys;
+    ``all_error`` and ``iters`` stay NumPy.  ``return_state=True`` (needs ``output="torch"``, else ``ValueError``) adds
+    ``"state"``: per view the raw ``(F, S, G, lambda, mu)`` after the last sweep, before the normalisation -- what a later
+    call resumes from.  Every result is bit for bit the host route's on ``t.double().cpu().numpy()`` of the same tensors.
+    A problem with nothing on the device and the default flags makes the calls it made before."""
+    _device_views.check_output(output)
+    if return_state and output != "torch":
+        raise ValueError("return_state=True needs output='torch' (the raw state is left on the device)")
     lib = _lib.load()
     job = _lib.GroupJob()
     keep = []
-    if any(_sparse.is_sparse(x) for x in problem["data"]):
+    tensors = [x for key in ("data", "init_f", "init_s", "init_g", "init_lam", "init_mu") for x in (problem.get(key) or ())]
+    if output == "torch" or any(_device_views.is_device_tensor(x) for x in tensors):
+        import torch                # (lazily: nothing else in this module needs it)
+        dev = _lib.Fp64Device()
+        dev.struct_size = C.sizeof(_lib.Fp64Device)
+        sp = None
+        if any(_sparse.is_sparse(x) for x in problem["data"]):
+            sp = _lib.Fp64Sparse()
+            sp.struct_size = C.sizeof(_lib.Fp64Sparse)
+        out = _fill_group_job(job, problem, 0, max_iters, keep, sp=sp, dev=dev, device_id=device_id, device_out=output == "torch")
+        if output == "torch":
+            _fp64_device_outputs(dev, job, out, device_id, return_state)
+        dev.stream = torch.cuda.current_stream(torch.device("cuda", int(device_id))).cuda_stream
+        rc = lib.resnmtf_fp64_run_device(int(device_id), C.byref(job), None if sp is None else C.byref(sp), C.byref(dev),
+                                         float(tol), int(max_iters))
+    elif any(_sparse.is_sparse(x) for x in problem["data"]):
         sp = _lib.Fp64Sparse()
         sp.struct_size = C.sizeof(_lib.Fp64Sparse)
         out = _fill_group_job(job, problem, 0, max_iters, keep, sp=sp)
