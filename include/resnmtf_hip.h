@@ -965,6 +965,58 @@ typedef struct resnmtf_fp64_device {
 int resnmtf_fp64_run_device(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp,
                             const resnmtf_fp64_device* dev, double tol, int max_iters);
 
+/*
+ * resnmtf_fp64_run_device with SPARSE views in device memory -- what torch's sparse_csc, sparse_csr
+ * and (coalesced) sparse_coo tensors hold, for data produced on the device (the reference densifies a sparse Matrix with
+ * as.matrix, R/utils.r:416-419, and res_nmtf_inner, R/main.r:32-140, factorises the matrix these arrays stand for).  With
+ * spd NULL the call is resnmtf_fp64_run_device: the same launches, the same bits.
+ *   view[v]     layout, index_type, dtype, ptr_or_rows, idx_or_cols, values and nnz as resnmtf_set_view_sparse_device takes
+ *               them: contiguous 0-based arrays, entries in ANY order, stored positions distinct (a position stored twice
+ *               is refused, nothing is summed), explicit zeros stay stored, the view taken as PRE-PROCESSED (R/utils.r:416-422
+ *               done).  A view is given when any of its seven fields is not zero; an all-zero entry is a view that comes
+ *               from elsewhere.
+ *   stream      as dev->stream: an event is recorded there and the run's stream waits for it.  With dev and spd both
+ *               given the two must name the same stream.  The call returns when the outputs are written, so the arrays
+ *               may be freed on return.
+ * A view's data are in exactly one of four places -- job->x, sp, dev->x, spd --; all four kinds mix in one job.
+ * Every result (F, S, G, lambda, mu, All_Error, the sweep count, the raw state) and the plan of the passes are BIT FOR BIT
+ * those of resnmtf_fp64_run_sparse on the canonical CSC (columns ascending, rows ascending within a column, explicit zeros
+ * kept) of the same (row, column, value widened to fp64) set: widening is exact, the positions are distinct (so their
+ * sorted order is unique), the CSR copy is the sort by r m + c (a row's entries in ascending column order, what the
+ * host's counting sort gives), and every sum order is a function of the structure alone.
+ * Nothing runs per entry on the host and no array of size nnz, n or m crosses the bus for such a view: it is checked and
+ * sorted on the device with the kernels of resnmtf_set_view_sparse_device (a CSC input whose rows already ascend strictly
+ * within every column skips the first of the two sorts); the host reads back the failure word and the longest row and
+ * column.  The canonical arrays are built in transient allocations and copied device to device into the job's buffer:
+ * at most 48 bytes per stored entry + 8 (n + m + 2) + 24 bytes + the sort's temporary storage while a view is built, 24
+ * bytes per stored entry + 8 (n + m + 2) kept per view until the job's buffer holds it.  Free device memory is checked
+ * before each allocation (RESNMTF_ERR_ALLOC, the byte count in resnmtf_last_error(NULL)).
+ * Refused before any device work (RESNMTF_ERR_INVALID), the text naming the view: a struct_size mismatch, a view given
+ * beyond n_views, a view given in two places or in none, an unknown layout, index type or dtype, nnz < 0, a NULL array
+ * (values / idx_or_cols, and COO's rows, may be NULL only when nnz = 0), dev->stream != spd->stream; then per array one
+ * that is not device memory of device_id or is shorter than its element count.  Refused by the device checks, with
+ * resnmtf_set_view_sparse_device's texts and its lowest-offender rule: pointers that do not start at 0, are not monotone
+ * or do not end at nnz; an index out of range; a non-finite or negative value; a position stored twice.  A view without
+ * a stored entry does what resnmtf_fp64_run_sparse does with the empty CSC.  A refusal writes no output.
+ */
+typedef struct resnmtf_fp64_sparse_device_view {
+  int layout;                               /* RESNMTF_SPARSE_CSC / _CSR / _COO */
+  int index_type;                           /* RESNMTF_INDEX_I32 / _I64, one type for both index arrays */
+  int dtype;                                /* RESNMTF_DTYPE_* of values */
+  const void* ptr_or_rows;                  /* CSC: n_cols + 1 column pointers; CSR: n_rows + 1 row pointers; COO: nnz rows */
+  const void* idx_or_cols;                  /* CSC: nnz row indices; CSR and COO: nnz column indices */
+  const void* values;                       /* nnz */
+  long long nnz;
+} resnmtf_fp64_sparse_device_view;
+typedef struct resnmtf_fp64_sparse_device {
+  int struct_size;                          /* sizeof the struct */
+  void* stream;
+  resnmtf_fp64_sparse_device_view view[RESNMTF_GROUP_MAX_VIEWS];
+} resnmtf_fp64_sparse_device;
+int resnmtf_fp64_run_sparse_device(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp,
+                                   const resnmtf_fp64_device* dev, const resnmtf_fp64_sparse_device* spd, double tol,
+                                   int max_iters);
+
 /* ---- phase-level entry points (views sharded one-per-GPU; host does the exchange) ---- */
 
 /* Which image of X the streaming passes of view v use after its upload: *uses_2byte = 0 (f32 images), 1 (fp16) or

@@ -140,6 +140,19 @@ class Fp64Device(C.Structure):
                                                       "state_f", "state_s", "state_g", "state_lambda", "state_mu")])
 
 
+class Fp64SparseDeviceView(C.Structure):
+    """``resnmtf_fp64_sparse_device_view`` (include/resnmtf_hip.h): the arrays of one sparse view in device memory, as
+    ``resnmtf_set_view_sparse_device`` takes them; all zero = the view comes from elsewhere."""
+    _fields_ = [("layout", C.c_int), ("index_type", C.c_int), ("dtype", C.c_int), ("ptr_or_rows", C.c_void_p),
+                ("idx_or_cols", C.c_void_p), ("values", C.c_void_p), ("nnz", C.c_longlong)]
+
+
+class Fp64SparseDevice(C.Structure):
+    """``resnmtf_fp64_sparse_device`` (include/resnmtf_hip.h): the sparse views ``resnmtf_fp64_run_sparse_device`` reads
+    from device memory."""
+    _fields_ = [("struct_size", C.c_int), ("stream", C.c_void_p), ("view", Fp64SparseDeviceView * _MV)]
+
+
 # name -> (restype, argtypes); must list every symbol include/resnmtf_hip.h declares
 SIGNATURES = {
     "resnmtf_abi_version": (C.c_int, []),
@@ -194,6 +207,8 @@ SIGNATURES = {
     "resnmtf_fp64_sparse_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong), _ip, _ip]),
     "resnmtf_fp64_run_device": (C.c_int, [C.c_int, C.POINTER(GroupJob), C.POINTER(Fp64Sparse), C.POINTER(Fp64Device), C.c_double,
                                           C.c_int]),
+    "resnmtf_fp64_run_sparse_device": (C.c_int, [C.c_int, C.POINTER(GroupJob), C.POINTER(Fp64Sparse), C.POINTER(Fp64Device),
+                                                 C.POINTER(Fp64SparseDevice), C.c_double, C.c_int]),
     "resnmtf_bisil": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_bisil_sparse": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_bisil_device": (C.c_int, [_h, C.c_int, C.c_int, _dm, _dm, C.c_int, C.c_void_p, C.c_void_p, _dp, C.c_void_p]),

@@ -106,7 +106,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
                    spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False,
                    sparse_on_device: bool = False, output: str = "numpy", init_lm=None, return_state: bool = False,
                    post_on_device: bool = False, precision: str = "f32", fp64_sparse: bool = False,
-                   fp64_device: bool = False):
+                   fp64_device: bool = False, fp64_sparse_device: bool = False):
     """``res_nmtf_inner`` (``R/main.r:32-140``).
 
     ``data``: list of pre-processed (non-negative, column-normalised) matrices; ``row_indices[v][w]``
@@ -193,7 +193,8 @@ def res_nmtf_inner(data, row_indices, column_indices,
     validated as on the f32 route, and stored and streamed sparse (``resnmtf_fp64_run_sparse``); dense and sparse views
     mix.  The initial state is the explicit factors (with ``init_lm``) or the device's SVD initialisation through a
     short-lived sparse engine; ``host_init=True`` without explicit factors raises ``NotImplementedError``, as on the f32
-    route.  Sparse tensors in device memory stay refused, and without the flag sparse views are refused as before.
+    route.  Sparse tensors in device memory stay refused (``fp64_sparse_device`` admits them), and without the flag sparse
+    views are refused as before.
 
     ``fp64_device`` (keyword-only opt-in; a no-op with ``precision="f32"``): with
     ``precision="fp64"``, dense views, initial factors and ``init_lm`` may be ``torch`` tensors on ``cuda:device_id`` (read
@@ -204,6 +205,19 @@ def res_nmtf_inner(data, row_indices, column_indices,
     ``set_view_device`` and read with ``get_factors_device``.  Combines with ``fp64_sparse`` (host ``scipy.sparse`` views
     beside device dense views).  Still refused: ``score_bisil``, ``spurious_on_device``, ``post_on_device`` and sparse
     tensors in device memory.  Without the flag every refusal above stands word for word.
+
+    ``fp64_sparse_device`` (keyword-only opt-in; a no-op with ``precision="f32"``): with
+    ``precision="fp64"``, a 2-D ``sparse_csc`` / ``sparse_csr`` / coalesced ``sparse_coo`` tensor on ``cuda:device_id`` (or
+    its ``device_views.SparseDeviceView``) is a sparse view of the fp64 path too, read where it lies
+    (``resnmtf_fp64_run_sparse_device``): taken as pre-processed, checked and sorted on the device -- its refusals surface
+    as ``ResnmtfError`` --, never brought to the host.  The result is bit for bit that of the ``scipy.sparse`` matrix of
+    the same stored entries under ``fp64_sparse``, with one difference: an explicitly stored zero stays stored on this
+    route, while ``sparse.canonical_csc`` drops it on the host route.  Such views mix with everything ``fp64_sparse`` and
+    ``fp64_device`` admit.  Without explicit factors the start is the device's SVD initialisation through a short-lived
+    sparse engine loaded with ``set_view_sparse_device(pre_processed=True)`` (read with ``get_factors_device`` under
+    ``fp64_device``); ``host_init=True`` then raises the sparse views' ``NotImplementedError``.  ``return_init``,
+    ``output="torch"`` and ``return_state`` behave as described above.  Without the flag every refusal above stands word
+    for word, the one of sparse tensors under ``fp64_device=True`` included.
     """
     if precision not in ("f32", "fp64"):
         raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
@@ -214,7 +228,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
                                     host_init=host_init, return_init=return_init, score_bisil=score_bisil,
                                     spurious_on_device=spurious_on_device, output=output, init_lm=init_lm,
                                     return_state=return_state, post_on_device=post_on_device, fp64_sparse=fp64_sparse,
-                                    fp64_device=fp64_device)
+                                    fp64_device=fp64_device, fp64_sparse_device=fp64_sparse_device)
     device_views.check_output(output)
     _check_post_on_device(post_on_device, output)
     data = _views(data, device_id)
@@ -306,11 +320,13 @@ def res_nmtf_inner(data, row_indices, column_indices,
 def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init_g, k_vec, phi, xi, psi, n_iters, spurious,
                          distance, no_clusts, *, row_names, col_names, device_id, max_iters, seed, engine_opts, host_init,
                          return_init, score_bisil, spurious_on_device, output, init_lm, return_state, post_on_device,
-                         fp64_sparse: bool = False, fp64_device: bool = False, runner: Optional[Callable] = None):
+                         fp64_sparse: bool = False, fp64_device: bool = False, fp64_sparse_device: bool = False,
+                         runner: Optional[Callable] = None):
     """``res_nmtf_inner(precision="fp64")``: the checks of the f32 call, the refusals of what needs a live handle, the
     initial state, then one ``engine.fp64_run`` (``runner`` replaces it: a test hook).  ``fp64_device``: views, factors
     and results may live in device memory (``res_nmtf_inner``'s docstring); the runner then also gets ``output`` and
-    ``return_state``."""
+    ``return_state``.  ``fp64_sparse_device``: a sparse tensor on ``cuda:device_id`` reaches the problem as its
+    ``SparseDeviceView`` -- the same tensor, untouched."""
     def refuse(flag):
         raise NotImplementedError(f'precision="fp64": {flag} needs a live engine handle, which the fp64 path does not '
                                   'keep (it runs through resnmtf_fp64_run); use precision="f32" for it')
@@ -335,6 +351,9 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
             sparse.validate(d, f"view {v}")
             views.append(d)
             continue
+        if fp64_sparse_device and device_views.is_sparse_device_view(d):      # opt-in: read where it lies (section 24)
+            views.append(device_views.as_sparse_view(d, device_id, f"view {v}"))
+            continue
         if sparse.is_sparse_view(d) or device_views.is_sparse_tensor(d):
             refuse(f"sparse views (view {v})")
         if device_views.is_device_view(d):
@@ -344,8 +363,8 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
             continue
         views.append(np.asarray(d, dtype=np.float64))
     data, n_v = views, len(views)
-    is_sp = [sparse.is_sparse(d) for d in data]
-    if any(device_views.is_device_view(d) for d in data) and host_init and (init_f is None or init_g is None or init_s is None):
+    is_sp = [sparse.is_sparse_view(d) for d in data]
+    if any(device_views.is_device_view(d) and not is_sp[v] for v, d in enumerate(data)) and host_init and (init_f is None or init_g is None or init_s is None):
         raise NotImplementedError("host_init=True (NumPy's dense SVD) is not available for views in device memory; the "
                                   "device initialisation (host_init=False) works on them")
     if any(is_sp) and host_init and (init_f is None or init_g is None or init_s is None):

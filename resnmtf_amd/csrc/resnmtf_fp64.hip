@@ -1,6 +1,7 @@
-// Device-wide fp64 factorisation (DESIGN.md sections 21 to 23): the host side of resnmtf_fp64_run, resnmtf_fp64_run_sparse,
-// resnmtf_fp64_run_device and the two plan queries, and -- through resnmtf_fp64.hip.inc, resnmtf_fp64_sparse.hip.inc (sparse
-// views) and resnmtf_fp64_device.hip.inc (views and factors from device memory) -- their kernels.  A translation unit of its own: the kernels get a code object of their
+// Device-wide fp64 factorisation (DESIGN.md sections 21 to 24): the host side of resnmtf_fp64_run, resnmtf_fp64_run_sparse,
+// resnmtf_fp64_run_device, resnmtf_fp64_run_sparse_device and the two plan queries, and -- through resnmtf_fp64.hip.inc,
+// resnmtf_fp64_sparse.hip.inc (sparse views), resnmtf_fp64_device.hip.inc (views and factors from device memory) and
+// resnmtf_fp64_sparse_device.hip.inc (sparse views from device memory) -- their kernels.  A translation unit of its own: the kernels get a code object of their
 // own and leave the main unit's device code as it was.  The job checks and the error text are the main unit's
 // (resnmtf_internal.h): this entry and resnmtf_group_run refuse the same things with the same texts.
 #include <hip/hip_runtime.h>
@@ -17,6 +18,7 @@
 #include "resnmtf_fp64.hip.inc"
 #include "resnmtf_fp64_sparse.hip.inc"
 #include "resnmtf_fp64_device.hip.inc"
+#include "resnmtf_fp64_sparse_device.hip.inc"
 
 namespace {
 struct DeviceBuffer {
@@ -444,8 +446,175 @@ std::string fp64_check_device_pointers(int device_id, const resnmtf_group_job& j
   return "";
 }
 
+// ---- resnmtf_fp64_run_sparse_device (section 24): sparse views from device memory ----
+inline bool fp64_spd_given(const resnmtf_fp64_sparse_device_view& c) {
+  return c.layout || c.index_type || c.dtype || c.ptr_or_rows || c.idx_or_cols || c.values || c.nnz;
+}
+
+// the refusals that need no device: the text, or "" when every view of the job has its data in exactly one place and
+// every sparse device view is well formed
+std::string fp64_check_sparse_device_struct(const resnmtf_group_job& j, const resnmtf_fp64_sparse* sp, const resnmtf_fp64_device* dev,
+                                            const resnmtf_fp64_sparse_device& d) {
+  if (dev && dev->struct_size == (int)sizeof(resnmtf_fp64_device) && dev->stream != d.stream)
+    return "dev->stream and spd->stream differ: both structs name the one stream the caller's work was enqueued on";
+  if (j.struct_size != (int)sizeof(resnmtf_group_job) || j.n_views < 1 || j.n_views > RESNMTF_GROUP_MAX_VIEWS) return "";   // (the job check says it)
+  auto view = [](int v) { return "view " + std::to_string(v) + ": "; };
+  for (int v = 0; v < RESNMTF_GROUP_MAX_VIEWS; ++v) {
+    const resnmtf_fp64_sparse_device_view& c = d.view[v];
+    const bool given = fp64_spd_given(c);
+    if (v >= j.n_views) {
+      if (given) return view(v) + "spd->view is given beyond n_views";
+      continue;
+    }
+    const bool in_job = j.x[v] != nullptr, in_sp = sp && sp->view[v].col_ptr, in_dev = dev && dev->x[v].ptr;
+    const int places = (in_job ? 1 : 0) + (in_sp ? 1 : 0) + (in_dev ? 1 : 0) + (given ? 1 : 0);
+    if (places > 1 && given)
+      return view(v) + "x is given in two places, in sparse device arrays (spd->view) and " +
+             (in_job ? "in the job (job->x)" : in_sp ? "as host CSC arrays (sp->view)" : "as a device matrix (dev->x)") +
+             ": exactly one of job->x, sp, dev->x and spd";
+    if (places == 0) return view(v) + "x is given in none of job->x, sp, dev->x and spd";
+    if (!given) continue;
+    const std::string w = view(v) + "spd->view: ";
+    if (c.layout != RESNMTF_SPARSE_CSC && c.layout != RESNMTF_SPARSE_CSR && c.layout != RESNMTF_SPARSE_COO)
+      return w + "unknown layout: one of RESNMTF_SPARSE_CSC / _CSR / _COO";
+    if (c.index_type != RESNMTF_INDEX_I32 && c.index_type != RESNMTF_INDEX_I64) return w + "unknown index type: RESNMTF_INDEX_I32 or _I64";
+    if (c.dtype != RESNMTF_DTYPE_F64 && c.dtype != RESNMTF_DTYPE_F32 && c.dtype != RESNMTF_DTYPE_F16 && c.dtype != RESNMTF_DTYPE_BF16)
+      return w + "unknown dtype: one of RESNMTF_DTYPE_F64 / _F32 / _F16 / _BF16";
+    if (c.nnz < 0) return w + "nnz is negative";
+    const bool coo = c.layout == RESNMTF_SPARSE_COO;
+    if ((!c.ptr_or_rows && !(coo && c.nnz == 0)) || ((!c.idx_or_cols || !c.values) && c.nnz > 0))
+      return w + "ptr_or_rows / idx_or_cols / values is NULL";
+  }
+  return "";
+}
+
+// the refusals that ask the runtime: every array is device memory of device_id and holds its element count
+std::string fp64_check_sparse_device_pointers(int device_id, const resnmtf_group_job& j, const resnmtf_fp64_sparse_device& d, unsigned spd_views) {
+  for (int v = 0; v < j.n_views; ++v) {
+    if (!((spd_views >> v) & 1u)) continue;
+    const resnmtf_fp64_sparse_device_view& c = d.view[v];
+    const bool coo = c.layout == RESNMTF_SPARSE_COO, csc = c.layout == RESNMTF_SPARSE_CSC;
+    const size_t ib = c.index_type == RESNMTF_INDEX_I64 ? 8 : 4, nnz = (size_t)c.nnz;
+    const size_t lines = (size_t)(csc ? j.n_cols[v] : j.n_rows[v]);
+    struct Arr { const char* name; const void* p; size_t count, elem; };
+    const Arr arrs[3] = {{"ptr_or_rows", c.ptr_or_rows, coo ? nnz : lines + 1, ib}, {"idx_or_cols", c.idx_or_cols, nnz, ib},
+                         {"values", c.values, nnz, fp64_dtype_bytes(c.dtype)}};
+    for (const Arr& a : arrs) {
+      if (!a.p) continue;                    // (NULL only where nnz = 0 allows it)
+      bool beyond = false;
+      if (!fp64_on_device(device_id, a.p, a.count * a.elem, beyond))
+        return "view " + std::to_string(v) + ": spd->view." + a.name +
+               (beyond ? " is shorter than its element count (" + std::to_string(a.count) + " elements of " + std::to_string(a.elem) + " bytes)"
+                       : " is not device memory of device " + std::to_string(device_id));
+    }
+  }
+  return "";
+}
+
+// The owner of the transient device memory of the sparse device views: free device memory is asked before each
+// allocation, a refusal leaves RESNMTF_ERR_ALLOC's text and nullptr; everything still held is freed on the way out.
+class F64Transient {
+ public:
+  F64Transient() = default;
+  F64Transient(const F64Transient&) = delete;
+  F64Transient& operator=(const F64Transient&) = delete;
+  ~F64Transient() { release_all(); }
+  void* take(size_t bytes) {
+    bytes = std::max<size_t>(bytes, 8);
+    size_t free_b = 0, total_b = 0;
+    hipError_t e = hipMemGetInfo(&free_b, &total_b);
+    void* p = nullptr;
+    if (e == hipSuccess && bytes <= free_b) e = hipMalloc(&p, bytes);
+    if (e != hipSuccess || !p) {
+      (void)hipGetLastError();
+      resnmtf_set_create_error("fp64_run: " + std::to_string(bytes) + " bytes asked for (the canonical arrays of a sparse view in device memory), " +
+                               std::to_string(free_b) + " free on the device");
+      return nullptr;
+    }
+    held_.push_back(p);
+    return p;
+  }
+  template <class T>
+  T* take_n(size_t count) { return static_cast<T*>(take(count * sizeof(T))); }
+  void release(const void* p) {
+    for (void*& q : held_)
+      if (q && q == p) { (void)hipFree(q); q = nullptr; }
+  }
+  void release_all() {
+    for (void*& q : held_)
+      if (q) { (void)hipFree(q); q = nullptr; }
+    held_.clear();
+  }
+  // (the sort's temporary storage, asked for by the main unit: remembered, so that release_sort_storage() can free it)
+  static void* alloc(void* self, size_t bytes) {
+    F64Transient* t = static_cast<F64Transient*>(self);
+    return t->sort_storage_ = t->take(bytes);
+  }
+  void release_sort_storage() { release(sort_storage_); sort_storage_ = nullptr; }
+ private:
+  std::vector<void*> held_;
+  void* sort_storage_ = nullptr;
+};
+
+// what the build of one sparse device view leaves in transient memory until the job's buffer holds it
+struct F64SpdView {
+  long long *cptr = nullptr, *rptr = nullptr;
+  int *cidx = nullptr, *ridx = nullptr;
+  const double* cval = nullptr;
+  const long long* perm = nullptr;
+};
+
+// View v of spd, n x m: checked and sorted on stream st (resnmtf_sparse_device_canonical), its longest row and column
+// reduced on the device; `sh` as fp64_check_csc fills it for the same canonical CSC.  Peak transient memory: five 8-byte
+// arrays of nnz, two 4-byte ones, the two pointer arrays, 24 bytes of flags and rocPRIM's storage; on return the two
+// key arrays, the spare payload array and that storage are free again.  RESNMTF_OK, or the code to return with the
+// error text set.
+int fp64_build_sparse_device_view(hipStream_t st, F64Transient& tr, int v, const resnmtf_fp64_sparse_device_view& c, int n, int m,
+                                  F64SpdView& out, F64SparseShape& sh) {
+  resnmtf_sparse_device_build b{};
+  b.layout = c.layout; b.index_type = c.index_type; b.dtype = c.dtype; b.n = n; b.m = m; b.nnz = c.nnz;
+  b.ptr_or_rows = c.ptr_or_rows; b.idx_or_cols = c.idx_or_cols; b.values = c.values;
+  const size_t nnz = (size_t)c.nnz;
+  unsigned long long* words = tr.take_n<unsigned long long>(3);        // the two flag words, then the two longest-line ints
+  if (!words) return RESNMTF_ERR_ALLOC;
+  b.flags = words;
+  int* longest = reinterpret_cast<int*>(words + 2);
+  if (nnz > 0) {
+    for (auto& p : b.key) if (!(p = tr.take_n<unsigned long long>(nnz))) return RESNMTF_ERR_ALLOC;
+    for (auto& p : b.pay) if (!(p = tr.take_n<long long>(nnz))) return RESNMTF_ERR_ALLOC;
+    if (!(b.cptr = tr.take_n<long long>((size_t)m + 1)) || !(b.rptr = tr.take_n<long long>((size_t)n + 1)) ||
+        !(b.cidx = tr.take_n<int>(nnz)) || !(b.ridx = tr.take_n<int>(nnz)))
+      return RESNMTF_ERR_ALLOC;
+  }
+  std::string why;
+  const int rc = resnmtf_sparse_device_canonical(st, b, &F64Transient::alloc, &tr, why);
+  if (rc == RESNMTF_ERR_INVALID) resnmtf_set_create_error("view " + std::to_string(v) + ": " + why);
+  if (rc == RESNMTF_ERR_HIP) resnmtf_set_create_error("fp64_run: view " + std::to_string(v) + ": " + why);
+  if (rc != RESNMTF_OK) return rc;
+  sh.sparse = true; sh.nnz = nnz; sh.longest_row = sh.longest_col = 0;
+  if (nnz == 0) return RESNMTF_OK;           // (zero pointers: the zeros of the job's buffer)
+  int host_longest[2] = {0, 0};
+  hipError_t e = hipMemsetAsync(longest, 0, 2 * sizeof(int), st);
+  if (e == hipSuccess) {
+    fp64_spd_longest(st, b.rptr, n, b.cptr, m, longest);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(host_longest, longest, sizeof(host_longest), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    resnmtf_set_create_error(std::string("fp64_run: view ") + std::to_string(v) + ": " + hipGetErrorString(e));
+    return RESNMTF_ERR_HIP;
+  }
+  sh.longest_row = host_longest[0]; sh.longest_col = host_longest[1];
+  out.cptr = b.cptr; out.rptr = b.rptr; out.cidx = b.cidx; out.ridx = b.ridx; out.cval = b.csc_values; out.perm = b.csr_perm;
+  for (const void* p : {(const void*)b.key[0], (const void*)b.key[1], (const void*)b.pay[0], (const void*)b.pay[1], (const void*)b.pay[2]})
+    if (p != (const void*)out.cval && p != (const void*)out.perm) tr.release(p);
+  tr.release_sort_storage();
+  return RESNMTF_OK;
+}
+
 int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp, const resnmtf_fp64_device* dev,
-                  double tol, int max_iters);
+                  const resnmtf_fp64_sparse_device* spd, double tol, int max_iters);
 }  // namespace
 
 extern "C" {
@@ -468,7 +637,7 @@ int resnmtf_fp64_sparse_plan(int n_rows, int n_cols, int k, const long long* col
 }
 
 int resnmtf_fp64_run(int device_id, const resnmtf_group_job* job, double tol, int max_iters) {
-  return fp64_run_impl(device_id, job, nullptr, nullptr, tol, max_iters);
+  return fp64_run_impl(device_id, job, nullptr, nullptr, nullptr, tol, max_iters);
 }
 
 int resnmtf_fp64_run_sparse(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp, double tol,
@@ -477,7 +646,7 @@ int resnmtf_fp64_run_sparse(int device_id, const resnmtf_group_job* job, const r
     resnmtf_set_create_error("resnmtf_fp64_sparse struct_size mismatch");
     return RESNMTF_ERR_INVALID;
   }
-  return fp64_run_impl(device_id, job, sp, nullptr, tol, max_iters);
+  return fp64_run_impl(device_id, job, sp, nullptr, nullptr, tol, max_iters);
 }
 
 int resnmtf_fp64_run_device(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp,
@@ -486,7 +655,23 @@ int resnmtf_fp64_run_device(int device_id, const resnmtf_group_job* job, const r
     resnmtf_set_create_error("resnmtf_fp64_sparse struct_size mismatch");
     return RESNMTF_ERR_INVALID;
   }
-  return fp64_run_impl(device_id, job, sp, dev, tol, max_iters);
+  return fp64_run_impl(device_id, job, sp, dev, nullptr, tol, max_iters);
+}
+
+// res_nmtf_inner (R/main.r:32-140) with sparse views that are already in device memory (R/utils.r:416-419 densifies a sparse
+// Matrix; these arrays stand for that matrix): resnmtf_fp64_run_device's body, the views of spd checked and sorted on the
+// device first
+int resnmtf_fp64_run_sparse_device(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp,
+                                   const resnmtf_fp64_device* dev, const resnmtf_fp64_sparse_device* spd, double tol, int max_iters) {
+  if (sp && sp->struct_size != (int)sizeof(resnmtf_fp64_sparse)) {
+    resnmtf_set_create_error("resnmtf_fp64_sparse struct_size mismatch");
+    return RESNMTF_ERR_INVALID;
+  }
+  if (spd && spd->struct_size != (int)sizeof(resnmtf_fp64_sparse_device)) {
+    resnmtf_set_create_error("resnmtf_fp64_sparse_device struct_size mismatch");
+    return RESNMTF_ERR_INVALID;
+  }
+  return fp64_run_impl(device_id, job, sp, dev, spd, tol, max_iters);
 }
 
 int resnmtf_fp64_plan(int n_rows, int n_cols, int k, int* out) {
@@ -506,11 +691,12 @@ int resnmtf_fp64_plan(int n_rows, int n_cols, int k, int* out) {
 }  // extern "C"
 
 namespace {
-// resnmtf_fp64_run (sp == nullptr), resnmtf_fp64_run_sparse (dev == nullptr) and resnmtf_fp64_run_device: one body.  Without
-// a sparse view every step below is resnmtf_fp64_run's own -- the same layout, the same launches, the same bits --, and
-// without dev every step is resnmtf_fp64_run_sparse's.
+// resnmtf_fp64_run (sp == nullptr), resnmtf_fp64_run_sparse (dev == nullptr), resnmtf_fp64_run_device (spd == nullptr) and
+// resnmtf_fp64_run_sparse_device: one body.  Without a sparse view every step below is resnmtf_fp64_run's own -- the same
+// layout, the same launches, the same bits --, without dev every step is resnmtf_fp64_run_sparse's, and without spd every
+// step is resnmtf_fp64_run_device's.
 int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp, const resnmtf_fp64_device* dev,
-                  double tol, int max_iters) {
+                  const resnmtf_fp64_sparse_device* spd, double tol, int max_iters) {
   auto bad = [](const std::string& msg) { resnmtf_set_create_error(msg); return RESNMTF_ERR_INVALID; };
   if (!job) return bad("job is NULL");
   if (max_iters < 1) return bad("max_iters must be >= 1");
@@ -520,9 +706,13 @@ int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp6
   if (sp)
     for (int v = 0; v < RESNMTF_GROUP_MAX_VIEWS; ++v)
       if (sp->view[v].col_ptr) sparse_views |= 1u << v;
+  unsigned spd_views = 0;                   // bit v: view v comes as sparse arrays in device memory (section 24)
+  if (spd)
+    for (int v = 0; v < RESNMTF_GROUP_MAX_VIEWS; ++v)
+      if (fp64_spd_given(spd->view[v])) spd_views |= 1u << v;
   // a shape no device holds is refused on its byte count before the data behind it is read
   if (fp64_shapes_ok(j)) {
-    const long double img = fp64_image_bytes(j, sparse_views);
+    const long double img = fp64_image_bytes(j, sparse_views | spd_views);
     if (img >= 0x1p58L) {
       char text[160];
       std::snprintf(text, sizeof(text), "fp64_run: more than %.0Lf bytes asked for (the fp64 images of the views alone)", img);
@@ -530,15 +720,23 @@ int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp6
       return RESNMTF_ERR_ALLOC;
     }
   }
-  F64DeviceUse use;                         // what comes from, and goes to, device memory (resnmtf_fp64_run_device)
-  if (dev) {
-    const std::string why = fp64_check_device_struct(j, *dev, sparse_views, use);
+  if (spd) {                                // (first: a view in two places or in none is named with all four of them)
+    const std::string why = fp64_check_sparse_device_struct(j, sp, dev, *spd);
     if (!why.empty()) return bad(why);
   }
-  if (const char* why = resnmtf_check_fp64_job(j, max_iters, sparse_views | use.views, use.factors, use.out)) return bad(why);
+  F64DeviceUse use;                         // what comes from, and goes to, device memory (resnmtf_fp64_run_device)
+  if (dev) {
+    const std::string why = fp64_check_device_struct(j, *dev, sparse_views | spd_views, use);
+    if (!why.empty()) return bad(why);
+  }
+  if (const char* why = resnmtf_check_fp64_job(j, max_iters, sparse_views | use.views | spd_views, use.factors, use.out)) return bad(why);
   if (sparse_views >> j.n_views) return bad("a sparse view is given beyond n_views");
   if (dev) {
     const std::string why = fp64_check_device_pointers(device_id, j, *dev, use);
+    if (!why.empty()) return bad(why);
+  }
+  if (spd_views) {
+    const std::string why = fp64_check_sparse_device_pointers(device_id, j, *spd, spd_views);
     if (!why.empty()) return bad(why);
   }
   F64SparseShape shapes[RESNMTF_GROUP_MAX_VIEWS];
@@ -550,25 +748,52 @@ int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp6
     if (!why.empty()) return bad("view " + std::to_string(v) + ": " + why);
   }
 
-  const int cap = j.n_iters > 0 ? std::min(j.n_iters, max_iters) : max_iters;
-  F64Layout L;
-  fp64_layout(j, cap, L, sparse_views ? shapes : nullptr);
-  const size_t bytes = L.total * sizeof(double);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { resnmtf_set_create_error("no HIP device"); return RESNMTF_ERR_NO_DEVICE; }
   if (device_id < 0 || device_id >= ndev) return bad("device_id out of range");
   hipError_t e = hipSetDevice(device_id);
   if (e != hipSuccess) { resnmtf_set_create_error(std::string("hipSetDevice: ") + hipGetErrorString(e)); return RESNMTF_ERR_HIP; }
+  hipStream_t st = nullptr;
+  // the sparse views in device memory (section 24): the layout needs their longest lines, so their canonical arrays are
+  // built first, in transient memory, on the run's own stream, and copied into the job's buffer once that exists
+  F64Transient transient;
+  F64SpdView spdv[RESNMTF_GROUP_MAX_VIEWS];
+  if (spd_views) {
+    e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e != hipSuccess) { resnmtf_set_create_error(std::string("hipStreamCreate: ") + hipGetErrorString(e)); return RESNMTF_ERR_HIP; }
+    hipEvent_t ev = nullptr;
+    e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e == hipSuccess) {
+      e = hipEventRecord(ev, static_cast<hipStream_t>(spd->stream));
+      if (e == hipSuccess) e = hipStreamWaitEvent(st, ev, 0);
+      (void)hipEventDestroy(ev);
+    }
+    int rc = RESNMTF_OK;
+    if (e != hipSuccess) { resnmtf_set_create_error(std::string("fp64_run: ") + hipGetErrorString(e)); rc = RESNMTF_ERR_HIP; }
+    for (int v = 0; v < j.n_views && rc == RESNMTF_OK; ++v)
+      if ((spd_views >> v) & 1u) rc = fp64_build_sparse_device_view(st, transient, v, spd->view[v], j.n_rows[v], j.n_cols[v], spdv[v], shapes[v]);
+    if (rc != RESNMTF_OK) {
+      (void)hipStreamSynchronize(st);
+      (void)hipStreamDestroy(st);
+      return rc;
+    }
+  }
+
+  const int cap = j.n_iters > 0 ? std::min(j.n_iters, max_iters) : max_iters;
+  F64Layout L;
+  fp64_layout(j, cap, L, (sparse_views | spd_views) ? shapes : nullptr);
+  const size_t bytes = L.total * sizeof(double);
+  auto drop_stream = [&]() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } };
   size_t free_b = 0, total_b = 0;
   e = hipMemGetInfo(&free_b, &total_b);
-  if (e != hipSuccess) { resnmtf_set_create_error(std::string("fp64_run: ") + hipGetErrorString(e)); return RESNMTF_ERR_HIP; }
+  if (e != hipSuccess) { drop_stream(); resnmtf_set_create_error(std::string("fp64_run: ") + hipGetErrorString(e)); return RESNMTF_ERR_HIP; }
   if (bytes > free_b) {
+    drop_stream();
     resnmtf_set_create_error("fp64_run: " + std::to_string(bytes) + " bytes asked for (two fp64 images of every view, factors, slabs), " +
                      std::to_string(free_b) + " free on the device");
     return RESNMTF_ERR_ALLOC;
   }
-  hipStream_t st = nullptr;
-  e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+  if (!st) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
   if (e != hipSuccess) { resnmtf_set_create_error(std::string("hipStreamCreate: ") + hipGetErrorString(e)); return RESNMTF_ERR_HIP; }
   DeviceBuffer owner;                      // (freed on every path out; hipFree waits for the stream's work)
   e = hipMalloc(&owner.p, std::max<size_t>(bytes, 8));
@@ -604,6 +829,20 @@ int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp6
     std::vector<double> img;
     for (int v = 0; v < V && e == hipSuccess; ++v) {
       const F64View& w = L.vw[v];
+      if ((spd_views >> v) & 1u) {           // from device memory (section 24): the canonical arrays device to device, the
+        const F64SpdView& c = spdv[v];       // CSR values gathered in fp64; nnz = 0: the zeros of the memset are the view
+        if (w.nnz == 0) continue;
+        e = hipMemcpyAsync(buf + w.cptr, c.cptr, ((size_t)w.m + 1) * sizeof(long long), hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(buf + w.rptr, c.rptr, ((size_t)w.n + 1) * sizeof(long long), hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(buf + w.cval, c.cval, w.nnz * sizeof(double), hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(buf + w.cidx, c.cidx, w.nnz * sizeof(int), hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(buf + w.ridx, c.ridx, w.nnz * sizeof(int), hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) {
+          fp64_spd_gather(st, c.perm, c.cval, (long long)w.nnz, buf + w.rval);
+          e = hipGetLastError();
+        }
+        continue;
+      }
       if (w.sparse) {                        // the CSC arrays as given, and the CSR copy built here
         const resnmtf_fp64_sparse_view& c = sp->view[v];
         std::vector<long long> rp;
@@ -636,6 +875,10 @@ int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp6
         for (size_t i = 0; i < n; ++i) img[c + i * w.ldm] = x[i + c * n];
       e = hipMemcpy(buf + w.xt, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice);
     }
+  }
+  if (e == hipSuccess && spd_views) {       // the job's buffer holds the views: their transient arrays go
+    e = hipStreamSynchronize(st);
+    transient.release_all();
   }
   if (e != hipSuccess) return fail(e);
   std::vector<double> host(L.out_end - L.out_begin, 0.0);

@@ -2292,6 +2292,54 @@ int resnmtf_subsample_view_sparse(resnmtf_handle* dst, int v, resnmtf_handle* sr
   return finish_sparse_build(dst, a, sc, sb, nnz, 0, e, "subsample_view_sparse");
 }
 
+// ---- what resnmtf_set_view_sparse_device and resnmtf_sparse_device_canonical (the fp64 path) share:
+// the launches of the device checks and the text of a failure word
+extern "C++" {
+namespace {
+void spdv_launch_ptr_check(hipStream_t st, bool i64, const void* ptr, int lines, long long nnz, unsigned long long* flags) {
+  if (i64) hipLaunchKernelGGL(sparse_device_ptr_check_kernel<true>, dim3(ceil_div(lines + 1, 256)), dim3(256), 0, st, ptr, lines, nnz, flags);
+  else hipLaunchKernelGGL(sparse_device_ptr_check_kernel<false>, dim3(ceil_div(lines + 1, 256)), dim3(256), 0, st, ptr, lines, nnz, flags);
+}
+// nnz >= 1
+void spdv_launch_entries(hipStream_t st, int layout, bool i64, int dtype, const void* a0, const void* a1, const void* values, long long nnz,
+                         int n, int m, unsigned long long* key, double* val, unsigned char* col_pos, unsigned long long* flags) {
+  const dim3 grid((unsigned)((nnz + 255) / 256));
+  pick_int<RESNMTF_SPARSE_CSC, RESNMTF_SPARSE_CSR, RESNMTF_SPARSE_COO>(layout, [&](auto lay) {
+    pick_bools([&](auto wide) {
+      pick_int<RESNMTF_DTYPE_F64, RESNMTF_DTYPE_F32, RESNMTF_DTYPE_F16, RESNMTF_DTYPE_BF16>(dtype, [&](auto dt) {
+        hipLaunchKernelGGL((sparse_device_entries_kernel<decltype(lay)::value, decltype(wide)::value, decltype(dt)::value>), grid, dim3(256), 0, st,
+                           a0, a1, values, nnz, n, m, key, val, col_pos, flags);
+      });
+    }, i64);
+  });
+}
+// word = kind << 56 | the lowest offending line, entry or sorted position; dup_key: the sorted key there (SPDV_DUPLICATE)
+std::string spdv_refusal_text(unsigned long long word, bool csc, long long nnz, int n, unsigned long long dup_key) {
+  const char* pname = csc ? "col_ptr" : "row_ptr";
+  const char* lname = csc ? "column" : "row";
+  const unsigned long long kind = word >> 56;
+  const std::string num = std::to_string((long long)(word & ((1ull << 56) - 1ull)));
+  switch (kind) {
+    case SPDV_PTR_FIRST: return std::string(pname) + "[0] must be 0 (0-based " + (csc ? "CSC)" : "CSR)");
+    case SPDV_PTR_MONOTONE: return std::string(pname) + " is not monotone (" + lname + " " + num + ")";
+    case SPDV_PTR_LAST: return std::string(pname) + "[" + num + "] must equal nnz = " + std::to_string(nnz);
+    case SPDV_ROW_RANGE: return "row index out of range (entry " + num + ")";
+    case SPDV_COL_RANGE: return "column index out of range (entry " + num + ")";
+    case SPDV_NON_FINITE: return "non-finite entry (entry " + num + ")";
+    case SPDV_NEGATIVE:
+      return "negative entry (entry " + num +
+             "): make_non_neg (R/utils.r:20-27) shifts a whole column by its minimum, which would turn every implicit zero of a "
+             "sparse view positive -- shift the data on the host and upload it dense";
+    case SPDV_DUPLICATE:
+      return "position (row " + std::to_string(dup_key % (unsigned long long)n) + ", column " + std::to_string(dup_key / (unsigned long long)n) +
+             ") is stored twice: coalesce the entries first (nothing is summed)";
+    default:
+      return "column " + num + " is all zero: matrix_normalisation (R/utils.r:86-88) would divide it by zero (a NaN column in the reference)";
+  }
+}
+}  // namespace
+}  // extern "C++"
+
 // A sparse view from CSC / CSR / COO arrays in the caller's device memory (resnmtf_sparse_device_view.hip.inc, DESIGN.md
 // section 16): checked on the device, turned into (position, value) pairs and built by finish_sparse_build.  Transient
 // device memory: SparseBuild's 40 bytes per entry + m flag bytes + the two flag words.
@@ -2319,8 +2367,6 @@ int resnmtf_set_view_sparse_device(resnmtf_handle* h, int v, int layout, const v
     if (p && !on_handle_device(h, p))
       return h->fail(RESNMTF_ERR_INVALID, w + "an array is not device memory of the handle's device (host data: resnmtf_set_view_csc)");
   const int n = vs.n, m = vs.m, lines = csc ? m : n;
-  const char* pname = csc ? "col_ptr" : "row_ptr";
-  const char* lname = csc ? "column" : "row";
   const bool i64 = index_type == RESNMTF_INDEX_I64;
   HIP_TRY(h, hipSetDevice(h->opt.device_id));
   if (int rc = sync_both(h)) return rc;
@@ -2336,31 +2382,12 @@ int resnmtf_set_view_sparse_device(resnmtf_handle* h, int v, int layout, const v
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return h->fail_hip(what, e);
     if (host_flags[0] == kSpdvNone) return RESNMTF_OK;
-    const unsigned long long kind = host_flags[0] >> 56;
-    const long long at = (long long)(host_flags[0] & ((1ull << 56) - 1ull));
-    const std::string num = std::to_string(at);
-    switch (kind) {
-      case SPDV_PTR_FIRST: return h->fail(RESNMTF_ERR_INVALID, std::string(pname) + "[0] must be 0 (0-based " + (csc ? "CSC)" : "CSR)"));
-      case SPDV_PTR_MONOTONE: return h->fail(RESNMTF_ERR_INVALID, std::string(pname) + " is not monotone (" + lname + " " + num + ")");
-      case SPDV_PTR_LAST: return h->fail(RESNMTF_ERR_INVALID, std::string(pname) + "[" + num + "] must equal nnz = " + std::to_string(nnz));
-      case SPDV_ROW_RANGE: return h->fail(RESNMTF_ERR_INVALID, "row index out of range (entry " + num + ")");
-      case SPDV_COL_RANGE: return h->fail(RESNMTF_ERR_INVALID, "column index out of range (entry " + num + ")");
-      case SPDV_NON_FINITE: return h->fail(RESNMTF_ERR_INVALID, "non-finite entry (entry " + num + ")");
-      case SPDV_NEGATIVE:
-        return h->fail(RESNMTF_ERR_INVALID, "negative entry (entry " + num +
-                       "): make_non_neg (R/utils.r:20-27) shifts a whole column by its minimum, which would turn every implicit zero of a "
-                       "sparse view positive -- shift the data on the host and upload it dense");
-      case SPDV_DUPLICATE: {
-        unsigned long long k = 0;
-        e = hipMemcpy(&k, sorted_keys + at, sizeof(k), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return h->fail_hip(what, e);
-        return h->fail(RESNMTF_ERR_INVALID, "position (row " + std::to_string(k % (unsigned long long)n) + ", column " + std::to_string(k / (unsigned long long)n) +
-                       ") is stored twice: coalesce the entries first (nothing is summed)");
-      }
-      default:
-        return h->fail(RESNMTF_ERR_INVALID, "column " + num +
-                       " is all zero: matrix_normalisation (R/utils.r:86-88) would divide it by zero (a NaN column in the reference)");
+    unsigned long long k = 0;                 // a duplicate is named by its position: the sorted key there
+    if (host_flags[0] >> 56 == SPDV_DUPLICATE) {
+      e = hipMemcpy(&k, sorted_keys + (host_flags[0] & ((1ull << 56) - 1ull)), sizeof(k), hipMemcpyDeviceToHost);
+      if (e != hipSuccess) return h->fail_hip(what, e);
     }
+    return h->fail(RESNMTF_ERR_INVALID, spdv_refusal_text(host_flags[0], csc, nnz, n, k));
   };
   hipError_t e = wait_for_caller(h, stream);
   if (e == hipSuccess) e = hipMemcpyAsync(flags, host_flags, sizeof(host_flags), hipMemcpyHostToDevice, st);
@@ -2368,8 +2395,7 @@ int resnmtf_set_view_sparse_device(resnmtf_handle* h, int v, int layout, const v
   if (e != hipSuccess) return h->fail_hip(what, e);
   // ---- the line pointers, judged before any kernel bounds a search by them
   if (!coo) {
-    if (i64) hipLaunchKernelGGL(sparse_device_ptr_check_kernel<true>, dim3(ceil_div(lines + 1, 256)), dim3(256), 0, st, ptr_or_rows, lines, nnz, flags);
-    else hipLaunchKernelGGL(sparse_device_ptr_check_kernel<false>, dim3(ceil_div(lines + 1, 256)), dim3(256), 0, st, ptr_or_rows, lines, nnz, flags);
+    spdv_launch_ptr_check(st, i64, ptr_or_rows, lines, nnz, flags);
     HIP_TRY(h, hipGetLastError());
     if (int rc = verdict(nullptr)) return rc;
   }
@@ -2379,15 +2405,7 @@ int resnmtf_set_view_sparse_device(resnmtf_handle* h, int v, int layout, const v
   const SparseBuild sb = take_sparse_build(sc, nnz, n, m);
   if (sc.error() != hipSuccess) return h->fail_hip("hipMalloc set_view_sparse_device build", sc.error());
   if (nnz > 0) {
-    const dim3 grid((unsigned)((nnz + 255) / 256));
-    pick_int<RESNMTF_SPARSE_CSC, RESNMTF_SPARSE_CSR, RESNMTF_SPARSE_COO>(layout, [&](auto lay) {
-      pick_bools([&](auto wide) {
-        pick_int<RESNMTF_DTYPE_F64, RESNMTF_DTYPE_F32, RESNMTF_DTYPE_F16, RESNMTF_DTYPE_BF16>(dtype, [&](auto dt) {
-          hipLaunchKernelGGL((sparse_device_entries_kernel<decltype(lay)::value, decltype(wide)::value, decltype(dt)::value>), grid, dim3(256), 0, st,
-                             ptr_or_rows, idx_or_cols, values, nnz, n, m, sb.key[0], reinterpret_cast<double*>(sb.pay[0]), col_pos, flags);
-        });
-      }, i64);
-    });
+    spdv_launch_entries(st, layout, i64, dtype, ptr_or_rows, idx_or_cols, values, nnz, n, m, sb.key[0], reinterpret_cast<double*>(sb.pay[0]), col_pos, flags);
     if (col_pos) hipLaunchKernelGGL(sparse_device_columns_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, col_pos, m, flags);
     HIP_TRY(h, hipGetLastError());
     if (int rc = verdict(nullptr)) return rc;
@@ -4721,6 +4739,84 @@ const char* resnmtf_check_fp64_job(const resnmtf_group_job& j, int max_iters, un
   return check_group_job(j, max_iters, kFp64Limits, x_elsewhere, factors_elsewhere, outputs_elsewhere);
 }
 void resnmtf_set_create_error(const std::string& text) { g_create_error = text; }
+
+// The canonical structure of a sparse view in the caller's device memory, for the fp64 path (resnmtf_internal.h; DESIGN.md
+// section 24): resnmtf_set_view_sparse_device's checks and finish_sparse_build's two sorts, into arrays the caller owns.
+// Host code only: every kernel launched here is one those two launch.
+int resnmtf_sparse_device_canonical(void* stream, resnmtf_sparse_device_build& b, void* (*alloc)(void* ctx, size_t bytes), void* ctx,
+                                    std::string& why) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool coo = b.layout == RESNMTF_SPARSE_COO, csc = b.layout == RESNMTF_SPARSE_CSC, i64 = b.index_type == RESNMTF_INDEX_I64;
+  const int n = b.n, m = b.m, lines = csc ? m : n;
+  const long long nnz = b.nnz;
+  unsigned long long host_flags[2] = {kSpdvNone, 0ull};
+  auto hip_fail = [&](hipError_t e) { why = hipGetErrorString(e); return (int)RESNMTF_ERR_HIP; };
+  // the flags as they are on the device after everything enqueued so far; the refusal, if the word holds one
+  auto verdict = [&](const unsigned long long* sorted_keys) -> int {
+    hipError_t e = hipMemcpyAsync(host_flags, b.flags, sizeof(host_flags), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(e);
+    if (host_flags[0] == kSpdvNone) return RESNMTF_OK;
+    unsigned long long k = 0;
+    if (host_flags[0] >> 56 == SPDV_DUPLICATE) {
+      e = hipMemcpy(&k, sorted_keys + (host_flags[0] & ((1ull << 56) - 1ull)), sizeof(k), hipMemcpyDeviceToHost);
+      if (e != hipSuccess) return hip_fail(e);
+    }
+    why = spdv_refusal_text(host_flags[0], csc, nnz, n, k);
+    return RESNMTF_ERR_INVALID;
+  };
+  hipError_t e = hipMemcpyAsync(b.flags, host_flags, sizeof(host_flags), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return hip_fail(e);
+  if (!coo) {                                // the line pointers, judged before any kernel bounds a search by them
+    spdv_launch_ptr_check(st, i64, b.ptr_or_rows, lines, nnz, b.flags);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e);
+    if (int rc = verdict(nullptr)) return rc;
+  }
+  if (nnz == 0) return RESNMTF_OK;
+  spdv_launch_entries(st, b.layout, i64, b.dtype, b.ptr_or_rows, b.idx_or_cols, b.values, nnz, n, m, b.key[0], reinterpret_cast<double*>(b.pay[0]),
+                      nullptr, b.flags);
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e);
+  if (int rc = verdict(nullptr)) return rc;
+  const bool presorted = csc && host_flags[1] == 0ull;
+  const unsigned grid = (unsigned)((nnz + 255) / 256);
+  const unsigned long long count = (unsigned long long)n * m;
+  unsigned int end_bit = 1;                  // the bits of n m: every key is < count
+  while (end_bit < 64 && ((count - 1) >> end_bit) != 0) ++end_bit;
+  rocprim::double_buffer<unsigned long long> kb(b.key[0], b.key[1]);
+  rocprim::double_buffer<double> vb(reinterpret_cast<double*>(b.pay[0]), reinterpret_cast<double*>(b.pay[1]));
+  rocprim::double_buffer<unsigned long long> kb2(b.key[0], b.key[1]);
+  rocprim::double_buffer<long long> pb(b.pay[1], b.pay[2]);
+  size_t tmp_bytes = 0, tmp_bytes2 = 0;
+  e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, kb, vb, (size_t)nnz, 0u, end_bit, st);
+  if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, tmp_bytes2, kb2, pb, (size_t)nnz, 0u, end_bit, st);
+  if (e != hipSuccess) return hip_fail(e);
+  tmp_bytes = std::max<size_t>(std::max(tmp_bytes, tmp_bytes2), 8);
+  void* tmp = alloc(ctx, tmp_bytes);
+  if (!tmp) return RESNMTF_ERR_ALLOC;
+  // ---- the CSC: the entries sorted by c n + r
+  if (!presorted) {
+    e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kb, vb, (size_t)nnz, 0u, end_bit, st);
+    if (e != hipSuccess) return hip_fail(e);
+    if (nnz > 1) {
+      hipLaunchKernelGGL(sparse_device_duplicates_kernel, dim3((unsigned)((nnz + 254) / 256)), dim3(256), 0, st, kb.current(), nnz, b.flags);
+      if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e);
+      if (int rc = verdict(kb.current())) return rc;
+    }
+  }
+  hipLaunchKernelGGL(sorted_lines_kernel, dim3(grid), dim3(256), 0, st, kb.current(), nnz, (unsigned long long)n, m, b.cptr, b.cidx);
+  // ---- the CSR: the CSC positions sorted by r m + c (the values stay where the first sort left them)
+  kb2 = rocprim::double_buffer<unsigned long long>(kb.alternate(), kb.current());
+  pb = rocprim::double_buffer<long long>(reinterpret_cast<long long*>(vb.alternate()), b.pay[2]);
+  hipLaunchKernelGGL(sparse_shuffle_csr_keys_kernel, dim3(grid), dim3(256), 0, st, kb.current(), nnz, n, m, kb2.current(), pb.current());
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e);
+  e = rocprim::radix_sort_pairs(tmp, tmp_bytes, kb2, pb, (size_t)nnz, 0u, end_bit, st);
+  if (e != hipSuccess) return hip_fail(e);
+  hipLaunchKernelGGL(sorted_lines_kernel, dim3(grid), dim3(256), 0, st, kb2.current(), nnz, (unsigned long long)m, n, b.rptr, b.ridx);
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e);
+  b.csc_values = vb.current();
+  b.csr_perm = pb.current();
+  return RESNMTF_OK;
+}
 extern "C" {
 
 int resnmtf_factor_device_ptr(resnmtf_handle* h, int v, int which, void** ptr, size_t* bytes) {

@@ -97,7 +97,7 @@ def _fill_fp64_device(dev, v: int, x, p, k: int, q: int, device_id: int, keep: l
     ``_fill_group_job``'s.  ``init_f[v]`` / ``init_s[v]`` / ``init_g[v]`` are all three device tensors or none is
     (``ValueError``); beside device factors ``init_lam[v]`` / ``init_mu[v]`` are moved to the device when they are not there."""
     n, m = (int(d) for d in x.shape)
-    x_there = _device_views.is_device_tensor(x)
+    x_there = _device_views.is_device_tensor(x)             # (a sparse tensor comes as a SparseDeviceView: not this route)
     if x_there:
         t = x.detach()
         keep.append(t)
@@ -125,6 +125,24 @@ def _fill_fp64_device(dev, v: int, x, p, k: int, q: int, device_id: int, keep: l
     return x_there, True
 
 
+_LAYOUT_CODES = {"torch.sparse_csc": _lib.SPARSE_CSC, "torch.sparse_csr": _lib.SPARSE_CSR, "torch.sparse_coo": _lib.SPARSE_COO}
+
+
+def _fill_fp64_sparse_device(spd, v: int, x, q: int, keep: list):
+    """The sparse view ``x`` (a checked ``device_views.SparseDeviceView``) into entry ``v`` of the
+    ``resnmtf_fp64_sparse_device`` ``spd``: the addresses of its own index and value arrays
+    (``device_views.sparse_tensor_parts``), ``.contiguous()`` only on a piece that is not."""
+    t = x.tensor.detach()
+    if str(t.dtype) not in _DTYPE_CODES:
+        raise ValueError(f"problem {q}, view {v}: data must be fp64, fp32, fp16 or bf16, got {t.dtype}")
+    a, b, vals = (piece if piece.is_contiguous() else piece.contiguous() for piece in _device_views.sparse_tensor_parts(t))
+    keep.extend([t, a, b, vals])
+    c = spd.view[v]
+    c.layout, c.dtype = _LAYOUT_CODES[str(t.layout)], _DTYPE_CODES[str(t.dtype)]
+    c.index_type = _lib.INDEX_I64 if str(a.dtype) == "torch.int64" else _lib.INDEX_I32
+    c.ptr_or_rows, c.idx_or_cols, c.values, c.nnz = a.data_ptr(), b.data_ptr(), vals.data_ptr(), int(t._nnz())
+
+
 def _fp64_device_outputs(dev, j, out: dict, device_id: int, return_state: bool):
     """``output="torch"``: the five results per view (and the raw state) as fp64 tensors on ``cuda:device_id``, F, S and G
     column-major (``torch.empty((k, n)).T``, as ``Engine.get_factors_device`` wraps its own), their addresses in ``dev``."""
@@ -143,7 +161,7 @@ def _fp64_device_outputs(dev, j, out: dict, device_id: int, return_state: bool):
 
 
 def _fill_group_job(j, p, q: int, max_iters: int, keep: list, sp=None, dev=None, device_id: int = 0,
-                    device_out: bool = False) -> dict:
+                    device_out: bool = False, spd=None) -> dict:
     """Fill one ``resnmtf_group_job`` (``j``) from the problem dict ``p`` (problem ``q`` of its call; the layout
     ``group_run`` documents) and return the output arrays it points to.  ``keep`` collects every array the struct
     points into: the caller holds it until the library call has returned.  ``sp`` (``fp64_run`` alone): the
@@ -151,10 +169,14 @@ def _fill_group_job(j, p, q: int, max_iters: int, keep: list, sp=None, dev=None,
     NULL; without it such a view is a ``ValueError``.  ``dev`` (``fp64_run`` alone): the ``resnmtf_fp64_device`` that
     receives every view and every set of initial factors that are ``torch`` tensors on ``cuda:device_id``
     (``_fill_fp64_device``); the job's own pointers to them stay NULL.  ``device_out``: the job's per-view output pointers
-    stay NULL and the returned lists empty (``_fp64_device_outputs`` fills them)."""
+    stay NULL and the returned lists empty (``_fp64_device_outputs`` fills them).  ``spd`` (``fp64_run`` alone): the
+    ``resnmtf_fp64_sparse_device`` that receives every view that is a sparse tensor on ``cuda:device_id`` (or a
+    ``SparseDeviceView`` of one), checked by ``device_views.check_sparse_tensor``; its ``x`` stays NULL too."""
     j.struct_size = C.sizeof(_lib.GroupJob)
     data = [_sparse.canonical_csc(x) if _sparse.is_sparse(x)
-            else x if dev is not None and _device_views.is_device_tensor(x) else _f64_colmajor(x) for x in p["data"]]
+            else _device_views.as_sparse_view(x, device_id, f"problem {q}, view {v}")
+            if spd is not None and _device_views.is_sparse_device_view(x)
+            else x if dev is not None and _device_views.is_device_tensor(x) else _f64_colmajor(x) for v, x in enumerate(p["data"])]
     if sp is None and any(_sparse.is_sparse(x) for x in data):
         raise ValueError(f"problem {q}: a sparse view (scipy.sparse) is taken by fp64_run alone")
     V, k = len(data), int(p["k"])
@@ -186,9 +208,13 @@ def _fill_group_job(j, p, q: int, max_iters: int, keep: list, sp=None, dev=None,
             sp.view[v].row_idx, sp.view[v].values = _ip(csc[1]), _dp(csc[2])
             keep.extend(csc)
             arrs = arrs[1:]
+        elif isinstance(x, _device_views.SparseDeviceView):      # its arrays go into spd; j.x[v] stays NULL
+            _fill_fp64_sparse_device(spd, v, x, q, keep)
+            arrs = arrs[1:]
         elif x_there:                         # dev.x[v] describes it; j.x[v] stays NULL
             arrs = arrs[1:]
-        for name, a in zip(("f0", "s0", "g0") if _sparse.is_sparse(x) or x_there else ("x", "f0", "s0", "g0"), arrs):
+        elsewhere = _sparse.is_sparse(x) or x_there or isinstance(x, _device_views.SparseDeviceView)
+        for name, a in zip(("f0", "s0", "g0") if elsewhere else ("x", "f0", "s0", "g0"), arrs):
             getattr(j, name)[v] = _dp(a)
         keep.extend(arrs)
         for name, key in (("lambda0", "init_lam"), ("mu0", "init_mu")):
@@ -281,7 +307,17 @@ def fp64_run(problem, tol: float = 1.0e-6, max_iters: int = 100000, device_id: i
     ``all_error`` and ``iters`` stay NumPy.  ``return_state=True`` (needs ``output="torch"``, else ``ValueError``) adds
     ``"state"``: per view the raw ``(F, S, G, lambda, mu)`` after the last sweep, before the normalisation -- what a later
     call resumes from.  Every result is bit for bit the host route's on ``t.double().cpu().numpy()`` of the same tensors.
-    A problem with nothing on the device and the default flags makes the calls it made before."""
+    A problem with nothing on the device and the default flags makes the calls it made before.
+
+    Sparse tensors in device memory (``resnmtf_fp64_run_sparse_device``).  An entry of
+    ``problem["data"]`` that is a 2-D ``sparse_csc`` / ``sparse_csr`` / coalesced ``sparse_coo`` tensor on
+    ``cuda:device_id`` (or a ``device_views.SparseDeviceView`` of one; checked by ``device_views.check_sparse_tensor``) is a
+    SPARSE view read where it lies: floating values of any of the four types, int32 / int64 indices, entries in any order,
+    stored positions distinct, taken as pre-processed.  It is checked and sorted on the device (its refusals surface as
+    ``ResnmtfError``) and nothing of it is brought to the host.  Every result is bit for bit that of the ``scipy.sparse``
+    matrix of the same stored entries -- with ONE difference: an explicitly stored zero stays stored here, while
+    ``sparse.canonical_csc`` drops it on the host route (the sums then differ in their last bits, not in what they stand
+    for).  Such views mix with every other kind.  A problem without one makes exactly the calls it made before."""
     _device_views.check_output(output)
     if return_state and output != "torch":
         raise ValueError("return_state=True needs output='torch' (the raw state is left on the device)")
@@ -289,20 +325,30 @@ def fp64_run(problem, tol: float = 1.0e-6, max_iters: int = 100000, device_id: i
     job = _lib.GroupJob()
     keep = []
     tensors = [x for key in ("data", "init_f", "init_s", "init_g", "init_lam", "init_mu") for x in (problem.get(key) or ())]
-    if output == "torch" or any(_device_views.is_device_tensor(x) for x in tensors):
+    sparse_there = any(_device_views.is_sparse_device_view(x) for x in problem["data"])      # (section 24)
+    if output == "torch" or sparse_there or any(_device_views.is_device_tensor(x) for x in tensors):
         import torch                # (lazily: nothing else in this module needs it)
         dev = _lib.Fp64Device()
         dev.struct_size = C.sizeof(_lib.Fp64Device)
-        sp = None
+        sp = spd = None
         if any(_sparse.is_sparse(x) for x in problem["data"]):
             sp = _lib.Fp64Sparse()
             sp.struct_size = C.sizeof(_lib.Fp64Sparse)
-        out = _fill_group_job(job, problem, 0, max_iters, keep, sp=sp, dev=dev, device_id=device_id, device_out=output == "torch")
+        if sparse_there:
+            spd = _lib.Fp64SparseDevice()
+            spd.struct_size = C.sizeof(_lib.Fp64SparseDevice)
+        out = _fill_group_job(job, problem, 0, max_iters, keep, sp=sp, dev=dev, device_id=device_id, device_out=output == "torch",
+                              spd=spd)
         if output == "torch":
             _fp64_device_outputs(dev, job, out, device_id, return_state)
         dev.stream = torch.cuda.current_stream(torch.device("cuda", int(device_id))).cuda_stream
-        rc = lib.resnmtf_fp64_run_device(int(device_id), C.byref(job), None if sp is None else C.byref(sp), C.byref(dev),
-                                         float(tol), int(max_iters))
+        if spd is None:
+            rc = lib.resnmtf_fp64_run_device(int(device_id), C.byref(job), None if sp is None else C.byref(sp), C.byref(dev),
+                                             float(tol), int(max_iters))
+        else:
+            spd.stream = dev.stream
+            rc = lib.resnmtf_fp64_run_sparse_device(int(device_id), C.byref(job), None if sp is None else C.byref(sp), C.byref(dev),
+                                                    C.byref(spd), float(tol), int(max_iters))
     elif any(_sparse.is_sparse(x) for x in problem["data"]):
         sp = _lib.Fp64Sparse()
         sp.struct_size = C.sizeof(_lib.Fp64Sparse)
