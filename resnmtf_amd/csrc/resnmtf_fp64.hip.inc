@@ -13,54 +13,12 @@
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
-#define F64_THREADS 256
-#define F64_ROWS 128          // rows of a product workgroup: 4 waves x two 16-row MFMA tiles
-#define F64_JC 64             // contraction indices per LDS stage of the product (X's columns are padded to this)
-#define F64_TARGET_WGS 512    // workgroups a product or residual launch aims for (a constant: the split count must
-                              // depend on (n, m, k) alone, never on the device)
-#define F64_GRAM_ROWS 256     // rows per workgroup of the Gram partials
+#include "resnmtf_fp64_job.h"   // the shape constants (F64_THREADS, F64_ROWS, ...) and the shape-only plans: host code, no HIP
+
 #define F64_GRAM_STAGE 32
-#define F64_UPD_ROWS 64       // rows (= threads) per workgroup of the row-local kernels
-#define F64_RES_ROWS 64       // rows per workgroup of the residual
 #define F64_RES_LD 80         // LDS stride of a column of the residual's F S tile (80 = 16 mod 32 doubles: the four
                               // k-slices of an MFMA operand read fall on disjoint halves of the banks)
-#define F64_NORM_CHUNK (F64_THREADS * 64)
 #define F64_MAX_VIEWS 8
-
-__host__ __device__ inline int f64_kp(int k) { return (k + 15) / 16 * 16; }
-
-// leading dimension of an image with `rows` rows: a multiple of 32 (two 16-row MFMA tiles per wave, 16-byte row pairs),
-// kept off the multiples of 1024 -- with a power-of-two column stride the columns a launch reads together fall on the
-// same memory channels (a precaution: its effect is within the noise of the measurements, DESIGN.md section 21)
-inline size_t f64_ld(size_t rows) {
-  const size_t ld = (rows + 31) / 32 * 32;
-  return ld % 1024 == 0 ? ld + 32 : ld;
-}
-
-// launch geometry of one tall-skinny product (rows x contr) . (contr x k): row tiles, contraction splits, indices per
-// split.  A function of the shapes alone.
-struct F64ProductPlan { int tiles, splits, chunk; };
-inline F64ProductPlan f64_plan_product(int rows, int contr) {
-  F64ProductPlan p;
-  p.tiles = (rows + F64_ROWS - 1) / F64_ROWS;
-  const int stages = (contr + F64_JC - 1) / F64_JC;
-  int splits = std::min(stages, std::max(1, F64_TARGET_WGS / p.tiles));
-  const int per = (stages + splits - 1) / splits;
-  p.splits = (stages + per - 1) / per;
-  p.chunk = per * F64_JC;
-  return p;
-}
-// the residual: 64-row tiles, the columns of X split in whole 16-column MFMA tiles (at least 4 per split: one per wave)
-inline F64ProductPlan f64_plan_resid(int n, int m) {
-  F64ProductPlan p;
-  p.tiles = (n + F64_RES_ROWS - 1) / F64_RES_ROWS;
-  const int jt = (m + 15) / 16;
-  int splits = std::min((jt + 3) / 4, std::max(1, F64_TARGET_WGS / p.tiles));
-  const int per = (jt + splits - 1) / splits;
-  p.splits = (jt + per - 1) / per;
-  p.chunk = per * 16;
-  return p;
-}
 
 // sum of one value per thread by a fixed tree; thread 0 gets the total
 __device__ inline double f64_block_sum(double x, double* red) {

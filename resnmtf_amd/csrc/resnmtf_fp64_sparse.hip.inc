@@ -11,25 +11,9 @@
 // up to the next symbol, so the last kernel of a section carries the section's tail, and a new neighbour would show as a
 // change of a kernel nobody touched.
 
-#define F64_SP_PIECE 256       // stored entries a line piece aims for: a line longer than this is cut
-#define F64_SP_MAX_SPLITS 16    // at most this many pieces (= slab splits) per line
+#include "resnmtf_fp64_job.h"   // F64_SP_PIECE, F64_SP_MAX_SPLITS, f64_sp_group and f64_plan_sparse: host code, no HIP
+
 #define F64_SP_T_ROWS 64        // rows per workgroup of the operand copy
-
-// lanes that own one line piece: KP of them where KP divides the wave (16, 32), else the whole wave (48, 64)
-__host__ __device__ constexpr int f64_sp_group(int KP) { return KP == 16 ? 16 : (KP == 32 ? 32 : 64); }
-
-// how one SpMM cuts its lines: `splits` pieces of `piece` entries each.  Piece s of a line of len entries holds its
-// entries [s piece, min((s + 1) piece, len)): a line of at most `piece` entries is whole in split 0 and zero in the
-// others.  A function of the longest line alone (so of the pointer array), never of the device.
-struct F64SparsePlan { int splits; long long piece, longest; };
-inline F64SparsePlan f64_plan_sparse(long long longest) {
-  F64SparsePlan p;
-  p.longest = longest;
-  const long long want = (longest + F64_SP_PIECE - 1) / F64_SP_PIECE;
-  p.splits = (int)std::max<long long>(1, std::min<long long>(F64_SP_MAX_SPLITS, want));
-  p.piece = std::max<long long>(1, (longest + p.splits - 1) / p.splits);
-  return p;
-}
 
 // ---- the operand once per product as a row-major, KP-padded, zero-filled copy: OT[j][c] = O[j, c] (c < k), else 0 ----
 // O (len x k) column-major.  64 rows per workgroup through LDS: coalesced on both sides.

@@ -78,33 +78,51 @@ _DTYPE_CODES = {"torch.float64": _lib.DTYPE_F64, "torch.float32": _lib.DTYPE_F32
                 "torch.bfloat16": _lib.DTYPE_BF16}
 
 
+def _dtype_code(t, what: str) -> int:
+    """The ``RESNMTF_DTYPE_*`` of the tensor ``t``; any other than the four floating types is a ``ValueError``."""
+    if str(t.dtype) not in _DTYPE_CODES:
+        raise ValueError(f"{what} must be fp64, fp32, fp16 or bf16, got {t.dtype}")
+    return _DTYPE_CODES[str(t.dtype)]
+
+
 def _device_matrix(t, shape, device_id: int, what: str) -> _lib.DeviceMatrix:
     """The ``resnmtf_device_matrix`` of a ``torch`` tensor as it lies (``data_ptr``, dtype, strides in elements), after the
     checks that need no device: fp64 / fp32 / fp16 / bf16, on ``cuda:device_id``, of ``shape`` (``ValueError``)."""
-    if str(t.dtype) not in _DTYPE_CODES:
-        raise ValueError(f"{what} must be fp64, fp32, fp16 or bf16, got {t.dtype}")
+    dtype = _dtype_code(t, what)
     if not _device_views.on_engine_device(t, device_id):
         raise ValueError(f"{what} lives on {t.device}, the run on cuda:{int(device_id)}")
     if tuple(t.shape) != tuple(shape):
         raise ValueError(f"{what}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
     strides = [int(x) for x in t.stride()] + [1]                      # (a vector: the column stride is not read)
-    return _lib.DeviceMatrix(t.data_ptr(), _DTYPE_CODES[str(t.dtype)], strides[0], strides[1])
+    return _lib.DeviceMatrix(t.data_ptr(), dtype, strides[0], strides[1])
 
 
-def _fill_fp64_device(dev, v: int, x, p, k: int, q: int, device_id: int, keep: list) -> tuple:
-    """View ``v`` of ``fp64_run``'s problem ``p`` into the ``resnmtf_fp64_device`` ``dev``: its data when ``x`` is a device
-    tensor, its initial factors when they are.  Returns (data on the device, factors on the device); what is not stays
-    ``_fill_group_job``'s.  ``init_f[v]`` / ``init_s[v]`` / ``init_g[v]`` are all three device tensors or none is
-    (``ValueError``); beside device factors ``init_lam[v]`` / ``init_mu[v]`` are moved to the device when they are not there."""
-    n, m = (int(d) for d in x.shape)
-    x_there = _device_views.is_device_tensor(x)             # (a sparse tensor comes as a SparseDeviceView: not this route)
-    if x_there:
-        t = x.detach()
-        keep.append(t)
-        dev.x[v] = _device_matrix(t, (n, m), device_id, f"problem {q}, view {v}: data")
+# Where the data of one view of a problem come from: exactly one of the four places the library knows (F64Source in
+# csrc/resnmtf_fp64_job.h).  ``group_run`` knows the first alone.
+_HOST_DENSE, _HOST_CSC, _DEVICE_DENSE, _DEVICE_SPARSE = "job->x", "sp", "dev->x", "spd"
+
+
+def _view_route(x, what: str, device_id: int, dev, spd) -> tuple:
+    """(route, the view as that route takes it): a ``scipy.sparse`` matrix as its canonical CSC; with ``spd`` a sparse
+    tensor on the device as a checked ``device_views.SparseDeviceView``; with ``dev`` a device tensor as it is; anything
+    else as an fp64 column-major array."""
+    if _sparse.is_sparse(x):
+        return _HOST_CSC, _sparse.canonical_csc(x)
+    if spd is not None and _device_views.is_sparse_device_view(x):
+        return _DEVICE_SPARSE, _device_views.as_sparse_view(x, device_id, what)
+    if dev is not None and _device_views.is_device_tensor(x):
+        return _DEVICE_DENSE, x
+    return _HOST_DENSE, _f64_colmajor(x)
+
+
+def _fill_fp64_device_factors(dev, v: int, n: int, m: int, p, k: int, q: int, device_id: int, keep: list) -> bool:
+    """The initial factors of view ``v`` of ``fp64_run``'s problem ``p`` into the ``resnmtf_fp64_device`` ``dev`` when they
+    are device tensors; False when they are not, and they stay ``_fill_group_job``'s.  ``init_f[v]`` / ``init_s[v]`` /
+    ``init_g[v]`` are all three device tensors or none is (``ValueError``); beside device factors ``init_lam[v]`` /
+    ``init_mu[v]`` are moved to the device when they are not there."""
     parts = [p["init_f"][v], p["init_s"][v], p["init_g"][v]]
     if not _device_views.factor_route(*parts, what=f"problem {q}, view {v}"):
-        return x_there, False
+        return False
     for t, name, shape in zip(parts, ("f0", "s0", "g0"), ((n, k), (k, k), (m, k))):
         t = t.detach()
         keep.append(t)
@@ -122,7 +140,7 @@ def _fill_fp64_device(dev, v: int, x, p, k: int, q: int, device_id: int, keep: l
         t = t.detach()
         keep.append(t)
         getattr(dev, name)[v] = _device_matrix(t, (k,), device_id, f"problem {q}, view {v}: {key}")
-    return x_there, True
+    return True
 
 
 _LAYOUT_CODES = {"torch.sparse_csc": _lib.SPARSE_CSC, "torch.sparse_csr": _lib.SPARSE_CSR, "torch.sparse_coo": _lib.SPARSE_COO}
@@ -133,12 +151,11 @@ def _fill_fp64_sparse_device(spd, v: int, x, q: int, keep: list):
     ``resnmtf_fp64_sparse_device`` ``spd``: the addresses of its own index and value arrays
     (``device_views.sparse_tensor_parts``), ``.contiguous()`` only on a piece that is not."""
     t = x.tensor.detach()
-    if str(t.dtype) not in _DTYPE_CODES:
-        raise ValueError(f"problem {q}, view {v}: data must be fp64, fp32, fp16 or bf16, got {t.dtype}")
+    dtype = _dtype_code(t, f"problem {q}, view {v}: data")
     a, b, vals = (piece if piece.is_contiguous() else piece.contiguous() for piece in _device_views.sparse_tensor_parts(t))
     keep.extend([t, a, b, vals])
     c = spd.view[v]
-    c.layout, c.dtype = _LAYOUT_CODES[str(t.layout)], _DTYPE_CODES[str(t.dtype)]
+    c.layout, c.dtype = _LAYOUT_CODES[str(t.layout)], dtype
     c.index_type = _lib.INDEX_I64 if str(a.dtype) == "torch.int64" else _lib.INDEX_I32
     c.ptr_or_rows, c.idx_or_cols, c.values, c.nnz = a.data_ptr(), b.data_ptr(), vals.data_ptr(), int(t._nnz())
 
@@ -164,25 +181,22 @@ def _fill_group_job(j, p, q: int, max_iters: int, keep: list, sp=None, dev=None,
                     device_out: bool = False, spd=None) -> dict:
     """Fill one ``resnmtf_group_job`` (``j``) from the problem dict ``p`` (problem ``q`` of its call; the layout
     ``group_run`` documents) and return the output arrays it points to.  ``keep`` collects every array the struct
-    points into: the caller holds it until the library call has returned.  ``sp`` (``fp64_run`` alone): the
-    ``resnmtf_fp64_sparse`` that receives the canonical CSC arrays of every ``scipy.sparse`` view, whose ``x`` stays
-    NULL; without it such a view is a ``ValueError``.  ``dev`` (``fp64_run`` alone): the ``resnmtf_fp64_device`` that
-    receives every view and every set of initial factors that are ``torch`` tensors on ``cuda:device_id``
-    (``_fill_fp64_device``); the job's own pointers to them stay NULL.  ``device_out``: the job's per-view output pointers
-    stay NULL and the returned lists empty (``_fp64_device_outputs`` fills them).  ``spd`` (``fp64_run`` alone): the
-    ``resnmtf_fp64_sparse_device`` that receives every view that is a sparse tensor on ``cuda:device_id`` (or a
-    ``SparseDeviceView`` of one), checked by ``device_views.check_sparse_tensor``; its ``x`` stays NULL too."""
+    points into: the caller holds it until the library call has returned.  Every view takes one route (``_view_route``)
+    and only a host dense view sets ``j.x[v]``.  ``sp`` (``fp64_run`` alone): the ``resnmtf_fp64_sparse`` that receives
+    the canonical CSC arrays of every ``scipy.sparse`` view; without it such a view is a ``ValueError``.  ``dev``
+    (``fp64_run`` alone): the ``resnmtf_fp64_device`` that receives every view and every set of initial factors that are
+    ``torch`` tensors on ``cuda:device_id``; the job's own pointers to them stay NULL.  ``device_out``: the job's per-view
+    output pointers stay NULL and the returned lists empty (``_fp64_device_outputs`` fills them).  ``spd`` (``fp64_run``
+    alone): the ``resnmtf_fp64_sparse_device`` that receives every view that is a sparse tensor on ``cuda:device_id`` (or
+    a ``SparseDeviceView`` of one), checked by ``device_views.check_sparse_tensor``."""
     j.struct_size = C.sizeof(_lib.GroupJob)
-    data = [_sparse.canonical_csc(x) if _sparse.is_sparse(x)
-            else _device_views.as_sparse_view(x, device_id, f"problem {q}, view {v}")
-            if spd is not None and _device_views.is_sparse_device_view(x)
-            else x if dev is not None and _device_views.is_device_tensor(x) else _f64_colmajor(x) for v, x in enumerate(p["data"])]
-    if sp is None and any(_sparse.is_sparse(x) for x in data):
+    views = [_view_route(x, f"problem {q}, view {v}", device_id, dev, spd) for v, x in enumerate(p["data"])]
+    if sp is None and any(route == _HOST_CSC for route, _ in views):
         raise ValueError(f"problem {q}: a sparse view (scipy.sparse) is taken by fp64_run alone")
-    V, k = len(data), int(p["k"])
+    V, k = len(views), int(p["k"])
     if V > _lib.GROUP_MAX_VIEWS:
         raise ValueError(f"problem {q}: at most {_lib.GROUP_MAX_VIEWS} views")
-    if any(x.ndim != 2 for x in data):
+    if any(x.ndim != 2 for _, x in views):
         raise ValueError(f"problem {q}: every view must be a matrix")
     for key in ("init_f", "init_s", "init_g", "init_lam", "init_mu"):
         if p.get(key) is not None and len(p[key]) != V:
@@ -192,31 +206,33 @@ def _fill_group_job(j, p, q: int, max_iters: int, keep: list, sp=None, dev=None,
     j.n_iters = 0 if n_iters is None else int(n_iters)
     cap = max(1, min(int(n_iters), int(max_iters)) if n_iters else int(max_iters))
     out = {"f": [], "s": [], "g": [], "lambda": [], "mu": [], "all_error": np.empty(cap), "iters": np.zeros(1, np.int32)}
-    for v, x in enumerate(data):
+    for v, (route, x) in enumerate(views):
         n, m = (int(d) for d in x.shape)
         j.n_rows[v], j.n_cols[v] = n, m
-        x_there, factors_there = (False, False) if dev is None else _fill_fp64_device(dev, v, x, p, k, q, device_id, keep)
-        try:                                  # (the library reads n k, k k and m k doubles through these pointers)
-            arrs = [x] + ([] if factors_there else [_f64_colmajor(p["init_f"][v], (n, k)), _f64_colmajor(p["init_s"][v], (k, k)),
-                                                    _f64_colmajor(p["init_g"][v], (m, k))])
-        except ValueError as exc:
-            raise ValueError(f"problem {q}, view {v}: initial factor: {exc}") from None
-        if _sparse.is_sparse(x):              # the CSC arrays go into sp; j.x[v] stays NULL
+        if route == _HOST_DENSE:
+            keep.append(x)
+            j.x[v] = _dp(x)
+        elif route == _HOST_CSC:              # the CSC arrays go into sp
             csc = [np.ascontiguousarray(x.indptr, dtype=np.int64), np.ascontiguousarray(x.indices, dtype=np.int32),
                    np.ascontiguousarray(x.data, dtype=np.float64)]
             sp.view[v].col_ptr = csc[0].ctypes.data_as(C.POINTER(C.c_longlong))
             sp.view[v].row_idx, sp.view[v].values = _ip(csc[1]), _dp(csc[2])
             keep.extend(csc)
-            arrs = arrs[1:]
-        elif isinstance(x, _device_views.SparseDeviceView):      # its arrays go into spd; j.x[v] stays NULL
+        elif route == _DEVICE_DENSE:          # dev.x[v] describes the tensor as it lies
+            t = x.detach()
+            keep.append(t)
+            dev.x[v] = _device_matrix(t, (n, m), device_id, f"problem {q}, view {v}: data")
+        else:                                 # its index and value arrays go into spd
             _fill_fp64_sparse_device(spd, v, x, q, keep)
-            arrs = arrs[1:]
-        elif x_there:                         # dev.x[v] describes it; j.x[v] stays NULL
-            arrs = arrs[1:]
-        elsewhere = _sparse.is_sparse(x) or x_there or isinstance(x, _device_views.SparseDeviceView)
-        for name, a in zip(("f0", "s0", "g0") if elsewhere else ("x", "f0", "s0", "g0"), arrs):
-            getattr(j, name)[v] = _dp(a)
-        keep.extend(arrs)
+        factors_there = dev is not None and _fill_fp64_device_factors(dev, v, n, m, p, k, q, device_id, keep)
+        if not factors_there:
+            try:                              # (the library reads n k, k k and m k doubles through these pointers)
+                arrs = [_f64_colmajor(p["init_f"][v], (n, k)), _f64_colmajor(p["init_s"][v], (k, k)),
+                        _f64_colmajor(p["init_g"][v], (m, k))]
+            except ValueError as exc:
+                raise ValueError(f"problem {q}, view {v}: initial factor: {exc}") from None
+            j.f0[v], j.s0[v], j.g0[v] = (_dp(a) for a in arrs)
+            keep.extend(arrs)
         for name, key in (("lambda0", "init_lam"), ("mu0", "init_mu")):
             vals = p.get(key)
             if vals is not None and vals[v] is not None and not factors_there:
@@ -324,39 +340,33 @@ def fp64_run(problem, tol: float = 1.0e-6, max_iters: int = 100000, device_id: i
     lib = _lib.load()
     job = _lib.GroupJob()
     keep = []
+    data = problem["data"]
     tensors = [x for key in ("data", "init_f", "init_s", "init_g", "init_lam", "init_mu") for x in (problem.get(key) or ())]
-    sparse_there = any(_device_views.is_sparse_device_view(x) for x in problem["data"])      # (section 24)
-    if output == "torch" or sparse_there or any(_device_views.is_device_tensor(x) for x in tensors):
+    # which of the three structs the problem needs; the entry follows from which of them exist
+    sp = _lib.Fp64Sparse() if any(_sparse.is_sparse(x) for x in data) else None                      # (section 22)
+    spd = _lib.Fp64SparseDevice() if any(_device_views.is_sparse_device_view(x) for x in data) else None      # (section 24)
+    dev = (_lib.Fp64Device() if output == "torch" or spd is not None or any(_device_views.is_device_tensor(x) for x in tensors)
+           else None)                                                                                 # (section 23)
+    for s in (sp, dev, spd):
+        if s is not None:
+            s.struct_size = C.sizeof(s)
+    out = _fill_group_job(job, problem, 0, max_iters, keep, sp=sp, dev=dev, device_id=device_id, device_out=output == "torch", spd=spd)
+    if dev is not None:
         import torch                # (lazily: nothing else in this module needs it)
-        dev = _lib.Fp64Device()
-        dev.struct_size = C.sizeof(_lib.Fp64Device)
-        sp = spd = None
-        if any(_sparse.is_sparse(x) for x in problem["data"]):
-            sp = _lib.Fp64Sparse()
-            sp.struct_size = C.sizeof(_lib.Fp64Sparse)
-        if sparse_there:
-            spd = _lib.Fp64SparseDevice()
-            spd.struct_size = C.sizeof(_lib.Fp64SparseDevice)
-        out = _fill_group_job(job, problem, 0, max_iters, keep, sp=sp, dev=dev, device_id=device_id, device_out=output == "torch",
-                              spd=spd)
         if output == "torch":
             _fp64_device_outputs(dev, job, out, device_id, return_state)
         dev.stream = torch.cuda.current_stream(torch.device("cuda", int(device_id))).cuda_stream
-        if spd is None:
-            rc = lib.resnmtf_fp64_run_device(int(device_id), C.byref(job), None if sp is None else C.byref(sp), C.byref(dev),
-                                             float(tol), int(max_iters))
-        else:
+        if spd is not None:
             spd.stream = dev.stream
-            rc = lib.resnmtf_fp64_run_sparse_device(int(device_id), C.byref(job), None if sp is None else C.byref(sp), C.byref(dev),
-                                                    C.byref(spd), float(tol), int(max_iters))
-    elif any(_sparse.is_sparse(x) for x in problem["data"]):
-        sp = _lib.Fp64Sparse()
-        sp.struct_size = C.sizeof(_lib.Fp64Sparse)
-        out = _fill_group_job(job, problem, 0, max_iters, keep, sp=sp)
-        rc = lib.resnmtf_fp64_run_sparse(int(device_id), C.byref(job), C.byref(sp), float(tol), int(max_iters))
+    head, tail = (int(device_id), C.byref(job)), (float(tol), int(max_iters))
+    if spd is not None:
+        rc = lib.resnmtf_fp64_run_sparse_device(*head, None if sp is None else C.byref(sp), C.byref(dev), C.byref(spd), *tail)
+    elif dev is not None:
+        rc = lib.resnmtf_fp64_run_device(*head, None if sp is None else C.byref(sp), C.byref(dev), *tail)
+    elif sp is not None:
+        rc = lib.resnmtf_fp64_run_sparse(*head, C.byref(sp), *tail)
     else:
-        out = _fill_group_job(job, problem, 0, max_iters, keep)
-        rc = lib.resnmtf_fp64_run(int(device_id), C.byref(job), float(tol), int(max_iters))
+        rc = lib.resnmtf_fp64_run(*head, *tail)
     if rc != _lib.OK:
         raise ResnmtfError(rc, (lib.resnmtf_last_error(None) or b"").decode())
     return _group_result(out)
