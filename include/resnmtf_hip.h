@@ -1017,6 +1017,55 @@ int resnmtf_fp64_run_sparse_device(int device_id, const resnmtf_group_job* job, 
                                    const resnmtf_fp64_device* dev, const resnmtf_fp64_sparse_device* spd, double tol,
                                    int max_iters);
 
+/*
+ * resnmtf_bisil in DOUBLE precision, without a handle: the per-member silhouettes that
+ *     bisilhouette::bisilhouette(data[[i]], row_clustering[[i]], col_clustering[[i]], method = distance)
+ * combines into res_nmtf_inner's `bisil` (R/obtain_bicl.r:189-199) and that the k sweep of apply_resnmtf ranks
+ * (R/main.r:269-321), computed on the fp64 values of X -- the numbers resnmtf_fp64_run factorised -- where resnmtf_bisil
+ * reads a handle's fp32 images.  The definition, the metrics and the layout of the outputs are resnmtf_bisil's; every
+ * value is carried in fp64, every sum has resnmtf_bisil's order (no atomics: two calls give equal bits), and on data that
+ * fp32 holds exactly the silhouettes are bit for bit resnmtf_bisil's.  Blocking.
+ *   n, m, k       the view is n x m, the cluster matrices n x k and m x k; k in [1, 64].
+ *   metric        0 = euclidean, 1 = manhattan, 2 = cosine.
+ *   x             X in host memory: n x m fp64 column-major, as resnmtf_group_job.x holds a view; copied once into a
+ *                 plain n x m fp64 device array (no padded images); or NULL.
+ *   x_dev, stream X in device memory: any of the four dtypes, any strides >= 0 (0: an expanded tensor), read where it
+ *                 lies after an event recorded on `stream` (the hipStream_t its producer ran on; NULL: the null stream);
+ *                 x_dev.ptr NULL when not given.  X is given in exactly one of the two places.
+ *   row_clusters, col_clusters   host, column-major 0 / 1 fp64, as resnmtf_bisil takes them.
+ *   row_sil, col_sil             host, n x k and m x k column-major, 0 at non-members and inactive biclusters.
+ * Per side and active bicluster the restricted block G[f][u] = X(U[u], J_l[f]) is gathered as doubles straight from X --
+ * with lanes along the points where the point stride is the smaller one, through a 32 x 32 LDS tile read along the
+ * features where the feature stride is --, then the norm, distance and epilogue kernels run on it.
+ * Refused before any device work (RESNMTF_ERR_INVALID, text in resnmtf_last_error(NULL)), neither output written: job NULL,
+ * a struct_size mismatch, k outside [1, 64], n or m below 1, an unknown metric, X in both places or in neither, NULL
+ * cluster or output pointers, an unknown dtype, a negative stride, x_dev.ptr not memory of device_id (or too short for
+ * the shape and strides), a cluster entry other than 0 or 1 (resnmtf_bisil's message, that of row_clusters first).
+ * The workspace is sized first -- the largest block max_l |J_l| x U_pad doubles, the chunk partials, the lists, the
+ * silhouettes and n m doubles for a host X -- and refused with RESNMTF_ERR_ALLOC and its byte count when it exceeds the
+ * free device memory.  No active bicluster: zero silhouettes, RESNMTF_OK.
+ */
+typedef struct resnmtf_fp64_bisil_job {
+  int struct_size;                          /* sizeof the struct */
+  int n, m, k, metric;
+  const double* x;
+  resnmtf_device_matrix x_dev;
+  void* stream;
+  const double *row_clusters, *col_clusters;
+  double *row_sil, *col_sil;
+} resnmtf_fp64_bisil_job;
+int resnmtf_fp64_bisil(int device_id, const resnmtf_fp64_bisil_job* job);
+
+/*
+ * How resnmtf_fp64_bisil launches one side of one bicluster (no device work): for |U| = n_u points, n_mem members and k
+ * biclusters, and a device X with the given strides, out receives {kq (the per-thread bicluster sums of the distance
+ * kernel: 1, 2, 4, 8 or 16), tiles of U per chunk, chunks, the gather form of the row side, of the column side
+ * (0 = lanes along the points, 1 = the LDS transpose)}.  A host X has row_stride 1 and col_stride n.
+ * Refused (RESNMTF_ERR_INVALID): out NULL, n_u or n_mem below 1, k outside [1, 64], a negative stride.
+ */
+#define RESNMTF_FP64_BISIL_PLAN_INTS 5
+int resnmtf_fp64_bisil_plan(int n_u, int n_mem, int k, long long row_stride, long long col_stride, int* out);
+
 /* ---- phase-level entry points (views sharded one-per-GPU; host does the exchange) ---- */
 
 /* Which image of X the streaming passes of view v use after its upload: *uses_2byte = 0 (f32 images), 1 (fp16) or

@@ -153,6 +153,17 @@ class Fp64SparseDevice(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("stream", C.c_void_p), ("view", Fp64SparseDeviceView * _MV)]
 
 
+FP64_BISIL_PLAN_INTS = 5   # RESNMTF_FP64_BISIL_PLAN_INTS
+
+
+class Fp64BisilJob(C.Structure):
+    """``resnmtf_fp64_bisil_job`` (include/resnmtf_hip.h): X in host memory (``x``) or in device memory (``x_dev`` read
+    after ``stream``), the host 0 / 1 cluster matrices and the host outputs of ``resnmtf_fp64_bisil``."""
+    _fields_ = [("struct_size", C.c_int), ("n", C.c_int), ("m", C.c_int), ("k", C.c_int), ("metric", C.c_int),
+                ("x", _dp), ("x_dev", DeviceMatrix), ("stream", C.c_void_p),
+                ("row_clusters", _dp), ("col_clusters", _dp), ("row_sil", _dp), ("col_sil", _dp)]
+
+
 # name -> (restype, argtypes); must list every symbol include/resnmtf_hip.h declares
 SIGNATURES = {
     "resnmtf_abi_version": (C.c_int, []),
@@ -209,6 +220,8 @@ SIGNATURES = {
                                           C.c_int]),
     "resnmtf_fp64_run_sparse_device": (C.c_int, [C.c_int, C.POINTER(GroupJob), C.POINTER(Fp64Sparse), C.POINTER(Fp64Device),
                                                  C.POINTER(Fp64SparseDevice), C.c_double, C.c_int]),
+    "resnmtf_fp64_bisil": (C.c_int, [C.c_int, C.POINTER(Fp64BisilJob)]),
+    "resnmtf_fp64_bisil_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, _ip]),
     "resnmtf_bisil": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_bisil_sparse": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_bisil_device": (C.c_int, [_h, C.c_int, C.c_int, _dm, _dm, C.c_int, C.c_void_p, C.c_void_p, _dp, C.c_void_p]),

@@ -31,6 +31,10 @@ are scored only with the further opt-in ``bisil_sparse=True`` (``resnmtf_bisil_s
 Its definition restates the published score (the R package's source is not available): parity with ``bisilhouette`` is
 unpinned.
 Without the opt-ins ``bisil`` stays ``None`` and ``k_val=None`` raises ``NotImplementedError``, as before.
+
+Under ``precision="fp64"`` the score is computed in double precision on the numbers that were factorised
+(``res_nmtf_inner(score_bisil=True, fp64_bisil=True)`` -> ``engine.fp64_bisil`` -> ``resnmtf_fp64_bisil``, no handle), and
+``apply_resnmtf(precision="fp64")`` runs a known k or the k sweep on it.
 """
 from __future__ import annotations
 
@@ -106,7 +110,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
                    spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False,
                    sparse_on_device: bool = False, output: str = "numpy", init_lm=None, return_state: bool = False,
                    post_on_device: bool = False, precision: str = "f32", fp64_sparse: bool = False,
-                   fp64_device: bool = False, fp64_sparse_device: bool = False):
+                   fp64_device: bool = False, fp64_sparse_device: bool = False, fp64_bisil: bool = False):
     """``res_nmtf_inner`` (``R/main.r:32-140``).
 
     ``data``: list of pre-processed (non-negative, column-normalised) matrices; ``row_indices[v][w]``
@@ -218,6 +222,15 @@ def res_nmtf_inner(data, row_indices, column_indices,
     ``fp64_device``); ``host_init=True`` then raises the sparse views' ``NotImplementedError``.  ``return_init``,
     ``output="torch"`` and ``return_state`` behave as described above.  Without the flag every refusal above stands word
     for word, the one of sparse tensors under ``fp64_device=True`` included.
+
+    ``fp64_bisil`` (keyword-only opt-in; a no-op with ``precision="f32"``): with
+    ``precision="fp64"``, ``score_bisil`` is honoured: ``"bisil"`` is ``bisil.score`` of the result's clusters over
+    ``engine.fp64_bisil`` -- the per-member silhouettes in double precision (``resnmtf_fp64_bisil``, no handle), computed
+    on the views exactly as the run received them: a host view is uploaded once more for the scoring, a device tensor
+    (``fp64_device``) is read where it lies.  The cluster matrices are brought to the host (n k + m k values per view)
+    and the score is combined there.  Combines with ``fp64_device`` and ``output="torch"``.  A sparse view with
+    ``score_bisil`` raises a ``NotImplementedError`` naming ``fp64_bisil`` and sparse views.  Without the flag every
+    refusal above stands word for word.
     """
     if precision not in ("f32", "fp64"):
         raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
@@ -228,7 +241,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
                                     host_init=host_init, return_init=return_init, score_bisil=score_bisil,
                                     spurious_on_device=spurious_on_device, output=output, init_lm=init_lm,
                                     return_state=return_state, post_on_device=post_on_device, fp64_sparse=fp64_sparse,
-                                    fp64_device=fp64_device, fp64_sparse_device=fp64_sparse_device)
+                                    fp64_device=fp64_device, fp64_sparse_device=fp64_sparse_device, fp64_bisil=fp64_bisil)
     device_views.check_output(output)
     _check_post_on_device(post_on_device, output)
     data = _views(data, device_id)
@@ -321,18 +334,19 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
                          distance, no_clusts, *, row_names, col_names, device_id, max_iters, seed, engine_opts, host_init,
                          return_init, score_bisil, spurious_on_device, output, init_lm, return_state, post_on_device,
                          fp64_sparse: bool = False, fp64_device: bool = False, fp64_sparse_device: bool = False,
-                         runner: Optional[Callable] = None):
+                         fp64_bisil: bool = False, runner: Optional[Callable] = None, sil: Optional[Callable] = None):
     """``res_nmtf_inner(precision="fp64")``: the checks of the f32 call, the refusals of what needs a live handle, the
     initial state, then one ``engine.fp64_run`` (``runner`` replaces it: a test hook).  ``fp64_device``: views, factors
     and results may live in device memory (``res_nmtf_inner``'s docstring); the runner then also gets ``output`` and
     ``return_state``.  ``fp64_sparse_device``: a sparse tensor on ``cuda:device_id`` reaches the problem as its
-    ``SparseDeviceView`` -- the same tensor, untouched."""
+    ``SparseDeviceView`` -- the same tensor, untouched.  ``fp64_bisil``: ``score_bisil`` is honoured through
+    ``engine.fp64_bisil`` on the views as they arrived (``sil(v, rc, cc, distance)`` replaces it: a test hook)."""
     def refuse(flag):
         raise NotImplementedError(f'precision="fp64": {flag} needs a live engine handle, which the fp64 path does not '
                                   'keep (it runs through resnmtf_fp64_run); use precision="f32" for it')
     device_views.check_output(output)
     remove = bool(spurious) and not no_clusts
-    for flag, on in (("spurious_on_device", remove and spurious_on_device), ("score_bisil", score_bisil),
+    for flag, on in (("spurious_on_device", remove and spurious_on_device), ("score_bisil", score_bisil and not fp64_bisil),
                      ("post_on_device", post_on_device), ('output="torch"', output == "torch" and not fp64_device),
                      ("return_state", return_state and not fp64_device)):
         if on:
@@ -364,6 +378,10 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
         views.append(np.asarray(d, dtype=np.float64))
     data, n_v = views, len(views)
     is_sp = [sparse.is_sparse_view(d) for d in data]
+    score = bool(score_bisil) and not no_clusts                  # (here: fp64_bisil is set, or the call was refused above)
+    if score and any(is_sp):
+        raise NotImplementedError(f'precision="fp64": score_bisil with fp64_bisil=True scores dense views only; sparse views '
+                                  f'(view {is_sp.index(True)}) are not supported by resnmtf_fp64_bisil')
     if any(device_views.is_device_view(d) and not is_sp[v] for v, d in enumerate(data)) and host_init and (init_f is None or init_g is None or init_s is None):
         raise NotImplementedError("host_init=True (NumPy's dense SVD) is not available for views in device memory; the "
                                   "device initialisation (host_init=False) works on them")
@@ -435,7 +453,14 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
         return inner_result(out["f"], out["s"], out["g"], init=init_state, state=state)
     clusters = _binary_clusters_device if output == "torch" else batched._binary_clusters
     rcs, ccs = zip(*[clusters(f, g, s) for f, g, s in zip(out["f"], out["g"], out["s"])])
-    return inner_result(out["f"], out["s"], out["g"], np.asarray(out["all_error"], dtype=np.float64), n_iters, bisil=None,
+    score_value = None
+    if score:                                     # obtain_bicl.r:189-199, on the numbers that were factorised (section 26)
+        if sil is None:
+            def sil(v, rc, cc, distance):
+                return _engine.fp64_bisil(data[v], rc, cc, distance, device_id=device_id)
+        score_value = bisil.score([device_views.to_numpy(rc) for rc in rcs], [device_views.to_numpy(cc) for cc in ccs],
+                                  distance, sil=sil)
+    return inner_result(out["f"], out["s"], out["g"], np.asarray(out["all_error"], dtype=np.float64), n_iters, bisil=score_value,
                         row_clusters=list(rcs), col_clusters=list(ccs), lam=out["lambda"], mu=out["mu"], init=init_state,
                         state=state)
 
@@ -654,7 +679,9 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                   device_id: int = 0, max_iters: int = 100000, seed: Optional[int] = None,
                   k_sweep: bool = False, return_sweep: bool = False, sweep_runner: Optional[Callable] = None,
                   spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False,
-                  sparse_on_device: bool = False, output: str = "numpy", post_on_device: bool = False):
+                  sparse_on_device: bool = False, output: str = "numpy", post_on_device: bool = False,
+                  precision: str = "f32", score_bisil: bool = False, fp64_sparse: bool = False, fp64_device: bool = False,
+                  fp64_sparse_device: bool = False, fp64_bisil: bool = False):
     """``apply_resnmtf`` (``R/main.r:214-335``) for a known ``k_val``: naming, shared-name maps, restriction
     symmetrisation, non-negativity shift and column normalisation on the host, then the device loop and -- with
     ``stability=True`` (the default) and ``spurious=False`` -- ``stability_check`` on the pre-processed data, as
@@ -706,7 +733,27 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     ``post_on_device=True`` (keyword-only opt-in, needs ``output="torch"``): the steps after the
     loop stay on the device, in ``res_nmtf_inner`` and for every k of the sweep, the extension k's included
     (``DeviceData.factorise(post_on_device=True)``; removal and ``bisil`` from the tensors it returns).  Same result,
-    bit for bit."""
+    bit for bit.
+
+    ``precision`` (keyword-only; ``"f32"``, the default, is everything above, untouched, and ``score_bisil`` and the
+    ``fp64_*`` flags are then not read; anything but ``"f32"`` or ``"fp64"`` is a ``ValueError``).  ``"fp64"`` (DESIGN.md
+    section 26) runs ``res_nmtf_inner(precision="fp64")`` on the prepared data: with a ``k_val`` once, ``score_bisil`` and
+    the ``fp64_sparse`` / ``fp64_device`` / ``fp64_sparse_device`` / ``fp64_bisil`` flags passed through; with
+    ``k_val=None, k_sweep=True`` for every k of the reference's sweep, each scored in double precision
+    (``score_bisil=True, fp64_bisil=True``, seed ``seed + k``, the correct shared maps for every k), the selection being
+    ``_sweep`` as above with the cap ``min(ncol, 64)``; ``return_sweep`` and ``sweep_runner`` work as before.  Refused
+    with a ``NotImplementedError`` naming the flag: ``stability=True`` (the repeats run on the f32 engine; mixing the two
+    precisions is left for later), ``spurious=True``, sparse views in the sweep, and views in device memory (their
+    pre-processing runs at an f32 engine's upload; pass pre-processed tensors to ``res_nmtf_inner``)."""
+    if precision not in ("f32", "fp64"):
+        raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
+    if precision == "fp64":
+        return _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_min, k_max, distance, spurious,
+                           num_repeats, no_clusts, sample_rate, n_stability, stability, stab_thres, row_names=row_names,
+                           col_names=col_names, device_id=device_id, max_iters=max_iters, seed=seed, k_sweep=k_sweep,
+                           return_sweep=return_sweep, sweep_runner=sweep_runner, output=output, score_bisil=score_bisil,
+                           fp64_sparse=fp64_sparse, fp64_device=fp64_device, fp64_sparse_device=fp64_sparse_device,
+                           fp64_bisil=fp64_bisil)
     device_views.check_output(output)
     _check_post_on_device(post_on_device, output)
     on_dev = {"sparse_on_device": True} if sparse_on_device else {}      # (off: every call below is the earlier one)
@@ -749,6 +796,75 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                                   row_names=p.row_names, col_names=p.col_names, device_id=device_id, seed=seed,
                                   max_iters=max_iters, spurious_on_device=spurious_on_device,
                                   shuffle_sparse=shuffle_sparse, **on_dev, **out_kw)
+    return results
+
+
+def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_min, k_max, distance, spurious, num_repeats,
+                no_clusts, sample_rate, n_stability, stability, stab_thres, *, row_names, col_names, device_id, max_iters,
+                seed, k_sweep, return_sweep, sweep_runner, output, score_bisil, fp64_sparse, fp64_device,
+                fp64_sparse_device, fp64_bisil):
+    """``apply_resnmtf(precision="fp64")``: the checks of the f32 function, the refusals of what runs on the f32 engine,
+    ``prepare``, then ``res_nmtf_inner(precision="fp64")`` -- once for a ``k_val``, or as ``run(k)`` of ``_sweep``."""
+    def refuse(flag, why):
+        raise NotImplementedError(f'apply_resnmtf(precision="fp64"): {flag} is not supported: {why}')
+    device_views.check_output(output)
+    data = _views(data, device_id)
+    n_v = len(data)
+    sweep = k_val is None and k_sweep
+    if k_val is None and not k_sweep:
+        raise NotImplementedError("the k sweep (R/main.r:279-321) needs the bisilhouette score, which is "
+                                  "outside the accelerated path; pass k_val")
+    _check_common(n_iters, num_repeats, n_stability, distance, sample_rate, stab_thres)
+    if sweep:                                     # the checks of _apply_k_sweep, in its order
+        _check_whole_number(k_min, "k_min")
+        _check_whole_number(k_max, "k_max")
+        if k_max <= k_min:
+            raise ValueError("k_max must be greater than k_min.")                                 # utils.r:250-252
+        k_min, k_max = int(k_min), int(k_max)
+        if no_clusts:
+            raise ValueError("the k sweep ranks the biclusters by their bisilhouette score: no_clusts=True has none")
+    if stability:
+        refuse("stability=True", "the stability repeats run on the f32 engine; pass stability=False")
+    if spurious and not no_clusts:
+        refuse("spurious=True", "spurious-bicluster removal runs on the f32 engine; pass spurious=False")
+    if any(device_views.is_device_view(d) for d in data):
+        refuse("a view in device memory", "its shift and column normalisation run at an f32 engine's upload; pass host "
+               "arrays, or pre-processed tensors to res_nmtf_inner(precision=\"fp64\", fp64_device=True)")
+    flags = {"fp64_sparse": fp64_sparse, "fp64_device": fp64_device, "fp64_sparse_device": fp64_sparse_device}
+    common = {"device_id": device_id, "max_iters": max_iters, "output": output, "precision": "fp64", **flags}
+    if not sweep:
+        k_vec = [int(np.atleast_1d(k_val)[0])] * n_v                                              # main.r:226
+        if any(k < 1 for k in k_vec):
+            raise ValueError("k_vec must be a vector of integers greater than 1.")                # utils.r:437
+        if any(k > d.shape[1] for k, d in zip(k_vec, data)):
+            raise ValueError("k_vec must be a vector of integers less than or equal to the ranks of the views.")
+        p = prepare(data, phi, xi, psi, row_names, col_names, normalise=True, symmetrise=True)    # main.r:228-237
+        return res_nmtf_inner(p.data, p.row_shared, p.col_shared, init_f, init_s, init_g, k_vec, p.phi, p.xi, p.psi, n_iters,
+                              num_repeats, spurious, distance, no_clusts, row_names=p.row_names, col_names=p.col_names,
+                              seed=seed, score_bisil=score_bisil, fp64_bisil=fp64_bisil, **common)
+    if any(sparse.is_sparse_view(d) for d in data):
+        refuse("a sparse view in the k sweep", "resnmtf_fp64_bisil scores dense views only; pass k_val (with fp64_sparse=True)")
+    if init_f is not None or init_s is not None or init_g is not None:
+        raise NotImplementedError("the k sweep starts every k from the device's SVD initialisation; explicit initial "
+                                  "factors are not supported with k_val=None")
+    cap = min(min(d.shape[1] for d in data), 64)
+    if k_max > cap:
+        raise ValueError("k_vec must be a vector of integers less than or equal to the ranks of the views.")
+    seed = _seed(seed)
+    p = prepare(data, phi, xi, psi, row_names, col_names, normalise=True, symmetrise=True)        # main.r:228-237
+
+    # every k, the extra ones included, with the correct shared maps (R's extension loop passes NULL ones,
+    # R/main.r:305-309; DESIGN.md section 13)
+    def run(k):
+        return res_nmtf_inner(p.data, p.row_shared, p.col_shared, None, None, None, [k] * n_v, p.phi, p.xi, p.psi, n_iters,
+                              num_repeats, False, distance, False, row_names=p.row_names, col_names=p.col_names,
+                              seed=seed + k, score_bisil=True, fp64_bisil=True, **common)
+
+    ks, scores, results, pick = _sweep(sweep_runner or run, k_min, k_max, cap)
+    results = results[pick]                                                                       # main.r:313-314
+    if return_sweep:
+        results = dict(results)
+        results["k_sweep"] = {"k": ks, "bisil": scores}
     return results
 
 

@@ -2,6 +2,8 @@
 // bisilhouette score that res_nmtf_inner reports as `bisil` (R/obtain_bicl.r:189-199) and that the k sweep of
 // apply_resnmtf ranks (R/main.r:291-312).  Included by resnmtf_hip.hip; fp64 arithmetic over the fp32 image values.
 // DESIGN.md section 13 holds the definition; this unit and resnmtf_amd/bisil.py are its only two statements.
+// resnmtf_fp64_bisil.hip.inc (the fp64 unit, section 26) is this file's TWIN: the norm, distance and epilogue arithmetic
+// stated a second time over a `double` G.  A change to the arithmetic here is a change there.
 //
 // One side (rows, or columns with the roles swapped) of one active bicluster k is three or four launches:
 //   bisil_gather_kernel   G[f][u] = X(U[u], J_k[f]) as fp32, feature-major [|J_k|][U_pad]: U = the union of the active
@@ -212,14 +214,9 @@ bisil_epilogue_kernel(const double* __restrict__ partial, int n_chunks, int n_me
   sil[(size_t)k * n_pts + upts[mpos[m]]] = s;
 }
 
-// one side of resnmtf_bisil on the host: points = rows (features = columns) or the reverse; every list is 0-based
-struct BisilSide {
-  int n_pts = 0;
-  std::vector<int> upts;                      // U: the points in an active bicluster, ascending
-  std::vector<unsigned long long> umask;      // their active-bicluster bits
-  std::vector<std::vector<int>> mpos;         // per bicluster: its members as positions in U
-  std::vector<int> cnt;                       // per bicluster: |I_l|
-};
+// (the host's lists of a call -- U, the masks, every bicluster's members and features -- are BisilHostLists,
+// resnmtf_bisil_plan.h, shared with resnmtf_fp64_bisil)
+static_assert(BISIL_TILE == BISIL_PLAN_TILE, "the chunk rule of resnmtf_bisil_plan.h counts this kernel's tiles");
 
 template <int METRIC>
 void bisil_launch_dist_m(int kq, dim3 grid, hipStream_t st, const float* G, int nf, int upad, int n_u, const int* mpos,

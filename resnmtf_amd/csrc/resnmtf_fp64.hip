@@ -9,6 +9,10 @@
 // checks, the launch sequence of a sweep (fp64_enqueue_sweep), the owner of a run's stream and memory (F64Run) and the
 // stages fp64_run_impl calls in order, one body for all four entries.  The job checks and the error text are the main
 // unit's (resnmtf_internal.h): these entries and resnmtf_group_run refuse the same things with the same texts.
+//
+// resnmtf_fp64_bisil (section 26), at the end of the file, scores a result in double precision: its kernels are
+// resnmtf_fp64_bisil.hip.inc, its index lists, chunk rule and workspace resnmtf_bisil_plan.h (plain C++, shared with the
+// main unit's resnmtf_bisil), its owner F64BisilRun.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,6 +29,8 @@
 #include "resnmtf_fp64_sparse.hip.inc"
 #include "resnmtf_fp64_device.hip.inc"
 #include "resnmtf_fp64_sparse_device.hip.inc"
+#include "resnmtf_bisil_plan.h"
+#include "resnmtf_fp64_bisil.hip.inc"
 
 namespace {
 // one sweep of update_matrices (R/update_steps.r:272-319, views in index order) and the error of every view; the mean
@@ -785,3 +791,154 @@ int fp64_run_impl(int device_id, const resnmtf_group_job* job, const resnmtf_fp6
   return rc;
 }
 }  // namespace
+
+// ---- resnmtf_fp64_bisil: the silhouettes of R/obtain_bicl.r:189-199 on the fp64 values of X ----
+namespace {
+// What a call holds on the device: its stream and its one buffer.  On every way out the destructor waits for the stream
+// and destroys it, then frees the buffer.
+class F64BisilRun {
+ public:
+  F64BisilRun() = default;
+  F64BisilRun(const F64BisilRun&) = delete;
+  F64BisilRun& operator=(const F64BisilRun&) = delete;
+  ~F64BisilRun() {
+    if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+    if (buf) (void)hipFree(buf);
+  }
+  int fail(hipError_t e, const char* what = "fp64_bisil: ") {
+    resnmtf_set_create_error(std::string(what) + hipGetErrorString(e));
+    return RESNMTF_ERR_HIP;
+  }
+  hipStream_t st = nullptr;
+  double* buf = nullptr;
+};
+
+// the launches of every side and active bicluster on the run's stream
+hipError_t fp64_bisil_enqueue(hipStream_t st, const resnmtf_device_matrix& x, int n, int m, int k, int metric,
+                              const BisilHostLists& L, const F64BisilPlan& plan, const F64BisilMeta& M, double* buf) {
+  double* G = buf;
+  double* norm2 = buf + plan.norm2;
+  double* partial = buf + plan.partial;
+  double* sil = buf + plan.sil;
+  const unsigned long long* dmeta = reinterpret_cast<const unsigned long long*>(buf + plan.meta);
+  const int* dints = reinterpret_cast<const int*>(dmeta);
+  hipError_t e = hipMemsetAsync(norm2, 0, plan.upad_max * sizeof(double), st);
+  for (int sd = 0; sd < 2 && e == hipSuccess; ++sd) {
+    const BisilHostSide& s = L.side[sd];
+    const int n_u = (int)s.upts.size(), upad = (n_u + F64_BISIL_TILE - 1) / F64_BISIL_TILE * F64_BISIL_TILE;
+    const int n_pts = sd == 0 ? n : m;
+    const unsigned long long* umask = dmeta + M.mask[sd];
+    const int* upts = dints + M.pts[sd];
+    double* out = sil + (sd == 0 ? 0 : (size_t)n * k);
+    for (int j = 0; j < k && e == hipSuccess; ++j) {
+      if (!((L.active >> j) & 1ull)) continue;
+      const int nf = L.side[1 - sd].cnt[j], n_mem = s.cnt[j];
+      const int* feat = dints + M.feat[sd][j];
+      const int* mpos = dints + M.mpos[sd][j];
+      fp64_bisil_gather(st, x, sd, feat, nf, upts, n_u, upad, G);
+      if (metric == F64_BISIL_COSINE)
+        hipLaunchKernelGGL(fp64_bisil_norm_kernel, dim3((upad + 255) / 256), dim3(256), 0, st, (const double*)G, nf, upad, norm2);
+      const dim3 grid((n_mem + F64_BISIL_TILE - 1) / F64_BISIL_TILE, plan.chunks[sd][j]);
+      fp64_bisil_dist(metric, plan.kq, grid, st, G, nf, upad, n_u, mpos, n_mem, umask, norm2, k, plan.chunk_tiles[sd][j], partial);
+      hipLaunchKernelGGL(fp64_bisil_epilogue_kernel, dim3((n_mem + 3) / 4), dim3(256), 0, st, (const double*)partial,
+                         plan.chunks[sd][j], n_mem, k, j, mpos, umask, upts, dints + M.cnt[sd], L.active, n_pts, out);
+      e = hipGetLastError();
+    }
+  }
+  return e;
+}
+}  // namespace
+
+extern "C" {
+
+int resnmtf_fp64_bisil(int device_id, const resnmtf_fp64_bisil_job* job) {
+  if (!job) return fp64_bad("job is NULL");
+  if (job->struct_size != (int)sizeof(resnmtf_fp64_bisil_job)) return fp64_bad("resnmtf_fp64_bisil_job struct_size mismatch");
+  const int n = job->n, m = job->m, k = job->k, metric = job->metric;
+  if (k < 1 || k > RESNMTF_MAX_K) return fp64_bad("k must be in [1, 64]");
+  if (n < 1 || m < 1) return fp64_bad("view dimensions must be positive");
+  if (metric < F64_BISIL_EUCLIDEAN || metric > F64_BISIL_COSINE)
+    return fp64_bad("metric must be 0 (euclidean), 1 (manhattan) or 2 (cosine)");
+  const bool host_x = job->x != nullptr;
+  if (host_x == (job->x_dev.ptr != nullptr))
+    return fp64_bad(host_x ? "X is given in two places (job->x and job->x_dev)" : "X is given in no place (job->x or job->x_dev)");
+  if (!job->row_clusters || !job->col_clusters || !job->row_sil || !job->col_sil)
+    return fp64_bad("row_clusters / col_clusters / row_sil / col_sil are NULL");
+  resnmtf_device_matrix x = job->x_dev;
+  if (!host_x) {
+    if (x.dtype < RESNMTF_DTYPE_F64 || x.dtype > RESNMTF_DTYPE_BF16) return fp64_bad("x_dev: unknown dtype");
+    if (x.row_stride < 0 || x.col_stride < 0) return fp64_bad("x_dev: strides must be >= 0");
+    const size_t last = (size_t)(n - 1) * (size_t)x.row_stride + (size_t)(m - 1) * (size_t)x.col_stride;
+    bool beyond = false;
+    if (!fp64_on_device(device_id, x.ptr, (last + 1) * fp64_dtype_bytes(x.dtype), beyond))
+      return fp64_bad(beyond ? std::string("x_dev reaches beyond its allocation (too short for the shape and strides given)")
+                             : "x_dev is not device memory of device " + std::to_string(device_id));
+  }
+  BisilHostLists L;
+  if (const int which = bisil_build_lists(n, m, k, job->row_clusters, job->col_clusters, L))
+    return fp64_bad(which == 1 ? "row_clusters entries must be 0 or 1" : "col_clusters entries must be 0 or 1");
+  if (!L.active) {
+    std::fill(job->row_sil, job->row_sil + (size_t)n * k, 0.0);
+    std::fill(job->col_sil, job->col_sil + (size_t)m * k, 0.0);
+    return RESNMTF_OK;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { resnmtf_set_create_error("no HIP device"); return RESNMTF_ERR_NO_DEVICE; }
+  if (device_id < 0 || device_id >= ndev) return fp64_bad("device_id out of range");
+  F64BisilRun run;
+  hipError_t e = hipSetDevice(device_id);
+  if (e != hipSuccess) return run.fail(e, "hipSetDevice: ");
+  // the workspace, sized before anything is allocated
+  F64BisilMeta M;
+  f64_bisil_pack(k, L, M);
+  const int n_u[2] = {(int)L.side[0].upts.size(), (int)L.side[1].upts.size()};
+  const int* const cnt[2] = {L.side[0].cnt.data(), L.side[1].cnt.data()};
+  F64BisilPlan plan;
+  f64_bisil_plan(n, m, k, L.active, n_u, cnt, M.words.size(), host_x, plan);
+  const size_t bytes = plan.total * sizeof(double);
+  size_t free_b = 0, total_b = 0;
+  if ((e = hipMemGetInfo(&free_b, &total_b)) != hipSuccess) return run.fail(e);
+  if (bytes > free_b) {
+    resnmtf_set_create_error("fp64_bisil workspace: " + std::to_string(bytes) + " bytes asked for (" + std::to_string(plan.g_dbl * sizeof(double)) +
+                             " of them the restricted block, features x padded members" +
+                             (host_x ? ", " + std::to_string((size_t)n * m * sizeof(double)) + " the fp64 copy of X" : std::string()) + "), " +
+                             std::to_string(free_b) + " free on the device");
+    return RESNMTF_ERR_ALLOC;
+  }
+  void* p = nullptr;
+  if ((e = hipMalloc(&p, bytes)) != hipSuccess) {
+    (void)hipGetLastError();
+    resnmtf_set_create_error(std::string("fp64_bisil workspace: ") + hipGetErrorString(e) + " (" + std::to_string(bytes) + " bytes asked for)");
+    return e == hipErrorOutOfMemory ? RESNMTF_ERR_ALLOC : RESNMTF_ERR_HIP;
+  }
+  run.buf = static_cast<double*>(p);
+  if ((e = hipStreamCreateWithFlags(&run.st, hipStreamNonBlocking)) != hipSuccess) { run.st = nullptr; return run.fail(e, "hipStreamCreate: "); }
+  if (host_x) {                               // one plain n x m fp64 copy; it then goes through the same gather
+    e = hipMemcpyAsync(run.buf + plan.x, job->x, (size_t)n * m * sizeof(double), hipMemcpyHostToDevice, run.st);
+    x.ptr = run.buf + plan.x; x.dtype = RESNMTF_DTYPE_F64; x.row_stride = 1; x.col_stride = n;
+  } else {
+    e = wait_for_caller(run.st, job->stream);
+  }
+  const size_t sil_dbl = (size_t)n * k + (size_t)m * k;
+  if (e == hipSuccess) e = hipMemcpyAsync(run.buf + plan.meta, M.words.data(), M.words.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, run.st);
+  if (e == hipSuccess) e = hipMemsetAsync(run.buf + plan.sil, 0, sil_dbl * sizeof(double), run.st);
+  if (e == hipSuccess) e = fp64_bisil_enqueue(run.st, x, n, m, k, metric, L, plan, M, run.buf);
+  if (e == hipSuccess) e = hipMemcpyAsync(job->row_sil, run.buf + plan.sil, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, run.st);
+  if (e == hipSuccess) e = hipMemcpyAsync(job->col_sil, run.buf + plan.sil + (size_t)n * k, (size_t)m * k * sizeof(double), hipMemcpyDeviceToHost, run.st);
+  if (e == hipSuccess) e = hipStreamSynchronize(run.st);
+  return e == hipSuccess ? RESNMTF_OK : run.fail(e);
+}
+
+int resnmtf_fp64_bisil_plan(int n_u, int n_mem, int k, long long row_stride, long long col_stride, int* out) {
+  if (!out) return fp64_bad("out is NULL");
+  if (n_u < 1 || n_mem < 1) return fp64_bad("n_u and n_mem must be positive");
+  if (k < 1 || k > RESNMTF_MAX_K) return fp64_bad("k must be in [1, 64]");
+  if (row_stride < 0 || col_stride < 0) return fp64_bad("strides must be >= 0");
+  const BisilChunks c = bisil_chunk_rule(n_u, n_mem);
+  const int vals[RESNMTF_FP64_BISIL_PLAN_INTS] = {bisil_kq(k), c.chunk_tiles, c.chunks, f64_bisil_side_form(0, row_stride, col_stride),
+                                                  f64_bisil_side_form(1, row_stride, col_stride)};
+  std::memcpy(out, vals, sizeof(vals));
+  return RESNMTF_OK;
+}
+
+}  // extern "C"

@@ -40,6 +40,7 @@
 #include "resnmtf_sparse_device_view.hip.inc"
 #include "resnmtf_jsd.hip.inc"
 #include "resnmtf_group.hip.inc"
+#include "resnmtf_bisil_plan.h"
 #include "resnmtf_bisil.hip.inc"
 #include "resnmtf_split_tu.h"
 #include "resnmtf_internal.h"
@@ -3938,21 +3939,21 @@ struct BisilPlan {
 void bisil_plan(int k, unsigned long long active, const int n_u[2], const int* const cnt[2], BisilPlan& p) {
   p = BisilPlan();
   for (int sd = 0; sd < 2; ++sd) {
-    const int upad = round_up(n_u[sd], BISIL_TILE), tiles_u = upad / BISIL_TILE;
+    const int upad = round_up(n_u[sd], BISIL_TILE);
     p.upad_max = std::max<size_t>(p.upad_max, upad);
     for (int j = 0; j < k; ++j) {
       if (!((active >> j) & 1ull)) continue;
-      const int n_mem = cnt[sd][j], tiles_m = ceil_div(n_mem, BISIL_TILE);
+      const int n_mem = cnt[sd][j];
       // enough workgroups to fill the device: the others are split into chunks of whole tiles, summed in order later
-      // (tests/test_gpu_bisil_forms.py restates this rule and the kq table below: change them together)
-      const int want = std::max(1, std::min(tiles_u, ceil_div(2048, tiles_m)));
-      p.chunk_tiles[sd][j] = ceil_div(tiles_u, want);
-      p.chunks[sd][j] = ceil_div(tiles_u, p.chunk_tiles[sd][j]);
+      // (the rule and the kq table: resnmtf_bisil_plan.h, one statement for this unit and resnmtf_fp64_bisil)
+      const BisilChunks c = bisil_chunk_rule(n_u[sd], n_mem);
+      p.chunk_tiles[sd][j] = c.chunk_tiles;
+      p.chunks[sd][j] = c.chunks;
       p.g_floats = std::max(p.g_floats, (size_t)cnt[1 - sd][j] * upad);
       p.part_dbl = std::max(p.part_dbl, (size_t)p.chunks[sd][j] * n_mem * k);
     }
   }
-  p.kq = k <= 4 ? 1 : k <= 8 ? 2 : k <= 16 ? 4 : k <= 32 ? 8 : 16;
+  p.kq = bisil_kq(k);
 }
 
 // `bytes` of transient device memory from `sc`, refused with the sizes when the device has not that much free
@@ -4047,46 +4048,19 @@ int bisil_impl(resnmtf_handle* h, int v, int k, const double* row_clusters, cons
   const ViewState& vs = h->views[v];
   if (int rc = bisil_check_state(h, vs, false, &from_sparse)) return rc;
   const int n = vs.n, m = vs.m;
-  std::vector<unsigned long long> rbits(n, 0ull), cbits(m, 0ull);
-  std::vector<int> rcount(k, 0), ccount(k, 0);
-  for (int j = 0; j < k; ++j) {
-    for (int r = 0; r < n; ++r) {
-      const double x = row_clusters[(size_t)j * n + r];
-      if (x != 0.0 && x != 1.0) return h->fail(RESNMTF_ERR_INVALID, "row_clusters entries must be 0 or 1");
-      if (x != 0.0) { rbits[r] |= 1ull << j; ++rcount[j]; }
-    }
-    for (int c = 0; c < m; ++c) {
-      const double x = col_clusters[(size_t)j * m + c];
-      if (x != 0.0 && x != 1.0) return h->fail(RESNMTF_ERR_INVALID, "col_clusters entries must be 0 or 1");
-      if (x != 0.0) { cbits[c] |= 1ull << j; ++ccount[j]; }
-    }
-  }
-  unsigned long long active = 0ull;                            // biclusters with rows and columns
-  for (int j = 0; j < k; ++j) if (rcount[j] > 0 && ccount[j] > 0) active |= 1ull << j;
-  auto build = [&](const std::vector<unsigned long long>& bits, const std::vector<int>& count, int n_pts) {
-    BisilSide s;
-    s.n_pts = n_pts; s.cnt = count; s.mpos.resize(k);
-    for (int p = 0; p < n_pts; ++p) {
-      const unsigned long long b = bits[p] & active;
-      if (!b) continue;
-      for (int j = 0; j < k; ++j) if ((b >> j) & 1ull) s.mpos[j].push_back((int)s.upts.size());
-      s.upts.push_back(p); s.umask.push_back(b);
-    }
-    return s;
-  };
-  const BisilSide side[2] = {build(rbits, rcount, n), build(cbits, ccount, m)};
-  // per side: the features of bicluster j are the other side's members of j, as point indices
-  auto features = [&](int sd, int j) {
-    std::vector<int> f;
-    const BisilSide& o = side[1 - sd];
-    for (int p : o.mpos[j]) f.push_back(o.upts[p]);
-    return f;
-  };
+  // the membership words, counts, U, masks and member lists of both sides (resnmtf_bisil_plan.h: shared with
+  // resnmtf_fp64_bisil); per side the features of bicluster j are the other side's members of j, as point indices
+  BisilHostLists lists;
+  if (const int which = bisil_build_lists(n, m, k, row_clusters, col_clusters, lists))
+    return h->fail(RESNMTF_ERR_INVALID, which == 1 ? "row_clusters entries must be 0 or 1" : "col_clusters entries must be 0 or 1");
+  const unsigned long long active = lists.active;              // biclusters with rows and columns
+  const BisilHostSide (&side)[2] = lists.side;
+  auto features = [&](int sd, int j) { return lists.features(sd, j); };
   std::fill(row_sil, row_sil + (size_t)n * k, 0.0);
   std::fill(col_sil, col_sil + (size_t)m * k, 0.0);
   if (!active) return RESNMTF_OK;
   const int n_u[2] = {(int)side[0].upts.size(), (int)side[1].upts.size()};
-  const int* const cnt[2] = {rcount.data(), ccount.data()};
+  const int* const cnt[2] = {side[0].cnt.data(), side[1].cnt.data()};
   BisilPlan plan;
   bisil_plan(k, active, n_u, cnt, plan);
   // host image of the metadata: per side [umask (u64) | upts | cnt | (sparse: rank) | per active j: mpos_j | feat_j];
@@ -4097,7 +4071,7 @@ int bisil_impl(resnmtf_handle* h, int v, int k, const double* row_clusters, cons
     std::vector<int> ints;
     auto put = [&](const std::vector<int>& a) { const size_t o = ints.size(); ints.insert(ints.end(), a.begin(), a.end()); return o; };
     for (int sd = 0; sd < 2; ++sd) {
-      const BisilSide& s = side[sd];
+      const BisilHostSide& s = side[sd];
       off_pts[sd] = put(s.upts);
       off_cnt[sd] = put(s.cnt);
       if (from_sparse) {

@@ -372,6 +372,64 @@ def fp64_run(problem, tol: float = 1.0e-6, max_iters: int = 100000, device_id: i
     return _group_result(out)
 
 
+def fp64_bisil(x, rc, cc, distance: str = "euclidean", device_id: int = 0):
+    """The per-member silhouettes of one view's biclusters in double precision (``resnmtf_fp64_bisil``, no handle;
+    DESIGN.md section 26): ``Engine.bisil``'s definition, metrics and result -- ``(row_sil, col_sil)``, n x k and m x k
+    NumPy arrays, 0 at non-members -- on the fp64 values of ``x``, where ``Engine.bisil`` reads a handle's fp32 image.
+    ``x``: a NumPy array or a CPU tensor (copied once to the device as fp64), or a 2-D floating ``torch`` tensor on
+    ``cuda:device_id`` (fp64 / fp32 / fp16 / bf16, any strides, an expanded one included), read where it lies, ordered
+    after the work on torch's current stream of that device (``device_views.as_view``'s checks: ``ValueError``).
+    ``rc`` / ``cc``: n x k and m x k 0 / 1 matrices, NumPy arrays or tensors (brought to the host).  Two calls give equal
+    bits; on data that fp32 holds exactly the result is bitwise ``Engine.bisil``'s.  Bad input is refused before any
+    device work (``ResnmtfError``), a workspace the device cannot hold with ``RESNMTF_ERR_ALLOC`` and its byte count."""
+    from .bisil import METRICS
+    if distance not in METRICS:
+        raise ValueError("distance must be one of 'euclidean', 'manhattan' or 'cosine'.")
+    lib = _lib.load()
+    x = _device_views.as_view(x, device_id, "fp64_bisil: x")
+    if _sparse.is_sparse_view(x) or isinstance(x, _device_views.RawDeviceView):
+        raise NotImplementedError("fp64_bisil scores dense views: a sparse view is not supported")
+    if len(x.shape) != 2:
+        raise ValueError("fp64_bisil: x must be an n x m matrix")
+    n, m = int(x.shape[0]), int(x.shape[1])
+    rc = np.asfortranarray(np.asarray(_device_views.to_numpy(rc), dtype=np.float64))
+    if rc.ndim != 2 or rc.shape[0] != n:
+        raise ValueError(f"row clusters must be {n} x k")
+    cc = _f64_colmajor(_device_views.to_numpy(cc), (m, rc.shape[1]))
+    k = int(rc.shape[1])
+    rs = np.zeros((n, k), order="F"); cs = np.zeros((m, k), order="F")
+    job = _lib.Fp64BisilJob()
+    job.struct_size = C.sizeof(job)
+    job.n, job.m, job.k, job.metric = n, m, k, METRICS[distance]
+    if _device_views.is_tensor(x):
+        import torch                # (lazily: nothing else in this module needs it)
+        job.x_dev = _device_matrix(x, (n, m), device_id, "fp64_bisil: x")
+        job.stream = torch.cuda.current_stream(torch.device("cuda", int(device_id))).cuda_stream
+    else:
+        x = _f64_colmajor(x)
+        job.x = _dp(x)
+    job.row_clusters, job.col_clusters, job.row_sil, job.col_sil = _dp(rc), _dp(cc), _dp(rs), _dp(cs)
+    code = lib.resnmtf_fp64_bisil(int(device_id), C.byref(job))
+    if code != _lib.OK:
+        raise ResnmtfError(code, (lib.resnmtf_last_error(None) or b"").decode())
+    return rs, cs
+
+
+def fp64_bisil_plan(n_u: int, n_mem: int, k: int, row_stride: int = 1, col_stride: int = 1) -> dict:
+    """How ``fp64_bisil`` launches one side of one bicluster (``resnmtf_fp64_bisil_plan``; no device work): ``{"kq",
+    "chunk_tiles", "chunks", "gather": (form of the row side, of the column side)}`` for ``n_u`` points in U, ``n_mem``
+    members, ``k`` biclusters and an X with the given strides in elements; a gather form is ``"points"`` (lanes along the
+    points, G written directly) or ``"lds"`` (a 32 x 32 tile through LDS, read along the features)."""
+    lib = _lib.load()
+    out = (C.c_int * _lib.FP64_BISIL_PLAN_INTS)()
+    rc = lib.resnmtf_fp64_bisil_plan(int(n_u), int(n_mem), int(k), int(row_stride), int(col_stride), out)
+    if rc != _lib.OK:
+        raise ResnmtfError(rc, (lib.resnmtf_last_error(None) or b"").decode())
+    v = list(out)
+    forms = ("points", "lds")
+    return {"kq": v[0], "chunk_tiles": v[1], "chunks": v[2], "gather": (forms[v[3]], forms[v[4]])}
+
+
 def fp64_sparse_plan(x, k: int) -> dict:
     """How ``fp64_run`` streams the sparse view ``x`` (a ``scipy.sparse`` matrix, taken as its canonical CSC) at ``k``
     (``resnmtf_fp64_sparse_plan``; no device work): ``{"kp", "xg": (splits, entries per piece, longest row), "xtf":
