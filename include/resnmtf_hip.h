@@ -1066,6 +1066,54 @@ int resnmtf_fp64_bisil(int device_id, const resnmtf_fp64_bisil_job* job);
 #define RESNMTF_FP64_BISIL_PLAN_INTS 5
 int resnmtf_fp64_bisil_plan(int n_u, int n_mem, int k, long long row_stride, long long col_stride, int* out);
 
+/*
+ * shuffle_view (R/obtain_bicl.r:11-22) of one view in DOUBLE precision, without a handle: the
+ * draw that obtain_shuffled_f (R/obtain_bicl.r:31-42) factorises, made of the fp64 values of X -- the numbers
+ * resnmtf_fp64_run factorised -- where resnmtf_shuffle_view permutes a handle's fp32 image.  Blocking.
+ *   n, m          the view is n x m.
+ *   seed          the draw: out[i] = X[pi(i)], i column-major in out, pi(i) row-major in X, pi the Feistel permutation
+ *                 of resnmtf_shuffle_view for the same seed (csrc/resnmtf_feistel.h).  Every source value is widened
+ *                 to fp64 exactly.
+ *   x             X in host memory: n x m fp64 column-major, as resnmtf_group_job.x holds a view; copied once into a
+ *                 plain n x m fp64 device array; or NULL.
+ *   x_dev, stream X in device memory: any of the four dtypes, any strides >= 0 (0: an expanded tensor), read where it
+ *                 lies after an event recorded on `stream` (the hipStream_t its producer ran on; NULL: the null stream);
+ *                 x_dev.ptr NULL when not given.  X is given in exactly one of the two places.
+ *   out           device memory of device_id owned by the caller: n m doubles, column-major (row stride 1, column
+ *                 stride n).  The draw is written there and normalised in place; a device source needs no n m buffer.
+ *                 It is written after the same event on `stream`, for a host X too (what the caller enqueued may still
+ *                 use the memory), and is complete when the call returns.
+ *   n_empty_rows, n_empty_cols   (host, not NULL) the rows / columns of the draw, BEFORE any shift, that sum to exactly
+ *                 0.0: the redraw condition of R/obtain_bicl.r:14-18 as resnmtf_view_empty_lines reports it.  The caller
+ *                 redraws with another seed; the library does not loop.
+ *   row_mask, col_mask           (host, n and m bytes, or NULL) 1 where a line is empty.
+ *   normalise     != 0: the non-negativity shift and column normalisation apply_resnmtf applies to shuffled data
+ *                 (R/obtain_bicl.r:35 -> R/utils.r:416,422) in fp64, out = (x + shift[c]) / colsum[c]; the column
+ *                 minimum and sum in column_stats_kernel's order (lane t of 256 takes rows t, t + 256, ..., then the
+ *                 256-wide tree), so that on a source fp32 holds the result rounded to fp32 is bit for bit what
+ *                 resnmtf_shuffle_view(normalise = 1) stores.  A column that shifts to all zero gives NaN, as in R.
+ *   was_negative  (host, or NULL) with normalise: 1 if an entry was negative (R/utils.r:23-25); 0 without.
+ * No floating-point atomics: two calls give equal bits (integer atomics for the two counts alone).
+ * Refused before any device work (RESNMTF_ERR_INVALID, text in resnmtf_last_error(NULL)), nothing written: job NULL, a
+ * struct_size mismatch, n or m below 1, n m above 2^62 (the Feistel domain), X in both places or in neither, out NULL,
+ * n_empty_rows / n_empty_cols NULL, an unknown dtype, a negative stride, x_dev.ptr or out not memory of device_id (or too
+ * short for the shape and strides: reaching beyond the allocation the pointer lies in), out overlapping x_dev, device_id
+ * out of range.  The n m doubles that stage a host X are refused with RESNMTF_ERR_ALLOC and the byte count when they
+ * exceed the free device memory, on the byte count alone: before x or out is looked at.
+ */
+typedef struct resnmtf_fp64_shuffle_job {
+  int struct_size;                          /* sizeof the struct */
+  int n, m, normalise;
+  unsigned long long seed;
+  const double* x;
+  resnmtf_device_matrix x_dev;
+  void* stream;
+  double* out;
+  int *was_negative, *n_empty_rows, *n_empty_cols;
+  unsigned char *row_mask, *col_mask;
+} resnmtf_fp64_shuffle_job;
+int resnmtf_fp64_shuffle(int device_id, const resnmtf_fp64_shuffle_job* job);
+
 /* ---- phase-level entry points (views sharded one-per-GPU; host does the exchange) ---- */
 
 /* Which image of X the streaming passes of view v use after its upload: *uses_2byte = 0 (f32 images), 1 (fp16) or

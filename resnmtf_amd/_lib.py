@@ -164,6 +164,15 @@ class Fp64BisilJob(C.Structure):
                 ("row_clusters", _dp), ("col_clusters", _dp), ("row_sil", _dp), ("col_sil", _dp)]
 
 
+class Fp64ShuffleJob(C.Structure):
+    """``resnmtf_fp64_shuffle_job`` (include/resnmtf_hip.h): X in host memory (``x``) or in device memory (``x_dev``), the
+    caller's device array ``out`` (n m doubles, written after ``stream``) and the host outputs of ``resnmtf_fp64_shuffle``."""
+    _fields_ = [("struct_size", C.c_int), ("n", C.c_int), ("m", C.c_int), ("normalise", C.c_int), ("seed", C.c_ulonglong),
+                ("x", _dp), ("x_dev", DeviceMatrix), ("stream", C.c_void_p), ("out", C.c_void_p),
+                ("was_negative", _ip), ("n_empty_rows", _ip), ("n_empty_cols", _ip),
+                ("row_mask", C.POINTER(C.c_ubyte)), ("col_mask", C.POINTER(C.c_ubyte))]
+
+
 # name -> (restype, argtypes); must list every symbol include/resnmtf_hip.h declares
 SIGNATURES = {
     "resnmtf_abi_version": (C.c_int, []),
@@ -222,6 +231,7 @@ SIGNATURES = {
                                                  C.POINTER(Fp64SparseDevice), C.c_double, C.c_int]),
     "resnmtf_fp64_bisil": (C.c_int, [C.c_int, C.POINTER(Fp64BisilJob)]),
     "resnmtf_fp64_bisil_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, _ip]),
+    "resnmtf_fp64_shuffle": (C.c_int, [C.c_int, C.POINTER(Fp64ShuffleJob)]),
     "resnmtf_bisil": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_bisil_sparse": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_bisil_device": (C.c_int, [_h, C.c_int, C.c_int, _dm, _dm, C.c_int, C.c_void_p, C.c_void_p, _dp, C.c_void_p]),

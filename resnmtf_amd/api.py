@@ -34,7 +34,10 @@ Without the opt-ins ``bisil`` stays ``None`` and ``k_val=None`` raises ``NotImpl
 
 Under ``precision="fp64"`` the score is computed in double precision on the numbers that were factorised
 (``res_nmtf_inner(score_bisil=True, fp64_bisil=True)`` -> ``engine.fp64_bisil`` -> ``resnmtf_fp64_bisil``, no handle), and
-``apply_resnmtf(precision="fp64")`` runs a known k or the k sweep on it.
+``apply_resnmtf(precision="fp64")`` runs a known k or the k sweep on it.  Spurious-bicluster
+removal runs there too with the opt-in ``fp64_spurious=True`` (beside ``spurious_on_device=True``): the shuffles are drawn
+from the fp64 values (``engine.fp64_shuffle`` -> ``resnmtf_fp64_shuffle``, no handle) and factorised by the fp64 path
+(``problem.shuffled_fits_fp64``).
 """
 from __future__ import annotations
 
@@ -110,7 +113,8 @@ def res_nmtf_inner(data, row_indices, column_indices,
                    spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False,
                    sparse_on_device: bool = False, output: str = "numpy", init_lm=None, return_state: bool = False,
                    post_on_device: bool = False, precision: str = "f32", fp64_sparse: bool = False,
-                   fp64_device: bool = False, fp64_sparse_device: bool = False, fp64_bisil: bool = False):
+                   fp64_device: bool = False, fp64_sparse_device: bool = False, fp64_bisil: bool = False,
+                   fp64_spurious: bool = False):
     """``res_nmtf_inner`` (``R/main.r:32-140``).
 
     ``data``: list of pre-processed (non-negative, column-normalised) matrices; ``row_indices[v][w]``
@@ -229,7 +233,15 @@ def res_nmtf_inner(data, row_indices, column_indices,
     on the views exactly as the run received them: a host view is uploaded once more for the scoring, a device tensor
     (``fp64_device``) is read where it lies.  The cluster matrices are brought to the host (n k + m k values per view)
     and the score is combined there.  Combines with ``fp64_device`` and ``output="torch"``.  A sparse view with
-    ``score_bisil`` raises a ``NotImplementedError`` naming ``fp64_bisil`` and sparse views.  Without the flag every
+    ``score_bisil`` raises a ``NotImplementedError`` naming ``fp64_bisil`` and sparse views.
+    ``fp64_spurious`` (keyword-only opt-in; a no-op with ``precision="f32"``): with
+    ``precision="fp64"``, ``spurious=True`` and ``spurious_on_device=True`` the removal runs in double precision: after the
+    run, ``check_biclusters(data, F, num_repeats, seed=seed, precision="fp64")`` on the views exactly as the run received
+    them (host arrays or dense device tensors) -- every shuffle drawn by ``engine.fp64_shuffle`` and factorised by the
+    fp64 path (``problem.shuffled_fits_fp64``) --, then the removal, then ``bisil`` of the cleaned clusters (with
+    ``score_bisil`` and ``fp64_bisil``); the result carries ``"spurious"`` and equals ``remove_spurious(data,
+    res_nmtf_inner(..., precision="fp64", spurious=False, seed=seed), num_repeats, seed=seed, precision="fp64")``.  A
+    sparse view with it is refused by name (no fp64 sparse shuffle exists).  Without the flag every
     refusal above stands word for word.
     """
     if precision not in ("f32", "fp64"):
@@ -241,7 +253,8 @@ def res_nmtf_inner(data, row_indices, column_indices,
                                     host_init=host_init, return_init=return_init, score_bisil=score_bisil,
                                     spurious_on_device=spurious_on_device, output=output, init_lm=init_lm,
                                     return_state=return_state, post_on_device=post_on_device, fp64_sparse=fp64_sparse,
-                                    fp64_device=fp64_device, fp64_sparse_device=fp64_sparse_device, fp64_bisil=fp64_bisil)
+                                    fp64_device=fp64_device, fp64_sparse_device=fp64_sparse_device, fp64_bisil=fp64_bisil,
+                                    fp64_spurious=fp64_spurious, num_repeats=num_repeats)
     device_views.check_output(output)
     _check_post_on_device(post_on_device, output)
     data = _views(data, device_id)
@@ -334,19 +347,24 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
                          distance, no_clusts, *, row_names, col_names, device_id, max_iters, seed, engine_opts, host_init,
                          return_init, score_bisil, spurious_on_device, output, init_lm, return_state, post_on_device,
                          fp64_sparse: bool = False, fp64_device: bool = False, fp64_sparse_device: bool = False,
-                         fp64_bisil: bool = False, runner: Optional[Callable] = None, sil: Optional[Callable] = None):
+                         fp64_bisil: bool = False, runner: Optional[Callable] = None, sil: Optional[Callable] = None,
+                         fp64_spurious: bool = False, num_repeats=5, checker: Optional[Callable] = None):
     """``res_nmtf_inner(precision="fp64")``: the checks of the f32 call, the refusals of what needs a live handle, the
     initial state, then one ``engine.fp64_run`` (``runner`` replaces it: a test hook).  ``fp64_device``: views, factors
     and results may live in device memory (``res_nmtf_inner``'s docstring); the runner then also gets ``output`` and
     ``return_state``.  ``fp64_sparse_device``: a sparse tensor on ``cuda:device_id`` reaches the problem as its
     ``SparseDeviceView`` -- the same tensor, untouched.  ``fp64_bisil``: ``score_bisil`` is honoured through
-    ``engine.fp64_bisil`` on the views as they arrived (``sil(v, rc, cc, distance)`` replaces it: a test hook)."""
+    ``engine.fp64_bisil`` on the views as they arrived (``sil(v, rc, cc, distance)`` replaces it: a test hook).
+    ``fp64_spurious``: ``spurious=True`` with ``spurious_on_device`` is honoured through
+    ``spurious.check_biclusters(..., precision="fp64")`` on the views as they arrived (``checker`` replaces it: a test
+    hook), then ``_remove_then_score``."""
     def refuse(flag):
         raise NotImplementedError(f'precision="fp64": {flag} needs a live engine handle, which the fp64 path does not '
                                   'keep (it runs through resnmtf_fp64_run); use precision="f32" for it')
     device_views.check_output(output)
     remove = bool(spurious) and not no_clusts
-    for flag, on in (("spurious_on_device", remove and spurious_on_device), ("score_bisil", score_bisil and not fp64_bisil),
+    for flag, on in (("spurious_on_device", remove and spurious_on_device and not fp64_spurious),
+                     ("score_bisil", score_bisil and not fp64_bisil),
                      ("post_on_device", post_on_device), ('output="torch"', output == "torch" and not fp64_device),
                      ("return_state", return_state and not fp64_device)):
         if on:
@@ -378,6 +396,9 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
         views.append(np.asarray(d, dtype=np.float64))
     data, n_v = views, len(views)
     is_sp = [sparse.is_sparse_view(d) for d in data]
+    if remove:                                    # (here: spurious_on_device and fp64_spurious are set, or the call was refused)
+        _spurious.check_num_repeats(num_repeats)
+        _spurious.refuse_sparse_fp64(data)
     score = bool(score_bisil) and not no_clusts                  # (here: fp64_bisil is set, or the call was refused above)
     if score and any(is_sp):
         raise NotImplementedError(f'precision="fp64": score_bisil with fp64_bisil=True scores dense views only; sparse views '
@@ -453,16 +474,24 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
         return inner_result(out["f"], out["s"], out["g"], init=init_state, state=state)
     clusters = _binary_clusters_device if output == "torch" else batched._binary_clusters
     rcs, ccs = zip(*[clusters(f, g, s) for f, g, s in zip(out["f"], out["g"], out["s"])])
-    score_value = None
+    check = None
+    if remove:                                    # obtain_bicl.r:151-188, on the numbers that were factorised (section 27)
+        check = (checker or _spurious.check_biclusters)(data, out["f"], num_repeats, seed=seed, device_id=device_id,
+                                                        max_iters=max_iters, precision="fp64")
+    score_fn = None
     if score:                                     # obtain_bicl.r:189-199, on the numbers that were factorised (section 26)
         if sil is None:
             def sil(v, rc, cc, distance):
                 return _engine.fp64_bisil(data[v], rc, cc, distance, device_id=device_id)
-        score_value = bisil.score([device_views.to_numpy(rc) for rc in rcs], [device_views.to_numpy(cc) for cc in ccs],
-                                  distance, sil=sil)
-    return inner_result(out["f"], out["s"], out["g"], np.asarray(out["all_error"], dtype=np.float64), n_iters, bisil=score_value,
-                        row_clusters=list(rcs), col_clusters=list(ccs), lam=out["lambda"], mu=out["mu"], init=init_state,
-                        state=state)
+
+        def score_fn(rcs, ccs):
+            return bisil.score([device_views.to_numpy(rc) for rc in rcs], [device_views.to_numpy(cc) for cc in ccs],
+                               distance, sil=sil)
+    cleaned = _remove_then_score({"output_s": out["s"], "row_clusters": list(rcs), "col_clusters": list(ccs)}, check, score_fn,
+                                 on_device=output == "torch")
+    return inner_result(out["f"], out["s"], out["g"], np.asarray(out["all_error"], dtype=np.float64), n_iters,
+                        bisil=cleaned["bisil"], row_clusters=cleaned["row_clusters"], col_clusters=cleaned["col_clusters"],
+                        lam=out["lambda"], mu=out["mu"], spurious=cleaned.get("spurious"), init=init_state, state=state)
 
 
 def _binary_clusters_device(f, g, s):
@@ -681,7 +710,7 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                   spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False,
                   sparse_on_device: bool = False, output: str = "numpy", post_on_device: bool = False,
                   precision: str = "f32", score_bisil: bool = False, fp64_sparse: bool = False, fp64_device: bool = False,
-                  fp64_sparse_device: bool = False, fp64_bisil: bool = False):
+                  fp64_sparse_device: bool = False, fp64_bisil: bool = False, fp64_spurious: bool = False):
     """``apply_resnmtf`` (``R/main.r:214-335``) for a known ``k_val``: naming, shared-name maps, restriction
     symmetrisation, non-negativity shift and column normalisation on the host, then the device loop and -- with
     ``stability=True`` (the default) and ``spurious=False`` -- ``stability_check`` on the pre-processed data, as
@@ -744,7 +773,13 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     ``_sweep`` as above with the cap ``min(ncol, 64)``; ``return_sweep`` and ``sweep_runner`` work as before.  Refused
     with a ``NotImplementedError`` naming the flag: ``stability=True`` (the repeats run on the f32 engine; mixing the two
     precisions is left for later), ``spurious=True``, sparse views in the sweep, and views in device memory (their
-    pre-processing runs at an f32 engine's upload; pass pre-processed tensors to ``res_nmtf_inner``)."""
+    pre-processing runs at an f32 engine's upload; pass pre-processed tensors to ``res_nmtf_inner``).
+    ``fp64_spurious=True`` (keyword-only opt-in; a no-op with ``precision="f32"``) lets
+    ``spurious=True`` run under ``"fp64"`` with ``spurious_on_device=True``: ``res_nmtf_inner(..., spurious=True,
+    spurious_on_device=True, fp64_spurious=True)`` for the ``k_val``, or for every k of the sweep, the extension k's
+    included, each with its own check at seed ``seed + k`` and ranked by the bisilhouette of its cleaned clusters --
+    ``apply_resnmtf(data, precision="fp64", k_sweep=True, stability=False, spurious_on_device=True, fp64_spurious=True)``
+    is the reference's default pipeline minus stability.  A sparse view with it is refused by name."""
     if precision not in ("f32", "fp64"):
         raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
     if precision == "fp64":
@@ -753,7 +788,7 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                            col_names=col_names, device_id=device_id, max_iters=max_iters, seed=seed, k_sweep=k_sweep,
                            return_sweep=return_sweep, sweep_runner=sweep_runner, output=output, score_bisil=score_bisil,
                            fp64_sparse=fp64_sparse, fp64_device=fp64_device, fp64_sparse_device=fp64_sparse_device,
-                           fp64_bisil=fp64_bisil)
+                           fp64_bisil=fp64_bisil, fp64_spurious=fp64_spurious, spurious_on_device=spurious_on_device)
     device_views.check_output(output)
     _check_post_on_device(post_on_device, output)
     on_dev = {"sparse_on_device": True} if sparse_on_device else {}      # (off: every call below is the earlier one)
@@ -802,7 +837,7 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
 def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_min, k_max, distance, spurious, num_repeats,
                 no_clusts, sample_rate, n_stability, stability, stab_thres, *, row_names, col_names, device_id, max_iters,
                 seed, k_sweep, return_sweep, sweep_runner, output, score_bisil, fp64_sparse, fp64_device,
-                fp64_sparse_device, fp64_bisil):
+                fp64_sparse_device, fp64_bisil, fp64_spurious=False, spurious_on_device=False):
     """``apply_resnmtf(precision="fp64")``: the checks of the f32 function, the refusals of what runs on the f32 engine,
     ``prepare``, then ``res_nmtf_inner(precision="fp64")`` -- once for a ``k_val``, or as ``run(k)`` of ``_sweep``."""
     def refuse(flag, why):
@@ -825,13 +860,23 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
             raise ValueError("the k sweep ranks the biclusters by their bisilhouette score: no_clusts=True has none")
     if stability:
         refuse("stability=True", "the stability repeats run on the f32 engine; pass stability=False")
-    if spurious and not no_clusts:
+    remove = bool(spurious) and not no_clusts
+    if remove and not fp64_spurious:
         refuse("spurious=True", "spurious-bicluster removal runs on the f32 engine; pass spurious=False")
+    _refuse_host_spurious(remove, spurious_on_device,
+                          "spurious-bicluster removal (R/obtain_bicl.r:31-133) is outside the accelerated path; "
+                          "pass spurious=False")
+    if remove:
+        _spurious.check_num_repeats(num_repeats)
+        if any(sparse.is_sparse_view(d) for d in data):
+            refuse("a sparse view with fp64_spurious", "no fp64 sparse shuffle exists; pass spurious=False")
     if any(device_views.is_device_view(d) for d in data):
         refuse("a view in device memory", "its shift and column normalisation run at an f32 engine's upload; pass host "
                "arrays, or pre-processed tensors to res_nmtf_inner(precision=\"fp64\", fp64_device=True)")
     flags = {"fp64_sparse": fp64_sparse, "fp64_device": fp64_device, "fp64_sparse_device": fp64_sparse_device}
     common = {"device_id": device_id, "max_iters": max_iters, "output": output, "precision": "fp64", **flags}
+    if remove:                                    # (only then: without the flag every call is the one it was)
+        common.update(spurious_on_device=True, fp64_spurious=True)
     if not sweep:
         k_vec = [int(np.atleast_1d(k_val)[0])] * n_v                                              # main.r:226
         if any(k < 1 for k in k_vec):
@@ -857,7 +902,7 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
     # R/main.r:305-309)
     def run(k):
         return res_nmtf_inner(p.data, p.row_shared, p.col_shared, None, None, None, [k] * n_v, p.phi, p.xi, p.psi, n_iters,
-                              num_repeats, False, distance, False, row_names=p.row_names, col_names=p.col_names,
+                              num_repeats, remove, distance, False, row_names=p.row_names, col_names=p.col_names,
                               seed=seed + k, score_bisil=True, fp64_bisil=True, **common)
 
     ks, scores, results, pick = _sweep(sweep_runner or run, k_min, k_max, cap)

@@ -13,6 +13,10 @@
 // resnmtf_fp64_bisil (section 26), at the end of the file, scores a result in double precision: its kernels are
 // resnmtf_fp64_bisil.hip.inc, its index lists, chunk rule and workspace resnmtf_bisil_plan.h (plain C++, shared with the
 // main unit's resnmtf_bisil), its owner F64BisilRun.
+//
+// resnmtf_fp64_shuffle (section 27), after it, draws shuffle_view of a view in double precision: its kernels are
+// resnmtf_fp64_shuffle.hip.inc, its permutation resnmtf_feistel.h (plain C++, shared with the main unit's shuffles), its
+// struct checks and workspace resnmtf_fp64_shuffle_job.h (plain C++), its owner F64ShuffleRun.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +35,9 @@
 #include "resnmtf_fp64_sparse_device.hip.inc"
 #include "resnmtf_bisil_plan.h"
 #include "resnmtf_fp64_bisil.hip.inc"
+#include "resnmtf_feistel.h"
+#include "resnmtf_fp64_shuffle_job.h"
+#include "resnmtf_fp64_shuffle.hip.inc"
 
 namespace {
 // one sweep of update_matrices (R/update_steps.r:272-319, views in index order) and the error of every view; the mean
@@ -938,6 +945,123 @@ int resnmtf_fp64_bisil_plan(int n_u, int n_mem, int k, long long row_stride, lon
   const int vals[RESNMTF_FP64_BISIL_PLAN_INTS] = {bisil_kq(k), c.chunk_tiles, c.chunks, f64_bisil_side_form(0, row_stride, col_stride),
                                                   f64_bisil_side_form(1, row_stride, col_stride)};
   std::memcpy(out, vals, sizeof(vals));
+  return RESNMTF_OK;
+}
+
+}  // extern "C"
+
+// ---- resnmtf_fp64_shuffle: shuffle_view of R/obtain_bicl.r:11-22 on the fp64 values of X ----
+namespace {
+// What a call holds on the device: its stream, the small workspace and, for a host X, the staging copy.  On every way
+// out the destructor waits for the stream and destroys it, then frees both buffers.
+class F64ShuffleRun {
+ public:
+  F64ShuffleRun() = default;
+  F64ShuffleRun(const F64ShuffleRun&) = delete;
+  F64ShuffleRun& operator=(const F64ShuffleRun&) = delete;
+  ~F64ShuffleRun() {
+    if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+    if (work) (void)hipFree(work);
+    if (staging) (void)hipFree(staging);
+  }
+  int fail(hipError_t e, const char* what = "fp64_shuffle: ") {
+    resnmtf_set_create_error(std::string(what) + hipGetErrorString(e));
+    return RESNMTF_ERR_HIP;
+  }
+  hipStream_t st = nullptr;
+  char* work = nullptr;
+  double* staging = nullptr;
+};
+}  // namespace
+
+extern "C" {
+
+int resnmtf_fp64_shuffle(int device_id, const resnmtf_fp64_shuffle_job* job) {
+  if (const char* why = f64_shuffle_check_job(job)) return fp64_bad(why);
+  const resnmtf_fp64_shuffle_job& j = *job;
+  const int n = j.n, m = j.m;
+  const bool host_x = j.x != nullptr;
+  if (f64_shuffle_bytes_overflow(j)) {        // 8 n m does not fit 64 bits: no device holds the staging copy, or `out`
+    if (!host_x) return fp64_bad("out reaches beyond its allocation (too short for n * m doubles)");
+    resnmtf_set_create_error("fp64_shuffle: more than 9223372036854775808 bytes asked for (the fp64 staging copy of a host X)");
+    return RESNMTF_ERR_ALLOC;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { resnmtf_set_create_error("no HIP device"); return RESNMTF_ERR_NO_DEVICE; }
+  if (device_id < 0 || device_id >= ndev) return fp64_bad("device_id out of range");
+  int host_ints[3] = {0, 0, 0};               // (declared before the run: its destructor waits for the copies into them)
+  std::vector<unsigned char> host_mask;
+  F64ShuffleRun run;
+  hipError_t e = hipSetDevice(device_id);
+  if (e != hipSuccess) return run.fail(e, "hipSetDevice: ");
+  const size_t out_bytes = f64_shuffle_out_bytes(j);
+  const F64ShufflePlan plan = f64_shuffle_plan(n, m);
+  if (host_x) {                               // a shape the device cannot stage is refused on its byte count, x unread
+    size_t free_b = 0, total_b = 0;
+    if ((e = hipMemGetInfo(&free_b, &total_b)) != hipSuccess) return run.fail(e);
+    if (out_bytes > free_b || plan.total > free_b - out_bytes) {
+      resnmtf_set_create_error("fp64_shuffle: " + std::to_string(out_bytes) + " bytes asked for (the fp64 staging copy of a host X), " +
+                               std::to_string(free_b) + " free on the device");
+      return RESNMTF_ERR_ALLOC;
+    }
+  }
+  bool beyond = false;
+  if (!fp64_on_device(device_id, j.out, out_bytes, beyond))
+    return fp64_bad(beyond ? std::string("out reaches beyond its allocation (too short for n * m doubles)")
+                           : "out is not device memory of device " + std::to_string(device_id));
+  resnmtf_device_matrix x = j.x_dev;
+  if (!host_x) {
+    const size_t src_bytes = f64_shuffle_source_bytes(j);
+    if (!fp64_on_device(device_id, x.ptr, src_bytes, beyond))
+      return fp64_bad(beyond ? std::string("x_dev reaches beyond its allocation (too short for the shape and strides given)")
+                             : "x_dev is not device memory of device " + std::to_string(device_id));
+    if (f64_shuffle_overlap(x.ptr, src_bytes, j.out, out_bytes)) return fp64_bad("out overlaps x_dev (the draw reads X while it writes out)");
+  }
+  void* p = nullptr;
+  if ((e = hipMalloc(&p, plan.total)) != hipSuccess) {
+    (void)hipGetLastError();
+    resnmtf_set_create_error(std::string("fp64_shuffle workspace: ") + hipGetErrorString(e) + " (" + std::to_string(plan.total) + " bytes asked for)");
+    return e == hipErrorOutOfMemory ? RESNMTF_ERR_ALLOC : RESNMTF_ERR_HIP;
+  }
+  run.work = static_cast<char*>(p);
+  if (host_x) {
+    if ((e = hipMalloc(&p, out_bytes)) != hipSuccess) {
+      (void)hipGetLastError();
+      resnmtf_set_create_error(std::string("fp64_shuffle: ") + hipGetErrorString(e) + " (" + std::to_string(out_bytes) +
+                               " bytes asked for, the fp64 staging copy of a host X)");
+      return e == hipErrorOutOfMemory ? RESNMTF_ERR_ALLOC : RESNMTF_ERR_HIP;
+    }
+    run.staging = static_cast<double*>(p);
+  }
+  if ((e = hipStreamCreateWithFlags(&run.st, hipStreamNonBlocking)) != hipSuccess) { run.st = nullptr; return run.fail(e, "hipStreamCreate: "); }
+  e = wait_for_caller(run.st, j.stream);      // (a host X too: `out` may still be in use by what the caller enqueued)
+  if (host_x) {                               // one plain n x m fp64 copy; it then goes through the same gather
+    if (e == hipSuccess) e = hipMemcpyAsync(run.staging, j.x, out_bytes, hipMemcpyHostToDevice, run.st);
+    x.ptr = run.staging; x.dtype = RESNMTF_DTYPE_F64; x.row_stride = 1; x.col_stride = n;
+  }
+  double* shift = reinterpret_cast<double*>(run.work + plan.shift);
+  double* colsum = reinterpret_cast<double*>(run.work + plan.colsum);
+  int* ints = reinterpret_cast<int*>(run.work + plan.ints);          // counts[0], counts[1], neg
+  unsigned char* mask = reinterpret_cast<unsigned char*>(run.work + plan.mask);
+  if (e == hipSuccess) e = hipMemsetAsync(ints, 0, 4 * sizeof(int), run.st);
+  if (e == hipSuccess) {
+    fp64_shuffle_gather(run.st, x, n, m, j.seed, j.out);
+    fp64_shuffle_lines(run.st, j.out, n, m, mask, ints);
+    if (j.normalise) fp64_shuffle_normalise(run.st, j.out, n, m, shift, colsum, ints + 2);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(host_ints, ints, sizeof(host_ints), hipMemcpyDeviceToHost, run.st);
+  if (e == hipSuccess && (j.row_mask || j.col_mask)) {
+    host_mask.resize((size_t)n + m);
+    e = hipMemcpyAsync(host_mask.data(), mask, host_mask.size(), hipMemcpyDeviceToHost, run.st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(run.st);
+  if (e != hipSuccess) return run.fail(e);
+  *j.n_empty_rows = host_ints[0];
+  *j.n_empty_cols = host_ints[1];
+  if (j.was_negative) *j.was_negative = j.normalise ? host_ints[2] : 0;
+  if (j.row_mask) std::memcpy(j.row_mask, host_mask.data(), (size_t)n);
+  if (j.col_mask) std::memcpy(j.col_mask, host_mask.data() + n, (size_t)m);
   return RESNMTF_OK;
 }
 

@@ -98,23 +98,9 @@ static __global__ __launch_bounds__(256) void column_stats_kernel(const double* 
 // permutation pi of the n m entries -- a 4-round Feistel network on the next even power of two with
 // cycle walking (a bijection on [0, n m), evaluated independently per element: no sort, no atomics).
 // R draws the permutation from its Mersenne Twister (sample()); neither is reproducible by the other.
+// feistel_perm itself is csrc/resnmtf_feistel.h: one text for this unit, the fp64 unit and the host check.
 // --------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long feistel_perm(unsigned long long i, unsigned long long count, int half_bits,
-                                                           unsigned long long seed) {
-  const unsigned long long mask = (1ull << half_bits) - 1ull;
-  do {
-    unsigned long long l = i >> half_bits, r = i & mask;
-#pragma unroll
-    for (int round = 0; round < 4; ++round) {
-      unsigned long long f = (r + seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(round + 1));
-      f ^= f >> 31; f *= 0xBF58476D1CE4E5B9ull; f ^= f >> 29; f *= 0x94D049BB133111EBull; f ^= f >> 32;
-      const unsigned long long nl = r, nr = (l ^ f) & mask;
-      l = nl; r = nr;
-    }
-    i = (l << half_bits) | r;
-  } while (i >= count);                              // cycle walking: < 4 expected trips
-  return i;
-}
+#include "resnmtf_feistel.h"
 static __global__ __launch_bounds__(256) void shuffle_gather_kernel(const float* __restrict__ X32, size_t tsx, int n, int m,
                                                              unsigned long long seed, double* __restrict__ staging) {
   const unsigned long long count = (unsigned long long)n * m;

@@ -16,25 +16,7 @@
 //   5. sparse_empty_lines_kernel: the redraw condition of shuffle_view (:14-18).
 // No float atomics anywhere; the two counts of empty lines are integer atomics, as in empty_lines_kernel.
 
-// The inverse of feistel_perm (same round constants, same half_bits): the four rounds in reverse order -- a forward round
-// maps (l, r) to (r, (l ^ f(r)) & mask), so r_old = l_new and l_old = (r_new ^ f(l_new)) & mask -- and cycle walking with
-// the inverse until the value is < count (the inverse of a cycle-walked bijection walks the same cycle backwards).
-__device__ __forceinline__ unsigned long long feistel_perm_inverse(unsigned long long j, unsigned long long count, int half_bits,
-                                                                   unsigned long long seed) {
-  const unsigned long long mask = (1ull << half_bits) - 1ull;
-  do {
-    unsigned long long l = j >> half_bits, r = j & mask;
-#pragma unroll
-    for (int round = 3; round >= 0; --round) {
-      unsigned long long f = (l + seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(round + 1));
-      f ^= f >> 31; f *= 0xBF58476D1CE4E5B9ull; f ^= f >> 29; f *= 0x94D049BB133111EBull; f ^= f >> 32;
-      const unsigned long long ol = (r ^ f) & mask, orr = l;
-      l = ol; r = orr;
-    }
-    j = (l << half_bits) | r;
-  } while (j >= count);
-  return j;
-}
+// The inverse of feistel_perm, feistel_perm_inverse, is csrc/resnmtf_feistel.h, beside the permutation itself.
 
 // one thread per stored entry e of the source CSC: its column from cp (the last column whose pointer is <= e), then
 // key[e] = pi^-1(r m + c) and val[e] = (double)vcsc[e]

@@ -415,6 +415,50 @@ def fp64_bisil(x, rc, cc, distance: str = "euclidean", device_id: int = 0):
     return rs, cs
 
 
+def fp64_shuffle(x, seed: int, normalise: bool = True, device_id: int = 0):
+    """``shuffle_view`` (``R/obtain_bicl.r:11-22``) of one view in double precision (``resnmtf_fp64_shuffle``, no handle;
+    DESIGN.md section 27): ``Engine.shuffle_view_from``'s draw for the same ``seed`` -- ``tests/shuffle_ref.shuffle_dense``
+    restates it -- made of the fp64 values of ``x``, where the engine permutes a handle's fp32 image.  Returns ``(tensor,
+    was_negative, empty_rows, empty_cols)``: the draw as an fp64 column-major ``torch`` tensor on ``cuda:device_id``
+    (``normalise``: shifted and column-normalised in fp64 as ``apply_resnmtf`` does to shuffled data, ``R/utils.r:416,422``),
+    whether an entry was negative (False without ``normalise``), and the boolean masks of the rows / columns of the draw
+    that sum to exactly zero before any shift (the redraw condition, ``:14-18``; the caller redraws with another seed).
+    ``x``: a NumPy array or a CPU tensor (copied once to the device as fp64), or a 2-D floating ``torch`` tensor on
+    ``cuda:device_id`` (fp64 / fp32 / fp16 / bf16, any strides, an expanded one included), read where it lies, ordered
+    after the work on torch's current stream of that device (``device_views.as_view``'s checks: ``ValueError``).  Two
+    calls give equal bits.  Bad input is refused before any device work (``ResnmtfError``)."""
+    import torch                    # (lazily: nothing else in this module needs it)
+    lib = _lib.load()
+    x = _device_views.as_view(x, device_id, "fp64_shuffle: x")
+    if _sparse.is_sparse_view(x) or isinstance(x, _device_views.RawDeviceView):
+        raise NotImplementedError("fp64_shuffle draws dense views: a sparse view is not supported")
+    if len(x.shape) != 2:
+        raise ValueError("fp64_shuffle: x must be an n x m matrix")
+    n, m = int(x.shape[0]), int(x.shape[1])
+    if n < 1 or m < 1:
+        raise ValueError("fp64_shuffle: x must have at least one row and one column")
+    dev = torch.device("cuda", int(device_id))
+    out = torch.empty((m, n), dtype=torch.float64, device=dev).t()          # n x m, column-major
+    neg, nr, nc = C.c_int(0), C.c_int(0), C.c_int(0)
+    rm = np.zeros(n, dtype=np.uint8); cm = np.zeros(m, dtype=np.uint8)
+    job = _lib.Fp64ShuffleJob()
+    job.struct_size = C.sizeof(job)
+    job.n, job.m, job.normalise, job.seed = n, m, 1 if normalise else 0, int(seed) & 0xFFFFFFFFFFFFFFFF
+    if _device_views.is_tensor(x):
+        job.x_dev = _device_matrix(x, (n, m), device_id, "fp64_shuffle: x")
+    else:
+        x = _f64_colmajor(x)
+        job.x = _dp(x)
+    job.stream = torch.cuda.current_stream(dev).cuda_stream
+    job.out = out.data_ptr()
+    job.was_negative, job.n_empty_rows, job.n_empty_cols = C.pointer(neg), C.pointer(nr), C.pointer(nc)
+    job.row_mask, job.col_mask = rm.ctypes.data_as(C.POINTER(C.c_ubyte)), cm.ctypes.data_as(C.POINTER(C.c_ubyte))
+    code = lib.resnmtf_fp64_shuffle(int(device_id), C.byref(job))
+    if code != _lib.OK:
+        raise ResnmtfError(code, (lib.resnmtf_last_error(None) or b"").decode())
+    return out, bool(neg.value), rm.astype(bool), cm.astype(bool)
+
+
 def fp64_bisil_plan(n_u: int, n_mem: int, k: int, row_stride: int = 1, col_stride: int = 1) -> dict:
     """How ``fp64_bisil`` launches one side of one bicluster (``resnmtf_fp64_bisil_plan``; no device work): ``{"kq",
     "chunk_tiles", "chunks", "gather": (form of the row side, of the column side)}`` for ``n_u`` points in U, ``n_mem``

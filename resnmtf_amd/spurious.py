@@ -26,7 +26,7 @@ import numpy as np
 
 from . import device_views, sparse
 from .engine import jsd_pairs
-from .problem import shuffled_engines
+from .problem import shuffled_engines, shuffled_fits_fp64
 
 
 # ---------------------------------------------------------------------------------------------
@@ -128,7 +128,7 @@ def _check_factors(mats, what):
 
 def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int] = None, device_id: int = 0,
                      group=None, max_iters: int = 100000, shuffled_f=None, jsd: Optional[Callable] = None,
-                     grouped: bool = False, shuffle_sparse: bool = False) -> dict:
+                     grouped: bool = False, shuffle_sparse: bool = False, precision: str = "f32") -> dict:
     """``check_biclusters`` (``R/obtain_bicl.r:113-133``) with ``get_thresholds`` (``:80-102``): returns
     ``{"score": n_views x K, "avg_threshold": n_views, "max_threshold": n_views}``.
 
@@ -143,7 +143,16 @@ def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int
     default path (the grouped kernel is latency-bound per job): it buys fp64 shuffled fits, not
     speed.  ``shuffle_sparse=True`` (opt-in): ``scipy.sparse`` views are shuffled as sparse views on the device
     (``resnmtf_shuffle_view_sparse``: the dense path's draws of the densified views, DESIGN.md section 10 "Sparse
-    shuffles"); without it they are refused as before, and with ``grouped`` they stay refused."""
+    shuffles"); without it they are refused as before, and with ``grouped`` they stay refused.
+    ``precision="fp64"`` (opt-in): the shuffled F's are ``problem.shuffled_fits_fp64(data, K,
+    num_repeats, seed)`` -- every view drawn in double precision from the view as given (``engine.fp64_shuffle``: a host
+    array, or a dense tensor on ``cuda:device_id`` read where it lies) and factorised by the fp64 path; the scorer, the
+    thresholds and the result are the same.  Sparse views, ``grouped`` and ``group`` are refused with it."""
+    if precision not in ("f32", "fp64"):
+        raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
+    if precision == "fp64":
+        return _check_biclusters_fp64(data, output_f, num_repeats, seed=seed, device_id=device_id, group=group,
+                                      max_iters=max_iters, shuffled_f=shuffled_f, jsd=jsd, grouped=grouped)
     R = check_num_repeats(num_repeats)
     views = list(data) if not (isinstance(data, np.ndarray) and data.ndim == 2) and not sparse.is_sparse(data) else [data]
     if any(sparse.is_sparse(d) for d in views):
@@ -154,18 +163,7 @@ def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int
             raise NotImplementedError("the grouped path takes dense views only; sparse views are shuffled on the device "
                                       "(grouped=False)")
     views = [sparse.canonical_csc(d) if sparse.is_sparse(d) else np.asarray(d, dtype=np.float64) for d in views]
-    output_f = [np.asarray(f, dtype=np.float64) for f in output_f]
-    n_v = len(views)
-    if len(output_f) != n_v:
-        raise ValueError("output_f must hold one F per view")
-    K = output_f[0].shape[1]
-    for i, f in enumerate(output_f):
-        if f.ndim != 2 or f.shape != (views[i].shape[0], K):
-            raise ValueError(f"output_f[{i}] must be {views[i].shape[0]} x {K}")
-        if f.shape[0] < 2:
-            raise ValueError("views need at least 2 rows (bw.nrd0 needs two data points)")
-    _check_null_count(K, R)
-    _check_factors(output_f, "output_f")
+    output_f, K = _checked_output_f([d.shape for d in views], output_f, R)
     if shuffled_f is None:
         from . import batched      # (lazy: batched imports this module at its top for check_on_device and the removal)
         seed = 0 if seed is None else int(seed)
@@ -180,6 +178,57 @@ def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int
             finally:
                 dev.close()
         shuffled_f = [rep["output_f"] for rep in reps]
+    return _score_against_shuffles(output_f, shuffled_f, R, jsd, device_id)
+
+
+def _checked_output_f(shapes, output_f, R: int):
+    """The result's F per view as fp64 arrays (a tensor is downloaded), checked against the views' shapes: (F's, K)."""
+    output_f = [np.asarray(device_views.to_numpy(f), dtype=np.float64) for f in output_f]
+    n_v = len(shapes)
+    if len(output_f) != n_v:
+        raise ValueError("output_f must hold one F per view")
+    K = output_f[0].shape[1]
+    for i, f in enumerate(output_f):
+        if f.ndim != 2 or f.shape != (shapes[i][0], K):
+            raise ValueError(f"output_f[{i}] must be {shapes[i][0]} x {K}")
+        if f.shape[0] < 2:
+            raise ValueError("views need at least 2 rows (bw.nrd0 needs two data points)")
+    _check_null_count(K, R)
+    _check_factors(output_f, "output_f")
+    return output_f, K
+
+
+def _check_biclusters_fp64(data, output_f, num_repeats, *, seed, device_id, group, max_iters, shuffled_f, jsd, grouped) -> dict:
+    """``check_biclusters(precision="fp64")``: the views as the fp64 run received them, the shuffled F's from
+    ``problem.shuffled_fits_fp64``, then the scoring every route shares."""
+    R = check_num_repeats(num_repeats)
+    if grouped or group is not None:
+        raise ValueError('precision="fp64": the shuffled fits run through resnmtf_fp64_run, one after another; grouped and '
+                         'group do not apply')
+    views = ([data] if (isinstance(data, np.ndarray) and data.ndim == 2) or sparse.is_sparse(data) or device_views.is_tensor(data)
+             else list(data))
+    views = [device_views.host_or_device(d, f"view {v}") for v, d in enumerate(views)]
+    refuse_sparse_fp64(views)
+    views = [device_views.as_view(d, device_id, f"view {v}") for v, d in enumerate(views)]
+    if any(isinstance(d, device_views.RawDeviceView) for d in views):
+        raise ValueError('precision="fp64": the views are taken as pre-processed; a RawDeviceView is not')
+    output_f, K = _checked_output_f([tuple(d.shape) for d in views], output_f, R)
+    if shuffled_f is None:
+        shuffled_f = shuffled_fits_fp64(views, K, R, 0 if seed is None else int(seed), max_iters=max_iters, device_id=device_id)
+    return _score_against_shuffles(output_f, shuffled_f, R, jsd, device_id)
+
+
+def refuse_sparse_fp64(views):
+    """``fp64_spurious`` / ``precision="fp64"`` with a sparse view of any kind: refused by name."""
+    for v, d in enumerate(views):
+        if sparse.is_sparse_view(d) or device_views.is_sparse_tensor(d) or isinstance(d, device_views.SparseDeviceView):
+            raise NotImplementedError(f'precision="fp64": spurious-bicluster removal in double precision (fp64_spurious) shuffles '
+                                      f'dense views only; a sparse view (view {v}) is not supported: no fp64 sparse shuffle exists')
+
+
+def _score_against_shuffles(output_f, shuffled_f, R: int, jsd, device_id: int) -> dict:
+    """The scores and thresholds of checked F's against ``shuffled_f`` (``R`` lists of one F per view)."""
+    n_v, K = len(output_f), output_f[0].shape[1]
     if len(shuffled_f) != R or any(len(fs) != n_v for fs in shuffled_f):
         raise ValueError("shuffled_f must hold num_repeats lists of one F per view")
     shuffled_f = [[np.asarray(f, dtype=np.float64) for f in fs] for fs in shuffled_f]
@@ -309,9 +358,14 @@ def remove_spurious(data, results: dict, num_repeats: int = 5, *, grouped: bool 
     results["output_f"], num_repeats, **kwargs)``, view i's cluster columns ``relations`` (``which.max`` of every S
     column) flagged by ``score < max_threshold | score == 0`` are zeroed in ``row_clusters`` and ``col_clusters``.
     Returns a copy (F, S, G unchanged; ``results`` is not modified) with ``"spurious"``: ``check`` plus ``"removed"``,
-    the n_views x K mask of the zeroed cluster columns.  ``grouped`` is passed on to ``check_biclusters``."""
+    the n_views x K mask of the zeroed cluster columns.  ``grouped`` is passed on to ``check_biclusters``, and so is
+    every other keyword -- ``precision="fp64"`` among them (the shuffles drawn and factorised in
+    double precision).  A result whose cluster matrices are tensors (``output="torch"``) is cleaned where it lives
+    (``apply_removal_device``)."""
     if not results.get("row_clusters") or not results.get("col_clusters"):
         raise ValueError("results has no cluster matrices (a no_clusts result): nothing to remove")
-    _check_factors(results["output_s"], "output_s")
+    _check_factors([device_views.to_numpy(s) for s in results["output_s"]], "output_s")
     check = check_biclusters(data, results["output_f"], num_repeats, grouped=grouped, **kwargs)
+    if any(device_views.is_tensor(c) for c in results["row_clusters"]):      # (an output="torch" result: removed where it lives)
+        return apply_removal_device(results, check)
     return apply_removal(results, check)
