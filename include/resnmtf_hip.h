@@ -1114,6 +1114,91 @@ typedef struct resnmtf_fp64_shuffle_job {
 } resnmtf_fp64_shuffle_job;
 int resnmtf_fp64_shuffle(int device_id, const resnmtf_fp64_shuffle_job* job);
 
+/*
+ * The sub-sample of stability_repeat (R/stability_analysis.r:124, :184, :232, :238: data[[i]][row_samples, col_samples])
+ * of one view in DOUBLE precision, without a handle: out[i, j] = X[rows[i], cols[j]] on the fp64
+ * values of X, where resnmtf_subsample_view gathers a handle's fp32 image.  Blocking.
+ *   n, m          the source view is n x m.
+ *   n_sub, m_sub  the sub-sample is n_sub x m_sub, 1 <= n_sub <= n, 1 <= m_sub <= m.
+ *   rows, cols    (host) n_sub / m_sub indices, 0-based, in any order, each at most once: destination row i is source
+ *                 row rows[i], destination column j source column cols[j].
+ *   x             X in host memory: n x m fp64 column-major; copied once into a plain n x m fp64 device array; or NULL.
+ *   x_dev, stream X in device memory: any of the four dtypes, any strides >= 0, read where it lies after an event recorded
+ *                 on `stream` (NULL: the null stream) and widened to fp64 exactly; x_dev.ptr NULL when not given.  X is
+ *                 given in exactly one of the two places.
+ *   out           device memory of device_id owned by the caller: n_sub m_sub doubles, column-major (row stride 1, column
+ *                 stride n_sub); written after the same event, complete when the call returns.  The values are carried
+ *                 over as they are: NOT re-normalised.
+ *   n_empty_rows, n_empty_cols   (host, not NULL) the rows / columns of the sub-sample that sum to exactly 0.0.  One
+ *                 running fp64 sum per line in resnmtf_view_empty_lines' order -- a row: destination columns ascending;
+ *                 a column: destination rows ascending -- so on any data fp32 holds, mixed signs included, the flags
+ *                 are those resnmtf_subsample_view + resnmtf_view_empty_lines report.
+ *   row_mask, col_mask           (host, n_sub and m_sub bytes, or NULL) 1 where a line is empty.
+ * No floating-point atomics: two calls give equal bits (integer atomics for the two counts alone).
+ * Refused before any device work (RESNMTF_ERR_INVALID, text in resnmtf_last_error(NULL)), nothing written: job NULL, a
+ * struct_size mismatch, n or m below 1, n_sub / m_sub outside [1, n] / [1, m], rows / cols NULL, X in both places or in
+ * neither, out NULL, n_empty_rows / n_empty_cols NULL, an unknown dtype, a negative stride, an index out of range or one
+ * that occurs twice (its position named), device_id out of range, x_dev.ptr or out not memory of device_id (or reaching
+ * beyond the allocation the pointer lies in), out overlapping x_dev.  The n m doubles that stage a host X are refused with
+ * RESNMTF_ERR_ALLOC and the byte count when they exceed the free device memory, on the byte count alone.
+ */
+typedef struct resnmtf_fp64_subsample_job {
+  int struct_size;                          /* sizeof the struct */
+  int n, m, n_sub, m_sub;
+  const int *rows, *cols;
+  const double* x;
+  resnmtf_device_matrix x_dev;
+  void* stream;
+  double* out;
+  int *n_empty_rows, *n_empty_cols;
+  unsigned char *row_mask, *col_mask;
+} resnmtf_fp64_subsample_job;
+int resnmtf_fp64_subsample(int device_id, const resnmtf_fp64_subsample_job* job);
+
+/*
+ * How resnmtf_fp64_subsample launches (no device work): for a source with the given strides in elements, out receives
+ * {the gather form (0 = lanes along the destination rows, 1 = the padded LDS tile transpose; a host X has row_stride 1
+ * and col_stride n), the destination rows per workgroup of form 0, the tile edge of form 1, the rows per workgroup of the
+ * row sums, the rows and the columns of the column sums' LDS tile}.
+ * Refused (RESNMTF_ERR_INVALID): out NULL, a negative stride.
+ */
+#define RESNMTF_FP64_SUBSAMPLE_PLAN_INTS 6
+int resnmtf_fp64_subsample_plan(long long row_stride, long long col_stride, int* out);
+
+/*
+ * relevance_results (R/stability_analysis.r:45-67, with jaccard_main :16-33) of cluster matrices that are in device
+ * memory, without a handle: the sub-sample's clusters against the reference clusters gathered
+ * through the sub-sample's index lists.  Blocking.
+ *   n, m, n_sub, m_sub, rows, cols   as in resnmtf_fp64_subsample_job.
+ *   k, k_ref      the clusters of the sub-sample / of the reference, each in [1, 64].
+ *   row_c, col_c  the sub-sample's clusters, n_sub x k and m_sub x k, in device memory: entries 0 / 1 in any of the four
+ *                 dtypes, any strides >= 0 (what resnmtf_fp64_run_device leaves as its row_clusters / col_clusters).
+ *   true_r / true_r_dev, true_c / true_c_dev   the reference's clusters, n x k_ref and m x k_ref: each either a host array
+ *                 of doubles, column-major, or a device matrix (ptr NULL when not given); exactly one of the two.
+ *   stream        the hipStream_t the device matrices' producer ran on (NULL: the null stream).
+ *   relevance     (host) k_ref doubles: relevance[j] = max_i I / U with I = |R_i ^ TR_j| |C_i ^ TC_j| and
+ *                 U = |R_i| |C_i| + |TR_j| |TC_j| - I in int64, one fp64 division, 0 when U = 0.  Decided on the row
+ *                 clusters alone: when exactly one of row_c / true_r has no non-empty column every value is 0, when
+ *                 neither has every value is 1.  (true_r counts as gathered: its rows `rows` alone.)
+ * Integer atomics only: two calls give equal bits.
+ * Refused (RESNMTF_ERR_INVALID, text in resnmtf_last_error(NULL)), relevance not written: job NULL, a struct_size
+ * mismatch, bad extents, k or k_ref outside [1, 64], NULL lists or outputs, a reference in both places or in neither, an
+ * unknown dtype, a negative stride, an index out of range or twice, device_id out of range, a matrix that is not memory of
+ * device_id (or reaches beyond its allocation), and -- found on the device for matrices there -- an entry other than
+ * 0 or 1, the matrix and the lowest offending (row, column) in column-major order named.
+ */
+typedef struct resnmtf_fp64_relevance_job {
+  int struct_size;                          /* sizeof the struct */
+  int n, m, n_sub, m_sub, k, k_ref;
+  resnmtf_device_matrix row_c, col_c;
+  const double *true_r, *true_c;
+  resnmtf_device_matrix true_r_dev, true_c_dev;
+  const int *rows, *cols;
+  void* stream;
+  double* relevance;
+} resnmtf_fp64_relevance_job;
+int resnmtf_fp64_relevance(int device_id, const resnmtf_fp64_relevance_job* job);
+
 /* ---- phase-level entry points (views sharded one-per-GPU; host does the exchange) ---- */
 
 /* Which image of X the streaming passes of view v use after its upload: *uses_2byte = 0 (f32 images), 1 (fp16) or

@@ -173,6 +173,29 @@ class Fp64ShuffleJob(C.Structure):
                 ("row_mask", C.POINTER(C.c_ubyte)), ("col_mask", C.POINTER(C.c_ubyte))]
 
 
+FP64_SUBSAMPLE_PLAN_INTS = 6   # RESNMTF_FP64_SUBSAMPLE_PLAN_INTS
+
+
+class Fp64SubsampleJob(C.Structure):
+    """``resnmtf_fp64_subsample_job`` (include/resnmtf_hip.h): the host index lists, X in host memory (``x``) or in device
+    memory (``x_dev``), the caller's device array ``out`` (n_sub m_sub doubles, written after ``stream``) and the host
+    outputs of ``resnmtf_fp64_subsample``."""
+    _fields_ = [("struct_size", C.c_int), ("n", C.c_int), ("m", C.c_int), ("n_sub", C.c_int), ("m_sub", C.c_int),
+                ("rows", _ip), ("cols", _ip), ("x", _dp), ("x_dev", DeviceMatrix), ("stream", C.c_void_p), ("out", C.c_void_p),
+                ("n_empty_rows", _ip), ("n_empty_cols", _ip),
+                ("row_mask", C.POINTER(C.c_ubyte)), ("col_mask", C.POINTER(C.c_ubyte))]
+
+
+class Fp64RelevanceJob(C.Structure):
+    """``resnmtf_fp64_relevance_job`` (include/resnmtf_hip.h): the sub-sample's cluster matrices in device memory, the
+    reference's in host memory (``true_r`` / ``true_c``) or in device memory (``true_r_dev`` / ``true_c_dev``), the host index
+    lists and the host result of ``resnmtf_fp64_relevance``."""
+    _fields_ = [("struct_size", C.c_int), ("n", C.c_int), ("m", C.c_int), ("n_sub", C.c_int), ("m_sub", C.c_int),
+                ("k", C.c_int), ("k_ref", C.c_int), ("row_c", DeviceMatrix), ("col_c", DeviceMatrix),
+                ("true_r", _dp), ("true_c", _dp), ("true_r_dev", DeviceMatrix), ("true_c_dev", DeviceMatrix),
+                ("rows", _ip), ("cols", _ip), ("stream", C.c_void_p), ("relevance", _dp)]
+
+
 # name -> (restype, argtypes); must list every symbol include/resnmtf_hip.h declares
 SIGNATURES = {
     "resnmtf_abi_version": (C.c_int, []),
@@ -232,6 +255,9 @@ SIGNATURES = {
     "resnmtf_fp64_bisil": (C.c_int, [C.c_int, C.POINTER(Fp64BisilJob)]),
     "resnmtf_fp64_bisil_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, _ip]),
     "resnmtf_fp64_shuffle": (C.c_int, [C.c_int, C.POINTER(Fp64ShuffleJob)]),
+    "resnmtf_fp64_subsample": (C.c_int, [C.c_int, C.POINTER(Fp64SubsampleJob)]),
+    "resnmtf_fp64_subsample_plan": (C.c_int, [C.c_longlong, C.c_longlong, _ip]),
+    "resnmtf_fp64_relevance": (C.c_int, [C.c_int, C.POINTER(Fp64RelevanceJob)]),
     "resnmtf_bisil": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_bisil_sparse": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_bisil_device": (C.c_int, [_h, C.c_int, C.c_int, _dm, _dm, C.c_int, C.c_void_p, C.c_void_p, _dp, C.c_void_p]),

@@ -37,7 +37,10 @@ Under ``precision="fp64"`` the score is computed in double precision on the numb
 ``apply_resnmtf(precision="fp64")`` runs a known k or the k sweep on it.  Spurious-bicluster
 removal runs there too with the opt-in ``fp64_spurious=True`` (beside ``spurious_on_device=True``): the shuffles are drawn
 from the fp64 values (``engine.fp64_shuffle`` -> ``resnmtf_fp64_shuffle``, no handle) and factorised by the fp64 path
-(``problem.shuffled_fits_fp64``).
+(``problem.shuffled_fits_fp64``).  Stability selection runs there with the opt-in
+``fp64_stability=True`` (``stability_check(precision="fp64")``): the sub-samples are gathered from the fp64 values
+(``engine.fp64_subsample`` -> ``resnmtf_fp64_subsample``, no handle), factorised by the fp64 path and scored from the
+cluster tensors it leaves on the device (``engine.fp64_relevance`` -> ``resnmtf_fp64_relevance``).
 """
 from __future__ import annotations
 
@@ -584,7 +587,7 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
                     row_names=None, col_names=None, device_id: int = 0, seed: Optional[int] = None, group=None,
                     max_iters: int = 100000, return_repeats: bool = False, repeat_runner: Optional[Callable] = None,
                     spurious_on_device: bool = False, shuffle_sparse: bool = False, sparse_on_device: bool = False,
-                    output: str = "numpy"):
+                    output: str = "numpy", precision: str = "f32"):
     """``stability_check`` (``R/stability_analysis.r:302-338``): ``n_stability`` factorisations of sub-samples
     (``sample_rate`` of the rows and columns, drawn and trimmed as ``stability_repeat`` does, ``:215-249``), each scored
     against ``results`` by ``relevance_results`` (``:45-67``) -- the gathers, the factorisations and the scoring run on
@@ -614,11 +617,29 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
     from there (``Engine.set_reference_clusters_device``) and are not turned into NumPy unless ``"numpy"`` asks for them;
     anything else is scored from NumPy copies.  The views may be ``torch`` tensors
     on that device, as for ``res_nmtf_inner``.
+
+    ``precision`` (keyword-only; ``"f32"``, the default, is everything above, untouched).  ``"fp64"`` (DESIGN.md section
+    28) runs the repeats in double precision without an f32 handle (``batched.stability_relevance_fp64``): the same draws
+    for the same seed, every sub-sample gathered from the fp64 values of the views (``engine.fp64_subsample``),
+    factorised by ``res_nmtf_inner(precision="fp64")`` and scored from the cluster tensors it leaves on the device
+    (``engine.fp64_relevance``).  ``data``: dense host arrays or dense tensors on ``cuda:device_id``, pre-processed, as
+    ``res_nmtf_inner`` receives them.  ``spurious=True`` with ``spurious_on_device=True`` is the fp64 removal inside every
+    repeat (``fp64_spurious``); ``remove_unstable``, ``return_repeats``, ``repeat_runner`` and ``output`` work as above.
+    A host view is copied to the device once and read there by every repeat.  Refused by name
+    (``NotImplementedError``): a sparse view of any kind, a device tensor still to be shifted and normalised
+    (``RawDeviceView``), ``group``, ``sparse_on_device``, ``shuffle_sparse``.
     """
+    if precision not in ("f32", "fp64"):
+        raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
     device_views.check_output(output)
     if _number_biclusters(results) == 0:                                                          # :308-311
         warnings.warn("No biclusters detected!")
         return results
+    if precision == "fp64":
+        for flag, on in (("group", group is not None), ("sparse_on_device", sparse_on_device), ("shuffle_sparse", shuffle_sparse)):
+            if on:
+                raise NotImplementedError(f'stability_check(precision="fp64"): {flag} is not supported: the fp64 repeats run '
+                                          'one after the other on dense views')
     _refuse_host_spurious(spurious, spurious_on_device,
                           "stability selection with spurious-bicluster removal inside its repeats "
                           "(R/stability_analysis.r:254-266) is outside the accelerated path; pass spurious=False")
@@ -628,6 +649,15 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
         raise ValueError("n_stability must be a positive integer.")
     data = _views(data, device_id)
     n_v = len(data)
+    if precision == "fp64":
+        for v, d in enumerate(data):
+            if isinstance(d, device_views.RawDeviceView):
+                raise NotImplementedError(f'stability_check(precision="fp64"): a device tensor still to be shifted and '
+                                          f'column-normalised (view {v}) is not supported: the route takes pre-processed '
+                                          'dense views')
+            if sparse.is_sparse_view(d) or device_views.is_sparse_device_view(d):
+                raise NotImplementedError(f'stability_check(precision="fp64"): a sparse view (view {v}) is not supported: '
+                                          'resnmtf_fp64_subsample gathers dense views')
     # host copies of the small cluster matrices for the scoring, unless both of a view's are on the engine's device (they
     # are then read in place); `given` keeps the caller's
     given = results
@@ -641,18 +671,26 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
     k = int(np.atleast_1d(k)[0])
     seed = _seed(seed)
     dev = None
-    if repeat_runner is None:
-        row_names, col_names = naming.give_names(data, None, None, row_names, col_names)
-        dev = batched.DeviceData(data, phi, xi, psi, row_names, col_names, device_id=device_id, pre_processed=True)
-    try:
-        stab = batched.stability_relevance_on_device(dev, results, k, int(n_stability), float(sample_rate), n_iters,
-                                                     seed, group, max_iters, keep_clusters=return_repeats,
-                                                     runner=repeat_runner, spurious_repeats=spurious_repeats,
-                                                     shuffle_sparse=shuffle_sparse,
-                                                     **({"sparse_on_device": True} if sparse_on_device else {}))
-    finally:
-        if dev is not None:
-            dev.close()
+    if precision == "fp64":
+        if repeat_runner is None:
+            row_names, col_names = naming.give_names(data, None, None, row_names, col_names)
+        stab = batched.stability_relevance_fp64(data, results, k, int(n_stability), float(sample_rate), n_iters, seed, phi, xi,
+                                                psi, row_names, col_names, max_iters, device_id,
+                                                keep_clusters=return_repeats, spurious_repeats=spurious_repeats,
+                                                runner=repeat_runner)
+    else:
+        if repeat_runner is None:
+            row_names, col_names = naming.give_names(data, None, None, row_names, col_names)
+            dev = batched.DeviceData(data, phi, xi, psi, row_names, col_names, device_id=device_id, pre_processed=True)
+        try:
+            stab = batched.stability_relevance_on_device(dev, results, k, int(n_stability), float(sample_rate), n_iters,
+                                                         seed, group, max_iters, keep_clusters=return_repeats,
+                                                         runner=repeat_runner, spurious_repeats=spurious_repeats,
+                                                         shuffle_sparse=shuffle_sparse,
+                                                         **({"sparse_on_device": True} if sparse_on_device else {}))
+        finally:
+            if dev is not None:
+                dev.close()
     if not stab["stability_performed"]:                                                          # :323-325
         warnings.warn("Unable to perform stability analysis due to sparsity of data.")
         return given
@@ -710,7 +748,8 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                   spurious_on_device: bool = False, bisil_sparse: bool = False, shuffle_sparse: bool = False,
                   sparse_on_device: bool = False, output: str = "numpy", post_on_device: bool = False,
                   precision: str = "f32", score_bisil: bool = False, fp64_sparse: bool = False, fp64_device: bool = False,
-                  fp64_sparse_device: bool = False, fp64_bisil: bool = False, fp64_spurious: bool = False):
+                  fp64_sparse_device: bool = False, fp64_bisil: bool = False, fp64_spurious: bool = False,
+                  fp64_stability: bool = False):
     """``apply_resnmtf`` (``R/main.r:214-335``) for a known ``k_val``: naming, shared-name maps, restriction
     symmetrisation, non-negativity shift and column normalisation on the host, then the device loop and -- with
     ``stability=True`` (the default) and ``spurious=False`` -- ``stability_check`` on the pre-processed data, as
@@ -779,7 +818,14 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     spurious_on_device=True, fp64_spurious=True)`` for the ``k_val``, or for every k of the sweep, the extension k's
     included, each with its own check at seed ``seed + k`` and ranked by the bisilhouette of its cleaned clusters --
     ``apply_resnmtf(data, precision="fp64", k_sweep=True, stability=False, spurious_on_device=True, fp64_spurious=True)``
-    is the reference's default pipeline minus stability.  A sparse view with it is refused by name."""
+    is the reference's default pipeline minus stability.  A sparse view with it is refused by name.
+    ``fp64_stability=True`` (keyword-only opt-in; a no-op with ``precision="f32"``) lets
+    ``stability=True`` run under ``"fp64"``: after the fit, ``stability_check(p.data, ..., precision="fp64")`` on the
+    prepared data -- for a ``k_val`` with ``remove_unstable`` NOT forwarded (``R/main.r:255-262``), after the k sweep's pick
+    with it forwarded (``:324-332``), exactly as the f32 function does; with ``spurious=True`` (which needs
+    ``fp64_spurious`` as above) the removal runs inside every repeat.  A sparse view with it is refused by name.
+    ``apply_resnmtf(data, precision="fp64", k_sweep=True, spurious_on_device=True, fp64_spurious=True,
+    fp64_stability=True)`` is the reference's default pipeline.  Without the flag ``stability=True`` stays refused."""
     if precision not in ("f32", "fp64"):
         raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
     if precision == "fp64":
@@ -788,7 +834,8 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                            col_names=col_names, device_id=device_id, max_iters=max_iters, seed=seed, k_sweep=k_sweep,
                            return_sweep=return_sweep, sweep_runner=sweep_runner, output=output, score_bisil=score_bisil,
                            fp64_sparse=fp64_sparse, fp64_device=fp64_device, fp64_sparse_device=fp64_sparse_device,
-                           fp64_bisil=fp64_bisil, fp64_spurious=fp64_spurious, spurious_on_device=spurious_on_device)
+                           fp64_bisil=fp64_bisil, fp64_spurious=fp64_spurious, spurious_on_device=spurious_on_device,
+                           fp64_stability=fp64_stability, remove_unstable=remove_unstable)
     device_views.check_output(output)
     _check_post_on_device(post_on_device, output)
     on_dev = {"sparse_on_device": True} if sparse_on_device else {}      # (off: every call below is the earlier one)
@@ -837,9 +884,11 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
 def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_min, k_max, distance, spurious, num_repeats,
                 no_clusts, sample_rate, n_stability, stability, stab_thres, *, row_names, col_names, device_id, max_iters,
                 seed, k_sweep, return_sweep, sweep_runner, output, score_bisil, fp64_sparse, fp64_device,
-                fp64_sparse_device, fp64_bisil, fp64_spurious=False, spurious_on_device=False):
+                fp64_sparse_device, fp64_bisil, fp64_spurious=False, spurious_on_device=False, fp64_stability=False,
+                remove_unstable=True):
     """``apply_resnmtf(precision="fp64")``: the checks of the f32 function, the refusals of what runs on the f32 engine,
-    ``prepare``, then ``res_nmtf_inner(precision="fp64")`` -- once for a ``k_val``, or as ``run(k)`` of ``_sweep``."""
+    ``prepare``, then ``res_nmtf_inner(precision="fp64")`` -- once for a ``k_val``, or as ``run(k)`` of ``_sweep`` --, then
+    with ``stability`` and ``fp64_stability`` ``stability_check(precision="fp64")`` on the prepared data."""
     def refuse(flag, why):
         raise NotImplementedError(f'apply_resnmtf(precision="fp64"): {flag} is not supported: {why}')
     device_views.check_output(output)
@@ -858,8 +907,10 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
         k_min, k_max = int(k_min), int(k_max)
         if no_clusts:
             raise ValueError("the k sweep ranks the biclusters by their bisilhouette score: no_clusts=True has none")
-    if stability:
+    if stability and not fp64_stability:
         refuse("stability=True", "the stability repeats run on the f32 engine; pass stability=False")
+    if stability and any(sparse.is_sparse_view(d) or device_views.is_sparse_device_view(d) for d in data):
+        refuse("a sparse view with fp64_stability", "resnmtf_fp64_subsample gathers dense views; pass stability=False")
     remove = bool(spurious) and not no_clusts
     if remove and not fp64_spurious:
         refuse("spurious=True", "spurious-bicluster removal runs on the f32 engine; pass spurious=False")
@@ -877,6 +928,10 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
     common = {"device_id": device_id, "max_iters": max_iters, "output": output, "precision": "fp64", **flags}
     if remove:                                    # (only then: without the flag every call is the one it was)
         common.update(spurious_on_device=True, fp64_spurious=True)
+
+    def stab_kw(p):                               # the keywords of stability_check(precision="fp64") on the prepared data
+        return {"row_names": p.row_names, "col_names": p.col_names, "device_id": device_id, "seed": seed, "max_iters": max_iters,
+                "spurious_on_device": spurious_on_device, "output": output, "precision": "fp64"}
     if not sweep:
         k_vec = [int(np.atleast_1d(k_val)[0])] * n_v                                              # main.r:226
         if any(k < 1 for k in k_vec):
@@ -884,9 +939,13 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
         if any(k > d.shape[1] for k, d in zip(k_vec, data)):
             raise ValueError("k_vec must be a vector of integers less than or equal to the ranks of the views.")
         p = prepare(data, phi, xi, psi, row_names, col_names, normalise=True, symmetrise=True)    # main.r:228-237
-        return res_nmtf_inner(p.data, p.row_shared, p.col_shared, init_f, init_s, init_g, k_vec, p.phi, p.xi, p.psi, n_iters,
-                              num_repeats, spurious, distance, no_clusts, row_names=p.row_names, col_names=p.col_names,
-                              seed=seed, score_bisil=score_bisil, fp64_bisil=fp64_bisil, **common)
+        results = res_nmtf_inner(p.data, p.row_shared, p.col_shared, init_f, init_s, init_g, k_vec, p.phi, p.xi, p.psi, n_iters,
+                                 num_repeats, spurious, distance, no_clusts, row_names=p.row_names, col_names=p.col_names,
+                                 seed=seed, score_bisil=score_bisil, fp64_bisil=fp64_bisil, **common)
+        if stability:                                                                             # main.r:255-262
+            results = stability_check(p.data, results, k_vec, p.phi, p.xi, p.psi, n_iters, spurious, num_repeats, no_clusts,
+                                      distance, sample_rate, n_stability, stab_thres, **stab_kw(p))
+        return results
     if any(sparse.is_sparse_view(d) for d in data):
         refuse("a sparse view in the k sweep", "resnmtf_fp64_bisil scores dense views only; pass k_val (with fp64_sparse=True)")
     if init_f is not None or init_s is not None or init_g is not None:
@@ -907,6 +966,9 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
 
     ks, scores, results, pick = _sweep(sweep_runner or run, k_min, k_max, cap)
     results = results[pick]                                                                       # main.r:313-314
+    if stability:                                                                                 # main.r:324-332
+        results = stability_check(p.data, results, [ks[pick]] * n_v, p.phi, p.xi, p.psi, n_iters, spurious, num_repeats,
+                                  no_clusts, distance, sample_rate, n_stability, stab_thres, remove_unstable, **stab_kw(p))
     if return_sweep:
         results = dict(results)
         results["k_sweep"] = {"k": ks, "bisil": scores}

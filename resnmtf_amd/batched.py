@@ -9,7 +9,9 @@ over the ranks of a ``torch.distributed`` process group when there is one (one p
 collective in the data path; the results are gathered as Python objects at the end).
 
 Stability selection is scored here too: ``stability_relevance_on_device`` runs the repeats of ``stability_check``
-and reduces each sub-sample's factorisation to its relevance values on the device (``resnmtf_relevance``).  What is
+and reduces each sub-sample's factorisation to its relevance values on the device (``resnmtf_relevance``);
+``stability_relevance_fp64`` does the same in double precision without a handle (``resnmtf_fp64_subsample``, the fp64
+run, ``resnmtf_fp64_relevance``), over the same draws and the same trimming loop.  What is
 NOT here: the other scores computed from the factorisations -- the bisilhouette (``bisil.py``, scored on
 ``DeviceData.base`` by the k sweep of ``api.apply_resnmtf``) and the JSD scores (``spurious.py``).
 
@@ -34,8 +36,8 @@ from . import device_views, naming, sparse, spurious
 from . import engine as _engine
 from ._lib import GROUP_MAX_K, GROUP_MAX_VIEW_ENTRIES, GROUP_MAX_VIEWS, MAX_K
 from .engine import Engine, group_run
-from .problem import (inner_result, load_child, pair_table, prepare, reported_error,  # noqa: F401  (shuffled_engines:
-                      shuffled_engines, svd_init)                                     # part of this module's surface)
+from .problem import (fit_fp64_on_device, inner_result, load_child, pair_table, prepare,  # noqa: F401  (shuffled_engines:
+                      reported_error, shuffled_engines, svd_init)                         # part of this module's surface)
 
 
 @dataclass
@@ -384,39 +386,22 @@ class DeviceData:
         (``Engine.subsample_count_sparse``), a sparse probe of that capacity, ``subsample_view_sparse_from``.  Returns the
         trimmed draws or ``None``.  ``counts``: a dict of the caller's that receives, per sparse view probed on the
         device, ``(rows, cols, stored entries)`` of its last probe (``child`` sizes its engine from them)."""
-        n_v = len(self.data_shapes)
-        rows = [np.asarray(r).copy() for r in samples[0]]; cols = [np.asarray(c).copy() for c in samples[1]]
-        for _ in range(max_rounds):
-            changed = False
-            for i in range(n_v):
-                if len(rows[i]) < 2 or len(cols[i]) < 2:
-                    return None
-                if self.sp[i] is not None and (sparse_on_device or self._sp_device(i)):
-                    count = self.base.subsample_count_sparse(i, rows[i], cols[i])
-                    if counts is not None:
-                        counts[i] = (rows[i], cols[i], count)
-                    with Engine([len(rows[i])], [len(cols[i])], [2], device_id=self.device_id, nnz=[count]) as probe:
-                        probe.subsample_view_sparse_from(0, self.base, i, rows[i], cols[i])
-                        er, ec = probe.empty_lines(0)
-                elif self.sp[i] is not None:        # sparse view: the sub-sample is gathered on the host
-                    _, er, ec = sparse.subsample(self.sp[i], rows[i], cols[i])
-                else:
-                    with Engine([len(rows[i])], [len(cols[i])], [2], device_id=self.device_id) as probe:
-                        probe.subsample_view_from(0, self.base, i, rows[i], cols[i])
-                        er, ec = probe.empty_lines(0)
-                if er.any() or ec.any():
-                    changed = True
-                    same_r = self.data_shapes[i][0] == self.data_shapes[0][0]
-                    same_c = self.data_shapes[i][1] == self.data_shapes[0][1]
-                    for p in (range(i + 1) if same_r else [i]):            # :168-174
-                        if len(rows[p]) == len(er):
-                            rows[p] = rows[p][~er]
-                    for p in (range(i + 1) if same_c else [i]):            # :175-181
-                        if len(cols[p]) == len(ec):
-                            cols[p] = cols[p][~ec]
-            if not changed:
-                return rows, cols
-        return None
+        def probe_view(i, rows_i, cols_i):
+            if self.sp[i] is not None and (sparse_on_device or self._sp_device(i)):
+                count = self.base.subsample_count_sparse(i, rows_i, cols_i)
+                if counts is not None:
+                    counts[i] = (rows_i, cols_i, count)
+                with Engine([len(rows_i)], [len(cols_i)], [2], device_id=self.device_id, nnz=[count]) as probe:
+                    probe.subsample_view_sparse_from(0, self.base, i, rows_i, cols_i)
+                    return probe.empty_lines(0)
+            if self.sp[i] is not None:              # sparse view: the sub-sample is gathered on the host
+                _, er, ec = sparse.subsample(self.sp[i], rows_i, cols_i)
+                return er, ec
+            with Engine([len(rows_i)], [len(cols_i)], [2], device_id=self.device_id) as probe:
+                probe.subsample_view_from(0, self.base, i, rows_i, cols_i)
+                return probe.empty_lines(0)
+
+        return trim_samples(self.data_shapes, samples, probe_view, max_rounds)
 
     def _subsample_count(self, v: int, rows, cols, counts: dict) -> int:
         """The stored entries of the sub-sample of sparse view ``v``: the count ``_trim_samples`` left in ``counts`` for
@@ -639,6 +624,36 @@ def stability_draws(shapes, n_stability: int, sample_rate: float, seed: int = 0)
     return draws
 
 
+def trim_samples(shapes, samples, probe: Callable, max_rounds: int = 20):
+    """``sample_view`` / ``stability_repeat`` (``R/stability_analysis.r:165-190``, ``:233-240``): all-zero rows and
+    columns of a sub-sample are dropped -- from every earlier view that shares the draw (equal extent along that axis)
+    -- and the sub-samples probed again, until none is left.  ``probe(i, rows, cols)`` returns the boolean masks
+    ``(empty_rows, empty_cols)`` of view i's sub-sample at these lists; which route answers it is the caller's (the f32
+    engine's probes: ``DeviceData._trim_samples``; ``engine.fp64_subsample``: ``stability_relevance_fp64``).  Returns the
+    trimmed ``(rows, cols)`` or ``None`` (a sub-sample below 2 x 2, or no fixed point after ``max_rounds``)."""
+    n_v = len(shapes)
+    rows = [np.asarray(r).copy() for r in samples[0]]; cols = [np.asarray(c).copy() for c in samples[1]]
+    for _ in range(max_rounds):
+        changed = False
+        for i in range(n_v):
+            if len(rows[i]) < 2 or len(cols[i]) < 2:
+                return None
+            er, ec = probe(i, rows[i], cols[i])
+            if er.any() or ec.any():
+                changed = True
+                same_r = shapes[i][0] == shapes[0][0]
+                same_c = shapes[i][1] == shapes[0][1]
+                for p in (range(i + 1) if same_r else [i]):            # :168-174
+                    if len(rows[p]) == len(er):
+                        rows[p] = rows[p][~er]
+                for p in (range(i + 1) if same_c else [i]):            # :175-181
+                    if len(cols[p]) == len(ec):
+                        cols[p] = cols[p][~ec]
+        if not changed:
+            return rows, cols
+    return None
+
+
 def mean_relevance(repeats: Sequence[dict], n_stability: int) -> Optional[np.ndarray]:
     """``stability_check``'s reduction (``R/stability_analysis.r:315-327``): the repeats' n_views x k relevance
     matrices summed on the host in repeat order, then divided by ``n_stability`` -- the same additions in the same
@@ -688,5 +703,81 @@ def stability_relevance_on_device(dev: Optional[DeviceData], results: dict, k: i
                                         keep_clusters=keep_clusters, spurious_repeats=spurious_repeats,
                                         spurious_seed=seed + 2000 + r, shuffle_sparse=shuffle_sparse, **more)
     repeats = run_jobs(list(range(n_stability)), group=group, runner=runner)
+    rel = mean_relevance(repeats, n_stability)
+    return {"stability_performed": rel is not None, "relevance": rel, "repeats": repeats}
+
+
+def stability_repeat_fp64(data, results, k: int, n_iters, seed: int, samples, phi, xi, psi, row_names, col_names,
+                          max_iters: int = 100000, device_id: int = 0, tag: str = "", keep_clusters: bool = False,
+                          spurious_repeats: int = 0, return_init: bool = False) -> dict:
+    """One repeat of ``stability_check`` (``R/stability_analysis.r:215-278``) in double precision:
+    the draws ``samples`` trimmed (``trim_samples`` with ``engine.fp64_subsample`` as the probe), every view's sub-sample
+    an fp64 tensor on the device (``resnmtf_fp64_subsample``: the fp64 values, not re-normalised, names carried over; the
+    tensor of the view's last probe, whose lists are the trimmed ones, is the one factorised: one gather per view when
+    nothing is trimmed), factorised by ``res_nmtf_inner(precision="fp64", fp64_device=True, output="torch")`` at ``seed`` --
+    with ``spurious_repeats`` = R >= 2 its spurious biclusters removed there (``fp64_spurious``, spurious seed ``seed``) --
+    and the cluster tensors it leaves scored against ``results``' clusters (``engine.fp64_relevance``; tensors on the
+    device are read in place).  Returns ``DeviceData.stability_repeat``'s dict, or ``{"stability_performed": False,
+    "tag"}`` when the trimming fails.  ``keep_clusters`` adds the sub-sample's (cleaned) clusters as NumPy arrays,
+    ``return_init`` the start of the factorisation (test hooks)."""
+    n_v = len(data)
+    shapes = [tuple(int(s) for s in d.shape) for d in data]
+    last = {}                                     # per view: the lists and the tensor of its latest probe (one alive per view)
+
+    def probe(i, rows_i, cols_i):
+        t, er, ec = _engine.fp64_subsample(data[i], rows_i, cols_i, device_id)
+        last[i] = (rows_i, cols_i, t)
+        return er, ec
+    trimmed = trim_samples(shapes, samples, probe)
+    if trimmed is None:
+        return {"stability_performed": False, "tag": tag}
+    rows, cols = trimmed
+    # trim_samples ends with a round in which every view was probed and nothing changed: each view's latest probe had
+    # the final lists, so its tensor is the sub-sample to factorise and nothing is gathered twice
+    assert all(np.array_equal(last[v][0], rows[v]) and np.array_equal(last[v][1], cols[v]) for v in range(n_v))
+    subs = [last[v][2] for v in range(n_v)]
+    last.clear()
+    rn = [[row_names[v][t] for t in rows[v]] for v in range(n_v)]
+    cn = [[col_names[v][t] for t in cols[v]] for v in range(n_v)]
+    more = {"return_init": True} if return_init else {}
+    if spurious_repeats:
+        more.update(spurious_on_device=True, fp64_spurious=True)
+    res = fit_fp64_on_device(subs, k, phi, xi, psi, n_iters, spurious_repeats if spurious_repeats else 5, bool(spurious_repeats),
+                             row_names=rn, col_names=cn, device_id=device_id, max_iters=max_iters, seed=seed, **more)
+    del subs
+    rel = [_engine.fp64_relevance(res["row_clusters"][v], res["col_clusters"][v], results["row_clusters"][v],
+                                  results["col_clusters"][v], rows[v], cols[v], device_id) for v in range(n_v)]
+    out = {"stability_performed": True, "relevance": np.stack(rel), "Error": res["Error"], "All_Error": res["All_Error"],
+           "tag": tag, "extras": {"row_samples": rows, "col_samples": cols}}
+    if keep_clusters:
+        out["row_clusters"] = [device_views.to_numpy(t) for t in res["row_clusters"]]
+        out["col_clusters"] = [device_views.to_numpy(t) for t in res["col_clusters"]]
+    if return_init:
+        out["init"] = res["init"]
+    return out
+
+
+def stability_relevance_fp64(data, results: dict, k: int, n_stability: int, sample_rate: float, n_iters, seed: int, phi, xi,
+                             psi, row_names, col_names, max_iters: int = 100000, device_id: int = 0,
+                             keep_clusters: bool = False, spurious_repeats: int = 0, runner: Optional[Callable] = None) -> dict:
+    """``stability_relevance_on_device`` in double precision: the repeats of ``stability_check``
+    without an f32 handle.  ``data``: the pre-processed dense views, host arrays or tensors on ``cuda:device_id``.  The
+    draws are ``stability_draws(shapes, n_stability, sample_rate, seed)`` -- the f32 route's for the same seed --, repeat
+    r is ``stability_repeat_fp64`` at the seed ``seed + 2000 + r`` (with ``spurious_repeats`` also its spurious seed, the
+    f32 route's convention), one after the other (no process group), and the reduction is ``mean_relevance``.
+    ``runner(r)`` replaces the repeat (the CPU tests inject a stand-in; nothing then touches the device).  Returns
+    ``{"stability_performed", "relevance" (None when not performed), "repeats"}``.  A host view is copied to the device
+    once, as an fp64 tensor (``engine.fp64_device_view``), and every probe and gather of every repeat reads that copy in
+    place -- one source copy per view, as ``DeviceData`` keeps one; a tensor already there is read where it lies."""
+    if runner is None:
+        shapes = [tuple(int(s) for s in d.shape) for d in data]
+        draws = stability_draws(shapes, n_stability, sample_rate, seed)
+        sources = [_engine.fp64_device_view(d, device_id) for d in data]
+
+        def runner(r):
+            return stability_repeat_fp64(sources, results, k, n_iters, seed + 2000 + r, draws[r], phi, xi, psi, row_names,
+                                         col_names, max_iters=max_iters, device_id=device_id, tag=f"stability={r}",
+                                         keep_clusters=keep_clusters, spurious_repeats=spurious_repeats)
+    repeats = [runner(r) for r in range(n_stability)]
     rel = mean_relevance(repeats, n_stability)
     return {"stability_performed": rel is not None, "relevance": rel, "repeats": repeats}

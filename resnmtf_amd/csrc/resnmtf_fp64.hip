@@ -16,7 +16,13 @@
 //
 // resnmtf_fp64_shuffle (section 27), after it, draws shuffle_view of a view in double precision: its kernels are
 // resnmtf_fp64_shuffle.hip.inc, its permutation resnmtf_feistel.h (plain C++, shared with the main unit's shuffles), its
-// struct checks and workspace resnmtf_fp64_shuffle_job.h (plain C++), its owner F64ShuffleRun.
+// struct checks and workspace resnmtf_fp64_shuffle_job.h (plain C++), its owner F64CallRun.
+//
+// resnmtf_fp64_subsample and resnmtf_fp64_relevance (section 28), last, are what a stability repeat needs around a
+// factorisation in double precision: the sub-sample of a view with its empty lines (resnmtf_fp64_subsample.hip.inc) and
+// the relevance of cluster matrices in device memory (resnmtf_fp64_relevance.hip.inc); their struct checks, index-list
+// checks, form chooser and workspaces are resnmtf_fp64_subsample_job.h (plain C++).  The three handle-free entries share
+// one owner of a call's stream and buffers, F64CallRun, and one header of pointer / extent helpers, resnmtf_fp64_extent.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,6 +44,9 @@
 #include "resnmtf_feistel.h"
 #include "resnmtf_fp64_shuffle_job.h"
 #include "resnmtf_fp64_shuffle.hip.inc"
+#include "resnmtf_fp64_subsample_job.h"
+#include "resnmtf_fp64_subsample.hip.inc"
+#include "resnmtf_fp64_relevance.hip.inc"
 
 namespace {
 // one sweep of update_matrices (R/update_steps.r:272-319, views in index order) and the error of every view; the mean
@@ -952,25 +961,39 @@ int resnmtf_fp64_bisil_plan(int n_u, int n_mem, int k, long long row_stride, lon
 
 // ---- resnmtf_fp64_shuffle: shuffle_view of R/obtain_bicl.r:11-22 on the fp64 values of X ----
 namespace {
-// What a call holds on the device: its stream, the small workspace and, for a host X, the staging copy.  On every way
-// out the destructor waits for the stream and destroys it, then frees both buffers.
-class F64ShuffleRun {
+// What a call of a handle-free entry (resnmtf_fp64_shuffle, and section 28's resnmtf_fp64_subsample and
+// resnmtf_fp64_relevance) holds on the device: its stream, the small workspace and, for a host X, the staging copy.  On
+// every way out the destructor waits for the stream and destroys it, then frees both buffers.  `name` heads its errors.
+class F64CallRun {
  public:
-  F64ShuffleRun() = default;
-  F64ShuffleRun(const F64ShuffleRun&) = delete;
-  F64ShuffleRun& operator=(const F64ShuffleRun&) = delete;
-  ~F64ShuffleRun() {
+  explicit F64CallRun(const char* name) : name_(name) {}
+  F64CallRun(const F64CallRun&) = delete;
+  F64CallRun& operator=(const F64CallRun&) = delete;
+  ~F64CallRun() {
     if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
     if (work) (void)hipFree(work);
     if (staging) (void)hipFree(staging);
   }
-  int fail(hipError_t e, const char* what = "fp64_shuffle: ") {
-    resnmtf_set_create_error(std::string(what) + hipGetErrorString(e));
+  // the HIP error as text, after `what` (the call that failed) or, without it, after the entry's name
+  int fail(hipError_t e, const char* what = nullptr) {
+    resnmtf_set_create_error((what ? std::string(what) : std::string(name_) + ": ") + hipGetErrorString(e));
     return RESNMTF_ERR_HIP;
+  }
+  // a buffer of `bytes`; a refusal names what it was for
+  int alloc(void** p, size_t bytes, const char* what) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) return RESNMTF_OK;
+    (void)hipGetLastError();
+    *p = nullptr;
+    resnmtf_set_create_error(std::string(name_) + ": " + hipGetErrorString(e) + " (" + std::to_string(bytes) + " bytes asked for, " + what + ")");
+    return e == hipErrorOutOfMemory ? RESNMTF_ERR_ALLOC : RESNMTF_ERR_HIP;
   }
   hipStream_t st = nullptr;
   char* work = nullptr;
   double* staging = nullptr;
+
+ private:
+  const char* name_;
 };
 }  // namespace
 
@@ -991,7 +1014,7 @@ int resnmtf_fp64_shuffle(int device_id, const resnmtf_fp64_shuffle_job* job) {
   if (device_id < 0 || device_id >= ndev) return fp64_bad("device_id out of range");
   int host_ints[3] = {0, 0, 0};               // (declared before the run: its destructor waits for the copies into them)
   std::vector<unsigned char> host_mask;
-  F64ShuffleRun run;
+  F64CallRun run("fp64_shuffle");
   hipError_t e = hipSetDevice(device_id);
   if (e != hipSuccess) return run.fail(e, "hipSetDevice: ");
   const size_t out_bytes = f64_shuffle_out_bytes(j);
@@ -1062,6 +1085,188 @@ int resnmtf_fp64_shuffle(int device_id, const resnmtf_fp64_shuffle_job* job) {
   if (j.was_negative) *j.was_negative = j.normalise ? host_ints[2] : 0;
   if (j.row_mask) std::memcpy(j.row_mask, host_mask.data(), (size_t)n);
   if (j.col_mask) std::memcpy(j.col_mask, host_mask.data() + n, (size_t)m);
+  return RESNMTF_OK;
+}
+
+}  // extern "C"
+
+// ---- resnmtf_fp64_subsample, resnmtf_fp64_relevance: a stability repeat's gather and scoring ----
+// (the owner of a call's stream, workspace and staging copy is F64CallRun, above)
+namespace {
+// device_id names a device; RESNMTF_OK or the refusal
+int fp64_check_device_id(int device_id) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { resnmtf_set_create_error("no HIP device"); return RESNMTF_ERR_NO_DEVICE; }
+  if (device_id < 0 || device_id >= ndev) return fp64_bad("device_id out of range");
+  return RESNMTF_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int resnmtf_fp64_subsample_plan(long long row_stride, long long col_stride, int* out) {
+  if (!out) return fp64_bad("out is NULL");
+  if (row_stride < 0 || col_stride < 0) return fp64_bad("strides must be >= 0");
+  const int vals[RESNMTF_FP64_SUBSAMPLE_PLAN_INTS] = {f64_subsample_form(row_stride, col_stride), F64_SUB_BLOCK, F64_SUB_TILE,
+                                                      F64_SUB_ROWSUM_BLOCK, F64_SUB_COLSUM_ROWS, F64_SUB_COLSUM_COLS};
+  std::memcpy(out, vals, sizeof(vals));
+  return RESNMTF_OK;
+}
+
+int resnmtf_fp64_subsample(int device_id, const resnmtf_fp64_subsample_job* job) {
+  if (const char* why = f64_subsample_check_job(job)) return fp64_bad(why);
+  const resnmtf_fp64_subsample_job& j = *job;
+  const int n = j.n, m = j.m, ns = j.n_sub, ms = j.m_sub;
+  const bool host_x = j.x != nullptr;
+  {
+    std::string why = f64_subsample_check_indices("rows", j.rows, ns, n);
+    if (why.empty()) why = f64_subsample_check_indices("cols", j.cols, ms, m);
+    if (!why.empty()) return fp64_bad(why);
+  }
+  if (host_x && f64_array_bytes_overflow(n, m)) {      // 8 n m does not fit 64 bits: no device holds the staging copy
+    resnmtf_set_create_error("fp64_subsample: more than 9223372036854775808 bytes asked for (the fp64 staging copy of a host X)");
+    return RESNMTF_ERR_ALLOC;
+  }
+  if (f64_array_bytes_overflow(ns, ms)) return fp64_bad("out reaches beyond its allocation (too short for n_sub * m_sub doubles)");
+  if (int rc = fp64_check_device_id(device_id)) return rc;
+  int host_ints[2] = {0, 0};                 // (declared before the run: its destructor waits for the copies into them)
+  std::vector<unsigned char> host_mask;
+  F64CallRun run("fp64_subsample");
+  hipError_t e = hipSetDevice(device_id);
+  if (e != hipSuccess) return run.fail(e, "hipSetDevice: ");
+  const size_t out_bytes = f64_array_bytes(ns, ms), stage_bytes = f64_array_bytes(n, m);
+  const F64SubsamplePlan plan = f64_subsample_plan(ns, ms);
+  if (host_x) {                               // a shape the device cannot stage is refused on its byte count, x unread
+    size_t free_b = 0, total_b = 0;
+    if ((e = hipMemGetInfo(&free_b, &total_b)) != hipSuccess) return run.fail(e);
+    if (stage_bytes > free_b || plan.total > free_b - stage_bytes) {
+      resnmtf_set_create_error("fp64_subsample: " + std::to_string(stage_bytes) + " bytes asked for (the fp64 staging copy of a host X), " +
+                               std::to_string(free_b) + " free on the device");
+      return RESNMTF_ERR_ALLOC;
+    }
+  }
+  bool beyond = false;
+  if (!fp64_on_device(device_id, j.out, out_bytes, beyond))
+    return fp64_bad(beyond ? std::string("out reaches beyond its allocation (too short for n_sub * m_sub doubles)")
+                           : "out is not device memory of device " + std::to_string(device_id));
+  resnmtf_device_matrix x = j.x_dev;
+  if (!host_x) {
+    const size_t src_bytes = f64_matrix_bytes(x, n, m);
+    if (!fp64_on_device(device_id, x.ptr, src_bytes, beyond))
+      return fp64_bad(beyond ? std::string("x_dev reaches beyond its allocation (too short for the shape and strides given)")
+                             : "x_dev is not device memory of device " + std::to_string(device_id));
+    if (f64_ranges_overlap(x.ptr, src_bytes, j.out, out_bytes)) return fp64_bad("out overlaps x_dev (the gather reads X while it writes out)");
+  }
+  void* p = nullptr;
+  if (int rc = run.alloc(&p, plan.total, "the workspace")) return rc;
+  run.work = static_cast<char*>(p);
+  if (host_x) {
+    if (int rc = run.alloc(&p, stage_bytes, "the fp64 staging copy of a host X")) return rc;
+    run.staging = static_cast<double*>(p);
+  }
+  if ((e = hipStreamCreateWithFlags(&run.st, hipStreamNonBlocking)) != hipSuccess) { run.st = nullptr; return run.fail(e, "hipStreamCreate: "); }
+  e = wait_for_caller(run.st, j.stream);      // (a host X too: `out` may still be in use by what the caller enqueued)
+  if (host_x) {                               // one plain n x m fp64 copy; it then goes through the same gather
+    if (e == hipSuccess) e = hipMemcpyAsync(run.staging, j.x, stage_bytes, hipMemcpyHostToDevice, run.st);
+    x.ptr = run.staging; x.dtype = RESNMTF_DTYPE_F64; x.row_stride = 1; x.col_stride = n;
+  }
+  int* ints = reinterpret_cast<int*>(run.work + plan.ints);            // counts[0], counts[1]
+  int* rows = reinterpret_cast<int*>(run.work + plan.rows);
+  int* cols = reinterpret_cast<int*>(run.work + plan.cols);
+  unsigned char* mask = reinterpret_cast<unsigned char*>(run.work + plan.mask);
+  if (e == hipSuccess) e = hipMemsetAsync(ints, 0, 4 * sizeof(int), run.st);
+  if (e == hipSuccess) e = hipMemcpyAsync(rows, j.rows, (size_t)ns * sizeof(int), hipMemcpyHostToDevice, run.st);
+  if (e == hipSuccess) e = hipMemcpyAsync(cols, j.cols, (size_t)ms * sizeof(int), hipMemcpyHostToDevice, run.st);
+  if (e == hipSuccess) {
+    fp64_subsample_gather(run.st, x, rows, cols, ns, ms, j.out);
+    fp64_subsample_lines(run.st, j.out, ns, ms, mask, ints);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(host_ints, ints, sizeof(host_ints), hipMemcpyDeviceToHost, run.st);
+  if (e == hipSuccess && (j.row_mask || j.col_mask)) {
+    host_mask.resize((size_t)ns + ms);
+    e = hipMemcpyAsync(host_mask.data(), mask, host_mask.size(), hipMemcpyDeviceToHost, run.st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(run.st);
+  if (e != hipSuccess) return run.fail(e);
+  *j.n_empty_rows = host_ints[0];
+  *j.n_empty_cols = host_ints[1];
+  if (j.row_mask) std::memcpy(j.row_mask, host_mask.data(), (size_t)ns);
+  if (j.col_mask) std::memcpy(j.col_mask, host_mask.data() + ns, (size_t)ms);
+  return RESNMTF_OK;
+}
+
+int resnmtf_fp64_relevance(int device_id, const resnmtf_fp64_relevance_job* job) {
+  if (const char* why = f64_relevance_check_job(job)) return fp64_bad(why);
+  const resnmtf_fp64_relevance_job& j = *job;
+  const int n = j.n, m = j.m, ns = j.n_sub, ms = j.m_sub, k = j.k, kr = j.k_ref;
+  {
+    std::string why = f64_subsample_check_indices("rows", j.rows, ns, n);
+    if (why.empty()) why = f64_subsample_check_indices("cols", j.cols, ms, m);
+    if (!why.empty()) return fp64_bad(why);
+  }
+  auto bad_entry = [](const char* name, unsigned long long pos, int len) {
+    return fp64_bad(std::string(name) + " entries must be 0 or 1 (row " + std::to_string(pos % (unsigned long long)len) + ", column " +
+                    std::to_string(pos / (unsigned long long)len) + ")");
+  };
+  if (j.true_r) { const long long at = f64_relevance_bad_entry(j.true_r, n, kr); if (at >= 0) return bad_entry("true_r", (unsigned long long)at, n); }
+  if (j.true_c) { const long long at = f64_relevance_bad_entry(j.true_c, m, kr); if (at >= 0) return bad_entry("true_c", (unsigned long long)at, m); }
+  if (int rc = fp64_check_device_id(device_id)) return rc;
+  // the four matrices as the kernels read them; a host reference becomes its staged copy below
+  struct Mat { const char* name; resnmtf_device_matrix a; int len, k; bool dev; };
+  Mat mats[4] = {{"row_c", j.row_c, ns, k, true}, {"col_c", j.col_c, ms, k, true},
+                 {"true_r_dev", j.true_r_dev, n, kr, j.true_r == nullptr}, {"true_c_dev", j.true_c_dev, m, kr, j.true_c == nullptr}};
+  unsigned long long host_bad[4] = {F64_REL_NONE, F64_REL_NONE, F64_REL_NONE, F64_REL_NONE};   // (before the run: see above)
+  std::vector<double> host_out((size_t)kr);
+  F64CallRun run("fp64_relevance");
+  hipError_t e = hipSetDevice(device_id);
+  if (e != hipSuccess) return run.fail(e, "hipSetDevice: ");
+  for (const Mat& t : mats) {
+    if (!t.dev) continue;
+    bool beyond = false;
+    if (!fp64_on_device(device_id, t.a.ptr, f64_matrix_bytes(t.a, t.len, t.k), beyond))
+      return fp64_bad(std::string(t.name) + (beyond ? " reaches beyond its allocation (too short for the shape and strides given)"
+                                                    : " is not device memory of device " + std::to_string(device_id)));
+  }
+  const F64RelevancePlan plan = f64_relevance_plan(j);
+  void* p = nullptr;
+  if (int rc = run.alloc(&p, plan.total, "the workspace")) return rc;
+  run.work = static_cast<char*>(p);
+  if ((e = hipStreamCreateWithFlags(&run.st, hipStreamNonBlocking)) != hipSuccess) { run.st = nullptr; return run.fail(e, "hipStreamCreate: "); }
+  e = wait_for_caller(run.st, j.stream);
+  unsigned long long* bad = reinterpret_cast<unsigned long long*>(run.work + plan.bad);
+  double* out = reinterpret_cast<double*>(run.work + plan.out);
+  unsigned int* counts = reinterpret_cast<unsigned int*>(run.work + plan.counts);
+  int* rows = reinterpret_cast<int*>(run.work + plan.rows);
+  int* cols = reinterpret_cast<int*>(run.work + plan.cols);
+  if (e == hipSuccess) e = hipMemsetAsync(bad, 0xFF, 4 * sizeof(unsigned long long), run.st);
+  if (e == hipSuccess) e = hipMemsetAsync(counts, 0, 2 * plan.side_counts * sizeof(unsigned int), run.st);
+  if (e == hipSuccess) e = hipMemcpyAsync(rows, j.rows, (size_t)ns * sizeof(int), hipMemcpyHostToDevice, run.st);
+  if (e == hipSuccess) e = hipMemcpyAsync(cols, j.cols, (size_t)ms * sizeof(int), hipMemcpyHostToDevice, run.st);
+  if (j.true_r) {
+    if (e == hipSuccess) e = hipMemcpyAsync(run.work + plan.true_r, j.true_r, (size_t)n * kr * sizeof(double), hipMemcpyHostToDevice, run.st);
+    mats[2].a = resnmtf_device_matrix{run.work + plan.true_r, RESNMTF_DTYPE_F64, 1, n};
+  }
+  if (j.true_c) {
+    if (e == hipSuccess) e = hipMemcpyAsync(run.work + plan.true_c, j.true_c, (size_t)m * kr * sizeof(double), hipMemcpyHostToDevice, run.st);
+    mats[3].a = resnmtf_device_matrix{run.work + plan.true_c, RESNMTF_DTYPE_F64, 1, m};
+  }
+  if (e == hipSuccess) {
+    for (int t = 0; t < 4; ++t)
+      if (mats[t].dev) fp64_relevance_check(run.st, mats[t].a, mats[t].len, mats[t].k, bad + t);
+    fp64_relevance_count(run.st, mats[0].a, ns, k, mats[2].a, kr, rows, counts);
+    fp64_relevance_count(run.st, mats[1].a, ms, k, mats[3].a, kr, cols, counts + plan.side_counts);
+    hipLaunchKernelGGL(fp64_relevance_epilogue_kernel, dim3(1), dim3(64), 0, run.st, k, kr, (const unsigned int*)counts,
+                       (const unsigned int*)(counts + plan.side_counts), out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(host_bad, bad, sizeof(host_bad), hipMemcpyDeviceToHost, run.st);
+  if (e == hipSuccess) e = hipMemcpyAsync(host_out.data(), out, (size_t)kr * sizeof(double), hipMemcpyDeviceToHost, run.st);
+  if (e == hipSuccess) e = hipStreamSynchronize(run.st);
+  if (e != hipSuccess) return run.fail(e);
+  for (int t = 0; t < 4; ++t)
+    if (host_bad[t] != F64_REL_NONE) return bad_entry(mats[t].name, host_bad[t], mats[t].len);
+  std::memcpy(j.relevance, host_out.data(), (size_t)kr * sizeof(double));
   return RESNMTF_OK;
 }
 

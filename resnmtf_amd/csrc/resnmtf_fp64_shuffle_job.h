@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "resnmtf_hip.h"
+#include "resnmtf_fp64_extent.h"
 
 constexpr unsigned long long F64_SHUFFLE_MAX_COUNT = 1ull << 62;      // the Feistel domain: 2^(2 half_bits), half_bits <= 31
 
@@ -31,23 +32,16 @@ inline const char* f64_shuffle_check_job(const resnmtf_fp64_shuffle_job* job) {
   return nullptr;
 }
 
-inline size_t f64_shuffle_dtype_bytes(int dtype) { return dtype == RESNMTF_DTYPE_F64 ? 8 : dtype == RESNMTF_DTYPE_F32 ? 4 : 2; }
-
+// the extents of the checked job, from the helpers the handle-free fp64 entries share (resnmtf_fp64_extent.h)
+inline size_t f64_shuffle_dtype_bytes(int dtype) { return f64_dtype_bytes(dtype); }
 // the bytes [ptr, ptr + bytes) a device source of the checked job spans: up to its last element
-inline size_t f64_shuffle_source_bytes(const resnmtf_fp64_shuffle_job& j) {
-  const size_t last = (size_t)(j.n - 1) * (size_t)j.x_dev.row_stride + (size_t)(j.m - 1) * (size_t)j.x_dev.col_stride;
-  return (last + 1) * f64_shuffle_dtype_bytes(j.x_dev.dtype);
-}
+inline size_t f64_shuffle_source_bytes(const resnmtf_fp64_shuffle_job& j) { return f64_matrix_bytes(j.x_dev, j.n, j.m); }
 // n m doubles beyond what 64 bits count in bytes (n m > 2^60): no device holds them; asked before f64_shuffle_out_bytes
-inline bool f64_shuffle_bytes_overflow(const resnmtf_fp64_shuffle_job& j) {
-  return (unsigned long long)j.n * (unsigned long long)j.m > (1ull << 60);
-}
-inline size_t f64_shuffle_out_bytes(const resnmtf_fp64_shuffle_job& j) { return (size_t)j.n * (size_t)j.m * sizeof(double); }
-
+inline bool f64_shuffle_bytes_overflow(const resnmtf_fp64_shuffle_job& j) { return f64_array_bytes_overflow(j.n, j.m); }
+inline size_t f64_shuffle_out_bytes(const resnmtf_fp64_shuffle_job& j) { return f64_array_bytes(j.n, j.m); }
 // two byte ranges share a byte
 inline bool f64_shuffle_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+  return f64_ranges_overlap(a, a_bytes, b, b_bytes);
 }
 
 // The small workspace of a call, in bytes from its start (the staging copy of a host X, n m doubles, is a buffer of its

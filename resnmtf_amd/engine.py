@@ -459,6 +459,162 @@ def fp64_shuffle(x, seed: int, normalise: bool = True, device_id: int = 0):
     return out, bool(neg.value), rm.astype(bool), cm.astype(bool)
 
 
+def _index_list(idx, what: str) -> np.ndarray:
+    """An index list as contiguous int32 (the C-ABI validates its range and that no index occurs twice)."""
+    arr = np.asarray(idx)
+    if arr.ndim != 1 or arr.size < 1:
+        raise ValueError(f"{what} must be a non-empty 1-D index list")
+    if not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError(f"{what} must hold integers, got {arr.dtype}")
+    if arr.min() < np.iinfo(np.int32).min or arr.max() > np.iinfo(np.int32).max:
+        raise ValueError(f"{what} holds an index beyond 32 bits")
+    return np.ascontiguousarray(arr, dtype=np.int32)
+
+
+def fp64_device_view(x, device_id: int = 0):
+    """The dense view ``x`` as ``fp64_subsample`` reads it many times: a tensor on ``cuda:device_id`` as it is, anything
+    else (a NumPy array, a CPU tensor) copied there once as an fp64 column-major tensor -- the same values, so a sub-sample
+    of the copy has the bits of a sub-sample of ``x``."""
+    import torch
+    if _device_views.is_tensor(x) and _device_views.on_engine_device(x, device_id):
+        return x
+    arr = _f64_colmajor(_device_views.to_numpy(x) if _device_views.is_tensor(x) else x)
+    return torch.as_tensor(np.ascontiguousarray(arr.T)).to(torch.device("cuda", int(device_id))).t()
+
+
+def fp64_subsample_plan(row_stride: int = 1, col_stride: int = 1) -> dict:
+    """How ``fp64_subsample`` launches for a source with the given strides in elements (``resnmtf_fp64_subsample_plan``;
+    no device work): ``{"gather": "rows" (lanes along the destination rows) or "lds" (the padded LDS tile transpose),
+    "gather_rows", "gather_tile", "row_sum_rows", "col_sum_rows", "col_sum_cols"}`` -- the form and every tile edge."""
+    lib = _lib.load()
+    out = (C.c_int * _lib.FP64_SUBSAMPLE_PLAN_INTS)()
+    rc = lib.resnmtf_fp64_subsample_plan(int(row_stride), int(col_stride), out)
+    if rc != _lib.OK:
+        raise ResnmtfError(rc, (lib.resnmtf_last_error(None) or b"").decode())
+    v = list(out)
+    return {"gather": ("rows", "lds")[v[0]], "gather_rows": v[1], "gather_tile": v[2], "row_sum_rows": v[3],
+            "col_sum_rows": v[4], "col_sum_cols": v[5]}
+
+
+def fp64_subsample(x, rows, cols, device_id: int = 0, out=None):
+    """The sub-sample ``x[rows, cols]`` of one view in double precision (``resnmtf_fp64_subsample``, no handle; DESIGN.md
+    section 28): ``stability_repeat``'s ``data[[i]][row_samples, col_samples]`` (``R/stability_analysis.r:124``) on the fp64
+    values of ``x``, not re-normalised.  Returns ``(tensor, empty_rows, empty_cols)``: the sub-sample as an fp64
+    column-major ``torch`` tensor on ``cuda:device_id`` and the boolean masks of its rows / columns that sum to exactly
+    zero (one running fp64 sum per line, a row over ascending columns, a column over ascending rows: the flags
+    ``Engine.subsample_view_from`` + ``Engine.empty_lines`` report on data fp32 holds).  ``x``: as for ``fp64_shuffle`` (a
+    NumPy array or CPU tensor, copied once to the device as fp64, or a floating ``torch`` tensor on ``cuda:device_id`` of
+    any strides, read where it lies after the work on torch's current stream).  ``rows`` / ``cols``: 0-based, in any
+    order, each index at most once.  ``out`` (a test hook): an fp64 tensor of shape ``(len(cols), len(rows))``, contiguous,
+    on the device, whose transpose receives the sub-sample instead of a fresh one.  Two calls give equal bits.  Bad input
+    is refused before any device work (``ResnmtfError``)."""
+    import torch                    # (lazily: nothing else in this module needs it)
+    lib = _lib.load()
+    x = _device_views.as_view(x, device_id, "fp64_subsample: x")
+    if isinstance(x, _device_views.RawDeviceView):
+        raise NotImplementedError("fp64_subsample gathers pre-processed dense views: a device tensor still to be shifted "
+                                  "and column-normalised (RawDeviceView) is not supported")
+    if _sparse.is_sparse_view(x) or _device_views.is_sparse_device_view(x):
+        raise NotImplementedError("fp64_subsample gathers dense views: a sparse view is not supported")
+    if len(x.shape) != 2:
+        raise ValueError("fp64_subsample: x must be an n x m matrix")
+    n, m = int(x.shape[0]), int(x.shape[1])
+    if n < 1 or m < 1:
+        raise ValueError("fp64_subsample: x must have at least one row and one column")
+    rows, cols = _index_list(rows, "fp64_subsample: rows"), _index_list(cols, "fp64_subsample: cols")
+    ns, ms = int(rows.size), int(cols.size)
+    dev = torch.device("cuda", int(device_id))
+    if out is None:
+        out = torch.empty((ms, ns), dtype=torch.float64, device=dev)
+    elif tuple(out.shape) != (ms, ns) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != dev:
+        raise ValueError("fp64_subsample: out must be a contiguous fp64 tensor of shape (len(cols), len(rows)) on the device")
+    nr, nc = C.c_int(0), C.c_int(0)
+    rm = np.zeros(ns, dtype=np.uint8); cm = np.zeros(ms, dtype=np.uint8)
+    job = _lib.Fp64SubsampleJob()
+    job.struct_size = C.sizeof(job)
+    job.n, job.m, job.n_sub, job.m_sub = n, m, ns, ms
+    job.rows, job.cols = _ip(rows), _ip(cols)
+    if _device_views.is_tensor(x):
+        job.x_dev = _device_matrix(x, (n, m), device_id, "fp64_subsample: x")
+    else:
+        x = _f64_colmajor(x)
+        job.x = _dp(x)
+    job.stream = torch.cuda.current_stream(dev).cuda_stream
+    job.out = out.data_ptr()
+    job.n_empty_rows, job.n_empty_cols = C.pointer(nr), C.pointer(nc)
+    job.row_mask, job.col_mask = rm.ctypes.data_as(C.POINTER(C.c_ubyte)), cm.ctypes.data_as(C.POINTER(C.c_ubyte))
+    code = lib.resnmtf_fp64_subsample(int(device_id), C.byref(job))
+    if code != _lib.OK:
+        raise ResnmtfError(code, (lib.resnmtf_last_error(None) or b"").decode())
+    return out.t(), rm.astype(bool), cm.astype(bool)             # n_sub x m_sub, column-major
+
+
+def fp64_relevance(row_c, col_c, true_r, true_c, rows, cols, device_id: int = 0) -> np.ndarray:
+    """``relevance_results`` (``R/stability_analysis.r:45-67``) of cluster matrices in device memory
+    (``resnmtf_fp64_relevance``, no handle): ``row_c`` (n_sub x k) and ``col_c`` (m_sub x k), the 0 / 1
+    clusters of a sub-sample as floating ``torch`` tensors on ``cuda:device_id`` of any strides (what the fp64 run leaves
+    with ``output="torch"``; anything else is copied there as fp64), scored against the reference's ``true_r`` (n x k_ref)
+    and ``true_c`` (m x k_ref) gathered through ``rows`` / ``cols`` -- each a tensor on the device, read in place, or
+    anything NumPy takes.  Returns the k_ref relevance values, bit for bit ``tests/stability_ref.relevance_counts`` of the
+    same matrices.  An entry other than 0 / 1 and bad lists are refused (``ResnmtfError``)."""
+    import torch
+    lib = _lib.load()
+    dev = torch.device("cuda", int(device_id))
+
+    def on_device(a):
+        return _device_views.is_tensor(a) and _device_views.on_engine_device(a, device_id) and a.dtype.is_floating_point
+
+    keep = []
+
+    def device_side(a, what):
+        if not on_device(a):
+            a = torch.as_tensor(_device_views.to_numpy(a) if _device_views.is_tensor(a) else np.asarray(a, dtype=np.float64),
+                                dtype=torch.float64).to(dev)
+            keep.append(a)
+        if a.dim() != 2:
+            raise ValueError(f"fp64_relevance: {what} must be a matrix")
+        return a
+
+    row_c, col_c = device_side(row_c, "row_c"), device_side(col_c, "col_c")
+    rows, cols = _index_list(rows, "fp64_relevance: rows"), _index_list(cols, "fp64_relevance: cols")
+    ns, ms, k = int(rows.size), int(cols.size), int(row_c.shape[1])
+    job = _lib.Fp64RelevanceJob()
+    job.struct_size = C.sizeof(job)
+    job.row_c = _device_matrix(row_c, (ns, k), device_id, "fp64_relevance: row_c")
+    job.col_c = _device_matrix(col_c, (ms, k), device_id, "fp64_relevance: col_c")
+    refs = []
+    for a, what in ((true_r, "true_r"), (true_c, "true_c")):
+        if on_device(a):
+            if a.dim() != 2:
+                raise ValueError(f"fp64_relevance: {what} must be a matrix")
+            refs.append(a)
+        else:
+            a = _f64_colmajor(_device_views.to_numpy(a) if _device_views.is_tensor(a) else a)
+            if a.ndim != 2:
+                raise ValueError(f"fp64_relevance: {what} must be a matrix")
+            refs.append(a)
+    n, m, k_ref = int(refs[0].shape[0]), int(refs[1].shape[0]), int(refs[0].shape[1])
+    if int(refs[1].shape[1]) != k_ref:
+        raise ValueError("fp64_relevance: true_r and true_c differ in their number of clusters")
+    if _device_views.is_tensor(refs[0]):
+        job.true_r_dev = _device_matrix(refs[0], (n, k_ref), device_id, "fp64_relevance: true_r")
+    else:
+        job.true_r = _dp(refs[0])
+    if _device_views.is_tensor(refs[1]):
+        job.true_c_dev = _device_matrix(refs[1], (m, k_ref), device_id, "fp64_relevance: true_c")
+    else:
+        job.true_c = _dp(refs[1])
+    job.n, job.m, job.n_sub, job.m_sub, job.k, job.k_ref = n, m, ns, ms, k, k_ref
+    job.rows, job.cols = _ip(rows), _ip(cols)
+    job.stream = torch.cuda.current_stream(dev).cuda_stream
+    out = np.zeros(max(k_ref, 1), dtype=np.float64)
+    job.relevance = _dp(out)
+    code = lib.resnmtf_fp64_relevance(int(device_id), C.byref(job))
+    if code != _lib.OK:
+        raise ResnmtfError(code, (lib.resnmtf_last_error(None) or b"").decode())
+    return out[:k_ref]
+
+
 def fp64_bisil_plan(n_u: int, n_mem: int, k: int, row_stride: int = 1, col_stride: int = 1) -> dict:
     """How ``fp64_bisil`` launches one side of one bicluster (``resnmtf_fp64_bisil_plan``; no device work): ``{"kq",
     "chunk_tiles", "chunks", "gather": (form of the row side, of the column side)}`` for ``n_u`` points in U, ``n_mem``

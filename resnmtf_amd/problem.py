@@ -214,6 +214,15 @@ def shuffled_fits_fp64(data, k: int, num_repeats: int, seed: int = 0, max_iters:
     return out
 
 
+def fit_fp64_on_device(tensors, k: int, phi, xi, psi, n_iters, num_repeats=5, spurious: bool = False, **kw) -> dict:
+    """``res_nmtf_inner(precision="fp64", fp64_device=True, output="torch")`` of views that are fp64 tensors on the device,
+    k biclusters per view, from the device's SVD start (shared maps from the names in ``kw``): the fit of a stability
+    repeat in double precision (``batched.stability_repeat_fp64``); ``kw`` goes on to it."""
+    from .api import res_nmtf_inner          # (lazy: api imports this module at its top)
+    return res_nmtf_inner(tensors, None, None, None, None, None, [k] * len(tensors), phi, xi, psi, n_iters, num_repeats, spurious,
+                          precision="fp64", fp64_device=True, output="torch", **kw)
+
+
 def reported_error(errs, n_iters) -> float:
     """``R/main.r:126-130``: the mean of the last ten errors of a run to convergence, else the last error."""
     return float(np.mean(errs[-10:])) if n_iters is None else float(errs[-1])
