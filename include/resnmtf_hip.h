@@ -1067,6 +1067,52 @@ int resnmtf_fp64_bisil(int device_id, const resnmtf_fp64_bisil_job* job);
 int resnmtf_fp64_bisil_plan(int n_u, int n_mem, int k, long long row_stride, long long col_stride, int* out);
 
 /*
+ * resnmtf_fp64_bisil of a SPARSE view, without a handle: the per-member silhouettes behind the
+ * `bisil` that res_nmtf_inner attaches to every result (R/obtain_bicl.r:189-199) and that the k sweep of apply_resnmtf
+ * ranks (R/main.r:269-321), for a view that resnmtf_fp64_run_sparse or resnmtf_fp64_run_sparse_device factorised -- on the
+ * fp64 values that were factorised, where resnmtf_bisil_sparse reads a handle's fp32 values, and without the n x m fp64
+ * matrix that resnmtf_fp64_bisil would need of it.  Blocking.
+ *   n, m, k, metric, row_clusters, col_clusters, row_sil, col_sil   as in resnmtf_fp64_bisil_job.
+ *   x             the view in host memory: the 0-based canonical CSC of the pre-processed view, as resnmtf_fp64_run_sparse
+ *                 takes it (col_ptr NULL when not given); or
+ *   x_dev, stream the view in device memory, as resnmtf_fp64_run_sparse_device takes it: CSC, CSR or coalesced COO, int32 or
+ *                 int64 indices, fp64 / fp32 / fp16 / bf16 values, entries in any order, explicit zeros stay stored (all
+ *                 seven fields zero when not given).  The arrays are read where they lie after an event recorded on
+ *                 `stream`; nothing of size nnz, n or m of the view crosses the bus.  X is given in exactly one place.
+ * The silhouettes are BIT FOR BIT those of resnmtf_fp64_bisil on the densified matrix of the same values widened to fp64,
+ * and so, on values fp32 holds exactly, those of resnmtf_bisil_sparse; two calls give equal bits.  Per side and active
+ * bicluster the block G, |J_l| x U_pad doubles, is zero-filled and one wave per feature line scatters the stored entries
+ * that fall in U into it (the row side from the CSC columns, the column side from the CSR rows; indices within a line are
+ * distinct: no atomics); the norm, distance and epilogue kernels of resnmtf_fp64_bisil then run on it unchanged.
+ * On the device the view is a CSC and a CSR copy, int64 pointers, int32 indices, fp64 values: 24 bytes per stored entry
+ * plus the pointers.  The host route builds the CSR by the counting sort of resnmtf_fp64_run_sparse; the device route
+ * checks and sorts the arrays with the kernels of resnmtf_set_view_sparse_device in transient allocations.  Every index
+ * is verified before the first scatter is launched.
+ * Refused before any device work (RESNMTF_ERR_INVALID, text in resnmtf_last_error(NULL)), neither output written: what
+ * resnmtf_fp64_bisil refuses, with its texts -- job NULL, a struct_size mismatch, k outside [1, 64], n or m below 1, an
+ * unknown metric, X in both places or in neither, NULL cluster or output pointers, a cluster entry other than 0 or 1 --;
+ * for a host view what resnmtf_fp64_run_sparse refuses of view 0 (NULL row_idx / values, col_ptr[0] != 0, col_ptr not
+ * monotone, a row index out of range or not strictly increasing within a column, a non-finite or negative value); for a
+ * device view what resnmtf_fp64_run_sparse_device refuses of view 0 (an unknown layout, index type or dtype, nnz < 0, a
+ * NULL array, an array that is not device memory of device_id or is too short; then, by the device checks, bad pointers,
+ * an index out of range, a non-finite or negative value, a position stored twice).
+ * The workspace -- the block, the norms, the chunk partials, the silhouettes, the lists, the two rank tables (n + m ints)
+ * and the two sparse copies -- is sized first and refused with RESNMTF_ERR_ALLOC and its byte count when it exceeds the
+ * free device memory.  No active bicluster: zero silhouettes, RESNMTF_OK, no device work.  A view without a stored entry
+ * is scored as the all-zero matrix.
+ */
+typedef struct resnmtf_fp64_bisil_sparse_job {
+  int struct_size;                          /* sizeof the struct */
+  int n, m, k, metric;
+  resnmtf_fp64_sparse_view x;
+  resnmtf_fp64_sparse_device_view x_dev;
+  void* stream;
+  const double *row_clusters, *col_clusters;
+  double *row_sil, *col_sil;
+} resnmtf_fp64_bisil_sparse_job;
+int resnmtf_fp64_bisil_sparse(int device_id, const resnmtf_fp64_bisil_sparse_job* job);
+
+/*
  * shuffle_view (R/obtain_bicl.r:11-22) of one view in DOUBLE precision, without a handle: the
  * draw that obtain_shuffled_f (R/obtain_bicl.r:31-42) factorises, made of the fp64 values of X -- the numbers
  * resnmtf_fp64_run factorised -- where resnmtf_shuffle_view permutes a handle's fp32 image.  Blocking.

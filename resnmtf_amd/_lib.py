@@ -164,6 +164,15 @@ class Fp64BisilJob(C.Structure):
                 ("row_clusters", _dp), ("col_clusters", _dp), ("row_sil", _dp), ("col_sil", _dp)]
 
 
+class Fp64BisilSparseJob(C.Structure):
+    """``resnmtf_fp64_bisil_sparse_job`` (include/resnmtf_hip.h): the view as host CSC arrays (``x``) or as sparse arrays in
+    device memory (``x_dev`` read after ``stream``), the host 0 / 1 cluster matrices and the host outputs of
+    ``resnmtf_fp64_bisil_sparse``."""
+    _fields_ = [("struct_size", C.c_int), ("n", C.c_int), ("m", C.c_int), ("k", C.c_int), ("metric", C.c_int),
+                ("x", Fp64SparseView), ("x_dev", Fp64SparseDeviceView), ("stream", C.c_void_p),
+                ("row_clusters", _dp), ("col_clusters", _dp), ("row_sil", _dp), ("col_sil", _dp)]
+
+
 class Fp64ShuffleJob(C.Structure):
     """``resnmtf_fp64_shuffle_job`` (include/resnmtf_hip.h): X in host memory (``x``) or in device memory (``x_dev``), the
     caller's device array ``out`` (n m doubles, written after ``stream``) and the host outputs of ``resnmtf_fp64_shuffle``."""
@@ -254,6 +263,7 @@ SIGNATURES = {
                                                  C.POINTER(Fp64SparseDevice), C.c_double, C.c_int]),
     "resnmtf_fp64_bisil": (C.c_int, [C.c_int, C.POINTER(Fp64BisilJob)]),
     "resnmtf_fp64_bisil_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, _ip]),
+    "resnmtf_fp64_bisil_sparse": (C.c_int, [C.c_int, C.POINTER(Fp64BisilSparseJob)]),
     "resnmtf_fp64_shuffle": (C.c_int, [C.c_int, C.POINTER(Fp64ShuffleJob)]),
     "resnmtf_fp64_subsample": (C.c_int, [C.c_int, C.POINTER(Fp64SubsampleJob)]),
     "resnmtf_fp64_subsample_plan": (C.c_int, [C.c_longlong, C.c_longlong, _ip]),

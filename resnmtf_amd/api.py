@@ -34,7 +34,9 @@ Without the opt-ins ``bisil`` stays ``None`` and ``k_val=None`` raises ``NotImpl
 
 Under ``precision="fp64"`` the score is computed in double precision on the numbers that were factorised
 (``res_nmtf_inner(score_bisil=True, fp64_bisil=True)`` -> ``engine.fp64_bisil`` -> ``resnmtf_fp64_bisil``, no handle), and
-``apply_resnmtf(precision="fp64")`` runs a known k or the k sweep on it.  Spurious-bicluster
+``apply_resnmtf(precision="fp64")`` runs a known k or the k sweep on it; with the further opt-in
+``fp64_bisil_sparse=True`` sparse views are scored too, stored sparse (``engine.fp64_bisil_sparse`` ->
+``resnmtf_fp64_bisil_sparse``), and the fp64 k sweep runs on them.  Spurious-bicluster
 removal runs there too with the opt-in ``fp64_spurious=True`` (beside ``spurious_on_device=True``): the shuffles are drawn
 from the fp64 values (``engine.fp64_shuffle`` -> ``resnmtf_fp64_shuffle``, no handle) and factorised by the fp64 path
 (``problem.shuffled_fits_fp64``).  Stability selection runs there with the opt-in
@@ -117,7 +119,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
                    sparse_on_device: bool = False, output: str = "numpy", init_lm=None, return_state: bool = False,
                    post_on_device: bool = False, precision: str = "f32", fp64_sparse: bool = False,
                    fp64_device: bool = False, fp64_sparse_device: bool = False, fp64_bisil: bool = False,
-                   fp64_spurious: bool = False):
+                   fp64_spurious: bool = False, fp64_bisil_sparse: bool = False):
     """``res_nmtf_inner`` (``R/main.r:32-140``).
 
     ``data``: list of pre-processed (non-negative, column-normalised) matrices; ``row_indices[v][w]``
@@ -237,6 +239,11 @@ def res_nmtf_inner(data, row_indices, column_indices,
     (``fp64_device``) is read where it lies.  The cluster matrices are brought to the host (n k + m k values per view)
     and the score is combined there.  Combines with ``fp64_device`` and ``output="torch"``.  A sparse view with
     ``score_bisil`` raises a ``NotImplementedError`` naming ``fp64_bisil`` and sparse views.
+    ``fp64_bisil_sparse`` (keyword-only opt-in; read only with ``precision="fp64"``, ``score_bisil``
+    and ``fp64_bisil=True``, a no-op everywhere else): the sparse views that ``fp64_sparse`` / ``fp64_sparse_device`` admit
+    are scored too, through ``engine.fp64_bisil_sparse`` (``resnmtf_fp64_bisil_sparse``: bit for bit ``engine.fp64_bisil``
+    of the densified view, without densifying it), dense views through ``engine.fp64_bisil`` as before, and the two
+    combine in ``bisil.score``.  Mixed view lists and ``output="torch"`` work.  Without it the refusal above stands.
     ``fp64_spurious`` (keyword-only opt-in; a no-op with ``precision="f32"``): with
     ``precision="fp64"``, ``spurious=True`` and ``spurious_on_device=True`` the removal runs in double precision: after the
     run, ``check_biclusters(data, F, num_repeats, seed=seed, precision="fp64")`` on the views exactly as the run received
@@ -257,7 +264,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
                                     spurious_on_device=spurious_on_device, output=output, init_lm=init_lm,
                                     return_state=return_state, post_on_device=post_on_device, fp64_sparse=fp64_sparse,
                                     fp64_device=fp64_device, fp64_sparse_device=fp64_sparse_device, fp64_bisil=fp64_bisil,
-                                    fp64_spurious=fp64_spurious, num_repeats=num_repeats)
+                                    fp64_spurious=fp64_spurious, num_repeats=num_repeats, fp64_bisil_sparse=fp64_bisil_sparse)
     device_views.check_output(output)
     _check_post_on_device(post_on_device, output)
     data = _views(data, device_id)
@@ -351,13 +358,15 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
                          return_init, score_bisil, spurious_on_device, output, init_lm, return_state, post_on_device,
                          fp64_sparse: bool = False, fp64_device: bool = False, fp64_sparse_device: bool = False,
                          fp64_bisil: bool = False, runner: Optional[Callable] = None, sil: Optional[Callable] = None,
-                         fp64_spurious: bool = False, num_repeats=5, checker: Optional[Callable] = None):
+                         fp64_spurious: bool = False, num_repeats=5, checker: Optional[Callable] = None,
+                         fp64_bisil_sparse: bool = False):
     """``res_nmtf_inner(precision="fp64")``: the checks of the f32 call, the refusals of what needs a live handle, the
     initial state, then one ``engine.fp64_run`` (``runner`` replaces it: a test hook).  ``fp64_device``: views, factors
     and results may live in device memory (``res_nmtf_inner``'s docstring); the runner then also gets ``output`` and
     ``return_state``.  ``fp64_sparse_device``: a sparse tensor on ``cuda:device_id`` reaches the problem as its
     ``SparseDeviceView`` -- the same tensor, untouched.  ``fp64_bisil``: ``score_bisil`` is honoured through
-    ``engine.fp64_bisil`` on the views as they arrived (``sil(v, rc, cc, distance)`` replaces it: a test hook).
+    ``engine.fp64_bisil`` on the views as they arrived (``sil(v, rc, cc, distance)`` replaces it: a test hook);
+    ``fp64_bisil_sparse``: a sparse view then goes to ``engine.fp64_bisil_sparse`` instead of being refused.
     ``fp64_spurious``: ``spurious=True`` with ``spurious_on_device`` is honoured through
     ``spurious.check_biclusters(..., precision="fp64")`` on the views as they arrived (``checker`` replaces it: a test
     hook), then ``_remove_then_score``."""
@@ -403,7 +412,7 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
         _spurious.check_num_repeats(num_repeats)
         _spurious.refuse_sparse_fp64(data)
     score = bool(score_bisil) and not no_clusts                  # (here: fp64_bisil is set, or the call was refused above)
-    if score and any(is_sp):
+    if score and any(is_sp) and not fp64_bisil_sparse:
         raise NotImplementedError(f'precision="fp64": score_bisil with fp64_bisil=True scores dense views only; sparse views '
                                   f'(view {is_sp.index(True)}) are not supported by resnmtf_fp64_bisil')
     if any(device_views.is_device_view(d) and not is_sp[v] for v, d in enumerate(data)) and host_init and (init_f is None or init_g is None or init_s is None):
@@ -484,8 +493,9 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
     score_fn = None
     if score:                                     # obtain_bicl.r:189-199, on the numbers that were factorised (section 26)
         if sil is None:
-            def sil(v, rc, cc, distance):
-                return _engine.fp64_bisil(data[v], rc, cc, distance, device_id=device_id)
+            def sil(v, rc, cc, distance):      # (a sparse view is here only with fp64_bisil_sparse: section 29)
+                one = _engine.fp64_bisil_sparse if is_sp[v] else _engine.fp64_bisil
+                return one(data[v], rc, cc, distance, device_id=device_id)
 
         def score_fn(rcs, ccs):
             return bisil.score([device_views.to_numpy(rc) for rc in rcs], [device_views.to_numpy(cc) for cc in ccs],
@@ -749,7 +759,7 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                   sparse_on_device: bool = False, output: str = "numpy", post_on_device: bool = False,
                   precision: str = "f32", score_bisil: bool = False, fp64_sparse: bool = False, fp64_device: bool = False,
                   fp64_sparse_device: bool = False, fp64_bisil: bool = False, fp64_spurious: bool = False,
-                  fp64_stability: bool = False):
+                  fp64_stability: bool = False, fp64_bisil_sparse: bool = False):
     """``apply_resnmtf`` (``R/main.r:214-335``) for a known ``k_val``: naming, shared-name maps, restriction
     symmetrisation, non-negativity shift and column normalisation on the host, then the device loop and -- with
     ``stability=True`` (the default) and ``spurious=False`` -- ``stability_check`` on the pre-processed data, as
@@ -825,7 +835,13 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     with it forwarded (``:324-332``), exactly as the f32 function does; with ``spurious=True`` (which needs
     ``fp64_spurious`` as above) the removal runs inside every repeat.  A sparse view with it is refused by name.
     ``apply_resnmtf(data, precision="fp64", k_sweep=True, spurious_on_device=True, fp64_spurious=True,
-    fp64_stability=True)`` is the reference's default pipeline.  Without the flag ``stability=True`` stays refused."""
+    fp64_stability=True)`` is the reference's default pipeline.  Without the flag ``stability=True`` stays refused.
+    ``fp64_bisil_sparse=True`` (keyword-only opt-in; a no-op with ``precision="f32"``) is passed
+    through to ``res_nmtf_inner`` -- for the ``k_val`` and for every k of the sweep -- and lifts the refusal of sparse views
+    in the fp64 k sweep: ``apply_resnmtf(data, precision="fp64", k_sweep=True, fp64_sparse=True, fp64_bisil_sparse=True,
+    spurious=False, stability=False)`` selects k on ``scipy.sparse`` views, every k scored by
+    ``engine.fp64_bisil_sparse``.  Still refused by name: ``fp64_spurious`` and ``fp64_stability`` on a sparse view, and
+    views in device memory."""
     if precision not in ("f32", "fp64"):
         raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
     if precision == "fp64":
@@ -835,7 +851,8 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                            return_sweep=return_sweep, sweep_runner=sweep_runner, output=output, score_bisil=score_bisil,
                            fp64_sparse=fp64_sparse, fp64_device=fp64_device, fp64_sparse_device=fp64_sparse_device,
                            fp64_bisil=fp64_bisil, fp64_spurious=fp64_spurious, spurious_on_device=spurious_on_device,
-                           fp64_stability=fp64_stability, remove_unstable=remove_unstable)
+                           fp64_stability=fp64_stability, remove_unstable=remove_unstable,
+                           fp64_bisil_sparse=fp64_bisil_sparse)
     device_views.check_output(output)
     _check_post_on_device(post_on_device, output)
     on_dev = {"sparse_on_device": True} if sparse_on_device else {}      # (off: every call below is the earlier one)
@@ -885,7 +902,7 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
                 no_clusts, sample_rate, n_stability, stability, stab_thres, *, row_names, col_names, device_id, max_iters,
                 seed, k_sweep, return_sweep, sweep_runner, output, score_bisil, fp64_sparse, fp64_device,
                 fp64_sparse_device, fp64_bisil, fp64_spurious=False, spurious_on_device=False, fp64_stability=False,
-                remove_unstable=True):
+                remove_unstable=True, fp64_bisil_sparse=False):
     """``apply_resnmtf(precision="fp64")``: the checks of the f32 function, the refusals of what runs on the f32 engine,
     ``prepare``, then ``res_nmtf_inner(precision="fp64")`` -- once for a ``k_val``, or as ``run(k)`` of ``_sweep`` --, then
     with ``stability`` and ``fp64_stability`` ``stability_check(precision="fp64")`` on the prepared data."""
@@ -928,6 +945,8 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
     common = {"device_id": device_id, "max_iters": max_iters, "output": output, "precision": "fp64", **flags}
     if remove:                                    # (only then: without the flag every call is the one it was)
         common.update(spurious_on_device=True, fp64_spurious=True)
+    if fp64_bisil_sparse:                         # (the same: passed through only when set)
+        common.update(fp64_bisil_sparse=True)
 
     def stab_kw(p):                               # the keywords of stability_check(precision="fp64") on the prepared data
         return {"row_names": p.row_names, "col_names": p.col_names, "device_id": device_id, "seed": seed, "max_iters": max_iters,
@@ -946,7 +965,7 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
             results = stability_check(p.data, results, k_vec, p.phi, p.xi, p.psi, n_iters, spurious, num_repeats, no_clusts,
                                       distance, sample_rate, n_stability, stab_thres, **stab_kw(p))
         return results
-    if any(sparse.is_sparse_view(d) for d in data):
+    if any(sparse.is_sparse_view(d) for d in data) and not fp64_bisil_sparse:
         refuse("a sparse view in the k sweep", "resnmtf_fp64_bisil scores dense views only; pass k_val (with fp64_sparse=True)")
     if init_f is not None or init_s is not None or init_g is not None:
         raise NotImplementedError("the k sweep starts every k from the device's SVD initialisation; explicit initial "

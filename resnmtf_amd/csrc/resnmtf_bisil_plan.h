@@ -7,7 +7,8 @@
 //   - the chunk rule (bisil_chunk_rule) and the kq table (bisil_kq) of the distance kernel;
 // resnmtf_hip.hip (resnmtf_bisil, resnmtf_bisil_sparse: the fp32 images) and resnmtf_fp64.hip (resnmtf_fp64_bisil: X read
 // where it lies, every value carried in fp64), which adds its workspace (f64_bisil_plan) and the choice of its gather
-// kernel (f64_bisil_gather_form).
+// kernel (f64_bisil_gather_form), and resnmtf_fp64_bisil_sparse's rank tables (f64_bisil_ranks) and workspace
+// (f64_bisil_sparse_plan; section 29).
 #ifndef RESNMTF_BISIL_PLAN_H
 #define RESNMTF_BISIL_PLAN_H
 
@@ -167,6 +168,46 @@ inline void f64_bisil_pack(int k, const BisilHostLists& L, F64BisilMeta& M) {
   std::copy(L.side[0].umask.begin(), L.side[0].umask.end(), M.words.begin());
   std::copy(L.side[1].umask.begin(), L.side[1].umask.end(), M.words.begin() + M.mask[1]);
   if (!ints.empty()) std::memcpy(M.words.data() + n_mask, ints.data(), ints.size() * sizeof(int));
+}
+
+// ---- resnmtf_fp64_bisil_sparse ----
+
+// The rank tables of the scatter, n + m ints, the rows' table first: rank[p] = the position of point p in U of its
+// side, or -1 when p is in no active bicluster.
+inline void f64_bisil_ranks(const BisilHostLists& L, std::vector<int>& rank) {
+  const size_t n = (size_t)L.side[0].n_pts, m = (size_t)L.side[1].n_pts;
+  rank.assign(n + m, -1);
+  for (int sd = 0; sd < 2; ++sd) {
+    int* r = rank.data() + (sd == 0 ? 0 : n);
+    const std::vector<int>& u = L.side[sd].upts;
+    for (size_t i = 0; i < u.size(); ++i) r[u[i]] = (int)i;
+  }
+}
+
+// The one device buffer of a sparse call, in doubles from its start: the dense call's regions without a copy of X
+// (`dense`: G, norm2, partial, sil, meta), then
+//   [rank: n + m ints, rows first][cptr: m + 1 int64][cval: nnz][cidx: nnz ints][rptr: n + 1 int64][rval: nnz][ridx: nnz ints]
+// -- the CSC and the CSR copy of X as section 22 stores a sparse view: 24 bytes per stored entry plus the pointers.
+struct F64BisilSparsePlan {
+  F64BisilPlan dense;
+  size_t rank = 0, cptr = 0, cval = 0, cidx = 0, rptr = 0, rval = 0, ridx = 0, total = 0;   // offsets, and the size of the buffer
+  size_t copies_dbl = 0;                                                                   // of them the two sparse copies
+};
+inline void f64_bisil_sparse_plan(int n, int m, int k, unsigned long long active, const int n_u[2], const int* const cnt[2],
+                                  size_t meta_words, size_t nnz, F64BisilSparsePlan& p) {
+  p = F64BisilSparsePlan();
+  f64_bisil_plan(n, m, k, active, n_u, cnt, meta_words, false, p.dense);
+  const size_t idx_dbl = (nnz + 1) / 2;
+  size_t off = p.dense.total;
+  p.rank = off; off += ((size_t)n + (size_t)m + 1) / 2;
+  p.cptr = off; off += (size_t)m + 1;
+  p.cval = off; off += nnz;
+  p.cidx = off; off += idx_dbl;
+  p.rptr = off; off += (size_t)n + 1;
+  p.rval = off; off += nnz;
+  p.ridx = off; off += idx_dbl;
+  p.total = off;
+  p.copies_dbl = p.total - p.cptr;
 }
 
 #endif

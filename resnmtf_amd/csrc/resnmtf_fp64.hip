@@ -12,7 +12,9 @@
 //
 // resnmtf_fp64_bisil (section 26), at the end of the file, scores a result in double precision: its kernels are
 // resnmtf_fp64_bisil.hip.inc, its index lists, chunk rule and workspace resnmtf_bisil_plan.h (plain C++, shared with the
-// main unit's resnmtf_bisil), its owner F64BisilRun.
+// main unit's resnmtf_bisil), its owner F64BisilRun.  resnmtf_fp64_bisil_sparse (section 29), right after it, scores a
+// sparse view through the same launches (fp64_bisil_enqueue, its gather step a parameter): its one kernel is
+// resnmtf_fp64_bisil_sparse.hip.inc, its rank tables and workspace resnmtf_bisil_plan.h.
 //
 // resnmtf_fp64_shuffle (section 27), after it, draws shuffle_view of a view in double precision: its kernels are
 // resnmtf_fp64_shuffle.hip.inc, its permutation resnmtf_feistel.h (plain C++, shared with the main unit's shuffles), its
@@ -41,6 +43,7 @@
 #include "resnmtf_fp64_sparse_device.hip.inc"
 #include "resnmtf_bisil_plan.h"
 #include "resnmtf_fp64_bisil.hip.inc"
+#include "resnmtf_fp64_bisil_sparse.hip.inc"
 #include "resnmtf_feistel.h"
 #include "resnmtf_fp64_shuffle_job.h"
 #include "resnmtf_fp64_shuffle.hip.inc"
@@ -230,7 +233,7 @@ std::string fp64_check_sparse_device_pointers(int device_id, const resnmtf_group
 // allocation, a refusal leaves RESNMTF_ERR_ALLOC's text and nullptr; everything still held is freed on the way out.
 class F64Transient {
  public:
-  F64Transient() = default;
+  explicit F64Transient(const char* name = "fp64_run") : name_(name) {}   // `name` heads its refusals
   F64Transient(const F64Transient&) = delete;
   F64Transient& operator=(const F64Transient&) = delete;
   ~F64Transient() { release_all(); }
@@ -242,7 +245,7 @@ class F64Transient {
     if (e == hipSuccess && bytes <= free_b) e = hipMalloc(&p, bytes);
     if (e != hipSuccess || !p) {
       (void)hipGetLastError();
-      resnmtf_set_create_error("fp64_run: " + std::to_string(bytes) + " bytes asked for (the canonical arrays of a sparse view in device memory), " +
+      resnmtf_set_create_error(std::string(name_) + ": " + std::to_string(bytes) + " bytes asked for (the canonical arrays of a sparse view in device memory), " +
                                std::to_string(free_b) + " free on the device");
       return nullptr;
     }
@@ -267,6 +270,7 @@ class F64Transient {
   }
   void release_sort_storage() { release(sort_storage_); sort_storage_ = nullptr; }
  private:
+  const char* name_;
   std::vector<void*> held_;
   void* sort_storage_ = nullptr;
 };
@@ -283,9 +287,9 @@ struct F64SpdView {
 // reduced on the device; `sh` as fp64_check_csc fills it for the same canonical CSC.  Peak transient memory: five 8-byte
 // arrays of nnz, two 4-byte ones, the two pointer arrays, 24 bytes of flags and rocPRIM's storage; on return the two
 // key arrays, the spare payload array and that storage are free again.  RESNMTF_OK, or the code to return with the
-// error text set.
+// error text set; `name` heads the texts of runtime failures.
 int fp64_build_sparse_device_view(hipStream_t st, F64Transient& tr, int v, const resnmtf_fp64_sparse_device_view& c, int n, int m,
-                                  F64SpdView& out, F64SparseShape& sh) {
+                                  F64SpdView& out, F64SparseShape& sh, const char* name = "fp64_run") {
   resnmtf_sparse_device_build b{};
   b.layout = c.layout; b.index_type = c.index_type; b.dtype = c.dtype; b.n = n; b.m = m; b.nnz = c.nnz;
   b.ptr_or_rows = c.ptr_or_rows; b.idx_or_cols = c.idx_or_cols; b.values = c.values;
@@ -304,7 +308,7 @@ int fp64_build_sparse_device_view(hipStream_t st, F64Transient& tr, int v, const
   std::string why;
   const int rc = resnmtf_sparse_device_canonical(st, b, &F64Transient::alloc, &tr, why);
   if (rc == RESNMTF_ERR_INVALID) resnmtf_set_create_error("view " + std::to_string(v) + ": " + why);
-  if (rc == RESNMTF_ERR_HIP) resnmtf_set_create_error("fp64_run: view " + std::to_string(v) + ": " + why);
+  if (rc == RESNMTF_ERR_HIP) resnmtf_set_create_error(std::string(name) + ": view " + std::to_string(v) + ": " + why);
   if (rc != RESNMTF_OK) return rc;
   sh.nnz = nnz; sh.longest_row = sh.longest_col = 0;
   if (nnz == 0) return RESNMTF_OK;           // (zero pointers: the zeros of the job's buffer)
@@ -317,7 +321,7 @@ int fp64_build_sparse_device_view(hipStream_t st, F64Transient& tr, int v, const
   if (e == hipSuccess) e = hipMemcpyAsync(host_longest, longest, sizeof(host_longest), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) {
-    resnmtf_set_create_error(std::string("fp64_run: view ") + std::to_string(v) + ": " + hipGetErrorString(e));
+    resnmtf_set_create_error(std::string(name) + ": view " + std::to_string(v) + ": " + hipGetErrorString(e));
     return RESNMTF_ERR_HIP;
   }
   sh.longest_row = host_longest[0]; sh.longest_col = host_longest[1];
@@ -543,43 +547,53 @@ int fp64_allocate(F64Job& J, F64Run& run) {
   return e == hipSuccess ? RESNMTF_OK : run.fail(e);
 }
 
+// where the CSC and the CSR copy of a sparse view lie in a device buffer, in doubles from its start (section 22's storage)
+struct F64SparseAt { size_t cptr, cval, cidx, rptr, rval, ridx; };
+
+// a checked host CSC (n x m, nnz entries) into `buf`: the CSC arrays as given, and the CSR copy built here; blocking copies
+hipError_t fp64_upload_host_csc(double* buf, const F64SparseAt& at, int n, int m, size_t nnz, const resnmtf_fp64_sparse_view& c) {
+  std::vector<long long> rp;
+  std::vector<int> ci;
+  std::vector<double> rv;
+  fp64_csr_from_csc(n, m, c.col_ptr, c.row_idx, c.values, rp, ci, rv);
+  hipError_t e = hipMemcpy(buf + at.cptr, c.col_ptr, ((size_t)m + 1) * sizeof(long long), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(buf + at.rptr, rp.data(), rp.size() * sizeof(long long), hipMemcpyHostToDevice);
+  if (nnz > 0) {
+    if (e == hipSuccess) e = hipMemcpy(buf + at.cval, c.values, nnz * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + at.cidx, c.row_idx, nnz * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + at.rval, rv.data(), nnz * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + at.ridx, ci.data(), nnz * sizeof(int), hipMemcpyHostToDevice);
+  }
+  return e;
+}
+
+// the canonical arrays of a sparse device view (section 24; nnz >= 1) into `buf`, device to device on `st`, the CSR values
+// gathered in fp64
+hipError_t fp64_copy_spd_view(hipStream_t st, double* buf, const F64SparseAt& at, int n, int m, size_t nnz, const F64SpdView& c) {
+  hipError_t e = hipMemcpyAsync(buf + at.cptr, c.cptr, ((size_t)m + 1) * sizeof(long long), hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(buf + at.rptr, c.rptr, ((size_t)n + 1) * sizeof(long long), hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(buf + at.cval, c.cval, nnz * sizeof(double), hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(buf + at.cidx, c.cidx, nnz * sizeof(int), hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(buf + at.ridx, c.ridx, nnz * sizeof(int), hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) {
+    fp64_spd_gather(st, c.perm, c.cval, (long long)nnz, buf + at.rval);
+    e = hipGetLastError();
+  }
+  return e;
+}
+
 // view v into the buffer, by where it comes from (`img`: the staging vector of the host dense views)
 hipError_t fp64_upload_view(const F64Job& J, F64Run& run, int v, std::vector<double>& img) {
   const F64View& w = J.L.vw[v];
   double* buf = run.buf;
   hipStream_t st = run.st;
   hipError_t e = hipSuccess;
+  const F64SparseAt at{w.cptr, w.cval, w.cidx, w.rptr, w.rval, w.ridx};
   switch (w.src) {
-    case F64Source::DeviceSparse: {         // from device memory (section 24): the canonical arrays device to device, the
-      const F64SpdView& c = run.spdv[v];    // CSR values gathered in fp64; nnz = 0: the zeros of the memset are the view
-      if (w.nnz == 0) return e;
-      e = hipMemcpyAsync(buf + w.cptr, c.cptr, ((size_t)w.m + 1) * sizeof(long long), hipMemcpyDeviceToDevice, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(buf + w.rptr, c.rptr, ((size_t)w.n + 1) * sizeof(long long), hipMemcpyDeviceToDevice, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(buf + w.cval, c.cval, w.nnz * sizeof(double), hipMemcpyDeviceToDevice, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(buf + w.cidx, c.cidx, w.nnz * sizeof(int), hipMemcpyDeviceToDevice, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(buf + w.ridx, c.ridx, w.nnz * sizeof(int), hipMemcpyDeviceToDevice, st);
-      if (e == hipSuccess) {
-        fp64_spd_gather(st, c.perm, c.cval, (long long)w.nnz, buf + w.rval);
-        e = hipGetLastError();
-      }
-      return e;
-    }
-    case F64Source::HostCsc: {              // the CSC arrays as given, and the CSR copy built here
-      const resnmtf_fp64_sparse_view& c = J.sp->view[v];
-      std::vector<long long> rp;
-      std::vector<int> ci;
-      std::vector<double> rv;
-      fp64_csr_from_csc(w.n, w.m, c.col_ptr, c.row_idx, c.values, rp, ci, rv);
-      e = hipMemcpy(buf + w.cptr, c.col_ptr, ((size_t)w.m + 1) * sizeof(long long), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMemcpy(buf + w.rptr, rp.data(), rp.size() * sizeof(long long), hipMemcpyHostToDevice);
-      if (w.nnz > 0) {
-        if (e == hipSuccess) e = hipMemcpy(buf + w.cval, c.values, w.nnz * sizeof(double), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(buf + w.cidx, c.row_idx, w.nnz * sizeof(int), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(buf + w.rval, rv.data(), w.nnz * sizeof(double), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(buf + w.ridx, ci.data(), w.nnz * sizeof(int), hipMemcpyHostToDevice);
-      }
-      return e;
-    }
+    case F64Source::DeviceSparse:           // from device memory (section 24); nnz = 0: the zeros of the memset are the view
+      return w.nnz == 0 ? e : fp64_copy_spd_view(st, buf, at, w.n, w.m, w.nnz, run.spdv[v]);
+    case F64Source::HostCsc:                // the CSC arrays as given, and the CSR copy built here
+      return fp64_upload_host_csc(buf, at, w.n, w.m, w.nnz, J.sp->view[v]);
     case F64Source::DeviceDense:            // from device memory: one read, both images, no staging (section 23)
       fp64_images(st, J.dev->x[v], w.n, w.m, buf + w.x, w.ldn, buf + w.xt, w.ldm);
       return hipGetLastError();
@@ -829,8 +843,11 @@ class F64BisilRun {
   double* buf = nullptr;
 };
 
-// the launches of every side and active bicluster on the run's stream
-hipError_t fp64_bisil_enqueue(hipStream_t st, const resnmtf_device_matrix& x, int n, int m, int k, int metric,
+// the launches of every side and active bicluster on the run's stream.  gather(sd, feat, nf, upts, n_u, upad, G) enqueues
+// what fills the restricted block G of side sd -- the gather of a dense X (resnmtf_fp64_bisil), the zero-fill and scatter
+// of a sparse one (resnmtf_fp64_bisil_sparse) -- and returns the runtime's answer; the rest is one text for both.
+template <class Gather>
+hipError_t fp64_bisil_enqueue(hipStream_t st, Gather&& gather, int n, int m, int k, int metric,
                               const BisilHostLists& L, const F64BisilPlan& plan, const F64BisilMeta& M, double* buf) {
   double* G = buf;
   double* norm2 = buf + plan.norm2;
@@ -851,7 +868,7 @@ hipError_t fp64_bisil_enqueue(hipStream_t st, const resnmtf_device_matrix& x, in
       const int nf = L.side[1 - sd].cnt[j], n_mem = s.cnt[j];
       const int* feat = dints + M.feat[sd][j];
       const int* mpos = dints + M.mpos[sd][j];
-      fp64_bisil_gather(st, x, sd, feat, nf, upts, n_u, upad, G);
+      if ((e = gather(sd, feat, nf, upts, n_u, upad, G)) != hipSuccess) break;
       if (metric == F64_BISIL_COSINE)
         hipLaunchKernelGGL(fp64_bisil_norm_kernel, dim3((upad + 255) / 256), dim3(256), 0, st, (const double*)G, nf, upad, norm2);
       const dim3 grid((n_mem + F64_BISIL_TILE - 1) / F64_BISIL_TILE, plan.chunks[sd][j]);
@@ -938,7 +955,11 @@ int resnmtf_fp64_bisil(int device_id, const resnmtf_fp64_bisil_job* job) {
   const size_t sil_dbl = (size_t)n * k + (size_t)m * k;
   if (e == hipSuccess) e = hipMemcpyAsync(run.buf + plan.meta, M.words.data(), M.words.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, run.st);
   if (e == hipSuccess) e = hipMemsetAsync(run.buf + plan.sil, 0, sil_dbl * sizeof(double), run.st);
-  if (e == hipSuccess) e = fp64_bisil_enqueue(run.st, x, n, m, k, metric, L, plan, M, run.buf);
+  auto gather = [&](int sd, const int* feat, int nf, const int* upts, int n_u, int upad, double* G) {
+    fp64_bisil_gather(run.st, x, sd, feat, nf, upts, n_u, upad, G);
+    return hipSuccess;
+  };
+  if (e == hipSuccess) e = fp64_bisil_enqueue(run.st, gather, n, m, k, metric, L, plan, M, run.buf);
   if (e == hipSuccess) e = hipMemcpyAsync(job->row_sil, run.buf + plan.sil, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, run.st);
   if (e == hipSuccess) e = hipMemcpyAsync(job->col_sil, run.buf + plan.sil + (size_t)n * k, (size_t)m * k * sizeof(double), hipMemcpyDeviceToHost, run.st);
   if (e == hipSuccess) e = hipStreamSynchronize(run.st);
@@ -955,6 +976,118 @@ int resnmtf_fp64_bisil_plan(int n_u, int n_mem, int k, long long row_stride, lon
                                                   f64_bisil_side_form(1, row_stride, col_stride)};
   std::memcpy(out, vals, sizeof(vals));
   return RESNMTF_OK;
+}
+
+// ---- resnmtf_fp64_bisil_sparse: the same silhouettes of a view stored sparse ----
+int resnmtf_fp64_bisil_sparse(int device_id, const resnmtf_fp64_bisil_sparse_job* job) {
+  static const char* const NAME = "fp64_bisil_sparse";
+  if (!job) return fp64_bad("job is NULL");
+  if (job->struct_size != (int)sizeof(resnmtf_fp64_bisil_sparse_job)) return fp64_bad("resnmtf_fp64_bisil_sparse_job struct_size mismatch");
+  const int n = job->n, m = job->m, k = job->k, metric = job->metric;
+  if (k < 1 || k > RESNMTF_MAX_K) return fp64_bad("k must be in [1, 64]");
+  if (n < 1 || m < 1) return fp64_bad("view dimensions must be positive");
+  if (metric < F64_BISIL_EUCLIDEAN || metric > F64_BISIL_COSINE)
+    return fp64_bad("metric must be 0 (euclidean), 1 (manhattan) or 2 (cosine)");
+  const bool host_x = job->x.col_ptr != nullptr;
+  if (host_x == fp64_spd_given(job->x_dev))
+    return fp64_bad(host_x ? "X is given in two places (job->x and job->x_dev)" : "X is given in no place (job->x or job->x_dev)");
+  if (!job->row_clusters || !job->col_clusters || !job->row_sil || !job->col_sil)
+    return fp64_bad("row_clusters / col_clusters / row_sil / col_sil are NULL");
+  // the view's own refusals are those of view 0 of a one-view run, through the run's checks and with their texts
+  F64SparseShape shape;
+  resnmtf_fp64_sparse_device spd{};
+  if (host_x) {
+    if (!job->x.values) return fp64_bad("view 0: values is NULL");
+    const std::string why = fp64_check_csc(n, m, job->x.col_ptr, job->x.row_idx, job->x.values, shape);
+    if (!why.empty()) return fp64_bad("view 0: " + why);
+  } else {
+    resnmtf_group_job one{};
+    one.struct_size = (int)sizeof(resnmtf_group_job);
+    one.n_views = 1; one.k = k; one.n_rows[0] = n; one.n_cols[0] = m;
+    spd.struct_size = (int)sizeof(resnmtf_fp64_sparse_device);
+    spd.stream = job->stream;
+    spd.view[0] = job->x_dev;
+    F64Source src[RESNMTF_GROUP_MAX_VIEWS];
+    fp64_resolve_sources(nullptr, nullptr, &spd, src);
+    std::string why = fp64_check_sparse_device_struct(one, nullptr, nullptr, spd);
+    if (why.empty()) why = fp64_check_sparse_device_pointers(device_id, one, spd, src);
+    if (!why.empty()) return fp64_bad(why);
+    shape.nnz = (size_t)job->x_dev.nnz;
+  }
+  BisilHostLists L;
+  if (const int which = bisil_build_lists(n, m, k, job->row_clusters, job->col_clusters, L))
+    return fp64_bad(which == 1 ? "row_clusters entries must be 0 or 1" : "col_clusters entries must be 0 or 1");
+  if (!L.active) {
+    std::fill(job->row_sil, job->row_sil + (size_t)n * k, 0.0);
+    std::fill(job->col_sil, job->col_sil + (size_t)m * k, 0.0);
+    return RESNMTF_OK;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { resnmtf_set_create_error("no HIP device"); return RESNMTF_ERR_NO_DEVICE; }
+  if (device_id < 0 || device_id >= ndev) return fp64_bad("device_id out of range");
+  // (declared before the run: what the stream may still read is released after the run has waited for it)
+  F64BisilMeta M;
+  std::vector<int> rank;
+  F64Transient transient(NAME);
+  F64BisilRun run;
+  hipError_t e = hipSetDevice(device_id);
+  if (e != hipSuccess) return run.fail(e, "hipSetDevice: ");
+  // the workspace, sized before anything is allocated
+  f64_bisil_pack(k, L, M);
+  f64_bisil_ranks(L, rank);
+  const int n_u[2] = {(int)L.side[0].upts.size(), (int)L.side[1].upts.size()};
+  const int* const cnt[2] = {L.side[0].cnt.data(), L.side[1].cnt.data()};
+  F64BisilSparsePlan plan;
+  f64_bisil_sparse_plan(n, m, k, L.active, n_u, cnt, M.words.size(), shape.nnz, plan);
+  const size_t nnz = shape.nnz, bytes = plan.total * sizeof(double);
+  size_t free_b = 0, total_b = 0;
+  if ((e = hipMemGetInfo(&free_b, &total_b)) != hipSuccess) return run.fail(e, "fp64_bisil_sparse: ");
+  if (bytes > free_b) {
+    resnmtf_set_create_error("fp64_bisil_sparse workspace: " + std::to_string(bytes) + " bytes asked for (" +
+                             std::to_string(plan.dense.g_dbl * sizeof(double)) + " of them the restricted block, features x padded members, " +
+                             std::to_string(plan.copies_dbl * sizeof(double)) + " the CSC and CSR copies of X), " +
+                             std::to_string(free_b) + " free on the device");
+    return RESNMTF_ERR_ALLOC;
+  }
+  if ((e = hipStreamCreateWithFlags(&run.st, hipStreamNonBlocking)) != hipSuccess) { run.st = nullptr; return run.fail(e, "hipStreamCreate: "); }
+  // a device view: checked and sorted on the device before anything is scattered (the failure word is read back and
+  // the stream synchronised inside); its canonical arrays wait in transient memory for the buffer
+  F64SpdView dv;
+  if (!host_x) {
+    if ((e = wait_for_caller(run.st, job->stream)) != hipSuccess) return run.fail(e, "fp64_bisil_sparse: ");
+    const int rc = fp64_build_sparse_device_view(run.st, transient, 0, job->x_dev, n, m, dv, shape, NAME);
+    if (rc != RESNMTF_OK) return rc;
+  }
+  void* p = nullptr;
+  if ((e = hipMalloc(&p, bytes)) != hipSuccess) {
+    (void)hipGetLastError();
+    resnmtf_set_create_error(std::string("fp64_bisil_sparse workspace: ") + hipGetErrorString(e) + " (" + std::to_string(bytes) + " bytes asked for)");
+    return e == hipErrorOutOfMemory ? RESNMTF_ERR_ALLOC : RESNMTF_ERR_HIP;
+  }
+  run.buf = static_cast<double*>(p);
+  double* buf = run.buf;
+  hipStream_t st = run.st;
+  // the two sparse copies into the buffer, as a run stores them (no stored entry: all pointers zero, nothing to scatter)
+  const F64SparseAt at{plan.cptr, plan.cval, plan.cidx, plan.rptr, plan.rval, plan.ridx};
+  if (nnz == 0) e = hipMemsetAsync(buf + plan.cptr, 0, plan.copies_dbl * sizeof(double), st);
+  else if (host_x) e = fp64_upload_host_csc(buf, at, n, m, nnz, job->x);
+  else e = fp64_copy_spd_view(st, buf, at, n, m, nnz, dv);
+  const size_t sil_dbl = (size_t)n * k + (size_t)m * k;
+  if (e == hipSuccess) e = hipMemcpyAsync(buf + plan.dense.meta, M.words.data(), M.words.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(buf + plan.rank, rank.data(), rank.size() * sizeof(int), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(buf + plan.dense.sil, 0, sil_dbl * sizeof(double), st);
+  // side 0 (points = rows): the features are columns, read from the CSC; side 1: rows of the CSR
+  const int* drank = reinterpret_cast<const int*>(buf + plan.rank);
+  auto scatter = [&](int sd, const int* feat, int nf, const int*, int, int upad, double* G) {
+    return fp64_bisil_scatter(st, reinterpret_cast<const long long*>(buf + (sd == 0 ? plan.cptr : plan.rptr)),
+                              reinterpret_cast<const int*>(buf + (sd == 0 ? plan.cidx : plan.ridx)),
+                              buf + (sd == 0 ? plan.cval : plan.rval), feat, nf, drank + (sd == 0 ? 0 : n), upad, G);
+  };
+  if (e == hipSuccess) e = fp64_bisil_enqueue(st, scatter, n, m, k, metric, L, plan.dense, M, buf);
+  if (e == hipSuccess) e = hipMemcpyAsync(job->row_sil, buf + plan.dense.sil, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(job->col_sil, buf + plan.dense.sil + (size_t)n * k, (size_t)m * k * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  return e == hipSuccess ? RESNMTF_OK : run.fail(e, "fp64_bisil_sparse: ");
 }
 
 }  // extern "C"

@@ -150,11 +150,15 @@ def _fill_fp64_sparse_device(spd, v: int, x, q: int, keep: list):
     """The sparse view ``x`` (a checked ``device_views.SparseDeviceView``) into entry ``v`` of the
     ``resnmtf_fp64_sparse_device`` ``spd``: the addresses of its own index and value arrays
     (``device_views.sparse_tensor_parts``), ``.contiguous()`` only on a piece that is not."""
+    _fill_sparse_device_view(spd.view[v], x, f"problem {q}, view {v}: data", keep)
+
+
+def _fill_sparse_device_view(c, x, what: str, keep: list):
+    """One ``resnmtf_fp64_sparse_device_view`` (``c``) from the checked ``SparseDeviceView`` ``x``."""
     t = x.tensor.detach()
-    dtype = _dtype_code(t, f"problem {q}, view {v}: data")
+    dtype = _dtype_code(t, what)
     a, b, vals = (piece if piece.is_contiguous() else piece.contiguous() for piece in _device_views.sparse_tensor_parts(t))
     keep.extend([t, a, b, vals])
-    c = spd.view[v]
     c.layout, c.dtype = _LAYOUT_CODES[str(t.layout)], dtype
     c.index_type = _lib.INDEX_I64 if str(a.dtype) == "torch.int64" else _lib.INDEX_I32
     c.ptr_or_rows, c.idx_or_cols, c.values, c.nnz = a.data_ptr(), b.data_ptr(), vals.data_ptr(), int(t._nnz())
@@ -410,6 +414,69 @@ def fp64_bisil(x, rc, cc, distance: str = "euclidean", device_id: int = 0):
         job.x = _dp(x)
     job.row_clusters, job.col_clusters, job.row_sil, job.col_sil = _dp(rc), _dp(cc), _dp(rs), _dp(cs)
     code = lib.resnmtf_fp64_bisil(int(device_id), C.byref(job))
+    if code != _lib.OK:
+        raise ResnmtfError(code, (lib.resnmtf_last_error(None) or b"").decode())
+    return rs, cs
+
+
+def _fp64_bisil_sparse_job(x, n: int, m: int, device_id: int, keep: list) -> _lib.Fp64BisilSparseJob:
+    """The ``resnmtf_fp64_bisil_sparse_job`` of the sparse view ``x`` with its one place for X filled: a canonical
+    ``scipy.sparse`` CSC as the host arrays ``job.x`` (``job.x_dev`` all zero), a checked ``SparseDeviceView`` as
+    ``job.x_dev`` -- the addresses of the tensor's own index and value arrays, ``job.x`` NULL: nothing of it comes to the
+    host -- and ``job.stream`` = torch's current stream.  ``keep`` collects what the struct points into."""
+    job = _lib.Fp64BisilSparseJob()
+    job.struct_size = C.sizeof(job)
+    job.n, job.m = n, m
+    if isinstance(x, _device_views.SparseDeviceView):
+        import torch                # (lazily: nothing else in this module needs it)
+        _fill_sparse_device_view(job.x_dev, x, "fp64_bisil_sparse: x", keep)
+        job.stream = torch.cuda.current_stream(torch.device("cuda", int(device_id))).cuda_stream
+        return job
+    csc = [np.ascontiguousarray(x.indptr, dtype=np.int64), np.ascontiguousarray(x.indices, dtype=np.int32),
+           np.ascontiguousarray(x.data, dtype=np.float64)]
+    if csc[1].size == 0:            # (never a NULL pointer)
+        csc[1], csc[2] = np.zeros(1, dtype=np.int32), np.zeros(1)
+    keep.extend(csc)
+    job.x.col_ptr = csc[0].ctypes.data_as(C.POINTER(C.c_longlong))
+    job.x.row_idx, job.x.values = _ip(csc[1]), _dp(csc[2])
+    return job
+
+
+def fp64_bisil_sparse(x, rc, cc, distance: str = "euclidean", device_id: int = 0):
+    """``fp64_bisil`` of a SPARSE view (``resnmtf_fp64_bisil_sparse``, no handle): the same
+    ``(row_sil, col_sil)``, bit for bit ``fp64_bisil`` of the densified view, without the n x m fp64 matrix -- on the
+    device the view is a CSC and a CSR copy (24 bytes per stored entry) and per bicluster the restricted block is
+    zero-filled and scattered into.  ``x``: a ``scipy.sparse`` matrix (a CPU sparse tensor is taken as its SciPy matrix),
+    made canonical with ``sparse.canonical_csc`` (a copy; duplicates summed, explicit zeros dropped) and taken as
+    pre-processed -- a negative or non-finite value is refused (``ValueError``, ``sparse.validate``'s texts), an all-zero
+    column is not: the score of a sub-sample or of an empty view is defined --; or a 2-D ``sparse_csc`` / ``sparse_csr`` /
+    coalesced ``sparse_coo`` tensor on ``cuda:device_id`` (or its ``device_views.SparseDeviceView``), read where it lies
+    on torch's current stream: checked and sorted on the device, explicit zeros kept, nothing of it brought to the host.
+    A dense view is a ``ValueError`` (``fp64_bisil`` takes those).  ``rc`` / ``cc`` and the refusals as ``fp64_bisil``."""
+    from .bisil import METRICS
+    if distance not in METRICS:
+        raise ValueError("distance must be one of 'euclidean', 'manhattan' or 'cosine'.")
+    lib = _lib.load()
+    x = _device_views.host_or_device(x, "fp64_bisil_sparse: x")
+    if _device_views.is_sparse_device_view(x):
+        x = _device_views.as_sparse_view(x, device_id, "fp64_bisil_sparse: x")
+    elif _sparse.is_sparse(x):
+        x = _sparse.canonical_csc(x)
+        _sparse.validate_values(x, "view")
+    else:
+        raise ValueError("fp64_bisil_sparse scores sparse views (scipy.sparse, or a sparse torch tensor): fp64_bisil takes a dense one")
+    n, m = int(x.shape[0]), int(x.shape[1])
+    rc = np.asfortranarray(np.asarray(_device_views.to_numpy(rc), dtype=np.float64))
+    if rc.ndim != 2 or rc.shape[0] != n:
+        raise ValueError(f"row clusters must be {n} x k")
+    cc = _f64_colmajor(_device_views.to_numpy(cc), (m, rc.shape[1]))
+    k = int(rc.shape[1])
+    rs = np.zeros((n, k), order="F"); cs = np.zeros((m, k), order="F")
+    keep = []
+    job = _fp64_bisil_sparse_job(x, n, m, device_id, keep)
+    job.k, job.metric = k, METRICS[distance]
+    job.row_clusters, job.col_clusters, job.row_sil, job.col_sil = _dp(rc), _dp(cc), _dp(rs), _dp(cs)
+    code = lib.resnmtf_fp64_bisil_sparse(int(device_id), C.byref(job))
     if code != _lib.OK:
         raise ResnmtfError(code, (lib.resnmtf_last_error(None) or b"").decode())
     return rs, cs

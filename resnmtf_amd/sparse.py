@@ -37,14 +37,20 @@ def validate(x, what: str = "view") -> None:
     """The checks of ``resnmtf_set_view_csc`` on the host, before any device work: no negative or non-finite entry (the
     per-column shift of ``make_non_neg``, ``R/utils.r:20-27``, would turn every implicit zero positive) and no all-zero
     column (``matrix_normalisation``, ``R/utils.r:86-88``, would divide it by zero: a NaN column in the reference)."""
+    validate_values(x, what)
+    if (np.diff(x.indptr) == 0).any():
+        raise ValueError(f"sparse {what} has an all-zero column: matrix_normalisation (R/utils.r:86-88) would divide it "
+                         "by zero.")
+
+
+def validate_values(x, what: str = "view") -> None:
+    """The part of ``validate`` that holds for a view that is already pre-processed (a sub-sample, a view to be scored):
+    no negative or non-finite entry; an all-zero column is fine there."""
     if not np.isfinite(x.data).all():
         raise ValueError(f"sparse {what} has a non-finite entry.")
     if (x.data < 0).any():
         raise ValueError(f"sparse {what} has a negative entry: the non-negativity shift of make_non_neg (R/utils.r:20-27) "
                          "would turn every implicit zero positive; shift the data and pass it dense.")
-    if (np.diff(x.indptr) == 0).any():
-        raise ValueError(f"sparse {what} has an all-zero column: matrix_normalisation (R/utils.r:86-88) would divide it "
-                         "by zero.")
 
 
 def check_data_one(x):
