@@ -1161,6 +1161,63 @@ typedef struct resnmtf_fp64_shuffle_job {
 int resnmtf_fp64_shuffle(int device_id, const resnmtf_fp64_shuffle_job* job);
 
 /*
+ * shuffle_view (R/obtain_bicl.r:11-22) of one SPARSE view in DOUBLE precision, without a handle:
+ * resnmtf_fp64_shuffle's draw of a view that is stored sparse, made of its stored entries alone -- no n x m array exists
+ * at any point.  Blocking.
+ *   n, m, seed    as in resnmtf_fp64_shuffle_job: a stored entry at (r, c) with value x lands at
+ *                 i = feistel_perm_inverse(r m + c, n m, seed) (csrc/resnmtf_feistel.h), that is column i / n, row i % n,
+ *                 with the value x widened to fp64.  Explicit zeros stay stored; the draw holds exactly the source's nnz
+ *                 entries.  Positions and values are bit for bit the CSC of resnmtf_fp64_shuffle(normalise = 0) of the
+ *                 densified view read at those positions (that draw is +0.0 everywhere else), and on values fp32 holds the
+ *                 structure and values of resnmtf_shuffle_view_sparse for the same seed.
+ *   x             the view in host memory: the 0-based canonical CSC of the pre-processed view, as resnmtf_fp64_run_sparse
+ *                 takes it (col_ptr NULL when not given); or
+ *   x_dev, stream the view in device memory, as resnmtf_fp64_run_sparse_device takes it: CSC, CSR or coalesced COO, int32 or
+ *                 int64 indices, fp64 / fp32 / fp16 / bf16 values, entries in any order (all seven fields zero when not
+ *                 given), read where it lies after an event recorded on `stream`.  X is given in exactly one place.
+ *   out_col_ptr, out_row_idx, out_values   device memory of device_id owned by the caller: m + 1 int64, nnz int64 and nnz
+ *                 doubles, the canonical CSC of the draw (rows ascending within a column) -- what torch.sparse_csc_tensor
+ *                 wraps and what resnmtf_fp64_run_sparse_device reads without its first sort.  Written after the same
+ *                 event, complete when the call returns.  out_row_idx / out_values may be NULL when nnz = 0.
+ *   n_empty_rows, n_empty_cols   (host, not NULL) the rows / columns of the draw that hold no stored entry > 0.  The
+ *                 values are non-negative, so these are the lines that sum to exactly 0.0: the counts and masks
+ *                 resnmtf_fp64_shuffle reports on the densified view.  The caller redraws; the library does not loop.
+ *   row_mask, col_mask           (host, n and m bytes, or NULL) 1 where a line is empty.
+ *   normalise     != 0: out_values[e] = (x + 0.0) / colsum[c] in fp64, colsum[c] summed over the stored entries of the
+ *                 column in fp64_shuffle_stats_kernel's order (lane t of 256 adds the entries whose row is = t mod 256 in
+ *                 ascending row order from 0.0, then the 256-wide tree).  The absent +0.0 entries change no bit of a
+ *                 non-negative sum and the shift of a non-negative column is 0, so the values are bit for bit those of
+ *                 resnmtf_fp64_shuffle(normalise = 1) of the densified view at the stored positions whenever that draw has
+ *                 no empty column; in an empty column a stored zero gives 0 / 0 = NaN, as there.  (The f32 route,
+ *                 resnmtf_shuffle_view_sparse, sums a column in plain entry order: against it the normalised values agree
+ *                 to f32 rounding only.)
+ * No floating-point atomics: two calls give equal bits (integer atomics for the two counts alone).  A view without a
+ * stored entry: zero pointers, every line empty, nothing of size zero is launched.
+ * Transient device memory: 68 bytes per stored entry at its peak plus the pointers and masks, sized
+ * first and refused with RESNMTF_ERR_ALLOC and its byte count when it exceeds the free device memory.
+ * Refused before any device work (RESNMTF_ERR_INVALID, text in resnmtf_last_error(NULL)), nothing written: what
+ * resnmtf_fp64_shuffle refuses, with its texts where the condition is the same -- job NULL, a struct_size mismatch, n or m
+ * below 1, n m above 2^62, X in both places or in neither, NULL outputs or counts, device_id out of range, an output that is
+ * not memory of device_id or too short, outputs that overlap each other or x_dev's arrays --; for a host view what
+ * resnmtf_fp64_run_sparse refuses of view 0, for a device view what resnmtf_fp64_run_sparse_device refuses of view 0, with
+ * their texts (the device checks -- bad pointers, an index out of range, a non-finite or negative value, a position stored
+ * twice -- run before any output is written).
+ */
+typedef struct resnmtf_fp64_shuffle_sparse_job {
+  int struct_size;                          /* sizeof the struct */
+  int n, m, normalise;
+  unsigned long long seed;
+  resnmtf_fp64_sparse_view x;
+  resnmtf_fp64_sparse_device_view x_dev;
+  void* stream;
+  long long *out_col_ptr, *out_row_idx;
+  double* out_values;
+  int *n_empty_rows, *n_empty_cols;
+  unsigned char *row_mask, *col_mask;
+} resnmtf_fp64_shuffle_sparse_job;
+int resnmtf_fp64_shuffle_sparse(int device_id, const resnmtf_fp64_shuffle_sparse_job* job);
+
+/*
  * The sub-sample of stability_repeat (R/stability_analysis.r:124, :184, :232, :238: data[[i]][row_samples, col_samples])
  * of one view in DOUBLE precision, without a handle: out[i, j] = X[rows[i], cols[j]] on the fp64
  * values of X, where resnmtf_subsample_view gathers a handle's fp32 image.  Blocking.

@@ -182,6 +182,17 @@ class Fp64ShuffleJob(C.Structure):
                 ("row_mask", C.POINTER(C.c_ubyte)), ("col_mask", C.POINTER(C.c_ubyte))]
 
 
+class Fp64ShuffleSparseJob(C.Structure):
+    """``resnmtf_fp64_shuffle_sparse_job`` (include/resnmtf_hip.h): the view as host CSC arrays (``x``) or as sparse arrays
+    in device memory (``x_dev`` read after ``stream``), the caller's three device arrays of the draw's canonical CSC and the
+    host outputs of ``resnmtf_fp64_shuffle_sparse``."""
+    _fields_ = [("struct_size", C.c_int), ("n", C.c_int), ("m", C.c_int), ("normalise", C.c_int), ("seed", C.c_ulonglong),
+                ("x", Fp64SparseView), ("x_dev", Fp64SparseDeviceView), ("stream", C.c_void_p),
+                ("out_col_ptr", C.c_void_p), ("out_row_idx", C.c_void_p), ("out_values", C.c_void_p),
+                ("n_empty_rows", _ip), ("n_empty_cols", _ip),
+                ("row_mask", C.POINTER(C.c_ubyte)), ("col_mask", C.POINTER(C.c_ubyte))]
+
+
 FP64_SUBSAMPLE_PLAN_INTS = 6   # RESNMTF_FP64_SUBSAMPLE_PLAN_INTS
 
 
@@ -265,6 +276,7 @@ SIGNATURES = {
     "resnmtf_fp64_bisil_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, _ip]),
     "resnmtf_fp64_bisil_sparse": (C.c_int, [C.c_int, C.POINTER(Fp64BisilSparseJob)]),
     "resnmtf_fp64_shuffle": (C.c_int, [C.c_int, C.POINTER(Fp64ShuffleJob)]),
+    "resnmtf_fp64_shuffle_sparse": (C.c_int, [C.c_int, C.POINTER(Fp64ShuffleSparseJob)]),
     "resnmtf_fp64_subsample": (C.c_int, [C.c_int, C.POINTER(Fp64SubsampleJob)]),
     "resnmtf_fp64_subsample_plan": (C.c_int, [C.c_longlong, C.c_longlong, _ip]),
     "resnmtf_fp64_relevance": (C.c_int, [C.c_int, C.POINTER(Fp64RelevanceJob)]),

@@ -119,7 +119,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
                    sparse_on_device: bool = False, output: str = "numpy", init_lm=None, return_state: bool = False,
                    post_on_device: bool = False, precision: str = "f32", fp64_sparse: bool = False,
                    fp64_device: bool = False, fp64_sparse_device: bool = False, fp64_bisil: bool = False,
-                   fp64_spurious: bool = False, fp64_bisil_sparse: bool = False):
+                   fp64_spurious: bool = False, fp64_bisil_sparse: bool = False, fp64_shuffle_sparse: bool = False):
     """``res_nmtf_inner`` (``R/main.r:32-140``).
 
     ``data``: list of pre-processed (non-negative, column-normalised) matrices; ``row_indices[v][w]``
@@ -253,6 +253,12 @@ def res_nmtf_inner(data, row_indices, column_indices,
     res_nmtf_inner(..., precision="fp64", spurious=False, seed=seed), num_repeats, seed=seed, precision="fp64")``.  A
     sparse view with it is refused by name (no fp64 sparse shuffle exists).  Without the flag every
     refusal above stands word for word.
+    ``fp64_shuffle_sparse`` (keyword-only opt-in; read only with ``precision="fp64"`` and
+    ``fp64_spurious=True``, a no-op everywhere else): the sparse views that ``fp64_sparse`` / ``fp64_sparse_device`` admit
+    are shuffled sparse (``engine.fp64_shuffle_sparse`` -> ``resnmtf_fp64_shuffle_sparse``: the dense draw of the densified
+    view at the stored positions, without densifying it) and the draws factorised as sparse device views; dense views go
+    through ``engine.fp64_shuffle`` as before, and mixed view lists work.  The result equals ``remove_spurious(data, plain
+    result, num_repeats, seed=seed, precision="fp64", fp64_shuffle_sparse=True)``.  Without it the refusal above stands.
     """
     if precision not in ("f32", "fp64"):
         raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
@@ -264,7 +270,8 @@ def res_nmtf_inner(data, row_indices, column_indices,
                                     spurious_on_device=spurious_on_device, output=output, init_lm=init_lm,
                                     return_state=return_state, post_on_device=post_on_device, fp64_sparse=fp64_sparse,
                                     fp64_device=fp64_device, fp64_sparse_device=fp64_sparse_device, fp64_bisil=fp64_bisil,
-                                    fp64_spurious=fp64_spurious, num_repeats=num_repeats, fp64_bisil_sparse=fp64_bisil_sparse)
+                                    fp64_spurious=fp64_spurious, num_repeats=num_repeats, fp64_bisil_sparse=fp64_bisil_sparse,
+                                    fp64_shuffle_sparse=fp64_shuffle_sparse)
     device_views.check_output(output)
     _check_post_on_device(post_on_device, output)
     data = _views(data, device_id)
@@ -359,7 +366,7 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
                          fp64_sparse: bool = False, fp64_device: bool = False, fp64_sparse_device: bool = False,
                          fp64_bisil: bool = False, runner: Optional[Callable] = None, sil: Optional[Callable] = None,
                          fp64_spurious: bool = False, num_repeats=5, checker: Optional[Callable] = None,
-                         fp64_bisil_sparse: bool = False):
+                         fp64_bisil_sparse: bool = False, fp64_shuffle_sparse: bool = False):
     """``res_nmtf_inner(precision="fp64")``: the checks of the f32 call, the refusals of what needs a live handle, the
     initial state, then one ``engine.fp64_run`` (``runner`` replaces it: a test hook).  ``fp64_device``: views, factors
     and results may live in device memory (``res_nmtf_inner``'s docstring); the runner then also gets ``output`` and
@@ -369,7 +376,8 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
     ``fp64_bisil_sparse``: a sparse view then goes to ``engine.fp64_bisil_sparse`` instead of being refused.
     ``fp64_spurious``: ``spurious=True`` with ``spurious_on_device`` is honoured through
     ``spurious.check_biclusters(..., precision="fp64")`` on the views as they arrived (``checker`` replaces it: a test
-    hook), then ``_remove_then_score``."""
+    hook), then ``_remove_then_score``; ``fp64_shuffle_sparse``: a sparse view is then shuffled sparse (section 30) instead
+    of being refused, and the checker gets the flag."""
     def refuse(flag):
         raise NotImplementedError(f'precision="fp64": {flag} needs a live engine handle, which the fp64 path does not '
                                   'keep (it runs through resnmtf_fp64_run); use precision="f32" for it')
@@ -410,7 +418,8 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
     is_sp = [sparse.is_sparse_view(d) for d in data]
     if remove:                                    # (here: spurious_on_device and fp64_spurious are set, or the call was refused)
         _spurious.check_num_repeats(num_repeats)
-        _spurious.refuse_sparse_fp64(data)
+        if not fp64_shuffle_sparse:
+            _spurious.refuse_sparse_fp64(data)
     score = bool(score_bisil) and not no_clusts                  # (here: fp64_bisil is set, or the call was refused above)
     if score and any(is_sp) and not fp64_bisil_sparse:
         raise NotImplementedError(f'precision="fp64": score_bisil with fp64_bisil=True scores dense views only; sparse views '
@@ -488,8 +497,9 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
     rcs, ccs = zip(*[clusters(f, g, s) for f, g, s in zip(out["f"], out["g"], out["s"])])
     check = None
     if remove:                                    # obtain_bicl.r:151-188, on the numbers that were factorised (section 27)
+        flag = {"fp64_shuffle_sparse": True} if fp64_shuffle_sparse else {}      # (only then: every other call is the one it was)
         check = (checker or _spurious.check_biclusters)(data, out["f"], num_repeats, seed=seed, device_id=device_id,
-                                                        max_iters=max_iters, precision="fp64")
+                                                        max_iters=max_iters, precision="fp64", **flag)
     score_fn = None
     if score:                                     # obtain_bicl.r:189-199, on the numbers that were factorised (section 26)
         if sil is None:
@@ -759,7 +769,7 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                   sparse_on_device: bool = False, output: str = "numpy", post_on_device: bool = False,
                   precision: str = "f32", score_bisil: bool = False, fp64_sparse: bool = False, fp64_device: bool = False,
                   fp64_sparse_device: bool = False, fp64_bisil: bool = False, fp64_spurious: bool = False,
-                  fp64_stability: bool = False, fp64_bisil_sparse: bool = False):
+                  fp64_stability: bool = False, fp64_bisil_sparse: bool = False, fp64_shuffle_sparse: bool = False):
     """``apply_resnmtf`` (``R/main.r:214-335``) for a known ``k_val``: naming, shared-name maps, restriction
     symmetrisation, non-negativity shift and column normalisation on the host, then the device loop and -- with
     ``stability=True`` (the default) and ``spurious=False`` -- ``stability_check`` on the pre-processed data, as
@@ -840,7 +850,13 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     through to ``res_nmtf_inner`` -- for the ``k_val`` and for every k of the sweep -- and lifts the refusal of sparse views
     in the fp64 k sweep: ``apply_resnmtf(data, precision="fp64", k_sweep=True, fp64_sparse=True, fp64_bisil_sparse=True,
     spurious=False, stability=False)`` selects k on ``scipy.sparse`` views, every k scored by
-    ``engine.fp64_bisil_sparse``.  Still refused by name: ``fp64_spurious`` and ``fp64_stability`` on a sparse view, and
+    ``engine.fp64_bisil_sparse``.
+    ``fp64_shuffle_sparse=True`` (keyword-only opt-in; read only with ``precision="fp64"`` and
+    ``fp64_spurious=True``, a no-op everywhere else) is passed through in the same way and lifts the refusal of a sparse
+    view with ``fp64_spurious``: ``apply_resnmtf(data, precision="fp64", k_sweep=True, fp64_sparse=True,
+    fp64_bisil_sparse=True, spurious_on_device=True, fp64_spurious=True, fp64_shuffle_sparse=True, stability=False)`` is the
+    reference's default pipeline minus stability on ``scipy.sparse`` views, every k with its own check at ``seed + k``.
+    Still refused by name: ``fp64_spurious`` on a sparse view without that flag, ``fp64_stability`` on a sparse view, and
     views in device memory."""
     if precision not in ("f32", "fp64"):
         raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
@@ -852,7 +868,7 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                            fp64_sparse=fp64_sparse, fp64_device=fp64_device, fp64_sparse_device=fp64_sparse_device,
                            fp64_bisil=fp64_bisil, fp64_spurious=fp64_spurious, spurious_on_device=spurious_on_device,
                            fp64_stability=fp64_stability, remove_unstable=remove_unstable,
-                           fp64_bisil_sparse=fp64_bisil_sparse)
+                           fp64_bisil_sparse=fp64_bisil_sparse, fp64_shuffle_sparse=fp64_shuffle_sparse)
     device_views.check_output(output)
     _check_post_on_device(post_on_device, output)
     on_dev = {"sparse_on_device": True} if sparse_on_device else {}      # (off: every call below is the earlier one)
@@ -902,7 +918,7 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
                 no_clusts, sample_rate, n_stability, stability, stab_thres, *, row_names, col_names, device_id, max_iters,
                 seed, k_sweep, return_sweep, sweep_runner, output, score_bisil, fp64_sparse, fp64_device,
                 fp64_sparse_device, fp64_bisil, fp64_spurious=False, spurious_on_device=False, fp64_stability=False,
-                remove_unstable=True, fp64_bisil_sparse=False):
+                remove_unstable=True, fp64_bisil_sparse=False, fp64_shuffle_sparse=False):
     """``apply_resnmtf(precision="fp64")``: the checks of the f32 function, the refusals of what runs on the f32 engine,
     ``prepare``, then ``res_nmtf_inner(precision="fp64")`` -- once for a ``k_val``, or as ``run(k)`` of ``_sweep`` --, then
     with ``stability`` and ``fp64_stability`` ``stability_check(precision="fp64")`` on the prepared data."""
@@ -936,7 +952,7 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
                           "pass spurious=False")
     if remove:
         _spurious.check_num_repeats(num_repeats)
-        if any(sparse.is_sparse_view(d) for d in data):
+        if any(sparse.is_sparse_view(d) for d in data) and not fp64_shuffle_sparse:
             refuse("a sparse view with fp64_spurious", "no fp64 sparse shuffle exists; pass spurious=False")
     if any(device_views.is_device_view(d) for d in data):
         refuse("a view in device memory", "its shift and column normalisation run at an f32 engine's upload; pass host "
@@ -945,6 +961,8 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
     common = {"device_id": device_id, "max_iters": max_iters, "output": output, "precision": "fp64", **flags}
     if remove:                                    # (only then: without the flag every call is the one it was)
         common.update(spurious_on_device=True, fp64_spurious=True)
+        if fp64_shuffle_sparse:                   # (the same: passed through only when set)
+            common.update(fp64_shuffle_sparse=True)
     if fp64_bisil_sparse:                         # (the same: passed through only when set)
         common.update(fp64_bisil_sparse=True)
 

@@ -20,11 +20,16 @@
 // resnmtf_fp64_shuffle.hip.inc, its permutation resnmtf_feistel.h (plain C++, shared with the main unit's shuffles), its
 // struct checks and workspace resnmtf_fp64_shuffle_job.h (plain C++), its owner F64CallRun.
 //
-// resnmtf_fp64_subsample and resnmtf_fp64_relevance (section 28), last, are what a stability repeat needs around a
+// resnmtf_fp64_subsample and resnmtf_fp64_relevance (section 28), after it, are what a stability repeat needs around a
 // factorisation in double precision: the sub-sample of a view with its empty lines (resnmtf_fp64_subsample.hip.inc) and
 // the relevance of cluster matrices in device memory (resnmtf_fp64_relevance.hip.inc); their struct checks, index-list
 // checks, form chooser and workspaces are resnmtf_fp64_subsample_job.h (plain C++).  The three handle-free entries share
 // one owner of a call's stream and buffers, F64CallRun, and one header of pointer / extent helpers, resnmtf_fp64_extent.h.
+//
+// resnmtf_fp64_shuffle_sparse (section 30), last, draws shuffle_view of a view stored sparse: its kernels are
+// resnmtf_fp64_shuffle_sparse.hip.inc, its struct checks, extents and workspace resnmtf_fp64_shuffle_sparse_job.h (plain
+// C++); the source comes in through the run's own checks (fp64_check_csc / fp64_build_sparse_device_view) and the
+// destination is sorted by the same canonicaliser; its owners are F64Transient and F64CallRun.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -47,6 +52,8 @@
 #include "resnmtf_feistel.h"
 #include "resnmtf_fp64_shuffle_job.h"
 #include "resnmtf_fp64_shuffle.hip.inc"
+#include "resnmtf_fp64_shuffle_sparse_job.h"
+#include "resnmtf_fp64_shuffle_sparse.hip.inc"
 #include "resnmtf_fp64_subsample_job.h"
 #include "resnmtf_fp64_subsample.hip.inc"
 #include "resnmtf_fp64_relevance.hip.inc"
@@ -1400,6 +1407,166 @@ int resnmtf_fp64_relevance(int device_id, const resnmtf_fp64_relevance_job* job)
   for (int t = 0; t < 4; ++t)
     if (host_bad[t] != F64_REL_NONE) return bad_entry(mats[t].name, host_bad[t], mats[t].len);
   std::memcpy(j.relevance, host_out.data(), (size_t)kr * sizeof(double));
+  return RESNMTF_OK;
+}
+
+}  // extern "C"
+
+// ---- resnmtf_fp64_shuffle_sparse: shuffle_view of R/obtain_bicl.r:11-22 on a view stored sparse ----
+extern "C" {
+
+int resnmtf_fp64_shuffle_sparse(int device_id, const resnmtf_fp64_shuffle_sparse_job* job) {
+  static const char* const NAME = "fp64_shuffle_sparse";
+  if (const char* why = f64_shuffle_sparse_check_job(job)) return fp64_bad(why);
+  const resnmtf_fp64_shuffle_sparse_job& j = *job;
+  const int n = j.n, m = j.m;
+  const bool host_x = j.x.col_ptr != nullptr;
+  // the view's own refusals are those of view 0 of a one-view run, through the run's checks and with their texts
+  F64SparseShape shape;
+  resnmtf_fp64_sparse_device spd{};
+  resnmtf_group_job one{};
+  F64Source src[RESNMTF_GROUP_MAX_VIEWS];
+  if (host_x) {
+    if (!j.x.values) return fp64_bad("view 0: values is NULL");
+    const std::string why = fp64_check_csc(n, m, j.x.col_ptr, j.x.row_idx, j.x.values, shape);
+    if (!why.empty()) return fp64_bad("view 0: " + why);
+  } else {
+    one.struct_size = (int)sizeof(resnmtf_group_job);
+    one.n_views = 1; one.k = 1; one.n_rows[0] = n; one.n_cols[0] = m;
+    spd.struct_size = (int)sizeof(resnmtf_fp64_sparse_device);
+    spd.stream = j.stream;
+    spd.view[0] = j.x_dev;
+    fp64_resolve_sources(nullptr, nullptr, &spd, src);
+    const std::string why = fp64_check_sparse_device_struct(one, nullptr, nullptr, spd);
+    if (!why.empty()) return fp64_bad(why);
+    shape.nnz = (size_t)j.x_dev.nnz;
+  }
+  const size_t nnz = shape.nnz;
+  if (const char* why = f64_shuffle_sparse_check_nnz(j, nnz)) return fp64_bad(why);
+  if (int rc = fp64_check_device_id(device_id)) return rc;
+  int host_ints[2] = {0, 0};                 // (declared before the owners: the run's destructor waits for the copies into them)
+  std::vector<unsigned char> host_mask;
+  F64Transient tr(NAME);                     // (before the run: what the stream may still read is freed after the run has waited)
+  F64CallRun run(NAME);
+  hipError_t e = hipSetDevice(device_id);
+  if (e != hipSuccess) return run.fail(e, "hipSetDevice: ");
+  // whose memory the arrays are and how far they reach; then what shares a byte with what
+  F64ShuffleSparseRange outs[3], ins[3];
+  f64_shuffle_sparse_outputs(j, nnz, outs);
+  static const char* const OUT_HOLDS[3] = {"m + 1 int64", "nnz int64", "nnz doubles"};
+  for (int a = 0; a < 3; ++a) {
+    if (!outs[a].bytes) continue;
+    bool beyond = false;
+    if (!fp64_on_device(device_id, outs[a].ptr, outs[a].bytes, beyond))
+      return fp64_bad(std::string(outs[a].name) + (beyond ? std::string(" reaches beyond its allocation (too short for ") + OUT_HOLDS[a] + ")"
+                                                          : " is not device memory of device " + std::to_string(device_id)));
+  }
+  if (!host_x) {
+    const std::string why = fp64_check_sparse_device_pointers(device_id, one, spd, src);
+    if (!why.empty()) return fp64_bad(why);
+    f64_shuffle_sparse_sources(j, ins);
+  }
+  {
+    const char *a = nullptr, *b = nullptr;
+    if (f64_shuffle_sparse_overlap(outs, host_x ? nullptr : ins, a, b))
+      return fp64_bad(std::string(a) + " overlaps " + b + (b[0] == 'o' ? " (each output is an array of its own)" : " (the draw reads X while it writes the outputs)"));
+  }
+  // the transient memory, sized per stored entry before anything is allocated
+  const F64ShuffleSparsePlan plan = f64_shuffle_sparse_plan(n, m);
+  {
+    const size_t bytes = f64_shuffle_sparse_transient_bytes(n, m, nnz) + plan.total;
+    size_t free_b = 0, total_b = 0;
+    if ((e = hipMemGetInfo(&free_b, &total_b)) != hipSuccess) return run.fail(e);
+    if (bytes > free_b) {
+      resnmtf_set_create_error(std::string(NAME) + ": " + std::to_string(bytes) + " bytes asked for (" + std::to_string(F64_SHUFFLE_SPARSE_BYTES_PER_ENTRY) +
+                               " per stored entry while the draw is sorted, the pointers and the masks), " + std::to_string(free_b) +
+                               " free on the device");
+      return RESNMTF_ERR_ALLOC;
+    }
+  }
+  void* p = nullptr;
+  if (int rc = run.alloc(&p, plan.total, "the workspace")) return rc;
+  run.work = static_cast<char*>(p);
+  if ((e = hipStreamCreateWithFlags(&run.st, hipStreamNonBlocking)) != hipSuccess) { run.st = nullptr; return run.fail(e, "hipStreamCreate: "); }
+  hipStream_t st = run.st;
+  if ((e = wait_for_caller(st, j.stream)) != hipSuccess) return run.fail(e);      // (a host X too: the outputs may still be in use)
+  double* colsum = reinterpret_cast<double*>(run.work + plan.colsum);
+  int* ints = reinterpret_cast<int*>(run.work + plan.ints);                      // counts[0], counts[1]
+  unsigned char* mask = reinterpret_cast<unsigned char*>(run.work + plan.mask);
+  if (nnz > 0) {
+    // ---- the source as a canonical CSC in device memory, every index verified
+    const long long* s_cptr = nullptr;
+    const int* s_rows = nullptr;
+    const double* s_val = nullptr;
+    if (host_x) {
+      long long* cp = tr.take_n<long long>((size_t)m + 1);
+      int* ri = cp ? tr.take_n<int>(nnz) : nullptr;
+      double* va = ri ? tr.take_n<double>(nnz) : nullptr;
+      if (!va) return RESNMTF_ERR_ALLOC;
+      e = hipMemcpyAsync(cp, j.x.col_ptr, ((size_t)m + 1) * sizeof(long long), hipMemcpyHostToDevice, st);
+      if (e == hipSuccess) e = hipMemcpyAsync(ri, j.x.row_idx, nnz * sizeof(int), hipMemcpyHostToDevice, st);
+      if (e == hipSuccess) e = hipMemcpyAsync(va, j.x.values, nnz * sizeof(double), hipMemcpyHostToDevice, st);
+      if (e != hipSuccess) return run.fail(e);
+      s_cptr = cp; s_rows = ri; s_val = va;
+    } else {                                  // checked and sorted on the device; the stream is synchronised inside
+      F64SpdView sv;
+      F64SparseShape unused;
+      if (int rc = fp64_build_sparse_device_view(st, tr, 0, j.x_dev, n, m, sv, unused, NAME)) return rc;
+      tr.release(sv.rptr); tr.release(sv.ridx); tr.release(sv.perm);           // (the CSR half is not needed)
+      s_cptr = sv.cptr; s_rows = sv.cidx; s_val = sv.cval;
+    }
+    // ---- where every stored entry lands, then the draw sorted into its canonical CSC by the same canonicaliser: a COO
+    // in any order whose values are the source's, in place.  It verifies the coordinates again before it uses them.
+    int* drow = tr.take_n<int>(nnz);
+    int* dcol = drow ? tr.take_n<int>(nnz) : nullptr;
+    if (!dcol) return RESNMTF_ERR_ALLOC;
+    fp64_shuffle_sparse_dest(st, s_cptr, s_rows, (long long)nnz, n, m, j.seed, drow, dcol);
+    if ((e = hipGetLastError()) != hipSuccess) return run.fail(e);
+    resnmtf_fp64_sparse_device_view coo{};
+    coo.layout = RESNMTF_SPARSE_COO; coo.index_type = RESNMTF_INDEX_I32; coo.dtype = RESNMTF_DTYPE_F64;
+    coo.ptr_or_rows = drow; coo.idx_or_cols = dcol; coo.values = s_val; coo.nnz = (long long)nnz;
+    F64SpdView dv;
+    F64SparseShape unused;
+    if (int rc = fp64_build_sparse_device_view(st, tr, 0, coo, n, m, dv, unused, NAME)) return rc;
+    for (const void* q : {(const void*)s_cptr, (const void*)s_rows, (const void*)s_val, (const void*)drow, (const void*)dcol,
+                          (const void*)dv.rptr, (const void*)dv.ridx, (const void*)dv.perm})
+      tr.release(q);                          // (the build has synchronised the stream: nothing reads these any more)
+    // ---- the outputs: pointers, rows widened, the redraw condition, the values
+    e = hipMemcpyAsync(j.out_col_ptr, dv.cptr, ((size_t)m + 1) * sizeof(long long), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(ints, 0, 4 * sizeof(int), st);
+    if (e == hipSuccess) {
+      fp64_shuffle_sparse_widen(st, dv.cidx, (long long)nnz, j.out_row_idx);
+      e = fp64_shuffle_sparse_lines(st, dv.cptr, dv.cidx, dv.cval, (long long)nnz, n, m, mask, ints);
+    }
+    if (e == hipSuccess) {
+      if (j.normalise) {
+        fp64_shuffle_sparse_normalise(st, dv.cptr, dv.cidx, dv.cval, m, colsum, j.out_values);
+        e = hipGetLastError();
+      } else {
+        e = hipMemcpyAsync(j.out_values, dv.cval, nnz * sizeof(double), hipMemcpyDeviceToDevice, st);
+      }
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(host_ints, ints, sizeof(host_ints), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && (j.row_mask || j.col_mask)) {
+      host_mask.resize((size_t)n + m);
+      e = hipMemcpyAsync(host_mask.data(), mask, host_mask.size(), hipMemcpyDeviceToHost, st);
+    }
+  } else {                                    // no stored entry: zero pointers, every line empty, nothing of size zero launched
+    if (!host_x) {                            // (the pointers of a CSC / CSR view are still judged on the device)
+      F64SpdView sv;
+      F64SparseShape unused;
+      if (int rc = fp64_build_sparse_device_view(st, tr, 0, j.x_dev, n, m, sv, unused, NAME)) return rc;
+    }
+    e = hipMemsetAsync(j.out_col_ptr, 0, ((size_t)m + 1) * sizeof(long long), st);
+    host_ints[0] = n; host_ints[1] = m;
+    host_mask.assign((size_t)n + m, 1);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return run.fail(e);
+  *j.n_empty_rows = host_ints[0];
+  *j.n_empty_cols = host_ints[1];
+  if (j.row_mask) std::memcpy(j.row_mask, host_mask.data(), (size_t)n);
+  if (j.col_mask) std::memcpy(j.col_mask, host_mask.data() + n, (size_t)m);
   return RESNMTF_OK;
 }
 

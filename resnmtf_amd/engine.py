@@ -419,19 +419,17 @@ def fp64_bisil(x, rc, cc, distance: str = "euclidean", device_id: int = 0):
     return rs, cs
 
 
-def _fp64_bisil_sparse_job(x, n: int, m: int, device_id: int, keep: list) -> _lib.Fp64BisilSparseJob:
-    """The ``resnmtf_fp64_bisil_sparse_job`` of the sparse view ``x`` with its one place for X filled: a canonical
-    ``scipy.sparse`` CSC as the host arrays ``job.x`` (``job.x_dev`` all zero), a checked ``SparseDeviceView`` as
-    ``job.x_dev`` -- the addresses of the tensor's own index and value arrays, ``job.x`` NULL: nothing of it comes to the
-    host -- and ``job.stream`` = torch's current stream.  ``keep`` collects what the struct points into."""
-    job = _lib.Fp64BisilSparseJob()
-    job.struct_size = C.sizeof(job)
-    job.n, job.m = n, m
+def _fill_fp64_sparse_source(job, x, device_id: int, keep: list, what: str):
+    """The one place for X of a job struct that takes a sparse view either way (``resnmtf_fp64_bisil_sparse_job``,
+    ``resnmtf_fp64_shuffle_sparse_job``): a canonical ``scipy.sparse`` CSC as the host arrays ``job.x`` (``job.x_dev`` all
+    zero), a checked ``SparseDeviceView`` as ``job.x_dev`` -- the addresses of the tensor's own index and value arrays,
+    ``job.x`` NULL: nothing of it comes to the host -- and ``job.stream`` = torch's current stream.  ``keep`` collects what
+    the struct points into."""
     if isinstance(x, _device_views.SparseDeviceView):
         import torch                # (lazily: nothing else in this module needs it)
-        _fill_sparse_device_view(job.x_dev, x, "fp64_bisil_sparse: x", keep)
+        _fill_sparse_device_view(job.x_dev, x, what, keep)
         job.stream = torch.cuda.current_stream(torch.device("cuda", int(device_id))).cuda_stream
-        return job
+        return
     csc = [np.ascontiguousarray(x.indptr, dtype=np.int64), np.ascontiguousarray(x.indices, dtype=np.int32),
            np.ascontiguousarray(x.data, dtype=np.float64)]
     if csc[1].size == 0:            # (never a NULL pointer)
@@ -439,6 +437,15 @@ def _fp64_bisil_sparse_job(x, n: int, m: int, device_id: int, keep: list) -> _li
     keep.extend(csc)
     job.x.col_ptr = csc[0].ctypes.data_as(C.POINTER(C.c_longlong))
     job.x.row_idx, job.x.values = _ip(csc[1]), _dp(csc[2])
+
+
+def _fp64_bisil_sparse_job(x, n: int, m: int, device_id: int, keep: list) -> _lib.Fp64BisilSparseJob:
+    """The ``resnmtf_fp64_bisil_sparse_job`` of the sparse view ``x`` with its one place for X filled
+    (``_fill_fp64_sparse_source``)."""
+    job = _lib.Fp64BisilSparseJob()
+    job.struct_size = C.sizeof(job)
+    job.n, job.m = n, m
+    _fill_fp64_sparse_source(job, x, device_id, keep, "fp64_bisil_sparse: x")
     return job
 
 
@@ -524,6 +531,55 @@ def fp64_shuffle(x, seed: int, normalise: bool = True, device_id: int = 0):
     if code != _lib.OK:
         raise ResnmtfError(code, (lib.resnmtf_last_error(None) or b"").decode())
     return out, bool(neg.value), rm.astype(bool), cm.astype(bool)
+
+
+def fp64_shuffle_sparse(x, seed: int, normalise: bool = True, device_id: int = 0):
+    """``fp64_shuffle`` of a SPARSE view (``resnmtf_fp64_shuffle_sparse``, no handle): the same draw
+    for the same ``seed``, made of the stored entries alone -- a stored entry at (r, c) lands at
+    ``feistel_perm_inverse(r m + c)``, explicit zeros stay stored, no n x m array exists at any point.  Returns ``(tensor,
+    empty_rows, empty_cols)``: the draw as a ``sparse_csc`` tensor on ``cuda:device_id`` with fp64 values and int64 indices
+    (canonical: rows ascending within a column; what ``fp64_run`` takes as a sparse device view), and the boolean masks of
+    the rows / columns that hold no stored entry > 0 (the redraw condition, ``R/obtain_bicl.r:14-18``; the caller redraws
+    with another seed).  Positions, values and masks are bit for bit those of ``fp64_shuffle`` of the densified view at the
+    stored positions -- with ``normalise`` too, the column sums being taken in its order --, and in an empty column a
+    stored zero gives NaN as there.  ``x``: a ``scipy.sparse`` matrix (a CPU sparse tensor is taken as its SciPy matrix),
+    made canonical with ``sparse.canonical_csc`` (a copy; duplicates summed, explicit zeros dropped) and taken as
+    pre-processed; or a 2-D ``sparse_csc`` / ``sparse_csr`` / coalesced ``sparse_coo`` tensor on ``cuda:device_id`` (or its
+    ``device_views.SparseDeviceView``), read where it lies on torch's current stream: checked and sorted on the device,
+    nothing of it brought to the host.  A dense view is a ``ValueError`` (``fp64_shuffle`` takes those).  Two calls give
+    equal bits.  Bad input is refused before any device work (``ResnmtfError``)."""
+    import torch                    # (lazily: nothing else in this module needs it)
+    lib = _lib.load()
+    x = _device_views.host_or_device(x, "fp64_shuffle_sparse: x")
+    if _device_views.is_sparse_device_view(x):
+        x = _device_views.as_sparse_view(x, device_id, "fp64_shuffle_sparse: x")
+    elif _sparse.is_sparse(x):
+        x = _sparse.canonical_csc(x)
+    else:
+        raise ValueError("fp64_shuffle_sparse draws sparse views (scipy.sparse, or a sparse torch tensor): fp64_shuffle takes a dense one")
+    n, m, nnz = int(x.shape[0]), int(x.shape[1]), int(x.nnz)
+    if n < 1 or m < 1:
+        raise ValueError("fp64_shuffle_sparse: x must have at least one row and one column")
+    dev = torch.device("cuda", int(device_id))
+    ccol = torch.empty(m + 1, dtype=torch.int64, device=dev)
+    rows = torch.empty(nnz, dtype=torch.int64, device=dev)
+    vals = torch.empty(nnz, dtype=torch.float64, device=dev)
+    nr, nc = C.c_int(0), C.c_int(0)
+    rm = np.zeros(n, dtype=np.uint8); cm = np.zeros(m, dtype=np.uint8)
+    keep = []
+    job = _lib.Fp64ShuffleSparseJob()
+    job.struct_size = C.sizeof(job)
+    job.n, job.m, job.normalise, job.seed = n, m, 1 if normalise else 0, int(seed) & 0xFFFFFFFFFFFFFFFF
+    _fill_fp64_sparse_source(job, x, device_id, keep, "fp64_shuffle_sparse: x")
+    job.stream = torch.cuda.current_stream(dev).cuda_stream
+    job.out_col_ptr, job.out_row_idx, job.out_values = ccol.data_ptr(), rows.data_ptr() or None, vals.data_ptr() or None
+    job.n_empty_rows, job.n_empty_cols = C.pointer(nr), C.pointer(nc)
+    job.row_mask, job.col_mask = rm.ctypes.data_as(C.POINTER(C.c_ubyte)), cm.ctypes.data_as(C.POINTER(C.c_ubyte))
+    code = lib.resnmtf_fp64_shuffle_sparse(int(device_id), C.byref(job))
+    if code != _lib.OK:
+        raise ResnmtfError(code, (lib.resnmtf_last_error(None) or b"").decode())
+    out = torch.sparse_csc_tensor(ccol, rows, vals, size=(n, m), check_invariants=False)
+    return out, rm.astype(bool), cm.astype(bool)
 
 
 def _index_list(idx, what: str) -> np.ndarray:

@@ -168,43 +168,66 @@ def shuffled_engines(src, k: int, num_repeats: int, seed: int = 0, max_iters: in
     return out
 
 
-def _draw_shuffle_fp64(x, v: int, shuffle_seed: int, device_id: int = 0, shuffle=None):
-    """``_draw_shuffle`` in double precision: ``shuffle_view`` (``R/obtain_bicl.r:11-22``) of the
-    view ``x`` (a host array or a dense tensor on the device) through ``engine.fp64_shuffle``, re-normalised there,
-    redrawn while a row or a column of the draw sums to zero (``:14-18``) -- the same draw seeds, the same bound of 64.
-    Returns ``(the fp64 tensor on the device, the draws made)``.  ``shuffle`` replaces ``engine.fp64_shuffle``: a test
-    hook."""
-    shuffle = shuffle or _engine.fp64_shuffle
+def _draw_shuffle_fp64(x, v: int, shuffle_seed: int, device_id: int = 0, shuffle=None, shuffle_sparse=None):
+    """``_draw_shuffle`` in double precision (DESIGN.md sections 27 and 30): ``shuffle_view`` (``R/obtain_bicl.r:11-22``) of
+    the view ``x`` -- a host array or a dense tensor on the device through ``engine.fp64_shuffle``, a sparse view (a
+    canonical ``scipy.sparse`` matrix or a ``SparseDeviceView``) through ``engine.fp64_shuffle_sparse`` --, re-normalised
+    there, redrawn while a row or a column of the draw sums to zero (``:14-18``) -- the same draw seeds, the same bound of
+    64.  A sparse view with fewer stored entries than ``max(n, m)`` is refused before the first draw, as ``_draw_shuffle``
+    does.  Returns ``(the fp64 tensor on the device -- a ``sparse_csc`` one for a sparse view --, the draws made)``.
+    ``shuffle`` replaces ``engine.fp64_shuffle``, ``shuffle_sparse`` ``engine.fp64_shuffle_sparse``: test hooks."""
+    if device_views.is_sparse_device_view(x) or type(x).__module__.startswith("scipy.sparse"):
+        if device_views.is_sparse_device_view(x):
+            x = device_views.as_sparse_view(x, device_id, f"view {v}")
+        lines, stored = max(int(x.shape[0]), int(x.shape[1])), int(x.nnz)        # (>= the number of positive entries)
+        if stored < lines:
+            raise ValueError(f"shuffle_view: view {v} stores {stored} entries, fewer than max(n, m) = {lines}: every shuffle "
+                             "of it has an all-zero row or column, and the reference's shuffle_view (R/obtain_bicl.r:14-18) "
+                             "would not terminate on this view")
+        sparse_draw = shuffle_sparse or _engine.fp64_shuffle_sparse
+
+        def draw(seed):
+            return sparse_draw(x, seed, normalise=True, device_id=device_id)
+    else:
+        dense_draw = shuffle or _engine.fp64_shuffle
+
+        def draw(seed):
+            t, _, er, ec = dense_draw(x, seed, normalise=True, device_id=device_id)
+            return t, er, ec
     for attempt in range(64):
-        t, _, er, ec = shuffle(x, (shuffle_seed + 7919 * attempt) * 1000003 + v, normalise=True, device_id=device_id)
+        t, er, ec = draw((shuffle_seed + 7919 * attempt) * 1000003 + v)
         if not (np.any(er) or np.any(ec)):
             return t, attempt + 1
     raise RuntimeError("shuffle_view: every draw left an all-zero row or column")
 
 
 def shuffled_fits_fp64(data, k: int, num_repeats: int, seed: int = 0, max_iters: int = 100000, device_id: int = 0, *,
-                       shuffle=None, fit=None, keep=None) -> list:
-    """``obtain_shuffled_f`` (``R/obtain_bicl.r:31-42``) in double precision: for every repeat r,
-    each view of ``data`` (host arrays or dense tensors on ``cuda:device_id``, as the fp64 run received them) drawn by
-    ``_draw_shuffle_fp64`` with ``shuffled_engines``' seeds -- the shuffle seed ``seed * 7919 + r + 1`` -- and the draws
-    factorised by ``res_nmtf_inner(precision="fp64", fp64_device=True, output="torch", n_iters=None, spurious=False,
-    seed=seed + 1000 + r)``: no restrictions, uncoupled, from the device SVD start the f32 shuffle engine takes for the
-    same draw, to convergence (``max_iters`` guards it).  Returns the ``num_repeats`` lists of normalised F's per view as
-    NumPy arrays -- ``check_biclusters``' ``shuffled_f``; the draws of one repeat are the only shuffled copies alive.
-    Test hooks: ``shuffle`` replaces ``engine.fp64_shuffle``, ``fit(tensors, k, seed, max_iters, device_id)`` the
-    factorisation (it returns the F's), ``keep(r, tensors, attempts)`` sees every repeat's draws before they go."""
+                       shuffle=None, fit=None, keep=None, shuffle_sparse=None) -> list:
+    """``obtain_shuffled_f`` (``R/obtain_bicl.r:31-42``) in double precision (DESIGN.md sections 27 and 30): for every
+    repeat r, each view of ``data`` (host arrays or dense tensors on ``cuda:device_id``, as the fp64 run received them; a
+    sparse view as its canonical ``scipy.sparse`` matrix or its ``SparseDeviceView``) drawn by ``_draw_shuffle_fp64`` with
+    ``shuffled_engines``' seeds -- the shuffle seed ``seed * 7919 + r + 1`` -- and the draws factorised by
+    ``res_nmtf_inner(precision="fp64", fp64_device=True, output="torch", n_iters=None, spurious=False, seed=seed + 1000 +
+    r)`` -- with a sparse draw among them also ``fp64_sparse_device=True``: the draw is factorised as the sparse device
+    view it is --: no restrictions, uncoupled, from the device SVD start the f32 shuffle engine takes for the same draw, to
+    convergence (``max_iters`` guards it).  Returns the ``num_repeats`` lists of normalised F's per view as NumPy arrays --
+    ``check_biclusters``' ``shuffled_f``; the draws of one repeat are the only shuffled copies alive, one per view.
+    Test hooks: ``shuffle`` replaces ``engine.fp64_shuffle``, ``shuffle_sparse`` ``engine.fp64_shuffle_sparse``,
+    ``fit(tensors, k, seed, max_iters, device_id)`` the factorisation (it returns the F's), ``keep(r, tensors, attempts)``
+    sees every repeat's draws before they go."""
     views = list(data)
     n_v = len(views)
     if fit is None:
         def fit(tensors, k, seed, max_iters, device_id):
             from .api import res_nmtf_inner          # (lazy: api imports this module at its top)
+            more = {"fp64_sparse_device": True} if any(device_views.is_sparse_tensor(t) for t in tensors) else {}
             res = res_nmtf_inner(tensors, None, None, None, None, None, [k] * n_v, None, None, None, None, spurious=False,
                                  seed=seed, max_iters=max_iters, device_id=device_id, precision="fp64", fp64_device=True,
-                                 output="torch")
+                                 output="torch", **more)
             return res["output_f"]
     out = []
     for r in range(num_repeats):
-        drawn = [_draw_shuffle_fp64(x, v, seed * 7919 + r + 1, device_id, shuffle) for v, x in enumerate(views)]
+        drawn = [_draw_shuffle_fp64(x, v, seed * 7919 + r + 1, device_id, shuffle, shuffle_sparse) for v, x in enumerate(views)]
         tensors = [t for t, _ in drawn]
         if keep is not None:
             keep(r, tensors, [a for _, a in drawn])

@@ -128,7 +128,8 @@ def _check_factors(mats, what):
 
 def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int] = None, device_id: int = 0,
                      group=None, max_iters: int = 100000, shuffled_f=None, jsd: Optional[Callable] = None,
-                     grouped: bool = False, shuffle_sparse: bool = False, precision: str = "f32") -> dict:
+                     grouped: bool = False, shuffle_sparse: bool = False, precision: str = "f32",
+                     fp64_shuffle_sparse: bool = False) -> dict:
     """``check_biclusters`` (``R/obtain_bicl.r:113-133``) with ``get_thresholds`` (``:80-102``): returns
     ``{"score": n_views x K, "avg_threshold": n_views, "max_threshold": n_views}``.
 
@@ -147,12 +148,16 @@ def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int
     ``precision="fp64"`` (opt-in): the shuffled F's are ``problem.shuffled_fits_fp64(data, K,
     num_repeats, seed)`` -- every view drawn in double precision from the view as given (``engine.fp64_shuffle``: a host
     array, or a dense tensor on ``cuda:device_id`` read where it lies) and factorised by the fp64 path; the scorer, the
-    thresholds and the result are the same.  Sparse views, ``grouped`` and ``group`` are refused with it."""
+    thresholds and the result are the same.  Sparse views, ``grouped`` and ``group`` are refused with it.
+    ``fp64_shuffle_sparse=True`` (opt-in; read only with ``precision="fp64"``): a sparse view -- a
+    ``scipy.sparse`` matrix, taken as its canonical CSC, or a sparse tensor on ``cuda:device_id`` read where it lies -- is
+    drawn by ``engine.fp64_shuffle_sparse`` and its draws are factorised as sparse device views; dense views as before."""
     if precision not in ("f32", "fp64"):
         raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
     if precision == "fp64":
         return _check_biclusters_fp64(data, output_f, num_repeats, seed=seed, device_id=device_id, group=group,
-                                      max_iters=max_iters, shuffled_f=shuffled_f, jsd=jsd, grouped=grouped)
+                                      max_iters=max_iters, shuffled_f=shuffled_f, jsd=jsd, grouped=grouped,
+                                      shuffle_sparse=fp64_shuffle_sparse)
     R = check_num_repeats(num_repeats)
     views = list(data) if not (isinstance(data, np.ndarray) and data.ndim == 2) and not sparse.is_sparse(data) else [data]
     if any(sparse.is_sparse(d) for d in views):
@@ -198,9 +203,11 @@ def _checked_output_f(shapes, output_f, R: int):
     return output_f, K
 
 
-def _check_biclusters_fp64(data, output_f, num_repeats, *, seed, device_id, group, max_iters, shuffled_f, jsd, grouped) -> dict:
+def _check_biclusters_fp64(data, output_f, num_repeats, *, seed, device_id, group, max_iters, shuffled_f, jsd, grouped,
+                           shuffle_sparse: bool = False) -> dict:
     """``check_biclusters(precision="fp64")``: the views as the fp64 run received them, the shuffled F's from
-    ``problem.shuffled_fits_fp64``, then the scoring every route shares."""
+    ``problem.shuffled_fits_fp64``, then the scoring every route shares.  ``shuffle_sparse``
+    (``fp64_shuffle_sparse``): sparse views are admitted, a ``scipy.sparse`` one as its canonical CSC."""
     R = check_num_repeats(num_repeats)
     if grouped or group is not None:
         raise ValueError('precision="fp64": the shuffled fits run through resnmtf_fp64_run, one after another; grouped and '
@@ -208,9 +215,11 @@ def _check_biclusters_fp64(data, output_f, num_repeats, *, seed, device_id, grou
     views = ([data] if (isinstance(data, np.ndarray) and data.ndim == 2) or sparse.is_sparse(data) or device_views.is_tensor(data)
              else list(data))
     views = [device_views.host_or_device(d, f"view {v}") for v, d in enumerate(views)]
-    refuse_sparse_fp64(views)
+    if not shuffle_sparse:
+        refuse_sparse_fp64(views)
     views = [device_views.as_view(d, device_id, f"view {v}") for v, d in enumerate(views)]
-    if any(isinstance(d, device_views.RawDeviceView) for d in views):
+    views = [sparse.canonical_csc(d) if sparse.is_sparse(d) else d for d in views]
+    if any(isinstance(d, device_views.RawDeviceView) or getattr(d, "raw", False) for d in views):
         raise ValueError('precision="fp64": the views are taken as pre-processed; a RawDeviceView is not')
     output_f, K = _checked_output_f([tuple(d.shape) for d in views], output_f, R)
     if shuffled_f is None:
