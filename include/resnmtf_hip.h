@@ -1269,6 +1269,68 @@ int resnmtf_fp64_subsample(int device_id, const resnmtf_fp64_subsample_job* job)
 int resnmtf_fp64_subsample_plan(long long row_stride, long long col_stride, int* out);
 
 /*
+ * The sub-sample of stability_repeat (R/stability_analysis.r:124, :184, :232, :238) of one SPARSE view in DOUBLE precision,
+ * without a handle: resnmtf_fp64_subsample's gather of a view that is stored sparse, made of its
+ * stored entries alone -- no n x m array exists at any point.  Blocking.
+ *   n, m, n_sub, m_sub, rows, cols   as in resnmtf_fp64_subsample_job: destination row i is source row rows[i], destination
+ *                 column j source column cols[j].  A stored entry survives iff its row is in rows and its column in cols;
+ *                 its value is carried as it is, widened to fp64 exactly, NOT re-normalised; explicit zeros
+ *                 stay stored.
+ *   x             the view in host memory: the 0-based canonical CSC of the pre-processed view, as resnmtf_fp64_run_sparse
+ *                 takes it (col_ptr NULL when not given); or
+ *   x_dev, stream the view in device memory, as resnmtf_fp64_run_sparse_device takes it: CSC, CSR or coalesced COO, int32 or
+ *                 int64 indices, fp64 / fp32 / fp16 / bf16 values, entries in any order (all seven fields zero when not
+ *                 given), read where it lies after an event recorded on `stream`.  X is given in exactly one place.
+ *   out_col_ptr, out_row_idx, out_values, out_capacity   device memory of device_id owned by the caller: m_sub + 1 int64,
+ *                 and out_capacity int64 and out_capacity doubles, of which the first nnz_sub are written: the canonical
+ *                 CSC of the sub-sample (rows ascending within a column) -- what torch.sparse_csc_tensor wraps and what
+ *                 resnmtf_fp64_run_sparse_device reads without its first sort.  Written after the same event, complete
+ *                 when the call returns.  out_row_idx / out_values may be NULL when out_capacity = 0.
+ *                 COUNT MODE: all three NULL and out_capacity 0 -- nothing is sorted or written to the caller's device
+ *                 memory; nnz_sub, the two counts and the masks are still delivered.
+ *   nnz_sub       (host, not NULL) the stored entries of the sub-sample.
+ *   n_empty_rows, n_empty_cols   (host, not NULL) the rows / columns of the sub-sample that hold no stored entry > 0.  The
+ *                 values are non-negative, so these are the lines that sum to exactly 0.0: the counts and masks
+ *                 resnmtf_fp64_subsample reports on the densified view.
+ *   row_mask, col_mask           (host, n_sub and m_sub bytes, or NULL) 1 where a line is empty.
+ * Structure, values, counts and masks are bit for bit resnmtf_fp64_subsample of the densified view read at the stored
+ * positions (+0.0 everywhere else) and, on values fp32 holds, resnmtf_subsample_view_sparse with resnmtf_view_empty_lines.
+ * No floating-point arithmetic and no floating-point atomics: two calls give equal bits (integer atomics for the two
+ * counts alone); no workgroup waits on another.  A sub-sample without a stored entry: zero pointers, every line empty,
+ * nothing of size zero is launched.
+ * Transient device memory: 12 bytes per stored entry (48 while a view in device memory is checked
+ * and sorted) and 64 per kept entry while the sub-sample is sorted, plus the pointers, the lists and the masks; sized
+ * first on min(nnz, n_sub m_sub) kept entries and refused with RESNMTF_ERR_ALLOC and its byte count when it exceeds the
+ * free device memory.
+ * Refused before any device work (RESNMTF_ERR_INVALID, text in resnmtf_last_error(NULL)), nothing written: what
+ * resnmtf_fp64_subsample refuses of the extents and the lists, with its texts -- job NULL, a struct_size mismatch, n or m
+ * below 1, n_sub / m_sub outside [1, n] / [1, m], rows / cols NULL, an index out of range or one that occurs twice --; what
+ * resnmtf_fp64_shuffle_sparse refuses of the source and the outputs, with its texts -- X in both places or in neither, in
+ * fill mode out_col_ptr NULL (or out_row_idx / out_values NULL with out_capacity > 0), counts or nnz_sub NULL, device_id
+ * out of range, an output that is not memory of device_id or too short, outputs that overlap each other or x_dev's arrays,
+ * and of a host view what resnmtf_fp64_run_sparse refuses of view 0, of a device view what
+ * resnmtf_fp64_run_sparse_device refuses of view 0 (the device checks -- bad pointers, an index out of range, a non-finite
+ * or negative value, a position stored twice -- run before any output is written) --; a negative out_capacity.
+ * out_capacity < nnz_sub is known only after the counting pass: RESNMTF_ERR_INVALID, the text names both numbers, *nnz_sub
+ * is set so that the caller can allocate again, nothing else is written.
+ */
+typedef struct resnmtf_fp64_subsample_sparse_job {
+  int struct_size;                          /* sizeof the struct */
+  int n, m, n_sub, m_sub;
+  const int *rows, *cols;
+  resnmtf_fp64_sparse_view x;
+  resnmtf_fp64_sparse_device_view x_dev;
+  void* stream;
+  long long *out_col_ptr, *out_row_idx;
+  double* out_values;
+  long long out_capacity;
+  long long* nnz_sub;
+  int *n_empty_rows, *n_empty_cols;
+  unsigned char *row_mask, *col_mask;
+} resnmtf_fp64_subsample_sparse_job;
+int resnmtf_fp64_subsample_sparse(int device_id, const resnmtf_fp64_subsample_sparse_job* job);
+
+/*
  * relevance_results (R/stability_analysis.r:45-67, with jaccard_main :16-33) of cluster matrices that are in device
  * memory, without a handle: the sub-sample's clusters against the reference clusters gathered
  * through the sub-sample's index lists.  Blocking.

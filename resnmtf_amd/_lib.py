@@ -206,6 +206,19 @@ class Fp64SubsampleJob(C.Structure):
                 ("row_mask", C.POINTER(C.c_ubyte)), ("col_mask", C.POINTER(C.c_ubyte))]
 
 
+class Fp64SubsampleSparseJob(C.Structure):
+    """``resnmtf_fp64_subsample_sparse_job`` (include/resnmtf_hip.h): the host index lists, the view as host CSC arrays
+    (``x``) or as sparse arrays in device memory (``x_dev`` read after ``stream``), the caller's three device arrays of the
+    sub-sample's canonical CSC with their capacity (all NULL and 0: count mode) and the host outputs of
+    ``resnmtf_fp64_subsample_sparse``."""
+    _fields_ = [("struct_size", C.c_int), ("n", C.c_int), ("m", C.c_int), ("n_sub", C.c_int), ("m_sub", C.c_int),
+                ("rows", _ip), ("cols", _ip), ("x", Fp64SparseView), ("x_dev", Fp64SparseDeviceView), ("stream", C.c_void_p),
+                ("out_col_ptr", C.c_void_p), ("out_row_idx", C.c_void_p), ("out_values", C.c_void_p),
+                ("out_capacity", C.c_longlong), ("nnz_sub", C.POINTER(C.c_longlong)),
+                ("n_empty_rows", _ip), ("n_empty_cols", _ip),
+                ("row_mask", C.POINTER(C.c_ubyte)), ("col_mask", C.POINTER(C.c_ubyte))]
+
+
 class Fp64RelevanceJob(C.Structure):
     """``resnmtf_fp64_relevance_job`` (include/resnmtf_hip.h): the sub-sample's cluster matrices in device memory, the
     reference's in host memory (``true_r`` / ``true_c``) or in device memory (``true_r_dev`` / ``true_c_dev``), the host index
@@ -278,6 +291,7 @@ SIGNATURES = {
     "resnmtf_fp64_shuffle": (C.c_int, [C.c_int, C.POINTER(Fp64ShuffleJob)]),
     "resnmtf_fp64_shuffle_sparse": (C.c_int, [C.c_int, C.POINTER(Fp64ShuffleSparseJob)]),
     "resnmtf_fp64_subsample": (C.c_int, [C.c_int, C.POINTER(Fp64SubsampleJob)]),
+    "resnmtf_fp64_subsample_sparse": (C.c_int, [C.c_int, C.POINTER(Fp64SubsampleSparseJob)]),
     "resnmtf_fp64_subsample_plan": (C.c_int, [C.c_longlong, C.c_longlong, _ip]),
     "resnmtf_fp64_relevance": (C.c_int, [C.c_int, C.POINTER(Fp64RelevanceJob)]),
     "resnmtf_bisil": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),

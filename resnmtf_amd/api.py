@@ -43,6 +43,9 @@ from the fp64 values (``engine.fp64_shuffle`` -> ``resnmtf_fp64_shuffle``, no ha
 ``fp64_stability=True`` (``stability_check(precision="fp64")``): the sub-samples are gathered from the fp64 values
 (``engine.fp64_subsample`` -> ``resnmtf_fp64_subsample``, no handle), factorised by the fp64 path and scored from the
 cluster tensors it leaves on the device (``engine.fp64_relevance`` -> ``resnmtf_fp64_relevance``).
+With the further opt-in ``fp64_subsample_sparse=True`` the sub-samples of sparse views are gathered sparse
+(``engine.fp64_subsample_sparse`` -> ``resnmtf_fp64_subsample_sparse``) and factorised as sparse device views (DESIGN.md
+section 31).
 """
 from __future__ import annotations
 
@@ -607,7 +610,8 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
                     row_names=None, col_names=None, device_id: int = 0, seed: Optional[int] = None, group=None,
                     max_iters: int = 100000, return_repeats: bool = False, repeat_runner: Optional[Callable] = None,
                     spurious_on_device: bool = False, shuffle_sparse: bool = False, sparse_on_device: bool = False,
-                    output: str = "numpy", precision: str = "f32"):
+                    output: str = "numpy", precision: str = "f32", fp64_subsample_sparse: bool = False,
+                    fp64_shuffle_sparse: bool = False):
     """``stability_check`` (``R/stability_analysis.r:302-338``): ``n_stability`` factorisations of sub-samples
     (``sample_rate`` of the rows and columns, drawn and trimmed as ``stability_repeat`` does, ``:215-249``), each scored
     against ``results`` by ``relevance_results`` (``:45-67``) -- the gathers, the factorisations and the scoring run on
@@ -648,6 +652,16 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
     A host view is copied to the device once and read there by every repeat.  Refused by name
     (``NotImplementedError``): a sparse view of any kind, a device tensor still to be shifted and normalised
     (``RawDeviceView``), ``group``, ``sparse_on_device``, ``shuffle_sparse``.
+    ``fp64_subsample_sparse=True`` (keyword-only opt-in; read only under ``precision="fp64"``, a
+    no-op everywhere else) admits views stored sparse -- ``scipy.sparse`` matrices (taken as their canonical CSC and
+    uploaded once) and sparse tensors on ``cuda:device_id`` (read where they lie) --, mixed with dense ones at will: their
+    sub-samples are gathered sparse (``engine.fp64_subsample_sparse``: bit for bit the dense gather of the densified view
+    at the stored positions, and the same empty lines, so the trimmed lists are those of the dense route), stay sparse
+    tensors on the device and are factorised as sparse device views.  ``spurious=True`` on a sparse view needs
+    ``fp64_shuffle_sparse=True`` as well (keyword-only opt-in; read only under ``precision="fp64"``):
+    the removal inside every repeat then shuffles the sparse sub-sample sparse; without it that combination is refused by
+    name.  ``group``, ``sparse_on_device``, ``shuffle_sparse`` and a ``RawDeviceView`` stay refused as above, and without
+    ``fp64_subsample_sparse`` so does every sparse view, word for word.
     """
     if precision not in ("f32", "fp64"):
         raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
@@ -675,9 +689,18 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
                 raise NotImplementedError(f'stability_check(precision="fp64"): a device tensor still to be shifted and '
                                           f'column-normalised (view {v}) is not supported: the route takes pre-processed '
                                           'dense views')
-            if sparse.is_sparse_view(d) or device_views.is_sparse_device_view(d):
+            if not (sparse.is_sparse_view(d) or device_views.is_sparse_device_view(d)):
+                continue
+            if not fp64_subsample_sparse:
                 raise NotImplementedError(f'stability_check(precision="fp64"): a sparse view (view {v}) is not supported: '
                                           'resnmtf_fp64_subsample gathers dense views')
+            if getattr(d, "raw", False):
+                raise NotImplementedError(f'stability_check(precision="fp64"): a sparse device tensor still to be '
+                                          f'column-normalised (view {v}) is not supported: the route takes pre-processed views')
+            if spurious and not fp64_shuffle_sparse:
+                raise NotImplementedError(f'stability_check(precision="fp64"): spurious=True on a sparse view (view {v}) is not '
+                                          'supported without fp64_shuffle_sparse=True: the removal inside a repeat shuffles '
+                                          'the sparse sub-sample (resnmtf_fp64_shuffle_sparse)')
     # host copies of the small cluster matrices for the scoring, unless both of a view's are on the engine's device (they
     # are then read in place); `given` keeps the caller's
     given = results
@@ -685,7 +708,8 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
             for rc, cc in zip(results["row_clusters"], results["col_clusters"])]
     results = dict(results, row_clusters=[rc if on else device_views.to_numpy(rc) for rc, on in zip(results["row_clusters"], kept)],
                    col_clusters=[cc if on else device_views.to_numpy(cc) for cc, on in zip(results["col_clusters"], kept)])
-    if spurious_repeats and repeat_runner is None and not shuffle_sparse and any(sparse.is_sparse_view(d) for d in data):
+    if (spurious_repeats and repeat_runner is None and not shuffle_sparse and precision != "fp64"       # (fp64: judged above)
+            and any(sparse.is_sparse_view(d) for d in data)):
         raise NotImplementedError("spurious-bicluster removal needs shuffled views: device shuffles of sparse views "
                                   "are not supported")
     k = int(np.atleast_1d(k)[0])
@@ -694,6 +718,7 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
     if precision == "fp64":
         if repeat_runner is None:
             row_names, col_names = naming.give_names(data, None, None, row_names, col_names)
+        # (sparse views, admitted above, are recognised there: the call is the one it was)
         stab = batched.stability_relevance_fp64(data, results, k, int(n_stability), float(sample_rate), n_iters, seed, phi, xi,
                                                 psi, row_names, col_names, max_iters, device_id,
                                                 keep_clusters=return_repeats, spurious_repeats=spurious_repeats,
@@ -769,7 +794,8 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                   sparse_on_device: bool = False, output: str = "numpy", post_on_device: bool = False,
                   precision: str = "f32", score_bisil: bool = False, fp64_sparse: bool = False, fp64_device: bool = False,
                   fp64_sparse_device: bool = False, fp64_bisil: bool = False, fp64_spurious: bool = False,
-                  fp64_stability: bool = False, fp64_bisil_sparse: bool = False, fp64_shuffle_sparse: bool = False):
+                  fp64_stability: bool = False, fp64_bisil_sparse: bool = False, fp64_shuffle_sparse: bool = False,
+                  fp64_subsample_sparse: bool = False):
     """``apply_resnmtf`` (``R/main.r:214-335``) for a known ``k_val``: naming, shared-name maps, restriction
     symmetrisation, non-negativity shift and column normalisation on the host, then the device loop and -- with
     ``stability=True`` (the default) and ``spurious=False`` -- ``stability_check`` on the pre-processed data, as
@@ -856,8 +882,16 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     view with ``fp64_spurious``: ``apply_resnmtf(data, precision="fp64", k_sweep=True, fp64_sparse=True,
     fp64_bisil_sparse=True, spurious_on_device=True, fp64_spurious=True, fp64_shuffle_sparse=True, stability=False)`` is the
     reference's default pipeline minus stability on ``scipy.sparse`` views, every k with its own check at ``seed + k``.
-    Still refused by name: ``fp64_spurious`` on a sparse view without that flag, ``fp64_stability`` on a sparse view, and
-    views in device memory."""
+    ``fp64_subsample_sparse=True`` (keyword-only opt-in; read only with ``precision="fp64"`` and
+    ``fp64_stability=True``, a no-op everywhere else) lifts the refusal of a sparse view with ``fp64_stability``: it is
+    passed on to ``stability_check(precision="fp64")`` -- for a ``k_val`` and after the sweep's pick --, together with
+    ``fp64_shuffle_sparse`` when that is set, and the sub-samples of ``scipy.sparse`` views are gathered, factorised and
+    screened sparse.  ``apply_resnmtf(data, precision="fp64", k_sweep=True, fp64_sparse=True, fp64_bisil_sparse=True,
+    spurious_on_device=True, fp64_spurious=True, fp64_shuffle_sparse=True, fp64_stability=True,
+    fp64_subsample_sparse=True)`` is the reference's default pipeline in double precision on data that stays sparse end to
+    end.
+    Still refused by name: ``fp64_spurious`` on a sparse view without ``fp64_shuffle_sparse``, ``fp64_stability`` on a
+    sparse view without ``fp64_subsample_sparse``, and views in device memory."""
     if precision not in ("f32", "fp64"):
         raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
     if precision == "fp64":
@@ -868,7 +902,8 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                            fp64_sparse=fp64_sparse, fp64_device=fp64_device, fp64_sparse_device=fp64_sparse_device,
                            fp64_bisil=fp64_bisil, fp64_spurious=fp64_spurious, spurious_on_device=spurious_on_device,
                            fp64_stability=fp64_stability, remove_unstable=remove_unstable,
-                           fp64_bisil_sparse=fp64_bisil_sparse, fp64_shuffle_sparse=fp64_shuffle_sparse)
+                           fp64_bisil_sparse=fp64_bisil_sparse, fp64_shuffle_sparse=fp64_shuffle_sparse,
+                           fp64_subsample_sparse=fp64_subsample_sparse)
     device_views.check_output(output)
     _check_post_on_device(post_on_device, output)
     on_dev = {"sparse_on_device": True} if sparse_on_device else {}      # (off: every call below is the earlier one)
@@ -918,7 +953,7 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
                 no_clusts, sample_rate, n_stability, stability, stab_thres, *, row_names, col_names, device_id, max_iters,
                 seed, k_sweep, return_sweep, sweep_runner, output, score_bisil, fp64_sparse, fp64_device,
                 fp64_sparse_device, fp64_bisil, fp64_spurious=False, spurious_on_device=False, fp64_stability=False,
-                remove_unstable=True, fp64_bisil_sparse=False, fp64_shuffle_sparse=False):
+                remove_unstable=True, fp64_bisil_sparse=False, fp64_shuffle_sparse=False, fp64_subsample_sparse=False):
     """``apply_resnmtf(precision="fp64")``: the checks of the f32 function, the refusals of what runs on the f32 engine,
     ``prepare``, then ``res_nmtf_inner(precision="fp64")`` -- once for a ``k_val``, or as ``run(k)`` of ``_sweep`` --, then
     with ``stability`` and ``fp64_stability`` ``stability_check(precision="fp64")`` on the prepared data."""
@@ -942,7 +977,8 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
             raise ValueError("the k sweep ranks the biclusters by their bisilhouette score: no_clusts=True has none")
     if stability and not fp64_stability:
         refuse("stability=True", "the stability repeats run on the f32 engine; pass stability=False")
-    if stability and any(sparse.is_sparse_view(d) or device_views.is_sparse_device_view(d) for d in data):
+    if (stability and not fp64_subsample_sparse
+            and any(sparse.is_sparse_view(d) or device_views.is_sparse_device_view(d) for d in data)):
         refuse("a sparse view with fp64_stability", "resnmtf_fp64_subsample gathers dense views; pass stability=False")
     remove = bool(spurious) and not no_clusts
     if remove and not fp64_spurious:
@@ -967,8 +1003,13 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
         common.update(fp64_bisil_sparse=True)
 
     def stab_kw(p):                               # the keywords of stability_check(precision="fp64") on the prepared data
-        return {"row_names": p.row_names, "col_names": p.col_names, "device_id": device_id, "seed": seed, "max_iters": max_iters,
-                "spurious_on_device": spurious_on_device, "output": output, "precision": "fp64"}
+        kw = {"row_names": p.row_names, "col_names": p.col_names, "device_id": device_id, "seed": seed, "max_iters": max_iters,
+              "spurious_on_device": spurious_on_device, "output": output, "precision": "fp64"}
+        if fp64_subsample_sparse:                 # (passed on only when set: without the flag every call is the one it was)
+            kw["fp64_subsample_sparse"] = True
+            if fp64_shuffle_sparse:
+                kw["fp64_shuffle_sparse"] = True
+        return kw
     if not sweep:
         k_vec = [int(np.atleast_1d(k_val)[0])] * n_v                                              # main.r:226
         if any(k < 1 for k in k_vec):

@@ -719,13 +719,21 @@ def stability_repeat_fp64(data, results, k: int, n_iters, seed: int, samples, ph
     and the cluster tensors it leaves scored against ``results``' clusters (``engine.fp64_relevance``; tensors on the
     device are read in place).  Returns ``DeviceData.stability_repeat``'s dict, or ``{"stability_performed": False,
     "tag"}`` when the trimming fails.  ``keep_clusters`` adds the sub-sample's (cleaned) clusters as NumPy arrays,
-    ``return_init`` the start of the factorisation (test hooks)."""
+    ``return_init`` the start of the factorisation (test hooks).
+    A view of ``data`` that is stored sparse (``stability_check`` admits it with
+    ``fp64_subsample_sparse=True``) is probed by ``engine.fp64_subsample_sparse`` instead: its sub-sample is a
+    ``sparse_csc`` tensor on the device, the same rule holds for it (the tensor of the last probe is the sub-sample), and the
+    fit then also gets ``fp64_sparse_device=True`` -- with ``spurious_repeats`` also ``fp64_shuffle_sparse=True`` -- so that
+    it is factorised, and its draws are shuffled, as the sparse device view it is.  Dense and sparse views mix; without a
+    sparse view every call is the one it was."""
     n_v = len(data)
     shapes = [tuple(int(s) for s in d.shape) for d in data]
+    stored_sparse = [sparse.is_sparse_view(d) for d in data]
     last = {}                                     # per view: the lists and the tensor of its latest probe (one alive per view)
 
     def probe(i, rows_i, cols_i):
-        t, er, ec = _engine.fp64_subsample(data[i], rows_i, cols_i, device_id)
+        gather = _engine.fp64_subsample_sparse if stored_sparse[i] else _engine.fp64_subsample
+        t, er, ec = gather(data[i], rows_i, cols_i, device_id)
         last[i] = (rows_i, cols_i, t)
         return er, ec
     trimmed = trim_samples(shapes, samples, probe)
@@ -742,6 +750,10 @@ def stability_repeat_fp64(data, results, k: int, n_iters, seed: int, samples, ph
     more = {"return_init": True} if return_init else {}
     if spurious_repeats:
         more.update(spurious_on_device=True, fp64_spurious=True)
+    if any(stored_sparse):                        # (only then: without a sparse sub-sample the fit is the call it was)
+        more.update(fp64_sparse_device=True)
+        if spurious_repeats:
+            more.update(fp64_shuffle_sparse=True)
     res = fit_fp64_on_device(subs, k, phi, xi, psi, n_iters, spurious_repeats if spurious_repeats else 5, bool(spurious_repeats),
                              row_names=rn, col_names=cn, device_id=device_id, max_iters=max_iters, seed=seed, **more)
     del subs
@@ -768,11 +780,16 @@ def stability_relevance_fp64(data, results: dict, k: int, n_stability: int, samp
     ``runner(r)`` replaces the repeat (the CPU tests inject a stand-in; nothing then touches the device).  Returns
     ``{"stability_performed", "relevance" (None when not performed), "repeats"}``.  A host view is copied to the device
     once, as an fp64 tensor (``engine.fp64_device_view``), and every probe and gather of every repeat reads that copy in
-    place -- one source copy per view, as ``DeviceData`` keeps one; a tensor already there is read where it lies."""
+    place -- one source copy per view, as ``DeviceData`` keeps one; a tensor already there is read where it lies.
+    A view stored sparse (a ``scipy.sparse`` matrix, a sparse tensor on the device or its
+    ``SparseDeviceView``) is uploaded once as a ``sparse_csc`` tensor of its canonical CSC
+    (``engine.fp64_sparse_device_view``), or read where it lies, and its sub-samples stay sparse
+    (``stability_repeat_fp64``)."""
     if runner is None:
         shapes = [tuple(int(s) for s in d.shape) for d in data]
         draws = stability_draws(shapes, n_stability, sample_rate, seed)
-        sources = [_engine.fp64_device_view(d, device_id) for d in data]
+        sources = [_engine.fp64_sparse_device_view(d, device_id) if sparse.is_sparse_view(d) else _engine.fp64_device_view(d, device_id)
+                   for d in data]
 
         def runner(r):
             return stability_repeat_fp64(sources, results, k, n_iters, seed + 2000 + r, draws[r], phi, xi, psi, row_names,

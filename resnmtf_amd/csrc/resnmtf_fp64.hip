@@ -30,6 +30,11 @@
 // resnmtf_fp64_shuffle_sparse.hip.inc, its struct checks, extents and workspace resnmtf_fp64_shuffle_sparse_job.h (plain
 // C++); the source comes in through the run's own checks (fp64_check_csc / fp64_build_sparse_device_view) and the
 // destination is sorted by the same canonicaliser; its owners are F64Transient and F64CallRun.
+//
+// resnmtf_fp64_subsample_sparse (section 31), last, gathers the sub-sample of a stability repeat from a view stored
+// sparse: its kernels are resnmtf_fp64_subsample_sparse.hip.inc, its struct checks, extents, workspace and transient byte
+// count resnmtf_fp64_subsample_sparse_job.h (plain C++); the source comes in and the kept entries are sorted as in section
+// 30, the lists are checked as in section 28; its owners are F64Transient and F64CallRun.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -57,6 +62,8 @@
 #include "resnmtf_fp64_subsample_job.h"
 #include "resnmtf_fp64_subsample.hip.inc"
 #include "resnmtf_fp64_relevance.hip.inc"
+#include "resnmtf_fp64_subsample_sparse_job.h"
+#include "resnmtf_fp64_subsample_sparse.hip.inc"
 
 namespace {
 // one sweep of update_matrices (R/update_steps.r:272-319, views in index order) and the error of every view; the mean
@@ -1567,6 +1574,201 @@ int resnmtf_fp64_shuffle_sparse(int device_id, const resnmtf_fp64_shuffle_sparse
   *j.n_empty_cols = host_ints[1];
   if (j.row_mask) std::memcpy(j.row_mask, host_mask.data(), (size_t)n);
   if (j.col_mask) std::memcpy(j.col_mask, host_mask.data() + n, (size_t)m);
+  return RESNMTF_OK;
+}
+
+}  // extern "C"
+
+// ---- resnmtf_fp64_subsample_sparse: data[[i]][row_samples, col_samples] of
+// R/stability_analysis.r:124 on a view stored sparse ----
+extern "C" {
+
+int resnmtf_fp64_subsample_sparse(int device_id, const resnmtf_fp64_subsample_sparse_job* job) {
+  static const char* const NAME = "fp64_subsample_sparse";
+  if (const char* why = f64_subsample_sparse_check_job(job)) return fp64_bad(why);
+  const resnmtf_fp64_subsample_sparse_job& j = *job;
+  const int n = j.n, m = j.m, ns = j.n_sub, ms = j.m_sub;
+  const bool host_x = j.x.col_ptr != nullptr, fill = !f64_subsample_sparse_count_mode(j);
+  {
+    std::string why = f64_subsample_check_indices("rows", j.rows, ns, n);
+    if (why.empty()) why = f64_subsample_check_indices("cols", j.cols, ms, m);
+    if (!why.empty()) return fp64_bad(why);
+  }
+  // the view's own refusals are those of view 0 of a one-view run, through the run's checks and with their texts
+  F64SparseShape shape;
+  resnmtf_fp64_sparse_device spd{};
+  resnmtf_group_job one{};
+  F64Source src[RESNMTF_GROUP_MAX_VIEWS];
+  if (host_x) {
+    if (!j.x.values) return fp64_bad("view 0: values is NULL");
+    const std::string why = fp64_check_csc(n, m, j.x.col_ptr, j.x.row_idx, j.x.values, shape);
+    if (!why.empty()) return fp64_bad("view 0: " + why);
+  } else {
+    one.struct_size = (int)sizeof(resnmtf_group_job);
+    one.n_views = 1; one.k = 1; one.n_rows[0] = n; one.n_cols[0] = m;
+    spd.struct_size = (int)sizeof(resnmtf_fp64_sparse_device);
+    spd.stream = j.stream;
+    spd.view[0] = j.x_dev;
+    fp64_resolve_sources(nullptr, nullptr, &spd, src);
+    const std::string why = fp64_check_sparse_device_struct(one, nullptr, nullptr, spd);
+    if (!why.empty()) return fp64_bad(why);
+    shape.nnz = (size_t)j.x_dev.nnz;
+  }
+  const size_t nnz = shape.nnz;
+  if (int rc = fp64_check_device_id(device_id)) return rc;
+  long long host_nnz_sub = 0;                // (declared before the owners: the run's destructor waits for the copies into them)
+  int host_ints[2] = {0, 0};
+  std::vector<unsigned char> host_mask;
+  F64Transient tr(NAME);                     // (before the run: what the stream may still read is freed after the run has waited)
+  F64CallRun run(NAME);
+  hipError_t e = hipSetDevice(device_id);
+  if (e != hipSuccess) return run.fail(e, "hipSetDevice: ");
+  // whose memory the arrays are and how far they reach; then what shares a byte with what
+  F64ShuffleSparseRange outs[3], ins[3];
+  f64_subsample_sparse_outputs(j, outs);
+  static const char* const OUT_HOLDS[3] = {"m_sub + 1 int64", "out_capacity int64", "out_capacity doubles"};
+  for (int a = 0; a < 3; ++a) {
+    if (!outs[a].bytes) continue;
+    bool beyond = false;
+    if (!fp64_on_device(device_id, outs[a].ptr, outs[a].bytes, beyond))
+      return fp64_bad(std::string(outs[a].name) + (beyond ? std::string(" reaches beyond its allocation (too short for ") + OUT_HOLDS[a] + ")"
+                                                          : " is not device memory of device " + std::to_string(device_id)));
+  }
+  if (!host_x) {
+    const std::string why = fp64_check_sparse_device_pointers(device_id, one, spd, src);
+    if (!why.empty()) return fp64_bad(why);
+    f64_subsample_sparse_sources(j, ins);
+  }
+  {
+    const char *a = nullptr, *b = nullptr;
+    if (f64_shuffle_sparse_overlap(outs, host_x ? nullptr : ins, a, b))
+      return fp64_bad(std::string(a) + " overlaps " + b + (b[0] == 'o' ? " (each output is an array of its own)" : " (the gather reads X while it writes the outputs)"));
+  }
+  // the transient memory, sized on the most entries the sub-sample can keep before anything is allocated
+  const F64SubsampleSparsePlan plan = f64_subsample_sparse_plan(n, ns, ms);
+  {
+    const unsigned long long bound = fill ? f64_subsample_sparse_bound(ns, ms, nnz) : 0;
+    const size_t bytes = f64_subsample_sparse_transient_bytes(n, m, ns, ms, nnz, bound, !host_x) + plan.total;
+    size_t free_b = 0, total_b = 0;
+    if ((e = hipMemGetInfo(&free_b, &total_b)) != hipSuccess) return run.fail(e);
+    if (bytes > free_b) {
+      resnmtf_set_create_error(std::string(NAME) + ": " + std::to_string(bytes) + " bytes asked for (" +
+                               std::to_string(F64_SUBSAMPLE_SPARSE_BYTES_PER_STORED) + " per stored entry, " +
+                               std::to_string(F64_SUBSAMPLE_SPARSE_BYTES_PER_STORED_BUILD) + " while a view in device memory is sorted, " +
+                               std::to_string(F64_SUBSAMPLE_SPARSE_BYTES_PER_KEPT) +
+                               " per kept entry while the sub-sample is sorted, the pointers, the lists and the masks), " +
+                               std::to_string(free_b) + " free on the device");
+      return RESNMTF_ERR_ALLOC;
+    }
+  }
+  void* p = nullptr;
+  if (int rc = run.alloc(&p, plan.total, "the workspace")) return rc;
+  run.work = static_cast<char*>(p);
+  if ((e = hipStreamCreateWithFlags(&run.st, hipStreamNonBlocking)) != hipSuccess) { run.st = nullptr; return run.fail(e, "hipStreamCreate: "); }
+  hipStream_t st = run.st;
+  if ((e = wait_for_caller(st, j.stream)) != hipSuccess) return run.fail(e);      // (a host X too: the outputs may still be in use)
+  long long* counts = reinterpret_cast<long long*>(run.work + plan.counts);
+  long long* scan = reinterpret_cast<long long*>(run.work + plan.scan);
+  int* inv_row = reinterpret_cast<int*>(run.work + plan.inv_row);
+  int* rows = reinterpret_cast<int*>(run.work + plan.rows);
+  int* cols = reinterpret_cast<int*>(run.work + plan.cols);
+  int* ints = reinterpret_cast<int*>(run.work + plan.ints);                      // counts[0], counts[1]
+  unsigned char* mask = reinterpret_cast<unsigned char*>(run.work + plan.mask);
+  bool lines_on_device = false;              // the counts and the masks come from the device (else: every line is empty)
+  if (nnz > 0) {
+    // ---- the source as a canonical CSC in device memory, every index verified
+    const long long* s_cptr = nullptr;
+    const int* s_rows = nullptr;
+    const double* s_val = nullptr;
+    if (host_x) {
+      long long* cp = tr.take_n<long long>((size_t)m + 1);
+      int* ri = cp ? tr.take_n<int>(nnz) : nullptr;
+      double* va = ri ? tr.take_n<double>(nnz) : nullptr;
+      if (!va) return RESNMTF_ERR_ALLOC;
+      e = hipMemcpyAsync(cp, j.x.col_ptr, ((size_t)m + 1) * sizeof(long long), hipMemcpyHostToDevice, st);
+      if (e == hipSuccess) e = hipMemcpyAsync(ri, j.x.row_idx, nnz * sizeof(int), hipMemcpyHostToDevice, st);
+      if (e == hipSuccess) e = hipMemcpyAsync(va, j.x.values, nnz * sizeof(double), hipMemcpyHostToDevice, st);
+      if (e != hipSuccess) return run.fail(e);
+      s_cptr = cp; s_rows = ri; s_val = va;
+    } else {                                  // checked and sorted on the device; the stream is synchronised inside
+      F64SpdView sv;
+      F64SparseShape unused;
+      if (int rc = fp64_build_sparse_device_view(st, tr, 0, j.x_dev, n, m, sv, unused, NAME)) return rc;
+      tr.release(sv.rptr); tr.release(sv.ridx); tr.release(sv.perm);           // (the CSR half is not needed)
+      s_cptr = sv.cptr; s_rows = sv.cidx; s_val = sv.cval;
+    }
+    // ---- the kept entries of every destination column, their scan, the empty lines; nnz_sub comes to the host
+    e = hipMemcpyAsync(rows, j.rows, (size_t)ns * sizeof(int), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(cols, j.cols, (size_t)ms * sizeof(int), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(ints, 0, 4 * sizeof(int), st);
+    if (e == hipSuccess) e = fp64_subsample_sparse_count(st, s_cptr, s_rows, s_val, rows, cols, n, ns, ms, inv_row, counts, scan, mask);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(fp64_shuffle_sparse_count_kernel, dim3(f64_shuffle_sparse_grid((long long)ns + ms)), dim3(256), 0, st,
+                         (const unsigned char*)mask, ns, ms, ints);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&host_nnz_sub, scan + ms, sizeof(long long), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(host_ints, ints, sizeof(host_ints), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && (j.row_mask || j.col_mask)) {
+      host_mask.resize((size_t)ns + ms);
+      e = hipMemcpyAsync(host_mask.data(), mask, host_mask.size(), hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return run.fail(e);
+    lines_on_device = true;
+    if (fill && host_nnz_sub > j.out_capacity) {             // known only now; nothing but *nnz_sub is written
+      *j.nnz_sub = host_nnz_sub;
+      return fp64_bad("out_capacity = " + std::to_string(j.out_capacity) + " is below nnz_sub = " + std::to_string(host_nnz_sub) +
+                      " (the stored entries of the sub-sample; *nnz_sub is set)");
+    }
+    if (fill && host_nnz_sub > 0) {
+      // ---- the kept entries as a COO, sorted into the canonical CSC by the same canonicaliser (the rows of a destination
+      // column arrive in SOURCE row order).  It verifies the coordinates again before it uses them.
+      const size_t kept = (size_t)host_nnz_sub;
+      int* drow = tr.take_n<int>(kept);
+      int* dcol = drow ? tr.take_n<int>(kept) : nullptr;
+      double* dval = dcol ? tr.take_n<double>(kept) : nullptr;
+      if (!dval) return RESNMTF_ERR_ALLOC;
+      if ((e = fp64_subsample_sparse_emit(st, s_cptr, s_rows, s_val, cols, inv_row, ms, scan, drow, dcol, dval)) != hipSuccess)
+        return run.fail(e);
+      resnmtf_fp64_sparse_device_view coo{};
+      coo.layout = RESNMTF_SPARSE_COO; coo.index_type = RESNMTF_INDEX_I32; coo.dtype = RESNMTF_DTYPE_F64;
+      coo.ptr_or_rows = drow; coo.idx_or_cols = dcol; coo.values = dval; coo.nnz = host_nnz_sub;
+      F64SpdView dv;
+      F64SparseShape unused;
+      if (int rc = fp64_build_sparse_device_view(st, tr, 0, coo, ns, ms, dv, unused, NAME)) return rc;
+      for (const void* q : {(const void*)s_cptr, (const void*)s_rows, (const void*)s_val, (const void*)drow, (const void*)dcol,
+                            (const void*)dval, (const void*)dv.rptr, (const void*)dv.ridx, (const void*)dv.perm})
+        tr.release(q);                        // (the build has synchronised the stream: nothing reads these any more)
+      // ---- the outputs: pointers, rows widened, values
+      e = hipMemcpyAsync(j.out_col_ptr, dv.cptr, ((size_t)ms + 1) * sizeof(long long), hipMemcpyDeviceToDevice, st);
+      if (e == hipSuccess) {
+        fp64_shuffle_sparse_widen(st, dv.cidx, host_nnz_sub, j.out_row_idx);
+        e = hipGetLastError();
+      }
+      if (e == hipSuccess) e = hipMemcpyAsync(j.out_values, dv.cval, kept * sizeof(double), hipMemcpyDeviceToDevice, st);
+    } else if (fill) {                        // nothing kept: zero pointers (the scan's own), nothing of size zero launched
+      e = hipMemcpyAsync(j.out_col_ptr, scan, ((size_t)ms + 1) * sizeof(long long), hipMemcpyDeviceToDevice, st);
+    }
+  } else {                                    // no stored entry: zero pointers, every line empty, nothing of size zero launched
+    if (!host_x) {                            // (the pointers of a CSC / CSR view are still judged on the device)
+      F64SpdView sv;
+      F64SparseShape unused;
+      if (int rc = fp64_build_sparse_device_view(st, tr, 0, j.x_dev, n, m, sv, unused, NAME)) return rc;
+    }
+    if (fill) e = hipMemsetAsync(j.out_col_ptr, 0, ((size_t)ms + 1) * sizeof(long long), st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return run.fail(e);
+  if (!lines_on_device) {
+    host_ints[0] = ns; host_ints[1] = ms;
+    host_mask.assign((size_t)ns + ms, 1);
+  }
+  *j.nnz_sub = host_nnz_sub;
+  *j.n_empty_rows = host_ints[0];
+  *j.n_empty_cols = host_ints[1];
+  if (j.row_mask) std::memcpy(j.row_mask, host_mask.data(), (size_t)ns);
+  if (j.col_mask) std::memcpy(j.col_mask, host_mask.data() + ns, (size_t)ms);
   return RESNMTF_OK;
 }
 

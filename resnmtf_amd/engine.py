@@ -421,7 +421,7 @@ def fp64_bisil(x, rc, cc, distance: str = "euclidean", device_id: int = 0):
 
 def _fill_fp64_sparse_source(job, x, device_id: int, keep: list, what: str):
     """The one place for X of a job struct that takes a sparse view either way (``resnmtf_fp64_bisil_sparse_job``,
-    ``resnmtf_fp64_shuffle_sparse_job``): a canonical ``scipy.sparse`` CSC as the host arrays ``job.x`` (``job.x_dev`` all
+    ``resnmtf_fp64_shuffle_sparse_job``, ``resnmtf_fp64_subsample_sparse_job``): a canonical ``scipy.sparse`` CSC as the host arrays ``job.x`` (``job.x_dev`` all
     zero), a checked ``SparseDeviceView`` as ``job.x_dev`` -- the addresses of the tensor's own index and value arrays,
     ``job.x`` NULL: nothing of it comes to the host -- and ``job.stream`` = torch's current stream.  ``keep`` collects what
     the struct points into."""
@@ -670,6 +670,89 @@ def fp64_subsample(x, rows, cols, device_id: int = 0, out=None):
     if code != _lib.OK:
         raise ResnmtfError(code, (lib.resnmtf_last_error(None) or b"").decode())
     return out.t(), rm.astype(bool), cm.astype(bool)             # n_sub x m_sub, column-major
+
+
+def fp64_sparse_device_view(x, device_id: int = 0):
+    """The sparse view ``x`` as ``fp64_subsample_sparse`` reads it many times, the sparse twin of ``fp64_device_view``: a
+    sparse tensor on ``cuda:device_id`` (or its ``SparseDeviceView``) as it is, anything else (a ``scipy.sparse`` matrix, a
+    CPU sparse tensor) uploaded there once as the ``sparse_csc`` tensor of its canonical CSC (``sparse.canonical_csc``:
+    fp64 values, int64 indices) -- the same stored values, so a sub-sample of the copy has the bits of a sub-sample of
+    ``x``."""
+    import torch
+    x = _device_views.host_or_device(x, "fp64_sparse_device_view: x")
+    if _device_views.is_sparse_device_view(x):
+        return x
+    if not _sparse.is_sparse(x):
+        raise ValueError("fp64_sparse_device_view takes sparse views (scipy.sparse, or a sparse torch tensor): fp64_device_view "
+                         "takes a dense one")
+    c = _sparse.canonical_csc(x)
+    dev = torch.device("cuda", int(device_id))
+    return torch.sparse_csc_tensor(torch.as_tensor(np.ascontiguousarray(c.indptr, dtype=np.int64)).to(dev),
+                                   torch.as_tensor(np.ascontiguousarray(c.indices, dtype=np.int64)).to(dev),
+                                   torch.as_tensor(np.ascontiguousarray(c.data, dtype=np.float64)).to(dev),
+                                   size=tuple(int(s) for s in c.shape), check_invariants=False)
+
+
+def fp64_subsample_sparse(x, rows, cols, device_id: int = 0, count_only: bool = False):
+    """``fp64_subsample`` of a SPARSE view (``resnmtf_fp64_subsample_sparse``, no handle): the
+    sub-sample ``x[rows, cols]`` made of the stored entries alone -- a stored entry survives iff its row is in ``rows`` and
+    its column in ``cols``, its value is carried as it is (widened to fp64 exactly, not re-normalised), explicit zeros stay
+    stored, no n x m array exists at any point.  Returns ``(tensor, empty_rows, empty_cols)``: the sub-sample as a
+    ``sparse_csc`` tensor on ``cuda:device_id`` with fp64 values and int64 indices (canonical: rows ascending within a
+    column; what ``fp64_run`` takes as a sparse device view), and the boolean masks of the rows / columns that hold no
+    stored entry > 0 -- the lines that sum to exactly zero, the condition under which ``stability_repeat`` trims
+    (``R/stability_analysis.r:165-190``).  Structure, values and masks are bit for bit those of ``fp64_subsample`` of the
+    densified view at the stored positions.  ``count_only``: nothing is sorted or written on the device; returns
+    ``(nnz_sub, empty_rows, empty_cols)``.  ``x``: a ``scipy.sparse`` matrix (a CPU sparse tensor is taken as its SciPy
+    matrix), made canonical with ``sparse.canonical_csc`` (a copy; duplicates summed, explicit zeros dropped) and taken as
+    pre-processed; or a 2-D ``sparse_csc`` / ``sparse_csr`` / coalesced ``sparse_coo`` tensor on ``cuda:device_id`` (or its
+    ``device_views.SparseDeviceView``), read where it lies on torch's current stream: checked and sorted on the device,
+    nothing of it brought to the host.  ``rows`` / ``cols``: 0-based, in any order, each index at most once.  The outputs
+    are allocated for ``min(nnz, len(rows) * len(cols))`` entries, one call is made and the first ``nnz_sub`` entries are
+    wrapped.  A dense view is a ``ValueError`` (``fp64_subsample`` takes those).  Two calls give equal bits.  Bad input is
+    refused before any device work (``ResnmtfError``)."""
+    import torch                    # (lazily: nothing else in this module needs it)
+    lib = _lib.load()
+    x = _device_views.host_or_device(x, "fp64_subsample_sparse: x")
+    if _device_views.is_sparse_device_view(x):
+        x = _device_views.as_sparse_view(x, device_id, "fp64_subsample_sparse: x")
+    elif _sparse.is_sparse(x):
+        x = _sparse.canonical_csc(x)
+    else:
+        raise ValueError("fp64_subsample_sparse gathers sparse views (scipy.sparse, or a sparse torch tensor): fp64_subsample takes a dense one")
+    n, m, nnz = int(x.shape[0]), int(x.shape[1]), int(x.nnz)
+    if n < 1 or m < 1:
+        raise ValueError("fp64_subsample_sparse: x must have at least one row and one column")
+    rows, cols = _index_list(rows, "fp64_subsample_sparse: rows"), _index_list(cols, "fp64_subsample_sparse: cols")
+    ns, ms = int(rows.size), int(cols.size)
+    dev = torch.device("cuda", int(device_id))
+    kept, nr, nc = C.c_longlong(0), C.c_int(0), C.c_int(0)
+    rm = np.zeros(ns, dtype=np.uint8); cm = np.zeros(ms, dtype=np.uint8)
+    keep = []
+    job = _lib.Fp64SubsampleSparseJob()
+    job.struct_size = C.sizeof(job)
+    job.n, job.m, job.n_sub, job.m_sub = n, m, ns, ms
+    job.rows, job.cols = _ip(rows), _ip(cols)
+    _fill_fp64_sparse_source(job, x, device_id, keep, "fp64_subsample_sparse: x")
+    job.stream = torch.cuda.current_stream(dev).cuda_stream
+    if not count_only:
+        cap = min(nnz, ns * ms)
+        ccol = torch.empty(ms + 1, dtype=torch.int64, device=dev)
+        ridx = torch.empty(cap, dtype=torch.int64, device=dev)
+        vals = torch.empty(cap, dtype=torch.float64, device=dev)
+        job.out_col_ptr, job.out_row_idx, job.out_values = ccol.data_ptr(), ridx.data_ptr() or None, vals.data_ptr() or None
+        job.out_capacity = cap
+    job.nnz_sub = C.pointer(kept)
+    job.n_empty_rows, job.n_empty_cols = C.pointer(nr), C.pointer(nc)
+    job.row_mask, job.col_mask = rm.ctypes.data_as(C.POINTER(C.c_ubyte)), cm.ctypes.data_as(C.POINTER(C.c_ubyte))
+    code = lib.resnmtf_fp64_subsample_sparse(int(device_id), C.byref(job))
+    if code != _lib.OK:
+        raise ResnmtfError(code, (lib.resnmtf_last_error(None) or b"").decode())
+    if count_only:
+        return int(kept.value), rm.astype(bool), cm.astype(bool)
+    k = int(kept.value)
+    out = torch.sparse_csc_tensor(ccol, ridx[:k], vals[:k], size=(ns, ms), check_invariants=False)
+    return out, rm.astype(bool), cm.astype(bool)
 
 
 def fp64_relevance(row_c, col_c, true_r, true_c, rows, cols, device_id: int = 0) -> np.ndarray:
