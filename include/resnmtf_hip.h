@@ -1364,6 +1364,51 @@ typedef struct resnmtf_fp64_relevance_job {
 } resnmtf_fp64_relevance_job;
 int resnmtf_fp64_relevance(int device_id, const resnmtf_fp64_relevance_job* job);
 
+/*
+ * init_mats_inner (R/update_steps.r:78-125) for every view of a job in DOUBLE precision, without a handle (DESIGN.md
+ * section 32): the start of the fp64 path on the fp64 values of the views, where resnmtf_init_svd starts from their f32
+ * images.  The algorithm is resnmtf_init_svd's, constant for constant: a randomized subspace iteration with
+ * L = min(64, 16 ceil((k + 8) / 16)) columns, n_power rounds (below 1: 3), CholeskyQR2 after every product but the last
+ * with the 1e-14 trace ridge in round 0 and the 2e-14 trace column cut in both, the L x L eigenproblem of Z^T Z,
+ * U = Q Ut, V = Z Ut Sigma^-1; the exact Gram of the short side when min(n, m) < L; then |U|, |V|, the constant unit
+ * vector for a zero one, S0 = (|diag(d)| + |N(0, sigma)|) swept by the column sums, F0 and G0 divided by them, lambda0
+ * and mu0 their sums.  Omega and the noise of view v come from std::mt19937_64(seed[v]) with std::normal_distribution in
+ * resnmtf_init_svd's draw order: the same seed is the same sketch on both routes.
+ *   job, sp, dev, spd   where the views' data are, exactly as resnmtf_fp64_run_sparse_device takes them (sp, dev and spd
+ *               may be NULL): of the job n_views, k, n_rows, n_cols and x are read, of dev its stream and x, nothing else
+ *               (no factors, restrictions, maps or run outputs).  A dense view goes through the two padded fp64 images
+ *               and the products of the run, a sparse view through its CSC + CSR copies and the fp64 SpMM passes (no image
+ *               is built for it).  The views are done one after another: the transient device memory is one view's.
+ *   f0 ... mu0  the outputs per view: F0 (n x k), S0 (k x k), G0 (m x k) column-major, lambda0 and mu0 (k) -- all five
+ *               of every view.  outputs_on_device = 0: host pointers; 1: device pointers (contiguous, as resnmtf_fp64_device's
+ *               outputs), and then nothing of size n or m crosses the bus.  Both kinds receive the same bits.
+ *   singular_values   optional per view (host, k): the k leading singular values.
+ *   basis_u / basis_v / basis_d / basis_n_d   optional per view, all four or none (host): the signed vectors the factors
+ *               are built from (n x k, m x k, column-major), every singular value the route computed (at most 64,
+ *               descending) and their count, as resnmtf_init_svd_basis returns them.
+ * The L x L factorisations run on the host in fp64 (at most 64 x 64).  No floating-point atomics and no waiting between
+ * workgroups; every sum order is a function of the shapes, k and a sparse view's structure: two calls give the same bits.
+ * Blocking.  Refused before any device work (RESNMTF_ERR_INVALID) with the texts of resnmtf_fp64_run_sparse_device for
+ * the job and the views' sources, and: init NULL, a struct_size mismatch, sigma negative or not finite, an output missing
+ * or given beyond n_views, a basis given in part, a device output that is not memory of device_id.  A view that is all
+ * zero or holds a value that is not finite is refused when the device finds it.  A refusal writes no output.
+ */
+typedef struct resnmtf_fp64_init {
+  int struct_size;                          /* sizeof the struct */
+  int n_power;                              /* below 1: 3 */
+  int outputs_on_device;                    /* 0: f0 ... mu0 are host pointers; 1: device pointers */
+  double sigma;                             /* the variance of the noise on S0, >= 0 */
+  unsigned long long seed[RESNMTF_GROUP_MAX_VIEWS];
+  double *f0[RESNMTF_GROUP_MAX_VIEWS], *s0[RESNMTF_GROUP_MAX_VIEWS], *g0[RESNMTF_GROUP_MAX_VIEWS];
+  double *lambda0[RESNMTF_GROUP_MAX_VIEWS], *mu0[RESNMTF_GROUP_MAX_VIEWS];
+  double* singular_values[RESNMTF_GROUP_MAX_VIEWS];
+  double *basis_u[RESNMTF_GROUP_MAX_VIEWS], *basis_v[RESNMTF_GROUP_MAX_VIEWS], *basis_d[RESNMTF_GROUP_MAX_VIEWS];
+  int* basis_n_d[RESNMTF_GROUP_MAX_VIEWS];
+} resnmtf_fp64_init;
+int resnmtf_fp64_init_svd(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp,
+                          const resnmtf_fp64_device* dev, const resnmtf_fp64_sparse_device* spd,
+                          const resnmtf_fp64_init* init);
+
 /* ---- phase-level entry points (views sharded one-per-GPU; host does the exchange) ---- */
 
 /* Which image of X the streaming passes of view v use after its upload: *uses_2byte = 0 (f32 images), 1 (fp16) or

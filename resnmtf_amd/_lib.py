@@ -229,6 +229,17 @@ class Fp64RelevanceJob(C.Structure):
                 ("rows", _ip), ("cols", _ip), ("stream", C.c_void_p), ("relevance", _dp)]
 
 
+class Fp64Init(C.Structure):
+    """``resnmtf_fp64_init`` (include/resnmtf_hip.h): the seeds, sigma and n_power of ``resnmtf_fp64_init_svd``, the five
+    outputs per view (host pointers, or device pointers with ``outputs_on_device``), and the optional host outputs: the k
+    leading singular values and the signed basis."""
+    _fields_ = ([("struct_size", C.c_int), ("n_power", C.c_int), ("outputs_on_device", C.c_int), ("sigma", C.c_double),
+                 ("seed", C.c_ulonglong * _MV)] +
+                [(name, C.c_void_p * _MV) for name in ("f0", "s0", "g0", "lambda0", "mu0")] +
+                [(name, _dp * _MV) for name in ("singular_values", "basis_u", "basis_v", "basis_d")] +
+                [("basis_n_d", _ip * _MV)])
+
+
 # name -> (restype, argtypes); must list every symbol include/resnmtf_hip.h declares
 SIGNATURES = {
     "resnmtf_abi_version": (C.c_int, []),
@@ -294,6 +305,8 @@ SIGNATURES = {
     "resnmtf_fp64_subsample_sparse": (C.c_int, [C.c_int, C.POINTER(Fp64SubsampleSparseJob)]),
     "resnmtf_fp64_subsample_plan": (C.c_int, [C.c_longlong, C.c_longlong, _ip]),
     "resnmtf_fp64_relevance": (C.c_int, [C.c_int, C.POINTER(Fp64RelevanceJob)]),
+    "resnmtf_fp64_init_svd": (C.c_int, [C.c_int, C.POINTER(GroupJob), C.POINTER(Fp64Sparse), C.POINTER(Fp64Device),
+                                        C.POINTER(Fp64SparseDevice), C.POINTER(Fp64Init)]),
     "resnmtf_bisil": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_bisil_sparse": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "resnmtf_bisil_device": (C.c_int, [_h, C.c_int, C.c_int, _dm, _dm, C.c_int, C.c_void_p, C.c_void_p, _dp, C.c_void_p]),

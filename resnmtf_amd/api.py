@@ -122,7 +122,8 @@ def res_nmtf_inner(data, row_indices, column_indices,
                    sparse_on_device: bool = False, output: str = "numpy", init_lm=None, return_state: bool = False,
                    post_on_device: bool = False, precision: str = "f32", fp64_sparse: bool = False,
                    fp64_device: bool = False, fp64_sparse_device: bool = False, fp64_bisil: bool = False,
-                   fp64_spurious: bool = False, fp64_bisil_sparse: bool = False, fp64_shuffle_sparse: bool = False):
+                   fp64_spurious: bool = False, fp64_bisil_sparse: bool = False, fp64_shuffle_sparse: bool = False,
+                   fp64_init: bool = False):
     """``res_nmtf_inner`` (``R/main.r:32-140``).
 
     ``data``: list of pre-processed (non-negative, column-normalised) matrices; ``row_indices[v][w]``
@@ -262,6 +263,12 @@ def res_nmtf_inner(data, row_indices, column_indices,
     view at the stored positions, without densifying it) and the draws factorised as sparse device views; dense views go
     through ``engine.fp64_shuffle`` as before, and mixed view lists work.  The result equals ``remove_spurious(data, plain
     result, num_repeats, seed=seed, precision="fp64", fp64_shuffle_sparse=True)``.  Without it the refusal above stands.
+    ``fp64_init`` (keyword-only opt-in; a no-op with ``precision="f32"``): read only where the fp64
+    call builds its short-lived engine -- no explicit factors and ``host_init=False``.  The start then comes from
+    ``engine.fp64_init_svd`` (``resnmtf_fp64_init_svd``: ``init_mats_inner``, ``R/update_steps.r:78-125``, on the fp64 values
+    of the views, same seeds ``seed + v``) and no ``Engine`` is constructed: on the device under ``fp64_device``, from the
+    sparse sources under ``fp64_sparse`` / ``fp64_sparse_device``.  ``return_init`` reports this start.  The flag passes on
+    to the shuffled fits of ``fp64_spurious``.  Without it every call, result and refusal is what it was.
     """
     if precision not in ("f32", "fp64"):
         raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
@@ -274,7 +281,7 @@ def res_nmtf_inner(data, row_indices, column_indices,
                                     return_state=return_state, post_on_device=post_on_device, fp64_sparse=fp64_sparse,
                                     fp64_device=fp64_device, fp64_sparse_device=fp64_sparse_device, fp64_bisil=fp64_bisil,
                                     fp64_spurious=fp64_spurious, num_repeats=num_repeats, fp64_bisil_sparse=fp64_bisil_sparse,
-                                    fp64_shuffle_sparse=fp64_shuffle_sparse)
+                                    fp64_shuffle_sparse=fp64_shuffle_sparse, fp64_init=fp64_init)
     device_views.check_output(output)
     _check_post_on_device(post_on_device, output)
     data = _views(data, device_id)
@@ -369,7 +376,7 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
                          fp64_sparse: bool = False, fp64_device: bool = False, fp64_sparse_device: bool = False,
                          fp64_bisil: bool = False, runner: Optional[Callable] = None, sil: Optional[Callable] = None,
                          fp64_spurious: bool = False, num_repeats=5, checker: Optional[Callable] = None,
-                         fp64_bisil_sparse: bool = False, fp64_shuffle_sparse: bool = False):
+                         fp64_bisil_sparse: bool = False, fp64_shuffle_sparse: bool = False, fp64_init: bool = False):
     """``res_nmtf_inner(precision="fp64")``: the checks of the f32 call, the refusals of what needs a live handle, the
     initial state, then one ``engine.fp64_run`` (``runner`` replaces it: a test hook).  ``fp64_device``: views, factors
     and results may live in device memory (``res_nmtf_inner``'s docstring); the runner then also gets ``output`` and
@@ -380,7 +387,8 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
     ``fp64_spurious``: ``spurious=True`` with ``spurious_on_device`` is honoured through
     ``spurious.check_biclusters(..., precision="fp64")`` on the views as they arrived (``checker`` replaces it: a test
     hook), then ``_remove_then_score``; ``fp64_shuffle_sparse``: a sparse view is then shuffled sparse (section 30) instead
-    of being refused, and the checker gets the flag."""
+    of being refused, and the checker gets the flag.  ``fp64_init``: without explicit factors and ``host_init`` the start
+    is ``engine.fp64_init_svd``'s (section 32) and no engine is built; the checker gets the flag."""
     def refuse(flag):
         raise NotImplementedError(f'precision="fp64": {flag} needs a live engine handle, which the fp64 path does not '
                                   'keep (it runs through resnmtf_fp64_run); use precision="f32" for it')
@@ -462,6 +470,10 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
 
     if init_f is None and host_init:
         init_f, init_s, init_g, lam, mu = svd_init(data, k_vec, seed)
+    elif init_f is None and fp64_init:            # init_mats_inner on the fp64 values, without an engine (section 32)
+        start = _engine.fp64_init_svd(data, k_vec[0], seed=_seed(seed), output="torch" if fp64_device else "numpy",
+                                      device_id=device_id)
+        init_f, init_s, init_g, lam, mu = (list(x) for x in zip(*start))
     elif init_f is None:                          # the device's own SVD initialisation: the start the f32 call reports
         more = {"nnz": [d.nnz if sp else None for d, sp in zip(data, is_sp)]} if any(is_sp) else {}      # (a short-lived sparse engine)
         eng = Engine([d.shape[0] for d in data], [d.shape[1] for d in data], k_vec, device_id=device_id, **more,
@@ -501,6 +513,8 @@ def _res_nmtf_inner_fp64(data, row_indices, column_indices, init_f, init_s, init
     check = None
     if remove:                                    # obtain_bicl.r:151-188, on the numbers that were factorised (section 27)
         flag = {"fp64_shuffle_sparse": True} if fp64_shuffle_sparse else {}      # (only then: every other call is the one it was)
+        if fp64_init:
+            flag["fp64_init"] = True
         check = (checker or _spurious.check_biclusters)(data, out["f"], num_repeats, seed=seed, device_id=device_id,
                                                         max_iters=max_iters, precision="fp64", **flag)
     score_fn = None
@@ -611,7 +625,7 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
                     max_iters: int = 100000, return_repeats: bool = False, repeat_runner: Optional[Callable] = None,
                     spurious_on_device: bool = False, shuffle_sparse: bool = False, sparse_on_device: bool = False,
                     output: str = "numpy", precision: str = "f32", fp64_subsample_sparse: bool = False,
-                    fp64_shuffle_sparse: bool = False):
+                    fp64_shuffle_sparse: bool = False, fp64_init: bool = False):
     """``stability_check`` (``R/stability_analysis.r:302-338``): ``n_stability`` factorisations of sub-samples
     (``sample_rate`` of the rows and columns, drawn and trimmed as ``stability_repeat`` does, ``:215-249``), each scored
     against ``results`` by ``relevance_results`` (``:45-67``) -- the gathers, the factorisations and the scoring run on
@@ -722,7 +736,7 @@ def stability_check(data, results, k, phi, xi, psi, n_iters, spurious, num_repea
         stab = batched.stability_relevance_fp64(data, results, k, int(n_stability), float(sample_rate), n_iters, seed, phi, xi,
                                                 psi, row_names, col_names, max_iters, device_id,
                                                 keep_clusters=return_repeats, spurious_repeats=spurious_repeats,
-                                                runner=repeat_runner)
+                                                runner=repeat_runner, **({"fp64_init": True} if fp64_init else {}))
     else:
         if repeat_runner is None:
             row_names, col_names = naming.give_names(data, None, None, row_names, col_names)
@@ -795,7 +809,7 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                   precision: str = "f32", score_bisil: bool = False, fp64_sparse: bool = False, fp64_device: bool = False,
                   fp64_sparse_device: bool = False, fp64_bisil: bool = False, fp64_spurious: bool = False,
                   fp64_stability: bool = False, fp64_bisil_sparse: bool = False, fp64_shuffle_sparse: bool = False,
-                  fp64_subsample_sparse: bool = False):
+                  fp64_subsample_sparse: bool = False, fp64_init: bool = False):
     """``apply_resnmtf`` (``R/main.r:214-335``) for a known ``k_val``: naming, shared-name maps, restriction
     symmetrisation, non-negativity shift and column normalisation on the host, then the device loop and -- with
     ``stability=True`` (the default) and ``spurious=False`` -- ``stability_check`` on the pre-processed data, as
@@ -891,7 +905,10 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
     fp64_subsample_sparse=True)`` is the reference's default pipeline in double precision on data that stays sparse end to
     end.
     Still refused by name: ``fp64_spurious`` on a sparse view without ``fp64_shuffle_sparse``, ``fp64_stability`` on a
-    sparse view without ``fp64_subsample_sparse``, and views in device memory."""
+    sparse view without ``fp64_subsample_sparse``, and views in device memory.
+    ``fp64_init=True`` (keyword-only opt-in; a no-op with ``precision="f32"``) is passed on to every
+    fit that would build a short-lived f32 engine for its start -- the ``k_val`` fit, every k of the sweep, the shuffled
+    fits of the removal and the stability repeats --: each starts from ``engine.fp64_init_svd`` under the seed it had."""
     if precision not in ("f32", "fp64"):
         raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
     if precision == "fp64":
@@ -903,7 +920,7 @@ def apply_resnmtf(data, init_f=None, init_s=None, init_g=None, k_val=None,
                            fp64_bisil=fp64_bisil, fp64_spurious=fp64_spurious, spurious_on_device=spurious_on_device,
                            fp64_stability=fp64_stability, remove_unstable=remove_unstable,
                            fp64_bisil_sparse=fp64_bisil_sparse, fp64_shuffle_sparse=fp64_shuffle_sparse,
-                           fp64_subsample_sparse=fp64_subsample_sparse)
+                           fp64_subsample_sparse=fp64_subsample_sparse, fp64_init=fp64_init)
     device_views.check_output(output)
     _check_post_on_device(post_on_device, output)
     on_dev = {"sparse_on_device": True} if sparse_on_device else {}      # (off: every call below is the earlier one)
@@ -953,7 +970,8 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
                 no_clusts, sample_rate, n_stability, stability, stab_thres, *, row_names, col_names, device_id, max_iters,
                 seed, k_sweep, return_sweep, sweep_runner, output, score_bisil, fp64_sparse, fp64_device,
                 fp64_sparse_device, fp64_bisil, fp64_spurious=False, spurious_on_device=False, fp64_stability=False,
-                remove_unstable=True, fp64_bisil_sparse=False, fp64_shuffle_sparse=False, fp64_subsample_sparse=False):
+                remove_unstable=True, fp64_bisil_sparse=False, fp64_shuffle_sparse=False, fp64_subsample_sparse=False,
+                fp64_init=False):
     """``apply_resnmtf(precision="fp64")``: the checks of the f32 function, the refusals of what runs on the f32 engine,
     ``prepare``, then ``res_nmtf_inner(precision="fp64")`` -- once for a ``k_val``, or as ``run(k)`` of ``_sweep`` --, then
     with ``stability`` and ``fp64_stability`` ``stability_check(precision="fp64")`` on the prepared data."""
@@ -1001,6 +1019,8 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
             common.update(fp64_shuffle_sparse=True)
     if fp64_bisil_sparse:                         # (the same: passed through only when set)
         common.update(fp64_bisil_sparse=True)
+    if fp64_init:                                 # (the same)
+        common.update(fp64_init=True)
 
     def stab_kw(p):                               # the keywords of stability_check(precision="fp64") on the prepared data
         kw = {"row_names": p.row_names, "col_names": p.col_names, "device_id": device_id, "seed": seed, "max_iters": max_iters,
@@ -1009,6 +1029,8 @@ def _apply_fp64(data, init_f, init_s, init_g, k_val, phi, xi, psi, n_iters, k_mi
             kw["fp64_subsample_sparse"] = True
             if fp64_shuffle_sparse:
                 kw["fp64_shuffle_sparse"] = True
+        if fp64_init:
+            kw["fp64_init"] = True
         return kw
     if not sweep:
         k_vec = [int(np.atleast_1d(k_val)[0])] * n_v                                              # main.r:226

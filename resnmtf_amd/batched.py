@@ -709,7 +709,7 @@ def stability_relevance_on_device(dev: Optional[DeviceData], results: dict, k: i
 
 def stability_repeat_fp64(data, results, k: int, n_iters, seed: int, samples, phi, xi, psi, row_names, col_names,
                           max_iters: int = 100000, device_id: int = 0, tag: str = "", keep_clusters: bool = False,
-                          spurious_repeats: int = 0, return_init: bool = False) -> dict:
+                          spurious_repeats: int = 0, return_init: bool = False, fp64_init: bool = False) -> dict:
     """One repeat of ``stability_check`` (``R/stability_analysis.r:215-278``) in double precision:
     the draws ``samples`` trimmed (``trim_samples`` with ``engine.fp64_subsample`` as the probe), every view's sub-sample
     an fp64 tensor on the device (``resnmtf_fp64_subsample``: the fp64 values, not re-normalised, names carried over; the
@@ -725,7 +725,8 @@ def stability_repeat_fp64(data, results, k: int, n_iters, seed: int, samples, ph
     ``sparse_csc`` tensor on the device, the same rule holds for it (the tensor of the last probe is the sub-sample), and the
     fit then also gets ``fp64_sparse_device=True`` -- with ``spurious_repeats`` also ``fp64_shuffle_sparse=True`` -- so that
     it is factorised, and its draws are shuffled, as the sparse device view it is.  Dense and sparse views mix; without a
-    sparse view every call is the one it was."""
+    sparse view every call is the one it was.  ``fp64_init``: the fit starts from
+    ``engine.fp64_init_svd`` of the sub-samples at ``seed`` instead of a short-lived f32 engine; passed on only when set."""
     n_v = len(data)
     shapes = [tuple(int(s) for s in d.shape) for d in data]
     stored_sparse = [sparse.is_sparse_view(d) for d in data]
@@ -754,6 +755,8 @@ def stability_repeat_fp64(data, results, k: int, n_iters, seed: int, samples, ph
         more.update(fp64_sparse_device=True)
         if spurious_repeats:
             more.update(fp64_shuffle_sparse=True)
+    if fp64_init:
+        more.update(fp64_init=True)
     res = fit_fp64_on_device(subs, k, phi, xi, psi, n_iters, spurious_repeats if spurious_repeats else 5, bool(spurious_repeats),
                              row_names=rn, col_names=cn, device_id=device_id, max_iters=max_iters, seed=seed, **more)
     del subs
@@ -771,7 +774,8 @@ def stability_repeat_fp64(data, results, k: int, n_iters, seed: int, samples, ph
 
 def stability_relevance_fp64(data, results: dict, k: int, n_stability: int, sample_rate: float, n_iters, seed: int, phi, xi,
                              psi, row_names, col_names, max_iters: int = 100000, device_id: int = 0,
-                             keep_clusters: bool = False, spurious_repeats: int = 0, runner: Optional[Callable] = None) -> dict:
+                             keep_clusters: bool = False, spurious_repeats: int = 0, runner: Optional[Callable] = None,
+                             fp64_init: bool = False) -> dict:
     """``stability_relevance_on_device`` in double precision: the repeats of ``stability_check``
     without an f32 handle.  ``data``: the pre-processed dense views, host arrays or tensors on ``cuda:device_id``.  The
     draws are ``stability_draws(shapes, n_stability, sample_rate, seed)`` -- the f32 route's for the same seed --, repeat
@@ -794,7 +798,8 @@ def stability_relevance_fp64(data, results: dict, k: int, n_stability: int, samp
         def runner(r):
             return stability_repeat_fp64(sources, results, k, n_iters, seed + 2000 + r, draws[r], phi, xi, psi, row_names,
                                          col_names, max_iters=max_iters, device_id=device_id, tag=f"stability={r}",
-                                         keep_clusters=keep_clusters, spurious_repeats=spurious_repeats)
+                                         keep_clusters=keep_clusters, spurious_repeats=spurious_repeats,
+                                         **({"fp64_init": True} if fp64_init else {}))
     repeats = [runner(r) for r in range(n_stability)]
     rel = mean_relevance(repeats, n_stability)
     return {"stability_performed": rel is not None, "relevance": rel, "repeats": repeats}

@@ -35,12 +35,19 @@
 // sparse: its kernels are resnmtf_fp64_subsample_sparse.hip.inc, its struct checks, extents, workspace and transient byte
 // count resnmtf_fp64_subsample_sparse_job.h (plain C++); the source comes in and the kept entries are sorted as in section
 // 30, the lists are checked as in section 28; its owners are F64Transient and F64CallRun.
+//
+// resnmtf_fp64_init_svd (section 32), last, is init_mats_inner (R/update_steps.r:78-125) for every view of a job in double
+// precision: the randomized subspace iteration of the main unit's resnmtf_init_svd on the fp64 values.  Its views come in
+// through the run's checks and uploads (fp64_checks with F64Job::start_only, fp64_upload_view), its products, SpMM and
+// Gram partials are the run's kernels, its own kernels are resnmtf_fp64_init.hip.inc, its L x L factorisations
+// resnmtf_small_linalg.h (plain C++, shared with the main unit); its owners are F64Run, one buffer per view, and F64Block.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <random>
 #include <string>
 #include <vector>
 
@@ -64,6 +71,8 @@
 #include "resnmtf_fp64_relevance.hip.inc"
 #include "resnmtf_fp64_subsample_sparse_job.h"
 #include "resnmtf_fp64_subsample_sparse.hip.inc"
+#include "resnmtf_small_linalg.h"
+#include "resnmtf_fp64_init.hip.inc"
 
 namespace {
 // one sweep of update_matrices (R/update_steps.r:272-319, views in index order) and the error of every view; the mean
@@ -427,6 +436,7 @@ struct F64Job {
   F64DeviceUse use;                         // the factors and the outputs in device memory (resnmtf_fp64_run_device)
   F64SparseShape shapes[RESNMTF_GROUP_MAX_VIEWS];
   F64Layout L;
+  bool start_only = false;                  // resnmtf_fp64_init_svd: the views alone; the job holds no factors and no run outputs
   bool any(F64Source s) const { return std::find(src, src + RESNMTF_GROUP_MAX_VIEWS, s) != src + RESNMTF_GROUP_MAX_VIEWS; }
 };
 
@@ -492,7 +502,9 @@ int fp64_checks(F64Job& J) {
     const std::string why = fp64_check_device_struct(j, *J.dev, J.src, J.use);
     if (!why.empty()) return fp64_bad(why);
   }
-  if (const char* why = resnmtf_check_fp64_job(j, J.max_iters, fp64_x_elsewhere(J.src), J.use.factors, J.use.out)) return fp64_bad(why);
+  if (const char* why = resnmtf_check_fp64_job(j, J.max_iters, fp64_x_elsewhere(J.src), J.start_only ? ~0u : J.use.factors,
+                                               J.start_only || J.use.out))
+    return fp64_bad(why);
   for (int v = j.n_views; v < RESNMTF_GROUP_MAX_VIEWS; ++v)
     if (J.src[v] == F64Source::HostCsc) return fp64_bad("a sparse view is given beyond n_views");
   if (J.dev) {
@@ -1769,6 +1781,404 @@ int resnmtf_fp64_subsample_sparse(int device_id, const resnmtf_fp64_subsample_sp
   *j.n_empty_cols = host_ints[1];
   if (j.row_mask) std::memcpy(j.row_mask, host_mask.data(), (size_t)ns);
   if (j.col_mask) std::memcpy(j.col_mask, host_mask.data() + ns, (size_t)ms);
+  return RESNMTF_OK;
+}
+
+}  // extern "C"
+
+// ---- resnmtf_fp64_init_svd: init_mats_inner (R/update_steps.r:78-125) in double precision ----
+// The algorithm and its constants are resnmtf_init_svd's (resnmtf_hip.hip); tests/init_ref.py describes both.  A view's
+// data come in through the run's own checks and uploads (fp64_checks, fp64_upload_view); its buffer is the run's layout
+// of a one-view job whose k is the sketch width, so the products, the SpMM and the Gram find what they find in a run.
+namespace {
+const char* const F64_INIT_NAME = "fp64_init_svd";
+constexpr double kF64InitRidge = 1e-14;     // times trace(C), round 0 of CholeskyQR2 (orthonormalise of resnmtf_init_svd)
+constexpr double kF64InitRankCut = 2e-14;   // times trace(C): kRankCut of resnmtf_init_svd
+
+inline int f64_init_width(int k) { return std::min(64, 16 * ((k + 8 + 15) / 16)); }
+
+// device memory that goes with its scope
+struct F64Block {
+  F64Block() = default;
+  F64Block(const F64Block&) = delete;
+  F64Block& operator=(const F64Block&) = delete;
+  ~F64Block() { if (p) (void)hipFree(p); }
+  double* p = nullptr;
+};
+
+// where the results of one view lie in the results block, in doubles; the block holds them until every view is done
+struct F64InitOut { size_t f = 0, s = 0, g = 0, lam = 0, mu = 0, cf = 0, cg = 0; };
+// what waits on the host for the same reason
+struct F64InitHost { std::vector<double> d, u, v; };
+
+int f64_init_fail(F64Run& run, hipError_t e) { return run.fail(e, "fp64_init_svd: "); }
+
+// C = Y^T Y (width x width) on the host: the run's Gram partials, reduced in workgroup order
+int f64_init_gram(F64Run& run, const F64Layout& L1, const double* Y, int len, int width, std::vector<double>& C) {
+  const int nblk = (len + F64_GRAM_ROWS - 1) / F64_GRAM_ROWS;
+  F64GramArgs ga{};
+  ga.A[0] = Y; ga.B[0] = Y; ga.part[0] = run.buf + L1.part0; ga.len = len; ga.k = width;
+  hipLaunchKernelGGL(fp64_gram_kernel, dim3(nblk, 1), dim3(F64_THREADS), 0, run.st, ga);
+  fp64_init_reduce(run.st, run.buf + L1.part0, nblk, width * width, run.buf + L1.kk);
+  C.resize((size_t)width * width);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(C.data(), run.buf + L1.kk, C.size() * sizeof(double), hipMemcpyDeviceToHost, run.st);
+  if (e == hipSuccess) e = hipStreamSynchronize(run.st);
+  return e == hipSuccess ? RESNMTF_OK : f64_init_fail(run, e);
+}
+
+// Q = Y M (M width x width, row-major, from the host)
+int f64_init_apply_host(F64Run& run, const F64Layout& L1, const double* Y, int len, int width, const std::vector<double>& M, double* Q) {
+  double* dM = run.buf + L1.kk + (size_t)width * width;
+  hipError_t e = hipMemcpyAsync(dM, M.data(), M.size() * sizeof(double), hipMemcpyHostToDevice, run.st);
+  if (e == hipSuccess) {
+    fp64_init_apply(run.st, Y, len, width, dM, Q);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(run.st);     // (M may go out of scope)
+  return e == hipSuccess ? RESNMTF_OK : f64_init_fail(run, e);
+}
+
+// CholeskyQR2 with the ridge in round 0 and the rank cut in both: Y (in `a`) -> orthonormal columns (back in `a`, `b` is scratch)
+int f64_init_orthonormalise(F64Run& run, const F64Layout& L1, int v, double* a, double* b, int len, int width) {
+  std::vector<double> C, R, Ri;
+  for (int round = 0; round < 2; ++round) {
+    double* src = round == 0 ? a : b;
+    double* dst = round == 0 ? b : a;
+    if (int rc = f64_init_gram(run, L1, src, len, width, C)) return rc;
+    double tr = 0.0;
+    for (int i = 0; i < width; ++i) tr += C[(size_t)i * width + i];
+    if (round == 0)
+      for (int i = 0; i < width; ++i) C[(size_t)i * width + i] += kF64InitRidge * tr;
+    const int kept = cholesky_upper(C, width, kF64InitRankCut * tr, R);
+    if (kept < 0) return fp64_bad("fp64_init_svd: view " + std::to_string(v) + " holds entries that are not finite");
+    if (kept == 0) return fp64_bad("fp64_init_svd: view " + std::to_string(v) + " is all zero");
+    invert_upper(R, width, Ri);
+    if (int rc = f64_init_apply_host(run, L1, src, len, width, Ri, dst)) return rc;
+  }
+  return RESNMTF_OK;
+}
+
+// the eigenpairs of the Gram C in descending order: d = sqrt of the eigenvalues, Ms the vectors, Mn the vectors over d
+void f64_init_eigen(std::vector<double>& C, int width, std::vector<double>& d, std::vector<double>& Ms, std::vector<double>& Mn) {
+  std::vector<double> W;
+  jacobi_eigen(C, width, W);
+  std::vector<int> order(width);
+  for (int i = 0; i < width; ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](int a, int b) { return C[(size_t)a * width + a] > C[(size_t)b * width + b]; });
+  d.assign(width, 0.0); Ms.assign((size_t)width * width, 0.0); Mn.assign((size_t)width * width, 0.0);
+  for (int j = 0; j < width; ++j) {
+    const int src = order[j];
+    d[j] = std::sqrt(std::max(C[(size_t)src * width + src], 0.0));
+    for (int i = 0; i < width; ++i) {
+      Ms[(size_t)i * width + j] = W[(size_t)i * width + src];
+      Mn[(size_t)i * width + j] = d[j] > 0.0 ? W[(size_t)i * width + src] / d[j] : 0.0;
+    }
+  }
+}
+
+// one view: its data into a buffer of its own, the iteration (or the thin route), the finish into the results block
+int f64_init_view(F64Job& J, F64Run& run, int v, const resnmtf_fp64_init& in, double* res, const F64InitOut& at, F64InitHost& hs) {
+  const int n = J.j.n_rows[v], m = J.j.n_cols[v], k = J.j.k;
+  const int L = f64_init_width(k);
+  const bool thin = std::min(n, m) < L, tall = m <= n;
+  const int width = thin ? std::min(n, m) : L;
+  hipStream_t st = run.st;
+  if (J.src[v] == F64Source::DeviceSparse)
+    if (int rc = fp64_build_sparse_device_view(st, run.transient, v, J.spd->view[v], n, m, run.spdv[v], J.shapes[v], F64_INIT_NAME)) return rc;
+  resnmtf_group_job one{};
+  one.struct_size = (int)sizeof(resnmtf_group_job);
+  one.n_views = 1; one.k = width; one.n_rows[0] = n; one.n_cols[0] = m;
+  F64Source src1[RESNMTF_GROUP_MAX_VIEWS] = {};
+  F64SparseShape sh1[RESNMTF_GROUP_MAX_VIEWS];
+  src1[0] = J.src[v]; sh1[0] = J.shapes[v];
+  F64Layout L1;
+  fp64_layout(one, 1, L1, src1, sh1);
+  J.L.vw[v] = L1.vw[0];                      // (what fp64_upload_view reads)
+  const F64View& w = J.L.vw[v];
+  const size_t bytes = L1.total * sizeof(double);
+  size_t free_b = 0, total_b = 0;
+  hipError_t e = hipMemGetInfo(&free_b, &total_b);
+  if (e != hipSuccess) return f64_init_fail(run, e);
+  if (bytes > free_b) {
+    resnmtf_set_create_error("fp64_init_svd: " + std::to_string(bytes) + " bytes asked for (view " + std::to_string(v) +
+                             ": its fp64 images or sparse copies, four sketch matrices, a product slab), " + std::to_string(free_b) +
+                             " free on the device");
+    return RESNMTF_ERR_ALLOC;
+  }
+  void* p = nullptr;
+  if ((e = hipMalloc(&p, std::max<size_t>(bytes, 8))) != hipSuccess) {
+    (void)hipGetLastError();
+    resnmtf_set_create_error(std::string("fp64_init_svd: ") + hipGetErrorString(e) + " (" + std::to_string(bytes) + " bytes asked for)");
+    return e == hipErrorOutOfMemory ? RESNMTF_ERR_ALLOC : RESNMTF_ERR_HIP;
+  }
+  double* buf = run.buf = static_cast<double*>(p);
+  e = hipMemsetAsync(buf, 0, bytes, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  std::vector<double> img;
+  if (e == hipSuccess) e = fp64_upload_view(J, run, v, img);
+  if (e == hipSuccess && J.src[v] == F64Source::DeviceSparse) {
+    e = hipStreamSynchronize(st);
+    run.transient.release_all();
+  }
+  if (e != hipSuccess) return f64_init_fail(run, e);
+  img = std::vector<double>();
+
+  std::mt19937_64 gen(in.seed[v]);
+  std::vector<double> d, Ms, Mn, C;
+  const double *U = nullptr, *V = nullptr;     // n x width and m x width, column-major
+  if (thin) {
+    // the exact SVD through the Gram of the short side: Y = X (m <= n) or X^T, len x width, no sketch and no iteration
+    const int len = tall ? n : m;
+    double* Y = buf + L1.scratch;
+    double* Yl = buf + L1.scratch2;
+    if (w.sparse()) {
+      fp64_init_densify(st, reinterpret_cast<const long long*>(buf + (tall ? w.cptr : w.rptr)),
+                        reinterpret_cast<const int*>(buf + (tall ? w.cidx : w.ridx)), buf + (tall ? w.cval : w.rval), width, len, Y);
+      e = hipGetLastError();
+    } else {
+      e = hipMemcpy2DAsync(Y, (size_t)len * sizeof(double), buf + (tall ? w.x : w.xt), (tall ? w.ldn : w.ldm) * sizeof(double),
+                           (size_t)len * sizeof(double), (size_t)width, hipMemcpyDeviceToDevice, st);
+    }
+    if (e != hipSuccess) return f64_init_fail(run, e);
+    if (int rc = f64_init_gram(run, L1, Y, len, width, C)) return rc;
+    for (double x : C)
+      if (x != x) return fp64_bad("fp64_init_svd: view " + std::to_string(v) + " holds entries that are not finite");
+    f64_init_eigen(C, width, d, Ms, Mn);
+    if (int rc = f64_init_apply_host(run, L1, Y, len, width, Mn, Yl)) return rc;            // the long-side vectors
+    std::vector<double> short_cm((size_t)width * width);                                    // the short side's, column-major
+    for (int i = 0; i < width; ++i)
+      for (int j = 0; j < width; ++j) short_cm[(size_t)i + (size_t)j * width] = Ms[(size_t)i * width + j];
+    double* Ws = buf + w.f;
+    e = hipMemcpyAsync(Ws, short_cm.data(), short_cm.size() * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return f64_init_fail(run, e);
+    U = tall ? Yl : Ws;
+    V = tall ? Ws : Yl;
+  } else {
+    double* Yn = buf + w.f;
+    double* Zm = buf + w.g;
+    double* Yn2 = buf + L1.scratch;
+    double* Zm2 = buf + L1.scratch2;
+    {  // Omega: m x L standard normal, drawn row by row as resnmtf_init_svd draws it
+      std::normal_distribution<double> normal(0.0, 1.0);
+      std::vector<double> omega((size_t)m * L);
+      for (size_t j = 0; j < (size_t)m; ++j)
+        for (int c = 0; c < L; ++c) omega[j + (size_t)c * m] = normal(gen);
+      e = hipMemcpyAsync(Zm, omega.data(), omega.size() * sizeof(double), hipMemcpyHostToDevice, st);
+      if (e == hipSuccess) e = hipStreamSynchronize(st);
+      if (e != hipSuccess) return f64_init_fail(run, e);
+    }
+    auto product = [&](bool is_xg) {             // Y = X Z into Yn, or Z = X^T Q into Zm
+      const double* O = is_xg ? Zm : Yn;
+      const int contr = is_xg ? m : n, lines = is_xg ? n : m;
+      const size_t ld = is_xg ? w.ldn : w.ldm;
+      int splits;
+      if (w.sparse()) {
+        const F64SparsePlan& sp = is_xg ? w.sxg : w.sxtf;
+        fp64_spmm(st, L, sp, reinterpret_cast<const long long*>(buf + (is_xg ? w.rptr : w.cptr)),
+                  reinterpret_cast<const int*>(buf + (is_xg ? w.ridx : w.cidx)), buf + (is_xg ? w.rval : w.cval), O, contr, L,
+                  buf + L1.ot, lines, ld, buf + L1.slab);
+        splits = sp.splits;
+      } else {
+        const F64ProductPlan& pp = is_xg ? w.xg : w.xtf;
+        fp64_product(st, L, pp, buf + (is_xg ? w.x : w.xt), ld, O, contr, L, is_xg ? w.mpad : w.npad, buf + L1.slab);
+        splits = pp.splits;
+      }
+      fp64_init_slab_sum(st, L, buf + L1.slab, splits, ld, lines, is_xg ? Yn : Zm);
+      return hipGetLastError();
+    };
+    const int n_power = in.n_power < 1 ? 3 : in.n_power;
+    for (int it = 0; it < n_power; ++it) {
+      if ((e = product(true)) != hipSuccess) return f64_init_fail(run, e);
+      if (int rc = f64_init_orthonormalise(run, L1, v, Yn, Yn2, n, L)) return rc;
+      if ((e = product(false)) != hipSuccess) return f64_init_fail(run, e);
+      if (it + 1 < n_power)
+        if (int rc = f64_init_orthonormalise(run, L1, v, Zm, Zm2, m, L)) return rc;
+    }
+    // Z = X^T Q = V Sigma Ut^T  ->  Z^T Z = Ut Sigma^2 Ut^T;  U = Q Ut,  V = Z Ut Sigma^-1
+    if (int rc = f64_init_gram(run, L1, Zm, m, L, C)) return rc;
+    f64_init_eigen(C, L, d, Ms, Mn);
+    if (int rc = f64_init_apply_host(run, L1, Yn, n, L, Ms, Yn2)) return rc;
+    if (int rc = f64_init_apply_host(run, L1, Zm, m, L, Mn, Zm2)) return rc;
+    U = Yn2; V = Zm2;
+  }
+
+  // R/update_steps.r:93-115 on the k leading triplets; the noise in resnmtf_init_svd's draw order (column by column)
+  std::vector<double> base((size_t)k * k);
+  std::normal_distribution<double> noise(0.0, std::sqrt(in.sigma));                 // mvrnorm(k, 0, sigma I), :96-99
+  for (int j = 0; j < k; ++j)
+    for (int i = 0; i < k; ++i) {
+      double sv = (i == j ? std::fabs(d[j]) : 0.0);                                 // :95
+      if (in.sigma > 0.0) sv += std::fabs(noise(gen));
+      base[(size_t)j * k + i] = sv;
+    }
+  double* dbase = buf + L1.kk + 2 * (size_t)width * width;
+  e = hipMemcpyAsync(dbase, base.data(), base.size() * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    F64InitFinishArgs fa{};
+    fa.U = U; fa.V = V; fa.n = n; fa.m = m;
+    fa.F0 = res + at.f; fa.G0 = res + at.g; fa.cf = res + at.cf; fa.cg = res + at.cg; fa.lam = res + at.lam; fa.mu = res + at.mu;
+    fp64_init_finish(st, fa, k, dbase, res + at.s);
+    e = hipGetLastError();
+  }
+  hs.d = d;
+  if (in.basis_u[v]) {                       // the signed basis, asked for: the k leading columns
+    hs.u.resize((size_t)n * k); hs.v.resize((size_t)m * k);
+    if (e == hipSuccess) e = hipMemcpyAsync(hs.u.data(), U, hs.u.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(hs.v.data(), V, hs.v.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return f64_init_fail(run, e);
+  (void)hipFree(run.buf);                    // the next view's buffer takes its place
+  run.buf = nullptr;
+  return RESNMTF_OK;
+}
+
+// the refusals of the outputs that need no device: all five of every view, none beyond; a basis whole or not at all
+std::string f64_init_check_outputs(const resnmtf_group_job& j, const resnmtf_fp64_init& in) {
+  auto view = [](int v) { return "view " + std::to_string(v) + ": "; };
+  for (int v = 0; v < RESNMTF_GROUP_MAX_VIEWS; ++v) {
+    const int five = (in.f0[v] ? 1 : 0) + (in.s0[v] ? 1 : 0) + (in.g0[v] ? 1 : 0) + (in.lambda0[v] ? 1 : 0) + (in.mu0[v] ? 1 : 0);
+    const int four = (in.basis_u[v] ? 1 : 0) + (in.basis_v[v] ? 1 : 0) + (in.basis_d[v] ? 1 : 0) + (in.basis_n_d[v] ? 1 : 0);
+    if (v >= j.n_views) {
+      if (five || four || in.singular_values[v]) return view(v) + "an output is given beyond n_views";
+      continue;
+    }
+    if (five != 5) return view(v) + "an output is NULL: f0, s0, g0, lambda0 and mu0 of every view";
+    if (four != 0 && four != 4) return view(v) + "the basis is given in part: basis_u, basis_v, basis_d and basis_n_d, or none of them";
+  }
+  return "";
+}
+// ... and the one that asks the runtime: device outputs are device memory of device_id and hold their element counts
+std::string f64_init_check_output_pointers(int device_id, const resnmtf_group_job& j, const resnmtf_fp64_init& in) {
+  auto view = [](int v) { return "view " + std::to_string(v) + ": "; };
+  if (!in.outputs_on_device) return "";
+  for (int v = 0; v < j.n_views; ++v) {
+    const size_t n = (size_t)j.n_rows[v], m = (size_t)j.n_cols[v], k = (size_t)j.k;
+    struct Out { const char* name; const double* p; size_t count; };
+    const Out outs[5] = {{"f0", in.f0[v], n * k}, {"s0", in.s0[v], k * k}, {"g0", in.g0[v], m * k}, {"lambda0", in.lambda0[v], k}, {"mu0", in.mu0[v], k}};
+    for (const Out& o : outs) {
+      bool beyond = false;
+      if (!fp64_on_device(device_id, o.p, o.count * sizeof(double), beyond))
+        return view(v) + "init->" + o.name + (beyond ? " reaches beyond its allocation" : " is not device memory of device " + std::to_string(device_id));
+    }
+  }
+  return "";
+}
+}  // namespace
+
+extern "C" {
+
+int resnmtf_fp64_init_svd(int device_id, const resnmtf_group_job* job, const resnmtf_fp64_sparse* sp, const resnmtf_fp64_device* dev,
+                          const resnmtf_fp64_sparse_device* spd, const resnmtf_fp64_init* init) {
+  if (sp && sp->struct_size != (int)sizeof(resnmtf_fp64_sparse)) return fp64_bad("resnmtf_fp64_sparse struct_size mismatch");
+  if (spd && spd->struct_size != (int)sizeof(resnmtf_fp64_sparse_device)) return fp64_bad("resnmtf_fp64_sparse_device struct_size mismatch");
+  if (dev && dev->struct_size != (int)sizeof(resnmtf_fp64_device)) return fp64_bad("resnmtf_fp64_device struct_size mismatch");
+  if (!job) return fp64_bad("job is NULL");
+  if (!init) return fp64_bad("init is NULL");
+  if (init->struct_size != (int)sizeof(resnmtf_fp64_init)) return fp64_bad("resnmtf_fp64_init struct_size mismatch");
+  if (job->struct_size != (int)sizeof(resnmtf_group_job)) return fp64_bad("resnmtf_group_job struct_size mismatch");
+  if (!std::isfinite(init->sigma) || init->sigma < 0.0) return fp64_bad("sigma must be finite and >= 0");
+  // what is read of the job and of dev, and nothing else: the shapes, k and where the views are
+  resnmtf_group_job jj{};
+  double unused_err = 0.0;
+  int unused_iters = 0;
+  jj.struct_size = (int)sizeof(resnmtf_group_job);
+  jj.n_views = job->n_views; jj.k = job->k; jj.n_iters = 1;
+  std::memcpy(jj.n_rows, job->n_rows, sizeof(jj.n_rows));
+  std::memcpy(jj.n_cols, job->n_cols, sizeof(jj.n_cols));
+  std::memcpy(jj.x, job->x, sizeof(jj.x));
+  jj.all_error = &unused_err; jj.err_capacity = 1; jj.iters_done = &unused_iters;
+  resnmtf_fp64_device dd{};
+  if (dev) {
+    dd.struct_size = (int)sizeof(resnmtf_fp64_device);
+    dd.stream = dev->stream;
+    std::memcpy(dd.x, dev->x, sizeof(dd.x));
+  }
+  F64Job J{device_id, jj, sp, dev ? &dd : nullptr, spd, 0.0, 1, {}, {}, {}, {}};
+  J.start_only = true;
+  F64Block results;                         // (before the run: freed after the run's stream has been waited for)
+  F64Run run;
+  if (fp64_shapes_ok(jj)) {                 // (else the job's own checks refuse it below)
+    const std::string why = f64_init_check_outputs(jj, *init);
+    if (!why.empty()) return fp64_bad(why);
+  }
+  int rc = fp64_checks(J);
+  if (rc != RESNMTF_OK) return rc;
+  const std::string why = f64_init_check_output_pointers(device_id, jj, *init);
+  if (!why.empty()) return fp64_bad(why);
+  if ((rc = fp64_open_stream(J, run)) != RESNMTF_OK) return rc;
+
+  const int V = jj.n_views, k = jj.k;
+  F64InitOut at[RESNMTF_GROUP_MAX_VIEWS];
+  size_t total = 0;
+  for (int v = 0; v < V; ++v) {
+    const size_t n = (size_t)jj.n_rows[v], m = (size_t)jj.n_cols[v], sk = (size_t)k;
+    at[v].f = total; total += n * sk;
+    at[v].s = total; total += sk * sk;
+    at[v].g = total; total += m * sk;
+    at[v].lam = total; total += sk;
+    at[v].mu = total; total += sk;
+    at[v].cf = total; total += sk;
+    at[v].cg = total; total += sk;
+  }
+  size_t free_b = 0, total_b = 0;
+  hipError_t e = hipMemGetInfo(&free_b, &total_b);
+  if (e != hipSuccess) return f64_init_fail(run, e);
+  if (total * sizeof(double) > free_b) {
+    resnmtf_set_create_error("fp64_init_svd: " + std::to_string(total * sizeof(double)) + " bytes asked for (the initial factors of every view), " +
+                             std::to_string(free_b) + " free on the device");
+    return RESNMTF_ERR_ALLOC;
+  }
+  void* p = nullptr;
+  if ((e = hipMalloc(&p, total * sizeof(double))) != hipSuccess) {
+    (void)hipGetLastError();
+    resnmtf_set_create_error(std::string("fp64_init_svd: ") + hipGetErrorString(e) + " (" + std::to_string(total * sizeof(double)) + " bytes asked for)");
+    return e == hipErrorOutOfMemory ? RESNMTF_ERR_ALLOC : RESNMTF_ERR_HIP;
+  }
+  results.p = static_cast<double*>(p);
+
+  std::vector<F64InitHost> hs((size_t)V);
+  for (int v = 0; v < V; ++v)
+    if ((rc = f64_init_view(J, run, v, *init, results.p, at[v], hs[(size_t)v])) != RESNMTF_OK) return rc;
+
+  // every view is done: the outputs, device to device or through one host copy
+  const resnmtf_fp64_init& in = *init;
+  std::vector<double> host;
+  if (in.outputs_on_device) {
+    for (int v = 0; v < V && e == hipSuccess; ++v) {
+      const size_t n = (size_t)jj.n_rows[v], m = (size_t)jj.n_cols[v], sk = (size_t)k;
+      struct Piece { double* to; size_t from, count; };
+      const Piece pieces[5] = {{in.f0[v], at[v].f, n * sk}, {in.s0[v], at[v].s, sk * sk}, {in.g0[v], at[v].g, m * sk},
+                               {in.lambda0[v], at[v].lam, sk}, {in.mu0[v], at[v].mu, sk}};
+      for (int q = 0; q < 5 && e == hipSuccess; ++q)
+        e = hipMemcpyAsync(pieces[q].to, results.p + pieces[q].from, pieces[q].count * sizeof(double), hipMemcpyDeviceToDevice, run.st);
+    }
+  } else {
+    host.resize(total);
+    e = hipMemcpyAsync(host.data(), results.p, total * sizeof(double), hipMemcpyDeviceToHost, run.st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(run.st);
+  if (e != hipSuccess) return f64_init_fail(run, e);
+  for (int v = 0; v < V; ++v) {
+    const size_t n = (size_t)jj.n_rows[v], m = (size_t)jj.n_cols[v], sk = (size_t)k;
+    if (!in.outputs_on_device) {
+      std::memcpy(in.f0[v], &host[at[v].f], n * sk * sizeof(double));
+      std::memcpy(in.s0[v], &host[at[v].s], sk * sk * sizeof(double));
+      std::memcpy(in.g0[v], &host[at[v].g], m * sk * sizeof(double));
+      std::memcpy(in.lambda0[v], &host[at[v].lam], sk * sizeof(double));
+      std::memcpy(in.mu0[v], &host[at[v].mu], sk * sizeof(double));
+    }
+    const F64InitHost& h = hs[(size_t)v];
+    if (in.singular_values[v]) std::memcpy(in.singular_values[v], h.d.data(), sk * sizeof(double));
+    if (in.basis_u[v]) {
+      std::memcpy(in.basis_u[v], h.u.data(), h.u.size() * sizeof(double));
+      std::memcpy(in.basis_v[v], h.v.data(), h.v.size() * sizeof(double));
+      std::memcpy(in.basis_d[v], h.d.data(), h.d.size() * sizeof(double));
+      *in.basis_n_d[v] = (int)h.d.size();
+    }
+  }
   return RESNMTF_OK;
 }
 

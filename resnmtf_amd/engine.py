@@ -181,6 +181,42 @@ def _fp64_device_outputs(dev, j, out: dict, device_id: int, return_state: bool):
                 getattr(dev, (prefix + key) if prefix else key + "_out")[v] = t.data_ptr()
 
 
+def _job_views(j, data, q: int, device_id: int, sp, dev, spd) -> list:
+    """The views of problem ``q`` by the route each takes (``_view_route``), after the checks that need no library call;
+    ``j`` (a ``resnmtf_group_job``) gets its struct size.  What ``fp64_run`` and ``fp64_init_svd`` share."""
+    j.struct_size = C.sizeof(_lib.GroupJob)
+    views = [_view_route(x, f"problem {q}, view {v}", device_id, dev, spd) for v, x in enumerate(data)]
+    if sp is None and any(route == _HOST_CSC for route, _ in views):
+        raise ValueError(f"problem {q}: a sparse view (scipy.sparse) is taken by fp64_run alone")
+    if len(views) > _lib.GROUP_MAX_VIEWS:
+        raise ValueError(f"problem {q}: at most {_lib.GROUP_MAX_VIEWS} views")
+    if any(x.ndim != 2 for _, x in views):
+        raise ValueError(f"problem {q}: every view must be a matrix")
+    return views
+
+
+def _fill_job_view(j, v: int, route: str, x, q: int, device_id: int, keep: list, sp, dev, spd) -> tuple:
+    """View ``v`` of problem ``q`` into the one of ``j`` / ``sp`` / ``dev`` / ``spd`` its route names; returns ``(n, m)``."""
+    n, m = (int(d) for d in x.shape)
+    j.n_rows[v], j.n_cols[v] = n, m
+    if route == _HOST_DENSE:
+        keep.append(x)
+        j.x[v] = _dp(x)
+    elif route == _HOST_CSC:              # the CSC arrays go into sp
+        csc = [np.ascontiguousarray(x.indptr, dtype=np.int64), np.ascontiguousarray(x.indices, dtype=np.int32),
+               np.ascontiguousarray(x.data, dtype=np.float64)]
+        sp.view[v].col_ptr = csc[0].ctypes.data_as(C.POINTER(C.c_longlong))
+        sp.view[v].row_idx, sp.view[v].values = _ip(csc[1]), _dp(csc[2])
+        keep.extend(csc)
+    elif route == _DEVICE_DENSE:          # dev.x[v] describes the tensor as it lies
+        t = x.detach()
+        keep.append(t)
+        dev.x[v] = _device_matrix(t, (n, m), device_id, f"problem {q}, view {v}: data")
+    else:                                 # its index and value arrays go into spd
+        _fill_fp64_sparse_device(spd, v, x, q, keep)
+    return n, m
+
+
 def _fill_group_job(j, p, q: int, max_iters: int, keep: list, sp=None, dev=None, device_id: int = 0,
                     device_out: bool = False, spd=None) -> dict:
     """Fill one ``resnmtf_group_job`` (``j``) from the problem dict ``p`` (problem ``q`` of its call; the layout
@@ -193,15 +229,8 @@ def _fill_group_job(j, p, q: int, max_iters: int, keep: list, sp=None, dev=None,
     output pointers stay NULL and the returned lists empty (``_fp64_device_outputs`` fills them).  ``spd`` (``fp64_run``
     alone): the ``resnmtf_fp64_sparse_device`` that receives every view that is a sparse tensor on ``cuda:device_id`` (or
     a ``SparseDeviceView`` of one), checked by ``device_views.check_sparse_tensor``."""
-    j.struct_size = C.sizeof(_lib.GroupJob)
-    views = [_view_route(x, f"problem {q}, view {v}", device_id, dev, spd) for v, x in enumerate(p["data"])]
-    if sp is None and any(route == _HOST_CSC for route, _ in views):
-        raise ValueError(f"problem {q}: a sparse view (scipy.sparse) is taken by fp64_run alone")
+    views = _job_views(j, p["data"], q, device_id, sp, dev, spd)
     V, k = len(views), int(p["k"])
-    if V > _lib.GROUP_MAX_VIEWS:
-        raise ValueError(f"problem {q}: at most {_lib.GROUP_MAX_VIEWS} views")
-    if any(x.ndim != 2 for _, x in views):
-        raise ValueError(f"problem {q}: every view must be a matrix")
     for key in ("init_f", "init_s", "init_g", "init_lam", "init_mu"):
         if p.get(key) is not None and len(p[key]) != V:
             raise ValueError(f"problem {q}: {key} must hold one entry per view")
@@ -211,23 +240,7 @@ def _fill_group_job(j, p, q: int, max_iters: int, keep: list, sp=None, dev=None,
     cap = max(1, min(int(n_iters), int(max_iters)) if n_iters else int(max_iters))
     out = {"f": [], "s": [], "g": [], "lambda": [], "mu": [], "all_error": np.empty(cap), "iters": np.zeros(1, np.int32)}
     for v, (route, x) in enumerate(views):
-        n, m = (int(d) for d in x.shape)
-        j.n_rows[v], j.n_cols[v] = n, m
-        if route == _HOST_DENSE:
-            keep.append(x)
-            j.x[v] = _dp(x)
-        elif route == _HOST_CSC:              # the CSC arrays go into sp
-            csc = [np.ascontiguousarray(x.indptr, dtype=np.int64), np.ascontiguousarray(x.indices, dtype=np.int32),
-                   np.ascontiguousarray(x.data, dtype=np.float64)]
-            sp.view[v].col_ptr = csc[0].ctypes.data_as(C.POINTER(C.c_longlong))
-            sp.view[v].row_idx, sp.view[v].values = _ip(csc[1]), _dp(csc[2])
-            keep.extend(csc)
-        elif route == _DEVICE_DENSE:          # dev.x[v] describes the tensor as it lies
-            t = x.detach()
-            keep.append(t)
-            dev.x[v] = _device_matrix(t, (n, m), device_id, f"problem {q}, view {v}: data")
-        else:                                 # its index and value arrays go into spd
-            _fill_fp64_sparse_device(spd, v, x, q, keep)
+        n, m = _fill_job_view(j, v, route, x, q, device_id, keep, sp, dev, spd)
         factors_there = dev is not None and _fill_fp64_device_factors(dev, v, n, m, p, k, q, device_id, keep)
         if not factors_there:
             try:                              # (the library reads n k, k k and m k doubles through these pointers)
@@ -374,6 +387,75 @@ def fp64_run(problem, tol: float = 1.0e-6, max_iters: int = 100000, device_id: i
     if rc != _lib.OK:
         raise ResnmtfError(rc, (lib.resnmtf_last_error(None) or b"").decode())
     return _group_result(out)
+
+
+def fp64_init_svd(views, k: int, seed=0, sigma: float = 0.05, n_power: int = 0, return_basis: bool = False,
+                  output: str = "numpy", device_id: int = 0) -> list:
+    """``init_mats_inner`` (``R/update_steps.r:78-125``) of every view in double precision, without an engine
+    (``resnmtf_fp64_init_svd``): the algorithm of ``Engine.init_svd`` -- the same sketch width,
+    rounds, ridge, rank cut and draw order, so the same seed is the same sketch -- on the fp64 values of the views, where
+    the engine's starts from their f32 images.
+
+    ``views`` are what ``fp64_run`` takes as ``problem["data"]``: fp64 arrays, ``scipy.sparse`` matrices (taken as
+    pre-processed), dense and sparse ``torch`` tensors on ``cuda:device_id``; a dense view goes through the fp64 images and
+    products of the run, a sparse one through its CSC + CSR copies and the fp64 SpMM.  ``k``: one k for all views.
+    ``seed``: an integer (view v draws from ``seed + v``, as ``res_nmtf_inner`` seeds the engine) or one seed per view.
+    Returns per view ``(F0, S0, G0, lambda0, mu0)``; with ``return_basis=True`` each tuple goes on with ``(d, U, V, d_all)``
+    as ``Engine.init_svd(return_basis=True)`` returns them.  ``output="torch"``: the five come back as fp64 tensors on the
+    device (F0, S0, G0 column-major) and nothing of size n or m crosses the bus; both outputs hold the same bits.  Bad
+    input is refused before any device work (``ResnmtfError``)."""
+    _device_views.check_output(output)
+    lib = _lib.load()
+    views = list(views)
+    job, init, keep = _lib.GroupJob(), _lib.Fp64Init(), []
+    sp = _lib.Fp64Sparse() if any(_sparse.is_sparse(x) for x in views) else None
+    spd = _lib.Fp64SparseDevice() if any(_device_views.is_sparse_device_view(x) for x in views) else None
+    dev = _lib.Fp64Device() if spd is not None or any(_device_views.is_device_tensor(x) for x in views) else None
+    for s in (sp, dev, spd, init):
+        if s is not None:
+            s.struct_size = C.sizeof(s)
+    routed = _job_views(job, views, 0, device_id, sp, dev, spd)
+    V, k = len(routed), int(k)
+    job.n_views, job.k = V, k
+    seeds = [int(seed) + v for v in range(V)] if np.ndim(seed) == 0 else [int(s) for s in seed]
+    if len(seeds) != V:
+        raise ValueError("seed must be one integer or one seed per view")
+    init.sigma, init.n_power, init.outputs_on_device = float(sigma), int(n_power), int(output == "torch")
+    out, extra = [], []
+    for v, (route, x) in enumerate(routed):
+        n, m = _fill_job_view(job, v, route, x, 0, device_id, keep, sp, dev, spd)
+        init.seed[v] = seeds[v] & 0xFFFFFFFFFFFFFFFF
+        shapes = ((n, k), (k, k), (m, k), (k,), (k,))
+        if output == "torch":
+            import torch                # (lazily: nothing else in this module needs it)
+            where = torch.device("cuda", int(device_id))
+            five = [torch.empty(s[::-1], dtype=torch.float64, device=where).T if len(s) == 2
+                    else torch.empty(s, dtype=torch.float64, device=where) for s in shapes]
+            addr = [t.data_ptr() for t in five]
+        else:
+            five = [np.zeros(s, dtype=np.float64, order="F") for s in shapes]
+            addr = [a.ctypes.data for a in five]
+        for name, a in zip(("f0", "s0", "g0", "lambda0", "mu0"), addr):
+            getattr(init, name)[v] = a
+        out.append(tuple(five))
+        if return_basis:
+            d, u, w = np.zeros(k), np.zeros((n, k), order="F"), np.zeros((m, k), order="F")
+            d_all, n_d = np.zeros(64), np.zeros(1, np.int32)
+            init.singular_values[v], init.basis_u[v], init.basis_v[v], init.basis_d[v] = _dp(d), _dp(u), _dp(w), _dp(d_all)
+            init.basis_n_d[v] = _ip(n_d)
+            extra.append((d, u, w, d_all, n_d))
+    if dev is not None:
+        import torch
+        dev.stream = torch.cuda.current_stream(torch.device("cuda", int(device_id))).cuda_stream
+        if spd is not None:
+            spd.stream = dev.stream
+    rc = lib.resnmtf_fp64_init_svd(int(device_id), C.byref(job), None if sp is None else C.byref(sp),
+                                   None if dev is None else C.byref(dev), None if spd is None else C.byref(spd), C.byref(init))
+    if rc != _lib.OK:
+        raise ResnmtfError(rc, (lib.resnmtf_last_error(None) or b"").decode())
+    if return_basis:
+        out = [five + (d, u, w, d_all[:int(n_d[0])].copy()) for five, (d, u, w, d_all, n_d) in zip(out, extra)]
+    return out
 
 
 def fp64_bisil(x, rc, cc, distance: str = "euclidean", device_id: int = 0):

@@ -202,7 +202,7 @@ def _draw_shuffle_fp64(x, v: int, shuffle_seed: int, device_id: int = 0, shuffle
 
 
 def shuffled_fits_fp64(data, k: int, num_repeats: int, seed: int = 0, max_iters: int = 100000, device_id: int = 0, *,
-                       shuffle=None, fit=None, keep=None, shuffle_sparse=None) -> list:
+                       shuffle=None, fit=None, keep=None, shuffle_sparse=None, fp64_init: bool = False) -> list:
     """``obtain_shuffled_f`` (``R/obtain_bicl.r:31-42``) in double precision (DESIGN.md sections 27 and 30): for every
     repeat r, each view of ``data`` (host arrays or dense tensors on ``cuda:device_id``, as the fp64 run received them; a
     sparse view as its canonical ``scipy.sparse`` matrix or its ``SparseDeviceView``) drawn by ``_draw_shuffle_fp64`` with
@@ -210,7 +210,8 @@ def shuffled_fits_fp64(data, k: int, num_repeats: int, seed: int = 0, max_iters:
     ``res_nmtf_inner(precision="fp64", fp64_device=True, output="torch", n_iters=None, spurious=False, seed=seed + 1000 +
     r)`` -- with a sparse draw among them also ``fp64_sparse_device=True``: the draw is factorised as the sparse device
     view it is --: no restrictions, uncoupled, from the device SVD start the f32 shuffle engine takes for the same draw, to
-    convergence (``max_iters`` guards it).  Returns the ``num_repeats`` lists of normalised F's per view as NumPy arrays --
+    convergence (``max_iters`` guards it); with ``fp64_init`` from ``engine.fp64_init_svd`` of the
+    draw under the same seed, and no engine is built.  Returns the ``num_repeats`` lists of normalised F's per view as NumPy arrays --
     ``check_biclusters``' ``shuffled_f``; the draws of one repeat are the only shuffled copies alive, one per view.
     Test hooks: ``shuffle`` replaces ``engine.fp64_shuffle``, ``shuffle_sparse`` ``engine.fp64_shuffle_sparse``,
     ``fit(tensors, k, seed, max_iters, device_id)`` the factorisation (it returns the F's), ``keep(r, tensors, attempts)``
@@ -221,6 +222,8 @@ def shuffled_fits_fp64(data, k: int, num_repeats: int, seed: int = 0, max_iters:
         def fit(tensors, k, seed, max_iters, device_id):
             from .api import res_nmtf_inner          # (lazy: api imports this module at its top)
             more = {"fp64_sparse_device": True} if any(device_views.is_sparse_tensor(t) for t in tensors) else {}
+            if fp64_init:
+                more["fp64_init"] = True
             res = res_nmtf_inner(tensors, None, None, None, None, None, [k] * n_v, None, None, None, None, spurious=False,
                                  seed=seed, max_iters=max_iters, device_id=device_id, precision="fp64", fp64_device=True,
                                  output="torch", **more)

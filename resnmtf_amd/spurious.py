@@ -129,7 +129,7 @@ def _check_factors(mats, what):
 def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int] = None, device_id: int = 0,
                      group=None, max_iters: int = 100000, shuffled_f=None, jsd: Optional[Callable] = None,
                      grouped: bool = False, shuffle_sparse: bool = False, precision: str = "f32",
-                     fp64_shuffle_sparse: bool = False) -> dict:
+                     fp64_shuffle_sparse: bool = False, fp64_init: bool = False) -> dict:
     """``check_biclusters`` (``R/obtain_bicl.r:113-133``) with ``get_thresholds`` (``:80-102``): returns
     ``{"score": n_views x K, "avg_threshold": n_views, "max_threshold": n_views}``.
 
@@ -151,13 +151,15 @@ def check_biclusters(data, output_f, num_repeats: int = 5, *, seed: Optional[int
     thresholds and the result are the same.  Sparse views, ``grouped`` and ``group`` are refused with it.
     ``fp64_shuffle_sparse=True`` (opt-in; read only with ``precision="fp64"``): a sparse view -- a
     ``scipy.sparse`` matrix, taken as its canonical CSC, or a sparse tensor on ``cuda:device_id`` read where it lies -- is
-    drawn by ``engine.fp64_shuffle_sparse`` and its draws are factorised as sparse device views; dense views as before."""
+    drawn by ``engine.fp64_shuffle_sparse`` and its draws are factorised as sparse device views; dense views as before.
+    ``fp64_init=True`` (opt-in; read only with ``precision="fp64"``): every shuffled fit starts from
+    ``engine.fp64_init_svd`` of its draws instead of a short-lived f32 engine, with the same seeds."""
     if precision not in ("f32", "fp64"):
         raise ValueError(f"precision must be 'f32' or 'fp64', got {precision!r}")
     if precision == "fp64":
         return _check_biclusters_fp64(data, output_f, num_repeats, seed=seed, device_id=device_id, group=group,
                                       max_iters=max_iters, shuffled_f=shuffled_f, jsd=jsd, grouped=grouped,
-                                      shuffle_sparse=fp64_shuffle_sparse)
+                                      shuffle_sparse=fp64_shuffle_sparse, fp64_init=fp64_init)
     R = check_num_repeats(num_repeats)
     views = list(data) if not (isinstance(data, np.ndarray) and data.ndim == 2) and not sparse.is_sparse(data) else [data]
     if any(sparse.is_sparse(d) for d in views):
@@ -204,10 +206,11 @@ def _checked_output_f(shapes, output_f, R: int):
 
 
 def _check_biclusters_fp64(data, output_f, num_repeats, *, seed, device_id, group, max_iters, shuffled_f, jsd, grouped,
-                           shuffle_sparse: bool = False) -> dict:
+                           shuffle_sparse: bool = False, fp64_init: bool = False) -> dict:
     """``check_biclusters(precision="fp64")``: the views as the fp64 run received them, the shuffled F's from
     ``problem.shuffled_fits_fp64``, then the scoring every route shares.  ``shuffle_sparse``
-    (``fp64_shuffle_sparse``): sparse views are admitted, a ``scipy.sparse`` one as its canonical CSC."""
+    (``fp64_shuffle_sparse``): sparse views are admitted, a ``scipy.sparse`` one as its canonical CSC.  ``fp64_init``: passed
+    on to the shuffled fits, and only when it is set."""
     R = check_num_repeats(num_repeats)
     if grouped or group is not None:
         raise ValueError('precision="fp64": the shuffled fits run through resnmtf_fp64_run, one after another; grouped and '
@@ -223,7 +226,9 @@ def _check_biclusters_fp64(data, output_f, num_repeats, *, seed, device_id, grou
         raise ValueError('precision="fp64": the views are taken as pre-processed; a RawDeviceView is not')
     output_f, K = _checked_output_f([tuple(d.shape) for d in views], output_f, R)
     if shuffled_f is None:
-        shuffled_f = shuffled_fits_fp64(views, K, R, 0 if seed is None else int(seed), max_iters=max_iters, device_id=device_id)
+        flag = {"fp64_init": True} if fp64_init else {}
+        shuffled_f = shuffled_fits_fp64(views, K, R, 0 if seed is None else int(seed), max_iters=max_iters, device_id=device_id,
+                                        **flag)
     return _score_against_shuffles(output_f, shuffled_f, R, jsd, device_id)
 
 
