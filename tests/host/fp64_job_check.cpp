@@ -1,6 +1,6 @@
 // Stand-alone host check of csrc/resnmtf_fp64_job.h: the layout of the fp64 job's one device
-// buffer, the CSC check, the CSR build and the two struct checks that need no device.  No HIP call; built with a plain
-// C++17 compiler by tests/test_fp64_job_check.py.  Prints every offset of every job (the printout of two builds is
+// buffer, the CSC check, the CSR build, the two struct checks that need no device and the restriction column sums.  No
+// HIP call; built with a plain C++17 compiler by tests/test_fp64_job_check_host.py.  Prints every offset of every job (the printout of two builds is
 // compared when the layout code moves) and exits non-zero at the first condition that does not hold.
 #include <cstdio>
 #include <cstdlib>
@@ -429,6 +429,26 @@ void check_sparse_device_struct() {
   d.view[0] = good; d.view[0].values = nullptr;
   CHECK(fp64_check_sparse_device_struct(j, nullptr, nullptr, d) == "view 0: spd->view: ptr_or_rows / idx_or_cols / values is NULL");
 }
+// ---- fp64_col_sum / fp64_all_zero: the restriction column sums that decide the branch and scale the denominator ----
+// R[w, v] = 1 / (3 + 6 w + 10 v) (odd denominators: no entry is dyadic), column-major V x V, for V = 1 .. 8: one correctly
+// rounded division per entry, so tests/test_fp64_job_check_host.py rebuilds the same doubles and requires every printed
+// sum to be numpy's, bit for bit (sequential below 8 entries, the 8-accumulator pairwise form at 8).
+void check_col_sums() {
+  for (int V = 1; V <= RESNMTF_GROUP_MAX_VIEWS; ++V) {
+    std::vector<double> r((size_t)V * V);
+    for (int v = 0; v < V; ++v)
+      for (int w = 0; w < V; ++w) r[(size_t)w + (size_t)v * V] = 1.0 / (double)(3 + 6 * w + 10 * v);
+    for (int v = 0; v < V; ++v) std::printf("colsum V %d v %d: %a\n", V, v, fp64_col_sum(r.data(), V, v));
+    CHECK(!fp64_all_zero(r.data(), V));
+    std::vector<double> z((size_t)V * V, 0.0);
+    CHECK(fp64_all_zero(z.data(), V));
+    for (int v = 0; v < V; ++v) CHECK(fp64_col_sum(z.data(), V, v) == 0.0);
+    z[(size_t)V * V - 1] = 0x1p-1074;                   // the last entry alone, the smallest double there is
+    CHECK(!fp64_all_zero(z.data(), V) && fp64_col_sum(z.data(), V, V - 1) == 0x1p-1074);
+    if (V > 1) CHECK(fp64_col_sum(z.data(), V, 0) == 0.0);
+    CHECK(fp64_all_zero(nullptr, V) && fp64_col_sum(nullptr, V, V - 1) == 0.0);
+  }
+}
 }  // namespace
 
 int main() {
@@ -436,6 +456,7 @@ int main() {
   check_csc();
   check_device_struct();
   check_sparse_device_struct();
+  check_col_sums();
   std::printf("fp64_job_check: %d jobs, all checks passed\n", jobs);
   return 0;
 }
